@@ -15,12 +15,20 @@ steps' frames over the wall time between the two synchronisation points.  `roofl
 three steps strictly back to back just before the timed region (`single_batch`; what a rocprofv3 profile of `bench.py --in-flight 1`
 shows, profiles/*_kernel_stats_in_flight_1.txt), pipelined = the same events inside the timed region, where kernels share the GPU.
 
-The same JSON line carries (rank 0, N = 1): `extra.level13` = BASELINE configs[2] (Syllable Features on the same batch),
-`extra.streaming` = configs[4] (512 x 48 kHz streams, one hipGraph step per 25 ms frame, p50 / p99 timed inside libwsa),
+A plain run does only what the headline needs: set-up (the planned batches, then SETTLE_S seconds of pipelined steps so that the GPU
+has left its idle clocks), W warm-up steps, ONE timed region of exactly K steps (`ms_per_step` = its wall time / K), the outputs
+of its last step when --dump-outputs DIR is given, and the result line.
+With --full the line also carries the figures that take runs of their own (rank 0): the timed region repeated --repeats times (default 9,
+median reported), `single_batch`, `roofline`, `issue_bound`, and at N = 1 `extra.level13` = BASELINE configs[2] (Syllable Features on the
+same batch), `extra.streaming` = configs[4] (512 x 48 kHz streams, one hipGraph step per 25 ms frame, p50 / p99 timed inside libwsa),
 `extra.offline_48k` = the headline batch at the reference's offline context rate (48 kHz, 3072-point FFT),
 `cpu_baseline` with `cpu_parity` (the CPU rows of the sampled clips compared with the GPU's rows of the same clips).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--level 5|13] [--clips C] [--no-cpu-baseline] [--no-extra]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--level 5|13] [--clips C] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-extra]]
+--dump-outputs DIR writes what the last timed step computed, as a caller of the batch path receives it (rank 0: its rows, or at N > 1 the
+rows gathered from every rank), as DIR/<name>.npy in float64: meta, feat, segments, row_off, seg_off (at N > 1: meta, feat).  The inputs
+are seeded, so two builds run with the same arguments can be compared array for array.  Above DUMP_CAP_BYTES in all, a fixed seeded sample
+of rows is written (DIR/<name>_rows.npy holds the row indices kept).
 With --gpus N > 1 and no WORLD_SIZE in the environment the script starts its own ranks
 (`python -m torch.distributed.run --nproc-per-node N ... bench.py ...` as a child process, before anything touches a GPU).
 Prints ONE JSON line on rank 0.
@@ -36,6 +44,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0        # MI355X HBM3E peak (MI355X_MICROARCH.md: 8.0 TB/s spec, 6.29 TB/s float4 copy)
+SETTLE_S = 1.0              # set-up: seconds of pipelined steps before the warm-up (the first ~300 steps after an idle GPU run a few per cent slow)
+DUMP_CAP_BYTES = 64 << 20
 LEVEL_NAME = {5: "Segment Features (level 5)", 13: "Syllable Features (level 13)", 10: "Syllable Formants (level 10)",
               11: "Utterance Features (level 11)", 12: "Syllable Polynomials (level 12)"}
 
@@ -45,10 +55,14 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=9,
-                    help="the timed region (W warm-up + K timed steps between two synchronisation points) is run this many times in one invocation; "
-                         "ms_per_step / value are the MEDIAN region, min / max are reported beside it (the first one or two regions of an invocation run "
-                         "~5 %% slower — the GPU has been idle through the set-up —, so the median wants more than five of them)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline (repeated regions, single_batch, roofline, issue_bound, extra.*, cpu_baseline); "
+                         "a plain run times one region of exactly K steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed to DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the timed region (W warm-up + K timed steps between two synchronisation points) is run this many times in one invocation "
+                         "(default 1, with --full 9); ms_per_step / value are the MEDIAN region, min / max are reported beside it")
     ap.add_argument("--level", type=int, default=5, choices=(5, 13, 10, 11, 12))
     ap.add_argument("--clips", type=int, default=0, help="clips per GPU (default: 1024 at N = 1, the 12 500-clip shard of BASELINE config 4 at N > 1)")
     ap.add_argument("--seconds", type=float, default=10.0)
@@ -59,8 +73,8 @@ def parse_args():
     ap.add_argument("--slots-per-stream", type=int, default=0,
                     help="planned batches per stream (default 2 at N = 1, 1 at N > 1): with 2 a stream's next step is already queued behind the running one while "
                          "the host reads the finished step's counters, so no stream waits for the host's round trip")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the level-13 and streaming blocks")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline block")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the extra.* blocks")
     ap.add_argument("--cpu-clips", type=int, default=768)
     ap.add_argument("--master-port", type=int, default=29533)
     return ap.parse_args()
@@ -76,6 +90,8 @@ def spawn_ranks(args):
 
 def main():
     args = parse_args()
+    if args.repeats is None:
+        args.repeats = 9 if args.full else 1
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
     import numpy as np
@@ -175,21 +191,32 @@ def main():
     # with --warmup smaller than the pipeline depth no slot's first pass falls into the timed region
     run_steps(slots, depth, depth)
     torch.cuda.synchronize()
+    # then SETTLE_S seconds of pipelined steps, so that the timed region does not start on an idle GPU's clocks; the ranks stop together
+    # (every step of N > 1 ends in a collective gather)
+    t_settle = time.perf_counter()
+    while True:
+        run_steps(slots, 8 * depth, depth)
+        more = torch.tensor([1.0 if time.perf_counter() - t_settle < SETTLE_S else 0.0], dtype=torch.float64, device=dev)
+        if world > 1:
+            dist.all_reduce(more, op=dist.ReduceOp.MIN)
+        if float(more.item()) == 0.0:
+            break
     run_steps(slots, args.warmup, depth)
-    # strictly back to back (no overlap, warm): per-kernel times of kernels that have the GPU to themselves
     solo_ms = np.zeros(4)
     solo_wall = 0.0
-    for _ in range(3):
-        torch.cuda.synchronize()
-        t_s = time.perf_counter()
-        slots[0].launch()
-        _, ms1 = slots[0].finish()
-        solo_wall += time.perf_counter() - t_s
-        solo_ms += ms1
-    solo_ms /= 3
-    solo_wall /= 3
-    # the timed region, `repeats` times: W untimed warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides, MAX over
-    # ranks; a single 100-step region lasts ~65 ms and two of them differ by a per cent or two, so the line reports the median region
+    if args.full:
+        # strictly back to back (no overlap, warm): per-kernel times of kernels that have the GPU to themselves
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t_s = time.perf_counter()
+            slots[0].launch()
+            _, ms1 = slots[0].finish()
+            solo_wall += time.perf_counter() - t_s
+            solo_ms += ms1
+        solo_ms /= 3
+        solo_wall /= 3
+    # the timed region, `repeats` times (1 in a plain run): W untimed warm-up steps, then EXACTLY K steps between barrier + synchronize on both
+    # sides, MAX over ranks; a single 100-step region lasts ~55 ms and two of them differ by a per cent or two, so --full reports the median of 9
     regions = []
     for rep_i in range(max(1, args.repeats)):
         if rep_i:
@@ -214,6 +241,13 @@ def main():
     region_ms = [r[0] / max(args.steps, 1) * 1e3 for r in regions]
     stage = stage / max(args.steps, 1)
     reruns = sum(s.batch.backend_reruns() for s in slots)
+    last = slots[(args.steps - 1) % depth]                   # the slot of the last timed step (run_steps counts k from 0)
+    if args.dump_outputs and rank == 0:
+        if world == 1:
+            got = last.batch.rows(last.stream.cuda_stream)
+        else:
+            got = {"meta": last.recv[0][:last.gathered].cpu().numpy(), "feat": last.recv[1][:last.gathered].cpu().numpy()}
+        dump_outputs(args.dump_outputs, got)
 
     def copy_ceiling():
         """measured device-to-device copy rate on this box (bytes read + bytes written per second), the practical HBM ceiling"""
@@ -229,7 +263,6 @@ def main():
 
     if rank == 0:
         fe_name = "fe_kernel_r8" if geo["nfft"] == 1024 else ("fe_kernel_r3" if geo["nfft"] % 3 == 0 else "fe_kernel_rx")
-        traffic, traffic_per_kernel, traffic_src = pmc_traffic(n_clips, fs, args.level, args.seconds)
         total_frames = frames * world * args.steps
         value = total_frames / dt
         # roofline of the pipeline step: algorithmic bytes per step = 4 * hop samples per frame (PCM read once) + the 53-feature rows
@@ -247,8 +280,8 @@ def main():
         out = {
             "metric": "53-feat frames/sec", "value": value, "unit": "frames/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "repeats": {"n": len(regions), "what": "the timed region (warm-up + K steps between two synchronisation points) repeated inside this invocation; "
-                                                   "ms_per_step / value = the median region",
+            "repeats": {"n": len(regions), "what": "the timed region (warm-up + K steps between two synchronisation points) run this many times inside this "
+                                                   "invocation (1 in a plain run, 9 with --full); ms_per_step / value = the median region",
                         "ms_per_step_all": region_ms, "min": min(region_ms), "median": dt / args.steps * 1e3, "max": max(region_ms)},
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32 front end / f64 tracker",
             "data": "synthetic",
@@ -268,34 +301,38 @@ def main():
             "backend_reruns": int(reruns),
             "stage_ms": {"frontend_fft_mel": float(stage[0]), "backend_peaks_gate_tracker": float(stage[1] + stage[2]),
                          "compaction": float(stage[3])},
-            # primary object: the whole step against the HBM roofline (frac = achieved / peak can be recomputed from this line alone:
-            # algorithmic_bytes_per_step / ms_per_step); the dominant kernel's own figures sit below it
-            "roofline": {"bound": "hbm", "scope": "pipeline step: front end + peak scan + gate + tracker + compaction over one batch",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_per_kernel": traffic_per_kernel, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_step": alg_bytes, "ms_per_step": step_s * 1e3,
-                         "copy_ceiling_GBps_measured": copy_ceiling(),
-                         "dominant_kernel": {
-                             "alone": dom, "alone_ms": alone[dom], "kernels_alone_ms": alone,
-                             "pipelined": max(piped, key=piped.get), "kernels_pipelined_ms": piped,
-                             "front_end_alone_hbm_frac": float(alg_bytes / (float(solo_ms[0]) / 1e3) / 1e9 / HBM_PEAK_GBS) if solo_ms[0] > 0 else 0.0,
-                             "note": "alone = HIP events between the stages of 3 back-to-back steps (one batch has the GPU to itself; agrees with the "
-                                     "per-kernel averages of profiles/*_kernel_stats_in_flight_1.txt); pipelined = the same events inside the timed "
-                                     "region, where the kernels of the batches in flight share the CUs (an interval also contains the time a "
-                                     "launch waited for them; profiles/*_kernel_stats_default.txt has the profiler's own begin/end times)"}},
-            "issue_bound": issue_bound(n_clips, fs, args.level, args.seconds, step_s * 1e3, alg_bytes),
-            "single_batch": {"what": "3 steps strictly back to back before the timed region (one rank, includes the gather when n_gpus > 1)",
-                             "ms_per_step": solo_wall * 1e3, "value": frames / solo_wall,
-                             "frontend_fft_mel_ms": float(solo_ms[0]), "backend_ms": float(solo_ms[1] + solo_ms[2]),
-                             "peaks_gate_ms": float(solo_ms[1]), "tracker_ms": float(solo_ms[2]),
-                             "compaction_ms": float(solo_ms[3]),
-                             "frontend_hbm_frac": float(alg_bytes / (float(solo_ms[0]) / 1e3) / 1e9 / HBM_PEAK_GBS) if solo_ms[0] > 0 else 0.0,
-                             # SURVEY.md 8d asks for the fp32 FLOP fraction next to the HBM one (the FFT sits near the ridge):
-                             # algorithmic flops = 2.5 N log2 N (real FFT) + ~2 k (power, mel) per frame, vector fp32 peak 157.3 TFLOP/s
-                             "frontend_fp32_flop_frac": float(frames * (2.5 * geo["nfft"] * np.log2(geo["nfft"]) + 2000.0) / (float(solo_ms[0]) / 1e3) / 157.3e12) if solo_ms[0] > 0 else 0.0},
         }
-        if world == 1 and not args.no_extra:
-            gpu_rows_last = slots[(args.steps - 1) % depth].batch.rows(slots[(args.steps - 1) % depth].stream.cuda_stream)
+        if args.full:
+            traffic, traffic_per_kernel, traffic_src = pmc_traffic(n_clips, fs, args.level, args.seconds)
+            out.update({
+                # primary object: the whole step against the HBM roofline (frac = achieved / peak can be recomputed from this line alone:
+                # algorithmic_bytes_per_step / ms_per_step); the dominant kernel's own figures sit below it
+                "roofline": {"bound": "hbm", "scope": "pipeline step: front end + peak scan + gate + tracker + compaction over one batch",
+                             "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                             "traffic": traffic, "traffic_per_kernel": traffic_per_kernel, "traffic_source": traffic_src,
+                             "algorithmic_bytes_per_step": alg_bytes, "ms_per_step": step_s * 1e3,
+                             "copy_ceiling_GBps_measured": copy_ceiling(),
+                             "dominant_kernel": {
+                                 "alone": dom, "alone_ms": alone[dom], "kernels_alone_ms": alone,
+                                 "pipelined": max(piped, key=piped.get), "kernels_pipelined_ms": piped,
+                                 "front_end_alone_hbm_frac": float(alg_bytes / (float(solo_ms[0]) / 1e3) / 1e9 / HBM_PEAK_GBS) if solo_ms[0] > 0 else 0.0,
+                                 "note": "alone = HIP events between the stages of 3 back-to-back steps (one batch has the GPU to itself; agrees with the "
+                                         "per-kernel averages of profiles/*_kernel_stats_in_flight_1.txt); pipelined = the same events inside the timed "
+                                         "region, where the kernels of the batches in flight share the CUs (an interval also contains the time a "
+                                         "launch waited for them; profiles/*_kernel_stats_default.txt has the profiler's own begin/end times)"}},
+                "issue_bound": issue_bound(n_clips, fs, args.level, args.seconds, step_s * 1e3, alg_bytes),
+                "single_batch": {"what": "3 steps strictly back to back before the timed region (one rank, includes the gather when n_gpus > 1)",
+                                 "ms_per_step": solo_wall * 1e3, "value": frames / solo_wall,
+                                 "frontend_fft_mel_ms": float(solo_ms[0]), "backend_ms": float(solo_ms[1] + solo_ms[2]),
+                                 "peaks_gate_ms": float(solo_ms[1]), "tracker_ms": float(solo_ms[2]),
+                                 "compaction_ms": float(solo_ms[3]),
+                                 "frontend_hbm_frac": float(alg_bytes / (float(solo_ms[0]) / 1e3) / 1e9 / HBM_PEAK_GBS) if solo_ms[0] > 0 else 0.0,
+                                 # SURVEY.md 8d asks for the fp32 FLOP fraction next to the HBM one (the FFT sits near the ridge):
+                                 # algorithmic flops = 2.5 N log2 N (real FFT) + ~2 k (power, mel) per frame, vector fp32 peak 157.3 TFLOP/s
+                                 "frontend_fp32_flop_frac": float(frames * (2.5 * geo["nfft"] * np.log2(geo["nfft"]) + 2000.0) / (float(solo_ms[0]) / 1e3) / 157.3e12) if solo_ms[0] > 0 else 0.0},
+            })
+        if args.full and world == 1 and not args.no_extra:
+            gpu_rows_last = last.batch.rows(last.stream.cuda_stream)
             for s in slots:
                 s.batch.close()
             slots.clear()
@@ -314,13 +351,30 @@ def main():
                 "48k": extra_offline_48k(local_rank, n_clips, args.seconds, n_streams, level=13, window_step=15.0),
                 "16k": extra_offline_48k(local_rank, n_clips, args.seconds, n_streams, fs=16000, level=13, window_step=15.0)}
         else:
-            gpu_rows_last = slots[(args.steps - 1) % depth].batch.rows(slots[(args.steps - 1) % depth].stream.cuda_stream) if world == 1 else None
-        if not args.no_cpu_baseline and world == 1:          # the CPU figure is taken once, at N = 1
+            gpu_rows_last = last.batch.rows(last.stream.cuda_stream) if args.full and world == 1 else None
+        if args.full and not args.no_cpu_baseline and world == 1:          # the CPU figure is taken once, at N = 1
             out["cpu_baseline"] = cpu_baseline(pcm, fs, args.level, min(args.cpu_clips, n_clips), gpu_rows_last)
         print(json.dumps(out))
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(d, arrays):
+    """arrays (name -> numpy array) as d/<name>.npy in float64; above DUMP_CAP_BYTES in all, every array longer than the kept fraction
+    keeps a fixed seeded sample of its rows (the same indices for arrays of equal length, so meta and feat stay aligned), listed in d/<name>_rows.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.size * 8 for a in arrays.values())
+    keep = min(1.0, 0.95 * DUMP_CAP_BYTES / max(total, 1))
+    for name, a in arrays.items():
+        k = max(1, int(len(a) * keep)) if a.ndim and len(a) else 0
+        if keep < 1.0 and a.ndim and k < len(a):
+            idx = np.sort(np.random.default_rng(20240917).choice(len(a), k, replace=False))
+            np.save(os.path.join(d, name + "_rows.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def median_regions(run_region, repeats):

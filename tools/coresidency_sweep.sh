@@ -3,7 +3,7 @@ export WSA_TUNING_ENV=1   # libwsa reads its tuning switches only when this is s
 # Co-residency A/B: the pipelined bench with the front end / peak scan / tracker / finalize capped to fewer waves per CU,
 # so that kernels of the other steps in flight fit beside them.  Every line = median of 5 timed regions of 100 steps on THIS box.
 # usage (GPU box): tools/coresidency_sweep.sh [set] > gpurun_out/coresidency.txt
-run() { label="$1"; shift; env "$@" python3 bench.py --no-cpu-baseline --no-extra --steps 100 --warmup 3 --repeats 5 $DEPTH 2>/dev/null | python3 tools/bench_field.py "$label"; }
+run() { label="$1"; shift; env "$@" python3 bench.py --full --no-cpu-baseline --no-extra --steps 100 --warmup 3 --repeats 5 $DEPTH 2>/dev/null | python3 tools/bench_field.py "$label"; }
 set=${1:-a}
 if [ $set = a ]; then
 for d in "" "--in-flight 2" "--in-flight 4"; do

@@ -10,7 +10,7 @@ done
 python3 tools/pmc_traffic.py $(find /tmp/pmc_FETCH_SIZE -name '*counter_collection.csv' | head -1) $(find /tmp/pmc_WRITE_SIZE -name '*counter_collection.csv' | head -1) 1024 16000 5 10 > $O/pmc_traffic.json; cp $O/pmc_traffic.json profiles/r06_pmc_traffic.json
 tools/refresh_profiles.sh r06 > $O/refresh.log 2>&1
 python3 bench.py --steps 20 --warmup 5 > $O/bench_steps20.json 2>> $O/bench.err
-python3 bench.py --level 12 --no-cpu-baseline --no-extra > $O/bench_level12.json 2>> $O/bench.err
+python3 bench.py --full --level 12 --no-cpu-baseline --no-extra > $O/bench_level12.json 2>> $O/bench.err
 tools/pmc_util.sh > $O/pmc_util.txt 2>&1
 tools/pmc_lds.sh > $O/pmc_lds.txt 2>&1
 tools/refresh_shard.sh r06 >> $O/refresh.log 2>&1

@@ -4,8 +4,8 @@ export WSA_TUNING_ENV=1   # libwsa reads its tuning switches only when this is s
 tag=${1:-x}
 export TMPDIR=/tmp
 ROOT=$(pwd); O=$ROOT/gpurun_out/prof_$tag; mkdir -p $O
-python3 bench.py > $O/bench.json 2> $O/bench.err
-python3 bench.py --level 13 --no-cpu-baseline > $O/bench_level13.json 2>> $O/bench.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
+python3 bench.py --full --level 13 --no-cpu-baseline > $O/bench_level13.json 2>> $O/bench.err
 python3 bench_stream.py 2>> $O/bench.err | tail -1 > $O/stream_bench.json
 for mode in default in_flight_1 stream; do
   d=/tmp/prof_$mode; rm -rf $d

@@ -5,7 +5,7 @@ export WSA_TUNING_ENV=1   # libwsa reads its tuning switches only when this is s
 tag=${1:-x}
 export TMPDIR=/tmp
 ROOT=$(pwd); O=$ROOT/gpurun_out/prof_$tag; mkdir -p $O
-python3 bench.py --clips 12500 --steps 10 --warmup 2 --repeats 3 --no-cpu-baseline --no-extra > $O/bench_shard.json 2>> $O/bench.err
+python3 bench.py --full --clips 12500 --steps 10 --warmup 2 --repeats 3 --no-cpu-baseline --no-extra > $O/bench_shard.json 2>> $O/bench.err
 for mode in default in_flight_1; do
   d=/tmp/prof_shard_$mode; rm -rf $d
   extra=""; [ $mode = in_flight_1 ] && extra="--in-flight 1"
