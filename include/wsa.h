@@ -338,6 +338,62 @@ wsa_status wsa_stream_enable_graph(wsa_stream *st, int32_t on);
  * host's monotonic clock; out_us[k] = microseconds of step k, *rows_total = feature rows produced (may be NULL). */
 wsa_status wsa_stream_time_steps(wsa_stream *st, uint32_t n_steps, const float *feed, uint32_t feed_steps, void *stream, double *out_us, uint64_t *rows_total);
 
+/*
+ * ---- Syllable classification (additions within version 5: probe for wsa_model_create).
+ * Stands in for what the reference APPLICATION does with the level-13 rows when `predict_en` is set (ref src/index.js:56,
+ * src/prediction.js:47-169): ml5 `classifyMultiple` with a trained dense network (dist/nnmodel/<db>/cats_<label>/) over a
+ * callback's syllables, the fold of the per-syllable confidences into one [label, confidence] per callback, and the per-launch
+ * accumulator behind the app's meters (Label_conf_all).  K6 runs the network (f32 MFMA; tolerance against tfjs, DESIGN.md
+ * "K6"), K6b the fold (exact double arithmetic).  Everything is enqueued on the caller's stream; after the first
+ * wsa_batch_classify on a batch nothing is allocated, so wsa_batch_run + wsa_batch_classify can be captured into a hipGraph.
+ * A model belongs to the context it was created on; destroy it before that context.
+ */
+typedef struct wsa_model wsa_model;
+enum { WSA_ACT_LINEAR = 0, WSA_ACT_RELU = 1, WSA_ACT_SIGMOID = 2, WSA_ACT_TANH = 3, WSA_ACT_SOFTMAX = 4 };
+#define WSA_MODEL_MAX_LAYERS 8
+#define WSA_MODEL_MAX_WIDTH 1024
+#define WSA_MODEL_MAX_CLASSES 64
+typedef struct {
+    int32_t n_layers;                     /* Dense layers, 1 .. WSA_MODEL_MAX_LAYERS */
+    const int32_t *units;                 /* [n_layers + 1]; units[0] must be WSA_NFEAT, widths <= WSA_MODEL_MAX_WIDTH,
+                                             units[n_layers] <= WSA_MODEL_MAX_CLASSES */
+    const int32_t *activation;            /* [n_layers] WSA_ACT_*; softmax only on the last layer */
+    const float *const *kernel;           /* [n_layers] -> [units[i]][units[i+1]] row-major (the tfjs Dense kernel) */
+    const float *const *bias;             /* [n_layers] -> [units[i+1]] */
+    const double *in_min, *in_max;        /* [WSA_NFEAT] model_meta.json inputs["0".."52"].min / max */
+    const char *const *labels;            /* [units[n_layers]] the legend keys in legend order, or NULL.  Only used for the order in which the
+                                             fold scans labels: keys that are array indices ("0", "17") come first, ascending, as in
+                                             Object.keys (ref prediction.js:134) */
+} wsa_model_desc;
+wsa_status wsa_model_create(wsa_ctx *ctx, const wsa_model_desc *d, wsa_model **out);    /* copies the weights to the context's device */
+void       wsa_model_destroy(wsa_model *m);
+/* prob[r][c] (f32, [n_rows][units[n_layers]]) of device rows feat[r][WSA_NFEAT] (double): normalised as ml5's normalizeValue
+ * ((x - min) / (max - min) in double, no clamping), rounded to f32, then the network.  Device pointers; asynchronous on `stream`. */
+wsa_status wsa_classify_rows(const wsa_model *m, const double *d_feat, uint32_t n_rows, float *d_prob, void *stream);
+/* After a run at output_level 5 or 13: the probabilities of every row of the batch and, at level 13 (softmax models only), the
+ * fold per callback and per clip.  WSA_ERR_INVALID at any other level, for a model of another context, and for a fold requested
+ * from a model without a softmax output. */
+wsa_status wsa_batch_classify(wsa_batch *b, const wsa_model *m, void *stream);
+/* Synchronises `stream` and hands out the last classification (device pointers valid until the next wsa_batch_classify with a
+ * model of more classes or wsa_batch_destroy):
+ *   d_prob      [n_rows][n_classes] f32, rows in the order of wsa_device_result's tables
+ *   d_cb        [n_callbacks][4] = {clip, si, first row, rows} — one entry per level-13 callback (a run of rows with the same clip, si)
+ *   d_cb_label  [n_callbacks] class index of the callback's label; -1 = the reference's `null` (no sum above 0); -2 = no prediction
+ *               at all (the callback's durations sum to 0: the reference skips the model and callback_after_pred)
+ *   d_cb_conf   [n_callbacks] f64 confidence: max label sum / sum of the durations (ref prediction.js:168)
+ *   d_clip_conf [n_clips][n_classes] f64: Label_conf_all of each clip (reset per launch, ref src/index.js:395), 0 for labels never added
+ * Level 5: n_callbacks = 0 and no clip sums (d_cb* / d_clip_conf NULL). */
+typedef struct {
+    uint32_t n_rows, n_classes, n_callbacks, n_clips;
+    const float *d_prob; const int32_t *d_cb; const int32_t *d_cb_label;
+    const double *d_cb_conf; const double *d_clip_conf;
+} wsa_class_result;
+wsa_status wsa_batch_class_result(wsa_batch *b, void *stream, wsa_class_result *out);
+/* The same tables copied to host buffers (any pointer may be NULL to skip it), for hosts without a HIP binding: prob [rows_cap][n_classes],
+ * cb [cb_cap][4], cb_label / cb_conf [cb_cap], clip_conf [n_clips][n_classes] (level 13 only).  WSA_ERR_INVALID if a capacity is too small. */
+wsa_status wsa_batch_copy_classes(wsa_batch *b, void *stream, float *prob, uint32_t rows_cap, int32_t *cb, int32_t *cb_label, double *cb_conf,
+                                  uint32_t cb_cap, double *clip_conf);
+
 #ifdef __cplusplus
 }
 #endif

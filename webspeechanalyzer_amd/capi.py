@@ -84,6 +84,18 @@ class _BatchInfo(ctypes.Structure):
                 ("workspace_bytes", ctypes.c_uint64)]
 
 
+class _ModelDesc(ctypes.Structure):
+    _fields_ = [("n_layers", ctypes.c_int32), ("units", ctypes.c_void_p), ("activation", ctypes.c_void_p),
+                ("kernel", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("in_min", ctypes.c_void_p), ("in_max", ctypes.c_void_p),
+                ("labels", ctypes.c_void_p)]
+
+
+class _ClassResult(ctypes.Structure):
+    _fields_ = [("n_rows", ctypes.c_uint32), ("n_classes", ctypes.c_uint32), ("n_callbacks", ctypes.c_uint32), ("n_clips", ctypes.c_uint32),
+                ("d_prob", ctypes.c_void_p), ("d_cb", ctypes.c_void_p), ("d_cb_label", ctypes.c_void_p),
+                ("d_cb_conf", ctypes.c_void_p), ("d_clip_conf", ctypes.c_void_p)]
+
+
 # every symbol include/wsa.h declares (checked by tests/test_abi.py)
 ABI_VERSION = 5            # WSA_ABI_VERSION of include/wsa.h this binding's structures follow
 ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destroy", "wsa_last_error",
@@ -95,7 +107,9 @@ ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destr
                "wsa_stream_create", "wsa_stream_destroy", "wsa_stream_samples_per_step", "wsa_stream_step",
                "wsa_stream_host_input", "wsa_stream_step_host", "wsa_stream_collect", "wsa_stream_enable_graph",
                "wsa_batch_keep_spectra", "wsa_batch_backend_reruns", "wsa_stream_time_steps", "wsa_batch_run_host_i16",
-               "wsa_gather_create", "wsa_gather_destroy", "wsa_gather_rows", "wsa_gather_copy_rows", "wsa_host_alloc", "wsa_host_free", "wsa_queue_create", "wsa_queue_destroy"]
+               "wsa_gather_create", "wsa_gather_destroy", "wsa_gather_rows", "wsa_gather_copy_rows", "wsa_host_alloc", "wsa_host_free", "wsa_queue_create", "wsa_queue_destroy",
+               # additions within version 5 (probe for wsa_model_create): the app's syllable classifier
+               "wsa_model_create", "wsa_model_destroy", "wsa_classify_rows", "wsa_batch_classify", "wsa_batch_class_result", "wsa_batch_copy_classes"]
 
 _LIB = None
 
@@ -178,9 +192,16 @@ def lib():
     L.wsa_gather_destroy.argtypes = [vp]
     L.wsa_gather_rows.argtypes = [vp, vp, vp, vp]
     L.wsa_gather_copy_rows.argtypes = [vp, vp, vp, u32]
+    L.wsa_model_create.argtypes = [vp, ctypes.POINTER(_ModelDesc), ctypes.POINTER(vp)]
+    L.wsa_model_destroy.argtypes = [vp]
+    L.wsa_classify_rows.argtypes = [vp, vp, u32, vp, vp]
+    L.wsa_batch_classify.argtypes = [vp, vp, vp]
+    L.wsa_batch_class_result.argtypes = [vp, vp, ctypes.POINTER(_ClassResult)]
+    L.wsa_batch_copy_classes.argtypes = [vp, vp, vp, u32, vp, vp, vp, u32, vp]
     for name in ABI_SYMBOLS:
         if name not in ("wsa_abi_version", "wsa_last_error", "wsa_config_default", "wsa_destroy", "wsa_batch_destroy", "wsa_resample_length",
-                        "wsa_stream_destroy", "wsa_stream_samples_per_step", "wsa_stream_host_input", "wsa_gather_destroy", "wsa_host_free"):
+                        "wsa_stream_destroy", "wsa_stream_samples_per_step", "wsa_stream_host_input", "wsa_gather_destroy", "wsa_host_free",
+                        "wsa_model_destroy"):
             getattr(L, name).restype = ctypes.c_int
     _LIB = L
     return L
@@ -239,6 +260,18 @@ class Analyzer:
 
     def streams(self, n_streams, fs, frames_per_step=1, max_span_frames=1024):
         return Streams(self, n_streams, fs, frames_per_step, max_span_frames)
+
+    def load_model(self, src):
+        """The app's trained classifier on this context's device: `src` = a directory as dist/nnmodel/<db>/cats_<label>/ ships it, a
+        (model_json, meta_json, weights_bytes) tuple, or a parsed nnmodel.ModelSpec."""
+        from . import nnmodel
+        if isinstance(src, nnmodel.ModelSpec):
+            spec = src
+        elif isinstance(src, (tuple, list)):
+            spec = nnmodel.parse(*src)
+        else:
+            spec = nnmodel.load_dir(src)
+        return Model(self, spec)
 
     def close(self):
         if self.h:
@@ -429,9 +462,69 @@ class Batch:
                             flags=[int(s[3]) for s in r["segments"][sa:sb]], meta=meta))
         return out
 
+    def classify(self, model, stream=0):
+        """K6 (+ K6b at level 13) on the rows of the last run, enqueued on `stream` (wsa_batch_classify)."""
+        self.an._check(self.L.wsa_batch_classify(self.h, model.h, stream))
+        self._model = model
+
+    def class_result(self, stream=0):
+        r = _ClassResult()
+        self.an._check(self.L.wsa_batch_class_result(self.h, stream, ctypes.byref(r)))
+        return r
+
+    def classes(self, stream=0):
+        """Host copies of the last classification: dict(prob [n_rows, C] f32, cb [n_cb, 4] i32 = {clip, si, first row, rows},
+        cb_label [n_cb] i32 (-1: null, -2: not predicted), cb_conf [n_cb] f64, clip_conf [n_clips, C] f64, labels)."""
+        r = self.class_result(stream)
+        C, n, k = int(r.n_classes), int(r.n_rows), int(r.n_callbacks)
+        prob, cb = np.zeros((n, C), np.float32), np.zeros((k, 4), np.int32)
+        lab, conf = np.zeros(k, np.int32), np.zeros(k, np.float64)
+        clip = np.zeros((int(r.n_clips), C), np.float64) if r.d_clip_conf else np.zeros((0, C))
+        self.an._check(self.L.wsa_batch_copy_classes(self.h, stream, prob.ctypes.data, max(n, 1), cb.ctypes.data, lab.ctypes.data, conf.ctypes.data,
+                                                      max(k, 1), clip.ctypes.data if r.d_clip_conf else None))
+        return dict(prob=prob, cb=cb, cb_label=lab, cb_conf=conf, clip_conf=clip, labels=list(self._model.labels))
+
     def close(self):
         if self.h:
             self.L.wsa_batch_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Model:
+    """wsa_model: a Dense classifier (the app's ml5 model) on the device of one context."""
+
+    def __init__(self, an, spec):
+        from . import nnmodel
+        self.an, self.L, self.spec = an, an.L, spec
+        self.labels = list(spec.labels)
+        self.n_classes = spec.n_classes
+        nl = len(spec.kernels)
+        self._keep = [np.ascontiguousarray(k, np.float32) for k in spec.kernels] + [np.ascontiguousarray(b, np.float32) for b in spec.biases]
+        units = (ctypes.c_int32 * (nl + 1))(*spec.units)
+        acts = (ctypes.c_int32 * nl)(*[nnmodel.ACT[a] for a in spec.activations])
+        kp = (ctypes.c_void_p * nl)(*[a.ctypes.data for a in self._keep[:nl]])
+        bp = (ctypes.c_void_p * nl)(*[a.ctypes.data for a in self._keep[nl:]])
+        mn, mx = np.ascontiguousarray(spec.in_min, np.float64), np.ascontiguousarray(spec.in_max, np.float64)
+        lab = (ctypes.c_char_p * len(self.labels))(*[str(x).encode() for x in self.labels]) if len(self.labels) == spec.n_classes else None
+        d = _ModelDesc(nl, ctypes.cast(units, ctypes.c_void_p), ctypes.cast(acts, ctypes.c_void_p), ctypes.cast(kp, ctypes.c_void_p),
+                       ctypes.cast(bp, ctypes.c_void_p), mn.ctypes.data, mx.ctypes.data, ctypes.cast(lab, ctypes.c_void_p) if lab is not None else None)
+        self.h = ctypes.c_void_p()
+        an._check(self.L.wsa_model_create(an.h, ctypes.byref(d), ctypes.byref(self.h)))
+        self._keep = None
+
+    def classify_rows(self, d_feat, n_rows, d_prob, stream=0):
+        """K6 on device rows: d_feat [n_rows][53] f64 -> d_prob [n_rows][n_classes] f32 (device pointers, asynchronous on `stream`)."""
+        self.an._check(self.L.wsa_classify_rows(self.h, d_feat, int(n_rows), d_prob, stream))
+
+    def close(self):
+        if self.h:
+            self.L.wsa_model_destroy(self.h)
             self.h = ctypes.c_void_p()
 
     def __del__(self):

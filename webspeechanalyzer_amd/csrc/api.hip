@@ -71,6 +71,7 @@ struct wsa_batch {
     uint32_t reruns = 0;
     uint32_t res_rows = 0, res_segs = 0, res_flags = 0;
     const uint32_t* spec_in_use = nullptr;
+    wsa_cls* cls = nullptr;                 // wsa_batch_classify (classify.hip)
 };
 
 template <typename T>
@@ -195,6 +196,7 @@ void wsa_batch_destroy(wsa_batch* b) {
     if (b->up_start) (void)hipEventDestroy(b->up_start);
     if (b->h_totals) (void)hipHostFree(b->h_totals);
     for (auto& e : b->ev) if (e) (void)hipEventDestroy(e);
+    wsa_cls_free(b->cls);
     delete b;
 }
 
@@ -709,6 +711,12 @@ void wsa_queue_destroy(wsa_ctx* ctx, void* stream) {
     if (ctx) (void)hipSetDevice(ctx->device);
     (void)hipStreamDestroy(reinterpret_cast<hipStream_t>(stream));
 }
+
+void wsa_batch_view_internal(wsa_batch* b, wsa_batch_view* v) {
+    v->ctx = b->ctx; v->level = b->ctx->cfg.output_level; v->n_clips = b->n_clips; v->rows_cap = b->n_clips * (uint32_t)b->row_cap;
+    v->d_meta = b->d_meta; v->d_feat = b->d_feat; v->d_row_off = b->d_row_off; v->reruns = b->reruns; v->cls = &b->cls;
+}
+wsa_status wsa_batch_fetch_internal(wsa_batch* b, hipStream_t s) { return fetch_totals(b, s); }
 
 // (gather.cpp checks that a rank's batch belongs to the rank's context)
 wsa_ctx* wsa_batch_ctx_internal(const wsa_batch* b) { return b ? b->ctx : nullptr; }

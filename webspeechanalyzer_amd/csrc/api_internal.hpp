@@ -19,5 +19,19 @@ inline wsa_status fail(wsa_ctx* c, wsa_status st, const std::string& msg) {
 }
 }  // namespace wsa_api
 
+// classify.hip (K6 / K6b) reads a batch's compacted rows and keeps its own per-batch state; api.hip owns the batch object
+struct wsa_cls;                                 // classification buffers of one batch (allocated by the first wsa_batch_classify)
+void wsa_cls_free(wsa_cls* c);                  // (wsa_batch_destroy)
+struct wsa_batch_view {
+    wsa_ctx* ctx; int level; uint32_t n_clips, rows_cap;
+    const int32_t* d_meta; const double* d_feat; const uint32_t* d_row_off;     // compacted rows, d_row_off[n_clips] = rows on the device
+    uint32_t reruns;                                                            // wsa_batch_backend_reruns
+    wsa_cls** cls;
+};
+extern "C" {
+void wsa_batch_view_internal(wsa_batch* b, wsa_batch_view* v);
+wsa_status wsa_batch_fetch_internal(wsa_batch* b, hipStream_t s);
+}              // fetch_totals: synchronise, read the counters (reruns the back end on a table overflow)
+
 #define HIP_TRY(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
         return wsa_api::fail((ctx), WSA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)

@@ -156,7 +156,11 @@ function drop_contexts(nat) {
   for (const c of ctx_cache.ctxs) { try { nat.destroy(c); } catch (e) { /* still in use by a failed launch's stragglers: left to process exit */ } }
   ctx_cache = { key: null, ctxs: [] };
 }
-function shutdown() { if (native && !playing) { drop_contexts(native); drop_pipe_contexts(native); } }
+function shutdown() {
+  if (playing) return;
+  if (native) { drop_contexts(native); drop_pipe_contexts(native); }
+  release_models();
+}
 
 // ---- page-locked clip memory (ours; no counterpart in the reference, which hands the browser a file's ArrayBuffer, src/index.js:291).  A clip that
 // lies in an ArrayBuffer from allocPinned goes to the GPU by DMA at the PCIe link's rate; a clip in ordinary memory is staged by the runtime
@@ -178,8 +182,110 @@ let playing = false, stop_requested = false;
 let labels_per_segment = [];
 const open_streams = new Set();
 
+// ---- the app's syllable classifier (ref src/index.js:56 -> src/prediction.js:47; K6 / K6b, include/wsa.h "Syllable classification").
+// loadModel(dir | {model, meta, weights}) parses the files the app ships in dist/nnmodel/<db>/cats_<label>/ (model.json: a Sequential stack of
+// Dense layers + weightsManifest; model.weights.bin: float32 kernels [in][out] and biases; model_meta.json: input ranges, output legend) and
+// returns a handle; setPredictionModel(handle | null, on_prediction) makes every level-13 launch classify its syllables on the GPU and call
+//     on_prediction(si, [label, confidence], clip_index, per_syllable)
+// right after each segment's callback — the first two arguments are what the app's callback_after_pred receives (ref prediction.js:70), so
+// `(si, lc) => fa.set_predicted_label_for_segment(si, 1, lc)` is the app's wiring (ref src/index.js:102-104); per_syllable is what ml5's
+// classifyMultiple returned for the segment's syllables (for ONE syllable: that syllable's sorted list itself).  Callbacks whose durations
+// sum to 0 get no on_prediction (the reference predicts nothing there).  The per-clip accumulator behind the app's meters (Label_conf_all,
+// reset per launch) is on the resolved result of LaunchBatch / LaunchBatches as `meters`.  With no model set nothing changes.
+const ACT = { linear: 0, relu: 1, sigmoid: 2, tanh: 3, softmax: 4 };
+const loaded_models = new Set();
+let prediction = null;                  // {model, on_prediction}
+function parse_model(mj, meta, weights) {
+  const topo = mj.modelTopology, layers = topo && topo.config && (Array.isArray(topo.config) ? topo.config : topo.config.layers);
+  if (!topo || topo.class_name !== 'Sequential' || !Array.isArray(layers)) throw 'loadModel: model.json is not a Sequential model';
+  const man = [].concat(...(mj.weightsManifest || []).map((g) => g.weights));
+  if (layers.length < 1 || man.length !== 2 * layers.length) throw 'loadModel: weightsManifest does not list a kernel and a bias per layer';
+  const act = layers.map((l, i) => {
+    if (l.class_name !== 'Dense') throw 'loadModel: layer ' + i + ' is ' + l.class_name + '; only Dense layers are supported';
+    const a = l.config.activation || 'linear';
+    if (!(a in ACT)) throw 'loadModel: layer ' + i + ' has activation ' + a;
+    return ACT[a];
+  });
+  const bytes = man.reduce((t, w) => t + 4 * w.shape.reduce((x, y) => x * y, 1), 0);
+  if (weights.byteLength !== bytes) throw 'loadModel: model.weights.bin holds ' + weights.byteLength + ' bytes, the weightsManifest needs ' + bytes;
+  const buf = new Uint8Array(weights.buffer ? weights.buffer.slice(weights.byteOffset, weights.byteOffset + weights.byteLength) : weights);
+  const units = [man[0].shape[0]], kernels = [], biases = [];
+  let off = 0;
+  for (let i = 0; i < layers.length; i++) {
+    const ks = man[2 * i].shape, bs = man[2 * i + 1].shape;
+    if (ks.length !== 2 || ks[0] !== units[i] || bs[0] !== ks[1]) throw 'loadModel: layer ' + i + ' shapes do not chain';
+    kernels.push(new Float32Array(buf.slice(off, off + 4 * ks[0] * ks[1]).buffer)); off += 4 * ks[0] * ks[1];
+    biases.push(new Float32Array(buf.slice(off, off + 4 * bs[0]).buffer)); off += 4 * bs[0];
+    units.push(ks[1]);
+  }
+  if (units[0] !== 53) throw 'loadModel: the model takes ' + units[0] + ' inputs; the feature rows have 53';
+  const inMin = new Float64Array(53), inMax = new Float64Array(53);
+  for (let k = 0; k < 53; k++) { const r = meta.inputs[String(k)]; inMin[k] = r.min; inMax[k] = r.max; }
+  const out = meta.outputs.y || Object.values(meta.outputs)[0];
+  const labels = Object.keys(out.legend);
+  return { units: Int32Array.from(units), activation: Int32Array.from(act), kernels, biases, inMin, inMax, labels };
+}
+function loadModel(src) {
+  const fs = require('fs');
+  let mj, meta, weights;
+  if (typeof src === 'string') {
+    mj = JSON.parse(fs.readFileSync(path.join(src, 'model.json'), 'utf8'));
+    meta = JSON.parse(fs.readFileSync(path.join(src, 'model_meta.json'), 'utf8'));
+    const paths = [].concat(...(mj.weightsManifest || []).map((g) => g.paths || []));
+    weights = Buffer.concat((paths.length ? paths : ['model.weights.bin']).map((p) => fs.readFileSync(path.join(src, path.basename(p)))));
+  } else if (src && src.model && src.meta && src.weights) {
+    mj = typeof src.model === 'string' ? JSON.parse(src.model) : src.model;
+    meta = typeof src.meta === 'string' ? JSON.parse(src.meta) : src.meta;
+    weights = src.weights;
+  } else throw 'loadModel(dir | {model, meta, weights})';
+  const h = { spec: parse_model(mj, meta, weights), natives: new Map(), released: false };
+  h.labels = h.spec.labels.slice();
+  loaded_models.add(h);
+  return h;
+}
+function setPredictionModel(handle, on_prediction) {
+  if (handle === null || handle === undefined) { prediction = null; return; }
+  if (!loaded_models.has(handle) || handle.released) throw 'setPredictionModel: the model handle was released (shutdown()) or is not one of loadModel';
+  if (typeof on_prediction !== 'function') throw 'setPredictionModel(handle, on_prediction)';
+  prediction = { model: handle, on_prediction };
+}
+function release_models() {           // shutdown(): the native models go with their contexts; the handles are refused from here on
+  for (const h of loaded_models) { h.released = true; h.natives.clear(); }
+  loaded_models.clear();
+  prediction = null;
+}
+function model_on(nat, ctx) {         // the native model of the prediction model on one context (created at its first use there)
+  if (!prediction || settings.output_level !== 13) return undefined;
+  const h = prediction.model;
+  if (h.released) throw 'the prediction model was released (shutdown())';
+  let m = h.natives.get(ctx);
+  if (!m) { m = nat.modelCreate(ctx, h.spec); h.natives.set(ctx, m); }
+  return m;
+}
+// per clip: Label_conf_all as {label: sum} in legend order (labels never added: 0)
+function meters_of(res, clip, labels) {
+  const C = res.nClasses, o = {};
+  for (let c = 0; c < C; c++) o[labels[c]] = res.clipConf[clip * C + c];
+  return o;
+}
+// the prediction of the level-13 callback whose first row is r (res.cb lists them in row order)
+function predict_after(res, r, si, clip, pred) {
+  if (!res.cbIndex) { res.cbIndex = new Map(); for (let k = 0; k < res.cb.length / 4; k++) res.cbIndex.set(res.cb[k * 4 + 2], k); }
+  const k = res.cbIndex.get(r);
+  if (k === undefined || res.cbLabel[k] === -2) return;
+  const labels = pred.model.labels, C = res.nClasses, n = res.cb[k * 4 + 3];
+  const sorted = (q) => {
+    const e = [];
+    for (let c = 0; c < C; c++) e.push({ [labels[c]]: res.prob[q * C + c], label: labels[c], confidence: res.prob[q * C + c] });
+    return e.sort((a, b) => b.confidence - a.confidence);             // ml5 classifyInternal (a stable sort: ties keep legend order)
+  };
+  const per = n === 1 ? sorted(r) : Array.from({ length: n }, (_, q) => sorted(r + q));
+  const lab = res.cbLabel[k] >= 0 ? labels[res.cbLabel[k]] : null;
+  pred.on_prediction(si, [lab, res.cbConf[k]], clip, per);
+}
+
 // rows of one clip -> the reference's callback sequence (ref dispatcher P() @B28869)
-function dispatch(res, clip, callback, label) {
+function dispatch(res, clip, callback, label, pred = null, clip_index = clip) {
   const level = settings.output_level, step = settings.window_step / 1e3;
   const a = res.rowOff[clip], b = res.rowOff[clip + 1];
   const feat = (r) => Array.from(res.feat.subarray(r * 53, r * 53 + 53));
@@ -205,7 +311,10 @@ function dispatch(res, clip, callback, label) {
         if (!cut) feats.push(nf === 53 ? feat(r) : Array.from(res.feat.subarray(r * 53, r * 53 + nf)));
         r++;
       }
-      if (feats.length > 0) callback(si, label, times, feats);                                // ref @B29138 (`p[e].length>0`)
+      if (feats.length > 0) {
+        if (callback) callback(si, label, times, feats);                                      // ref @B29138 (`p[e].length>0`)
+        if (pred && res.cb && level === 13) predict_after(res, r - times.length, si, clip_index, pred);       // ref src/index.js:56 -> prediction.js:70
+      }
     }
   } else if (level === 11) {
     // utterance features: after every result the 264 histogram bins over everything so far, callback index 0 (ref @B28869)
@@ -303,10 +412,13 @@ async function run(clips, callback, labels_of, test_play) {
     // the feature rows of all shards in one piece: they stay on their devices, one grouped RCCL send / receive over xGMI moves them to the first
     // device (include/wsa.h wsa_gather_rows) and ONE copy brings them to the host; a shard's small tables (segments, offsets) come with its own job
     const gather = (settings.output_level === 5 || settings.output_level === 13) && (settings.gather === null ? devs.length > 1 && new Set(devs).size === devs.length : settings.gather);      // (a rank is a GPU: contexts that share a device are not gathered)
+    const pred = prediction && settings.output_level === 13 ? prediction : null;
+    const models = ctxs.map((c) => (pred ? model_on(nat, c) : undefined));
     const job = ([a, b], i) => {
       const part = clips.slice(a, b);
-      return all16 ? nat.processBatch(ctxs[i], part.map((c) => c.pcm16), fs, settings.output_level, fs_an, Uint32Array.from(part, (c) => c.channels), gather)
-        : nat.processBatch(ctxs[i], part.map(clip_floats), fs, settings.output_level, fs_an, undefined, gather);
+      const extra = pred ? [models[i]] : [];                     // (no model: the addon is called exactly as before)
+      return all16 ? nat.processBatch(ctxs[i], part.map((c) => c.pcm16), fs, settings.output_level, fs_an, Uint32Array.from(part, (c) => c.channels), gather, ...extra)
+        : nat.processBatch(ctxs[i], part.map(clip_floats), fs, settings.output_level, fs_an, undefined, gather, ...extra);
     };
     // every shard runs to its end before anything else happens (a context with work in flight must not be touched), then the
     // first failure, if any, is what the launch rejects with
@@ -325,10 +437,11 @@ async function run(clips, callback, labels_of, test_play) {
     }
     // StopAudioNodes while the work was in flight: the reference tears the nodes down at the next frame and resolves (ref @B8851) —
     // nothing is dispatched any more, the launch still resolves
-    if (!test_play && callback) {                                                              // ref @B24762: silent when test_play
+    if (!test_play && (callback || pred)) {                                                   // ref @B24762: silent when test_play
       for (let i = 0; i < shards.length && !stop_requested; i++)
-        for (let c = shards[i][0]; c < shards[i][1] && !stop_requested; c++) dispatch(results[i], c - shards[i][0], callback, labels_of(c));
+        for (let c = shards[i][0]; c < shards[i][1] && !stop_requested; c++) dispatch(results[i], c - shards[i][0], callback, labels_of(c), pred, c);
     }
+    if (pred) results.meters = [].concat(...shards.map(([a, b], i) => Array.from({ length: b - a }, (_, c) => meters_of(results[i], c, pred.model.labels))));
     return results;
   } finally {
     playing = false;
@@ -362,8 +475,8 @@ function LaunchBatch(clips, callback = null, labels = [], test_play = false) {
     let current = 0;
     const cb = callback ? (si, label, t, f) => callback(si, label, t, f, current) : null;
     const labels_of = (c) => { current = c; return labels[c] || []; };
-    run(list, cb, labels_of, test_play).then((rs) => resolve({ rows: rs.reduce((t, r) => t + r.meta.length / 8, 0), segments: rs.reduce((t, r) => t + r.segments.length / 4, 0),
-      stageMs: Array.from(rs[0].stageMs), shards: rs.length, stopped: stop_requested }),
+    run(list, cb, labels_of, test_play).then((rs) => resolve(Object.assign({ rows: rs.reduce((t, r) => t + r.meta.length / 8, 0), segments: rs.reduce((t, r) => t + r.segments.length / 4, 0),
+      stageMs: Array.from(rs[0].stageMs), shards: rs.length, stopped: stop_requested }, rs.meters ? { meters: rs.meters } : {})),
       (e) => reject(typeof e === 'string' ? e : String(e.message || e)));
   });
 }
@@ -395,6 +508,9 @@ async function run_batches(batches, callback, labels, test_play) {
   playing = true; stop_requested = false; labels_per_segment = [];
   try {
     const ctxs = pipe_contexts(nat);
+    const pred = prediction && settings.output_level === 13 ? prediction : null;
+    const models = ctxs.map((c) => (pred ? model_on(nat, c) : undefined));
+    const meters = pred ? [] : null;
     const lists = batches.map((b) => b.map(to_pcm));
     const bands = settings.spec_type === 1 ? settings.N_mel_bins : settings.N_fft_bins;
     const start = (k) => {
@@ -405,8 +521,9 @@ async function run_batches(batches, callback, labels, test_play) {
       const g = nat.geometry(ctxs[k % 2], fs_an);
       if (g.bands !== bands) throw 'Bins count mismatch: ' + g.bands + ', ' + bands;          // ref @B8568 check
       const all16 = clips.every((c) => c.pcm16);
-      return all16 ? nat.processBatch(ctxs[k % 2], clips.map((c) => c.pcm16), fs, settings.output_level, fs_an, Uint32Array.from(clips, (c) => c.channels), false)
-        : nat.processBatch(ctxs[k % 2], clips.map(clip_floats), fs, settings.output_level, fs_an, undefined, false);
+      const extra = pred ? [models[k % 2]] : [];
+      return all16 ? nat.processBatch(ctxs[k % 2], clips.map((c) => c.pcm16), fs, settings.output_level, fs_an, Uint32Array.from(clips, (c) => c.channels), false, ...extra)
+        : nat.processBatch(ctxs[k % 2], clips.map(clip_floats), fs, settings.output_level, fs_an, undefined, false, ...extra);
     };
     let rows = 0, segments = 0, done = 0;
     let next = lists.length > 0 ? start(0) : null;
@@ -421,16 +538,18 @@ async function run_batches(batches, callback, labels, test_play) {
       catch (e) { if (next) { try { await next; } catch (e2) { /* the first failure is reported */ } } drop_pipe_contexts(nat); throw e; }
       if (start_err) { drop_pipe_contexts(nat); throw start_err; }
       rows += res.meta.length / 8; segments += res.segments.length / 4; done++;
-      if (!test_play && callback && !stop_requested) {                                        // ref @B24762: silent when test_play
+      if (!test_play && (callback || pred) && !stop_requested) {                              // ref @B24762: silent when test_play
         const lb = labels[k] || [];
         for (let c = 0; c < lists[k].length && !stop_requested; c++) {
-          const cb = (si, label, t, f) => callback(si, label, t, f, c, k);
-          dispatch(res, c, cb, lb[c] || []);
+          const cb = callback ? (si, label, t, f) => callback(si, label, t, f, c, k) : null;
+          const pk = pred ? { model: pred.model, on_prediction: (si, lc, ci, per) => pred.on_prediction(si, lc, ci, per, k) } : null;
+          dispatch(res, c, cb, lb[c] || [], pk, c);
         }
       }
+      if (meters) meters.push(Array.from({ length: lists[k].length }, (_, c) => meters_of(res, c, pred.model.labels)));
       if (stop_requested && next) { try { await next; } catch (e) { /* stopping */ } next = null; done++; break; }
     }
-    return { rows, segments, batches: done, stopped: stop_requested };
+    return Object.assign({ rows, segments, batches: done, stopped: stop_requested }, meters ? { meters } : {});
   } finally {
     playing = false;
   }
@@ -566,4 +685,4 @@ function set_predicted_label_for_segment(si, idx, label) {                      
 
 module.exports = { configure, LaunchAudioNodes, StopAudioNodes, set_predicted_label_for_segment, LaunchBatch, LaunchBatches,
   StreamOpen, STREAM_ACTIVE, STREAM_START, STREAM_STOP, shutdown, allocPinned, freePinned,
-  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats };
+  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, loadModel, setPredictionModel };

@@ -94,7 +94,15 @@ typedef struct {
     /* the context's own HIP stream (wsa_queue_create, made by the first processBatch): every job of the context runs on it, so that the jobs of TWO
      * contexts on one device overlap — the upload of one batch under the kernels of the other — instead of queueing on the device's null stream */
     void *queue;
+    struct model_box *models;     /* the classifier models created on this context (modelCreate): destroy() destroys them with it */
 } ctx_box;
+/* What JS holds for a model (wsa_model): like the context's box it outlives the model, so that a handle used after modelDestroy() or after its
+ * context's destroy() finds NULL; `busy` counts the jobs that classify with it (modelDestroy() refuses meanwhile) */
+typedef struct model_box { wsa_model *m; ctx_box *owner; uint32_t busy, n_classes; struct model_box *next; } model_box;
+static void model_unlink(model_box *mb) {
+    if (mb->owner) for (model_box **q = &mb->owner->models; *q; q = &(*q)->next) if (*q == mb) { *q = mb->next; break; }
+    mb->owner = NULL; mb->next = NULL;
+}
 static void box_drop_plan(ctx_box *b) {
     if (b->plan) wsa_batch_destroy(b->plan);
     free(b->plan_ns); b->plan = NULL; b->plan_ns = NULL; b->plan_n = 0;
@@ -143,6 +151,7 @@ static napi_value fn_destroy(napi_env env, napi_callback_info info) {
         for (uint32_t i = 0; i < g_gather_n; i++) if (g_gather_ctxs[i] == b->ctx) { gather_drop(); break; }      /* the communicator goes before its contexts */
         pthread_mutex_unlock(&g_gather_lock);
         box_drop_plan(b);
+        while (b->models) { model_box *mb = b->models; wsa_model_destroy(mb->m); mb->m = NULL; model_unlink(mb); }     /* models go before their context */
         if (b->queue) { wsa_queue_destroy(b->ctx, b->queue); b->queue = NULL; }
         wsa_destroy(b->ctx); b->ctx = NULL;
     }
@@ -236,6 +245,8 @@ typedef struct {
     int level; uint32_t trk_segs; uint64_t trk_np, trk_nr; uint64_t *trk_off; int32_t *trk_pts, *trk_rank;   /* level 3 */
     ctx_box *box;                 /* the JS handle's box: one child while the job runs */
     void *queue;                  /* the context's stream (ctx_box.queue) */
+    model_box *model;             /* classify the rows with it (levels 5 / 13), or NULL */
+    uint32_t n_classes, n_cb; float *prob; int32_t *cb, *cb_label; double *cb_conf, *clip_conf;
 } job_t;
 
 static void job_execute(napi_env env, void *data) {
@@ -298,6 +309,23 @@ static void job_execute(napi_env env, void *data) {
             j->st = wsa_batch_copy_tracks(b, j->queue, j->trk_off, j->trk_pts, ti.n_points, j->trk_rank, ti.n_ranked);
             if (j->st != WSA_OK) break;
         }
+        if (j->model) {                                       /* K6 (+ K6b at level 13) on the batch's rows: the app's classifier */
+            j->st = wsa_batch_classify(b, j->model->m, j->queue);
+            if (j->st != WSA_OK) break;
+            wsa_class_result cr;
+            j->st = wsa_batch_class_result(b, j->queue, &cr);
+            if (j->st != WSA_OK) break;
+            j->n_classes = cr.n_classes; j->n_cb = cr.n_callbacks;
+            j->prob = malloc(sizeof(float) * (size_t)cr.n_classes * (cr.n_rows ? cr.n_rows : 1));
+            j->cb = malloc(sizeof(int32_t) * 4 * (size_t)(cr.n_callbacks ? cr.n_callbacks : 1));
+            j->cb_label = malloc(sizeof(int32_t) * (size_t)(cr.n_callbacks ? cr.n_callbacks : 1));
+            j->cb_conf = malloc(sizeof(double) * (size_t)(cr.n_callbacks ? cr.n_callbacks : 1));
+            j->clip_conf = malloc(sizeof(double) * (size_t)cr.n_classes * (j->n_clips ? j->n_clips : 1));
+            if (!j->prob || !j->cb || !j->cb_label || !j->cb_conf || !j->clip_conf) { j->st = WSA_ERR_INVALID; snprintf(j->err, sizeof j->err, "out of memory"); return; }
+            memset(j->clip_conf, 0, sizeof(double) * (size_t)cr.n_classes * j->n_clips);
+            j->st = wsa_batch_copy_classes(b, j->queue, j->prob, cr.n_rows ? cr.n_rows : 1, j->cb, j->cb_label, j->cb_conf, cr.n_callbacks ? cr.n_callbacks : 1, j->clip_conf);
+            if (j->st != WSA_OK) break;
+        }
         wsa_batch_stage_ms(b, j->stage_ms);
     } while (0);
     if (j->st != WSA_OK) snprintf(j->err, sizeof j->err, "%s", wsa_last_error(j->ctx));
@@ -315,6 +343,7 @@ static napi_value make_typed(napi_env env, napi_typedarray_type type, const void
 static void job_complete(napi_env env, napi_status status, void *data) {
     job_t *j = (job_t *)data;
     if (j->box && j->box->children) j->box->children--;
+    if (j->model && j->model->busy) j->model->busy--;
     if (j->plan) {                       /* keep the plan for the next call of the same shape (one entry; a failed run drops it) */
         if (j->box && j->box->ctx && j->st == WSA_OK && !j->box->plan) {
             j->box->plan = j->plan; j->box->plan_n = j->n_clips; j->box->plan_fs = j->fs; j->box->plan_fs_out = j->fs_out;
@@ -357,18 +386,37 @@ static void job_complete(napi_env env, napi_status status, void *data) {
             napi_set_named_property(env, o, "formants", make_typed(env, napi_float32_array, j->formants, (size_t)j->n_frames * 9, 4));
             napi_set_named_property(env, o, "frameOff", make_typed(env, napi_uint32_array, j->frame_off, (size_t)j->n_clips + 1, 4));
         }
+        if (j->prob) {                    /* the classifier's tables (include/wsa.h wsa_batch_copy_classes) */
+            napi_value nc; napi_create_uint32(env, j->n_classes, &nc); napi_set_named_property(env, o, "nClasses", nc);
+            napi_set_named_property(env, o, "prob", make_typed(env, napi_float32_array, j->prob, (size_t)j->n_rows * j->n_classes, 4));
+            napi_set_named_property(env, o, "cb", make_typed(env, napi_int32_array, j->cb, (size_t)j->n_cb * 4, 4));
+            napi_set_named_property(env, o, "cbLabel", make_typed(env, napi_int32_array, j->cb_label, (size_t)j->n_cb, 4));
+            napi_set_named_property(env, o, "cbConf", make_typed(env, napi_float64_array, j->cb_conf, (size_t)j->n_cb, 8));
+            napi_set_named_property(env, o, "clipConf", make_typed(env, napi_float64_array, j->clip_conf, (size_t)j->n_clips * j->n_classes, 8));
+        }
         napi_resolve_deferred(env, j->deferred, o);
     }
     napi_delete_async_work(env, j->work);
+    free(j->prob); free(j->cb); free(j->cb_label); free(j->cb_conf); free(j->clip_conf);
     free(j->meta); free(j->feat); free(j->segs); free(j->row_off); free(j->seg_off); free(j->formants); free(j->frame_off); free(j->utt_meta); free(j->utt_feat); free(j->utt_off); free(j->trk_off); free(j->trk_pts); free(j->trk_rank);
     free(j->n_samples); free((void *)j->pcm); free(j->clip_refs); free(j->channels); free(j);
 }
 
 static napi_value fn_process_batch(napi_env env, napi_callback_info info) {
-    size_t argc = 7; napi_value argv[7];
+    size_t argc = 8; napi_value argv[8];
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     wsa_ctx *ctx = argc ? get_ctx(env, argv[0]) : NULL;
     bool is_arr = false; double fs = 0; uint32_t n = 0;
+    model_box *mb = NULL;                                        /* 8th argument: a model of modelCreate on this context (classify the rows), or undefined / null */
+    if (argc >= 8) {
+        napi_valuetype t; napi_typeof(env, argv[7], &t);
+        if (t != napi_undefined && t != napi_null) {
+            void *p = NULL;
+            if (t != napi_external || napi_get_value_external(env, argv[7], &p) != napi_ok || !((model_box *)p)->m) { napi_throw_error(env, NULL, "processBatch: the model handle was destroyed (or is not a model)"); return NULL; }
+            mb = (model_box *)p;
+            if (!ctx || mb->owner != get_box(env, argv[0])) { napi_throw_error(env, NULL, "processBatch: the model belongs to another context"); return NULL; }
+        }
+    }
     if (!ctx || argc < 3 || napi_is_array(env, argv[1], &is_arr) != napi_ok || !is_arr ||
         napi_get_value_double(env, argv[2], &fs) != napi_ok || napi_get_array_length(env, argv[1], &n) != napi_ok) {
         napi_throw_type_error(env, NULL, "processBatch(ctx, Float32Array[] | Int16Array[], fs[, level[, analysisRate[, channels[, deferRows]]]])"); return NULL;
@@ -376,7 +424,7 @@ static napi_value fn_process_batch(napi_env env, napi_callback_info info) {
     job_t *j = calloc(1, sizeof *j);
     if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
     if (argc >= 7) { bool d = false; if (napi_get_value_bool(env, argv[6], &d) == napi_ok) j->defer_rows = d ? 1 : 0; }
-    j->ctx = ctx; j->fs = fs; j->n_clips = n; j->box = get_box(env, argv[0]);
+    j->ctx = ctx; j->fs = fs; j->n_clips = n; j->box = get_box(env, argv[0]); j->model = mb;
     if (argc >= 4) { int32_t lv = 0; if (napi_get_value_int32(env, argv[3], &lv) == napi_ok) j->level = lv; }
     if (argc >= 5) { double fo = 0; if (napi_get_value_double(env, argv[4], &fo) == napi_ok) j->fs_out = fo; }           /* analysis rate */   /* the ctx's output_level: 3 adds the raw tracks */
     j->n_samples = calloc(n ? n : 1, sizeof(uint32_t)); j->pcm = calloc(n ? n : 1, sizeof(float *)); j->clip_refs = calloc(n ? n : 1, sizeof(napi_ref));
@@ -418,6 +466,7 @@ static napi_value fn_process_batch(napi_env env, napi_callback_info info) {
     NAPI_OK(env, napi_create_async_work(env, NULL, name, job_execute, job_complete, j, &j->work));
     NAPI_OK(env, napi_queue_async_work(env, j->work));
     j->box->children++;                                          /* until job_complete */
+    if (mb) mb->busy++;
     return promise;
 }
 
@@ -605,13 +654,85 @@ static napi_value fn_stream_close(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* ---- the app's classifier: modelCreate(ctx, {units, activation, kernels, biases, inMin, inMax, labels}) -> handle (wsa_model_create);
+ * modelDestroy(handle).  The handle is a box: after modelDestroy() or its context's destroy() any use throws instead of touching freed memory. */
+static void model_finalize(napi_env env, void *data, void *hint) {
+    model_box *mb = (model_box *)data;
+    if (!mb->m && !mb->owner) free(mb);              /* a live model stays (explicit destroy only, as contexts) */
+}
+static int typed_of(napi_env env, napi_value o, const char *name, napi_typedarray_type want, void **data, size_t *len) {
+    napi_value v; bool ta = false; napi_typedarray_type t;
+    if (napi_get_named_property(env, o, name, &v) != napi_ok || napi_is_typedarray(env, v, &ta) != napi_ok || !ta) return 0;
+    if (napi_get_typedarray_info(env, v, &t, len, data, NULL, NULL) != napi_ok || t != want) return 0;
+    return 1;
+}
+static napi_value fn_model_create(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ctx_box *box = argc ? get_box(env, argv[0]) : NULL;
+    const char *usage = "modelCreate(ctx, {units: Int32Array, activation: Int32Array, kernels: Float32Array[], biases: Float32Array[], inMin: Float64Array, inMax: Float64Array, labels: string[]})";
+    if (!box || !box->ctx || argc < 2) { napi_throw_type_error(env, NULL, usage); return NULL; }
+    int32_t *units = NULL, *act = NULL; double *mn = NULL, *mx = NULL; size_t nu = 0, na = 0, nmn = 0, nmx = 0;
+    if (!typed_of(env, argv[1], "units", napi_int32_array, (void **)&units, &nu) || !typed_of(env, argv[1], "activation", napi_int32_array, (void **)&act, &na) ||
+        !typed_of(env, argv[1], "inMin", napi_float64_array, (void **)&mn, &nmn) || !typed_of(env, argv[1], "inMax", napi_float64_array, (void **)&mx, &nmx) ||
+        nu < 2 || na != nu - 1 || na > WSA_MODEL_MAX_LAYERS || nmn != WSA_NFEAT || nmx != WSA_NFEAT) { napi_throw_type_error(env, NULL, usage); return NULL; }
+    napi_value ka, ba; bool ia = false, ib = false; uint32_t nk = 0, nb = 0;
+    if (napi_get_named_property(env, argv[1], "kernels", &ka) != napi_ok || napi_is_array(env, ka, &ia) != napi_ok || !ia || napi_get_array_length(env, ka, &nk) != napi_ok ||
+        napi_get_named_property(env, argv[1], "biases", &ba) != napi_ok || napi_is_array(env, ba, &ib) != napi_ok || !ib || napi_get_array_length(env, ba, &nb) != napi_ok ||
+        nk != na || nb != na) { napi_throw_type_error(env, NULL, usage); return NULL; }
+    const float *kp[WSA_MODEL_MAX_LAYERS], *bp[WSA_MODEL_MAX_LAYERS];
+    for (uint32_t l = 0; l < na; l++) {
+        napi_value kv, bv; bool t1 = false, t2 = false; napi_typedarray_type tk, tb; size_t lk = 0, lb = 0; void *dk = NULL, *db = NULL;
+        if (napi_get_element(env, ka, l, &kv) != napi_ok || napi_is_typedarray(env, kv, &t1) != napi_ok || !t1 || napi_get_typedarray_info(env, kv, &tk, &lk, &dk, NULL, NULL) != napi_ok ||
+            napi_get_element(env, ba, l, &bv) != napi_ok || napi_is_typedarray(env, bv, &t2) != napi_ok || !t2 || napi_get_typedarray_info(env, bv, &tb, &lb, &db, NULL, NULL) != napi_ok ||
+            tk != napi_float32_array || tb != napi_float32_array || lk != (size_t)units[l] * (size_t)units[l + 1] || lb != (size_t)units[l + 1]) {
+            napi_throw_type_error(env, NULL, "modelCreate: kernels[i] must be a Float32Array of units[i] x units[i+1], biases[i] one of units[i+1]"); return NULL;
+        }
+        kp[l] = (const float *)dk; bp[l] = (const float *)db;
+    }
+    /* labels (optional): strings, legend order */
+    char **labels = NULL; uint32_t nl = 0;
+    { napi_value la; bool il = false;
+      if (napi_get_named_property(env, argv[1], "labels", &la) == napi_ok && napi_is_array(env, la, &il) == napi_ok && il && napi_get_array_length(env, la, &nl) == napi_ok && nl == (uint32_t)units[na]) {
+          labels = calloc(nl, sizeof(char *));
+          for (uint32_t i = 0; labels && i < nl; i++) {
+              napi_value e; size_t len = 0;
+              if (napi_get_element(env, la, i, &e) != napi_ok || napi_get_value_string_utf8(env, e, NULL, 0, &len) != napi_ok) { len = 0; labels[i] = calloc(1, 1); continue; }
+              labels[i] = calloc(len + 1, 1);
+              if (labels[i]) napi_get_value_string_utf8(env, e, labels[i], len + 1, &len);
+          }
+      } else nl = 0; }
+    wsa_model_desc d = {(int32_t)na, units, act, kp, bp, mn, mx, (const char *const *)labels};
+    wsa_model *m = NULL;
+    const wsa_status st = wsa_model_create(box->ctx, &d, &m);
+    for (uint32_t i = 0; labels && i < nl; i++) free(labels[i]);
+    free(labels);
+    if (st != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(box->ctx)); return NULL; }
+    model_box *mb = calloc(1, sizeof *mb);
+    if (!mb) { wsa_model_destroy(m); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    mb->m = m; mb->owner = box; mb->n_classes = (uint32_t)units[na]; mb->next = box->models; box->models = mb;
+    napi_value ext; NAPI_OK(env, napi_create_external(env, mb, model_finalize, NULL, &ext));
+    return ext;
+}
+static napi_value fn_model_destroy(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1]; void *p = NULL;
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 1 || napi_get_value_external(env, argv[0], &p) != napi_ok || !p) { napi_throw_type_error(env, NULL, "modelDestroy(model)"); return NULL; }
+    model_box *mb = (model_box *)p;
+    if (mb->busy) { napi_throw_error(env, NULL, "the model is in use by a batch in flight"); return NULL; }
+    if (mb->m) { wsa_model_destroy(mb->m); mb->m = NULL; }
+    model_unlink(mb);
+    return NULL;
+}
+
 NAPI_MODULE_INIT() {
     /* the structures below follow the header this file was compiled against: refuse a libwsa.so of another ABI version */
     if (wsa_abi_version() != WSA_ABI_VERSION) { napi_throw_error(env, NULL, "libwsa.so ABI version differs from the one wsa_napi.node was built against (include/wsa.h): rebuild"); return NULL; }
     const struct { const char *name; napi_callback fn; } fns[] = {
         {"abiVersion", fn_abi_version}, {"freePinned", fn_free_pinned}, {"defaults", fn_defaults}, {"create", fn_create}, {"destroy", fn_destroy},
         {"geometry", fn_geometry}, {"allocPinned", fn_alloc_pinned}, {"binsHz", fn_bins_hz}, {"processBatch", fn_process_batch}, {"gatherRows", fn_gather_rows},
-        {"streamOpen", fn_stream_open}, {"streamInput", fn_stream_input}, {"streamStep", fn_stream_step}, {"streamClose", fn_stream_close}};
+        {"streamOpen", fn_stream_open}, {"streamInput", fn_stream_input}, {"streamStep", fn_stream_step}, {"streamClose", fn_stream_close},
+        {"modelCreate", fn_model_create}, {"modelDestroy", fn_model_destroy}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

@@ -1,0 +1,100 @@
+"""The reference application's trained classifiers (dist/nnmodel/<db>/cats_<label>/ — model.json, model_meta.json,
+model.weights.bin as ml5 0.6.0 saves them) parsed into what wsa_model_create takes.  Pure Python: no device needed."""
+import json
+import os
+
+import numpy as np
+
+NFEAT = 53
+ACT = {"linear": 0, "relu": 1, "sigmoid": 2, "tanh": 3, "softmax": 4}
+MAX_LAYERS, MAX_WIDTH, MAX_CLASSES = 8, 1024, 64
+
+
+class ModelFormatError(ValueError):
+    pass
+
+
+class ModelSpec:
+    """units [n_layers + 1], activation names, kernels [in][out] f32, biases f32, in_min / in_max f64, labels (legend order)."""
+
+    def __init__(self, units, activations, kernels, biases, in_min, in_max, labels):
+        self.units, self.activations, self.kernels, self.biases = units, activations, kernels, biases
+        self.in_min, self.in_max, self.labels = in_min, in_max, labels
+
+    @property
+    def n_classes(self):
+        return self.units[-1]
+
+
+def parse(model_json, meta_json, weights):
+    """model_json / meta_json: dicts or JSON text; weights: the bytes of model.weights.bin.  Raises ModelFormatError."""
+    mj = json.loads(model_json) if isinstance(model_json, (str, bytes)) else model_json
+    meta = json.loads(meta_json) if isinstance(meta_json, (str, bytes)) else meta_json
+    try:
+        topo = mj["modelTopology"]
+        layers = topo["config"]["layers"] if isinstance(topo["config"], dict) else topo["config"]
+        manifest = [w for group in mj["weightsManifest"] for w in group["weights"]]
+    except (KeyError, TypeError) as e:
+        raise ModelFormatError(f"model.json: no modelTopology / weightsManifest ({e})")
+    if topo.get("class_name") != "Sequential":
+        raise ModelFormatError(f"model.json: a {topo.get('class_name')} model; only Sequential stacks of Dense layers are supported")
+    if not 1 <= len(layers) <= MAX_LAYERS:
+        raise ModelFormatError(f"model.json: {len(layers)} layers (1 .. {MAX_LAYERS} supported)")
+    acts = []
+    for i, l in enumerate(layers):
+        if l.get("class_name") != "Dense":
+            raise ModelFormatError(f"model.json: layer {i} is {l.get('class_name')}; only Dense layers are supported")
+        a = l["config"].get("activation", "linear")
+        if a not in ACT:
+            raise ModelFormatError(f"model.json: layer {i} has activation {a!r}")
+        if a == "softmax" and i != len(layers) - 1:
+            raise ModelFormatError("model.json: softmax is only supported on the last layer")
+        if not l["config"].get("use_bias", True):
+            raise ModelFormatError(f"model.json: layer {i} has no bias")
+        acts.append(a)
+    if len(manifest) != 2 * len(layers):
+        raise ModelFormatError(f"weightsManifest lists {len(manifest)} tensors for {len(layers)} Dense layers (kernel + bias each)")
+    total = 0
+    for w in manifest:
+        if w.get("dtype", "float32") != "float32":
+            raise ModelFormatError(f"weight {w.get('name')}: dtype {w.get('dtype')} (float32 only)")
+        total += int(np.prod(w["shape"])) * 4
+    weights = bytes(weights)
+    if len(weights) != total:
+        raise ModelFormatError(f"model.weights.bin holds {len(weights)} bytes, the weightsManifest needs {total}")
+    units = [int(manifest[0]["shape"][0])]
+    kernels, biases, off = [], [], 0
+    for i in range(len(layers)):
+        ks, bs = manifest[2 * i]["shape"], manifest[2 * i + 1]["shape"]
+        if len(ks) != 2 or ks[0] != units[-1] or bs != [ks[1]] or ks[1] != layers[i]["config"]["units"]:
+            raise ModelFormatError(f"layer {i}: kernel {ks} / bias {bs} do not chain from {units[-1]} inputs to {layers[i]['config']['units']} units")
+        k = np.frombuffer(weights, "<f4", ks[0] * ks[1], off).reshape(ks).copy(); off += k.nbytes
+        b = np.frombuffer(weights, "<f4", bs[0], off).copy(); off += b.nbytes
+        kernels.append(k); biases.append(b); units.append(int(ks[1]))
+    if units[0] != NFEAT:
+        raise ModelFormatError(f"the model takes {units[0]} inputs; the feature rows have {NFEAT}")
+    if max(units[1:]) > MAX_WIDTH or units[-1] > MAX_CLASSES:
+        raise ModelFormatError(f"layer widths {units[1:]} exceed {MAX_WIDTH} (or more than {MAX_CLASSES} outputs)")
+    try:
+        ins = meta["inputs"]
+        in_min = np.array([float(ins[str(i)]["min"]) for i in range(NFEAT)])
+        in_max = np.array([float(ins[str(i)]["max"]) for i in range(NFEAT)])
+        legend = list(meta["outputs"]["y"]["legend"].keys()) if "y" in meta["outputs"] else list(next(iter(meta["outputs"].values()))["legend"].keys())
+    except (KeyError, TypeError, StopIteration) as e:
+        raise ModelFormatError(f"model_meta.json: no inputs '0'..'52' min / max or output legend ({e})")
+    if not (np.all(np.isfinite(in_min)) and np.all(np.isfinite(in_max))):
+        raise ModelFormatError("model_meta.json: non-finite input range")
+    if acts[-1] == "softmax" and len(legend) != units[-1]:
+        raise ModelFormatError(f"model_meta.json: {len(legend)} legend labels for {units[-1]} outputs")
+    return ModelSpec(units, acts, kernels, biases, in_min, in_max, legend)
+
+
+def load_dir(path):
+    """A directory as the app ships it: model.json, model_meta.json, model.weights.bin (the manifest's path)."""
+    with open(os.path.join(path, "model.json")) as f:
+        mj = json.load(f)
+    with open(os.path.join(path, "model_meta.json")) as f:
+        meta = json.load(f)
+    paths = [p for g in mj.get("weightsManifest", []) for p in g.get("paths", [])] or ["model.weights.bin"]
+    data = b"".join(open(os.path.join(path, os.path.basename(p)), "rb").read() for p in paths)
+    return parse(mj, meta, data)
