@@ -394,6 +394,33 @@ wsa_status wsa_batch_class_result(wsa_batch *b, void *stream, wsa_class_result *
 wsa_status wsa_batch_copy_classes(wsa_batch *b, void *stream, float *prob, uint32_t rows_cap, int32_t *cb, int32_t *cb_label, double *cb_conf,
                                   uint32_t cb_cap, double *clip_conf);
 
+/*
+ * ---- Classification inside the stream step (additions within version 5: probe for wsa_stream_set_model).
+ * The app's live path (ref src/prediction.js:47: predict_by_multiple_syllables after every level-13 callback of a live source, the
+ * per-launch Label_conf_all behind the meters) for every stream of a wsa_stream: K6 on each step's rows and, at level 13, the fold with
+ * one accumulator per stream carried on the device from step to step.  Both are kernels of the step, so a step stays one graph launch
+ * and its results arrive through the step's mapped pinned buffers.
+ *   - One accumulator per stream (Label_conf_all and the order its labels were added in), reset by START — a START step's rows
+ *     already belong to the new launch — untouched on idle steps, kept after STOP until the stream's next START.
+ *   - STOP-flush rows and the rows of cut spans (WSA_FLAG_STREAM_CUT) are classified like any others.
+ *   - wsa_stream_time_steps times the step with the classifier in it when one is attached.
+ */
+/* Attach (m != NULL) or detach (NULL) a classifier.  Levels 5 / 13 only; level 13 needs a softmax model; same context.
+ * Synchronises the last step, (re)allocates the class tables, zeroes every stream's accumulator and drops the captured graph
+ * (the next step recaptures with the classifier in it).  The model must outlive its attachment. */
+wsa_status wsa_stream_set_model(wsa_stream *st, const wsa_model *m);
+typedef struct {
+    uint32_t n_rows, n_classes, n_callbacks, n_streams;
+    const float   *prob;         /* [n_rows][n_classes], rows in wsa_stream_rows order */
+    const int32_t *cb;           /* [n_callbacks][4] = {stream, si, first row, rows} (level 13; else 0 / NULL) */
+    const int32_t *cb_label;     /* as wsa_class_result: -1 = null, -2 = no prediction */
+    const double  *cb_conf;
+    const double  *stream_conf;  /* [n_streams][n_classes] Label_conf_all since each stream's START (level 13), 0 for labels never added */
+} wsa_stream_class_result;
+/* After wsa_stream_collect of the same step: host memory owned by the stream object, valid until the next step.
+ * WSA_ERR_INVALID without an attached model. */
+wsa_status wsa_stream_classes(wsa_stream *st, wsa_stream_class_result *out);
+
 #ifdef __cplusplus
 }
 #endif

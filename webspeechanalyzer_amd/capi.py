@@ -96,6 +96,12 @@ class _ClassResult(ctypes.Structure):
                 ("d_cb_conf", ctypes.c_void_p), ("d_clip_conf", ctypes.c_void_p)]
 
 
+class _StreamClassResult(ctypes.Structure):
+    _fields_ = [("n_rows", ctypes.c_uint32), ("n_classes", ctypes.c_uint32), ("n_callbacks", ctypes.c_uint32), ("n_streams", ctypes.c_uint32),
+                ("prob", ctypes.c_void_p), ("cb", ctypes.c_void_p), ("cb_label", ctypes.c_void_p), ("cb_conf", ctypes.c_void_p),
+                ("stream_conf", ctypes.c_void_p)]
+
+
 # every symbol include/wsa.h declares (checked by tests/test_abi.py)
 ABI_VERSION = 5            # WSA_ABI_VERSION of include/wsa.h this binding's structures follow
 ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destroy", "wsa_last_error",
@@ -109,7 +115,9 @@ ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destr
                "wsa_batch_keep_spectra", "wsa_batch_backend_reruns", "wsa_stream_time_steps", "wsa_batch_run_host_i16",
                "wsa_gather_create", "wsa_gather_destroy", "wsa_gather_rows", "wsa_gather_copy_rows", "wsa_host_alloc", "wsa_host_free", "wsa_queue_create", "wsa_queue_destroy",
                # additions within version 5 (probe for wsa_model_create): the app's syllable classifier
-               "wsa_model_create", "wsa_model_destroy", "wsa_classify_rows", "wsa_batch_classify", "wsa_batch_class_result", "wsa_batch_copy_classes"]
+               "wsa_model_create", "wsa_model_destroy", "wsa_classify_rows", "wsa_batch_classify", "wsa_batch_class_result", "wsa_batch_copy_classes",
+               # additions within version 5 (probe for wsa_stream_set_model): the classifier inside the stream step
+               "wsa_stream_set_model", "wsa_stream_classes"]
 
 _LIB = None
 
@@ -198,6 +206,8 @@ def lib():
     L.wsa_batch_classify.argtypes = [vp, vp, vp]
     L.wsa_batch_class_result.argtypes = [vp, vp, ctypes.POINTER(_ClassResult)]
     L.wsa_batch_copy_classes.argtypes = [vp, vp, vp, u32, vp, vp, vp, u32, vp]
+    L.wsa_stream_set_model.argtypes = [vp, vp]
+    L.wsa_stream_classes.argtypes = [vp, ctypes.POINTER(_StreamClassResult)]
     for name in ABI_SYMBOLS:
         if name not in ("wsa_abi_version", "wsa_last_error", "wsa_config_default", "wsa_destroy", "wsa_batch_destroy", "wsa_resample_length",
                         "wsa_stream_destroy", "wsa_stream_samples_per_step", "wsa_stream_host_input", "wsa_gather_destroy", "wsa_host_free",
@@ -627,6 +637,30 @@ class Streams:
             fptr, fk = feed.ctypes.data, feed.shape[0]
         self.an._check(self.L.wsa_stream_time_steps(self.h, int(n_steps), fptr, int(fk), stream, out.ctypes.data, ctypes.byref(rows)))
         return out, rows.value
+
+    def set_model(self, model):
+        """Attach a Model (K6 on every step's rows; at level 13 the fold, one accumulator per stream reset by START) or detach (None).
+        The next step recaptures the graph."""
+        self.an._check(self.L.wsa_stream_set_model(self.h, model.h if model is not None else None))
+        self._model = model
+
+    def classes(self):
+        """After collect(): host copies of the step's classification, dict(prob [n_rows, C] f32, cb [n_cb, 4] i32 = {stream, si, first row,
+        rows}, cb_label [n_cb] i32 (-1: null, -2: not predicted), cb_conf [n_cb] f64, stream_conf [n, C] f64 = Label_conf_all since each
+        stream's START, labels).  Level 5: cb / cb_label / cb_conf / stream_conf are None."""
+        r = _StreamClassResult()
+        self.an._check(self.L.wsa_stream_classes(self.h, ctypes.byref(r)))
+        n, C, k = int(r.n_rows), int(r.n_classes), int(r.n_callbacks)
+
+        def arr(ptr, ctype, dtype, shape):
+            if not ptr:
+                return None
+            if not int(np.prod(shape)):
+                return np.zeros(shape, dtype)
+            return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctype)), shape=shape).copy()
+        return dict(prob=arr(r.prob, ctypes.c_float, np.float32, (n, C)), cb=arr(r.cb, ctypes.c_int32, np.int32, (k, 4)),
+                    cb_label=arr(r.cb_label, ctypes.c_int32, np.int32, (k,)), cb_conf=arr(r.cb_conf, ctypes.c_double, np.float64, (k,)),
+                    stream_conf=arr(r.stream_conf, ctypes.c_double, np.float64, (int(r.n_streams), C)), labels=list(self._model.labels))
 
     def collect(self, stream=0):
         """Rows of the last step: dict(meta [n,8] i32, feat [n,53] f64, segments [m,4] i32) (copies)."""

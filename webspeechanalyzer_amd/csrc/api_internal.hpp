@@ -33,5 +33,18 @@ void wsa_batch_view_internal(wsa_batch* b, wsa_batch_view* v);
 wsa_status wsa_batch_fetch_internal(wsa_batch* b, hipStream_t s);
 }              // fetch_totals: synchronise, read the counters (reruns the back end on a table overflow)
 
+// classify.hip also runs K6 / K6b inside a stream object's step (wsa_stream_set_model); stream_api.hip owns the stream object
+struct wsa_scls;                                // classification state of one stream object: class tables, carried fold, pinned D2H tables
+struct wsa_scls_view {
+    wsa_ctx* ctx; int level; uint32_t n_streams, rows_cap, d2h_rows;
+    const int32_t* d_meta; const double* d_feat; const uint32_t* d_row_off;     // the step's compacted rows, d_row_off [n_streams + 1]
+    const uint32_t* d_totals;                                                   // [0] = rows of the step, on the device
+    const uint32_t* d_bits;                                                     // per stream control word of the step (bit 0: START)
+};
+wsa_status wsa_scls_create(const wsa_scls_view& v, const wsa_model* m, wsa_scls** out);   // checks the model, allocates, zeroes the fold state
+void wsa_scls_free(wsa_scls* c);
+wsa_status wsa_scls_enqueue(wsa_scls* c, hipStream_t s);                                   // part of enqueue_step (captured)
+wsa_status wsa_scls_result(wsa_scls* c, uint32_t rows, wsa_stream_class_result* out);    // after the step completed
+
 #define HIP_TRY(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
         return wsa_api::fail((ctx), WSA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)

@@ -151,6 +151,54 @@ __device__ __forceinline__ long long wave_min_ll(long long v) {
     return v;
 }
 
+// what one clip's (or stream's) fold carries from callback to callback, per lane = class
+struct FoldAcc {
+    double acc_all;                          // Label_conf_all[label]
+    bool in_all;                             // the label is a key of Label_conf_all
+    long long first;                         // its insertion stamp
+    long long stamp;
+};
+
+// one callback: rows r .. e - 1 (the same clip / stream and si); label -1 / -2 as wsa_class_result
+__device__ __forceinline__ void fold_callback(const int32_t* meta, const float* prob, uint32_t C, double step_s, int lane, bool cls, int kr,
+                                              uint32_t r, uint32_t e, FoldAcc& a, int& label, double& conf) {
+    const uint32_t nsyl = e - r;
+    double seg_weight = 0.0;                 // sum of parseFloat(seg_time[ph][1]) (ref prediction.js:55)
+    for (uint32_t q = r; q < e; q++) seg_weight += fixed3((double)(meta[(size_t)q * 8 + 3] + 1) * step_s);
+    label = -2; conf = 0.0;
+    if (!(seg_weight > 0.0)) return;
+    double acc_seg = 0.0; bool in_seg = false;
+    for (uint32_t q = r; q < e; q++) {
+        const double w = __dsqrt_rn(fixed3((double)(meta[(size_t)q * 8 + 3] + 1) * step_s));
+        const float pf = cls ? prob[(size_t)q * C + lane] : 0.f;
+        // rank in classifyMultiple's order: confidence descending, ties in legend order (a stable sort)
+        int rank = 0;
+        for (int j = 0; j < (int)C; j++) {
+            const float pj = __shfl(pf, j);
+            rank += (pj > pf || (pj == pf && j < lane)) ? 1 : 0;
+        }
+        const bool add = cls && (nsyl > 1 || rank == 0);   // one syllable: only result_out[0] (the one-input quirk)
+        if (add) {
+            const double wc = (double)pf * w;
+            // `if(!acc[label]) acc[label] = wconf; else acc[label] += wconf;` — a present 0 or NaN is overwritten
+            acc_seg = (in_seg && acc_seg != 0.0 && acc_seg == acc_seg) ? acc_seg + wc : wc; in_seg = true;
+            a.acc_all = (a.in_all && a.acc_all != 0.0 && a.acc_all == a.acc_all) ? a.acc_all + wc : wc;
+            if (!a.in_all) { a.in_all = true; a.first = a.stamp + rank; }
+        }
+        a.stamp += C;
+    }
+    // segment label: keys of Label_conf_all in Object.keys order, the first whose segment sum exceeds the running maximum (from 0)
+    const double v = (in_seg && acc_seg > 0.0) ? acc_seg : 0.0;
+    const double mx = wave_max_d(v);
+    const long long key = (kr >= 0) ? (long long)kr : ((1ll << 40) + a.first);
+    const long long best = wave_min_ll((in_seg && a.in_all && v == mx && mx > 0.0) ? key : 0x7fffffffffffffffll);
+    if (mx > 0.0) {
+        const unsigned long long hit = __ballot(cls && in_seg && a.in_all && v == mx && key == best);
+        label = (int)__ffsll(hit) - 1;
+    } else label = -1;
+    conf = mx / seg_weight;
+}
+
 __global__ void __launch_bounds__(256) fold_kernel(FoldParams p) {
     const int lane = threadIdx.x & 63;
     const uint32_t clip = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -158,57 +206,20 @@ __global__ void __launch_bounds__(256) fold_kernel(FoldParams p) {
     const uint32_t r0 = p.row_off[clip], r1 = p.row_off[clip + 1];
     const bool cls = (uint32_t)lane < p.C;
     const int kr = cls ? p.key_rank[lane] : -1;
-    double acc_all = 0.0;                    // Label_conf_all[label]
-    bool in_all = false;                     // the label is a key of Label_conf_all
-    long long first = 0;                     // its insertion stamp
-    long long stamp = 0;
+    FoldAcc a{0.0, false, 0, 0};
     uint32_t ncb = 0;
     for (uint32_t r = r0; r < r1;) {
         const int si = p.meta[(size_t)r * 8 + 1];
         uint32_t e = r + 1;
         while (e < r1 && p.meta[(size_t)e * 8 + 1] == si) e++;
-        const uint32_t nsyl = e - r;
-        double seg_weight = 0.0;             // sum of parseFloat(seg_time[ph][1]) (ref prediction.js:55)
-        for (uint32_t q = r; q < e; q++) seg_weight += fixed3((double)(p.meta[(size_t)q * 8 + 3] + 1) * p.step_s);
-        int label = -2; double conf = 0.0;
-        if (seg_weight > 0.0) {
-            double acc_seg = 0.0; bool in_seg = false;
-            for (uint32_t q = r; q < e; q++) {
-                const double w = __dsqrt_rn(fixed3((double)(p.meta[(size_t)q * 8 + 3] + 1) * p.step_s));
-                const float pf = cls ? p.prob[(size_t)q * p.C + lane] : 0.f;
-                // rank in classifyMultiple's order: confidence descending, ties in legend order (a stable sort)
-                int rank = 0;
-                for (int j = 0; j < (int)p.C; j++) {
-                    const float pj = __shfl(pf, j);
-                    rank += (pj > pf || (pj == pf && j < lane)) ? 1 : 0;
-                }
-                const bool add = cls && (nsyl > 1 || rank == 0);   // one syllable: only result_out[0] (the one-input quirk)
-                if (add) {
-                    const double wc = (double)pf * w;
-                    // `if(!acc[label]) acc[label] = wconf; else acc[label] += wconf;` — a present 0 or NaN is overwritten
-                    acc_seg = (in_seg && acc_seg != 0.0 && acc_seg == acc_seg) ? acc_seg + wc : wc; in_seg = true;
-                    acc_all = (in_all && acc_all != 0.0 && acc_all == acc_all) ? acc_all + wc : wc;
-                    if (!in_all) { in_all = true; first = stamp + rank; }
-                }
-                stamp += p.C;
-            }
-            // segment label: keys of Label_conf_all in Object.keys order, the first whose segment sum exceeds the running maximum (from 0)
-            const double v = (in_seg && acc_seg > 0.0) ? acc_seg : 0.0;
-            const double mx = wave_max_d(v);
-            const long long key = (kr >= 0) ? (long long)kr : ((1ll << 40) + first);
-            const long long best = wave_min_ll((in_seg && in_all && v == mx && mx > 0.0) ? key : 0x7fffffffffffffffll);
-            if (mx > 0.0) {
-                const unsigned long long hit = __ballot(cls && in_seg && in_all && v == mx && key == best);
-                label = (int)__ffsll(hit) - 1;
-            } else label = -1;
-            conf = mx / seg_weight;
-        }
-        if (lane == 0) { p.t_label[r] = label; p.t_conf[r] = conf; p.t_n[r] = (int32_t)nsyl; p.t_local[r] = (int32_t)ncb; }
+        int label; double conf;
+        fold_callback(p.meta, p.prob, p.C, p.step_s, lane, cls, kr, r, e, a, label, conf);
+        if (lane == 0) { p.t_label[r] = label; p.t_conf[r] = conf; p.t_n[r] = (int32_t)(e - r); p.t_local[r] = (int32_t)ncb; }
         for (uint32_t q = r + 1 + lane; q < e; q += 64) p.t_n[q] = 0;
         ncb++;
         r = e;
     }
-    if (cls) p.clip_conf[(size_t)clip * p.C + lane] = acc_all;
+    if (cls) p.clip_conf[(size_t)clip * p.C + lane] = a.acc_all;
     if (lane == 0) p.clip_cb[clip] = ncb;
 }
 
@@ -248,6 +259,62 @@ __global__ void __launch_bounds__(1024) fold_compact_kernel(uint32_t n_clips, co
         cb_label[k] = t_label[r]; cb_conf[k] = t_conf[r];
     }
     if (tid == 0) host[0] = s_base;
+}
+
+// ---- K6b on a stream step: one wave per stream, classes on lanes.  The fold's state (Label_conf_all, key insertion stamps) lives in
+// device memory from step to step, zeroed here when the step's control word has START (bit 0: the step's rows belong to the new launch).
+// Callbacks are written straight to their place in the step's table: a stream's first callback index is the number of callback starts
+// (a row whose stream or si differs from the row before) among the rows in front of it — a ballot over tens to hundreds of rows, instead
+// of a scan kernel.  Probabilities, callbacks and the per-stream sums go to the mapped pinned buffers (rows / callbacks below `cap`).
+struct StreamClsParams {
+    uint32_t n, C, cap; int fold; double step_s;
+    const int32_t* meta; const uint32_t* row_off; const float* prob; const int32_t* key_rank; const uint32_t* bits;
+    double* acc_all; int32_t* in_all; long long* first; long long* stamp;          // [n][C], [n][C], [n][C], [n]
+    int32_t* cb; int32_t* cb_label; double* cb_conf;                               // device: every callback of the step
+    float* h_prob; int32_t* h_cb; int32_t* h_cb_label; double* h_cb_conf; double* h_conf; uint32_t* h_count;   // mapped pinned
+};
+
+__global__ void __launch_bounds__(256) stream_classes_kernel(StreamClsParams p) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t s = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= p.n) return;
+    const uint32_t r0 = p.row_off[s], r1 = p.row_off[s + 1];
+    const uint32_t pe = (r1 < p.cap ? r1 : p.cap) * p.C;
+    for (uint32_t i = r0 * p.C + lane; i < pe; i += 64) p.h_prob[i] = p.prob[i];
+    if (!p.fold) return;
+    const bool cls = (uint32_t)lane < p.C;
+    const int kr = cls ? p.key_rank[lane] : -1;
+    const size_t sc = (size_t)s * p.C + lane;
+    FoldAcc a{0.0, false, 0, 0};
+    if (!(p.bits[s] & 1u)) {
+        if (cls) { a.acc_all = p.acc_all[sc]; a.in_all = p.in_all[sc] != 0; a.first = p.first[sc]; }
+        a.stamp = p.stamp[s];
+    }
+    uint32_t k = 0;
+    for (uint32_t q0 = 0; q0 < r0; q0 += 64) {
+        const uint32_t q = q0 + lane;
+        const bool start = q < r0 && (q == 0 || p.meta[(size_t)q * 8] != p.meta[(size_t)(q - 1) * 8] || p.meta[(size_t)q * 8 + 1] != p.meta[(size_t)(q - 1) * 8 + 1]);
+        k += (uint32_t)__popcll(__ballot(start));
+    }
+    for (uint32_t r = r0; r < r1;) {
+        const int si = p.meta[(size_t)r * 8 + 1];
+        uint32_t e = r + 1;
+        while (e < r1 && p.meta[(size_t)e * 8 + 1] == si) e++;
+        int label; double conf;
+        fold_callback(p.meta, p.prob, p.C, p.step_s, lane, cls, kr, r, e, a, label, conf);
+        if (lane == 0) {
+            p.cb[(size_t)k * 4 + 0] = (int32_t)s; p.cb[(size_t)k * 4 + 1] = si; p.cb[(size_t)k * 4 + 2] = (int32_t)r; p.cb[(size_t)k * 4 + 3] = (int32_t)(e - r);
+            p.cb_label[k] = label; p.cb_conf[k] = conf;
+            if (k < p.cap) {
+                p.h_cb[(size_t)k * 4 + 0] = (int32_t)s; p.h_cb[(size_t)k * 4 + 1] = si; p.h_cb[(size_t)k * 4 + 2] = (int32_t)r; p.h_cb[(size_t)k * 4 + 3] = (int32_t)(e - r);
+                p.h_cb_label[k] = label; p.h_cb_conf[k] = conf;
+            }
+        }
+        k++;
+        r = e;
+    }
+    if (cls) { p.acc_all[sc] = a.acc_all; p.in_all[sc] = a.in_all ? 1 : 0; p.first[sc] = a.first; p.h_conf[sc] = a.acc_all; }
+    if (lane == 0) { p.stamp[s] = a.stamp; if (s == p.n - 1) p.h_count[0] = k; }
 }
 
 }  // namespace
@@ -301,18 +368,21 @@ bool array_index_key(const char* s, int32_t* out) {       // "0", "17" (no sign,
     return true;
 }
 
-void launch_classify(const wsa_model* m, const double* feat, uint32_t n_rows, const uint32_t* d_n_rows, uint32_t rows_cap, float* prob, hipStream_t s) {
+// rows_cap sizes the grid (one workgroup per tile up to one per CU; the kernel strides over tiles beyond); rb = 16-row blocks per tile
+// (the model's own choice for batches; streams pass 1).  A row's probabilities do not depend on the tile it lands in.
+void launch_classify(const wsa_model* m, const double* feat, uint32_t n_rows, const uint32_t* d_n_rows, uint32_t rows_cap, float* prob, hipStream_t s, int rb = 0) {
     ClsParams p{};
     for (int l = 0; l < m->n_layers; l++) p.L[l] = m->L[l];
     p.n_layers = m->n_layers; p.C = m->C; p.S = m->S; p.in_min = m->d_min; p.in_max = m->d_max;
     p.feat = feat; p.n_rows = n_rows; p.d_n_rows = d_n_rows; p.prob = prob;
-    const int TM = 16 * m->rb;
+    if (rb <= 0 || rb > m->rb) rb = m->rb;
+    const int TM = 16 * rb;
     int n_cu = m->ctx->n_cu > 0 ? m->ctx->n_cu : 256;
     const uint32_t tiles = (rows_cap + TM - 1) / TM;
     const uint32_t grid = tiles < (uint32_t)n_cu ? (tiles ? tiles : 1) : (uint32_t)n_cu;
     const size_t lds = (size_t)2 * TM * m->S * sizeof(float);
-    if (m->rb == 4) hipLaunchKernelGGL(classify_kernel<4>, dim3(grid), dim3(CLS_THREADS), lds, s, p);
-    else if (m->rb == 2) hipLaunchKernelGGL(classify_kernel<2>, dim3(grid), dim3(CLS_THREADS), lds, s, p);
+    if (rb == 4) hipLaunchKernelGGL(classify_kernel<4>, dim3(grid), dim3(CLS_THREADS), lds, s, p);
+    else if (rb == 2) hipLaunchKernelGGL(classify_kernel<2>, dim3(grid), dim3(CLS_THREADS), lds, s, p);
     else hipLaunchKernelGGL(classify_kernel<1>, dim3(grid), dim3(CLS_THREADS), lds, s, p);
 }
 
@@ -335,7 +405,127 @@ wsa_status enqueue_batch(wsa_batch* b, const wsa_batch_view& v, wsa_cls* c, cons
     return WSA_OK;
 }
 
+// ---- streams (wsa_stream_set_model): K6 on every step's rows, the carried fold at level 13; everything allocated at attach time
+wsa_status stream_cls_check(wsa_ctx* ctx, int level, const wsa_model* m) {
+    if (level != 5 && level != 13)
+        return fail(ctx, WSA_ERR_INVALID, "wsa_stream_set_model needs streams at output_level 5 (segment features) or 13 (syllable features), not " + std::to_string(level));
+    if (m->ctx != ctx) return fail(ctx, WSA_ERR_INVALID, "the model was created on another context (or device) than the streams");
+    if (level == 13 && !m->softmax) return fail(ctx, WSA_ERR_INVALID, "the level-13 fold needs class probabilities: the model's last layer is not softmax");
+    return WSA_OK;
+}
+
 }  // namespace
+
+struct wsa_scls {
+    int device = 0;
+    const wsa_model* model = nullptr;
+    wsa_scls_view v{};
+    uint32_t C = 0;
+    float* d_prob = nullptr;
+    double *d_acc = nullptr, *d_cb_conf = nullptr; int32_t *d_in = nullptr, *d_cb = nullptr, *d_cb_label = nullptr; long long *d_first = nullptr, *d_stamp = nullptr;
+    std::vector<void*> allocs, pinned;
+    float *h_prob = nullptr, *h_prob_dev = nullptr;
+    int32_t *h_cb = nullptr, *h_cb_dev = nullptr, *h_cb_label = nullptr, *h_cb_label_dev = nullptr;
+    double *h_cb_conf = nullptr, *h_cb_conf_dev = nullptr, *h_conf = nullptr, *h_conf_dev = nullptr;
+    uint32_t *h_count = nullptr, *h_count_dev = nullptr;
+    std::vector<float> x_prob; std::vector<int32_t> x_cb, x_cb_label; std::vector<double> x_cb_conf;     // steps beyond the D2H window
+};
+
+void wsa_scls_free(wsa_scls* c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    for (void* q : c->allocs) (void)hipFree(q);
+    for (void* q : c->pinned) (void)hipHostFree(q);
+    delete c;
+}
+
+namespace {
+template <typename T>
+bool pin_to(wsa_scls* c, T** h, T** dev, size_t count) {
+    void* q = nullptr;
+    if (hipHostMalloc(&q, (count ? count : 1) * sizeof(T), hipHostMallocMapped) != hipSuccess) return false;
+    c->pinned.push_back(q);
+    std::memset(q, 0, (count ? count : 1) * sizeof(T));
+    *h = reinterpret_cast<T*>(q);
+    return hipHostGetDevicePointer(reinterpret_cast<void**>(dev), q, 0) == hipSuccess;
+}
+}  // namespace
+
+wsa_status wsa_scls_create(const wsa_scls_view& v, const wsa_model* m, wsa_scls** out) {
+    wsa_ctx* ctx = v.ctx;
+    *out = nullptr;
+    const wsa_status chk = stream_cls_check(ctx, v.level, m);
+    if (chk != WSA_OK) return chk;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    wsa_scls* c = new wsa_scls();
+    c->device = ctx->device; c->model = m; c->v = v; c->C = (uint32_t)m->C;
+    const size_t R = v.rows_cap ? v.rows_cap : 1, NC = (size_t)v.n_streams * c->C, W = v.d2h_rows ? v.d2h_rows : 1;
+    bool ok = alloc_to(c->allocs, &c->d_prob, R * c->C);
+    if (ok && v.level == 13) {
+        ok = alloc_to(c->allocs, &c->d_acc, NC) && alloc_to(c->allocs, &c->d_in, NC) && alloc_to(c->allocs, &c->d_first, NC)
+             && alloc_to(c->allocs, &c->d_stamp, (size_t)v.n_streams) && alloc_to(c->allocs, &c->d_cb, R * 4)
+             && alloc_to(c->allocs, &c->d_cb_label, R) && alloc_to(c->allocs, &c->d_cb_conf, R)
+             && hipMemset(c->d_acc, 0, NC * sizeof(double)) == hipSuccess && hipMemset(c->d_in, 0, NC * sizeof(int32_t)) == hipSuccess
+             && hipMemset(c->d_first, 0, NC * sizeof(long long)) == hipSuccess && hipMemset(c->d_stamp, 0, (size_t)v.n_streams * sizeof(long long)) == hipSuccess
+             && pin_to(c, &c->h_cb, &c->h_cb_dev, W * 4) && pin_to(c, &c->h_cb_label, &c->h_cb_label_dev, W)
+             && pin_to(c, &c->h_cb_conf, &c->h_cb_conf_dev, W) && pin_to(c, &c->h_conf, &c->h_conf_dev, NC) && pin_to(c, &c->h_count, &c->h_count_dev, 4);
+    }
+    ok = ok && pin_to(c, &c->h_prob, &c->h_prob_dev, W * c->C) && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) {
+        const std::string msg = std::string("device allocation failed: ") + hipGetErrorString(hipGetLastError());
+        wsa_scls_free(c);
+        return fail(ctx, WSA_ERR_HIP, msg);
+    }
+    *out = c;
+    return WSA_OK;
+}
+
+// K6 on the step's compacted rows (count on the device), then the stream fold / push: two kernel nodes of the captured step
+wsa_status wsa_scls_enqueue(wsa_scls* c, hipStream_t s) {
+    const wsa_scls_view& v = c->v;
+    const wsa_model* m = c->model;
+    // a step at config 5 has tens to hundreds of rows: tiles of 16 rows spread them over as many CUs as possible, and the grid covers the
+    // D2H window (1024 rows) in one pass — a larger step strides over its tiles instead of launching rows_cap / 16 mostly idle workgroups
+    launch_classify(m, v.d_feat, 0, v.d_totals, v.rows_cap < v.d2h_rows ? v.rows_cap : v.d2h_rows, c->d_prob, s, 1);
+    HIP_TRY(v.ctx, hipGetLastError());
+    StreamClsParams p{};
+    p.n = v.n_streams; p.C = c->C; p.cap = v.d2h_rows; p.fold = v.level == 13 ? 1 : 0; p.step_s = v.ctx->cfg.window_step / 1e3;
+    p.meta = v.d_meta; p.row_off = v.d_row_off; p.prob = c->d_prob; p.key_rank = m->d_key_rank; p.bits = v.d_bits;
+    p.acc_all = c->d_acc; p.in_all = c->d_in; p.first = c->d_first; p.stamp = c->d_stamp;
+    p.cb = c->d_cb; p.cb_label = c->d_cb_label; p.cb_conf = c->d_cb_conf;
+    p.h_prob = c->h_prob_dev; p.h_cb = c->h_cb_dev; p.h_cb_label = c->h_cb_label_dev; p.h_cb_conf = c->h_cb_conf_dev; p.h_conf = c->h_conf_dev; p.h_count = c->h_count_dev;
+    hipLaunchKernelGGL(stream_classes_kernel, dim3((v.n_streams + 3) / 4), dim3(256), 0, s, p);
+    HIP_TRY(v.ctx, hipGetLastError());
+    return WSA_OK;
+}
+
+// after the step has completed: the tables of `rows` rows; a step beyond the D2H window is fetched from the device here
+wsa_status wsa_scls_result(wsa_scls* c, uint32_t rows, wsa_stream_class_result* o) {
+    const wsa_scls_view& v = c->v;
+    wsa_ctx* ctx = v.ctx;
+    const bool fold = v.level == 13;
+    const uint32_t ncb = fold ? ((const volatile uint32_t*)c->h_count)[0] : 0u;
+    o->n_rows = rows; o->n_classes = c->C; o->n_callbacks = ncb; o->n_streams = v.n_streams;
+    o->prob = c->h_prob;
+    o->cb = fold ? c->h_cb : nullptr; o->cb_label = fold ? c->h_cb_label : nullptr; o->cb_conf = fold ? c->h_cb_conf : nullptr;
+    o->stream_conf = fold ? c->h_conf : nullptr;
+    if (rows > v.d2h_rows) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        c->x_prob.resize((size_t)rows * c->C);
+        HIP_TRY(ctx, hipMemcpy(c->x_prob.data(), c->d_prob, c->x_prob.size() * sizeof(float), hipMemcpyDeviceToHost));
+        o->prob = c->x_prob.data();
+        if (fold) {
+            c->x_cb.resize((size_t)ncb * 4 + 4); c->x_cb_label.resize((size_t)ncb + 1); c->x_cb_conf.resize((size_t)ncb + 1);
+            if (ncb) {
+                HIP_TRY(ctx, hipMemcpy(c->x_cb.data(), c->d_cb, (size_t)ncb * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
+                HIP_TRY(ctx, hipMemcpy(c->x_cb_label.data(), c->d_cb_label, (size_t)ncb * sizeof(int32_t), hipMemcpyDeviceToHost));
+                HIP_TRY(ctx, hipMemcpy(c->x_cb_conf.data(), c->d_cb_conf, (size_t)ncb * sizeof(double), hipMemcpyDeviceToHost));
+            }
+            o->cb = c->x_cb.data(); o->cb_label = c->x_cb_label.data(); o->cb_conf = c->x_cb_conf.data();
+        }
+    }
+    return WSA_OK;
+}
 
 extern "C" {
 

@@ -71,6 +71,7 @@ struct wsa_stream {
     hipGraphExec_t gexec = nullptr;
     hipStream_t own = nullptr; hipEvent_t ev_in = nullptr;   // the legacy NULL stream cannot be captured: steps given stream 0 run on `own`
     const float* g_pcm = nullptr; uint64_t g_stride = 0; hipStream_t g_stream = nullptr; bool g_host = false;
+    wsa_scls* scls = nullptr;               // the attached classifier's tables and carried fold (wsa_stream_set_model), or NULL
 };
 
 template <typename T>
@@ -147,6 +148,7 @@ void wsa_stream_destroy(wsa_stream* b) {
     if (b->ev_in) (void)hipEventDestroy(b->ev_in);
     for (void* p : b->allocs) (void)hipFree(p);
     if (b->d_collect) (void)hipFree(b->d_collect);
+    wsa_scls_free(b->scls);
     for (void* p : {(void*)b->h_ctl, (void*)b->h_pcm, (void*)b->h_totals, (void*)b->h_meta, (void*)b->h_seg, (void*)b->h_feat}) if (p) (void)hipHostFree(p);
     delete b;
 }
@@ -339,6 +341,10 @@ static wsa_status enqueue_step(wsa_stream* b, const float* d_pcm, uint64_t strid
         u.totals = b->d_totals; u.state = b->d_utt_state; u.carry = b->d_carry; u.ctl = d_bits; u.ring_mask = b->ring - 1;
         launch_utterance(u, s);
         HIP_TRY(ctx, hipGetLastError());
+    }
+    if (b->scls) {                         // K6 on the step's rows, then (level 13) the fold carried per stream; both push their tables themselves
+        const wsa_status st = wsa_scls_enqueue(b->scls, s);
+        if (st != WSA_OK) return st;
     }
     hipLaunchKernelGGL(stream_push_kernel, dim3(16), dim3(256), 0, s, b->d_totals, b->d_counters, b->d_meta, b->d_feat, b->d_seg,
                        b->h_totals_dev, b->h_meta_dev, b->h_feat_dev, b->h_seg_dev, b->d2h_rows, b->d2h_segs, b->d_state, b->n);
@@ -544,6 +550,33 @@ wsa_status wsa_stream_collect(wsa_stream* b, void* stream, wsa_stream_rows* o) {
         return fail(ctx, WSA_ERR_CAPACITY, "a device-side arena overflowed; results are invalid (step "
                     + std::to_string(b->steps) + ", flags " + std::to_string(b->h_totals[3]) + ", history " + std::to_string(b->h_totals[2]) + ")");
     return WSA_OK;
+}
+
+wsa_status wsa_stream_set_model(wsa_stream* b, const wsa_model* m) {
+    if (!b) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = b->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (b->stepped) HIP_TRY(ctx, hipStreamSynchronize(b->last_stream ? b->last_stream : b->own));     // the last step may still read the tables
+    wsa_scls* n = nullptr;
+    if (m) {
+        const wsa_scls_view v{ctx, ctx->cfg.output_level, b->n, b->rows_cap, b->d2h_rows, b->d_meta, b->d_feat, b->d_row_off, b->d_totals, b->d_ctl + 2 * (size_t)b->n};
+        const wsa_status st = wsa_scls_create(v, m, &n);
+        if (st != WSA_OK) return st;
+    }
+    if (b->gexec) { (void)hipGraphExecDestroy(b->gexec); b->gexec = nullptr; }         // the next step recaptures with (or without) the classifier
+    wsa_scls_free(b->scls);
+    b->scls = n;
+    return WSA_OK;
+}
+
+wsa_status wsa_stream_classes(wsa_stream* b, wsa_stream_class_result* out) {
+    if (!b || !out) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = b->ctx;
+    if (!b->scls) return fail(ctx, WSA_ERR_INVALID, "no classifier attached to these streams (wsa_stream_set_model)");
+    if (!b->stepped) return fail(ctx, WSA_ERR_INVALID, "no step on this stream object yet");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(b->last_stream ? b->last_stream : b->own));
+    return wsa_scls_result(b->scls, b->h_totals[0], out);
 }
 
 // Timed steps for the latency figure of BASELINE config 5: step k copies feed[k mod feed_steps] (n_streams x samples_per_step floats,

@@ -568,11 +568,16 @@ function LaunchBatches(batches, callback = null, labels = [], test_play = false)
 // push(); callbacks fire as callback(si, labels[stream], seg_time, features, stream) for every segment that
 // closed in that step.  ctl = Uint8Array of STREAM_ACTIVE | STREAM_START | STREAM_STOP per stream, or
 // omitted (all streams start on the first push and stay active).
+// With a prediction model set (setPredictionModel) when a level-13 stream object opens, its steps classify their syllables on the GPU:
+// on_prediction(si, [label, confidence], stream, per_syllable) follows each callback (as for LaunchBatch, the stream in place of the clip),
+// and push() / close() return `meters`, one {label: Label_conf_all} per stream (reset by the stream's START).  The object keeps the model it
+// opened with until close().
 const STREAM_ACTIVE = 1, STREAM_START = 2, STREAM_STOP = 4;
 function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames_per_step = 1, max_span_frames = 1024) {
   const nat = addon();
   const level = settings.output_level, step = settings.window_step / 1e3;
   if (![3, 4, 5, 10, 11, 12, 13].includes(level)) throw 'output_level ' + level + ' is not available for streams through this build (3, 4, 5, 10, 11, 12 and 13 are)';
+  const pred = prediction && level === 13 ? prediction : null;
   const ctx = nat.create(native_config(), settings.device);
   let st;
   try {
@@ -580,9 +585,14 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
     const bands = settings.spec_type === 1 ? settings.N_mel_bins : settings.N_fft_bins;
     if (g.bands !== bands) throw 'Bins count mismatch: ' + g.bands + ', ' + bands;              // ref @B8568 check
     st = nat.streamOpen(ctx, n_streams, sample_rate, frames_per_step, max_span_frames);
-  } catch (e) { nat.destroy(ctx); throw (typeof e === 'string' ? e : String(e.message || e)); }
+    if (pred) nat.streamSetModel(st, model_on(nat, ctx));       // the native model on the stream's own context (ref src/index.js:56)
+  } catch (e) {
+    if (st) nat.streamClose(st);
+    if (pred) pred.model.natives.delete(ctx);
+    nat.destroy(ctx); throw (typeof e === 'string' ? e : String(e.message || e));
+  }
   const input = nat.streamInput(st);
-  let open = true, started = false;
+  let open = true, started = false, meters = null;      // meters: the per-stream Label_conf_all of the last step (a prediction model only)
   const stopped = new Uint8Array(n_streams);          // streams that have had their segment_truncate since their last START
   const seg_seen = new Uint32Array(n_streams);        // level 3: segments a stream has closed since its last START (the callback index, ref @B28273)
   const feat = (res, r) => Array.from(res.feat.subarray(r * 53, r * 53 + 53));
@@ -601,7 +611,7 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
         const m = res.uttMeta.subarray(k * 4, k * 4 + 4);
         callback(0, labels[m[0]] || [], [m[2] * step, (m[3] + 1) * step], Array.from(res.uttFeat.subarray(k * 264, k * 264 + 264)), m[0]);   // ref Y() @B31330
       }
-    } else if (callback) {
+    } else if (callback || (pred && level === 13)) {
       let r = 0;
       while (r < rows) {
         const s = res.meta[r * 8], si = res.meta[r * 8 + 1];
@@ -627,11 +637,16 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
             if (!cut) feats.push(level === 12 ? Array.from(res.feat.subarray(r * 53, r * 53 + 23)) : feat(res, r));
             r++;
           }
-          if (feats.length > 0) callback(si, labels[s] || [], times, feats, s);                                                // ref @B29138 (`p[e].length>0`)
+          if (feats.length > 0) {
+            if (callback) callback(si, labels[s] || [], times, feats, s);                                                      // ref @B29138 (`p[e].length>0`)
+            if (pred && res.cb && level === 13) predict_after(res, r - times.length, si, s, pred);                              // ref prediction.js:70
+          }
         }
       }
     }
-    return { rows, segments: res.segments.length / 4, cuts: res.cuts, cut: (res.flags & 8) !== 0 };   // cut: some stream's span reached max_span_frames in this step (WSA_FLAG_STREAM_CUT)
+    const out = { rows, segments: res.segments.length / 4, cuts: res.cuts, cut: (res.flags & 8) !== 0 };   // cut: some stream's span reached max_span_frames in this step (WSA_FLAG_STREAM_CUT)
+    if (pred && res.streamConf) meters = out.meters = Array.from({ length: n_streams }, (_, s) => meters_of({ nClasses: res.nClasses, clipConf: res.streamConf }, s, pred.model.labels));
+    return out;
   };
   const handle = {
     input, samplesPerStep: input.length / n_streams, stopPending: false,
@@ -655,14 +670,16 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
     // segment a source is in the middle of is reported like the reference reports it when its nodes are disconnected
     close(flush = true) {
       if (!open) return { rows: 0, segments: 0 };
-      let out = { rows: 0, segments: 0 };
+      let out = Object.assign({ rows: 0, segments: 0 }, meters ? { meters } : {});
       if (flush && started && stopped.some((v) => !v)) {
         const c = new Uint8Array(n_streams);
         for (let i = 0; i < n_streams; i++) if (!stopped[i]) { c[i] = STREAM_STOP; stopped[i] = 1; }
         out = deliver(nat.streamStep(st, c));
       }
       open = false; open_streams.delete(handle);
-      nat.streamClose(st); nat.destroy(ctx);           // detaches `input`: the pinned buffer is gone
+      nat.streamClose(st);                             // detaches `input`: the pinned buffer is gone; releases the model
+      if (pred) pred.model.natives.delete(ctx);        // the native model goes with the stream's context
+      nat.destroy(ctx);
       return out;
     },
   };

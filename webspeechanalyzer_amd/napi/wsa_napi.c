@@ -16,6 +16,7 @@
  *   streamInput(stream) -> Float32Array over the pinned [nStreams][samplesPerStep] input buffer (no copy)
  *   streamStep(stream, ctl: Uint8Array | null) -> {meta, feat, segments}   (wsa_stream_step_host + wsa_stream_collect;
  *       one hipGraph launch, well under a millisecond, so it runs on the calling thread)
+ *   streamSetModel(stream, model | null)        (wsa_stream_set_model: streamStep results gain prob, cb, cbLabel, cbConf, streamConf, nClasses)
  *   streamClose(stream)
  * Rejections carry the library's error string.  No compute happens in this file.
  */
@@ -554,7 +555,7 @@ static napi_value fn_gather_rows(napi_env env, napi_callback_info info) {
 }
 
 /* ---- streams ---- */
-typedef struct { wsa_stream *st; wsa_ctx *ctx; ctx_box *box; uint32_t n, sps; napi_ref input_ref; } stream_t;   /* input_ref: the ArrayBuffer over the pinned input, detached at close */
+typedef struct { wsa_stream *st; wsa_ctx *ctx; ctx_box *box; uint32_t n, sps; napi_ref input_ref; model_box *model; } stream_t;   /* input_ref: the ArrayBuffer over the pinned input, detached at close; model: attached classifier (holds its busy count) */
 static void stream_finalize(napi_env env, void *data, void *hint) { /* explicit streamClose() only */ }
 static stream_t *get_stream(napi_env env, napi_value v) {
     void *p = NULL; if (napi_get_value_external(env, v, &p) != napi_ok) return NULL; return (stream_t *)p;
@@ -636,6 +637,18 @@ static napi_value fn_stream_step(napi_env env, napi_callback_info info) {
         napi_set_named_property(env, o, "trackRanked", make_typed(env, napi_int32_array, r.track_ranked, (size_t)r.n_track_ranked, 4));
     }
     { napi_value fl; napi_create_uint32(env, r.status_flags, &fl); napi_set_named_property(env, o, "flags", fl); }   /* WSA_FLAG_* (8: a span was cut in this step) */
+    if (h->model) {                                 /* the attached classifier's tables of this step, named as processBatch's (streamConf: per stream, carried) */
+        wsa_stream_class_result c;
+        if (wsa_stream_classes(h->st, &c) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(h->ctx)); return NULL; }
+        napi_set_named_property(env, o, "prob", make_typed(env, napi_float32_array, c.prob, (size_t)c.n_rows * c.n_classes, 4));
+        if (c.cb) {
+            napi_set_named_property(env, o, "cb", make_typed(env, napi_int32_array, c.cb, (size_t)c.n_callbacks * 4, 4));
+            napi_set_named_property(env, o, "cbLabel", make_typed(env, napi_int32_array, c.cb_label, (size_t)c.n_callbacks, 4));
+            napi_set_named_property(env, o, "cbConf", make_typed(env, napi_float64_array, c.cb_conf, (size_t)c.n_callbacks, 8));
+            napi_set_named_property(env, o, "streamConf", make_typed(env, napi_float64_array, c.stream_conf, (size_t)c.n_streams * c.n_classes, 8));
+        }
+        napi_value nc; napi_create_uint32(env, c.n_classes, &nc); napi_set_named_property(env, o, "nClasses", nc);
+    }
     return o;
 }
 static napi_value fn_stream_close(napi_env env, napi_callback_info info) {
@@ -649,8 +662,29 @@ static napi_value fn_stream_close(napi_env env, napi_callback_info info) {
             napi_delete_reference(env, h->input_ref); h->input_ref = NULL;
         }
         wsa_stream_destroy(h->st); h->st = NULL;
+        if (h->model) { if (h->model->busy) h->model->busy--; h->model = NULL; }
         if (h->box && h->box->children) h->box->children--;
     }
+    return NULL;
+}
+static napi_value fn_stream_set_model(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    stream_t *h = argc ? get_stream(env, argv[0]) : NULL;
+    if (!h || !h->st || argc < 2) { napi_throw_type_error(env, NULL, "streamSetModel(stream, model | null)"); return NULL; }
+    model_box *mb = NULL;
+    napi_valuetype t;
+    NAPI_OK(env, napi_typeof(env, argv[1], &t));
+    if (t != napi_null && t != napi_undefined) {
+        void *p = NULL;
+        if (t != napi_external || napi_get_value_external(env, argv[1], &p) != napi_ok || !p || !((model_box *)p)->m) { napi_throw_error(env, NULL, "streamSetModel: the model handle was destroyed (or is not a model)"); return NULL; }
+        mb = (model_box *)p;
+        if (mb->owner != h->box) { napi_throw_error(env, NULL, "streamSetModel: the model belongs to another context"); return NULL; }
+    }
+    if (wsa_stream_set_model(h->st, mb ? mb->m : NULL) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(h->ctx)); return NULL; }
+    if (h->model && h->model->busy) h->model->busy--;          /* modelDestroy() refuses while a stream holds the model */
+    h->model = mb;
+    if (mb) mb->busy++;
     return NULL;
 }
 
@@ -719,7 +753,7 @@ static napi_value fn_model_destroy(napi_env env, napi_callback_info info) {
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     if (argc < 1 || napi_get_value_external(env, argv[0], &p) != napi_ok || !p) { napi_throw_type_error(env, NULL, "modelDestroy(model)"); return NULL; }
     model_box *mb = (model_box *)p;
-    if (mb->busy) { napi_throw_error(env, NULL, "the model is in use by a batch in flight"); return NULL; }
+    if (mb->busy) { napi_throw_error(env, NULL, "the model is in use by a batch in flight or an open stream"); return NULL; }
     if (mb->m) { wsa_model_destroy(mb->m); mb->m = NULL; }
     model_unlink(mb);
     return NULL;
@@ -731,7 +765,7 @@ NAPI_MODULE_INIT() {
     const struct { const char *name; napi_callback fn; } fns[] = {
         {"abiVersion", fn_abi_version}, {"freePinned", fn_free_pinned}, {"defaults", fn_defaults}, {"create", fn_create}, {"destroy", fn_destroy},
         {"geometry", fn_geometry}, {"allocPinned", fn_alloc_pinned}, {"binsHz", fn_bins_hz}, {"processBatch", fn_process_batch}, {"gatherRows", fn_gather_rows},
-        {"streamOpen", fn_stream_open}, {"streamInput", fn_stream_input}, {"streamStep", fn_stream_step}, {"streamClose", fn_stream_close},
+        {"streamOpen", fn_stream_open}, {"streamInput", fn_stream_input}, {"streamStep", fn_stream_step}, {"streamClose", fn_stream_close}, {"streamSetModel", fn_stream_set_model},
         {"modelCreate", fn_model_create}, {"modelDestroy", fn_model_destroy}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
