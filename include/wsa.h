@@ -92,6 +92,24 @@ wsa_status wsa_batch_create(wsa_ctx *ctx, uint32_t n_clips, const uint32_t *n_sa
  */
 wsa_status wsa_batch_create_resampled(wsa_ctx *ctx, uint32_t n_clips, const uint32_t *n_samples_in, double fs_in, double fs_out, wsa_batch **out);
 uint64_t   wsa_resample_length(uint64_t n_in, double fs_in, double fs_out);      /* trunc(n_in * fs_out / fs_in) */
+/*
+ * The same for clips of different rates (an addition within version 5: probe for wsa_batch_create_mixed): clip i arrives at
+ * fs_in[i] (n_samples_in[i] samples) and is analysed at fs_out.  Stands in for the application's folder loop: every file of a
+ * folder, one after the other (ref src/index.js:277-296), goes to the browser's decodeAudioData inside
+ * `new OfflineAudioContext(1, 48e6, 48e3)` (ref dist/main.js:2 @B18769), which converts whatever rate the file has - here as ONE launch.
+ *   - fs_in[i] != fs_out: clip i is converted by RS-1 with its own ratio = fs_in[i] / fs_out (in double, exactly like that) and
+ *     its own offset-kernel table; wsa_resample_length(n_samples_in[i], fs_in[i], fs_out) samples.
+ *   - fs_in[i] == fs_out: clip i is NOT filtered; its samples reach the front end bit for bit, length unchanged (what the browser
+ *     does with a file at the context's rate).  RS-1 at ratio 1 is a 0.9-Nyquist low-pass, not an identity:
+ *     wsa_batch_create_resampled with equal rates keeps filtering, this entry point copies.
+ *   - Every rate positive and within a factor 16 of fs_out, converted lengths below 2^32 - 16: else WSA_ERR_INVALID with a message
+ *     that names the clip.  Any number of distinct rates (one 8.4 KB table per rate).
+ *   - Everything that works on a resampling batch works on this one, unchanged in shape: wsa_batch_run (clip i at
+ *     d_pcm + i * clip_stride, clip_stride >= the longest INPUT clip), wsa_batch_run_host, wsa_batch_run_host_i16,
+ *     wsa_batch_copy_pcm, wsa_batch_get_info, results, stage times, wsa_batch_classify.  wsa_batch_run allocates nothing and
+ *     stays capturable into a hipGraph.
+ */
+wsa_status wsa_batch_create_mixed(wsa_ctx *ctx, uint32_t n_clips, const uint32_t *n_samples_in, const double *fs_in, double fs_out, wsa_batch **out);
 /* converted PCM of a resampling batch after a run: pcm [n_clips][stride] floats, stride >= the longest converted clip */
 wsa_status wsa_batch_copy_pcm(wsa_batch *b, void *stream, float *pcm, uint64_t stride);
 void       wsa_batch_destroy(wsa_batch *b);

@@ -109,7 +109,7 @@ ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destr
                "wsa_batch_run_host", "wsa_batch_result", "wsa_batch_copy_rows", "wsa_batch_copy_spectra",
                "wsa_batch_get_info", "wsa_batch_stage_ms", "wsa_batch_enable_timing", "wsa_batch_run_frontend",
                "wsa_batch_run_backend", "wsa_batch_enable_trace", "wsa_batch_copy_trace", "wsa_batch_copy_formants", "wsa_batch_copy_utterance",
-               "wsa_batch_tracks_info", "wsa_batch_copy_tracks", "wsa_batch_create_resampled", "wsa_resample_length", "wsa_batch_copy_pcm",
+               "wsa_batch_tracks_info", "wsa_batch_copy_tracks", "wsa_batch_create_resampled", "wsa_resample_length", "wsa_batch_copy_pcm", "wsa_batch_create_mixed",
                "wsa_stream_create", "wsa_stream_destroy", "wsa_stream_samples_per_step", "wsa_stream_step",
                "wsa_stream_host_input", "wsa_stream_step_host", "wsa_stream_collect", "wsa_stream_enable_graph",
                "wsa_batch_keep_spectra", "wsa_batch_backend_reruns", "wsa_stream_time_steps", "wsa_batch_run_host_i16",
@@ -162,6 +162,7 @@ def lib():
     L.wsa_bins_hz.argtypes = [vp, dbl, vp, i32]
     L.wsa_batch_create.argtypes = [vp, u32, vp, dbl, ctypes.POINTER(vp)]
     L.wsa_batch_create_resampled.argtypes = [vp, u32, vp, dbl, dbl, ctypes.POINTER(vp)]
+    L.wsa_batch_create_mixed.argtypes = [vp, u32, vp, vp, dbl, ctypes.POINTER(vp)]
     L.wsa_resample_length.argtypes = [u64, dbl, dbl]
     L.wsa_resample_length.restype = ctypes.c_uint64
     L.wsa_batch_copy_pcm.argtypes = [vp, vp, vp, u64]
@@ -265,7 +266,8 @@ class Analyzer:
         return out
 
     def batch(self, n_samples, fs, resample_to=None):
-        """resample_to: analysis rate when the clips handed to run* are at `fs` and are to be converted first (spec RS-1)."""
+        """resample_to: analysis rate when the clips handed to run* are at `fs` and are to be converted first (spec RS-1); `fs` may then be a
+        sequence with one rate per clip (a folder of files of different rates in one launch)."""
         return Batch(self, n_samples, fs, resample_to)
 
     def streams(self, n_streams, fs, frames_per_step=1, max_span_frames=1024):
@@ -301,9 +303,17 @@ class Batch:
     def __init__(self, an, n_samples, fs, resample_to=None):
         self.an, self.L = an, an.L
         self.n_samples = np.ascontiguousarray(n_samples, dtype=np.uint32)
-        self.fs = float(fs)
+        self.fs = float(fs) if np.ndim(fs) == 0 else None
         self.h = ctypes.c_void_p()
-        if resample_to:
+        if self.fs is None and not resample_to:
+            raise WsaError("one rate per clip needs resample_to: a launch has one geometry")
+        if resample_to and np.ndim(fs) > 0:              # one rate per clip (wsa_batch_create_mixed); clips already at resample_to pass unfiltered
+            self.n_samples_in, self.fs_in, self.fs = self.n_samples, np.ascontiguousarray(fs, dtype=np.float64), float(resample_to)
+            if self.fs_in.shape != self.n_samples_in.shape:
+                raise WsaError("fs as a sequence holds one rate per clip")
+            an._check(self.L.wsa_batch_create_mixed(an.h, len(self.n_samples_in), self.n_samples_in.ctypes.data, self.fs_in.ctypes.data, self.fs, ctypes.byref(self.h)))
+            self.n_samples = np.array([self.L.wsa_resample_length(int(n), float(f), self.fs) for n, f in zip(self.n_samples_in, self.fs_in)], np.uint32)
+        elif resample_to:
             self.n_samples_in, self.fs_in, self.fs = self.n_samples, self.fs, float(resample_to)
             an._check(self.L.wsa_batch_create_resampled(an.h, len(self.n_samples_in), self.n_samples_in.ctypes.data, self.fs_in, self.fs, ctypes.byref(self.h)))
             self.n_samples = np.array([self.L.wsa_resample_length(int(n), self.fs_in, self.fs) for n in self.n_samples_in], np.uint32)

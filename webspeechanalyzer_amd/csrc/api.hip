@@ -56,6 +56,8 @@ struct wsa_batch {
     // sample-rate conversion in front of the path (wsa_batch_create_resampled): input lengths / rate, offset-kernel table, converted PCM
     bool rs_on = false; double fs_in = 0; std::vector<uint32_t> n_samples_in; uint32_t max_samples_in = 0;
     uint32_t *d_rs_n_in = nullptr, *d_rs_n_out = nullptr; float *d_rs_table = nullptr, *d_rs_pcm = nullptr; uint64_t rs_stride = 0;
+    // ... for clips of different rates (wsa_batch_create_mixed): rate classes and the work list of K0's blocks, planned once (tables and list live on the device)
+    bool rs_mixed = false; RsMixedPlan rs_plan; RsClass* d_rs_cls = nullptr; uint32_t* d_rs_clip_class = nullptr; RsWork* d_rs_work = nullptr;
     int4* d_trk_pts = nullptr; int32_t* d_trk_rank = nullptr; int32_t* d_trk_seg = nullptr;      // level 3: raw-track pools (TrParams)
     bool counters_clean = false, end_clears = false, capturing = false, ever_captured = false;      // the fused compaction of the previous run has left the counters cleared: the next run launches no clear kernel
     char* d_trk_stage = nullptr; size_t trk_stage_cap = 0; std::vector<uint64_t> h_trk_desc;        // level 3: wsa_batch_copy_tracks gathers through this
@@ -105,7 +107,7 @@ Tuning Tuning::from_env() {
     t.full_table = num("WSA_FULL_TABLE", -1);
     t.tracker_wpc = num("WSA_TRACKER_WPC", 0); t.fin_wpc = num("WSA_FIN_WPC", 0); t.fpw = num("WSA_FPW", 0);
     t.fe_wg_per_cu = num("WSA_FE_WGS", 0); t.fe_no_queue = std::getenv("WSA_FE_NO_QUEUE") != nullptr; t.peaks_wpc = num("WSA_PEAKS_WPC", 0); t.peaks_w = num("WSA_PEAKS_W", 0); t.upload_threads = num("WSA_UPLOAD_THREADS", 0);
-    t.rs_s = num("WSA_RS_S", 0); t.rs_j = num("WSA_RS_J", 0); t.rs_c = num("WSA_RS_C", 0);
+    t.rs_s = num("WSA_RS_S", 0); t.rs_j = num("WSA_RS_J", 0); t.rs_c = num("WSA_RS_C", 0); t.rs_one_launch = std::getenv("WSA_RS_ONE_LAUNCH") != nullptr;
     return t;
 }
 // run prologue: work-queue counters and totals back to zero.  A kernel, not hipMemsetAsync: memset / memcpy nodes of a
@@ -200,7 +202,7 @@ void wsa_batch_destroy(wsa_batch* b) {
     delete b;
 }
 
-static wsa_status batch_create_impl(wsa_ctx* ctx, uint32_t n_clips, const uint32_t* n_samples, double fs, const uint32_t* n_samples_in, double fs_in, wsa_batch** out) {
+static wsa_status batch_create_impl(wsa_ctx* ctx, uint32_t n_clips, const uint32_t* n_samples, double fs, const uint32_t* n_samples_in, double fs_in, wsa_batch** out, const double* fs_in_each = nullptr) {
     if (!ctx || !out || (n_clips && !n_samples)) return fail(ctx, WSA_ERR_INVALID, "null argument");
     *out = nullptr;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -304,10 +306,18 @@ static wsa_status batch_create_impl(wsa_ctx* ctx, uint32_t n_clips, const uint32
     if (ok && n_samples_in) {              // K0 in front: the caller's PCM is at fs_in, everything planned above works on the converted clips
         b->rs_on = true; b->fs_in = fs_in; b->n_samples_in.assign(n_samples_in, n_samples_in + n_clips);
         for (uint32_t i = 0; i < n_clips; i++) if (n_samples_in[i] > b->max_samples_in) b->max_samples_in = n_samples_in[i];
-        std::vector<float> K0, K; build_resample_table(fs_in, fs, K0); resample_table_image(K0, K);
         b->rs_stride = ((uint64_t)b->max_samples + 3u) & ~3ull;
-        ok = dev_upload(b, &b->d_rs_table, K) && dev_upload(b, &b->d_rs_n_in, b->n_samples_in) && dev_upload(b, &b->d_rs_n_out, b->n_samples)
-             && dev_alloc(b, &b->d_rs_pcm, (size_t)n_clips * b->rs_stride + 4);
+        ok = dev_upload(b, &b->d_rs_n_in, b->n_samples_in) && dev_upload(b, &b->d_rs_n_out, b->n_samples) && dev_alloc(b, &b->d_rs_pcm, (size_t)n_clips * b->rs_stride + 4);
+        if (ok && fs_in_each) {            // one rate per clip: classes + work list
+            b->rs_mixed = true;
+            if (!plan_resample_mixed(n_clips, b->n_samples.data(), fs_in_each, fs, b->rs_plan, err)) { wsa_batch_destroy(b); return fail(ctx, WSA_ERR_INVALID, err); }
+            RsMixedPlan& M = b->rs_plan;
+            ok = dev_upload(b, &b->d_rs_table, M.tables) && dev_upload(b, &b->d_rs_cls, M.cls) && dev_upload(b, &b->d_rs_clip_class, M.clip_class) && dev_upload(b, &b->d_rs_work, M.work);
+            std::vector<float>().swap(M.tables); std::vector<RsWork>().swap(M.work);
+        } else if (ok) {
+            std::vector<float> K0, K; build_resample_table(fs_in, fs, K0); resample_table_image(K0, K);
+            ok = dev_upload(b, &b->d_rs_table, K);
+        }
     }
     if (!ok) {
         const std::string m = std::string("device allocation failed: ") + hipGetErrorString(hipGetLastError());
@@ -334,6 +344,19 @@ wsa_status wsa_batch_create_resampled(wsa_ctx* ctx, uint32_t n_clips, const uint
         n_out[i] = (uint32_t)n;
     }
     return batch_create_impl(ctx, n_clips, n_out.data(), fs_out, n_samples_in, fs_in, out);
+}
+
+wsa_status wsa_batch_create_mixed(wsa_ctx* ctx, uint32_t n_clips, const uint32_t* n_samples_in, const double* fs_in, double fs_out, wsa_batch** out) {
+    if (!ctx || !out || (n_clips && (!n_samples_in || !fs_in))) return fail(ctx, WSA_ERR_INVALID, n_clips && ctx && out && !fs_in ? "null argument: fs_in holds one rate per clip (clip 0 has none)" : "null argument");
+    if (!(fs_out > 0)) return fail(ctx, WSA_ERR_INVALID, "sample rates must be positive and at most a factor 16 apart");
+    std::vector<uint32_t> n_out(n_clips);
+    for (uint32_t i = 0; i < n_clips; i++) {
+        if (!(fs_in[i] > 0) || fs_in[i] / fs_out > 16 || fs_out / fs_in[i] > 16) return fail(ctx, WSA_ERR_INVALID, "sample rates must be positive and at most a factor 16 apart (clip " + std::to_string(i) + ")");
+        const uint64_t n = resample_length(n_samples_in[i], fs_in[i], fs_out);
+        if (n > 0xfffffff0ull) return fail(ctx, WSA_ERR_INVALID, "a converted clip would exceed 2^32 samples (clip " + std::to_string(i) + ")");
+        n_out[i] = (uint32_t)n;
+    }
+    return batch_create_impl(ctx, n_clips, n_out.data(), fs_out, n_samples_in, 0, out, fs_in);
 }
 
 wsa_status wsa_batch_get_info(const wsa_batch* b, wsa_batch_info* o) {
@@ -455,7 +478,13 @@ static wsa_status run_impl(wsa_batch* b, const float* d_pcm, uint64_t stride, co
     if (fe) {
         if (!d_pcm && b->total_frames) return fail(ctx, WSA_ERR_INVALID, "null PCM pointer");
         if (stride < (b->rs_on ? b->max_samples_in : b->max_samples) && b->n_clips > 1) return fail(ctx, WSA_ERR_INVALID, "clip_stride smaller than the longest clip");
-        if (b->rs_on) {                      // K0: the caller's PCM (fs_in) -> the batch's own buffer at the analysis rate
+        if (b->rs_mixed) {                   // K0 over the planned work list: every clip from its own rate (or copied as it is)
+            RsMixedParams r; r.in = d_pcm; r.stride_in = stride; r.out = b->d_rs_pcm; r.stride_out = b->rs_stride; r.n_in = b->d_rs_n_in; r.n_out = b->d_rs_n_out;
+            r.tables = b->d_rs_table; r.cls = b->d_rs_cls; r.clip_class = b->d_rs_clip_class; r.work = b->d_rs_work;
+            launch_resample_mixed(r, b->rs_plan, !b->tune.rs_one_launch, s);       // (one launch per class beat one launch over the whole list: profiles/mixed_rate.md)
+            HIP_TRY(ctx, hipGetLastError());
+            d_pcm = b->d_rs_pcm; stride = b->rs_stride;
+        } else if (b->rs_on) {               // K0: the caller's PCM (fs_in) -> the batch's own buffer at the analysis rate
             RsParams r; r.in = d_pcm; r.stride_in = stride; r.out = b->d_rs_pcm; r.stride_out = b->rs_stride;
             r.n_in = b->d_rs_n_in; r.n_out = b->d_rs_n_out; r.table = b->d_rs_table; r.ratio = b->fs_in / b->fs; r.S = b->tune.rs_s > 0 ? b->tune.rs_s : resample_stride(b->fs_in, b->fs);
             r.J = b->tune.rs_j > 0 ? b->tune.rs_j : resample_outputs_per_lane(r.S, r.ratio); r.span = resample_span(r.ratio, r.S, r.J); r.chunks = b->tune.rs_c > 0 ? b->tune.rs_c : 1;       // (more runs per block never won: tools/resample_sweep.sh)
@@ -862,7 +891,7 @@ wsa_status wsa_batch_copy_pcm(wsa_batch* b, void* stream, float* pcm, uint64_t s
     if (!b || !pcm) return WSA_ERR_INVALID;
     wsa_ctx* ctx = b->ctx;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (!b->rs_on || !b->ran) return fail(ctx, WSA_ERR_INVALID, "no converted PCM: the batch must come from wsa_batch_create_resampled and must have run");
+    if (!b->rs_on || !b->ran) return fail(ctx, WSA_ERR_INVALID, "no converted PCM: the batch must come from wsa_batch_create_resampled / wsa_batch_create_mixed and must have run");
     if (stride < b->max_samples) return fail(ctx, WSA_ERR_INVALID, "stride smaller than the longest converted clip");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     for (uint32_t i = 0; i < b->n_clips; i++)

@@ -60,14 +60,13 @@ typedef float rs_v2f __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) const float rs_lds_cf;
 __host__ __device__ inline int rs_xlen(int span) { return (span + 6) & ~3; }    // staged inputs: the span, up to 3 samples in front of it (the run starts at a multiple of 4), rounded up to whole 16-byte words
 
-__global__ __launch_bounds__(512) void resample_kernel(RsParams p) {
-    extern __shared__ __attribute__((aligned(16))) float s_mem[];
+// What block `bx` of clip `clip` does; both kernels below are this function (p, clip and bx are the same for the whole block).
+__device__ __forceinline__ void rs_block(const RsParams& p, float* const s_mem, const uint32_t clip, const uint32_t bx) {
     rs_v2f* const s_k = reinterpret_cast<rs_v2f*>(s_mem);                               // [32][33] pairs
     float* const s_x0 = s_mem + 2 * RS_OFFS * RS_KSTRIDE;                               // s_x0[q] = x[lo4 + q]
-    const uint32_t clip = blockIdx.y;
     const uint64_t n_in = p.n_in[clip], n_out = p.n_out[clip];
     const int J = p.J;
-    if ((uint64_t)blockIdx.x * (uint64_t)p.chunks * (uint64_t)(p.S * J) >= n_out) return;
+    if ((uint64_t)bx * (uint64_t)p.chunks * (uint64_t)(p.S * J) >= n_out) return;
     const float* x = p.in + (uint64_t)clip * p.stride_in;
     const int tid = threadIdx.x, nt = blockDim.x;
     constexpr int U = 6;
@@ -89,7 +88,7 @@ __global__ __launch_bounds__(512) void resample_kernel(RsParams p) {
     float* const out = p.out + (uint64_t)clip * p.stride_out;
     // the block takes p.chunks consecutive runs of S * J outputs: the table is staged once for all of them
     for (int c = 0; c < p.chunks; c++) {
-    const uint64_t n0 = ((uint64_t)blockIdx.x * (uint64_t)p.chunks + (uint64_t)c) * (uint64_t)(p.S * J);
+    const uint64_t n0 = ((uint64_t)bx * (uint64_t)p.chunks + (uint64_t)c) * (uint64_t)(p.S * J);
     if (n0 >= n_out) break;
     if (c) __syncthreads();                                                 // the previous run's inputs are not needed any more
     int ts = tid;
@@ -183,6 +182,36 @@ __global__ __launch_bounds__(512) void resample_kernel(RsParams p) {
     }
 }
 
+// one rate for the whole batch: grid = (the longest clip's blocks) x clips, blocks past their clip's end return at once
+__global__ __launch_bounds__(512) void resample_kernel(RsParams p) {
+    extern __shared__ __attribute__((aligned(16))) float s_mem[];
+    rs_block(p, s_mem, blockIdx.y, blockIdx.x);
+}
+
+// Clips of different rates: block b takes entry b of the plan-time work list — (clip, block of that clip) — and its clip's rate class.  The list is
+// sorted by class, so neighbouring blocks share table and shape, and it holds no entry for outputs a clip does not have.  Entry, class and clip lengths
+// are the same for the whole block (scalar loads).  Launched once per class over the class's slice of the list (block size and LDS as the single-rate
+// launch has them), or - WSA_RS_ONE_LAUNCH - once over the whole list with the block as large as the largest class needs: lanes beyond a class's S stage
+// and then leave, as the lanes of a block's last wave always did (slower: a 160-output class in 320-lane blocks; profiles/mixed_rate.md).  A copy class (fs_in == fs_out) moves RS_COPY_RUN samples per block as they are.
+constexpr uint32_t RS_COPY_RUN = 8192;
+__global__ __launch_bounds__(512) void resample_mixed_kernel(RsMixedParams m) {
+    extern __shared__ __attribute__((aligned(16))) float s_mem[];
+    const RsWork w = m.work[blockIdx.x];
+    const RsClass c = m.cls[m.clip_class[w.clip]];
+    if (c.copy) {
+        const uint64_t n_in = m.n_in[w.clip], n_out = m.n_out[w.clip], lim = n_out < n_in ? n_out : n_in;
+        const uint64_t n0 = (uint64_t)w.blk * RS_COPY_RUN, end = n0 + RS_COPY_RUN < lim ? n0 + RS_COPY_RUN : lim;
+        const float* x = m.in + (uint64_t)w.clip * m.stride_in;
+        float* const out = m.out + (uint64_t)w.clip * m.stride_out;
+        for (uint64_t n = n0 + threadIdx.x; n < end; n += blockDim.x) out[n] = x[n];
+        return;
+    }
+    RsParams p;
+    p.in = m.in; p.stride_in = m.stride_in; p.out = m.out; p.stride_out = m.stride_out; p.n_in = m.n_in; p.n_out = m.n_out;
+    p.chunks = 1; p.table = m.tables + c.table_off; p.ratio = c.ratio; p.span = c.span; p.S = c.S; p.J = c.J;
+    rs_block(p, s_mem, w.clip, w.blk);
+}
+
 // outputs per block row: a multiple of the conversion's period when the rates are integers with a short period
 int resample_stride(double fs_in, double fs_out) {
     const double ri = std::floor(fs_in), ro = std::floor(fs_out);
@@ -215,5 +244,60 @@ void launch_resample(const RsParams& p, uint32_t n_clips, uint64_t max_out, hipS
 
 int resample_outputs_per_lane(int S, double ratio) { return rs_j(S, ratio); }
 int resample_span(double ratio, int S, int J) { return (int)std::ceil((double)(S * J - 1) * ratio) + RS_TAPS + 2; }
+
+// The rate classes of a mixed batch (the distinct fs_in, in order of first appearance) and the work list: per class every clip's blocks, clip by clip.
+bool plan_resample_mixed(uint32_t n_clips, const uint32_t* n_out, const double* fs_in, double fs_out, RsMixedPlan& P, std::string& err) {
+    P = RsMixedPlan();
+    P.clip_class.resize(n_clips);
+    std::vector<double> rates;
+    for (uint32_t i = 0; i < n_clips; i++) {
+        size_t c = 0;
+        while (c < rates.size() && rates[c] != fs_in[i]) c++;       // (a map from the rate's bits would do for thousands of distinct rates; a folder has a handful)
+        if (c == rates.size()) {
+            rates.push_back(fs_in[i]);
+            RsClass k = {};
+            k.ratio = fs_in[i] / fs_out;
+            if (fs_in[i] == fs_out) { k.copy = 1; P.block.push_back(256); P.lds.push_back(0); }
+            else {
+                std::vector<float> K0, K; build_resample_table(fs_in[i], fs_out, K0); resample_table_image(K0, K);
+                k.table_off = (uint32_t)P.tables.size();
+                P.tables.insert(P.tables.end(), K.begin(), K.end());
+                k.S = resample_stride(fs_in[i], fs_out); k.J = rs_j(k.S, k.ratio); k.span = resample_span(k.ratio, k.S, k.J);
+                P.block.push_back((uint32_t)((k.S + 63) / 64 * 64));
+                P.lds.push_back((uint32_t)(sizeof(float) * ((size_t)2 * RS_OFFS * RS_KSTRIDE + (size_t)rs_xlen(k.span))));
+            }
+            P.cls.push_back(k);
+            if (P.block.back() > P.max_block) P.max_block = P.block.back();
+            if (P.lds.back() > P.max_lds) P.max_lds = P.lds.back();
+        }
+        P.clip_class[i] = (uint32_t)c;
+    }
+    P.first.assign(P.cls.size() + 1, 0);
+    for (size_t c = 0; c < P.cls.size(); c++) {
+        const uint64_t per_block = P.cls[c].copy ? (uint64_t)RS_COPY_RUN : (uint64_t)P.cls[c].S * (uint64_t)P.cls[c].J;
+        for (uint32_t i = 0; i < n_clips; i++) {
+            if (P.clip_class[i] != c) continue;
+            const uint64_t nb = ((uint64_t)n_out[i] + per_block - 1) / per_block;
+            if ((uint64_t)P.work.size() + nb > 0x7fffffffull) { err = "the batch needs more rate-converter blocks than one launch holds"; return false; }
+            for (uint64_t b = 0; b < nb; b++) P.work.push_back(RsWork{i, (uint32_t)b});
+        }
+        P.first[c + 1] = (uint32_t)P.work.size();
+    }
+    P.n_work = (uint32_t)P.work.size();
+    return true;
+}
+
+void launch_resample_mixed(const RsMixedParams& p, const RsMixedPlan& P, bool per_class, hipStream_t s) {
+    if (P.n_work == 0) return;
+    if (!per_class) {
+        hipLaunchKernelGGL(resample_mixed_kernel, dim3(P.n_work), dim3(P.max_block), P.max_lds, s, p);
+        return;
+    }
+    for (size_t c = 0; c < P.cls.size(); c++) {
+        if (P.first[c + 1] == P.first[c]) continue;
+        RsMixedParams q = p; q.work = p.work + P.first[c];
+        hipLaunchKernelGGL(resample_mixed_kernel, dim3(P.first[c + 1] - P.first[c]), dim3(P.block[c]), P.lds[c], s, q);
+    }
+}
 
 }  // namespace wsa

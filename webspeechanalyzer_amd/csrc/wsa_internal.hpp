@@ -43,6 +43,7 @@ struct Tuning {
     int peaks_w = 0;                    // WSA_PEAKS_W: bins per round of the lane-per-frame peak scan, 16 or 32 (0: default)
     int upload_threads = 0;             // WSA_UPLOAD_THREADS (0: default)
     int rs_s = 0, rs_j = 0, rs_c = 0;   // WSA_RS_S / WSA_RS_J / WSA_RS_C: the rate converter's outputs per block row / per lane and run, runs per block (0: default)
+    bool rs_one_launch = false;         // WSA_RS_ONE_LAUNCH: a mixed-rate batch's K0 as one launch over the whole work list instead of one per rate class
     static Tuning from_env();
 };
 
@@ -199,6 +200,24 @@ int resample_stride(double fs_in, double fs_out);
 int resample_span(double ratio, int S, int J);
 int resample_outputs_per_lane(int S, double ratio);
 void launch_resample(const RsParams& p, uint32_t n_clips, uint64_t max_out, hipStream_t s);
+// K0 for clips of different rates (wsa_batch_create_mixed): one rate class per distinct fs_in, each with the table, S, J and span the single-rate
+// launch would choose for it (copy: fs_in == fs_out, the samples pass unfiltered), and a plan-time work list of one entry per block, sorted by class.
+// A pass is one launch per class over that class's slice of the list, with the class's own block size and LDS (default), or one launch over the whole
+// list with the largest class's (measured slower, profiles/mixed_rate.md: 1.77 against 1.48 ms on 1024 ten-second clips of four rates)
+struct RsClass { double ratio; uint32_t table_off; int span, S, J, copy, pad; };      // table_off: floats into RsMixedParams::tables
+struct RsWork { uint32_t clip, blk; };                                                 // block blk of its clip: outputs blk * S * J ... of the clip's class (copy: blk * RS_COPY_RUN ...)
+struct RsMixedParams {
+    const float* in; uint64_t stride_in; float* out; uint64_t stride_out;
+    const uint32_t* n_in; const uint32_t* n_out;
+    const float* tables; const RsClass* cls; const uint32_t* clip_class; const RsWork* work;
+};
+struct RsMixedPlan {
+    std::vector<float> tables; std::vector<RsClass> cls; std::vector<uint32_t> clip_class; std::vector<RsWork> work;
+    std::vector<uint32_t> first, block, lds;          // per class: its slice of the work list [first[c], first[c + 1]), the block size and dynamic LDS of its own launch
+    uint32_t max_block = 64, max_lds = 0, n_work = 0;  // (n_work = work.size(): the batch drops the host copies of tables and work once they are on the device)
+};
+bool plan_resample_mixed(uint32_t n_clips, const uint32_t* n_out, const double* fs_in, double fs_out, RsMixedPlan& P, std::string& err);
+void launch_resample_mixed(const RsMixedParams& p, const RsMixedPlan& P, bool per_class, hipStream_t s);     // per_class: one launch per class instead of one over the whole list
 
 void launch_frontend(const FeParams& p, int n_clips, int max_frames, int R, int three, hipStream_t s);
 bool fe_supported_R(int R, int three);  // packed FFT length 64 R, R in {2, 4, 8, 16, 32, 64}, or 3 * 64 R, R in {1, 2, 4, 8, 16, 32}

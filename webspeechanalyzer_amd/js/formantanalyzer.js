@@ -383,6 +383,11 @@ function tracks_of_segment(res, k) {
   return out;
 }
 
+// what processBatch takes as the clips' rate: the number when they share one, else a Float64Array with one rate per clip
+function rates_of(clips) {
+  return clips.every((c) => c.sampleRate === clips[0].sampleRate) ? clips[0].sampleRate : Float64Array.from(clips, (c) => c.sampleRate);
+}
+
 // contiguous block partition of n clips over k shards (the first n % k shards take one more)
 function shard_ranges(n, k) {
   const out = [], q = Math.floor(n / k), r = n % k;
@@ -395,8 +400,10 @@ async function run(clips, callback, labels_of, test_play) {
   if (playing) throw 'Error: Already playing';                                               // ref @B4554
   playing = true; stop_requested = false; labels_per_segment = [];
   try {
+    // one geometry per launch: without a conversion in front the clips must share a rate; with resample_to every clip is converted from its own
+    // (what the app's folder loop gets from decodeAudioData, ref src/index.js:277-296) and a clip already at resample_to passes unfiltered
     const rates = new Set(clips.map((c) => c.sampleRate));
-    if (rates.size !== 1) throw 'All clips of one launch must share a sample rate';
+    if (rates.size !== 1 && !(settings.resample_to > 0)) throw 'All clips of one launch must share a sample rate';
     const fs = clips[0].sampleRate;
     const fs_an = settings.resample_to > 0 ? settings.resample_to : fs;         // the rate the analysis runs at (K0 converts in front, spec RS-1)
     // clips are independent launches (SURVEY.md 8e): shard them contiguously over the configured devices, one context each; every
@@ -417,8 +424,9 @@ async function run(clips, callback, labels_of, test_play) {
     const job = ([a, b], i) => {
       const part = clips.slice(a, b);
       const extra = pred ? [models[i]] : [];                     // (no model: the addon is called exactly as before)
-      return all16 ? nat.processBatch(ctxs[i], part.map((c) => c.pcm16), fs, settings.output_level, fs_an, Uint32Array.from(part, (c) => c.channels), gather, ...extra)
-        : nat.processBatch(ctxs[i], part.map(clip_floats), fs, settings.output_level, fs_an, undefined, gather, ...extra);
+      const fs_i = rates_of(part);                               // (a shard whose clips share a rate: the number, as before)
+      return all16 ? nat.processBatch(ctxs[i], part.map((c) => c.pcm16), fs_i, settings.output_level, fs_an, Uint32Array.from(part, (c) => c.channels), gather, ...extra)
+        : nat.processBatch(ctxs[i], part.map(clip_floats), fs_i, settings.output_level, fs_an, undefined, gather, ...extra);
     };
     // every shard runs to its end before anything else happens (a context with work in flight must not be touched), then the
     // first failure, if any, is what the launch rejects with
@@ -516,8 +524,8 @@ async function run_batches(batches, callback, labels, test_play) {
     const start = (k) => {
       const clips = lists[k];
       const rates = new Set(clips.map((c) => c.sampleRate));
-      if (rates.size !== 1) throw 'All clips of one launch must share a sample rate';
-      const fs = clips[0].sampleRate, fs_an = settings.resample_to > 0 ? settings.resample_to : fs;
+      if (rates.size !== 1 && !(settings.resample_to > 0)) throw 'All clips of one launch must share a sample rate';
+      const fs = rates_of(clips), fs_an = settings.resample_to > 0 ? settings.resample_to : clips[0].sampleRate;
       const g = nat.geometry(ctxs[k % 2], fs_an);
       if (g.bands !== bands) throw 'Bins count mismatch: ' + g.bands + ', ' + bands;          // ref @B8568 check
       const all16 = clips.every((c) => c.pcm16);

@@ -91,7 +91,7 @@ typedef struct {
     wsa_ctx *ctx; uint32_t children;
     /* the planned batch of the last processBatch call: a call with the same clip lengths and rates reuses it (planning a 1024-clip
      * batch allocates GBs of work space: ~3 ms and more); taken out of the box while a job uses it, dropped by destroy() */
-    wsa_batch *plan; uint32_t plan_n; uint32_t *plan_ns; double plan_fs, plan_fs_out;
+    wsa_batch *plan; uint32_t plan_n; uint32_t *plan_ns; double plan_fs, plan_fs_out; double *plan_fs_each;   /* plan_fs_each: one rate per clip (wsa_batch_create_mixed), else NULL */
     /* the context's own HIP stream (wsa_queue_create, made by the first processBatch): every job of the context runs on it, so that the jobs of TWO
      * contexts on one device overlap — the upload of one batch under the kernels of the other — instead of queueing on the device's null stream */
     void *queue;
@@ -106,7 +106,7 @@ static void model_unlink(model_box *mb) {
 }
 static void box_drop_plan(ctx_box *b) {
     if (b->plan) wsa_batch_destroy(b->plan);
-    free(b->plan_ns); b->plan = NULL; b->plan_ns = NULL; b->plan_n = 0;
+    free(b->plan_ns); free(b->plan_fs_each); b->plan = NULL; b->plan_ns = NULL; b->plan_fs_each = NULL; b->plan_n = 0;
 }
 /* the communicator of gatherRows (one at a time; rebuilt when the set of contexts changes, dropped before any of its contexts is destroyed) */
 static wsa_gather *g_gather = NULL; static wsa_ctx **g_gather_ctxs = NULL; static uint32_t g_gather_n = 0;
@@ -234,6 +234,7 @@ static napi_value fn_bins_hz(napi_env env, napi_callback_info info) {
 typedef struct {
     napi_async_work work; napi_deferred deferred;
     wsa_ctx *ctx; double fs; double fs_out;      /* fs_out != fs: convert in front (wsa_batch_create_resampled) */
+    double *fs_each;                             /* one rate per clip (a Float64Array in place of fs): wsa_batch_create_mixed, fs is 0 */
     uint32_t n_clips; uint32_t *n_samples; const float **pcm; napi_ref *clip_refs;
     int is_i16; uint32_t *channels;   /* Int16Array clips (pcm[] then holds int16 pointers): wsa_batch_run_host_i16 */
     wsa_batch *plan; int plan_reused; /* taken from / returned to the box on the JS thread */
@@ -259,7 +260,8 @@ static void job_execute(napi_env env, void *data) {
     }
     j->queue = j->box->queue;
     if (!b) {
-        j->st = (j->fs_out > 0 && j->fs_out != j->fs) ? wsa_batch_create_resampled(j->ctx, j->n_clips, j->n_samples, j->fs, j->fs_out, &b)
+        j->st = j->fs_each ? wsa_batch_create_mixed(j->ctx, j->n_clips, j->n_samples, j->fs_each, j->fs_out, &b)
+              : (j->fs_out > 0 && j->fs_out != j->fs) ? wsa_batch_create_resampled(j->ctx, j->n_clips, j->n_samples, j->fs, j->fs_out, &b)
                                                       : wsa_batch_create(j->ctx, j->n_clips, j->n_samples, j->fs, &b);
         if (j->st != WSA_OK) { snprintf(j->err, sizeof j->err, "%s", wsa_last_error(j->ctx)); return; }
         j->plan = b;
@@ -348,7 +350,7 @@ static void job_complete(napi_env env, napi_status status, void *data) {
     if (j->plan) {                       /* keep the plan for the next call of the same shape (one entry; a failed run drops it) */
         if (j->box && j->box->ctx && j->st == WSA_OK && !j->box->plan) {
             j->box->plan = j->plan; j->box->plan_n = j->n_clips; j->box->plan_fs = j->fs; j->box->plan_fs_out = j->fs_out;
-            j->box->plan_ns = j->n_samples; j->n_samples = NULL;
+            j->box->plan_ns = j->n_samples; j->n_samples = NULL; j->box->plan_fs_each = j->fs_each; j->fs_each = NULL;
         } else wsa_batch_destroy(j->plan);
         j->plan = NULL;
     }
@@ -400,7 +402,7 @@ static void job_complete(napi_env env, napi_status status, void *data) {
     napi_delete_async_work(env, j->work);
     free(j->prob); free(j->cb); free(j->cb_label); free(j->cb_conf); free(j->clip_conf);
     free(j->meta); free(j->feat); free(j->segs); free(j->row_off); free(j->seg_off); free(j->formants); free(j->frame_off); free(j->utt_meta); free(j->utt_feat); free(j->utt_off); free(j->trk_off); free(j->trk_pts); free(j->trk_rank);
-    free(j->n_samples); free((void *)j->pcm); free(j->clip_refs); free(j->channels); free(j);
+    free(j->n_samples); free(j->fs_each); free((void *)j->pcm); free(j->clip_refs); free(j->channels); free(j);
 }
 
 static napi_value fn_process_batch(napi_env env, napi_callback_info info) {
@@ -418,18 +420,26 @@ static napi_value fn_process_batch(napi_env env, napi_callback_info info) {
             if (!ctx || mb->owner != get_box(env, argv[0])) { napi_throw_error(env, NULL, "processBatch: the model belongs to another context"); return NULL; }
         }
     }
+    /* fs: a number, or a Float64Array with one rate per clip (the clips are then converted to analysisRate, each from its own rate) */
+    double *fs_each = NULL; size_t fs_each_n = 0; bool fs_ok = false;
+    if (argc >= 3) {
+        bool ta = false; napi_typedarray_type ft; void *fd = NULL;
+        if (napi_get_value_double(env, argv[2], &fs) == napi_ok) fs_ok = true;
+        else if (napi_is_typedarray(env, argv[2], &ta) == napi_ok && ta && napi_get_typedarray_info(env, argv[2], &ft, &fs_each_n, &fd, NULL, NULL) == napi_ok && ft == napi_float64_array) { fs_each = (double *)fd; fs_ok = true; fs = 0; }
+    }
     if (!ctx || argc < 3 || napi_is_array(env, argv[1], &is_arr) != napi_ok || !is_arr ||
-        napi_get_value_double(env, argv[2], &fs) != napi_ok || napi_get_array_length(env, argv[1], &n) != napi_ok) {
+        !fs_ok || napi_get_array_length(env, argv[1], &n) != napi_ok || (fs_each && fs_each_n != n)) {
         napi_throw_type_error(env, NULL, "processBatch(ctx, Float32Array[] | Int16Array[], fs[, level[, analysisRate[, channels[, deferRows]]]])"); return NULL;
     }
     job_t *j = calloc(1, sizeof *j);
     if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
     if (argc >= 7) { bool d = false; if (napi_get_value_bool(env, argv[6], &d) == napi_ok) j->defer_rows = d ? 1 : 0; }
     j->ctx = ctx; j->fs = fs; j->n_clips = n; j->box = get_box(env, argv[0]); j->model = mb;
+    if (fs_each) { j->fs_each = malloc(sizeof(double) * (n ? n : 1)); if (!j->fs_each) { free(j); napi_throw_error(env, NULL, "out of memory"); return NULL; } memcpy(j->fs_each, fs_each, sizeof(double) * n); }
     if (argc >= 4) { int32_t lv = 0; if (napi_get_value_int32(env, argv[3], &lv) == napi_ok) j->level = lv; }
     if (argc >= 5) { double fo = 0; if (napi_get_value_double(env, argv[4], &fo) == napi_ok) j->fs_out = fo; }           /* analysis rate */   /* the ctx's output_level: 3 adds the raw tracks */
     j->n_samples = calloc(n ? n : 1, sizeof(uint32_t)); j->pcm = calloc(n ? n : 1, sizeof(float *)); j->clip_refs = calloc(n ? n : 1, sizeof(napi_ref));
-    if (!j->n_samples || !j->pcm || !j->clip_refs) { free(j->n_samples); free((void *)j->pcm); free(j->clip_refs); free(j); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    if (!j->n_samples || !j->pcm || !j->clip_refs) { free(j->n_samples); free(j->fs_each); free((void *)j->pcm); free(j->clip_refs); free(j); napi_throw_error(env, NULL, "out of memory"); return NULL; }
     /* clips: all Float32Array (mono floats) or all Int16Array (16-bit PCM as a WAV file holds it, interleaved over channels[i] channels
      * given by the optional 6th argument, a Uint32Array; channel 0 is analysed and the conversion runs on the device) */
     uint32_t *chan = NULL; size_t chan_len = 0;
@@ -445,7 +455,7 @@ static napi_value fn_process_batch(napi_env env, napi_callback_info info) {
         else if (i > 0 && (tt == napi_int16_array) != (j->is_i16 != 0)) bad = "the clips of one batch must be of one kind";
         if (bad) {
             for (uint32_t k = 0; k < i; k++) napi_delete_reference(env, j->clip_refs[k]);
-            free(j->n_samples); free((void *)j->pcm); free(j->clip_refs); free(j->channels); free(j);
+            free(j->n_samples); free(j->fs_each); free((void *)j->pcm); free(j->clip_refs); free(j->channels); free(j);
             napi_throw_type_error(env, NULL, bad); return NULL;
         }
         if (i == 0) { j->is_i16 = tt == napi_int16_array; if (j->is_i16) j->channels = calloc(n, sizeof(uint32_t)); }
@@ -456,9 +466,9 @@ static napi_value fn_process_batch(napi_env env, napi_callback_info info) {
     }
     /* a plan of exactly this shape waiting in the box?  (one job at a time uses a context: the plan leaves the box while it runs) */
     if (j->box->plan) {
-        int same = j->box->plan_n == n && j->box->plan_fs == j->fs && j->box->plan_fs_out == j->fs_out;
-        for (uint32_t i = 0; same && i < n; i++) same = j->box->plan_ns[i] == j->n_samples[i];
-        if (same) { j->plan = j->box->plan; j->plan_reused = 1; j->box->plan = NULL; free(j->box->plan_ns); j->box->plan_ns = NULL; j->box->plan_n = 0; }
+        int same = j->box->plan_n == n && j->box->plan_fs == j->fs && j->box->plan_fs_out == j->fs_out && (j->box->plan_fs_each != NULL) == (j->fs_each != NULL);
+        for (uint32_t i = 0; same && i < n; i++) same = j->box->plan_ns[i] == j->n_samples[i] && (!j->fs_each || j->box->plan_fs_each[i] == j->fs_each[i]);
+        if (same) { j->plan = j->box->plan; j->plan_reused = 1; j->box->plan = NULL; free(j->box->plan_ns); free(j->box->plan_fs_each); j->box->plan_ns = NULL; j->box->plan_fs_each = NULL; j->box->plan_n = 0; }
         else box_drop_plan(j->box);
     }
     napi_value promise, name;
