@@ -54,7 +54,10 @@ def designed_clip(name, frames, bands=128):
     gate_sweep  five steady ridges whose level ramps over 7.5 decades and back, in bursts separated by pauses, so that the auto noise
                 gate C(h) (ref @B28506) walks ctx_max through every branch of its piecewise floor (log10(y) = 1, 2, 4, 6, 7, ref @B28615)
     syl_edges   one long segment whose energy is on for u = 5 / 11 / 21 frames and off for 1 / 2 / 5 frames in every combination: the
-                run / gap rule of sep_syllables (ref @B34864: (u>20 && c>0) || (u>10 && c>1) || (u>0 && c>4) || (last && u>4))"""
+                run / gap rule of sep_syllables (ref @B34864: (u>20 && c>0) || (u>10 && c>1) || (u>0 && c>4) || (last && u>4))
+    long_voiced three steady, slowly wobbling ridges over the whole clip but ten frames at either end, with a short dip below half the level every 37
+                frames (one energy event of formant_features, ref @B32369, each): at a 10 ms step ONE segment of nearly `frames` frames, and at
+                level 13 one syllable nearly as long — spans past the 2048 frames that the block-event feature reduction of the tracker takes"""
     rng = np.random.default_rng(12345)
     base = _ridges(1, bands, [14, 27, 43, 61, 80, 99], [1.6, 2.0, 2.2, 2.6, 3.0, 3.0], [1.0, 0.25, 0.2, 0.15, 0.1, 0.1])[0]   # one dominant ridge: the start test (ref @B26527) wants h (n - 1) / (d - h) > 4
     spec = np.zeros((frames, bands))
@@ -80,6 +83,20 @@ def designed_clip(name, frames, bands=128):
                     spec[f:f + u] = 3.0e4 * (1.0 + 0.2 * np.sin(np.arange(u) + rep))[:, None] * base[None, :]
                     f += u + gap
         spec += rng.uniform(0, 1.5, spec.shape)
+    elif name == "long_voiced":
+        rng = np.random.default_rng(frames)
+        k = np.arange(bands)[None, :]
+        lead = 10
+        n = frames - 2 * lead
+        t = np.arange(n)
+        env = np.ones(n)
+        for a in range(20, n - 10, 37):          # a peak, then a fall below half of it: one energy event per 37 frames
+            env[a:a + int(rng.integers(2, 6))] *= rng.uniform(0.15, 0.4)
+        for j, c0 in enumerate((0.15, 0.4, 0.7)):
+            c = bands * c0 + 3 * np.sin(2 * np.pi * t / (90 + 17 * j))
+            amp = 1e5 * 10 ** (-0.3 * j) * (1 + 0.2 * np.sin(t / (11.0 + j)))
+            spec[lead:lead + n] += (env * amp)[:, None] * np.exp(-0.5 * ((k - c[:, None]) / 1.8) ** 2)
+        spec += rng.uniform(0, 30, spec.shape)
     else:
         raise KeyError(name)
     return np.minimum(spec, 4294967295.0).astype(np.uint32)

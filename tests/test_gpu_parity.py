@@ -724,6 +724,83 @@ def test_long_segments_in_and_out_of_lds(wsa, monkeypatch, level):
         assert ok, f"clip {i} vs the generic path: {why}"
 
 
+LONG_FRAMES = (2000, 2100, 2600, 4500, 9000)
+LONG_SETTINGS = dict(window_step=10.0, pause_length=200.0, min_seg_length=50.0, auto_noise_gate=1, voiced_max_dB=100.0, voiced_min_dB=10.0)
+
+
+def _span_canary(frames):
+    """The 1e-12 canary of test_backend_matches_reference_fixtures (spans of up to 128 frames), scaled with the span: a sum's rounding error grows at most
+    linearly with the number of its terms."""
+    return 1e-12 * max(1.0, frames / 128.0)
+
+
+@pytest.mark.parametrize("level", [5, 13, 10, 11])
+def test_spans_past_2048_frames_vs_oracle(wsa, monkeypatch, level):
+    """One voiced span of 1980 ... 8980 frames per clip (designed_clip "long_voiced" at a 10 ms step; 2048 frames are 20 s without a pause: music, a
+    sustained tone), and at level 13 one syllable nearly as long.  The block-event feature reduction keeps one event bit per 64-frame block in a 32-bit
+    word, so spans past 2048 frames must not take it: segments and syllables equal the oracle's exactly, the rows to 1e-4 and to the length-scaled
+    canary, on the default path and with the generic finalize forced for every span (WSA_DBG bit 256)."""
+    from oracle import pyoracle
+    import sys
+    sys.path.insert(0, os.path.join(GOLDEN, "gen"))
+    from synth_spectra import designed_clip
+    from tests.util import feature_events
+    clips = [designed_clip("long_voiced", f) for f in LONG_FRAMES]
+    ref = [pyoracle.run_backend(c, pyoracle.default_cfg(level=level, **LONG_SETTINGS)) for c in clips]
+    # what the clips are built for, asserted on the oracle's side before the GPU is looked at
+    for f, c, r in zip(LONG_FRAMES, clips, ref):
+        assert len(r["segments_ci"]) == 1 and r["segments_ci"][0][1] >= f - 40 and len(r["callbacks"]) == 1, f
+        syl = pyoracle.run_backend(c, pyoracle.default_cfg(level=13, **LONG_SETTINGS))["syllables_ci"][0]
+        assert f < 2100 or max(sl for _, sl in syl) > 2048, (f, syl)
+        frames4 = pyoracle.run_backend(c, pyoracle.default_cfg(level=4, **LONG_SETTINGS))["formants"][0]
+        assert min(feature_events(frames4)) >= 40, (f, feature_events(frames4))
+    for tag, dbg in (("default", None), ("generic", "256")):
+        monkeypatch.delenv("WSA_DBG", raising=False)
+        if dbg:
+            monkeypatch.setenv("WSA_DBG", dbg)
+        out = _run_backend_on(wsa, clips, LONG_SETTINGS, level)
+        monkeypatch.delenv("WSA_DBG", raising=False)
+        for f, r, g in zip(LONG_FRAMES, ref, out):
+            assert r["segments_ci"] == g["segments_ci"], (tag, f)
+            if level in (10, 11):
+                ok, why = callbacks_equal(level, r["callbacks"], g["callbacks"])
+                assert ok, f"{tag}, {f} frames: {why}"
+                continue
+            for name, tol in (("contract", 1e-4), ("canary", _span_canary(r["segments_ci"][0][1]))):
+                ok, why = callbacks_equal(level, r["callbacks"], g["callbacks"], exact=False, tol=tol)
+                if not ok:      # the features that differ, for the report
+                    a = np.asarray(r["callbacks"][0][3], np.float64).reshape(-1, 53)
+                    b = np.asarray(g["callbacks"][0][3], np.float64).reshape(-1, 53)
+                    rel = np.abs(a - b) / np.maximum(np.abs(a), 1e-6) if a.shape == b.shape else None
+                    why += f"; features off by more than {tol:.3g}: {[(int(i), int(j), float(rel[i, j])) for i, j in zip(*np.nonzero(rel > tol))][:12] if rel is not None else 'row count'}"
+                assert ok, f"{tag}, {f} frames, level {level} ({name} {tol:.3g}): {why}"
+
+
+@pytest.mark.parametrize("level", [5, 13])
+def test_long_voiced_audio_vs_oracle(wsa, level):
+    """26 s of audio without a pause (tests.util.long_voiced_audio; 25 ms windows every 10 ms) through the whole batch path: one span of some 2500 frames
+    with dozens of energy events, against the oracle."""
+    from oracle import pyoracle
+    from tests.util import feature_events, long_voiced_audio
+    fs = 16000
+    kw = dict(window_width=25.0, window_step=10.0)
+    sig = long_voiced_audio()
+    spec = pyoracle.FrontEnd(pyoracle.fe_cfg(fs=float(fs), **kw)).run(sig)
+    ref = pyoracle.run_backend(spec, pyoracle.default_cfg(level=level, window_step=10.0))
+    frames4 = pyoracle.run_backend(spec, pyoracle.default_cfg(level=4, window_step=10.0))["formants"][0]
+    assert len(ref["segments_ci"]) == 1 and ref["segments_ci"][0][1] > 2400 and sorted(feature_events(frames4))[1] >= 40, (ref["segments_ci"], feature_events(frames4))
+    pcm = torch.from_numpy(sig[None, :]).cuda().contiguous()
+    an = wsa.Analyzer(wsa.Config(output_level=level, **kw))
+    b = an.batch([len(sig)], fs)
+    b.run(pcm.data_ptr(), pcm.stride(0), _stream())
+    got = b.callbacks(_stream())[0]
+    b.close(); an.close()
+    assert ref["segments_ci"] == got["segments_ci"]
+    for tol in (1e-4, _span_canary(ref["segments_ci"][0][1])):
+        ok, why = callbacks_equal(level, ref["callbacks"], got["callbacks"], exact=False, tol=tol)
+        assert ok, f"tolerance {tol:.3g}: {why}"
+
+
 def test_c_abi_error_paths(wsa):
     """Bad arguments and unsupported configurations come back as error codes with a message, never as a crash
     or a silently different computation."""
@@ -802,7 +879,7 @@ def test_backend_level_11_utterance_features(wsa):
 
 
 def test_packed_feature_columns_equal_the_column_loop(wsa, monkeypatch):
-    """tracker.hip formant_columns_packed: inputs of at most 15 frames (half of level 13's syllables) take all three formant columns through the feature
+    """tracker_features.hpp formant_columns_packed: inputs of at most 15 frames (half of level 13's syllables) take all three formant columns through the feature
     sums at once (lane 16 n + t = frame t of column n); every sum keeps the tree it has in the one-column-at-a-time loop, so the rows are the same bit
     for bit.  WSA_DBG bit 65536 switches the packed form off."""
     from webspeechanalyzer_amd.synth import synth_clips
@@ -857,7 +934,7 @@ def test_persistent_front_end_equals_one_chunk_per_workgroup(wsa, monkeypatch, f
 
 
 def test_event_walk_equals_the_block_scan(wsa, monkeypatch):
-    """tracker.hip formant_features_lds: the energy peak-then-halve events of inputs of at most 128 frames come from three lanes walking the three formant
+    """tracker_features.hpp formant_features_lds: the energy peak-then-halve events of inputs of at most 128 frames come from three lanes walking the three formant
     columns frame by frame (the reference's own walk); longer inputs — and every input under WSA_DBG bit 131072 — take energy_events_block (a max-scan
     per run and event).  Same fp32 comparisons: the rows must be the same bit for bit, segments (level 5) and syllables (level 13), also with overlapping
     windows (longer segments, some beyond 64 frames)."""

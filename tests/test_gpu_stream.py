@@ -223,6 +223,48 @@ def test_stream_span_longer_than_ring_is_cut_for_that_stream_only(wsa):
     assert ok, why
 
 
+def test_stream_span_past_2048_frames_with_and_without_room(wsa):
+    """26 s of audio without a pause (tests.util.long_voiced_audio, 25 ms windows every 10 ms: one span of some 2500 frames with dozens of energy events).
+    A stream created with max_span_frames = 4096 holds the span and gives the oracle's rows at levels 5 and 13; one created with 512 (a ring of 1024
+    frames) cuts it and raises WSA_FLAG_STREAM_CUT in exactly the steps in which its cut counter moved."""
+    from oracle import pyoracle
+    from tests.util import feature_events, long_voiced_audio
+    fs, F = 16000, 16
+    kw = dict(window_width=25.0, window_step=10.0)
+    sig = long_voiced_audio()
+    pcm = torch.from_numpy(sig[None, :]).cuda().contiguous()
+    fe = pyoracle.FrontEnd(pyoracle.fe_cfg(fs=float(fs), **kw))
+    span = None
+    for level in (5, 13):
+        got, segs, used = _run_streams(wsa, pcm, fs, level, F, True, False, cfg_kw=kw, max_span=4096)
+        spec = fe.run(sig[:used])
+        ref = pyoracle.run_backend(spec, pyoracle.default_cfg(level=level, window_step=10.0))
+        frames4 = pyoracle.run_backend(spec, pyoracle.default_cfg(level=4, window_step=10.0))["formants"][0]
+        span = ref["segments_ci"][0][1]
+        assert len(ref["segments_ci"]) == 1 and span > 2400 and sorted(feature_events(frames4))[1] >= 40, (ref["segments_ci"], feature_events(frames4))
+        assert ref["segments_ci"] == segs[0]
+        for tol in (1e-4, 1e-12 * span / 128.0):          # the contract, and the 1e-12 canary of spans of up to 128 frames scaled with the span
+            ok, why = callbacks_equal(level, ref["callbacks"], got[0], exact=False, tol=tol)
+            assert ok, f"level {level}, tolerance {tol:.3g}: {why}"
+    an = wsa.Analyzer(wsa.Config(output_level=5, **kw))
+    st = an.streams(1, fs, frames_per_step=F, max_span_frames=512)
+    sps = st.samples_per_step
+    nsteps = pcm.shape[1] // sps
+    seg0, cuts, nflag = [], None, 0
+    for k in range(nsteps):
+        buf = pcm[:, k * sps:(k + 1) * sps].contiguous()
+        ctl = np.full(1, wsa.ACTIVE | (wsa.START if k == 0 else 0) | (wsa.STOP if k == nsteps - 1 else 0), np.uint8)
+        st.step(buf.data_ptr(), buf.stride(0), ctl, _stream())
+        r = st.collect(_stream())
+        assert bool(r["flags"] & 8) == (cuts is not None and (r["cuts"] != cuts).any()) or (cuts is None and bool(r["flags"] & 8) == bool(r["cuts"].any()))
+        nflag += 1 if r["flags"] & 8 else 0
+        cuts = r["cuts"]
+        seg0 += [[int(g[1]), int(g[2])] for g in r["segments"] if g[0] == 0]
+    st.close(); an.close()
+    assert cuts[0] >= 2 and nflag == cuts[0]
+    assert len(seg0) >= 3 and max(l for _, l in seg0) <= 1024 and sum(l for _, l in seg0) > 0.8 * span
+
+
 @pytest.mark.parametrize("seed", list(range(1, 13)))
 def test_stream_random_settings_vs_oracle(wsa, seed):
     """Random rate / hop / window / frames per step / level / graph on or off: stream rows == oracle on the whole signal."""

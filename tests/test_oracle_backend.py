@@ -77,6 +77,31 @@ def test_fuzz_against_reference_fixtures():
         assert ok, why
 
 
+def test_long_span_against_reference_fixture():
+    """One voiced span of 2580 frames (designed_clip "long_voiced", 2600 frames at a 10 ms step; at level 13 one syllable nearly as long, 69 energy
+    events per formant column) at levels 5 and 13: what the reference itself returned (tests/golden/gen/make_long_golden.py) vs the oracle, bit for
+    bit — the oracle is the reference of the GPU tests of spans past 2048 frames.  The committed spectrum is what the generator's recipe gives today."""
+    import sys
+    sys.path.insert(0, os.path.join(GOLDEN, "gen"))
+    from synth_spectra import designed_clip
+    spectra = np.load(os.path.join(GOLDEN, "long_spectra.npz"))
+    d = json.load(open(os.path.join(GOLDEN, "long_expected.json")))
+    s = d["settings"]
+    assert [c["level"] for c in d["cases"]] == [5, 13]
+    for c in d["cases"]:
+        spec = spectra[c["key"]]
+        assert np.array_equal(spec, designed_clip("long_voiced", len(spec)))
+        out = pyoracle.run_backend(spec, pyoracle.default_cfg(level=c["level"], window_step=float(s["window_step"]), pause_length=float(s["pause_length"]),
+                                                               min_seg_length=float(s["min_seg_length"]), auto_noise_gate=s["auto_noise_gate"],
+                                                               voiced_max_dB=float(s["voiced_max_dB"]), voiced_min_dB=float(s["voiced_min_dB"])))
+        assert out["segments_ci"] == c["segments_ci"] == [[20, 2580]]
+        assert len(c["callbacks"]) == 1
+        ok, why = callbacks_equal(c["level"], c["callbacks"], out["callbacks"], exact=True)
+        assert ok, why
+        if c["level"] == 13:
+            assert max(sl for _, sl in out["syllables_ci"][0]) > 2048
+
+
 def test_match_score_function_level():
     """G2: the tracker's match score `_` (ref dist/main.js:2 @B37340) on 6 000 argument rows around every branch (amplitude ratio .1 / .001 / 1,
     bin distance against velocity, track length 10, gaps 0..3 inside their windows) — the reference's own function under Node

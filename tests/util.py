@@ -104,3 +104,44 @@ def callbacks_equal(level, ref_cbs, got_cbs, exact=True, tol=1e-4):
             if not same_f64(a, np.asarray(o[3], dtype=np.float64)):
                 return False, f"si {r[0]} formant frames differ"
     return True, ""
+
+
+def feature_events(fr9):
+    """Energy events per formant column of [n, 9] straightened frames: the peak-then-halve walk of the reference's formant_features
+    (ref dist/main.js:2 @B32369), counts only."""
+    counts = []
+    for n in range(3):
+        prev, S, L, c = False, 0, 0.0, 0
+        for r, E in zip(np.asarray(fr9)[:, 3 * n].tolist(), np.asarray(fr9)[:, 3 * n + 1].tolist()):
+            if r > 0 and E > 0:
+                if prev:
+                    if E > L:
+                        L, S = E, 1
+                    elif S == 1 and E < L / 2:
+                        c += 1 if L > 10 else 0
+                        L, S = 0.0, -1
+                prev = True
+            else:
+                prev, S, L = False, 0, 0.0
+        counts.append(c)
+    return counts
+
+
+def long_voiced_audio(seconds=26.0, fs=16000):
+    """Three frequency-wobbled sines at 420 / 1150 / 2300 Hz without a pause, the amplitude down to 0.15 - 0.4 of itself for 30 - 60 ms every 0.37 s (an
+    energy event of formant_features each), 0.1 s of silence at both ends: one voiced span as long as the clip."""
+    rng = np.random.default_rng(2600)
+    n = int(seconds * fs)
+    t = np.arange(n) / fs
+    env = np.ones(n)
+    for a in np.arange(0.5, seconds - 0.3, 0.37):
+        i = int(a * fs)
+        env[i:i + int(rng.uniform(0.03, 0.06) * fs)] *= rng.uniform(0.15, 0.4)
+    sig = np.zeros(n)
+    for j, (f0, amp) in enumerate(((420.0, 0.3), (1150.0, 0.2), (2300.0, 0.12))):
+        phase = 2 * np.pi * np.cumsum(f0 * (1 + 0.02 * np.sin(2 * np.pi * t / (0.9 + 0.17 * j)))) / fs
+        sig += amp * np.sin(phase)
+    sig *= env
+    lead = int(0.1 * fs)
+    sig[:lead] = 0; sig[n - lead:] = 0
+    return sig.astype(np.float32)

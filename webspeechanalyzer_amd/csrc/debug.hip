@@ -5,6 +5,7 @@
 #include "jsmath_device.hpp"
 #include "gate_floor.hpp"
 #include "tracker_score.hpp"
+#include "tracker_features.hpp"
 
 namespace wsa {
 // fn 0: jsm::log10(x[i]); fn 1: jsm::pow_pos(x[i], y[i]) — the V8 Math.log10 / Math.pow ports the noise gate's
@@ -33,6 +34,27 @@ __global__ void debug_floor_law_kernel(uint64_t lo, uint64_t hi, unsigned long l
     }
     if (bad) { atomicAdd(&out[0], bad); atomicMin(&out[1], first); }
     if (exact) atomicAdd(&out[2], exact);
+}
+
+// the 53-feature reduction on its own: ONE wavefront over n frames of nine floats.  SEL 0: formant_features_wave (frames and the event list in global
+// memory); 1: formant_features_lds, frames in LDS, walking events; 2: the same with block events (no_walk); 3: block events with the frames read from
+// global memory (as the generic finalize calls it for spans that do not fit its LDS block); 4: the packed form.  Writes x[5 .. 52] like the tracker's calls.
+constexpr int DBG_FEAT_LDS_FRAMES = 1024;           // frames the test kernel holds in LDS (36 KB; the tracker's own blocks hold up to 288)
+static_assert(DBG_FEAT_LDS_FRAMES <= FEAT_LDS_MAX, "selector 2 stays inside formant_features_lds's domain");
+template <int SEL>
+__global__ __launch_bounds__(64) void debug_features_kernel(const float* fr_g, int n, double ctx_max, double* x, double* aev) {
+    constexpr int LDSF = SEL == 2 ? DBG_FEAT_LDS_FRAMES : (SEL == 1 ? 128 : (SEL == 4 ? 16 : 1));
+    __shared__ __attribute__((aligned(16))) float s_fr[LDSF * 9];
+    __shared__ __attribute__((aligned(16))) double s_red[FEAT_SCRATCH];
+    const int lane = threadIdx.x;
+    if (SEL == 0) { formant_features_wave(fr_g, n, ctx_max, x, aev, n + 2, lane); return; }
+    const float* fr = fr_g;
+    if (SEL != 3) {
+        for (int q = lane; q < 9 * n && q < 9 * LDSF; q += 64) s_fr[q] = fr_g[q];
+        wsync();
+        fr = s_fr;
+    }
+    formant_features_lds(fr, n, ctx_max, x, lane, s_red, SEL == 4, SEL == 2 || SEL == 3);
 }
 }  // namespace wsa
 
@@ -78,6 +100,31 @@ extern "C" int wsa_debug_jsmath(int32_t device, int32_t fn, const double* x, con
         ok = hipGetLastError() == hipSuccess && hipMemcpy(out, dout, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
     }
     (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(dout);
+    return ok ? WSA_OK : WSA_ERR_HIP;
+}
+
+// selector: see debug_features_kernel; a selector outside its variant's domain (1: n <= 128, 2: n <= DBG_FEAT_LDS_FRAMES, 3: n <= FEAT_LDS_MAX, 4: n <= 15) is refused, never run.
+// frames9 = n x [bin, energy, width] x 3 (host), out53 (host): [5 .. 52] are what the device function writes, [0 .. 4] (the caller's in the tracker) stay 0
+extern "C" int wsa_debug_features(int32_t device, const float* frames9, uint32_t n, double ctx_max, int32_t selector, double* out53) {
+    if (!frames9 || !out53 || n < 1 || n > (1u << 24) || selector < 0 || selector > 4) return WSA_ERR_INVALID;
+    if ((selector == 1 && n > 128) || (selector == 2 && n > (uint32_t)wsa::DBG_FEAT_LDS_FRAMES) || (selector == 3 && n > (uint32_t)wsa::FEAT_LDS_MAX) || (selector == 4 && n > 15)) return WSA_ERR_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return WSA_ERR_NO_DEVICE;
+    float* dfr = nullptr; double *dx = nullptr, *daev = nullptr;
+    const size_t nfr = (size_t)n * 9 * sizeof(float), naev = (size_t)3 * (n + 2) * sizeof(double);
+    bool ok = hipMalloc(&dfr, nfr) == hipSuccess && hipMalloc(&dx, 53 * sizeof(double)) == hipSuccess && hipMalloc(&daev, naev) == hipSuccess;
+    ok = ok && hipMemcpy(dfr, frames9, nfr, hipMemcpyHostToDevice) == hipSuccess && hipMemset(dx, 0, 53 * sizeof(double)) == hipSuccess && hipMemset(daev, 0, naev) == hipSuccess;
+    if (ok) {
+        const int a = (int)n;
+        switch (selector) {
+        case 0: hipLaunchKernelGGL(wsa::debug_features_kernel<0>, dim3(1), dim3(64), 0, nullptr, dfr, a, ctx_max, dx, daev); break;
+        case 1: hipLaunchKernelGGL(wsa::debug_features_kernel<1>, dim3(1), dim3(64), 0, nullptr, dfr, a, ctx_max, dx, daev); break;
+        case 2: hipLaunchKernelGGL(wsa::debug_features_kernel<2>, dim3(1), dim3(64), 0, nullptr, dfr, a, ctx_max, dx, daev); break;
+        case 3: hipLaunchKernelGGL(wsa::debug_features_kernel<3>, dim3(1), dim3(64), 0, nullptr, dfr, a, ctx_max, dx, daev); break;
+        default: hipLaunchKernelGGL(wsa::debug_features_kernel<4>, dim3(1), dim3(64), 0, nullptr, dfr, a, ctx_max, dx, daev); break;
+        }
+        ok = hipGetLastError() == hipSuccess && hipMemcpy(out53, dx, 53 * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    (void)hipFree(dfr); (void)hipFree(dx); (void)hipFree(daev);
     return ok ? WSA_OK : WSA_ERR_HIP;
 }
 
