@@ -439,6 +439,63 @@ typedef struct {
  * WSA_ERR_INVALID without an attached model. */
 wsa_status wsa_stream_classes(wsa_stream *st, wsa_stream_class_result *out);
 
+/*
+ * ---- Streams of different rates, converted inside the step (additions within version 5: probe for wsa_stream_create_mixed).
+ * Stream i arrives at fs_in[i] and is analysed at fs_out: the conversion RS-1 (wsa_batch_create_resampled above) runs as a
+ * kernel of the step (K0s) with per-stream state carried on the device, so that a stream fed a signal in pieces gives exactly the rows
+ * wsa_batch_create_mixed gives for the whole signal.  This has no counterpart in the reference: its live path (ref dist/main.js:2 @B8752)
+ * runs at whatever rate the audio hardware has and converts nothing; only its offline path sees converted samples, because the browser
+ * decodes every file into the 48 kHz context (@B18769).  Like `resample_to` for batches it is ours: it lets a live 44.1 kHz or 16 kHz
+ * source be analysed with the geometry — and the classifier of wsa_stream_set_model be fed the features — of the 48 kHz files the shipped
+ * models were trained on, and lets sources of different rates share one lock-step set.
+ *
+ * Per stream, counted since its last START: N input samples received, Y converted samples handed to the front end, K frames analysed;
+ * ratio = fs_in[i] / fs_out in double, exactly as K0 forms it.
+ *   - Output n is READY when every tap RS-1 reads for it has arrived: floor((double)n * ratio) + 16 <= N (taps before sample 0 are RS-1's
+ *     zeros).  Its value is the one the batch computes (position from the absolute index n, same table, same order of operations), so
+ *     nothing is ever revised.  A step hands on all ready outputs, never more than wsa_resample_length(N, ...): wsa_resample_ready.
+ *   - STOP, after the step's samples are counted: the outputs up to wsa_resample_length(N, ...) are produced with zeros for the taps at or
+ *     beyond N (as a batch pads a clip's end), the frames they complete are analysed, then segment_truncate as for any stream.
+ *   - fs_in[i] == fs_out: the stream is copied, not filtered, and has no look-ahead (the rule of wsa_batch_create_mixed).  A set whose
+ *     streams all sit at fs_out, fed frames_per_step * hop samples per step, gives the rows of a wsa_stream_create set in the same steps.
+ *   - Frame k is y[k * hop, k * hop + win) of the converted signal and is analysed in the step in which Y reaches k * hop + win — the
+ *     batch's frames.  A step analyses ALL frames that became complete; there is no backlog.
+ *   - A step accepts n_in[i] <= wsa_stream_input_capacity(st, i) = ceil(frames_per_step * hop * ratio) samples of stream i (more:
+ *     WSA_ERR_INVALID naming the stream); 0 on an active stream is legal.  A host that sends the capacity every step completes
+ *     frames_per_step + 1 frames in a step now and then, and a STOP step adds the tail (about 16 / ratio outputs); the step's internal
+ *     frame capacity is derived from that (wsa_stream_frames_bound), not from frames_per_step.
+ *   - n_in == NULL: PACED input, every active stream delivers what keeps it on real time, floor((s + 1) * F * hop * ratio) -
+ *     floor(s * F * hop * ratio) samples in its s-th active step since START (1102 / 1103 alternating at 44.1 -> 48 kHz, 25 ms steps);
+ *     wsa_stream_paced_input tells the next count.  Paced streams never exceed frames_per_step frames per step.
+ *   - START resets N, Y, K, the input history and the carried converted samples; idle streams keep everything; after STOP a stream needs
+ *     START.  Control bytes, cuts (WSA_FLAG_STREAM_CUT), rows and wsa_stream_collect are those of any stream set.
+ *   - Rates: each positive and within a factor 16 of fs_out, else WSA_ERR_INVALID naming the stream; any number of distinct rates.
+ * The host decides every count (N, Y, K, the step's outputs, the carried samples, the frames): integer bookkeeping and the one predicate
+ * above, written into the step's mapped control words.  The device never decides how many outputs exist, and the captured graph is
+ * replayed unchanged whatever the counts are.  wsa_stream_step / wsa_stream_step_host on a mixed set are the _n forms with n_in == NULL;
+ * the _n forms on a plain set accept NULL or exactly samples_per_step for every active stream.  wsa_stream_samples_per_step is
+ * frames_per_step * hop (samples at fs_out); wsa_stream_host_input is [n_streams][wsa_stream_input_stride] floats, stream i's samples of
+ * the step at the start of its row; wsa_stream_time_steps takes feed blocks of that shape and steps paced.  wsa_stream_set_model and every
+ * output level streams serve work unchanged.
+ */
+wsa_status wsa_stream_create_mixed(wsa_ctx *ctx, uint32_t n_streams, const double *fs_in, double fs_out, uint32_t frames_per_step,
+                                   uint32_t max_span_frames, wsa_stream **out);
+uint32_t   wsa_stream_input_capacity(const wsa_stream *st, uint32_t stream);   /* samples one step accepts (a plain set: samples_per_step) */
+uint32_t   wsa_stream_input_stride(const wsa_stream *st);                      /* floats per stream in the pinned input buffer */
+uint32_t   wsa_stream_paced_input(const wsa_stream *st, uint32_t stream);      /* what n_in == NULL takes in the next step (without a START in it) */
+uint32_t   wsa_stream_step_frame_capacity(const wsa_stream *st);               /* frames per stream the step is sized for (a plain set: frames_per_step) */
+/* stream i's n_in[i] samples at d_pcm + i * stream_stride (stream_stride >= the largest count of the step) */
+wsa_status wsa_stream_step_n(wsa_stream *st, const float *d_pcm, uint64_t stream_stride, const uint32_t *n_in, const uint8_t *ctl, void *stream);
+wsa_status wsa_stream_step_host_n(wsa_stream *st, const uint32_t *n_in, const uint8_t *ctl, void *stream);
+/* pure: the outputs of the first n_in samples that are ready (the rule above, clamp included; n_in at equal rates) */
+uint64_t   wsa_resample_ready(uint64_t n_in, double fs_in, double fs_out);
+/* pure: the frames one step can complete at most, for frames_per_step, the hop in samples at fs_out and the smallest fs_in / fs_out of the
+ * set's converted streams (0: every stream at fs_out): ceil((frames_per_step * hop + ceil(16 / min_ratio) + 3) / hop) */
+uint32_t   wsa_stream_frames_bound(uint32_t frames_per_step, uint32_t hop, double min_ratio);
+/* after wsa_stream_collect: the converted samples the last step produced (the copied ones of a stream at fs_out), out [n_streams][cap]
+ * floats, counts [n_streams]; either may be NULL.  WSA_ERR_INVALID if a stream produced more than cap. */
+wsa_status wsa_stream_copy_converted(wsa_stream *st, float *out, uint32_t cap, uint32_t *counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,9 +117,13 @@ ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destr
                # additions within version 5 (probe for wsa_model_create): the app's syllable classifier
                "wsa_model_create", "wsa_model_destroy", "wsa_classify_rows", "wsa_batch_classify", "wsa_batch_class_result", "wsa_batch_copy_classes",
                # additions within version 5 (probe for wsa_stream_set_model): the classifier inside the stream step
-               "wsa_stream_set_model", "wsa_stream_classes"]
+               "wsa_stream_set_model", "wsa_stream_classes",
+               # additions within version 5 (probe for wsa_stream_create_mixed): streams of different rates, converted inside the step
+               "wsa_stream_create_mixed", "wsa_stream_input_capacity", "wsa_stream_input_stride", "wsa_stream_paced_input", "wsa_stream_step_frame_capacity",
+               "wsa_stream_step_n", "wsa_stream_step_host_n", "wsa_resample_ready", "wsa_stream_frames_bound", "wsa_stream_copy_converted"]
 
 _LIB = None
+_U32_RESULT = ("wsa_stream_input_capacity", "wsa_stream_paced_input", "wsa_stream_input_stride", "wsa_stream_step_frame_capacity", "wsa_stream_frames_bound")
 
 
 def library_path():
@@ -209,7 +213,22 @@ def lib():
     L.wsa_batch_copy_classes.argtypes = [vp, vp, vp, u32, vp, vp, vp, u32, vp]
     L.wsa_stream_set_model.argtypes = [vp, vp]
     L.wsa_stream_classes.argtypes = [vp, ctypes.POINTER(_StreamClassResult)]
+    L.wsa_stream_create_mixed.argtypes = [vp, u32, vp, dbl, u32, u32, ctypes.POINTER(vp)]
+    for name in ("wsa_stream_input_capacity", "wsa_stream_paced_input"):
+        getattr(L, name).argtypes = [vp, u32]
+    for name in ("wsa_stream_input_stride", "wsa_stream_step_frame_capacity"):
+        getattr(L, name).argtypes = [vp]
+    L.wsa_stream_frames_bound.argtypes = [u32, u32, dbl]
+    for name in _U32_RESULT:
+        getattr(L, name).restype = u32
+    L.wsa_stream_step_n.argtypes = [vp, vp, u64, vp, vp, vp]
+    L.wsa_stream_step_host_n.argtypes = [vp, vp, vp, vp]
+    L.wsa_resample_ready.argtypes = [u64, dbl, dbl]
+    L.wsa_resample_ready.restype = ctypes.c_uint64
+    L.wsa_stream_copy_converted.argtypes = [vp, vp, u32, vp]
     for name in ABI_SYMBOLS:
+        if name in _U32_RESULT or name == "wsa_resample_ready":
+            continue
         if name not in ("wsa_abi_version", "wsa_last_error", "wsa_config_default", "wsa_destroy", "wsa_batch_destroy", "wsa_resample_length",
                         "wsa_stream_destroy", "wsa_stream_samples_per_step", "wsa_stream_host_input", "wsa_gather_destroy", "wsa_host_free",
                         "wsa_model_destroy"):
@@ -270,8 +289,10 @@ class Analyzer:
         sequence with one rate per clip (a folder of files of different rates in one launch)."""
         return Batch(self, n_samples, fs, resample_to)
 
-    def streams(self, n_streams, fs, frames_per_step=1, max_span_frames=1024):
-        return Streams(self, n_streams, fs, frames_per_step, max_span_frames)
+    def streams(self, n_streams, fs, frames_per_step=1, max_span_frames=1024, resample_to=None):
+        """resample_to: analysis rate of a set whose streams arrive at `fs` — one rate, or a sequence with one rate per stream — and are
+        converted inside the step (spec RS-1, wsa_stream_create_mixed); streams already at resample_to pass unfiltered."""
+        return Streams(self, n_streams, fs, frames_per_step, max_span_frames, resample_to)
 
     def load_model(self, src):
         """The app's trained classifier on this context's device: `src` = a directory as dist/nnmodel/<db>/cats_<label>/ ships it, a
@@ -605,20 +626,53 @@ class Streams:
     """n concurrent launches advancing in lock step (wsa_stream): the reference's online path — one
     spectrum_push per frame with carried state, callbacks as segments close (dist/main.js:2 @B8752, @B28869)."""
 
-    def __init__(self, an, n_streams, fs, frames_per_step=1, max_span_frames=1024):
+    def __init__(self, an, n_streams, fs, frames_per_step=1, max_span_frames=1024, resample_to=None):
         self.an, self.L = an, an.L
         self.n = int(n_streams)
         self.h = ctypes.c_void_p()
-        an._check(self.L.wsa_stream_create(an.h, self.n, float(fs), int(frames_per_step), int(max_span_frames), ctypes.byref(self.h)))
+        self.mixed = bool(resample_to)
+        if np.ndim(fs) > 0 and not resample_to:
+            raise WsaError("one rate per stream needs resample_to: a stream set has one geometry")
+        if resample_to:
+            self.fs_in = np.ascontiguousarray(np.broadcast_to(np.asarray(fs, np.float64), (self.n,)) if np.ndim(fs) == 0 else fs, dtype=np.float64)
+            if self.fs_in.shape != (self.n,):
+                raise WsaError("fs as a sequence holds one rate per stream")
+            self.fs = float(resample_to)
+            an._check(self.L.wsa_stream_create_mixed(an.h, self.n, self.fs_in.ctypes.data, self.fs, int(frames_per_step), int(max_span_frames), ctypes.byref(self.h)))
+        else:
+            self.fs = float(fs)
+            self.fs_in = np.full(self.n, self.fs)
+            an._check(self.L.wsa_stream_create(an.h, self.n, self.fs, int(frames_per_step), int(max_span_frames), ctypes.byref(self.h)))
         self.samples_per_step = int(self.L.wsa_stream_samples_per_step(self.h))
+        self.input_stride = int(self.L.wsa_stream_input_stride(self.h))
+        self.input_capacity = np.array([self.L.wsa_stream_input_capacity(self.h, i) for i in range(self.n)], np.uint32)
+        self.frame_capacity = int(self.L.wsa_stream_step_frame_capacity(self.h))
+
+    def paced_input(self):
+        """What n_in=None takes from every stream in the next step (a step without START): [n] uint32."""
+        return np.array([self.L.wsa_stream_paced_input(self.h, i) for i in range(self.n)], np.uint32)
+
+    @staticmethod
+    def resample_ready(n_in, fs_in, fs_out):
+        """Outputs of the first n_in samples whose taps have all arrived (wsa_resample_ready; pure)."""
+        return int(lib().wsa_resample_ready(int(n_in), float(fs_in), float(fs_out)))
+
+    def converted(self):
+        """After collect(): the converted samples the last step produced, a list of n float32 arrays (a mixed set)."""
+        counts = np.zeros(self.n, np.uint32)
+        self.an._check(self.L.wsa_stream_copy_converted(self.h, None, 0, counts.ctypes.data))
+        cap = max(int(counts.max()), 1)
+        out = np.zeros((self.n, cap), np.float32)
+        self.an._check(self.L.wsa_stream_copy_converted(self.h, out.ctypes.data, cap, counts.ctypes.data))
+        return [out[i, :int(c)].copy() for i, c in enumerate(counts)]
 
     def enable_graph(self, on=True):
         self.an._check(self.L.wsa_stream_enable_graph(self.h, int(on)))
 
     def host_input(self):
-        """The pinned [n, samples_per_step] float32 input buffer of step_host (a numpy view)."""
+        """The pinned [n, input_stride] float32 input buffer of step_host (a numpy view; input_stride = samples_per_step on a plain set)."""
         p = self.L.wsa_stream_host_input(self.h)
-        return np.ctypeslib.as_array(p, shape=(self.n, self.samples_per_step))
+        return np.ctypeslib.as_array(p, shape=(self.n, self.input_stride))
 
     @staticmethod
     def _ctl(ctl):
@@ -627,23 +681,32 @@ class Streams:
         a = np.ascontiguousarray(ctl, dtype=np.uint8)
         return a, a.ctypes.data
 
-    def step(self, d_pcm, stream_stride, ctl=None, stream=0):
+    def step(self, d_pcm, stream_stride, ctl=None, stream=0, n_in=None):
+        """n_in: samples per stream in this step ([n] uint32, at most input_capacity); None: paced (a plain set: samples_per_step)."""
         keep, ptr = self._ctl(ctl)
-        self.an._check(self.L.wsa_stream_step(self.h, d_pcm, int(stream_stride), ptr, stream))
+        if n_in is None:
+            self.an._check(self.L.wsa_stream_step(self.h, d_pcm, int(stream_stride), ptr, stream))
+        else:
+            cnt = np.ascontiguousarray(n_in, dtype=np.uint32)
+            self.an._check(self.L.wsa_stream_step_n(self.h, d_pcm, int(stream_stride), cnt.ctypes.data, ptr, stream))
 
-    def step_host(self, ctl=None, stream=0):
+    def step_host(self, ctl=None, stream=0, n_in=None):
         keep, ptr = self._ctl(ctl)
-        self.an._check(self.L.wsa_stream_step_host(self.h, ptr, stream))
+        if n_in is None:
+            self.an._check(self.L.wsa_stream_step_host(self.h, ptr, stream))
+        else:
+            cnt = np.ascontiguousarray(n_in, dtype=np.uint32)
+            self.an._check(self.L.wsa_stream_step_host_n(self.h, cnt.ctypes.data, ptr, stream))
 
     def time_steps(self, n_steps, feed=None, stream=0):
-        """n_steps steps timed inside the library (step_host + collect, microseconds each); feed = [k, n, samples_per_step] float32
+        """n_steps steps timed inside the library (step_host + collect, microseconds each); feed = [k, n, input_stride] float32
         blocks copied into the pinned input before each step (cycled), or None.  Returns (us array, rows produced)."""
         out = np.zeros(n_steps)
         rows = ctypes.c_uint64(0)
         fptr, fk = None, 0
         if feed is not None:
             feed = np.ascontiguousarray(feed, dtype=np.float32)
-            assert feed.ndim == 3 and feed.shape[1:] == (self.n, self.samples_per_step)
+            assert feed.ndim == 3 and feed.shape[1:] == (self.n, self.input_stride)
             fptr, fk = feed.ctypes.data, feed.shape[0]
         self.an._check(self.L.wsa_stream_time_steps(self.h, int(n_steps), fptr, int(fk), stream, out.ctypes.data, ctypes.byref(rows)))
         return out, rows.value

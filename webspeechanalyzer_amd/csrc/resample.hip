@@ -6,6 +6,8 @@
 // ("parity unpinned").  RS-1 = the published windowed-sinc scheme of the Chromium family: 32 taps, 32 + 1 sub-sample
 // offset kernels (Blackman window, cut-off 0.9 x the lower Nyquist), linear interpolation between the two neighbouring
 // kernels, 16 zeros of history, one fused multiply-add per tap.  Bit-exact against oracle/resample.c (same table, same operation order).
+// Also here: K0s, the same conversion inside a stream step (one workgroup per stream, state carried between steps), and the host's rule for
+// which outputs a stream may produce so far (resample_ready).
 #include "wsa_internal.hpp"
 #include <cmath>
 
@@ -210,6 +212,123 @@ __global__ __launch_bounds__(512) void resample_mixed_kernel(RsMixedParams m) {
     p.in = m.in; p.stride_in = m.stride_in; p.out = m.out; p.stride_out = m.stride_out; p.n_in = m.n_in; p.n_out = m.n_out;
     p.chunks = 1; p.table = m.tables + c.table_off; p.ratio = c.ratio; p.span = c.span; p.S = c.S; p.J = c.J;
     rs_block(p, s_mem, w.clip, w.blk);
+}
+
+// ---- K0s: the conversion inside a stream step (wsa_stream_create_mixed).  One workgroup per stream:
+//   1. the carried converted samples (overlap history + what has not filled a frame yet) move to the front of the stream's stage row
+//      — what stream_stage_kernel does for a plain set, so a mixed set has this node in its place;
+//   2. [input history | this step's samples | zeros] goes to LDS beside the stream's table image, the newest RS_HIST of them back to HBM as the next history;
+//   3. outputs [Y, Y + n_out) are formed behind the carried samples, each exactly as rs_block forms it: fp64 position from the ABSOLUTE index, the two
+//      offset kernels of the pair image, 32 fmaf per sum in ascending tap order (v_pk_fma_f32 advances both sums, each half the IEEE fma), the fp64 blend.
+// A step has about a thousand outputs per stream (four per lane): the kernel is a latency chain — table and inputs staged with all loads in flight, one
+// barrier, a few outputs per lane — so rs_block's register-resident kernel rows (worth it at 20 to 96 outputs per lane) are not kept: every output
+// reads its 32 pairs from LDS.  Every count comes from the host's control words; the kernel never decides how many outputs exist.
+constexpr int RS_STREAM_BLOCK = 256;
+__global__ __launch_bounds__(RS_STREAM_BLOCK) void resample_stream_kernel(RsStreamParams p) {
+    extern __shared__ __attribute__((aligned(16))) float s_mem[];
+    const uint32_t s = blockIdx.x, n = p.n, tid = threadIdx.x;
+    const uint32_t* ctl = p.ctl + s;
+    if (!(ctl[RS_CTL_BITS * n] & 4u)) return;                              // idle in this step: stage row, history and counts stay
+    const bool fresh = (ctl[RS_CTL_BITS * n] & 1u) != 0;                   // START: zeros in front of the first sample (RS-1's history)
+    const uint32_t n_in = ctl[RS_CTL_NIN * n], n_out = ctl[RS_CTL_NOUT * n], shift = ctl[RS_CTL_SHIFT * n], carry = ctl[RS_CTL_CARRY * n];
+    const int32_t dst0 = (int32_t)ctl[RS_CTL_DST * n];
+    float* const st = p.stage + (uint64_t)s * p.stage_stride;
+    float* const cv = p.conv + (uint64_t)s * p.conv_stride;
+    const float* const x = p.in + (uint64_t)s * p.in_stride;
+    // 1. towards the front, in ascending runs through registers: a run's stores land below everything a later run still reads
+    if (shift) {
+        for (uint32_t c0 = 0; c0 < carry; c0 += RS_STREAM_BLOCK) {
+            const uint32_t i = c0 + tid;
+            const float v = i < carry ? st[shift + i] : 0.f;
+            __syncthreads();
+            if (i < carry) st[i] = v;
+        }
+        __syncthreads();                                                   // the outputs below may land on what was just read
+    }
+    const RsClass c = p.cls[p.stream_class[s]];
+    if (c.copy) {                                                          // a stream at the analysis rate: unfiltered, no look-ahead
+        for (uint32_t j = tid; j < n_out; j += RS_STREAM_BLOCK) {
+            const float v = x[j];
+            if (dst0 + (int32_t)j >= 0) st[dst0 + (int32_t)j] = v;
+            cv[j] = v;
+        }
+        return;
+    }
+    // 2.
+    {
+        const float4* timg = reinterpret_cast<const float4*>(p.tables + c.table_off);
+        float4* d = reinterpret_cast<float4*>(s_mem);
+        for (int q = tid; q < RS_IMG4; q += RS_STREAM_BLOCK) d[q] = timg[q];
+    }
+    float* const s_x = s_mem + 2 * RS_OFFS * RS_KSTRIDE;                   // s_x[q] = input (N - RS_HIST + q), zeros before the START and beyond the newest sample
+    float* const hist = p.hist + (uint64_t)s * RS_HIST;
+    const uint32_t xlen = min((uint32_t)RS_HIST + n_in + (uint32_t)RS_TAPS, p.xcap);
+    for (uint32_t q = tid; q < xlen; q += RS_STREAM_BLOCK)
+        s_x[q] = q < (uint32_t)RS_HIST ? (fresh ? 0.f : hist[q]) : (q - RS_HIST < n_in ? x[q - RS_HIST] : 0.f);
+    __syncthreads();
+    if (tid < (uint32_t)RS_HIST) hist[tid] = s_x[n_in + tid];
+    // 3.
+    const uint64_t Y = (uint64_t)ctl[RS_CTL_Y_LO * n] | ((uint64_t)ctl[RS_CTL_Y_HI * n] << 32);
+    const int64_t in0 = (int64_t)((uint64_t)ctl[RS_CTL_IN0_LO * n] | ((uint64_t)ctl[RS_CTL_IN0_HI * n] << 32));
+    const rs_v2f* const s_k = reinterpret_cast<const rs_v2f*>(s_mem);
+    for (uint32_t j = tid; j < n_out; j += RS_STREAM_BLOCK) {
+        const double pos = (double)(Y + j) * c.ratio;
+        const double fl = floor(pos);
+        const double vo = (pos - fl) * RS_OFFS;
+        const int o = (int)vo;
+        const double f = vo - (double)o;
+        const int64_t w = (int64_t)fl - RS_TAPS / 2 - in0;                 // first tap in s_x; the host has checked 0 <= w and w + 32 <= xlen
+        float v = 0.f;
+        if (w >= 0 && w + RS_TAPS <= (int64_t)xlen) {
+            const rs_v2f* k = s_k + o * RS_KSTRIDE;
+            const float* xw = s_x + w;
+            rs_v2f acc; acc.x = 0.f; acc.y = 0.f;
+#pragma unroll
+            for (int i = 0; i < RS_TAPS; i++) {
+                rs_v2f xa; xa.x = xw[i]; xa.y = xw[i];
+                acc = __builtin_elementwise_fma(xa, k[i], acc);
+            }
+            v = (float)((1.0 - f) * (double)acc.x + f * (double)acc.y);
+        }
+        if (dst0 + (int32_t)j >= 0) st[dst0 + (int32_t)j] = v;
+        cv[j] = v;
+    }
+}
+
+size_t resample_stream_lds(uint32_t xcap) { return sizeof(float) * ((size_t)2 * RS_OFFS * RS_KSTRIDE + (size_t)xcap); }
+void launch_resample_stream(const RsStreamParams& p, hipStream_t s) {
+    if (p.n) hipLaunchKernelGGL(resample_stream_kernel, dim3(p.n), dim3(RS_STREAM_BLOCK), resample_stream_lds(p.xcap), s, p);
+}
+
+// Output n is ready when its last tap has arrived: floor((double)n * ratio) + 16 <= N, the position formed as K0 and oracle/resample.c form it.
+// The predicate is monotone in n; the count of ready outputs is found from an estimate by walking the predicate itself, then clamped to the length.
+uint64_t resample_ready(uint64_t n_in, double fs_in, double fs_out) {
+    if (fs_in == fs_out) return n_in;
+    const double ratio = fs_in / fs_out;
+    if (n_in < (uint64_t)(RS_TAPS / 2)) return 0;
+    auto ready = [&](uint64_t n) { return (uint64_t)std::floor((double)n * ratio) + (uint64_t)(RS_TAPS / 2) <= n_in; };
+    uint64_t g = (uint64_t)((double)(n_in - RS_TAPS / 2) / ratio);
+    while (g > 0 && !ready(g - 1)) g--;
+    while (ready(g)) g++;
+    const uint64_t len = resample_length(n_in, fs_in, fs_out);
+    return g < len ? g : len;
+}
+
+// What one step can produce, for a stream of ratio r that hands in at most cap = ceil(F hop r) <= F hop r + 1 samples:
+//   the tap rule alone counts the n with n r < N - 15, so a step adds at most n_in / r + 1 of them; the length clamp holds at most one back
+//   (ceil((N - 15) / r) - floor(N / r) < 2 - 15 / r, r <= 16), which a later step hands on: n_in / r + 2 <= F hop + 1 / r + 2 outputs without STOP;
+//   with STOP the step ends at floor(N' / r) from at least (N - 15) / r - 1: (n_in + 15) / r + 1 <= F hop + 16 / r + 1.
+// One more for the rounding of the fp64 products: F hop + ceil(16 / r) + 3.  Streams at the analysis rate are copied: at most their F hop inputs.
+uint32_t resample_step_outputs_bound(uint32_t frames_per_step, uint32_t hop, double min_ratio) {
+    const uint64_t base = (uint64_t)frames_per_step * hop;
+    const uint64_t v = min_ratio > 0 ? base + (uint64_t)std::ceil(16.0 / min_ratio) + 3 : base;
+    return v > 0xffffffffull ? 0xffffffffu : (uint32_t)v;
+}
+// Frames: before the step Y < K hop + win (frame K is not complete), after it (K' - 1) hop + win <= Y + outputs, so K' - K < outputs / hop + 1.
+uint32_t resample_step_frames_bound(uint32_t frames_per_step, uint32_t hop, double min_ratio) {
+    if (!hop) return 0;
+    const uint64_t o = resample_step_outputs_bound(frames_per_step, hop, min_ratio);
+    return (uint32_t)((o + hop - 1) / hop);
 }
 
 // outputs per block row: a multiple of the conversion's period when the rates are integers with a short period

@@ -72,6 +72,14 @@ struct wsa_stream {
     hipStream_t own = nullptr; hipEvent_t ev_in = nullptr;   // the legacy NULL stream cannot be captured: steps given stream 0 run on `own`
     const float* g_pcm = nullptr; uint64_t g_stride = 0; hipStream_t g_stream = nullptr; bool g_host = false;
     wsa_scls* scls = nullptr;               // the attached classifier's tables and carried fold (wsa_stream_set_model), or NULL
+    uint32_t in_stride = 0, ctl_words = 3;  // floats per stream in the input buffers (a plain set: step_samples), control words per stream
+    // a mixed set (wsa_stream_create_mixed): F above is the step's internal frame CAPACITY (resample_step_frames_bound), F_user the caller's frames_per_step
+    bool mixed = false;
+    uint32_t F_user = 0, out_cap = 0, conv_stride = 0, xcap = 0;
+    std::vector<double> fs_in, ratio;
+    std::vector<uint32_t> in_cap, last_nfr, last_out;      // per stream: samples one step accepts, frames / outputs of its last active step
+    std::vector<uint64_t> cN, cY, cK, cS;                  // per stream since START: inputs received, outputs handed on, frames analysed, active steps
+    float *d_conv = nullptr, *d_hist = nullptr, *d_rs_tables = nullptr; RsClass* d_rs_cls = nullptr; uint32_t* d_rs_class = nullptr;
 };
 
 template <typename T>
@@ -153,9 +161,16 @@ void wsa_stream_destroy(wsa_stream* b) {
     delete b;
 }
 
-wsa_status wsa_stream_create(wsa_ctx* ctx, uint32_t n_streams, double fs, uint32_t frames_per_step, uint32_t max_span_frames, wsa_stream** out) {
+// fs_in == nullptr: a plain set (every stream at fs); else a mixed set, stream i arriving at fs_in[i] and analysed at fs
+static wsa_status create_impl(wsa_ctx* ctx, uint32_t n_streams, const double* fs_in, double fs, uint32_t frames_per_step, uint32_t max_span_frames, wsa_stream** out) {
     if (!ctx || !out || n_streams == 0 || frames_per_step == 0) return fail(ctx, WSA_ERR_INVALID, "bad stream arguments");
     *out = nullptr;
+    if (fs_in) {
+        if (!(fs > 0)) return fail(ctx, WSA_ERR_INVALID, "sample rates must be positive and at most a factor 16 apart");
+        for (uint32_t i = 0; i < n_streams; i++)
+            if (!(fs_in[i] > 0) || fs_in[i] / fs > 16 || fs / fs_in[i] > 16)
+                return fail(ctx, WSA_ERR_INVALID, "sample rates must be positive and at most a factor 16 apart (stream " + std::to_string(i) + ")");
+    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const wsa_config& c = ctx->cfg;
     if (!(c.output_level == 5 || c.output_level == 13 || c.output_level == 4 || c.output_level == 10 || c.output_level == 12 || c.output_level == 11 || c.output_level == 3))
@@ -172,6 +187,36 @@ wsa_status wsa_stream_create(wsa_ctx* ctx, uint32_t n_streams, double fs, uint32
     b->hist = (b->q - 1) * (uint32_t)P.hop;
     b->step_samples = b->F * (uint32_t)P.hop;
     b->stage_stride = (b->hist + b->step_samples + (uint32_t)P.win + 3u) & ~3u;
+    b->in_stride = b->step_samples; b->F_user = b->F;
+    RsMixedPlan rs;
+    if (fs_in) {
+        // the step's frame capacity — everything F sizes below — comes from the bound on what one step can produce at the set's smallest ratio
+        // (resample.hip), not from frames_per_step: a step fed its capacity completes frames_per_step + 1 frames now and then, a STOP step adds the tail
+        b->mixed = true; b->ctl_words = RS_CTL_WORDS; b->hist = 0;
+        b->fs_in.assign(fs_in, fs_in + n_streams); b->ratio.resize(n_streams); b->in_cap.resize(n_streams);
+        b->last_nfr.assign(n_streams, 0); b->last_out.assign(n_streams, 0);
+        b->cN.assign(n_streams, 0); b->cY.assign(n_streams, 0); b->cK.assign(n_streams, 0); b->cS.assign(n_streams, 0);
+        double min_ratio = 0; uint64_t max_in = 0;
+        for (uint32_t i = 0; i < n_streams; i++) {
+            b->ratio[i] = fs_in[i] / fs;
+            const uint64_t cap = fs_in[i] == fs ? (uint64_t)b->step_samples : (uint64_t)std::ceil((double)b->step_samples * b->ratio[i]);
+            if (fs_in[i] != fs && (min_ratio == 0 || b->ratio[i] < min_ratio)) min_ratio = b->ratio[i];
+            if (cap > max_in) max_in = cap;
+            b->in_cap[i] = (uint32_t)cap;
+        }
+        b->out_cap = resample_step_outputs_bound(b->F_user, (uint32_t)P.hop, min_ratio);
+        b->F = resample_step_frames_bound(b->F_user, (uint32_t)P.hop, min_ratio);
+        b->in_stride = ((uint32_t)max_in + 3u) & ~3u;
+        b->conv_stride = (b->out_cap + 3u) & ~3u;
+        b->xcap = ((uint32_t)RS_HIST + (uint32_t)max_in + (uint32_t)RS_TAPS + 3u) & ~3u;
+        b->stage_stride = ((uint32_t)P.win + b->out_cap + 7u) & ~3u;          // fewer than win carried samples in front of at most out_cap new ones
+        if (const size_t need = resample_stream_lds(b->xcap); need > 160 * 1024) {
+            delete b;
+            return fail(ctx, WSA_ERR_INVALID, "a step of " + std::to_string(max_in) + " input samples per stream needs " + std::to_string(need) + " bytes of LDS for the rate converter (limit 163840): fewer frames per step");
+        }
+        std::vector<uint32_t> none(n_streams, 0);
+        if (!plan_resample_mixed(n_streams, none.data(), fs_in, fs, rs, err)) { delete b; return fail(ctx, WSA_ERR_INVALID, err); }
+    }
     uint32_t want = max_span_frames ? max_span_frames : 1024u;
     if (want < 2 * b->F + 64) want = 2 * b->F + 64;
     uint32_t ring = 64; while (ring < want + b->F) ring <<= 1;
@@ -203,7 +248,7 @@ wsa_status wsa_stream_create(wsa_ctx* ctx, uint32_t n_streams, double fs, uint32
            && s_upload(b, &b->d_tw_nfft, P.tw_nfft) && s_upload(b, &b->d_mel_k0, P.mel_k0) && s_upload(b, &b->d_mel_cnt, P.mel_cnt)
            && s_upload(b, &b->d_mel_off, P.mel_off) && s_upload(b, &b->d_mel_w, P.mel_w) && s_upload(b, &b->d_emph, P.emph)
            && s_upload(b, &b->d_frame_off, foff) && s_upload(b, &b->d_ring_off, roff)
-           && s_alloc(b, &b->d_ctl, (size_t)3 * n_streams, true) && s_alloc(b, &b->d_spec, (size_t)n_streams * b->F * P.bands)
+           && s_alloc(b, &b->d_ctl, (size_t)b->ctl_words * n_streams, true) && s_alloc(b, &b->d_spec, (size_t)n_streams * b->F * P.bands)
            && s_alloc(b, &b->rec.hdr, nfr_ring) && s_alloc(b, &b->rec.amp, nfr_ring * CAND_CAP) && s_alloc(b, &b->rec.ent, nfr_ring * CAND_CAP) && s_alloc(b, &b->d_state, (size_t)n_streams * GATE_STATE, true)
            && s_alloc(b, &b->d_fr_info, nfr_ring) && s_alloc(b, &b->d_fr_v, nfr_ring) && s_alloc(b, &b->d_fr_fl, nfr_ring)
            && s_alloc(b, &b->d_seg_i, (size_t)n_streams * b->seg_cap * 8) && s_alloc(b, &b->d_seg_d, (size_t)n_streams * b->seg_cap * 2)
@@ -221,10 +266,15 @@ wsa_status wsa_stream_create(wsa_ctx* ctx, uint32_t n_streams, double fs, uint32
            && s_alloc(b, &b->d_totals, 4, true) && s_alloc(b, &b->d_ws, b->ws_stride * (size_t)n_streams, true)      /* one tracker work space per stream (its filing generations start at zero) */
            && s_alloc(b, &b->d_tr_state, (size_t)n_streams * TR_STATE_WORDS, true) && s_alloc(b, &b->d_tr_act, (size_t)n_streams * TR_ACT_BYTES, true)
            && s_alloc(b, &b->d_fr_span, nfr_ring, true)
-           && s_alloc(b, &b->d_pcm_in, (size_t)n_streams * b->step_samples);
-    if (ok && b->hist) ok = s_alloc(b, &b->d_stage, (size_t)n_streams * b->stage_stride, true);
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_ctl), (size_t)3 * n_streams * sizeof(uint32_t), hipHostMallocMapped) == hipSuccess
-            && hipHostMalloc(reinterpret_cast<void**>(&b->h_pcm), (size_t)n_streams * b->step_samples * sizeof(float), hipHostMallocMapped) == hipSuccess
+           && s_alloc(b, &b->d_pcm_in, (size_t)n_streams * b->in_stride);
+    if (ok && (b->hist || b->mixed)) ok = s_alloc(b, &b->d_stage, (size_t)n_streams * b->stage_stride, true);
+    if (ok && b->mixed) {
+        if (rs.tables.empty()) rs.tables.assign(4, 0.f);                   // (every stream at the analysis rate: no table is read)
+        ok = s_alloc(b, &b->d_conv, (size_t)n_streams * b->conv_stride, true) && s_alloc(b, &b->d_hist, (size_t)n_streams * RS_HIST, true)
+          && s_upload(b, &b->d_rs_tables, rs.tables) && s_upload(b, &b->d_rs_cls, rs.cls) && s_upload(b, &b->d_rs_class, rs.clip_class);
+    }
+    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&b->h_ctl), (size_t)b->ctl_words * n_streams * sizeof(uint32_t), hipHostMallocMapped) == hipSuccess
+            && hipHostMalloc(reinterpret_cast<void**>(&b->h_pcm), (size_t)n_streams * b->in_stride * sizeof(float), hipHostMallocMapped) == hipSuccess
             && hipHostMalloc(reinterpret_cast<void**>(&b->h_totals), (4 + (size_t)n_streams) * sizeof(uint32_t), hipHostMallocMapped) == hipSuccess
             && hipHostMalloc(reinterpret_cast<void**>(&b->h_meta), (size_t)(b->d2h_rows ? b->d2h_rows : 1) * 8 * sizeof(int32_t), hipHostMallocMapped) == hipSuccess
             && hipHostMalloc(reinterpret_cast<void**>(&b->h_feat), (size_t)(b->d2h_rows ? b->d2h_rows : 1) * WSA_NFEAT * sizeof(double), hipHostMallocMapped) == hipSuccess
@@ -235,7 +285,8 @@ wsa_status wsa_stream_create(wsa_ctx* ctx, uint32_t n_streams, double fs, uint32
         wsa_stream_destroy(b);
         return fail(ctx, WSA_ERR_HIP, m);
     }
-    std::memset(b->h_pcm, 0, (size_t)n_streams * b->step_samples * sizeof(float));
+    std::memset(b->h_pcm, 0, (size_t)n_streams * b->in_stride * sizeof(float));
+    std::memset(b->h_ctl, 0, (size_t)b->ctl_words * n_streams * sizeof(uint32_t));
     std::memset(b->h_totals, 0, (4 + (size_t)n_streams) * sizeof(uint32_t));
     if (hipHostGetDevicePointer(reinterpret_cast<void**>(&b->h_pcm_dev), b->h_pcm, 0) != hipSuccess
         || hipHostGetDevicePointer(reinterpret_cast<void**>(&b->h_ctl_dev), b->h_ctl, 0) != hipSuccess
@@ -250,7 +301,27 @@ wsa_status wsa_stream_create(wsa_ctx* ctx, uint32_t n_streams, double fs, uint32
     return WSA_OK;
 }
 
+wsa_status wsa_stream_create(wsa_ctx* ctx, uint32_t n_streams, double fs, uint32_t frames_per_step, uint32_t max_span_frames, wsa_stream** out) {
+    return create_impl(ctx, n_streams, nullptr, fs, frames_per_step, max_span_frames, out);
+}
+wsa_status wsa_stream_create_mixed(wsa_ctx* ctx, uint32_t n_streams, const double* fs_in, double fs_out, uint32_t frames_per_step, uint32_t max_span_frames, wsa_stream** out) {
+    if (ctx && out && n_streams && !fs_in) return fail(ctx, WSA_ERR_INVALID, "null argument: fs_in holds one rate per stream (stream 0 has none)");
+    return create_impl(ctx, n_streams, fs_in, fs_out, frames_per_step, max_span_frames, out);
+}
+
 uint32_t wsa_stream_samples_per_step(const wsa_stream* b) { return b ? b->step_samples : 0; }
+uint32_t wsa_stream_input_capacity(const wsa_stream* b, uint32_t i) { return !b || i >= b->n ? 0 : (b->mixed ? b->in_cap[i] : b->step_samples); }
+uint32_t wsa_stream_input_stride(const wsa_stream* b) { return b ? b->in_stride : 0; }
+uint32_t wsa_stream_step_frame_capacity(const wsa_stream* b) { return b ? b->F : 0; }
+// the paced count of a stream's s-th active step since START: floor((s + 1) F hop ratio) - floor(s F hop ratio)
+static uint32_t paced_count(const wsa_stream* b, uint32_t i, uint64_t s) {
+    if (b->fs_in[i] == b->fs) return b->step_samples;
+    const double r = b->ratio[i];
+    return (uint32_t)((uint64_t)std::floor((double)((s + 1) * b->step_samples) * r) - (uint64_t)std::floor((double)(s * b->step_samples) * r));
+}
+uint32_t wsa_stream_paced_input(const wsa_stream* b, uint32_t i) { return !b || i >= b->n ? 0 : (b->mixed ? paced_count(b, i, b->cS[i]) : b->step_samples); }
+uint64_t wsa_resample_ready(uint64_t n_in, double fs_in, double fs_out) { return fs_in > 0 && fs_out > 0 ? resample_ready(n_in, fs_in, fs_out) : 0; }
+uint32_t wsa_stream_frames_bound(uint32_t frames_per_step, uint32_t hop, double min_ratio) { return resample_step_frames_bound(frames_per_step, hop, min_ratio); }
 float* wsa_stream_host_input(wsa_stream* b) { return b ? b->h_pcm : nullptr; }
 
 wsa_status wsa_stream_enable_graph(wsa_stream* b, int32_t on) {
@@ -267,12 +338,13 @@ static wsa_status enqueue_step(wsa_stream* b, const float* d_pcm, uint64_t strid
     const FePlanHost& P = b->plan;
     const uint32_t n = b->n;
     // no memcpy / memset nodes: everything that crosses PCIe goes through mapped pinned buffers, moved by kernels
-    hipLaunchKernelGGL(stream_begin_kernel, dim3((3 * n + 255) / 256), dim3(256), 0, s, b->d_ctl, b->h_ctl_dev, 3 * n, b->d_counters, b->d_totals,
+    const uint32_t cw = b->ctl_words * n;
+    hipLaunchKernelGGL(stream_begin_kernel, dim3((cw + 255) / 256), dim3(256), 0, s, b->d_ctl, b->h_ctl_dev, cw, b->d_counters, b->d_totals,
                        b->d_trk_seg, b->d_trk_seg ? (uint32_t)((size_t)n * b->seg_cap * 4) : 0u);
     if (host_in) {
-        const size_t cnt = (size_t)n * b->step_samples;
+        const size_t cnt = (size_t)n * b->in_stride;
         hipLaunchKernelGGL(stream_pull_kernel, dim3((unsigned)((cnt / 4 + 256) / 256)), dim3(256), 0, s, b->d_pcm_in, b->h_pcm_dev, cnt);
-        d_pcm = b->d_pcm_in; stride = b->step_samples;
+        d_pcm = b->d_pcm_in; stride = b->in_stride;
     }
     const uint32_t *d_nfr = b->d_ctl, *d_off = b->d_ctl + n, *d_bits = b->d_ctl + 2 * n;
     GateParams g;
@@ -280,7 +352,13 @@ static wsa_status enqueue_step(wsa_stream* b, const float* d_pcm, uint64_t strid
     if (g.auto_gate) { g.ctx_max0 = 50; g.floor0 = 2; }                                            // ref @B25471
     else { g.ctx_max0 = std::pow(10.0, c.voiced_max_dB / 20); g.floor0 = std::pow(10.0, c.voiced_min_dB / 20); }
     launch_stream_prepare(b->d_state, b->d_carry, b->d_tr_state, d_bits, n, g.ctx_max0, g.floor0, s);
-    if (b->hist) {
+    if (b->mixed) {                        // K0s in the place of the history shuffle: carried converted samples to the front, this step's outputs behind them
+        RsStreamParams r;
+        r.stage = b->d_stage; r.stage_stride = b->stage_stride; r.conv = b->d_conv; r.conv_stride = b->conv_stride; r.in = d_pcm; r.in_stride = stride;
+        r.hist = b->d_hist; r.ctl = b->d_ctl; r.n = n; r.tables = b->d_rs_tables; r.cls = b->d_rs_cls; r.stream_class = b->d_rs_class; r.xcap = b->xcap;
+        launch_resample_stream(r, s);
+        d_pcm = b->d_stage; stride = b->stage_stride;
+    } else if (b->hist) {
         hipLaunchKernelGGL(stream_stage_kernel, dim3(n), dim3(256), (size_t)b->hist * sizeof(float), s,
                            b->d_stage, b->stage_stride, d_pcm, stride, d_bits, b->hist, b->step_samples);
         d_pcm = b->d_stage; stride = b->stage_stride;
@@ -352,7 +430,7 @@ static wsa_status enqueue_step(wsa_stream* b, const float* d_pcm, uint64_t strid
     return WSA_OK;
 }
 
-static wsa_status step_impl(wsa_stream* b, const float* d_pcm, uint64_t stride, bool host_in, const uint8_t* ctl, hipStream_t s) {
+static wsa_status step_impl(wsa_stream* b, const float* d_pcm, uint64_t stride, bool host_in, const uint32_t* n_in, const uint8_t* ctl, hipStream_t s) {
     wsa_ctx* ctx = b->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!s) {                      // NULL stream: run on the object's own stream, after what the NULL stream holds now
@@ -361,13 +439,56 @@ static wsa_status step_impl(wsa_stream* b, const float* d_pcm, uint64_t stride, 
         HIP_TRY(ctx, hipStreamWaitEvent(s, b->ev_in, 0));
     }
     if (!host_in && !d_pcm) return fail(ctx, WSA_ERR_INVALID, "null PCM pointer");
-    if (!host_in && stride < b->step_samples && b->n > 1) return fail(ctx, WSA_ERR_INVALID, "stream_stride smaller than samples_per_step");
+    if (!b->mixed && !host_in && stride < b->step_samples && b->n > 1) return fail(ctx, WSA_ERR_INVALID, "stream_stride smaller than samples_per_step");
+    const auto ctl_of = [&](uint32_t i) -> uint32_t { return ctl ? ctl[i] : (b->steps == 0 ? (WSA_STREAM_ACTIVE | WSA_STREAM_START) : WSA_STREAM_ACTIVE); };
+    for (uint32_t i = 0; n_in && i < b->n; i++) {           // counts are checked before anything is counted
+        if (!(ctl_of(i) & WSA_STREAM_ACTIVE)) continue;
+        if (!b->mixed && n_in[i] != b->step_samples)
+            return fail(ctx, WSA_ERR_INVALID, "stream " + std::to_string(i) + ": a plain stream set takes exactly " + std::to_string(b->step_samples) + " samples per step, not " + std::to_string(n_in[i]));
+        if (b->mixed && n_in[i] > b->in_cap[i])
+            return fail(ctx, WSA_ERR_INVALID, "stream " + std::to_string(i) + ": " + std::to_string(n_in[i]) + " samples in one step, its capacity is " + std::to_string(b->in_cap[i]));
+        if (b->mixed && !host_in && b->n > 1 && stride < n_in[i]) return fail(ctx, WSA_ERR_INVALID, "stream_stride smaller than the samples of stream " + std::to_string(i));
+    }
+    for (uint32_t i = 0; b->mixed && !n_in && !host_in && b->n > 1 && i < b->n; i++)      // paced: no count exceeds the capacity
+        if (stride < b->in_cap[i]) return fail(ctx, WSA_ERR_INVALID, "stream_stride smaller than the input capacity of stream " + std::to_string(i));
     // the pinned control words are read by the step's first H2D copy: the previous step must be done
     if (b->stepped) HIP_TRY(ctx, hipStreamSynchronize(b->last_stream ? b->last_stream : s));      // ... on whichever stream it ran
     b->last_stream = s;
     const uint32_t n = b->n, F = b->F;
-    for (uint32_t i = 0; i < n; i++) {
-        const uint32_t cb = ctl ? ctl[i] : (b->steps == 0 ? (WSA_STREAM_ACTIVE | WSA_STREAM_START) : WSA_STREAM_ACTIVE);
+    for (uint32_t i = 0; b->mixed && i < n; i++) {
+        // Every count of a mixed set is decided here, in integers and one exact predicate in double (resample_ready); the device only carries them out.
+        const uint32_t cb = ctl_of(i), hop = (uint32_t)b->plan.hop, win = (uint32_t)b->plan.win;
+        uint32_t* w = b->h_ctl + i;
+        uint32_t bits = 0;
+        if (cb & WSA_STREAM_START) { b->cN[i] = b->cY[i] = b->cK[i] = b->cS[i] = 0; b->last_nfr[i] = 0; bits |= 1u; }
+        if (cb & WSA_STREAM_STOP) bits |= 2u;
+        b->last_out[i] = 0;
+        w[RS_CTL_NFR * n] = 0; w[RS_CTL_OFF * n] = 0; w[RS_CTL_NIN * n] = 0; w[RS_CTL_NOUT * n] = 0;
+        if (cb & WSA_STREAM_ACTIVE) {
+            bits |= 4u;
+            const uint32_t cnt = n_in ? n_in[i] : paced_count(b, i, b->cS[i]);
+            const uint64_t N0 = b->cN[i], Y0 = b->cY[i], K0 = b->cK[i], N1 = N0 + cnt;
+            uint64_t Y1 = (cb & WSA_STREAM_STOP) ? resample_length(N1, b->fs_in[i], b->fs) : resample_ready(N1, b->fs_in[i], b->fs);
+            if (b->fs_in[i] == b->fs) Y1 = N1;
+            if (Y1 < Y0) Y1 = Y0;                          // (active again after a STOP without a START: nothing is taken back)
+            const uint64_t K1 = Y1 >= win ? (Y1 - win) / hop + 1 : 0;
+            const int64_t in0 = (int64_t)N0 - RS_HIST, dst0 = (int64_t)Y0 - (int64_t)(K0 * hop);
+            const bool conv = b->fs_in[i] != b->fs && Y1 > Y0;
+            if (Y1 - Y0 > b->out_cap || K1 < K0 || K1 - K0 > b->F || dst0 + (int64_t)(Y1 - Y0) > (int64_t)b->stage_stride || dst0 < -(int64_t)hop || (conv && (int64_t)std::floor((double)Y0 * b->ratio[i]) - RS_TAPS / 2 < in0)
+                || (conv && (int64_t)std::floor((double)(Y1 - 1) * b->ratio[i]) + RS_TAPS / 2 - in0 > (int64_t)b->xcap))
+                return fail(ctx, WSA_ERR_CAPACITY, "stream " + std::to_string(i) + ": a step outside the derived bounds (" + std::to_string(Y1 - Y0) + " outputs, "
+                            + std::to_string(K1 - K0) + " frames; capacity " + std::to_string(b->out_cap) + ", " + std::to_string(b->F) + ")");
+            w[RS_CTL_NFR * n] = (uint32_t)(K1 - K0); w[RS_CTL_NIN * n] = cnt; w[RS_CTL_NOUT * n] = (uint32_t)(Y1 - Y0);
+            w[RS_CTL_DST * n] = (uint32_t)(int32_t)dst0; w[RS_CTL_SHIFT * n] = b->last_nfr[i] * hop; w[RS_CTL_CARRY * n] = dst0 > 0 ? (uint32_t)dst0 : 0u;
+            w[RS_CTL_Y_LO * n] = (uint32_t)Y0; w[RS_CTL_Y_HI * n] = (uint32_t)(Y0 >> 32);
+            w[RS_CTL_IN0_LO * n] = (uint32_t)(uint64_t)in0; w[RS_CTL_IN0_HI * n] = (uint32_t)((uint64_t)in0 >> 32);
+            b->cN[i] = N1; b->cY[i] = Y1; b->cK[i] = K1; b->cS[i]++;
+            b->last_nfr[i] = (uint32_t)(K1 - K0); b->last_out[i] = (uint32_t)(Y1 - Y0);
+        }
+        w[RS_CTL_BITS * n] = bits;
+    }
+    for (uint32_t i = 0; !b->mixed && i < n; i++) {
+        const uint32_t cb = ctl_of(i);
         uint32_t bits = 0, nfr = 0, off = 0;
         if (cb & WSA_STREAM_START) { b->warm[i] = b->q - 1; bits |= 1u; }
         if (cb & WSA_STREAM_ACTIVE) {
@@ -402,11 +523,35 @@ static wsa_status step_impl(wsa_stream* b, const float* d_pcm, uint64_t stride, 
 
 wsa_status wsa_stream_step(wsa_stream* b, const float* d_pcm, uint64_t stream_stride, const uint8_t* ctl, void* stream) {
     if (!b) return WSA_ERR_INVALID;
-    return step_impl(b, d_pcm, stream_stride, false, ctl, reinterpret_cast<hipStream_t>(stream));
+    return step_impl(b, d_pcm, stream_stride, false, nullptr, ctl, reinterpret_cast<hipStream_t>(stream));
 }
 wsa_status wsa_stream_step_host(wsa_stream* b, const uint8_t* ctl, void* stream) {
     if (!b) return WSA_ERR_INVALID;
-    return step_impl(b, nullptr, 0, true, ctl, reinterpret_cast<hipStream_t>(stream));
+    return step_impl(b, nullptr, 0, true, nullptr, ctl, reinterpret_cast<hipStream_t>(stream));
+}
+wsa_status wsa_stream_step_n(wsa_stream* b, const float* d_pcm, uint64_t stream_stride, const uint32_t* n_in, const uint8_t* ctl, void* stream) {
+    if (!b) return WSA_ERR_INVALID;
+    return step_impl(b, d_pcm, stream_stride, false, n_in, ctl, reinterpret_cast<hipStream_t>(stream));
+}
+wsa_status wsa_stream_step_host_n(wsa_stream* b, const uint32_t* n_in, const uint8_t* ctl, void* stream) {
+    if (!b) return WSA_ERR_INVALID;
+    return step_impl(b, nullptr, 0, true, n_in, ctl, reinterpret_cast<hipStream_t>(stream));
+}
+wsa_status wsa_stream_copy_converted(wsa_stream* b, float* out, uint32_t cap, uint32_t* counts) {
+    if (!b) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = b->ctx;
+    if (!b->mixed) return fail(ctx, WSA_ERR_INVALID, "no converted samples: the stream set must come from wsa_stream_create_mixed");
+    if (!b->stepped) return fail(ctx, WSA_ERR_INVALID, "no step on this stream object yet");
+    for (uint32_t i = 0; i < b->n; i++) {
+        if (out && b->last_out[i] > cap) return fail(ctx, WSA_ERR_INVALID, "stream " + std::to_string(i) + " produced " + std::to_string(b->last_out[i]) + " converted samples in the last step, the buffer holds " + std::to_string(cap) + " per stream");
+        if (counts) counts[i] = b->last_out[i];
+    }
+    if (!out) return WSA_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(b->last_stream ? b->last_stream : b->own));
+    const uint32_t wcols = cap < b->conv_stride ? cap : b->conv_stride;
+    if (wcols) HIP_TRY(ctx, hipMemcpy2D(out, (size_t)cap * sizeof(float), b->d_conv, (size_t)b->conv_stride * sizeof(float), (size_t)wcols * sizeof(float), b->n, hipMemcpyDeviceToHost));
+    return WSA_OK;
 }
 
 }  // extern "C"
@@ -584,7 +729,7 @@ wsa_status wsa_stream_classes(wsa_stream* b, wsa_stream_class_result* out) {
 // wsa_stream_collect with the host's monotonic clock and notes the microseconds (no interpreter between the two calls).
 wsa_status wsa_stream_time_steps(wsa_stream* b, uint32_t n_steps, const float* feed, uint32_t feed_steps, void* stream, double* out_us, uint64_t* rows_total) {
     if (!b || !out_us || (feed && feed_steps == 0)) return WSA_ERR_INVALID;
-    const size_t words = (size_t)b->n * b->step_samples;
+    const size_t words = (size_t)b->n * b->in_stride;
     uint64_t rows = 0;
     for (uint32_t k = 0; k < n_steps; k++) {
         if (feed) std::memcpy(b->h_pcm, feed + (size_t)(k % feed_steps) * words, words * sizeof(float));

@@ -219,6 +219,34 @@ struct RsMixedPlan {
 bool plan_resample_mixed(uint32_t n_clips, const uint32_t* n_out, const double* fs_in, double fs_out, RsMixedPlan& P, std::string& err);
 void launch_resample_mixed(const RsMixedParams& p, const RsMixedPlan& P, bool per_class, hipStream_t s);     // per_class: one launch per class instead of one over the whole list
 
+// K0s: the conversion inside a stream step (wsa_stream_create_mixed), one workgroup per stream.  Every count is the host's (the step's mapped
+// control words, RS_CTL_WORDS per stream, word w of stream s at ctl[w * n + s]); the kernel decides nothing about how many outputs exist.
+enum { RS_CTL_NFR = 0, RS_CTL_OFF = 1, RS_CTL_BITS = 2,      // the three words every stream set has: frames of the step, sample offset, control bits
+       RS_CTL_NIN = 3, RS_CTL_NOUT = 4,                      // input samples of the step, outputs [Y, Y + n_out) to convert
+       RS_CTL_DST = 5,                                       // int32: stage position of output Y = Y - K * hop (negative where windows leave gaps: those outputs belong to no frame)
+       RS_CTL_SHIFT = 6, RS_CTL_CARRY = 7,                   // the carried converted samples: `carry` of them move from stage position `shift` to the front
+       RS_CTL_Y_LO = 8, RS_CTL_Y_HI = 9,                     // Y, the absolute index of the step's first output
+       RS_CTL_IN0_LO = 10, RS_CTL_IN0_HI = 11,               // int64: absolute index of the first sample of [history | step's samples] = N - RS_HIST
+       RS_CTL_WORDS = 12 };
+// Input history a stream keeps between steps.  The first output a step could not produce, n, failed floor(n ratio) + 16 <= N, so its oldest tap
+// floor(n ratio) - 16 >= N - 31: 31 samples are enough — except behind a step that the length clamp stopped one output short (ratios above 15:
+// n ratio > N - ratio - 1, oldest tap >= N - 33).  48 covers both and keeps the rows 16-byte multiples; the host checks every step's oldest tap against it.
+constexpr int RS_HIST = 48;
+struct RsStreamParams {
+    float* stage; uint32_t stage_stride;              // per stream: [carried converted samples | this step's outputs], what the front end reads
+    float* conv; uint32_t conv_stride;                // per stream: this step's outputs alone (wsa_stream_copy_converted)
+    const float* in; uint64_t in_stride;              // per stream: this step's input samples
+    float* hist;                                      // [n][RS_HIST] the newest inputs of the previous steps
+    const uint32_t* ctl; uint32_t n;
+    const float* tables; const RsClass* cls; const uint32_t* stream_class;
+    uint32_t xcap;                                    // floats of LDS behind the table image: RS_HIST + the largest input capacity + RS_TAPS
+};
+void launch_resample_stream(const RsStreamParams& p, hipStream_t s);
+size_t resample_stream_lds(uint32_t xcap);
+uint64_t resample_ready(uint64_t n_in, double fs_in, double fs_out);      // outputs whose taps have all arrived, never more than resample_length
+uint32_t resample_step_frames_bound(uint32_t frames_per_step, uint32_t hop, double min_ratio);   // frames one step can complete (min_ratio: smallest fs_in / fs_out of the converted streams, 0: none)
+uint32_t resample_step_outputs_bound(uint32_t frames_per_step, uint32_t hop, double min_ratio);  // converted samples one step can produce, a STOP step's tail included
+
 void launch_frontend(const FeParams& p, int n_clips, int max_frames, int R, int three, hipStream_t s);
 bool fe_supported_R(int R, int three);  // packed FFT length 64 R, R in {2, 4, 8, 16, 32, 64}, or 3 * 64 R, R in {1, 2, 4, 8, 16, 32}
 size_t fe_lds_required(const FePlanHost& P, bool fat);      // dynamic LDS of the front-end kernel this geometry selects (limit: 160 KB per workgroup)

@@ -580,19 +580,33 @@ function LaunchBatches(batches, callback = null, labels = [], test_play = false)
 // on_prediction(si, [label, confidence], stream, per_syllable) follows each callback (as for LaunchBatch, the stream in place of the clip),
 // and push() / close() return `meters`, one {label: Label_conf_all} per stream (reset by the stream's START).  The object keeps the model it
 // opened with until close().
+// sample_rate may be an array with one rate per stream.  With configure({resample_to: R}), R > 0, every stream is converted from its own rate to R
+// inside the step (spec RS-1, as LaunchBatch converts clips; geometry, bins_Hz and the band check come from R) and streams already at R pass
+// unfiltered; without it the streams must share a rate.  The handle of a converting set also has `capacity` (Uint32Array: the samples one push
+// accepts per stream), `inputStride` (floats per stream in `input`: stream i's samples of a push start at input[i * inputStride]), paced() (what a
+// push without counts takes from every stream next: what keeps it on real time) and push(ctl, counts) with counts = Uint32Array of samples per
+// stream.  samplesPerStep keeps its meaning: frames_per_step * hop samples at the analysis rate.  The reference's live path runs at the hardware's
+// rate and converts nothing; this is ours, like resample_to.
 const STREAM_ACTIVE = 1, STREAM_START = 2, STREAM_STOP = 4;
 function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames_per_step = 1, max_span_frames = 1024) {
   const nat = addon();
   const level = settings.output_level, step = settings.window_step / 1e3;
   if (![3, 4, 5, 10, 11, 12, 13].includes(level)) throw 'output_level ' + level + ' is not available for streams through this build (3, 4, 5, 10, 11, 12 and 13 are)';
+  const per_stream = Array.isArray(sample_rate) || ArrayBuffer.isView(sample_rate);
+  if (per_stream && sample_rate.length !== n_streams) throw 'sample_rate as an array holds one rate per stream (' + sample_rate.length + ' rates, ' + n_streams + ' streams)';
+  const rates = per_stream ? Array.from(sample_rate) : [sample_rate];
+  const convert = settings.resample_to > 0;
+  if (new Set(rates).size !== 1 && !convert) throw 'All streams of one set must share a sample rate (configure resample_to to convert each from its own)';
+  const fs_an = convert ? settings.resample_to : rates[0];      // the rate the analysis runs at (K0s converts inside the step)
   const pred = prediction && level === 13 ? prediction : null;
   const ctx = nat.create(native_config(), settings.device);
   let st;
   try {
-    const g = nat.geometry(ctx, sample_rate);
+    const g = nat.geometry(ctx, fs_an);
     const bands = settings.spec_type === 1 ? settings.N_mel_bins : settings.N_fft_bins;
     if (g.bands !== bands) throw 'Bins count mismatch: ' + g.bands + ', ' + bands;              // ref @B8568 check
-    st = nat.streamOpen(ctx, n_streams, sample_rate, frames_per_step, max_span_frames);
+    st = convert ? nat.streamOpenMixed(ctx, n_streams, Float64Array.from(per_stream ? rates : new Array(n_streams).fill(rates[0])), fs_an, frames_per_step, max_span_frames)
+      : nat.streamOpen(ctx, n_streams, rates[0], frames_per_step, max_span_frames);
     if (pred) nat.streamSetModel(st, model_on(nat, ctx));       // the native model on the stream's own context (ref src/index.js:56)
   } catch (e) {
     if (st) nat.streamClose(st);
@@ -600,6 +614,7 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
     nat.destroy(ctx); throw (typeof e === 'string' ? e : String(e.message || e));
   }
   const input = nat.streamInput(st);
+  const info = convert ? nat.streamInfo(st) : null;
   let open = true, started = false, meters = null;      // meters: the per-stream Label_conf_all of the last step (a prediction model only)
   const stopped = new Uint8Array(n_streams);          // streams that have had their segment_truncate since their last START
   const seg_seen = new Uint32Array(n_streams);        // level 3: segments a stream has closed since its last START (the callback index, ref @B28273)
@@ -657,8 +672,8 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
     return out;
   };
   const handle = {
-    input, samplesPerStep: input.length / n_streams, stopPending: false,
-    push(ctl = null) {
+    input, samplesPerStep: info ? info.samplesPerStep : input.length / n_streams, stopPending: false,
+    push(ctl = null, counts = null) {
       if (!open) throw 'stream closed';
       // StopAudioNodes (ref @B5699 -> disconnect_nodes @B21559): the frame in flight is still pushed, then every source is truncated
       // (segment_truncate, ref @B8851 / @B30757) — the open segments are flushed and reported, the object closes
@@ -670,7 +685,7 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
         if (c[i] & STREAM_STOP) stopped[i] = 1;
       }
       started = true;
-      const out = deliver(nat.streamStep(st, c));
+      const out = deliver(counts ? nat.streamStep(st, c, counts instanceof Uint32Array ? counts : Uint32Array.from(counts)) : nat.streamStep(st, c));
       if (handle.stopPending) handle.close(false);
       return out;
     },
@@ -691,6 +706,7 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
       return out;
     },
   };
+  if (info) Object.assign(handle, { capacity: info.capacity, inputStride: info.inputStride, paced: () => nat.streamPaced(st) });
   open_streams.add(handle);
   return handle;
 }

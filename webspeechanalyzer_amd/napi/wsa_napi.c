@@ -13,9 +13,13 @@
  *       runs wsa_batch_create / wsa_batch_run_host / wsa_batch_copy_rows on a worker thread
  *       (napi_async_work) so the JS thread stays free; the promise settles on the JS main thread.
  *   streamOpen(ctx, nStreams, fs, framesPerStep, maxSpanFrames) -> external stream      (wsa_stream_create)
- *   streamInput(stream) -> Float32Array over the pinned [nStreams][samplesPerStep] input buffer (no copy)
- *   streamStep(stream, ctl: Uint8Array | null) -> {meta, feat, segments}   (wsa_stream_step_host + wsa_stream_collect;
- *       one hipGraph launch, well under a millisecond, so it runs on the calling thread)
+ *   streamOpenMixed(ctx, nStreams, rates: Float64Array, fsOut, framesPerStep, maxSpanFrames) -> external stream   (wsa_stream_create_mixed:
+ *       stream i arrives at rates[i] and is converted to fsOut inside the step)
+ *   streamInfo(stream) -> {capacity: Uint32Array, inputStride, samplesPerStep}   (wsa_stream_input_capacity / _input_stride / _samples_per_step)
+ *   streamPaced(stream) -> Uint32Array: the samples a paced step takes from every stream next   (wsa_stream_paced_input)
+ *   streamInput(stream) -> Float32Array over the pinned [nStreams][inputStride] input buffer (no copy; inputStride = samplesPerStep on a plain set)
+ *   streamStep(stream, ctl: Uint8Array | null[, counts: Uint32Array | null]) -> {meta, feat, segments}   (wsa_stream_step_host[_n] + wsa_stream_collect;
+ *       one hipGraph launch, well under a millisecond, so it runs on the calling thread; counts: samples per stream in this step, else paced)
  *   streamSetModel(stream, model | null)        (wsa_stream_set_model: streamStep results gain prob, cb, cbLabel, cbConf, streamConf, nClasses)
  *   streamClose(stream)
  * Rejections carry the library's error string.  No compute happens in this file.
@@ -584,9 +588,56 @@ static napi_value fn_stream_open(napi_env env, napi_callback_info info) {
     if (wsa_stream_create(ctx, n, fs, fps, span, &h->st) != WSA_OK) { free(h); napi_throw_error(env, NULL, wsa_last_error(ctx)); return NULL; }
     h->box->children++;                                          /* until streamClose */
     wsa_stream_enable_graph(h->st, 1);
-    h->sps = wsa_stream_samples_per_step(h->st);
+    h->sps = wsa_stream_input_stride(h->st);                     /* (a plain set: samples_per_step) */
     napi_value ext; NAPI_OK(env, napi_create_external(env, h, stream_finalize, NULL, &ext));
     return ext;
+}
+static napi_value fn_stream_open_mixed(napi_env env, napi_callback_info info) {
+    size_t argc = 6; napi_value argv[6]; double fs_out = 0; uint32_t n = 0, fps = 1, span = 1024;
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    wsa_ctx *ctx = argc ? get_ctx(env, argv[0]) : NULL;
+    bool is_ta = false; napi_typedarray_type tt = napi_int8_array; size_t len = 0; void *data = NULL;
+    if (!ctx || argc < 4 || napi_get_value_uint32(env, argv[1], &n) != napi_ok || napi_is_typedarray(env, argv[2], &is_ta) != napi_ok || !is_ta
+        || napi_get_typedarray_info(env, argv[2], &tt, &len, &data, NULL, NULL) != napi_ok || tt != napi_float64_array || len != n
+        || napi_get_value_double(env, argv[3], &fs_out) != napi_ok) {
+        napi_throw_type_error(env, NULL, "streamOpenMixed(ctx, nStreams, rates: Float64Array(nStreams), fsOut, framesPerStep, maxSpanFrames)"); return NULL;
+    }
+    if (argc > 4) napi_get_value_uint32(env, argv[4], &fps);
+    if (argc > 5) napi_get_value_uint32(env, argv[5], &span);
+    stream_t *h = calloc(1, sizeof *h);
+    h->ctx = ctx; h->n = n; h->box = get_box(env, argv[0]);
+    if (wsa_stream_create_mixed(ctx, n, (const double *)data, fs_out, fps, span, &h->st) != WSA_OK) { free(h); napi_throw_error(env, NULL, wsa_last_error(ctx)); return NULL; }
+    h->box->children++;
+    wsa_stream_enable_graph(h->st, 1);
+    h->sps = wsa_stream_input_stride(h->st);
+    napi_value ext; NAPI_OK(env, napi_create_external(env, h, stream_finalize, NULL, &ext));
+    return ext;
+}
+static napi_value fn_stream_info(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    stream_t *h = argc ? get_stream(env, argv[0]) : NULL;
+    if (!h || !h->st) { napi_throw_type_error(env, NULL, "streamInfo(stream)"); return NULL; }
+    uint32_t *cap = malloc(sizeof(uint32_t) * (h->n ? h->n : 1));
+    for (uint32_t i = 0; i < h->n; i++) cap[i] = wsa_stream_input_capacity(h->st, i);
+    napi_value o, v;
+    napi_create_object(env, &o);
+    napi_set_named_property(env, o, "capacity", make_typed(env, napi_uint32_array, cap, (size_t)h->n, 4));
+    free(cap);
+    napi_create_uint32(env, wsa_stream_input_stride(h->st), &v); napi_set_named_property(env, o, "inputStride", v);
+    napi_create_uint32(env, wsa_stream_samples_per_step(h->st), &v); napi_set_named_property(env, o, "samplesPerStep", v);
+    return o;
+}
+static napi_value fn_stream_paced(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    stream_t *h = argc ? get_stream(env, argv[0]) : NULL;
+    if (!h || !h->st) { napi_throw_type_error(env, NULL, "streamPaced(stream)"); return NULL; }
+    uint32_t *cnt = malloc(sizeof(uint32_t) * (h->n ? h->n : 1));
+    for (uint32_t i = 0; i < h->n; i++) cnt[i] = wsa_stream_paced_input(h->st, i);
+    napi_value ta = make_typed(env, napi_uint32_array, cnt, (size_t)h->n, 4);
+    free(cnt);
+    return ta;
 }
 static napi_value fn_stream_input(napi_env env, napi_callback_info info) {
     size_t argc = 1; napi_value argv[1];
@@ -605,11 +656,21 @@ static napi_value fn_stream_input(napi_env env, napi_callback_info info) {
     return ta;
 }
 static napi_value fn_stream_step(napi_env env, napi_callback_info info) {
-    size_t argc = 2; napi_value argv[2];
+    size_t argc = 3; napi_value argv[3];
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     stream_t *h = argc ? get_stream(env, argv[0]) : NULL;
-    if (!h || !h->st) { napi_throw_type_error(env, NULL, "streamStep(stream, ctl)"); return NULL; }
+    if (!h || !h->st) { napi_throw_type_error(env, NULL, "streamStep(stream, ctl[, counts])"); return NULL; }
     const uint8_t *ctl = NULL;
+    const uint32_t *counts = NULL;
+    if (argc > 2) {
+        bool is_ta = false; napi_typedarray_type tt; size_t len; void *data;
+        if (napi_is_typedarray(env, argv[2], &is_ta) == napi_ok && is_ta) {
+            if (napi_get_typedarray_info(env, argv[2], &tt, &len, &data, NULL, NULL) != napi_ok || tt != napi_uint32_array || len != h->n) {
+                napi_throw_type_error(env, NULL, "counts must be a Uint32Array with one count per stream"); return NULL;
+            }
+            counts = (const uint32_t *)data;
+        }
+    }
     if (argc > 1) {
         bool is_ta = false; napi_typedarray_type tt; size_t len; void *data;
         if (napi_is_typedarray(env, argv[1], &is_ta) == napi_ok && is_ta) {
@@ -620,7 +681,7 @@ static napi_value fn_stream_step(napi_env env, napi_callback_info info) {
         }
     }
     wsa_stream_rows r;
-    if (wsa_stream_step_host(h->st, ctl, NULL) != WSA_OK || wsa_stream_collect(h->st, NULL, &r) != WSA_OK) {
+    if ((counts ? wsa_stream_step_host_n(h->st, counts, ctl, NULL) : wsa_stream_step_host(h->st, ctl, NULL)) != WSA_OK || wsa_stream_collect(h->st, NULL, &r) != WSA_OK) {
         napi_throw_error(env, NULL, wsa_last_error(h->ctx)); return NULL;
     }
     napi_value o;
@@ -775,7 +836,7 @@ NAPI_MODULE_INIT() {
     const struct { const char *name; napi_callback fn; } fns[] = {
         {"abiVersion", fn_abi_version}, {"freePinned", fn_free_pinned}, {"defaults", fn_defaults}, {"create", fn_create}, {"destroy", fn_destroy},
         {"geometry", fn_geometry}, {"allocPinned", fn_alloc_pinned}, {"binsHz", fn_bins_hz}, {"processBatch", fn_process_batch}, {"gatherRows", fn_gather_rows},
-        {"streamOpen", fn_stream_open}, {"streamInput", fn_stream_input}, {"streamStep", fn_stream_step}, {"streamClose", fn_stream_close}, {"streamSetModel", fn_stream_set_model},
+        {"streamOpen", fn_stream_open}, {"streamOpenMixed", fn_stream_open_mixed}, {"streamInfo", fn_stream_info}, {"streamPaced", fn_stream_paced}, {"streamInput", fn_stream_input}, {"streamStep", fn_stream_step}, {"streamClose", fn_stream_close}, {"streamSetModel", fn_stream_set_model},
         {"modelCreate", fn_model_create}, {"modelDestroy", fn_model_destroy}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
