@@ -12,11 +12,9 @@
 #include <mutex>
 #include <system_error>
 #include <thread>
-#include "wsa_internal.hpp"
+#include "host_plan.hpp"
 
 using namespace wsa;
-
-#include "api_internal.hpp"
 
 thread_local std::string wsa_api::g_create_error;
 using wsa_api::fail;
@@ -27,19 +25,12 @@ struct wsa_batch {
     double fs = 0;
     std::vector<uint32_t> n_samples, n_frames, frame_off;
     uint32_t total_frames = 0, max_frames = 0, max_samples = 0;
-    FePlanHost plan;
-    int seg_cap = 0, row_cap = 0, tcap = 0, pcap = 0, fcap = 0, n_waves = 0;
-    size_t ws_stride = 0, dev_bytes = 0;
-    // device memory
-    std::vector<void*> allocs;
-    float *d_window = nullptr, *d_mel_w = nullptr, *d_emph = nullptr;
-    float2 *d_tw_n2 = nullptr, *d_tw_64 = nullptr, *d_tw_nfft = nullptr, *d_tw_m = nullptr;
-    int32_t *d_mel_k0 = nullptr, *d_mel_cnt = nullptr, *d_mel_off = nullptr;
+    DevArena mem;                        // device and pinned memory (host_plan.hpp); the buffers that grow on demand (d_i16, the track gather's staging) are their own allocations
+    FeDev fe;                            // front-end plan and its device tables
+    Derived D;                           // what the configuration decides for the back end
+    BackEnd be;                          // back-end buffers and capacities
+    int n_waves = 0;
     uint32_t *d_n_frames = nullptr, *d_frame_off = nullptr, *d_spec = nullptr;
-    RecPtrs rec = {nullptr, nullptr, nullptr};      // frame records (wsa_internal.hpp)
-    char* d_ws = nullptr;
-    int32_t *d_seg_i = nullptr, *d_meta_pool = nullptr, *d_seg = nullptr, *d_meta = nullptr, *d_fr_info = nullptr;
-    double *d_seg_d = nullptr, *d_feat_pool = nullptr, *d_feat = nullptr, *d_fr_v = nullptr, *d_fr_fl = nullptr;
     uint2* d_order = nullptr;            // spans sorted by length, longest first (launch_span_order)
     uint2* d_redo = nullptr;             // spans the paired tracker variant hands to the one-span kernel
     char* d_pool = nullptr; double* d_span_hdr = nullptr; bool split = false; size_t pool_bpf = 0;   // split finalize: span regions (pool_bpf bytes per frame) + a header per span
@@ -50,20 +41,15 @@ struct wsa_batch {
     bool published = false;              // the last back-end run's compaction kernel has handed the result counters to the host itself
     Tuning tune;                         // tuning / test switches, read from the environment when the batch is planned
     uint32_t* d_span_hist = nullptr; uint2* d_span_key = nullptr;       // the gate's part of that sort: bucket counts, {bucket, rank} per segment
-    uint32_t *d_seg_count = nullptr, *d_clip_rows = nullptr, *d_counters = nullptr, *d_row_off = nullptr, *d_seg_off = nullptr, *d_totals = nullptr;
     float* d_pcm_own = nullptr;
-    float* d_formants = nullptr;            // levels 4 / 10 / 11: [total_frames][9]
     // sample-rate conversion in front of the path (wsa_batch_create_resampled): input lengths / rate, offset-kernel table, converted PCM
     bool rs_on = false; double fs_in = 0; std::vector<uint32_t> n_samples_in; uint32_t max_samples_in = 0;
     uint32_t *d_rs_n_in = nullptr, *d_rs_n_out = nullptr; float *d_rs_table = nullptr, *d_rs_pcm = nullptr; uint64_t rs_stride = 0;
     // ... for clips of different rates (wsa_batch_create_mixed): rate classes and the work list of K0's blocks, planned once (tables and list live on the device)
     bool rs_mixed = false; RsMixedPlan rs_plan; RsClass* d_rs_cls = nullptr; uint32_t* d_rs_clip_class = nullptr; RsWork* d_rs_work = nullptr;
-    int4* d_trk_pts = nullptr; int32_t* d_trk_rank = nullptr; int32_t* d_trk_seg = nullptr;      // level 3: raw-track pools (TrParams)
     bool counters_clean = false, end_clears = false, capturing = false, ever_captured = false;      // the fused compaction of the previous run has left the counters cleared: the next run launches no clear kernel
-    char* d_trk_stage = nullptr; size_t trk_stage_cap = 0; std::vector<uint64_t> h_trk_desc;        // level 3: wsa_batch_copy_tracks gathers through this
+    TrackGather trk;                                                                            // level 3: wsa_batch_copy_tracks gathers through this
     std::vector<int32_t> h_trk_seg; std::vector<uint32_t> h_seg_count;                          // level 3: host copies for wsa_batch_copy_tracks
-    float* d_sums = nullptr; double* d_coef_ws = nullptr;    // level 12
-    int32_t* d_utt_meta = nullptr; double* d_utt_feat = nullptr; uint32_t* d_utt_off = nullptr;   // level 11
     uint32_t res_utt = 0;
     double* d_trace = nullptr;
     uint32_t* h_totals = nullptr;           // pinned + mapped: rows, segs, flags, utterance results — written by batch_publish_kernel at the end of every run
@@ -75,24 +61,6 @@ struct wsa_batch {
     const uint32_t* spec_in_use = nullptr;
     wsa_cls* cls = nullptr;                 // wsa_batch_classify (classify.hip)
 };
-
-template <typename T>
-static bool dev_alloc(wsa_batch* b, T** p, size_t count) {
-    const size_t bytes = (count ? count : 1) * sizeof(T);
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes) != hipSuccess) return false;
-    b->allocs.push_back(q); b->dev_bytes += bytes;
-    *p = reinterpret_cast<T*>(q);
-    return true;
-}
-template <typename T, typename U>
-static bool dev_upload(wsa_batch* b, T** p, const std::vector<U>& v) {
-    static_assert(sizeof(U) <= sizeof(T) && sizeof(T) % sizeof(U) == 0, "upload type");
-    const size_t count = v.size() * sizeof(U) / sizeof(T);
-    if (!dev_alloc(b, p, count)) return false;
-    if (!v.empty() && hipMemcpy(*p, v.data(), v.size() * sizeof(U), hipMemcpyHostToDevice) != hipSuccess) return false;
-    return true;
-}
 
 namespace wsa {
 Tuning Tuning::from_env() {
@@ -190,16 +158,13 @@ wsa_status wsa_bins_hz(const wsa_ctx* ctx, double fs, double* out, int32_t n) {
 void wsa_batch_destroy(wsa_batch* b) {
     if (!b) return;
     (void)hipSetDevice(b->ctx->device);
-    for (void* p : b->allocs) (void)hipFree(p);
-    if (b->d_trk_stage) (void)hipFree(b->d_trk_stage);
     if (b->d_i16) (void)hipFree(b->d_i16);
     for (auto& st : b->up_stream) if (st) (void)hipStreamDestroy(st);
     for (auto& e : b->up_event) if (e) (void)hipEventDestroy(e);
     if (b->up_start) (void)hipEventDestroy(b->up_start);
-    if (b->h_totals) (void)hipHostFree(b->h_totals);
     for (auto& e : b->ev) if (e) (void)hipEventDestroy(e);
     wsa_cls_free(b->cls);
-    delete b;
+    delete b;                           // (the arena frees the rest)
 }
 
 static wsa_status batch_create_impl(wsa_ctx* ctx, uint32_t n_clips, const uint32_t* n_samples, double fs, const uint32_t* n_samples_in, double fs_in, wsa_batch** out, const double* fs_in_each = nullptr) {
@@ -210,13 +175,11 @@ static wsa_status batch_create_impl(wsa_ctx* ctx, uint32_t n_clips, const uint32
     b->ctx = ctx; b->n_clips = n_clips; b->fs = fs;
     b->tune = Tuning::from_env();
     std::string err;
-    if (!build_fe_plan(ctx->cfg, fs, b->plan, err)) { delete b; return fail(ctx, WSA_ERR_INVALID, err); }
-    const FePlanHost& P = b->plan;
-    if (!fe_supported_R(P.R, P.three)) { delete b; return fail(ctx, WSA_ERR_INVALID, "unsupported FFT length: NFFT = the smallest of {2^k, 3 * 2^k} >= max(window, fs * N_fft_bins / f_max) must lie in 256 .. 8192 or be 3 * 2^k up to 12288"); }
-    {   // the front-end kernel keeps its tables (window, twiddles, mel taps / power rows) in LDS: a geometry that needs more than a workgroup may have is refused here, not at the first launch
-        const size_t need = fe_lds_required(P, b->tune.fe_fat);
-        if (need > 160 * 1024) { delete b; return fail(ctx, WSA_ERR_INVALID, "this window / band setting needs " + std::to_string(need) + " bytes of LDS for the front end's tables (limit 163840): shorten the window or lower f_max / N_fft_bins"); }
-    }
+    const FeDev::Refusal refused = b->fe.build(ctx->cfg, fs, b->tune.fe_fat, err);
+    if (refused == FeDev::BAD_FFT) err = "unsupported FFT length: NFFT = the smallest of {2^k, 3 * 2^k} >= max(window, fs * N_fft_bins / f_max) must lie in 256 .. 8192 or be 3 * 2^k up to 12288";
+    if (refused == FeDev::LDS) err += ": shorten the window or lower f_max / N_fft_bins";
+    if (refused != FeDev::OK) { delete b; return fail(ctx, WSA_ERR_INVALID, err); }
+    const FePlanHost& P = b->fe.plan;
     b->n_samples.assign(n_samples, n_samples + n_clips);
     b->n_frames.resize(n_clips); b->frame_off.resize(n_clips + 1);
     uint64_t tot = 0;
@@ -231,92 +194,67 @@ static wsa_status batch_create_impl(wsa_ctx* ctx, uint32_t n_clips, const uint32
     b->frame_off[n_clips] = (uint32_t)tot; b->total_frames = (uint32_t)tot;
 
     // capacity bounds (DESIGN.md "capacities"): nothing below can overflow for any input
-    const wsa_config& c = ctx->cfg;
-    const double breaker = c.pause_length > 2 * c.window_step ? c.pause_length / c.window_step : 250 / c.window_step;
-    const double min_frames = std::trunc(c.min_seg_length / c.window_step);
-    const int period = (int)min_frames + 1 + (int)std::floor(breaker);
-    b->fcap = (int)b->max_frames + 2;
-    b->seg_cap = (int)b->max_frames / (period > 0 ? period : 1) + 2;
-    b->row_cap = (c.output_level == 10 || c.output_level == 11 || c.output_level == 12 || c.output_level == 13) ? (int)b->max_frames / 2 + 2 : b->seg_cap;
-    b->tcap = ((P.bands + 1) / 2) * b->fcap;
-    b->pcap = b->tcap;
-    b->ws_stride = tracker_ws_bytes(b->tcap, b->pcap, b->fcap, c.output_level == 3);
+    const Derived& D = b->D = Derived(ctx->cfg, P.bands);
+    BackEnd& B = b->be;
+    B.n = n_clips;
+    B.set_caps(D, P.bands, b->max_frames);
+    B.seg_cap = (int)b->max_frames / D.period + 2;
+    B.row_cap = D.syllable_rows ? (int)b->max_frames / 2 + 2 : B.seg_cap;
     // two spans per wave (two work spaces each) wherever the paired tracker variant applies: its bit map of peak bins covers 128 bands,
     // level 3 and the per-frame trace keep the one-span kernel (WSA_NO_PAIR=1: test hook)
-    b->pair = c.output_level != 3 && P.bands <= 128 && !b->tune.no_pair;
+    b->pair = !D.raw_tracks && P.bands <= 128 && !b->tune.no_pair;
     // split finalize (the paired accumulate and the finalize as two kernels; WSA_NO_SPLIT=1: test hook for the one-kernel variant): the spans' tracks and points
     // live in regions of one pool (4.7 KB per frame of the batch) instead of per-wave work spaces
     b->pool_bpf = tracker_pool_bpf();
     b->split = b->pair && !b->tune.no_split && (size_t)b->total_frames * b->pool_bpf <= ((size_t)48 << 30);      // (a plan of more than ~10 M frames keeps the per-wave work spaces: bounded memory)
     const size_t budget = (size_t)(b->pair ? 16 : 8) << 30;
-    size_t waves = budget / ((b->ws_stride ? b->ws_stride : 1) * (b->pair ? 2 : 1));
+    size_t waves = budget / ((b->be.ws_stride ? b->be.ws_stride : 1) * (b->pair ? 2 : 1));
     size_t wpc = 16;                                          // tracker waves per CU = what the default variant's registers and LDS allow (tuning knob WSA_TRACKER_WPC)
     if (b->tune.tracker_wpc >= 1 && b->tune.tracker_wpc <= 32) wpc = (size_t)b->tune.tracker_wpc;
     const size_t want = (size_t)ctx->n_cu * wpc;
     if (waves > want) waves = want;
-    if (waves > (size_t)n_clips * (size_t)b->seg_cap) waves = (size_t)n_clips * (size_t)b->seg_cap;
-    if (b->pair && waves > ((size_t)n_clips * (size_t)b->seg_cap + 1) / 2 && n_clips * (size_t)b->seg_cap > 256) waves = ((size_t)n_clips * (size_t)b->seg_cap + 1) / 2;   // a wave takes two spans (the redo kernel runs on up to 1024 of them)
+    if (waves > (size_t)n_clips * (size_t)b->be.seg_cap) waves = (size_t)n_clips * (size_t)b->be.seg_cap;
+    if (b->pair && waves > ((size_t)n_clips * (size_t)b->be.seg_cap + 1) / 2 && n_clips * (size_t)b->be.seg_cap > 256) waves = ((size_t)n_clips * (size_t)b->be.seg_cap + 1) / 2;   // a wave takes two spans (the redo kernel runs on up to 1024 of them)
     if (waves < 1) waves = 1;
     b->n_waves = (int)waves;
 
-    bool ok = true;
-    ok = ok && dev_upload(b, &b->d_window, P.window) && dev_upload(b, &b->d_tw_n2, P.tw_n2) && dev_upload(b, &b->d_tw_m, P.tw_m) && dev_upload(b, &b->d_tw_64, P.tw_64)
-            && dev_upload(b, &b->d_tw_nfft, P.tw_nfft) && dev_upload(b, &b->d_mel_k0, P.mel_k0) && dev_upload(b, &b->d_mel_cnt, P.mel_cnt)
-            && dev_upload(b, &b->d_mel_off, P.mel_off) && dev_upload(b, &b->d_mel_w, P.mel_w) && dev_upload(b, &b->d_emph, P.emph)
-            && dev_upload(b, &b->d_n_frames, b->n_frames) && dev_upload(b, &b->d_frame_off, b->frame_off);
-    ok = ok && dev_alloc(b, &b->d_spec, (size_t)b->total_frames * P.bands);
-    if (ok && c.output_level > 2 && b->split) {
+    DevArena& A = b->mem;
+    const size_t spans = (size_t)n_clips * B.seg_cap;
+    bool ok = b->fe.upload(A) && A.upload(&b->d_n_frames, b->n_frames) && A.upload(&b->d_frame_off, b->frame_off) && A.alloc(&b->d_spec, (size_t)b->total_frames * P.bands);
+    if (ok && D.level > 2 && b->split) {
         // split finalize: the span pool (4.7 KB per frame of the batch) and the span headers first — when the device cannot give them (several planned batches,
         // a cached plan, a smaller device), the plan falls back to the one-kernel paired tracker with its per-wave work spaces instead of failing
         size_t free_b = 0, total_b = 0;
         const size_t pool_bytes = (size_t)b->total_frames * b->pool_bpf;
         const bool room = hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b > pool_bytes + ((size_t)2 << 30);
-        if (!(room && dev_alloc(b, &b->d_pool, pool_bytes) && dev_alloc(b, &b->d_span_hdr, (size_t)n_clips * b->seg_cap * 8))) {
+        if (!(room && A.alloc(&b->d_pool, pool_bytes) && A.alloc(&b->d_span_hdr, spans * 8))) {
             (void)hipGetLastError();
             b->split = false; b->d_pool = nullptr; b->d_span_hdr = nullptr;
         }
     }
-    if (c.output_level > 2) {
-        const size_t ncand = (size_t)b->total_frames * CAND_CAP;
-        ok = ok && dev_alloc(b, &b->rec.hdr, (size_t)b->total_frames) && dev_alloc(b, &b->rec.amp, ncand) && dev_alloc(b, &b->rec.ent, ncand)
-                && dev_alloc(b, &b->d_ws, b->ws_stride * (size_t)b->n_waves * (b->pair && !b->split ? 2 : 1)) && dev_alloc(b, &b->d_redo, (size_t)n_clips * b->seg_cap)
-                && dev_alloc(b, &b->d_seg_i, (size_t)n_clips * b->seg_cap * 8) && dev_alloc(b, &b->d_seg_d, (size_t)n_clips * b->seg_cap * 2)
-                && dev_alloc(b, &b->d_seg_count, (size_t)n_clips) && dev_alloc(b, &b->d_clip_rows, (size_t)n_clips) && dev_alloc(b, &b->d_order, (size_t)n_clips * b->seg_cap)
-                && dev_alloc(b, &b->d_span_hist, (size_t)SPAN_BUCKETS) && dev_alloc(b, &b->d_span_key, (size_t)n_clips * b->seg_cap)
-                && dev_alloc(b, &b->d_fr_info, (size_t)b->total_frames) && dev_alloc(b, &b->d_fr_v, (size_t)b->total_frames)
-                && dev_alloc(b, &b->d_fr_fl, (size_t)b->total_frames)
-                && dev_alloc(b, &b->d_meta_pool, (size_t)n_clips * b->row_cap * 8) && dev_alloc(b, &b->d_feat_pool, (size_t)n_clips * b->row_cap * WSA_NFEAT)
-                && dev_alloc(b, &b->d_seg, (size_t)n_clips * b->seg_cap * 4) && dev_alloc(b, &b->d_meta, (size_t)n_clips * b->row_cap * 8)
-                && dev_alloc(b, &b->d_feat, (size_t)n_clips * b->row_cap * WSA_NFEAT);
-        if (c.output_level == 4 || c.output_level == 10 || c.output_level == 11 || c.output_level == 12) ok = ok && dev_alloc(b, &b->d_formants, (size_t)b->total_frames * 9);
-        if (c.output_level == 3) ok = ok && dev_alloc(b, &b->d_trk_pts, ((size_t)b->total_frames + 1) * 64 * 2) && dev_alloc(b, &b->d_trk_rank, ((size_t)b->total_frames + 1) * 64)
-                                         && dev_alloc(b, &b->d_trk_seg, (size_t)n_clips * b->seg_cap * 4);
-        if (c.output_level == 12) ok = ok && dev_alloc(b, &b->d_sums, (size_t)b->total_frames) && dev_alloc(b, &b->d_coef_ws, (size_t)b->total_frames * 8);
-        if (c.output_level == 11)
-            ok = ok && dev_alloc(b, &b->d_utt_meta, (size_t)n_clips * b->seg_cap * 4) && dev_alloc(b, &b->d_utt_feat, (size_t)n_clips * b->seg_cap * WSA_NUTT)
-                    && dev_alloc(b, &b->d_utt_off, (size_t)n_clips + 1);
-    }
-    ok = ok && dev_alloc(b, &b->d_counters, 16) && dev_alloc(b, &b->d_row_off, (size_t)n_clips + 1) && dev_alloc(b, &b->d_seg_off, (size_t)n_clips + 1)
-            && dev_alloc(b, &b->d_totals, 4);
-    if (ok) ok = hipHostMalloc(reinterpret_cast<void**>(&b->h_totals), 8 * sizeof(uint32_t), hipHostMallocMapped) == hipSuccess
-                 && hipHostGetDevicePointer(reinterpret_cast<void**>(&b->h_totals_dev), b->h_totals, 0) == hipSuccess;
-    if (ok) std::memset(b->h_totals, 0, 8 * sizeof(uint32_t));
+    ok = ok && B.alloc(A, D, b->total_frames, false) && A.alloc(&B.d_counters, 16);
+    if (D.level > 2)
+        ok = ok && A.alloc(&B.d_ws, B.ws_stride * (size_t)b->n_waves * (b->pair && !b->split ? 2 : 1)) && A.alloc(&b->d_redo, spans) && A.alloc(&b->d_order, spans)
+                && A.alloc(&b->d_span_hist, (size_t)SPAN_BUCKETS) && A.alloc(&b->d_span_key, spans)
+                && (!D.raw_tracks || (A.alloc(&B.d_trk_pts, ((size_t)b->total_frames + 1) * 64 * 2) && A.alloc(&B.d_trk_rank, ((size_t)b->total_frames + 1) * 64)))
+                && (D.level != 12 || A.alloc(&B.d_coef_ws, (size_t)b->total_frames * 8));
+    ok = ok && A.pin(&b->h_totals, &b->h_totals_dev, 8);
     for (auto& e : b->ev) if (ok) ok = hipEventCreate(&e) == hipSuccess;
     if (b->tune.full_table >= 0) b->full_table = b->tune.full_table != 0;       // test hook: start with the worst-case tracker variant
     if (ok && n_samples_in) {              // K0 in front: the caller's PCM is at fs_in, everything planned above works on the converted clips
         b->rs_on = true; b->fs_in = fs_in; b->n_samples_in.assign(n_samples_in, n_samples_in + n_clips);
         for (uint32_t i = 0; i < n_clips; i++) if (n_samples_in[i] > b->max_samples_in) b->max_samples_in = n_samples_in[i];
         b->rs_stride = ((uint64_t)b->max_samples + 3u) & ~3ull;
-        ok = dev_upload(b, &b->d_rs_n_in, b->n_samples_in) && dev_upload(b, &b->d_rs_n_out, b->n_samples) && dev_alloc(b, &b->d_rs_pcm, (size_t)n_clips * b->rs_stride + 4);
+        ok = A.upload(&b->d_rs_n_in, b->n_samples_in) && A.upload(&b->d_rs_n_out, b->n_samples) && b->mem.alloc(&b->d_rs_pcm, (size_t)n_clips * b->rs_stride + 4);
         if (ok && fs_in_each) {            // one rate per clip: classes + work list
             b->rs_mixed = true;
             if (!plan_resample_mixed(n_clips, b->n_samples.data(), fs_in_each, fs, b->rs_plan, err)) { wsa_batch_destroy(b); return fail(ctx, WSA_ERR_INVALID, err); }
             RsMixedPlan& M = b->rs_plan;
-            ok = dev_upload(b, &b->d_rs_table, M.tables) && dev_upload(b, &b->d_rs_cls, M.cls) && dev_upload(b, &b->d_rs_clip_class, M.clip_class) && dev_upload(b, &b->d_rs_work, M.work);
+            ok = A.upload(&b->d_rs_table, M.tables) && A.upload(&b->d_rs_cls, M.cls) && A.upload(&b->d_rs_clip_class, M.clip_class) && A.upload(&b->d_rs_work, M.work);
             std::vector<float>().swap(M.tables); std::vector<RsWork>().swap(M.work);
         } else if (ok) {
             std::vector<float> K0, K; build_resample_table(fs_in, fs, K0); resample_table_image(K0, K);
-            ok = dev_upload(b, &b->d_rs_table, K);
+            ok = A.upload(&b->d_rs_table, K);
         }
     }
     if (!ok) {
@@ -336,7 +274,7 @@ uint64_t wsa_resample_length(uint64_t n_in, double fs_in, double fs_out) { retur
 
 wsa_status wsa_batch_create_resampled(wsa_ctx* ctx, uint32_t n_clips, const uint32_t* n_samples_in, double fs_in, double fs_out, wsa_batch** out) {
     if (!ctx || !out || (n_clips && !n_samples_in)) return fail(ctx, WSA_ERR_INVALID, "null argument");
-    if (!(fs_in > 0) || !(fs_out > 0) || fs_in / fs_out > 16 || fs_out / fs_in > 16) return fail(ctx, WSA_ERR_INVALID, "sample rates must be positive and at most a factor 16 apart");
+    if (const wsa_status st = check_rates(ctx, &fs_in, 1, fs_out, nullptr); st != WSA_OK) return st;
     std::vector<uint32_t> n_out(n_clips);
     for (uint32_t i = 0; i < n_clips; i++) {
         const uint64_t n = resample_length(n_samples_in[i], fs_in, fs_out);
@@ -348,10 +286,9 @@ wsa_status wsa_batch_create_resampled(wsa_ctx* ctx, uint32_t n_clips, const uint
 
 wsa_status wsa_batch_create_mixed(wsa_ctx* ctx, uint32_t n_clips, const uint32_t* n_samples_in, const double* fs_in, double fs_out, wsa_batch** out) {
     if (!ctx || !out || (n_clips && (!n_samples_in || !fs_in))) return fail(ctx, WSA_ERR_INVALID, n_clips && ctx && out && !fs_in ? "null argument: fs_in holds one rate per clip (clip 0 has none)" : "null argument");
-    if (!(fs_out > 0)) return fail(ctx, WSA_ERR_INVALID, "sample rates must be positive and at most a factor 16 apart");
+    if (const wsa_status st = check_rates(ctx, fs_in, n_clips, fs_out, "clip"); st != WSA_OK) return st;
     std::vector<uint32_t> n_out(n_clips);
     for (uint32_t i = 0; i < n_clips; i++) {
-        if (!(fs_in[i] > 0) || fs_in[i] / fs_out > 16 || fs_out / fs_in[i] > 16) return fail(ctx, WSA_ERR_INVALID, "sample rates must be positive and at most a factor 16 apart (clip " + std::to_string(i) + ")");
         const uint64_t n = resample_length(n_samples_in[i], fs_in[i], fs_out);
         if (n > 0xfffffff0ull) return fail(ctx, WSA_ERR_INVALID, "a converted clip would exceed 2^32 samples (clip " + std::to_string(i) + ")");
         n_out[i] = (uint32_t)n;
@@ -361,68 +298,40 @@ wsa_status wsa_batch_create_mixed(wsa_ctx* ctx, uint32_t n_clips, const uint32_t
 
 wsa_status wsa_batch_get_info(const wsa_batch* b, wsa_batch_info* o) {
     if (!b || !o) return WSA_ERR_INVALID;
-    o->n_clips = b->n_clips; o->n_frames_total = b->total_frames; o->max_frames_per_clip = b->max_frames; o->bands = (uint32_t)b->plan.bands;
-    o->rows_cap = b->n_clips * (uint32_t)b->row_cap; o->segments_cap = b->n_clips * (uint32_t)b->seg_cap; o->workspace_bytes = b->dev_bytes;
+    o->n_clips = b->n_clips; o->n_frames_total = b->total_frames; o->max_frames_per_clip = b->max_frames; o->bands = (uint32_t)b->fe.plan.bands;
+    o->rows_cap = b->n_clips * (uint32_t)b->be.row_cap; o->segments_cap = b->n_clips * (uint32_t)b->be.seg_cap; o->workspace_bytes = b->mem.dev_bytes;
     return WSA_OK;
-}
-
-static void fill_fe(const wsa_batch* b, const float* d_pcm, uint64_t stride, FeParams& p) {
-    const FePlanHost& P = b->plan;
-    p.pcm = d_pcm; p.clip_stride = stride; p.n_frames = b->d_n_frames; p.frame_off = b->d_frame_off; p.spec = b->d_spec;
-    p.win = P.win; p.hop = P.hop; p.kmax = P.kmax; p.bands = P.bands; p.spec_type = P.spec_type; p.mel_total = (int)P.mel_w.size();
-    p.mel_max_taps = 0; for (int32_t c_ : P.mel_cnt) if (c_ > p.mel_max_taps) p.mel_max_taps = c_;
-    p.mel_max_taps_lo = 0; for (size_t i_ = 0; i_ < P.mel_cnt.size() && i_ < 64; i_++) if (P.mel_cnt[i_] > p.mel_max_taps_lo) p.mel_max_taps_lo = P.mel_cnt[i_];
-    p.frames_per_wave = b->tune.fpw > 0 ? b->tune.fpw : 25; p.pcm_off = nullptr;
-    p.fat = b->tune.fe_fat ? 1 : 0; p.wg_per_cu = b->tune.fe_wg_per_cu;
-    p.queue = b->tune.fe_no_queue ? nullptr : b->d_counters + 8; p.chunks_per_clip = 0; p.n_chunks = 0; p.n_cu = b->ctx->n_cu;      // (counters[8]: the front end's chunk queue, zeroed by batch_clear_kernel)
-    p.window = b->d_window; p.tw_n2 = b->d_tw_n2; p.tw_64 = b->d_tw_64; p.tw_nfft = b->d_tw_nfft; p.tw_m = b->d_tw_m;
-    p.mel_k0 = b->d_mel_k0; p.mel_cnt = b->d_mel_cnt; p.mel_off = b->d_mel_off; p.mel_w = b->d_mel_w; p.emph = b->d_emph; p.gain = P.gain;
 }
 
 static wsa_status run_backend_stages(wsa_batch* b, const uint32_t* d_spec, bool skip_peaks, hipStream_t s) {
     wsa_ctx* ctx = b->ctx;
-    const wsa_config& c = ctx->cfg;
+    const Derived& D = b->D;
+    const BackEnd& B = b->be;
     b->published = false;
-    if (c.output_level <= 2) return WSA_OK;
+    if (D.level <= 2) return WSA_OK;
     const int dbg = b->tune.dbg;
     {
         hipStream_t cs = s;
-        uint32_t* counters = b->d_counters + 4;             // [0] largest per-clip segment count
-        uint32_t* shared = b->d_counters;                   // [1] flags
-        PkParams pk; pk.spec = d_spec; pk.rec = b->rec; pk.frame0 = 0; pk.total_frames = b->total_frames; pk.bands = b->plan.bands;
-        pk.stream_state = nullptr; pk.n_frames = nullptr; pk.step_frames = 0; pk.ring = 0; pk.flags = shared + 1; pk.dbg = (b->tune.dbg >> 20) & 0xff; pk.lanes_only = b->tune.peaks_lanes ? 1 : 0;      // (WSA_DBG bits 20 .. 27: the peak scan's what-if switches, TUNING=1 builds only)
+        uint32_t* counters = B.d_counters + 4;              // [0] largest per-clip segment count
+        PkParams pk; pk.spec = d_spec; pk.rec = B.rec; pk.total_frames = b->total_frames; pk.bands = b->fe.plan.bands;
+        pk.flags = B.d_counters + 1; pk.dbg = (b->tune.dbg >> 20) & 0xff; pk.lanes_only = b->tune.peaks_lanes ? 1 : 0;      // (WSA_DBG bits 20 .. 27: the peak scan's what-if switches, TUNING=1 builds only)
         pk.wpc = b->tune.peaks_wpc; pk.round_bins = b->tune.peaks_w;
         if (!skip_peaks) launch_peaks(pk, cs);        // (a rerun of the back end finds the frame records in place)
         GateParams g;
-        g.rec = b->rec; g.n_frames = b->d_n_frames; g.frame_off = b->d_frame_off; g.clip0 = 0; g.n_clips = b->n_clips;
-        const int klevel = (c.output_level == 11 || c.output_level == 12) ? 10 : c.output_level;      // levels 11 / 12 store what level 10 stores (ref @B27713, @B27240)
-        g.level = klevel;
-        g.max_voiced_bin = (int)std::trunc(0.7 * b->plan.bands);                                   // ref @B25136
-        g.breaker = c.pause_length > 2 * c.window_step ? c.pause_length / c.window_step : 250 / c.window_step;   // ref @B25188
-        g.min_frames = std::trunc(c.min_seg_length / c.window_step);                               // ref @B25218
-        g.auto_gate = c.auto_noise_gate ? 1 : 0;
-        if (g.auto_gate) { g.ctx_max0 = 50; g.floor0 = 2; }                                        // ref @B25471
-        else { g.ctx_max0 = std::pow(10.0, c.voiced_max_dB / 20); g.floor0 = std::pow(10.0, c.voiced_min_dB / 20); }
-        g.fr_info = b->d_fr_info; g.fr_v = b->d_fr_v; g.fr_fl = b->d_fr_fl;
-        g.seg_i = b->d_seg_i; g.seg_d = b->d_seg_d; g.seg_cap = b->seg_cap; g.seg_count = b->d_seg_count;
-        g.clip_rows = b->d_clip_rows; g.counters = counters; g.shared = shared; g.trace = b->d_trace; g.dbg = dbg; g.strided = 1;
+        B.fill(g, D);
+        g.n_frames = b->d_n_frames; g.frame_off = b->d_frame_off; g.trace = b->d_trace; g.dbg = dbg; g.prio = 1;
         const bool ordered = !(dbg & 8192);                         // WSA_DBG bit 8192: (clip, segment) enumeration instead of the length-sorted order
         g.span_hist = ordered ? b->d_span_hist : nullptr; g.span_key = b->d_span_key;
-        g.state = nullptr; g.ctl = nullptr; g.ring = 0; g.step_frames = 0; g.prio = 1;
         launch_gate(g, cs);
         TrParams t;
-        t.rec = b->rec; t.frame_off = b->d_frame_off; t.level = klevel;
-        t.fr_info = b->d_fr_info; t.fr_v = b->d_fr_v; t.fr_fl = b->d_fr_fl;
-        t.seg_i = b->d_seg_i; t.seg_d = b->d_seg_d; t.seg_cap = b->seg_cap; t.seg_count = b->d_seg_count; t.n_clips = b->n_clips; t.counters = counters; t.shared = shared;
-        t.ws = b->d_ws; t.ws_stride = b->ws_stride; t.tcap = b->tcap; t.pcap = b->pcap; t.fcap = b->fcap;
-        t.row_meta = b->d_meta_pool; t.row_feat = b->d_feat_pool; t.row_cap = (uint32_t)b->row_cap; t.clip_rows = b->d_clip_rows; t.trace = b->d_trace;
-        t.dbg = dbg; t.ring_mask = 0xffffffffu; t.formants = b->d_formants; t.sums = b->d_sums; t.trk_pts = b->d_trk_pts; t.trk_rank = b->d_trk_rank; t.trk_seg = b->d_trk_seg;
-        t.order = ordered ? b->d_order : nullptr; t.order_cnt = 1; t.redo = b->d_redo; t.redo_count = counters + 2;
+        B.fill(t, D);
+        t.frame_off = b->d_frame_off; t.trace = b->d_trace; t.dbg = dbg;
+        t.order = ordered ? b->d_order : nullptr; t.redo = b->d_redo; t.redo_count = counters + 2;
         t.fin_waves = b->tune.fin_wpc >= 1 && b->tune.fin_wpc <= 32 ? ctx->n_cu * b->tune.fin_wpc : 0;
         // four spans per wave where the batch has spans enough to keep every wave slot busy that way (the 12 500-clip shard: -5 % per step); a 1024-clip batch
         // has ~6 000 spans = 1 500 such waves on 4 096 slots, and the longer waves cost more than the instructions they save (WSA_QUAD=1 / WSA_NO_QUAD=1 force it)
         t.quad = b->split && !b->tune.no_quad && (b->tune.quad || b->total_frames >= 1200000u) ? 1 : 0;
-        t.quad_waves = (int)std::min<size_t>((size_t)b->n_waves, ((size_t)b->n_clips * (size_t)b->seg_cap + 3) / 4 + 1);
+        t.quad_waves = (int)std::min<size_t>((size_t)b->n_waves, ((size_t)b->n_clips * (size_t)B.seg_cap + 3) / 4 + 1);
         t.pool = b->split ? b->d_pool : nullptr; t.pool_bpf = (uint32_t)b->pool_bpf; t.span_hdr = b->split ? b->d_span_hdr : nullptr;
         if (t.order) launch_span_order(t, b->d_span_hist, b->d_span_key, b->d_order, counters, cs);
         if (b->timing) HIP_TRY(ctx, hipEventRecord(b->ev[2], s));          // stage 1 = peak scan + gate + span order, stage 2 = tracker
@@ -430,31 +339,26 @@ static wsa_status run_backend_stages(wsa_batch* b, const uint32_t* d_spec, bool 
     }
     if (b->timing) HIP_TRY(ctx, hipEventRecord(b->ev[3], s));
     CompactParams cp;
-    cp.n_clips = b->n_clips; cp.seg_cap = b->seg_cap; cp.level = (c.output_level == 11 || c.output_level == 12) ? 10 : c.output_level;
-    cp.seg_i = b->d_seg_i; cp.seg_count = b->d_seg_count; cp.row_meta_in = b->d_meta_pool; cp.row_feat_in = b->d_feat_pool;
-    cp.seg_out = b->d_seg; cp.row_meta_out = b->d_meta; cp.row_feat_out = b->d_feat;
-    cp.clip_row_off = b->d_row_off; cp.clip_seg_off = b->d_seg_off; cp.totals = b->d_totals; cp.carry = nullptr; cp.ctl = nullptr;
+    B.fill(cp, D);
     // levels 11 / 12 run a kernel behind the compaction that adds to the result counters: they keep the separate publish at the end of the run
-    cp.clip_rows = b->d_clip_rows; cp.flags = b->d_counters + 1; cp.fused = b->tune.no_fuse ? 0 : 1;
-    cp.host = (c.output_level == 11 || c.output_level == 12) ? nullptr : b->h_totals_dev;
+    cp.clip_rows = B.d_clip_rows; cp.flags = B.d_counters + 1; cp.fused = b->tune.no_fuse ? 0 : 1;
+    cp.host = D.tail_kernel ? nullptr : b->h_totals_dev;
     b->published = compact_is_fused(cp) && cp.host != nullptr;
     // ... and, outside a stream capture, it leaves the counters cleared for the batch's next run (a captured run keeps its own clear kernel: a graph must not depend on what ran before it)
     const bool self_clear = b->published && !b->capturing;
-    cp.clr_counters = self_clear ? b->d_counters : nullptr; cp.clr_hist = self_clear ? b->d_span_hist : nullptr;
+    cp.clr_counters = self_clear ? B.d_counters : nullptr; cp.clr_hist = self_clear ? b->d_span_hist : nullptr;
     b->end_clears = self_clear;
     launch_compact(cp, s);
-    if (c.output_level == 11) {
+    if (D.level == 11) {
         UttParams u;
-        u.n_clips = b->n_clips; u.segments = b->d_seg; u.row_meta = b->d_meta; u.clip_seg_off = b->d_seg_off; u.clip_row_off = b->d_row_off;
-        u.frame_off = b->d_frame_off; u.formants = b->d_formants; u.clip_utt_off = b->d_utt_off; u.utt_meta = b->d_utt_meta; u.utt_feat = b->d_utt_feat;
-        u.totals = b->d_totals; u.state = nullptr; u.carry = nullptr; u.ctl = nullptr; u.ring_mask = 0xffffffffu;
+        B.fill(u, b->d_frame_off);
         launch_utterance(u, s);
     }
-    if (c.output_level == 12) {
+    if (D.level == 12) {
         CoefParams q;
-        q.row_meta = b->d_meta; q.row_feat = b->d_feat; q.frame_off = b->d_frame_off; q.totals = b->d_totals; q.formants = b->d_formants; q.sums = b->d_sums;
-        q.ws = b->d_coef_ws; q.total_frames = b->total_frames; q.shared = b->d_counters; q.ring_mask = 0xffffffffu; q.scratch_stride = 0;
-        launch_coeffs(q, b->n_clips * (uint32_t)b->row_cap, s);
+        B.fill(q, b->d_frame_off);
+        q.total_frames = b->total_frames;
+        launch_coeffs(q, b->n_clips * (uint32_t)B.row_cap, s);
     }
     HIP_TRY(ctx, hipGetLastError());
     return WSA_OK;
@@ -471,7 +375,7 @@ static wsa_status run_impl(wsa_batch* b, const float* d_pcm, uint64_t stride, co
     }
     // (the previous run's last kernel has cleared the counters already when it was the fused compaction: b->counters_clean.  A batch that has ever been
     //  captured into a graph clears in front of every run: a replay is a run this function does not see)
-    if (!b->counters_clean || b->ever_captured) hipLaunchKernelGGL(batch_clear_kernel, dim3(1), dim3(256), 0, s, b->d_counters, b->d_totals, b->d_span_hist);
+    if (!b->counters_clean || b->ever_captured) hipLaunchKernelGGL(batch_clear_kernel, dim3(1), dim3(256), 0, s, b->be.d_counters, b->be.d_totals, b->d_span_hist);
     b->counters_clean = false; b->end_clears = false;
     if (b->timing) HIP_TRY(ctx, hipEventRecord(b->ev[0], s));
     const uint32_t* spec = d_spec_in ? d_spec_in : b->d_spec;
@@ -492,8 +396,12 @@ static wsa_status run_impl(wsa_batch* b, const float* d_pcm, uint64_t stride, co
             HIP_TRY(ctx, hipGetLastError());
             d_pcm = b->d_rs_pcm; stride = b->rs_stride;
         }
-        FeParams p; fill_fe(b, d_pcm, stride, p);
-        launch_frontend(p, (int)b->n_clips, (int)b->max_frames, b->plan.R, b->plan.three, s);
+        FeParams p;
+        b->fe.fill(p, b->tune.fe_fat);
+        p.pcm = d_pcm; p.clip_stride = stride; p.n_frames = b->d_n_frames; p.frame_off = b->d_frame_off; p.spec = b->d_spec;
+        p.frames_per_wave = b->tune.fpw > 0 ? b->tune.fpw : 25; p.wg_per_cu = b->tune.fe_wg_per_cu;
+        p.queue = b->tune.fe_no_queue ? nullptr : b->be.d_counters + 8; p.n_cu = b->ctx->n_cu;      // (counters[8]: the front end's chunk queue, zeroed by batch_clear_kernel)
+        launch_frontend(p, (int)b->n_clips, (int)b->max_frames, b->fe.plan.R, b->fe.plan.three, s);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (b->timing) HIP_TRY(ctx, hipEventRecord(b->ev[1], s));
@@ -501,7 +409,7 @@ static wsa_status run_impl(wsa_batch* b, const float* d_pcm, uint64_t stride, co
         const wsa_status st = run_backend_stages(b, spec, false, s);
         if (st != WSA_OK) return st;
     } else if (b->timing) { HIP_TRY(ctx, hipEventRecord(b->ev[2], s)); HIP_TRY(ctx, hipEventRecord(b->ev[3], s)); }
-    if (!(be && b->published)) hipLaunchKernelGGL(batch_publish_kernel, dim3(1), dim3(64), 0, s, b->d_totals, b->d_counters, b->h_totals_dev);
+    if (!(be && b->published)) hipLaunchKernelGGL(batch_publish_kernel, dim3(1), dim3(64), 0, s, b->be.d_totals, b->be.d_counters, b->h_totals_dev);
     if (b->timing) HIP_TRY(ctx, hipEventRecord(b->ev[4], s));
     b->ran = true; b->spec_in_use = spec;
     b->counters_clean = be && b->end_clears && !b->capturing;
@@ -511,7 +419,7 @@ static wsa_status run_impl(wsa_batch* b, const float* d_pcm, uint64_t stride, co
 // tuning (not part of wsa.h): the batch's 16 device counters as the last run left them
 int wsa_debug_batch_counters(wsa_batch* b, uint32_t* out16) {
     if (!b || !out16) return WSA_ERR_INVALID;
-    return hipMemcpy(out16, b->d_counters, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess ? WSA_OK : WSA_ERR_HIP;
+    return hipMemcpy(out16, b->be.d_counters, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess ? WSA_OK : WSA_ERR_HIP;
 }
 
 wsa_status wsa_batch_run(wsa_batch* b, const float* d_pcm, uint64_t clip_stride, void* stream) {
@@ -633,7 +541,7 @@ wsa_status wsa_batch_run_host(wsa_batch* b, const float* const* pcm, void* strea
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const std::vector<uint32_t>& ns_host = b->rs_on ? b->n_samples_in : b->n_samples;      // what the caller holds: clips at the input rate
     const uint64_t stride = ((b->rs_on ? b->max_samples_in : b->max_samples) + 3u) & ~3ull;
-    if (!b->d_pcm_own && !dev_alloc(b, &b->d_pcm_own, (size_t)b->n_clips * stride)) return fail(ctx, WSA_ERR_HIP, "PCM staging allocation failed");
+    if (!b->d_pcm_own && !b->mem.alloc(&b->d_pcm_own, (size_t)b->n_clips * stride)) return fail(ctx, WSA_ERR_HIP, "PCM staging allocation failed");
     {
         const wsa_status st = upload_clips(b, b->n_clips, [&](uint32_t i) { return b->d_pcm_own + (size_t)i * stride; }, [&](uint32_t i) { return pcm[i]; },
                                            [&](uint32_t i) { return (size_t)ns_host[i] * sizeof(float); }, s);
@@ -649,7 +557,7 @@ wsa_status wsa_batch_run_host_i16(wsa_batch* b, const int16_t* const* pcm, const
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const std::vector<uint32_t>& ns_host = b->rs_on ? b->n_samples_in : b->n_samples;
     const uint64_t stride = ((b->rs_on ? b->max_samples_in : b->max_samples) + 3u) & ~3ull;
-    if (!b->d_pcm_own && !dev_alloc(b, &b->d_pcm_own, (size_t)b->n_clips * stride)) return fail(ctx, WSA_ERR_HIP, "PCM staging allocation failed");
+    if (!b->d_pcm_own && !b->mem.alloc(&b->d_pcm_own, (size_t)b->n_clips * stride)) return fail(ctx, WSA_ERR_HIP, "PCM staging allocation failed");
     // clip offsets inside one int16 upload buffer (8-byte aligned starts), grown when a run needs more than the last one
     std::vector<uint64_t> off(b->n_clips + 1, 0); std::vector<uint32_t> ch(b->n_clips ? b->n_clips : 1, 1u);
     for (uint32_t i = 0; i < b->n_clips; i++) {
@@ -663,7 +571,7 @@ wsa_status wsa_batch_run_host_i16(wsa_batch* b, const int16_t* const* pcm, const
         b->i16_cap = off[b->n_clips];
     }
     if (!b->d_i16_off) {
-        if (!dev_alloc(b, &b->d_i16_off, (size_t)b->n_clips + 1) || !dev_alloc(b, &b->d_i16_ch, (size_t)b->n_clips + 1) || !dev_alloc(b, &b->d_i16_ns, (size_t)b->n_clips + 1))
+        if (!b->mem.alloc(&b->d_i16_off, (size_t)b->n_clips + 1) || !b->mem.alloc(&b->d_i16_ch, (size_t)b->n_clips + 1) || !b->mem.alloc(&b->d_i16_ns, (size_t)b->n_clips + 1))
             return fail(ctx, WSA_ERR_HIP, "int16 staging allocation failed");
     }
     // (the three small tables travel from buffers the batch owns: the copies are asynchronous)
@@ -698,12 +606,12 @@ static wsa_status fetch_totals(wsa_batch* b, hipStream_t s) {
             // Unconditional on full_table: a hipGraph captured before the switch keeps replaying the fast
             // variant and may overflow again (wsa.h: re-capture after wsa_batch_backend_reruns() changed).
             b->full_table = true; b->reruns++;
-            hipLaunchKernelGGL(batch_clear_kernel, dim3(1), dim3(256), 0, s, b->d_counters, b->d_totals, b->d_span_hist);
+            hipLaunchKernelGGL(batch_clear_kernel, dim3(1), dim3(256), 0, s, b->be.d_counters, b->be.d_totals, b->d_span_hist);
             const bool tm = b->timing; b->timing = false;
             const wsa_status st = run_backend_stages(b, b->spec_in_use, true, s);
             b->timing = tm;
             if (st != WSA_OK) return st;
-            if (!b->published) hipLaunchKernelGGL(batch_publish_kernel, dim3(1), dim3(64), 0, s, b->d_totals, b->d_counters, b->h_totals_dev);
+            if (!b->published) hipLaunchKernelGGL(batch_publish_kernel, dim3(1), dim3(64), 0, s, b->be.d_totals, b->be.d_counters, b->h_totals_dev);
             HIP_TRY(ctx, hipStreamSynchronize(s));
             b->res_rows = ht[0]; b->res_segs = ht[1]; b->res_flags = ht[2]; b->res_utt = ht[3];
         }
@@ -742,8 +650,8 @@ void wsa_queue_destroy(wsa_ctx* ctx, void* stream) {
 }
 
 void wsa_batch_view_internal(wsa_batch* b, wsa_batch_view* v) {
-    v->ctx = b->ctx; v->level = b->ctx->cfg.output_level; v->n_clips = b->n_clips; v->rows_cap = b->n_clips * (uint32_t)b->row_cap;
-    v->d_meta = b->d_meta; v->d_feat = b->d_feat; v->d_row_off = b->d_row_off; v->reruns = b->reruns; v->cls = &b->cls;
+    v->ctx = b->ctx; v->level = b->ctx->cfg.output_level; v->n_clips = b->n_clips; v->rows_cap = b->n_clips * (uint32_t)b->be.row_cap;
+    v->d_meta = b->be.d_meta; v->d_feat = b->be.d_feat; v->d_row_off = b->be.d_row_off; v->reruns = b->reruns; v->cls = &b->cls;
 }
 wsa_status wsa_batch_fetch_internal(wsa_batch* b, hipStream_t s) { return fetch_totals(b, s); }
 
@@ -755,9 +663,9 @@ wsa_status wsa_batch_result(wsa_batch* b, void* stream, wsa_device_result* o) {
     const wsa_status st = fetch_totals(b, reinterpret_cast<hipStream_t>(stream));
     o->n_clips = b->n_clips; o->n_rows = b->res_rows; o->n_segments = b->res_segs; o->n_frames_total = b->total_frames;
     o->status_flags = b->res_flags;
-    o->d_row_meta = b->d_meta; o->d_row_feat = b->d_feat; o->d_segments = b->d_seg; o->d_clip_row_off = b->d_row_off; o->d_clip_seg_off = b->d_seg_off;
-    o->d_spectra = b->spec_in_use; o->d_clip_frame_off = b->d_frame_off; o->d_formants = b->d_formants;
-    o->n_utterance_rows = b->d_utt_feat ? b->res_utt : 0; o->d_utt_meta = b->d_utt_meta; o->d_utt_feat = b->d_utt_feat; o->d_clip_utt_off = b->d_utt_off;
+    o->d_row_meta = b->be.d_meta; o->d_row_feat = b->be.d_feat; o->d_segments = b->be.d_seg; o->d_clip_row_off = b->be.d_row_off; o->d_clip_seg_off = b->be.d_seg_off;
+    o->d_spectra = b->spec_in_use; o->d_clip_frame_off = b->d_frame_off; o->d_formants = b->be.d_formants;
+    o->n_utterance_rows = b->be.d_utt_feat ? b->res_utt : 0; o->d_utt_meta = b->be.d_utt_meta; o->d_utt_feat = b->be.d_utt_feat; o->d_clip_utt_off = b->be.d_utt_off;
     return st;
 }
 
@@ -770,11 +678,11 @@ wsa_status wsa_batch_copy_rows(wsa_batch* b, void* stream, int32_t* row_meta, do
     if (st != WSA_OK) return st;
     if ((row_meta || row_feat) && rows_cap < b->res_rows) return fail(ctx, WSA_ERR_INVALID, "row buffer too small");
     if (segments && seg_cap < b->res_segs) return fail(ctx, WSA_ERR_INVALID, "segment buffer too small");
-    if (row_meta && b->res_rows) HIP_TRY(ctx, hipMemcpyAsync(row_meta, b->d_meta, (size_t)b->res_rows * 8 * sizeof(int32_t), hipMemcpyDefault, s));
-    if (row_feat && b->res_rows) HIP_TRY(ctx, hipMemcpyAsync(row_feat, b->d_feat, (size_t)b->res_rows * WSA_NFEAT * sizeof(double), hipMemcpyDefault, s));
-    if (segments && b->res_segs) HIP_TRY(ctx, hipMemcpyAsync(segments, b->d_seg, (size_t)b->res_segs * 4 * sizeof(int32_t), hipMemcpyDefault, s));
-    if (clip_row_off) HIP_TRY(ctx, hipMemcpyAsync(clip_row_off, b->d_row_off, ((size_t)b->n_clips + 1) * sizeof(uint32_t), hipMemcpyDefault, s));
-    if (clip_seg_off) HIP_TRY(ctx, hipMemcpyAsync(clip_seg_off, b->d_seg_off, ((size_t)b->n_clips + 1) * sizeof(uint32_t), hipMemcpyDefault, s));
+    if (row_meta && b->res_rows) HIP_TRY(ctx, hipMemcpyAsync(row_meta, b->be.d_meta, (size_t)b->res_rows * 8 * sizeof(int32_t), hipMemcpyDefault, s));
+    if (row_feat && b->res_rows) HIP_TRY(ctx, hipMemcpyAsync(row_feat, b->be.d_feat, (size_t)b->res_rows * WSA_NFEAT * sizeof(double), hipMemcpyDefault, s));
+    if (segments && b->res_segs) HIP_TRY(ctx, hipMemcpyAsync(segments, b->be.d_seg, (size_t)b->res_segs * 4 * sizeof(int32_t), hipMemcpyDefault, s));
+    if (clip_row_off) HIP_TRY(ctx, hipMemcpyAsync(clip_row_off, b->be.d_row_off, ((size_t)b->n_clips + 1) * sizeof(uint32_t), hipMemcpyDefault, s));
+    if (clip_seg_off) HIP_TRY(ctx, hipMemcpyAsync(clip_seg_off, b->be.d_seg_off, ((size_t)b->n_clips + 1) * sizeof(uint32_t), hipMemcpyDefault, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
     return WSA_OK;
 }
@@ -785,7 +693,7 @@ wsa_status wsa_batch_copy_spectra(wsa_batch* b, void* stream, uint32_t* spectra,
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (!b->ran) return fail(ctx, WSA_ERR_INVALID, "no run on this batch yet");
     if (spectra && !b->spec_in_use) return fail(ctx, WSA_ERR_INVALID, "the u32 frames of this run were not stored: call wsa_batch_keep_spectra(batch, 1) before the run");
-    const uint64_t words = (uint64_t)b->total_frames * (uint32_t)b->plan.bands;
+    const uint64_t words = (uint64_t)b->total_frames * (uint32_t)b->fe.plan.bands;
     if (spectra && cap_words < words) return fail(ctx, WSA_ERR_INVALID, "spectra buffer too small");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (spectra && words) HIP_TRY(ctx, hipMemcpyAsync(spectra, b->spec_in_use, words * sizeof(uint32_t), hipMemcpyDefault, s));
@@ -798,13 +706,13 @@ wsa_status wsa_batch_copy_utterance(wsa_batch* b, void* stream, int32_t* utt_met
     if (!b) return WSA_ERR_INVALID;
     wsa_ctx* ctx = b->ctx;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (!b->d_utt_feat) return fail(ctx, WSA_ERR_INVALID, "no utterance features: output_level must be 11");
+    if (!b->be.d_utt_feat) return fail(ctx, WSA_ERR_INVALID, "no utterance features: output_level must be 11");
     const wsa_status st = fetch_totals(b, s);
     if (st != WSA_OK) return st;
     if ((utt_meta || utt_feat) && cap_rows < b->res_utt) return fail(ctx, WSA_ERR_INVALID, "utterance buffer too small");
-    if (utt_meta && b->res_utt) HIP_TRY(ctx, hipMemcpyAsync(utt_meta, b->d_utt_meta, (size_t)b->res_utt * 4 * sizeof(int32_t), hipMemcpyDefault, s));
-    if (utt_feat && b->res_utt) HIP_TRY(ctx, hipMemcpyAsync(utt_feat, b->d_utt_feat, (size_t)b->res_utt * WSA_NUTT * sizeof(double), hipMemcpyDefault, s));
-    if (clip_utt_off) HIP_TRY(ctx, hipMemcpyAsync(clip_utt_off, b->d_utt_off, ((size_t)b->n_clips + 1) * sizeof(uint32_t), hipMemcpyDefault, s));
+    if (utt_meta && b->res_utt) HIP_TRY(ctx, hipMemcpyAsync(utt_meta, b->be.d_utt_meta, (size_t)b->res_utt * 4 * sizeof(int32_t), hipMemcpyDefault, s));
+    if (utt_feat && b->res_utt) HIP_TRY(ctx, hipMemcpyAsync(utt_feat, b->be.d_utt_feat, (size_t)b->res_utt * WSA_NUTT * sizeof(double), hipMemcpyDefault, s));
+    if (clip_utt_off) HIP_TRY(ctx, hipMemcpyAsync(clip_utt_off, b->be.d_utt_off, ((size_t)b->n_clips + 1) * sizeof(uint32_t), hipMemcpyDefault, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
     return WSA_OK;
 }
@@ -813,10 +721,10 @@ wsa_status wsa_batch_copy_formants(wsa_batch* b, void* stream, float* formants, 
     if (!b || !formants) return WSA_ERR_INVALID;
     wsa_ctx* ctx = b->ctx;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (!b->ran || !b->d_formants) return fail(ctx, WSA_ERR_INVALID, "no formant frames: output_level must be 4, 10, 11 or 12 and the batch must have run");
+    if (!b->ran || !b->be.d_formants) return fail(ctx, WSA_ERR_INVALID, "no formant frames: output_level must be 4, 10, 11 or 12 and the batch must have run");
     if (cap_frames < b->total_frames) return fail(ctx, WSA_ERR_INVALID, "formant buffer too small");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (b->total_frames) HIP_TRY(ctx, hipMemcpyAsync(formants, b->d_formants, (size_t)b->total_frames * 9 * sizeof(float), hipMemcpyDefault, s));
+    if (b->total_frames) HIP_TRY(ctx, hipMemcpyAsync(formants, b->be.d_formants, (size_t)b->total_frames * 9 * sizeof(float), hipMemcpyDefault, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
     return WSA_OK;
 }
@@ -825,26 +733,30 @@ wsa_status wsa_batch_copy_formants(wsa_batch* b, void* stream, float* formants, 
 // ---- level 3: the ranked raw tracks of every segment (ref @B28273 `s.push(i)`, dispatched at @B30132)
 static wsa_status fetch_track_tables(wsa_batch* b, hipStream_t s) {
     wsa_ctx* ctx = b->ctx;
-    if (!b->d_trk_seg) return fail(ctx, WSA_ERR_INVALID, "no raw tracks: output_level must be 3");
+    if (!b->be.d_trk_seg) return fail(ctx, WSA_ERR_INVALID, "no raw tracks: output_level must be 3");
     const wsa_status st = fetch_totals(b, s);
     if (st != WSA_OK) return st;
-    b->h_trk_seg.resize((size_t)b->n_clips * b->seg_cap * 4); b->h_seg_count.resize(b->n_clips);
+    b->h_trk_seg.resize((size_t)b->n_clips * b->be.seg_cap * 4); b->h_seg_count.resize(b->n_clips);
     if (b->n_clips) {
-        HIP_TRY(ctx, hipMemcpyAsync(b->h_trk_seg.data(), b->d_trk_seg, b->h_trk_seg.size() * sizeof(int32_t), hipMemcpyDefault, s));
-        HIP_TRY(ctx, hipMemcpyAsync(b->h_seg_count.data(), b->d_seg_count, b->h_seg_count.size() * sizeof(uint32_t), hipMemcpyDefault, s));
+        HIP_TRY(ctx, hipMemcpyAsync(b->h_trk_seg.data(), b->be.d_trk_seg, b->h_trk_seg.size() * sizeof(int32_t), hipMemcpyDefault, s));
+        HIP_TRY(ctx, hipMemcpyAsync(b->h_seg_count.data(), b->be.d_seg_count, b->h_seg_count.size() * sizeof(uint32_t), hipMemcpyDefault, s));
         HIP_TRY(ctx, hipStreamSynchronize(s));
     }
     return WSA_OK;
+}
+
+static void batch_track_list(wsa_batch* b) {          // the segments in hand-out order: (clip, k); the batch's pool is one region
+    b->trk.begin();
+    for (uint32_t c = 0; c < b->n_clips; c++)
+        for (uint32_t k = 0; k < b->h_seg_count[c]; k++) b->trk.add(&b->h_trk_seg[((size_t)c * b->be.seg_cap + k) * 4], 0);
 }
 
 wsa_status wsa_batch_tracks_info(wsa_batch* b, void* stream, wsa_tracks_info* out) {
     if (!b || !out) return WSA_ERR_INVALID;
     const wsa_status st = fetch_track_tables(b, reinterpret_cast<hipStream_t>(stream));
     if (st != WSA_OK) return st;
-    uint64_t np = 0, nr = 0; uint32_t ns = 0;
-    for (uint32_t c = 0; c < b->n_clips; c++)
-        for (uint32_t k = 0; k < b->h_seg_count[c]; k++) { const int32_t* t = &b->h_trk_seg[((size_t)c * b->seg_cap + k) * 4]; np += (uint32_t)t[1]; nr += (uint32_t)t[2]; ns++; }
-    out->n_segments = ns; out->n_points = np; out->n_ranked = nr;
+    batch_track_list(b);
+    out->n_segments = b->trk.segments(); out->n_points = b->trk.n_points; out->n_ranked = b->trk.n_ranked;
     return WSA_OK;
 }
 
@@ -854,35 +766,11 @@ wsa_status wsa_batch_copy_tracks(wsa_batch* b, void* stream, uint64_t* seg_off, 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const wsa_status st = fetch_track_tables(b, s);
     if (st != WSA_OK) return st;
-    // one gather kernel into a staging buffer and two copies (a copy per segment was ~12 000 small copies for a 1024-clip batch)
-    uint64_t np = 0, nr = 0; uint32_t ns = 0;
-    b->h_trk_desc.clear();
-    for (uint32_t c = 0; c < b->n_clips; c++)
-        for (uint32_t k = 0; k < b->h_seg_count[c]; k++) {
-            const int32_t* t = &b->h_trk_seg[((size_t)c * b->seg_cap + k) * 4];
-            const uint64_t pool0 = (uint64_t)(uint32_t)t[0] | ((uint64_t)(uint32_t)t[3] << 32);
-            const uint32_t n_pt = (uint32_t)t[1], nq = (uint32_t)t[2];
-            if (np + n_pt > cap_points || nr + nq > cap_ranked) return fail(ctx, WSA_ERR_INVALID, "track buffers too small");
-            seg_off[2 * ns] = np; seg_off[2 * ns + 1] = nr;
-            const uint64_t d[6] = {pool0, 0ull, n_pt, nq, np, nr};
-            b->h_trk_desc.insert(b->h_trk_desc.end(), d, d + 6);
-            np += n_pt; nr += nq; ns++;
-        }
-    seg_off[2 * ns] = np; seg_off[2 * ns + 1] = nr;
-    if (np + nr) {
-        const size_t o_pts = ((size_t)ns * 6 * sizeof(uint64_t) + 255) & ~(size_t)255, o_rank = o_pts + (size_t)np * 8 * sizeof(int32_t), need = o_rank + (size_t)nr * sizeof(int32_t);
-        if (need > b->trk_stage_cap) {
-            if (b->d_trk_stage) { (void)hipFree(b->d_trk_stage); b->d_trk_stage = nullptr; b->trk_stage_cap = 0; }
-            if (hipMalloc(reinterpret_cast<void**>(&b->d_trk_stage), need + need / 4) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, WSA_ERR_HIP, "no device memory for the raw-track staging buffer"); }
-            b->trk_stage_cap = need + need / 4;
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(b->d_trk_stage, b->h_trk_desc.data(), (size_t)ns * 6 * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-        launch_gather_tracks(reinterpret_cast<const uint64_t*>(b->d_trk_stage), ns, 1ull << 63, b->d_trk_pts, b->d_trk_rank,
-                             reinterpret_cast<int4*>(b->d_trk_stage + o_pts), reinterpret_cast<int32_t*>(b->d_trk_stage + o_rank), s);
-        HIP_TRY(ctx, hipGetLastError());
-        if (np) HIP_TRY(ctx, hipMemcpyAsync(points, b->d_trk_stage + o_pts, (size_t)np * 8 * sizeof(int32_t), hipMemcpyDefault, s));
-        if (nr) HIP_TRY(ctx, hipMemcpyAsync(ranked, b->d_trk_stage + o_rank, (size_t)nr * sizeof(int32_t), hipMemcpyDefault, s));
-    }
+    TrackGather& G = b->trk;
+    batch_track_list(b);
+    if (G.n_points > cap_points || G.n_ranked > cap_ranked) return fail(ctx, WSA_ERR_INVALID, "track buffers too small");
+    G.offsets(seg_off);
+    if (const wsa_status gs = G.run(ctx, 1ull << 63, b->be.d_trk_pts, b->be.d_trk_rank, points, ranked, s); gs != WSA_OK) return gs;
     HIP_TRY(ctx, hipStreamSynchronize(s));
     return WSA_OK;
 }
@@ -914,7 +802,7 @@ wsa_status wsa_batch_enable_trace(wsa_batch* b, int32_t on) {
     if (on && !b->d_trace) {
         HIP_TRY(b->ctx, hipSetDevice(b->ctx->device));
         const size_t rows = b->total_frames ? b->total_frames : 1;      // an empty batch still gets a valid (unused) buffer
-        if (!dev_alloc(b, &b->d_trace, rows * 12)) return fail(b->ctx, WSA_ERR_HIP, "trace allocation failed");
+        if (!b->mem.alloc(&b->d_trace, rows * 12)) return fail(b->ctx, WSA_ERR_HIP, "trace allocation failed");
         HIP_TRY(b->ctx, hipMemset(b->d_trace, 0, rows * 12 * sizeof(double)));
     }
     if (!on) b->d_trace = nullptr;       // the allocation stays owned by the batch

@@ -7,8 +7,7 @@
 #include <cstring>
 #include <string>
 #include <vector>
-#include "wsa_internal.hpp"
-#include "api_internal.hpp"
+#include "host_plan.hpp"
 
 using wsa_api::fail;
 
@@ -326,7 +325,7 @@ struct wsa_model {
     double *d_min = nullptr, *d_max = nullptr;
     int32_t* d_key_rank = nullptr;
     bool softmax = false;
-    std::vector<void*> allocs;
+    wsa::DevArena mem;
 };
 
 struct wsa_cls {
@@ -337,27 +336,17 @@ struct wsa_cls {
     double *d_t_conf = nullptr, *d_cb_conf = nullptr, *d_clip_conf = nullptr;
     uint32_t *d_clip_cb = nullptr, *d_cb_off = nullptr;
     uint32_t *h_count = nullptr, *h_count_dev = nullptr;     // pinned + mapped: callbacks of the last fold
-    std::vector<void*> allocs;
+    wsa::DevArena mem;
     const wsa_model* model = nullptr; int level = 0, n_classes = 0; uint32_t reruns = 0; bool done = false;
 };
 
 void wsa_cls_free(wsa_cls* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    for (void* q : c->allocs) (void)hipFree(q);
-    if (c->h_count) (void)hipHostFree(c->h_count);
     delete c;
 }
 
 namespace {
-
-template <typename T>
-bool alloc_to(std::vector<void*>& v, T** p, size_t count) {
-    void* q = nullptr;
-    if (hipMalloc(&q, (count ? count : 1) * sizeof(T)) != hipSuccess) return false;
-    v.push_back(q); *p = reinterpret_cast<T*>(q);
-    return true;
-}
 
 bool array_index_key(const char* s, int32_t* out) {       // "0", "17" (no sign, no leading zero) below 2^31: an array index for Object.keys
     if (!s || !*s) return false;
@@ -423,7 +412,7 @@ struct wsa_scls {
     uint32_t C = 0;
     float* d_prob = nullptr;
     double *d_acc = nullptr, *d_cb_conf = nullptr; int32_t *d_in = nullptr, *d_cb = nullptr, *d_cb_label = nullptr; long long *d_first = nullptr, *d_stamp = nullptr;
-    std::vector<void*> allocs, pinned;
+    wsa::DevArena mem;
     float *h_prob = nullptr, *h_prob_dev = nullptr;
     int32_t *h_cb = nullptr, *h_cb_dev = nullptr, *h_cb_label = nullptr, *h_cb_label_dev = nullptr;
     double *h_cb_conf = nullptr, *h_cb_conf_dev = nullptr, *h_conf = nullptr, *h_conf_dev = nullptr;
@@ -434,22 +423,8 @@ struct wsa_scls {
 void wsa_scls_free(wsa_scls* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    for (void* q : c->allocs) (void)hipFree(q);
-    for (void* q : c->pinned) (void)hipHostFree(q);
     delete c;
 }
-
-namespace {
-template <typename T>
-bool pin_to(wsa_scls* c, T** h, T** dev, size_t count) {
-    void* q = nullptr;
-    if (hipHostMalloc(&q, (count ? count : 1) * sizeof(T), hipHostMallocMapped) != hipSuccess) return false;
-    c->pinned.push_back(q);
-    std::memset(q, 0, (count ? count : 1) * sizeof(T));
-    *h = reinterpret_cast<T*>(q);
-    return hipHostGetDevicePointer(reinterpret_cast<void**>(dev), q, 0) == hipSuccess;
-}
-}  // namespace
 
 wsa_status wsa_scls_create(const wsa_scls_view& v, const wsa_model* m, wsa_scls** out) {
     wsa_ctx* ctx = v.ctx;
@@ -460,17 +435,15 @@ wsa_status wsa_scls_create(const wsa_scls_view& v, const wsa_model* m, wsa_scls*
     wsa_scls* c = new wsa_scls();
     c->device = ctx->device; c->model = m; c->v = v; c->C = (uint32_t)m->C;
     const size_t R = v.rows_cap ? v.rows_cap : 1, NC = (size_t)v.n_streams * c->C, W = v.d2h_rows ? v.d2h_rows : 1;
-    bool ok = alloc_to(c->allocs, &c->d_prob, R * c->C);
+    wsa::DevArena& A = c->mem;
+    bool ok = A.alloc(&c->d_prob, R * c->C);
     if (ok && v.level == 13) {
-        ok = alloc_to(c->allocs, &c->d_acc, NC) && alloc_to(c->allocs, &c->d_in, NC) && alloc_to(c->allocs, &c->d_first, NC)
-             && alloc_to(c->allocs, &c->d_stamp, (size_t)v.n_streams) && alloc_to(c->allocs, &c->d_cb, R * 4)
-             && alloc_to(c->allocs, &c->d_cb_label, R) && alloc_to(c->allocs, &c->d_cb_conf, R)
-             && hipMemset(c->d_acc, 0, NC * sizeof(double)) == hipSuccess && hipMemset(c->d_in, 0, NC * sizeof(int32_t)) == hipSuccess
-             && hipMemset(c->d_first, 0, NC * sizeof(long long)) == hipSuccess && hipMemset(c->d_stamp, 0, (size_t)v.n_streams * sizeof(long long)) == hipSuccess
-             && pin_to(c, &c->h_cb, &c->h_cb_dev, W * 4) && pin_to(c, &c->h_cb_label, &c->h_cb_label_dev, W)
-             && pin_to(c, &c->h_cb_conf, &c->h_cb_conf_dev, W) && pin_to(c, &c->h_conf, &c->h_conf_dev, NC) && pin_to(c, &c->h_count, &c->h_count_dev, 4);
+        ok = A.alloc(&c->d_acc, NC, true) && A.alloc(&c->d_in, NC, true) && A.alloc(&c->d_first, NC, true) && A.alloc(&c->d_stamp, (size_t)v.n_streams, true)
+             && A.alloc(&c->d_cb, R * 4) && A.alloc(&c->d_cb_label, R) && A.alloc(&c->d_cb_conf, R)
+             && A.pin(&c->h_cb, &c->h_cb_dev, W * 4) && A.pin(&c->h_cb_label, &c->h_cb_label_dev, W)
+             && A.pin(&c->h_cb_conf, &c->h_cb_conf_dev, W) && A.pin(&c->h_conf, &c->h_conf_dev, NC) && A.pin(&c->h_count, &c->h_count_dev, 4);
     }
-    ok = ok && pin_to(c, &c->h_prob, &c->h_prob_dev, W * c->C) && hipDeviceSynchronize() == hipSuccess;
+    ok = ok && A.pin(&c->h_prob, &c->h_prob_dev, W * c->C) && hipDeviceSynchronize() == hipSuccess;
     if (!ok) {
         const std::string msg = std::string("device allocation failed: ") + hipGetErrorString(hipGetLastError());
         wsa_scls_free(c);
@@ -565,17 +538,14 @@ wsa_status wsa_model_create(wsa_ctx* ctx, const wsa_model_desc* d, wsa_model** o
         for (int k = 0; k < K; k++) std::memcpy(&w[(size_t)k * np], d->kernel[l] + (size_t)k * N, N * sizeof(float));
         std::memcpy(bb.data(), d->bias[l], N * sizeof(float));
         float *dw = nullptr, *db = nullptr;
-        ok = alloc_to(m->allocs, &dw, w.size()) && alloc_to(m->allocs, &db, bb.size())
-             && hipMemcpy(dw, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess
-             && hipMemcpy(db, bb.data(), bb.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+        ok = m->mem.upload(&dw, w) && m->mem.upload(&db, bb);
         m->L[l] = ClsLayer{dw, db, kp, np, N, d->activation[l]};
     }
     std::vector<int32_t> kr(m->C, -1);
     if (d->labels) for (int c = 0; c < m->C; c++) { int32_t v; if (array_index_key(d->labels[c], &v)) kr[c] = v; }
-    ok = ok && alloc_to(m->allocs, &m->d_min, WSA_NFEAT) && alloc_to(m->allocs, &m->d_max, WSA_NFEAT) && alloc_to(m->allocs, &m->d_key_rank, (size_t)m->C)
+    ok = ok && m->mem.alloc(&m->d_min, WSA_NFEAT) && m->mem.alloc(&m->d_max, WSA_NFEAT) && m->mem.upload(&m->d_key_rank, kr)
          && hipMemcpy(m->d_min, d->in_min, WSA_NFEAT * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
-         && hipMemcpy(m->d_max, d->in_max, WSA_NFEAT * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
-         && hipMemcpy(m->d_key_rank, kr.data(), kr.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
+         && hipMemcpy(m->d_max, d->in_max, WSA_NFEAT * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) {
         const std::string msg = std::string("device allocation / copy failed: ") + hipGetErrorString(hipGetLastError());
         wsa_model_destroy(m);
@@ -588,7 +558,6 @@ wsa_status wsa_model_create(wsa_ctx* ctx, const wsa_model_desc* d, wsa_model** o
 void wsa_model_destroy(wsa_model* m) {
     if (!m) return;
     (void)hipSetDevice(m->ctx->device);
-    for (void* q : m->allocs) (void)hipFree(q);
     delete m;
 }
 
@@ -618,19 +587,18 @@ wsa_status wsa_batch_classify(wsa_batch* b, const wsa_model* m, void* stream) {
         wsa_cls* n = new wsa_cls();
         n->device = ctx->device; n->cap_rows = v.rows_cap; n->cap_c = (uint32_t)m->C; n->n_clips = v.n_clips;
         const size_t R = v.rows_cap ? v.rows_cap : 1;
-        bool ok = alloc_to(n->allocs, &n->d_prob, R * m->C) && alloc_to(n->allocs, &n->d_t_label, R) && alloc_to(n->allocs, &n->d_t_conf, R)
-                  && alloc_to(n->allocs, &n->d_t_n, R) && alloc_to(n->allocs, &n->d_t_local, R) && alloc_to(n->allocs, &n->d_cb, R * 4)
-                  && alloc_to(n->allocs, &n->d_cb_label, R) && alloc_to(n->allocs, &n->d_cb_conf, R)
-                  && alloc_to(n->allocs, &n->d_clip_conf, (size_t)v.n_clips * m->C) && alloc_to(n->allocs, &n->d_clip_cb, (size_t)v.n_clips)
-                  && alloc_to(n->allocs, &n->d_cb_off, (size_t)v.n_clips);
-        ok = ok && hipHostMalloc(reinterpret_cast<void**>(&n->h_count), 4 * sizeof(uint32_t), hipHostMallocMapped) == hipSuccess
-                && hipHostGetDevicePointer(reinterpret_cast<void**>(&n->h_count_dev), n->h_count, 0) == hipSuccess;
+        wsa::DevArena& A = n->mem;
+        bool ok = A.alloc(&n->d_prob, R * m->C) && A.alloc(&n->d_t_label, R) && A.alloc(&n->d_t_conf, R)
+                  && A.alloc(&n->d_t_n, R) && A.alloc(&n->d_t_local, R) && A.alloc(&n->d_cb, R * 4)
+                  && A.alloc(&n->d_cb_label, R) && A.alloc(&n->d_cb_conf, R)
+                  && A.alloc(&n->d_clip_conf, (size_t)v.n_clips * m->C) && A.alloc(&n->d_clip_cb, (size_t)v.n_clips)
+                  && A.alloc(&n->d_cb_off, (size_t)v.n_clips);
+        ok = ok && A.pin(&n->h_count, &n->h_count_dev, 4);
         if (!ok) {
             const std::string msg = std::string("device allocation failed: ") + hipGetErrorString(hipGetLastError());
             wsa_cls_free(n);
             return fail(ctx, WSA_ERR_HIP, msg);
         }
-        std::memset(n->h_count, 0, 4 * sizeof(uint32_t));
         wsa_cls_free(c);
         c = n;
     }

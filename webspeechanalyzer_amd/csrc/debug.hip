@@ -1,7 +1,7 @@
 // debug.hip — test entries of libwsa that are NOT part of include/wsa.h: unit access to device-side pieces that the public
 // entry points only exercise through their consequences (tests/test_gpu_units.py).
 #include <vector>
-#include "wsa_internal.hpp"
+#include "host_plan.hpp"
 #include "jsmath_device.hpp"
 #include "gate_floor.hpp"
 #include "tracker_score.hpp"
@@ -61,28 +61,26 @@ __global__ __launch_bounds__(64) void debug_features_kernel(const float* fr_g, i
 extern "C" int wsa_debug_score(int32_t device, const double* args8, double* out, uint32_t n) {
     if (!args8 || !out) return WSA_ERR_INVALID;
     if (hipSetDevice(device) != hipSuccess) return WSA_ERR_NO_DEVICE;
-    double *da = nullptr, *dout = nullptr;
-    bool ok = hipMalloc(&da, (size_t)(n ? n : 1) * 64) == hipSuccess && hipMalloc(&dout, (size_t)(n ? n : 1) * 8) == hipSuccess;
+    wsa::DevArena A; double *da = nullptr, *dout = nullptr;
+    bool ok = A.alloc(&da, (size_t)n * 8) && A.alloc(&dout, n);
     ok = ok && hipMemcpy(da, args8, (size_t)n * 64, hipMemcpyHostToDevice) == hipSuccess;
     if (ok && n) {
         hipLaunchKernelGGL(wsa::debug_score_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, da, dout, n);
         ok = hipGetLastError() == hipSuccess && hipMemcpy(out, dout, (size_t)n * 8, hipMemcpyDeviceToHost) == hipSuccess;
     }
-    (void)hipFree(da); (void)hipFree(dout);
     return ok ? WSA_OK : WSA_ERR_HIP;
 }
 
 extern "C" int wsa_debug_floor_law(int32_t device, uint64_t lo, uint64_t hi, uint64_t* out3) {
     if (!out3 || hi > (1ull << 32) || lo > hi) return WSA_ERR_INVALID;
     if (hipSetDevice(device) != hipSuccess) return WSA_ERR_NO_DEVICE;
-    unsigned long long* d = nullptr;
+    wsa::DevArena A; unsigned long long* d = nullptr;
     unsigned long long init[3] = {0ull, ~0ull, 0ull};
-    bool ok = hipMalloc(&d, sizeof(init)) == hipSuccess && hipMemcpy(d, init, sizeof(init), hipMemcpyHostToDevice) == hipSuccess;
+    bool ok = A.alloc(&d, 3) && hipMemcpy(d, init, sizeof(init), hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
         hipLaunchKernelGGL(wsa::debug_floor_law_kernel, dim3(256 * 32), dim3(256), 0, nullptr, lo, hi, d);
         ok = hipGetLastError() == hipSuccess && hipMemcpy(init, d, sizeof(init), hipMemcpyDeviceToHost) == hipSuccess;
     }
-    (void)hipFree(d);
     out3[0] = init[0]; out3[1] = init[1]; out3[2] = init[2];
     return ok ? WSA_OK : WSA_ERR_HIP;
 }
@@ -90,16 +88,14 @@ extern "C" int wsa_debug_floor_law(int32_t device, uint64_t lo, uint64_t hi, uin
 extern "C" int wsa_debug_jsmath(int32_t device, int32_t fn, const double* x, const double* y, double* out, uint32_t n) {
     if (!x || !out || (fn == 1 && !y) || fn < 0 || fn > 2) return WSA_ERR_INVALID;
     if (hipSetDevice(device) != hipSuccess) return WSA_ERR_NO_DEVICE;
-    double *dx = nullptr, *dy = nullptr, *dout = nullptr;
-    const size_t bytes = (size_t)(n ? n : 1) * sizeof(double);
-    bool ok = hipMalloc(&dx, bytes) == hipSuccess && hipMalloc(&dy, bytes) == hipSuccess && hipMalloc(&dout, bytes) == hipSuccess;
+    wsa::DevArena A; double *dx = nullptr, *dy = nullptr, *dout = nullptr;
+    bool ok = A.alloc(&dx, n) && A.alloc(&dy, n) && A.alloc(&dout, n);
     ok = ok && hipMemcpy(dx, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
     if (ok && y) ok = hipMemcpy(dy, y, (size_t)n * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
     if (ok && n) {
         hipLaunchKernelGGL(wsa::debug_jsmath_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, fn, dx, dy, dout, n);
         ok = hipGetLastError() == hipSuccess && hipMemcpy(out, dout, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
     }
-    (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(dout);
     return ok ? WSA_OK : WSA_ERR_HIP;
 }
 
@@ -109,10 +105,9 @@ extern "C" int wsa_debug_features(int32_t device, const float* frames9, uint32_t
     if (!frames9 || !out53 || n < 1 || n > (1u << 24) || selector < 0 || selector > 4) return WSA_ERR_INVALID;
     if ((selector == 1 && n > 128) || (selector == 2 && n > (uint32_t)wsa::DBG_FEAT_LDS_FRAMES) || (selector == 3 && n > (uint32_t)wsa::FEAT_LDS_MAX) || (selector == 4 && n > 15)) return WSA_ERR_INVALID;
     if (hipSetDevice(device) != hipSuccess) return WSA_ERR_NO_DEVICE;
-    float* dfr = nullptr; double *dx = nullptr, *daev = nullptr;
-    const size_t nfr = (size_t)n * 9 * sizeof(float), naev = (size_t)3 * (n + 2) * sizeof(double);
-    bool ok = hipMalloc(&dfr, nfr) == hipSuccess && hipMalloc(&dx, 53 * sizeof(double)) == hipSuccess && hipMalloc(&daev, naev) == hipSuccess;
-    ok = ok && hipMemcpy(dfr, frames9, nfr, hipMemcpyHostToDevice) == hipSuccess && hipMemset(dx, 0, 53 * sizeof(double)) == hipSuccess && hipMemset(daev, 0, naev) == hipSuccess;
+    wsa::DevArena A; float* dfr = nullptr; double *dx = nullptr, *daev = nullptr;
+    const size_t nfr = (size_t)n * 9 * sizeof(float);
+    bool ok = A.alloc(&dfr, (size_t)n * 9) && A.alloc(&dx, 53, true) && A.alloc(&daev, (size_t)3 * (n + 2), true) && hipMemcpy(dfr, frames9, nfr, hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
         const int a = (int)n;
         switch (selector) {
@@ -124,7 +119,6 @@ extern "C" int wsa_debug_features(int32_t device, const float* frames9, uint32_t
         }
         ok = hipGetLastError() == hipSuccess && hipMemcpy(out53, dx, 53 * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
     }
-    (void)hipFree(dfr); (void)hipFree(dx); (void)hipFree(daev);
     return ok ? WSA_OK : WSA_ERR_HIP;
 }
 
@@ -135,9 +129,9 @@ extern "C" int wsa_debug_peaks(int32_t device, const uint32_t* spec, uint32_t n_
     if (!spec || !hdr || !amp || !ent || !flags || bands < 1 || n_frames < 1) return WSA_ERR_INVALID;
     if (hipSetDevice(device) != hipSuccess) return WSA_ERR_NO_DEVICE;
     const size_t nsp = (size_t)n_frames * bands * 4, nh = (size_t)n_frames * 16, na = (size_t)n_frames * wsa::CAND_CAP * 4, ne = (size_t)n_frames * wsa::CAND_CAP * 16;
-    char* d = nullptr;
+    wsa::DevArena A; char* d = nullptr;
     const size_t o_h = (nsp + 255) & ~(size_t)255, o_a = o_h + ((nh + 255) & ~(size_t)255), o_e = o_a + ((na + 255) & ~(size_t)255), o_f = o_e + ((ne + 255) & ~(size_t)255);
-    bool ok = hipMalloc(&d, o_f + 256) == hipSuccess && hipMemset(d, 0, o_f + 256) == hipSuccess && hipMemcpy(d, spec, nsp, hipMemcpyHostToDevice) == hipSuccess;
+    bool ok = A.alloc(&d, o_f + 256, true) && hipMemcpy(d, spec, nsp, hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
         wsa::PkParams p{};
         p.spec = reinterpret_cast<const uint32_t*>(d);
@@ -148,7 +142,6 @@ extern "C" int wsa_debug_peaks(int32_t device, const uint32_t* spec, uint32_t n_
              && hipMemcpy(hdr, d + o_h, nh, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(amp, d + o_a, na, hipMemcpyDeviceToHost) == hipSuccess
              && hipMemcpy(ent, d + o_e, ne, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(flags, d + o_f, 4, hipMemcpyDeviceToHost) == hipSuccess;
     }
-    (void)hipFree(d);
     return ok ? WSA_OK : WSA_ERR_HIP;
 }
 
@@ -157,9 +150,9 @@ extern "C" int wsa_debug_peaks_time(int32_t device, const uint32_t* spec, uint32
     if (!spec || !ms || bands < 1 || n_frames < 1 || reps < 1) return WSA_ERR_INVALID;
     if (hipSetDevice(device) != hipSuccess) return WSA_ERR_NO_DEVICE;
     const size_t nsp = (size_t)n_frames * bands * 4, nh = (size_t)n_frames * 16, na = (size_t)n_frames * wsa::CAND_CAP * 4, ne = (size_t)n_frames * wsa::CAND_CAP * 16;
-    char* d = nullptr;
+    wsa::DevArena A; char* d = nullptr;
     const size_t o_h = (nsp + 255) & ~(size_t)255, o_a = o_h + ((nh + 255) & ~(size_t)255), o_e = o_a + ((na + 255) & ~(size_t)255), o_f = o_e + ((ne + 255) & ~(size_t)255);
-    bool ok = hipMalloc(&d, o_f + 256) == hipSuccess && hipMemset(d, 0, o_f + 256) == hipSuccess && hipMemcpy(d, spec, nsp, hipMemcpyHostToDevice) == hipSuccess;
+    bool ok = A.alloc(&d, o_f + 256, true) && hipMemcpy(d, spec, nsp, hipMemcpyHostToDevice) == hipSuccess;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ok = ok && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
     if (ok) {
@@ -176,6 +169,5 @@ extern "C" int wsa_debug_peaks_time(int32_t device, const uint32_t* spec, uint32
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(d);
     return ok ? WSA_OK : WSA_ERR_HIP;
 }

@@ -48,21 +48,21 @@ struct Tuning {
 };
 
 struct FeParams {
-    const float* pcm; uint64_t clip_stride;
-    const uint32_t* n_frames;           // [n_clips]
-    const uint32_t* frame_off;          // [n_clips+1]
-    uint32_t* spec;                     // [total_frames][bands]
-    int win, hop, kmax, bands, spec_type, frames_per_wave, mel_total, mel_max_taps;
-    int mel_max_taps_lo;                // ... of the bands below 64 (the lower band of every lane)
-    const float* window; const float2* tw_n2; const float2* tw_64; const float2* tw_nfft;
-    const float2* tw_m;                 // W_M^j of the three M-point transforms behind the radix-3 stage (NFFT = 3 * 2^k), else nullptr
-    const int32_t* mel_k0; const int32_t* mel_cnt; const int32_t* mel_off; const float* mel_w;
-    const float* emph; float gain;
-    const uint32_t* pcm_off;            // optional per-clip sample offset into the clip's PCM (streaming warm-up), or nullptr
-    int fat, wg_per_cu;                 // host side only (Tuning::fe_fat, fe_wg_per_cu)
+    const float* pcm = nullptr; uint64_t clip_stride = 0;
+    const uint32_t* n_frames = nullptr; // [n_clips]
+    const uint32_t* frame_off = nullptr; // [n_clips+1]
+    uint32_t* spec = nullptr;           // [total_frames][bands]
+    int win = 0, hop = 0, kmax = 0, bands = 0, spec_type = 0, frames_per_wave = 0, mel_total = 0, mel_max_taps = 0;
+    int mel_max_taps_lo = 0;            // ... of the bands below 64 (the lower band of every lane)
+    const float* window = nullptr; const float2* tw_n2 = nullptr; const float2* tw_64 = nullptr; const float2* tw_nfft = nullptr;
+    const float2* tw_m = nullptr;       // W_M^j of the three M-point transforms behind the radix-3 stage (NFFT = 3 * 2^k), else nullptr
+    const int32_t* mel_k0 = nullptr; const int32_t* mel_cnt = nullptr; const int32_t* mel_off = nullptr; const float* mel_w = nullptr;
+    const float* emph = nullptr; float gain = 0;
+    const uint32_t* pcm_off = nullptr;  // optional per-clip sample offset into the clip's PCM (streaming warm-up), or nullptr
+    int fat = 0, wg_per_cu = 0;         // host side only (Tuning::fe_fat, fe_wg_per_cu)
     // persistent launch of the 1024-point kernel: workgroups take chunks of 4 x frames_per_wave frames of a clip from this counter (zeroed before the
     // launch) until all n_chunks = chunks_per_clip x clips are handed out; nullptr: one chunk per workgroup (grid = chunks)
-    uint32_t* queue; uint32_t chunks_per_clip, n_chunks; int n_cu;
+    uint32_t* queue = nullptr; uint32_t chunks_per_clip = 0, n_chunks = 0; int n_cu = 0;
 };
 
 // ---- per-frame peak candidates (output of the parallel half of the reference's frame loop D(), ref @B25827).
@@ -76,16 +76,16 @@ struct FeParams {
 // 20 bytes per candidate, a frame's candidates contiguous (the gate reads only hdr + amp).  Every frame (ring slot of a stream) has
 // its own CAND_CAP entries; consumers find a frame's table through hdr.w.
 constexpr int CAND_CAP = 64;               // candidates per frame (all a spectrum of <= 128 bands can have)
-struct RecPtrs { uint4* hdr; uint32_t* amp; uint4* ent; };
+struct RecPtrs { uint4* hdr = nullptr; uint32_t* amp = nullptr; uint4* ent = nullptr; };
 struct PkParams {
-    const uint32_t* spec; RecPtrs rec; uint32_t frame0, total_frames; int bands;   // frames [frame0, frame0 + total_frames)
+    const uint32_t* spec = nullptr; RecPtrs rec; uint32_t frame0 = 0, total_frames = 0; int bands = 0;   // frames [frame0, frame0 + total_frames)
     // streaming (stream_state != nullptr): spec holds step_frames frames per stream; frame j of stream s goes to
     // record slot s * ring + ((frames the stream has seen so far + j) & (ring - 1)); frames j >= n_frames[s] are skipped
-    const double* stream_state; const uint32_t* n_frames; uint32_t step_frames, ring;
-    uint32_t* flags;                    // bit 0 is raised when a frame holds more than CAND_CAP candidates (only possible above 128 bands)
-    int dbg;                            // tuning experiments (TUNING=1 builds, wsa_debug_peaks_time): 1 no emission, 2 no state machine, 4 no mask pass
-    int lanes_only, wpc;                // host side only (Tuning::peaks_lanes, peaks_wpc)
-    int round_bins;                     // host side only: bins per round of the lane-per-frame kernel, 16 or 32 (0: default)
+    const double* stream_state = nullptr; const uint32_t* n_frames = nullptr; uint32_t step_frames = 0, ring = 0;
+    uint32_t* flags = nullptr;          // bit 0 is raised when a frame holds more than CAND_CAP candidates (only possible above 128 bands)
+    int dbg = 0;                        // tuning experiments (TUNING=1 builds, wsa_debug_peaks_time): 1 no emission, 2 no state machine, 4 no mask pass
+    int lanes_only = 0, wpc = 0;        // host side only (Tuning::peaks_lanes, peaks_wpc)
+    int round_bins = 0;                 // host side only: bins per round of the lane-per-frame kernel, 16 or 32 (0: default)
 };
 
 // ---- sequential half, split in two (DESIGN.md "back end"):
@@ -96,92 +96,92 @@ struct PkParams {
 //                      so spans are independent of each other and run in parallel.
 struct GateParams {
     RecPtrs rec;
-    const uint32_t* n_frames; const uint32_t* frame_off; uint32_t clip0, n_clips;     // clips [clip0, clip0 + n_clips)
-    int level, max_voiced_bin; double breaker, min_frames; int auto_gate; double ctx_max0, floor0;   // ref @B24629
-    int32_t* fr_info;                   // per frame: -1 = accumulate_fm not called, else filing index | stale << 30
-    double* fr_v;                       // per frame: noise floor the peak scan used (`v` at frame start)
-    double* fr_fl;                      // per frame: noise floor handed to accumulate_fm (after the gate)
-    int32_t* seg_i; double* seg_d; int seg_cap;   // per clip [seg_cap][8] / [seg_cap][2], see SEG_* below
-    uint32_t* seg_count;                // [n_clips]
-    uint32_t* clip_rows;                // [n_clips] rows handed out of the clip's part of the row pool (zeroed here, bumped by the tracker)
-    uint32_t* counters;                 // [0] largest number of segments any clip holds (the tracker's enumeration bound)
-    uint32_t* shared;                   // batch-wide [1] flags (bit0 capacity overflow)
-    double* trace; int dbg;
+    const uint32_t* n_frames = nullptr; const uint32_t* frame_off = nullptr; uint32_t clip0 = 0, n_clips = 0;     // clips [clip0, clip0 + n_clips)
+    int level = 0, max_voiced_bin = 0; double breaker = 0, min_frames = 0; int auto_gate = 0; double ctx_max0 = 0, floor0 = 0;   // ref @B24629
+    int32_t* fr_info = nullptr;         // per frame: -1 = accumulate_fm not called, else filing index | stale << 30
+    double* fr_v = nullptr;             // per frame: noise floor the peak scan used (`v` at frame start)
+    double* fr_fl = nullptr;            // per frame: noise floor handed to accumulate_fm (after the gate)
+    int32_t* seg_i = nullptr; double* seg_d = nullptr; int seg_cap = 0;   // per clip [seg_cap][8] / [seg_cap][2], see SEG_* below
+    uint32_t* seg_count = nullptr;      // [n_clips]
+    uint32_t* clip_rows = nullptr;      // [n_clips] rows handed out of the clip's part of the row pool (zeroed here, bumped by the tracker)
+    uint32_t* counters = nullptr;       // [0] largest number of segments any clip holds (the tracker's enumeration bound)
+    uint32_t* shared = nullptr;         // batch-wide [1] flags (bit0 capacity overflow)
+    double* trace = nullptr; int dbg = 0;
     // span order (batch): every finalized segment takes a rank inside the bucket of its span length (longest first) — an atomic on
     // span_hist[bucket] — and notes {bucket, rank} in span_key[clip * seg_cap + segment]; launch_span_order turns them into the sorted list.  nullptr: off
-    uint32_t* span_hist; uint2* span_key;
-    int strided;                        // 1: frame slot's candidates start at slot * CAND_CAP (what the peak scans write); 0: a producer that packs the tables (none at present)
+    uint32_t* span_hist = nullptr; uint2* span_key = nullptr;
+    int strided = 1;                    // 1: frame slot's candidates start at slot * CAND_CAP (what the peak scans write); 0: a producer that packs the tables (none at present)
     // streaming (gate_stream_kernel): per-stream state carried from step to step, ring-indexed per-frame arrays
-    double* state;                      // [n_streams][GATE_STATE]
-    const uint32_t* ctl;                // [n_streams] bit0: fresh stream (launch state) before this step, bit1: segment_truncate after it
-    uint32_t ring, step_frames;         // ring = frames of history per stream (power of two)
-    int32_t* fr_span;                   // streams: per frame (ring-indexed) the first frame of the span the frame's accumulate_fm call belongs to, or nullptr
-    int prio;                           // 1: the batch gate kernel raises its wave priority
+    double* state = nullptr;            // [n_streams][GATE_STATE]
+    const uint32_t* ctl = nullptr;      // [n_streams] bit0: fresh stream (launch state) before this step, bit1: segment_truncate after it
+    uint32_t ring = 0, step_frames = 0; // ring = frames of history per stream (power of two)
+    int32_t* fr_span = nullptr;         // streams: per frame (ring-indexed) the first frame of the span the frame's accumulate_fm call belongs to, or nullptr
+    int prio = 0;                       // 1: the batch gate kernel raises its wave priority
 };
 enum { GATE_STATE = 16 };               // doubles per stream: cur_frame, no_fm, c_ci, c_started, ctx_max, floor, last_max, last_floor, w, T, k, span_begin, spans cut at the ring's capacity
 enum { SEG_START = 0, SEG_LEN = 1, SEG_FBEGIN = 2, SEG_FEND = 3, SEG_CCI = 4, SEG_FLAG = 5, SEG_NROWS = 6, SEG_ROW0 = 7 };
 
 struct TrParams {
     RecPtrs rec;
-    const uint32_t* frame_off;
-    int level;
-    const int32_t* fr_info; const double* fr_v; const double* fr_fl;
-    int32_t* seg_i; const double* seg_d; int seg_cap;
-    const uint32_t* seg_count; uint32_t n_clips; const uint32_t* counters; uint32_t* shared;
-    char* ws; uint64_t ws_stride; int tcap, pcap, fcap;
-    int32_t* row_meta; double* row_feat; uint32_t row_cap; uint32_t* clip_rows;     // row pool: row_cap rows per clip, filled in completion order
-    double* trace;
-    int dbg;                            // tuning experiments only (WSA_DBG)
-    uint32_t ring_mask;                 // 0xffffffff for a batch; ring - 1 when frames live in per-stream rings
-    float* formants;                    // levels 4 / 10: [total_frames][9] f32 straightened frames, or nullptr
+    const uint32_t* frame_off = nullptr;
+    int level = 0;
+    const int32_t* fr_info = nullptr; const double* fr_v = nullptr; const double* fr_fl = nullptr;
+    int32_t* seg_i = nullptr; const double* seg_d = nullptr; int seg_cap = 0;
+    const uint32_t* seg_count = nullptr; uint32_t n_clips = 0; const uint32_t* counters = nullptr; uint32_t* shared = nullptr;
+    char* ws = nullptr; uint64_t ws_stride = 0; int tcap = 0, pcap = 0, fcap = 0;
+    int32_t* row_meta = nullptr; double* row_feat = nullptr; uint32_t row_cap = 0; uint32_t* clip_rows = nullptr;     // row pool: row_cap rows per clip, filled in completion order
+    double* trace = nullptr;
+    int dbg = 0;                        // tuning experiments only (WSA_DBG)
+    uint32_t ring_mask = 0xffffffffu;   // 0xffffffff for a batch; ring - 1 when frames live in per-stream rings
+    float* formants = nullptr;          // levels 4 / 10: [total_frames][9] f32 straightened frames, or nullptr
     // incremental streaming (tracker_kernel_stream): tracker state of every stream between steps
-    int32_t* st_state; char* st_act;    // [n_streams][TR_STATE_WORDS] counters + accumulators, [n_streams][TR_ACT_BYTES] the active-track table
-    const int32_t* fr_span; const uint32_t* n_frames_step; const double* gate_state;   // GateParams::fr_span, frames of this step, GateParams::state
-    int4* trk_pts; int32_t* trk_rank; int32_t* trk_seg;   // level 3: point pool [frames * 64][2 x int4], ranked track ids [frames * 64], per segment {pool offset lo, points, ranked, offset hi}
-    const uint2* order;                 // batch: spans sorted by length (launch_span_order), counters[1] of them; nullptr: enumerate (clip, segment)
-    float* sums;                        // level 12: [total_frames] f32 per-frame energy sum of straighten (ref sums[d][1]), or nullptr
+    int32_t* st_state = nullptr; char* st_act = nullptr;    // [n_streams][TR_STATE_WORDS] counters + accumulators, [n_streams][TR_ACT_BYTES] the active-track table
+    const int32_t* fr_span = nullptr; const uint32_t* n_frames_step = nullptr; const double* gate_state = nullptr;   // GateParams::fr_span, frames of this step, GateParams::state
+    int4* trk_pts = nullptr; int32_t* trk_rank = nullptr; int32_t* trk_seg = nullptr;   // level 3: point pool [frames * 64][2 x int4], ranked track ids [frames * 64], per segment {pool offset lo, points, ranked, offset hi}
+    const uint2* order = nullptr;       // batch: spans sorted by length (launch_span_order), counters[1] of them; nullptr: enumerate (clip, segment)
+    float* sums = nullptr;              // level 12: [total_frames] f32 per-frame energy sum of straighten (ref sums[d][1]), or nullptr
     // paired spans (tracker_kernel_pair): spans the lock-step variant declines (more than 32 accepted peaks in a frame, more than 64 live tracks)
     // are listed here and redone by the one-span-per-wave kernel, which then runs with order = redo, order_cnt = 2
-    uint2* redo; uint32_t* redo_count;
-    int order_cnt;                      // `order` holds counters[order_cnt] entries
+    uint2* redo = nullptr; uint32_t* redo_count = nullptr;
+    int order_cnt = 1;                  // `order` holds counters[order_cnt] entries
     // split finalize (tracker_kernel_pair_acc + tracker_kernel_finalize): a span's tracks and points live in ITS region of `pool` — pool_bpf bytes per frame
     // of the batch, the region of a span starts at its first frame — and the accumulate kernel leaves span_hdr[(clip * seg_cap + segment) * 8] =
     // {tracks, points, stale index, stale points, sum g, sum E, 1 (finalize) | 2 (arena overflow) | 0 (on the redo list)} for the finalize kernel
-    char* pool; uint32_t pool_bpf; double* span_hdr;
-    int fin_waves;                      // host side only: grid of the finalize kernel (0: 2 x the tracking kernel's; Tuning::fin_wpc)
-    int quad, quad_waves;               // host side only: four spans per wave in the tracking kernel of the split tracker, its grid
+    char* pool = nullptr; uint32_t pool_bpf = 0; double* span_hdr = nullptr;
+    int fin_waves = 0;                  // host side only: grid of the finalize kernel (0: 2 x the tracking kernel's; Tuning::fin_wpc)
+    int quad = 0, quad_waves = 0;       // host side only: four spans per wave in the tracking kernel of the split tracker, its grid
 };
 
 struct CompactParams {
-    uint32_t n_clips; int seg_cap, level;
-    const int32_t* seg_i; const uint32_t* seg_count;
-    const int32_t* row_meta_in; const double* row_feat_in;
-    int32_t* seg_out; int32_t* row_meta_out; double* row_feat_out;
-    uint32_t* clip_row_off; uint32_t* clip_seg_off; uint32_t* totals;   // totals[0]=rows, [1]=segs
+    uint32_t n_clips = 0; int seg_cap = 0, level = 0;
+    const int32_t* seg_i = nullptr; const uint32_t* seg_count = nullptr;
+    const int32_t* row_meta_in = nullptr; const double* row_feat_in = nullptr;
+    int32_t* seg_out = nullptr; int32_t* row_meta_out = nullptr; double* row_feat_out = nullptr;
+    uint32_t* clip_row_off = nullptr; uint32_t* clip_seg_off = nullptr; uint32_t* totals = nullptr;   // totals[0]=rows, [1]=segs
     // streaming: the callback index and the segments_ci history continue across steps
-    int32_t* carry;                     // [n_streams][CARRY_WORDS]: segments so far, results so far, last CARRY_HIST [start, len]
-    const uint32_t* ctl;                // as GateParams::ctl
+    int32_t* carry = nullptr;           // [n_streams][CARRY_WORDS]: segments so far, results so far, last CARRY_HIST [start, len]
+    const uint32_t* ctl = nullptr;      // as GateParams::ctl
     // fused form (batches; compact_gather_kernel<true>): per-clip row counters as the tracker left them, the flag word, the host's mapped result words (or nullptr)
-    const uint32_t* clip_rows; const uint32_t* flags; uint32_t* host; int fused;
+    const uint32_t* clip_rows = nullptr; const uint32_t* flags = nullptr; uint32_t* host = nullptr; int fused = 0;
     // fused form only: the run's last wave leaves the batch's 16 counters, its totals and its span histogram cleared for the next run (nullptr: the caller launches its clear kernel)
-    uint32_t* clr_counters; uint32_t* clr_hist;
+    uint32_t* clr_counters = nullptr; uint32_t* clr_hist = nullptr;
 };
 bool compact_is_fused(const CompactParams& p);
 enum { CARRY_HIST = 32, CARRY_WORDS = 2 + 2 * CARRY_HIST };
 
 // ---- K4 utterance features (output_level 11): reads the compacted level-10 products
 struct UttParams {
-    uint32_t n_clips;
-    const int32_t* segments; const int32_t* row_meta;                       // compacted tables (K3 output)
-    const uint32_t* clip_seg_off; const uint32_t* clip_row_off; const uint32_t* frame_off;
-    const float* formants;
-    uint32_t* clip_utt_off;             // [n_clips + 1]
-    int32_t* utt_meta; double* utt_feat; // [results][4] = {clip, k, first start, sum of lengths}, [results][264]
-    uint32_t* totals;                   // totals[3] = number of results
+    uint32_t n_clips = 0;
+    const int32_t* segments = nullptr; const int32_t* row_meta = nullptr;   // compacted tables (K3 output)
+    const uint32_t* clip_seg_off = nullptr; const uint32_t* clip_row_off = nullptr; const uint32_t* frame_off = nullptr;
+    const float* formants = nullptr;
+    uint32_t* clip_utt_off = nullptr;   // [n_clips + 1]
+    int32_t* utt_meta = nullptr; double* utt_feat = nullptr; // [results][4] = {clip, k, first start, sum of lengths}, [results][264]
+    uint32_t* totals = nullptr;         // totals[3] = number of results
     // streams (state != nullptr): the tables hold this step's segments / rows only and everything the reference accumulates over a launch is
     // carried per stream: [UTT_STATE_WORDS] = 264 histogram bins, 16 ghost counters, results / segments so far, prev_end, tsum, first start;
     // carry = CompactParams::carry (segments_ci history, already advanced over this step), ctl as GateParams::ctl, frames in rings
-    uint32_t* state; const int32_t* carry; const uint32_t* ctl; uint32_t ring_mask;
+    uint32_t* state = nullptr; const int32_t* carry = nullptr; const uint32_t* ctl = nullptr; uint32_t ring_mask = 0xffffffffu;
 };
 enum { UTT_STATE_WORDS = 288 };
 
@@ -249,7 +249,7 @@ uint32_t resample_step_outputs_bound(uint32_t frames_per_step, uint32_t hop, dou
 
 void launch_frontend(const FeParams& p, int n_clips, int max_frames, int R, int three, hipStream_t s);
 bool fe_supported_R(int R, int three);  // packed FFT length 64 R, R in {2, 4, 8, 16, 32, 64}, or 3 * 64 R, R in {1, 2, 4, 8, 16, 32}
-size_t fe_lds_required(const FePlanHost& P, bool fat);      // dynamic LDS of the front-end kernel this geometry selects (limit: 160 KB per workgroup)
+size_t fe_lds_required(const FePlanHost& P, bool fat);      // dynamic LDS of the front-end kernel this geometry selects (limit: LDS_LIMIT, host_plan.hpp)
 void launch_peaks(const PkParams& p, hipStream_t s);
 void launch_peaks_mode(const PkParams& p, int mode, hipStream_t s);   // 1: lane-per-frame kernel, 2: wave-per-frame kernel (tests)
 void launch_gate(const GateParams& p, hipStream_t s);
@@ -259,22 +259,20 @@ void launch_tracker(const TrParams& p, int n_waves, bool full_table, bool pair, 
 enum { SPAN_BUCKETS = 2048 };          // span lengths 0 .. 2047+ frames, bucket = SPAN_BUCKETS - 1 - min(frames, SPAN_BUCKETS - 1)
 void launch_span_order(const TrParams& p, uint32_t* span_hist, const uint2* span_key, uint2* order, uint32_t* counters, hipStream_t s);
 void launch_tracker_stream(const TrParams& p, uint32_t n_streams, hipStream_t s);
-// level 3: gathers the segments' raw-track pieces out of the pools (desc: 6 words per segment, stream_api.hip) into dense tables
-void launch_gather_tracks(const uint64_t* desc, uint32_t n_segments, uint64_t region, const int4* pts, const int32_t* rank, int4* out_pts, int32_t* out_rank, hipStream_t s);
 enum { TR_STATE_WORDS = 16, TR_ACT_MAX = 320, TR_ACT_BYTES = TR_ACT_MAX * 44 };
 void launch_compact(const CompactParams& p, hipStream_t s);
 void launch_utterance(const UttParams& p, hipStream_t s);
 
 // ---- K5 polynomial coefficients (output_level 12): reads the compacted level-10 rows + frames + energy sums
 struct CoefParams {
-    const int32_t* row_meta; double* row_feat;      // compacted rows: 23 numbers go to row_feat[row][0..22]
-    const uint32_t* frame_off; const uint32_t* totals;   // totals[0] = number of rows
-    const float* formants; const float* sums;        // [total_frames][9], [total_frames]
-    double* ws; uint32_t total_frames;               // scratch: 8 x total_frames doubles (points of the four fits)
-    uint32_t* shared;                                // flags (bit 2: a fit hit numeric's "gradient fails" path)
+    const int32_t* row_meta = nullptr; double* row_feat = nullptr;      // compacted rows: 23 numbers go to row_feat[row][0..22]
+    const uint32_t* frame_off = nullptr; const uint32_t* totals = nullptr;   // totals[0] = number of rows
+    const float* formants = nullptr; const float* sums = nullptr;        // [total_frames][9], [total_frames]
+    double* ws = nullptr; uint32_t total_frames = 0;               // scratch: 8 x total_frames doubles (points of the four fits)
+    uint32_t* shared = nullptr;                      // flags (bit 2: a fit hit numeric's "gradient fails" path)
     // streams: the frames live in per-stream rings (frame f of stream c at frame_off[c] + (f & ring_mask)); a syllable's scratch rows are
     // then taken from a per-stream region of scratch_stride (= 2 x ring) rows, where they do not wrap.  Batches: ring_mask = ~0, scratch_stride = 0
-    uint32_t ring_mask, scratch_stride;
+    uint32_t ring_mask = 0xffffffffu, scratch_stride = 0;
 };
 void launch_coeffs(const CoefParams& p, uint32_t rows_cap, hipStream_t s);
 size_t tracker_ws_bytes(int tcap, int pcap, int fcap, bool raw_tracks);
