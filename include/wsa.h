@@ -413,6 +413,82 @@ wsa_status wsa_batch_copy_classes(wsa_batch *b, void *stream, float *prob, uint3
                                   uint32_t cb_cap, double *clip_conf);
 
 /*
+ * ---- Ensembles: every model DB of the application in one pass (additions within version 5: probe for wsa_ensemble_create).
+ * The reference application does not predict with one model: predict_by_multiple_syllables runs the model of every DB in
+ * `available_DBs` over a callback's syllables (ref src/prediction.js:12, 60-63) and folds each DB's confidences separately
+ * (Label_conf_all[db], Label_conf_seg[db]).  seg_confidence_sort (ref prediction.js:127-169) then reports the label of the DB with
+ * the largest segment sum and keeps `min_entropy_db`, the DB whose launch-long accumulator is the most decided; that DB's meters
+ * and "Entropy" readout are what the user sees (plot_prediction_meters, ref prediction.js:172-215).  An ensemble is that list of
+ * DBs.  K6e classifies with all members in one launch over (member, tile) pairs — a member's probabilities are bit for bit those of
+ * wsa_classify_rows with that model — K6b-e folds with one wave per (clip, member) and decides in the same kernel, and one compaction
+ * writes every table, so an ensemble costs three launches whatever its size (DESIGN.md "K6e").
+ *
+ * One difference from the reference, on purpose: it never resets `min_entropy_db` itself — reset_predictions(true) resets only
+ * max_inv_entropy (ref prediction.js:35) — so a launch in which no accumulator exceeds 0 keeps showing the previous launch's DB.
+ * The device knows one launch at a time and reports -1 for such a clip or stream; a host that wants the reference's behaviour
+ * carries the last non-negative value across launches, in the order it dispatched them (the N-API layer's job).
+ */
+#define WSA_ENSEMBLE_MAX 8
+typedef struct wsa_ensemble wsa_ensemble;
+/* Members in the order of `available_DBs`: every tie between DBs goes to the earlier member (the strict > of ref prediction.js:156,
+ * 161).  n = 1 .. WSA_ENSEMBLE_MAX; the same model may be two members.  WSA_ERR_INVALID: n out of range, a NULL member, a member of
+ * another context.  The models must outlive the ensemble; destroy it before its context. */
+wsa_status wsa_ensemble_create(wsa_ctx *ctx, const wsa_model *const *models, uint32_t n, wsa_ensemble **out);
+void       wsa_ensemble_destroy(wsa_ensemble *e);
+/* As wsa_batch_classify, with every member: level 13 gives probabilities, per-member folds and the decision (every member must
+ * end in softmax, else WSA_ERR_INVALID), level 5 per-member probabilities only, any other level WSA_ERR_INVALID.  Enqueued on
+ * `stream`; after the first call with an ensemble on a batch nothing is allocated, so wsa_batch_run + wsa_batch_classify_ensemble
+ * can be captured into a hipGraph.  The ensemble must outlive the batch's use of its tables. */
+wsa_status wsa_batch_classify_ensemble(wsa_batch *b, const wsa_ensemble *e, void *stream);
+/* Synchronises `stream` and hands out the last ensemble classification (device pointers, valid until the next
+ * wsa_batch_classify_ensemble with another ensemble or wsa_batch_destroy).  Per member d < n_members:
+ *   d_prob[d]       [n_rows][n_classes[d]] f32
+ *   d_cb_label[d], d_cb_conf[d] [n_callbacks]: what wsa_class_result gives for that model alone (-1 / -2 alike)
+ *   d_cb_all_max[d] [n_callbacks] f64: DB_entropies_all[d] after that callback, the largest entry of the member's Label_conf_all (0 if none
+ *                   exceeds 0; ref prediction.js:136-153)
+ *   d_clip_conf[d]  [n_clips][n_classes[d]] f64: the member's Label_conf_all per clip
+ * Across members:
+ *   d_cb           [n_callbacks][4] = {clip, si, first row, rows}
+ *   d_cb_db        [n_callbacks] the member whose label won the callback (the first whose segment maximum exceeds the running one, from 0);
+ *                  -1 = no member has a segment sum above 0 (the reference's label `null`, confidence 0); -2 = skipped, as d_cb_label
+ *   d_cb_top_label [n_callbacks] class index within that member's legend (-1 where d_cb_db < 0)
+ *   d_cb_top_conf  [n_callbacks] f64 max_conf_db_seg / seg_weight (ref prediction.js:168)
+ *   d_cb_min_db    [n_callbacks] min_entropy_db after that callback: updated only where a member's DB_entropies_all exceeds
+ *                  max_inv_entropy, which runs across the clip's callbacks (ref prediction.js:161-165); -1 while none has exceeded 0.
+ *                  Skipped callbacks leave it as it was.
+ *   d_cb_entropy   [n_callbacks] f64 1 - DB_entropies_all[min_db] / all_class_sum, the sum over Label_conf_all[min_db] in Object.keys
+ *                  order (ref prediction.js:182-184, 207); NaN while d_cb_min_db is -1
+ *   d_clip_min_db  [n_clips] the clip's last callback's d_cb_min_db (-1 for a clip without one)
+ * Level 5: n_callbacks = 0 and only d_prob is set.  Single-model and ensemble results of one batch are separate:
+ * wsa_batch_class_result after an ensemble call returns WSA_ERR_INVALID, and the other way round. */
+typedef struct {
+    uint32_t n_rows, n_members, n_callbacks, n_clips;
+    uint32_t n_classes[WSA_ENSEMBLE_MAX];
+    const float   *d_prob[WSA_ENSEMBLE_MAX];
+    const int32_t *d_cb_label[WSA_ENSEMBLE_MAX];
+    const double  *d_cb_conf[WSA_ENSEMBLE_MAX];
+    const double  *d_cb_all_max[WSA_ENSEMBLE_MAX];
+    const double  *d_clip_conf[WSA_ENSEMBLE_MAX];
+    const int32_t *d_cb; const int32_t *d_cb_db; const int32_t *d_cb_top_label; const double *d_cb_top_conf;
+    const int32_t *d_cb_min_db; const double *d_cb_entropy; const int32_t *d_clip_min_db;
+} wsa_ensemble_result;
+wsa_status wsa_batch_ensemble_result(wsa_batch *b, void *stream, wsa_ensemble_result *out);
+/* The same tables copied to host buffers (any pointer may be NULL to skip it): prob[d] [rows_cap][n_classes[d]], the per-callback
+ * tables [cb_cap] (cb [cb_cap][4]), clip_conf[d] [n_clips][n_classes[d]], clip_min_db [n_clips].  WSA_ERR_INVALID if a capacity
+ * is too small. */
+typedef struct {
+    uint32_t rows_cap, cb_cap;
+    float   *prob[WSA_ENSEMBLE_MAX];
+    int32_t *cb_label[WSA_ENSEMBLE_MAX];
+    double  *cb_conf[WSA_ENSEMBLE_MAX];
+    double  *cb_all_max[WSA_ENSEMBLE_MAX];
+    double  *clip_conf[WSA_ENSEMBLE_MAX];
+    int32_t *cb; int32_t *cb_db; int32_t *cb_top_label; double *cb_top_conf;
+    int32_t *cb_min_db; double *cb_entropy; int32_t *clip_min_db;
+} wsa_ensemble_host;
+wsa_status wsa_batch_copy_ensemble(wsa_batch *b, void *stream, const wsa_ensemble_host *dst);
+
+/*
  * ---- Classification inside the stream step (additions within version 5: probe for wsa_stream_set_model).
  * The app's live path (ref src/prediction.js:47: predict_by_multiple_syllables after every level-13 callback of a live source, the
  * per-launch Label_conf_all behind the meters) for every stream of a wsa_stream: K6 on each step's rows and, at level 13, the fold with
@@ -438,6 +514,27 @@ typedef struct {
 /* After wsa_stream_collect of the same step: host memory owned by the stream object, valid until the next step.
  * WSA_ERR_INVALID without an attached model. */
 wsa_status wsa_stream_classes(wsa_stream *st, wsa_stream_class_result *out);
+/* The same with an ensemble (additions within version 5: probe for wsa_ensemble_create): K6e on each step's rows and, at level 13, one
+ * accumulator per stream and member plus one running max_inv_entropy / min_entropy_db per stream (ref prediction.js:16-17), all carried
+ * on the device, reset by START, untouched on idle steps and kept after STOP.  Three kernels of the step; the step stays one graph
+ * launch.  Attach (e != NULL) or detach (NULL) as wsa_stream_set_model does; setting a model detaches an ensemble and vice versa. */
+wsa_status wsa_stream_set_ensemble(wsa_stream *st, const wsa_ensemble *e);
+typedef struct {
+    uint32_t n_rows, n_members, n_callbacks, n_streams;
+    uint32_t n_classes[WSA_ENSEMBLE_MAX];
+    const float   *prob[WSA_ENSEMBLE_MAX];         /* [n_rows][n_classes[d]] */
+    const int32_t *cb_label[WSA_ENSEMBLE_MAX];     /* the tables of wsa_ensemble_result for the step's callbacks (level 13; else NULL) */
+    const double  *cb_conf[WSA_ENSEMBLE_MAX];
+    const double  *cb_all_max[WSA_ENSEMBLE_MAX];
+    const double  *stream_conf[WSA_ENSEMBLE_MAX];  /* [n_streams][n_classes[d]] the member's Label_conf_all since each stream's START */
+    const int32_t *cb;                             /* [n_callbacks][4] = {stream, si, first row, rows} */
+    const int32_t *cb_db; const int32_t *cb_top_label; const double *cb_top_conf;
+    const int32_t *cb_min_db; const double *cb_entropy;
+    const int32_t *stream_min_db;                  /* [n_streams] min_entropy_db since each stream's START (-1: none yet) */
+} wsa_stream_ensemble_result;
+/* After wsa_stream_collect of the same step: host memory owned by the stream object, valid until the next step.
+ * WSA_ERR_INVALID without an attached ensemble. */
+wsa_status wsa_stream_ensemble_classes(wsa_stream *st, wsa_stream_ensemble_result *out);
 
 /*
  * ---- Streams of different rates, converted inside the step (additions within version 5: probe for wsa_stream_create_mixed).

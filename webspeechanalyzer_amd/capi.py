@@ -102,6 +102,31 @@ class _StreamClassResult(ctypes.Structure):
                 ("stream_conf", ctypes.c_void_p)]
 
 
+ENSEMBLE_MAX = 8           # WSA_ENSEMBLE_MAX
+_VP8, _U32x8 = ctypes.c_void_p * ENSEMBLE_MAX, ctypes.c_uint32 * ENSEMBLE_MAX
+
+
+class _EnsembleResult(ctypes.Structure):
+    _fields_ = [("n_rows", ctypes.c_uint32), ("n_members", ctypes.c_uint32), ("n_callbacks", ctypes.c_uint32), ("n_clips", ctypes.c_uint32),
+                ("n_classes", _U32x8), ("d_prob", _VP8), ("d_cb_label", _VP8), ("d_cb_conf", _VP8), ("d_cb_all_max", _VP8), ("d_clip_conf", _VP8),
+                ("d_cb", ctypes.c_void_p), ("d_cb_db", ctypes.c_void_p), ("d_cb_top_label", ctypes.c_void_p), ("d_cb_top_conf", ctypes.c_void_p),
+                ("d_cb_min_db", ctypes.c_void_p), ("d_cb_entropy", ctypes.c_void_p), ("d_clip_min_db", ctypes.c_void_p)]
+
+
+class _EnsembleHost(ctypes.Structure):
+    _fields_ = [("rows_cap", ctypes.c_uint32), ("cb_cap", ctypes.c_uint32),
+                ("prob", _VP8), ("cb_label", _VP8), ("cb_conf", _VP8), ("cb_all_max", _VP8), ("clip_conf", _VP8),
+                ("cb", ctypes.c_void_p), ("cb_db", ctypes.c_void_p), ("cb_top_label", ctypes.c_void_p), ("cb_top_conf", ctypes.c_void_p),
+                ("cb_min_db", ctypes.c_void_p), ("cb_entropy", ctypes.c_void_p), ("clip_min_db", ctypes.c_void_p)]
+
+
+class _StreamEnsembleResult(ctypes.Structure):
+    _fields_ = [("n_rows", ctypes.c_uint32), ("n_members", ctypes.c_uint32), ("n_callbacks", ctypes.c_uint32), ("n_streams", ctypes.c_uint32),
+                ("n_classes", _U32x8), ("prob", _VP8), ("cb_label", _VP8), ("cb_conf", _VP8), ("cb_all_max", _VP8), ("stream_conf", _VP8),
+                ("cb", ctypes.c_void_p), ("cb_db", ctypes.c_void_p), ("cb_top_label", ctypes.c_void_p), ("cb_top_conf", ctypes.c_void_p),
+                ("cb_min_db", ctypes.c_void_p), ("cb_entropy", ctypes.c_void_p), ("stream_min_db", ctypes.c_void_p)]
+
+
 # every symbol include/wsa.h declares (checked by tests/test_abi.py)
 ABI_VERSION = 5            # WSA_ABI_VERSION of include/wsa.h this binding's structures follow
 ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destroy", "wsa_last_error",
@@ -118,6 +143,9 @@ ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destr
                "wsa_model_create", "wsa_model_destroy", "wsa_classify_rows", "wsa_batch_classify", "wsa_batch_class_result", "wsa_batch_copy_classes",
                # additions within version 5 (probe for wsa_stream_set_model): the classifier inside the stream step
                "wsa_stream_set_model", "wsa_stream_classes",
+               # additions within version 5 (probe for wsa_ensemble_create): every model DB of the app in one pass
+               "wsa_ensemble_create", "wsa_ensemble_destroy", "wsa_batch_classify_ensemble", "wsa_batch_ensemble_result", "wsa_batch_copy_ensemble",
+               "wsa_stream_set_ensemble", "wsa_stream_ensemble_classes",
                # additions within version 5 (probe for wsa_stream_create_mixed): streams of different rates, converted inside the step
                "wsa_stream_create_mixed", "wsa_stream_input_capacity", "wsa_stream_input_stride", "wsa_stream_paced_input", "wsa_stream_step_frame_capacity",
                "wsa_stream_step_n", "wsa_stream_step_host_n", "wsa_resample_ready", "wsa_stream_frames_bound", "wsa_stream_copy_converted"]
@@ -213,6 +241,13 @@ def lib():
     L.wsa_batch_copy_classes.argtypes = [vp, vp, vp, u32, vp, vp, vp, u32, vp]
     L.wsa_stream_set_model.argtypes = [vp, vp]
     L.wsa_stream_classes.argtypes = [vp, ctypes.POINTER(_StreamClassResult)]
+    L.wsa_ensemble_create.argtypes = [vp, vp, u32, ctypes.POINTER(vp)]
+    L.wsa_ensemble_destroy.argtypes = [vp]
+    L.wsa_batch_classify_ensemble.argtypes = [vp, vp, vp]
+    L.wsa_batch_ensemble_result.argtypes = [vp, vp, ctypes.POINTER(_EnsembleResult)]
+    L.wsa_batch_copy_ensemble.argtypes = [vp, vp, ctypes.POINTER(_EnsembleHost)]
+    L.wsa_stream_set_ensemble.argtypes = [vp, vp]
+    L.wsa_stream_ensemble_classes.argtypes = [vp, ctypes.POINTER(_StreamEnsembleResult)]
     L.wsa_stream_create_mixed.argtypes = [vp, u32, vp, dbl, u32, u32, ctypes.POINTER(vp)]
     for name in ("wsa_stream_input_capacity", "wsa_stream_paced_input"):
         getattr(L, name).argtypes = [vp, u32]
@@ -231,7 +266,7 @@ def lib():
             continue
         if name not in ("wsa_abi_version", "wsa_last_error", "wsa_config_default", "wsa_destroy", "wsa_batch_destroy", "wsa_resample_length",
                         "wsa_stream_destroy", "wsa_stream_samples_per_step", "wsa_stream_host_input", "wsa_gather_destroy", "wsa_host_free",
-                        "wsa_model_destroy"):
+                        "wsa_model_destroy", "wsa_ensemble_destroy"):
             getattr(L, name).restype = ctypes.c_int
     _LIB = L
     return L
@@ -305,6 +340,10 @@ class Analyzer:
         else:
             spec = nnmodel.load_dir(src)
         return Model(self, spec)
+
+    def ensemble(self, models):
+        """The app's `available_DBs` on this context: a list of 1 .. 8 Models in that order (every tie between DBs goes to the earlier one)."""
+        return Ensemble(self, models)
 
     def close(self):
         if self.h:
@@ -525,6 +564,44 @@ class Batch:
                                                       max(k, 1), clip.ctypes.data if r.d_clip_conf else None))
         return dict(prob=prob, cb=cb, cb_label=lab, cb_conf=conf, clip_conf=clip, labels=list(self._model.labels))
 
+    def classify_ensemble(self, ensemble, stream=0):
+        """K6e (+ K6b-e and the cross-DB decision at level 13) on the rows of the last run, enqueued on `stream` (wsa_batch_classify_ensemble)."""
+        self.an._check(self.L.wsa_batch_classify_ensemble(self.h, ensemble.h, stream))
+        self._ensemble = ensemble
+
+    def ensemble_result(self, stream=0):
+        r = _EnsembleResult()
+        self.an._check(self.L.wsa_batch_ensemble_result(self.h, stream, ctypes.byref(r)))
+        return r
+
+    def ensemble_classes(self, stream=0):
+        """Host copies of the last ensemble classification.  Per member (lists of n_members arrays): prob [n_rows, C_d] f32, cb_label /
+        cb_conf / cb_all_max [n_cb], clip_conf [n_clips, C_d].  Across members: cb [n_cb, 4], cb_db (-1: null, -2: not predicted),
+        cb_top_label, cb_top_conf, cb_min_db, cb_entropy [n_cb], clip_min_db [n_clips]; labels = the members' legends.  Level 5: prob only."""
+        r = self.ensemble_result(stream)
+        nm, n, k, nc = int(r.n_members), int(r.n_rows), int(r.n_callbacks), int(r.n_clips)
+        fold = bool(r.d_cb)
+        C = [int(r.n_classes[d]) for d in range(nm)]
+        out = dict(prob=[np.zeros((n, c), np.float32) for c in C], labels=[list(m.labels) for m in self._ensemble.models])
+        h = _EnsembleHost()
+        h.rows_cap, h.cb_cap = max(n, 1), max(k, 1)
+        if fold:
+            for name, dt in (("cb_label", np.int32), ("cb_conf", np.float64), ("cb_all_max", np.float64)):
+                out[name] = [np.zeros(k, dt) for _ in C]
+            out["clip_conf"] = [np.zeros((nc, c), np.float64) for c in C]
+            out.update(cb=np.zeros((k, 4), np.int32), cb_db=np.zeros(k, np.int32), cb_top_label=np.zeros(k, np.int32), cb_top_conf=np.zeros(k),
+                       cb_min_db=np.zeros(k, np.int32), cb_entropy=np.zeros(k), clip_min_db=np.zeros(nc, np.int32))
+        for name, v in out.items():
+            if name == "labels":
+                continue
+            if isinstance(v, list):
+                for d in range(nm):
+                    getattr(h, name)[d] = v[d].ctypes.data
+            else:
+                setattr(h, name, v.ctypes.data)
+        self.an._check(self.L.wsa_batch_copy_ensemble(self.h, stream, ctypes.byref(h)))
+        return out
+
     def close(self):
         if self.h:
             self.L.wsa_batch_destroy(self.h)
@@ -566,6 +643,27 @@ class Model:
     def close(self):
         if self.h:
             self.L.wsa_model_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Ensemble:
+    """wsa_ensemble: the models of the app's `available_DBs`, in that order, classified and folded in one pass."""
+
+    def __init__(self, an, models):
+        self.an, self.L, self.models = an, an.L, list(models)
+        arr = (ctypes.c_void_p * max(len(self.models), 1))(*[m.h if m is not None else None for m in self.models])
+        self.h = ctypes.c_void_p()
+        an._check(self.L.wsa_ensemble_create(an.h, ctypes.cast(arr, ctypes.c_void_p), len(self.models), ctypes.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            self.L.wsa_ensemble_destroy(self.h)
             self.h = ctypes.c_void_p()
 
     def __del__(self):
@@ -734,6 +832,36 @@ class Streams:
         return dict(prob=arr(r.prob, ctypes.c_float, np.float32, (n, C)), cb=arr(r.cb, ctypes.c_int32, np.int32, (k, 4)),
                     cb_label=arr(r.cb_label, ctypes.c_int32, np.int32, (k,)), cb_conf=arr(r.cb_conf, ctypes.c_double, np.float64, (k,)),
                     stream_conf=arr(r.stream_conf, ctypes.c_double, np.float64, (int(r.n_streams), C)), labels=list(self._model.labels))
+
+    def set_ensemble(self, ensemble):
+        """Attach an Ensemble (K6e on every step's rows; at level 13 one accumulator per stream and member and one running min_entropy_db
+        per stream, reset by START) or detach (None).  Detaches a Model; the next step recaptures the graph."""
+        self.an._check(self.L.wsa_stream_set_ensemble(self.h, ensemble.h if ensemble is not None else None))
+        self._ensemble = ensemble
+
+    def ensemble_classes(self):
+        """After collect(): host copies of the step's ensemble classification, the tables of Batch.ensemble_classes with `stream` for `clip`
+        (stream_conf, stream_min_db).  Level 5: prob only."""
+        r = _StreamEnsembleResult()
+        self.an._check(self.L.wsa_stream_ensemble_classes(self.h, ctypes.byref(r)))
+        nm, n, k, ns = int(r.n_members), int(r.n_rows), int(r.n_callbacks), int(r.n_streams)
+        C = [int(r.n_classes[d]) for d in range(nm)]
+
+        def arr(ptr, ctype, dtype, shape):
+            if not int(np.prod(shape)):
+                return np.zeros(shape, dtype)
+            return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctype)), shape=shape).copy()
+        out = dict(prob=[arr(r.prob[d], ctypes.c_float, np.float32, (n, C[d])) for d in range(nm)], labels=[list(m.labels) for m in self._ensemble.models])
+        if not r.cb:
+            return out
+        i32, f64 = (ctypes.c_int32, np.int32), (ctypes.c_double, np.float64)
+        out.update(cb_label=[arr(r.cb_label[d], *i32, (k,)) for d in range(nm)], cb_conf=[arr(r.cb_conf[d], *f64, (k,)) for d in range(nm)],
+                   cb_all_max=[arr(r.cb_all_max[d], *f64, (k,)) for d in range(nm)],
+                   stream_conf=[arr(r.stream_conf[d], *f64, (ns, C[d])) for d in range(nm)],
+                   cb=arr(r.cb, *i32, (k, 4)), cb_db=arr(r.cb_db, *i32, (k,)), cb_top_label=arr(r.cb_top_label, *i32, (k,)),
+                   cb_top_conf=arr(r.cb_top_conf, *f64, (k,)), cb_min_db=arr(r.cb_min_db, *i32, (k,)), cb_entropy=arr(r.cb_entropy, *f64, (k,)),
+                   stream_min_db=arr(r.stream_min_db, *i32, (ns,)))
+        return out
 
     def collect(self, stream=0):
         """Rows of the last step: dict(meta [n,8] i32, feat [n,53] f64, segments [m,4] i32) (copies)."""

@@ -60,6 +60,8 @@ struct wsa_batch {
     uint32_t res_rows = 0, res_segs = 0, res_flags = 0;
     const uint32_t* spec_in_use = nullptr;
     wsa_cls* cls = nullptr;                 // wsa_batch_classify (classify.hip)
+    wsa_ecls* ecls = nullptr;               // wsa_batch_classify_ensemble (classify.hip)
+    int cls_last = 0;                       // which of the two the last classification was (1 / 2): their results stay apart
 };
 
 namespace wsa {
@@ -164,6 +166,7 @@ void wsa_batch_destroy(wsa_batch* b) {
     if (b->up_start) (void)hipEventDestroy(b->up_start);
     for (auto& e : b->ev) if (e) (void)hipEventDestroy(e);
     wsa_cls_free(b->cls);
+    wsa_ecls_free(b->ecls);
     delete b;                           // (the arena frees the rest)
 }
 
@@ -651,7 +654,7 @@ void wsa_queue_destroy(wsa_ctx* ctx, void* stream) {
 
 void wsa_batch_view_internal(wsa_batch* b, wsa_batch_view* v) {
     v->ctx = b->ctx; v->level = b->ctx->cfg.output_level; v->n_clips = b->n_clips; v->rows_cap = b->n_clips * (uint32_t)b->be.row_cap;
-    v->d_meta = b->be.d_meta; v->d_feat = b->be.d_feat; v->d_row_off = b->be.d_row_off; v->reruns = b->reruns; v->cls = &b->cls;
+    v->d_meta = b->be.d_meta; v->d_feat = b->be.d_feat; v->d_row_off = b->be.d_row_off; v->reruns = b->reruns; v->cls = &b->cls; v->ecls = &b->ecls; v->cls_last = &b->cls_last;
 }
 wsa_status wsa_batch_fetch_internal(wsa_batch* b, hipStream_t s) { return fetch_totals(b, s); }
 

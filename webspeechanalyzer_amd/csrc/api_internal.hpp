@@ -22,11 +22,14 @@ inline wsa_status fail(wsa_ctx* c, wsa_status st, const std::string& msg) {
 // classify.hip (K6 / K6b) reads a batch's compacted rows and keeps its own per-batch state; api.hip owns the batch object
 struct wsa_cls;                                 // classification buffers of one batch (allocated by the first wsa_batch_classify)
 void wsa_cls_free(wsa_cls* c);                  // (wsa_batch_destroy)
+struct wsa_ecls;                                // ensemble tables of one batch (allocated by the first wsa_batch_classify_ensemble with an ensemble)
+void wsa_ecls_free(wsa_ecls* c);
 struct wsa_batch_view {
     wsa_ctx* ctx; int level; uint32_t n_clips, rows_cap;
     const int32_t* d_meta; const double* d_feat; const uint32_t* d_row_off;     // compacted rows, d_row_off[n_clips] = rows on the device
     uint32_t reruns;                                                            // wsa_batch_backend_reruns
-    wsa_cls** cls;
+    wsa_cls** cls; wsa_ecls** ecls;
+    int* cls_last;                                                              // 1: the last classification was one model's, 2: an ensemble's
 };
 extern "C" {
 void wsa_batch_view_internal(wsa_batch* b, wsa_batch_view* v);
@@ -45,6 +48,12 @@ wsa_status wsa_scls_create(const wsa_scls_view& v, const wsa_model* m, wsa_scls*
 void wsa_scls_free(wsa_scls* c);
 wsa_status wsa_scls_enqueue(wsa_scls* c, hipStream_t s);                                   // part of enqueue_step (captured)
 wsa_status wsa_scls_result(wsa_scls* c, uint32_t rows, wsa_stream_class_result* out);    // after the step completed
+// ... or K6e and the ensemble's folds and decision (wsa_stream_set_ensemble)
+struct wsa_sens;
+wsa_status wsa_sens_create(const wsa_scls_view& v, const wsa_ensemble* e, wsa_sens** out);
+void wsa_sens_free(wsa_sens* c);
+wsa_status wsa_sens_enqueue(wsa_sens* c, hipStream_t s);
+wsa_status wsa_sens_result(wsa_sens* c, uint32_t rows, wsa_stream_ensemble_result* out);
 
 #define HIP_TRY(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
         return wsa_api::fail((ctx), WSA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)

@@ -192,9 +192,22 @@ const open_streams = new Set();
 // classifyMultiple returned for the segment's syllables (for ONE syllable: that syllable's sorted list itself).  Callbacks whose durations
 // sum to 0 get no on_prediction (the reference predicts nothing there).  The per-clip accumulator behind the app's meters (Label_conf_all,
 // reset per launch) is on the resolved result of LaunchBatch / LaunchBatches as `meters`.  With no model set nothing changes.
+//
+// setPredictionModels([handles], on_prediction) is the same with ALL of the app's model DBs (ref src/prediction.js:12 `available_DBs`, in that order;
+// K6e, include/wsa.h "Ensembles"): every level-13 launch classifies with all of them in one pass and calls
+//     on_prediction(si, [label, confidence], clip_index, detail)
+// where the first two arguments are what callback_after_pred receives with all DBs active (the label of the DB with the largest segment sum,
+// ref prediction.js:156-168) and detail = {db, per_db: [{label, confidence, per_syllable}], min_entropy_db, entropy, meters}: the index of the
+// winning DB (null with the label), every DB's own pair and classifyMultiple result, and what plot_prediction_meters draws after the
+// callback (ref prediction.js:172-215) — the DB whose accumulator is the most decided, `1 - max / sum` of its Label_conf_all, and each label's
+// share of that sum in Object.keys order.  The device reports no min_entropy_db for a launch in which no accumulator has exceeded 0; the
+// reference keeps the previous launch's DB there (it never resets the variable), so this module carries the last one across launches in dispatch
+// order, as the reference's one global does: min_entropy_db is null only before any launch had one; entropy is NaN and meters is {} while the
+// carried DB's accumulator of this launch is empty.  The resolved result's `meters` holds, per clip, the meters of the clip's own
+// min_entropy_db ({} for a clip without one), `min_entropy_db` the clips' DBs (null: none) and `shown_min_entropy_db` the carried one.  setPredictionModel and setPredictionModels replace each other.
 const ACT = { linear: 0, relu: 1, sigmoid: 2, tanh: 3, softmax: 4 };
 const loaded_models = new Set();
-let prediction = null;                  // {model, on_prediction}
+let prediction = null;                  // {model, on_prediction} | {models, on_prediction, state: {min_db}} (an ensemble; state: the carried min_entropy_db)
 function parse_model(mj, meta, weights) {
   const topo = mj.modelTopology, layers = topo && topo.config && (Array.isArray(topo.config) ? topo.config : topo.config.layers);
   if (!topo || topo.class_name !== 'Sequential' || !Array.isArray(layers)) throw 'loadModel: model.json is not a Sequential model';
@@ -249,6 +262,15 @@ function setPredictionModel(handle, on_prediction) {
   if (typeof on_prediction !== 'function') throw 'setPredictionModel(handle, on_prediction)';
   prediction = { model: handle, on_prediction };
 }
+function setPredictionModels(handles, on_prediction) {
+  if (handles === null || handles === undefined) { prediction = null; return; }
+  if (!Array.isArray(handles) || handles.length < 1 || handles.length > 8) throw 'setPredictionModels([handles], on_prediction): 1 .. 8 model handles';
+  for (const h of handles) if (!loaded_models.has(h) || h.released) throw 'setPredictionModels: a model handle was released (shutdown()) or is not one of loadModel';
+  if (typeof on_prediction !== 'function') throw 'setPredictionModels([handles], on_prediction)';
+  // the carried min_entropy_db is an index into the list: the same list keeps it (the reference's available_DBs never changes), another list starts anew
+  const same = prediction && prediction.models && prediction.models.length === handles.length && prediction.models.every((h, i) => h === handles[i]);
+  prediction = { models: handles.slice(), on_prediction, state: same ? prediction.state : { min_db: null } };
+}
 function release_models() {           // shutdown(): the native models go with their contexts; the handles are refused from here on
   for (const h of loaded_models) { h.released = true; h.natives.clear(); }
   loaded_models.clear();
@@ -256,12 +278,16 @@ function release_models() {           // shutdown(): the native models go with t
 }
 function model_on(nat, ctx) {         // the native model of the prediction model on one context (created at its first use there)
   if (!prediction || settings.output_level !== 13) return undefined;
-  const h = prediction.model;
-  if (h.released) throw 'the prediction model was released (shutdown())';
-  let m = h.natives.get(ctx);
-  if (!m) { m = nat.modelCreate(ctx, h.spec); h.natives.set(ctx, m); }
-  return m;
+  const one = (h) => {
+    if (h.released) throw 'the prediction model was released (shutdown())';
+    let m = h.natives.get(ctx);
+    if (!m) { m = nat.modelCreate(ctx, h.spec); h.natives.set(ctx, m); }
+    return m;
+  };
+  return prediction.models ? prediction.models.map(one) : one(prediction.model);      // (an array: the addon classifies with the ensemble of them)
 }
+function forget_natives(pred, ctx) { for (const h of pred.models || [pred.model]) h.natives.delete(ctx); }
+const has_cb = (res) => !!(res.cb || (res.ens && res.ens.cb));
 // per clip: Label_conf_all as {label: sum} in legend order (labels never added: 0)
 function meters_of(res, clip, labels) {
   const C = res.nClasses, o = {};
@@ -270,6 +296,7 @@ function meters_of(res, clip, labels) {
 }
 // the prediction of the level-13 callback whose first row is r (res.cb lists them in row order)
 function predict_after(res, r, si, clip, pred) {
+  if (pred.models) { predict_after_ensemble(res, r, si, clip, pred); return; }
   if (!res.cbIndex) { res.cbIndex = new Map(); for (let k = 0; k < res.cb.length / 4; k++) res.cbIndex.set(res.cb[k * 4 + 2], k); }
   const k = res.cbIndex.get(r);
   if (k === undefined || res.cbLabel[k] === -2) return;
@@ -282,6 +309,64 @@ function predict_after(res, r, si, clip, pred) {
   const per = n === 1 ? sorted(r) : Array.from({ length: n }, (_, q) => sorted(r + q));
   const lab = res.cbLabel[k] >= 0 ? labels[res.cbLabel[k]] : null;
   pred.on_prediction(si, [lab, res.cbConf[k]], clip, per);
+}
+
+// the share of each label in an accumulator's sum, keys and additions in Object.keys order (ref prediction.js:180-191)
+function shares_of(acc) {
+  const keys = Object.keys(acc), o = {};
+  let sum = 0;
+  for (const k of keys) sum += acc[k];
+  for (const k of keys) o[k] = acc[k] / sum;
+  return o;
+}
+// with an ensemble: res.ens holds the device's tables; the accumulators behind the meters are kept here per launch unit (clip / stream), by the
+// reference's own rule (ref prediction.js:91-115), so that the gauges exist after EVERY callback (the device hands out only each unit's last state)
+function predict_after_ensemble(res, r, si, unit, pred) {
+  const E = res.ens;
+  if (!E.cbIndex) { E.cbIndex = new Map(); for (let k = 0; k < E.cb.length / 4; k++) E.cbIndex.set(E.cb[k * 4 + 2], k); }
+  const k = E.cbIndex.get(r);
+  if (k === undefined || E.cbDb[k] === -2) return;
+  const n = E.cb[k * 4 + 3], step = settings.window_step / 1e3;
+  const accs_of = pred.accs || (res.ensAccs = res.ensAccs || new Map());
+  if (!accs_of.get(unit)) accs_of.set(unit, pred.models.map(() => ({})));
+  const accs = accs_of.get(unit);
+  const per_db = pred.models.map((h, d) => {
+    const labels = h.labels, C = E.nClasses[d], prob = E.prob[d];
+    const sorted = (q) => {
+      const e = [];
+      for (let c = 0; c < C; c++) e.push({ [labels[c]]: prob[q * C + c], label: labels[c], confidence: prob[q * C + c] });
+      return e.sort((a, b) => b.confidence - a.confidence);
+    };
+    const per = n === 1 ? sorted(r) : Array.from({ length: n }, (_, q) => sorted(r + q));
+    for (let q = 0; q < n; q++) {
+      const w = Math.sqrt(parseFloat(((res.meta[(r + q) * 8 + 3] + 1) * step).toFixed(3)));
+      for (const e of (n === 1 ? [per[0]] : per[q])) {
+        const wc = e.confidence * w;
+        if (!accs[d][e.label]) accs[d][e.label] = wc; else accs[d][e.label] += wc;
+      }
+    }
+    return { label: E.cbLabel[d][k] >= 0 ? labels[E.cbLabel[d][k]] : null, confidence: E.cbConf[d][k], per_syllable: per };
+  });
+  const db = E.cbDb[k];
+  if (E.cbMinDb[k] >= 0) pred.state.min_db = E.cbMinDb[k];
+  const m = pred.state.min_db;
+  const fresh = E.cbMinDb[k] >= 0;                       // else: a DB carried from an earlier launch, whose accumulator of this one has nothing above 0
+  const meters = m === null ? {} : shares_of(accs[m] || {});
+  const entropy = fresh ? E.cbEntropy[k] : NaN;
+  pred.on_prediction(si, [db >= 0 ? pred.models[db].labels[E.cbTopLabel[k]] : null, E.cbTopConf[k]], unit,
+    { db: db >= 0 ? db : null, per_db, min_entropy_db: m, entropy, meters });
+}
+// (a clip without a callback of its own says nothing: the carried DB stays)
+// the resolved result's meters of one clip / stream: those of its own min_entropy_db, from the accumulators kept while dispatching (else the
+// device's sums, added in legend order)
+function ensemble_meters_of(res, unit, pred, accs_of) {
+  const E = res.ens, m = E.minDb[unit];
+  if (m < 0) return {};
+  const kept = accs_of && accs_of.get(unit);
+  if (kept) return shares_of(kept[m]);
+  const C = E.nClasses[m], acc = {};
+  pred.models[m].labels.forEach((l, c) => { if (E.conf[m][unit * C + c] !== 0) acc[l] = E.conf[m][unit * C + c]; });
+  return shares_of(acc);
 }
 
 // rows of one clip -> the reference's callback sequence (ref dispatcher P() @B28869)
@@ -313,7 +398,7 @@ function dispatch(res, clip, callback, label, pred = null, clip_index = clip) {
       }
       if (feats.length > 0) {
         if (callback) callback(si, label, times, feats);                                      // ref @B29138 (`p[e].length>0`)
-        if (pred && res.cb && level === 13) predict_after(res, r - times.length, si, clip_index, pred);       // ref src/index.js:56 -> prediction.js:70
+        if (pred && has_cb(res) && level === 13) predict_after(res, r - times.length, si, clip_index, pred);       // ref src/index.js:56 -> prediction.js:70
       }
     }
   } else if (level === 11) {
@@ -449,7 +534,13 @@ async function run(clips, callback, labels_of, test_play) {
       for (let i = 0; i < shards.length && !stop_requested; i++)
         for (let c = shards[i][0]; c < shards[i][1] && !stop_requested; c++) dispatch(results[i], c - shards[i][0], callback, labels_of(c), pred, c);
     }
-    if (pred) results.meters = [].concat(...shards.map(([a, b], i) => Array.from({ length: b - a }, (_, c) => meters_of(results[i], c, pred.model.labels))));
+    if (pred && pred.models) {
+      // (dispatch numbers the clips of all shards 0 .. n - 1, a shard's tables its own from 0)
+      results.meters = [].concat(...shards.map(([a, b], i) => Array.from({ length: b - a }, (_, c) =>
+        ensemble_meters_of(results[i], c, pred, results[i].ensAccs && new Map([[c, results[i].ensAccs.get(a + c)]])))));
+      results.min_entropy_db = [].concat(...shards.map(([a, b], i) => Array.from(results[i].ens.minDb.subarray(0, b - a), (v) => (v >= 0 ? v : null))));
+      results.shown_min_entropy_db = pred.state.min_db;     // what the app's gauges still show: the last DB any launch had (the reference's global)
+    } else if (pred) results.meters = [].concat(...shards.map(([a, b], i) => Array.from({ length: b - a }, (_, c) => meters_of(results[i], c, pred.model.labels))));
     return results;
   } finally {
     playing = false;
@@ -484,7 +575,8 @@ function LaunchBatch(clips, callback = null, labels = [], test_play = false) {
     const cb = callback ? (si, label, t, f) => callback(si, label, t, f, current) : null;
     const labels_of = (c) => { current = c; return labels[c] || []; };
     run(list, cb, labels_of, test_play).then((rs) => resolve(Object.assign({ rows: rs.reduce((t, r) => t + r.meta.length / 8, 0), segments: rs.reduce((t, r) => t + r.segments.length / 4, 0),
-      stageMs: Array.from(rs[0].stageMs), shards: rs.length, stopped: stop_requested }, rs.meters ? { meters: rs.meters } : {})),
+      stageMs: Array.from(rs[0].stageMs), shards: rs.length, stopped: stop_requested }, rs.meters ? { meters: rs.meters } : {},
+      rs.min_entropy_db ? { min_entropy_db: rs.min_entropy_db, shown_min_entropy_db: rs.shown_min_entropy_db } : {})),
       (e) => reject(typeof e === 'string' ? e : String(e.message || e)));
   });
 }
@@ -519,6 +611,7 @@ async function run_batches(batches, callback, labels, test_play) {
     const pred = prediction && settings.output_level === 13 ? prediction : null;
     const models = ctxs.map((c) => (pred ? model_on(nat, c) : undefined));
     const meters = pred ? [] : null;
+    const mdbs = pred && pred.models ? [] : null;          // per batch and clip: the clip's min_entropy_db (null: none)
     const lists = batches.map((b) => b.map(to_pcm));
     const bands = settings.spec_type === 1 ? settings.N_mel_bins : settings.N_fft_bins;
     const start = (k) => {
@@ -550,14 +643,16 @@ async function run_batches(batches, callback, labels, test_play) {
         const lb = labels[k] || [];
         for (let c = 0; c < lists[k].length && !stop_requested; c++) {
           const cb = callback ? (si, label, t, f) => callback(si, label, t, f, c, k) : null;
-          const pk = pred ? { model: pred.model, on_prediction: (si, lc, ci, per) => pred.on_prediction(si, lc, ci, per, k) } : null;
+          const pk = pred ? { model: pred.model, models: pred.models, state: pred.state, on_prediction: (si, lc, ci, per) => pred.on_prediction(si, lc, ci, per, k) } : null;
           dispatch(res, c, cb, lb[c] || [], pk, c);
         }
       }
-      if (meters) meters.push(Array.from({ length: lists[k].length }, (_, c) => meters_of(res, c, pred.model.labels)));
+      if (meters) meters.push(Array.from({ length: lists[k].length }, (_, c) => (pred.models ? ensemble_meters_of(res, c, pred, res.ensAccs) : meters_of(res, c, pred.model.labels))));
+      if (mdbs) mdbs.push(Array.from(res.ens.minDb.subarray(0, lists[k].length), (v) => (v >= 0 ? v : null)));
       if (stop_requested && next) { try { await next; } catch (e) { /* stopping */ } next = null; done++; break; }
     }
-    return Object.assign({ rows, segments, batches: done, stopped: stop_requested }, meters ? { meters } : {});
+    return Object.assign({ rows, segments, batches: done, stopped: stop_requested }, meters ? { meters } : {},
+      mdbs ? { min_entropy_db: mdbs, shown_min_entropy_db: pred.state.min_db } : {});
   } finally {
     playing = false;
   }
@@ -607,14 +702,16 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
     if (g.bands !== bands) throw 'Bins count mismatch: ' + g.bands + ', ' + bands;              // ref @B8568 check
     st = convert ? nat.streamOpenMixed(ctx, n_streams, Float64Array.from(per_stream ? rates : new Array(n_streams).fill(rates[0])), fs_an, frames_per_step, max_span_frames)
       : nat.streamOpen(ctx, n_streams, rates[0], frames_per_step, max_span_frames);
-    if (pred) nat.streamSetModel(st, model_on(nat, ctx));       // the native model on the stream's own context (ref src/index.js:56)
+    if (pred && pred.models) nat.streamSetEnsemble(st, model_on(nat, ctx));
+    else if (pred) nat.streamSetModel(st, model_on(nat, ctx));       // the native model on the stream's own context (ref src/index.js:56)
   } catch (e) {
     if (st) nat.streamClose(st);
-    if (pred) pred.model.natives.delete(ctx);
+    if (pred) forget_natives(pred, ctx);
     nat.destroy(ctx); throw (typeof e === 'string' ? e : String(e.message || e));
   }
   const input = nat.streamInput(st);
   const info = convert ? nat.streamInfo(st) : null;
+  const spred = pred && pred.models ? { models: pred.models, state: pred.state, on_prediction: pred.on_prediction, accs: new Map() } : pred;   // accs: per stream, since its START
   let open = true, started = false, meters = null;      // meters: the per-stream Label_conf_all of the last step (a prediction model only)
   const stopped = new Uint8Array(n_streams);          // streams that have had their segment_truncate since their last START
   const seg_seen = new Uint32Array(n_streams);        // level 3: segments a stream has closed since its last START (the callback index, ref @B28273)
@@ -662,13 +759,17 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
           }
           if (feats.length > 0) {
             if (callback) callback(si, labels[s] || [], times, feats, s);                                                      // ref @B29138 (`p[e].length>0`)
-            if (pred && res.cb && level === 13) predict_after(res, r - times.length, si, s, pred);                              // ref prediction.js:70
+            if (pred && has_cb(res) && level === 13) predict_after(res, r - times.length, si, s, spred);                              // ref prediction.js:70
           }
         }
       }
     }
     const out = { rows, segments: res.segments.length / 4, cuts: res.cuts, cut: (res.flags & 8) !== 0 };   // cut: some stream's span reached max_span_frames in this step (WSA_FLAG_STREAM_CUT)
-    if (pred && res.streamConf) meters = out.meters = Array.from({ length: n_streams }, (_, s) => meters_of({ nClasses: res.nClasses, clipConf: res.streamConf }, s, pred.model.labels));
+    if (pred && pred.models && res.ens && res.ens.cb) {
+      meters = out.meters = Array.from({ length: n_streams }, (_, s) => ensemble_meters_of(res, s, pred, spred.accs));
+      out.min_entropy_db = Array.from(res.ens.minDb, (v) => (v >= 0 ? v : null));
+      out.shown_min_entropy_db = pred.state.min_db;
+    } else if (pred && res.streamConf) meters = out.meters = Array.from({ length: n_streams }, (_, s) => meters_of({ nClasses: res.nClasses, clipConf: res.streamConf }, s, pred.model.labels));
     return out;
   };
   const handle = {
@@ -681,7 +782,7 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
       for (let i = 0; i < n_streams; i++) {
         c[i] = ctl ? ctl[i] : (STREAM_ACTIVE | (started ? 0 : STREAM_START));
         if (handle.stopPending && !stopped[i]) c[i] |= STREAM_STOP;
-        if (c[i] & STREAM_START) { stopped[i] = 0; seg_seen[i] = 0; }
+        if (c[i] & STREAM_START) { stopped[i] = 0; seg_seen[i] = 0; if (spred && spred.accs) spred.accs.delete(i); }
         if (c[i] & STREAM_STOP) stopped[i] = 1;
       }
       started = true;
@@ -701,7 +802,7 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
       }
       open = false; open_streams.delete(handle);
       nat.streamClose(st);                             // detaches `input`: the pinned buffer is gone; releases the model
-      if (pred) pred.model.natives.delete(ctx);        // the native model goes with the stream's context
+      if (pred) forget_natives(pred, ctx);              // the native models go with the stream's context
       nat.destroy(ctx);
       return out;
     },
@@ -726,4 +827,4 @@ function set_predicted_label_for_segment(si, idx, label) {                      
 
 module.exports = { configure, LaunchAudioNodes, StopAudioNodes, set_predicted_label_for_segment, LaunchBatch, LaunchBatches,
   StreamOpen, STREAM_ACTIVE, STREAM_START, STREAM_STOP, shutdown, allocPinned, freePinned,
-  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, loadModel, setPredictionModel };
+  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, loadModel, setPredictionModel, setPredictionModels };

@@ -20,6 +20,8 @@
  *   streamInput(stream) -> Float32Array over the pinned [nStreams][inputStride] input buffer (no copy; inputStride = samplesPerStep on a plain set)
  *   streamStep(stream, ctl: Uint8Array | null[, counts: Uint32Array | null]) -> {meta, feat, segments}   (wsa_stream_step_host[_n] + wsa_stream_collect;
  *       one hipGraph launch, well under a millisecond, so it runs on the calling thread; counts: samples per stream in this step, else paced)
+ *   processBatch(..., [models])                 (8th argument an array of models: wsa_batch_classify_ensemble; the result gains `ens`)
+ *   streamSetEnsemble(stream, [models] | null)  (wsa_stream_set_ensemble: streamStep results gain `ens`)
  *   streamSetModel(stream, model | null)        (wsa_stream_set_model: streamStep results gain prob, cb, cbLabel, cbConf, streamConf, nClasses)
  *   streamClose(stream)
  * Rejections carry the library's error string.  No compute happens in this file.
@@ -100,6 +102,9 @@ typedef struct {
      * contexts on one device overlap — the upload of one batch under the kernels of the other — instead of queueing on the device's null stream */
     void *queue;
     struct model_box *models;     /* the classifier models created on this context (modelCreate): destroy() destroys them with it */
+    /* the ensemble of the last processBatch call that had one (wsa_ensemble_create over ens_models): a call with the same list reuses it, so the
+     * kept plan keeps its ensemble tables too; made and replaced by the job (one job at a time uses a context), dropped by destroy() */
+    wsa_ensemble *ens; struct model_box *ens_models[WSA_ENSEMBLE_MAX]; uint32_t ens_n;
 } ctx_box;
 /* What JS holds for a model (wsa_model): like the context's box it outlives the model, so that a handle used after modelDestroy() or after its
  * context's destroy() finds NULL; `busy` counts the jobs that classify with it (modelDestroy() refuses meanwhile) */
@@ -107,6 +112,10 @@ typedef struct model_box { wsa_model *m; ctx_box *owner; uint32_t busy, n_classe
 static void model_unlink(model_box *mb) {
     if (mb->owner) for (model_box **q = &mb->owner->models; *q; q = &(*q)->next) if (*q == mb) { *q = mb->next; break; }
     mb->owner = NULL; mb->next = NULL;
+}
+static void box_drop_ensemble(ctx_box *b) {
+    if (b->ens) wsa_ensemble_destroy(b->ens);
+    b->ens = NULL; b->ens_n = 0;
 }
 static void box_drop_plan(ctx_box *b) {
     if (b->plan) wsa_batch_destroy(b->plan);
@@ -156,6 +165,7 @@ static napi_value fn_destroy(napi_env env, napi_callback_info info) {
         for (uint32_t i = 0; i < g_gather_n; i++) if (g_gather_ctxs[i] == b->ctx) { gather_drop(); break; }      /* the communicator goes before its contexts */
         pthread_mutex_unlock(&g_gather_lock);
         box_drop_plan(b);
+        box_drop_ensemble(b);                /* (before its models) */
         while (b->models) { model_box *mb = b->models; wsa_model_destroy(mb->m); mb->m = NULL; model_unlink(mb); }     /* models go before their context */
         if (b->queue) { wsa_queue_destroy(b->ctx, b->queue); b->queue = NULL; }
         wsa_destroy(b->ctx); b->ctx = NULL;
@@ -253,7 +263,51 @@ typedef struct {
     void *queue;                  /* the context's stream (ctx_box.queue) */
     model_box *model;             /* classify the rows with it (levels 5 / 13), or NULL */
     uint32_t n_classes, n_cb; float *prob; int32_t *cb, *cb_label; double *cb_conf, *clip_conf;
+    /* ... or with an ensemble of n_ens models (wsa_batch_classify_ensemble): the tables of wsa_batch_copy_ensemble */
+    model_box *ens_models[WSA_ENSEMBLE_MAX]; uint32_t n_ens; int ens_done; uint32_t ens_classes[WSA_ENSEMBLE_MAX]; wsa_ensemble_host eh;
 } job_t;
+
+/* the ensemble tables as a JS object: {nMembers, nClasses, prob[], cbLabel[], cbConf[], cbAllMax[], conf[] (Label_conf_all per clip / stream),
+ * cb, cbDb, cbTopLabel, cbTopConf, cbMinDb, cbEntropy, minDb (per clip / stream)}; fold = 0 (level 5): nMembers, nClasses and prob only */
+typedef struct {
+    uint32_t n, n_rows, n_cb, n_units; const uint32_t *n_classes; int fold;
+    const float *const *prob; const int32_t *const *cb_label; const double *const *cb_conf; const double *const *cb_all_max; const double *const *conf;
+    const int32_t *cb, *cb_db, *cb_top_label, *cb_min_db, *min_db; const double *cb_top_conf, *cb_entropy;
+} ens_view;
+static napi_value make_typed(napi_env env, napi_typedarray_type type, const void *src, size_t count, size_t elt);
+static napi_value ens_object(napi_env env, const ens_view *v) {
+    napi_value o, nm, a_prob, a_lab, a_conf, a_max, a_acc;
+    napi_create_object(env, &o);
+    napi_create_uint32(env, v->n, &nm); napi_set_named_property(env, o, "nMembers", nm);
+    napi_set_named_property(env, o, "nClasses", make_typed(env, napi_uint32_array, v->n_classes, v->n, 4));
+    napi_create_array_with_length(env, v->n, &a_prob); napi_create_array_with_length(env, v->n, &a_lab); napi_create_array_with_length(env, v->n, &a_conf);
+    napi_create_array_with_length(env, v->n, &a_max); napi_create_array_with_length(env, v->n, &a_acc);
+    for (uint32_t d = 0; d < v->n; d++) {
+        napi_set_element(env, a_prob, d, make_typed(env, napi_float32_array, v->prob[d], (size_t)v->n_rows * v->n_classes[d], 4));
+        if (!v->fold) continue;
+        napi_set_element(env, a_lab, d, make_typed(env, napi_int32_array, v->cb_label[d], v->n_cb, 4));
+        napi_set_element(env, a_conf, d, make_typed(env, napi_float64_array, v->cb_conf[d], v->n_cb, 8));
+        napi_set_element(env, a_max, d, make_typed(env, napi_float64_array, v->cb_all_max[d], v->n_cb, 8));
+        napi_set_element(env, a_acc, d, make_typed(env, napi_float64_array, v->conf[d], (size_t)v->n_units * v->n_classes[d], 8));
+    }
+    napi_set_named_property(env, o, "prob", a_prob);
+    if (!v->fold) return o;
+    napi_set_named_property(env, o, "cbLabel", a_lab); napi_set_named_property(env, o, "cbConf", a_conf);
+    napi_set_named_property(env, o, "cbAllMax", a_max); napi_set_named_property(env, o, "conf", a_acc);
+    napi_set_named_property(env, o, "cb", make_typed(env, napi_int32_array, v->cb, (size_t)v->n_cb * 4, 4));
+    napi_set_named_property(env, o, "cbDb", make_typed(env, napi_int32_array, v->cb_db, v->n_cb, 4));
+    napi_set_named_property(env, o, "cbTopLabel", make_typed(env, napi_int32_array, v->cb_top_label, v->n_cb, 4));
+    napi_set_named_property(env, o, "cbTopConf", make_typed(env, napi_float64_array, v->cb_top_conf, v->n_cb, 8));
+    napi_set_named_property(env, o, "cbMinDb", make_typed(env, napi_int32_array, v->cb_min_db, v->n_cb, 4));
+    napi_set_named_property(env, o, "cbEntropy", make_typed(env, napi_float64_array, v->cb_entropy, v->n_cb, 8));
+    napi_set_named_property(env, o, "minDb", make_typed(env, napi_int32_array, v->min_db, v->n_units, 4));
+    return o;
+}
+static void ens_host_free(wsa_ensemble_host *h) {
+    for (int d = 0; d < WSA_ENSEMBLE_MAX; d++) { free(h->prob[d]); free(h->cb_label[d]); free(h->cb_conf[d]); free(h->cb_all_max[d]); free(h->clip_conf[d]); }
+    free(h->cb); free(h->cb_db); free(h->cb_top_label); free(h->cb_top_conf); free(h->cb_min_db); free(h->cb_entropy); free(h->clip_min_db);
+    memset(h, 0, sizeof *h);
+}
 
 static void job_execute(napi_env env, void *data) {
     job_t *j = (job_t *)data;
@@ -333,6 +387,42 @@ static void job_execute(napi_env env, void *data) {
             j->st = wsa_batch_copy_classes(b, j->queue, j->prob, cr.n_rows ? cr.n_rows : 1, j->cb, j->cb_label, j->cb_conf, cr.n_callbacks ? cr.n_callbacks : 1, j->clip_conf);
             if (j->st != WSA_OK) break;
         }
+        if (j->n_ens) {                                       /* K6e (+ K6b-e and the decision at level 13): every model DB of the app at once */
+            ctx_box *bx = j->box;
+            int same = bx->ens && bx->ens_n == j->n_ens;
+            for (uint32_t d = 0; same && d < j->n_ens; d++) same = bx->ens_models[d] == j->ens_models[d];
+            if (!same) {
+                const wsa_model *ms[WSA_ENSEMBLE_MAX];
+                for (uint32_t d = 0; d < j->n_ens; d++) ms[d] = j->ens_models[d]->m;
+                box_drop_ensemble(bx);
+                j->st = wsa_ensemble_create(j->ctx, ms, j->n_ens, &bx->ens);
+                if (j->st != WSA_OK) break;
+                bx->ens_n = j->n_ens; memcpy(bx->ens_models, j->ens_models, sizeof bx->ens_models);
+            }
+            j->st = wsa_batch_classify_ensemble(b, bx->ens, j->queue);
+            if (j->st != WSA_OK) break;
+            wsa_ensemble_result er;
+            j->st = wsa_batch_ensemble_result(b, j->queue, &er);
+            if (j->st != WSA_OK) break;
+            const size_t R = er.n_rows ? er.n_rows : 1, K = er.n_callbacks ? er.n_callbacks : 1, NC = j->n_clips ? j->n_clips : 1;
+            const int fold = er.d_cb != NULL;
+            wsa_ensemble_host *h = &j->eh;
+            int ok = 1;
+            h->rows_cap = (uint32_t)R; h->cb_cap = (uint32_t)K; j->n_cb = er.n_callbacks;
+            for (uint32_t d = 0; d < j->n_ens; d++) {
+                j->ens_classes[d] = er.n_classes[d];
+                ok = ok && (h->prob[d] = malloc(sizeof(float) * R * er.n_classes[d]));
+                if (fold) ok = ok && (h->cb_label[d] = malloc(sizeof(int32_t) * K)) && (h->cb_conf[d] = malloc(sizeof(double) * K))
+                               && (h->cb_all_max[d] = malloc(sizeof(double) * K)) && (h->clip_conf[d] = calloc(NC * er.n_classes[d], sizeof(double)));
+            }
+            if (fold) ok = ok && (h->cb = malloc(sizeof(int32_t) * 4 * K)) && (h->cb_db = malloc(sizeof(int32_t) * K)) && (h->cb_top_label = malloc(sizeof(int32_t) * K))
+                           && (h->cb_top_conf = malloc(sizeof(double) * K)) && (h->cb_min_db = malloc(sizeof(int32_t) * K)) && (h->cb_entropy = malloc(sizeof(double) * K))
+                           && (h->clip_min_db = malloc(sizeof(int32_t) * NC));
+            if (!ok) { j->st = WSA_ERR_INVALID; snprintf(j->err, sizeof j->err, "out of memory"); return; }
+            j->st = wsa_batch_copy_ensemble(b, j->queue, h);
+            if (j->st != WSA_OK) break;
+            j->ens_done = fold ? 2 : 1;
+        }
         wsa_batch_stage_ms(b, j->stage_ms);
     } while (0);
     if (j->st != WSA_OK) snprintf(j->err, sizeof j->err, "%s", wsa_last_error(j->ctx));
@@ -351,6 +441,7 @@ static void job_complete(napi_env env, napi_status status, void *data) {
     job_t *j = (job_t *)data;
     if (j->box && j->box->children) j->box->children--;
     if (j->model && j->model->busy) j->model->busy--;
+    for (uint32_t d = 0; d < j->n_ens; d++) if (j->ens_models[d]->busy) j->ens_models[d]->busy--;
     if (j->plan) {                       /* keep the plan for the next call of the same shape (one entry; a failed run drops it) */
         if (j->box && j->box->ctx && j->st == WSA_OK && !j->box->plan) {
             j->box->plan = j->plan; j->box->plan_n = j->n_clips; j->box->plan_fs = j->fs; j->box->plan_fs_out = j->fs_out;
@@ -401,9 +492,17 @@ static void job_complete(napi_env env, napi_status status, void *data) {
             napi_set_named_property(env, o, "cbConf", make_typed(env, napi_float64_array, j->cb_conf, (size_t)j->n_cb, 8));
             napi_set_named_property(env, o, "clipConf", make_typed(env, napi_float64_array, j->clip_conf, (size_t)j->n_clips * j->n_classes, 8));
         }
+        if (j->ens_done) {                /* the ensemble's tables (include/wsa.h wsa_batch_copy_ensemble) */
+            const wsa_ensemble_host *h = &j->eh;
+            const ens_view v = {j->n_ens, j->n_rows, j->n_cb, j->n_clips, j->ens_classes, j->ens_done == 2,
+                                (const float *const *)h->prob, (const int32_t *const *)h->cb_label, (const double *const *)h->cb_conf, (const double *const *)h->cb_all_max,
+                                (const double *const *)h->clip_conf, h->cb, h->cb_db, h->cb_top_label, h->cb_min_db, h->clip_min_db, h->cb_top_conf, h->cb_entropy};
+            napi_set_named_property(env, o, "ens", ens_object(env, &v));
+        }
         napi_resolve_deferred(env, j->deferred, o);
     }
     napi_delete_async_work(env, j->work);
+    ens_host_free(&j->eh);
     free(j->prob); free(j->cb); free(j->cb_label); free(j->cb_conf); free(j->clip_conf);
     free(j->meta); free(j->feat); free(j->segs); free(j->row_off); free(j->seg_off); free(j->formants); free(j->frame_off); free(j->utt_meta); free(j->utt_feat); free(j->utt_off); free(j->trk_off); free(j->trk_pts); free(j->trk_rank);
     free(j->n_samples); free(j->fs_each); free((void *)j->pcm); free(j->clip_refs); free(j->channels); free(j);
@@ -414,8 +513,23 @@ static napi_value fn_process_batch(napi_env env, napi_callback_info info) {
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     wsa_ctx *ctx = argc ? get_ctx(env, argv[0]) : NULL;
     bool is_arr = false; double fs = 0; uint32_t n = 0;
-    model_box *mb = NULL;                                        /* 8th argument: a model of modelCreate on this context (classify the rows), or undefined / null */
-    if (argc >= 8) {
+    model_box *mb = NULL;                                        /* 8th argument: a model of modelCreate on this context (classify the rows), an array of 1 .. 8 of them (an ensemble), or undefined / null */
+    model_box *ens_models[WSA_ENSEMBLE_MAX] = {0}; uint32_t n_ens = 0;
+    bool ens_arr = false;
+    if (argc >= 8 && napi_is_array(env, argv[7], &ens_arr) == napi_ok && ens_arr) {
+        uint32_t len = 0;
+        napi_get_array_length(env, argv[7], &len);
+        if (len < 1 || len > WSA_ENSEMBLE_MAX) { napi_throw_error(env, NULL, "processBatch: an ensemble has 1 .. 8 models"); return NULL; }
+        for (uint32_t d = 0; d < len; d++) {
+            napi_value el; napi_valuetype t = napi_undefined; void *p = NULL;
+            if (napi_get_element(env, argv[7], d, &el) != napi_ok || napi_typeof(env, el, &t) != napi_ok || t != napi_external || napi_get_value_external(env, el, &p) != napi_ok || !p || !((model_box *)p)->m) {
+                napi_throw_error(env, NULL, "processBatch: a model handle of the ensemble was destroyed (or is not a model)"); return NULL;
+            }
+            if (!ctx || ((model_box *)p)->owner != get_box(env, argv[0])) { napi_throw_error(env, NULL, "processBatch: a model of the ensemble belongs to another context"); return NULL; }
+            ens_models[d] = (model_box *)p;
+        }
+        n_ens = len;
+    } else if (argc >= 8) {
         napi_valuetype t; napi_typeof(env, argv[7], &t);
         if (t != napi_undefined && t != napi_null) {
             void *p = NULL;
@@ -439,6 +553,7 @@ static napi_value fn_process_batch(napi_env env, napi_callback_info info) {
     if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
     if (argc >= 7) { bool d = false; if (napi_get_value_bool(env, argv[6], &d) == napi_ok) j->defer_rows = d ? 1 : 0; }
     j->ctx = ctx; j->fs = fs; j->n_clips = n; j->box = get_box(env, argv[0]); j->model = mb;
+    j->n_ens = n_ens; memcpy(j->ens_models, ens_models, sizeof j->ens_models);
     if (fs_each) { j->fs_each = malloc(sizeof(double) * (n ? n : 1)); if (!j->fs_each) { free(j); napi_throw_error(env, NULL, "out of memory"); return NULL; } memcpy(j->fs_each, fs_each, sizeof(double) * n); }
     if (argc >= 4) { int32_t lv = 0; if (napi_get_value_int32(env, argv[3], &lv) == napi_ok) j->level = lv; }
     if (argc >= 5) { double fo = 0; if (napi_get_value_double(env, argv[4], &fo) == napi_ok) j->fs_out = fo; }           /* analysis rate */   /* the ctx's output_level: 3 adds the raw tracks */
@@ -482,6 +597,7 @@ static napi_value fn_process_batch(napi_env env, napi_callback_info info) {
     NAPI_OK(env, napi_queue_async_work(env, j->work));
     j->box->children++;                                          /* until job_complete */
     if (mb) mb->busy++;
+    for (uint32_t d = 0; d < n_ens; d++) ens_models[d]->busy++;
     return promise;
 }
 
@@ -569,7 +685,7 @@ static napi_value fn_gather_rows(napi_env env, napi_callback_info info) {
 }
 
 /* ---- streams ---- */
-typedef struct { wsa_stream *st; wsa_ctx *ctx; ctx_box *box; uint32_t n, sps; napi_ref input_ref; model_box *model; } stream_t;   /* input_ref: the ArrayBuffer over the pinned input, detached at close; model: attached classifier (holds its busy count) */
+typedef struct { wsa_stream *st; wsa_ctx *ctx; ctx_box *box; uint32_t n, sps; napi_ref input_ref; model_box *model; wsa_ensemble *ens; model_box *ens_models[WSA_ENSEMBLE_MAX]; uint32_t n_ens; } stream_t;   /* input_ref: the ArrayBuffer over the pinned input, detached at close; model: attached classifier (holds its busy count) */
 static void stream_finalize(napi_env env, void *data, void *hint) { /* explicit streamClose() only */ }
 static stream_t *get_stream(napi_env env, napi_value v) {
     void *p = NULL; if (napi_get_value_external(env, v, &p) != napi_ok) return NULL; return (stream_t *)p;
@@ -720,7 +836,19 @@ static napi_value fn_stream_step(napi_env env, napi_callback_info info) {
         }
         napi_value nc; napi_create_uint32(env, c.n_classes, &nc); napi_set_named_property(env, o, "nClasses", nc);
     }
+    if (h->ens) {                                   /* the attached ensemble's tables of this step (conf / minDb: per stream, carried) */
+        wsa_stream_ensemble_result c;
+        if (wsa_stream_ensemble_classes(h->st, &c) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(h->ctx)); return NULL; }
+        const ens_view v = {c.n_members, c.n_rows, c.n_callbacks, c.n_streams, c.n_classes, c.cb != NULL, c.prob, c.cb_label, c.cb_conf, c.cb_all_max, c.stream_conf,
+                            c.cb, c.cb_db, c.cb_top_label, c.cb_min_db, c.stream_min_db, c.cb_top_conf, c.cb_entropy};
+        napi_set_named_property(env, o, "ens", ens_object(env, &v));
+    }
     return o;
+}
+static void stream_drop_ensemble(stream_t *h) {     /* after the stream object stopped using it */
+    if (h->ens) wsa_ensemble_destroy(h->ens);
+    for (uint32_t d = 0; d < h->n_ens; d++) if (h->ens_models[d]->busy) h->ens_models[d]->busy--;
+    h->ens = NULL; h->n_ens = 0;
 }
 static napi_value fn_stream_close(napi_env env, napi_callback_info info) {
     size_t argc = 1; napi_value argv[1];
@@ -734,6 +862,7 @@ static napi_value fn_stream_close(napi_env env, napi_callback_info info) {
         }
         wsa_stream_destroy(h->st); h->st = NULL;
         if (h->model) { if (h->model->busy) h->model->busy--; h->model = NULL; }
+        stream_drop_ensemble(h);
         if (h->box && h->box->children) h->box->children--;
     }
     return NULL;
@@ -755,7 +884,41 @@ static napi_value fn_stream_set_model(napi_env env, napi_callback_info info) {
     if (wsa_stream_set_model(h->st, mb ? mb->m : NULL) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(h->ctx)); return NULL; }
     if (h->model && h->model->busy) h->model->busy--;          /* modelDestroy() refuses while a stream holds the model */
     h->model = mb;
-    if (mb) mb->busy++;
+    if (mb) { mb->busy++; stream_drop_ensemble(h); }            /* (the library detached the ensemble) */
+    return NULL;
+}
+/* streamSetEnsemble(stream, [models] | null): the stream object owns the wsa_ensemble it makes of them, until it is replaced, detached or closed */
+static napi_value fn_stream_set_ensemble(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    stream_t *h = argc ? get_stream(env, argv[0]) : NULL;
+    if (!h || !h->st || argc < 2) { napi_throw_type_error(env, NULL, "streamSetEnsemble(stream, [models] | null)"); return NULL; }
+    model_box *mbs[WSA_ENSEMBLE_MAX] = {0}; const wsa_model *ms[WSA_ENSEMBLE_MAX]; uint32_t n = 0;
+    bool arr = false;
+    napi_valuetype t;
+    NAPI_OK(env, napi_typeof(env, argv[1], &t));
+    if (t != napi_null && t != napi_undefined) {
+        if (napi_is_array(env, argv[1], &arr) != napi_ok || !arr || napi_get_array_length(env, argv[1], &n) != napi_ok || n < 1 || n > WSA_ENSEMBLE_MAX) {
+            napi_throw_error(env, NULL, "streamSetEnsemble: an ensemble has 1 .. 8 models"); return NULL;
+        }
+        for (uint32_t d = 0; d < n; d++) {
+            napi_value el; napi_valuetype et = napi_undefined; void *p = NULL;
+            if (napi_get_element(env, argv[1], d, &el) != napi_ok || napi_typeof(env, el, &et) != napi_ok || et != napi_external || napi_get_value_external(env, el, &p) != napi_ok || !p || !((model_box *)p)->m) {
+                napi_throw_error(env, NULL, "streamSetEnsemble: a model handle was destroyed (or is not a model)"); return NULL;
+            }
+            mbs[d] = (model_box *)p; ms[d] = mbs[d]->m;
+            if (mbs[d]->owner != h->box) { napi_throw_error(env, NULL, "streamSetEnsemble: a model belongs to another context"); return NULL; }
+        }
+    }
+    wsa_ensemble *e = NULL;
+    if (n && wsa_ensemble_create(h->ctx, ms, n, &e) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(h->ctx)); return NULL; }
+    if (wsa_stream_set_ensemble(h->st, e) != WSA_OK) { if (e) wsa_ensemble_destroy(e); napi_throw_error(env, NULL, wsa_last_error(h->ctx)); return NULL; }
+    stream_drop_ensemble(h);
+    if (e) {
+        h->ens = e; h->n_ens = n; memcpy(h->ens_models, mbs, sizeof h->ens_models);
+        for (uint32_t d = 0; d < n; d++) mbs[d]->busy++;
+        if (h->model) { if (h->model->busy) h->model->busy--; h->model = NULL; }     /* (the library detached the model) */
+    }
     return NULL;
 }
 
@@ -825,6 +988,12 @@ static napi_value fn_model_destroy(napi_env env, napi_callback_info info) {
     if (argc < 1 || napi_get_value_external(env, argv[0], &p) != napi_ok || !p) { napi_throw_type_error(env, NULL, "modelDestroy(model)"); return NULL; }
     model_box *mb = (model_box *)p;
     if (mb->busy) { napi_throw_error(env, NULL, "the model is in use by a batch in flight or an open stream"); return NULL; }
+    if (mb->owner && mb->owner->ens) {          /* the context's kept ensemble may hold it: no job is in flight with it (busy is 0), so it goes first */
+        for (uint32_t d = 0; d < mb->owner->ens_n; d++) if (mb->owner->ens_models[d] == mb) {
+            if (mb->owner->children) { napi_throw_error(env, NULL, "the model is part of the context's ensemble while a batch is in flight"); return NULL; }
+            box_drop_ensemble(mb->owner); break;
+        }
+    }
     if (mb->m) { wsa_model_destroy(mb->m); mb->m = NULL; }
     model_unlink(mb);
     return NULL;
@@ -836,7 +1005,7 @@ NAPI_MODULE_INIT() {
     const struct { const char *name; napi_callback fn; } fns[] = {
         {"abiVersion", fn_abi_version}, {"freePinned", fn_free_pinned}, {"defaults", fn_defaults}, {"create", fn_create}, {"destroy", fn_destroy},
         {"geometry", fn_geometry}, {"allocPinned", fn_alloc_pinned}, {"binsHz", fn_bins_hz}, {"processBatch", fn_process_batch}, {"gatherRows", fn_gather_rows},
-        {"streamOpen", fn_stream_open}, {"streamOpenMixed", fn_stream_open_mixed}, {"streamInfo", fn_stream_info}, {"streamPaced", fn_stream_paced}, {"streamInput", fn_stream_input}, {"streamStep", fn_stream_step}, {"streamClose", fn_stream_close}, {"streamSetModel", fn_stream_set_model},
+        {"streamOpen", fn_stream_open}, {"streamOpenMixed", fn_stream_open_mixed}, {"streamInfo", fn_stream_info}, {"streamPaced", fn_stream_paced}, {"streamInput", fn_stream_input}, {"streamStep", fn_stream_step}, {"streamClose", fn_stream_close}, {"streamSetModel", fn_stream_set_model}, {"streamSetEnsemble", fn_stream_set_ensemble},
         {"modelCreate", fn_model_create}, {"modelDestroy", fn_model_destroy}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
