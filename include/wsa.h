@@ -593,6 +593,39 @@ uint32_t   wsa_stream_frames_bound(uint32_t frames_per_step, uint32_t hop, doubl
  * floats, counts [n_streams]; either may be NULL.  WSA_ERR_INVALID if a stream produced more than cap. */
 wsa_status wsa_stream_copy_converted(wsa_stream *st, float *out, uint32_t cap, uint32_t *counts);
 
+/*
+ * ---- Training (additions within version 5: probe for wsa_trainer_create).
+ * Stands in for the other half of the reference APPLICATION's "ML" panel: src/neuralmodel.js:163-403 (train_nn) hands the stored
+ * level-13 rows to ml5.neuralNetwork(...).train({epochs, batchSize}).  In dist/ml5.min.js (ml5 0.6.0 on tfjs 1.7.2, byte offsets):
+ * `compile` @2770937 (task classification: categoricalCrossentropy, tf.train.sgd(learningRate), metrics ["accuracy"]),
+ * `trainInternal` @2768349 ({epochs: 10, batchSize: 32, validationSplit: .1}; model.fit @2755107 shuffles per epoch),
+ * `normalizeValue` @2469274, `createOneHotEncodings` @2745375.  One run is the deterministic function TR-1 of DESIGN.md: the SGD
+ * arithmetic is pinned to tfjs by tests/golden/train_expected.json; the initial weights and the order of the training rows in every
+ * epoch are the caller's (the reference draws both from Math.random).  K7 (csrc/train.hip) is reproducible bit for bit.
+ * Classification only: the regression models (ords_*: mean squared error, Adam) are not trained.
+ * A trainer belongs to the context it was created on; destroy it before that context.
+ */
+typedef struct wsa_trainer wsa_trainer;
+typedef struct { uint32_t epochs_done; double loss, acc, val_loss, val_acc; } wsa_train_stats;   /* of the last finished epoch; val_* are 0 when n_val is 0 */
+/* init: the stack with its INITIAL kernels / biases, in_min / in_max the ranges to normalise with, labels the legend (or NULL).
+ * feat: host [n_rows][WSA_NFEAT] double; label: host [n_rows] class index; the last n_val rows are validation and never trained on.
+ * A batch_size above the number of training rows is one step over all of them.  WSA_ERR_INVALID with a message: a last layer that
+ * is not softmax, a label outside 0 .. classes - 1, n_val >= n_rows, batch_size 0, a learning rate that is not finite as an f32, and a
+ * feature with in_max == in_min (ml5 would train on NaN inputs; refused instead, naming the feature). */
+wsa_status wsa_trainer_create(wsa_ctx *ctx, const wsa_model_desc *init, const double *feat, const int32_t *label, uint32_t n_rows,
+                              uint32_t n_val, uint32_t batch_size, double learning_rate, wsa_trainer **out);
+/* One epoch: ceil(n_train / batch_size) SGD steps over the training rows taken in `order` (host [n_rows - n_val], every entry in
+ * 0 .. n_train - 1, checked before anything is enqueued; NULL = 0, 1, 2, ...), then one forward pass over the validation rows.
+ * Only enqueues on `stream`; allocates nothing.  A trainer has one set of buffers: every call on it (epoch, stats, copy_weights,
+ * model) must pass the SAME stream, whose order is what serialises the epochs. */
+wsa_status wsa_trainer_epoch(wsa_trainer *t, const uint32_t *order, void *stream);
+wsa_status wsa_trainer_stats(wsa_trainer *t, void *stream, wsa_train_stats *out);                            /* synchronises `stream` */
+/* the current weights, unpadded, in the tfjs layout of wsa_model_desc (kernel[l] [units[l]][units[l+1]], bias[l] [units[l+1]]); synchronises */
+wsa_status wsa_trainer_copy_weights(wsa_trainer *t, void *stream, float *const *kernel, float *const *bias);
+/* a snapshot of the current weights as a model every wsa_*classify* entry point takes (the caller destroys it); synchronises */
+wsa_status wsa_trainer_model(wsa_trainer *t, void *stream, wsa_model **out);
+void       wsa_trainer_destroy(wsa_trainer *t);
+
 #ifdef __cplusplus
 }
 #endif

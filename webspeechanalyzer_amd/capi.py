@@ -102,6 +102,11 @@ class _StreamClassResult(ctypes.Structure):
                 ("stream_conf", ctypes.c_void_p)]
 
 
+class _TrainStats(ctypes.Structure):
+    _fields_ = [("epochs_done", ctypes.c_uint32), ("loss", ctypes.c_double), ("acc", ctypes.c_double),
+                ("val_loss", ctypes.c_double), ("val_acc", ctypes.c_double)]
+
+
 ENSEMBLE_MAX = 8           # WSA_ENSEMBLE_MAX
 _VP8, _U32x8 = ctypes.c_void_p * ENSEMBLE_MAX, ctypes.c_uint32 * ENSEMBLE_MAX
 
@@ -148,7 +153,9 @@ ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destr
                "wsa_stream_set_ensemble", "wsa_stream_ensemble_classes",
                # additions within version 5 (probe for wsa_stream_create_mixed): streams of different rates, converted inside the step
                "wsa_stream_create_mixed", "wsa_stream_input_capacity", "wsa_stream_input_stride", "wsa_stream_paced_input", "wsa_stream_step_frame_capacity",
-               "wsa_stream_step_n", "wsa_stream_step_host_n", "wsa_resample_ready", "wsa_stream_frames_bound", "wsa_stream_copy_converted"]
+               "wsa_stream_step_n", "wsa_stream_step_host_n", "wsa_resample_ready", "wsa_stream_frames_bound", "wsa_stream_copy_converted",
+               # additions within version 5 (probe for wsa_trainer_create): training the app's classifiers (K7, spec TR-1)
+               "wsa_trainer_create", "wsa_trainer_destroy", "wsa_trainer_epoch", "wsa_trainer_stats", "wsa_trainer_copy_weights", "wsa_trainer_model"]
 
 _LIB = None
 _U32_RESULT = ("wsa_stream_input_capacity", "wsa_stream_paced_input", "wsa_stream_input_stride", "wsa_stream_step_frame_capacity", "wsa_stream_frames_bound")
@@ -261,12 +268,18 @@ def lib():
     L.wsa_resample_ready.argtypes = [u64, dbl, dbl]
     L.wsa_resample_ready.restype = ctypes.c_uint64
     L.wsa_stream_copy_converted.argtypes = [vp, vp, u32, vp]
+    L.wsa_trainer_create.argtypes = [vp, ctypes.POINTER(_ModelDesc), vp, vp, u32, u32, u32, dbl, ctypes.POINTER(vp)]
+    L.wsa_trainer_destroy.argtypes = [vp]
+    L.wsa_trainer_epoch.argtypes = [vp, vp, vp]
+    L.wsa_trainer_stats.argtypes = [vp, vp, ctypes.POINTER(_TrainStats)]
+    L.wsa_trainer_copy_weights.argtypes = [vp, vp, vp, vp]
+    L.wsa_trainer_model.argtypes = [vp, vp, ctypes.POINTER(vp)]
     for name in ABI_SYMBOLS:
         if name in _U32_RESULT or name == "wsa_resample_ready":
             continue
         if name not in ("wsa_abi_version", "wsa_last_error", "wsa_config_default", "wsa_destroy", "wsa_batch_destroy", "wsa_resample_length",
                         "wsa_stream_destroy", "wsa_stream_samples_per_step", "wsa_stream_host_input", "wsa_gather_destroy", "wsa_host_free",
-                        "wsa_model_destroy", "wsa_ensemble_destroy"):
+                        "wsa_model_destroy", "wsa_ensemble_destroy", "wsa_trainer_destroy"):
             getattr(L, name).restype = ctypes.c_int
     _LIB = L
     return L
@@ -340,6 +353,10 @@ class Analyzer:
         else:
             spec = nnmodel.load_dir(src)
         return Model(self, spec)
+
+    def trainer(self, spec, features, labels, n_val, batch_size, learning_rate):
+        """K7 on this context: SGD from the weights of `spec` over host rows (see Trainer; webspeechanalyzer_amd.train drives it)."""
+        return Trainer(self, spec, features, labels, n_val, batch_size, learning_rate)
 
     def ensemble(self, models):
         """The app's `available_DBs` on this context: a list of 1 .. 8 Models in that order (every tie between DBs goes to the earlier one)."""
@@ -614,24 +631,31 @@ class Batch:
             pass
 
 
+def _model_desc(spec):
+    """(wsa_model_desc of an nnmodel.ModelSpec, the objects that own what it points to)."""
+    from . import nnmodel
+    nl = len(spec.kernels)
+    keep = [np.ascontiguousarray(k, np.float32) for k in spec.kernels] + [np.ascontiguousarray(b, np.float32) for b in spec.biases]
+    units = (ctypes.c_int32 * (nl + 1))(*spec.units)
+    acts = (ctypes.c_int32 * nl)(*[nnmodel.ACT[a] for a in spec.activations])
+    kp = (ctypes.c_void_p * nl)(*[a.ctypes.data for a in keep[:nl]])
+    bp = (ctypes.c_void_p * nl)(*[a.ctypes.data for a in keep[nl:]])
+    mn, mx = np.ascontiguousarray(spec.in_min, np.float64), np.ascontiguousarray(spec.in_max, np.float64)
+    labels = list(spec.labels)
+    lab = (ctypes.c_char_p * len(labels))(*[str(x).encode() for x in labels]) if len(labels) == spec.n_classes else None
+    d = _ModelDesc(nl, ctypes.cast(units, ctypes.c_void_p), ctypes.cast(acts, ctypes.c_void_p), ctypes.cast(kp, ctypes.c_void_p),
+                   ctypes.cast(bp, ctypes.c_void_p), mn.ctypes.data, mx.ctypes.data, ctypes.cast(lab, ctypes.c_void_p) if lab is not None else None)
+    return d, (keep, units, acts, kp, bp, mn, mx, lab)
+
+
 class Model:
     """wsa_model: a Dense classifier (the app's ml5 model) on the device of one context."""
 
     def __init__(self, an, spec):
-        from . import nnmodel
         self.an, self.L, self.spec = an, an.L, spec
         self.labels = list(spec.labels)
         self.n_classes = spec.n_classes
-        nl = len(spec.kernels)
-        self._keep = [np.ascontiguousarray(k, np.float32) for k in spec.kernels] + [np.ascontiguousarray(b, np.float32) for b in spec.biases]
-        units = (ctypes.c_int32 * (nl + 1))(*spec.units)
-        acts = (ctypes.c_int32 * nl)(*[nnmodel.ACT[a] for a in spec.activations])
-        kp = (ctypes.c_void_p * nl)(*[a.ctypes.data for a in self._keep[:nl]])
-        bp = (ctypes.c_void_p * nl)(*[a.ctypes.data for a in self._keep[nl:]])
-        mn, mx = np.ascontiguousarray(spec.in_min, np.float64), np.ascontiguousarray(spec.in_max, np.float64)
-        lab = (ctypes.c_char_p * len(self.labels))(*[str(x).encode() for x in self.labels]) if len(self.labels) == spec.n_classes else None
-        d = _ModelDesc(nl, ctypes.cast(units, ctypes.c_void_p), ctypes.cast(acts, ctypes.c_void_p), ctypes.cast(kp, ctypes.c_void_p),
-                       ctypes.cast(bp, ctypes.c_void_p), mn.ctypes.data, mx.ctypes.data, ctypes.cast(lab, ctypes.c_void_p) if lab is not None else None)
+        d, self._keep = _model_desc(spec)
         self.h = ctypes.c_void_p()
         an._check(self.L.wsa_model_create(an.h, ctypes.byref(d), ctypes.byref(self.h)))
         self._keep = None
@@ -643,6 +667,74 @@ class Model:
     def close(self):
         if self.h:
             self.L.wsa_model_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Trainer:
+    """wsa_trainer: minibatch SGD on the app's Dense classifiers (K7, spec TR-1).  `spec` holds the INITIAL weights, the ranges to
+    normalise with and the legend; features [n][53] f64 and labels [n] class indices are host arrays, the last n_val rows validation."""
+
+    def __init__(self, an, spec, features, labels, n_val, batch_size, learning_rate):
+        self.an, self.L, self.spec = an, an.L, spec
+        feat = np.ascontiguousarray(features, np.float64)
+        lab = np.ascontiguousarray(labels, np.int32)
+        if feat.ndim != 2 or feat.shape[1] != 53 or lab.shape != (feat.shape[0],):
+            raise ValueError(f"features {feat.shape} / labels {lab.shape}: expected [n][53] and [n]")
+        self.n_rows, self.n_val, self.n_train = feat.shape[0], int(n_val), feat.shape[0] - int(n_val)
+        d, keep = _model_desc(spec)
+        self.h = ctypes.c_void_p()
+        an._check(self.L.wsa_trainer_create(an.h, ctypes.byref(d), feat.ctypes.data, lab.ctypes.data, feat.shape[0], int(n_val), int(batch_size),
+                                            float(learning_rate), ctypes.byref(self.h)))
+        del keep
+
+    def epoch(self, order=None, stream=0):
+        """Enqueues one epoch over the training rows in `order` (a sequence of n_train row indices; None = 0, 1, 2, ...)."""
+        o = None if order is None else np.ascontiguousarray(order, np.uint32)
+        if o is not None and o.shape != (self.n_train,):
+            raise ValueError(f"order has shape {o.shape}, the trainer has {self.n_train} training rows")
+        self.an._check(self.L.wsa_trainer_epoch(self.h, o.ctypes.data if o is not None else None, stream))
+
+    def stats(self, stream=0):
+        """Synchronises; {epochs_done, loss, acc, val_loss, val_acc} of the last finished epoch (ml5's whileTraining / tfjs history)."""
+        st = _TrainStats()
+        self.an._check(self.L.wsa_trainer_stats(self.h, stream, ctypes.byref(st)))
+        return {k: getattr(st, k) for k, _ in _TrainStats._fields_}
+
+    def weights(self, stream=0):
+        """Synchronises; (kernels, biases) as nnmodel.ModelSpec holds them."""
+        u = self.spec.units
+        ks = [np.zeros((u[i], u[i + 1]), np.float32) for i in range(len(u) - 1)]
+        bs = [np.zeros(u[i + 1], np.float32) for i in range(len(u) - 1)]
+        kp = (ctypes.c_void_p * len(ks))(*[a.ctypes.data for a in ks])
+        bp = (ctypes.c_void_p * len(bs))(*[a.ctypes.data for a in bs])
+        self.an._check(self.L.wsa_trainer_copy_weights(self.h, stream, ctypes.cast(kp, ctypes.c_void_p), ctypes.cast(bp, ctypes.c_void_p)))
+        return ks, bs
+
+    def spec_now(self, stream=0):
+        """The current weights as an nnmodel.ModelSpec (what nnmodel.save_dir writes)."""
+        from . import nnmodel
+        ks, bs = self.weights(stream)
+        s = self.spec
+        return nnmodel.ModelSpec(list(s.units), list(s.activations), ks, bs, np.array(s.in_min, np.float64), np.array(s.in_max, np.float64), list(s.labels))
+
+    def model(self, stream=0):
+        """A snapshot of the current weights as a Model on the same context (wsa_trainer_model)."""
+        m = Model.__new__(Model)
+        m.an, m.L, m.spec = self.an, self.L, self.spec
+        m.labels, m.n_classes, m._keep = list(self.spec.labels), self.spec.n_classes, None
+        m.h = ctypes.c_void_p()
+        self.an._check(self.L.wsa_trainer_model(self.h, stream, ctypes.byref(m.h)))
+        return m
+
+    def close(self):
+        if self.h:
+            self.L.wsa_trainer_destroy(self.h)
             self.h = ctypes.c_void_p()
 
     def __del__(self):

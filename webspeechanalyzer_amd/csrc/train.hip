@@ -1,0 +1,495 @@
+// train.hip — K7: minibatch SGD for the app's Dense classifiers (specification TR-1), and its part of the C ABI
+// (include/wsa.h "Training").
+//
+// Stands in for the reference APPLICATION's training path: src/neuralmodel.js:163-403 (train_nn) -> ml5 0.6.0
+// neuralNetwork.train: tfjs 1.7.2 model.fit with categoricalCrossentropy, tf.train.sgd(learningRate), metrics ["accuracy"].
+//
+// One step is a chain of kernels on the caller's stream; every dependency between stages is a kernel boundary:
+//   forward  l = 0 .. L-1   A[l+1] = act_l(A[l] W_l + b_l)          one wave per 16 x 16 tile of A[l+1]; f32 MFMA partial sums, added in double
+//   loss                    p, per-row loss / hit, dZ_{L-1}          one workgroup, fixed-order sums -> the step's partial
+//   backward l = L-1 .. 0   dZ_{l-1} = (dZ_l W_l^T) . act'(A[l])     one wave per 16 x 16 tile (l > 0 only), BEFORE W_l changes
+//                           W_l -= lr A[l]^T dZ_l, b_l -= lr 1^T dZ_l one wave per 16 x 16 tile of W_l: it owns the whole sum over the
+//                                                                    batch rows (ascending, four per MFMA) and applies the update
+// Every sum has one owner and one order, nothing is accumulated with atomics, so a run is reproducible bit for bit.
+// mfma_f32_16x16x4f32 as in K6: lane l holds A[row l&15][k l>>4], B[k l>>4][col l&15]; D col = l&15, row = 4 (l>>4) + i.
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+#include "host_plan.hpp"
+
+using wsa_api::fail;
+
+namespace {
+
+constexpr int TR_THREADS = 256;                  // 4 waves, one 16 x 16 output tile each
+constexpr int TR_WAVES = TR_THREADS / 64;
+constexpr int TR_LOSS_THREADS = 1024;
+constexpr int TR_XS = 64;                        // stride of the normalised rows: WSA_NFEAT padded to 16-column blocks
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// rows of a step's input: row r of the step is base[(idx ? idx[off + r] : off + r) * stride]; rows >= m read as zero
+struct TrRows { const float* base; int stride; const uint32_t* idx; uint32_t off, m; };
+
+__device__ __forceinline__ const float* tr_row(const TrRows& a, uint32_t r) {
+    if (r >= a.m) return nullptr;
+    const size_t g = a.idx ? a.idx[a.off + r] : a.off + r;
+    return a.base + g * (size_t)a.stride;
+}
+
+__device__ __forceinline__ float tr_activate(float v, int act) {            // K6's activate
+    switch (act) {
+        case WSA_ACT_RELU: return v < 0.f ? 0.f : v;
+        case WSA_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
+        case WSA_ACT_TANH: return tanhf(v);
+        default: return v;
+    }
+}
+
+__device__ __forceinline__ float tr_derivative(float a, int act) {          // tfjs gradients, from the layer's OUTPUT a
+    switch (act) {
+        case WSA_ACT_RELU: return a > 0.f ? 1.f : 0.f;                      // step(x); a > 0 exactly when x > 0
+        case WSA_ACT_SIGMOID: return a * (1.f - a);
+        case WSA_ACT_TANH: return 1.f - a * a;
+        default: return 1.f;
+    }
+}
+
+// ---- forward: out [mp][np] = act(in [m][kp] . w [kp][np] + b), rows m .. mp-1 and columns n .. np-1 written as zero
+struct TrFwd { TrRows in; const float* w; const float* b; float* out; int kp, np, n, act; uint32_t mp; };
+
+__global__ void __launch_bounds__(TR_THREADS) train_forward_kernel(TrFwd p) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t cbs = p.np / 16, tile = blockIdx.x * TR_WAVES + wave;
+    if (tile >= (p.mp / 16) * cbs) return;
+    const uint32_t r0 = (tile / cbs) * 16; const int n0 = (tile % cbs) * 16;
+    const float* ap = tr_row(p.in, r0 + (lane & 15));
+    const float* wp = p.w + (size_t)(lane >> 4) * p.np + n0 + (lane & 15);
+    // Every MFMA starts from zero and its f32 result (four products) is added to a double accumulator: a layer's output is rounded to
+    // f32 once, as tfjs's CPU backend rounds it (it sums each dot product in a double); DESIGN.md "K7" has the finding that asks for it.
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    for (int k1 = 0; k1 < p.kp; k1 += 16) {                                 // kp is a multiple of 16: four loads in flight
+        float av[4], bv[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) { av[j] = ap ? ap[k1 + 4 * j + (lane >> 4)] : 0.f; bv[j] = wp[(size_t)(k1 + 4 * j) * p.np]; }
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const f32x4 part = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], bv[j], zero, 0, 0, 0);
+#pragma unroll
+            for (int i = 0; i < 4; i++) acc[i] += (double)part[i];          // K ascending, one owner: the same bits every run
+        }
+    }
+    const int col = n0 + (lane & 15);
+    const double bias = (double)p.b[col];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const uint32_t row = r0 + (lane >> 4) * 4 + i;
+        float v = (float)(acc[i] + bias);                                   // tfjs Dense: matMul + bias, then the activation
+        if (p.act != WSA_ACT_SOFTMAX) v = tr_activate(v, p.act);
+        if (col >= p.n || row >= p.in.m) v = 0.f;
+        p.out[(size_t)row * p.np + col] = v;
+    }
+}
+
+// ---- loss: softmax (K6's formula), tfjs categoricalCrossentropy and categoricalAccuracy per row, dZ of the last layer; one workgroup:
+// thread t sums rows t, t + 1024, ... in that order, then a fixed tree over the threads -> part_loss / part_hit [slot]
+struct TrLoss {
+    const float* z; int np, C; uint32_t m, mp;
+    const int32_t* label; const uint32_t* idx; uint32_t off;
+    float* dz;                                                              // NULL: evaluation only
+    double* part_loss; uint32_t* part_hit; uint32_t slot;
+};
+
+__global__ void __launch_bounds__(TR_LOSS_THREADS) train_loss_kernel(TrLoss p) {
+    __shared__ double s_loss[TR_LOSS_THREADS];
+    __shared__ uint32_t s_hit[TR_LOSS_THREADS];
+    const int tid = threadIdx.x;
+    double loss = 0.0; uint32_t hit = 0;
+    for (uint32_t r = tid; r < p.mp; r += TR_LOSS_THREADS) {
+        float* d = p.dz ? p.dz + (size_t)r * p.np : nullptr;
+        if (r >= p.m) {
+            if (d) for (int c = 0; c < p.np; c++) d[c] = 0.f;
+            continue;
+        }
+        const float* x = p.z + (size_t)r * p.np;
+        const int t = p.label[p.idx ? p.idx[p.off + r] : p.off + r];
+        // the f32 logits' softmax and loss in double: a row costs C exponentials, and the step's gradient starts without libm's f32 error
+        double mx = x[0];
+        for (int c = 1; c < p.C; c++) mx = fmax(mx, (double)x[c]);
+        double s = 0.0;
+        for (int c = 0; c < p.C; c++) s += exp((double)x[c] - mx);
+        const double lse = mx + log(s);
+        double sum = 0.0, pt = 0.0, best = -1.0; int arg = 0;
+        for (int c = 0; c < p.C; c++) {
+            const double pc = exp((double)x[c] - lse);
+            sum += pc;
+            if (c == t) pt = pc;
+            if (pc > best) { best = pc; arg = c; }                          // first maximum on a tie
+        }
+        const double q = pt / sum, lo = 1e-7, hi = 1.0 - 1e-7;              // the loss renormalises, then clips
+        const bool clipped = q < lo;
+        loss += -log(q < lo ? lo : (q > hi ? hi : q));
+        hit += arg == t ? 1u : 0u;
+        if (d) {
+            const double b = (double)p.m;
+            for (int c = 0; c < p.np; c++) {
+                float g = 0.f;
+                if (c < p.C && !clipped) g = (float)((exp((double)x[c] - lse) - (c == t ? 1.0 : 0.0)) / b);   // tfjs's clip passes no gradient below its minimum
+                d[c] = g;
+            }
+        }
+    }
+    s_loss[tid] = loss; s_hit[tid] = hit;
+    __syncthreads();
+    for (int w = TR_LOSS_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) { s_loss[tid] += s_loss[tid + w]; s_hit[tid] += s_hit[tid + w]; }
+        __syncthreads();
+    }
+    if (tid == 0) { p.part_loss[p.slot] = s_loss[0]; p.part_hit[p.slot] = s_hit[0]; }
+}
+
+// ---- backward through one layer's kernel: dzp [mp][kp] = (dz [mp][np] . w^T) . act'(a [mp][kp]); columns k .. kp-1, rows m .. zero
+struct TrBack { const float* dz; const float* w; const float* a; float* dzp; int kp, np, k, act; uint32_t m, mp; };
+
+__global__ void __launch_bounds__(TR_THREADS) train_backward_kernel(TrBack p) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t kbs = p.kp / 16, tile = blockIdx.x * TR_WAVES + wave;
+    if (tile >= (p.mp / 16) * kbs) return;
+    const uint32_t r0 = (tile / kbs) * 16; const int k0 = (tile % kbs) * 16;
+    const float* ap = p.dz + (size_t)(r0 + (lane & 15)) * p.np + (lane >> 4);
+    const float* wp = p.w + (size_t)(k0 + (lane & 15)) * p.np + (lane >> 4);      // B[n][k] = w[k][n]
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int n1 = 0; n1 < p.np; n1 += 16) {
+        float av[4], bv[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) { av[j] = ap[n1 + 4 * j]; bv[j] = wp[n1 + 4 * j]; }
+#pragma unroll
+        for (int j = 0; j < 4; j++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], bv[j], acc, 0, 0, 0);
+    }
+    const int col = k0 + (lane & 15);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const uint32_t row = r0 + (lane >> 4) * 4 + i;
+        const size_t at = (size_t)row * p.kp + col;
+        float v = acc[i] * tr_derivative(p.a[at], p.act);
+        if (col >= p.k || row >= p.m) v = 0.f;
+        p.dzp[at] = v;
+    }
+}
+
+// ---- update: w [kp][np] -= lr a^T dz, b -= lr 1^T dz.  Tiles (kb, cb), kb = kp / 16 is the bias's tile (A = ones).  The wave that
+// owns a tile sums over all batch rows in ascending order and writes the new weights; padded rows / columns stay zero.
+struct TrUpd { TrRows a; const float* dz; float* w; float* b; int kp, np, k, n; uint32_t mp; float lr; };
+
+__global__ void __launch_bounds__(TR_THREADS) train_update_kernel(TrUpd p) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t cbs = p.np / 16, kbs = p.kp / 16, tile = blockIdx.x * TR_WAVES + wave;
+    if (tile >= (kbs + 1) * cbs) return;
+    const uint32_t kb = tile / cbs; const int n0 = (tile % cbs) * 16, k0 = kb * 16;
+    const bool bias = kb == kbs;
+    const float* dp = p.dz + (size_t)(lane >> 4) * p.np + n0 + (lane & 15);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (uint32_t r1 = 0; r1 < p.mp; r1 += 16) {                            // mp is a multiple of 16; dz rows m .. mp-1 are zero
+        float av[4], bv[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint32_t r = r1 + 4 * j + (lane >> 4);
+            if (bias) av[j] = 1.f;
+            else { const float* ar = tr_row(p.a, r); av[j] = ar ? ar[k0 + (lane & 15)] : 0.f; }
+            bv[j] = dp[(size_t)(r1 + 4 * j) * p.np];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], bv[j], acc, 0, 0, 0);
+    }
+    const int col = n0 + (lane & 15);
+    if (col >= p.n) return;
+    if (bias) {
+        if ((lane >> 4) == 0) p.b[col] = p.b[col] - p.lr * acc[0];          // every row of the tile holds the column sums
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int row = k0 + (lane >> 4) * 4 + i;
+        if (row >= p.k) continue;
+        const size_t at = (size_t)row * p.np + col;
+        p.w[at] = p.w[at] - p.lr * acc[i];                                  // tf.train.sgd: value + (-lr) gradient, in f32
+    }
+}
+
+// ---- epoch end: the steps' partials in a fixed order -> the epoch's statistics (history of tfjs's BaseLogger / testLoop)
+struct TrFin { const double* part_loss; const uint32_t* part_hit; uint32_t n_steps, n_train, n_val, epoch; wsa_train_stats* out; };
+
+__global__ void __launch_bounds__(256) train_finish_kernel(TrFin p) {
+    __shared__ double s_loss[256];
+    __shared__ uint32_t s_hit[256];
+    const int tid = threadIdx.x;
+    double loss = 0.0; uint32_t hit = 0;
+    for (uint32_t i = tid; i < p.n_steps; i += 256) { loss += p.part_loss[i]; hit += p.part_hit[i]; }
+    s_loss[tid] = loss; s_hit[tid] = hit;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) { s_loss[tid] += s_loss[tid + w]; s_hit[tid] += s_hit[tid + w]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        wsa_train_stats st;
+        st.epochs_done = p.epoch;
+        st.loss = s_loss[0] / (double)p.n_train; st.acc = (double)s_hit[0] / (double)p.n_train;
+        st.val_loss = p.n_val ? p.part_loss[p.n_steps] / (double)p.n_val : 0.0;
+        st.val_acc = p.n_val ? (double)p.part_hit[p.n_steps] / (double)p.n_val : 0.0;
+        *p.out = st;
+    }
+}
+
+// ---- create: (x - min) / (max - min) in double, rounded to f32 (ml5 normalizeValue, as K6), rows padded to TR_XS zero columns
+__global__ void __launch_bounds__(256) train_normalise_kernel(const double* feat, const double* mn, const double* mx, uint64_t n_rows, float* x) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_rows * TR_XS) return;
+    const uint64_t r = i / TR_XS; const int k = (int)(i % TR_XS);
+    x[i] = k < WSA_NFEAT ? (float)((feat[r * WSA_NFEAT + k] - mn[k]) / (mx[k] - mn[k])) : 0.f;
+}
+
+}  // namespace
+
+struct wsa_trainer {
+    wsa_ctx* ctx = nullptr;
+    int nl = 0;
+    int units[WSA_MODEL_MAX_LAYERS + 1] = {}, pad[WSA_MODEL_MAX_LAYERS + 1] = {}, act[WSA_MODEL_MAX_LAYERS] = {};
+    uint32_t n_rows = 0, n_train = 0, n_val = 0, batch = 0, n_steps = 0, mcap = 0, epoch = 0;
+    float lr = 0.f;
+    float* d_x = nullptr; int32_t* d_label = nullptr;
+    float *d_w[WSA_MODEL_MAX_LAYERS] = {}, *d_b[WSA_MODEL_MAX_LAYERS] = {};
+    float* d_a[WSA_MODEL_MAX_LAYERS + 1] = {};                 // d_a[l], l >= 1: the output of layer l - 1, [mcap][pad[l]]
+    float* d_dz[2] = {};                                       // [mcap][widest layer]: dZ of a layer and of the one below it
+    uint32_t *d_order = nullptr, *d_identity = nullptr;
+    uint32_t* h_order[2] = {}; hipEvent_t ev[2] = {};          // pinned staging of the order, two epochs deep
+    double* d_part_loss = nullptr; uint32_t* d_part_hit = nullptr;
+    wsa_train_stats* d_stats = nullptr;
+    std::vector<double> in_min, in_max;
+    std::vector<std::string> labels; bool has_labels = false;
+    wsa::DevArena mem;
+};
+
+namespace {
+
+inline uint32_t up16(uint32_t v) { return (v + 15u) & ~15u; }
+inline uint32_t blocks_for(uint64_t tiles) { return (uint32_t)((tiles + TR_WAVES - 1) / TR_WAVES); }
+
+// the forward pass over m rows (a step's, through `idx`, or the validation rows); leaves the logits in d_a[nl]
+void enqueue_forward(wsa_trainer* t, const uint32_t* idx, uint32_t off, uint32_t m, hipStream_t s) {
+    const uint32_t mp = up16(m);
+    for (int l = 0; l < t->nl; l++) {
+        TrFwd f{};
+        f.in = l == 0 ? TrRows{t->d_x, TR_XS, idx, off, m} : TrRows{t->d_a[l], t->pad[l], nullptr, 0, m};
+        f.w = t->d_w[l]; f.b = t->d_b[l]; f.out = t->d_a[l + 1];
+        f.kp = t->pad[l]; f.np = t->pad[l + 1]; f.n = t->units[l + 1]; f.act = t->act[l]; f.mp = mp;
+        hipLaunchKernelGGL(train_forward_kernel, dim3(blocks_for((uint64_t)(mp / 16) * (f.np / 16))), dim3(TR_THREADS), 0, s, f);
+    }
+}
+
+void enqueue_loss(wsa_trainer* t, const uint32_t* idx, uint32_t off, uint32_t m, float* dz, uint32_t slot, hipStream_t s) {
+    TrLoss p{};
+    p.z = t->d_a[t->nl]; p.np = t->pad[t->nl]; p.C = t->units[t->nl]; p.m = m; p.mp = up16(m);
+    p.label = t->d_label; p.idx = idx; p.off = off; p.dz = dz;
+    p.part_loss = t->d_part_loss; p.part_hit = t->d_part_hit; p.slot = slot;
+    hipLaunchKernelGGL(train_loss_kernel, dim3(1), dim3(TR_LOSS_THREADS), 0, s, p);
+}
+
+void enqueue_step(wsa_trainer* t, const uint32_t* idx, uint32_t step, hipStream_t s) {
+    const uint32_t off = step * t->batch, m = t->n_train - off < t->batch ? t->n_train - off : t->batch, mp = up16(m);
+    enqueue_forward(t, idx, off, m, s);
+    int cur = 0;
+    enqueue_loss(t, idx, off, m, t->d_dz[cur], step, s);
+    for (int l = t->nl - 1; l >= 0; l--) {
+        if (l > 0) {                                                       // reads W_l: enqueued before W_l's update
+            TrBack b{};
+            b.dz = t->d_dz[cur]; b.w = t->d_w[l]; b.a = t->d_a[l]; b.dzp = t->d_dz[cur ^ 1];
+            b.kp = t->pad[l]; b.np = t->pad[l + 1]; b.k = t->units[l]; b.act = t->act[l - 1]; b.m = m; b.mp = mp;
+            hipLaunchKernelGGL(train_backward_kernel, dim3(blocks_for((uint64_t)(mp / 16) * (b.kp / 16))), dim3(TR_THREADS), 0, s, b);
+        }
+        TrUpd u{};
+        u.a = l == 0 ? TrRows{t->d_x, TR_XS, idx, off, m} : TrRows{t->d_a[l], t->pad[l], nullptr, 0, m};
+        u.dz = t->d_dz[cur]; u.w = t->d_w[l]; u.b = t->d_b[l];
+        u.kp = t->pad[l]; u.np = t->pad[l + 1]; u.k = t->units[l]; u.n = t->units[l + 1]; u.mp = mp; u.lr = t->lr;
+        hipLaunchKernelGGL(train_update_kernel, dim3(blocks_for((uint64_t)(u.kp / 16 + 1) * (u.np / 16))), dim3(TR_THREADS), 0, s, u);
+        cur ^= 1;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+wsa_status wsa_trainer_create(wsa_ctx* ctx, const wsa_model_desc* d, const double* feat, const int32_t* label, uint32_t n_rows,
+                              uint32_t n_val, uint32_t batch_size, double learning_rate, wsa_trainer** out) {
+    if (!ctx || !d || !out) return fail(ctx, WSA_ERR_INVALID, "null argument");
+    *out = nullptr;
+    const int nl = d->n_layers;
+    if (nl < 1 || nl > WSA_MODEL_MAX_LAYERS) return fail(ctx, WSA_ERR_INVALID, "a model has 1 .. 8 Dense layers, got " + std::to_string(nl));
+    if (!d->units || !d->activation || !d->kernel || !d->bias) return fail(ctx, WSA_ERR_INVALID, "null units / activation / kernel / bias array");
+    if (d->units[0] != WSA_NFEAT) return fail(ctx, WSA_ERR_INVALID, "the model takes " + std::to_string(d->units[0]) + " inputs; the feature rows have 53");
+    for (int l = 0; l < nl; l++) {
+        const int u = d->units[l + 1], a = d->activation[l];
+        if (u < 1 || u > WSA_MODEL_MAX_WIDTH) return fail(ctx, WSA_ERR_INVALID, "layer " + std::to_string(l) + " has " + std::to_string(u) + " units (limit 1024)");
+        if (a < WSA_ACT_LINEAR || a > WSA_ACT_SOFTMAX) return fail(ctx, WSA_ERR_INVALID, "layer " + std::to_string(l) + ": unknown activation " + std::to_string(a));
+        if (a == WSA_ACT_SOFTMAX && l != nl - 1) return fail(ctx, WSA_ERR_INVALID, "softmax is only supported on the last layer");
+        if (!d->kernel[l] || !d->bias[l]) return fail(ctx, WSA_ERR_INVALID, "null kernel / bias of layer " + std::to_string(l));
+    }
+    if (d->activation[nl - 1] != WSA_ACT_SOFTMAX) return fail(ctx, WSA_ERR_INVALID, "training needs a softmax output layer (categoricalCrossentropy)");
+    const int C = d->units[nl];
+    if (C > WSA_MODEL_MAX_CLASSES) return fail(ctx, WSA_ERR_INVALID, "the output layer has " + std::to_string(C) + " units (limit 64)");
+    if (!d->in_min || !d->in_max) return fail(ctx, WSA_ERR_INVALID, "null in_min / in_max");
+    for (int k = 0; k < WSA_NFEAT; k++) {
+        if (!std::isfinite(d->in_min[k]) || !std::isfinite(d->in_max[k])) return fail(ctx, WSA_ERR_INVALID, "non-finite in_min / in_max of input " + std::to_string(k));
+        if (d->in_max[k] == d->in_min[k]) return fail(ctx, WSA_ERR_INVALID, "feature " + std::to_string(k) + " has max == min: it cannot be normalised");
+    }
+    if (!feat || !label) return fail(ctx, WSA_ERR_INVALID, "null feature / label pointer");
+    if (n_val >= n_rows) return fail(ctx, WSA_ERR_INVALID, "n_val " + std::to_string(n_val) + " leaves no training rows of " + std::to_string(n_rows));
+    if (batch_size == 0) return fail(ctx, WSA_ERR_INVALID, "batch_size must be at least 1");
+    if (!std::isfinite(learning_rate) || !std::isfinite((float)learning_rate)) return fail(ctx, WSA_ERR_INVALID, "the learning rate is not finite as an f32");
+    for (uint32_t r = 0; r < n_rows; r++)
+        if (label[r] < 0 || label[r] >= C) return fail(ctx, WSA_ERR_INVALID, "label " + std::to_string(label[r]) + " of row " + std::to_string(r) + " is outside 0 .. " + std::to_string(C - 1));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    wsa_trainer* t = new wsa_trainer();
+    t->ctx = ctx; t->nl = nl; t->n_rows = n_rows; t->n_val = n_val; t->n_train = n_rows - n_val;
+    t->batch = batch_size < t->n_train ? batch_size : t->n_train;            // a larger batch is one step over all training rows
+    t->n_steps = (t->n_train + t->batch - 1) / t->batch;
+    t->mcap = up16(t->batch > n_val ? t->batch : n_val);
+    t->lr = (float)learning_rate;
+    t->in_min.assign(d->in_min, d->in_min + WSA_NFEAT); t->in_max.assign(d->in_max, d->in_max + WSA_NFEAT);
+    if (d->labels) { t->has_labels = true; for (int c = 0; c < C; c++) t->labels.emplace_back(d->labels[c] ? d->labels[c] : ""); }
+    int pmax = 0;
+    for (int l = 0; l <= nl; l++) { t->units[l] = d->units[l]; t->pad[l] = (d->units[l] + 15) & ~15; if (l && t->pad[l] > pmax) pmax = t->pad[l]; }
+    for (int l = 0; l < nl; l++) t->act[l] = d->activation[l];
+    bool ok = true;
+    for (int l = 0; l < nl && ok; l++) {                                      // zero padded as K6 pads them
+        const int K = d->units[l], N = d->units[l + 1], kp = t->pad[l], np = t->pad[l + 1];
+        std::vector<float> w((size_t)kp * np, 0.f), bb(np, 0.f);
+        for (int k = 0; k < K; k++) std::memcpy(&w[(size_t)k * np], d->kernel[l] + (size_t)k * N, N * sizeof(float));
+        std::memcpy(bb.data(), d->bias[l], N * sizeof(float));
+        ok = t->mem.upload(&t->d_w[l], w) && t->mem.upload(&t->d_b[l], bb) && t->mem.alloc(&t->d_a[l + 1], (size_t)t->mcap * np, true);
+    }
+    std::vector<uint32_t> ident(t->n_train);
+    for (uint32_t i = 0; i < t->n_train; i++) ident[i] = i;
+    double *d_feat = nullptr, *d_mn = nullptr, *d_mx = nullptr;
+    {
+        wsa::DevArena tmp;                                                   // the double rows live only until they are normalised
+        ok = ok && t->mem.alloc(&t->d_dz[0], (size_t)t->mcap * pmax, true) && t->mem.alloc(&t->d_dz[1], (size_t)t->mcap * pmax, true)
+             && t->mem.alloc(&t->d_x, (size_t)n_rows * TR_XS) && t->mem.alloc(&t->d_label, n_rows)
+             && t->mem.alloc(&t->d_order, t->n_train) && t->mem.upload(&t->d_identity, ident)
+             && t->mem.alloc(&t->d_part_loss, t->n_steps + 1, true) && t->mem.alloc(&t->d_part_hit, t->n_steps + 1, true)
+             && t->mem.alloc(&t->d_stats, 1, true)
+             && hipHostMalloc(reinterpret_cast<void**>(&t->h_order[0]), (size_t)t->n_train * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess
+             && hipHostMalloc(reinterpret_cast<void**>(&t->h_order[1]), (size_t)t->n_train * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess
+             && hipEventCreateWithFlags(&t->ev[0], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&t->ev[1], hipEventDisableTiming) == hipSuccess
+             && tmp.alloc(&d_feat, (size_t)n_rows * WSA_NFEAT) && tmp.alloc(&d_mn, WSA_NFEAT) && tmp.alloc(&d_mx, WSA_NFEAT)
+             && hipMemcpy(d_feat, feat, (size_t)n_rows * WSA_NFEAT * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
+             && hipMemcpy(d_mn, d->in_min, WSA_NFEAT * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
+             && hipMemcpy(d_mx, d->in_max, WSA_NFEAT * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
+             && hipMemcpy(t->d_label, label, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
+        if (ok) {
+            const uint64_t total = (uint64_t)n_rows * TR_XS;
+            hipLaunchKernelGGL(train_normalise_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, nullptr, d_feat, d_mn, d_mx, (uint64_t)n_rows, t->d_x);
+            ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+        }
+    }
+    if (!ok) {
+        const std::string msg = std::string("device allocation / copy failed: ") + hipGetErrorString(hipGetLastError());
+        wsa_trainer_destroy(t);
+        return fail(ctx, WSA_ERR_HIP, msg);
+    }
+    *out = t;
+    return WSA_OK;
+}
+
+void wsa_trainer_destroy(wsa_trainer* t) {
+    if (!t) return;
+    (void)hipSetDevice(t->ctx->device);
+    for (int i = 0; i < 2; i++) {
+        if (t->ev[i]) { (void)hipEventSynchronize(t->ev[i]); (void)hipEventDestroy(t->ev[i]); }
+        if (t->h_order[i]) (void)hipHostFree(t->h_order[i]);
+    }
+    delete t;
+}
+
+wsa_status wsa_trainer_epoch(wsa_trainer* t, const uint32_t* order, void* stream) {
+    if (!t) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = t->ctx;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (order)
+        for (uint32_t i = 0; i < t->n_train; i++)
+            if (order[i] >= t->n_train) return fail(ctx, WSA_ERR_INVALID, "order[" + std::to_string(i) + "] = " + std::to_string(order[i]) + " is outside 0 .. " + std::to_string(t->n_train - 1));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint32_t* idx = t->d_identity;
+    if (order) {
+        const int slot = t->epoch & 1;                                       // the copy that last read this staging buffer is two epochs back
+        HIP_TRY(ctx, hipEventSynchronize(t->ev[slot]));
+        std::memcpy(t->h_order[slot], order, (size_t)t->n_train * sizeof(uint32_t));
+        HIP_TRY(ctx, hipMemcpyAsync(t->d_order, t->h_order[slot], (size_t)t->n_train * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipEventRecord(t->ev[slot], s));
+        idx = t->d_order;
+    }
+    for (uint32_t step = 0; step < t->n_steps; step++) enqueue_step(t, idx, step, s);
+    if (t->n_val) {                                                          // the same forward over the validation rows, after the last update
+        enqueue_forward(t, nullptr, t->n_train, t->n_val, s);
+        enqueue_loss(t, nullptr, t->n_train, t->n_val, nullptr, t->n_steps, s);
+    }
+    t->epoch++;
+    TrFin f{t->d_part_loss, t->d_part_hit, t->n_steps, t->n_train, t->n_val, t->epoch, t->d_stats};
+    hipLaunchKernelGGL(train_finish_kernel, dim3(1), dim3(256), 0, s, f);
+    HIP_TRY(ctx, hipGetLastError());
+    return WSA_OK;
+}
+
+wsa_status wsa_trainer_stats(wsa_trainer* t, void* stream, wsa_train_stats* out) {
+    if (!t) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = t->ctx;
+    if (!out) return fail(ctx, WSA_ERR_INVALID, "null argument");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(out, t->d_stats, sizeof(wsa_train_stats), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    return WSA_OK;
+}
+
+wsa_status wsa_trainer_copy_weights(wsa_trainer* t, void* stream, float* const* kernel, float* const* bias) {
+    if (!t) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = t->ctx;
+    if (!kernel || !bias) return fail(ctx, WSA_ERR_INVALID, "null kernel / bias array");
+    for (int l = 0; l < t->nl; l++) if (!kernel[l] || !bias[l]) return fail(ctx, WSA_ERR_INVALID, "null kernel / bias of layer " + std::to_string(l));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    for (int l = 0; l < t->nl; l++) {                                        // strided: the padded columns stay behind
+        const size_t n = (size_t)t->units[l + 1] * sizeof(float);
+        HIP_TRY(ctx, hipMemcpy2DAsync(kernel[l], n, t->d_w[l], (size_t)t->pad[l + 1] * sizeof(float), n, t->units[l], hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipMemcpyAsync(bias[l], t->d_b[l], n, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    return WSA_OK;
+}
+
+wsa_status wsa_trainer_model(wsa_trainer* t, void* stream, wsa_model** out) {
+    if (!t) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = t->ctx;
+    if (!out) return fail(ctx, WSA_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::vector<std::vector<float>> k(t->nl), b(t->nl);
+    std::vector<float*> kp(t->nl), bp(t->nl);
+    for (int l = 0; l < t->nl; l++) {
+        k[l].resize((size_t)t->units[l] * t->units[l + 1]); b[l].resize(t->units[l + 1]);
+        kp[l] = k[l].data(); bp[l] = b[l].data();
+    }
+    const wsa_status st = wsa_trainer_copy_weights(t, stream, kp.data(), bp.data());
+    if (st != WSA_OK) return st;
+    std::vector<const char*> lab;
+    for (const std::string& x : t->labels) lab.push_back(x.c_str());
+    wsa_model_desc d{};
+    d.n_layers = t->nl; d.units = t->units; d.activation = t->act;
+    d.kernel = kp.data(); d.bias = bp.data(); d.in_min = t->in_min.data(); d.in_max = t->in_max.data();
+    d.labels = t->has_labels ? lab.data() : nullptr;
+    return wsa_model_create(ctx, &d, out);
+}
+
+}  // extern "C"

@@ -256,6 +256,40 @@ function loadModel(src) {
   loaded_models.add(h);
   return h;
 }
+// ---- training (ref src/neuralmodel.js:163-403 train_nn + download_nn_model; K7 / specification TR-1, include/wsa.h "Training").
+// trainModel({features: [[53 numbers]], labels, classes, options, epochs, batchSize, seed, onEpoch}) -> Promise of a model handle that
+// setPredictionModel / setPredictionModels accept.  `options` is the app's options JSON ({layers, learningRate}); onEpoch(epoch, {loss, acc,
+// val_loss, val_acc}) mirrors ml5's whileTraining.  The selection, balancing, seeded initial weights and epoch orders live in trainmodel.js;
+// `init` ({kernels, biases}) and `orders` (Uint32Array [epochs][nTrain]) replace the seeded ones.  The epochs run off the JS thread.
+// The handle also carries `history` ([{loss, acc, val_loss, val_acc}] per epoch).  saveModel(handle, dir) writes the three files loadModel reads.
+function trainModel(o) {
+  const tm = require('./trainmodel.js');
+  let nat, ctx, spec, data, job;
+  try {
+    const opt = Object.assign({}, tm.DEFAULT_OPTIONS, o.options || {});
+    data = tm.prepare(o.features, o.labels, o.classes);
+    const st = tm.stack(opt.layers, data.legend.length), epochs = o.epochs === undefined ? 10 : o.epochs | 0, seed = o.seed | 0;
+    const sp = tm.split(data.y.length, o.validationSplit);
+    const init = o.init || tm.glorotInit(Array.from(st.units), seed);
+    spec = { units: st.units, activation: st.activation, kernels: init.kernels.map((k) => Float32Array.from(k)), biases: init.biases.map((b) => Float32Array.from(b)),
+      inMin: data.inMin, inMax: data.inMax, labels: data.legend.slice() };
+    job = { features: data.features, y: data.y, nVal: sp.nVal, batchSize: o.batchSize === undefined ? 32 : o.batchSize, learningRate: opt.learningRate, epochs,
+      orders: o.orders || tm.epochOrders(sp.nTrain, epochs, seed + 1) };
+    nat = addon();
+    ctx = contexts_for(nat, settings.devices ? settings.devices.slice() : [settings.device])[0];
+  } catch (e) { return Promise.reject(e); }
+  return nat.train(ctx, spec, job, typeof o.onEpoch === 'function' ? o.onEpoch : undefined).then((r) => {
+    const h = { spec: Object.assign({}, spec, { kernels: r.kernels, biases: r.biases }), natives: new Map(), released: false, history: [] };
+    for (let e = 0; e < job.epochs; e++) h.history.push({ loss: r.history[4 * e], acc: r.history[4 * e + 1], val_loss: r.history[4 * e + 2], val_acc: r.history[4 * e + 3] });
+    h.labels = h.spec.labels.slice();
+    loaded_models.add(h);
+    return h;
+  });
+}
+function saveModel(handle, dir) {
+  if (!handle || !handle.spec) throw 'saveModel(handle, dir)';
+  require('./trainmodel.js').saveModelFiles(handle.spec, dir);
+}
 function setPredictionModel(handle, on_prediction) {
   if (handle === null || handle === undefined) { prediction = null; return; }
   if (!loaded_models.has(handle) || handle.released) throw 'setPredictionModel: the model handle was released (shutdown()) or is not one of loadModel';
@@ -827,4 +861,4 @@ function set_predicted_label_for_segment(si, idx, label) {                      
 
 module.exports = { configure, LaunchAudioNodes, StopAudioNodes, set_predicted_label_for_segment, LaunchBatch, LaunchBatches,
   StreamOpen, STREAM_ACTIVE, STREAM_START, STREAM_STOP, shutdown, allocPinned, freePinned,
-  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, loadModel, setPredictionModel, setPredictionModels };
+  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, loadModel, setPredictionModel, setPredictionModels, trainModel, saveModel };

@@ -1,0 +1,106 @@
+// trainmodel.js — the host side of training the app's classifiers (specification TR-1, K7): what src/neuralmodel.js:163-403 (train_nn) does
+// around ml5.neuralNetwork(...).train — selecting and balancing the stored rows, the input ranges — plus what the reference draws from
+// Math.random and TR-1 leaves to the host (initial weights, one order of the training rows per epoch; here from a seeded generator of our own),
+// and the three files ml5 0.6.0's save() writes.  Pure JavaScript, no device.  Classification only; the '*' wildcard class is not supported.
+'use strict';
+const fs = require('fs');
+const path = require('path');
+
+const ACT = { linear: 0, relu: 1, sigmoid: 2, tanh: 3, softmax: 4 };
+const ACT_NAME = Object.keys(ACT);
+const DEFAULT_OPTIONS = { layers: [{ type: 'dense', units: 8, activation: 'relu' }, { type: 'dense', activation: 'softmax' }], learningRate: 0.2 };   // ref src/neuralmodel_aux.js:106-124
+
+// ref neuralmodel.js:216-264: rows whose label is one of `classes` in DB order; fewer than 10 refused; every class with more than 3 and fewer
+// than the largest count is topped up by cycling through the DB in order; min / max over the balanced set; legend = order of first appearance
+function prepare(features, labels, classes) {
+  classes = classes.map(String);
+  if (classes.indexOf('*') >= 0) throw "trainModel: the '*' wildcard class is not supported";
+  if (!Array.isArray(features) || features.length !== labels.length) throw 'trainModel: features and labels must have one entry per row';
+  const cls = labels.map((v) => (v === null || v === undefined ? -1 : classes.indexOf(String(v))));
+  const rows = [], count = new Array(classes.length).fill(0);
+  cls.forEach((c, i) => { if (c >= 0) { rows.push(i); count[c]++; } });
+  if (rows.length < 10) throw 'Sample size ' + rows.length + '/' + features.length + ' too small for training';
+  const max_n = Math.max(...count);
+  for (let c = 0; c < classes.length; c++)
+    while (count[c] < max_n && count[c] > 3)
+      for (let i = 0; i < features.length; i++) {
+        if (cls[i] === c && count[c] < max_n) { rows.push(i); count[c]++; }
+        if (count[c] >= max_n) break;
+      }
+  const legend = [];
+  for (const i of rows) if (legend.indexOf(classes[cls[i]]) < 0) legend.push(classes[cls[i]]);
+  const x = new Float64Array(rows.length * 53), y = new Int32Array(rows.length);
+  const inMin = new Float64Array(53).fill(Infinity), inMax = new Float64Array(53).fill(-Infinity);
+  rows.forEach((i, r) => {
+    if (features[i].length !== 53) throw 'trainModel: row ' + i + ' has ' + features[i].length + ' features; 53 expected';
+    for (let k = 0; k < 53; k++) { const v = Number(features[i][k]); x[r * 53 + k] = v; if (v < inMin[k]) inMin[k] = v; if (v > inMax[k]) inMax[k] = v; }
+    y[r] = legend.indexOf(classes[cls[i]]);
+  });
+  return { features: x, y, legend, inMin, inMax, counts: count, rows };
+}
+
+function rng(seed) {            // mulberry32: 32 bits of state, enough for weights and shuffles that only have to be repeatable
+  let a = (seed >>> 0) || 1;
+  return () => { a = (a + 0x6D2B79F5) >>> 0; let t = a; t = Math.imul(t ^ (t >>> 15), t | 1); t ^= t + Math.imul(t ^ (t >>> 7), t | 61); return ((t ^ (t >>> 14)) >>> 0) / 4294967296; };
+}
+// tfjs's default Dense initialisers: truncated normal (redrawn beyond two standard deviations), sd sqrt(2 / (fan_in + fan_out)); zero biases
+function glorotInit(units, seed) {
+  const u = rng(seed), kernels = [], biases = [];
+  const normal = () => { let z; do { z = Math.sqrt(-2 * Math.log(1 - u())) * Math.cos(2 * Math.PI * u()); } while (Math.abs(z) > 2); return z; };
+  for (let l = 0; l + 1 < units.length; l++) {
+    const sd = Math.sqrt(2 / (units[l] + units[l + 1])), k = new Float32Array(units[l] * units[l + 1]);
+    for (let i = 0; i < k.length; i++) k[i] = normal() * sd;
+    kernels.push(k); biases.push(new Float32Array(units[l + 1]));
+  }
+  return { kernels, biases };
+}
+function epochOrders(nTrain, epochs, seed) {       // one Fisher-Yates permutation per epoch, [epochs][nTrain]
+  const u = rng(seed), out = new Uint32Array(epochs * nTrain);
+  for (let e = 0; e < epochs; e++) {
+    const o = out.subarray(e * nTrain, (e + 1) * nTrain);
+    for (let i = 0; i < nTrain; i++) o[i] = i;
+    for (let i = nTrain - 1; i > 0; i--) { const j = Math.floor(u() * (i + 1)), t = o[i]; o[i] = o[j]; o[j] = t; }
+  }
+  return out;
+}
+function split(n, validationSplit) { const nTrain = Math.floor(n * (1 - (validationSplit === undefined ? 0.1 : validationSplit))); return { nTrain, nVal: n - nTrain }; }
+function stack(layers, nClasses) {
+  const units = [53], activation = [];
+  layers.forEach((l, i) => {
+    if ((l.type || 'dense') !== 'dense') throw 'trainModel: layer ' + i + ' is ' + l.type + '; only dense layers are supported';
+    const a = l.activation || 'linear';
+    if (!(a in ACT)) throw 'trainModel: layer ' + i + ' has activation ' + a;
+    units.push(i === layers.length - 1 ? nClasses : l.units | 0); activation.push(ACT[a]);
+  });
+  if (activation[activation.length - 1] !== ACT.softmax) throw 'trainModel: training needs a softmax output layer';
+  return { units: Int32Array.from(units), activation: Int32Array.from(activation) };
+}
+
+// model.json, model_meta.json, model.weights.bin in the key layout of the directories the app ships (dist/nnmodel/<db>/cats_<label>/)
+function saveModelFiles(spec, dir) {
+  const nl = spec.kernels.length, layers = [], weights = [], blobs = [];
+  if (spec.labels.length !== spec.units[nl]) throw 'saveModel: ' + spec.labels.length + ' legend labels for ' + spec.units[nl] + ' outputs';
+  for (let i = 0; i < nl; i++) {
+    const name = 'dense_Dense' + (i + 1);
+    const cfg = { units: spec.units[i + 1], activation: ACT_NAME[spec.activation[i]], use_bias: true,
+      kernel_initializer: { class_name: 'VarianceScaling', config: { scale: 1, mode: 'fan_avg', distribution: 'normal', seed: null } },
+      bias_initializer: { class_name: 'Zeros', config: {} }, kernel_regularizer: null, bias_regularizer: null, activity_regularizer: null,
+      kernel_constraint: null, bias_constraint: null, name, trainable: true };
+    if (i === 0) { cfg.batch_input_shape = [null, spec.units[0]]; cfg.dtype = 'float32'; }
+    layers.push({ class_name: 'Dense', config: cfg });
+    weights.push({ name: name + '/kernel', shape: [spec.units[i], spec.units[i + 1]], dtype: 'float32' }, { name: name + '/bias', shape: [spec.units[i + 1]], dtype: 'float32' });
+    for (const a of [spec.kernels[i], spec.biases[i]]) blobs.push(Buffer.from(a.buffer, a.byteOffset, a.byteLength));
+  }
+  const mj = { modelTopology: { class_name: 'Sequential', config: { name: 'sequential_1', layers }, keras_version: 'tfjs-layers 1.7.2', backend: 'tensor_flow.js' },
+    weightsManifest: [{ paths: ['./model.weights.bin'], weights }] };
+  const inputs = {}, legend = {}, C = spec.labels.length;
+  for (let k = 0; k < spec.units[0]; k++) inputs[String(k)] = { dtype: 'number', min: spec.inMin[k], max: spec.inMax[k] };
+  spec.labels.forEach((lab, j) => { legend[lab] = Array.from({ length: C }, (_, c) => (c === j ? 1 : 0)); });
+  const meta = { inputUnits: [spec.units[0]], outputUnits: C, inputs, outputs: { y: { dtype: 'string', min: 0, max: 1, uniqueValues: spec.labels.slice(), legend } }, isNormalized: true };
+  fs.mkdirSync(dir, { recursive: true });
+  fs.writeFileSync(path.join(dir, 'model.json'), JSON.stringify(mj));
+  fs.writeFileSync(path.join(dir, 'model_meta.json'), JSON.stringify(meta));
+  fs.writeFileSync(path.join(dir, 'model.weights.bin'), Buffer.concat(blobs));
+}
+
+module.exports = { prepare, glorotInit, epochOrders, split, stack, saveModelFiles, DEFAULT_OPTIONS };

@@ -999,6 +999,144 @@ static napi_value fn_model_destroy(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* ---- training (wsa_trainer_*, K7): train(ctx, spec, {features: Float64Array [n][53], y: Int32Array [n], nVal, batchSize, learningRate, epochs,
+ * orders: Uint32Array [epochs][n - nVal] | undefined}, onEpoch | undefined) -> Promise of {kernels: Float32Array[], biases: Float32Array[],
+ * history: Float64Array [epochs][4] = loss, acc, val_loss, val_acc}.  `spec` is modelCreate's object and holds the INITIAL weights.  The epochs run
+ * on a thread of their own (the inputs are copied first); after every epoch onEpoch(epoch, {loss, acc, val_loss, val_acc}) is queued to the JS
+ * thread (ml5's whileTraining), and the Promise settles after the last of them was delivered: both go through one first-in first-out queue. */
+typedef struct {
+    ctx_box *box; napi_deferred deferred; napi_threadsafe_function tsfn; pthread_t thread; napi_ref on_epoch;
+    int32_t nl, units[WSA_MODEL_MAX_LAYERS + 1], act[WSA_MODEL_MAX_LAYERS];
+    float *kernel[WSA_MODEL_MAX_LAYERS], *bias[WSA_MODEL_MAX_LAYERS];
+    double mn[WSA_NFEAT], mx[WSA_NFEAT];
+    double *feat; int32_t *y; uint32_t *orders; uint32_t n, n_val, batch, epochs; double lr;
+    double *history; wsa_status st; char err[512];
+} train_job;
+typedef struct { train_job *j; int32_t epoch; wsa_train_stats s; } train_msg;          /* epoch < 0: the run is over */
+
+static void train_job_free(train_job *j) {
+    for (int l = 0; l < WSA_MODEL_MAX_LAYERS; l++) { free(j->kernel[l]); free(j->bias[l]); }
+    free(j->feat); free(j->y); free(j->orders); free(j->history); free(j);
+}
+static void *train_thread(void *arg) {
+    train_job *j = (train_job *)arg;
+    wsa_ctx *ctx = j->box->ctx;
+    wsa_trainer *t = NULL;
+    wsa_model_desc d = {j->nl, j->units, j->act, (const float *const *)j->kernel, (const float *const *)j->bias, j->mn, j->mx, NULL};
+    j->st = wsa_trainer_create(ctx, &d, j->feat, j->y, j->n, j->n_val, j->batch, j->lr, &t);
+    for (uint32_t e = 0; j->st == WSA_OK && e < j->epochs; e++) {
+        j->st = wsa_trainer_epoch(t, j->orders ? j->orders + (size_t)e * (j->n - j->n_val) : NULL, j->box->queue);
+        wsa_train_stats s;
+        if (j->st == WSA_OK) j->st = wsa_trainer_stats(t, j->box->queue, &s);
+        if (j->st != WSA_OK) break;
+        j->history[4 * e] = s.loss; j->history[4 * e + 1] = s.acc; j->history[4 * e + 2] = s.val_loss; j->history[4 * e + 3] = s.val_acc;
+        train_msg *m = malloc(sizeof *m);
+        if (m) { m->j = j; m->epoch = (int32_t)e; m->s = s; if (napi_call_threadsafe_function(j->tsfn, m, napi_tsfn_blocking) != napi_ok) free(m); }
+    }
+    if (j->st == WSA_OK) j->st = wsa_trainer_copy_weights(t, j->box->queue, j->kernel, j->bias);
+    if (j->st != WSA_OK) snprintf(j->err, sizeof j->err, "%s", wsa_last_error(ctx));
+    if (t) wsa_trainer_destroy(t);
+    train_msg *m = malloc(sizeof *m);                       /* (a few bytes: if even this fails the Promise stays pending) */
+    if (m) { m->j = j; m->epoch = -1; napi_call_threadsafe_function(j->tsfn, m, napi_tsfn_blocking); }
+    return NULL;
+}
+static void train_call_js(napi_env env, napi_value js_cb, void *context, void *data) {
+    train_msg *m = (train_msg *)data;
+    train_job *j = m->j;
+    if (!env) { free(m); return; }
+    if (m->epoch >= 0) {
+        napi_value fn, undef, argv[2], v;
+        if (j->on_epoch && napi_get_reference_value(env, j->on_epoch, &fn) == napi_ok && napi_get_undefined(env, &undef) == napi_ok &&
+            napi_create_int32(env, m->epoch, &argv[0]) == napi_ok && napi_create_object(env, &argv[1]) == napi_ok) {
+            const char *names[4] = {"loss", "acc", "val_loss", "val_acc"}; const double vals[4] = {m->s.loss, m->s.acc, m->s.val_loss, m->s.val_acc};
+            for (int i = 0; i < 4; i++) if (napi_create_double(env, vals[i], &v) == napi_ok) napi_set_named_property(env, argv[1], names[i], v);
+            napi_call_function(env, undef, fn, 2, argv, NULL);
+        }
+        free(m);
+        return;
+    }
+    free(m);
+    pthread_join(j->thread, NULL);
+    if (j->box->children) j->box->children--;
+    if (j->st != WSA_OK) {
+        napi_value msg; napi_create_string_utf8(env, j->err, NAPI_AUTO_LENGTH, &msg);
+        napi_reject_deferred(env, j->deferred, msg);
+    } else {
+        napi_value o, ka, ba; napi_create_object(env, &o); napi_create_array_with_length(env, (size_t)j->nl, &ka); napi_create_array_with_length(env, (size_t)j->nl, &ba);
+        for (int l = 0; l < j->nl; l++) {
+            napi_set_element(env, ka, (uint32_t)l, make_typed(env, napi_float32_array, j->kernel[l], (size_t)j->units[l] * (size_t)j->units[l + 1], sizeof(float)));
+            napi_set_element(env, ba, (uint32_t)l, make_typed(env, napi_float32_array, j->bias[l], (size_t)j->units[l + 1], sizeof(float)));
+        }
+        napi_set_named_property(env, o, "kernels", ka); napi_set_named_property(env, o, "biases", ba);
+        napi_set_named_property(env, o, "history", make_typed(env, napi_float64_array, j->history, (size_t)j->epochs * 4, sizeof(double)));
+        napi_resolve_deferred(env, j->deferred, o);
+    }
+    if (j->on_epoch) napi_delete_reference(env, j->on_epoch);
+    napi_release_threadsafe_function(j->tsfn, napi_tsfn_release);
+    train_job_free(j);
+}
+static int num_of(napi_env env, napi_value o, const char *name, double *out) {
+    napi_value v; napi_valuetype t;
+    return napi_get_named_property(env, o, name, &v) == napi_ok && napi_typeof(env, v, &t) == napi_ok && t == napi_number && napi_get_value_double(env, v, out) == napi_ok;
+}
+static void *dup_bytes(const void *p, size_t bytes) { void *q = malloc(bytes ? bytes : 1); if (q && bytes) memcpy(q, p, bytes); return q; }
+static napi_value fn_train(napi_env env, napi_callback_info info) {
+    size_t argc = 4; napi_value argv[4];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ctx_box *box = argc ? get_box(env, argv[0]) : NULL;
+    const char *usage = "train(ctx, {units, activation, kernels, biases, inMin, inMax}, {features: Float64Array, y: Int32Array, nVal, batchSize, learningRate, epochs, orders?: Uint32Array}, onEpoch?)";
+    if (!box || !box->ctx || argc < 3) { napi_throw_type_error(env, NULL, usage); return NULL; }
+    int32_t *units = NULL, *act = NULL, *y = NULL; double *mn = NULL, *mx = NULL, *feat = NULL; uint32_t *orders = NULL;
+    size_t nu = 0, na = 0, nmn = 0, nmx = 0, nf = 0, ny = 0, no = 0;
+    double n_val = 0, batch = 0, lr = 0, epochs = 0;
+    if (!typed_of(env, argv[1], "units", napi_int32_array, (void **)&units, &nu) || !typed_of(env, argv[1], "activation", napi_int32_array, (void **)&act, &na) ||
+        !typed_of(env, argv[1], "inMin", napi_float64_array, (void **)&mn, &nmn) || !typed_of(env, argv[1], "inMax", napi_float64_array, (void **)&mx, &nmx) ||
+        nu < 2 || na != nu - 1 || na > WSA_MODEL_MAX_LAYERS || nmn != WSA_NFEAT || nmx != WSA_NFEAT ||
+        !typed_of(env, argv[2], "features", napi_float64_array, (void **)&feat, &nf) || !typed_of(env, argv[2], "y", napi_int32_array, (void **)&y, &ny) ||
+        ny < 1 || nf != ny * WSA_NFEAT || ny > 0xffffffffu ||
+        !num_of(env, argv[2], "nVal", &n_val) || !num_of(env, argv[2], "batchSize", &batch) || !num_of(env, argv[2], "learningRate", &lr) || !num_of(env, argv[2], "epochs", &epochs) ||
+        n_val < 0 || n_val >= (double)ny || batch < 0 || batch > 4294967295.0 || epochs < 1 || epochs > 1e6) { napi_throw_type_error(env, NULL, usage); return NULL; }
+    const uint32_t n_train = (uint32_t)ny - (uint32_t)n_val;
+    if (typed_of(env, argv[2], "orders", napi_uint32_array, (void **)&orders, &no) && no != (size_t)epochs * n_train) { napi_throw_type_error(env, NULL, "train: orders must hold epochs x (rows - nVal) indices"); return NULL; }
+    napi_value ka, ba; bool ia = false, ib = false; uint32_t nk = 0, nb = 0;
+    if (napi_get_named_property(env, argv[1], "kernels", &ka) != napi_ok || napi_is_array(env, ka, &ia) != napi_ok || !ia || napi_get_array_length(env, ka, &nk) != napi_ok ||
+        napi_get_named_property(env, argv[1], "biases", &ba) != napi_ok || napi_is_array(env, ba, &ib) != napi_ok || !ib || napi_get_array_length(env, ba, &nb) != napi_ok ||
+        nk != na || nb != na) { napi_throw_type_error(env, NULL, usage); return NULL; }
+    for (size_t l = 0; l <= na; l++) if (units[l] < 1 || units[l] > WSA_MODEL_MAX_WIDTH) { napi_throw_type_error(env, NULL, "train: layer widths are 1 .. 1024"); return NULL; }
+    train_job *j = calloc(1, sizeof *j);
+    if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    j->box = box; j->nl = (int32_t)na; j->n = (uint32_t)ny; j->n_val = (uint32_t)n_val; j->batch = (uint32_t)batch; j->epochs = (uint32_t)epochs; j->lr = lr;
+    memcpy(j->units, units, nu * sizeof(int32_t)); memcpy(j->act, act, na * sizeof(int32_t)); memcpy(j->mn, mn, sizeof j->mn); memcpy(j->mx, mx, sizeof j->mx);
+    bool ok = true;
+    for (uint32_t l = 0; l < na && ok; l++) {
+        napi_value kv, bv; bool t1 = false, t2 = false; napi_typedarray_type tk, tb; size_t lk = 0, lb = 0; void *dk = NULL, *db = NULL;
+        ok = napi_get_element(env, ka, l, &kv) == napi_ok && napi_is_typedarray(env, kv, &t1) == napi_ok && t1 && napi_get_typedarray_info(env, kv, &tk, &lk, &dk, NULL, NULL) == napi_ok &&
+             napi_get_element(env, ba, l, &bv) == napi_ok && napi_is_typedarray(env, bv, &t2) == napi_ok && t2 && napi_get_typedarray_info(env, bv, &tb, &lb, &db, NULL, NULL) == napi_ok &&
+             tk == napi_float32_array && tb == napi_float32_array && lk == (size_t)units[l] * (size_t)units[l + 1] && lb == (size_t)units[l + 1];
+        if (ok) { j->kernel[l] = dup_bytes(dk, lk * sizeof(float)); j->bias[l] = dup_bytes(db, lb * sizeof(float)); ok = j->kernel[l] && j->bias[l]; }
+    }
+    if (!ok) { train_job_free(j); napi_throw_type_error(env, NULL, "train: kernels[i] must be a Float32Array of units[i] x units[i+1], biases[i] one of units[i+1]"); return NULL; }
+    j->feat = dup_bytes(feat, nf * sizeof(double)); j->y = dup_bytes(y, ny * sizeof(int32_t)); j->history = calloc((size_t)j->epochs * 4, sizeof(double));
+    if (orders) j->orders = dup_bytes(orders, no * sizeof(uint32_t));
+    if (!j->feat || !j->y || !j->history || (orders && !j->orders)) { train_job_free(j); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    napi_valuetype ft = napi_undefined;
+    if (argc > 3 && napi_typeof(env, argv[3], &ft) == napi_ok && ft == napi_function && napi_create_reference(env, argv[3], 1, &j->on_epoch) != napi_ok) j->on_epoch = NULL;
+    napi_value promise, name;
+    if (napi_create_promise(env, &j->deferred, &promise) != napi_ok || napi_create_string_utf8(env, "wsa_train", NAPI_AUTO_LENGTH, &name) != napi_ok ||
+        napi_create_threadsafe_function(env, NULL, NULL, name, 0, 1, NULL, NULL, NULL, train_call_js, &j->tsfn) != napi_ok) {
+        if (j->on_epoch) napi_delete_reference(env, j->on_epoch);
+        train_job_free(j); napi_throw_error(env, NULL, "train: could not set up the job"); return NULL;
+    }
+    box->children++;                                             /* until the run's last message: destroy() refuses meanwhile */
+    if (pthread_create(&j->thread, NULL, train_thread, j) != 0) {
+        box->children--; napi_release_threadsafe_function(j->tsfn, napi_tsfn_release);
+        if (j->on_epoch) napi_delete_reference(env, j->on_epoch);
+        napi_value msg; napi_create_string_utf8(env, "train: could not start a thread", NAPI_AUTO_LENGTH, &msg); napi_reject_deferred(env, j->deferred, msg);
+        train_job_free(j);
+    }
+    return promise;
+}
+
 NAPI_MODULE_INIT() {
     /* the structures below follow the header this file was compiled against: refuse a libwsa.so of another ABI version */
     if (wsa_abi_version() != WSA_ABI_VERSION) { napi_throw_error(env, NULL, "libwsa.so ABI version differs from the one wsa_napi.node was built against (include/wsa.h): rebuild"); return NULL; }
@@ -1006,7 +1144,7 @@ NAPI_MODULE_INIT() {
         {"abiVersion", fn_abi_version}, {"freePinned", fn_free_pinned}, {"defaults", fn_defaults}, {"create", fn_create}, {"destroy", fn_destroy},
         {"geometry", fn_geometry}, {"allocPinned", fn_alloc_pinned}, {"binsHz", fn_bins_hz}, {"processBatch", fn_process_batch}, {"gatherRows", fn_gather_rows},
         {"streamOpen", fn_stream_open}, {"streamOpenMixed", fn_stream_open_mixed}, {"streamInfo", fn_stream_info}, {"streamPaced", fn_stream_paced}, {"streamInput", fn_stream_input}, {"streamStep", fn_stream_step}, {"streamClose", fn_stream_close}, {"streamSetModel", fn_stream_set_model}, {"streamSetEnsemble", fn_stream_set_ensemble},
-        {"modelCreate", fn_model_create}, {"modelDestroy", fn_model_destroy}};
+        {"modelCreate", fn_model_create}, {"modelDestroy", fn_model_destroy}, {"train", fn_train}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

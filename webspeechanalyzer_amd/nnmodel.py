@@ -98,3 +98,46 @@ def load_dir(path):
     paths = [p for g in mj.get("weightsManifest", []) for p in g.get("paths", [])] or ["model.weights.bin"]
     data = b"".join(open(os.path.join(path, os.path.basename(p)), "rb").read() for p in paths)
     return parse(mj, meta, data)
+
+
+def save_dir(spec, path):
+    """Writes model.json, model_meta.json and model.weights.bin as ml5 0.6.0's neuralNetwork.save does (download_nn_model of
+    src/neuralmodel.js), in the key layout of the directories the app ships: load_dir reads them back bit for bit, and ml5's
+    neuralNetwork.load takes them."""
+    nl = len(spec.kernels)
+    if len(spec.labels) != spec.units[-1]:
+        raise ModelFormatError(f"{len(spec.labels)} legend labels for {spec.units[-1]} outputs")
+    layers, weights, blob = [], [], []
+    for i in range(nl):
+        name = f"dense_Dense{i + 1}"
+        cfg = {"units": int(spec.units[i + 1]), "activation": spec.activations[i], "use_bias": True,
+               "kernel_initializer": {"class_name": "VarianceScaling", "config": {"scale": 1, "mode": "fan_avg", "distribution": "normal", "seed": None}},
+               "bias_initializer": {"class_name": "Zeros", "config": {}},
+               "kernel_regularizer": None, "bias_regularizer": None, "activity_regularizer": None, "kernel_constraint": None, "bias_constraint": None,
+               "name": name, "trainable": True}
+        if i == 0:
+            cfg.update(batch_input_shape=[None, int(spec.units[0])], dtype="float32")
+        layers.append({"class_name": "Dense", "config": cfg})
+        k = np.ascontiguousarray(spec.kernels[i], "<f4")
+        b = np.ascontiguousarray(spec.biases[i], "<f4")
+        if k.shape != (spec.units[i], spec.units[i + 1]) or b.shape != (spec.units[i + 1],):
+            raise ModelFormatError(f"layer {i}: kernel {k.shape} / bias {b.shape} do not match units {spec.units}")
+        weights += [{"name": name + "/kernel", "shape": list(k.shape), "dtype": "float32"}, {"name": name + "/bias", "shape": list(b.shape), "dtype": "float32"}]
+        blob += [k.tobytes(), b.tobytes()]
+    mj = {"modelTopology": {"class_name": "Sequential", "config": {"name": "sequential_1", "layers": layers},
+                            "keras_version": "tfjs-layers 1.7.2", "backend": "tensor_flow.js"},
+          "weightsManifest": [{"paths": ["./model.weights.bin"], "weights": weights}]}
+    labels = [str(x) for x in spec.labels]
+    C = len(labels)
+    meta = {"inputUnits": [int(spec.units[0])], "outputUnits": C,
+            "inputs": {str(i): {"dtype": "number", "min": float(spec.in_min[i]), "max": float(spec.in_max[i])} for i in range(int(spec.units[0]))},
+            "outputs": {"y": {"dtype": "string", "min": 0, "max": 1, "uniqueValues": labels,
+                              "legend": {lab: [1 if c == j else 0 for c in range(C)] for j, lab in enumerate(labels)}}},
+            "isNormalized": True}
+    os.makedirs(path, exist_ok=True)
+    with open(os.path.join(path, "model.json"), "w") as f:
+        json.dump(mj, f)
+    with open(os.path.join(path, "model_meta.json"), "w") as f:
+        json.dump(meta, f)
+    with open(os.path.join(path, "model.weights.bin"), "wb") as f:
+        f.write(b"".join(blob))

@@ -1,0 +1,114 @@
+"""Training the app's syllable classifiers (specification TR-1, K7): what src/neuralmodel.js:163-403 (train_nn) does around
+ml5.neuralNetwork(...).train — selecting and balancing the stored level-13 rows, the input ranges, the initial weights and the
+per-epoch orders (both from numpy's generator: the reference draws them from Math.random, so they are ours) — and the epochs on the
+GPU through capi.Trainer.  Classification only: the regression models (ords_*) and the '*' wildcard class are not supported."""
+import math
+
+import numpy as np
+
+from . import nnmodel
+
+DEFAULT_LAYERS = [{"type": "dense", "units": 8, "activation": "relu"}, {"type": "dense", "activation": "softmax"}]   # src/neuralmodel_aux.js:106-124
+DEFAULT_LEARNING_RATE = 0.2
+
+
+def prepare(features, labels, classes):
+    """The selection and balancing loop of neuralmodel.js:216-264.  features [n][53]; labels: per row the label's value or None;
+    classes: the label's class list.  Rows whose label is one of `classes` are added in DB order; fewer than 10 of them is refused;
+    then each class with more than 3 and fewer than the largest count is topped up by cycling through the DB in order until it
+    reaches that count.  Returns dict(features, y, legend, in_min, in_max, counts, rows): y are indices into legend, which lists the
+    labels in order of first appearance (ml5's uniqueValues); in_min / in_max are taken over the balanced set, duplicates included
+    (ml5 normalizeData); rows are the DB indices in the order added."""
+    classes = [str(c) for c in classes]
+    if "*" in classes:
+        raise ValueError("the '*' wildcard class is not supported")
+    feat = np.asarray(features, np.float64)
+    if feat.ndim != 2 or feat.shape[1] != nnmodel.NFEAT or len(labels) != len(feat):
+        raise ValueError(f"features {feat.shape} / {len(labels)} labels: expected [n][{nnmodel.NFEAT}] and n labels")
+    cls = [classes.index(str(v)) if v is not None and str(v) in classes else -1 for v in labels]
+    rows = [i for i, c in enumerate(cls) if c >= 0]
+    count = [sum(1 for i in rows if cls[i] == c) for c in range(len(classes))]
+    if len(rows) < 10:
+        raise ValueError(f"Sample size {len(rows)}/{len(feat)} too small for training")
+    max_n = max(count)
+    for c in range(len(classes)):
+        while 3 < count[c] < max_n:
+            for i in range(len(feat)):
+                if cls[i] == c and count[c] < max_n:
+                    rows.append(i); count[c] += 1
+                if count[c] >= max_n:
+                    break
+    legend = []
+    for i in rows:
+        if classes[cls[i]] not in legend:
+            legend.append(classes[cls[i]])
+    x = feat[rows]
+    y = np.array([legend.index(classes[cls[i]]) for i in rows], np.int32)
+    return dict(features=x, y=y, legend=legend, in_min=x.min(axis=0), in_max=x.max(axis=0), counts=count, rows=rows)
+
+
+def glorot_init(units, seed):
+    """tfjs's default Dense initialisers with numpy's generator: kernels truncated normal (redrawn beyond two standard deviations) with
+    standard deviation sqrt(2 / (fan_in + fan_out)), zero biases."""
+    rng = np.random.default_rng(seed)
+    ks, bs = [], []
+    for i in range(len(units) - 1):
+        std = math.sqrt(2.0 / (units[i] + units[i + 1]))
+        w = rng.standard_normal((units[i], units[i + 1]))
+        while True:
+            bad = np.abs(w) > 2.0
+            if not bad.any():
+                break
+            w[bad] = rng.standard_normal(int(bad.sum()))
+        ks.append((w * std).astype(np.float32)); bs.append(np.zeros(units[i + 1], np.float32))
+    return ks, bs
+
+
+def epoch_orders(n_train, epochs, seed):
+    """One permutation of the training rows per epoch (tfjs shuffles the training indices every epoch)."""
+    rng = np.random.default_rng(seed)
+    return [rng.permutation(n_train).astype(np.uint32) for _ in range(epochs)]
+
+
+def split(n, validation_split=0.1):
+    """(n_train, n_val) as tfjs's fit splits: the last n - floor(n (1 - validationSplit)) rows are validation."""
+    n_train = int(math.floor(n * (1 - validation_split)))
+    return n_train, n - n_train
+
+
+def stack(layers, n_classes):
+    """(units, activations) of the app's options JSON `layers`; the last layer's units are the number of classes."""
+    units, acts = [nnmodel.NFEAT], []
+    for i, l in enumerate(layers):
+        if l.get("type", "dense") != "dense":
+            raise ValueError(f"layer {i} is {l.get('type')!r}; only dense layers are supported")
+        units.append(n_classes if i == len(layers) - 1 else int(l["units"]))
+        acts.append(l.get("activation", "linear"))
+    if acts[-1] != "softmax":
+        raise ValueError("training needs a softmax output layer")
+    return units, acts
+
+
+def train(an, data, layers=None, learning_rate=DEFAULT_LEARNING_RATE, epochs=10, batch_size=32, validation_split=0.1, seed=0,
+          init=None, orders=None, on_epoch=None, stream=0):
+    """Trains on `an` (a capi.Analyzer) over data = prepare(...).  init: (kernels, biases) instead of glorot_init(units, seed); orders:
+    one order per epoch instead of epoch_orders(n_train, epochs, seed + 1).  on_epoch(epoch, stats) mirrors ml5's whileTraining (it
+    synchronises every epoch; without it only the last epoch is waited for).  Returns (nnmodel.ModelSpec, history)."""
+    units, acts = stack(layers or DEFAULT_LAYERS, len(data["legend"]))
+    ks, bs = init if init is not None else glorot_init(units, seed)
+    n_train, n_val = split(len(data["features"]), validation_split)
+    orders = orders if orders is not None else epoch_orders(n_train, epochs, seed + 1)
+    spec = nnmodel.ModelSpec(units, acts, ks, bs, np.asarray(data["in_min"], np.float64), np.asarray(data["in_max"], np.float64), list(data["legend"]))
+    tr = an.trainer(spec, data["features"], data["y"], n_val, batch_size, learning_rate)
+    try:
+        history = []
+        for e in range(epochs):
+            tr.epoch(orders[e], stream)
+            if on_epoch is not None or e == epochs - 1:
+                st = tr.stats(stream)
+                history.append(st)
+                if on_epoch is not None:
+                    on_epoch(e, st)
+        return tr.spec_now(stream), history
+    finally:
+        tr.close()
