@@ -147,6 +147,9 @@ void       wsa_host_free(void *p);
  * link busy that way) — where runs on NULL, the device's null stream, queue up behind each other.  Destroy a queue only when nothing runs on it. */
 wsa_status wsa_queue_create(wsa_ctx *ctx, void **stream);
 void       wsa_queue_destroy(wsa_ctx *ctx, void *stream);
+/* Waits for everything enqueued on `stream` (NULL: the device's null stream) — for hosts without a HIP binding that call an entry which
+ * only enqueues and hands out no copy of its own, such as wsa_regress_rows on page-locked rows (probe for it: an addition within version 5). */
+wsa_status wsa_queue_synchronize(wsa_ctx *ctx, void *stream);
 
 /*
  * Results of the last run (device resident, compacted in (clip, si[, syllable]) order — the order
@@ -625,6 +628,44 @@ wsa_status wsa_trainer_copy_weights(wsa_trainer *t, void *stream, float *const *
 /* a snapshot of the current weights as a model every wsa_*classify* entry point takes (the caller destroys it); synchronises */
 wsa_status wsa_trainer_model(wsa_trainer *t, void *stream, wsa_model **out);
 void       wsa_trainer_destroy(wsa_trainer *t);
+
+/*
+ * ---- Regression models (additions within version 5: probe for wsa_regress_trainer_create).
+ * The app's other kind of model, dist/nnmodel/<db>/ords_<label>/ for the ordinal labels V, A and D: ref src/neuralmodel.js:268-333
+ * (train_nn, ordinal branch) with nn_default_options_ords (src/neuralmodel_aux.js:127-150: task "regression", 64 sigmoid / 16 sigmoid /
+ * 1 sigmoid, learningRate 0.2).  In dist/ml5.min.js `compile` @2770937 gives a regression task meanSquaredError,
+ * tf.train.adam(learningRate) (tfjs 1.7.2 AdamOptimizer.applyGradients @548581) and ["accuracy"], which tfjs resolves to binaryAccuracy
+ * for a one-unit output; ml5 normalises the output `y` to (y - min) / (max - min) (normalizeData) and un-normalises every prediction,
+ * t * (max - min) + min (unnormalizeValue @2469277), with model_meta.json's outputs.y.{min,max}.  One run is the deterministic function
+ * TR-2 of DESIGN.md, pinned to tfjs by tests/golden/regress_expected.json.
+ * A regression model is an ordinary wsa_model whose last layer has ONE unit and is linear, relu, sigmoid or tanh; wsa_model_desc is
+ * unchanged and the output range travels as arguments.  Every entry refuses (WSA_ERR_INVALID with a message) more than one output
+ * unit, a softmax last layer, non-finite out_min / out_max and out_max == out_min.
+ * No fold and no per-callback decision: the reference's live path with an ords model sums the `confidence` fields a regression result
+ * does not have (ref src/prediction.js:96-101: undefined, so NaN) and defines nothing worth restating.  Streams take no regression model.
+ */
+/* K6 with the un-normalising epilogue on device rows (ref src/neuralmodel.js:540-585 predict_single -> predictMultiple; :410-535
+ * predict_db_nn -> result_out[0].value): d_feat [n_rows][WSA_NFEAT] f64 -> d_value [n_rows] f64 = (double)p * (out_max - out_min) +
+ * out_min, p the f32 output of the one unit, the product and the sum rounded separately.  Asynchronous on `stream`; allocates nothing. */
+wsa_status wsa_regress_rows(const wsa_model *m, double out_min, double out_max,
+                            const double *d_feat, uint32_t n_rows, double *d_value, void *stream);
+/* The same on the rows of the batch's last run: levels 5 and 13; one value per row in the order of wsa_device_result's tables, equal bit
+ * for bit to wsa_regress_rows over d_feat.  Only enqueues; after the first call on a batch nothing is allocated.  Also refuses a model
+ * of another context.  A batch keeps ONE last model call: after this one wsa_batch_class_result is refused, and the other way round. */
+wsa_status wsa_batch_regress(wsa_batch *b, const wsa_model *m, double out_min, double out_max, void *stream);
+/* Synchronises `stream`; *n_rows (may be NULL) = the rows of the last run, value (may be NULL) [rows_cap] their values.
+ * WSA_ERR_INVALID if rows_cap is too small or the batch's last model call was not wsa_batch_regress. */
+wsa_status wsa_batch_copy_values(wsa_batch *b, void *stream, double *value, uint32_t rows_cap, uint32_t *n_rows);
+/* wsa_trainer_create for a regression model (ref src/neuralmodel.js:268-333 -> ml5 neuralNetwork.train, task "regression"):
+ * target: host [n_rows] double, the label's values; out_min / out_max the range they are normalised with.  Returns the same
+ * wsa_trainer: wsa_trainer_epoch, _stats (loss = mean squared error of the normalised output; acc = tfjs's binaryAccuracy, the app
+ * prints both), _copy_weights, _model (a model for wsa_regress_rows / wsa_batch_regress) and _destroy work on it unchanged.  Adam's
+ * two moments and accumulated betas live on the device for the life of the trainer and are carried from epoch to epoch; an epoch is
+ * still only enqueued.  Refuses, beside the above and everything wsa_trainer_create refuses but the softmax rule and the labels: a
+ * target that is not finite, or whose normalised value is not finite as an f32. */
+wsa_status wsa_regress_trainer_create(wsa_ctx *ctx, const wsa_model_desc *init, const double *feat,
+                                      const double *target, uint32_t n_rows, uint32_t n_val, uint32_t batch_size,
+                                      double learning_rate, double out_min, double out_max, wsa_trainer **out);
 
 #ifdef __cplusplus
 }

@@ -155,7 +155,9 @@ ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destr
                "wsa_stream_create_mixed", "wsa_stream_input_capacity", "wsa_stream_input_stride", "wsa_stream_paced_input", "wsa_stream_step_frame_capacity",
                "wsa_stream_step_n", "wsa_stream_step_host_n", "wsa_resample_ready", "wsa_stream_frames_bound", "wsa_stream_copy_converted",
                # additions within version 5 (probe for wsa_trainer_create): training the app's classifiers (K7, spec TR-1)
-               "wsa_trainer_create", "wsa_trainer_destroy", "wsa_trainer_epoch", "wsa_trainer_stats", "wsa_trainer_copy_weights", "wsa_trainer_model"]
+               "wsa_trainer_create", "wsa_trainer_destroy", "wsa_trainer_epoch", "wsa_trainer_stats", "wsa_trainer_copy_weights", "wsa_trainer_model",
+               # additions within version 5 (probe for wsa_regress_trainer_create): the app's regression models (ords_*, spec TR-2)
+               "wsa_regress_rows", "wsa_batch_regress", "wsa_batch_copy_values", "wsa_regress_trainer_create", "wsa_queue_synchronize"]
 
 _LIB = None
 _U32_RESULT = ("wsa_stream_input_capacity", "wsa_stream_paced_input", "wsa_stream_input_stride", "wsa_stream_step_frame_capacity", "wsa_stream_frames_bound")
@@ -274,6 +276,11 @@ def lib():
     L.wsa_trainer_stats.argtypes = [vp, vp, ctypes.POINTER(_TrainStats)]
     L.wsa_trainer_copy_weights.argtypes = [vp, vp, vp, vp]
     L.wsa_trainer_model.argtypes = [vp, vp, ctypes.POINTER(vp)]
+    L.wsa_queue_synchronize.argtypes = [vp, vp]
+    L.wsa_regress_rows.argtypes = [vp, dbl, dbl, vp, u32, vp, vp]
+    L.wsa_batch_regress.argtypes = [vp, vp, dbl, dbl, vp]
+    L.wsa_batch_copy_values.argtypes = [vp, vp, vp, u32, ctypes.POINTER(u32)]
+    L.wsa_regress_trainer_create.argtypes = [vp, ctypes.POINTER(_ModelDesc), vp, vp, u32, u32, u32, dbl, dbl, dbl, ctypes.POINTER(vp)]
     for name in ABI_SYMBOLS:
         if name in _U32_RESULT or name == "wsa_resample_ready":
             continue
@@ -357,6 +364,12 @@ class Analyzer:
     def trainer(self, spec, features, labels, n_val, batch_size, learning_rate):
         """K7 on this context: SGD from the weights of `spec` over host rows (see Trainer; webspeechanalyzer_amd.train drives it)."""
         return Trainer(self, spec, features, labels, n_val, batch_size, learning_rate)
+
+    def regress_trainer(self, spec, features, values, n_val, batch_size, learning_rate, out_min=None, out_max=None):
+        """K7 on this context for a regression model (spec TR-2): Adam on the mean squared error from the weights of `spec` over host rows
+        and their real-valued targets; the range defaults to spec.out_min / spec.out_max (webspeechanalyzer_amd.train drives it)."""
+        return Trainer(self, spec, features, values, n_val, batch_size, learning_rate,
+                       regression=(spec.out_min if out_min is None else out_min, spec.out_max if out_max is None else out_max))
 
     def ensemble(self, models):
         """The app's `available_DBs` on this context: a list of 1 .. 8 Models in that order (every tie between DBs goes to the earlier one)."""
@@ -581,6 +594,21 @@ class Batch:
                                                       max(k, 1), clip.ctypes.data if r.d_clip_conf else None))
         return dict(prob=prob, cb=cb, cb_label=lab, cb_conf=conf, clip_conf=clip, labels=list(self._model.labels))
 
+    def regress(self, model, out_min=None, out_max=None, stream=0):
+        """K6 with the un-normalising epilogue on the rows of the last run, enqueued on `stream` (wsa_batch_regress); the range defaults
+        to the model's own (spec.out_min / spec.out_max)."""
+        lo, hi = model.out_range(out_min, out_max)
+        self.an._check(self.L.wsa_batch_regress(self.h, model.h, lo, hi, stream))
+        self._model = model
+
+    def values(self, stream=0):
+        """Host copy of the last regress: [n_rows] f64, one value per row in the order of rows()."""
+        n = ctypes.c_uint32()
+        self.an._check(self.L.wsa_batch_copy_values(self.h, stream, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, np.float64)
+        self.an._check(self.L.wsa_batch_copy_values(self.h, stream, out.ctypes.data, max(n.value, 1), ctypes.byref(n)))
+        return out
+
     def classify_ensemble(self, ensemble, stream=0):
         """K6e (+ K6b-e and the cross-DB decision at level 13) on the rows of the last run, enqueued on `stream` (wsa_batch_classify_ensemble)."""
         self.an._check(self.L.wsa_batch_classify_ensemble(self.h, ensemble.h, stream))
@@ -664,6 +692,20 @@ class Model:
         """K6 on device rows: d_feat [n_rows][53] f64 -> d_prob [n_rows][n_classes] f32 (device pointers, asynchronous on `stream`)."""
         self.an._check(self.L.wsa_classify_rows(self.h, d_feat, int(n_rows), d_prob, stream))
 
+    def out_range(self, out_min=None, out_max=None):
+        """(out_min, out_max) as floats: the arguments, else the spec's own; a model without a range and no arguments is refused"""
+        lo = getattr(self.spec, "out_min", None) if out_min is None else out_min
+        hi = getattr(self.spec, "out_max", None) if out_max is None else out_max
+        if lo is None or hi is None:
+            raise ValueError("the model has no output range (out_min / out_max): not a regression model's spec, and none was given")
+        return float(lo), float(hi)
+
+    def regress_rows(self, d_feat, n_rows, d_value, out_min=None, out_max=None, stream=0):
+        """K6 with the un-normalising epilogue on device rows: d_feat [n_rows][53] f64 -> d_value [n_rows] f64 (device pointers,
+        asynchronous on `stream`); the range defaults to the spec's own."""
+        lo, hi = self.out_range(out_min, out_max)
+        self.an._check(self.L.wsa_regress_rows(self.h, lo, hi, d_feat, int(n_rows), d_value, stream))
+
     def close(self):
         if self.h:
             self.L.wsa_model_destroy(self.h)
@@ -680,17 +722,23 @@ class Trainer:
     """wsa_trainer: minibatch SGD on the app's Dense classifiers (K7, spec TR-1).  `spec` holds the INITIAL weights, the ranges to
     normalise with and the legend; features [n][53] f64 and labels [n] class indices are host arrays, the last n_val rows validation."""
 
-    def __init__(self, an, spec, features, labels, n_val, batch_size, learning_rate):
+    def __init__(self, an, spec, features, labels, n_val, batch_size, learning_rate, regression=None):
+        """regression: None, or (out_min, out_max): `labels` are then real-valued targets and the trainer is TR-2's (Adam, mean squared error)"""
         self.an, self.L, self.spec = an, an.L, spec
+        self.out_range = None if regression is None else (float(regression[0]), float(regression[1]))
         feat = np.ascontiguousarray(features, np.float64)
-        lab = np.ascontiguousarray(labels, np.int32)
+        lab = np.ascontiguousarray(labels, np.int32 if regression is None else np.float64)
         if feat.ndim != 2 or feat.shape[1] != 53 or lab.shape != (feat.shape[0],):
             raise ValueError(f"features {feat.shape} / labels {lab.shape}: expected [n][53] and [n]")
         self.n_rows, self.n_val, self.n_train = feat.shape[0], int(n_val), feat.shape[0] - int(n_val)
         d, keep = _model_desc(spec)
         self.h = ctypes.c_void_p()
-        an._check(self.L.wsa_trainer_create(an.h, ctypes.byref(d), feat.ctypes.data, lab.ctypes.data, feat.shape[0], int(n_val), int(batch_size),
-                                            float(learning_rate), ctypes.byref(self.h)))
+        if regression is None:
+            an._check(self.L.wsa_trainer_create(an.h, ctypes.byref(d), feat.ctypes.data, lab.ctypes.data, feat.shape[0], int(n_val), int(batch_size),
+                                                float(learning_rate), ctypes.byref(self.h)))
+        else:
+            an._check(self.L.wsa_regress_trainer_create(an.h, ctypes.byref(d), feat.ctypes.data, lab.ctypes.data, feat.shape[0], int(n_val),
+                                                        int(batch_size), float(learning_rate), self.out_range[0], self.out_range[1], ctypes.byref(self.h)))
         del keep
 
     def epoch(self, order=None, stream=0):
@@ -721,12 +769,17 @@ class Trainer:
         from . import nnmodel
         ks, bs = self.weights(stream)
         s = self.spec
-        return nnmodel.ModelSpec(list(s.units), list(s.activations), ks, bs, np.array(s.in_min, np.float64), np.array(s.in_max, np.float64), list(s.labels))
+        out = nnmodel.ModelSpec(list(s.units), list(s.activations), ks, bs, np.array(s.in_min, np.float64), np.array(s.in_max, np.float64), list(s.labels))
+        if self.out_range is not None:
+            out.out_min, out.out_max = self.out_range
+        return out
 
     def model(self, stream=0):
         """A snapshot of the current weights as a Model on the same context (wsa_trainer_model)."""
         m = Model.__new__(Model)
         m.an, m.L, m.spec = self.an, self.L, self.spec
+        if self.out_range is not None:
+            m.spec = self.spec_now(stream)
         m.labels, m.n_classes, m._keep = list(self.spec.labels), self.spec.n_classes, None
         m.h = ctypes.c_void_p()
         self.an._check(self.L.wsa_trainer_model(self.h, stream, ctypes.byref(m.h)))

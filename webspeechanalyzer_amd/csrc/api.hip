@@ -61,7 +61,7 @@ struct wsa_batch {
     const uint32_t* spec_in_use = nullptr;
     wsa_cls* cls = nullptr;                 // wsa_batch_classify (classify.hip)
     wsa_ecls* ecls = nullptr;               // wsa_batch_classify_ensemble (classify.hip)
-    int cls_last = 0;                       // which of the two the last classification was (1 / 2): their results stay apart
+    int cls_last = 0;                       // which the last classification was (1 / 2; 3: wsa_batch_regress): their results stay apart
 };
 
 namespace wsa {
@@ -644,6 +644,12 @@ wsa_status wsa_queue_create(wsa_ctx* ctx, void** stream) {
     hipStream_t s = nullptr;
     HIP_TRY(ctx, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     *stream = s;
+    return WSA_OK;
+}
+wsa_status wsa_queue_synchronize(wsa_ctx* ctx, void* stream) {
+    if (!ctx) return WSA_ERR_INVALID;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
     return WSA_OK;
 }
 void wsa_queue_destroy(wsa_ctx* ctx, void* stream) {

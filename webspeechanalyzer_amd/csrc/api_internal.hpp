@@ -29,7 +29,7 @@ struct wsa_batch_view {
     const int32_t* d_meta; const double* d_feat; const uint32_t* d_row_off;     // compacted rows, d_row_off[n_clips] = rows on the device
     uint32_t reruns;                                                            // wsa_batch_backend_reruns
     wsa_cls** cls; wsa_ecls** ecls;
-    int* cls_last;                                                              // 1: the last classification was one model's, 2: an ensemble's
+    int* cls_last;                                                              // 1: the last classification was one model's, 2: an ensemble's, 3: wsa_batch_regress
 };
 extern "C" {
 void wsa_batch_view_internal(wsa_batch* b, wsa_batch_view* v);

@@ -23,7 +23,16 @@ struct ClsParams {
     const double* in_min; const double* in_max;
     const double* feat; uint32_t n_rows; const uint32_t* d_n_rows;           // rows = *d_n_rows when set (a batch's count, on the device)
     float* prob;
+    double* value; double out_min, out_span;                                 // value != NULL: a regression model, one f64 per row instead of prob
 };
+
+// ml5 unnormalizeValue on the f32 output of a regression model's one unit (ref dist/ml5.min.js @2469277, t * (max - min) + min with
+// JavaScript doubles): the product and the sum are rounded separately, JavaScript has no fused multiply-add
+__device__ __forceinline__ double unnormalise_value(float p, double out_min, double out_span) {
+#pragma clang fp contract(off)
+    const double scaled = (double)p * out_span;
+    return scaled + out_min;
+}
 
 __device__ __forceinline__ float activate(float v, int act) {
     switch (act) {
@@ -103,6 +112,10 @@ __device__ __forceinline__ void classify_tile(const ClsParams& p, float* s_act, 
         for (int r = tid; r < TM; r += CLS_THREADS) {
             if (row0 + r >= n) continue;
             const float* x = in + r * S;
+            if (p.value) {                                                  // K6's regression epilogue: the one unit's output, un-normalised
+                p.value[row0 + r] = unnormalise_value(x[0], p.out_min, p.out_span);
+                continue;
+            }
             float* o = p.prob + (size_t)(row0 + r) * p.C;
             if (sm) {
                 float m = x[0];
@@ -629,6 +642,7 @@ struct wsa_cls {
     uint32_t *h_count = nullptr, *h_count_dev = nullptr;     // pinned + mapped: callbacks of the last fold
     wsa::DevArena mem;
     const wsa_model* model = nullptr; int level = 0, n_classes = 0; uint32_t reruns = 0; bool done = false;
+    double* d_value = nullptr; double out_min = 0.0, out_span = 0.0;      // wsa_batch_regress: one value per row
 };
 
 struct wsa_ensemble {
@@ -691,8 +705,7 @@ ClsParams cls_params(const wsa_model* m, const double* feat, uint32_t n_rows, co
 
 // rows_cap sizes the grid (one workgroup per tile up to one per CU; the kernel strides over tiles beyond); rb = 16-row blocks per tile
 // (the model's own choice for batches; streams pass 1).  A row's probabilities do not depend on the tile it lands in.
-void launch_classify(const wsa_model* m, const double* feat, uint32_t n_rows, const uint32_t* d_n_rows, uint32_t rows_cap, float* prob, hipStream_t s, int rb = 0) {
-    const ClsParams p = cls_params(m, feat, n_rows, d_n_rows, prob);
+void launch_classify(const wsa_model* m, const ClsParams& p, uint32_t rows_cap, hipStream_t s, int rb = 0) {
     if (rb <= 0 || rb > m->rb) rb = m->rb;
     const int TM = 16 * rb;
     int n_cu = m->ctx->n_cu > 0 ? m->ctx->n_cu : 256;
@@ -704,8 +717,34 @@ void launch_classify(const wsa_model* m, const double* feat, uint32_t n_rows, co
     else hipLaunchKernelGGL(classify_kernel<1>, dim3(grid), dim3(CLS_THREADS), lds, s, p);
 }
 
+void launch_classify(const wsa_model* m, const double* feat, uint32_t n_rows, const uint32_t* d_n_rows, uint32_t rows_cap, float* prob, hipStream_t s, int rb = 0) {
+    launch_classify(m, cls_params(m, feat, n_rows, d_n_rows, prob), rows_cap, s, rb);
+}
+
+// the same launch with the regression epilogue: value [rows] f64 = the one output unit, un-normalised with the caller's range
+void launch_regress(const wsa_model* m, const double* feat, uint32_t n_rows, const uint32_t* d_n_rows, uint32_t rows_cap, double* value,
+                    double out_min, double out_span, hipStream_t s) {
+    ClsParams p = cls_params(m, feat, n_rows, d_n_rows, nullptr);
+    p.value = value; p.out_min = out_min; p.out_span = out_span;
+    launch_classify(m, p, rows_cap, s);
+}
+
+// what every regression entry point refuses (all WSA_ERR_INVALID); NULL when the model and the range will do
+const char* regress_refusal(const wsa_model* m, double out_min, double out_max) {
+    if (m->softmax) return "a regression model's last layer is linear, relu, sigmoid or tanh, not softmax";
+    if (m->C != 1) return "a regression model has one output unit";
+    if (!std::isfinite(out_min) || !std::isfinite(out_max)) return "non-finite out_min / out_max";
+    if (out_max == out_min) return "the output has max == min: it cannot be un-normalised";
+    return nullptr;
+}
+
 wsa_status enqueue_batch(wsa_batch* b, const wsa_batch_view& v, wsa_cls* c, const wsa_model* m, hipStream_t s) {
     wsa_ctx* ctx = v.ctx;
+    if (*v.cls_last == 3) {                       // wsa_batch_regress: no fold, no per-callback decision
+        launch_regress(m, v.d_feat, 0, v.d_row_off + v.n_clips, v.rows_cap, c->d_value, c->out_min, c->out_span, s);
+        HIP_TRY(ctx, hipGetLastError());
+        return WSA_OK;
+    }
     launch_classify(m, v.d_feat, 0, v.d_row_off + v.n_clips, v.rows_cap, c->d_prob, s);
     HIP_TRY(ctx, hipGetLastError());
     if (v.level == 13) {
@@ -1161,6 +1200,7 @@ wsa_status wsa_batch_class_result(wsa_batch* b, void* stream, wsa_class_result* 
     wsa_ctx* ctx = v.ctx;
     wsa_cls* c = *v.cls;
     if (!c || !c->done) return fail(ctx, WSA_ERR_INVALID, "no wsa_batch_classify on this batch yet");
+    if (*v.cls_last == 3) return fail(ctx, WSA_ERR_INVALID, "the batch's last model call was wsa_batch_regress: its values are wsa_batch_copy_values'");
     if (*v.cls_last != 1) return fail(ctx, WSA_ERR_INVALID, "the batch's last classification was an ensemble's: its tables are wsa_batch_ensemble_result's");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     wsa_status st = wsa_batch_fetch_internal(b, s);
@@ -1204,6 +1244,68 @@ wsa_status wsa_batch_copy_classes(wsa_batch* b, void* stream, float* prob, uint3
     }
     if (clip_conf && r.d_clip_conf && r.n_clips) HIP_TRY(ctx, hipMemcpyAsync(clip_conf, r.d_clip_conf, (size_t)r.n_clips * r.n_classes * sizeof(double), hipMemcpyDefault, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
+    return WSA_OK;
+}
+
+// ---- regression models (ords_<label>): K6 with the un-normalising epilogue (ref src/neuralmodel.js:410-585, predict_db_nn / predict_single)
+wsa_status wsa_regress_rows(const wsa_model* m, double out_min, double out_max, const double* d_feat, uint32_t n_rows, double* d_value, void* stream) {
+    if (!m) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = m->ctx;
+    if (const char* why = regress_refusal(m, out_min, out_max)) return fail(ctx, WSA_ERR_INVALID, why);
+    if (n_rows && (!d_feat || !d_value)) return fail(ctx, WSA_ERR_INVALID, "null feature / value pointer");
+    if (!n_rows) return WSA_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    launch_regress(m, d_feat, n_rows, nullptr, n_rows, d_value, out_min, out_max - out_min, reinterpret_cast<hipStream_t>(stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return WSA_OK;
+}
+
+wsa_status wsa_batch_regress(wsa_batch* b, const wsa_model* m, double out_min, double out_max, void* stream) {
+    if (!b || !m) return WSA_ERR_INVALID;
+    wsa_batch_view v;
+    wsa_batch_view_internal(b, &v);
+    wsa_ctx* ctx = v.ctx;
+    if (v.level != 5 && v.level != 13)
+        return fail(ctx, WSA_ERR_INVALID, "wsa_batch_regress needs a batch at output_level 5 (segment features) or 13 (syllable features), not " + std::to_string(v.level));
+    if (m->ctx != ctx) return fail(ctx, WSA_ERR_INVALID, "the model was created on another context (or device) than the batch");
+    if (const char* why = regress_refusal(m, out_min, out_max)) return fail(ctx, WSA_ERR_INVALID, why);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    wsa_cls*& c = *v.cls;
+    if (!c) { c = new wsa_cls(); c->device = ctx->device; c->cap_rows = v.rows_cap; c->n_clips = v.n_clips; }   // cap_c 0: a later classify builds its own tables
+    if (!c->d_value && !c->mem.alloc(&c->d_value, v.rows_cap ? v.rows_cap : 1))     // first call: the only allocation of this path
+        return fail(ctx, WSA_ERR_HIP, std::string("device allocation failed: ") + hipGetErrorString(hipGetLastError()));
+    *v.cls_last = 3;
+    c->model = m; c->level = v.level; c->n_classes = 1; c->reruns = v.reruns; c->done = true;
+    c->out_min = out_min; c->out_span = out_max - out_min;
+    return enqueue_batch(b, v, c, m, reinterpret_cast<hipStream_t>(stream));
+}
+
+wsa_status wsa_batch_copy_values(wsa_batch* b, void* stream, double* value, uint32_t rows_cap, uint32_t* n_rows) {
+    if (!b) return WSA_ERR_INVALID;
+    wsa_batch_view v;
+    wsa_batch_view_internal(b, &v);
+    wsa_ctx* ctx = v.ctx;
+    wsa_cls* c = *v.cls;
+    if (!c || !c->done || *v.cls_last != 3) return fail(ctx, WSA_ERR_INVALID, "the batch's last model call was not wsa_batch_regress");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    wsa_status st = wsa_batch_fetch_internal(b, s);
+    if (st != WSA_OK) return st;
+    wsa_batch_view_internal(b, &v);
+    if (v.reruns != c->reruns) {                  // the back end was rerun with the full tracker table: its rows again
+        c->reruns = v.reruns;
+        st = enqueue_batch(b, v, c, c->model, s);
+        if (st != WSA_OK) return st;
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    wsa_device_result r;
+    st = wsa_batch_result(b, stream, &r);
+    if (st != WSA_OK) return st;
+    if (n_rows) *n_rows = r.n_rows;
+    if (value && rows_cap < r.n_rows) return fail(ctx, WSA_ERR_INVALID, "value buffer too small");
+    if (value && r.n_rows) {
+        HIP_TRY(ctx, hipMemcpyAsync(value, c->d_value, (size_t)r.n_rows * sizeof(double), hipMemcpyDefault, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+    }
     return WSA_OK;
 }
 

@@ -11,6 +11,13 @@
 //                           W_l -= lr A[l]^T dZ_l, b_l -= lr 1^T dZ_l one wave per 16 x 16 tile of W_l: it owns the whole sum over the
 //                                                                    batch rows (ascending, four per MFMA) and applies the update
 // Every sum has one owner and one order, nothing is accumulated with atomics, so a run is reproducible bit for bit.
+//
+// The app's regression models (ords_<label>, specification TR-2: one output unit, tfjs meanSquaredError, tf.train.adam; ref
+// src/neuralmodel.js:268-333 and nn_default_options_ords, src/neuralmodel_aux.js:127-150) run the same chain with two kernels swapped:
+//   loss     train_loss_mse_kernel     per-row squared error and dZ_{L-1} = 2 (p - t) / b . act'(p) in double; its thread 0 also advances
+//                                      Adam's device-side step state (accumulated betas), so an epoch needs no host round trip
+//   update   train_update_adam_kernel  the same tile owner and the same ascending sum, then tfjs's AdamOptimizer.applyGradients on the
+//                                      owner's elements of w, m and v
 // mfma_f32_16x16x4f32 as in K6: lane l holds A[row l&15][k l>>4], B[k l>>4][col l&15]; D col = l&15, row = 4 (l>>4) + i.
 #include <cmath>
 #include <cstring>
@@ -183,12 +190,8 @@ __global__ void __launch_bounds__(TR_THREADS) train_backward_kernel(TrBack p) {
 // owns a tile sums over all batch rows in ascending order and writes the new weights; padded rows / columns stay zero.
 struct TrUpd { TrRows a; const float* dz; float* w; float* b; int kp, np, k, n; uint32_t mp; float lr; };
 
-__global__ void __launch_bounds__(TR_THREADS) train_update_kernel(TrUpd p) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t cbs = p.np / 16, kbs = p.kp / 16, tile = blockIdx.x * TR_WAVES + wave;
-    if (tile >= (kbs + 1) * cbs) return;
-    const uint32_t kb = tile / cbs; const int n0 = (tile % cbs) * 16, k0 = kb * 16;
-    const bool bias = kb == kbs;
+// the gradient tile a wave owns: sum over the batch rows of a[r][k0 + ..] dz[r][n0 + ..] (bias: of dz alone), rows ascending, four per MFMA
+__device__ __forceinline__ f32x4 tr_gradient_tile(const TrUpd& p, int lane, int k0, int n0, bool bias) {
     const float* dp = p.dz + (size_t)(lane >> 4) * p.np + n0 + (lane & 15);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (uint32_t r1 = 0; r1 < p.mp; r1 += 16) {                            // mp is a multiple of 16; dz rows m .. mp-1 are zero
@@ -203,6 +206,16 @@ __global__ void __launch_bounds__(TR_THREADS) train_update_kernel(TrUpd p) {
 #pragma unroll
         for (int j = 0; j < 4; j++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], bv[j], acc, 0, 0, 0);
     }
+    return acc;
+}
+
+__global__ void __launch_bounds__(TR_THREADS) train_update_kernel(TrUpd p) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t cbs = p.np / 16, kbs = p.kp / 16, tile = blockIdx.x * TR_WAVES + wave;
+    if (tile >= (kbs + 1) * cbs) return;
+    const uint32_t kb = tile / cbs; const int n0 = (tile % cbs) * 16, k0 = kb * 16;
+    const bool bias = kb == kbs;
+    const f32x4 acc = tr_gradient_tile(p, lane, k0, n0, bias);
     const int col = n0 + (lane & 15);
     if (col >= p.n) return;
     if (bias) {
@@ -216,6 +229,125 @@ __global__ void __launch_bounds__(TR_THREADS) train_update_kernel(TrUpd p) {
         const size_t at = (size_t)row * p.np + col;
         p.w[at] = p.w[at] - p.lr * acc[i];                                  // tf.train.sgd: value + (-lr) gradient, in f32
     }
+}
+
+// ---- loss of a regression model (TR-2): tfjs meanSquaredError over the one output unit, binaryAccuracy (what "accuracy" resolves to for
+// a one-unit output: the target equals 1 if p > 0.5 else 0), dZ of the last layer THROUGH its activation (the forward pass has applied
+// it: z holds p).  The same fixed-order sums as train_loss_kernel.  adam != NULL (a training step): thread 0 publishes this step's
+// 1 - accBeta1 / 1 - accBeta2 for the update kernels behind it on the stream and advances accBeta (tfjs: sub(1, accBeta) before the
+// variables, accBeta.mul(beta) after them); the state is {accBeta1, accBeta2, 1 - accBeta1, 1 - accBeta2}, all f32 as tfjs keeps them.
+constexpr float ADAM_BETA1 = 0.9f, ADAM_BETA2 = 0.999f;                     // tf.train.adam's defaults as f32 scalars
+constexpr float ADAM_ONE_M_BETA1 = (float)(1.0 - 0.9), ADAM_ONE_M_BETA2 = (float)(1.0 - 0.999);   // `1 - this.beta`: a double, then the f32 scalar
+constexpr float ADAM_EPSILON = 1e-7f;                                       // the CPU backend's epsilon()
+
+struct TrLossMse {
+    const float* z; int np, act; uint32_t m, mp;
+    const float* target; const uint32_t* idx; uint32_t off;
+    float* dz;                                                              // NULL: evaluation only
+    float* adam;                                                            // NULL: evaluation only
+    double* part_loss; uint32_t* part_hit; uint32_t slot;
+};
+
+__device__ __forceinline__ double tr_derivative_f64(double a, int act) {    // tr_derivative in double
+    switch (act) {
+        case WSA_ACT_RELU: return a > 0.0 ? 1.0 : 0.0;
+        case WSA_ACT_SIGMOID: return a * (1.0 - a);
+        case WSA_ACT_TANH: return 1.0 - a * a;
+        default: return 1.0;
+    }
+}
+
+__global__ void __launch_bounds__(TR_LOSS_THREADS) train_loss_mse_kernel(TrLossMse p) {
+    __shared__ double s_loss[TR_LOSS_THREADS];
+    __shared__ uint32_t s_hit[TR_LOSS_THREADS];
+    const int tid = threadIdx.x;
+    double loss = 0.0; uint32_t hit = 0;
+    for (uint32_t r = tid; r < p.mp; r += TR_LOSS_THREADS) {
+        float* d = p.dz ? p.dz + (size_t)r * p.np : nullptr;
+        float g = 0.f;
+        if (r < p.m) {
+            const float pf = p.z[(size_t)r * p.np];
+            const float tf = p.target[p.idx ? p.idx[p.off + r] : p.off + r];
+            const double e = (double)pf - (double)tf;
+            loss += e * e;
+            hit += tf == (pf > 0.5f ? 1.f : 0.f) ? 1u : 0u;
+            g = (float)(2.0 * e / (double)p.m * tr_derivative_f64((double)pf, p.act));   // the short last batch divides by its own size
+        }
+        if (d) {
+            d[0] = g;
+            for (int c = 1; c < p.np; c++) d[c] = 0.f;
+        }
+    }
+    s_loss[tid] = loss; s_hit[tid] = hit;
+    __syncthreads();
+    for (int w = TR_LOSS_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) { s_loss[tid] += s_loss[tid + w]; s_hit[tid] += s_hit[tid + w]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        p.part_loss[p.slot] = s_loss[0]; p.part_hit[p.slot] = s_hit[0];
+        if (p.adam) {
+            const float a1 = p.adam[0], a2 = p.adam[1];
+            p.adam[2] = 1.f - a1; p.adam[3] = 1.f - a2;
+            p.adam[0] = a1 * ADAM_BETA1; p.adam[1] = a2 * ADAM_BETA2;
+        }
+    }
+}
+
+// ---- tfjs 1.7.2 AdamOptimizer.applyGradients on one element, operation for operation; every intermediate is rounded to f32 once, as
+// the CPU backend's Float32Array stores round it.  Its divisions and its square root are JavaScript doubles stored to f32: written
+// that way here, so their rounding does not hang on how the compiler expands an f32 division or square root.  No contraction: JavaScript
+// has no fused multiply-add.  A gradient of exactly 0 with m = v = 0 gives 0 / (0 + epsilon) . (-lr) + w = w.
+__device__ __forceinline__ float adam_step(float w, float g, float* m, float* v, float c1, float c2, float neg_lr) {
+#pragma clang fp contract(off)
+    const float m0 = *m * ADAM_BETA1, m1 = g * ADAM_ONE_M_BETA1, mn = m0 + m1;
+    const float g2 = g * g;
+    const float v0 = *v * ADAM_BETA2, v1 = g2 * ADAM_ONE_M_BETA2, vn = v0 + v1;
+    *m = mn; *v = vn;
+    const float mh = (float)((double)mn / (double)c1);
+    const float vh = (float)((double)vn / (double)c2);
+    const float den = (float)sqrt((double)vh) + ADAM_EPSILON;
+    const float q = (float)((double)mh / (double)den);
+    const float step = q * neg_lr;
+    return step + w;
+}
+
+// ---- update of a regression model: train_update_kernel's tiles, owners and order of summation; the owner then applies Adam to its own
+// elements of w / m / v (mw, vw [kp][np] and mb, vb [np]: padded exactly as the weights are; padded elements are never touched and stay 0)
+struct TrUpdAdam { TrUpd u; float* mw; float* vw; float* mb; float* vb; const float* adam; };
+
+__global__ void __launch_bounds__(TR_THREADS) train_update_adam_kernel(TrUpdAdam q) {
+    const TrUpd& p = q.u;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t cbs = p.np / 16, kbs = p.kp / 16, tile = blockIdx.x * TR_WAVES + wave;
+    if (tile >= (kbs + 1) * cbs) return;
+    const uint32_t kb = tile / cbs; const int n0 = (tile % cbs) * 16, k0 = kb * 16;
+    const bool bias = kb == kbs;
+    const f32x4 acc = tr_gradient_tile(p, lane, k0, n0, bias);
+    const int col = n0 + (lane & 15);
+    if (col >= p.n) return;
+    const float c1 = q.adam[2], c2 = q.adam[3], neg_lr = -p.lr;
+    if (bias) {
+        if ((lane >> 4) == 0) p.b[col] = adam_step(p.b[col], acc[0], q.mb + col, q.vb + col, c1, c2, neg_lr);   // every row of the tile holds the column sums
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int row = k0 + (lane >> 4) * 4 + i;
+        if (row >= p.k) continue;
+        const size_t at = (size_t)row * p.np + col;
+        p.w[at] = adam_step(p.w[at], acc[i], q.mw + at, q.vw + at, c1, c2, neg_lr);
+    }
+}
+
+__global__ void train_adam_reset_kernel(float* adam) {                      // accBeta = beta: no step taken yet
+    if (threadIdx.x == 0 && blockIdx.x == 0) { adam[0] = ADAM_BETA1; adam[1] = ADAM_BETA2; adam[2] = 1.f - ADAM_BETA1; adam[3] = 1.f - ADAM_BETA2; }
+}
+
+// ---- create: a regression model's targets, (y - min) / (max - min) in double, rounded to f32 (ml5 normalizeData on the output `y`)
+__global__ void __launch_bounds__(256) train_normalise_target_kernel(const double* y, double mn, double mx, uint64_t n_rows, float* t) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n_rows) t[i] = (float)((y[i] - mn) / (mx - mn));
 }
 
 // ---- epoch end: the steps' partials in a fixed order -> the epoch's statistics (history of tfjs's BaseLogger / testLoop)
@@ -260,6 +392,9 @@ struct wsa_trainer {
     uint32_t n_rows = 0, n_train = 0, n_val = 0, batch = 0, n_steps = 0, mcap = 0, epoch = 0;
     float lr = 0.f;
     float* d_x = nullptr; int32_t* d_label = nullptr;
+    bool regress = false;                                      // TR-2: d_target instead of d_label, Adam's moments beside the weights
+    float* d_target = nullptr; float* d_adam = nullptr;
+    float *d_mw[WSA_MODEL_MAX_LAYERS] = {}, *d_vw[WSA_MODEL_MAX_LAYERS] = {}, *d_mb[WSA_MODEL_MAX_LAYERS] = {}, *d_vb[WSA_MODEL_MAX_LAYERS] = {};
     float *d_w[WSA_MODEL_MAX_LAYERS] = {}, *d_b[WSA_MODEL_MAX_LAYERS] = {};
     float* d_a[WSA_MODEL_MAX_LAYERS + 1] = {};                 // d_a[l], l >= 1: the output of layer l - 1, [mcap][pad[l]]
     float* d_dz[2] = {};                                       // [mcap][widest layer]: dZ of a layer and of the one below it
@@ -290,6 +425,14 @@ void enqueue_forward(wsa_trainer* t, const uint32_t* idx, uint32_t off, uint32_t
 }
 
 void enqueue_loss(wsa_trainer* t, const uint32_t* idx, uint32_t off, uint32_t m, float* dz, uint32_t slot, hipStream_t s) {
+    if (t->regress) {
+        TrLossMse p{};
+        p.z = t->d_a[t->nl]; p.np = t->pad[t->nl]; p.act = t->act[t->nl - 1]; p.m = m; p.mp = up16(m);
+        p.target = t->d_target; p.idx = idx; p.off = off; p.dz = dz; p.adam = dz ? t->d_adam : nullptr;
+        p.part_loss = t->d_part_loss; p.part_hit = t->d_part_hit; p.slot = slot;
+        hipLaunchKernelGGL(train_loss_mse_kernel, dim3(1), dim3(TR_LOSS_THREADS), 0, s, p);
+        return;
+    }
     TrLoss p{};
     p.z = t->d_a[t->nl]; p.np = t->pad[t->nl]; p.C = t->units[t->nl]; p.m = m; p.mp = up16(m);
     p.label = t->d_label; p.idx = idx; p.off = off; p.dz = dz;
@@ -313,17 +456,25 @@ void enqueue_step(wsa_trainer* t, const uint32_t* idx, uint32_t step, hipStream_
         u.a = l == 0 ? TrRows{t->d_x, TR_XS, idx, off, m} : TrRows{t->d_a[l], t->pad[l], nullptr, 0, m};
         u.dz = t->d_dz[cur]; u.w = t->d_w[l]; u.b = t->d_b[l];
         u.kp = t->pad[l]; u.np = t->pad[l + 1]; u.k = t->units[l]; u.n = t->units[l + 1]; u.mp = mp; u.lr = t->lr;
-        hipLaunchKernelGGL(train_update_kernel, dim3(blocks_for((uint64_t)(u.kp / 16 + 1) * (u.np / 16))), dim3(TR_THREADS), 0, s, u);
+        const dim3 grid(blocks_for((uint64_t)(u.kp / 16 + 1) * (u.np / 16)));
+        if (t->regress) {
+            const TrUpdAdam q{u, t->d_mw[l], t->d_vw[l], t->d_mb[l], t->d_vb[l], t->d_adam};
+            hipLaunchKernelGGL(train_update_adam_kernel, grid, dim3(TR_THREADS), 0, s, q);
+        } else {
+            hipLaunchKernelGGL(train_update_kernel, grid, dim3(TR_THREADS), 0, s, u);
+        }
         cur ^= 1;
     }
 }
 
 }  // namespace
 
-extern "C" {
+namespace {
 
-wsa_status wsa_trainer_create(wsa_ctx* ctx, const wsa_model_desc* d, const double* feat, const int32_t* label, uint32_t n_rows,
-                              uint32_t n_val, uint32_t batch_size, double learning_rate, wsa_trainer** out) {
+// both kinds of trainer: label != NULL a classifier's (TR-1), target != NULL a regression model's (TR-2)
+wsa_status trainer_create(wsa_ctx* ctx, const wsa_model_desc* d, const double* feat, const int32_t* label, const double* target, bool regress,
+                          uint32_t n_rows, uint32_t n_val, uint32_t batch_size, double learning_rate, double out_min, double out_max,
+                          wsa_trainer** out) {
     if (!ctx || !d || !out) return fail(ctx, WSA_ERR_INVALID, "null argument");
     *out = nullptr;
     const int nl = d->n_layers;
@@ -337,7 +488,10 @@ wsa_status wsa_trainer_create(wsa_ctx* ctx, const wsa_model_desc* d, const doubl
         if (a == WSA_ACT_SOFTMAX && l != nl - 1) return fail(ctx, WSA_ERR_INVALID, "softmax is only supported on the last layer");
         if (!d->kernel[l] || !d->bias[l]) return fail(ctx, WSA_ERR_INVALID, "null kernel / bias of layer " + std::to_string(l));
     }
-    if (d->activation[nl - 1] != WSA_ACT_SOFTMAX) return fail(ctx, WSA_ERR_INVALID, "training needs a softmax output layer (categoricalCrossentropy)");
+    if (regress) {
+        if (d->activation[nl - 1] == WSA_ACT_SOFTMAX) return fail(ctx, WSA_ERR_INVALID, "a regression model's last layer is linear, relu, sigmoid or tanh, not softmax (meanSquaredError)");
+        if (d->units[nl] != 1) return fail(ctx, WSA_ERR_INVALID, "a regression model has one output unit, got " + std::to_string(d->units[nl]));
+    } else if (d->activation[nl - 1] != WSA_ACT_SOFTMAX) return fail(ctx, WSA_ERR_INVALID, "training needs a softmax output layer (categoricalCrossentropy)");
     const int C = d->units[nl];
     if (C > WSA_MODEL_MAX_CLASSES) return fail(ctx, WSA_ERR_INVALID, "the output layer has " + std::to_string(C) + " units (limit 64)");
     if (!d->in_min || !d->in_max) return fail(ctx, WSA_ERR_INVALID, "null in_min / in_max");
@@ -345,11 +499,18 @@ wsa_status wsa_trainer_create(wsa_ctx* ctx, const wsa_model_desc* d, const doubl
         if (!std::isfinite(d->in_min[k]) || !std::isfinite(d->in_max[k])) return fail(ctx, WSA_ERR_INVALID, "non-finite in_min / in_max of input " + std::to_string(k));
         if (d->in_max[k] == d->in_min[k]) return fail(ctx, WSA_ERR_INVALID, "feature " + std::to_string(k) + " has max == min: it cannot be normalised");
     }
-    if (!feat || !label) return fail(ctx, WSA_ERR_INVALID, "null feature / label pointer");
+    if (!feat || (regress ? !target : !label)) return fail(ctx, WSA_ERR_INVALID, regress ? "null feature / target pointer" : "null feature / label pointer");
     if (n_val >= n_rows) return fail(ctx, WSA_ERR_INVALID, "n_val " + std::to_string(n_val) + " leaves no training rows of " + std::to_string(n_rows));
     if (batch_size == 0) return fail(ctx, WSA_ERR_INVALID, "batch_size must be at least 1");
     if (!std::isfinite(learning_rate) || !std::isfinite((float)learning_rate)) return fail(ctx, WSA_ERR_INVALID, "the learning rate is not finite as an f32");
-    for (uint32_t r = 0; r < n_rows; r++)
+    if (regress) {
+        if (!std::isfinite(out_min) || !std::isfinite(out_max)) return fail(ctx, WSA_ERR_INVALID, "non-finite out_min / out_max");
+        if (out_max == out_min) return fail(ctx, WSA_ERR_INVALID, "the output has max == min: it cannot be normalised");
+        for (uint32_t r = 0; r < n_rows; r++)
+            if (!std::isfinite(target[r]) || !std::isfinite((float)((target[r] - out_min) / (out_max - out_min))))
+                return fail(ctx, WSA_ERR_INVALID, "the target of row " + std::to_string(r) + " is not finite as a normalised f32");
+    }
+    if (!regress) for (uint32_t r = 0; r < n_rows; r++)
         if (label[r] < 0 || label[r] >= C) return fail(ctx, WSA_ERR_INVALID, "label " + std::to_string(label[r]) + " of row " + std::to_string(r) + " is outside 0 .. " + std::to_string(C - 1));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     wsa_trainer* t = new wsa_trainer();
@@ -357,7 +518,7 @@ wsa_status wsa_trainer_create(wsa_ctx* ctx, const wsa_model_desc* d, const doubl
     t->batch = batch_size < t->n_train ? batch_size : t->n_train;            // a larger batch is one step over all training rows
     t->n_steps = (t->n_train + t->batch - 1) / t->batch;
     t->mcap = up16(t->batch > n_val ? t->batch : n_val);
-    t->lr = (float)learning_rate;
+    t->lr = (float)learning_rate; t->regress = regress;
     t->in_min.assign(d->in_min, d->in_min + WSA_NFEAT); t->in_max.assign(d->in_max, d->in_max + WSA_NFEAT);
     if (d->labels) { t->has_labels = true; for (int c = 0; c < C; c++) t->labels.emplace_back(d->labels[c] ? d->labels[c] : ""); }
     int pmax = 0;
@@ -370,14 +531,16 @@ wsa_status wsa_trainer_create(wsa_ctx* ctx, const wsa_model_desc* d, const doubl
         for (int k = 0; k < K; k++) std::memcpy(&w[(size_t)k * np], d->kernel[l] + (size_t)k * N, N * sizeof(float));
         std::memcpy(bb.data(), d->bias[l], N * sizeof(float));
         ok = t->mem.upload(&t->d_w[l], w) && t->mem.upload(&t->d_b[l], bb) && t->mem.alloc(&t->d_a[l + 1], (size_t)t->mcap * np, true);
+        if (regress) ok = ok && t->mem.alloc(&t->d_mw[l], w.size(), true) && t->mem.alloc(&t->d_vw[l], w.size(), true)
+                          && t->mem.alloc(&t->d_mb[l], bb.size(), true) && t->mem.alloc(&t->d_vb[l], bb.size(), true);
     }
     std::vector<uint32_t> ident(t->n_train);
     for (uint32_t i = 0; i < t->n_train; i++) ident[i] = i;
-    double *d_feat = nullptr, *d_mn = nullptr, *d_mx = nullptr;
+    double *d_feat = nullptr, *d_mn = nullptr, *d_mx = nullptr, *d_y = nullptr;
     {
         wsa::DevArena tmp;                                                   // the double rows live only until they are normalised
         ok = ok && t->mem.alloc(&t->d_dz[0], (size_t)t->mcap * pmax, true) && t->mem.alloc(&t->d_dz[1], (size_t)t->mcap * pmax, true)
-             && t->mem.alloc(&t->d_x, (size_t)n_rows * TR_XS) && t->mem.alloc(&t->d_label, n_rows)
+             && t->mem.alloc(&t->d_x, (size_t)n_rows * TR_XS) && (regress ? t->mem.alloc(&t->d_target, n_rows) && t->mem.alloc(&t->d_adam, 4) : t->mem.alloc(&t->d_label, n_rows))
              && t->mem.alloc(&t->d_order, t->n_train) && t->mem.upload(&t->d_identity, ident)
              && t->mem.alloc(&t->d_part_loss, t->n_steps + 1, true) && t->mem.alloc(&t->d_part_hit, t->n_steps + 1, true)
              && t->mem.alloc(&t->d_stats, 1, true)
@@ -388,7 +551,12 @@ wsa_status wsa_trainer_create(wsa_ctx* ctx, const wsa_model_desc* d, const doubl
              && hipMemcpy(d_feat, feat, (size_t)n_rows * WSA_NFEAT * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
              && hipMemcpy(d_mn, d->in_min, WSA_NFEAT * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
              && hipMemcpy(d_mx, d->in_max, WSA_NFEAT * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
-             && hipMemcpy(t->d_label, label, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
+             && (regress ? tmp.alloc(&d_y, n_rows) && hipMemcpy(d_y, target, (size_t)n_rows * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
+                         : hipMemcpy(t->d_label, label, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess);
+        if (ok && regress) {
+            hipLaunchKernelGGL(train_normalise_target_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, nullptr, d_y, out_min, out_max, (uint64_t)n_rows, t->d_target);
+            hipLaunchKernelGGL(train_adam_reset_kernel, dim3(1), dim3(1), 0, nullptr, t->d_adam);
+        }
         if (ok) {
             const uint64_t total = (uint64_t)n_rows * TR_XS;
             hipLaunchKernelGGL(train_normalise_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, nullptr, d_feat, d_mn, d_mx, (uint64_t)n_rows, t->d_x);
@@ -402,6 +570,20 @@ wsa_status wsa_trainer_create(wsa_ctx* ctx, const wsa_model_desc* d, const doubl
     }
     *out = t;
     return WSA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+wsa_status wsa_trainer_create(wsa_ctx* ctx, const wsa_model_desc* d, const double* feat, const int32_t* label, uint32_t n_rows,
+                              uint32_t n_val, uint32_t batch_size, double learning_rate, wsa_trainer** out) {
+    return trainer_create(ctx, d, feat, label, nullptr, false, n_rows, n_val, batch_size, learning_rate, 0.0, 1.0, out);
+}
+
+wsa_status wsa_regress_trainer_create(wsa_ctx* ctx, const wsa_model_desc* d, const double* feat, const double* target, uint32_t n_rows,
+                                      uint32_t n_val, uint32_t batch_size, double learning_rate, double out_min, double out_max, wsa_trainer** out) {
+    return trainer_create(ctx, d, feat, nullptr, target, true, n_rows, n_val, batch_size, learning_rate, out_min, out_max, out);
 }
 
 void wsa_trainer_destroy(wsa_trainer* t) {

@@ -235,6 +235,11 @@ function parse_model(mj, meta, weights) {
   const inMin = new Float64Array(53), inMax = new Float64Array(53);
   for (let k = 0; k < 53; k++) { const r = meta.inputs[String(k)]; inMin[k] = r.min; inMax[k] = r.max; }
   const out = meta.outputs.y || Object.values(meta.outputs)[0];
+  if (out && !out.legend && typeof out.min === 'number' && typeof out.max === 'number') {       // a regression model (ords_<label>): the output's range, no legend
+    if (units[units.length - 1] !== 1 || act[act.length - 1] === ACT.softmax) throw 'loadModel: model_meta.json describes a regression output; the model does not end in one non-softmax unit';
+    if (!(out.max !== out.min) || !isFinite(out.min) || !isFinite(out.max)) throw 'loadModel: model_meta.json: output range ' + out.min + ' .. ' + out.max;
+    return { units: Int32Array.from(units), activation: Int32Array.from(act), kernels, biases, inMin, inMax, labels: [], outMin: out.min, outMax: out.max };
+  }
   const labels = Object.keys(out.legend);
   return { units: Int32Array.from(units), activation: Int32Array.from(act), kernels, biases, inMin, inMax, labels };
 }
@@ -286,6 +291,53 @@ function trainModel(o) {
     return h;
   });
 }
+// ---- the app's regression models for the ordinal labels V, A and D (ref src/neuralmodel.js:268-333 train_nn's ordinal branch, :410-585 predict_db_nn /
+// predict_single; specification TR-2, include/wsa.h "Regression models").
+// trainRegression(features: [[53 numbers]], values, {options, epochs, batchSize, seed, validationSplit, init, orders, onEpoch}) -> Promise of a model
+// handle; `values` holds per row the label's value (null: unlabelled), `options` defaults to the app's nn_default_options_ords.  The handle carries
+// `history` and spec.outMin / spec.outMax; saveModel / loadModel write and read its directory (dist/nnmodel/<db>/ords_<label>/).
+// predictValues(handle, features: [[53 numbers]]) -> Float64Array, per row what ml5's predictMultiple gives as result[0].value.
+// A regression handle is not a prediction model: setPredictionModel(s) need class probabilities, and trainModel keeps refusing a stack without softmax.
+function trainRegression(features, values, o) {
+  o = o || {};
+  const tm = require('./trainmodel.js');
+  let nat, ctx, spec, data, job;
+  try {
+    const opt = Object.assign({}, tm.DEFAULT_OPTIONS_ORDS, o.options || {});
+    data = tm.prepareOrdinal(features, values);
+    const st = tm.stackRegression(opt.layers), epochs = o.epochs === undefined ? 10 : o.epochs | 0, seed = o.seed | 0;
+    const sp = tm.split(data.values.length, o.validationSplit);
+    const init = o.init || tm.glorotInit(Array.from(st.units), seed);
+    spec = { units: st.units, activation: st.activation, kernels: init.kernels.map((k) => Float32Array.from(k)), biases: init.biases.map((b) => Float32Array.from(b)),
+      inMin: data.inMin, inMax: data.inMax, labels: [], outMin: data.outMin, outMax: data.outMax };
+    job = { features: data.features, values: data.values, outMin: data.outMin, outMax: data.outMax, nVal: sp.nVal, batchSize: o.batchSize === undefined ? 32 : o.batchSize,
+      learningRate: opt.learningRate, epochs, orders: o.orders || tm.epochOrders(sp.nTrain, epochs, seed + 1) };
+    nat = addon();
+    ctx = contexts_for(nat, settings.devices ? settings.devices.slice() : [settings.device])[0];
+  } catch (e) { return Promise.reject(e); }
+  return nat.train(ctx, spec, job, typeof o.onEpoch === 'function' ? o.onEpoch : undefined).then((r) => {
+    const h = { spec: Object.assign({}, spec, { kernels: r.kernels, biases: r.biases }), natives: new Map(), released: false, history: [] };
+    for (let e = 0; e < job.epochs; e++) h.history.push({ loss: r.history[4 * e], acc: r.history[4 * e + 1], val_loss: r.history[4 * e + 2], val_acc: r.history[4 * e + 3] });
+    h.labels = [];
+    loaded_models.add(h);
+    return h;
+  });
+}
+function predictValues(handle, features) {
+  if (!loaded_models.has(handle) || handle.released) throw 'predictValues: the model handle was released (shutdown()) or is not one of loadModel / trainRegression';
+  if (typeof handle.spec.outMin !== 'number' || typeof handle.spec.outMax !== 'number') throw 'predictValues: not a regression model (no output range)';
+  if (!Array.isArray(features)) throw 'predictValues(handle, [[53 numbers]])';
+  const x = new Float64Array(features.length * 53);
+  features.forEach((row, r) => {
+    if (row.length !== 53) throw 'predictValues: row ' + r + ' has ' + row.length + ' features; 53 expected';
+    for (let k = 0; k < 53; k++) x[r * 53 + k] = Number(row[k]);
+  });
+  const nat = addon();
+  const ctx = contexts_for(nat, settings.devices ? settings.devices.slice() : [settings.device])[0];
+  let m = handle.natives.get(ctx);
+  if (!m) { m = nat.modelCreate(ctx, handle.spec); handle.natives.set(ctx, m); }
+  return nat.regressRows(ctx, m, x, handle.spec.outMin, handle.spec.outMax);
+}
 function saveModel(handle, dir) {
   if (!handle || !handle.spec) throw 'saveModel(handle, dir)';
   require('./trainmodel.js').saveModelFiles(handle.spec, dir);
@@ -293,6 +345,7 @@ function saveModel(handle, dir) {
 function setPredictionModel(handle, on_prediction) {
   if (handle === null || handle === undefined) { prediction = null; return; }
   if (!loaded_models.has(handle) || handle.released) throw 'setPredictionModel: the model handle was released (shutdown()) or is not one of loadModel';
+  if (typeof handle.spec.outMin === 'number') throw 'setPredictionModel: a regression model has no class probabilities to fold; predictValues gives its values';
   if (typeof on_prediction !== 'function') throw 'setPredictionModel(handle, on_prediction)';
   prediction = { model: handle, on_prediction };
 }
@@ -300,6 +353,7 @@ function setPredictionModels(handles, on_prediction) {
   if (handles === null || handles === undefined) { prediction = null; return; }
   if (!Array.isArray(handles) || handles.length < 1 || handles.length > 8) throw 'setPredictionModels([handles], on_prediction): 1 .. 8 model handles';
   for (const h of handles) if (!loaded_models.has(h) || h.released) throw 'setPredictionModels: a model handle was released (shutdown()) or is not one of loadModel';
+  for (const h of handles) if (typeof h.spec.outMin === 'number') throw 'setPredictionModels: a regression model has no class probabilities to fold; predictValues gives its values';
   if (typeof on_prediction !== 'function') throw 'setPredictionModels([handles], on_prediction)';
   // the carried min_entropy_db is an index into the list: the same list keeps it (the reference's available_DBs never changes), another list starts anew
   const same = prediction && prediction.models && prediction.models.length === handles.length && prediction.models.every((h, i) => h === handles[i]);
@@ -861,4 +915,4 @@ function set_predicted_label_for_segment(si, idx, label) {                      
 
 module.exports = { configure, LaunchAudioNodes, StopAudioNodes, set_predicted_label_for_segment, LaunchBatch, LaunchBatches,
   StreamOpen, STREAM_ACTIVE, STREAM_START, STREAM_STOP, shutdown, allocPinned, freePinned,
-  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, loadModel, setPredictionModel, setPredictionModels, trainModel, saveModel };
+  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, loadModel, setPredictionModel, setPredictionModels, trainModel, saveModel, trainRegression, predictValues };

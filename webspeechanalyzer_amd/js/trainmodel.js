@@ -2,6 +2,7 @@
 // around ml5.neuralNetwork(...).train — selecting and balancing the stored rows, the input ranges — plus what the reference draws from
 // Math.random and TR-1 leaves to the host (initial weights, one order of the training rows per epoch; here from a seeded generator of our own),
 // and the three files ml5 0.6.0's save() writes.  Pure JavaScript, no device.  Classification only; the '*' wildcard class is not supported.
+// (prepare / stack; the regression models, specification TR-2, have prepareOrdinal / stackRegression below: ref neuralmodel.js:268-333.)
 'use strict';
 const fs = require('fs');
 const path = require('path');
@@ -63,6 +64,48 @@ function epochOrders(nTrain, epochs, seed) {       // one Fisher-Yates permutati
   }
   return out;
 }
+// ref src/neuralmodel_aux.js:127-150 (nn_default_options_ords: task "regression")
+const DEFAULT_OPTIONS_ORDS = { layers: [{ type: 'dense', units: 64, activation: 'sigmoid' }, { type: 'dense', units: 16, activation: 'sigmoid' }, { type: 'dense', activation: 'sigmoid' }], learningRate: 0.2 };
+const ORDINAL_RANGES = [0.25, 0.5, 0.75, 1.0];
+// ref neuralmodel.js:278-332: a row's bin is the first range that holds its value; null / undefined and values above 1.0 are dropped; fewer than 10
+// rows refused; only when the largest bin exceeds 3, every bin with more than 3 and fewer than the largest count is topped up by cycling through
+// the DB in order; the input and output ranges over the balanced set
+function prepareOrdinal(features, values) {
+  if (!Array.isArray(features) || features.length !== values.length) throw 'trainRegression: features and values must have one entry per row';
+  const nb = ORDINAL_RANGES.length;
+  const bins = values.map((v) => (v === null || v === undefined ? -1 : ORDINAL_RANGES.findIndex((hi) => v <= hi)));       // -1: above 1.0 (or NaN)
+  const rows = [], count = new Array(nb).fill(0);
+  bins.forEach((b, i) => { if (b >= 0) { rows.push(i); count[b]++; } });
+  if (rows.length < 10) throw 'Sample size ' + rows.length + '/' + features.length + ' too small for training';
+  const max_n = Math.max(...count);
+  if (max_n > 3)
+    for (let c = 0; c < nb; c++)
+      while (count[c] < max_n && count[c] > 3)
+        for (let i = 0; i < features.length; i++) {
+          if (bins[i] === c && count[c] < max_n) { rows.push(i); count[c]++; }
+          if (count[c] >= max_n) break;
+        }
+  const x = new Float64Array(rows.length * 53), y = new Float64Array(rows.length);
+  const inMin = new Float64Array(53).fill(Infinity), inMax = new Float64Array(53).fill(-Infinity);
+  let outMin = Infinity, outMax = -Infinity;
+  rows.forEach((i, r) => {
+    if (features[i].length !== 53) throw 'trainRegression: row ' + i + ' has ' + features[i].length + ' features; 53 expected';
+    for (let k = 0; k < 53; k++) { const v = Number(features[i][k]); x[r * 53 + k] = v; if (v < inMin[k]) inMin[k] = v; if (v > inMax[k]) inMax[k] = v; }
+    y[r] = Number(values[i]); if (y[r] < outMin) outMin = y[r]; if (y[r] > outMax) outMax = y[r];
+  });
+  return { features: x, values: y, inMin, inMax, outMin, outMax, counts: count, rows };
+}
+function stackRegression(layers) {
+  const units = [53], activation = [];
+  layers.forEach((l, i) => {
+    if ((l.type || 'dense') !== 'dense') throw 'trainRegression: layer ' + i + ' is ' + l.type + '; only dense layers are supported';
+    const a = l.activation || 'linear';
+    if (!(a in ACT)) throw 'trainRegression: layer ' + i + ' has activation ' + a;
+    units.push(i === layers.length - 1 ? 1 : l.units | 0); activation.push(ACT[a]);
+  });
+  if (activation[activation.length - 1] === ACT.softmax) throw "trainRegression: a regression model's last layer is linear, relu, sigmoid or tanh, not softmax";
+  return { units: Int32Array.from(units), activation: Int32Array.from(activation) };
+}
 function split(n, validationSplit) { const nTrain = Math.floor(n * (1 - (validationSplit === undefined ? 0.1 : validationSplit))); return { nTrain, nVal: n - nTrain }; }
 function stack(layers, nClasses) {
   const units = [53], activation = [];
@@ -79,7 +122,9 @@ function stack(layers, nClasses) {
 // model.json, model_meta.json, model.weights.bin in the key layout of the directories the app ships (dist/nnmodel/<db>/cats_<label>/)
 function saveModelFiles(spec, dir) {
   const nl = spec.kernels.length, layers = [], weights = [], blobs = [];
-  if (spec.labels.length !== spec.units[nl]) throw 'saveModel: ' + spec.labels.length + ' legend labels for ' + spec.units[nl] + ' outputs';
+  const regression = typeof spec.outMin === 'number' && typeof spec.outMax === 'number';       // ords_<label>: no legend, the output's range
+  if (regression && (spec.units[nl] !== 1 || spec.activation[nl - 1] === ACT.softmax)) throw 'saveModel: a regression model ends in one non-softmax unit';
+  if (!regression && spec.labels.length !== spec.units[nl]) throw 'saveModel: ' + spec.labels.length + ' legend labels for ' + spec.units[nl] + ' outputs';
   for (let i = 0; i < nl; i++) {
     const name = 'dense_Dense' + (i + 1);
     const cfg = { units: spec.units[i + 1], activation: ACT_NAME[spec.activation[i]], use_bias: true,
@@ -97,10 +142,11 @@ function saveModelFiles(spec, dir) {
   for (let k = 0; k < spec.units[0]; k++) inputs[String(k)] = { dtype: 'number', min: spec.inMin[k], max: spec.inMax[k] };
   spec.labels.forEach((lab, j) => { legend[lab] = Array.from({ length: C }, (_, c) => (c === j ? 1 : 0)); });
   const meta = { inputUnits: [spec.units[0]], outputUnits: C, inputs, outputs: { y: { dtype: 'string', min: 0, max: 1, uniqueValues: spec.labels.slice(), legend } }, isNormalized: true };
+  if (regression) { meta.outputUnits = 1; meta.outputs = { y: { dtype: 'number', min: spec.outMin, max: spec.outMax } }; }
   fs.mkdirSync(dir, { recursive: true });
   fs.writeFileSync(path.join(dir, 'model.json'), JSON.stringify(mj));
   fs.writeFileSync(path.join(dir, 'model_meta.json'), JSON.stringify(meta));
   fs.writeFileSync(path.join(dir, 'model.weights.bin'), Buffer.concat(blobs));
 }
 
-module.exports = { prepare, glorotInit, epochOrders, split, stack, saveModelFiles, DEFAULT_OPTIONS };
+module.exports = { prepare, glorotInit, epochOrders, split, stack, saveModelFiles, DEFAULT_OPTIONS, prepareOrdinal, stackRegression, DEFAULT_OPTIONS_ORDS };

@@ -1010,20 +1010,22 @@ typedef struct {
     float *kernel[WSA_MODEL_MAX_LAYERS], *bias[WSA_MODEL_MAX_LAYERS];
     double mn[WSA_NFEAT], mx[WSA_NFEAT];
     double *feat; int32_t *y; uint32_t *orders; uint32_t n, n_val, batch, epochs; double lr;
+    double *values, out_min, out_max;                     /* values != NULL: a regression model (wsa_regress_trainer_create) instead of y */
     double *history; wsa_status st; char err[512];
 } train_job;
 typedef struct { train_job *j; int32_t epoch; wsa_train_stats s; } train_msg;          /* epoch < 0: the run is over */
 
 static void train_job_free(train_job *j) {
     for (int l = 0; l < WSA_MODEL_MAX_LAYERS; l++) { free(j->kernel[l]); free(j->bias[l]); }
-    free(j->feat); free(j->y); free(j->orders); free(j->history); free(j);
+    free(j->feat); free(j->y); free(j->values); free(j->orders); free(j->history); free(j);
 }
 static void *train_thread(void *arg) {
     train_job *j = (train_job *)arg;
     wsa_ctx *ctx = j->box->ctx;
     wsa_trainer *t = NULL;
     wsa_model_desc d = {j->nl, j->units, j->act, (const float *const *)j->kernel, (const float *const *)j->bias, j->mn, j->mx, NULL};
-    j->st = wsa_trainer_create(ctx, &d, j->feat, j->y, j->n, j->n_val, j->batch, j->lr, &t);
+    j->st = j->values ? wsa_regress_trainer_create(ctx, &d, j->feat, j->values, j->n, j->n_val, j->batch, j->lr, j->out_min, j->out_max, &t)
+                      : wsa_trainer_create(ctx, &d, j->feat, j->y, j->n, j->n_val, j->batch, j->lr, &t);
     for (uint32_t e = 0; j->st == WSA_OK && e < j->epochs; e++) {
         j->st = wsa_trainer_epoch(t, j->orders ? j->orders + (size_t)e * (j->n - j->n_val) : NULL, j->box->queue);
         wsa_train_stats s;
@@ -1084,15 +1086,18 @@ static napi_value fn_train(napi_env env, napi_callback_info info) {
     size_t argc = 4; napi_value argv[4];
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     ctx_box *box = argc ? get_box(env, argv[0]) : NULL;
-    const char *usage = "train(ctx, {units, activation, kernels, biases, inMin, inMax}, {features: Float64Array, y: Int32Array, nVal, batchSize, learningRate, epochs, orders?: Uint32Array}, onEpoch?)";
+    const char *usage = "train(ctx, {units, activation, kernels, biases, inMin, inMax}, {features: Float64Array, y: Int32Array | values: Float64Array + outMin + outMax, nVal, batchSize, learningRate, epochs, orders?: Uint32Array}, onEpoch?)";
     if (!box || !box->ctx || argc < 3) { napi_throw_type_error(env, NULL, usage); return NULL; }
-    int32_t *units = NULL, *act = NULL, *y = NULL; double *mn = NULL, *mx = NULL, *feat = NULL; uint32_t *orders = NULL;
+    int32_t *units = NULL, *act = NULL, *y = NULL; double *mn = NULL, *mx = NULL, *feat = NULL, *values = NULL; uint32_t *orders = NULL;
     size_t nu = 0, na = 0, nmn = 0, nmx = 0, nf = 0, ny = 0, no = 0;
-    double n_val = 0, batch = 0, lr = 0, epochs = 0;
+    double n_val = 0, batch = 0, lr = 0, epochs = 0, out_min = 0, out_max = 0;
+    /* a regression run (specification TR-2): `values` (the label's real values) with `outMin` / `outMax` in place of `y` */
+    const int regress = argc >= 3 && typed_of(env, argv[2], "values", napi_float64_array, (void **)&values, &ny);
+    if (regress && (!num_of(env, argv[2], "outMin", &out_min) || !num_of(env, argv[2], "outMax", &out_max))) { napi_throw_type_error(env, NULL, usage); return NULL; }
     if (!typed_of(env, argv[1], "units", napi_int32_array, (void **)&units, &nu) || !typed_of(env, argv[1], "activation", napi_int32_array, (void **)&act, &na) ||
         !typed_of(env, argv[1], "inMin", napi_float64_array, (void **)&mn, &nmn) || !typed_of(env, argv[1], "inMax", napi_float64_array, (void **)&mx, &nmx) ||
         nu < 2 || na != nu - 1 || na > WSA_MODEL_MAX_LAYERS || nmn != WSA_NFEAT || nmx != WSA_NFEAT ||
-        !typed_of(env, argv[2], "features", napi_float64_array, (void **)&feat, &nf) || !typed_of(env, argv[2], "y", napi_int32_array, (void **)&y, &ny) ||
+        !typed_of(env, argv[2], "features", napi_float64_array, (void **)&feat, &nf) || (!regress && !typed_of(env, argv[2], "y", napi_int32_array, (void **)&y, &ny)) ||
         ny < 1 || nf != ny * WSA_NFEAT || ny > 0xffffffffu ||
         !num_of(env, argv[2], "nVal", &n_val) || !num_of(env, argv[2], "batchSize", &batch) || !num_of(env, argv[2], "learningRate", &lr) || !num_of(env, argv[2], "epochs", &epochs) ||
         n_val < 0 || n_val >= (double)ny || batch < 0 || batch > 4294967295.0 || epochs < 1 || epochs > 1e6) { napi_throw_type_error(env, NULL, usage); return NULL; }
@@ -1116,9 +1121,11 @@ static napi_value fn_train(napi_env env, napi_callback_info info) {
         if (ok) { j->kernel[l] = dup_bytes(dk, lk * sizeof(float)); j->bias[l] = dup_bytes(db, lb * sizeof(float)); ok = j->kernel[l] && j->bias[l]; }
     }
     if (!ok) { train_job_free(j); napi_throw_type_error(env, NULL, "train: kernels[i] must be a Float32Array of units[i] x units[i+1], biases[i] one of units[i+1]"); return NULL; }
-    j->feat = dup_bytes(feat, nf * sizeof(double)); j->y = dup_bytes(y, ny * sizeof(int32_t)); j->history = calloc((size_t)j->epochs * 4, sizeof(double));
+    j->feat = dup_bytes(feat, nf * sizeof(double)); j->history = calloc((size_t)j->epochs * 4, sizeof(double));
+    if (regress) { j->values = dup_bytes(values, ny * sizeof(double)); j->out_min = out_min; j->out_max = out_max; }
+    else j->y = dup_bytes(y, ny * sizeof(int32_t));
     if (orders) j->orders = dup_bytes(orders, no * sizeof(uint32_t));
-    if (!j->feat || !j->y || !j->history || (orders && !j->orders)) { train_job_free(j); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    if (!j->feat || (regress ? !j->values : !j->y) || !j->history || (orders && !j->orders)) { train_job_free(j); napi_throw_error(env, NULL, "out of memory"); return NULL; }
     napi_valuetype ft = napi_undefined;
     if (argc > 3 && napi_typeof(env, argv[3], &ft) == napi_ok && ft == napi_function && napi_create_reference(env, argv[3], 1, &j->on_epoch) != napi_ok) j->on_epoch = NULL;
     napi_value promise, name;
@@ -1137,6 +1144,35 @@ static napi_value fn_train(napi_env env, napi_callback_info info) {
     return promise;
 }
 
+/* ---- a regression model's values (wsa_regress_rows): regressRows(ctx, model, features: Float64Array [n][53], outMin, outMax) -> Float64Array [n].
+ * What the app's predict_db_nn does over stored rows (ref src/neuralmodel.js:410-535).  Synchronous: the rows go through one page-locked
+ * allocation the device reads and writes in place. */
+static napi_value fn_regress_rows(napi_env env, napi_callback_info info) {
+    size_t argc = 5; napi_value argv[5]; void *p = NULL;
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ctx_box *box = argc ? get_box(env, argv[0]) : NULL;
+    const char *usage = "regressRows(ctx, model, features: Float64Array [n][53], outMin, outMax)";
+    bool ta = false; napi_typedarray_type tt; size_t nf = 0; void *feat = NULL; double lo = 0, hi = 0;
+    if (!box || !box->ctx || argc < 5 || napi_get_value_external(env, argv[1], &p) != napi_ok || !p ||
+        napi_is_typedarray(env, argv[2], &ta) != napi_ok || !ta || napi_get_typedarray_info(env, argv[2], &tt, &nf, &feat, NULL, NULL) != napi_ok ||
+        tt != napi_float64_array || nf % WSA_NFEAT || nf / WSA_NFEAT > 0xffffffffu ||
+        napi_get_value_double(env, argv[3], &lo) != napi_ok || napi_get_value_double(env, argv[4], &hi) != napi_ok) { napi_throw_type_error(env, NULL, usage); return NULL; }
+    model_box *mb = (model_box *)p;
+    if (!mb->m || mb->owner != box) { napi_throw_error(env, NULL, "regressRows: the model was destroyed or belongs to another context"); return NULL; }
+    const size_t n = nf / WSA_NFEAT;
+    void *slab = NULL;
+    if (wsa_host_alloc(box->ctx, (uint64_t)(nf + n) * sizeof(double), &slab) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(box->ctx)); return NULL; }
+    double *rows = (double *)slab, *value = rows + nf;
+    if (nf) memcpy(rows, feat, nf * sizeof(double));
+    wsa_status st = wsa_regress_rows(mb->m, lo, hi, rows, (uint32_t)n, value, box->queue);
+    if (st == WSA_OK) st = wsa_queue_synchronize(box->ctx, box->queue);
+    napi_value out = NULL;
+    if (st == WSA_OK) out = make_typed(env, napi_float64_array, value, n, sizeof(double));
+    else napi_throw_error(env, NULL, wsa_last_error(box->ctx));
+    wsa_host_free(slab);
+    return out;
+}
+
 NAPI_MODULE_INIT() {
     /* the structures below follow the header this file was compiled against: refuse a libwsa.so of another ABI version */
     if (wsa_abi_version() != WSA_ABI_VERSION) { napi_throw_error(env, NULL, "libwsa.so ABI version differs from the one wsa_napi.node was built against (include/wsa.h): rebuild"); return NULL; }
@@ -1144,7 +1180,7 @@ NAPI_MODULE_INIT() {
         {"abiVersion", fn_abi_version}, {"freePinned", fn_free_pinned}, {"defaults", fn_defaults}, {"create", fn_create}, {"destroy", fn_destroy},
         {"geometry", fn_geometry}, {"allocPinned", fn_alloc_pinned}, {"binsHz", fn_bins_hz}, {"processBatch", fn_process_batch}, {"gatherRows", fn_gather_rows},
         {"streamOpen", fn_stream_open}, {"streamOpenMixed", fn_stream_open_mixed}, {"streamInfo", fn_stream_info}, {"streamPaced", fn_stream_paced}, {"streamInput", fn_stream_input}, {"streamStep", fn_stream_step}, {"streamClose", fn_stream_close}, {"streamSetModel", fn_stream_set_model}, {"streamSetEnsemble", fn_stream_set_ensemble},
-        {"modelCreate", fn_model_create}, {"modelDestroy", fn_model_destroy}, {"train", fn_train}};
+        {"modelCreate", fn_model_create}, {"modelDestroy", fn_model_destroy}, {"train", fn_train}, {"regressRows", fn_regress_rows}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

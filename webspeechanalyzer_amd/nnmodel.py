@@ -1,5 +1,6 @@
 """The reference application's trained classifiers (dist/nnmodel/<db>/cats_<label>/ — model.json, model_meta.json,
-model.weights.bin as ml5 0.6.0 saves them) parsed into what wsa_model_create takes.  Pure Python: no device needed."""
+model.weights.bin as ml5 0.6.0 saves them) parsed into what wsa_model_create takes, and its regression models (ords_<label>/: one
+output unit, no legend, the output range in model_meta.json's outputs.y.{min,max}).  Pure Python: no device needed."""
 import json
 import os
 
@@ -15,11 +16,17 @@ class ModelFormatError(ValueError):
 
 
 class ModelSpec:
-    """units [n_layers + 1], activation names, kernels [in][out] f32, biases f32, in_min / in_max f64, labels (legend order)."""
+    """units [n_layers + 1], activation names, kernels [in][out] f32, biases f32, in_min / in_max f64, labels (legend order).
+    A regression model has out_min / out_max (the range its one output is un-normalised with) and no labels."""
 
-    def __init__(self, units, activations, kernels, biases, in_min, in_max, labels):
+    def __init__(self, units, activations, kernels, biases, in_min, in_max, labels, out_min=None, out_max=None):
         self.units, self.activations, self.kernels, self.biases = units, activations, kernels, biases
         self.in_min, self.in_max, self.labels = in_min, in_max, labels
+        self.out_min, self.out_max = out_min, out_max
+
+    @property
+    def is_regression(self):
+        return self.out_min is not None and self.out_max is not None
 
     @property
     def n_classes(self):
@@ -79,6 +86,21 @@ def parse(model_json, meta_json, weights):
         ins = meta["inputs"]
         in_min = np.array([float(ins[str(i)]["min"]) for i in range(NFEAT)])
         in_max = np.array([float(ins[str(i)]["max"]) for i in range(NFEAT)])
+        y = meta["outputs"].get("y") if isinstance(meta["outputs"], dict) else None
+        regression = isinstance(y, dict) and "legend" not in y and "min" in y and "max" in y
+        if regression:
+            out_min, out_max = float(y["min"]), float(y["max"])
+    except (KeyError, TypeError, ValueError) as e:
+        raise ModelFormatError(f"model_meta.json: no inputs '0'..'52' min / max or output legend ({e})")
+    if regression:                                   # ml5 task "regression": outputs.y = {dtype: "number", min, max}
+        if not (np.all(np.isfinite(in_min)) and np.all(np.isfinite(in_max))):
+            raise ModelFormatError("model_meta.json: non-finite input range")
+        if units[-1] != 1 or acts[-1] == "softmax":
+            raise ModelFormatError(f"model_meta.json describes a regression output; the model ends in {units[-1]} {acts[-1]} units")
+        if not (np.isfinite(out_min) and np.isfinite(out_max)) or out_max == out_min:
+            raise ModelFormatError(f"model_meta.json: output range {out_min} .. {out_max}")
+        return ModelSpec(units, acts, kernels, biases, in_min, in_max, [], out_min, out_max)
+    try:
         legend = list(meta["outputs"]["y"]["legend"].keys()) if "y" in meta["outputs"] else list(next(iter(meta["outputs"].values()))["legend"].keys())
     except (KeyError, TypeError, StopIteration) as e:
         raise ModelFormatError(f"model_meta.json: no inputs '0'..'52' min / max or output legend ({e})")
@@ -105,7 +127,10 @@ def save_dir(spec, path):
     src/neuralmodel.js), in the key layout of the directories the app ships: load_dir reads them back bit for bit, and ml5's
     neuralNetwork.load takes them."""
     nl = len(spec.kernels)
-    if len(spec.labels) != spec.units[-1]:
+    regression = getattr(spec, "is_regression", False)
+    if regression and (spec.units[-1] != 1 or spec.activations[-1] == "softmax"):
+        raise ModelFormatError(f"a regression model ends in one non-softmax unit, not {spec.units[-1]} {spec.activations[-1]}")
+    if not regression and len(spec.labels) != spec.units[-1]:
         raise ModelFormatError(f"{len(spec.labels)} legend labels for {spec.units[-1]} outputs")
     layers, weights, blob = [], [], []
     for i in range(nl):
@@ -134,6 +159,9 @@ def save_dir(spec, path):
             "outputs": {"y": {"dtype": "string", "min": 0, "max": 1, "uniqueValues": labels,
                               "legend": {lab: [1 if c == j else 0 for c in range(C)] for j, lab in enumerate(labels)}}},
             "isNormalized": True}
+    if regression:                                   # as ml5 writes a task "regression" model: no legend, the output's range
+        meta["outputUnits"] = 1
+        meta["outputs"] = {"y": {"dtype": "number", "min": float(spec.out_min), "max": float(spec.out_max)}}
     os.makedirs(path, exist_ok=True)
     with open(os.path.join(path, "model.json"), "w") as f:
         json.dump(mj, f)

@@ -1,7 +1,9 @@
 """Training the app's syllable classifiers (specification TR-1, K7): what src/neuralmodel.js:163-403 (train_nn) does around
 ml5.neuralNetwork(...).train — selecting and balancing the stored level-13 rows, the input ranges, the initial weights and the
 per-epoch orders (both from numpy's generator: the reference draws them from Math.random, so they are ours) — and the epochs on the
-GPU through capi.Trainer.  Classification only: the regression models (ords_*) and the '*' wildcard class are not supported."""
+GPU through capi.Trainer.  Classification only: the regression models (ords_*) and the '*' wildcard class are not supported.
+(That holds for prepare / stack / train.  The regression models have their own entry points below, specification TR-2:
+prepare_ordinal and train_regression.)"""
 import math
 
 import numpy as np
@@ -10,6 +12,10 @@ from . import nnmodel
 
 DEFAULT_LAYERS = [{"type": "dense", "units": 8, "activation": "relu"}, {"type": "dense", "activation": "softmax"}]   # src/neuralmodel_aux.js:106-124
 DEFAULT_LEARNING_RATE = 0.2
+# nn_default_options_ords, src/neuralmodel_aux.js:127-150 (task "regression", learningRate 0.2)
+DEFAULT_LAYERS_ORDS = [{"type": "dense", "units": 64, "activation": "sigmoid"}, {"type": "dense", "units": 16, "activation": "sigmoid"},
+                       {"type": "dense", "activation": "sigmoid"}]
+ORDINAL_RANGES = (0.25, 0.5, 0.75, 1.0)              # neuralmodel.js:281: the bins the ordinal values are balanced over
 
 
 def prepare(features, labels, classes):
@@ -100,6 +106,84 @@ def train(an, data, layers=None, learning_rate=DEFAULT_LEARNING_RATE, epochs=10,
     orders = orders if orders is not None else epoch_orders(n_train, epochs, seed + 1)
     spec = nnmodel.ModelSpec(units, acts, ks, bs, np.asarray(data["in_min"], np.float64), np.asarray(data["in_max"], np.float64), list(data["legend"]))
     tr = an.trainer(spec, data["features"], data["y"], n_val, batch_size, learning_rate)
+    try:
+        history = []
+        for e in range(epochs):
+            tr.epoch(orders[e], stream)
+            if on_epoch is not None or e == epochs - 1:
+                st = tr.stats(stream)
+                history.append(st)
+                if on_epoch is not None:
+                    on_epoch(e, st)
+        return tr.spec_now(stream), history
+    finally:
+        tr.close()
+
+
+def prepare_ordinal(features, values):
+    """The selection and balancing loop of neuralmodel.js:278-332 for an ordinal label (V, A or D).  features [n][53]; values: per row
+    the label's value or None.  A row's bin is the first of (-inf, 0.25], (0.25, 0.5], (0.5, 0.75], (0.75, 1.0] that holds its value; rows
+    with None or a value above 1.0 are dropped; the others are added in DB order; fewer than 10 of them is refused; then, only when the
+    largest bin holds more than 3, each bin with more than 3 and fewer than the largest count is topped up by cycling through the DB in
+    order until it reaches that count.  Returns dict(features, values, in_min, in_max, out_min, out_max, counts, rows): the ranges are
+    taken over the balanced set, duplicates included (ml5 normalizeData); rows are the DB indices in the order added."""
+    feat = np.asarray(features, np.float64)
+    if feat.ndim != 2 or feat.shape[1] != nnmodel.NFEAT or len(values) != len(feat):
+        raise ValueError(f"features {feat.shape} / {len(values)} values: expected [n][{nnmodel.NFEAT}] and n values")
+    nb = len(ORDINAL_RANGES)
+
+    def bin_of(v):
+        if v is None:
+            return -1
+        b = 0
+        while b < nb and not float(v) <= ORDINAL_RANGES[b]:
+            b += 1
+        return b if b < nb else -1
+
+    bins = [bin_of(v) for v in values]
+    rows = [i for i, b in enumerate(bins) if b >= 0]
+    count = [sum(1 for i in rows if bins[i] == b) for b in range(nb)]
+    if len(rows) < 10:
+        raise ValueError(f"Sample size {len(rows)}/{len(feat)} too small for training")
+    max_n = max(count)
+    if max_n > 3:
+        for b in range(nb):
+            while 3 < count[b] < max_n:
+                for i in range(len(feat)):
+                    if bins[i] == b and count[b] < max_n:
+                        rows.append(i); count[b] += 1
+                    if count[b] >= max_n:
+                        break
+    x = feat[rows]
+    y = np.array([float(values[i]) for i in rows], np.float64)
+    return dict(features=x, values=y, in_min=x.min(axis=0), in_max=x.max(axis=0), out_min=float(y.min()), out_max=float(y.max()), counts=count, rows=rows)
+
+
+def stack_regression(layers):
+    """(units, activations) of the app's options JSON `layers` for a regression task: the last layer has one unit and is not softmax."""
+    units, acts = [nnmodel.NFEAT], []
+    for i, l in enumerate(layers):
+        if l.get("type", "dense") != "dense":
+            raise ValueError(f"layer {i} is {l.get('type')!r}; only dense layers are supported")
+        units.append(1 if i == len(layers) - 1 else int(l["units"]))
+        acts.append(l.get("activation", "linear"))
+    if acts[-1] not in ("linear", "relu", "sigmoid", "tanh"):
+        raise ValueError(f"a regression model's last layer is linear, relu, sigmoid or tanh, not {acts[-1]}")
+    return units, acts
+
+
+def train_regression(an, data, layers=None, learning_rate=DEFAULT_LEARNING_RATE, epochs=10, batch_size=32, validation_split=0.1, seed=0,
+                     init=None, orders=None, on_epoch=None, stream=0):
+    """train(...) for a regression model (specification TR-2) over data = prepare_ordinal(...): the app's nn_default_options_ords stack
+    unless `layers` is given, Adam on the mean squared error of the normalised output.  Returns (nnmodel.ModelSpec with out_min /
+    out_max, history)."""
+    units, acts = stack_regression(layers or DEFAULT_LAYERS_ORDS)
+    ks, bs = init if init is not None else glorot_init(units, seed)
+    n_train, n_val = split(len(data["features"]), validation_split)
+    orders = orders if orders is not None else epoch_orders(n_train, epochs, seed + 1)
+    spec = nnmodel.ModelSpec(units, acts, ks, bs, np.asarray(data["in_min"], np.float64), np.asarray(data["in_max"], np.float64), [],
+                             float(data["out_min"]), float(data["out_max"]))
+    tr = an.regress_trainer(spec, data["features"], data["values"], n_val, batch_size, learning_rate)
     try:
         history = []
         for e in range(epochs):
