@@ -71,12 +71,16 @@ class Adam:
         self.acc1, self.acc2 = F32(self.acc1 * BETA1), F32(self.acc2 * BETA2)
 
 
-def run(x, t, kernels, biases, acts, n_val, batch, lr, orders, bias_correction=True, carry_acc=True, eps_inside=False, own_batch_size=True):
+def run(x, t, kernels, biases, acts, n_val, batch, lr, orders, bias_correction=True, carry_acc=True, eps_inside=False, own_batch_size=True,
+        grad_dtype=np.float64, fault=None):
     """x [n][53] normalised rows, t [n] normalised targets, the last n_val rows validation; orders: one sequence of n_train indices
     (or None = 0, 1, 2, ...) per epoch.  Returns one dict per epoch: loss, acc, val_loss, val_acc, correct, val_correct, kernels, biases
     (f32 copies after the epoch), min_gap (smallest |p - 0.5| of any row that can hit, in any evaluation).
     The keyword arguments select the WRONG variants the reference test must tell apart: no bias correction, the accumulated betas
-    reset at every epoch, epsilon inside the square root, means over the nominal batch size in a short last batch."""
+    reset at every epoch, epsilon inside the square root, means over the nominal batch size in a short last batch.
+    grad_dtype=np.float32 (a model of a correct f32 implementation's gradients) and fault= (one wrong variant per kernel edge) are
+    train_ref.run's."""
+    assert fault is None or fault in train_ref.FAULTS
     x, t = np.asarray(x, np.float64), np.asarray(t, np.float64)
     n = len(x)
     n_train = n - n_val
@@ -98,21 +102,35 @@ def run(x, t, kernels, biases, acts, n_val, batch, lr, orders, bias_correction=T
             div = m if own_batch_size else b_eff
             a = train_ref.forward_all(x[rows], ks, bs, acts)
             se, hit, gap = evaluate(a[-1], t[rows])
-            loss_sum += se.sum() / div * m            # the batch's mean loss, weighted by the batch's size
-            correct += int(hit.sum()); min_gap = min(min_gap, gap)
+            if fault == "rows_past_1024":
+                se, hit = se[:train_ref.LOSS_ROWS], hit[:train_ref.LOSS_ROWS]
+            if fault != "steps_past_256" or s // b_eff < train_ref.FINISH_STEPS:
+                loss_sum += se.sum() / div * m        # the batch's mean loss, weighted by the batch's size
+                correct += int(hit.sum())
+            min_gap = min(min_gap, gap)
             dz = (2.0 * (a[-1][:, 0] - t[rows]) / div)[:, None] * train_ref._dact(a[-1], acts[-1])
+            if fault == "last_row":
+                dz[m - 1] = 0.0
+            if fault == "rows_past_1024":
+                dz[train_ref.LOSS_ROWS:] = 0.0
+            if grad_dtype != np.float64:
+                dz = train_ref.f32(dz)
             opt.begin()
             for l in range(nl - 1, -1, -1):
-                dw = a[l].T @ dz
-                db = dz.sum(axis=0)
+                dw, db = train_ref.gradient_sums(a[l], dz, grad_dtype)
                 if l > 0:
-                    dz = (dz @ ks[l].astype(np.float64).T) * train_ref._dact(a[l], acts[l - 1])
+                    dz = train_ref.gradient_back(dz, ks[l], a[l], acts[l - 1], grad_dtype)
+                kept_bias = bs[l][-1]
                 ks[l] = opt.apply(l, ks[l], dw)
                 bs[l] = opt.apply(nl + l, bs[l], db)
+                if fault == "last_unit":
+                    bs[l][-1] = kept_bias
             opt.end()
         rec = dict(loss=loss_sum / n_train, acc=correct / n_train, correct=correct)
         if n_val:
             se, hit, gap = evaluate(train_ref.forward_all(x[n_train:], ks, bs, acts)[-1], t[n_train:])
+            if fault == "rows_past_1024":
+                se[train_ref.LOSS_ROWS:], hit[train_ref.LOSS_ROWS:] = 0.0, False
             rec.update(val_loss=float(se.mean()), val_acc=float(hit.mean()), val_correct=int(hit.sum()))
             min_gap = min(min_gap, gap)
         else:

@@ -57,13 +57,66 @@ def evaluate(p, t):
     return loss, hit, q < EPS, gap
 
 
-def run(x, labels, kernels, biases, acts, n_val, batch, lr, orders, clip_rule=True, own_batch_size=True):
+AMBIGUOUS = 1e-4      # a top-two probability gap below this makes a row's hit ambiguous: ten times the 1e-5 by which K6's f32 probabilities
+                      # may differ from the float64 forward (tests/test_gpu_classify.py)
+FAULTS = ("last_row", "rows_past_1024", "steps_past_256", "last_unit")
+LOSS_ROWS, FINISH_STEPS = 1024, 256          # the strides of the loss kernels' row loop and of the finish kernel's loop over step partials
+
+
+def ambiguous_rows(p):
+    """how many rows of p have a top-two probability gap below AMBIGUOUS"""
+    if p.shape[1] < 2:
+        return 0
+    top = np.sort(p, axis=1)
+    return int((top[:, -1] - top[:, -2] < AMBIGUOUS).sum())
+
+
+def f32(a):
+    """rounded to f32, held as double (as the weights are)"""
+    return np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
+
+
+def gradient_sums(a_l, dz, grad_dtype=np.float64):
+    """dW = a_l^T dz and db = 1^T dz.  grad_dtype=np.float32: both accumulated in f32 over ascending rows, four rows at a time (the
+    four products of an element are summed exactly, rounded to f32 and added to the f32 accumulator); dz holds f32 values already."""
+    if grad_dtype == np.float64:
+        return a_l.T @ dz, dz.sum(axis=0)
+    a32 = f32(a_l)
+    dw = np.zeros((a_l.shape[1], dz.shape[1]), np.float32)
+    db = np.zeros(dz.shape[1], np.float32)
+    for r in range(0, len(dz), 4):
+        dw = dw + (a32[r:r + 4].T @ dz[r:r + 4]).astype(np.float32)
+        db = db + dz[r:r + 4].sum(axis=0).astype(np.float32)
+    return dw.astype(np.float64), db.astype(np.float64)
+
+
+def gradient_back(dz, k, a_l, act, grad_dtype=np.float64):
+    """dZ of the layer below: (dz k^T) . act'(a_l).  grad_dtype=np.float32: the product accumulated in f32 over ascending columns of dz,
+    four at a time, the derivative and the result in f32."""
+    if grad_dtype == np.float64:
+        return (dz @ k.astype(np.float64).T) * _dact(a_l, act)
+    k64 = k.astype(np.float64)
+    acc = np.zeros((len(dz), k.shape[0]), np.float32)
+    for c in range(0, dz.shape[1], 4):
+        acc = acc + (dz[:, c:c + 4] @ k64[:, c:c + 4].T).astype(np.float32)
+    return (acc * _dact(a_l.astype(np.float32), act).astype(np.float32)).astype(np.float64)
+
+
+def run(x, labels, kernels, biases, acts, n_val, batch, lr, orders, clip_rule=True, own_batch_size=True, grad_dtype=np.float64, fault=None):
     """x [n][53] normalised rows, labels [n] class indices, the last n_val rows validation; orders: one sequence of n_train indices (or
     None = 0, 1, 2, ...) per epoch.  Returns a list with one dict per epoch: loss, acc, val_loss, val_acc, correct, val_correct,
     kernels, biases (f32 copies after the epoch), clipped (rows whose true-class probability was clipped from below in a step),
-    min_gap (smallest top-two probability gap of any evaluation).
+    min_gap (smallest top-two probability gap of any evaluation), ambiguous / val_ambiguous (rows of the steps' / the validation's
+    evaluations whose top-two gap is below AMBIGUOUS: a correct f32 implementation may count those the other way).
     clip_rule=False / own_batch_size=False are the two WRONG variants the reference test must tell apart: a gradient through clipped
-    rows, and means over the nominal batch size in a short last batch."""
+    rows, and means over the nominal batch size in a short last batch.
+    grad_dtype=np.float32 is a model of a CORRECT f32 implementation (not of K7's code): the layer outputs stay as they are, dZ is
+    rounded to f32 at every layer, dW, db and the backward product are f32 sums (gradient_sums, gradient_back).
+    fault= names one WRONG variant per kernel edge (tests/test_train_shapes_reference.py): "last_row" the last row of every step passes no
+    gradient; "rows_past_1024" rows 1024 and up of a step or of the validation pass are left out of the loss and hit sums and pass no
+    gradient; "steps_past_256" the partials of steps 256 and up are left out of the epoch's loss and count; "last_unit" the last unit of
+    every layer keeps its bias."""
+    assert fault is None or fault in FAULTS
     x = np.asarray(x, np.float64)
     y = np.asarray(labels, np.int64)
     n = len(x)
@@ -76,7 +129,7 @@ def run(x, labels, kernels, biases, acts, n_val, batch, lr, orders, clip_rule=Tr
     out = []
     for order in orders:
         order = np.arange(n_train) if order is None else np.asarray(order, np.int64)
-        loss_sum, correct, clipped, min_gap = 0.0, 0, 0, np.inf
+        loss_sum, correct, clipped, min_gap, ambiguous, val_ambiguous = 0.0, 0, 0, np.inf, 0, 0
         for s in range(0, n_train, b_eff):
             rows = order[s:s + b_eff]
             m = len(rows)
@@ -84,28 +137,45 @@ def run(x, labels, kernels, biases, acts, n_val, batch, lr, orders, clip_rule=Tr
             t = y[rows]
             a = forward_all(x[rows], ks, bs, acts)
             loss, hit, low, gap = evaluate(a[-1], t)
-            loss_sum += loss.sum() / div * m      # the batch's mean loss, weighted by the batch's size
-            correct += int(hit.sum()); clipped += int(low.sum()); min_gap = min(min_gap, gap)
+            ambiguous += ambiguous_rows(a[-1])
+            if fault == "rows_past_1024":
+                loss, hit = loss[:LOSS_ROWS], hit[:LOSS_ROWS]
+            if fault != "steps_past_256" or s // b_eff < FINISH_STEPS:
+                loss_sum += loss.sum() / div * m  # the batch's mean loss, weighted by the batch's size
+                correct += int(hit.sum())
+            clipped += int(low.sum()); min_gap = min(min_gap, gap)
             dz = a[-1].copy()
             dz[np.arange(m), t] -= 1.0
             dz /= div
             if clip_rule:
                 dz[low] = 0.0                     # tfjs's clipByValue passes no gradient below its minimum
+            if fault == "last_row":
+                dz[m - 1] = 0.0
+            if fault == "rows_past_1024":
+                dz[LOSS_ROWS:] = 0.0
+            if grad_dtype != np.float64:
+                dz = f32(dz)
             for l in range(len(ks) - 1, -1, -1):
-                dw = a[l].T @ dz
-                db = dz.sum(axis=0)
+                dw, db = gradient_sums(a[l], dz, grad_dtype)
                 if l > 0:
-                    dz = (dz @ ks[l].astype(np.float64).T) * _dact(a[l], acts[l - 1])
+                    dz = gradient_back(dz, ks[l], a[l], acts[l - 1], grad_dtype)
+                if fault == "last_unit":
+                    db[-1] = 0.0
                 ks[l] = (ks[l].astype(np.float64) - lr64 * dw).astype(np.float32)
                 bs[l] = (bs[l].astype(np.float64) - lr64 * db).astype(np.float32)
         rec = dict(loss=loss_sum / n_train, acc=correct / n_train, correct=correct, clipped=clipped)
         if n_val:
-            loss, hit, _, gap = evaluate(forward_all(x[n_train:], ks, bs, acts)[-1], y[n_train:])
-            rec.update(val_loss=float(loss.mean()), val_acc=float(hit.mean()), val_correct=int(hit.sum()))
+            p = forward_all(x[n_train:], ks, bs, acts)[-1]
+            loss, hit, _, gap = evaluate(p, y[n_train:])
+            val_ambiguous = ambiguous_rows(p)
+            if fault == "rows_past_1024":
+                rec.update(val_loss=float(loss[:LOSS_ROWS].sum() / n_val), val_acc=float(hit[:LOSS_ROWS].sum() / n_val), val_correct=int(hit[:LOSS_ROWS].sum()))
+            else:
+                rec.update(val_loss=float(loss.mean()), val_acc=float(hit.mean()), val_correct=int(hit.sum()))
             min_gap = min(min_gap, gap)
         else:
             rec.update(val_loss=0.0, val_acc=0.0, val_correct=0)
-        rec.update(min_gap=float(min_gap), kernels=[k.copy() for k in ks], biases=[b.copy() for b in bs])
+        rec.update(min_gap=float(min_gap), ambiguous=ambiguous, val_ambiguous=val_ambiguous, kernels=[k.copy() for k in ks], biases=[b.copy() for b in bs])
         out.append(rec)
     return out
 
