@@ -667,6 +667,69 @@ wsa_status wsa_regress_trainer_create(wsa_ctx *ctx, const wsa_model_desc *init, 
                                       const double *target, uint32_t n_rows, uint32_t n_val, uint32_t batch_size,
                                       double learning_rate, double out_min, double out_max, wsa_trainer **out);
 
+/*
+ * ---- Predicting a labelled feature DB and the app's results table (additions within version 5: probe for wsa_dbstats_create).
+ * Stands in for the reference APPLICATION's "Predict" button and the panel it fills: src/neuralmodel.js:410-535 (start_nn_prediction ->
+ * predict_db_nn -> nn_db_results_handler) runs a model over EVERY stored row of a DB, update_pred_label (src/localstore.js:723-769)
+ * writes each row's prediction into the row's `pred` pair, and shows_stats_table (src/localstore.js:498-627) counts, per categorical
+ * head, correct / wrong / blank rows and per class count, duration, correct and wrong, and per ordinal head the range, the samples, the
+ * predicted rows and the squared error.  Specification DS-1 and kernels K8 of DESIGN.md (csrc/dbstats.hip).
+ * A wsa_dbstats object holds one DB on the context's device: its feature rows, one duration per row (parseFloat(time[1]),
+ * localstore.js:534) and, per head, a true column and a predicted column.  The HOST resolves everything that is a string: it builds each
+ * categorical head's vocabulary (the head's counted true labels and the model's legend labels) and applies the class-list / '*' rule of
+ * localstore.js:523; the device sees indices.  The DEVICE applies the numeric rules: the decision over a row's probabilities
+ * (neuralmodel.js nn_db_results_handler: the first entry of ml5's stably sorted result whose confidence is > a maximum that starts at 0)
+ * and "truthy and not NaN" for ordinal values (v == v && v != 0; localstore.js:587, 593), so that a predicted 0 is dropped where it is made.
+ * Every f64 sum of the table is "rows of a chunk of WSA_DBSTATS_CHUNK_ROWS consecutive rows in row order, then chunks in chunk order",
+ * whatever the grid: a run is reproducible bit for bit and a CPU restatement gives the same bits.  No floating-point atomics.
+ * A DB object belongs to the context it was created on; destroy it before that context.  One set of buffers: pass the SAME stream to
+ * every call on it.
+ */
+#define WSA_DBSTATS_MAX_CLASSES 256   /* vocabulary entries of one categorical head */
+#define WSA_DBSTATS_MAX_HEADS   8     /* heads of each kind */
+#define WSA_DBSTATS_CHUNK_ROWS  256   /* R of DS-1 */
+typedef struct wsa_dbstats wsa_dbstats;
+/* predicted_states of one categorical head (ref localstore.js:517, 541-552) */
+typedef struct { uint64_t correct, wrong, blank; } wsa_dbstats_cat;
+/* one vocabulary entry (ref localstore.js:525-548: label_class_samples / _duration / _correct / _wrong); first_row = the smallest counted
+ * row with this true class, UINT32_MAX if none: label_unique_value lists the classes in ascending first_row */
+typedef struct { uint64_t count, correct, wrong; double duration; uint32_t first_row, reserved; } wsa_dbstats_class;
+/* one ordinal head (ref localstore.js:584-598): min starts at +Infinity, max at 0, sq_sum = sum of (pred - true)^2, d * d in double */
+typedef struct { uint64_t true_n, pred_n; double min, max, sq_sum; } wsa_dbstats_ord;
+/* feat: host [n_rows][WSA_NFEAT] double (NULL: a DB that is only counted, never predicted); duration: host [n_rows] double;
+ * vocab: host [n_cat] vocabulary sizes.  Every true column starts as "does not count" and every predicted column as blank / missing.
+ * WSA_ERR_INVALID with a message: n_rows 0, more than WSA_DBSTATS_MAX_HEADS heads of a kind, no head at all, a vocabulary of 0 or of more
+ * than WSA_DBSTATS_MAX_CLASSES entries (naming the head). */
+wsa_status wsa_dbstats_create(wsa_ctx *ctx, const double *feat, const double *duration, uint32_t n_rows,
+                              uint32_t n_cat, const uint32_t *vocab, uint32_t n_ord, wsa_dbstats **out);
+void       wsa_dbstats_destroy(wsa_dbstats *db);
+/* host [n_rows] columns of categorical head `head`: true_idx -1 = the row does not count (no true pair, a falsy label, a label outside
+ * the class list: localstore.js:523), pred_idx (NULL: all blank) -1 = blank (localstore.js:537).  An index outside -1 .. V - 1 is refused
+ * naming the row.  Synchronous. */
+wsa_status wsa_dbstats_set_classes(wsa_dbstats *db, uint32_t head, const int32_t *true_idx, const int32_t *pred_idx);
+/* host [n_rows] columns of ordinal head `head`; NaN = missing; pred_value may be NULL (all missing).  The device drops 0 and NaN. */
+wsa_status wsa_dbstats_set_values(wsa_dbstats *db, uint32_t head, const double *true_value, const double *pred_value);
+/* predict_db_nn with a cats model (ref neuralmodel.js:410-535): wsa_classify_rows over all rows, then K8's decision per row into the
+ * head's predicted column: legend_to_vocab[c] (host [classes of m], each -1 .. V - 1) of the first class c in legend order with the
+ * largest probability, -1 (the reference's null) when no probability is > 0.  A NaN probability never wins (not pinned against the
+ * reference).  Only enqueues; after the first call nothing is allocated.  WSA_ERR_INVALID: a regression model (one unit without
+ * softmax), a model of another context, a DB without feature rows. */
+wsa_status wsa_dbstats_predict_classes(wsa_dbstats *db, uint32_t head, const wsa_model *m, const int32_t *legend_to_vocab, void *stream);
+/* the decision alone, on the caller's device table d_prob [n_rows][n_classes] f32, n_classes 1 .. 64 */
+wsa_status wsa_dbstats_decide_rows(wsa_dbstats *db, uint32_t head, const float *d_prob, uint32_t n_classes, const int32_t *legend_to_vocab, void *stream);
+/* predict_db_nn with an ords model (result_out[0].value): wsa_regress_rows into the head's predicted column.  Only enqueues; allocates
+ * nothing.  WSA_ERR_INVALID: everything wsa_regress_rows refuses (a classifier among it), a model of another context, no feature rows. */
+wsa_status wsa_dbstats_predict_values(wsa_dbstats *db, uint32_t head, const wsa_model *m, double out_min, double out_max, void *stream);
+/* shows_stats_table's numbers: enqueues the two passes over all heads at once, synchronises `stream` and copies out cat [n_cat],
+ * cls [sum of the vocabulary sizes] (head 0's entries first) and ord [n_ord]; a pointer may be NULL to skip it. */
+wsa_status wsa_dbstats_table(wsa_dbstats *db, void *stream, wsa_dbstats_cat *cat, wsa_dbstats_class *cls, wsa_dbstats_ord *ord);
+/* a head's predicted column, for the host to write the `pred` pairs back (update_pred_label); synchronises `stream` */
+wsa_status wsa_dbstats_copy_classes(wsa_dbstats *db, uint32_t head, void *stream, int32_t *pred_idx);
+wsa_status wsa_dbstats_copy_values(wsa_dbstats *db, uint32_t head, void *stream, double *pred_value);
+/* the probabilities the last wsa_dbstats_predict_classes decided on, prob [n_rows][n_classes] f32 (n_classes must be that model's);
+ * synchronises `stream`.  WSA_ERR_INVALID before the first prediction. */
+wsa_status wsa_dbstats_copy_probs(wsa_dbstats *db, void *stream, float *prob, uint32_t n_classes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,7 +157,11 @@ ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destr
                # additions within version 5 (probe for wsa_trainer_create): training the app's classifiers (K7, spec TR-1)
                "wsa_trainer_create", "wsa_trainer_destroy", "wsa_trainer_epoch", "wsa_trainer_stats", "wsa_trainer_copy_weights", "wsa_trainer_model",
                # additions within version 5 (probe for wsa_regress_trainer_create): the app's regression models (ords_*, spec TR-2)
-               "wsa_regress_rows", "wsa_batch_regress", "wsa_batch_copy_values", "wsa_regress_trainer_create", "wsa_queue_synchronize"]
+               "wsa_regress_rows", "wsa_batch_regress", "wsa_batch_copy_values", "wsa_regress_trainer_create", "wsa_queue_synchronize",
+               # additions within version 5 (probe for wsa_dbstats_create): predicting a labelled feature DB and the app's results table (K8, spec DS-1)
+               "wsa_dbstats_create", "wsa_dbstats_destroy", "wsa_dbstats_set_classes", "wsa_dbstats_set_values", "wsa_dbstats_predict_classes",
+               "wsa_dbstats_decide_rows", "wsa_dbstats_predict_values", "wsa_dbstats_table", "wsa_dbstats_copy_classes", "wsa_dbstats_copy_values",
+               "wsa_dbstats_copy_probs"]
 
 _LIB = None
 _U32_RESULT = ("wsa_stream_input_capacity", "wsa_stream_paced_input", "wsa_stream_input_stride", "wsa_stream_step_frame_capacity", "wsa_stream_frames_bound")
@@ -281,12 +285,23 @@ def lib():
     L.wsa_batch_regress.argtypes = [vp, vp, dbl, dbl, vp]
     L.wsa_batch_copy_values.argtypes = [vp, vp, vp, u32, ctypes.POINTER(u32)]
     L.wsa_regress_trainer_create.argtypes = [vp, ctypes.POINTER(_ModelDesc), vp, vp, u32, u32, u32, dbl, dbl, dbl, ctypes.POINTER(vp)]
+    L.wsa_dbstats_create.argtypes = [vp, vp, vp, u32, u32, vp, u32, ctypes.POINTER(vp)]
+    L.wsa_dbstats_destroy.argtypes = [vp]
+    L.wsa_dbstats_set_classes.argtypes = [vp, u32, vp, vp]
+    L.wsa_dbstats_set_values.argtypes = [vp, u32, vp, vp]
+    L.wsa_dbstats_predict_classes.argtypes = [vp, u32, vp, vp, vp]
+    L.wsa_dbstats_decide_rows.argtypes = [vp, u32, vp, u32, vp, vp]
+    L.wsa_dbstats_predict_values.argtypes = [vp, u32, vp, dbl, dbl, vp]
+    L.wsa_dbstats_table.argtypes = [vp, vp, vp, vp, vp]
+    L.wsa_dbstats_copy_classes.argtypes = [vp, u32, vp, vp]
+    L.wsa_dbstats_copy_values.argtypes = [vp, u32, vp, vp]
+    L.wsa_dbstats_copy_probs.argtypes = [vp, vp, vp, u32]
     for name in ABI_SYMBOLS:
         if name in _U32_RESULT or name == "wsa_resample_ready":
             continue
         if name not in ("wsa_abi_version", "wsa_last_error", "wsa_config_default", "wsa_destroy", "wsa_batch_destroy", "wsa_resample_length",
                         "wsa_stream_destroy", "wsa_stream_samples_per_step", "wsa_stream_host_input", "wsa_gather_destroy", "wsa_host_free",
-                        "wsa_model_destroy", "wsa_ensemble_destroy", "wsa_trainer_destroy"):
+                        "wsa_model_destroy", "wsa_ensemble_destroy", "wsa_trainer_destroy", "wsa_dbstats_destroy"):
             getattr(L, name).restype = ctypes.c_int
     _LIB = L
     return L
@@ -370,6 +385,10 @@ class Analyzer:
         and their real-valued targets; the range defaults to spec.out_min / spec.out_max (webspeechanalyzer_amd.train drives it)."""
         return Trainer(self, spec, features, values, n_val, batch_size, learning_rate,
                        regression=(spec.out_min if out_min is None else out_min, spec.out_max if out_max is None else out_max))
+
+    def feature_db(self, features, durations, vocab_sizes=(), n_ord=0):
+        """K8 on this context: a labelled feature DB on the device (see FeatureDBStats; webspeechanalyzer_amd.dbstats drives it)."""
+        return FeatureDBStats(self, features, durations, vocab_sizes, n_ord)
 
     def ensemble(self, models):
         """The app's `available_DBs` on this context: a list of 1 .. 8 Models in that order (every tie between DBs goes to the earlier one)."""
@@ -788,6 +807,105 @@ class Trainer:
     def close(self):
         if self.h:
             self.L.wsa_trainer_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+DBSTATS_MAX_CLASSES, DBSTATS_MAX_HEADS, DBSTATS_CHUNK_ROWS = 256, 8, 256      # WSA_DBSTATS_* of include/wsa.h
+_DB_CAT = np.dtype([("correct", "<u8"), ("wrong", "<u8"), ("blank", "<u8")])
+_DB_CLASS = np.dtype([("count", "<u8"), ("correct", "<u8"), ("wrong", "<u8"), ("duration", "<f8"), ("first_row", "<u4"), ("reserved", "<u4")])
+_DB_ORD = np.dtype([("true_n", "<u8"), ("pred_n", "<u8"), ("min", "<f8"), ("max", "<f8"), ("sq_sum", "<f8")])
+
+
+class FeatureDBStats:
+    """wsa_dbstats: one labelled feature DB on the device (K8, spec DS-1).  features [n][53] f64 (None: a DB that is only counted) and
+    durations [n] f64 are host arrays; vocab_sizes has one vocabulary size per categorical head, n_ord is the number of ordinal heads.
+    Indices and values are what the device sees; webspeechanalyzer_amd.dbstats builds them from the app's rows."""
+
+    def __init__(self, an, features, durations, vocab_sizes=(), n_ord=0):
+        self.an, self.L = an, an.L
+        dur = np.ascontiguousarray(durations, np.float64)
+        feat = None if features is None else np.ascontiguousarray(features, np.float64)
+        if dur.ndim != 1 or (feat is not None and (feat.ndim != 2 or feat.shape != (dur.shape[0], 53))):
+            raise ValueError(f"features {None if feat is None else feat.shape} / durations {dur.shape}: expected [n][53] and [n]")
+        self.n_rows, self.vocab, self.n_ord = dur.shape[0], [int(v) for v in vocab_sizes], int(n_ord)
+        voc = np.ascontiguousarray(self.vocab, np.uint32)
+        self.h = ctypes.c_void_p()
+        an._check(self.L.wsa_dbstats_create(an.h, None if feat is None else feat.ctypes.data, dur.ctypes.data if self.n_rows else None, self.n_rows,
+                                            len(self.vocab), voc.ctypes.data if len(self.vocab) else None, self.n_ord, ctypes.byref(self.h)))
+
+    def _column(self, x, dtype, name):
+        if x is None:
+            return None
+        a = np.ascontiguousarray(x, dtype)
+        if a.shape != (self.n_rows,):
+            raise ValueError(f"{name} has shape {a.shape}, the DB has {self.n_rows} rows")
+        return a
+
+    def set_classes(self, head, true_idx, pred_idx=None):
+        """true_idx [n] (-1: the row does not count), pred_idx [n] (-1: blank) or None (all blank): vocabulary indices of categorical head `head`."""
+        t, p = self._column(true_idx, np.int32, "true_idx"), self._column(pred_idx, np.int32, "pred_idx")
+        self.an._check(self.L.wsa_dbstats_set_classes(self.h, int(head), t.ctypes.data, None if p is None else p.ctypes.data))
+
+    def set_values(self, head, true_value, pred_value=None):
+        """true_value [n], pred_value [n] or None (all missing) of ordinal head `head`; NaN = missing."""
+        t, p = self._column(true_value, np.float64, "true_value"), self._column(pred_value, np.float64, "pred_value")
+        self.an._check(self.L.wsa_dbstats_set_values(self.h, int(head), t.ctypes.data, None if p is None else p.ctypes.data))
+
+    @staticmethod
+    def _map(legend_to_vocab):
+        return np.ascontiguousarray(legend_to_vocab, np.int32)
+
+    def predict_classes(self, head, model, legend_to_vocab, stream=0):
+        """K6 over every row, then K8's decision into the head's predicted column (enqueues)."""
+        m = self._map(legend_to_vocab)
+        if m.shape != (model.n_classes,):
+            raise ValueError(f"legend_to_vocab has shape {m.shape}, the model has {model.n_classes} classes")
+        self.an._check(self.L.wsa_dbstats_predict_classes(self.h, int(head), model.h, m.ctypes.data, stream))
+
+    def decide_rows(self, head, d_prob, n_classes, legend_to_vocab, stream=0):
+        """K8's decision alone on a device table d_prob [n_rows][n_classes] f32 (enqueues)."""
+        m = self._map(legend_to_vocab)
+        if m.shape != (int(n_classes),):
+            raise ValueError(f"legend_to_vocab has shape {m.shape}, the table has {n_classes} classes")
+        self.an._check(self.L.wsa_dbstats_decide_rows(self.h, int(head), d_prob, int(n_classes), m.ctypes.data, stream))
+
+    def predict_values(self, head, model, out_min=None, out_max=None, stream=0):
+        """K6 with the regression epilogue into the head's predicted column (enqueues); the range defaults to the spec's own."""
+        lo, hi = model.out_range(out_min, out_max)
+        self.an._check(self.L.wsa_dbstats_predict_values(self.h, int(head), model.h, lo, hi, stream))
+
+    def table(self, stream=0):
+        """Synchronises; (cat [n_cat], cls [sum V], ord [n_ord]) as numpy records (wsa_dbstats_cat / _class / _ord)."""
+        cat, cls, od = np.zeros(len(self.vocab), _DB_CAT), np.zeros(sum(self.vocab), _DB_CLASS), np.zeros(self.n_ord, _DB_ORD)
+        self.an._check(self.L.wsa_dbstats_table(self.h, stream, cat.ctypes.data if len(cat) else None, cls.ctypes.data if len(cls) else None,
+                                                od.ctypes.data if len(od) else None))
+        return cat, cls, od
+
+    def pred_classes(self, head, stream=0):
+        out = np.zeros(self.n_rows, np.int32)
+        self.an._check(self.L.wsa_dbstats_copy_classes(self.h, int(head), stream, out.ctypes.data))
+        return out
+
+    def pred_values(self, head, stream=0):
+        out = np.zeros(self.n_rows, np.float64)
+        self.an._check(self.L.wsa_dbstats_copy_values(self.h, int(head), stream, out.ctypes.data))
+        return out
+
+    def probs(self, n_classes, stream=0):
+        """The probabilities the last predict_classes decided on, [n_rows][n_classes] f32."""
+        out = np.zeros((self.n_rows, int(n_classes)), np.float32)
+        self.an._check(self.L.wsa_dbstats_copy_probs(self.h, stream, out.ctypes.data, int(n_classes)))
+        return out
+
+    def close(self):
+        if self.h:
+            self.L.wsa_dbstats_destroy(self.h)
             self.h = ctypes.c_void_p()
 
     def __del__(self):

@@ -34,6 +34,7 @@ struct wsa_batch_view {
 extern "C" {
 void wsa_batch_view_internal(wsa_batch* b, wsa_batch_view* v);
 wsa_status wsa_batch_fetch_internal(wsa_batch* b, hipStream_t s);
+void wsa_model_info_internal(const wsa_model* m, wsa_ctx** ctx, int* n_classes, int* softmax);   // classify.hip, for dbstats.hip (K8)
 }              // fetch_totals: synchronise, read the counters (reruns the back end on a table overflow)
 
 // classify.hip also runs K6 / K6b inside a stream object's step (wsa_stream_set_model); stream_api.hip owns the stream object

@@ -1147,6 +1147,11 @@ void wsa_model_destroy(wsa_model* m) {
     delete m;
 }
 
+// what K8 (dbstats.hip) has to know of a model before it hands it to wsa_classify_rows / wsa_regress_rows
+void wsa_model_info_internal(const wsa_model* m, wsa_ctx** ctx, int* n_classes, int* softmax) {
+    *ctx = m->ctx; *n_classes = m->C; *softmax = m->softmax ? 1 : 0;
+}
+
 wsa_status wsa_classify_rows(const wsa_model* m, const double* d_feat, uint32_t n_rows, float* d_prob, void* stream) {
     if (!m) return WSA_ERR_INVALID;
     wsa_ctx* ctx = m->ctx;

@@ -338,6 +338,33 @@ function predictValues(handle, features) {
   if (!m) { m = nat.modelCreate(ctx, handle.spec); handle.natives.set(ctx, m); }
   return nat.regressRows(ctx, m, x, handle.spec.outMin, handle.spec.outMax);
 }
+// ---- predicting a labelled feature DB and the app's results table (ref src/neuralmodel.js:410-535 predict_db_nn, src/localstore.js:723-769
+// update_pred_label, :498-627 shows_stats_table; specification DS-1 / K8, include/wsa.h "Predicting a labelled feature DB"): what replaces the app's
+// Predict button and results panel.
+// predictDB(featureDB, {db, type: 'cats'|'ords', label, model | modelDir, classLabels, ordinalLabels}) runs the model over EVERY sample of the DB
+// (featuredb.js), fills the samples' `pred` pairs by update_pred_label's rule and returns the per-row predictions (labels or null / values);
+// FeatureDB.to_json / to_csv then export the pred_<name> columns as for imported pairs.
+// statsTable(featureDB, {db, classLabels, ordinalLabels}) -> {cats, ords, lines}: the table as data and the text the app prints (dbstats.js).
+function dbstats_device() {
+  const nat = addon();
+  const ctx = contexts_for(nat, settings.devices ? settings.devices.slice() : [settings.device])[0];
+  return {
+    predict(handle, x, ords) {
+      if (!loaded_models.has(handle) || handle.released) throw 'predictDB: the model handle was released (shutdown()) or is not one of loadModel / trainModel / trainRegression';
+      let m = handle.natives.get(ctx);
+      if (!m) { m = nat.modelCreate(ctx, handle.spec); handle.natives.set(ctx, m); }
+      return ords ? nat.dbPredict(ctx, m, x, true, handle.spec.outMin, handle.spec.outMax) : nat.dbPredict(ctx, m, x, false);
+    },
+    table(col) { return nat.dbTable(ctx, col); },
+  };
+}
+function predictDB(featureDB, o) {
+  o = Object.assign({}, o || {});
+  if (!o.model && o.modelDir) o.model = loadModel(o.modelDir);
+  if (!o.model || !o.model.spec) throw "predictDB(featureDB, {db, type: 'cats'|'ords', label, model | modelDir, classLabels, ordinalLabels})";
+  return require('./dbstats.js').predictDB(dbstats_device(), featureDB, o);
+}
+function statsTable(featureDB, o) { return require('./dbstats.js').statsTable(dbstats_device(), featureDB, o || {}); }
 function saveModel(handle, dir) {
   if (!handle || !handle.spec) throw 'saveModel(handle, dir)';
   require('./trainmodel.js').saveModelFiles(handle.spec, dir);
@@ -915,4 +942,4 @@ function set_predicted_label_for_segment(si, idx, label) {                      
 
 module.exports = { configure, LaunchAudioNodes, StopAudioNodes, set_predicted_label_for_segment, LaunchBatch, LaunchBatches,
   StreamOpen, STREAM_ACTIVE, STREAM_START, STREAM_STOP, shutdown, allocPinned, freePinned,
-  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, loadModel, setPredictionModel, setPredictionModels, trainModel, saveModel, trainRegression, predictValues };
+  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, loadModel, setPredictionModel, setPredictionModels, trainModel, saveModel, trainRegression, predictValues, predictDB, statsTable };

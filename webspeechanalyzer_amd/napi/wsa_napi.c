@@ -1173,6 +1173,99 @@ static napi_value fn_regress_rows(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* ---- predicting a labelled feature DB and the app's results table (wsa_dbstats_*, K8, specification DS-1): what the app's Predict button does over
+ * the stored rows (ref src/neuralmodel.js:410-535 predict_db_nn, src/localstore.js:498-627 shows_stats_table).  Both calls are synchronous and
+ * build the device object for the call; js/dbstats.js resolves everything that is a string and hands over indices and values.
+ *   dbPredict(ctx, model, features: Float64Array [n][53], ords: boolean, outMin, outMax) -> Int32Array [n] legend indices (-1 = the reference's
+ *     null) for a classifier, Float64Array [n] values for a regression model
+ *   dbTable(ctx, {durations: Float64Array [n], vocab: Uint32Array [nCat], trueIdx, predIdx: Int32Array [nCat][n], trueVal, predVal: Float64Array
+ *     [nOrd][n]}) -> {cat: Float64Array [nCat][3] correct, wrong, blank; cls: Float64Array [sum vocab][5] count, correct, wrong, duration,
+ *     first_row (4294967295 = none); ord: Float64Array [nOrd][5] true_n, pred_n, min, max, sq_sum} */
+static int typed_arg(napi_env env, napi_value v, napi_typedarray_type want, void **data, size_t *len) {
+    bool ta = false; napi_typedarray_type t;
+    if (napi_is_typedarray(env, v, &ta) != napi_ok || !ta) return 0;
+    return napi_get_typedarray_info(env, v, &t, len, data, NULL, NULL) == napi_ok && t == want;
+}
+static napi_value fn_db_predict(napi_env env, napi_callback_info info) {
+    size_t argc = 6; napi_value argv[6]; void *p = NULL;
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ctx_box *box = argc ? get_box(env, argv[0]) : NULL;
+    const char *usage = "dbPredict(ctx, model, features: Float64Array [n][53], ords: boolean, outMin, outMax)";
+    size_t nf = 0; void *feat = NULL; bool ords = false; double lo = 0, hi = 1;
+    if (!box || !box->ctx || argc < 4 || napi_get_value_external(env, argv[1], &p) != napi_ok || !p || !typed_arg(env, argv[2], napi_float64_array, &feat, &nf) ||
+        nf % WSA_NFEAT || nf / WSA_NFEAT > 0xffffffffu || napi_get_value_bool(env, argv[3], &ords) != napi_ok ||
+        (ords && (argc < 6 || napi_get_value_double(env, argv[4], &lo) != napi_ok || napi_get_value_double(env, argv[5], &hi) != napi_ok))) {
+        napi_throw_type_error(env, NULL, usage); return NULL;
+    }
+    model_box *mb = (model_box *)p;
+    if (!mb->m || mb->owner != box) { napi_throw_error(env, NULL, "dbPredict: the model was destroyed or belongs to another context"); return NULL; }
+    const uint32_t n = (uint32_t)(nf / WSA_NFEAT), vocab = mb->n_classes;
+    double *dur = calloc(n ? n : 1, sizeof(double));
+    void *out = malloc((n ? n : 1) * sizeof(double));
+    int32_t map[WSA_MODEL_MAX_CLASSES];
+    for (int c = 0; c < WSA_MODEL_MAX_CLASSES; c++) map[c] = c;
+    wsa_dbstats *db = NULL;
+    wsa_status st = dur && out ? wsa_dbstats_create(box->ctx, (const double *)feat, dur, n, ords ? 0 : 1, &vocab, ords ? 1 : 0, &db) : WSA_ERR_INVALID;
+    if (st == WSA_OK) st = ords ? wsa_dbstats_predict_values(db, 0, mb->m, lo, hi, box->queue) : wsa_dbstats_predict_classes(db, 0, mb->m, map, box->queue);
+    if (st == WSA_OK) st = ords ? wsa_dbstats_copy_values(db, 0, box->queue, (double *)out) : wsa_dbstats_copy_classes(db, 0, box->queue, (int32_t *)out);
+    napi_value res = NULL;
+    if (st == WSA_OK) res = ords ? make_typed(env, napi_float64_array, out, n, sizeof(double)) : make_typed(env, napi_int32_array, out, n, sizeof(int32_t));
+    else napi_throw_error(env, NULL, dur && out ? wsa_last_error(box->ctx) : "out of memory");
+    if (db) wsa_dbstats_destroy(db);
+    free(dur); free(out);
+    return res;
+}
+static napi_value fn_db_table(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ctx_box *box = argc ? get_box(env, argv[0]) : NULL;
+    const char *usage = "dbTable(ctx, {durations: Float64Array [n], vocab: Uint32Array [nCat], trueIdx, predIdx: Int32Array [nCat][n], trueVal, predVal: Float64Array [nOrd][n]})";
+    double *dur = NULL, *tv = NULL, *pv = NULL; uint32_t *vocab = NULL; int32_t *ti = NULL, *pi = NULL;
+    size_t n = 0, n_cat = 0, nti = 0, npi = 0, ntv = 0, npv = 0;
+    if (!box || !box->ctx || argc < 2 || !typed_of(env, argv[1], "durations", napi_float64_array, (void **)&dur, &n) ||
+        !typed_of(env, argv[1], "vocab", napi_uint32_array, (void **)&vocab, &n_cat) || !typed_of(env, argv[1], "trueIdx", napi_int32_array, (void **)&ti, &nti) ||
+        !typed_of(env, argv[1], "predIdx", napi_int32_array, (void **)&pi, &npi) || !typed_of(env, argv[1], "trueVal", napi_float64_array, (void **)&tv, &ntv) ||
+        !typed_of(env, argv[1], "predVal", napi_float64_array, (void **)&pv, &npv) || n < 1 || n > 0xffffffffu || nti != n_cat * n || npi != nti || ntv % n || npv != ntv) {
+        napi_throw_type_error(env, NULL, usage); return NULL;
+    }
+    const size_t n_ord = ntv / n;
+    if (n_cat > 0xffff || n_ord > 0xffff) { napi_throw_type_error(env, NULL, usage); return NULL; }
+    wsa_dbstats *db = NULL;
+    wsa_status st = wsa_dbstats_create(box->ctx, NULL, dur, (uint32_t)n, (uint32_t)n_cat, vocab, (uint32_t)n_ord, &db);
+    size_t items = 0;
+    for (size_t h = 0; st == WSA_OK && h < n_cat; h++) { items += vocab[h]; st = wsa_dbstats_set_classes(db, (uint32_t)h, ti + h * n, pi + h * n); }
+    for (size_t o = 0; st == WSA_OK && o < n_ord; o++) st = wsa_dbstats_set_values(db, (uint32_t)o, tv + o * n, pv + o * n);
+    wsa_dbstats_cat *cat = calloc(n_cat ? n_cat : 1, sizeof *cat); wsa_dbstats_class *cls = calloc(items ? items : 1, sizeof *cls);
+    wsa_dbstats_ord *od = calloc(n_ord ? n_ord : 1, sizeof *od);
+    double *flat = calloc((n_cat * 3 + items * 5 + n_ord * 5) + 1, sizeof(double));
+    napi_value res = NULL;
+    if (st == WSA_OK && !(cat && cls && od && flat)) { napi_throw_error(env, NULL, "out of memory"); goto done; }
+    if (st == WSA_OK) st = wsa_dbstats_table(db, box->queue, cat, cls, od);
+    if (st != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(box->ctx)); goto done; }
+    {
+        double *fc = flat, *fk = fc + n_cat * 3, *fo = fk + items * 5;
+        for (size_t h = 0; h < n_cat; h++) { fc[h * 3] = (double)cat[h].correct; fc[h * 3 + 1] = (double)cat[h].wrong; fc[h * 3 + 2] = (double)cat[h].blank; }
+        for (size_t i = 0; i < items; i++) {
+            fk[i * 5] = (double)cls[i].count; fk[i * 5 + 1] = (double)cls[i].correct; fk[i * 5 + 2] = (double)cls[i].wrong;
+            fk[i * 5 + 3] = cls[i].duration; fk[i * 5 + 4] = (double)cls[i].first_row;
+        }
+        for (size_t o = 0; o < n_ord; o++) {
+            fo[o * 5] = (double)od[o].true_n; fo[o * 5 + 1] = (double)od[o].pred_n; fo[o * 5 + 2] = od[o].min; fo[o * 5 + 3] = od[o].max; fo[o * 5 + 4] = od[o].sq_sum;
+        }
+        napi_value a, b, c;
+        if (napi_create_object(env, &res) != napi_ok) { res = NULL; goto done; }
+        a = make_typed(env, napi_float64_array, fc, n_cat * 3, sizeof(double));
+        b = make_typed(env, napi_float64_array, fk, items * 5, sizeof(double));
+        c = make_typed(env, napi_float64_array, fo, n_ord * 5, sizeof(double));
+        if (!a || !b || !c || napi_set_named_property(env, res, "cat", a) != napi_ok || napi_set_named_property(env, res, "cls", b) != napi_ok ||
+            napi_set_named_property(env, res, "ord", c) != napi_ok) res = NULL;
+    }
+done:
+    if (db) wsa_dbstats_destroy(db);
+    free(cat); free(cls); free(od); free(flat);
+    return res;
+}
+
 NAPI_MODULE_INIT() {
     /* the structures below follow the header this file was compiled against: refuse a libwsa.so of another ABI version */
     if (wsa_abi_version() != WSA_ABI_VERSION) { napi_throw_error(env, NULL, "libwsa.so ABI version differs from the one wsa_napi.node was built against (include/wsa.h): rebuild"); return NULL; }
@@ -1180,7 +1273,8 @@ NAPI_MODULE_INIT() {
         {"abiVersion", fn_abi_version}, {"freePinned", fn_free_pinned}, {"defaults", fn_defaults}, {"create", fn_create}, {"destroy", fn_destroy},
         {"geometry", fn_geometry}, {"allocPinned", fn_alloc_pinned}, {"binsHz", fn_bins_hz}, {"processBatch", fn_process_batch}, {"gatherRows", fn_gather_rows},
         {"streamOpen", fn_stream_open}, {"streamOpenMixed", fn_stream_open_mixed}, {"streamInfo", fn_stream_info}, {"streamPaced", fn_stream_paced}, {"streamInput", fn_stream_input}, {"streamStep", fn_stream_step}, {"streamClose", fn_stream_close}, {"streamSetModel", fn_stream_set_model}, {"streamSetEnsemble", fn_stream_set_ensemble},
-        {"modelCreate", fn_model_create}, {"modelDestroy", fn_model_destroy}, {"train", fn_train}, {"regressRows", fn_regress_rows}};
+        {"modelCreate", fn_model_create}, {"modelDestroy", fn_model_destroy}, {"train", fn_train}, {"regressRows", fn_regress_rows},
+        {"dbPredict", fn_db_predict}, {"dbTable", fn_db_table}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;
