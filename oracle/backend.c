@@ -37,6 +37,7 @@ typedef struct {
     double feat[53];
     float *fr;              /* len x 9, level >= 4 */
     float *sm;              /* len x 3 (sum f*E, sum E, sum w*E), level >= 4 */
+    int32_t max_peaks, max_live;  /* the span's load (see wsa_or_segment_load) */
     double *trk; int32_t trk_n;   /* level 3: the ranked tracks the reference stores (`s.push(i)` @B28273), flattened:
                                    * n_tracks, then per track 10 scalars ([0] [1] [2] [4] [5] [6] [13] [14] [15] [17]) and
                                    * its six per-point arrays ([7] .. [12], `count` numbers each) */
@@ -56,6 +57,7 @@ struct wsa_or_seg {
     /* tracker module state l, s, c (@B31818) */
     VEC(track_t) tracks;
     double accS, accC;
+    int32_t max_peaks, max_live;       /* load of the tracks held now, since clear_fm (wsa_or_segment_load) */
     /* outputs */
     VEC(segment_t) segs;
     VEC(syllable_t) syls;
@@ -71,6 +73,7 @@ static void track_free(track_t *t) {
 static void clear_fm(wsa_or_seg *s) {
     for (int32_t i = 0; i < s->tracks.n; i++) track_free(&s->tracks.p[i]);
     s->tracks.n = 0; s->accS = 0; s->accC = 0;
+    s->max_peaks = 0; s->max_live = 0;
 }
 
 /* L(e) reset_segment @B25649 */
@@ -196,6 +199,11 @@ static void accumulate_fm(wsa_or_seg *S, const uint32_t *e, const peak_t *pk, in
         }
     }
     free(asg); free(best);
+    /* the load the device tracker's tables see: peaks handed in, and tracks not yet 4 filing indices old once the frame's new ones are in */
+    int32_t live = 0;
+    for (int32_t r = 0; r < S->tracks.n; r++) if (n - S->tracks.p[r].last_frame < 4) live++;
+    if (U > S->max_peaks) S->max_peaks = U;
+    if (live > S->max_live) S->max_live = live;
 }
 
 /* stats helpers: array_mean_NZ @B2203, only_std_NZ @B1978 / mean_std_NZ @B2089 (= src/stats.js:29-55) */
@@ -293,6 +301,7 @@ static void finalize(wsa_or_seg *S, double e) {
     }
     segment_t seg; memset(&seg, 0, sizeof(seg));
     seg.start = start; seg.len = len; seg.syl0 = S->syls.n;
+    seg.max_peaks = S->max_peaks; seg.max_live = S->max_live;
     if (level == 3) {            /* ref @B28273: `u.push([e,a]), ..., s.push(i)` with i = get_ranked_formants() */
         size_t words = 1;
         for (int32_t t = 0; t < nr; t++) words += 10 + 6 * (size_t)S->tracks.p[rk[t]].frames.n;
@@ -460,6 +469,9 @@ int32_t wsa_or_n_segments(const wsa_or_seg *s) { return s->segs.n; }
 void wsa_or_segment(const wsa_or_seg *s, int32_t i, int32_t out[5]) {
     const segment_t *g = &s->segs.p[i];
     out[0] = g->start; out[1] = g->len; out[2] = g->syl0; out[3] = g->nsyl; out[4] = g->has_feat;
+}
+void wsa_or_segment_load(const wsa_or_seg *s, int32_t i, int32_t out[2]) {
+    out[0] = s->segs.p[i].max_peaks; out[1] = s->segs.p[i].max_live;
 }
 const double *wsa_or_segment_features(const wsa_or_seg *s, int32_t i) { return s->segs.p[i].feat; }
 const float *wsa_or_segment_formants(const wsa_or_seg *s, int32_t i) { return s->segs.p[i].fr; }

@@ -60,6 +60,7 @@ def lib():
         getattr(L, name).argtypes = [vp]
     L.wsa_or_segment.argtypes = [vp, i32, ctypes.POINTER(i32)]
     L.wsa_or_syllable.argtypes = [vp, i32, ctypes.POINTER(i32)]
+    L.wsa_or_segment_load.argtypes = [vp, i32, ctypes.POINTER(i32)]
     for name in ("wsa_or_segment_features", "wsa_or_syllable_features"):
         getattr(L, name).restype = ctypes.POINTER(d)
         getattr(L, name).argtypes = [vp, i32]
@@ -158,7 +159,8 @@ def default_cfg(level=5, bands=128, **kw):
 def run_backend(spectra, cfg, trace=False):
     """spectra: (frames, bands) uint32.  Returns dict mirroring tests/golden/gen/ref_driver.js output:
     segments_ci [[start,len]], syllables_ci [[[start,len]...]] (levels 10/13), features
-    (level 5: [53] per segment; level 13: [[53]...] per segment), formants (level>=4)."""
+    (level 5: [53] per segment; level 13: [[53]...] per segment), formants (level>=4); load [[max peaks, max live]] per
+    segment (wsa_or_segment_load: what the device tracker's table limits are compared with)."""
     L = lib()
     spectra = np.ascontiguousarray(spectra, dtype=np.uint32)
     frames, bands = spectra.shape
@@ -176,14 +178,17 @@ def run_backend(spectra, cfg, trace=False):
         for f in range(frames):
             L.wsa_or_seg_push(h, spectra[f].ctypes.data)
         L.wsa_or_seg_finish(h)
-        out = {"segments_ci": [], "syllables_ci": [], "features": [], "formants": [], "flags": [], "sums": []}
+        out = {"segments_ci": [], "syllables_ci": [], "features": [], "formants": [], "flags": [], "sums": [], "load": []}
         info = (ctypes.c_int32 * 5)()
+        load = (ctypes.c_int32 * 2)()
         sy = (ctypes.c_int32 * 3)()
         for i in range(L.wsa_or_n_segments(h)):
             L.wsa_or_segment(h, i, info)
             start, ln, syl0, nsyl, has = list(info)
             out["segments_ci"].append([start, ln])
             out["flags"].append(has)
+            L.wsa_or_segment_load(h, i, load)
+            out["load"].append(list(load))
             if has < 0:          # straighten threw in the reference: no result entry
                 out["sums"].append(None)
                 out["formants"].append(None)

@@ -104,7 +104,10 @@ def test_gate_block_edges_and_crowded_frames(wsa):
     leaves its steady-state loops for the general path on every event.  Clips of 0, 1, 63, 64, 65, 127, 128, 129 and 200 frames, made of
     (a) speech-like random spectra and (b) saw-tooth spectra with a candidate at every other band (up to 64 per frame, amplitudes
     spread over five decades so that the floor law's arms and the d-clause are all visited), against the CPU oracle: segments, state trace
-    on every frame (general path) and callbacks (fast paths)."""
+    on every frame (general path) and callbacks (fast paths).
+    "Crowded" means the gate's work here, not the tracker's tables: counted by the oracle (run_backend's "load", what the tracker's limits are compared
+    with), the saw-tooth clips reach 55 live tracks and 29 accepted peaks in a frame, and 40 synth_clip speech clips of 400 frames 43 and 25 — past the
+    four-spans-per-wave tier's 38 / 16 by accident, short of every other limit.  The tracker at its limits: tests/test_gpu_tracker_limits.py."""
     from oracle import pyoracle
     import sys, os
     sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden", "gen"))

@@ -473,6 +473,21 @@ class Batch:
         self.an._check(self.L.wsa_batch_backend_reruns(self.h, ctypes.byref(n)))
         return n.value
 
+    def keep_counters(self, on=True):
+        """Test entry (csrc/debug.hip, not part of wsa.h): the batch's runs leave their device counters standing for tiers()."""
+        self.L.wsa_debug_batch_keep_counters.argtypes = [ctypes.c_void_p, ctypes.c_int32]
+        self.an._check(self.L.wsa_debug_batch_keep_counters(self.h, int(on)))
+        return self
+
+    def tiers(self, stream=0):
+        """Test entry: dict(flags, spans, redo) of the last run — the flag word (bit 1: the 140-entry track table overflowed), the number of spans and
+        how many of them the paired tracker kernel handed to the one-span kernel.  Needs keep_counters() before the run, and is to be read before
+        the first fetch of results (rows(), callbacks(), ...): a fetch that finds flag bit 1 reruns the back end, and these are the rerun's then."""
+        out = (ctypes.c_uint32 * 3)()
+        self.L.wsa_debug_batch_tiers.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        self.an._check(self.L.wsa_debug_batch_tiers(self.h, stream, out))
+        return dict(flags=int(out[0]), spans=int(out[1]), redo=int(out[2]))
+
     def enable_trace(self, on=True):
         self.an._check(self.L.wsa_batch_enable_trace(self.h, int(on)))
 

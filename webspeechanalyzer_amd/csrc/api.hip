@@ -47,6 +47,7 @@ struct wsa_batch {
     uint32_t *d_rs_n_in = nullptr, *d_rs_n_out = nullptr; float *d_rs_table = nullptr, *d_rs_pcm = nullptr; uint64_t rs_stride = 0;
     // ... for clips of different rates (wsa_batch_create_mixed): rate classes and the work list of K0's blocks, planned once (tables and list live on the device)
     bool rs_mixed = false; RsMixedPlan rs_plan; RsClass* d_rs_cls = nullptr; uint32_t* d_rs_clip_class = nullptr; RsWork* d_rs_work = nullptr;
+    bool keep_counters = false;          // test hook (wsa_debug_batch_tiers): the runs leave their counters standing, the next run clears in front
     bool counters_clean = false, end_clears = false, capturing = false, ever_captured = false;      // the fused compaction of the previous run has left the counters cleared: the next run launches no clear kernel
     TrackGather trk;                                                                            // level 3: wsa_batch_copy_tracks gathers through this
     std::vector<int32_t> h_trk_seg; std::vector<uint32_t> h_seg_count;                          // level 3: host copies for wsa_batch_copy_tracks
@@ -348,7 +349,7 @@ static wsa_status run_backend_stages(wsa_batch* b, const uint32_t* d_spec, bool 
     cp.host = D.tail_kernel ? nullptr : b->h_totals_dev;
     b->published = compact_is_fused(cp) && cp.host != nullptr;
     // ... and, outside a stream capture, it leaves the counters cleared for the batch's next run (a captured run keeps its own clear kernel: a graph must not depend on what ran before it)
-    const bool self_clear = b->published && !b->capturing;
+    const bool self_clear = b->published && !b->capturing && !b->keep_counters;
     cp.clr_counters = self_clear ? B.d_counters : nullptr; cp.clr_hist = self_clear ? b->d_span_hist : nullptr;
     b->end_clears = self_clear;
     launch_compact(cp, s);
@@ -663,6 +664,11 @@ void wsa_batch_view_internal(wsa_batch* b, wsa_batch_view* v) {
     v->d_meta = b->be.d_meta; v->d_feat = b->be.d_feat; v->d_row_off = b->be.d_row_off; v->reruns = b->reruns; v->cls = &b->cls; v->ecls = &b->ecls; v->cls_last = &b->cls_last;
 }
 wsa_status wsa_batch_fetch_internal(wsa_batch* b, hipStream_t s) { return fetch_totals(b, s); }
+const uint32_t* wsa_batch_counters_internal(wsa_batch* b, int keep, wsa_ctx** ctx) {
+    if (keep >= 0) b->keep_counters = keep != 0;
+    if (ctx) *ctx = b->ctx;
+    return b->be.d_counters;
+}
 
 // (gather.cpp checks that a rank's batch belongs to the rank's context)
 wsa_ctx* wsa_batch_ctx_internal(const wsa_batch* b) { return b ? b->ctx : nullptr; }

@@ -34,6 +34,9 @@ struct wsa_batch_view {
 extern "C" {
 void wsa_batch_view_internal(wsa_batch* b, wsa_batch_view* v);
 wsa_status wsa_batch_fetch_internal(wsa_batch* b, hipStream_t s);
+// debug.hip (wsa_debug_batch_tiers): keep >= 0 sets whether the batch's runs leave their device counters standing (1) instead of having the fused
+// compaction clear them for the next run (0, the default); returns the batch's 16 device counters
+const uint32_t* wsa_batch_counters_internal(wsa_batch* b, int keep, wsa_ctx** ctx);
 void wsa_model_info_internal(const wsa_model* m, wsa_ctx** ctx, int* n_classes, int* softmax);   // classify.hip, for dbstats.hip (K8)
 }              // fetch_totals: synchronise, read the counters (reruns the back end on a table overflow)
 

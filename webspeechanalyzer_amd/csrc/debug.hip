@@ -2,6 +2,7 @@
 // entry points only exercise through their consequences (tests/test_gpu_units.py).
 #include <vector>
 #include "host_plan.hpp"
+#include "api_internal.hpp"
 #include "jsmath_device.hpp"
 #include "gate_floor.hpp"
 #include "tracker_score.hpp"
@@ -170,4 +171,24 @@ extern "C" int wsa_debug_peaks_time(int32_t device, const uint32_t* spec, uint32
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     return ok ? WSA_OK : WSA_ERR_HIP;
+}
+
+// which tier of the tracker did a batch's work: out3 = {flag word (bit 0: an arena overflowed, bit 1: the 140-entry table did), spans, spans on the
+// redo list} as the batch's last run left them on the device.  A run normally ends with its compaction clearing these counters for the next run, so
+// wsa_debug_batch_keep_counters(b, 1) comes first: from then on the batch's runs leave them standing (and start with the clear kernel).  Call it behind
+// the run and BEFORE the first fetch of results: a fetch that sees flag bit 1 reruns the back end with the full table, and the counters are the rerun's then.
+extern "C" int wsa_debug_batch_keep_counters(wsa_batch* b, int32_t on) {
+    if (!b) return WSA_ERR_INVALID;
+    (void)wsa_batch_counters_internal(b, on ? 1 : 0, nullptr);
+    return WSA_OK;
+}
+extern "C" int wsa_debug_batch_tiers(wsa_batch* b, void* stream, uint32_t* out3) {
+    if (!b || !out3) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = nullptr;
+    const uint32_t* d = wsa_batch_counters_internal(b, -1, &ctx);
+    uint32_t c[16] = {0};
+    if (!ctx || !d || hipSetDevice(ctx->device) != hipSuccess) return WSA_ERR_NO_DEVICE;
+    if (hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)) != hipSuccess || hipMemcpy(c, d, sizeof(c), hipMemcpyDeviceToHost) != hipSuccess) return WSA_ERR_HIP;
+    out3[0] = c[1]; out3[1] = c[5]; out3[2] = c[6];       // d_counters[1]: flags; [4 + 1]: spans (span_order_kernel); [4 + 2]: TrParams::redo_count
+    return WSA_OK;
 }
