@@ -376,24 +376,37 @@ enum { WSA_ACT_LINEAR = 0, WSA_ACT_RELU = 1, WSA_ACT_SIGMOID = 2, WSA_ACT_TANH =
 #define WSA_MODEL_MAX_CLASSES 64
 typedef struct {
     int32_t n_layers;                     /* Dense layers, 1 .. WSA_MODEL_MAX_LAYERS */
-    const int32_t *units;                 /* [n_layers + 1]; units[0] must be WSA_NFEAT, widths <= WSA_MODEL_MAX_WIDTH,
-                                             units[n_layers] <= WSA_MODEL_MAX_CLASSES */
+    const int32_t *units;                 /* [n_layers + 1]; units[0] must be the row width of an ML level (wsa_level_feature_count:
+                                             53, 264 or 23), widths <= WSA_MODEL_MAX_WIDTH, units[n_layers] <= WSA_MODEL_MAX_CLASSES */
     const int32_t *activation;            /* [n_layers] WSA_ACT_*; softmax only on the last layer */
     const float *const *kernel;           /* [n_layers] -> [units[i]][units[i+1]] row-major (the tfjs Dense kernel) */
     const float *const *bias;             /* [n_layers] -> [units[i+1]] */
-    const double *in_min, *in_max;        /* [WSA_NFEAT] model_meta.json inputs["0".."52"].min / max */
+    const double *in_min, *in_max;        /* [units[0]] model_meta.json inputs["0" .. "units[0] - 1"].min / max */
     const char *const *labels;            /* [units[n_layers]] the legend keys in legend order, or NULL.  Only used for the order in which the
                                              fold scans labels: keys that are array indices ("0", "17") come first, ascending, as in
                                              Object.keys (ref prediction.js:134) */
 } wsa_model_desc;
+/* The feature count of one stored row at an output level whose ML panel the reference application enables (ref src/index.js:723,
+ * src/localstore.js:7 process_exp_features_len): 53 at levels 5 and 13, 264 at level 11, 23 at level 12; 0 at every other level.  A
+ * model's input count must be one of the three (anything else, the 63 of the shipped ords_V among it, is refused).  A pure function;
+ * hosts probe for this symbol to learn that models of 264 and 23 inputs are taken (an addition within version 5). */
+int32_t    wsa_level_feature_count(int32_t output_level);
 wsa_status wsa_model_create(wsa_ctx *ctx, const wsa_model_desc *d, wsa_model **out);    /* copies the weights to the context's device */
 void       wsa_model_destroy(wsa_model *m);
-/* prob[r][c] (f32, [n_rows][units[n_layers]]) of device rows feat[r][WSA_NFEAT] (double): normalised as ml5's normalizeValue
+/* prob[r][c] (f32, [n_rows][units[n_layers]]) of dense device rows feat[r][units[0]] (double): normalised as ml5's normalizeValue
  * ((x - min) / (max - min) in double, no clamping), rounded to f32, then the network.  Device pointers; asynchronous on `stream`. */
 wsa_status wsa_classify_rows(const wsa_model *m, const double *d_feat, uint32_t n_rows, float *d_prob, void *stream);
 /* After a run at output_level 5 or 13: the probabilities of every row of the batch and, at level 13 (softmax models only), the
  * fold per callback and per clip.  WSA_ERR_INVALID at any other level, for a model of another context, and for a fold requested
- * from a model without a softmax output. */
+ * from a model without a softmax output.
+ * ML at levels 11 and 12 (per-row outputs only, no fold and no per-clip sums, as at level 5):
+ *   level 11 with a 264-input model: the rows are the utterance table (wsa_device_result d_utt_feat, n_utterance_rows rows in its
+ *            order); wsa_class_result.n_rows is that count.  The app stores a file's LAST utterance row (ref src/index.js:42 stores
+ *            under part 0, every callback overwriting the one before): row d_clip_utt_off[clip + 1] - 1 of a clip that has any.
+ *   level 12 with a 23-input model: the rows are the row table, read at its stride of WSA_NFEAT, slots 0 .. 22.  A row whose slot 23
+ *            marks a thrown uncmin gets NaN in every output (written by the epilogue: deterministic, and unusable).
+ * Every other pairing of the batch's level and the model's input count is refused with a message that names both.  Ensembles and
+ * streams take 53-input models only. */
 wsa_status wsa_batch_classify(wsa_batch *b, const wsa_model *m, void *stream);
 /* Synchronises `stream` and hands out the last classification (device pointers valid until the next wsa_batch_classify with a
  * model of more classes or wsa_batch_destroy):
@@ -611,7 +624,7 @@ wsa_status wsa_stream_copy_converted(wsa_stream *st, float *out, uint32_t cap, u
 typedef struct wsa_trainer wsa_trainer;
 typedef struct { uint32_t epochs_done; double loss, acc, val_loss, val_acc; } wsa_train_stats;   /* of the last finished epoch; val_* are 0 when n_val is 0 */
 /* init: the stack with its INITIAL kernels / biases, in_min / in_max the ranges to normalise with, labels the legend (or NULL).
- * feat: host [n_rows][WSA_NFEAT] double; label: host [n_rows] class index; the last n_val rows are validation and never trained on.
+ * feat: host [n_rows][units[0]] double (dense rows of the model's input count: 53, 264 or 23); label: host [n_rows] class index; the last n_val rows are validation and never trained on.
  * A batch_size above the number of training rows is one step over all of them.  WSA_ERR_INVALID with a message: a last layer that
  * is not softmax, a label outside 0 .. classes - 1, n_val >= n_rows, batch_size 0, a learning rate that is not finite as an f32, and a
  * feature with in_max == in_min (ml5 would train on NaN inputs; refused instead, naming the feature). */
@@ -645,11 +658,12 @@ void       wsa_trainer_destroy(wsa_trainer *t);
  * does not have (ref src/prediction.js:96-101: undefined, so NaN) and defines nothing worth restating.  Streams take no regression model.
  */
 /* K6 with the un-normalising epilogue on device rows (ref src/neuralmodel.js:540-585 predict_single -> predictMultiple; :410-535
- * predict_db_nn -> result_out[0].value): d_feat [n_rows][WSA_NFEAT] f64 -> d_value [n_rows] f64 = (double)p * (out_max - out_min) +
+ * predict_db_nn -> result_out[0].value): dense d_feat [n_rows][units[0]] f64 -> d_value [n_rows] f64 = (double)p * (out_max - out_min) +
  * out_min, p the f32 output of the one unit, the product and the sum rounded separately.  Asynchronous on `stream`; allocates nothing. */
 wsa_status wsa_regress_rows(const wsa_model *m, double out_min, double out_max,
                             const double *d_feat, uint32_t n_rows, double *d_value, void *stream);
-/* The same on the rows of the batch's last run: levels 5 and 13; one value per row in the order of wsa_device_result's tables, equal bit
+/* The same on the rows of the batch's last run: levels 5 and 13 (and 11 with a 264-input model, 12 with a 23-input model: the rows
+ * and the NaN rule of wsa_batch_classify); one value per row in the order of wsa_device_result's tables, equal bit
  * for bit to wsa_regress_rows over d_feat.  Only enqueues; after the first call on a batch nothing is allocated.  Also refuses a model
  * of another context.  A batch keeps ONE last model call: after this one wsa_batch_class_result is refused, and the other way round. */
 wsa_status wsa_batch_regress(wsa_batch *b, const wsa_model *m, double out_min, double out_max, void *stream);
@@ -696,12 +710,17 @@ typedef struct { uint64_t correct, wrong, blank; } wsa_dbstats_cat;
 typedef struct { uint64_t count, correct, wrong; double duration; uint32_t first_row, reserved; } wsa_dbstats_class;
 /* one ordinal head (ref localstore.js:584-598): min starts at +Infinity, max at 0, sq_sum = sum of (pred - true)^2, d * d in double */
 typedef struct { uint64_t true_n, pred_n; double min, max, sq_sum; } wsa_dbstats_ord;
-/* feat: host [n_rows][WSA_NFEAT] double (NULL: a DB that is only counted, never predicted); duration: host [n_rows] double;
+/* feat: host [n_rows][n_feat] double (NULL: a DB that is only counted, never predicted); duration: host [n_rows] double;
  * vocab: host [n_cat] vocabulary sizes.  Every true column starts as "does not count" and every predicted column as blank / missing.
  * WSA_ERR_INVALID with a message: n_rows 0, more than WSA_DBSTATS_MAX_HEADS heads of a kind, no head at all, a vocabulary of 0 or of more
  * than WSA_DBSTATS_MAX_CLASSES entries (naming the head). */
 wsa_status wsa_dbstats_create(wsa_ctx *ctx, const double *feat, const double *duration, uint32_t n_rows,
-                              uint32_t n_cat, const uint32_t *vocab, uint32_t n_ord, wsa_dbstats **out);
+                              uint32_t n_cat, const uint32_t *vocab, uint32_t n_ord, wsa_dbstats **out);          /* n_feat = WSA_NFEAT */
+/* The same for a DB of rows of n_feat features: 53 (levels 5 and 13), 264 (level 11) or 23 (level 12), any other width is refused.
+ * wsa_dbstats_predict_classes / _predict_values refuse a model whose input count is not the DB's width (an addition within
+ * version 5: probe for wsa_level_feature_count). */
+wsa_status wsa_wide_dbstats_create(wsa_ctx *ctx, const double *feat, uint32_t n_feat, const double *duration, uint32_t n_rows,
+                                   uint32_t n_cat, const uint32_t *vocab, uint32_t n_ord, wsa_dbstats **out);
 void       wsa_dbstats_destroy(wsa_dbstats *db);
 /* host [n_rows] columns of categorical head `head`: true_idx -1 = the row does not count (no true pair, a falsy label, a label outside
  * the class list: localstore.js:523), pred_idx (NULL: all blank) -1 = blank (localstore.js:537).  An index outside -1 .. V - 1 is refused
@@ -713,7 +732,7 @@ wsa_status wsa_dbstats_set_values(wsa_dbstats *db, uint32_t head, const double *
  * head's predicted column: legend_to_vocab[c] (host [classes of m], each -1 .. V - 1) of the first class c in legend order with the
  * largest probability, -1 (the reference's null) when no probability is > 0.  A NaN probability never wins (not pinned against the
  * reference).  Only enqueues; after the first call nothing is allocated.  WSA_ERR_INVALID: a regression model (one unit without
- * softmax), a model of another context, a DB without feature rows. */
+ * softmax), a model of another context, a DB without feature rows, a model whose input count is not the DB's width. */
 wsa_status wsa_dbstats_predict_classes(wsa_dbstats *db, uint32_t head, const wsa_model *m, const int32_t *legend_to_vocab, void *stream);
 /* the decision alone, on the caller's device table d_prob [n_rows][n_classes] f32, n_classes 1 .. 64 */
 wsa_status wsa_dbstats_decide_rows(wsa_dbstats *db, uint32_t head, const float *d_prob, uint32_t n_classes, const int32_t *legend_to_vocab, void *stream);

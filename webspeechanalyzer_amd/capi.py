@@ -161,7 +161,9 @@ ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destr
                # additions within version 5 (probe for wsa_dbstats_create): predicting a labelled feature DB and the app's results table (K8, spec DS-1)
                "wsa_dbstats_create", "wsa_dbstats_destroy", "wsa_dbstats_set_classes", "wsa_dbstats_set_values", "wsa_dbstats_predict_classes",
                "wsa_dbstats_decide_rows", "wsa_dbstats_predict_values", "wsa_dbstats_table", "wsa_dbstats_copy_classes", "wsa_dbstats_copy_values",
-               "wsa_dbstats_copy_probs"]
+               "wsa_dbstats_copy_probs",
+               # additions within version 5 (probe for wsa_level_feature_count): models, training and DBs at the row widths of levels 11 and 12
+               "wsa_level_feature_count", "wsa_wide_dbstats_create"]
 
 _LIB = None
 _U32_RESULT = ("wsa_stream_input_capacity", "wsa_stream_paced_input", "wsa_stream_input_stride", "wsa_stream_step_frame_capacity", "wsa_stream_frames_bound")
@@ -286,6 +288,9 @@ def lib():
     L.wsa_batch_copy_values.argtypes = [vp, vp, vp, u32, ctypes.POINTER(u32)]
     L.wsa_regress_trainer_create.argtypes = [vp, ctypes.POINTER(_ModelDesc), vp, vp, u32, u32, u32, dbl, dbl, dbl, ctypes.POINTER(vp)]
     L.wsa_dbstats_create.argtypes = [vp, vp, vp, u32, u32, vp, u32, ctypes.POINTER(vp)]
+    L.wsa_wide_dbstats_create.argtypes = [vp, vp, u32, vp, u32, u32, vp, u32, ctypes.POINTER(vp)]
+    L.wsa_level_feature_count.argtypes = [i32]
+    L.wsa_level_feature_count.restype = i32
     L.wsa_dbstats_destroy.argtypes = [vp]
     L.wsa_dbstats_set_classes.argtypes = [vp, u32, vp, vp]
     L.wsa_dbstats_set_values.argtypes = [vp, u32, vp, vp]
@@ -297,7 +302,7 @@ def lib():
     L.wsa_dbstats_copy_values.argtypes = [vp, u32, vp, vp]
     L.wsa_dbstats_copy_probs.argtypes = [vp, vp, vp, u32]
     for name in ABI_SYMBOLS:
-        if name in _U32_RESULT or name == "wsa_resample_ready":
+        if name in _U32_RESULT or name in ("wsa_resample_ready", "wsa_level_feature_count"):
             continue
         if name not in ("wsa_abi_version", "wsa_last_error", "wsa_config_default", "wsa_destroy", "wsa_batch_destroy", "wsa_resample_length",
                         "wsa_stream_destroy", "wsa_stream_samples_per_step", "wsa_stream_host_input", "wsa_gather_destroy", "wsa_host_free",
@@ -305,6 +310,11 @@ def lib():
             getattr(L, name).restype = ctypes.c_int
     _LIB = L
     return L
+
+
+def level_feature_count(output_level):
+    """wsa_level_feature_count: 53 (levels 5 and 13), 264 (level 11), 23 (level 12), 0 at any other level."""
+    return int(lib().wsa_level_feature_count(int(output_level)))
 
 
 class Config(dict):
@@ -607,7 +617,9 @@ class Batch:
         return out
 
     def classify(self, model, stream=0):
-        """K6 (+ K6b at level 13) on the rows of the last run, enqueued on `stream` (wsa_batch_classify)."""
+        """K6 (+ K6b at level 13) on the rows of the last run, enqueued on `stream` (wsa_batch_classify).  Level 11 takes a 264-input
+        model and classifies the utterance rows (utterance()'s order), level 12 a 23-input model over slots 0 .. 22 of the rows (NaN
+        for a row whose fit threw); both give prob only."""
         self.an._check(self.L.wsa_batch_classify(self.h, model.h, stream))
         self._model = model
 
@@ -717,13 +729,14 @@ class Model:
         self.an, self.L, self.spec = an, an.L, spec
         self.labels = list(spec.labels)
         self.n_classes = spec.n_classes
+        self.n_inputs = int(spec.units[0])
         d, self._keep = _model_desc(spec)
         self.h = ctypes.c_void_p()
         an._check(self.L.wsa_model_create(an.h, ctypes.byref(d), ctypes.byref(self.h)))
         self._keep = None
 
     def classify_rows(self, d_feat, n_rows, d_prob, stream=0):
-        """K6 on device rows: d_feat [n_rows][53] f64 -> d_prob [n_rows][n_classes] f32 (device pointers, asynchronous on `stream`)."""
+        """K6 on device rows: d_feat [n_rows][n_inputs] f64 (dense) -> d_prob [n_rows][n_classes] f32 (device pointers, asynchronous on `stream`)."""
         self.an._check(self.L.wsa_classify_rows(self.h, d_feat, int(n_rows), d_prob, stream))
 
     def out_range(self, out_min=None, out_max=None):
@@ -735,7 +748,7 @@ class Model:
         return float(lo), float(hi)
 
     def regress_rows(self, d_feat, n_rows, d_value, out_min=None, out_max=None, stream=0):
-        """K6 with the un-normalising epilogue on device rows: d_feat [n_rows][53] f64 -> d_value [n_rows] f64 (device pointers,
+        """K6 with the un-normalising epilogue on device rows: d_feat [n_rows][n_inputs] f64 (dense) -> d_value [n_rows] f64 (device pointers,
         asynchronous on `stream`); the range defaults to the spec's own."""
         lo, hi = self.out_range(out_min, out_max)
         self.an._check(self.L.wsa_regress_rows(self.h, lo, hi, d_feat, int(n_rows), d_value, stream))
@@ -754,7 +767,7 @@ class Model:
 
 class Trainer:
     """wsa_trainer: minibatch SGD on the app's Dense classifiers (K7, spec TR-1).  `spec` holds the INITIAL weights, the ranges to
-    normalise with and the legend; features [n][53] f64 and labels [n] class indices are host arrays, the last n_val rows validation."""
+    normalise with and the legend; features [n][spec.units[0]] f64 (53, 264 or 23 wide) and labels [n] class indices are host arrays, the last n_val rows validation."""
 
     def __init__(self, an, spec, features, labels, n_val, batch_size, learning_rate, regression=None):
         """regression: None, or (out_min, out_max): `labels` are then real-valued targets and the trainer is TR-2's (Adam, mean squared error)"""
@@ -762,8 +775,8 @@ class Trainer:
         self.out_range = None if regression is None else (float(regression[0]), float(regression[1]))
         feat = np.ascontiguousarray(features, np.float64)
         lab = np.ascontiguousarray(labels, np.int32 if regression is None else np.float64)
-        if feat.ndim != 2 or feat.shape[1] != 53 or lab.shape != (feat.shape[0],):
-            raise ValueError(f"features {feat.shape} / labels {lab.shape}: expected [n][53] and [n]")
+        if feat.ndim != 2 or feat.shape[1] != int(spec.units[0]) or lab.shape != (feat.shape[0],):
+            raise ValueError(f"features {feat.shape} / labels {lab.shape}: expected [n][{int(spec.units[0])}] (the model's inputs) and [n]")
         self.n_rows, self.n_val, self.n_train = feat.shape[0], int(n_val), feat.shape[0] - int(n_val)
         d, keep = _model_desc(spec)
         self.h = ctypes.c_void_p()
@@ -814,7 +827,7 @@ class Trainer:
         m.an, m.L, m.spec = self.an, self.L, self.spec
         if self.out_range is not None:
             m.spec = self.spec_now(stream)
-        m.labels, m.n_classes, m._keep = list(self.spec.labels), self.spec.n_classes, None
+        m.labels, m.n_classes, m._keep, m.n_inputs = list(self.spec.labels), self.spec.n_classes, None, int(self.spec.units[0])
         m.h = ctypes.c_void_p()
         self.an._check(self.L.wsa_trainer_model(self.h, stream, ctypes.byref(m.h)))
         return m
@@ -838,7 +851,7 @@ _DB_ORD = np.dtype([("true_n", "<u8"), ("pred_n", "<u8"), ("min", "<f8"), ("max"
 
 
 class FeatureDBStats:
-    """wsa_dbstats: one labelled feature DB on the device (K8, spec DS-1).  features [n][53] f64 (None: a DB that is only counted) and
+    """wsa_dbstats: one labelled feature DB on the device (K8, spec DS-1).  features [n][53] f64, or 264 / 23 wide: the rows of level 11 / 12 (None: a DB that is only counted) and
     durations [n] f64 are host arrays; vocab_sizes has one vocabulary size per categorical head, n_ord is the number of ordinal heads.
     Indices and values are what the device sees; webspeechanalyzer_amd.dbstats builds them from the app's rows."""
 
@@ -846,13 +859,14 @@ class FeatureDBStats:
         self.an, self.L = an, an.L
         dur = np.ascontiguousarray(durations, np.float64)
         feat = None if features is None else np.ascontiguousarray(features, np.float64)
-        if dur.ndim != 1 or (feat is not None and (feat.ndim != 2 or feat.shape != (dur.shape[0], 53))):
-            raise ValueError(f"features {None if feat is None else feat.shape} / durations {dur.shape}: expected [n][53] and [n]")
+        if dur.ndim != 1 or (feat is not None and (feat.ndim != 2 or feat.shape[0] != dur.shape[0] or feat.shape[1] not in (53, 264, 23))):
+            raise ValueError(f"features {None if feat is None else feat.shape} / durations {dur.shape}: expected [n][53] (or [n][264], [n][23]) and [n]")
+        self.n_feat = 53 if feat is None else feat.shape[1]
         self.n_rows, self.vocab, self.n_ord = dur.shape[0], [int(v) for v in vocab_sizes], int(n_ord)
         voc = np.ascontiguousarray(self.vocab, np.uint32)
         self.h = ctypes.c_void_p()
-        an._check(self.L.wsa_dbstats_create(an.h, None if feat is None else feat.ctypes.data, dur.ctypes.data if self.n_rows else None, self.n_rows,
-                                            len(self.vocab), voc.ctypes.data if len(self.vocab) else None, self.n_ord, ctypes.byref(self.h)))
+        an._check(self.L.wsa_wide_dbstats_create(an.h, None if feat is None else feat.ctypes.data, self.n_feat, dur.ctypes.data if self.n_rows else None,
+                                                 self.n_rows, len(self.vocab), voc.ctypes.data if len(self.vocab) else None, self.n_ord, ctypes.byref(self.h)))
 
     def _column(self, x, dtype, name):
         if x is None:

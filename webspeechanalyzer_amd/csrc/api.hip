@@ -661,6 +661,7 @@ void wsa_queue_destroy(wsa_ctx* ctx, void* stream) {
 
 void wsa_batch_view_internal(wsa_batch* b, wsa_batch_view* v) {
     v->ctx = b->ctx; v->level = b->ctx->cfg.output_level; v->n_clips = b->n_clips; v->rows_cap = b->n_clips * (uint32_t)b->be.row_cap;
+    v->d_utt_feat = b->be.d_utt_feat; v->d_utt_off = b->be.d_utt_off; v->utt_cap = b->n_clips * (uint32_t)b->be.seg_cap;
     v->d_meta = b->be.d_meta; v->d_feat = b->be.d_feat; v->d_row_off = b->be.d_row_off; v->reruns = b->reruns; v->cls = &b->cls; v->ecls = &b->ecls; v->cls_last = &b->cls_last;
 }
 wsa_status wsa_batch_fetch_internal(wsa_batch* b, hipStream_t s) { return fetch_totals(b, s); }

@@ -27,6 +27,7 @@ void wsa_ecls_free(wsa_ecls* c);
 struct wsa_batch_view {
     wsa_ctx* ctx; int level; uint32_t n_clips, rows_cap;
     const int32_t* d_meta; const double* d_feat; const uint32_t* d_row_off;     // compacted rows, d_row_off[n_clips] = rows on the device
+    const double* d_utt_feat; const uint32_t* d_utt_off; uint32_t utt_cap;      // level 11: utterance rows [..][WSA_NUTT], d_utt_off[n_clips] = their count on the device
     uint32_t reruns;                                                            // wsa_batch_backend_reruns
     wsa_cls** cls; wsa_ecls** ecls;
     int* cls_last;                                                              // 1: the last classification was one model's, 2: an ensemble's, 3: wsa_batch_regress
@@ -38,6 +39,7 @@ wsa_status wsa_batch_fetch_internal(wsa_batch* b, hipStream_t s);
 // compaction clear them for the next run (0, the default); returns the batch's 16 device counters
 const uint32_t* wsa_batch_counters_internal(wsa_batch* b, int keep, wsa_ctx** ctx);
 void wsa_model_info_internal(const wsa_model* m, wsa_ctx** ctx, int* n_classes, int* softmax);   // classify.hip, for dbstats.hip (K8)
+int wsa_model_inputs_internal(const wsa_model* m);                                               // units[0]
 }              // fetch_totals: synchronise, read the counters (reruns the back end on a table overflow)
 
 // classify.hip also runs K6 / K6b inside a stream object's step (wsa_stream_set_model); stream_api.hip owns the stream object
@@ -58,6 +60,9 @@ wsa_status wsa_sens_create(const wsa_scls_view& v, const wsa_ensemble* e, wsa_se
 void wsa_sens_free(wsa_sens* c);
 wsa_status wsa_sens_enqueue(wsa_sens* c, hipStream_t s);
 wsa_status wsa_sens_result(wsa_sens* c, uint32_t rows, wsa_stream_ensemble_result* out);
+
+// classify.hip: NULL for the row width of an ML level (53, 264, 23), else the rest of the refusal after "the model takes N"
+const char* wsa_model_width_refusal(int n_inputs);
 
 #define HIP_TRY(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
         return wsa_api::fail((ctx), WSA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)

@@ -16,12 +16,15 @@ namespace {
 
 constexpr int CLS_THREADS = 512;                 // 8 waves: 2 per SIMD
 constexpr int CLS_LDS_BUDGET = 160 * 1024;
+constexpr int L12_NCOEF = 23;                    // level 12: slots 0 .. 22 of a row are the syllable's coefficients, slot 23 the `numeric threw` mark (coeffs.hip)
 
 struct ClsLayer { const float* w; const float* b; int kp, np, n, act; };     // w [kp][np], b [np], zero padded; n = real width
 struct ClsParams {
     ClsLayer L[WSA_MODEL_MAX_LAYERS]; int n_layers, C, S;                      // S = LDS row stride (floats)
     const double* in_min; const double* in_max;
     const double* feat; uint32_t n_rows; const uint32_t* d_n_rows;           // rows = *d_n_rows when set (a batch's count, on the device)
+    int nin, stride, nan_slot;               // inputs read per row (units[0]); doubles from one row to the next; nan_slot >= 0: a row whose
+                                             // slot nan_slot is not 0 (level 12: uncmin threw) gets NaN in every output
     float* prob;
     double* value; double out_min, out_span;                                 // value != NULL: a regression model, one f64 per row instead of prob
 };
@@ -64,8 +67,8 @@ __device__ __forceinline__ void classify_tile(const ClsParams& p, float* s_act, 
         for (int idx = tid; idx < TM * p0; idx += CLS_THREADS) {
             const int r = idx / p0, k = idx - r * p0;
             float v = 0.f;
-            if (row0 + r < n && k < WSA_NFEAT) {                               // ml5 normalizeValue in double, then the f32 tensor
-                const double x = p.feat[(size_t)(row0 + r) * WSA_NFEAT + k];
+            if (row0 + r < n && k < p.nin) {                                   // ml5 normalizeValue in double, then the f32 tensor
+                const double x = p.feat[(size_t)(row0 + r) * p.stride + k];
                 v = (float)((x - p.in_min[k]) / (p.in_max[k] - p.in_min[k]));
             }
             in[r * S + k] = v;
@@ -112,6 +115,11 @@ __device__ __forceinline__ void classify_tile(const ClsParams& p, float* s_act, 
         for (int r = tid; r < TM; r += CLS_THREADS) {
             if (row0 + r >= n) continue;
             const float* x = in + r * S;
+            if (p.nan_slot >= 0 && p.feat[(size_t)(row0 + r) * p.stride + p.nan_slot] != 0.0) {   // no coefficients: nothing to predict from
+                if (p.value) p.value[row0 + r] = __longlong_as_double(0x7ff8000000000000ll);
+                else for (int c = 0; c < p.C; c++) p.prob[(size_t)(row0 + r) * p.C + c] = __int_as_float(0x7fc00000);
+                continue;
+            }
             if (p.value) {                                                  // K6's regression epilogue: the one unit's output, un-normalised
                 p.value[row0 + r] = unnormalise_value(x[0], p.out_min, p.out_span);
                 continue;
@@ -624,7 +632,7 @@ __global__ void __launch_bounds__(256) stream_decide_kernel(StreamEnsParams p) {
 
 struct wsa_model {
     wsa_ctx* ctx = nullptr;
-    int n_layers = 0, C = 0, S = 0, rb = 0;
+    int n_layers = 0, C = 0, S = 0, rb = 0, nin = 0;      // nin = units[0], the row width of the level the model was trained at
     ClsLayer L[WSA_MODEL_MAX_LAYERS] = {};
     double *d_min = nullptr, *d_max = nullptr;
     int32_t* d_key_rank = nullptr;
@@ -700,6 +708,7 @@ ClsParams cls_params(const wsa_model* m, const double* feat, uint32_t n_rows, co
     for (int l = 0; l < m->n_layers; l++) p.L[l] = m->L[l];
     p.n_layers = m->n_layers; p.C = m->C; p.S = m->S; p.in_min = m->d_min; p.in_max = m->d_max;
     p.feat = feat; p.n_rows = n_rows; p.d_n_rows = d_n_rows; p.prob = prob;
+    p.nin = m->nin; p.stride = m->nin; p.nan_slot = -1;                       // dense rows of the model's own width
     return p;
 }
 
@@ -738,14 +747,37 @@ const char* regress_refusal(const wsa_model* m, double out_min, double out_max) 
     return nullptr;
 }
 
+// the rows a batch hands K6: the row table (levels 5 and 13; level 12 at its stride of WSA_NFEAT, slots 0 .. 22, slot 23 the throw mark)
+// or the utterance table (level 11); both counts sit on the device
+ClsParams batch_params(const wsa_batch_view& v, const wsa_model* m, float* prob) {
+    ClsParams p = cls_params(m, v.d_feat, 0, v.d_row_off + v.n_clips, prob);
+    if (v.level == 11) { p.feat = v.d_utt_feat; p.d_n_rows = v.d_utt_off + v.n_clips; }
+    if (v.level == 12) { p.stride = WSA_NFEAT; p.nan_slot = L12_NCOEF; }
+    return p;
+}
+
+// every pairing of a batch's level and a model's input count but 5 / 13 with 53, 11 with 264 and 12 with 23 is refused
+wsa_status batch_pairing_check(wsa_ctx* ctx, const char* entry, int level, const wsa_model* m) {
+    const int have = wsa_level_feature_count(level);
+    if (have == m->nin) return WSA_OK;
+    const char* levels = m->nin == WSA_NUTT ? "output_level 11 (utterance features)" : m->nin == L12_NCOEF ? "output_level 12 (syllable coefficients)"
+                                            : "output_level 5 (segment features) or 13 (syllable features)";
+    return fail(ctx, WSA_ERR_INVALID, std::string(entry) + " needs a batch at " + levels + ", not " + std::to_string(level) + ": the model takes " + std::to_string(m->nin)
+                                      + " inputs" + (have ? ", the rows of output_level " + std::to_string(level) + " have " + std::to_string(have) + " features" : std::string())
+                                      + " (264-input models go with output_level 11, 23-input models with output_level 12)");
+}
+
 wsa_status enqueue_batch(wsa_batch* b, const wsa_batch_view& v, wsa_cls* c, const wsa_model* m, hipStream_t s) {
     wsa_ctx* ctx = v.ctx;
+    const uint32_t cap = v.level == 11 ? v.utt_cap : v.rows_cap;
     if (*v.cls_last == 3) {                       // wsa_batch_regress: no fold, no per-callback decision
-        launch_regress(m, v.d_feat, 0, v.d_row_off + v.n_clips, v.rows_cap, c->d_value, c->out_min, c->out_span, s);
+        ClsParams p = batch_params(v, m, nullptr);
+        p.value = c->d_value; p.out_min = c->out_min; p.out_span = c->out_span;
+        launch_classify(m, p, cap, s);
         HIP_TRY(ctx, hipGetLastError());
         return WSA_OK;
     }
-    launch_classify(m, v.d_feat, 0, v.d_row_off + v.n_clips, v.rows_cap, c->d_prob, s);
+    launch_classify(m, batch_params(v, m, c->d_prob), cap, s);
     HIP_TRY(ctx, hipGetLastError());
     if (v.level == 13) {
         FoldParams f{};
@@ -836,6 +868,8 @@ wsa_status stream_cls_check(wsa_ctx* ctx, int level, const wsa_model* m) {
     if (level != 5 && level != 13)
         return fail(ctx, WSA_ERR_INVALID, "wsa_stream_set_model needs streams at output_level 5 (segment features) or 13 (syllable features), not " + std::to_string(level));
     if (m->ctx != ctx) return fail(ctx, WSA_ERR_INVALID, "the model was created on another context (or device) than the streams");
+    if (m->nin != WSA_NFEAT)
+        return fail(ctx, WSA_ERR_INVALID, "the model takes " + std::to_string(m->nin) + " inputs: streams classify the 53-feature rows of output_level 5 and 13");
     if (level == 13 && !m->softmax) return fail(ctx, WSA_ERR_INVALID, "the level-13 fold needs class probabilities: the model's last layer is not softmax");
     return WSA_OK;
 }
@@ -1086,7 +1120,22 @@ wsa_status wsa_sens_result(wsa_sens* c, uint32_t rows, wsa_stream_ensemble_resul
     return WSA_OK;
 }
 
+// NULL for the row width of an ML level, else the rest of the sentence every layer refuses the width with ("the model takes N" ...)
+const char* wsa_model_width_refusal(int n_inputs) {
+    if (n_inputs == 53 || n_inputs == 264 || n_inputs == 23) return nullptr;
+    return " inputs; the feature rows have 53 (output_level 5 and 13), 264 (output_level 11) or 23 (output_level 12)";
+}
+
 extern "C" {
+
+int32_t wsa_level_feature_count(int32_t output_level) {          // ref src/localstore.js:7 process_exp_features_len, src/index.js:723
+    switch (output_level) {
+        case 5: case 13: return WSA_NFEAT;
+        case 11: return WSA_NUTT;
+        case 12: return L12_NCOEF;
+        default: return 0;
+    }
+}
 
 wsa_status wsa_model_create(wsa_ctx* ctx, const wsa_model_desc* d, wsa_model** out) {
     if (!ctx || !d || !out) return fail(ctx, WSA_ERR_INVALID, "null argument");
@@ -1094,7 +1143,8 @@ wsa_status wsa_model_create(wsa_ctx* ctx, const wsa_model_desc* d, wsa_model** o
     const int nl = d->n_layers;
     if (nl < 1 || nl > WSA_MODEL_MAX_LAYERS) return fail(ctx, WSA_ERR_INVALID, "a model has 1 .. 8 Dense layers, got " + std::to_string(nl));
     if (!d->units || !d->activation || !d->kernel || !d->bias) return fail(ctx, WSA_ERR_INVALID, "null units / activation / kernel / bias array");
-    if (d->units[0] != WSA_NFEAT) return fail(ctx, WSA_ERR_INVALID, "the model takes " + std::to_string(d->units[0]) + " inputs; the feature rows have 53");
+    if (const char* why = wsa_model_width_refusal(d->units[0])) return fail(ctx, WSA_ERR_INVALID, "the model takes " + std::to_string(d->units[0]) + why);
+    const int nin = d->units[0];
     for (int l = 0; l < nl; l++) {
         const int u = d->units[l + 1];
         if (u < 1 || u > WSA_MODEL_MAX_WIDTH) return fail(ctx, WSA_ERR_INVALID, "layer " + std::to_string(l) + " has " + std::to_string(u) + " units (limit 1024)");
@@ -1105,11 +1155,11 @@ wsa_status wsa_model_create(wsa_ctx* ctx, const wsa_model_desc* d, wsa_model** o
     }
     if (d->units[nl] > WSA_MODEL_MAX_CLASSES) return fail(ctx, WSA_ERR_INVALID, "the output layer has " + std::to_string(d->units[nl]) + " units (limit 64)");
     if (!d->in_min || !d->in_max) return fail(ctx, WSA_ERR_INVALID, "null in_min / in_max");
-    for (int k = 0; k < WSA_NFEAT; k++)
+    for (int k = 0; k < nin; k++)
         if (!std::isfinite(d->in_min[k]) || !std::isfinite(d->in_max[k])) return fail(ctx, WSA_ERR_INVALID, "non-finite in_min / in_max of input " + std::to_string(k));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     wsa_model* m = new wsa_model();
-    m->ctx = ctx; m->n_layers = nl; m->C = d->units[nl]; m->softmax = d->activation[nl - 1] == WSA_ACT_SOFTMAX;
+    m->ctx = ctx; m->n_layers = nl; m->nin = nin; m->C = d->units[nl]; m->softmax = d->activation[nl - 1] == WSA_ACT_SOFTMAX;
     int pmax = 0;
     std::vector<int> pad(nl + 1);
     for (int l = 0; l <= nl; l++) pad[l] = (d->units[l] + 15) & ~15;          // 16-column blocks; K in steps of 16 (four MFMAs)
@@ -1129,9 +1179,9 @@ wsa_status wsa_model_create(wsa_ctx* ctx, const wsa_model_desc* d, wsa_model** o
     }
     std::vector<int32_t> kr(m->C, -1);
     if (d->labels) for (int c = 0; c < m->C; c++) { int32_t v; if (array_index_key(d->labels[c], &v)) kr[c] = v; }
-    ok = ok && m->mem.alloc(&m->d_min, WSA_NFEAT) && m->mem.alloc(&m->d_max, WSA_NFEAT) && m->mem.upload(&m->d_key_rank, kr)
-         && hipMemcpy(m->d_min, d->in_min, WSA_NFEAT * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
-         && hipMemcpy(m->d_max, d->in_max, WSA_NFEAT * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && m->mem.alloc(&m->d_min, (size_t)nin) && m->mem.alloc(&m->d_max, (size_t)nin) && m->mem.upload(&m->d_key_rank, kr)
+         && hipMemcpy(m->d_min, d->in_min, (size_t)nin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
+         && hipMemcpy(m->d_max, d->in_max, (size_t)nin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) {
         const std::string msg = std::string("device allocation / copy failed: ") + hipGetErrorString(hipGetLastError());
         wsa_model_destroy(m);
@@ -1151,6 +1201,7 @@ void wsa_model_destroy(wsa_model* m) {
 void wsa_model_info_internal(const wsa_model* m, wsa_ctx** ctx, int* n_classes, int* softmax) {
     *ctx = m->ctx; *n_classes = m->C; *softmax = m->softmax ? 1 : 0;
 }
+int wsa_model_inputs_internal(const wsa_model* m) { return m->nin; }
 
 wsa_status wsa_classify_rows(const wsa_model* m, const double* d_feat, uint32_t n_rows, float* d_prob, void* stream) {
     if (!m) return WSA_ERR_INVALID;
@@ -1168,8 +1219,7 @@ wsa_status wsa_batch_classify(wsa_batch* b, const wsa_model* m, void* stream) {
     wsa_batch_view v;
     wsa_batch_view_internal(b, &v);
     wsa_ctx* ctx = v.ctx;
-    if (v.level != 5 && v.level != 13)
-        return fail(ctx, WSA_ERR_INVALID, "wsa_batch_classify needs a batch at output_level 5 (segment features) or 13 (syllable features), not " + std::to_string(v.level));
+    if (const wsa_status st = batch_pairing_check(ctx, "wsa_batch_classify", v.level, m)) return st;
     if (m->ctx != ctx) return fail(ctx, WSA_ERR_INVALID, "the model was created on another context (or device) than the batch");
     if (v.level == 13 && !m->softmax) return fail(ctx, WSA_ERR_INVALID, "the level-13 fold needs class probabilities: the model's last layer is not softmax");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1177,7 +1227,8 @@ wsa_status wsa_batch_classify(wsa_batch* b, const wsa_model* m, void* stream) {
     if (!c || c->cap_c < (uint32_t)m->C) {        // first call (or a model of more classes): the only allocation of this path
         wsa_cls* n = new wsa_cls();
         n->device = ctx->device; n->cap_rows = v.rows_cap; n->cap_c = (uint32_t)m->C; n->n_clips = v.n_clips;
-        const size_t R = v.rows_cap ? v.rows_cap : 1;
+        const uint32_t cap = v.level == 11 ? v.utt_cap : v.rows_cap;           // level 11: one output row per utterance row
+        const size_t R = cap ? cap : 1;
         wsa::DevArena& A = n->mem;
         bool ok = A.alloc(&n->d_prob, R * m->C) && A.alloc(&n->d_t_label, R) && A.alloc(&n->d_t_conf, R)
                   && A.alloc(&n->d_t_n, R) && A.alloc(&n->d_t_local, R) && A.alloc(&n->d_cb, R * 4)
@@ -1220,7 +1271,7 @@ wsa_status wsa_batch_class_result(wsa_batch* b, void* stream, wsa_class_result* 
     wsa_device_result r;
     st = wsa_batch_result(b, stream, &r);
     if (st != WSA_OK) return st;
-    out->n_rows = r.n_rows; out->n_classes = (uint32_t)c->n_classes; out->n_clips = v.n_clips;
+    out->n_rows = c->level == 11 ? r.n_utterance_rows : r.n_rows; out->n_classes = (uint32_t)c->n_classes; out->n_clips = v.n_clips;
     out->d_prob = c->d_prob;
     const bool fold = c->level == 13;
     out->n_callbacks = fold ? ((const volatile uint32_t*)c->h_count)[0] : 0u;
@@ -1270,14 +1321,14 @@ wsa_status wsa_batch_regress(wsa_batch* b, const wsa_model* m, double out_min, d
     wsa_batch_view v;
     wsa_batch_view_internal(b, &v);
     wsa_ctx* ctx = v.ctx;
-    if (v.level != 5 && v.level != 13)
-        return fail(ctx, WSA_ERR_INVALID, "wsa_batch_regress needs a batch at output_level 5 (segment features) or 13 (syllable features), not " + std::to_string(v.level));
+    if (const wsa_status st = batch_pairing_check(ctx, "wsa_batch_regress", v.level, m)) return st;
     if (m->ctx != ctx) return fail(ctx, WSA_ERR_INVALID, "the model was created on another context (or device) than the batch");
     if (const char* why = regress_refusal(m, out_min, out_max)) return fail(ctx, WSA_ERR_INVALID, why);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     wsa_cls*& c = *v.cls;
     if (!c) { c = new wsa_cls(); c->device = ctx->device; c->cap_rows = v.rows_cap; c->n_clips = v.n_clips; }   // cap_c 0: a later classify builds its own tables
-    if (!c->d_value && !c->mem.alloc(&c->d_value, v.rows_cap ? v.rows_cap : 1))     // first call: the only allocation of this path
+    const uint32_t cap = v.level == 11 ? v.utt_cap : v.rows_cap;
+    if (!c->d_value && !c->mem.alloc(&c->d_value, cap ? cap : 1))                   // first call: the only allocation of this path
         return fail(ctx, WSA_ERR_HIP, std::string("device allocation failed: ") + hipGetErrorString(hipGetLastError()));
     *v.cls_last = 3;
     c->model = m; c->level = v.level; c->n_classes = 1; c->reruns = v.reruns; c->done = true;
@@ -1305,10 +1356,11 @@ wsa_status wsa_batch_copy_values(wsa_batch* b, void* stream, double* value, uint
     wsa_device_result r;
     st = wsa_batch_result(b, stream, &r);
     if (st != WSA_OK) return st;
-    if (n_rows) *n_rows = r.n_rows;
-    if (value && rows_cap < r.n_rows) return fail(ctx, WSA_ERR_INVALID, "value buffer too small");
-    if (value && r.n_rows) {
-        HIP_TRY(ctx, hipMemcpyAsync(value, c->d_value, (size_t)r.n_rows * sizeof(double), hipMemcpyDefault, s));
+    const uint32_t rows = c->level == 11 ? r.n_utterance_rows : r.n_rows;
+    if (n_rows) *n_rows = rows;
+    if (value && rows_cap < rows) return fail(ctx, WSA_ERR_INVALID, "value buffer too small");
+    if (value && rows) {
+        HIP_TRY(ctx, hipMemcpyAsync(value, c->d_value, (size_t)rows * sizeof(double), hipMemcpyDefault, s));
         HIP_TRY(ctx, hipStreamSynchronize(s));
     }
     return WSA_OK;
@@ -1323,6 +1375,8 @@ wsa_status wsa_ensemble_create(wsa_ctx* ctx, const wsa_model* const* models, uin
     for (uint32_t d = 0; d < n; d++) {
         if (!models[d]) return fail(ctx, WSA_ERR_INVALID, "member " + std::to_string(d) + " is NULL");
         if (models[d]->ctx != ctx) return fail(ctx, WSA_ERR_INVALID, "member " + std::to_string(d) + " was created on another context (or device) than the ensemble");
+        if (models[d]->nin != WSA_NFEAT)
+            return fail(ctx, WSA_ERR_INVALID, "member " + std::to_string(d) + " takes " + std::to_string(models[d]->nin) + " inputs: an ensemble classifies the 53-feature rows of output_level 5 and 13");
     }
     static std::atomic<uint64_t> serial{0};
     wsa_ensemble* e = new wsa_ensemble();

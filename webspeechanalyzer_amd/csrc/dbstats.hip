@@ -202,7 +202,7 @@ __global__ void __launch_bounds__(DS_THREADS) dbstats_sum_kernel(DsTable p) {
 
 struct wsa_dbstats {
     wsa_ctx* ctx = nullptr;
-    uint32_t n_rows = 0, n_chunks = 0, n_cat = 0, n_ord = 0, items = 0;
+    uint32_t n_rows = 0, n_chunks = 0, n_cat = 0, n_ord = 0, items = 0, n_feat = 0;     // n_feat: features per row (53, 264 or 23)
     uint32_t voff[DS_H + 1] = {};
     double *d_feat = nullptr, *d_dur = nullptr;
     int32_t *d_t_idx[DS_H] = {}, *d_p_idx[DS_H] = {};
@@ -218,6 +218,13 @@ wsa_status check_head(wsa_dbstats* db, uint32_t head, bool cat) {
     const uint32_t n = cat ? db->n_cat : db->n_ord;
     if (head >= n) return fail(db->ctx, WSA_ERR_INVALID, std::string(cat ? "categorical" : "ordinal") + " head " + std::to_string(head) + " of " + std::to_string(n));
     return WSA_OK;
+}
+
+// predict_db_nn runs a model over the stored rows as they are: the model's input count must be the DB's width
+wsa_status check_width(wsa_dbstats* db, const wsa_model* m) {
+    const int nin = wsa_model_inputs_internal(m);
+    if ((uint32_t)nin == db->n_feat) return WSA_OK;
+    return fail(db->ctx, WSA_ERR_INVALID, "the model takes " + std::to_string(nin) + " inputs; the DB's rows have " + std::to_string(db->n_feat) + " features");
 }
 
 wsa_status check_map(wsa_dbstats* db, uint32_t head, const int32_t* map, uint32_t C, DsDecide* p) {
@@ -245,8 +252,15 @@ extern "C" {
 
 wsa_status wsa_dbstats_create(wsa_ctx* ctx, const double* feat, const double* duration, uint32_t n_rows, uint32_t n_cat, const uint32_t* vocab,
                               uint32_t n_ord, wsa_dbstats** out) {
+    return wsa_wide_dbstats_create(ctx, feat, WSA_NFEAT, duration, n_rows, n_cat, vocab, n_ord, out);
+}
+
+wsa_status wsa_wide_dbstats_create(wsa_ctx* ctx, const double* feat, uint32_t n_feat, const double* duration, uint32_t n_rows, uint32_t n_cat,
+                                   const uint32_t* vocab, uint32_t n_ord, wsa_dbstats** out) {
     if (!ctx || !out) return fail(ctx, WSA_ERR_INVALID, "null argument");
     *out = nullptr;
+    if (n_feat > 0x7fffffffu || wsa_model_width_refusal((int)n_feat))
+        return fail(ctx, WSA_ERR_INVALID, "a feature DB of " + std::to_string(n_feat) + " features per row; the feature rows have 53 (output_level 5 and 13), 264 (output_level 11) or 23 (output_level 12)");
     if (n_rows == 0) return fail(ctx, WSA_ERR_INVALID, "a feature DB has at least one row");
     if (!duration) return fail(ctx, WSA_ERR_INVALID, "null duration pointer");
     if (n_cat > (uint32_t)DS_H) return fail(ctx, WSA_ERR_INVALID, std::to_string(n_cat) + " categorical heads (limit " + std::to_string(DS_H) + ")");
@@ -259,7 +273,7 @@ wsa_status wsa_dbstats_create(wsa_ctx* ctx, const double* feat, const double* du
                                               + std::to_string(WSA_DBSTATS_MAX_CLASSES) + ")");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     wsa_dbstats* db = new wsa_dbstats();
-    db->ctx = ctx; db->n_rows = n_rows; db->n_cat = n_cat; db->n_ord = n_ord;
+    db->ctx = ctx; db->n_rows = n_rows; db->n_cat = n_cat; db->n_ord = n_ord; db->n_feat = n_feat;
     db->n_chunks = (uint32_t)(((uint64_t)n_rows + DS_R - 1) / DS_R);
     for (uint32_t h = 0; h < n_cat; h++) db->voff[h + 1] = db->voff[h] + vocab[h];
     for (uint32_t h = n_cat; h < (uint32_t)DS_H; h++) db->voff[h + 1] = db->voff[h];
@@ -268,8 +282,8 @@ wsa_status wsa_dbstats_create(wsa_ctx* ctx, const double* feat, const double* du
     const std::vector<double> missing(n_rows, std::numeric_limits<double>::quiet_NaN());
     DsTable& t = db->tab;
     bool ok = db->mem.alloc(&db->d_dur, n_rows) && hipMemcpy(db->d_dur, duration, (size_t)n_rows * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-    if (feat) ok = ok && db->mem.alloc(&db->d_feat, (size_t)n_rows * WSA_NFEAT)
-                      && hipMemcpy(db->d_feat, feat, (size_t)n_rows * WSA_NFEAT * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+    if (feat) ok = ok && db->mem.alloc(&db->d_feat, (size_t)n_rows * n_feat)
+                      && hipMemcpy(db->d_feat, feat, (size_t)n_rows * n_feat * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
     for (uint32_t h = 0; h < n_cat && ok; h++) ok = db->mem.upload(&db->d_t_idx[h], blank) && db->mem.upload(&db->d_p_idx[h], blank);
     for (uint32_t o = 0; o < n_ord && ok; o++) ok = db->mem.upload(&db->d_t_val[o], missing) && db->mem.upload(&db->d_p_val[o], missing);
     ok = ok && db->mem.alloc(&t.s_u32, (size_t)db->n_chunks * 4 * db->items) && db->mem.alloc(&t.s_dur, (size_t)db->n_chunks * db->items)
@@ -350,6 +364,7 @@ wsa_status wsa_dbstats_predict_classes(wsa_dbstats* db, uint32_t head, const wsa
     if (mctx != ctx) return fail(ctx, WSA_ERR_INVALID, "the model belongs to another context");
     if (C == 1 && !softmax) return fail(ctx, WSA_ERR_INVALID, "a regression model (one unit, no softmax) predicts values, not classes: wsa_dbstats_predict_values");
     if (!db->d_feat) return fail(ctx, WSA_ERR_INVALID, "the DB was created without feature rows");
+    if (const wsa_status st = check_width(db, m)) return st;
     DsDecide p{};
     if (const wsa_status st = check_map(db, head, legend_to_vocab, (uint32_t)C, &p)) return st;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -370,6 +385,7 @@ wsa_status wsa_dbstats_predict_values(wsa_dbstats* db, uint32_t head, const wsa_
     wsa_model_info_internal(m, &mctx, &C, &softmax);
     if (mctx != ctx) return fail(ctx, WSA_ERR_INVALID, "the model belongs to another context");
     if (!db->d_feat) return fail(ctx, WSA_ERR_INVALID, "the DB was created without feature rows");
+    if (const wsa_status st = check_width(db, m)) return st;
     return wsa_regress_rows(m, out_min, out_max, db->d_feat, db->n_rows, db->d_p_val[head], stream);   // refuses a classifier and a bad range
 }
 

@@ -32,7 +32,6 @@ namespace {
 constexpr int TR_THREADS = 256;                  // 4 waves, one 16 x 16 output tile each
 constexpr int TR_WAVES = TR_THREADS / 64;
 constexpr int TR_LOSS_THREADS = 1024;
-constexpr int TR_XS = 64;                        // stride of the normalised rows: WSA_NFEAT padded to 16-column blocks
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -375,12 +374,13 @@ __global__ void __launch_bounds__(256) train_finish_kernel(TrFin p) {
     }
 }
 
-// ---- create: (x - min) / (max - min) in double, rounded to f32 (ml5 normalizeValue, as K6), rows padded to TR_XS zero columns
-__global__ void __launch_bounds__(256) train_normalise_kernel(const double* feat, const double* mn, const double* mx, uint64_t n_rows, float* x) {
+// ---- create: (x - min) / (max - min) in double, rounded to f32 (ml5 normalizeValue, as K6); feat [n_rows][nin] dense, x [n_rows][xs],
+// xs = nin padded to 16-column blocks, the padding written as zero
+__global__ void __launch_bounds__(256) train_normalise_kernel(const double* feat, const double* mn, const double* mx, uint64_t n_rows, int nin, int xs, float* x) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_rows * TR_XS) return;
-    const uint64_t r = i / TR_XS; const int k = (int)(i % TR_XS);
-    x[i] = k < WSA_NFEAT ? (float)((feat[r * WSA_NFEAT + k] - mn[k]) / (mx[k] - mn[k])) : 0.f;
+    if (i >= n_rows * (uint64_t)xs) return;
+    const uint64_t r = i / (uint64_t)xs; const int k = (int)(i % (uint64_t)xs);
+    x[i] = k < nin ? (float)((feat[r * (uint64_t)nin + k] - mn[k]) / (mx[k] - mn[k])) : 0.f;
 }
 
 }  // namespace
@@ -417,7 +417,7 @@ void enqueue_forward(wsa_trainer* t, const uint32_t* idx, uint32_t off, uint32_t
     const uint32_t mp = up16(m);
     for (int l = 0; l < t->nl; l++) {
         TrFwd f{};
-        f.in = l == 0 ? TrRows{t->d_x, TR_XS, idx, off, m} : TrRows{t->d_a[l], t->pad[l], nullptr, 0, m};
+        f.in = l == 0 ? TrRows{t->d_x, t->pad[0], idx, off, m} : TrRows{t->d_a[l], t->pad[l], nullptr, 0, m};
         f.w = t->d_w[l]; f.b = t->d_b[l]; f.out = t->d_a[l + 1];
         f.kp = t->pad[l]; f.np = t->pad[l + 1]; f.n = t->units[l + 1]; f.act = t->act[l]; f.mp = mp;
         hipLaunchKernelGGL(train_forward_kernel, dim3(blocks_for((uint64_t)(mp / 16) * (f.np / 16))), dim3(TR_THREADS), 0, s, f);
@@ -453,7 +453,7 @@ void enqueue_step(wsa_trainer* t, const uint32_t* idx, uint32_t step, hipStream_
             hipLaunchKernelGGL(train_backward_kernel, dim3(blocks_for((uint64_t)(mp / 16) * (b.kp / 16))), dim3(TR_THREADS), 0, s, b);
         }
         TrUpd u{};
-        u.a = l == 0 ? TrRows{t->d_x, TR_XS, idx, off, m} : TrRows{t->d_a[l], t->pad[l], nullptr, 0, m};
+        u.a = l == 0 ? TrRows{t->d_x, t->pad[0], idx, off, m} : TrRows{t->d_a[l], t->pad[l], nullptr, 0, m};
         u.dz = t->d_dz[cur]; u.w = t->d_w[l]; u.b = t->d_b[l];
         u.kp = t->pad[l]; u.np = t->pad[l + 1]; u.k = t->units[l]; u.n = t->units[l + 1]; u.mp = mp; u.lr = t->lr;
         const dim3 grid(blocks_for((uint64_t)(u.kp / 16 + 1) * (u.np / 16)));
@@ -480,7 +480,9 @@ wsa_status trainer_create(wsa_ctx* ctx, const wsa_model_desc* d, const double* f
     const int nl = d->n_layers;
     if (nl < 1 || nl > WSA_MODEL_MAX_LAYERS) return fail(ctx, WSA_ERR_INVALID, "a model has 1 .. 8 Dense layers, got " + std::to_string(nl));
     if (!d->units || !d->activation || !d->kernel || !d->bias) return fail(ctx, WSA_ERR_INVALID, "null units / activation / kernel / bias array");
-    if (d->units[0] != WSA_NFEAT) return fail(ctx, WSA_ERR_INVALID, "the model takes " + std::to_string(d->units[0]) + " inputs; the feature rows have 53");
+    if (const char* why = wsa_model_width_refusal(d->units[0])) return fail(ctx, WSA_ERR_INVALID, "the model takes " + std::to_string(d->units[0]) + why);
+    const int nin = d->units[0];
+    const size_t xs = (size_t)((nin + 15) & ~15);                            // stride of the normalised rows: pad[0]
     for (int l = 0; l < nl; l++) {
         const int u = d->units[l + 1], a = d->activation[l];
         if (u < 1 || u > WSA_MODEL_MAX_WIDTH) return fail(ctx, WSA_ERR_INVALID, "layer " + std::to_string(l) + " has " + std::to_string(u) + " units (limit 1024)");
@@ -495,7 +497,7 @@ wsa_status trainer_create(wsa_ctx* ctx, const wsa_model_desc* d, const double* f
     const int C = d->units[nl];
     if (C > WSA_MODEL_MAX_CLASSES) return fail(ctx, WSA_ERR_INVALID, "the output layer has " + std::to_string(C) + " units (limit 64)");
     if (!d->in_min || !d->in_max) return fail(ctx, WSA_ERR_INVALID, "null in_min / in_max");
-    for (int k = 0; k < WSA_NFEAT; k++) {
+    for (int k = 0; k < nin; k++) {
         if (!std::isfinite(d->in_min[k]) || !std::isfinite(d->in_max[k])) return fail(ctx, WSA_ERR_INVALID, "non-finite in_min / in_max of input " + std::to_string(k));
         if (d->in_max[k] == d->in_min[k]) return fail(ctx, WSA_ERR_INVALID, "feature " + std::to_string(k) + " has max == min: it cannot be normalised");
     }
@@ -519,7 +521,7 @@ wsa_status trainer_create(wsa_ctx* ctx, const wsa_model_desc* d, const double* f
     t->n_steps = (t->n_train + t->batch - 1) / t->batch;
     t->mcap = up16(t->batch > n_val ? t->batch : n_val);
     t->lr = (float)learning_rate; t->regress = regress;
-    t->in_min.assign(d->in_min, d->in_min + WSA_NFEAT); t->in_max.assign(d->in_max, d->in_max + WSA_NFEAT);
+    t->in_min.assign(d->in_min, d->in_min + nin); t->in_max.assign(d->in_max, d->in_max + nin);
     if (d->labels) { t->has_labels = true; for (int c = 0; c < C; c++) t->labels.emplace_back(d->labels[c] ? d->labels[c] : ""); }
     int pmax = 0;
     for (int l = 0; l <= nl; l++) { t->units[l] = d->units[l]; t->pad[l] = (d->units[l] + 15) & ~15; if (l && t->pad[l] > pmax) pmax = t->pad[l]; }
@@ -540,17 +542,17 @@ wsa_status trainer_create(wsa_ctx* ctx, const wsa_model_desc* d, const double* f
     {
         wsa::DevArena tmp;                                                   // the double rows live only until they are normalised
         ok = ok && t->mem.alloc(&t->d_dz[0], (size_t)t->mcap * pmax, true) && t->mem.alloc(&t->d_dz[1], (size_t)t->mcap * pmax, true)
-             && t->mem.alloc(&t->d_x, (size_t)n_rows * TR_XS) && (regress ? t->mem.alloc(&t->d_target, n_rows) && t->mem.alloc(&t->d_adam, 4) : t->mem.alloc(&t->d_label, n_rows))
+             && t->mem.alloc(&t->d_x, (size_t)n_rows * xs) && (regress ? t->mem.alloc(&t->d_target, n_rows) && t->mem.alloc(&t->d_adam, 4) : t->mem.alloc(&t->d_label, n_rows))
              && t->mem.alloc(&t->d_order, t->n_train) && t->mem.upload(&t->d_identity, ident)
              && t->mem.alloc(&t->d_part_loss, t->n_steps + 1, true) && t->mem.alloc(&t->d_part_hit, t->n_steps + 1, true)
              && t->mem.alloc(&t->d_stats, 1, true)
              && hipHostMalloc(reinterpret_cast<void**>(&t->h_order[0]), (size_t)t->n_train * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess
              && hipHostMalloc(reinterpret_cast<void**>(&t->h_order[1]), (size_t)t->n_train * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess
              && hipEventCreateWithFlags(&t->ev[0], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&t->ev[1], hipEventDisableTiming) == hipSuccess
-             && tmp.alloc(&d_feat, (size_t)n_rows * WSA_NFEAT) && tmp.alloc(&d_mn, WSA_NFEAT) && tmp.alloc(&d_mx, WSA_NFEAT)
-             && hipMemcpy(d_feat, feat, (size_t)n_rows * WSA_NFEAT * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
-             && hipMemcpy(d_mn, d->in_min, WSA_NFEAT * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
-             && hipMemcpy(d_mx, d->in_max, WSA_NFEAT * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
+             && tmp.alloc(&d_feat, (size_t)n_rows * nin) && tmp.alloc(&d_mn, (size_t)nin) && tmp.alloc(&d_mx, (size_t)nin)
+             && hipMemcpy(d_feat, feat, (size_t)n_rows * nin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
+             && hipMemcpy(d_mn, d->in_min, (size_t)nin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
+             && hipMemcpy(d_mx, d->in_max, (size_t)nin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
              && (regress ? tmp.alloc(&d_y, n_rows) && hipMemcpy(d_y, target, (size_t)n_rows * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
                          : hipMemcpy(t->d_label, label, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess);
         if (ok && regress) {
@@ -558,8 +560,8 @@ wsa_status trainer_create(wsa_ctx* ctx, const wsa_model_desc* d, const double* f
             hipLaunchKernelGGL(train_adam_reset_kernel, dim3(1), dim3(1), 0, nullptr, t->d_adam);
         }
         if (ok) {
-            const uint64_t total = (uint64_t)n_rows * TR_XS;
-            hipLaunchKernelGGL(train_normalise_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, nullptr, d_feat, d_mn, d_mx, (uint64_t)n_rows, t->d_x);
+            const uint64_t total = (uint64_t)n_rows * xs;
+            hipLaunchKernelGGL(train_normalise_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, nullptr, d_feat, d_mn, d_mx, (uint64_t)n_rows, nin, (int)xs, t->d_x);
             ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
         }
     }

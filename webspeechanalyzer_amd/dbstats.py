@@ -276,12 +276,15 @@ def predict_db(an, db_rows, heads, label_type, label_name, spec, out_min=None, o
     cats, ords = head_settings(*heads)
     if len(db_rows) < 1:
         raise ValueError("a feature DB has at least one row")
+    from . import nnmodel
     feat = np.array([r["features"] for r in db_rows], np.float64)
-    if feat.ndim != 2 or feat.shape[1] != 53:
-        raise ValueError(f"features {feat.shape}: the models take level-5 / level-13 rows of 53 features")
+    if feat.ndim != 2 or feat.shape[1] not in nnmodel.WIDTHS:
+        raise ValueError(f"features {feat.shape}: the models take level-5 / level-13 rows of 53 features (or level-11 rows of 264, level-12 rows of 23)")
     dur = np.array([parse_float(r["time"][1]) for r in db_rows], np.float64)
     model, mine = _model_of(an, spec)
     try:
+        if model.n_inputs != feat.shape[1]:              # before anything is uploaded or enqueued
+            raise ValueError(f"the model takes {model.n_inputs} inputs; the DB's rows have {feat.shape[1]} features")
         if label_type == "cats":
             legend = [js_str(x) for x in model.labels]
             if len(legend) != model.n_classes:

@@ -100,17 +100,20 @@ function updatePredLabel(sample, hd, label, value) {
   sample.guess = JSON.parse(JSON.stringify(pair));
 }
 
-// device: {predict(handle, Float64Array [n][53], ords) -> Int32Array | Float64Array, table(col) -> counters} (formantanalyzer.js binds the addon)
+// device: {predict(handle, Float64Array [n][width], ords) -> Int32Array | Float64Array, table(col) -> counters} (formantanalyzer.js binds the addon)
 function predictDB(device, featureDB, o) {
   if (!o || (o.type !== 'cats' && o.type !== 'ords') || !o.label) throw "predictDB(featureDB, {db, type: 'cats'|'ords', label, model | modelDir, classLabels, ordinalLabels})";
   const samples = featureDB.samples(o.db), hd = heads(o.classLabels, o.ordinalLabels);
   if (!samples.length) throw 'predictDB: no data for prediction';                              // neuralmodel.js:460
-  const x = new Float64Array(samples.length * 53);
-  samples.forEach((s, r) => {
-    if (s.vector.length !== 53) throw 'predictDB: row ' + r + ' has ' + s.vector.length + ' features; the models take level-5 / level-13 rows of 53';
-    for (let k = 0; k < 53; k++) x[r * 53 + k] = Number(s.vector[k]);
-  });
+  const W = samples[0].vector.length;             // the DB's width: that of an ML level, and the model's input count
+  if ([53, 264, 23].indexOf(W) < 0) throw 'predictDB: row 0 has ' + W + ' features; the models take level-5 / level-13 rows of 53 (or level-11 rows of 264, level-12 rows of 23)';
   const handle = o.model, regression = typeof handle.spec.outMin === 'number';
+  if (handle.spec.units[0] !== W) throw 'predictDB: the model takes ' + handle.spec.units[0] + ' inputs; the rows of the DB have ' + W + ' features';
+  const x = new Float64Array(samples.length * W);
+  samples.forEach((s, r) => {
+    if (s.vector.length !== W) throw 'predictDB: row ' + r + ' has ' + s.vector.length + ' features; the models take level-5 / level-13 rows of 53';
+    for (let k = 0; k < W; k++) x[r * W + k] = Number(s.vector[k]);
+  });
   if (regression !== (o.type === 'ords')) throw 'predictDB: a ' + o.type + ' prediction needs a ' + (o.type === 'ords' ? 'regression model' : 'classifier');
   const raw = device.predict(handle, x, o.type === 'ords');
   const preds = Array.from(raw, (v) => (o.type === 'ords' ? v : (v >= 0 ? handle.labels[v] : null)));

@@ -231,9 +231,10 @@ function parse_model(mj, meta, weights) {
     biases.push(new Float32Array(buf.slice(off, off + 4 * bs[0]).buffer)); off += 4 * bs[0];
     units.push(ks[1]);
   }
-  if (units[0] !== 53) throw 'loadModel: the model takes ' + units[0] + ' inputs; the feature rows have 53';
-  const inMin = new Float64Array(53), inMax = new Float64Array(53);
-  for (let k = 0; k < 53; k++) { const r = meta.inputs[String(k)]; inMin[k] = r.min; inMax[k] = r.max; }
+  const W = units[0];                   // the row width of an ML level: 53 (levels 5 and 13), 264 (level 11) or 23 (level 12)
+  if (W !== 53 && W !== 264 && W !== 23) throw 'loadModel: the model takes ' + W + ' inputs; the feature rows have 53 (output_level 5 and 13), 264 (output_level 11) or 23 (output_level 12)';
+  const inMin = new Float64Array(W), inMax = new Float64Array(W);
+  for (let k = 0; k < W; k++) { const r = meta.inputs[String(k)]; inMin[k] = r.min; inMax[k] = r.max; }
   const out = meta.outputs.y || Object.values(meta.outputs)[0];
   if (out && !out.legend && typeof out.min === 'number' && typeof out.max === 'number') {       // a regression model (ords_<label>): the output's range, no legend
     if (units[units.length - 1] !== 1 || act[act.length - 1] === ACT.softmax) throw 'loadModel: model_meta.json describes a regression output; the model does not end in one non-softmax unit';
@@ -262,7 +263,7 @@ function loadModel(src) {
   return h;
 }
 // ---- training (ref src/neuralmodel.js:163-403 train_nn + download_nn_model; K7 / specification TR-1, include/wsa.h "Training").
-// trainModel({features: [[53 numbers]], labels, classes, options, epochs, batchSize, seed, onEpoch}) -> Promise of a model handle that
+// trainModel({features: [[53 numbers]] (or rows of 264 / 23 numbers: the vectors of output_level 11 / 12), labels, classes, options, epochs, batchSize, seed, onEpoch}) -> Promise of a model handle that
 // setPredictionModel / setPredictionModels accept.  `options` is the app's options JSON ({layers, learningRate}); onEpoch(epoch, {loss, acc,
 // val_loss, val_acc}) mirrors ml5's whileTraining.  The selection, balancing, seeded initial weights and epoch orders live in trainmodel.js;
 // `init` ({kernels, biases}) and `orders` (Uint32Array [epochs][nTrain]) replace the seeded ones.  The epochs run off the JS thread.
@@ -273,7 +274,7 @@ function trainModel(o) {
   try {
     const opt = Object.assign({}, tm.DEFAULT_OPTIONS, o.options || {});
     data = tm.prepare(o.features, o.labels, o.classes);
-    const st = tm.stack(opt.layers, data.legend.length), epochs = o.epochs === undefined ? 10 : o.epochs | 0, seed = o.seed | 0;
+    const st = tm.stack(opt.layers, data.legend.length, data.width), epochs = o.epochs === undefined ? 10 : o.epochs | 0, seed = o.seed | 0;
     const sp = tm.split(data.y.length, o.validationSplit);
     const init = o.init || tm.glorotInit(Array.from(st.units), seed);
     spec = { units: st.units, activation: st.activation, kernels: init.kernels.map((k) => Float32Array.from(k)), biases: init.biases.map((b) => Float32Array.from(b)),
@@ -305,7 +306,7 @@ function trainRegression(features, values, o) {
   try {
     const opt = Object.assign({}, tm.DEFAULT_OPTIONS_ORDS, o.options || {});
     data = tm.prepareOrdinal(features, values);
-    const st = tm.stackRegression(opt.layers), epochs = o.epochs === undefined ? 10 : o.epochs | 0, seed = o.seed | 0;
+    const st = tm.stackRegression(opt.layers, data.width), epochs = o.epochs === undefined ? 10 : o.epochs | 0, seed = o.seed | 0;
     const sp = tm.split(data.values.length, o.validationSplit);
     const init = o.init || tm.glorotInit(Array.from(st.units), seed);
     spec = { units: st.units, activation: st.activation, kernels: init.kernels.map((k) => Float32Array.from(k)), biases: init.biases.map((b) => Float32Array.from(b)),
@@ -327,10 +328,11 @@ function predictValues(handle, features) {
   if (!loaded_models.has(handle) || handle.released) throw 'predictValues: the model handle was released (shutdown()) or is not one of loadModel / trainRegression';
   if (typeof handle.spec.outMin !== 'number' || typeof handle.spec.outMax !== 'number') throw 'predictValues: not a regression model (no output range)';
   if (!Array.isArray(features)) throw 'predictValues(handle, [[53 numbers]])';
-  const x = new Float64Array(features.length * 53);
+  const W = handle.spec.units[0];       // 53, or the 264 / 23 of a model trained on level-11 / level-12 rows
+  const x = new Float64Array(features.length * W);
   features.forEach((row, r) => {
-    if (row.length !== 53) throw 'predictValues: row ' + r + ' has ' + row.length + ' features; 53 expected';
-    for (let k = 0; k < 53; k++) x[r * 53 + k] = Number(row[k]);
+    if (row.length !== W) throw 'predictValues: row ' + r + ' has ' + row.length + ' features; ' + W + ' expected';
+    for (let k = 0; k < W; k++) x[r * W + k] = Number(row[k]);
   });
   const nat = addon();
   const ctx = contexts_for(nat, settings.devices ? settings.devices.slice() : [settings.device])[0];
@@ -373,6 +375,7 @@ function setPredictionModel(handle, on_prediction) {
   if (handle === null || handle === undefined) { prediction = null; return; }
   if (!loaded_models.has(handle) || handle.released) throw 'setPredictionModel: the model handle was released (shutdown()) or is not one of loadModel';
   if (typeof handle.spec.outMin === 'number') throw 'setPredictionModel: a regression model has no class probabilities to fold; predictValues gives its values';
+  if (handle.spec.units[0] !== 53) throw 'setPredictionModel: the model takes ' + handle.spec.units[0] + ' inputs; live prediction folds the 53-feature syllable rows of output_level 13';
   if (typeof on_prediction !== 'function') throw 'setPredictionModel(handle, on_prediction)';
   prediction = { model: handle, on_prediction };
 }
@@ -381,6 +384,7 @@ function setPredictionModels(handles, on_prediction) {
   if (!Array.isArray(handles) || handles.length < 1 || handles.length > 8) throw 'setPredictionModels([handles], on_prediction): 1 .. 8 model handles';
   for (const h of handles) if (!loaded_models.has(h) || h.released) throw 'setPredictionModels: a model handle was released (shutdown()) or is not one of loadModel';
   for (const h of handles) if (typeof h.spec.outMin === 'number') throw 'setPredictionModels: a regression model has no class probabilities to fold; predictValues gives its values';
+  for (const h of handles) if (h.spec.units[0] !== 53) throw 'setPredictionModels: a model takes ' + h.spec.units[0] + ' inputs; live prediction folds the 53-feature syllable rows of output_level 13';
   if (typeof on_prediction !== 'function') throw 'setPredictionModels([handles], on_prediction)';
   // the carried min_entropy_db is an index into the list: the same list keeps it (the reference's available_DBs never changes), another list starts anew
   const same = prediction && prediction.models && prediction.models.length === handles.length && prediction.models.every((h, i) => h === handles[i]);

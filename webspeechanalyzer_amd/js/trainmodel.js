@@ -9,6 +9,13 @@ const path = require('path');
 
 const ACT = { linear: 0, relu: 1, sigmoid: 2, tanh: 3, softmax: 4 };
 const ACT_NAME = Object.keys(ACT);
+const WIDTHS = [53, 264, 23];        // the row width of an ML level: 5 and 13, 11, 12 (ref src/localstore.js:7; wsa_level_feature_count)
+// the width of the rows: that of the first one, which must be an ML level's; every row used is checked against it
+function rowWidth(features, who) {
+  const w = features.length && features[0] ? features[0].length : 0;
+  if (WIDTHS.indexOf(w) < 0) throw who + ': row 0 has ' + w + ' features; 53 expected (or 264 at output_level 11, 23 at output_level 12)';
+  return w;
+}
 const DEFAULT_OPTIONS = { layers: [{ type: 'dense', units: 8, activation: 'relu' }, { type: 'dense', activation: 'softmax' }], learningRate: 0.2 };   // ref src/neuralmodel_aux.js:106-124
 
 // ref neuralmodel.js:216-264: rows whose label is one of `classes` in DB order; fewer than 10 refused; every class with more than 3 and fewer
@@ -30,14 +37,15 @@ function prepare(features, labels, classes) {
       }
   const legend = [];
   for (const i of rows) if (legend.indexOf(classes[cls[i]]) < 0) legend.push(classes[cls[i]]);
-  const x = new Float64Array(rows.length * 53), y = new Int32Array(rows.length);
-  const inMin = new Float64Array(53).fill(Infinity), inMax = new Float64Array(53).fill(-Infinity);
+  const W = rowWidth(features, 'trainModel');
+  const x = new Float64Array(rows.length * W), y = new Int32Array(rows.length);
+  const inMin = new Float64Array(W).fill(Infinity), inMax = new Float64Array(W).fill(-Infinity);
   rows.forEach((i, r) => {
-    if (features[i].length !== 53) throw 'trainModel: row ' + i + ' has ' + features[i].length + ' features; 53 expected';
-    for (let k = 0; k < 53; k++) { const v = Number(features[i][k]); x[r * 53 + k] = v; if (v < inMin[k]) inMin[k] = v; if (v > inMax[k]) inMax[k] = v; }
+    if (features[i].length !== W) throw 'trainModel: row ' + i + ' has ' + features[i].length + ' features; ' + W + ' expected';
+    for (let k = 0; k < W; k++) { const v = Number(features[i][k]); x[r * W + k] = v; if (v < inMin[k]) inMin[k] = v; if (v > inMax[k]) inMax[k] = v; }
     y[r] = legend.indexOf(classes[cls[i]]);
   });
-  return { features: x, y, legend, inMin, inMax, counts: count, rows };
+  return { features: x, y, legend, inMin, inMax, counts: count, rows, width: W };
 }
 
 function rng(seed) {            // mulberry32: 32 bits of state, enough for weights and shuffles that only have to be repeatable
@@ -85,18 +93,19 @@ function prepareOrdinal(features, values) {
           if (bins[i] === c && count[c] < max_n) { rows.push(i); count[c]++; }
           if (count[c] >= max_n) break;
         }
-  const x = new Float64Array(rows.length * 53), y = new Float64Array(rows.length);
-  const inMin = new Float64Array(53).fill(Infinity), inMax = new Float64Array(53).fill(-Infinity);
+  const W = rowWidth(features, 'trainRegression');
+  const x = new Float64Array(rows.length * W), y = new Float64Array(rows.length);
+  const inMin = new Float64Array(W).fill(Infinity), inMax = new Float64Array(W).fill(-Infinity);
   let outMin = Infinity, outMax = -Infinity;
   rows.forEach((i, r) => {
-    if (features[i].length !== 53) throw 'trainRegression: row ' + i + ' has ' + features[i].length + ' features; 53 expected';
-    for (let k = 0; k < 53; k++) { const v = Number(features[i][k]); x[r * 53 + k] = v; if (v < inMin[k]) inMin[k] = v; if (v > inMax[k]) inMax[k] = v; }
+    if (features[i].length !== W) throw 'trainRegression: row ' + i + ' has ' + features[i].length + ' features; ' + W + ' expected';
+    for (let k = 0; k < W; k++) { const v = Number(features[i][k]); x[r * W + k] = v; if (v < inMin[k]) inMin[k] = v; if (v > inMax[k]) inMax[k] = v; }
     y[r] = Number(values[i]); if (y[r] < outMin) outMin = y[r]; if (y[r] > outMax) outMax = y[r];
   });
-  return { features: x, values: y, inMin, inMax, outMin, outMax, counts: count, rows };
+  return { features: x, values: y, inMin, inMax, outMin, outMax, counts: count, rows, width: W };
 }
-function stackRegression(layers) {
-  const units = [53], activation = [];
+function stackRegression(layers, nInputs) {
+  const units = [nInputs === undefined ? 53 : nInputs], activation = [];
   layers.forEach((l, i) => {
     if ((l.type || 'dense') !== 'dense') throw 'trainRegression: layer ' + i + ' is ' + l.type + '; only dense layers are supported';
     const a = l.activation || 'linear';
@@ -107,8 +116,8 @@ function stackRegression(layers) {
   return { units: Int32Array.from(units), activation: Int32Array.from(activation) };
 }
 function split(n, validationSplit) { const nTrain = Math.floor(n * (1 - (validationSplit === undefined ? 0.1 : validationSplit))); return { nTrain, nVal: n - nTrain }; }
-function stack(layers, nClasses) {
-  const units = [53], activation = [];
+function stack(layers, nClasses, nInputs) {
+  const units = [nInputs === undefined ? 53 : nInputs], activation = [];
   layers.forEach((l, i) => {
     if ((l.type || 'dense') !== 'dense') throw 'trainModel: layer ' + i + ' is ' + l.type + '; only dense layers are supported';
     const a = l.activation || 'linear';
@@ -149,4 +158,4 @@ function saveModelFiles(spec, dir) {
   fs.writeFileSync(path.join(dir, 'model.weights.bin'), Buffer.concat(blobs));
 }
 
-module.exports = { prepare, glorotInit, epochOrders, split, stack, saveModelFiles, DEFAULT_OPTIONS, prepareOrdinal, stackRegression, DEFAULT_OPTIONS_ORDS };
+module.exports = { prepare, glorotInit, epochOrders, split, stack, saveModelFiles, DEFAULT_OPTIONS, prepareOrdinal, stackRegression, DEFAULT_OPTIONS_ORDS, WIDTHS };

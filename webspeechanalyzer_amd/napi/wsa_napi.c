@@ -108,7 +108,7 @@ typedef struct {
 } ctx_box;
 /* What JS holds for a model (wsa_model): like the context's box it outlives the model, so that a handle used after modelDestroy() or after its
  * context's destroy() finds NULL; `busy` counts the jobs that classify with it (modelDestroy() refuses meanwhile) */
-typedef struct model_box { wsa_model *m; ctx_box *owner; uint32_t busy, n_classes; struct model_box *next; } model_box;
+typedef struct model_box { wsa_model *m; ctx_box *owner; uint32_t busy, n_classes, n_inputs; struct model_box *next; } model_box;   /* n_inputs: units[0], the width of the rows the model takes (53, 264 or 23) */
 static void model_unlink(model_box *mb) {
     if (mb->owner) for (model_box **q = &mb->owner->models; *q; q = &(*q)->next) if (*q == mb) { *q = mb->next; break; }
     mb->owner = NULL; mb->next = NULL;
@@ -943,7 +943,7 @@ static napi_value fn_model_create(napi_env env, napi_callback_info info) {
     int32_t *units = NULL, *act = NULL; double *mn = NULL, *mx = NULL; size_t nu = 0, na = 0, nmn = 0, nmx = 0;
     if (!typed_of(env, argv[1], "units", napi_int32_array, (void **)&units, &nu) || !typed_of(env, argv[1], "activation", napi_int32_array, (void **)&act, &na) ||
         !typed_of(env, argv[1], "inMin", napi_float64_array, (void **)&mn, &nmn) || !typed_of(env, argv[1], "inMax", napi_float64_array, (void **)&mx, &nmx) ||
-        nu < 2 || na != nu - 1 || na > WSA_MODEL_MAX_LAYERS || nmn != WSA_NFEAT || nmx != WSA_NFEAT) { napi_throw_type_error(env, NULL, usage); return NULL; }
+        nu < 2 || na != nu - 1 || na > WSA_MODEL_MAX_LAYERS || units[0] < 1 || nmn != (size_t)units[0] || nmx != (size_t)units[0]) { napi_throw_type_error(env, NULL, usage); return NULL; }
     napi_value ka, ba; bool ia = false, ib = false; uint32_t nk = 0, nb = 0;
     if (napi_get_named_property(env, argv[1], "kernels", &ka) != napi_ok || napi_is_array(env, ka, &ia) != napi_ok || !ia || napi_get_array_length(env, ka, &nk) != napi_ok ||
         napi_get_named_property(env, argv[1], "biases", &ba) != napi_ok || napi_is_array(env, ba, &ib) != napi_ok || !ib || napi_get_array_length(env, ba, &nb) != napi_ok ||
@@ -978,7 +978,7 @@ static napi_value fn_model_create(napi_env env, napi_callback_info info) {
     if (st != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(box->ctx)); return NULL; }
     model_box *mb = calloc(1, sizeof *mb);
     if (!mb) { wsa_model_destroy(m); napi_throw_error(env, NULL, "out of memory"); return NULL; }
-    mb->m = m; mb->owner = box; mb->n_classes = (uint32_t)units[na]; mb->next = box->models; box->models = mb;
+    mb->m = m; mb->owner = box; mb->n_classes = (uint32_t)units[na]; mb->n_inputs = (uint32_t)units[0]; mb->next = box->models; box->models = mb;
     napi_value ext; NAPI_OK(env, napi_create_external(env, mb, model_finalize, NULL, &ext));
     return ext;
 }
@@ -999,7 +999,7 @@ static napi_value fn_model_destroy(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
-/* ---- training (wsa_trainer_*, K7): train(ctx, spec, {features: Float64Array [n][53], y: Int32Array [n], nVal, batchSize, learningRate, epochs,
+/* ---- training (wsa_trainer_*, K7): train(ctx, spec, {features: Float64Array [n][units[0]] (53, 264 or 23 wide), y: Int32Array [n], nVal, batchSize, learningRate, epochs,
  * orders: Uint32Array [epochs][n - nVal] | undefined}, onEpoch | undefined) -> Promise of {kernels: Float32Array[], biases: Float32Array[],
  * history: Float64Array [epochs][4] = loss, acc, val_loss, val_acc}.  `spec` is modelCreate's object and holds the INITIAL weights.  The epochs run
  * on a thread of their own (the inputs are copied first); after every epoch onEpoch(epoch, {loss, acc, val_loss, val_acc}) is queued to the JS
@@ -1008,7 +1008,7 @@ typedef struct {
     ctx_box *box; napi_deferred deferred; napi_threadsafe_function tsfn; pthread_t thread; napi_ref on_epoch;
     int32_t nl, units[WSA_MODEL_MAX_LAYERS + 1], act[WSA_MODEL_MAX_LAYERS];
     float *kernel[WSA_MODEL_MAX_LAYERS], *bias[WSA_MODEL_MAX_LAYERS];
-    double mn[WSA_NFEAT], mx[WSA_NFEAT];
+    double mn[WSA_NUTT], mx[WSA_NUTT];                     /* units[0] entries: the widest row of an ML level has WSA_NUTT */
     double *feat; int32_t *y; uint32_t *orders; uint32_t n, n_val, batch, epochs; double lr;
     double *values, out_min, out_max;                     /* values != NULL: a regression model (wsa_regress_trainer_create) instead of y */
     double *history; wsa_status st; char err[512];
@@ -1096,9 +1096,9 @@ static napi_value fn_train(napi_env env, napi_callback_info info) {
     if (regress && (!num_of(env, argv[2], "outMin", &out_min) || !num_of(env, argv[2], "outMax", &out_max))) { napi_throw_type_error(env, NULL, usage); return NULL; }
     if (!typed_of(env, argv[1], "units", napi_int32_array, (void **)&units, &nu) || !typed_of(env, argv[1], "activation", napi_int32_array, (void **)&act, &na) ||
         !typed_of(env, argv[1], "inMin", napi_float64_array, (void **)&mn, &nmn) || !typed_of(env, argv[1], "inMax", napi_float64_array, (void **)&mx, &nmx) ||
-        nu < 2 || na != nu - 1 || na > WSA_MODEL_MAX_LAYERS || nmn != WSA_NFEAT || nmx != WSA_NFEAT ||
+        nu < 2 || na != nu - 1 || na > WSA_MODEL_MAX_LAYERS || units[0] < 1 || units[0] > WSA_NUTT || nmn != (size_t)units[0] || nmx != (size_t)units[0] ||
         !typed_of(env, argv[2], "features", napi_float64_array, (void **)&feat, &nf) || (!regress && !typed_of(env, argv[2], "y", napi_int32_array, (void **)&y, &ny)) ||
-        ny < 1 || nf != ny * WSA_NFEAT || ny > 0xffffffffu ||
+        ny < 1 || nf != ny * (size_t)units[0] || ny > 0xffffffffu ||
         !num_of(env, argv[2], "nVal", &n_val) || !num_of(env, argv[2], "batchSize", &batch) || !num_of(env, argv[2], "learningRate", &lr) || !num_of(env, argv[2], "epochs", &epochs) ||
         n_val < 0 || n_val >= (double)ny || batch < 0 || batch > 4294967295.0 || epochs < 1 || epochs > 1e6) { napi_throw_type_error(env, NULL, usage); return NULL; }
     const uint32_t n_train = (uint32_t)ny - (uint32_t)n_val;
@@ -1111,7 +1111,7 @@ static napi_value fn_train(napi_env env, napi_callback_info info) {
     train_job *j = calloc(1, sizeof *j);
     if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
     j->box = box; j->nl = (int32_t)na; j->n = (uint32_t)ny; j->n_val = (uint32_t)n_val; j->batch = (uint32_t)batch; j->epochs = (uint32_t)epochs; j->lr = lr;
-    memcpy(j->units, units, nu * sizeof(int32_t)); memcpy(j->act, act, na * sizeof(int32_t)); memcpy(j->mn, mn, sizeof j->mn); memcpy(j->mx, mx, sizeof j->mx);
+    memcpy(j->units, units, nu * sizeof(int32_t)); memcpy(j->act, act, na * sizeof(int32_t)); memcpy(j->mn, mn, nmn * sizeof(double)); memcpy(j->mx, mx, nmx * sizeof(double));
     bool ok = true;
     for (uint32_t l = 0; l < na && ok; l++) {
         napi_value kv, bv; bool t1 = false, t2 = false; napi_typedarray_type tk, tb; size_t lk = 0, lb = 0; void *dk = NULL, *db = NULL;
@@ -1144,22 +1144,23 @@ static napi_value fn_train(napi_env env, napi_callback_info info) {
     return promise;
 }
 
-/* ---- a regression model's values (wsa_regress_rows): regressRows(ctx, model, features: Float64Array [n][53], outMin, outMax) -> Float64Array [n].
+/* ---- a regression model's values (wsa_regress_rows): regressRows(ctx, model, features: Float64Array [n][the model's inputs], outMin, outMax) -> Float64Array [n].
  * What the app's predict_db_nn does over stored rows (ref src/neuralmodel.js:410-535).  Synchronous: the rows go through one page-locked
  * allocation the device reads and writes in place. */
 static napi_value fn_regress_rows(napi_env env, napi_callback_info info) {
     size_t argc = 5; napi_value argv[5]; void *p = NULL;
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     ctx_box *box = argc ? get_box(env, argv[0]) : NULL;
-    const char *usage = "regressRows(ctx, model, features: Float64Array [n][53], outMin, outMax)";
+    const char *usage = "regressRows(ctx, model, features: Float64Array [n][the model's inputs], outMin, outMax)";
     bool ta = false; napi_typedarray_type tt; size_t nf = 0; void *feat = NULL; double lo = 0, hi = 0;
     if (!box || !box->ctx || argc < 5 || napi_get_value_external(env, argv[1], &p) != napi_ok || !p ||
         napi_is_typedarray(env, argv[2], &ta) != napi_ok || !ta || napi_get_typedarray_info(env, argv[2], &tt, &nf, &feat, NULL, NULL) != napi_ok ||
-        tt != napi_float64_array || nf % WSA_NFEAT || nf / WSA_NFEAT > 0xffffffffu ||
+        tt != napi_float64_array ||
         napi_get_value_double(env, argv[3], &lo) != napi_ok || napi_get_value_double(env, argv[4], &hi) != napi_ok) { napi_throw_type_error(env, NULL, usage); return NULL; }
     model_box *mb = (model_box *)p;
     if (!mb->m || mb->owner != box) { napi_throw_error(env, NULL, "regressRows: the model was destroyed or belongs to another context"); return NULL; }
-    const size_t n = nf / WSA_NFEAT;
+    if (nf % mb->n_inputs || nf / mb->n_inputs > 0xffffffffu) { napi_throw_type_error(env, NULL, usage); return NULL; }
+    const size_t n = nf / mb->n_inputs;
     void *slab = NULL;
     if (wsa_host_alloc(box->ctx, (uint64_t)(nf + n) * sizeof(double), &slab) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(box->ctx)); return NULL; }
     double *rows = (double *)slab, *value = rows + nf;
@@ -1176,7 +1177,7 @@ static napi_value fn_regress_rows(napi_env env, napi_callback_info info) {
 /* ---- predicting a labelled feature DB and the app's results table (wsa_dbstats_*, K8, specification DS-1): what the app's Predict button does over
  * the stored rows (ref src/neuralmodel.js:410-535 predict_db_nn, src/localstore.js:498-627 shows_stats_table).  Both calls are synchronous and
  * build the device object for the call; js/dbstats.js resolves everything that is a string and hands over indices and values.
- *   dbPredict(ctx, model, features: Float64Array [n][53], ords: boolean, outMin, outMax) -> Int32Array [n] legend indices (-1 = the reference's
+ *   dbPredict(ctx, model, features: Float64Array [n][the model's inputs], ords: boolean, outMin, outMax) -> Int32Array [n] legend indices (-1 = the reference's
  *     null) for a classifier, Float64Array [n] values for a regression model
  *   dbTable(ctx, {durations: Float64Array [n], vocab: Uint32Array [nCat], trueIdx, predIdx: Int32Array [nCat][n], trueVal, predVal: Float64Array
  *     [nOrd][n]}) -> {cat: Float64Array [nCat][3] correct, wrong, blank; cls: Float64Array [sum vocab][5] count, correct, wrong, duration,
@@ -1190,22 +1191,23 @@ static napi_value fn_db_predict(napi_env env, napi_callback_info info) {
     size_t argc = 6; napi_value argv[6]; void *p = NULL;
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     ctx_box *box = argc ? get_box(env, argv[0]) : NULL;
-    const char *usage = "dbPredict(ctx, model, features: Float64Array [n][53], ords: boolean, outMin, outMax)";
+    const char *usage = "dbPredict(ctx, model, features: Float64Array [n][the model's inputs], ords: boolean, outMin, outMax)";
     size_t nf = 0; void *feat = NULL; bool ords = false; double lo = 0, hi = 1;
     if (!box || !box->ctx || argc < 4 || napi_get_value_external(env, argv[1], &p) != napi_ok || !p || !typed_arg(env, argv[2], napi_float64_array, &feat, &nf) ||
-        nf % WSA_NFEAT || nf / WSA_NFEAT > 0xffffffffu || napi_get_value_bool(env, argv[3], &ords) != napi_ok ||
+        napi_get_value_bool(env, argv[3], &ords) != napi_ok ||
         (ords && (argc < 6 || napi_get_value_double(env, argv[4], &lo) != napi_ok || napi_get_value_double(env, argv[5], &hi) != napi_ok))) {
         napi_throw_type_error(env, NULL, usage); return NULL;
     }
     model_box *mb = (model_box *)p;
     if (!mb->m || mb->owner != box) { napi_throw_error(env, NULL, "dbPredict: the model was destroyed or belongs to another context"); return NULL; }
-    const uint32_t n = (uint32_t)(nf / WSA_NFEAT), vocab = mb->n_classes;
+    if (nf % mb->n_inputs || nf / mb->n_inputs > 0xffffffffu) { napi_throw_type_error(env, NULL, usage); return NULL; }
+    const uint32_t n = (uint32_t)(nf / mb->n_inputs), vocab = mb->n_classes;
     double *dur = calloc(n ? n : 1, sizeof(double));
     void *out = malloc((n ? n : 1) * sizeof(double));
     int32_t map[WSA_MODEL_MAX_CLASSES];
     for (int c = 0; c < WSA_MODEL_MAX_CLASSES; c++) map[c] = c;
     wsa_dbstats *db = NULL;
-    wsa_status st = dur && out ? wsa_dbstats_create(box->ctx, (const double *)feat, dur, n, ords ? 0 : 1, &vocab, ords ? 1 : 0, &db) : WSA_ERR_INVALID;
+    wsa_status st = dur && out ? wsa_wide_dbstats_create(box->ctx, (const double *)feat, mb->n_inputs, dur, n, ords ? 0 : 1, &vocab, ords ? 1 : 0, &db) : WSA_ERR_INVALID;
     if (st == WSA_OK) st = ords ? wsa_dbstats_predict_values(db, 0, mb->m, lo, hi, box->queue) : wsa_dbstats_predict_classes(db, 0, mb->m, map, box->queue);
     if (st == WSA_OK) st = ords ? wsa_dbstats_copy_values(db, 0, box->queue, (double *)out) : wsa_dbstats_copy_classes(db, 0, box->queue, (int32_t *)out);
     napi_value res = NULL;

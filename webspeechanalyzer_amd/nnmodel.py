@@ -7,6 +7,11 @@ import os
 import numpy as np
 
 NFEAT = 53
+# the row width of every output level whose ML panel the app enables (ref src/index.js:723, src/localstore.js:7 process_exp_features_len;
+# wsa_level_feature_count of include/wsa.h): a model's input count is one of these
+LEVEL_FEATURES = {5: 53, 11: 264, 12: 23, 13: 53}
+WIDTHS = (53, 264, 23)
+WIDTHS_TEXT = "53 (output_level 5 and 13), 264 (output_level 11) or 23 (output_level 12)"
 ACT = {"linear": 0, "relu": 1, "sigmoid": 2, "tanh": 3, "softmax": 4}
 MAX_LAYERS, MAX_WIDTH, MAX_CLASSES = 8, 1024, 64
 
@@ -78,20 +83,20 @@ def parse(model_json, meta_json, weights):
         k = np.frombuffer(weights, "<f4", ks[0] * ks[1], off).reshape(ks).copy(); off += k.nbytes
         b = np.frombuffer(weights, "<f4", bs[0], off).copy(); off += b.nbytes
         kernels.append(k); biases.append(b); units.append(int(ks[1]))
-    if units[0] != NFEAT:
-        raise ModelFormatError(f"the model takes {units[0]} inputs; the feature rows have {NFEAT}")
+    if units[0] not in WIDTHS:
+        raise ModelFormatError(f"the model takes {units[0]} inputs; the feature rows have {WIDTHS_TEXT}")
     if max(units[1:]) > MAX_WIDTH or units[-1] > MAX_CLASSES:
         raise ModelFormatError(f"layer widths {units[1:]} exceed {MAX_WIDTH} (or more than {MAX_CLASSES} outputs)")
     try:
         ins = meta["inputs"]
-        in_min = np.array([float(ins[str(i)]["min"]) for i in range(NFEAT)])
-        in_max = np.array([float(ins[str(i)]["max"]) for i in range(NFEAT)])
+        in_min = np.array([float(ins[str(i)]["min"]) for i in range(units[0])])
+        in_max = np.array([float(ins[str(i)]["max"]) for i in range(units[0])])
         y = meta["outputs"].get("y") if isinstance(meta["outputs"], dict) else None
         regression = isinstance(y, dict) and "legend" not in y and "min" in y and "max" in y
         if regression:
             out_min, out_max = float(y["min"]), float(y["max"])
     except (KeyError, TypeError, ValueError) as e:
-        raise ModelFormatError(f"model_meta.json: no inputs '0'..'52' min / max or output legend ({e})")
+        raise ModelFormatError(f"model_meta.json: no inputs '0'..'{units[0] - 1}' min / max or output legend ({e})")
     if regression:                                   # ml5 task "regression": outputs.y = {dtype: "number", min, max}
         if not (np.all(np.isfinite(in_min)) and np.all(np.isfinite(in_max))):
             raise ModelFormatError("model_meta.json: non-finite input range")
@@ -103,7 +108,7 @@ def parse(model_json, meta_json, weights):
     try:
         legend = list(meta["outputs"]["y"]["legend"].keys()) if "y" in meta["outputs"] else list(next(iter(meta["outputs"].values()))["legend"].keys())
     except (KeyError, TypeError, StopIteration) as e:
-        raise ModelFormatError(f"model_meta.json: no inputs '0'..'52' min / max or output legend ({e})")
+        raise ModelFormatError(f"model_meta.json: no inputs '0'..'{units[0] - 1}' min / max or output legend ({e})")
     if not (np.all(np.isfinite(in_min)) and np.all(np.isfinite(in_max))):
         raise ModelFormatError("model_meta.json: non-finite input range")
     if acts[-1] == "softmax" and len(legend) != units[-1]:
@@ -127,6 +132,8 @@ def save_dir(spec, path):
     src/neuralmodel.js), in the key layout of the directories the app ships: load_dir reads them back bit for bit, and ml5's
     neuralNetwork.load takes them."""
     nl = len(spec.kernels)
+    if len(spec.in_min) != spec.units[0] or len(spec.in_max) != spec.units[0]:
+        raise ModelFormatError(f"the model takes {spec.units[0]} inputs; in_min / in_max hold {len(spec.in_min)} / {len(spec.in_max)} ranges")
     regression = getattr(spec, "is_regression", False)
     if regression and (spec.units[-1] != 1 or spec.activations[-1] == "softmax"):
         raise ModelFormatError(f"a regression model ends in one non-softmax unit, not {spec.units[-1]} {spec.activations[-1]}")

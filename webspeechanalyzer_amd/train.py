@@ -18,8 +18,16 @@ DEFAULT_LAYERS_ORDS = [{"type": "dense", "units": 64, "activation": "sigmoid"}, 
 ORDINAL_RANGES = (0.25, 0.5, 0.75, 1.0)              # neuralmodel.js:281: the bins the ordinal values are balanced over
 
 
+def _rows_2d(features, n_labels, what):
+    """features as [n][width] f64, width the row width of an ML level (nnmodel.WIDTHS), one label / value per row"""
+    feat = np.asarray(features, np.float64)
+    if feat.ndim != 2 or feat.shape[1] not in nnmodel.WIDTHS or n_labels != len(feat):
+        raise ValueError(f"features {feat.shape} / {n_labels} {what}: expected [n][{nnmodel.NFEAT}] (or [n][264] at output_level 11, [n][23] at 12) and n {what}")
+    return feat
+
+
 def prepare(features, labels, classes):
-    """The selection and balancing loop of neuralmodel.js:216-264.  features [n][53]; labels: per row the label's value or None;
+    """The selection and balancing loop of neuralmodel.js:216-264.  features [n][53] (or 264 / 23 wide: the rows of level 11 / 12); labels: per row the label's value or None;
     classes: the label's class list.  Rows whose label is one of `classes` are added in DB order; fewer than 10 of them is refused;
     then each class with more than 3 and fewer than the largest count is topped up by cycling through the DB in order until it
     reaches that count.  Returns dict(features, y, legend, in_min, in_max, counts, rows): y are indices into legend, which lists the
@@ -28,9 +36,7 @@ def prepare(features, labels, classes):
     classes = [str(c) for c in classes]
     if "*" in classes:
         raise ValueError("the '*' wildcard class is not supported")
-    feat = np.asarray(features, np.float64)
-    if feat.ndim != 2 or feat.shape[1] != nnmodel.NFEAT or len(labels) != len(feat):
-        raise ValueError(f"features {feat.shape} / {len(labels)} labels: expected [n][{nnmodel.NFEAT}] and n labels")
+    feat = _rows_2d(features, len(labels), "labels")
     cls = [classes.index(str(v)) if v is not None and str(v) in classes else -1 for v in labels]
     rows = [i for i, c in enumerate(cls) if c >= 0]
     count = [sum(1 for i in rows if cls[i] == c) for c in range(len(classes))]
@@ -82,9 +88,10 @@ def split(n, validation_split=0.1):
     return n_train, n - n_train
 
 
-def stack(layers, n_classes):
-    """(units, activations) of the app's options JSON `layers`; the last layer's units are the number of classes."""
-    units, acts = [nnmodel.NFEAT], []
+def stack(layers, n_classes, n_inputs=nnmodel.NFEAT):
+    """(units, activations) of the app's options JSON `layers`; the last layer's units are the number of classes; n_inputs the width of
+    the rows (ml5 infers it from them)."""
+    units, acts = [int(n_inputs)], []
     for i, l in enumerate(layers):
         if l.get("type", "dense") != "dense":
             raise ValueError(f"layer {i} is {l.get('type')!r}; only dense layers are supported")
@@ -100,7 +107,7 @@ def train(an, data, layers=None, learning_rate=DEFAULT_LEARNING_RATE, epochs=10,
     """Trains on `an` (a capi.Analyzer) over data = prepare(...).  init: (kernels, biases) instead of glorot_init(units, seed); orders:
     one order per epoch instead of epoch_orders(n_train, epochs, seed + 1).  on_epoch(epoch, stats) mirrors ml5's whileTraining (it
     synchronises every epoch; without it only the last epoch is waited for).  Returns (nnmodel.ModelSpec, history)."""
-    units, acts = stack(layers or DEFAULT_LAYERS, len(data["legend"]))
+    units, acts = stack(layers or DEFAULT_LAYERS, len(data["legend"]), np.shape(data["features"])[1])
     ks, bs = init if init is not None else glorot_init(units, seed)
     n_train, n_val = split(len(data["features"]), validation_split)
     orders = orders if orders is not None else epoch_orders(n_train, epochs, seed + 1)
@@ -121,15 +128,13 @@ def train(an, data, layers=None, learning_rate=DEFAULT_LEARNING_RATE, epochs=10,
 
 
 def prepare_ordinal(features, values):
-    """The selection and balancing loop of neuralmodel.js:278-332 for an ordinal label (V, A or D).  features [n][53]; values: per row
+    """The selection and balancing loop of neuralmodel.js:278-332 for an ordinal label (V, A or D).  features [n][53] (or 264 / 23 wide); values: per row
     the label's value or None.  A row's bin is the first of (-inf, 0.25], (0.25, 0.5], (0.5, 0.75], (0.75, 1.0] that holds its value; rows
     with None or a value above 1.0 are dropped; the others are added in DB order; fewer than 10 of them is refused; then, only when the
     largest bin holds more than 3, each bin with more than 3 and fewer than the largest count is topped up by cycling through the DB in
     order until it reaches that count.  Returns dict(features, values, in_min, in_max, out_min, out_max, counts, rows): the ranges are
     taken over the balanced set, duplicates included (ml5 normalizeData); rows are the DB indices in the order added."""
-    feat = np.asarray(features, np.float64)
-    if feat.ndim != 2 or feat.shape[1] != nnmodel.NFEAT or len(values) != len(feat):
-        raise ValueError(f"features {feat.shape} / {len(values)} values: expected [n][{nnmodel.NFEAT}] and n values")
+    feat = _rows_2d(features, len(values), "values")
     nb = len(ORDINAL_RANGES)
 
     def bin_of(v):
@@ -159,9 +164,10 @@ def prepare_ordinal(features, values):
     return dict(features=x, values=y, in_min=x.min(axis=0), in_max=x.max(axis=0), out_min=float(y.min()), out_max=float(y.max()), counts=count, rows=rows)
 
 
-def stack_regression(layers):
-    """(units, activations) of the app's options JSON `layers` for a regression task: the last layer has one unit and is not softmax."""
-    units, acts = [nnmodel.NFEAT], []
+def stack_regression(layers, n_inputs=nnmodel.NFEAT):
+    """(units, activations) of the app's options JSON `layers` for a regression task: the last layer has one unit and is not softmax;
+    n_inputs the width of the rows."""
+    units, acts = [int(n_inputs)], []
     for i, l in enumerate(layers):
         if l.get("type", "dense") != "dense":
             raise ValueError(f"layer {i} is {l.get('type')!r}; only dense layers are supported")
@@ -177,7 +183,7 @@ def train_regression(an, data, layers=None, learning_rate=DEFAULT_LEARNING_RATE,
     """train(...) for a regression model (specification TR-2) over data = prepare_ordinal(...): the app's nn_default_options_ords stack
     unless `layers` is given, Adam on the mean squared error of the normalised output.  Returns (nnmodel.ModelSpec with out_min /
     out_max, history)."""
-    units, acts = stack_regression(layers or DEFAULT_LAYERS_ORDS)
+    units, acts = stack_regression(layers or DEFAULT_LAYERS_ORDS, np.shape(data["features"])[1])
     ks, bs = init if init is not None else glorot_init(units, seed)
     n_train, n_val = split(len(data["features"]), validation_split)
     orders = orders if orders is not None else epoch_orders(n_train, epochs, seed + 1)
