@@ -318,13 +318,13 @@ static wsa_status run_backend_stages(wsa_batch* b, const uint32_t* d_spec, bool 
         hipStream_t cs = s;
         uint32_t* counters = B.d_counters + 4;              // [0] largest per-clip segment count
         PkParams pk; pk.spec = d_spec; pk.rec = B.rec; pk.total_frames = b->total_frames; pk.bands = b->fe.plan.bands;
-        pk.flags = B.d_counters + 1; pk.dbg = (b->tune.dbg >> 20) & 0xff; pk.lanes_only = b->tune.peaks_lanes ? 1 : 0;      // (WSA_DBG bits 20 .. 27: the peak scan's what-if switches, TUNING=1 builds only)
+        pk.flags = B.d_counters + 1; pk.dbg = (b->tune.dbg >> DBG_PEAKS_SHIFT) & 0xff; pk.lanes_only = b->tune.peaks_lanes ? 1 : 0;      // (WSA_DBG bits 20 .. 27: the peak scan's what-if switches, TUNING=1 builds only)
         pk.wpc = b->tune.peaks_wpc; pk.round_bins = b->tune.peaks_w;
         if (!skip_peaks) launch_peaks(pk, cs);        // (a rerun of the back end finds the frame records in place)
         GateParams g;
         B.fill(g, D);
         g.n_frames = b->d_n_frames; g.frame_off = b->d_frame_off; g.trace = b->d_trace; g.dbg = dbg; g.prio = 1;
-        const bool ordered = !(dbg & 8192);                         // WSA_DBG bit 8192: (clip, segment) enumeration instead of the length-sorted order
+        const bool ordered = !(dbg & DBG_UNSORTED_SPANS);            // (clip, segment) enumeration instead of the length-sorted order
         g.span_hist = ordered ? b->d_span_hist : nullptr; g.span_key = b->d_span_key;
         launch_gate(g, cs);
         TrParams t;

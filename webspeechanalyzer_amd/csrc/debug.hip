@@ -146,7 +146,7 @@ extern "C" int wsa_debug_peaks(int32_t device, const uint32_t* spec, uint32_t n_
     return ok ? WSA_OK : WSA_ERR_HIP;
 }
 
-// timing of the peak-candidate scan on its own (tuning): the same frames `reps` times, average kernel time in ms; dbg = PkParams::dbg
+// timing of the peak-candidate scan on its own (tuning): the same frames `reps` times, average kernel time in ms; dbg = PkParams::dbg (PK_DBG_* bits)
 extern "C" int wsa_debug_peaks_time(int32_t device, const uint32_t* spec, uint32_t n_frames, int32_t bands, int32_t mode, int32_t dbg, int32_t reps, float* ms) {
     if (!spec || !ms || bands < 1 || n_frames < 1 || reps < 1) return WSA_ERR_INVALID;
     if (hipSetDevice(device) != hipSuccess) return WSA_ERR_NO_DEVICE;

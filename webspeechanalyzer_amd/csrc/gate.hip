@@ -176,7 +176,7 @@ __global__ __launch_bounds__(64) void gate_kernel_t(GateParams p) {
             }
             if (lane == jf) { o_info = info; o_v = v; o_fl = floor_; o_span = span_begin; }
             if (lane == 0) {
-                if (!ST && p.trace && !(p.dbg & 16)) {
+                if (!ST && p.trace && !(p.dbg & DBG_CYCLES)) {
                     double* tr = p.trace + ((uint64_t)foff + f) * 12;
                     tr[0] = c_ci; tr[1] = c_started; tr[2] = no_fm; tr[3] = ctx_max; tr[4] = floor_; tr[5] = n; tr[6] = pbin;
                     tr[7] = h; tr[8] = d; tr[9] = g; tr[10] = 0; tr[11] = 0;
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(64) void gate_kernel_auto(GateParams p) {
     const int lane = threadIdx.x;
     const int br_i = p.breaker >= 2147483647.0 ? 2147483647 : (int)ceil(p.breaker);
     const int maxvb = p.max_voiced_bin;
-    const bool want_trace = TRACE && p.trace && !(p.dbg & 16);
+    const bool want_trace = TRACE && p.trace && !(p.dbg & DBG_CYCLES);
     const uint64_t lt_l = lanemask_lt(lane);
     for (uint32_t clip = p.clip0 + blockIdx.x; clip < p.clip0 + p.n_clips; clip += gridDim.x) {
         const uint32_t nfr = p.n_frames[clip];
@@ -541,8 +541,8 @@ __global__ void stream_prepare_kernel(double* state, int32_t* carry, int32_t* tr
 void launch_gate(const GateParams& p, hipStream_t s) {
     if (p.n_clips == 0) return;
     // WSA_DBG bit 2048: the general (f64, lane = candidate) kernel also under the auto gate
-    if (p.auto_gate && p.strided && !(p.dbg & 2048)) {
-        if ((p.trace && !(p.dbg & 16)) || (p.dbg & 4096)) hipLaunchKernelGGL(gate_kernel_auto<true>, dim3(p.n_clips), dim3(64), 0, s, p);
+    if (p.auto_gate && p.strided && !(p.dbg & DBG_GATE_F64)) {
+        if ((p.trace && !(p.dbg & DBG_CYCLES)) || (p.dbg & DBG_GATE_GENERAL)) hipLaunchKernelGGL(gate_kernel_auto<true>, dim3(p.n_clips), dim3(64), 0, s, p);
         else hipLaunchKernelGGL(gate_kernel_auto<false>, dim3(p.n_clips), dim3(64), 0, s, p);
     }
     else hipLaunchKernelGGL(gate_kernel_t<false>, dim3(p.n_clips), dim3(64), 0, s, p);

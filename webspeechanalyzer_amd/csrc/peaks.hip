@@ -90,7 +90,7 @@ __global__ __launch_bounds__(64) void peaks_kernel(PkParams p) {
     auto flush = [&](int lo_valid, bool any_hi, bool all) __attribute__((always_inline)) {
         wsync();
         const int nwork = all ? nlist : (nlist & ~63);
-        for (int j0 = 0; j0 < (WSA_PKT(1) ? 0 : nwork); j0 += 64) {
+        for (int j0 = 0; j0 < (WSA_PKT(PK_DBG_NO_EMISSION) ? 0 : nwork); j0 += 64) {
             const int j = j0 + lane;
             if (j < nwork) {
                 const uint32_t wa = lstA[j], wb = lstB[j];
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(64) void peaks_kernel(PkParams p) {
                     const int h = (x / PK_W) & 1;
                     return hib[h][fl] + (uint32_t)__popc(cmw[h][fl] & (0xffffffffu >> (31 - (x & (PK_W - 1)))));
                 };
-                if (__builtin_expect((ci > 0 ? ci - 1 : 0) < lo_valid && !WSA_PKT(32), 0)) {
+                if (__builtin_expect((ci > 0 ? ci - 1 : 0) < lo_valid && !WSA_PKT(PK_DBG_NO_GLOBAL_PATH), 0)) {
                     // the ring holds P[lo_valid ..]: what lies below is P[lo_valid] minus the bins between, read from the frame's row
                     const uint32_t* e = src + (uint64_t)fl * (uint32_t)B;
                     qe = e[cl];
@@ -148,9 +148,9 @@ __global__ __launch_bounds__(64) void peaks_kernel(PkParams p) {
                     }
                 }
                 const uint32_t c_ = cbl[fl] + (uint32_t)ord;
-                if (!WSA_PKT(8)) p.rec.ent[c_] = make_uint4((uint32_t)qi | ((uint32_t)qs << 8) | (wa & 0xffff0000u), pil, psl, pih | (psh << 8));
-                if (!WSA_PKT(8)) p.rec.amp[c_] = qe; else if (qe == 0x12345u && pil == 77u && psl == 99u) p.rec.amp[c_] = qe + (uint32_t)qi + (uint32_t)qs + pih + psh;
-                if (!(wa >> 24) && !WSA_PKT(16)) atomicMax(&mxk[fl], ((unsigned long long)qe << 32) | (unsigned long long)(((63u - (uint32_t)ord) << 8) | (uint32_t)cl));
+                if (!WSA_PKT(PK_DBG_NO_STORES)) p.rec.ent[c_] = make_uint4((uint32_t)qi | ((uint32_t)qs << 8) | (wa & 0xffff0000u), pil, psl, pih | (psh << 8));
+                if (!WSA_PKT(PK_DBG_NO_STORES)) p.rec.amp[c_] = qe; else if (qe == 0x12345u && pil == 77u && psl == 99u) p.rec.amp[c_] = qe + (uint32_t)qi + (uint32_t)qs + pih + psh;
+                if (!(wa >> 24) && !WSA_PKT(PK_DBG_NO_LDS_ATOMIC)) atomicMax(&mxk[fl], ((unsigned long long)qe << 32) | (unsigned long long)(((63u - (uint32_t)ord) << 8) | (uint32_t)cl));
             }
         }
         wsync();
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(64) void peaks_kernel(PkParams p) {
                 WSA_PUSH_GT(mR, ea, hi3); WSA_PUSH_LT(mF, ea, lo3); WSA_PUSH_GT(mG, ea, e1);
                 e3 = e2; e2 = e1; e1 = ea;
             };
-            if (WSA_PKT(4)) {}
+            if (WSA_PKT(PK_DBG_NO_MASK_PASS)) {}
             else if (tw == PK_W && t0 > 0) {
 #pragma unroll
                 for (int q = 0; q < PK_W; q++) step_fast(q);
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(64) void peaks_kernel(PkParams p) {
             const uint32_t mN = ~(mR | mF);
             uint32_t rem = tw == 32 ? ~0u : ((1u << tw) - 1u);         // bins of this word not yet visited
             if (t0 == 0) rem &= ~1u;                                   // the scan starts at bin 1
-            if (!live || WSA_PKT(2)) rem = 0u;
+            if (!live || WSA_PKT(PK_DBG_NO_STATE_MACHINE)) rem = 0u;
             const int lo_valid = max(0, t0 - PK_W);
             while (__ballot(rem != 0u) != 0ull) {
                 // idle or falling: on to the next rise — through the flat bins of a falling stretch, which end it at the third

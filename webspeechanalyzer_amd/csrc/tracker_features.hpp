@@ -255,7 +255,7 @@ constexpr int FEAT_SCRATCH = 8 * 64 + 3 * FEAT_FX;   // doubles
 constexpr int FEAT_LDS_MAX = 2048;                   // frames formant_features_lds takes
 __device__ __forceinline__ void formant_features_lds(const float* fr, int a, double ctx_max, double* x, int lane, double* red, bool packed = false, bool no_walk = false) {
     double* const fx = red + 8 * 64;
-    // ---- energy peak-then-halve events of inputs of at most 128 frames (every segment finalize_fast takes, every syllable): lanes 0 .. 2 walk the frames of
+    // ---- energy peak-then-halve events of inputs of at most 128 frames (every segment finalize_lds takes, every syllable): lanes 0 .. 2 walk the frames of
     //      columns 0 .. 2 one after the other — the reference's own walk, three columns at a time, ~16 instructions per frame for all of them — and keep the event
     //      frames as bit masks (evw0: frames 0 .. 63, evw1: 64 .. 127).  energy_events_block (a max-scan, a ballot and a branch per run and per event of ONE
     //      column: ~1 400 instructions for the three columns of a 48-frame segment against ~800 here) serves the longer ones.  Same fp32 comparisons, same events.

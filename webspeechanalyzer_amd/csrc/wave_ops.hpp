@@ -85,6 +85,10 @@ __device__ __forceinline__ double dpp_f64_row(double v) {
 __device__ __forceinline__ double read_lane_f64(double v, int src) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
 }
+__device__ __forceinline__ int read_first_lane_i32(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ double read_first_lane_f64(double v) {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
 // sums over the 64 lanes of N values at once (results valid in every lane).  The summation order is a fixed tree: inclusive scans inside the four
 // rows of 16 lanes (Kogge-Stone: shifts by 1, 2, 4, 8), then (row3 + row2) + (row1 + row0) — the tree of the six-step DPP form
 // (row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3) this replaces, so every sum keeps its bits.  The N chains advance step by step

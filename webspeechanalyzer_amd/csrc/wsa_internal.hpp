@@ -30,7 +30,7 @@ bool build_fe_plan(const wsa_config& cfg, double fs, FePlanHost& out, std::strin
 // ---- tuning and test switches (tools/README.md).  The environment is read ONCE per planned batch / stream set (wsa_batch_create,
 // wsa_stream_create) and the values travel in the plan: no launch path looks at the environment.
 struct Tuning {
-    int dbg = 0;                        // WSA_DBG
+    int dbg = 0;                        // WSA_DBG: the DBG_* bits below
     bool no_pair = false, no_split = false, fe_fat = false, peaks_lanes = false;      // WSA_NO_PAIR, WSA_NO_SPLIT, WSA_FE_FAT, WSA_PEAKS_LANES
     bool no_quad = false, quad = false; // WSA_NO_QUAD / WSA_QUAD: two / four spans per wave in the split tracker's tracking kernel whatever the batch size
     bool no_fuse = false;               // WSA_NO_FUSE: the separate scan / gather / publish kernels at the end of a run instead of the fused compaction
@@ -45,6 +45,40 @@ struct Tuning {
     int rs_s = 0, rs_j = 0, rs_c = 0;   // WSA_RS_S / WSA_RS_J / WSA_RS_C: the rate converter's outputs per block row / per lane and run, runs per block (0: default)
     bool rs_one_launch = false;         // WSA_RS_ONE_LAUNCH: a mixed-rate batch's K0 as one launch over the whole work list instead of one per rate class
     static Tuning from_env();
+};
+
+// The bits of WSA_DBG (Tuning::dbg, handed to the kernels as GateParams::dbg / TrParams::dbg; tools/README.md lists the numbers, which tests and tools
+// pass through the environment).  TUNING: the switch exists only in a library built with `make TUNING=1` (tracker.hip's WSA_TUNE).
+enum : int {
+    DBG_NO_FINALIZE = 1,                // TUNING, tracker: spans are tracked but not finalized (tools/dbg_sweep.sh, tools/span_probe.py)
+    DBG_NO_ACCUMULATE = 2,              // TUNING, tracker: the spans' frames are walked, nothing is tracked (tools/dbg_sweep.sh)
+    DBG_NO_FEATURES = 4,                // TUNING, tracker: rows without their feature reductions (tools/dbg_sweep.sh, tools/pmc_whatif.sh)
+    DBG_NO_STRAIGHTEN = 8,              // TUNING, tracker: finalize without the straighten loop (tools/dbg_sweep.sh, tools/pmc_whatif.sh)
+    DBG_CYCLES = 16,                    // the trace buffer holds the tracker's cycle counts, not the reference trace: the gate leaves it alone, the paired kernels may run (always there);
+                                        // TUNING: the tracker writes them (tools/span_probe.py, pair_probe.py, fin_probe.py, redo_probe.py)
+    DBG_NO_ENTRIES = 32,                // TUNING, tracker: no candidate entries are loaded (tools/span_probe.py what-ifs)
+    DBG_NO_PREFETCH = 64,               // TUNING, tracker: the one-span kernel does not fetch frame headers two blocks ahead
+    DBG_GENERIC_FINALIZE = 256,         // tracker: the generic (HBM) finalize for every span (tests/test_gpu_parity.py, tools/dbg_sweep.sh)
+    DBG_PHASES = 512,                   // TUNING, tracker: with DBG_CYCLES, cycles per accumulate phase of the one-span kernel (tools/span_probe.py)
+    DBG_SMALL_TABLE = 1024,             // tracker: the fast variant's track table overflows at 12 tracks — the rerun path (tests/test_gpu_parity.py)
+    DBG_GATE_F64 = 2048,                // gate: the f64 lane-per-candidate kernel also under the auto gate (tests/test_gpu_parity.py)
+    DBG_GATE_GENERAL = 4096,            // gate: every frame through the integer kernel's general path (tests/test_gpu_parity.py)
+    DBG_UNSORTED_SPANS = 8192,          // batch: spans in (clip, segment) order instead of sorted by length (tools/README.md)
+    DBG_SMALL_GROUP_TABLE = 16384,      // tracker: the paired / quad variant's table overflows at 12 tracks — the redo list (tests/test_gpu_parity.py, test_gpu_tracker_limits.py)
+    DBG_SELECT_LOOP = 32768,            // tracker: straighten keeps the selection loop instead of the [filing index][rank] table (tests/test_gpu_parity.py "select")
+    DBG_NO_PACKED_COLUMNS = 65536,      // tracker: feature sums one formant column at a time also for inputs of at most 15 frames (tests/test_gpu_parity.py)
+    DBG_EVENTS_BLOCK = 131072,          // tracker: the energy events of every input through energy_events_block (tests/test_gpu_parity.py)
+    DBG_NO_THIRD_FORM = 262144,         // tracker: the finalize kernel's third LDS form off (tests/test_gpu_parity.py)
+    DBG_PEAKS_SHIFT = 20,               // bits 20 .. 27 are PkParams::dbg of a batch's peak scan, shifted up (the PK_DBG_* below; tools/app_defaults_profile.sh, tools/pmc_whatif.sh)
+};
+// PkParams::dbg, all TUNING (peaks.hip's WSA_PKT): parts of the peak scan switched off (tools/peaks_probe.py, tools/pmc_probe.sh through wsa_debug_peaks_time)
+enum : int {
+    PK_DBG_NO_EMISSION = 1,             // the candidate list is not worked off
+    PK_DBG_NO_STATE_MACHINE = 2,        // the per-bin walk of a word's remaining bins is skipped
+    PK_DBG_NO_MASK_PASS = 4,            // the rise / fall masks of a round are not formed
+    PK_DBG_NO_STORES = 8,               // candidates are not stored
+    PK_DBG_NO_LDS_ATOMIC = 16,          // no arg-max of the largest candidate
+    PK_DBG_NO_GLOBAL_PATH = 32,         // prefix sums below the ring are not fetched from global memory
 };
 
 struct FeParams {
@@ -83,7 +117,7 @@ struct PkParams {
     // record slot s * ring + ((frames the stream has seen so far + j) & (ring - 1)); frames j >= n_frames[s] are skipped
     const double* stream_state = nullptr; const uint32_t* n_frames = nullptr; uint32_t step_frames = 0, ring = 0;
     uint32_t* flags = nullptr;          // bit 0 is raised when a frame holds more than CAND_CAP candidates (only possible above 128 bands)
-    int dbg = 0;                        // tuning experiments (TUNING=1 builds, wsa_debug_peaks_time): 1 no emission, 2 no state machine, 4 no mask pass
+    int dbg = 0;                        // tuning experiments (TUNING=1 builds, wsa_debug_peaks_time): PK_DBG_* bits
     int lanes_only = 0, wpc = 0;        // host side only (Tuning::peaks_lanes, peaks_wpc)
     int round_bins = 0;                 // host side only: bins per round of the lane-per-frame kernel, 16 or 32 (0: default)
 };
@@ -131,7 +165,7 @@ struct TrParams {
     char* ws = nullptr; uint64_t ws_stride = 0; int tcap = 0, pcap = 0, fcap = 0;
     int32_t* row_meta = nullptr; double* row_feat = nullptr; uint32_t row_cap = 0; uint32_t* clip_rows = nullptr;     // row pool: row_cap rows per clip, filled in completion order
     double* trace = nullptr;
-    int dbg = 0;                        // tuning experiments only (WSA_DBG)
+    int dbg = 0;                        // WSA_DBG: DBG_* bits
     uint32_t ring_mask = 0xffffffffu;   // 0xffffffff for a batch; ring - 1 when frames live in per-stream rings
     float* formants = nullptr;          // levels 4 / 10: [total_frames][9] f32 straightened frames, or nullptr
     // incremental streaming (tracker_kernel_stream): tracker state of every stream between steps
