@@ -93,7 +93,8 @@ def norm2(x):
     return math.sqrt(acc)
 
 
-def gradient(f, x):
+def gradient(f, x, shrink=16):
+    """numeric.gradient; shrink = 16 is numeric's own divisor of the step h on a retry (tests pass another one to see which results depend on it)."""
     n = len(x)
     f0 = f(x)
     if f0 != f0:
@@ -113,7 +114,7 @@ def gradient(f, x):
             f2 = f(x0)
             x0[i] = x[i]
             if f1 != f1 or f2 != f2:
-                h /= 16
+                h /= shrink
                 continue
             J[i] = _div(f1 - f2, 2 * h)
             t0, t1, t2 = x[i] - h, x[i], x[i] + h
@@ -122,7 +123,7 @@ def gradient(f, x):
             N = max(abs(J[i]), abs(f0), abs(f1), abs(f2), abs(t0), abs(t1), abs(t2), 1e-8)
             errest = min(_div(max(abs(d1 - J[i]), abs(d2 - J[i]), abs(d1 - d2)), N), _div(h, N))
             if errest > 1e-3:
-                h /= 16
+                h /= shrink
             else:
                 break
     return J

@@ -1,5 +1,5 @@
 // debug.hip — test entries of libwsa that are NOT part of include/wsa.h: unit access to device-side pieces that the public
-// entry points only exercise through their consequences (tests/test_gpu_units.py).
+// entry points only exercise through their consequences (tests/test_gpu_units.py, tests/test_gpu_coeffs.py).
 #include <vector>
 #include "host_plan.hpp"
 #include "api_internal.hpp"
@@ -191,4 +191,56 @@ extern "C" int wsa_debug_batch_tiers(wsa_batch* b, void* stream, uint32_t* out3)
     if (hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)) != hipSuccess || hipMemcpy(c, d, sizeof(c), hipMemcpyDeviceToHost) != hipSuccess) return WSA_ERR_HIP;
     out3[0] = c[1]; out3[1] = c[5]; out3[2] = c[6];       // d_counters[1]: flags; [4 + 1]: spans (span_order_kernel); [4 + 2]: TrParams::redo_count
     return WSA_OK;
+}
+
+// K5 (csrc/coeffs.hip) on its own: hand-built syllables straight into coeffs_kernel, in the batch geometry (ring_mask = ~0, scratch_stride = 0: clip c's
+// frames are rows frame_off[c] .. frame_off[c + 1] of the frame tables) or the streams' (ring_mask = ring - 1, scratch_stride >= ring_mask + longest
+// syllable: stream c's ring is rows frame_off[c] .. + ring).  formants [frame_off[n_clips]][9] f32, sums [frame_off[n_clips]] f32, frame_off [n_clips + 1],
+// row_meta [n_rows][8] i32 (slot 0 the clip, 6 the syllable's first frame, 7 its length), one launch_coeffs over rows_cap >= n_rows rows.
+// out [rows_cap][WSA_NFEAT] f64: every slot starts as `sentinel`, slot 23 of the first n_rows rows as 0 (what the level-10 row leaves there).
+// total_frames is the drivers': all frames of a batch (api.hip), n x 2 x ring for streams (stream_api.hip; here n x scratch_stride).
+// Refused, nothing run: whatever would make the kernel read or write outside these tables.
+extern "C" int wsa_debug_coeffs(int32_t device, const float* formants, const float* sums, const uint32_t* frame_off, uint32_t n_clips,
+                                const int32_t* row_meta, uint32_t n_rows, uint32_t rows_cap, uint32_t ring_mask, uint32_t scratch_stride,
+                                double sentinel, double* out) {
+    if (!formants || !sums || !frame_off || !row_meta || !out || n_clips < 1 || n_clips > (1u << 16) || n_rows < 1 || rows_cap < n_rows || rows_cap > (1u << 20)) return WSA_ERR_INVALID;
+    const uint64_t ring = (uint64_t)ring_mask + 1;
+    if ((ring & (ring - 1)) != 0) return WSA_ERR_INVALID;                                   // frames are read at (st + r) & ring_mask
+    if (scratch_stride == 0 && ring_mask != 0xffffffffu) return WSA_ERR_INVALID;            // batches do not wrap
+    if (scratch_stride != 0 && ring_mask == 0xffffffffu) return WSA_ERR_INVALID;
+    for (uint32_t c = 0; c < n_clips; c++) {
+        if (frame_off[c + 1] < frame_off[c] || frame_off[c + 1] > (1u << 24)) return WSA_ERR_INVALID;
+        if (scratch_stride && frame_off[c + 1] - frame_off[c] < ring) return WSA_ERR_INVALID;    // a whole ring per stream
+    }
+    for (uint32_t r = 0; r < n_rows; r++) {
+        const int32_t* m = row_meta + (size_t)r * 8;
+        if (m[0] < 0 || (uint32_t)m[0] >= n_clips || m[6] < 0 || m[7] < 0) return WSA_ERR_INVALID;
+        const uint64_t frames = frame_off[m[0] + 1] - frame_off[m[0]];
+        if (scratch_stride == 0 ? (uint64_t)m[6] + (uint64_t)m[7] > frames : (uint64_t)m[7] > ring) return WSA_ERR_INVALID;      // a syllable outside its clip's frames (its ring)
+        if (scratch_stride && (uint64_t)ring_mask + (uint64_t)m[7] > scratch_stride) return WSA_ERR_INVALID;                    // scratch rows (st & ring_mask) .. + sl stay inside the stream's region
+    }
+    const uint64_t frames_all = frame_off[n_clips];
+    const uint64_t total = scratch_stride ? (uint64_t)n_clips * scratch_stride : frames_all;
+    if (total > (1u << 26)) return WSA_ERR_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return WSA_ERR_NO_DEVICE;
+    std::vector<double> h((size_t)rows_cap * WSA_NFEAT, sentinel);
+    for (uint32_t r = 0; r < n_rows; r++) h[(size_t)r * WSA_NFEAT + 23] = 0.0;
+    const uint32_t totals[4] = {n_rows, 0, 0, 0};
+    wsa::DevArena A; float *dfr = nullptr, *dsum = nullptr; uint32_t *doff = nullptr, *dtot = nullptr; int32_t* dmeta = nullptr; double *dfeat = nullptr, *dws = nullptr;
+    bool ok = A.alloc(&dfr, (size_t)frames_all * 9) && A.alloc(&dsum, (size_t)frames_all) && A.alloc(&doff, (size_t)n_clips + 1) && A.alloc(&dtot, 4)
+           && A.alloc(&dmeta, (size_t)n_rows * 8) && A.alloc(&dfeat, h.size()) && A.alloc(&dws, (size_t)total * 8, true)
+           && (frames_all == 0 || (hipMemcpy(dfr, formants, (size_t)frames_all * 9 * sizeof(float), hipMemcpyHostToDevice) == hipSuccess
+                                   && hipMemcpy(dsum, sums, (size_t)frames_all * sizeof(float), hipMemcpyHostToDevice) == hipSuccess))
+           && hipMemcpy(doff, frame_off, ((size_t)n_clips + 1) * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess
+           && hipMemcpy(dtot, totals, sizeof(totals), hipMemcpyHostToDevice) == hipSuccess
+           && hipMemcpy(dmeta, row_meta, (size_t)n_rows * 8 * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess
+           && hipMemcpy(dfeat, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        wsa::CoefParams q;
+        q.row_meta = dmeta; q.row_feat = dfeat; q.frame_off = doff; q.totals = dtot; q.formants = dfr; q.sums = dsum;
+        q.ws = dws; q.total_frames = (uint32_t)total; q.ring_mask = ring_mask; q.scratch_stride = scratch_stride;
+        wsa::launch_coeffs(q, rows_cap, nullptr);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dfeat, h.size() * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    return ok ? WSA_OK : WSA_ERR_HIP;
 }

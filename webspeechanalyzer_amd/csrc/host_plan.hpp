@@ -181,7 +181,7 @@ struct BackEnd {
     }
     void fill(CoefParams& q, const uint32_t* frame_off) const {
         q.row_meta = d_meta; q.row_feat = d_feat; q.frame_off = frame_off; q.totals = d_totals; q.formants = d_formants; q.sums = d_sums;
-        q.ws = d_coef_ws; q.shared = d_counters;
+        q.ws = d_coef_ws;          // (a fit that numeric would have thrown out of is reported per row, in slot 23: no flag word)
     }
 };
 

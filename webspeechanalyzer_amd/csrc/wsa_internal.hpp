@@ -303,7 +303,6 @@ struct CoefParams {
     const uint32_t* frame_off = nullptr; const uint32_t* totals = nullptr;   // totals[0] = number of rows
     const float* formants = nullptr; const float* sums = nullptr;        // [total_frames][9], [total_frames]
     double* ws = nullptr; uint32_t total_frames = 0;               // scratch: 8 x total_frames doubles (points of the four fits)
-    uint32_t* shared = nullptr;                      // flags (bit 2: a fit hit numeric's "gradient fails" path)
     // streams: the frames live in per-stream rings (frame f of stream c at frame_off[c] + (f & ring_mask)); a syllable's scratch rows are
     // then taken from a per-stream region of scratch_stride (= 2 x ring) rows, where they do not wrap.  Batches: ring_mask = ~0, scratch_stride = 0
     uint32_t ring_mask = 0xffffffffu, scratch_stride = 0;
