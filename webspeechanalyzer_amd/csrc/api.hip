@@ -60,8 +60,8 @@ struct wsa_batch {
     uint32_t reruns = 0;
     uint32_t res_rows = 0, res_segs = 0, res_flags = 0;
     const uint32_t* spec_in_use = nullptr;
-    wsa_cls* cls = nullptr;                 // wsa_batch_classify (classify.hip)
-    wsa_ecls* ecls = nullptr;               // wsa_batch_classify_ensemble (classify.hip)
+    wsa_cls* cls = nullptr;                 // wsa_batch_classify (classify_batch.hip)
+    wsa_ecls* ecls = nullptr;               // wsa_batch_classify_ensemble (classify_batch.hip)
     int cls_last = 0;                       // which the last classification was (1 / 2; 3: wsa_batch_regress): their results stay apart
 };
 

@@ -19,7 +19,7 @@ inline wsa_status fail(wsa_ctx* c, wsa_status st, const std::string& msg) {
 }
 }  // namespace wsa_api
 
-// classify.hip (K6 / K6b) reads a batch's compacted rows and keeps its own per-batch state; api.hip owns the batch object
+// classify_batch.hip (K6 / K6b) reads a batch's compacted rows and keeps its own per-batch state; api.hip owns the batch object
 struct wsa_cls;                                 // classification buffers of one batch (allocated by the first wsa_batch_classify)
 void wsa_cls_free(wsa_cls* c);                  // (wsa_batch_destroy)
 struct wsa_ecls;                                // ensemble tables of one batch (allocated by the first wsa_batch_classify_ensemble with an ensemble)
@@ -42,7 +42,7 @@ void wsa_model_info_internal(const wsa_model* m, wsa_ctx** ctx, int* n_classes, 
 int wsa_model_inputs_internal(const wsa_model* m);                                               // units[0]
 }              // fetch_totals: synchronise, read the counters (reruns the back end on a table overflow)
 
-// classify.hip also runs K6 / K6b inside a stream object's step (wsa_stream_set_model); stream_api.hip owns the stream object
+// classify_stream.hip runs K6 / K6b inside a stream object's step (wsa_stream_set_model); stream_api.hip owns the stream object
 struct wsa_scls;                                // classification state of one stream object: class tables, carried fold, pinned D2H tables
 struct wsa_scls_view {
     wsa_ctx* ctx; int level; uint32_t n_streams, rows_cap, d2h_rows;
