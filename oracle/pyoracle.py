@@ -412,8 +412,8 @@ def utterance_features(segs, syl_ci, frames):
             bump("h", trunc(4 * log10(f_)))
             bump("p", trunc(l_ / 2))
             bump("m", trunc(d_ / 2))
-            bump("g", trunc(10 * (sl - c_) / sl))
-            bump("y", trunc(10 * (sl - p_) / sl))
+            bump("g", trunc(div(10 * (sl - c_), sl)))       # a syllable of no frames: 0 / 0
+            bump("y", trunc(div(10 * (sl - p_), sl)))
             bump("v", trunc(20 * (s_ + 50) / 100), lo_clamp=True)
             bump("x", trunc(20 * (h_ + 50) / 100), lo_clamp=True)
             osum += sl

@@ -1,0 +1,292 @@
+"""K4 (csrc/utterance.hip) on its own: the hand-built results of tests/utterance_cases.py through the test entry wsa_debug_utterance (csrc/debug.hip)
+— one launch_utterance per batch layout (one case per clip; all cases with empty and all-dropped clips between them at other frame offsets; that launch
+at 1 / 255 / 256 / 257 / 513 clips for the count kernel's ranges) and one per step of the stream layouts (one segment per step in rings of 64 with
+wrapping syllables, steps of 0 .. 3 segments, everything in one step, 129 syllables in a step's result, START in mid-life, an idle stream beside the
+busy ones, entries that have left the 32-deep history), the host model of the steps advancing `carry` as compact_gather_kernel does.
+
+Level 11's contract is bit for bit, so nothing here has a tolerance: the 264 doubles of a row equal what the REFERENCE's get_utterance_features
+returned for the same result prefix (tests/golden/utterance_expected.json; tests/test_utterance_reference.py shows the oracle to equal it and counts
+the clamps, poisonings, loop trips and index shifts the cases reach), utt_meta is {clip, result index, first start, summed lengths}, clip_utt_off and
+totals[3] count the results, rows past them keep the sentinel.  A case gives the same bits wherever it sits — any clip index, clip count, frame
+offset, ring position, split into steps — and the state a stream is left with is the same for every split.
+
+Each test takes well under a second: the tables are 76 .. 7000 frames per batch launch and 64 .. 1024 frames per stream and step.
+
+Mutation check (scratch builds of utterance.hip, not committed; each run through this file on an MI355X).  Failing it, with the tests that fail:
+  the upper clamp to n instead of n - 1 (the last histogram's kept inside the table)   every batch and stream layout
+  `if (o > 0)` dropped                                                                 every batch and stream layout
+  the syllable loop stopping after its first trip                                      batch-one-per-clip, batch-interleaved, stream-counts
+  the ghost counters not saved to the state                                            stream-each / -gappy / -counts / -restart / -lost, same bits wherever
+  prev_end not carried                                                                 the same five stream layouts, same bits wherever, the state test
+  `% CARRY_HIST` replaced by `% (CARRY_HIST - 1)`                                      stream-each, stream-gappy, same bits wherever, the state test
+  `per` computed with floor in the count kernel (the entry's offsets starting as 0,    every batch layout but batch-256-clips (where floor and ceiling
+    so that the clips it skips cannot send rows outside utt_feat)                        agree), every stream layout
+  lo_clamp applied to `d`                                                              six batch layouts, stream-each / -gappy / -all
+Surviving, and bound to: lo_clamp applied to `g`.  g's argument is 10 (e - c1) / e with 0 <= c1 <= e, the number of the syllable's e frames that
+have a first formant: it is never negative, and its only other value, NaN for e = 0 (poison-no-frames), is taken before the clamp is looked at.  No
+input the entry admits tells that build from the committed one; the same change on `d`, whose argument does go negative, is the last line above.
+
+On an MI355X every row of every layout equalled the reference bit for bit: 49 cases, 251 rows, 13 layouts (7 batch launches, 145 stream steps in 6 stream layouts), 0.21 s for the launches, the file in 2.5 s.
+"""
+import collections
+import ctypes
+import os
+import time
+
+import numpy as np
+import pytest
+
+from tests import utterance_cases as uc
+from tests.util import GOLDEN
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+SENTINEL = -77777
+WSA_OK, WSA_ERR_INVALID = 0, 1
+LAYOUTS = {l["name"]: l for l in uc.layouts()}
+BATCH = [n for n, l in LAYOUTS.items() if l["geometry"] == "batch"]
+STREAM = [n for n, l in LAYOUTS.items() if l["geometry"] == "stream"]
+GARBAGE = (0xA5C30000 + 257 * np.arange(uc.UTT_STATE_WORDS)).astype(np.uint32)      # what a stream's state holds before its first START (word 280, the result count, above 2^31)
+
+
+def _lib():
+    from webspeechanalyzer_amd import capi
+    L = capi.lib()
+    vp, u32, i32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32
+    L.wsa_debug_utterance.argtypes = [i32, vp, u32, vp, vp, u32, vp, vp, vp, u32, u32, u32, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.wsa_debug_utterance.restype = ctypes.c_int
+    return L
+
+
+Out = collections.namedtuple("Out", "rc feat meta off totals state")
+
+
+def _call(t, state=None, **over):
+    """one launch; the host's output tables start as SENTINEL + 1, so an entry that returns without running leaves them; `over` replaces tables or
+    n_segs / n_rows / n_clips / rows_cap / ring_mask / carry / ctl"""
+    t = dict(t, **over)
+    seg, so = np.ascontiguousarray(t["segments"], np.int32), np.ascontiguousarray(t["clip_seg_off"], np.uint32)
+    rm, ro = np.ascontiguousarray(t["row_meta"], np.int32), np.ascontiguousarray(t["clip_row_off"], np.uint32)
+    fr, fo = np.ascontiguousarray(t["formants"], np.float32), np.ascontiguousarray(t["frame_off"], np.uint32)
+    n_clips, cap = t["n_clips"], t["rows_cap"]
+    feat, meta = np.full((cap, uc.NBINS), float(SENTINEL + 1)), np.full((cap, 4), SENTINEL + 1, np.int32)
+    off, totals = np.full(n_clips + 1, (SENTINEL + 1) & 0xFFFFFFFF, np.uint32), np.full(4, (SENTINEL + 1) & 0xFFFFFFFF, np.uint32)
+    st = None if state is None else np.ascontiguousarray(state, np.uint32).copy()
+    carry = None if t.get("carry") is None else np.ascontiguousarray(t["carry"], np.int32)
+    ctl = None if t.get("ctl") is None else np.ascontiguousarray(t["ctl"], np.uint32)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    rc = _lib().wsa_debug_utterance(0, ptr(seg), t.get("n_segs", len(seg)), ptr(so), ptr(rm), t.get("n_rows", len(rm)), ptr(ro), ptr(fr), ptr(fo), n_clips, cap,
+                                    t.get("ring_mask", 0xFFFFFFFF), ptr(st), ptr(carry), ptr(ctl), SENTINEL, ptr(feat), ptr(meta), ptr(off), ptr(totals))
+    return Out(rc, feat, meta, off, totals, st)
+
+
+def _untouched(o, state_in=None):
+    return ((o.feat == SENTINEL + 1).all() and (o.meta == SENTINEL + 1).all() and (o.off == (SENTINEL + 1) & 0xFFFFFFFF).all()
+            and (o.totals == (SENTINEL + 1) & 0xFFFFFFFF).all() and (state_in is None or np.array_equal(o.state, state_in)))
+
+
+@pytest.fixture(scope="module")
+def golden():
+    rows, digests = uc.load_golden(os.path.join(GOLDEN, "utterance_expected.json"))
+    assert list(rows) == [c["name"] for c in uc.CASES] and all(digests[c["name"]] == uc.digest(c) for c in uc.CASES)
+    return [rows[c["name"]] for c in uc.CASES]
+
+
+@pytest.fixture(scope="module")
+def device():
+    """every layout once: name -> (tables, outputs, seconds); a stream layout's tables and outputs are per step, the state threaded through"""
+    assert torch.cuda.is_available(), "needs a GPU"
+    res = {}
+    for name, lay in LAYOUTS.items():
+        tabs = uc.tables(lay)
+        t0 = time.perf_counter()
+        if lay["geometry"] == "batch":
+            outs = _call(tabs)
+            assert outs.rc == WSA_OK, (name, outs.rc)
+        else:
+            state, outs = np.tile(GARBAGE, (len(lay["streams"]), 1)), []
+            for k, t in enumerate(tabs):
+                o = _call(t, state)
+                assert o.rc == WSA_OK, (name, k, o.rc)
+                outs.append(o)
+                state = o.state
+        res[name] = (tabs, outs, time.perf_counter() - t0)
+    return res
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+def _check_rows(where, t, o, golden, skip=()):
+    """the launch's rows against the golden, its offsets and totals; rows of the streams in `skip` are not compared"""
+    n = len(t["expect"])
+    per_clip = collections.Counter(clip for clip, _, _ in t["expect"])
+    want_off = np.concatenate([[0], np.cumsum([per_clip[c] for c in range(t["n_clips"])])])
+    assert np.array_equal(o.off, want_off), (where, o.off.tolist(), want_off.tolist())
+    assert o.totals[3] == n and o.totals[0] == 0 and o.totals[1] == 0, (where, o.totals.tolist())
+    compared = 0
+    for j, (clip, ci, k) in enumerate(t["expect"]):
+        c = uc.CASES[ci]
+        if clip in skip:
+            continue
+        bad = np.flatnonzero(_bits(o.feat[j]) != _bits(golden[ci][k]))
+        assert len(bad) == 0, (where, "row", j, c["name"], "result", k, "clip", clip, "slots", bad.tolist(), o.feat[j][bad].tolist(), golden[ci][k][bad].tolist())
+        assert o.meta[j].tolist() == [clip, k, *uc.expected_meta(c, k)], (where, j, c["name"], k, o.meta[j].tolist())
+        compared += 1
+    assert (o.feat[n:] == float(SENTINEL)).all() and (o.meta[n:] == SENTINEL).all() and len(o.feat) > n, where      # rows past the result count: untouched
+    return compared
+
+
+@pytest.mark.parametrize("name", BATCH)
+def test_batch_rows_equal_the_reference_bit_for_bit(name, device, golden):
+    t, o, secs = device[name]
+    n = _check_rows(name, t, o, golden)
+    assert o.totals[2] == 0
+    print(f"\n{name}: {t['n_clips']} clips, {len(t['segments'])} segments, {len(t['row_meta'])} syllables, {len(t['formants'])} frames, {n} rows equal the reference, {secs * 1e3:.1f} ms")
+
+
+@pytest.mark.parametrize("name", STREAM)
+def test_stream_rows_equal_the_reference_after_every_step(name, device, golden):
+    tabs, outs, secs = device[name]
+    lay = LAYOUTS[name]
+    n = flagged = 0
+    lost_so_far = set()
+    for k, (t, o) in enumerate(zip(tabs, outs)):
+        lost_so_far |= set(t["lost"])
+        n += _check_rows((name, "step", k), t, o, golden, skip=t["lost"])
+        assert (o.totals[2] & 1) == (1 if t["lost"] else 0), (name, k, o.totals.tolist(), t["lost"])      # an entry has left the history: said, for that launch alone
+        flagged += bool(t["lost"])
+    assert (name == "stream-lost") == bool(lost_so_far)
+    print(f"\n{name}: ring {lay['ring']}, {len(lay['streams'])} streams, {len(tabs)} steps, {n} rows equal the reference, {flagged} steps flagged, {secs * 1e3:.1f} ms")
+
+
+def test_a_case_gives_the_same_bits_wherever_it_sits(device, golden):
+    """over all layouts: clip index, clip count, frame offset, ring position and the split into steps do not show in a row"""
+    rows = collections.defaultdict(list)
+    for name in LAYOUTS:
+        tabs, outs, _ = device[name]
+        for t, o in ([(tabs, outs)] if LAYOUTS[name]["geometry"] == "batch" else zip(tabs, outs)):
+            for j, (clip, ci, k) in enumerate(t["expect"]):
+                if clip not in t.get("lost", ()):
+                    rows[(ci, k)].append((name, clip, o.feat[j]))
+    for (ci, k), lst in rows.items():
+        for name, clip, r in lst[1:]:
+            assert np.array_equal(_bits(r), _bits(lst[0][2])), (uc.CASES[ci]["name"], k, lst[0][:2], (name, clip))
+    assert len(rows) == sum(len(c["results"]) for c in uc.CASES)
+    places = sorted(len(v) for v in rows.values())
+    print(f"\n{len(rows)} rows of {len(uc.CASES)} cases, each in {places[0]} .. {places[-1]} places; launches took {1e3 * sum(s for _, _, s in device.values()):.0f} ms in all")
+    assert places[0] >= 2 and places[len(places) // 10] >= 4
+
+
+def _lives(script):
+    """[(case index, first step, [segment indices fed])] of a stream's script"""
+    out = []
+    for k, st in enumerate(script):
+        if st and st[1]:
+            out.append([st[0], k, []])
+        if st:
+            out[-1][2] += st[2]
+    return out
+
+
+def test_a_streams_state_is_the_same_for_every_split(device):
+    """the 288 words a stream is left with — bins, ghost counters, result count, prev_end, tsum, first start — after a whole case, whichever way its
+    segments were dealt over the steps, behind a START in mid-life as on a fresh stream; an idle stream's words come back as they went in"""
+    final = collections.defaultdict(list)
+    idle = 0
+    for name in STREAM:
+        tabs, outs, _ = device[name]
+        lost = {s for t in tabs for s in t["lost"]}
+        for s, sc in enumerate(LAYOUTS[name]["streams"]):
+            st = outs[-1].state[s]
+            lives = _lives(sc)
+            if not lives:
+                assert np.array_equal(st, GARBAGE), (name, s)
+                idle += 1
+            elif lives[-1][2] == list(range(len(uc.CASES[lives[-1][0]]["segs"]))) and s not in lost:
+                final[lives[-1][0]].append((name, s, len(lives), st))
+    restarted = 0
+    for ci, lst in final.items():
+        for name, s, nl, st in lst[1:]:
+            bad = np.flatnonzero(st != lst[0][3])
+            assert len(bad) == 0, (uc.CASES[ci]["name"], lst[0][:2], (name, s), bad.tolist())
+        restarted += any(nl > 1 for _, _, nl, _ in lst) and len(lst) > 1
+        st = lst[0][3]                                                   # and the words are what they are said to be
+        c = uc.CASES[ci]
+        first, tsum = c["segs"][0][0], sum(sg[1] for sg in c["segs"])
+        assert (int(st[280]), int(st[284]), int(st[285]), int(st[286])) == (len(c["results"]), tsum, first, 1), (c["name"], st[280:287].tolist())
+        k = len(c["results"]) - 1
+        assert np.array([st[282], st[283]], np.uint32).view(np.float64)[0] == float(c["segs"][k][0] + c["segs"][k][1]), c["name"]
+        assert np.array_equal(st[[279, 281, 287]], GARBAGE[[279, 281, 287]])
+        ghosts = collections.Counter(h for row in uc.bumps(c) for h, x, _ in row if uc.classify(h, x) in ("nan", "negative"))
+        assert st[264:279].tolist() == [ghosts[h] for h in uc.ORDER], (c["name"], st[264:279].tolist())       # the ghost counters: one per poisoning bump
+        bumped = collections.Counter(h for row in uc.bumps(c) for h, _, _ in row)
+        assert [int(st[uc.OFF[h]:uc.OFF[h] + uc.SIZES[h]].sum()) + ghosts[h] for h in uc.ORDER] == [bumped[h] for h in uc.ORDER], c["name"]
+    several = sum(len(v) >= 3 for v in final.values())
+    print(f"\n{len(final)} cases' final states, {several} of them from three splits or more, {restarted} also behind a START in mid-life; {idle} idle streams")
+    assert several >= 30 and restarted >= 3 and idle >= 4
+
+
+def test_the_entry_refuses_what_would_leave_its_tables():
+    assert torch.cuda.is_available(), "needs a GPU"
+    I = uc.INDEX
+    t = uc.tables(dict(name="two", geometry="batch", clips=[(I["top-d"], 2), (None, 0), (I["drop-two"], 0)]))
+    o = _call(t)
+    assert o.rc == WSA_OK and not _untouched(o)                                   # the valid call, then one thing wrong at a time
+    bad = []
+    tamper = lambda key, fn: tamper_s(t, key, fn)
+    def swap(a):
+        a[1], a[2] = a[2] + 1, a[1]
+    bad.append(("segment offsets that go down", t, None, tamper("clip_seg_off", swap)))
+    bad.append(("row offsets that go down", t, None, tamper("clip_row_off", swap)))
+    bad.append(("frame offsets that go down", t, None, tamper("frame_off", swap)))
+    bad.append(("segment offsets that end past the table", t, None, dict(n_segs=len(t["segments"]) - 1)))
+    clip0_rows = int(t["clip_row_off"][1])
+    m = t["row_meta"][:clip0_rows]
+    r = int(np.argmax(m[:, 6] + m[:, 7]))
+    room = int(t["frame_off"][1]) - int(m[r, 6] + m[r, 7])
+    def past(a):
+        a[r, 7] += room + 1
+    def fits(a):
+        a[r, 7] += room
+    assert _call(t, **tamper("row_meta", fits)).rc == WSA_OK                       # up to its clip's last frame: fine
+    bad.append(("a syllable one frame past its clip's last", t, None, tamper("row_meta", past)))
+    bad.append(("a negative first frame", t, None, tamper("row_meta", lambda a: a.__setitem__((0, 6), -1))))
+    bad.append(("a row of a clip that does not exist", t, None, tamper("row_meta", lambda a: a.__setitem__((0, 0), t["n_clips"]))))
+    bad.append(("a row of another clip", t, None, tamper("row_meta", lambda a: a.__setitem__((0, 0), 2))))
+    results = len(t["expect"])
+    assert _call(t, rows_cap=results).rc == WSA_OK
+    bad.append(("more results than rows_cap", t, None, dict(rows_cap=results - 1)))
+    bad.append(("a ring in the batch geometry", t, None, dict(ring_mask=63)))
+    # streams: one step of two streams
+    lay = dict(name="s", geometry="stream", ring=64, streams=[uc.script(I["drop-two"], "all"), uc.script(I["top-u"], "each")])
+    s = uc.tables(lay)[0]
+    state = np.tile(GARBAGE, (2, 1))
+    o = _call(s, state)
+    assert o.rc == WSA_OK and not _untouched(o, state)
+    bad.append(("state without carry", s, state, dict(carry=None)))
+    bad.append(("state without ctl", s, state, dict(ctl=None)))
+    bad.append(("carry and ctl without state", s, None, dict(ring_mask=0xFFFFFFFF)))
+    bad.append(("ring_mask + 1 = 63, no power of two", s, state, dict(ring_mask=62)))
+    bad.append(("ring_mask + 1 = 48, no power of two", s, state, dict(ring_mask=47)))
+    bad.append(("a ring larger than a stream's frames", s, state, dict(ring_mask=127)))
+    bad.append(("streams without a ring", s, state, dict(ring_mask=0xFFFFFFFF)))
+    bad.append(("a syllable longer than the ring", s, state, tamper_s(s, "row_meta", lambda a: a.__setitem__((0, 7), 65))))
+    assert _call(s, state, **tamper_s(s, "row_meta", lambda a: a.__setitem__((0, 7), 64))).rc == WSA_OK
+    nseg0 = int(s["clip_seg_off"][1])
+    bad.append(("a history that has counted fewer segments than the step holds", s, state, tamper_s(s, "carry", lambda a: a.__setitem__((0, 0), nseg0 - 1))))
+    cont = s["ctl"].copy(); cont[:] = 0
+    bad.append(("a result count above 2^31 in the state of a stream that goes on", s, state, dict(ctl=cont)))
+    for what, tab, st, over in bad:
+        o = _call(tab, st, **over)
+        assert o.rc == WSA_ERR_INVALID and _untouched(o, st), what
+    print(f"\n{len(bad)} refusals")
+
+
+def tamper_s(t, key, fn):
+    a = t[key].copy()
+    fn(a)
+    return {key: a}

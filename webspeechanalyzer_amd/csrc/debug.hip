@@ -1,5 +1,6 @@
 // debug.hip — test entries of libwsa that are NOT part of include/wsa.h: unit access to device-side pieces that the public
-// entry points only exercise through their consequences (tests/test_gpu_units.py, tests/test_gpu_coeffs.py).
+// entry points only exercise through their consequences (tests/test_gpu_units.py, tests/test_gpu_coeffs.py, tests/test_gpu_utterance.py).
+#include <cstring>
 #include <vector>
 #include "host_plan.hpp"
 #include "api_internal.hpp"
@@ -191,6 +192,97 @@ extern "C" int wsa_debug_batch_tiers(wsa_batch* b, void* stream, uint32_t* out3)
     if (hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)) != hipSuccess || hipMemcpy(c, d, sizeof(c), hipMemcpyDeviceToHost) != hipSuccess) return WSA_ERR_HIP;
     out3[0] = c[1]; out3[1] = c[5]; out3[2] = c[6];       // d_counters[1]: flags; [4 + 1]: spans (span_order_kernel); [4 + 2]: TrParams::redo_count
     return WSA_OK;
+}
+
+// K4 (csrc/utterance.hip) on its own: hand-built segments, syllable rows and frames straight into ONE launch_utterance, in the batch geometry
+// (state == NULL, ring_mask = ~0: clip c's frames are rows frame_off[c] .. frame_off[c + 1] of `formants`, the tables hold the whole clips) or the
+// streams' (state, carry and ctl given, ring_mask = ring - 1: stream c's ring is rows frame_off[c] .. + ring, the tables hold ONE step's segments and
+// rows, carry [n_clips][CARRY_WORDS] is already advanced over them as compact_gather_kernel leaves it, state [n_clips][UTT_STATE_WORDS] goes in and
+// comes back).  segments [n_segs][4] i32 {clip, start, len, flag}, clip_seg_off / clip_row_off / frame_off [n_clips + 1], row_meta [n_rows][8] i32
+// (slot 0 the clip, 1 the result index, 6 the syllable's first frame, 7 its length).  Out: utt_feat [rows_cap][264] f64 and utt_meta [rows_cap][4] i32,
+// every slot starting as `sentinel`, clip_utt_off [n_clips + 1] and totals[3] likewise; totals[0 .. 2] start as 0 (K4 only ever ORs into totals[2]).
+// Refused, nothing run and nothing written: whatever would make the kernel read or write outside these tables.
+extern "C" int wsa_debug_utterance(int32_t device, const int32_t* segments, uint32_t n_segs, const uint32_t* clip_seg_off, const int32_t* row_meta, uint32_t n_rows,
+                                   const uint32_t* clip_row_off, const float* formants, const uint32_t* frame_off, uint32_t n_clips, uint32_t rows_cap,
+                                   uint32_t ring_mask, uint32_t* state, const int32_t* carry, const uint32_t* ctl, int32_t sentinel,
+                                   double* utt_feat, int32_t* utt_meta, uint32_t* clip_utt_off, uint32_t* totals4) {
+    if (!clip_seg_off || !clip_row_off || !frame_off || !utt_feat || !utt_meta || !clip_utt_off || !totals4) return WSA_ERR_INVALID;
+    if ((!segments && n_segs) || (!row_meta && n_rows) || n_clips < 1 || n_clips > (1u << 16) || rows_cap < 1 || rows_cap > (1u << 20)) return WSA_ERR_INVALID;
+    const bool streams = state != nullptr;
+    if (streams != (carry != nullptr) || streams != (ctl != nullptr)) return WSA_ERR_INVALID;          // the three stream tables come together
+    const uint64_t ring = (uint64_t)ring_mask + 1;
+    if ((ring & (ring - 1)) != 0) return WSA_ERR_INVALID;                                               // frames are read at (st + o) & ring_mask
+    if (streams == (ring_mask == 0xffffffffu)) return WSA_ERR_INVALID;                                  // batches do not wrap, streams do
+    if (clip_seg_off[0] != 0 || clip_row_off[0] != 0 || frame_off[0] != 0) return WSA_ERR_INVALID;
+    for (uint32_t c = 0; c < n_clips; c++) {
+        if (clip_seg_off[c + 1] < clip_seg_off[c] || clip_row_off[c + 1] < clip_row_off[c] || frame_off[c + 1] < frame_off[c]) return WSA_ERR_INVALID;
+        if (frame_off[c + 1] > (1u << 26)) return WSA_ERR_INVALID;
+        if (streams && frame_off[c + 1] - frame_off[c] < ring) return WSA_ERR_INVALID;                 // a whole ring per stream
+    }
+    if (clip_seg_off[n_clips] != n_segs || clip_row_off[n_clips] != n_rows || (formants == nullptr && frame_off[n_clips] != 0)) return WSA_ERR_INVALID;
+    uint64_t results = 0;
+    for (uint32_t c = 0; c < n_clips; c++) {
+        const uint32_t nseg = clip_seg_off[c + 1] - clip_seg_off[c];
+        for (uint32_t s = clip_seg_off[c]; s < clip_seg_off[c + 1]; s++) results += segments[(size_t)s * 4 + 3] >= 0 ? 1 : 0;
+        const uint64_t frames = frame_off[c + 1] - frame_off[c];
+        for (uint32_t r = clip_row_off[c]; r < clip_row_off[c + 1]; r++) {
+            const int32_t* m = row_meta + (size_t)r * 8;
+            if (m[0] < 0 || (uint32_t)m[0] >= n_clips || (uint32_t)m[0] != c || m[6] < 0 || m[7] < 0) return WSA_ERR_INVALID;   // a row of another clip, or of none
+            if (streams ? (uint64_t)m[7] > ring : (uint64_t)m[6] + (uint64_t)m[7] > frames) return WSA_ERR_INVALID;             // a syllable outside its clip's frames (its ring)
+        }
+        if (streams && nseg) {
+            const int32_t* cy = carry + (size_t)c * wsa::CARRY_WORDS;
+            if (cy[0] < 0 || (uint32_t)cy[0] < nseg) return WSA_ERR_INVALID;                            // K3 has counted this step's segments in already
+            if (!(ctl[c] & 1u) && state[(size_t)c * wsa::UTT_STATE_WORDS + 280] > 0x7fffffffu) return WSA_ERR_INVALID;    // the history is indexed with the result count
+        }
+    }
+    if (results > rows_cap) return WSA_ERR_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return WSA_ERR_NO_DEVICE;
+    const uint64_t frames_all = frame_off[n_clips];
+    std::vector<double> hf((size_t)rows_cap * 264, (double)sentinel);
+    std::vector<int32_t> hm((size_t)rows_cap * 4, sentinel);
+    std::vector<uint32_t> ho((size_t)n_clips + 1, (uint32_t)sentinel);
+    const uint32_t tot0[4] = {0, 0, 0, (uint32_t)sentinel};
+    wsa::DevArena A; float* dfr = nullptr; int32_t *dseg = nullptr, *dmeta = nullptr, *dum = nullptr, *dcarry = nullptr; double* duf = nullptr;
+    uint32_t *dso = nullptr, *dro = nullptr, *dfo = nullptr, *duo = nullptr, *dtot = nullptr, *dstate = nullptr, *dctl = nullptr;
+    const size_t noff = ((size_t)n_clips + 1) * sizeof(uint32_t);
+    bool ok = A.alloc(&dfr, (size_t)frames_all * 9 + 1) && A.alloc(&dseg, (size_t)n_segs * 4 + 1) && A.alloc(&dmeta, (size_t)n_rows * 8 + 1) && A.alloc(&dso, (size_t)n_clips + 1)
+           && A.alloc(&dro, (size_t)n_clips + 1) && A.alloc(&dfo, (size_t)n_clips + 1) && A.alloc(&duo, (size_t)n_clips + 1) && A.alloc(&dtot, 4) && A.alloc(&duf, hf.size()) && A.alloc(&dum, hm.size())
+           && (frames_all == 0 || hipMemcpy(dfr, formants, (size_t)frames_all * 9 * sizeof(float), hipMemcpyHostToDevice) == hipSuccess)
+           && (n_segs == 0 || hipMemcpy(dseg, segments, (size_t)n_segs * 4 * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess)
+           && (n_rows == 0 || hipMemcpy(dmeta, row_meta, (size_t)n_rows * 8 * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess)
+           && hipMemcpy(dso, clip_seg_off, noff, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dro, clip_row_off, noff, hipMemcpyHostToDevice) == hipSuccess
+           && hipMemcpy(dfo, frame_off, noff, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(duo, ho.data(), noff, hipMemcpyHostToDevice) == hipSuccess
+           && hipMemcpy(dtot, tot0, sizeof(tot0), hipMemcpyHostToDevice) == hipSuccess
+           && hipMemcpy(duf, hf.data(), hf.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
+           && hipMemcpy(dum, hm.data(), hm.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
+    const size_t nstate = (size_t)n_clips * wsa::UTT_STATE_WORDS, ncarry = (size_t)n_clips * wsa::CARRY_WORDS;
+    if (ok && streams)
+        ok = A.alloc(&dstate, nstate) && A.alloc(&dcarry, ncarry) && A.alloc(&dctl, n_clips)
+             && hipMemcpy(dstate, state, nstate * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess
+             && hipMemcpy(dcarry, carry, ncarry * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess
+             && hipMemcpy(dctl, ctl, (size_t)n_clips * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        wsa::UttParams u;
+        u.n_clips = n_clips; u.segments = dseg; u.row_meta = dmeta; u.clip_seg_off = dso; u.clip_row_off = dro; u.frame_off = dfo; u.formants = dfr;
+        u.clip_utt_off = duo; u.utt_meta = dum; u.utt_feat = duf; u.totals = dtot;
+        u.state = dstate; u.carry = dcarry; u.ctl = dctl; u.ring_mask = ring_mask;
+        wsa::launch_utterance(u, nullptr);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess
+             && hipMemcpy(hf.data(), duf, hf.size() * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess
+             && hipMemcpy(hm.data(), dum, hm.size() * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess
+             && hipMemcpy(ho.data(), duo, noff, hipMemcpyDeviceToHost) == hipSuccess;
+        uint32_t tot[4];
+        ok = ok && hipMemcpy(tot, dtot, sizeof(tot), hipMemcpyDeviceToHost) == hipSuccess;
+        std::vector<uint32_t> hs;
+        if (ok && streams) { hs.resize(nstate); ok = hipMemcpy(hs.data(), dstate, nstate * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess; }
+        if (ok) {                                                            // all or nothing: a failed run leaves the caller's tables as they were
+            memcpy(utt_feat, hf.data(), hf.size() * sizeof(double)); memcpy(utt_meta, hm.data(), hm.size() * sizeof(int32_t));
+            memcpy(clip_utt_off, ho.data(), noff); memcpy(totals4, tot, sizeof(tot));
+            if (streams) memcpy(state, hs.data(), nstate * sizeof(uint32_t));
+        }
+    }
+    return ok ? WSA_OK : WSA_ERR_HIP;
 }
 
 // K5 (csrc/coeffs.hip) on its own: hand-built syllables straight into coeffs_kernel, in the batch geometry (ring_mask = ~0, scratch_stride = 0: clip c's
