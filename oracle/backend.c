@@ -38,12 +38,37 @@ typedef struct {
     float *fr;              /* len x 9, level >= 4 */
     float *sm;              /* len x 3 (sum f*E, sum E, sum w*E), level >= 4 */
     int32_t max_peaks, max_live;  /* the span's load (see wsa_or_segment_load) */
+    int32_t fbegin, fend, cci;    /* the span of frames whose tracks it owns, c_ci at finalize (wsa_or_gate_segment) */
+    double g_ctx_max, g_floor;    /* ctx_max and the floor at finalize */
     double *trk; int32_t trk_n;   /* level 3: the ranked tracks the reference stores (`s.push(i)` @B28273), flattened:
                                    * n_tracks, then per track 10 scalars ([0] [1] [2] [4] [5] [6] [13] [14] [15] [17]) and
                                    * its six per-point arrays ([7] .. [12], `count` numbers each) */
 } segment_t;
 
 typedef struct { int32_t seg, start, len; double feat[53]; } syllable_t;
+
+/* the arms of the gate's state machine that tests/gate_cases.py aims at (wsa_or_gate_arm_*): bumped where the arm is taken, read only by tests */
+#define GATE_ARMS(X) \
+    X(start_pass) X(start_n4) X(start_n5) X(start_p7) X(start_p8) X(start_pmax) X(start_pmax_m1) X(start_r_equal) X(start_r_above) \
+    X(voiced_n0) X(voiced_p0) X(voiced_p6) X(voiced_p7) X(voiced_pmax_m1) X(voiced_pmax) \
+    X(d_equal) X(d_below) X(d_n3) X(d_g_equals_d) X(mx_covers) X(mx_short_n3) X(mx_short_d_covers) \
+    X(hdr_eos_largest) X(hdr_tie) \
+    X(unvoiced_at_0) X(unvoiced_at_1) X(unvoiced_at_2) X(voiced_at_0) X(voiced_at_1) \
+    X(gate_raise_above) X(gate_raise_equal_w) X(gate_decay) X(gate_decay_edge) X(gate_decay_refused_equal) X(gate_neither) X(gate_w40) X(gate_w41) \
+    X(floor_t7) X(floor_t6) X(floor_t4) X(floor_t2) X(floor_t1) X(floor_one) \
+    X(tk_reset_voiced) X(tk_reset_unvoiced) X(tk_equal) \
+    X(decay_first_w21) X(decay_stop) X(decay_clamp10) X(decay_zero_step) \
+    X(pause_int) X(pause_frac) X(breaker_rule_250) \
+    X(fin_len_min) X(fin_len_min1) X(fin_end_unstarted) X(fin_truncate_open) \
+    X(cand_16) X(cand_17) X(cand_64) X(late_n4) X(late_n3) X(late_d) \
+    X(ring_cut)
+#define X(a) ARM_##a,
+enum { GATE_ARMS(X) ARM_COUNT };
+#undef X
+#define X(a) #a,
+static const char *const arm_names[ARM_COUNT] = { GATE_ARMS(X) };
+#undef X
+#define ARM(S, a) ((S)->arms[ARM_##a]++)
 
 struct wsa_or_seg {
     wsa_or_cfg cfg;
@@ -63,6 +88,10 @@ struct wsa_or_seg {
     VEC(syllable_t) syls;
     int32_t trace_on;
     VEC(double) trace;
+    /* what the gate decided (test access, wsa_or_gate_*): per frame the accumulate_fm call, the span bookkeeping of csrc/gate.hip, the arm counters */
+    VEC(wsa_or_gate_frame) gframes;
+    int32_t span_begin, reset0_in_frame, voiced_now;
+    int64_t arms[ARM_COUNT];
 };
 
 static void track_free(track_t *t) {
@@ -79,6 +108,7 @@ static void clear_fm(wsa_or_seg *s) {
 /* L(e) reset_segment @B25649 */
 static void reset_segment(wsa_or_seg *s, int32_t started) {
     s->c_ci = 0; s->c_started = started; s->no_fm = 0; clear_fm(s);
+    if (started == 0) s->reset0_in_frame = 1;
 }
 
 wsa_or_seg *wsa_or_seg_new(const wsa_or_cfg *cfg) {
@@ -91,6 +121,7 @@ wsa_or_seg *wsa_or_seg_new(const wsa_or_cfg *cfg) {
                                                          : 250 / cfg->window_step;  /* @B25188 */
     s->min_frames = js_trunc(cfg->min_seg_length / cfg->window_step);        /* @B25218 */
     s->c_started = -1;
+    if (!(cfg->pause_length > 2 * cfg->window_step)) ARM(s, breaker_rule_250);
     if (cfg->auto_noise_gate) { s->ctx_max = 50; s->floor_ = 2; }           /* @B25471 */
     else {
         s->ctx_max = wsa_or_pow(10, cfg->voiced_max_dB / 20);
@@ -104,7 +135,7 @@ void wsa_or_seg_free(wsa_or_seg *s) {
     if (!s) return;
     clear_fm(s); VFREE(s->tracks);
     for (int32_t i = 0; i < s->segs.n; i++) { free(s->segs.p[i].fr); free(s->segs.p[i].sm); free(s->segs.p[i].trk); }
-    VFREE(s->segs); VFREE(s->syls); VFREE(s->trace);
+    VFREE(s->segs); VFREE(s->syls); VFREE(s->trace); VFREE(s->gframes);
     free(s);
 }
 
@@ -276,6 +307,8 @@ void wsa_or_formant_features(const float *fr, int32_t a, double ctx_max, double 
  * sep_syllables @B34757, make_syl_features @B34407 */
 static void finalize(wsa_or_seg *S, double e) {
     double len_d = e - S->no_fm;
+    if (S->c_started >= 2 && len_d == S->min_frames) ARM(S, fin_len_min);
+    if (S->c_started >= 2 && len_d == S->min_frames + 1) ARM(S, fin_len_min1);
     if (!(len_d > S->min_frames && S->c_started >= 2)) return;
     int32_t len = (int32_t)len_d;
     int32_t start = (int32_t)(S->cur_frame - len_d);
@@ -302,6 +335,8 @@ static void finalize(wsa_or_seg *S, double e) {
     segment_t seg; memset(&seg, 0, sizeof(seg));
     seg.start = start; seg.len = len; seg.syl0 = S->syls.n;
     seg.max_peaks = S->max_peaks; seg.max_live = S->max_live;
+    seg.fbegin = S->span_begin; seg.fend = (int32_t)S->cur_frame; seg.cci = (int32_t)S->c_ci;
+    seg.g_ctx_max = S->ctx_max; seg.g_floor = S->floor_;
     if (level == 3) {            /* ref @B28273: `u.push([e,a]), ..., s.push(i)` with i = get_ranked_formants() */
         size_t words = 1;
         for (int32_t t = 0; t < nr; t++) words += 10 + 6 * (size_t)S->tracks.p[rk[t]].frames.n;
@@ -380,23 +415,41 @@ static void finalize(wsa_or_seg *S, double e) {
 /* auto noise gate C(h) @B28506 */
 static void noise_gate(wsa_or_seg *S, double h) {
     S->w++;
+    if (S->w == 40 && h <= S->ctx_max && h > 2 * S->floor_) ARM(S, gate_w40);
     if (h > S->ctx_max || (S->w > 40 && h > 2 * S->floor_)) {
-        if (h >= S->ctx_max) { S->w = 0; S->last_max = S->ctx_max = h; }
-        else if (h > S->last_max / 100) { S->ctx_max -= js_trunc(S->ctx_max / 8); S->w = 35; }
+        if (!(h > S->ctx_max) && S->w == 41) ARM(S, gate_w41);
+        if (h >= S->ctx_max) {
+            if (h > S->ctx_max) ARM(S, gate_raise_above); else ARM(S, gate_raise_equal_w);
+            S->w = 0; S->last_max = S->ctx_max = h;
+        }
+        else if (h > S->last_max / 100) {
+            ARM(S, gate_decay);
+            if (100 * h == S->last_max + 1) ARM(S, gate_decay_edge);
+            S->ctx_max -= js_trunc(S->ctx_max / 8); S->w = 35;
+        } else {
+            ARM(S, gate_neither);
+            if (100 * h == S->last_max) ARM(S, gate_decay_refused_equal);
+        }
         double y = S->ctx_max, t = wsa_or_log10(y), v;
-        if (t > 7) v = js_trunc(wsa_or_pow(10, t - 3) / 20);
-        else if (t > 6) v = js_trunc(wsa_or_pow(10, t - 3) / 2);
-        else if (t > 4) v = js_trunc(wsa_or_pow(10, t - 2) / 2);
-        else if (t > 2) v = js_trunc(wsa_or_pow(10, t / 3));
-        else if (t > 1) v = js_trunc(y / 10);
-        else v = 1;
+        if (t > 7) { v = js_trunc(wsa_or_pow(10, t - 3) / 20); ARM(S, floor_t7); }
+        else if (t > 6) { v = js_trunc(wsa_or_pow(10, t - 3) / 2); ARM(S, floor_t6); }
+        else if (t > 4) { v = js_trunc(wsa_or_pow(10, t - 2) / 2); ARM(S, floor_t4); }
+        else if (t > 2) { v = js_trunc(wsa_or_pow(10, t / 3)); ARM(S, floor_t2); }
+        else if (t > 1) { v = js_trunc(y / 10); ARM(S, floor_t1); }
+        else { v = 1; ARM(S, floor_one); }
         S->floor_ = v; S->last_floor = v;
-        if (S->k > 0 && S->T / S->k < 30 * v) { reset_segment(S, 0); S->k = 0; S->T = 0; }
+        if (S->k > 0 && S->T / S->k == 30 * v) ARM(S, tk_equal);
+        if (S->k > 0 && S->T / S->k < 30 * v) {
+            if (S->voiced_now) ARM(S, tk_reset_voiced); else ARM(S, tk_reset_unvoiced);
+            reset_segment(S, 0); S->k = 0; S->T = 0;
+        }
         S->T += S->ctx_max; S->k += 1;
     } else if (S->floor_ > 10 && S->floor_ > S->last_floor / 10 && S->w > 20) {
+        if (S->w == 21) ARM(S, decay_first_w21);
+        if (js_trunc(S->last_floor / 20) == 0) ARM(S, decay_zero_step);
         S->floor_ -= js_trunc(S->last_floor / 20);
-        if (S->floor_ < 10) S->floor_ = 10;
-    }
+        if (S->floor_ < 10) { S->floor_ = 10; ARM(S, decay_clamp10); }
+    } else if (S->w > 20 && S->floor_ < S->last_floor) ARM(S, decay_stop);      /* a decay that has run into max(10, last_floor / 10) */
 }
 
 /* spectrum_push I(e,t) @B30392 (levels > 2) followed by one pass of the frame loop D() @B25717 */
@@ -408,7 +461,8 @@ void wsa_or_seg_push(wsa_or_seg *S, const uint32_t *e) {
     int32_t n = 0, i = 0, l = 0, s = 0, c = 0, u = 0, p = 0;
     double d = 0, h = 2 * v, g = 0;
     peak_t *pk = malloc(sizeof(peak_t) * (size_t)(B > 0 ? B : 1));
-#define EMIT(upd) do { if ((upd) && e[l] > h) { h = e[l]; p = l; } \
+    int32_t raw = 0, n_early = 0; double d_early = 0;     /* tests only: candidates by geometry alone (the device's table order); accepted ones among the first 16 */
+#define EMIT(upd) do { if (raw - 1 < 16) { n_early++; d_early += e[l]; } if ((upd) && e[l] > h) { h = e[l]; p = l; } \
         double thr = e[l] / 10.0; \
         while (i < l && e[i] < thr) i++; \
         while (s > l && e[s] < thr) s--; \
@@ -417,7 +471,7 @@ void wsa_or_seg_push(wsa_or_seg *S, const uint32_t *e) {
         g += e[a];
         if (e[a] > e[a - 1] && (a < 2 || e[a] > e[a - 2]) && (a < 3 || e[a] > e[a - 3])) {
             if (u == -1 || u == 0) {
-                if (u == -1 && e[l] > v && i <= l && l < s) EMIT(1);
+                if (u == -1 && i <= l && l < s) { raw++; if (e[l] > v) EMIT(1); }
                 i = a - 1; l = a;
             } else if (u == 1) l = a;
             u = 1;
@@ -425,29 +479,82 @@ void wsa_or_seg_push(wsa_or_seg *S, const uint32_t *e) {
             if (u == 1 || u == -1) { s = a; u = -1; }
         } else if (u == -1) {
             c++;
-            if (c > 2) { c = 0; if (e[l] > v && i <= l && l < s) EMIT(1); u = 0; }
+            if (c > 2) { c = 0; if (i <= l && l < s) { raw++; if (e[l] > v) EMIT(1); } u = 0; }
         } else if (u == 1 && e[a] > e[a - 1]) l = a;
-        if (a == B - 1 && u == 1) { s = a; l = a; if (e[l] > v && i < l && l <= s) EMIT(0); }
+        if (a == B - 1 && u == 1) { s = a; l = a; if (i < l && l <= s) { raw++; if (e[l] > v) EMIT(0); } }
     }
 #undef EMIT
+    /* ---- what the arms below are counted from (tests only; nothing here feeds the state) */
+    const double mvb = S->max_voiced_bin;
+    const double d16 = d_early; const int32_t n16 = n_early;
+    int32_t ties = 0;                                      /* (a candidate sits on bin B - 1 only as the end-of-spectrum emission, which is not in h / p) */
+    for (int32_t o = 0; o < n; o++) if (p > 0 && pk[o].l != B - 1 && e[pk[o].l] == h) ties++;
+    if (n > 0 && pk[n - 1].l == B - 1 && e[B - 1] > h) ARM(S, hdr_eos_largest);
+    if (ties > 1) ARM(S, hdr_tie);
+    if (n == 16) ARM(S, cand_16);
+    if (n == 17) ARM(S, cand_17);
+    if (n == 64) ARM(S, cand_64);
+    S->reset0_in_frame = 0;
+    wsa_or_gate_frame rec = {0, (int32_t)t, 0, v, v};
     if (S->c_started < 0) {                                                    /* @B26527 */
         double r = d > h ? h * (n - 1) / (d - h) : 0;
-        if (n > 0 && p > 7 && p < S->max_voiced_bin && n > 4 && r > 4) reset_segment(S, 0);
+        const int c_n = n > 4, c_lo = p > 7, c_hi = p < S->max_voiced_bin, c_r = r > 4;
+        if (n > 0 && c_lo && c_hi && c_n && c_r) {
+            ARM(S, start_pass);
+            if (n == 5) ARM(S, start_n5);
+            if (p == 8) ARM(S, start_p8);
+            if (p == mvb - 1) ARM(S, start_pmax_m1);
+            if (h * (n - 1) - 4 * (d - h) == 1) ARM(S, start_r_above);
+            if (n16 <= 4) ARM(S, late_n4);
+        } else {
+            if (n == 4 && c_lo && c_hi && d > h && h * (n - 1) > 4 * (d - h)) ARM(S, start_n4);
+            if (p == 7 && c_n && c_r) ARM(S, start_p7);
+            if (p == mvb && c_n && c_r) ARM(S, start_pmax);
+            if (c_n && c_lo && c_hi && d > h && h * (n - 1) == 4 * (d - h)) ARM(S, start_r_equal);
+        }
+        if (n > 0 && p > 7 && p < S->max_voiced_bin && n > 4 && r > 4) { reset_segment(S, 0); S->span_begin = (int32_t)S->cur_frame - 1; }
         else S->no_fm++;
     }
     int32_t do_reset = 0;
     if (S->c_started >= 0) {                                                   /* @B26646 */
+        const int unv = n == 0 || p < 7 || p >= S->max_voiced_bin || (n > 3 && d / (g - d) < .1);
+        if (n == 0) ARM(S, voiced_n0);
+        else if (p == 0) ARM(S, voiced_p0);
+        else if (p == 6) ARM(S, voiced_p6);
+        else if (p == mvb) ARM(S, voiced_pmax);
+        else if (p >= 7 && p < mvb) {
+            if (p == 7 && !unv) ARM(S, voiced_p7);
+            if (p == mvb - 1 && !unv) ARM(S, voiced_pmax_m1);
+            if (n > 3 && 11 * d == g) ARM(S, d_equal);
+            if (n > 3 && 11 * d == g - 1) ARM(S, d_below);
+            if (n == 3 && 11 * d < g) ARM(S, d_n3);
+            if (n > 3 && g == d) ARM(S, d_g_equals_d);
+            if (11 * h >= g) ARM(S, mx_covers);
+            else if (n <= 3) ARM(S, mx_short_n3);
+            else if (g <= 11 * d) ARM(S, mx_short_d_covers);
+            if (n > 3 && n16 <= 3 && unv) ARM(S, late_n3);
+            if (n > 3 && n > n16 && 11 * h < g && 11 * d16 < g && g <= 11 * d) ARM(S, late_d);
+        }
+        if (unv) S->arms[ARM_unvoiced_at_0 + S->c_started]++;          /* c_started is 0, 1 or 2 here */
+        else if (S->c_started < 2) S->arms[ARM_voiced_at_0 + S->c_started]++;
+        S->voiced_now = !unv;
         if (n == 0 || p < 7 || p >= S->max_voiced_bin || (n > 3 && d / (g - d) < .1)) {
             S->no_fm++;
             if (S->c_started < 2) S->c_started--;
-            else if (S->no_fm >= S->breaker) { finalize(S, S->c_ci + 1); do_reset = 1; }
-            else if (S->cfg.auto_noise_gate) noise_gate(S, h);
+            else if (S->no_fm >= S->breaker) {
+                if (S->breaker == trunc(S->breaker)) ARM(S, pause_int); else ARM(S, pause_frac);
+                finalize(S, S->c_ci + 1); do_reset = 1;
+            }
+            else if (S->cfg.auto_noise_gate) { noise_gate(S, h); if (S->reset0_in_frame) S->span_begin = (int32_t)S->cur_frame; }
         } else {
-            if (S->cfg.auto_noise_gate) noise_gate(S, h);
+            if (S->cfg.auto_noise_gate) { const int32_t before = S->reset0_in_frame; noise_gate(S, h); if (S->reset0_in_frame && !before) S->span_begin = (int32_t)S->cur_frame - 1; }
+            rec.called = 1; rec.stale = S->reset0_in_frame; rec.fl = S->floor_;
             accumulate_fm(S, e, pk, n, t, g, S->floor_);
             if (S->c_started < 2) S->c_started++; else S->no_fm = 0;
         }
     }
+    if (!rec.called) rec.fl = S->floor_;
+    VPUSH(S->gframes, rec);
     if (S->trace_on) {
         double row[10] = {S->c_ci, (double)S->c_started, S->no_fm, S->ctx_max, S->floor_, (double)n,
                           (double)p, h, d, g};
@@ -455,15 +562,40 @@ void wsa_or_seg_push(wsa_or_seg *S, const uint32_t *e) {
     }
     S->c_ci++;
     /* the reference resets in the Promise .then microtask, i.e. after the frame completes (quirk 8) */
-    if (do_reset) reset_segment(S, -1);
+    if (do_reset) { reset_segment(S, -1); S->span_begin = (int32_t)S->cur_frame; }
     free(pk);
 }
 
 /* segment_truncate N() @B30757 -> D() with play_end -> O(c_ci) -> L(1) */
 void wsa_or_seg_finish(wsa_or_seg *S) {
+    const int32_t before = S->segs.n;
+    if (S->c_started < 2 && S->c_started >= 0 && S->c_ci - S->no_fm > S->min_frames) ARM(S, fin_end_unstarted);
     finalize(S, S->c_ci);
-    reset_segment(S, 1);
+    if (S->segs.n > before) ARM(S, fin_truncate_open);
+    reset_segment(S, 1); S->span_begin = (int32_t)S->cur_frame;
 }
+
+/* What csrc/gate.hip does when a stream's open span would outgrow its ring (DESIGN.md "streams"; our own rule, not the reference's): the body of
+ * segment_truncate, O(c_ci) then L(1), after which pushes go on */
+void wsa_or_seg_cut(wsa_or_seg *S) {
+    ARM(S, ring_cut);
+    finalize(S, S->c_ci);
+    reset_segment(S, 1); S->span_begin = (int32_t)S->cur_frame;
+}
+
+int32_t wsa_or_gate_n_frames(const wsa_or_seg *s) { return s->gframes.n; }
+const wsa_or_gate_frame *wsa_or_gate_frames(const wsa_or_seg *s) { return s->gframes.p; }
+void wsa_or_gate_segment(const wsa_or_seg *s, int32_t i, int32_t out3[3], double out2[2]) {
+    const segment_t *g = &s->segs.p[i];
+    out3[0] = g->fbegin; out3[1] = g->fend; out3[2] = g->cci; out2[0] = g->g_ctx_max; out2[1] = g->g_floor;
+}
+void wsa_or_gate_state(const wsa_or_seg *s, double out[12]) {
+    out[0] = s->cur_frame; out[1] = s->no_fm; out[2] = s->c_ci; out[3] = s->c_started; out[4] = s->ctx_max; out[5] = s->floor_;
+    out[6] = s->last_max; out[7] = s->last_floor; out[8] = s->w; out[9] = s->T; out[10] = s->k; out[11] = s->span_begin;
+}
+int32_t wsa_or_gate_n_arms(void) { return ARM_COUNT; }
+const char *wsa_or_gate_arm_name(int32_t i) { return i >= 0 && i < ARM_COUNT ? arm_names[i] : NULL; }
+int64_t wsa_or_gate_arm_count(const wsa_or_seg *s, int32_t i) { return i >= 0 && i < ARM_COUNT ? s->arms[i] : -1; }
 
 int32_t wsa_or_n_segments(const wsa_or_seg *s) { return s->segs.n; }
 void wsa_or_segment(const wsa_or_seg *s, int32_t i, int32_t out[5]) {

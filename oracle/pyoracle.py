@@ -19,6 +19,10 @@ class Cfg(ctypes.Structure):
                 ("voiced_max_dB", ctypes.c_double), ("voiced_min_dB", ctypes.c_double)]
 
 
+class GateFrame(ctypes.Structure):
+    _fields_ = [("called", ctypes.c_int32), ("t", ctypes.c_int32), ("stale", ctypes.c_int32), ("v", ctypes.c_double), ("fl", ctypes.c_double)]
+
+
 class FeCfg(ctypes.Structure):
     _fields_ = [("fs", ctypes.c_double), ("spec_type", ctypes.c_int32), ("f_min", ctypes.c_double),
                 ("f_max", ctypes.c_double), ("n_fft_bins", ctypes.c_int32), ("n_mel_bins", ctypes.c_int32),
@@ -53,6 +57,18 @@ def lib():
     L.wsa_or_seg_new.argtypes = [ctypes.POINTER(Cfg)]
     L.wsa_or_seg_push.argtypes = [vp, vp]
     L.wsa_or_seg_finish.argtypes = [vp]
+    L.wsa_or_seg_cut.argtypes = [vp]
+    L.wsa_or_gate_n_frames.restype = i32
+    L.wsa_or_gate_n_frames.argtypes = [vp]
+    L.wsa_or_gate_frames.restype = ctypes.POINTER(GateFrame)
+    L.wsa_or_gate_frames.argtypes = [vp]
+    L.wsa_or_gate_segment.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(d)]
+    L.wsa_or_gate_state.argtypes = [vp, ctypes.POINTER(d)]
+    L.wsa_or_gate_n_arms.restype = i32
+    L.wsa_or_gate_arm_name.restype = ctypes.c_char_p
+    L.wsa_or_gate_arm_name.argtypes = [i32]
+    L.wsa_or_gate_arm_count.restype = ctypes.c_int64
+    L.wsa_or_gate_arm_count.argtypes = [vp, i32]
     L.wsa_or_enable_trace.argtypes = [vp, i32]
     L.wsa_or_seg_free.argtypes = [vp]
     for name in ("wsa_or_n_segments", "wsa_or_n_syllables", "wsa_or_trace_len"):
@@ -156,11 +172,38 @@ def default_cfg(level=5, bands=128, **kw):
     return Cfg(**c)
 
 
-def run_backend(spectra, cfg, trace=False):
+def gate_arm_names():
+    L = lib()
+    return [L.wsa_or_gate_arm_name(i).decode() for i in range(L.wsa_or_gate_n_arms())]
+
+
+def _gate_report(L, h):
+    """What the gate decided (wsa_oracle.h "what the gate decided"): per frame called / t / stale / v / fl, per finalized segment
+    [start, len, span begin, span end, c_ci, ctx_max, floor], the arm counters by name, the state as gate.hip's streams carry it."""
+    n = L.wsa_or_gate_n_frames(h)
+    fr = L.wsa_or_gate_frames(h)
+    out = dict(called=np.array([fr[i].called for i in range(n)], np.int32), t=np.array([fr[i].t for i in range(n)], np.int32),
+               stale=np.array([fr[i].stale for i in range(n)], np.int32), v=np.array([fr[i].v for i in range(n)], np.float64),
+               fl=np.array([fr[i].fl for i in range(n)], np.float64), segments=[])
+    info, o3, o2 = (ctypes.c_int32 * 5)(), (ctypes.c_int32 * 3)(), (ctypes.c_double * 2)()
+    for i in range(L.wsa_or_n_segments(h)):
+        L.wsa_or_segment(h, i, info)
+        L.wsa_or_gate_segment(h, i, o3, o2)
+        out["segments"].append([info[0], info[1], o3[0], o3[1], o3[2], o2[0], o2[1]])
+    out["arms"] = {L.wsa_or_gate_arm_name(i).decode(): int(L.wsa_or_gate_arm_count(h, i)) for i in range(L.wsa_or_gate_n_arms())}
+    st = (ctypes.c_double * 12)()
+    L.wsa_or_gate_state(h, st)
+    out["state"] = list(st)
+    return out
+
+
+def run_backend(spectra, cfg, trace=False, gate=False, cuts=()):
     """spectra: (frames, bands) uint32.  Returns dict mirroring tests/golden/gen/ref_driver.js output:
     segments_ci [[start,len]], syllables_ci [[[start,len]...]] (levels 10/13), features
     (level 5: [53] per segment; level 13: [[53]...] per segment), formants (level>=4); load [[max peaks, max live]] per
-    segment (wsa_or_segment_load: what the device tracker's table limits are compared with)."""
+    segment (wsa_or_segment_load: what the device tracker's table limits are compared with).
+    gate: also out["gate"], what the gate decided and which arms it took (_gate_report).  cuts: frames f after which (once frame f is pushed)
+    wsa_or_seg_cut is called, as csrc/gate.hip's stream kernel cuts a span at its ring."""
     L = lib()
     spectra = np.ascontiguousarray(spectra, dtype=np.uint32)
     frames, bands = spectra.shape
@@ -175,8 +218,11 @@ def run_backend(spectra, cfg, trace=False):
     h = L.wsa_or_seg_new(ctypes.byref(cfg))
     try:
         L.wsa_or_enable_trace(h, int(trace))
+        cuts = set(int(c) for c in cuts)
         for f in range(frames):
             L.wsa_or_seg_push(h, spectra[f].ctypes.data)
+            if f in cuts:
+                L.wsa_or_seg_cut(h)
         L.wsa_or_seg_finish(h)
         out = {"segments_ci": [], "syllables_ci": [], "features": [], "formants": [], "flags": [], "sums": [], "load": []}
         info = (ctypes.c_int32 * 5)()
@@ -219,6 +265,8 @@ def run_backend(spectra, cfg, trace=False):
             cfg = Cfg(**{k: getattr(cfg, k) for k, _ in Cfg._fields_})
             cfg.level = want_level
         out["callbacks"] = callbacks(out, cfg)
+        if gate:
+            out["gate"] = _gate_report(L, h)
         if trace:
             n = L.wsa_or_trace_len(h)
             out["trace"] = np.ctypeslib.as_array(L.wsa_or_trace(h), shape=(n, 10)).copy() if n else np.zeros((0, 10))

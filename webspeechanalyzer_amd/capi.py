@@ -1192,3 +1192,61 @@ class Streams:
             self.close()
         except Exception:
             pass
+
+
+GATE_INT_RUNS, GATE_INT_GENERAL, GATE_F64, GATE_STREAM = 0, 1, 2, 3
+GATE_STATE_WORDS = 16
+GATE_SENTINEL = -2
+
+
+def debug_gate(variant, clips, settings, blocks=0, F=0, max_span=0, step_nfr=None, step_ctl=None, device=0):
+    """Test access to the gate on its own (csrc/debug.hip wsa_debug_gate; not part of include/wsa.h): clips = [frames_c, bands] u32 arrays, settings =
+    the six gate settings by name, variant = GATE_*.  Streams (GATE_STREAM): step_nfr / step_ctl [n_steps, n_clips].  Returns the gate's outputs as the
+    kernel left them: fr_info / fr_v / fr_fl (fr_span) per clip, seg_i [.., seg_cap, 8], seg_d [.., seg_cap, 2], seg_count, flags, counter0, seg_cap (ring,
+    state per step); frames no step fed keep GATE_SENTINEL.  Raises WsaError on a refusal."""
+    L = lib()
+    vp, i32, u32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32
+    L.wsa_debug_gate.argtypes = [i32, i32, vp, vp, u32, i32, vp, u32, u32, u32, u32, vp, vp, vp] + [vp] * 9
+    L.wsa_debug_gate.restype = ctypes.c_int
+    n = len(clips)
+    bands = int(clips[0].shape[1])
+    nfr = np.array([len(c) for c in clips], np.uint32)
+    total = int(nfr.sum())
+    spec = np.ascontiguousarray(np.concatenate([np.asarray(c, np.uint32).reshape(-1, bands) for c in clips], axis=0)) if total else np.zeros((1, bands), np.uint32)
+    s6 = np.array([settings["window_step"], settings["pause_length"], settings["min_seg_length"], float(bool(settings["auto_noise_gate"])),
+                   settings["voiced_max_dB"], settings["voiced_min_dB"]], np.float64)
+    streams = variant == GATE_STREAM
+    n_steps = 0
+    if streams:
+        step_nfr = np.ascontiguousarray(step_nfr, np.uint32)
+        step_ctl = np.ascontiguousarray(step_ctl, np.uint32)
+        n_steps = step_nfr.shape[0]
+        assert step_nfr.shape == (n_steps, n) and step_ctl.shape == (n_steps, n)
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    caps = np.zeros(2, np.int32)
+
+    def call(*outs):
+        rc = L.wsa_debug_gate(device, variant, ptr(spec), ptr(nfr), n, bands, ptr(s6), blocks, F, max_span, n_steps, ptr(step_nfr) if streams else None,
+                              ptr(step_ctl) if streams else None, ptr(caps), *outs)
+        if rc != 0:
+            raise WsaError(f"wsa_debug_gate: error {rc}")
+    call(*([None] * 9))
+    seg_cap, ring = int(caps[0]), int(caps[1])
+    lead = (n_steps, n) if streams else (n,)
+    fr_info = np.full(max(total, 1), GATE_SENTINEL, np.int32)
+    fr_span = np.full(max(total, 1), GATE_SENTINEL, np.int32)
+    fr_v = np.full(max(total, 1), float(GATE_SENTINEL))
+    fr_fl = np.full(max(total, 1), float(GATE_SENTINEL))
+    seg_i = np.full(lead + (seg_cap, 8), GATE_SENTINEL, np.int32)
+    seg_d = np.full(lead + (seg_cap, 2), float(GATE_SENTINEL))
+    seg_count = np.full(lead, 0xffffffff, np.uint32)
+    flags2 = np.zeros(2, np.uint32)
+    state = np.zeros((max(n_steps, 1), n, GATE_STATE_WORDS))
+    call(ptr(fr_info), ptr(fr_v), ptr(fr_fl), ptr(fr_span), ptr(seg_i), ptr(seg_d), ptr(seg_count), ptr(flags2), ptr(state))
+    off = np.concatenate([[0], np.cumsum(nfr)]).astype(np.int64)
+    cut = lambda a: [a[off[i]:off[i + 1]] for i in range(n)]
+    out = dict(fr_info=cut(fr_info), fr_v=cut(fr_v), fr_fl=cut(fr_fl), seg_i=seg_i, seg_d=seg_d, seg_count=seg_count, flags=int(flags2[0]), counter0=int(flags2[1]),
+               seg_cap=seg_cap)
+    if streams:
+        out.update(fr_span=cut(fr_span), state=state, ring=ring)
+    return out

@@ -202,7 +202,7 @@ static wsa_status batch_create_impl(wsa_ctx* ctx, uint32_t n_clips, const uint32
     BackEnd& B = b->be;
     B.n = n_clips;
     B.set_caps(D, P.bands, b->max_frames);
-    B.seg_cap = (int)b->max_frames / D.period + 2;
+    B.seg_cap = batch_seg_cap(b->max_frames, D);
     B.row_cap = D.syllable_rows ? (int)b->max_frames / 2 + 2 : B.seg_cap;
     // two spans per wave (two work spaces each) wherever the paired tracker variant applies: its bit map of peak bins covers 128 bands,
     // level 3 and the per-frame trace keep the one-span kernel (WSA_NO_PAIR=1: test hook)

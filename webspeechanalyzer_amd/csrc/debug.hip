@@ -1,5 +1,5 @@
 // debug.hip — test entries of libwsa that are NOT part of include/wsa.h: unit access to device-side pieces that the public
-// entry points only exercise through their consequences (tests/test_gpu_units.py, tests/test_gpu_coeffs.py, tests/test_gpu_utterance.py).
+// entry points only exercise through their consequences (tests/test_gpu_units.py, tests/test_gpu_coeffs.py, tests/test_gpu_utterance.py, tests/test_gpu_gate.py).
 #include <cstring>
 #include <vector>
 #include "host_plan.hpp"
@@ -333,6 +333,143 @@ extern "C" int wsa_debug_coeffs(int32_t device, const float* formants, const flo
         q.ws = dws; q.total_frames = (uint32_t)total; q.ring_mask = ring_mask; q.scratch_stride = scratch_stride;
         wsa::launch_coeffs(q, rows_cap, nullptr);
         ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dfeat, h.size() * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    return ok ? WSA_OK : WSA_ERR_HIP;
+}
+
+// K2a (csrc/gate.hip) on its own: host spectra through the peak scan and ONE gate variant, the gate's outputs copied back as they are.
+//   variant 0: the integer kernel with its runs (gate_kernel_auto<false>)      1: the integer kernel, every frame through the general path (<true>, WSA_DBG 4096)
+//           2: the f64 lane-per-candidate kernel (gate_kernel_t<false>; what a fixed gate uses, and WSA_DBG 2048)      3: the stream step kernel (gate_kernel_t<true>)
+// spec = the clips' frames one after the other ([sum n_frames][bands] u32), settings6 = {window_step, pause_length, min_seg_length, auto_noise_gate, voiced_max_dB,
+// voiced_min_dB}; blocks = workgroups of the gate launch (0: one per clip; fewer: a workgroup walks several clips).
+// caps_io = {seg_cap, ring}: called with seg_cap 0 the entry only fills in both (seg_cap as the drivers size a clip's / a step's segment table from host_plan.hpp's
+// period, ring as a stream set of F frames per step and max_span sizes it) and runs nothing; a run must be handed the same numbers back.
+// Batch (variants 0 .. 2) out: fr_info / fr_v / fr_fl [sum n_frames], seg_i [n_clips][seg_cap][8], seg_d [n_clips][seg_cap][2], seg_count [n_clips], flags2 = {the overflow
+// flag word, counters[0]}; fr_span and state are not touched.
+// Streams (variant 3): clip c is stream c; step k feeds it its next step_nfr[k][c] <= F frames under step_ctl[k][c] (bit 0 START: launch state first, bit 1 STOP:
+// segment_truncate behind the frames), launch_stream_prepare + the peak scan + launch_gate_stream once per step.  Out: the per-frame arrays (fr_span too) at the frames'
+// place in their clip, read from their ring slot right behind their step; seg_i [n_steps][n_clips][seg_cap][8], seg_d, seg_count [n_steps][n_clips] and state
+// [n_steps][n_clips][GATE_STATE] per step; flags2 = {OR of the flag words, largest counters[0]}.  Frames never fed keep what the caller put there.
+// Refused, nothing run: the integer kernel under a fixed gate, more than CAND_CAP candidates in a frame (reported after the scan, the gate not run), a step that
+// feeds more than F frames or more than the clip has left, a ring the caller did not get from here.
+extern "C" int wsa_debug_gate(int32_t device, int32_t variant, const uint32_t* spec, const uint32_t* n_frames, uint32_t n_clips, int32_t bands, const double* settings6,
+                              uint32_t blocks, uint32_t F, uint32_t max_span, uint32_t n_steps, const uint32_t* step_nfr, const uint32_t* step_ctl, int32_t* caps_io,
+                              int32_t* fr_info, double* fr_v, double* fr_fl, int32_t* fr_span, int32_t* seg_i, double* seg_d, uint32_t* seg_count, uint32_t* flags2, double* state) {
+    using namespace wsa;
+    if (!n_frames || !settings6 || !caps_io || variant < 0 || variant > 3 || n_clips < 1 || n_clips > 4096 || bands < 4 || bands > 256) return WSA_ERR_INVALID;
+    const bool streams = variant == 3;
+    wsa_config c{};
+    c.output_level = 5; c.N_mel_bins = bands; c.window_width = c.window_step = settings6[0]; c.pause_length = settings6[1]; c.min_seg_length = settings6[2];
+    c.auto_noise_gate = settings6[3] != 0 ? 1 : 0; c.voiced_max_dB = settings6[4]; c.voiced_min_dB = settings6[5];
+    if (!(c.window_step > 0) || !(c.pause_length >= 0) || !(c.min_seg_length >= 0)) return WSA_ERR_INVALID;
+    if (variant < 2 && !c.auto_noise_gate) return WSA_ERR_INVALID;                     // the integer kernel's state is integers only under the auto gate
+    uint64_t total = 0; uint32_t max_frames = 0;
+    std::vector<uint32_t> foff((size_t)n_clips + 1, 0);
+    for (uint32_t i = 0; i < n_clips; i++) {
+        if (n_frames[i] > (1u << 20)) return WSA_ERR_INVALID;
+        total += n_frames[i]; foff[i + 1] = (uint32_t)total; if (n_frames[i] > max_frames) max_frames = n_frames[i];
+    }
+    if (total > (1u << 22) || (total && !spec)) return WSA_ERR_INVALID;
+    if (streams && (F < 1 || F > 4096 || n_steps < 1 || n_steps > (1u << 20) || !step_nfr || !step_ctl || max_span > (1u << 16))) return WSA_ERR_INVALID;
+    const Derived D(c, bands);
+    const int seg_cap = streams ? stream_seg_cap(F, D) : batch_seg_cap(max_frames, D);
+    const uint32_t ring = streams ? stream_ring_frames(F, max_span) : 0;
+    if (caps_io[0] == 0) { caps_io[0] = seg_cap; caps_io[1] = (int32_t)ring; return WSA_OK; }
+    if (caps_io[0] != seg_cap || caps_io[1] != (int32_t)ring) return WSA_ERR_INVALID;
+    if (!fr_info || !fr_v || !fr_fl || !seg_i || !seg_d || !seg_count || !flags2 || (streams && (!fr_span || !state))) return WSA_ERR_INVALID;
+    if (streams) {                                                                       // the schedule stays inside the clips and the step buffer
+        std::vector<uint64_t> fed(n_clips, 0);
+        for (uint32_t k = 0; k < n_steps; k++)
+            for (uint32_t i = 0; i < n_clips; i++) {
+                const uint32_t nf = step_nfr[(size_t)k * n_clips + i];
+                if (nf > F || (step_ctl[(size_t)k * n_clips + i] & ~3u)) return WSA_ERR_INVALID;
+                fed[i] += nf;
+                if (fed[i] > n_frames[i]) return WSA_ERR_INVALID;
+            }
+    }
+    if (hipSetDevice(device) != hipSuccess) return WSA_ERR_NO_DEVICE;
+    const size_t slots = streams ? (size_t)n_clips * ring : (size_t)total;              // frame records and per-frame outputs: one per frame, or one per ring slot
+    const size_t spec_rows = streams ? (size_t)n_clips * F : (size_t)total;
+    const size_t segs = (size_t)n_clips * seg_cap;
+    DevArena A;
+    uint32_t *d_spec = nullptr, *d_nfr = nullptr, *d_foff = nullptr, *d_seg_count = nullptr, *d_clip_rows = nullptr, *d_counters = nullptr, *d_ctl = nullptr;
+    RecPtrs rec; int32_t *d_info = nullptr, *d_span = nullptr, *d_seg_i = nullptr, *d_carry = nullptr; double *d_v = nullptr, *d_fl = nullptr, *d_seg_d = nullptr, *d_state = nullptr;
+    bool ok = A.alloc(&d_spec, spec_rows * bands + 4, true) && A.alloc(&d_nfr, n_clips) && A.alloc(&d_foff, (size_t)n_clips + 1) && A.alloc(&rec.hdr, slots, true)
+           && A.alloc(&rec.amp, slots * CAND_CAP, true) && A.alloc(&rec.ent, slots * CAND_CAP, true) && A.alloc(&d_info, slots, true) && A.alloc(&d_v, slots, true)
+           && A.alloc(&d_fl, slots, true) && A.alloc(&d_seg_i, segs * 8, true) && A.alloc(&d_seg_d, segs * 2, true) && A.alloc(&d_seg_count, n_clips, true)
+           && A.alloc(&d_clip_rows, n_clips, true) && A.alloc(&d_counters, 16, true)
+           && hipMemcpy(d_foff, foff.data(), foff.size() * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && streams) ok = A.alloc(&d_span, slots, true) && A.alloc(&d_state, (size_t)n_clips * GATE_STATE, true) && A.alloc(&d_carry, (size_t)n_clips * CARRY_WORDS, true) && A.alloc(&d_ctl, n_clips, true);
+    if (!ok) return WSA_ERR_HIP;
+    PkParams pk; pk.spec = d_spec; pk.rec = rec; pk.bands = bands; pk.flags = d_counters + 8;
+    GateParams g;
+    g.rec = rec; g.n_frames = d_nfr; g.frame_off = d_foff; g.n_clips = n_clips; g.level = D.klevel; g.max_voiced_bin = D.max_voiced_bin; g.breaker = D.breaker;
+    g.min_frames = D.min_frames; g.auto_gate = D.auto_gate; g.ctx_max0 = D.ctx_max0; g.floor0 = D.floor0; g.fr_info = d_info; g.fr_v = d_v; g.fr_fl = d_fl;
+    g.seg_i = d_seg_i; g.seg_d = d_seg_d; g.seg_cap = seg_cap; g.seg_count = d_seg_count; g.clip_rows = d_clip_rows; g.counters = d_counters + 4; g.shared = d_counters;
+    g.dbg = variant == 1 ? DBG_GATE_GENERAL : (variant == 2 ? DBG_GATE_F64 : 0);
+    uint32_t cnt[16];
+    if (!streams) {
+        ok = hipMemcpy(d_nfr, n_frames, (size_t)n_clips * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess
+          && (total == 0 || hipMemcpy(d_spec, spec, (size_t)total * bands * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess);
+        if (ok && total) {
+            pk.total_frames = (uint32_t)total;
+            launch_peaks(pk, nullptr);
+            ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(cnt, d_counters, sizeof(cnt), hipMemcpyDeviceToHost) == hipSuccess;
+            if (ok && (cnt[8] & 1u)) return WSA_ERR_INVALID;                            // a frame with more than CAND_CAP candidates: its table is cut short
+        }
+        if (ok) {
+            launch_gate_blocks(g, blocks, nullptr);
+            ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(cnt, d_counters, sizeof(cnt), hipMemcpyDeviceToHost) == hipSuccess
+              && (total == 0 || (hipMemcpy(fr_info, d_info, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess
+                                 && hipMemcpy(fr_v, d_v, (size_t)total * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess
+                                 && hipMemcpy(fr_fl, d_fl, (size_t)total * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess))
+              && hipMemcpy(seg_i, d_seg_i, segs * 8 * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess
+              && hipMemcpy(seg_d, d_seg_d, segs * 2 * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess
+              && hipMemcpy(seg_count, d_seg_count, (size_t)n_clips * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess;
+            if (ok) { flags2[0] = cnt[1]; flags2[1] = cnt[4]; }
+        }
+        return ok ? WSA_OK : WSA_ERR_HIP;
+    }
+    // ---- streams: one prepare + scan + gate per step
+    pk.stream_state = d_state; pk.n_frames = d_nfr; pk.step_frames = F; pk.ring = ring; pk.total_frames = n_clips * F;
+    g.state = d_state; g.ctl = d_ctl; g.ring = ring; g.step_frames = F; g.fr_span = d_span;
+    std::vector<uint32_t> hspec(spec_rows * bands), fed(n_clips, 0);
+    std::vector<int32_t> h_info(slots), h_span(slots); std::vector<double> h_v(slots), h_fl(slots);
+    flags2[0] = 0; flags2[1] = 0;
+    for (uint32_t k = 0; k < n_steps && ok; k++) {
+        const uint32_t* nf = step_nfr + (size_t)k * n_clips;
+        for (uint32_t i = 0; i < n_clips; i++)
+            if (nf[i]) memcpy(&hspec[(size_t)i * F * bands], spec + ((size_t)foff[i] + fed[i]) * bands, (size_t)nf[i] * bands * sizeof(uint32_t));
+        const uint32_t zero16[16] = {0};
+        ok = hipMemcpy(d_spec, hspec.data(), hspec.size() * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess
+          && hipMemcpy(d_nfr, nf, (size_t)n_clips * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess
+          && hipMemcpy(d_ctl, step_ctl + (size_t)k * n_clips, (size_t)n_clips * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess
+          && hipMemcpy(d_counters, zero16, sizeof(zero16), hipMemcpyHostToDevice) == hipSuccess;
+        if (!ok) break;
+        launch_stream_prepare(d_state, d_carry, nullptr, d_ctl, n_clips, D.ctx_max0, D.floor0, nullptr);
+        launch_peaks(pk, nullptr);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(cnt, d_counters, sizeof(cnt), hipMemcpyDeviceToHost) == hipSuccess;
+        if (ok && (cnt[8] & 1u)) return WSA_ERR_INVALID;
+        if (!ok) break;
+        launch_gate_stream_blocks(g, blocks, nullptr);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(cnt, d_counters, sizeof(cnt), hipMemcpyDeviceToHost) == hipSuccess
+          && hipMemcpy(h_info.data(), d_info, slots * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(h_span.data(), d_span, slots * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess
+          && hipMemcpy(h_v.data(), d_v, slots * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(h_fl.data(), d_fl, slots * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess
+          && hipMemcpy(seg_i + (size_t)k * segs * 8, d_seg_i, segs * 8 * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess
+          && hipMemcpy(seg_d + (size_t)k * segs * 2, d_seg_d, segs * 2 * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess
+          && hipMemcpy(seg_count + (size_t)k * n_clips, d_seg_count, (size_t)n_clips * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess
+          && hipMemcpy(state + (size_t)k * n_clips * GATE_STATE, d_state, (size_t)n_clips * GATE_STATE * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+        if (!ok) break;
+        flags2[0] |= cnt[1]; if (cnt[4] > flags2[1]) flags2[1] = cnt[4];
+        for (uint32_t i = 0; i < n_clips; i++) {
+            // the stream's frame count after this step (state word 0) minus the step's frames = the absolute number of the step's first frame
+            const uint32_t seen = (uint32_t)state[((size_t)k * n_clips + i) * GATE_STATE] - nf[i];
+            for (uint32_t j = 0; j < nf[i]; j++) {
+                const size_t slot = (size_t)i * ring + ((seen + j) & (ring - 1)), dst = (size_t)foff[i] + fed[i] + j;
+                fr_info[dst] = h_info[slot]; fr_span[dst] = h_span[slot]; fr_v[dst] = h_v[slot]; fr_fl[dst] = h_fl[slot];
+            }
+            fed[i] += nf[i];
+        }
     }
     return ok ? WSA_OK : WSA_ERR_HIP;
 }

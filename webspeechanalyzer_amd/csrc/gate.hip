@@ -538,24 +538,28 @@ __global__ void stream_prepare_kernel(double* state, int32_t* carry, int32_t* tr
     }
 }
 
-void launch_gate(const GateParams& p, hipStream_t s) {
+// blocks: workgroups of the launch, 0 = one per clip (what the drivers use); fewer make a workgroup walk several clips (tests: wsa_debug_gate)
+void launch_gate_blocks(const GateParams& p, uint32_t blocks, hipStream_t s) {
     if (p.n_clips == 0) return;
+    const dim3 grid(blocks ? min(blocks, p.n_clips) : p.n_clips);
     // WSA_DBG bit 2048: the general (f64, lane = candidate) kernel also under the auto gate
     if (p.auto_gate && p.strided && !(p.dbg & DBG_GATE_F64)) {
-        if ((p.trace && !(p.dbg & DBG_CYCLES)) || (p.dbg & DBG_GATE_GENERAL)) hipLaunchKernelGGL(gate_kernel_auto<true>, dim3(p.n_clips), dim3(64), 0, s, p);
-        else hipLaunchKernelGGL(gate_kernel_auto<false>, dim3(p.n_clips), dim3(64), 0, s, p);
+        if ((p.trace && !(p.dbg & DBG_CYCLES)) || (p.dbg & DBG_GATE_GENERAL)) hipLaunchKernelGGL(gate_kernel_auto<true>, grid, dim3(64), 0, s, p);
+        else hipLaunchKernelGGL(gate_kernel_auto<false>, grid, dim3(64), 0, s, p);
     }
-    else hipLaunchKernelGGL(gate_kernel_t<false>, dim3(p.n_clips), dim3(64), 0, s, p);
+    else hipLaunchKernelGGL(gate_kernel_t<false>, grid, dim3(64), 0, s, p);
 }
+void launch_gate(const GateParams& p, hipStream_t s) { launch_gate_blocks(p, 0, s); }
 
 void launch_stream_prepare(double* state, int32_t* carry, int32_t* tr_state, const uint32_t* ctl, uint32_t n, double ctx_max0, double floor0, hipStream_t s) {
     if (n == 0) return;
     hipLaunchKernelGGL(stream_prepare_kernel, dim3((n + 255) / 256), dim3(256), 0, s, state, carry, tr_state, ctl, n, ctx_max0, floor0);
 }
 
-void launch_gate_stream(const GateParams& p, hipStream_t s) {
+void launch_gate_stream_blocks(const GateParams& p, uint32_t blocks, hipStream_t s) {
     if (p.n_clips == 0) return;
-    hipLaunchKernelGGL(gate_kernel_t<true>, dim3(p.n_clips), dim3(64), 0, s, p);
+    hipLaunchKernelGGL(gate_kernel_t<true>, dim3(blocks ? min(blocks, p.n_clips) : p.n_clips), dim3(64), 0, s, p);
 }
+void launch_gate_stream(const GateParams& p, hipStream_t s) { launch_gate_stream_blocks(p, 0, s); }
 
 }  // namespace wsa

@@ -115,6 +115,17 @@ struct Derived {
     }
 };
 
+// capacities that follow from `period` (DESIGN.md "capacities"): segments a clip of max_frames frames can finalize (+ the one segment_truncate adds, + 1),
+// segments one step of F frames can close (+ the ones STOP and a ring cut add), and a stream's ring: max_span frames of an open span plus one more step
+inline int batch_seg_cap(uint32_t max_frames, const Derived& D) { return (int)max_frames / D.period + 2; }
+inline int stream_seg_cap(uint32_t F, const Derived& D) { return (int)F / D.period + 3; }
+inline uint32_t stream_ring_frames(uint32_t F, uint32_t max_span_frames) {
+    uint32_t want = max_span_frames ? max_span_frames : 1024u;
+    if (want < 2 * F + 64) want = 2 * F + 64;
+    uint32_t ring = 64; while (ring < want + F) ring <<= 1;
+    return ring;
+}
+
 // ---- the back end's buffers, embedded by wsa_batch (n = clips, frames = all frames of the batch) and wsa_stream (n = streams, frames = n rings),
 // and the part of each kernel parameter block that follows from them.  A driver writes the rest: only the fields it means.
 struct BackEnd {

@@ -184,15 +184,13 @@ static wsa_status create_impl(wsa_ctx* ctx, uint32_t n_streams, const double* fs
         std::vector<uint32_t> none(n_streams, 0);
         if (!plan_resample_mixed(n_streams, none.data(), fs_in, fs, rs, err)) { delete b; return fail(ctx, WSA_ERR_INVALID, err); }
     }
-    uint32_t want = max_span_frames ? max_span_frames : 1024u;
-    if (want < 2 * b->F + 64) want = 2 * b->F + 64;
-    uint32_t ring = 64; while (ring < want + b->F) ring <<= 1;
+    const uint32_t ring = stream_ring_frames(b->F, max_span_frames);
     b->ring = ring;
     const Derived& D = b->D = Derived(c, P.bands);
     BackEnd& B = b->be;
     B.n = n_streams;
     B.set_caps(D, P.bands, ring);
-    B.seg_cap = (int)b->F / D.period + 3;
+    B.seg_cap = stream_seg_cap(b->F, D);
     B.row_cap = D.syllable_rows ? (int)(ring + b->F) / 2 + 4 : B.seg_cap;
     b->rows_cap = n_streams * (uint32_t)b->be.row_cap; b->segs_cap = n_streams * (uint32_t)b->be.seg_cap;
     b->d2h_rows = b->rows_cap < 1024u ? b->rows_cap : 1024u;

@@ -288,6 +288,8 @@ void launch_peaks(const PkParams& p, hipStream_t s);
 void launch_peaks_mode(const PkParams& p, int mode, hipStream_t s);   // 1: lane-per-frame kernel, 2: wave-per-frame kernel (tests)
 void launch_gate(const GateParams& p, hipStream_t s);
 void launch_gate_stream(const GateParams& p, hipStream_t s);
+void launch_gate_blocks(const GateParams& p, uint32_t blocks, hipStream_t s);          // blocks workgroups (0: one per clip) — a workgroup walks clips blockIdx.x, + gridDim.x, ...
+void launch_gate_stream_blocks(const GateParams& p, uint32_t blocks, hipStream_t s);
 void launch_stream_prepare(double* state, int32_t* carry, int32_t* tr_state, const uint32_t* ctl, uint32_t n, double ctx_max0, double floor0, hipStream_t s);
 void launch_tracker(const TrParams& p, int n_waves, bool full_table, bool pair, hipStream_t s);
 enum { SPAN_BUCKETS = 2048 };          // span lengths 0 .. 2047+ frames, bucket = SPAN_BUCKETS - 1 - min(frames, SPAN_BUCKETS - 1)
