@@ -749,6 +749,66 @@ wsa_status wsa_dbstats_copy_values(wsa_dbstats *db, uint32_t head, void *stream,
  * synchronises `stream`.  WSA_ERR_INVALID before the first prediction. */
 wsa_status wsa_dbstats_copy_probs(wsa_dbstats *db, void *stream, float *prob, uint32_t n_classes);
 
+/*
+ * ---- KNN classifier (additions within version 5: probe for wsa_knn_create).
+ * Stands in for the application's third learner, ref src/neuralmodel.js:729-837 (train_knn; its button handler is exported at
+ * src/index.js:165-168): ml5.KNNClassifier() over a labelled feature DB — addExample(features, label) for the first 80 % of the rows,
+ * classify(features, 10, ...) for the next 100.  In dist/ml5.min.js that is the tfjs knn-classifier (addExample, similarities,
+ * predictClass, calculateTopClass, normalizeVectorToUnitLength): specification KN-1 of DESIGN.md §3, kernels K9 (csrc/knn.hip).
+ * The classifier is deterministic, so every output is pinned: tests/golden/knn_expected.json holds what ml5 itself computes.
+ * A store belongs to the context it was created on; destroy it before that context.  One set of buffers: pass the SAME stream to every
+ * call on it (adds and classifications are ordered by that stream).
+ * The device never sees label strings.  Class indices are in ml5's class-id order, which the HOST works out (webspeechanalyzer_amd/knn.py
+ * label_order, js/knn.js labelOrder): ml5 gives a string label the index of its first appearance, and a number label is its own class id.
+ */
+#define WSA_KNN_MAX_K 64        /* one query's neighbour list fits the lanes of one wave */
+typedef struct wsa_knn wsa_knn;
+/* ref ml5.KNNClassifier() (neuralmodel.js:764).  width: the row width of an ML level (wsa_level_feature_count: 53, 264 or 23, anything
+ * else is refused); n_classes 1 .. WSA_MODEL_MAX_CLASSES; capacity: the most rows the store will ever hold (allocated here). */
+wsa_status wsa_knn_create(wsa_ctx *ctx, int32_t width, int32_t n_classes, uint32_t capacity, wsa_knn **out);
+void       wsa_knn_destroy(wsa_knn *knn);
+/* ref knnClassifier.addExample(features, label) (neuralmodel.js:777), n rows at once: d_feat device [n][width] f64 (dense), d_class device
+ * [n] i32 class indices.  Each row is rounded to f32 and divided by its Euclidean norm in f32; rows are kept in insertion order and never
+ * move; every row's grouped rank (rows of earlier classes + index within its own class) is recomputed.  Only enqueues; allocates nothing.
+ * Adding after classifying is legal, as in ml5.  WSA_ERR_CAPACITY when the rows do not fit.  A class index outside 0 .. n_classes - 1 is
+ * stored as class 0 and reported by the next wsa_knn_count. */
+wsa_status wsa_knn_add(wsa_knn *knn, const double *d_feat, const int32_t *d_class, uint32_t n, void *stream);
+/* ref knnClassifier.getCountByLabel(): synchronises `stream`; *n_rows = rows stored, class_rows [n_classes] = rows per class (either may be
+ * NULL).  WSA_ERR_INVALID naming the row if an add carried a class index out of range. */
+wsa_status wsa_knn_count(wsa_knn *knn, void *stream, uint32_t *n_rows, uint32_t *class_rows);
+/* ref knnClassifier.classify(features, k, cb) (neuralmodel.js:811) for n_rows dense device rows d_feat [n_rows][width] f64; k 1 ..
+ * WSA_KNN_MAX_K, k_eff = min(k, rows stored).  Any output may be NULL:
+ *   d_label [n_rows] i32      the first class, in index order, with the most votes (ml5 calculateTopClass)
+ *   d_conf  [n_rows][n_classes] f64   votes / k_eff
+ *   d_nbr   [n_rows][k] i32   insertion indices of the k_eff neighbours in selection order (similarity descending, then grouped rank
+ *                             ascending: ml5's stable top-k over its grouped train matrix); entries k_eff .. k - 1 are -1
+ *   d_sim   [n_rows][k] f32   their similarities; entries k_eff .. k - 1 are NaN
+ * Similarities are f32 with the device's own fixed summation order (a tolerance against tfjs, DESIGN.md "K9"); given them, everything
+ * else is exact.  A NaN similarity (a zero or non-finite row: not pinned against ml5) is lower than every number, ranks decide among
+ * NaNs, and it is written as NaN.  Only enqueues; allocates nothing.  WSA_ERR_INVALID: k out of range, an empty store. */
+wsa_status wsa_knn_classify_rows(const wsa_knn *knn, const double *d_feat, uint32_t n_rows, uint32_t k, int32_t *d_label, double *d_conf,
+                                 int32_t *d_nbr, float *d_sim, void *stream);
+/* rows per tile of K9 (tests place their edge cases by these): the store is streamed train_rows rows at a time, a workgroup keeps
+ * query_rows query rows resident */
+wsa_status wsa_knn_tile_info(int32_t *train_rows, int32_t *query_rows);
+/* The same over the rows of the batch's last run, the row count read on the device: levels 5 and 13 with a 53-wide store (the row table),
+ * level 11 with a 264-wide store (the utterance table, in its order), level 12 with a 23-wide store (slots 0 .. 22 of the row table; a
+ * row whose slot 23 marks a thrown uncmin gets label -1, NaN confidences and similarities and neighbours -1, as wsa_batch_classify gives it
+ * NaN).  Every other pairing is refused with a message that names both.  Equal bit for bit to wsa_knn_classify_rows over the same rows.
+ * After the first call on a batch (or the first with more classes or a larger k) nothing is allocated, so wsa_batch_run + wsa_batch_knn can
+ * be captured into a hipGraph; a captured graph keeps the store's row count of the capture.  The KNN tables of a batch are separate from
+ * its model calls' (wsa_batch_classify, _ensemble, _regress). */
+wsa_status wsa_batch_knn(wsa_batch *b, const wsa_knn *knn, uint32_t k, void *stream);
+/* device tables of the last wsa_batch_knn, laid out as wsa_knn_classify_rows' outputs; valid until the next wsa_batch_knn that allocates
+ * or wsa_batch_destroy */
+typedef struct {
+    uint32_t n_rows, n_classes, k, k_eff;
+    const int32_t *d_label; const double *d_conf; const int32_t *d_nbr; const float *d_sim;
+} wsa_knn_result;
+wsa_status wsa_batch_knn_result(wsa_batch *b, void *stream, wsa_knn_result *out);          /* synchronises `stream` */
+/* the same tables copied to host buffers of rows_cap rows (any pointer may be NULL to skip it); WSA_ERR_INVALID if rows_cap is too small */
+wsa_status wsa_batch_copy_knn(wsa_batch *b, void *stream, int32_t *label, double *conf, int32_t *nbr, float *sim, uint32_t rows_cap);
+
 #ifdef __cplusplus
 }
 #endif

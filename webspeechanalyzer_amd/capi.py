@@ -132,6 +132,11 @@ class _StreamEnsembleResult(ctypes.Structure):
                 ("cb_min_db", ctypes.c_void_p), ("cb_entropy", ctypes.c_void_p), ("stream_min_db", ctypes.c_void_p)]
 
 
+class _KnnResult(ctypes.Structure):
+    _fields_ = [("n_rows", ctypes.c_uint32), ("n_classes", ctypes.c_uint32), ("k", ctypes.c_uint32), ("k_eff", ctypes.c_uint32),
+                ("d_label", ctypes.c_void_p), ("d_conf", ctypes.c_void_p), ("d_nbr", ctypes.c_void_p), ("d_sim", ctypes.c_void_p)]
+
+
 # every symbol include/wsa.h declares (checked by tests/test_abi.py)
 ABI_VERSION = 5            # WSA_ABI_VERSION of include/wsa.h this binding's structures follow
 ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destroy", "wsa_last_error",
@@ -163,7 +168,10 @@ ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destr
                "wsa_dbstats_decide_rows", "wsa_dbstats_predict_values", "wsa_dbstats_table", "wsa_dbstats_copy_classes", "wsa_dbstats_copy_values",
                "wsa_dbstats_copy_probs",
                # additions within version 5 (probe for wsa_level_feature_count): models, training and DBs at the row widths of levels 11 and 12
-               "wsa_level_feature_count", "wsa_wide_dbstats_create"]
+               "wsa_level_feature_count", "wsa_wide_dbstats_create",
+               # additions within version 5 (probe for wsa_knn_create): the app's ml5 KNN classifier (K9, spec KN-1)
+               "wsa_knn_create", "wsa_knn_destroy", "wsa_knn_add", "wsa_knn_count", "wsa_knn_classify_rows", "wsa_knn_tile_info",
+               "wsa_batch_knn", "wsa_batch_knn_result", "wsa_batch_copy_knn"]
 
 _LIB = None
 _U32_RESULT = ("wsa_stream_input_capacity", "wsa_stream_paced_input", "wsa_stream_input_stride", "wsa_stream_step_frame_capacity", "wsa_stream_frames_bound")
@@ -301,12 +309,21 @@ def lib():
     L.wsa_dbstats_copy_classes.argtypes = [vp, u32, vp, vp]
     L.wsa_dbstats_copy_values.argtypes = [vp, u32, vp, vp]
     L.wsa_dbstats_copy_probs.argtypes = [vp, vp, vp, u32]
+    L.wsa_knn_create.argtypes = [vp, i32, i32, u32, ctypes.POINTER(vp)]
+    L.wsa_knn_destroy.argtypes = [vp]
+    L.wsa_knn_add.argtypes = [vp, vp, vp, u32, vp]
+    L.wsa_knn_count.argtypes = [vp, vp, ctypes.POINTER(u32), vp]
+    L.wsa_knn_classify_rows.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp, vp]
+    L.wsa_knn_tile_info.argtypes = [ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.wsa_batch_knn.argtypes = [vp, vp, u32, vp]
+    L.wsa_batch_knn_result.argtypes = [vp, vp, ctypes.POINTER(_KnnResult)]
+    L.wsa_batch_copy_knn.argtypes = [vp, vp, vp, vp, vp, vp, u32]
     for name in ABI_SYMBOLS:
         if name in _U32_RESULT or name in ("wsa_resample_ready", "wsa_level_feature_count"):
             continue
         if name not in ("wsa_abi_version", "wsa_last_error", "wsa_config_default", "wsa_destroy", "wsa_batch_destroy", "wsa_resample_length",
                         "wsa_stream_destroy", "wsa_stream_samples_per_step", "wsa_stream_host_input", "wsa_gather_destroy", "wsa_host_free",
-                        "wsa_model_destroy", "wsa_ensemble_destroy", "wsa_trainer_destroy", "wsa_dbstats_destroy"):
+                        "wsa_model_destroy", "wsa_ensemble_destroy", "wsa_trainer_destroy", "wsa_dbstats_destroy", "wsa_knn_destroy"):
             getattr(L, name).restype = ctypes.c_int
     _LIB = L
     return L
@@ -399,6 +416,10 @@ class Analyzer:
     def feature_db(self, features, durations, vocab_sizes=(), n_ord=0):
         """K8 on this context: a labelled feature DB on the device (see FeatureDBStats; webspeechanalyzer_amd.dbstats drives it)."""
         return FeatureDBStats(self, features, durations, vocab_sizes, n_ord)
+
+    def knn_store(self, width, n_classes, capacity):
+        """K9 on this context: an empty ml5 KNN store of `capacity` rows of `width` features (see KnnStore; webspeechanalyzer_amd.knn drives it)."""
+        return KnnStore(self, width, n_classes, capacity)
 
     def ensemble(self, models):
         """The app's `available_DBs` on this context: a list of 1 .. 8 Models in that order (every tie between DBs goes to the earlier one)."""
@@ -653,6 +674,26 @@ class Batch:
         self.an._check(self.L.wsa_batch_copy_values(self.h, stream, None, 0, ctypes.byref(n)))
         out = np.zeros(n.value, np.float64)
         self.an._check(self.L.wsa_batch_copy_values(self.h, stream, out.ctypes.data, max(n.value, 1), ctypes.byref(n)))
+        return out
+
+    def knn(self, store, k=10, stream=0):
+        """K9 on the rows of the last run, enqueued on `stream` (wsa_batch_knn): levels 5 / 13 with a 53-wide store, level 11 with a
+        264-wide one (the utterance rows), level 12 with a 23-wide one (label -1 and NaN for a row whose fit threw)."""
+        self.an._check(self.L.wsa_batch_knn(self.h, store.h, int(k), stream))
+        self._knn = store
+
+    def knn_result(self, stream=0):
+        r = _KnnResult()
+        self.an._check(self.L.wsa_batch_knn_result(self.h, stream, ctypes.byref(r)))
+        return r
+
+    def knn_classes(self, stream=0):
+        """Host copies of the last knn(): dict(label [n] i32, conf [n, C] f64, nbr [n, k] i32, sim [n, k] f32, k_eff), rows in the order of
+        rows() (level 11: utterance())."""
+        r = self.knn_result(stream)
+        n, C, k = int(r.n_rows), int(r.n_classes), int(r.k)
+        out = dict(label=np.zeros(n, np.int32), conf=np.zeros((n, C), np.float64), nbr=np.zeros((n, k), np.int32), sim=np.zeros((n, k), np.float32), k_eff=int(r.k_eff))
+        self.an._check(self.L.wsa_batch_copy_knn(self.h, stream, out["label"].ctypes.data, out["conf"].ctypes.data, out["nbr"].ctypes.data, out["sim"].ctypes.data, max(n, 1)))
         return out
 
     def classify_ensemble(self, ensemble, stream=0):
@@ -936,6 +977,48 @@ class FeatureDBStats:
         if self.h:
             self.L.wsa_dbstats_destroy(self.h)
             self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KnnStore:
+    """wsa_knn: the unit rows of an ml5 KNN classifier on the device (K9, spec KN-1).  Class indices are what the device sees;
+    webspeechanalyzer_amd.knn maps labels to them."""
+
+    def __init__(self, an, width, n_classes, capacity):
+        self.an, self.L, self.h = an, an.L, ctypes.c_void_p()
+        self.width, self.n_classes, self.capacity = int(width), int(n_classes), int(capacity)
+        an._check(self.L.wsa_knn_create(an.h, self.width, self.n_classes, self.capacity, ctypes.byref(self.h)))
+
+    @staticmethod
+    def tile_info():
+        """(train rows per tile, query rows per workgroup) of K9."""
+        t, q = ctypes.c_int32(), ctypes.c_int32()
+        lib().wsa_knn_tile_info(ctypes.byref(t), ctypes.byref(q))
+        return t.value, q.value
+
+    def add(self, d_feat, d_class, n, stream=0):
+        """n dense device rows [n][width] f64 with their device class indices [n] i32 (wsa_knn_add); only enqueues."""
+        self.an._check(self.L.wsa_knn_add(self.h, d_feat, d_class, int(n), stream))
+
+    def count(self, stream=0):
+        """Synchronises; (rows stored, rows per class [n_classes])."""
+        n, per = ctypes.c_uint32(), np.zeros(self.n_classes, np.uint32)
+        self.an._check(self.L.wsa_knn_count(self.h, stream, ctypes.byref(n), per.ctypes.data))
+        return n.value, per
+
+    def classify_rows(self, d_feat, n_rows, k, d_label=None, d_conf=None, d_nbr=None, d_sim=None, stream=0):
+        """wsa_knn_classify_rows on device pointers (any output may be None); only enqueues."""
+        self.an._check(self.L.wsa_knn_classify_rows(self.h, d_feat, int(n_rows), int(k), d_label, d_conf, d_nbr, d_sim, stream))
+
+    def close(self):
+        if self.h:
+            self.L.wsa_knn_destroy(self.h)
+            self.h = None
 
     def __del__(self):
         try:

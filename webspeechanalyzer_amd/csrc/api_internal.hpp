@@ -24,12 +24,14 @@ struct wsa_cls;                                 // classification buffers of one
 void wsa_cls_free(wsa_cls* c);                  // (wsa_batch_destroy)
 struct wsa_ecls;                                // ensemble tables of one batch (allocated by the first wsa_batch_classify_ensemble with an ensemble)
 void wsa_ecls_free(wsa_ecls* c);
+struct wsa_kcls;                                // KNN tables of one batch (allocated by the first wsa_batch_knn, knn.hip)
+void wsa_kcls_free(wsa_kcls* c);
 struct wsa_batch_view {
     wsa_ctx* ctx; int level; uint32_t n_clips, rows_cap;
     const int32_t* d_meta; const double* d_feat; const uint32_t* d_row_off;     // compacted rows, d_row_off[n_clips] = rows on the device
     const double* d_utt_feat; const uint32_t* d_utt_off; uint32_t utt_cap;      // level 11: utterance rows [..][WSA_NUTT], d_utt_off[n_clips] = their count on the device
     uint32_t reruns;                                                            // wsa_batch_backend_reruns
-    wsa_cls** cls; wsa_ecls** ecls;
+    wsa_cls** cls; wsa_ecls** ecls; wsa_kcls** kcls;
     int* cls_last;                                                              // 1: the last classification was one model's, 2: an ensemble's, 3: wsa_batch_regress
 };
 extern "C" {

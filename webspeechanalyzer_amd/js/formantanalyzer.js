@@ -367,6 +367,28 @@ function predictDB(featureDB, o) {
   return require('./dbstats.js').predictDB(dbstats_device(), featureDB, o);
 }
 function statsTable(featureDB, o) { return require('./dbstats.js').statsTable(dbstats_device(), featureDB, o || {}); }
+// ---- the app's ml5 KNN classifier (ref src/neuralmodel.js:729-837 train_knn; specification KN-1 / K9, include/wsa.h "KNN classifier"; js/knn.js).
+// KNNClassifier(width, capacity) -> ml5.KNNClassifier()'s addExample / classify / getCountByLabel on the device (classify is synchronous and
+//   returns ml5's result object; addExamples / classifyMultiple take many rows at once);
+// trainKnn(featureDB, {db, label, classes, k}) -> {knn, samples, correct, all}: train_knn's procedure over a feature DB (featuredb.js);
+// predictKnn(knn, [[numbers]], k) -> ml5's result per row.  knn.release() frees the device store (shutdown() frees it with its context).
+function knn_device() {
+  const nat = addon();
+  const ctx = contexts_for(nat, settings.devices ? settings.devices.slice() : [settings.device])[0];
+  return {
+    create: (width, classes, capacity) => nat.knnCreate(ctx, width, classes, capacity),
+    add: (store, x, cls) => nat.knnAdd(store, x, cls),
+    classify: (store, x, k) => nat.knnClassify(store, x, k),
+    batch: (store, k) => nat.batchKnn(ctx, store, k),
+    destroy: (store) => nat.knnDestroy(store),
+  };
+}
+function KNNClassifier(width, capacity) { return new (require('./knn.js').KnnClassifier)(knn_device(), width === undefined ? 53 : width, capacity); }
+function trainKnn(featureDB, o) { return require('./knn.js').trainKnn(knn_device(), featureDB, o); }
+function predictKnn(knn, rows, k) {
+  if (!knn || typeof knn.classifyMultiple !== 'function' || !Array.isArray(rows)) throw 'predictKnn(knn, [[numbers]], k)';
+  return knn.classifyMultiple(rows, k === undefined ? 10 : k);
+}
 function saveModel(handle, dir) {
   if (!handle || !handle.spec) throw 'saveModel(handle, dir)';
   require('./trainmodel.js').saveModelFiles(handle.spec, dir);
@@ -946,4 +968,5 @@ function set_predicted_label_for_segment(si, idx, label) {                      
 
 module.exports = { configure, LaunchAudioNodes, StopAudioNodes, set_predicted_label_for_segment, LaunchBatch, LaunchBatches,
   StreamOpen, STREAM_ACTIVE, STREAM_START, STREAM_STOP, shutdown, allocPinned, freePinned,
-  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, loadModel, setPredictionModel, setPredictionModels, trainModel, saveModel, trainRegression, predictValues, predictDB, statsTable };
+  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, loadModel, setPredictionModel, setPredictionModels, trainModel, saveModel, trainRegression, predictValues, predictDB, statsTable,
+  KNNClassifier, trainKnn, predictKnn };

@@ -105,6 +105,7 @@ typedef struct {
     /* the ensemble of the last processBatch call that had one (wsa_ensemble_create over ens_models): a call with the same list reuses it, so the
      * kept plan keeps its ensemble tables too; made and replaced by the job (one job at a time uses a context), dropped by destroy() */
     wsa_ensemble *ens; struct model_box *ens_models[WSA_ENSEMBLE_MAX]; uint32_t ens_n;
+    struct knn_box *knns;         /* the KNN stores created on this context (knnCreate): destroy() destroys them with it */
 } ctx_box;
 /* What JS holds for a model (wsa_model): like the context's box it outlives the model, so that a handle used after modelDestroy() or after its
  * context's destroy() finds NULL; `busy` counts the jobs that classify with it (modelDestroy() refuses meanwhile) */
@@ -112,6 +113,12 @@ typedef struct model_box { wsa_model *m; ctx_box *owner; uint32_t busy, n_classe
 static void model_unlink(model_box *mb) {
     if (mb->owner) for (model_box **q = &mb->owner->models; *q; q = &(*q)->next) if (*q == mb) { *q = mb->next; break; }
     mb->owner = NULL; mb->next = NULL;
+}
+/* What JS holds for a KNN store (wsa_knn): a box like a model's; every call on a store is synchronous, so it is never busy */
+typedef struct knn_box { wsa_knn *k; ctx_box *owner; uint32_t width, n_classes; struct knn_box *next; } knn_box;
+static void knn_unlink(knn_box *kb) {
+    if (kb->owner) for (knn_box **q = &kb->owner->knns; *q; q = &(*q)->next) if (*q == kb) { *q = kb->next; break; }
+    kb->owner = NULL; kb->next = NULL;
 }
 static void box_drop_ensemble(ctx_box *b) {
     if (b->ens) wsa_ensemble_destroy(b->ens);
@@ -167,6 +174,7 @@ static napi_value fn_destroy(napi_env env, napi_callback_info info) {
         box_drop_plan(b);
         box_drop_ensemble(b);                /* (before its models) */
         while (b->models) { model_box *mb = b->models; wsa_model_destroy(mb->m); mb->m = NULL; model_unlink(mb); }     /* models go before their context */
+        while (b->knns) { knn_box *kb = b->knns; wsa_knn_destroy(kb->k); kb->k = NULL; knn_unlink(kb); }               /* and so do KNN stores */
         if (b->queue) { wsa_queue_destroy(b->ctx, b->queue); b->queue = NULL; }
         wsa_destroy(b->ctx); b->ctx = NULL;
     }
@@ -1268,6 +1276,148 @@ done:
     return res;
 }
 
+/* ---- the app's ml5 KNN classifier (wsa_knn_*, K9, specification KN-1): what train_knn does with ml5.KNNClassifier() (ref src/neuralmodel.js:729-837).
+ * js/knn.js resolves the labels (ml5's class order) and hands over class indices.  Every call is synchronous; rows travel through one page-locked
+ * allocation the device reads and writes in place.
+ *   knnCreate(ctx, width, nClasses, capacity) -> handle;  knnDestroy(handle)
+ *   knnAdd(knn, features: Float64Array [n][width], classes: Int32Array [n]) -> {rows, perClass: Uint32Array [nClasses]}  (addExample, n rows at once)
+ *   knnClassify(knn, features: Float64Array [n][width], k) -> {label: Int32Array [n], conf: Float64Array [n][nClasses], nbr: Int32Array [n][k],
+ *     sim: Float32Array [n][k], k, kEff, nClasses}  (the tables of wsa_knn_classify_rows)
+ *   batchKnn(ctx, knn, k) -> the same tables over the rows of the context's last processBatch (wsa_batch_knn on its kept plan; level 11: the
+ *     utterance rows) */
+static void knn_finalize(napi_env env, void *data, void *hint) {
+    knn_box *kb = (knn_box *)data;
+    if (!kb->k && !kb->owner) free(kb);              /* a live store stays (explicit destroy only, as models) */
+}
+static knn_box *get_knn(napi_env env, napi_value v) {
+    void *p = NULL; napi_valuetype t = napi_undefined;
+    if (napi_typeof(env, v, &t) != napi_ok || t != napi_external || napi_get_value_external(env, v, &p) != napi_ok) return NULL;
+    return (knn_box *)p;
+}
+static napi_value fn_knn_create(napi_env env, napi_callback_info info) {
+    size_t argc = 4; napi_value argv[4];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ctx_box *box = argc ? get_box(env, argv[0]) : NULL;
+    int32_t width = 0, classes = 0; uint32_t cap = 0;
+    if (!box || !box->ctx || argc < 4 || napi_get_value_int32(env, argv[1], &width) != napi_ok || napi_get_value_int32(env, argv[2], &classes) != napi_ok ||
+        napi_get_value_uint32(env, argv[3], &cap) != napi_ok) { napi_throw_type_error(env, NULL, "knnCreate(ctx, width, nClasses, capacity)"); return NULL; }
+    wsa_knn *k = NULL;
+    if (wsa_knn_create(box->ctx, width, classes, cap, &k) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(box->ctx)); return NULL; }
+    knn_box *kb = calloc(1, sizeof *kb);
+    if (!kb) { wsa_knn_destroy(k); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    kb->k = k; kb->owner = box; kb->width = (uint32_t)width; kb->n_classes = (uint32_t)classes; kb->next = box->knns; box->knns = kb;
+    napi_value ext; NAPI_OK(env, napi_create_external(env, kb, knn_finalize, NULL, &ext));
+    return ext;
+}
+static napi_value fn_knn_destroy(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    knn_box *kb = argc ? get_knn(env, argv[0]) : NULL;
+    if (!kb) { napi_throw_type_error(env, NULL, "knnDestroy(knn)"); return NULL; }
+    if (kb->owner && kb->owner->children) { napi_throw_error(env, NULL, "the KNN store's context has a batch in flight or open streams"); return NULL; }
+    if (kb->owner) box_drop_plan(kb->owner);         /* the kept plan's KNN tables name the store */
+    if (kb->k) { wsa_knn_destroy(kb->k); kb->k = NULL; }
+    knn_unlink(kb);
+    return NULL;
+}
+static napi_value fn_knn_add(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    const char *usage = "knnAdd(knn, features: Float64Array [n][width], classes: Int32Array [n])";
+    knn_box *kb = argc ? get_knn(env, argv[0]) : NULL;
+    void *feat = NULL, *cls = NULL; size_t nf = 0, n = 0;
+    if (!kb || argc < 3 || !typed_arg(env, argv[1], napi_float64_array, &feat, &nf) || !typed_arg(env, argv[2], napi_int32_array, &cls, &n) ||
+        (kb->width && (nf != n * kb->width || n > 0xffffffffu))) { napi_throw_type_error(env, NULL, usage); return NULL; }
+    if (!kb->k || !kb->owner || !kb->owner->ctx) { napi_throw_error(env, NULL, "knnAdd: the KNN store was destroyed"); return NULL; }
+    ctx_box *box = kb->owner;
+    void *slab = NULL;
+    if (wsa_host_alloc(box->ctx, (uint64_t)(nf + 1) * sizeof(double) + (uint64_t)(n + 1) * sizeof(int32_t), &slab) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(box->ctx)); return NULL; }
+    double *rows = (double *)slab; int32_t *ci = (int32_t *)(rows + nf + 1);
+    if (nf) memcpy(rows, feat, nf * sizeof(double));
+    if (n) memcpy(ci, cls, n * sizeof(int32_t));
+    uint32_t total = 0, per[WSA_MODEL_MAX_CLASSES] = {0};
+    wsa_status st = wsa_knn_add(kb->k, rows, ci, (uint32_t)n, box->queue);
+    if (st == WSA_OK) st = wsa_knn_count(kb->k, box->queue, &total, per);
+    napi_value out = NULL;
+    if (st == WSA_OK) {
+        napi_value nr;
+        napi_create_object(env, &out); napi_create_uint32(env, total, &nr);
+        napi_set_named_property(env, out, "rows", nr);
+        napi_set_named_property(env, out, "perClass", make_typed(env, napi_uint32_array, per, kb->n_classes, 4));
+    } else napi_throw_error(env, NULL, wsa_last_error(box->ctx));
+    wsa_host_free(slab);
+    return out;
+}
+/* the four tables out of one page-locked slab laid out [label n][nbr n k][sim n k][conf n C] behind `head` bytes */
+static napi_value knn_tables(napi_env env, const char *slab, size_t head, size_t n, uint32_t k, uint32_t k_eff, uint32_t C) {
+    const int32_t *label = (const int32_t *)(slab + head), *nbr = label + n; const float *sim = (const float *)(nbr + n * k);
+    const double *conf = (const double *)(slab + head + ((n + 2 * n * k) * 4 + 7) / 8 * 8);
+    napi_value o, v;
+    napi_create_object(env, &o);
+    napi_set_named_property(env, o, "label", make_typed(env, napi_int32_array, label, n, 4));
+    napi_set_named_property(env, o, "nbr", make_typed(env, napi_int32_array, nbr, n * k, 4));
+    napi_set_named_property(env, o, "sim", make_typed(env, napi_float32_array, sim, n * k, 4));
+    napi_set_named_property(env, o, "conf", make_typed(env, napi_float64_array, conf, n * C, 8));
+    napi_create_uint32(env, k, &v); napi_set_named_property(env, o, "k", v);
+    napi_create_uint32(env, k_eff, &v); napi_set_named_property(env, o, "kEff", v);
+    napi_create_uint32(env, C, &v); napi_set_named_property(env, o, "nClasses", v);
+    return o;
+}
+static size_t knn_tables_bytes(size_t n, uint32_t k, uint32_t C) { return ((n + 2 * n * k) * 4 + 7) / 8 * 8 + n * C * 8 + 8; }
+static napi_value fn_knn_classify(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    const char *usage = "knnClassify(knn, features: Float64Array [n][width], k)";
+    knn_box *kb = argc ? get_knn(env, argv[0]) : NULL;
+    void *feat = NULL; size_t nf = 0; uint32_t k = 0;
+    if (!kb || argc < 3 || !typed_arg(env, argv[1], napi_float64_array, &feat, &nf) || napi_get_value_uint32(env, argv[2], &k) != napi_ok ||
+        (kb->width && (nf % kb->width || nf / kb->width > 0xffffffffu))) { napi_throw_type_error(env, NULL, usage); return NULL; }
+    if (!kb->k || !kb->owner || !kb->owner->ctx) { napi_throw_error(env, NULL, "knnClassify: the KNN store was destroyed"); return NULL; }
+    if (k < 1 || k > WSA_KNN_MAX_K) { napi_throw_error(env, NULL, "knnClassify: k must be 1 .. 64"); return NULL; }
+    ctx_box *box = kb->owner;
+    const size_t n = nf / kb->width, head = (nf + 1) * sizeof(double);
+    const uint32_t C = kb->n_classes;
+    void *slab = NULL;
+    if (wsa_host_alloc(box->ctx, (uint64_t)head + knn_tables_bytes(n, k, C), &slab) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(box->ctx)); return NULL; }
+    char *base = (char *)slab;
+    if (nf) memcpy(base, feat, nf * sizeof(double));
+    int32_t *label = (int32_t *)(base + head), *nbr = label + n; float *sim = (float *)(nbr + n * k);
+    double *conf = (double *)(base + head + ((n + 2 * n * k) * 4 + 7) / 8 * 8);
+    uint32_t total = 0;
+    wsa_status st = wsa_knn_classify_rows(kb->k, (const double *)base, (uint32_t)n, k, label, conf, nbr, sim, box->queue);
+    if (st == WSA_OK) st = wsa_knn_count(kb->k, box->queue, &total, NULL);          /* synchronises; k_eff = min(k, rows) */
+    napi_value out = NULL;
+    if (st == WSA_OK) out = knn_tables(env, base, head, n, k, k < total ? k : total, C);
+    else napi_throw_error(env, NULL, wsa_last_error(box->ctx));
+    wsa_host_free(slab);
+    return out;
+}
+static napi_value fn_batch_knn(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ctx_box *box = argc ? get_box(env, argv[0]) : NULL;
+    knn_box *kb = argc > 1 ? get_knn(env, argv[1]) : NULL;
+    uint32_t k = 0;
+    if (!box || !box->ctx || !kb || argc < 3 || napi_get_value_uint32(env, argv[2], &k) != napi_ok) { napi_throw_type_error(env, NULL, "batchKnn(ctx, knn, k)"); return NULL; }
+    if (!kb->k || kb->owner != box) { napi_throw_error(env, NULL, "batchKnn: the KNN store was destroyed or belongs to another context"); return NULL; }
+    if (!box->plan) { napi_throw_error(env, NULL, "batchKnn: no finished processBatch on this context (or one is in flight)"); return NULL; }
+    wsa_knn_result r;
+    wsa_status st = wsa_batch_knn(box->plan, kb->k, k, box->queue);
+    if (st == WSA_OK) st = wsa_batch_knn_result(box->plan, box->queue, &r);
+    if (st != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(box->ctx)); return NULL; }
+    const size_t n = r.n_rows;
+    char *buf = malloc(knn_tables_bytes(n, r.k, r.n_classes));
+    if (!buf) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    int32_t *label = (int32_t *)buf, *nbr = label + n; float *sim = (float *)(nbr + n * r.k);
+    double *conf = (double *)(buf + ((n + 2 * n * r.k) * 4 + 7) / 8 * 8);
+    st = wsa_batch_copy_knn(box->plan, box->queue, label, conf, nbr, sim, (uint32_t)(n ? n : 1));
+    napi_value out = NULL;
+    if (st == WSA_OK) out = knn_tables(env, buf, 0, n, r.k, r.k_eff, r.n_classes);
+    else napi_throw_error(env, NULL, wsa_last_error(box->ctx));
+    free(buf);
+    return out;
+}
+
 NAPI_MODULE_INIT() {
     /* the structures below follow the header this file was compiled against: refuse a libwsa.so of another ABI version */
     if (wsa_abi_version() != WSA_ABI_VERSION) { napi_throw_error(env, NULL, "libwsa.so ABI version differs from the one wsa_napi.node was built against (include/wsa.h): rebuild"); return NULL; }
@@ -1276,7 +1426,8 @@ NAPI_MODULE_INIT() {
         {"geometry", fn_geometry}, {"allocPinned", fn_alloc_pinned}, {"binsHz", fn_bins_hz}, {"processBatch", fn_process_batch}, {"gatherRows", fn_gather_rows},
         {"streamOpen", fn_stream_open}, {"streamOpenMixed", fn_stream_open_mixed}, {"streamInfo", fn_stream_info}, {"streamPaced", fn_stream_paced}, {"streamInput", fn_stream_input}, {"streamStep", fn_stream_step}, {"streamClose", fn_stream_close}, {"streamSetModel", fn_stream_set_model}, {"streamSetEnsemble", fn_stream_set_ensemble},
         {"modelCreate", fn_model_create}, {"modelDestroy", fn_model_destroy}, {"train", fn_train}, {"regressRows", fn_regress_rows},
-        {"dbPredict", fn_db_predict}, {"dbTable", fn_db_table}};
+        {"dbPredict", fn_db_predict}, {"dbTable", fn_db_table},
+        {"knnCreate", fn_knn_create}, {"knnDestroy", fn_knn_destroy}, {"knnAdd", fn_knn_add}, {"knnClassify", fn_knn_classify}, {"batchKnn", fn_batch_knn}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;
