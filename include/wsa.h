@@ -809,6 +809,60 @@ wsa_status wsa_batch_knn_result(wsa_batch *b, void *stream, wsa_knn_result *out)
 /* the same tables copied to host buffers of rows_cap rows (any pointer may be NULL to skip it); WSA_ERR_INVALID if rows_cap is too small */
 wsa_status wsa_batch_copy_knn(wsa_batch *b, void *stream, int32_t *label, double *conf, int32_t *nbr, float *sim, uint32_t rows_cap);
 
+/*
+ * ---- KNN on live streams and the per-callback fold of KNN results (additions within version 5: probe for wsa_stream_set_knn).
+ * Kernels K9s (csrc/knn.hip) and the fold of specification KN-2 (csrc/knn_fold.hip).
+ * K9s is K9 for few query rows: the store is cut into S slices of whole tiles, one workgroup per (query tile, slice) selects within its
+ * slice and leaves a partial list in a scratch table, and one wave per query merges its S lists and runs K9's epilogue.  A similarity is
+ * the same bits as K9's and the order (similarity descending, grouped rank ascending) is total, so the four tables equal
+ * wsa_knn_classify_rows' bit for bit whatever S is.
+ *   S, chosen when a store is attached, for a window of W query rows (a stream set's D2H window of at most 1024 rows) against a store of
+ *   T tiles of 64 rows on a device of n_cu compute units: S = ceil(2 n_cu / ceil(W / 64)), so that (query tiles x S) gives every CU two
+ *   workgroups; at most ceil(T / 4), so that no slice is shorter than four tiles; at most WSA_KNN_SPLIT_MAX_SLICES; and at most what
+ *   keeps the scratch table, W x S x (12 k + 4) bytes, within WSA_KNN_SPLIT_SCRATCH_BYTES.  At least 1.
+ * KN-2 is K6b's fold (wsa_class_result, ref src/prediction.js:86-123) fed, per row, the n_classes pairs (class index, votes / k_eff as the
+ * f64 of d_conf) in classifyMultiple's order — confidence descending, ties in class-index order — with the class indices as the legend.
+ * The reference application has no KNN path there: the definition is this project's.
+ */
+#define WSA_KNN_SPLIT_MAX_SLICES 256
+#define WSA_KNN_SPLIT_SCRATCH_BYTES (64u << 20)
+/* KN-2 over the tables of the batch's last wsa_batch_knn (output_level 13 only: WSA_ERR_INVALID otherwise, or before a wsa_batch_knn),
+ * one accumulator per clip.  Only enqueues; after the first call on a batch nothing is allocated, so it can be captured behind
+ * wsa_batch_run + wsa_batch_knn. */
+wsa_status wsa_batch_knn_fold(wsa_batch *b, void *stream);
+/* as wsa_class_result's callback tables: d_cb [n_callbacks][4] = {clip, si, first row, rows}, d_cb_label (-1 = null, -2 = no prediction),
+ * d_cb_conf, d_clip_conf [n_clips][n_classes]; valid until the next wsa_batch_knn / wsa_batch_knn_fold that allocates */
+typedef struct {
+    uint32_t n_callbacks, n_classes, n_clips;
+    const int32_t *d_cb; const int32_t *d_cb_label; const double *d_cb_conf; const double *d_clip_conf;
+} wsa_knn_fold_result;
+wsa_status wsa_batch_knn_fold_result(wsa_batch *b, void *stream, wsa_knn_fold_result *out);      /* synchronises `stream` */
+/* the same tables copied to host buffers (any pointer may be NULL): cb [cb_cap][4], cb_label / cb_conf [cb_cap], clip_conf [n_clips][n_classes] */
+wsa_status wsa_batch_copy_knn_fold(wsa_batch *b, void *stream, int32_t *cb, int32_t *cb_label, double *cb_conf, uint32_t cb_cap, double *clip_conf);
+/* Attach (knn != NULL) or detach (NULL) a KNN store: K9s on every step's rows (partial + merge) and, at output_level 13, KN-2 with one
+ * accumulator per stream carried on the device — reset by START, untouched on idle steps, kept after STOP — as kernels of the step, on
+ * the step's own stream behind its other kernels; the step stays one graph launch.  Levels 5 and 13 with a 53-wide store only; refused
+ * with a message: any other level or width (naming both), a store of another context, k outside 1 .. WSA_KNN_MAX_K, an empty store.
+ * Synchronises the last step, allocates everything (tables, the K9s scratch, the accumulators, zeroed) and drops the captured graph.
+ * The store's row count is the one at attach (a captured graph keeps it); attaching again picks up added rows.  The KNN tables are
+ * separate from a model's or an ensemble's: attaching a store neither detaches nor is detached by wsa_stream_set_model /
+ * wsa_stream_set_ensemble.  The store must outlive its attachment.  wsa_stream_time_steps times the step with these kernels in it. */
+wsa_status wsa_stream_set_knn(wsa_stream *st, const wsa_knn *knn, uint32_t k);
+typedef struct {
+    uint32_t n_rows, n_classes, k, k_eff, n_callbacks, n_streams, slices;      /* slices: the S chosen at attach */
+    const int32_t *label;        /* [n_rows], rows in wsa_stream_rows order; the four row tables as wsa_knn_classify_rows' outputs */
+    const double  *conf;         /* [n_rows][n_classes] */
+    const int32_t *nbr;          /* [n_rows][k] */
+    const float   *sim;          /* [n_rows][k] */
+    const int32_t *cb;           /* [n_callbacks][4] = {stream, si, first row, rows} (level 13; else 0 / NULL) */
+    const int32_t *cb_label;     /* -1 = null, -2 = no prediction */
+    const double  *cb_conf;
+    const double  *stream_conf;  /* [n_streams][n_classes] KN-2's Label_conf_all since each stream's START (level 13) */
+} wsa_stream_knn_result;
+/* After wsa_stream_collect of the same step: host memory owned by the stream object, valid until the next step.
+ * WSA_ERR_INVALID without an attached store. */
+wsa_status wsa_stream_knn_classes(wsa_stream *st, wsa_stream_knn_result *out);
+
 #ifdef __cplusplus
 }
 #endif

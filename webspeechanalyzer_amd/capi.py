@@ -137,6 +137,18 @@ class _KnnResult(ctypes.Structure):
                 ("d_label", ctypes.c_void_p), ("d_conf", ctypes.c_void_p), ("d_nbr", ctypes.c_void_p), ("d_sim", ctypes.c_void_p)]
 
 
+class _KnnFoldResult(ctypes.Structure):
+    _fields_ = [("n_callbacks", ctypes.c_uint32), ("n_classes", ctypes.c_uint32), ("n_clips", ctypes.c_uint32),
+                ("d_cb", ctypes.c_void_p), ("d_cb_label", ctypes.c_void_p), ("d_cb_conf", ctypes.c_void_p), ("d_clip_conf", ctypes.c_void_p)]
+
+
+class _StreamKnnResult(ctypes.Structure):
+    _fields_ = [("n_rows", ctypes.c_uint32), ("n_classes", ctypes.c_uint32), ("k", ctypes.c_uint32), ("k_eff", ctypes.c_uint32),
+                ("n_callbacks", ctypes.c_uint32), ("n_streams", ctypes.c_uint32), ("slices", ctypes.c_uint32),
+                ("label", ctypes.c_void_p), ("conf", ctypes.c_void_p), ("nbr", ctypes.c_void_p), ("sim", ctypes.c_void_p),
+                ("cb", ctypes.c_void_p), ("cb_label", ctypes.c_void_p), ("cb_conf", ctypes.c_void_p), ("stream_conf", ctypes.c_void_p)]
+
+
 # every symbol include/wsa.h declares (checked by tests/test_abi.py)
 ABI_VERSION = 5            # WSA_ABI_VERSION of include/wsa.h this binding's structures follow
 ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destroy", "wsa_last_error",
@@ -171,7 +183,9 @@ ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destr
                "wsa_level_feature_count", "wsa_wide_dbstats_create",
                # additions within version 5 (probe for wsa_knn_create): the app's ml5 KNN classifier (K9, spec KN-1)
                "wsa_knn_create", "wsa_knn_destroy", "wsa_knn_add", "wsa_knn_count", "wsa_knn_classify_rows", "wsa_knn_tile_info",
-               "wsa_batch_knn", "wsa_batch_knn_result", "wsa_batch_copy_knn"]
+               "wsa_batch_knn", "wsa_batch_knn_result", "wsa_batch_copy_knn",
+               # additions within version 5 (probe for wsa_stream_set_knn): KNN on live streams (K9s) and the fold of KNN results (spec KN-2)
+               "wsa_batch_knn_fold", "wsa_batch_knn_fold_result", "wsa_batch_copy_knn_fold", "wsa_stream_set_knn", "wsa_stream_knn_classes"]
 
 _LIB = None
 _U32_RESULT = ("wsa_stream_input_capacity", "wsa_stream_paced_input", "wsa_stream_input_stride", "wsa_stream_step_frame_capacity", "wsa_stream_frames_bound")
@@ -318,6 +332,11 @@ def lib():
     L.wsa_batch_knn.argtypes = [vp, vp, u32, vp]
     L.wsa_batch_knn_result.argtypes = [vp, vp, ctypes.POINTER(_KnnResult)]
     L.wsa_batch_copy_knn.argtypes = [vp, vp, vp, vp, vp, vp, u32]
+    L.wsa_batch_knn_fold.argtypes = [vp, vp]
+    L.wsa_batch_knn_fold_result.argtypes = [vp, vp, ctypes.POINTER(_KnnFoldResult)]
+    L.wsa_batch_copy_knn_fold.argtypes = [vp, vp, vp, vp, vp, u32, vp]
+    L.wsa_stream_set_knn.argtypes = [vp, vp, u32]
+    L.wsa_stream_knn_classes.argtypes = [vp, ctypes.POINTER(_StreamKnnResult)]
     for name in ABI_SYMBOLS:
         if name in _U32_RESULT or name in ("wsa_resample_ready", "wsa_level_feature_count"):
             continue
@@ -694,6 +713,22 @@ class Batch:
         n, C, k = int(r.n_rows), int(r.n_classes), int(r.k)
         out = dict(label=np.zeros(n, np.int32), conf=np.zeros((n, C), np.float64), nbr=np.zeros((n, k), np.int32), sim=np.zeros((n, k), np.float32), k_eff=int(r.k_eff))
         self.an._check(self.L.wsa_batch_copy_knn(self.h, stream, out["label"].ctypes.data, out["conf"].ctypes.data, out["nbr"].ctypes.data, out["sim"].ctypes.data, max(n, 1)))
+        return out
+
+    def knn_fold(self, stream=0):
+        """KN-2 on the tables of the last knn() at level 13, enqueued on `stream` (wsa_batch_knn_fold): K6b's fold fed the rows' KNN
+        confidences with the class indices as the legend, one accumulator per clip."""
+        self.an._check(self.L.wsa_batch_knn_fold(self.h, stream))
+
+    def knn_fold_classes(self, stream=0):
+        """Host copies of the last knn_fold(): dict(cb [n_cb, 4] i32 = {clip, si, first row, rows}, cb_label [n_cb] i32 (a class index;
+        -1: null, -2: not predicted), cb_conf [n_cb] f64, clip_conf [n_clips, C] f64)."""
+        r = _KnnFoldResult()
+        self.an._check(self.L.wsa_batch_knn_fold_result(self.h, stream, ctypes.byref(r)))
+        k, C = int(r.n_callbacks), int(r.n_classes)
+        out = dict(cb=np.zeros((k, 4), np.int32), cb_label=np.zeros(k, np.int32), cb_conf=np.zeros(k, np.float64), clip_conf=np.zeros((int(r.n_clips), C), np.float64))
+        self.an._check(self.L.wsa_batch_copy_knn_fold(self.h, stream, out["cb"].ctypes.data, out["cb_label"].ctypes.data, out["cb_conf"].ctypes.data, max(k, 1),
+                                                       out["clip_conf"].ctypes.data))
         return out
 
     def classify_ensemble(self, ensemble, stream=0):
@@ -1208,6 +1243,31 @@ class Streams:
                     cb_label=arr(r.cb_label, ctypes.c_int32, np.int32, (k,)), cb_conf=arr(r.cb_conf, ctypes.c_double, np.float64, (k,)),
                     stream_conf=arr(r.stream_conf, ctypes.c_double, np.float64, (int(r.n_streams), C)), labels=list(self._model.labels))
 
+    def set_knn(self, store, k=10):
+        """Attach a KnnStore (K9s on every step's rows; at level 13 the fold KN-2, one accumulator per stream reset by START) or detach
+        (None).  Stands beside a Model or an Ensemble; the next step recaptures the graph.  The store's rows are those at this call."""
+        self.an._check(self.L.wsa_stream_set_knn(self.h, store.h if store is not None else None, int(k)))
+        self._knn = store
+
+    def knn_classes(self):
+        """After collect(): host copies of the step's KNN tables, dict(label [n_rows] i32, conf [n_rows, C] f64, nbr [n_rows, k] i32,
+        sim [n_rows, k] f32, k_eff, slices, cb [n_cb, 4] i32 = {stream, si, first row, rows}, cb_label [n_cb] i32 (a class index; -1: null,
+        -2: not predicted), cb_conf [n_cb] f64, stream_conf [n, C] f64).  Level 5: cb / cb_label / cb_conf / stream_conf are None."""
+        r = _StreamKnnResult()
+        self.an._check(self.L.wsa_stream_knn_classes(self.h, ctypes.byref(r)))
+        n, C, k, ncb = int(r.n_rows), int(r.n_classes), int(r.k), int(r.n_callbacks)
+
+        def arr(ptr, ctype, dtype, shape):
+            if not ptr:
+                return None
+            if not int(np.prod(shape)):
+                return np.zeros(shape, dtype)
+            return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctype)), shape=shape).copy()
+        i32, f64 = (ctypes.c_int32, np.int32), (ctypes.c_double, np.float64)
+        return dict(label=arr(r.label, *i32, (n,)), conf=arr(r.conf, *f64, (n, C)), nbr=arr(r.nbr, *i32, (n, k)), sim=arr(r.sim, ctypes.c_float, np.float32, (n, k)),
+                    k_eff=int(r.k_eff), slices=int(r.slices), cb=arr(r.cb, *i32, (ncb, 4)), cb_label=arr(r.cb_label, *i32, (ncb,)),
+                    cb_conf=arr(r.cb_conf, *f64, (ncb,)), stream_conf=arr(r.stream_conf, *f64, (int(r.n_streams), C)))
+
     def set_ensemble(self, ensemble):
         """Attach an Ensemble (K6e on every step's rows; at level 13 one accumulator per stream and member and one running min_entropy_db
         per stream, reset by START) or detach (None).  Detaches a Model; the next step recaptures the graph."""
@@ -1280,6 +1340,17 @@ class Streams:
 GATE_INT_RUNS, GATE_INT_GENERAL, GATE_F64, GATE_STREAM = 0, 1, 2, 3
 GATE_STATE_WORDS = 16
 GATE_SENTINEL = -2
+
+
+def debug_knn_split(store, d_feat, n_rows, k, slices, d_label, d_conf, d_nbr, d_sim, stream=0):
+    """Test access to K9s on its own (csrc/knn.hip wsa_debug_knn_split; not part of include/wsa.h): the split-store kernels over n_rows dense
+    device rows with a forced slice count (0: the rule's), outputs as KnnStore.classify_rows.  Only enqueues (its scratch table stays with
+    the store); with n_rows = 0 the kernels still run, over no row."""
+    L = lib()
+    vp, u32 = ctypes.c_void_p, ctypes.c_uint32
+    L.wsa_debug_knn_split.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp, vp]
+    L.wsa_debug_knn_split.restype = ctypes.c_int
+    store.an._check(L.wsa_debug_knn_split(store.h, d_feat, int(n_rows), int(k), int(slices), d_label, d_conf, d_nbr, d_sim, stream))
 
 
 def debug_gate(variant, clips, settings, blocks=0, F=0, max_span=0, step_nfr=None, step_ctl=None, device=0):

@@ -63,6 +63,13 @@ void wsa_sens_free(wsa_sens* c);
 wsa_status wsa_sens_enqueue(wsa_sens* c, hipStream_t s);
 wsa_status wsa_sens_result(wsa_sens* c, uint32_t rows, wsa_stream_ensemble_result* out);
 
+// ... and, beside either, K9s and the fold KN-2 with an attached KNN store (wsa_stream_set_knn; knn_fold.hip)
+struct wsa_sknn;
+wsa_status wsa_sknn_create(const wsa_scls_view& v, const wsa_knn* kn, uint32_t k, wsa_sknn** out);   // checks the store and k, allocates, zeroes the fold state
+void wsa_sknn_free(wsa_sknn* c);
+wsa_status wsa_sknn_enqueue(wsa_sknn* c, hipStream_t s);
+wsa_status wsa_sknn_result(wsa_sknn* c, uint32_t rows, wsa_stream_knn_result* out);
+
 // classify.hip: NULL for the row width of an ML level (53, 264, 23), else the rest of the refusal after "the model takes N"
 const char* wsa_model_width_refusal(int n_inputs);
 

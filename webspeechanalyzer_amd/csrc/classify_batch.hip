@@ -47,83 +47,6 @@ void wsa_ecls_free(wsa_ecls* c) { free_on_device(c); }
 
 namespace {
 
-// ---- K6b: one wave per clip, classes on lanes, callbacks walked in order (ref prediction.js:86-169 with one model DB)
-struct FoldParams {
-    uint32_t n_clips, C; double step_s;
-    const int32_t* meta; const uint32_t* row_off; const float* prob;
-    const int32_t* key_rank;                 // [C] array-index value of the label, or -1
-    int32_t* t_label; double* t_conf; int32_t* t_n; int32_t* t_local;   // per row: the callback that starts there (t_n = 0 elsewhere)
-    uint32_t* clip_cb;                       // [n_clips] callbacks per clip
-    double* clip_conf;                       // [n_clips][C]
-};
-
-__global__ void __launch_bounds__(256) fold_kernel(FoldParams p) {
-    const int lane = threadIdx.x & 63;
-    const uint32_t clip = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (clip >= p.n_clips) return;
-    const uint32_t r0 = p.row_off[clip], r1 = p.row_off[clip + 1];
-    const bool cls = (uint32_t)lane < p.C;
-    const int kr = cls ? p.key_rank[lane] : -1;
-    FoldAcc a{0.0, false, 0, 0};
-    uint32_t ncb = 0;
-    for (uint32_t r = r0; r < r1;) {
-        const uint32_t e = callback_end(p.meta, r, r1);
-        int label; double conf, seg_max;
-        fold_callback(p.meta, p.prob, p.C, p.step_s, lane, cls, kr, r, e, a, label, conf, seg_max);
-        if (lane == 0) { p.t_label[r] = label; p.t_conf[r] = conf; p.t_n[r] = (int32_t)(e - r); p.t_local[r] = (int32_t)ncb; }
-        for (uint32_t q = r + 1 + lane; q < e; q += 64) p.t_n[q] = 0;
-        ncb++;
-        r = e;
-    }
-    if (cls) p.clip_conf[(size_t)clip * p.C + lane] = a.acc_all;
-    if (lane == 0) p.clip_cb[clip] = ncb;
-}
-
-// callbacks per clip -> offsets (one workgroup of 1024 threads; returns the total to every thread)
-__device__ __forceinline__ uint32_t compact_offsets(uint32_t n_clips, const uint32_t* clip_cb, uint32_t* cb_off, uint32_t* s_part, uint32_t* s_base) {
-    const int tid = threadIdx.x;
-    if (tid == 0) *s_base = 0;
-    __syncthreads();
-    for (uint32_t c0 = 0; c0 < n_clips; c0 += 1024) {
-        const uint32_t c = c0 + tid;
-        const uint32_t v = c < n_clips ? clip_cb[c] : 0u;
-        s_part[tid] = v;
-        __syncthreads();
-        for (int o = 1; o < 1024; o <<= 1) {                       // inclusive scan (Hillis-Steele)
-            const uint32_t t = tid >= o ? s_part[tid - o] : 0u;
-            __syncthreads();
-            s_part[tid] += t;
-            __syncthreads();
-        }
-        if (c < n_clips) cb_off[c] = *s_base + s_part[tid] - v;
-        __syncthreads();
-        if (tid == 1023) *s_base += s_part[1023];
-        __syncthreads();
-    }
-    return *s_base;
-}
-
-// the offsets, then every callback's entry from the row it starts at; the count goes to the host's mapped word
-__global__ void __launch_bounds__(1024) fold_compact_kernel(uint32_t n_clips, const uint32_t* row_off, const int32_t* meta, const uint32_t* clip_cb,
-                                                            uint32_t* cb_off, const int32_t* t_label, const double* t_conf, const int32_t* t_n,
-                                                            const int32_t* t_local, int32_t* cb, int32_t* cb_label, double* cb_conf, uint32_t* host) {
-    __shared__ uint32_t s_part[1024];
-    __shared__ uint32_t s_base;
-    const int tid = threadIdx.x;
-    const uint32_t n_cb = compact_offsets(n_clips, clip_cb, cb_off, s_part, &s_base);
-    const uint32_t n_rows = row_off[n_clips];
-    __syncthreads();
-    for (uint32_t r = tid; r < n_rows; r += 1024) {
-        const int32_t nsyl = t_n[r];
-        if (nsyl <= 0) continue;
-        const int32_t clip = meta[(size_t)r * 8];
-        const uint32_t k = cb_off[clip] + (uint32_t)t_local[r];
-        write_callback(cb, k, clip, meta[(size_t)r * 8 + 1], r, nsyl);
-        cb_label[k] = t_label[r]; cb_conf[k] = t_conf[r];
-    }
-    if (tid == 0) host[0] = n_cb;
-}
-
 // ---- K6b-e: the fold for every member of an ensemble, one wave per (clip, member)
 struct FoldGroupParams {
     uint32_t n_clips, n_members; double step_s;
@@ -234,12 +157,12 @@ wsa_status enqueue_batch(const wsa_batch_view& v, wsa_cls* c, const wsa_model* m
     launch_classify(m, batch_params(v, m, c->d_prob), cap, s);
     HIP_TRY(ctx, hipGetLastError());
     if (v.level == 13) {
-        FoldParams f{};
+        FoldParams<float> f{};
         f.n_clips = v.n_clips; f.C = (uint32_t)m->C; f.step_s = ctx->cfg.window_step / 1e3;
         f.meta = v.d_meta; f.row_off = v.d_row_off; f.prob = c->d_prob; f.key_rank = m->d_key_rank;
         f.t_label = c->d_t_label; f.t_conf = c->d_t_conf; f.t_n = c->d_t_n; f.t_local = c->d_t_local;
         f.clip_cb = c->d_clip_cb; f.clip_conf = c->d_clip_conf;
-        if (v.n_clips) hipLaunchKernelGGL(fold_kernel, dim3((v.n_clips + 3) / 4), dim3(256), 0, s, f);
+        if (v.n_clips) hipLaunchKernelGGL(fold_kernel<float>, dim3((v.n_clips + 3) / 4), dim3(256), 0, s, f);
         hipLaunchKernelGGL(fold_compact_kernel, dim3(1), dim3(1024), 0, s, v.n_clips, v.d_row_off, v.d_meta, c->d_clip_cb, c->d_cb_off,
                            c->d_t_label, c->d_t_conf, c->d_t_n, c->d_t_local, c->d_cb, c->d_cb_label, c->d_cb_conf, c->h_count_dev);
         HIP_TRY(ctx, hipGetLastError());

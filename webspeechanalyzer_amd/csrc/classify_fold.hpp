@@ -1,5 +1,5 @@
 // classify_fold.hpp — K6b's device code: what the four fold kernels (fold_kernel and fold_group_kernel in classify_batch.hip,
-// stream_classes_kernel and stream_fold_group_kernel in classify_stream.hip) and stream_decide_kernel share.  Stands in for the reference
+// stream_classes_kernel and stream_fold_group_kernel in classify_stream.hip), stream_decide_kernel and KN-2's two (knn_fold.hip) share.  Stands in for the reference
 // APPLICATION's src/prediction.js:86-169 (weights sqrt(duration), per-label sums, segment label, per-launch accumulator, the ensemble's
 // decision); this is the part that must match the JavaScript bit for bit, so each piece is written once.  Device only; every
 // translation unit that includes it gets its own copy.
@@ -83,8 +83,10 @@ __device__ __forceinline__ void store_fold(const CarriedFold& c, uint32_t s, siz
     if (lane == 0) c.stamp[s] = a.stamp;
 }
 
-// one callback: rows r .. e - 1 (the same clip / stream and si); label -1 / -2 as wsa_class_result
-__device__ __forceinline__ void fold_callback(const int32_t* meta, const float* prob, uint32_t C, double step_s, int lane, bool cls, int kr,
+// one callback: rows r .. e - 1 (the same clip / stream and si); label -1 / -2 as wsa_class_result.  P is the type the confidences
+// arrive in: float for a network's probabilities (K6), double for KNN's votes / k_eff (K9, specification KN-2); the sums are double.
+template <typename P>
+__device__ __forceinline__ void fold_callback(const int32_t* meta, const P* prob, uint32_t C, double step_s, int lane, bool cls, int kr,
                                               uint32_t r, uint32_t e, FoldAcc& a, int& label, double& conf, double& seg_max) {
     const uint32_t nsyl = e - r;
     double seg_weight = 0.0;                 // sum of parseFloat(seg_time[ph][1]) (ref prediction.js:55)
@@ -94,11 +96,11 @@ __device__ __forceinline__ void fold_callback(const int32_t* meta, const float* 
     double acc_seg = 0.0; bool in_seg = false;
     for (uint32_t q = r; q < e; q++) {
         const double w = __dsqrt_rn(fixed3((double)(meta[(size_t)q * 8 + 3] + 1) * step_s));
-        const float pf = cls ? prob[(size_t)q * C + lane] : 0.f;
+        const P pf = cls ? prob[(size_t)q * C + lane] : P(0);
         // rank in classifyMultiple's order: confidence descending, ties in legend order (a stable sort)
         int rank = 0;
         for (int j = 0; j < (int)C; j++) {
-            const float pj = __shfl(pf, j);
+            const P pj = __shfl(pf, j);
             rank += (pj > pf || (pj == pf && j < lane)) ? 1 : 0;
         }
         const bool add = cls && (nsyl > 1 || rank == 0);   // one syllable: only result_out[0] (the one-input quirk)
@@ -122,6 +124,121 @@ __device__ __forceinline__ void fold_callback(const int32_t* meta, const float* 
     } else label = -1;
     conf = mx / seg_weight;
     seg_max = mx;                            // DB_entropies_seg of this model DB (ref prediction.js:154)
+}
+
+// ---- K6b on a batch: one wave per clip, classes on lanes, callbacks walked in order (ref prediction.js:86-169 with one model DB); P as
+// for fold_callback
+template <typename P>
+struct FoldParams {
+    uint32_t n_clips, C; double step_s;
+    const int32_t* meta; const uint32_t* row_off; const P* prob;
+    const int32_t* key_rank;                 // [C] array-index value of the label, or -1
+    int32_t* t_label; double* t_conf; int32_t* t_n; int32_t* t_local;   // per row: the callback that starts there (t_n = 0 elsewhere)
+    uint32_t* clip_cb;                       // [n_clips] callbacks per clip
+    double* clip_conf;                       // [n_clips][C]
+};
+
+template <typename P>
+__global__ void __launch_bounds__(256) fold_kernel(FoldParams<P> p) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t clip = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (clip >= p.n_clips) return;
+    const uint32_t r0 = p.row_off[clip], r1 = p.row_off[clip + 1];
+    const bool cls = (uint32_t)lane < p.C;
+    const int kr = cls ? p.key_rank[lane] : -1;
+    FoldAcc a{0.0, false, 0, 0};
+    uint32_t ncb = 0;
+    for (uint32_t r = r0; r < r1;) {
+        const uint32_t e = callback_end(p.meta, r, r1);
+        int label; double conf, seg_max;
+        fold_callback(p.meta, p.prob, p.C, p.step_s, lane, cls, kr, r, e, a, label, conf, seg_max);
+        if (lane == 0) { p.t_label[r] = label; p.t_conf[r] = conf; p.t_n[r] = (int32_t)(e - r); p.t_local[r] = (int32_t)ncb; }
+        for (uint32_t q = r + 1 + lane; q < e; q += 64) p.t_n[q] = 0;
+        ncb++;
+        r = e;
+    }
+    if (cls) p.clip_conf[(size_t)clip * p.C + lane] = a.acc_all;
+    if (lane == 0) p.clip_cb[clip] = ncb;
+}
+
+// callbacks per clip -> offsets (one workgroup of 1024 threads; returns the total to every thread)
+__device__ __forceinline__ uint32_t compact_offsets(uint32_t n_clips, const uint32_t* clip_cb, uint32_t* cb_off, uint32_t* s_part, uint32_t* s_base) {
+    const int tid = threadIdx.x;
+    if (tid == 0) *s_base = 0;
+    __syncthreads();
+    for (uint32_t c0 = 0; c0 < n_clips; c0 += 1024) {
+        const uint32_t c = c0 + tid;
+        const uint32_t v = c < n_clips ? clip_cb[c] : 0u;
+        s_part[tid] = v;
+        __syncthreads();
+        for (int o = 1; o < 1024; o <<= 1) {                       // inclusive scan (Hillis-Steele)
+            const uint32_t t = tid >= o ? s_part[tid - o] : 0u;
+            __syncthreads();
+            s_part[tid] += t;
+            __syncthreads();
+        }
+        if (c < n_clips) cb_off[c] = *s_base + s_part[tid] - v;
+        __syncthreads();
+        if (tid == 1023) *s_base += s_part[1023];
+        __syncthreads();
+    }
+    return *s_base;
+}
+
+// the offsets, then every callback's entry from the row it starts at; the count goes to the host's mapped word
+__global__ void __launch_bounds__(1024) fold_compact_kernel(uint32_t n_clips, const uint32_t* row_off, const int32_t* meta, const uint32_t* clip_cb,
+                                                            uint32_t* cb_off, const int32_t* t_label, const double* t_conf, const int32_t* t_n,
+                                                            const int32_t* t_local, int32_t* cb, int32_t* cb_label, double* cb_conf, uint32_t* host) {
+    __shared__ uint32_t s_part[1024];
+    __shared__ uint32_t s_base;
+    const int tid = threadIdx.x;
+    const uint32_t n_cb = compact_offsets(n_clips, clip_cb, cb_off, s_part, &s_base);
+    const uint32_t n_rows = row_off[n_clips];
+    __syncthreads();
+    for (uint32_t r = tid; r < n_rows; r += 1024) {
+        const int32_t nsyl = t_n[r];
+        if (nsyl <= 0) continue;
+        const int32_t clip = meta[(size_t)r * 8];
+        const uint32_t k = cb_off[clip] + (uint32_t)t_local[r];
+        write_callback(cb, k, clip, meta[(size_t)r * 8 + 1], r, nsyl);
+        cb_label[k] = t_label[r]; cb_conf[k] = t_conf[r];
+    }
+    if (tid == 0) host[0] = n_cb;
+}
+
+// ---- the same fold on a stream step: one wave per stream with the stream's carried fold.  Callbacks are written straight to their place
+// in the step's table (callback_starts); callbacks and the per-stream sums also go to the mapped pinned tables (callbacks below `cap`).
+struct StepFoldTables {
+    uint32_t cap;
+    int32_t* cb; int32_t* cb_label; double* cb_conf;                               // device: every callback of the step
+    int32_t* h_cb; int32_t* h_cb_label; double* h_cb_conf; double* h_conf; uint32_t* h_count;   // mapped pinned
+};
+template <typename P>
+__device__ __forceinline__ void fold_stream_step(const int32_t* meta, const P* prob, uint32_t C, double step_s, int lane, int kr, uint32_t s, uint32_t n,
+                                                 uint32_t r0, uint32_t r1, const CarriedFold& carried, bool start, const StepFoldTables& t) {
+    const bool cls = (uint32_t)lane < C;
+    const size_t sc = (size_t)s * C + lane;
+    FoldAcc a = load_fold(carried, s, sc, cls, start);
+    uint32_t k = callback_starts(meta, 0, r0, lane);
+    for (uint32_t r = r0; r < r1;) {
+        const int si = meta[(size_t)r * 8 + 1];
+        const uint32_t e = callback_end(meta, r, r1);
+        int label; double conf, seg_max;
+        fold_callback(meta, prob, C, step_s, lane, cls, kr, r, e, a, label, conf, seg_max);
+        if (lane == 0) {
+            write_callback(t.cb, k, (int32_t)s, si, r, (int32_t)(e - r));
+            t.cb_label[k] = label; t.cb_conf[k] = conf;
+            if (k < t.cap) {
+                write_callback(t.h_cb, k, (int32_t)s, si, r, (int32_t)(e - r));
+                t.h_cb_label[k] = label; t.h_cb_conf[k] = conf;
+            }
+        }
+        k++;
+        r = e;
+    }
+    store_fold(carried, s, sc, cls, lane, a);
+    if (cls) t.h_conf[sc] = a.acc_all;
+    if (lane == 0 && s == n - 1) t.h_count[0] = k;
 }
 
 // ---- an ensemble (ref prediction.js:47-169 with several model DBs in available_DBs).  Besides what one model's fold writes, a callback

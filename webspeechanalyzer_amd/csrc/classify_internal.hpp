@@ -2,6 +2,7 @@
 // objects), classify_batch.hip (a batch's fold and its entry points) and classify_stream.hip (the fold inside a stream step).
 // Nothing here is exported.
 #pragma once
+#include <vector>
 #include "host_plan.hpp"
 
 namespace wsa_classify {
@@ -78,6 +79,15 @@ wsa_status alloc_failed(wsa_ctx* ctx, T* half_built) {
     const wsa_status st = alloc_failed(ctx);
     free_on_device(half_built);
     return st;
+}
+
+// a stream step beyond the D2H window: one of its tables from the device into x
+template <typename T>
+inline wsa_status fetch_table(wsa_ctx* ctx, std::vector<T>& x, const T* dev, size_t count, const T** out) {
+    x.resize(count + 1);
+    if (count) HIP_TRY(ctx, hipMemcpy(x.data(), dev, count * sizeof(T), hipMemcpyDeviceToHost));
+    *out = x.data();
+    return WSA_OK;
 }
 
 // What pairing a model or an ensemble with a batch or with streams refuses alike: a level other than 5 or 13 (entry == NULL: the caller has

@@ -12,15 +12,14 @@ using namespace wsa_classify;
 
 namespace {
 
-// ---- K6b on a stream step: one wave per stream, classes on lanes, with the stream's carried fold (CarriedFold).  Callbacks are written
-// straight to their place in the step's table (callback_starts).  Probabilities, callbacks and the per-stream sums go to the mapped
-// pinned buffers (rows / callbacks below `cap`).
+// ---- K6b on a stream step: one wave per stream pushes its rows' probabilities to the mapped pinned table (rows below the D2H window)
+// and, at level 13, folds them with the stream's carried fold (fold_stream_step, classify_fold.hpp).
 struct StreamClsParams {
-    uint32_t n, C, cap; int fold; double step_s;
+    uint32_t n, C; int fold; double step_s;
     const int32_t* meta; const uint32_t* row_off; const float* prob; const int32_t* key_rank; const uint32_t* bits;
     CarriedFold carried;
-    int32_t* cb; int32_t* cb_label; double* cb_conf;                               // device: every callback of the step
-    float* h_prob; int32_t* h_cb; int32_t* h_cb_label; double* h_cb_conf; double* h_conf; uint32_t* h_count;   // mapped pinned
+    StepFoldTables t;
+    float* h_prob;                                                                 // mapped pinned
 };
 
 // the probabilities of rows r0 .. r1 - 1 below `cap` (the D2H window), C per row, to the pinned table
@@ -34,32 +33,9 @@ __global__ void __launch_bounds__(256) stream_classes_kernel(StreamClsParams p) 
     const uint32_t s = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (s >= p.n) return;
     const uint32_t r0 = p.row_off[s], r1 = p.row_off[s + 1];
-    push_prob(p.h_prob, p.prob, r0, r1, p.cap, p.C, lane);
+    push_prob(p.h_prob, p.prob, r0, r1, p.t.cap, p.C, lane);
     if (!p.fold) return;
-    const bool cls = (uint32_t)lane < p.C;
-    const int kr = cls ? p.key_rank[lane] : -1;
-    const size_t sc = (size_t)s * p.C + lane;
-    FoldAcc a = load_fold(p.carried, s, sc, cls, p.bits[s] & 1u);
-    uint32_t k = callback_starts(p.meta, 0, r0, lane);
-    for (uint32_t r = r0; r < r1;) {
-        const int si = p.meta[(size_t)r * 8 + 1];
-        const uint32_t e = callback_end(p.meta, r, r1);
-        int label; double conf, seg_max;
-        fold_callback(p.meta, p.prob, p.C, p.step_s, lane, cls, kr, r, e, a, label, conf, seg_max);
-        if (lane == 0) {
-            write_callback(p.cb, k, (int32_t)s, si, r, (int32_t)(e - r));
-            p.cb_label[k] = label; p.cb_conf[k] = conf;
-            if (k < p.cap) {
-                write_callback(p.h_cb, k, (int32_t)s, si, r, (int32_t)(e - r));
-                p.h_cb_label[k] = label; p.h_cb_conf[k] = conf;
-            }
-        }
-        k++;
-        r = e;
-    }
-    store_fold(p.carried, s, sc, cls, lane, a);
-    if (cls) p.h_conf[sc] = a.acc_all;
-    if (lane == 0 && s == p.n - 1) p.h_count[0] = k;
+    fold_stream_step(p.meta, p.prob, p.C, p.step_s, lane, (uint32_t)lane < p.C ? p.key_rank[lane] : -1, s, p.n, r0, r1, p.carried, p.bits[s] & 1u, p.t);
 }
 
 // ---- K6b-e on a stream step: one wave per (stream, member) folds with that pair's carried accumulator and writes the member's entries
@@ -148,15 +124,6 @@ __global__ void __launch_bounds__(256) stream_decide_kernel(StreamEnsParams p) {
     p.h.clip_min_db[s] = min_db;
 }
 
-// a step beyond the D2H window: one of its tables from the device into x
-template <typename T>
-wsa_status fetch_table(wsa_ctx* ctx, std::vector<T>& x, const T* dev, size_t count, const T** out) {
-    x.resize(count + 1);
-    if (count) HIP_TRY(ctx, hipMemcpy(x.data(), dev, count * sizeof(T), hipMemcpyDeviceToHost));
-    *out = x.data();
-    return WSA_OK;
-}
-
 // the carried fold of n streams with C classes each, zeroed
 bool alloc_carried(wsa::DevArena& A, CarriedFold& f, size_t n, size_t C) {
     return A.alloc(&f.acc_all, n * C, true) && A.alloc(&f.in_all, n * C, true) && A.alloc(&f.first, n * C, true) && A.alloc(&f.stamp, n, true);
@@ -213,11 +180,11 @@ wsa_status wsa_scls_enqueue(wsa_scls* c, hipStream_t s) {
     launch_classify(m, cls_params(m, v.d_feat, 0, v.d_totals, c->d_prob), v.rows_cap < v.d2h_rows ? v.rows_cap : v.d2h_rows, s, 1);
     HIP_TRY(v.ctx, hipGetLastError());
     StreamClsParams p{};
-    p.n = v.n_streams; p.C = c->C; p.cap = v.d2h_rows; p.fold = v.level == 13 ? 1 : 0; p.step_s = v.ctx->cfg.window_step / 1e3;
+    p.n = v.n_streams; p.C = c->C; p.fold = v.level == 13 ? 1 : 0; p.step_s = v.ctx->cfg.window_step / 1e3;
     p.meta = v.d_meta; p.row_off = v.d_row_off; p.prob = c->d_prob; p.key_rank = m->d_key_rank; p.bits = v.d_bits;
     p.carried = c->carried;
-    p.cb = c->d_cb; p.cb_label = c->d_cb_label; p.cb_conf = c->d_cb_conf;
-    p.h_prob = c->h_prob_dev; p.h_cb = c->h_cb_dev; p.h_cb_label = c->h_cb_label_dev; p.h_cb_conf = c->h_cb_conf_dev; p.h_conf = c->h_conf_dev; p.h_count = c->h_count_dev;
+    p.t = StepFoldTables{v.d2h_rows, c->d_cb, c->d_cb_label, c->d_cb_conf, c->h_cb_dev, c->h_cb_label_dev, c->h_cb_conf_dev, c->h_conf_dev, c->h_count_dev};
+    p.h_prob = c->h_prob_dev;
     hipLaunchKernelGGL(stream_classes_kernel, dim3((v.n_streams + 3) / 4), dim3(256), 0, s, p);
     HIP_TRY(v.ctx, hipGetLastError());
     return WSA_OK;

@@ -1,5 +1,7 @@
 // knn.hip — K9: the app's ml5 KNN classifier (specification KN-1) on the device: the store object, knn_add_kernel,
-// knn_classify_kernel and the wsa_knn_* / wsa_batch_knn* entry points (include/wsa.h "KNN classifier").
+// knn_classify_kernel and the wsa_knn_* / wsa_batch_knn* entry points (include/wsa.h "KNN classifier"); and K9s, the same selection with
+// the store split over workgroups for the few rows of a stream step (knn_partial_kernel, knn_merge_kernel; knn_fold.hip puts them into
+// the step).
 //
 // Stands in for ref src/neuralmodel.js:729-837 (train_knn): ml5.KNNClassifier().addExample(features, label) over a labelled feature DB and
 // classify(features, 10, ...) — in dist/ml5.min.js the tfjs knn-classifier: rows normalised to unit length, sim = train . q as one f32
@@ -13,12 +15,14 @@
 // result does not depend on tile shape or grid.
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
-#include "host_plan.hpp"
+#include "knn_internal.hpp"
 #include "wave_ops.hpp"
 
 using wsa_api::fail;
+using namespace wsa_knn_detail;
 
 namespace {
 
@@ -92,15 +96,6 @@ __global__ void __launch_bounds__(256) knn_rank_kernel(const int32_t* __restrict
     if (r < n) rank[r] = (int32_t)s_off[cls[r]] + within[r];
 }
 
-struct KnnParams {
-    const float* rows; const int32_t* cls; const int32_t* rank; uint32_t n_store;
-    const double* feat; uint32_t n_rows; const uint32_t* d_n_rows;          // rows = *d_n_rows when set (a batch's count, on the device)
-    int width, stride, nan_slot;             // features read per row; doubles from one row to the next; nan_slot >= 0: a row whose slot
-                                             // nan_slot is not 0 (level 12: uncmin threw) gets label -1 and NaN in every other output
-    int C; uint32_t k, k_eff;                // k_eff = min(k, n_store): ml5 clamps k to the number of examples
-    int32_t* label; double* conf; int32_t* nbr; float* sim;                 // any may be NULL
-};
-
 // One candidate into one query's list (entry j on lane j, best first).  Order: the larger key, then the lower rank; ranks are unique, so
 // the order is total and the list does not depend on the order candidates arrive in.
 __device__ __forceinline__ void knn_insert(float* s_key, int* s_rk, int* s_ix, float* s_thr, int* s_cnt, int q, float ck, int cidx, int crank, int k_eff, int lane) {
@@ -121,13 +116,35 @@ __device__ __forceinline__ void knn_insert(float* s_key, int* s_rk, int* s_ix, f
     wsa::wsync();
 }
 
+// What a query's finished list becomes (lane j holds entry j): votes, confidences and the label (ml5 calculateTopClass: the first class, in
+// key order, whose confidence exceeds a maximum that starts at 0), and the neighbours in selection order
+__device__ __forceinline__ void knn_epilogue(const KnnParams& p, uint32_t q, bool thrown, float key, int idx, int lane) {
+    const int k_eff = (int)p.k_eff;
+    const float NEG_INF = -__builtin_huge_valf();
+    const bool in = lane < k_eff && !thrown;
+    const int c = in ? p.cls[idx] : -1;
+    int votes = 0;
+    for (int j = 0; j < k_eff; j++) votes += __shfl(c, j) == lane ? 1 : 0;
+    const uint32_t best = wsa::wave_max_u32(lane < p.C ? ((uint32_t)votes << 6) | (uint32_t)(63 - lane) : 0u);
+    if (p.label && lane == 0) p.label[q] = thrown ? -1 : 63 - (int)(best & 63u);
+    if (p.conf && lane < p.C) p.conf[(size_t)q * p.C + lane] = thrown ? __longlong_as_double(0x7ff8000000000000ll) : (double)votes / (double)k_eff;
+    if ((uint32_t)lane < p.k) {
+        if (p.nbr) p.nbr[(size_t)q * p.k + lane] = in ? idx : -1;
+        if (p.sim) p.sim[(size_t)q * p.k + lane] = in && key != NEG_INF ? key : __int_as_float(0x7fc00000);
+    }
+}
+
 // mfma_f32_16x16x4f32 as in K6 / K7: lane l holds A[row l&15][k l>>4], B[k l>>4][col l&15]; D col = l&15, row = 4 (l>>4) + i.  Here A
 // = 16 query rows of the wave, B = 16 train rows of the tile, and the k index of MFMA 2 jj + m is feature 8 jj + 2 (l>>4) + m on both
 // sides (a fixed permutation of the sum's terms), so a lane's B operands of two MFMAs are one 8-byte LDS read.  An MFMA is a k-ordered
 // chain of f32 fused multiply-adds; the steps of 8 features alternate between two accumulators that are added at the end, which halves the
 // chain's length (and its rounding error) at the price of four registers per block.
-template <int WP>
-__global__ void __launch_bounds__(KNN_THREADS) knn_classify_kernel(KnnParams p) {
+//
+// SPLIT (K9s, knn_partial_kernel): blockIdx.y is a slice of the store, a contiguous run of whole tiles.  The workgroup selects within its
+// slice only and leaves each query's list in the scratch table for knn_merge_kernel; tiles, fragments, the chain and the list logic are
+// the code below either way, so a (query, train row) pair has the same similarity bits in both kernels.
+template <int WP, bool SPLIT>
+__device__ __forceinline__ void knn_body(const KnnParams& p) {
     extern __shared__ __attribute__((aligned(16))) float s_mem[];
     constexpr int S = knn_stride(WP), V4 = WP / 4, NV = (KNN_T * V4 + KNN_THREADS - 1) / KNN_THREADS;
     float* s_tile = s_mem;
@@ -139,11 +156,19 @@ __global__ void __launch_bounds__(KNN_THREADS) knn_classify_kernel(KnnParams p) 
     int* s_flag = s_cnt + KNN_QT;
     int* s_trank = s_flag + KNN_QT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t nq = p.d_n_rows ? *p.d_n_rows : p.n_rows;
+    uint32_t nq = p.d_n_rows ? *p.d_n_rows : p.n_rows;
     const uint32_t n = p.n_store;
     const int k_eff = (int)p.k_eff;
     const float NEG_INF = -__builtin_huge_valf(), POS_INF = __builtin_huge_valf();
-    for (uint32_t qt = blockIdx.x; (uint64_t)qt * KNN_QT < nq; qt += gridDim.x) {
+    // the slice's rows t_lo .. t_hi - 1 (the whole store for K9); an empty slice has nothing to say
+    uint32_t t_lo = 0, t_hi = n;
+    if constexpr (SPLIT) {
+        const uint64_t per = (uint64_t)p.tiles_per_slice * KNN_T, lo = (uint64_t)blockIdx.y * per;
+        if (lo >= n) return;
+        t_lo = (uint32_t)lo; t_hi = lo + per < n ? (uint32_t)(lo + per) : n;
+        if (p.q_limit && nq > p.q_limit) nq = p.q_limit;
+    }
+    for (uint32_t qt = blockIdx.x + p.qt0; (uint64_t)qt * KNN_QT < nq; qt += gridDim.x) {
         const uint32_t q0 = qt * KNN_QT;
         __syncthreads();
         // the tile's queries as unit rows (one owner per row); a row past the end or thrown takes no part in the selection
@@ -178,8 +203,8 @@ __global__ void __launch_bounds__(KNN_THREADS) knn_classify_kernel(KnnParams p) 
             }
             if (tid < KNN_T) pr = t0 + (uint32_t)tid < n ? p.rank[t0 + tid] : 0;
         };
-        fetch(0);
-        for (uint32_t t0 = 0; t0 < n; t0 += KNN_T) {
+        fetch(t_lo);
+        for (uint32_t t0 = t_lo; t0 < t_hi; t0 += KNN_T) {
             __syncthreads();                                   // the queries' fragments, or the previous tile, have been read
 #pragma unroll
             for (int v = 0; v < NV; v++) {
@@ -189,7 +214,7 @@ __global__ void __launch_bounds__(KNN_THREADS) knn_classify_kernel(KnnParams p) 
             }
             if (tid < KNN_T) s_trank[tid] = pr;
             __syncthreads();
-            if (t0 + KNN_T < n) fetch(t0 + KNN_T);
+            if (t0 + KNN_T < t_hi) fetch(t0 + KNN_T);
             f32x4 acc[KNN_T / 16], odd[KNN_T / 16];            // two chains per block of 16 train rows: the even and the odd steps of 8 features
 #pragma unroll
             for (int cb = 0; cb < KNN_T / 16; cb++) acc[cb] = odd[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -234,59 +259,73 @@ __global__ void __launch_bounds__(KNN_THREADS) knn_classify_kernel(KnnParams p) 
                 for (int i = 0; i < 4; i++) thr[i] = s_thr[wave * 16 + 4 * (lane >> 4) + i];
             }
         }
-        // votes, confidences and the label of the wave's 16 queries (ml5 calculateTopClass: the first class, in key order, whose
-        // confidence exceeds a maximum that starts at 0), and the neighbours in selection order
         wsa::wsync();
         for (int r = 0; r < 16; r++) {
             const int ql = wave * 16 + r;
             const uint32_t q = q0 + (uint32_t)ql;
             if (q >= nq) break;
-            const bool thrown = s_flag[ql] != 0;
-            const bool in = lane < k_eff && !thrown;
             const float key = s_key[ql * WSA_KNN_MAX_K + lane];
             const int idx = s_ix[ql * WSA_KNN_MAX_K + lane];
-            const int c = in ? p.cls[idx] : -1;
-            int votes = 0;
-            for (int j = 0; j < k_eff; j++) votes += __shfl(c, j) == lane ? 1 : 0;
-            const uint32_t best = wsa::wave_max_u32(lane < p.C ? ((uint32_t)votes << 6) | (uint32_t)(63 - lane) : 0u);
-            if (p.label && lane == 0) p.label[q] = thrown ? -1 : 63 - (int)(best & 63u);
-            if (p.conf && lane < p.C) p.conf[(size_t)q * p.C + lane] = thrown ? __longlong_as_double(0x7ff8000000000000ll) : (double)votes / (double)k_eff;
-            if ((uint32_t)lane < p.k) {
-                if (p.nbr) p.nbr[(size_t)q * p.k + lane] = in ? idx : -1;
-                if (p.sim) p.sim[(size_t)q * p.k + lane] = in && key != NEG_INF ? key : __int_as_float(0x7fc00000);
+            if constexpr (SPLIT) {
+                const size_t at = (size_t)q * p.slices + blockIdx.y;
+                const int cnt = s_cnt[ql];
+                if (lane < cnt) { p.pt_key[at * p.k + lane] = key; p.pt_rank[at * p.k + lane] = s_rk[ql * WSA_KNN_MAX_K + lane]; p.pt_idx[at * p.k + lane] = idx; }
+                if (lane == 0) p.pt_cnt[at] = cnt;
+            } else {
+                knn_epilogue(p, q, s_flag[ql] != 0, key, idx, lane);
             }
         }
     }
 }
 
+template <int WP>
+__global__ void __launch_bounds__(KNN_THREADS) knn_classify_kernel(KnnParams p) { knn_body<WP, false>(p); }
+template <int WP>
+__global__ void __launch_bounds__(KNN_THREADS) knn_partial_kernel(KnnParams p) { knn_body<WP, true>(p); }
+
+// K9s, the merge: one wave per query row below q_limit.  The partial lists of the query's slices go through the same list (knn_insert:
+// the order is total, so neither the split nor the order the slices arrive in matters), best first each, then K9's epilogue.  A slice
+// without rows was never written and is not read; neither is the list of a thrown row.
+__global__ void __launch_bounds__(256) knn_merge_kernel(KnnParams p) {
+    __shared__ float s_key[4 * WSA_KNN_MAX_K], s_thr[4];
+    __shared__ int s_rk[4 * WSA_KNN_MAX_K], s_ix[4 * WSA_KNN_MAX_K], s_cnt[4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t nq = p.d_n_rows ? *p.d_n_rows : p.n_rows;
+    if (p.q_limit && nq > p.q_limit) nq = p.q_limit;
+    const int k_eff = (int)p.k_eff;
+    const uint64_t per = (uint64_t)p.tiles_per_slice * KNN_T;
+    for (uint32_t q = blockIdx.x * 4 + w; q < nq; q += gridDim.x * 4) {
+        const bool thrown = p.nan_slot >= 0 && p.feat[(size_t)q * p.stride + p.nan_slot] != 0.0;
+        if (lane == 0) { s_cnt[w] = 0; s_thr[w] = -__builtin_huge_valf(); }
+        wsa::wsync();
+        for (uint32_t sl = 0; !thrown && sl < p.slices && (uint64_t)sl * per < p.n_store; sl++) {
+            const size_t at = (size_t)q * p.slices + sl;
+            const int cnt = p.pt_cnt[at];
+            const float ck = lane < cnt ? p.pt_key[at * p.k + lane] : 0.f;
+            const int cr = lane < cnt ? p.pt_rank[at * p.k + lane] : 0, ci = lane < cnt ? p.pt_idx[at * p.k + lane] : 0;
+            uint64_t m = __ballot(lane < cnt && ck >= s_thr[w]);
+            while (m) {
+                const int l = __ffsll((unsigned long long)m) - 1;
+                m &= m - 1;
+                knn_insert(s_key, s_rk, s_ix, s_thr, s_cnt, w, __shfl(ck, l), __shfl(ci, l), __shfl(cr, l), k_eff, lane);
+            }
+            wsa::wsync();
+        }
+        knn_epilogue(p, q, thrown, s_key[w * WSA_KNN_MAX_K + lane], s_ix[w * WSA_KNN_MAX_K + lane], lane);
+        wsa::wsync();
+    }
+}
+
 }  // namespace
-
-struct wsa_knn {
-    wsa_ctx* ctx = nullptr;
-    int width = 0, wp = 0, C = 0;
-    uint32_t cap = 0, count = 0;
-    float* d_rows = nullptr;
-    int32_t *d_cls = nullptr, *d_within = nullptr, *d_rank = nullptr;
-    uint32_t *d_class_count = nullptr, *d_bad = nullptr;
-    wsa::DevArena mem;
-};
-
-// the KNN tables of one batch (the first wsa_batch_knn allocates them)
-struct wsa_kcls {
-    int device = 0;
-    uint32_t cap_rows = 0, cap_c = 0, cap_k = 0;
-    int32_t *d_label = nullptr, *d_nbr = nullptr; double* d_conf = nullptr; float* d_sim = nullptr;
-    const wsa_knn* knn = nullptr; uint32_t k = 0, k_eff = 0, reruns = 0; int level = 0;
-    wsa::DevArena mem;
-};
 
 void wsa_kcls_free(wsa_kcls* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
+    wsa_kfold_free(c->fold);
     delete c;
 }
 
-namespace {
+namespace wsa_knn_detail {
 
 void launch_knn(const wsa_knn* kn, const KnnParams& p, uint32_t rows_cap, hipStream_t s) {
     const uint64_t tiles = ((uint64_t)rows_cap + KNN_QT - 1) / KNN_QT;
@@ -312,6 +351,50 @@ wsa_status knn_refusal(const wsa_knn* kn, uint32_t k) {
     if (!kn->count) return fail(kn->ctx, WSA_ERR_INVALID, "the KNN store has no examples yet");
     return WSA_OK;
 }
+
+// ---- K9s on the host.  The slice count S for a window of query rows: as many slices as give every CU two workgroups (K9's LDS lets two
+// share a CU) over the window's query tiles, S = ceil(2 n_cu / query tiles) — but no slice shorter than KNN_SPLIT_MIN_TILES store tiles
+// (below that a workgroup's fixed cost, its queries' unit rows and its list write, outweighs its share of the store), no more than
+// WSA_KNN_SPLIT_MAX_SLICES (the merge walks a query's slices one after the other), and no more than the scratch bound
+// WSA_KNN_SPLIT_SCRATCH_BYTES allows at (12 k + 4) bytes per (query row, slice).
+constexpr uint32_t KNN_SPLIT_MIN_TILES = 4;
+
+uint32_t knn_split_slices(const wsa_knn* kn, uint32_t window, uint32_t k) {
+    const uint64_t q_tiles = ((uint64_t)(window ? window : 1) + KNN_QT - 1) / KNN_QT, tiles = ((uint64_t)kn->count + KNN_T - 1) / KNN_T;
+    const uint64_t n_cu = kn->ctx->n_cu > 0 ? kn->ctx->n_cu : 256;
+    uint64_t S = (2 * n_cu + q_tiles - 1) / q_tiles;
+    const uint64_t by_store = (tiles + KNN_SPLIT_MIN_TILES - 1) / KNN_SPLIT_MIN_TILES;
+    const uint64_t by_scratch = (uint64_t)WSA_KNN_SPLIT_SCRATCH_BYTES / ((uint64_t)(window ? window : 1) * (12ull * k + 4ull));
+    if (S > by_store) S = by_store;
+    if (S > WSA_KNN_SPLIT_MAX_SLICES) S = WSA_KNN_SPLIT_MAX_SLICES;
+    if (S > by_scratch) S = by_scratch;
+    return S ? (uint32_t)S : 1u;
+}
+
+bool knn_split_alloc(wsa::DevArena& A, const wsa_knn* kn, uint32_t window, uint32_t k, uint32_t slices, KnnSplit& out) {
+    const uint32_t tiles = (uint32_t)(((uint64_t)kn->count + KNN_T - 1) / KNN_T);
+    out.window = window; out.slices = slices ? slices : knn_split_slices(kn, window, k);
+    out.tiles_per_slice = (tiles + out.slices - 1) / out.slices;
+    if (!out.tiles_per_slice) out.tiles_per_slice = 1;
+    const size_t pairs = (size_t)(window ? window : 1) * out.slices;
+    return A.alloc(&out.key, pairs * k) && A.alloc(&out.rank, pairs * k) && A.alloc(&out.idx, pairs * k) && A.alloc(&out.cnt, pairs);
+}
+
+void launch_knn_split(const wsa_knn* kn, KnnParams p, const KnnSplit& sp, hipStream_t s) {
+    p.slices = sp.slices; p.tiles_per_slice = sp.tiles_per_slice; p.q_limit = sp.window;
+    p.pt_key = sp.key; p.pt_rank = sp.rank; p.pt_idx = sp.idx; p.pt_cnt = sp.cnt;
+    const uint32_t q_tiles = (sp.window + KNN_QT - 1) / KNN_QT;
+    const dim3 grid(q_tiles ? q_tiles : 1, sp.slices);
+    const size_t lds = knn_lds_bytes(kn->wp);
+    if (kn->wp == 24) hipLaunchKernelGGL(knn_partial_kernel<24>, grid, dim3(KNN_THREADS), lds, s, p);
+    else if (kn->wp == 56) hipLaunchKernelGGL(knn_partial_kernel<56>, grid, dim3(KNN_THREADS), lds, s, p);
+    else hipLaunchKernelGGL(knn_partial_kernel<264>, grid, dim3(KNN_THREADS), lds, s, p);
+    hipLaunchKernelGGL(knn_merge_kernel, dim3((sp.window + 3) / 4 ? (sp.window + 3) / 4 : 1), dim3(256), 0, s, p);
+}
+
+}  // namespace wsa_knn_detail
+
+namespace {
 
 // the rows a batch hands K9 (the rule of wsa_batch_classify): the row table (levels 5 and 13; level 12 at its stride of WSA_NFEAT, slots
 // 0 .. 22, slot 23 the throw mark) or the utterance table (level 11); both counts sit on the device
@@ -350,9 +433,10 @@ wsa_status wsa_knn_create(wsa_ctx* ctx, int32_t width, int32_t n_classes, uint32
     wsa::DevArena& A = kn->mem;
     const size_t lds = knn_lds_bytes(kn->wp);
     hipError_t e = hipSuccess;
-    if (kn->wp == 24) e = hipFuncSetAttribute(reinterpret_cast<const void*>(knn_classify_kernel<24>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    else if (kn->wp == 56) e = hipFuncSetAttribute(reinterpret_cast<const void*>(knn_classify_kernel<56>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    else e = hipFuncSetAttribute(reinterpret_cast<const void*>(knn_classify_kernel<264>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const auto allow_lds = [&](const void* kernel) { if (e == hipSuccess) e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); };
+    if (kn->wp == 24) { allow_lds(reinterpret_cast<const void*>(knn_classify_kernel<24>)); allow_lds(reinterpret_cast<const void*>(knn_partial_kernel<24>)); }
+    else if (kn->wp == 56) { allow_lds(reinterpret_cast<const void*>(knn_classify_kernel<56>)); allow_lds(reinterpret_cast<const void*>(knn_partial_kernel<56>)); }
+    else { allow_lds(reinterpret_cast<const void*>(knn_classify_kernel<264>)); allow_lds(reinterpret_cast<const void*>(knn_partial_kernel<264>)); }
     const bool ok = e == hipSuccess && A.alloc(&kn->d_rows, (size_t)capacity * kn->wp) && A.alloc(&kn->d_cls, (size_t)capacity) && A.alloc(&kn->d_within, (size_t)capacity)
                     && A.alloc(&kn->d_rank, (size_t)capacity) && A.alloc(&kn->d_class_count, (size_t)WSA_MODEL_MAX_CLASSES, true) && A.alloc(&kn->d_bad, 1, true);
     if (!ok) {
@@ -492,6 +576,38 @@ wsa_status wsa_batch_copy_knn(wsa_batch* b, void* stream, int32_t* label, double
     if (nbr) HIP_TRY(ctx, hipMemcpyAsync(nbr, r.d_nbr, R * r.k * sizeof(int32_t), hipMemcpyDefault, s));
     if (sim) HIP_TRY(ctx, hipMemcpyAsync(sim, r.d_sim, R * r.k * sizeof(float), hipMemcpyDefault, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
+    return WSA_OK;
+}
+
+// ---- test access (not part of include/wsa.h; in the manner of debug.hip): K9s over n_rows dense device rows with `slices` slices of
+// the store (0: the rule's), outputs as wsa_knn_classify_rows.  Only enqueues; the scratch table is kept with the store and allocated at
+// the first call or when a call needs a larger one (`stream` is drained first then).  With n_rows = 0 the kernels are launched all the
+// same (one query tile, no row): what a stream step without rows runs.
+wsa_status wsa_debug_knn_split(const wsa_knn* kn, const double* d_feat, uint32_t n_rows, uint32_t k, uint32_t slices, int32_t* d_label, double* d_conf,
+                               int32_t* d_nbr, float* d_sim, void* stream) {
+    if (!kn) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = kn->ctx;
+    if (const wsa_status st = knn_refusal(kn, k)) return st;
+    if (n_rows && !d_feat) return fail(ctx, WSA_ERR_INVALID, "null feature pointer");
+    if (slices > WSA_KNN_SPLIT_MAX_SLICES || (uint64_t)slices * n_rows * (12ull * k + 4ull) > WSA_KNN_SPLIT_SCRATCH_BYTES)
+        return fail(ctx, WSA_ERR_INVALID, std::to_string(slices) + " slices for " + std::to_string(n_rows) + " rows: K9s takes at most " + std::to_string(WSA_KNN_SPLIT_MAX_SLICES)
+                                          + " slices and " + std::to_string(WSA_KNN_SPLIT_SCRATCH_BYTES) + " bytes of scratch");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    wsa_knn::DebugSplit& d = kn->debug_split;
+    const uint32_t S = slices ? slices : knn_split_slices(kn, n_rows, k);
+    if (!d.mem || d.sp.window < n_rows || d.sp.slices != S || d.k != k || d.count != kn->count) {
+        HIP_TRY(ctx, hipStreamSynchronize(s));                 // an earlier call may still use the table that goes
+        d.mem.reset(new wsa::DevArena());
+        d.k = k; d.count = kn->count;
+        if (!knn_split_alloc(*d.mem, kn, n_rows, k, S, d.sp)) { d.mem.reset(); return fail(ctx, WSA_ERR_HIP, std::string("device allocation failed: ") + hipGetErrorString(hipGetLastError())); }
+    }
+    KnnSplit sp = d.sp;
+    sp.window = n_rows;
+    KnnParams p = knn_params(kn, d_feat, n_rows, nullptr, k);
+    p.label = d_label; p.conf = d_conf; p.nbr = d_nbr; p.sim = d_sim;
+    launch_knn_split(kn, p, sp, s);
+    HIP_TRY(ctx, hipGetLastError());
     return WSA_OK;
 }
 

@@ -153,6 +153,7 @@ function contexts_for(nat, devs) {
   return ctx_cache.ctxs;
 }
 function drop_contexts(nat) {
+  for (const c of ctx_cache.ctxs) knn_natives.delete(c);
   for (const c of ctx_cache.ctxs) { try { nat.destroy(c); } catch (e) { /* still in use by a failed launch's stragglers: left to process exit */ } }
   ctx_cache = { key: null, ctxs: [] };
 }
@@ -389,6 +390,39 @@ function predictKnn(knn, rows, k) {
   if (!knn || typeof knn.classifyMultiple !== 'function' || !Array.isArray(rows)) throw 'predictKnn(knn, [[numbers]], k)';
   return knn.classifyMultiple(rows, k === undefined ? 10 : k);
 }
+// setPredictionKnn(knn | null, k, on_prediction): as setPredictionModel with a KNNClassifier of 53-feature rows in the model's place.  Every level-13
+// LaunchBatch / LaunchBatches launch and every StreamOpen set opened from here on classifies its syllables with the store's k nearest rows (K9 / K9s)
+// and folds them as the app folds a network's result (specification KN-2: votes / k per label, ties in class order), calling
+//     on_prediction(si, [label, confidence], clip_or_stream_index, per_syllable)
+// in setPredictionModel's shape; `meters` is one {label: Label_conf_all} per clip / stream.  The rows are those the classifier holds when a
+// launch starts or a stream set opens (each context gets its own device copy of them).  setPredictionKnn and setPredictionModel(s) replace each other.
+const knn_natives = new Map();          // context -> {knn, n, store}: the device copy of a prediction KNN's rows on that context
+function setPredictionKnn(knn, k, on_prediction) {
+  if (knn === null || knn === undefined) { prediction = null; return; }
+  if (typeof knn !== 'object' || typeof knn.classifyMultiple !== 'function' || !Array.isArray(knn.labels)) throw 'setPredictionKnn(knn | null, k, on_prediction): knn is a KNNClassifier';
+  if (knn.width !== 53) throw 'setPredictionKnn: the store holds rows of ' + knn.width + ' features; live prediction folds the 53-feature syllable rows of output_level 13';
+  if (!Number.isInteger(k) || k < 1 || k > 64) throw 'setPredictionKnn: k must be 1 .. 64, got ' + String(k);
+  if (!knn.store) throw 'setPredictionKnn: the KNN store was released';
+  if (!knn.labels.length) throw 'setPredictionKnn: There is no example in any class';
+  if (typeof on_prediction !== 'function') throw 'setPredictionKnn(knn | null, k, on_prediction)';
+  prediction = { knn, k, on_prediction, get model() { return { labels: knn.names }; } };
+}
+function knn_store_on(nat, ctx, knn) {   // the prediction KNN's rows as a store on one context (made at its first use there, again when rows were added)
+  if (!knn.store) throw 'the prediction KNN store was released';
+  const e = knn_natives.get(ctx), n = knn.labels.length;
+  if (e && e.knn === knn && e.n === n) return e.store;
+  if (e) { knn_natives.delete(ctx); nat.knnDestroy(e.store); }
+  const K = require('./knn.js');
+  const store = nat.knnCreate(ctx, 53, K.MAX_CLASSES, n);
+  nat.knnAdd(store, K.pack(knn.rows, 53, 'KNN'), knn.index);
+  knn_natives.set(ctx, { knn, n, store });
+  return store;
+}
+// K9 + KN-2 over the rows of the batch a context has just finished: the tables predict_after and meters_of read, under a model's names
+function knn_fold_into(nat, ctx, res, pred) {
+  const t = nat.batchKnn(ctx, knn_store_on(nat, ctx, pred.knn), pred.k), f = nat.batchKnnFold(ctx);
+  res.prob = t.conf; res.nClasses = t.nClasses; res.cb = f.cb; res.cbLabel = f.cbLabel; res.cbConf = f.cbConf; res.clipConf = f.clipConf;
+}
 function saveModel(handle, dir) {
   if (!handle || !handle.spec) throw 'saveModel(handle, dir)';
   require('./trainmodel.js').saveModelFiles(handle.spec, dir);
@@ -415,10 +449,11 @@ function setPredictionModels(handles, on_prediction) {
 function release_models() {           // shutdown(): the native models go with their contexts; the handles are refused from here on
   for (const h of loaded_models) { h.released = true; h.natives.clear(); }
   loaded_models.clear();
+  knn_natives.clear();                  // (the stores went with their contexts)
   prediction = null;
 }
 function model_on(nat, ctx) {         // the native model of the prediction model on one context (created at its first use there)
-  if (!prediction || settings.output_level !== 13) return undefined;
+  if (!prediction || prediction.knn || settings.output_level !== 13) return undefined;
   const one = (h) => {
     if (h.released) throw 'the prediction model was released (shutdown())';
     let m = h.natives.get(ctx);
@@ -427,12 +462,15 @@ function model_on(nat, ctx) {         // the native model of the prediction mode
   };
   return prediction.models ? prediction.models.map(one) : one(prediction.model);      // (an array: the addon classifies with the ensemble of them)
 }
-function forget_natives(pred, ctx) { for (const h of pred.models || [pred.model]) h.natives.delete(ctx); }
+function forget_natives(pred, ctx) {
+  if (pred.knn) { knn_natives.delete(ctx); return; }
+  for (const h of pred.models || [pred.model]) h.natives.delete(ctx);
+}
 const has_cb = (res) => !!(res.cb || (res.ens && res.ens.cb));
 // per clip: Label_conf_all as {label: sum} in legend order (labels never added: 0)
 function meters_of(res, clip, labels) {
   const C = res.nClasses, o = {};
-  for (let c = 0; c < C; c++) o[labels[c]] = res.clipConf[clip * C + c];
+  for (let c = 0; c < C && c < labels.length; c++) o[labels[c]] = res.clipConf[clip * C + c];      // (a KNN store has 64 classes, its classifier fewer labels)
   return o;
 }
 // the prediction of the level-13 callback whose first row is r (res.cb lists them in row order)
@@ -444,7 +482,7 @@ function predict_after(res, r, si, clip, pred) {
   const labels = pred.model.labels, C = res.nClasses, n = res.cb[k * 4 + 3];
   const sorted = (q) => {
     const e = [];
-    for (let c = 0; c < C; c++) e.push({ [labels[c]]: res.prob[q * C + c], label: labels[c], confidence: res.prob[q * C + c] });
+    for (let c = 0; c < C && c < labels.length; c++) e.push({ [labels[c]]: res.prob[q * C + c], label: labels[c], confidence: res.prob[q * C + c] });
     return e.sort((a, b) => b.confidence - a.confidence);             // ml5 classifyInternal (a stable sort: ties keep legend order)
   };
   const per = n === 1 ? sorted(r) : Array.from({ length: n }, (_, q) => sorted(r + q));
@@ -649,7 +687,7 @@ async function run(clips, callback, labels_of, test_play) {
     const models = ctxs.map((c) => (pred ? model_on(nat, c) : undefined));
     const job = ([a, b], i) => {
       const part = clips.slice(a, b);
-      const extra = pred ? [models[i]] : [];                     // (no model: the addon is called exactly as before)
+      const extra = pred && !pred.knn ? [models[i]] : [];        // (no model: the addon is called exactly as before; a KNN store classifies behind the job)
       const fs_i = rates_of(part);                               // (a shard whose clips share a rate: the number, as before)
       return all16 ? nat.processBatch(ctxs[i], part.map((c) => c.pcm16), fs_i, settings.output_level, fs_an, Uint32Array.from(part, (c) => c.channels), gather, ...extra)
         : nat.processBatch(ctxs[i], part.map(clip_floats), fs_i, settings.output_level, fs_an, undefined, gather, ...extra);
@@ -668,6 +706,9 @@ async function run(clips, callback, labels_of, test_play) {
         results[i].meta = all.meta.subarray(off * 8, (off + k) * 8); results[i].feat = all.feat.subarray(off * 53, (off + k) * 53);
         off += k;
       }
+    }
+    if (pred && pred.knn) {
+      try { results.forEach((res, i) => knn_fold_into(nat, ctxs[i], res, pred)); } catch (e) { drop_contexts(nat); throw e; }
     }
     // StopAudioNodes while the work was in flight: the reference tears the nodes down at the next frame and resolves (ref @B8851) —
     // nothing is dispatched any more, the launch still resolves
@@ -740,6 +781,7 @@ function pipe_contexts(nat) {
   return pipe_cache.ctxs;
 }
 function drop_pipe_contexts(nat) {
+  for (const c of pipe_cache.ctxs) knn_natives.delete(c);
   for (const c of pipe_cache.ctxs) { try { nat.destroy(c); } catch (e) { /* a failed launch's straggler still uses it: left to process exit */ } }
   pipe_cache = { key: null, ctxs: [] };
 }
@@ -763,7 +805,7 @@ async function run_batches(batches, callback, labels, test_play) {
       const g = nat.geometry(ctxs[k % 2], fs_an);
       if (g.bands !== bands) throw 'Bins count mismatch: ' + g.bands + ', ' + bands;          // ref @B8568 check
       const all16 = clips.every((c) => c.pcm16);
-      const extra = pred ? [models[k % 2]] : [];
+      const extra = pred && !pred.knn ? [models[k % 2]] : [];
       return all16 ? nat.processBatch(ctxs[k % 2], clips.map((c) => c.pcm16), fs, settings.output_level, fs_an, Uint32Array.from(clips, (c) => c.channels), false, ...extra)
         : nat.processBatch(ctxs[k % 2], clips.map(clip_floats), fs, settings.output_level, fs_an, undefined, false, ...extra);
     };
@@ -779,6 +821,9 @@ async function run_batches(batches, callback, labels, test_play) {
       try { res = await mine; }
       catch (e) { if (next) { try { await next; } catch (e2) { /* the first failure is reported */ } } drop_pipe_contexts(nat); throw e; }
       if (start_err) { drop_pipe_contexts(nat); throw start_err; }
+      if (pred && pred.knn) {               // (context k % 2 is idle until batch k + 2 starts)
+        try { knn_fold_into(nat, ctxs[k % 2], res, pred); } catch (e) { if (next) { try { await next; } catch (e2) { /* the first failure is reported */ } } drop_pipe_contexts(nat); throw e; }
+      }
       rows += res.meta.length / 8; segments += res.segments.length / 4; done++;
       if (!test_play && (callback || pred) && !stop_requested) {                              // ref @B24762: silent when test_play
         const lb = labels[k] || [];
@@ -843,7 +888,8 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
     if (g.bands !== bands) throw 'Bins count mismatch: ' + g.bands + ', ' + bands;              // ref @B8568 check
     st = convert ? nat.streamOpenMixed(ctx, n_streams, Float64Array.from(per_stream ? rates : new Array(n_streams).fill(rates[0])), fs_an, frames_per_step, max_span_frames)
       : nat.streamOpen(ctx, n_streams, rates[0], frames_per_step, max_span_frames);
-    if (pred && pred.models) nat.streamSetEnsemble(st, model_on(nat, ctx));
+    if (pred && pred.knn) nat.streamSetKnn(st, knn_store_on(nat, ctx, pred.knn), pred.k);
+    else if (pred && pred.models) nat.streamSetEnsemble(st, model_on(nat, ctx));
     else if (pred) nat.streamSetModel(st, model_on(nat, ctx));       // the native model on the stream's own context (ref src/index.js:56)
   } catch (e) {
     if (st) nat.streamClose(st);
@@ -852,7 +898,10 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
   }
   const input = nat.streamInput(st);
   const info = convert ? nat.streamInfo(st) : null;
-  const spred = pred && pred.models ? { models: pred.models, state: pred.state, on_prediction: pred.on_prediction, accs: new Map() } : pred;   // accs: per stream, since its START
+  const names = pred && pred.knn ? pred.knn.names.slice() : null;       // a KNN store: the labels of the rows the set opened with
+  // the step's KNN tables under the names predict_after and meters_of read a model's by
+  const knn_view = (res) => ({ cb: res.knnCb, cbLabel: res.knnCbLabel, cbConf: res.knnCbConf, prob: res.knnConf, nClasses: res.knnNClasses });
+  const spred = pred && pred.knn ? { model: { labels: names }, on_prediction: pred.on_prediction } : pred && pred.models ? { models: pred.models, state: pred.state, on_prediction: pred.on_prediction, accs: new Map() } : pred;   // accs: per stream, since its START
   let open = true, started = false, meters = null;      // meters: the per-stream Label_conf_all of the last step (a prediction model only)
   const stopped = new Uint8Array(n_streams);          // streams that have had their segment_truncate since their last START
   const seg_seen = new Uint32Array(n_streams);        // level 3: segments a stream has closed since its last START (the callback index, ref @B28273)
@@ -900,13 +949,16 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
           }
           if (feats.length > 0) {
             if (callback) callback(si, labels[s] || [], times, feats, s);                                                      // ref @B29138 (`p[e].length>0`)
-            if (pred && has_cb(res) && level === 13) predict_after(res, r - times.length, si, s, spred);                              // ref prediction.js:70
+            if (pred && pred.knn) { if (res.knnCb) { res.knnView = res.knnView || knn_view(res); predict_after(res.knnView, r - times.length, si, s, spred); } }
+            else if (pred && has_cb(res) && level === 13) predict_after(res, r - times.length, si, s, spred);                         // ref prediction.js:70
           }
         }
       }
     }
     const out = { rows, segments: res.segments.length / 4, cuts: res.cuts, cut: (res.flags & 8) !== 0 };   // cut: some stream's span reached max_span_frames in this step (WSA_FLAG_STREAM_CUT)
-    if (pred && pred.models && res.ens && res.ens.cb) {
+    if (pred && pred.knn) {
+      if (res.knnStreamConf) meters = out.meters = Array.from({ length: n_streams }, (_, s) => meters_of({ nClasses: res.knnNClasses, clipConf: res.knnStreamConf }, s, names));
+    } else if (pred && pred.models && res.ens && res.ens.cb) {
       meters = out.meters = Array.from({ length: n_streams }, (_, s) => ensemble_meters_of(res, s, pred, spred.accs));
       out.min_entropy_db = Array.from(res.ens.minDb, (v) => (v >= 0 ? v : null));
       out.shown_min_entropy_db = pred.state.min_db;
@@ -968,5 +1020,5 @@ function set_predicted_label_for_segment(si, idx, label) {                      
 
 module.exports = { configure, LaunchAudioNodes, StopAudioNodes, set_predicted_label_for_segment, LaunchBatch, LaunchBatches,
   StreamOpen, STREAM_ACTIVE, STREAM_START, STREAM_STOP, shutdown, allocPinned, freePinned,
-  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, loadModel, setPredictionModel, setPredictionModels, trainModel, saveModel, trainRegression, predictValues, predictDB, statsTable,
+  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, loadModel, setPredictionModel, setPredictionModels, setPredictionKnn, trainModel, saveModel, trainRegression, predictValues, predictDB, statsTable,
   KNNClassifier, trainKnn, predictKnn };

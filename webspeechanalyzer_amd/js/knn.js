@@ -111,4 +111,4 @@ function trainKnn(device, featureDB, o) {
   return { knn, samples: plan.add.length, correct, all: plan.test.length };
 }
 
-module.exports = { labelOrder, evaluationPlan, KnnClassifier, trainKnn, MAX_K, MAX_CLASSES };
+module.exports = { labelOrder, evaluationPlan, KnnClassifier, trainKnn, pack, MAX_K, MAX_CLASSES };

@@ -64,8 +64,26 @@ def evaluation_plan(true_labels, classes):
     return add, test
 
 
+def name_results(classes, r):
+    """The class indices of a KNN result (Batch.knn_classes / knn_fold_classes, Streams.knn_classes: any of `label`, `cb_label`) as the
+    labels ml5 reports, `classes` being label_order's names: adds `label` / `cb_label` as lists of names (None for -1 = null and -2 = not
+    predicted) and keeps the indices as `index` / `cb_index`; confidence tables are cut to the classes in use.  A table the result does
+    not have (None at level 5) stays None."""
+    C = len(classes)
+    out = dict(r, classes=list(classes))
+    for key, raw in (("label", "index"), ("cb_label", "cb_index")):
+        if r.get(key) is not None:
+            out[raw] = r[key]
+            out[key] = [classes[i] if i >= 0 else None for i in r[key]]
+    for key in ("conf", "clip_conf", "stream_conf"):
+        if r.get(key) is not None:
+            out[key] = r[key][:, :C]
+    return out
+
+
 class Knn:
-    """ml5.KNNClassifier on an Analyzer's device: add(rows, labels), classify(rows, k), classify_batch(batch, k).  Keeps a host copy of what
+    """ml5.KNNClassifier on an Analyzer's device: add(rows, labels), classify(rows, k), classify_batch(batch, k), fold_batch(batch, k),
+    attach(streams, k) / stream_classes(streams).  Keeps a host copy of what
     was added: a label that sorts in front of stored classes (a number label below a stored one) renumbers them, and the store is then
     refilled."""
 
@@ -138,6 +156,25 @@ class Knn:
         batch.knn(self.store, k, stream)
         r = batch.knn_classes(stream)
         return self._result(r["label"], r["conf"], r["nbr"], r["sim"], r["k_eff"])
+
+    def fold_batch(self, batch, k=10, stream=0):
+        """classify_batch, then the per-callback fold KN-2 over it (level 13; wsa_batch_knn_fold): dict(cb [n_cb, 4], cb_label (names;
+        None: null or not predicted), cb_index, cb_conf, clip_conf [n_clips, C], classes)."""
+        batch.knn(self.store, k, stream)
+        batch.knn_fold(stream)
+        return name_results(self.classes, batch.knn_fold_classes(stream))
+
+    def attach(self, streams, k=10):
+        """K9s (and at level 13 the fold KN-2) inside every step of `streams` (wsa_stream_set_knn) with the rows stored NOW: attach again
+        after add() — a step keeps the row count of the attach, and an add() that renumbers the classes makes a new store."""
+        streams.set_knn(self.store, k)
+
+    def detach(self, streams):
+        streams.set_knn(None)
+
+    def stream_classes(self, streams):
+        """After streams.collect(): the step's KNN tables (Streams.knn_classes) with `label` and `cb_label` as label names."""
+        return name_results(self.classes, streams.knn_classes())
 
     def close(self):
         self.store.close()

@@ -22,6 +22,8 @@
  *       one hipGraph launch, well under a millisecond, so it runs on the calling thread; counts: samples per stream in this step, else paced)
  *   processBatch(..., [models])                 (8th argument an array of models: wsa_batch_classify_ensemble; the result gains `ens`)
  *   streamSetEnsemble(stream, [models] | null)  (wsa_stream_set_ensemble: streamStep results gain `ens`)
+ *   streamSetKnn(stream, knn | null, k)         (wsa_stream_set_knn: streamStep results gain knnLabel, knnConf, knnCb, knnCbLabel, knnCbConf, knnStreamConf, knnNClasses;
+ *                                                beside a model or an ensemble, not in place of one)
  *   streamSetModel(stream, model | null)        (wsa_stream_set_model: streamStep results gain prob, cb, cbLabel, cbConf, streamConf, nClasses)
  *   streamClose(stream)
  * Rejections carry the library's error string.  No compute happens in this file.
@@ -693,7 +695,7 @@ static napi_value fn_gather_rows(napi_env env, napi_callback_info info) {
 }
 
 /* ---- streams ---- */
-typedef struct { wsa_stream *st; wsa_ctx *ctx; ctx_box *box; uint32_t n, sps; napi_ref input_ref; model_box *model; wsa_ensemble *ens; model_box *ens_models[WSA_ENSEMBLE_MAX]; uint32_t n_ens; } stream_t;   /* input_ref: the ArrayBuffer over the pinned input, detached at close; model: attached classifier (holds its busy count) */
+typedef struct { wsa_stream *st; wsa_ctx *ctx; ctx_box *box; uint32_t n, sps; napi_ref input_ref; model_box *model; wsa_ensemble *ens; model_box *ens_models[WSA_ENSEMBLE_MAX]; uint32_t n_ens; struct knn_box *knn; } stream_t;   /* input_ref: the ArrayBuffer over the pinned input, detached at close; model: attached classifier (holds its busy count) */
 static void stream_finalize(napi_env env, void *data, void *hint) { /* explicit streamClose() only */ }
 static stream_t *get_stream(napi_env env, napi_value v) {
     void *p = NULL; if (napi_get_value_external(env, v, &p) != napi_ok) return NULL; return (stream_t *)p;
@@ -844,6 +846,19 @@ static napi_value fn_stream_step(napi_env env, napi_callback_info info) {
         }
         napi_value nc; napi_create_uint32(env, c.n_classes, &nc); napi_set_named_property(env, o, "nClasses", nc);
     }
+    if (h->knn) {                                   /* the attached KNN store's tables of this step (K9s; level 13: the fold KN-2, knnStreamConf per stream, carried) */
+        wsa_stream_knn_result c;
+        if (wsa_stream_knn_classes(h->st, &c) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(h->ctx)); return NULL; }
+        napi_set_named_property(env, o, "knnLabel", make_typed(env, napi_int32_array, c.label, (size_t)c.n_rows, 4));
+        napi_set_named_property(env, o, "knnConf", make_typed(env, napi_float64_array, c.conf, (size_t)c.n_rows * c.n_classes, 8));
+        if (c.cb) {
+            napi_set_named_property(env, o, "knnCb", make_typed(env, napi_int32_array, c.cb, (size_t)c.n_callbacks * 4, 4));
+            napi_set_named_property(env, o, "knnCbLabel", make_typed(env, napi_int32_array, c.cb_label, (size_t)c.n_callbacks, 4));
+            napi_set_named_property(env, o, "knnCbConf", make_typed(env, napi_float64_array, c.cb_conf, (size_t)c.n_callbacks, 8));
+            napi_set_named_property(env, o, "knnStreamConf", make_typed(env, napi_float64_array, c.stream_conf, (size_t)c.n_streams * c.n_classes, 8));
+        }
+        napi_value nc; napi_create_uint32(env, c.n_classes, &nc); napi_set_named_property(env, o, "knnNClasses", nc);
+    }
     if (h->ens) {                                   /* the attached ensemble's tables of this step (conf / minDb: per stream, carried) */
         wsa_stream_ensemble_result c;
         if (wsa_stream_ensemble_classes(h->st, &c) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(h->ctx)); return NULL; }
@@ -869,6 +884,7 @@ static napi_value fn_stream_close(napi_env env, napi_callback_info info) {
             napi_delete_reference(env, h->input_ref); h->input_ref = NULL;
         }
         wsa_stream_destroy(h->st); h->st = NULL;
+        h->knn = NULL;
         if (h->model) { if (h->model->busy) h->model->busy--; h->model = NULL; }
         stream_drop_ensemble(h);
         if (h->box && h->box->children) h->box->children--;
@@ -893,6 +909,27 @@ static napi_value fn_stream_set_model(napi_env env, napi_callback_info info) {
     if (h->model && h->model->busy) h->model->busy--;          /* modelDestroy() refuses while a stream holds the model */
     h->model = mb;
     if (mb) { mb->busy++; stream_drop_ensemble(h); }            /* (the library detached the ensemble) */
+    return NULL;
+}
+/* streamSetKnn(stream, knn | null, k): the store stays the caller's; knnDestroy() refuses while its context has open streams */
+static napi_value fn_stream_set_knn(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    stream_t *h = argc ? get_stream(env, argv[0]) : NULL;
+    if (!h || !h->st || argc < 2) { napi_throw_type_error(env, NULL, "streamSetKnn(stream, knn | null, k)"); return NULL; }
+    struct knn_box *kb = NULL;
+    uint32_t k = 0;
+    napi_valuetype t;
+    NAPI_OK(env, napi_typeof(env, argv[1], &t));
+    if (t != napi_null && t != napi_undefined) {
+        void *p = NULL;
+        if (t != napi_external || napi_get_value_external(env, argv[1], &p) != napi_ok || !p || !((struct knn_box *)p)->k) { napi_throw_error(env, NULL, "streamSetKnn: the KNN store was destroyed (or is not a store)"); return NULL; }
+        kb = (struct knn_box *)p;
+        if (kb->owner != h->box) { napi_throw_error(env, NULL, "streamSetKnn: the KNN store belongs to another context"); return NULL; }
+        if (argc < 3 || napi_get_value_uint32(env, argv[2], &k) != napi_ok) { napi_throw_type_error(env, NULL, "streamSetKnn(stream, knn | null, k)"); return NULL; }
+    }
+    if (wsa_stream_set_knn(h->st, kb ? kb->k : NULL, k) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(h->ctx)); return NULL; }
+    h->knn = kb;
     return NULL;
 }
 /* streamSetEnsemble(stream, [models] | null): the stream object owns the wsa_ensemble it makes of them, until it is replaced, detached or closed */
@@ -1417,6 +1454,36 @@ static napi_value fn_batch_knn(napi_env env, napi_callback_info info) {
     free(buf);
     return out;
 }
+/* batchKnnFold(ctx) -> {cb: Int32Array [n][4], cbLabel: Int32Array [n], cbConf: Float64Array [n], clipConf: Float64Array [clips][nClasses], nClasses}:
+ * the fold KN-2 over the tables of the context's last batchKnn (wsa_batch_knn_fold; output_level 13) */
+static napi_value fn_batch_knn_fold(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ctx_box *box = argc ? get_box(env, argv[0]) : NULL;
+    if (!box || !box->ctx) { napi_throw_type_error(env, NULL, "batchKnnFold(ctx)"); return NULL; }
+    if (!box->plan) { napi_throw_error(env, NULL, "batchKnnFold: no finished processBatch on this context (or one is in flight)"); return NULL; }
+    wsa_knn_fold_result r;
+    wsa_status st = wsa_batch_knn_fold(box->plan, box->queue);
+    if (st == WSA_OK) st = wsa_batch_knn_fold_result(box->plan, box->queue, &r);
+    if (st != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(box->ctx)); return NULL; }
+    const size_t n = r.n_callbacks, nc = (size_t)r.n_clips * r.n_classes;
+    double *conf = malloc((n + nc + 1) * sizeof(double));
+    int32_t *cb = malloc((5 * n + 1) * sizeof(int32_t));
+    napi_value out = NULL;
+    if (!conf || !cb) napi_throw_error(env, NULL, "out of memory");
+    else if (wsa_batch_copy_knn_fold(box->plan, box->queue, cb, cb + 4 * n, conf, (uint32_t)(n ? n : 1), conf + n) != WSA_OK) napi_throw_error(env, NULL, wsa_last_error(box->ctx));
+    else {
+        napi_value v;
+        napi_create_object(env, &out);
+        napi_set_named_property(env, out, "cb", make_typed(env, napi_int32_array, cb, n * 4, 4));
+        napi_set_named_property(env, out, "cbLabel", make_typed(env, napi_int32_array, cb + 4 * n, n, 4));
+        napi_set_named_property(env, out, "cbConf", make_typed(env, napi_float64_array, conf, n, 8));
+        napi_set_named_property(env, out, "clipConf", make_typed(env, napi_float64_array, conf + n, nc, 8));
+        napi_create_uint32(env, r.n_classes, &v); napi_set_named_property(env, out, "nClasses", v);
+    }
+    free(conf); free(cb);
+    return out;
+}
 
 NAPI_MODULE_INIT() {
     /* the structures below follow the header this file was compiled against: refuse a libwsa.so of another ABI version */
@@ -1424,10 +1491,10 @@ NAPI_MODULE_INIT() {
     const struct { const char *name; napi_callback fn; } fns[] = {
         {"abiVersion", fn_abi_version}, {"freePinned", fn_free_pinned}, {"defaults", fn_defaults}, {"create", fn_create}, {"destroy", fn_destroy},
         {"geometry", fn_geometry}, {"allocPinned", fn_alloc_pinned}, {"binsHz", fn_bins_hz}, {"processBatch", fn_process_batch}, {"gatherRows", fn_gather_rows},
-        {"streamOpen", fn_stream_open}, {"streamOpenMixed", fn_stream_open_mixed}, {"streamInfo", fn_stream_info}, {"streamPaced", fn_stream_paced}, {"streamInput", fn_stream_input}, {"streamStep", fn_stream_step}, {"streamClose", fn_stream_close}, {"streamSetModel", fn_stream_set_model}, {"streamSetEnsemble", fn_stream_set_ensemble},
+        {"streamOpen", fn_stream_open}, {"streamOpenMixed", fn_stream_open_mixed}, {"streamInfo", fn_stream_info}, {"streamPaced", fn_stream_paced}, {"streamInput", fn_stream_input}, {"streamStep", fn_stream_step}, {"streamClose", fn_stream_close}, {"streamSetModel", fn_stream_set_model}, {"streamSetEnsemble", fn_stream_set_ensemble}, {"streamSetKnn", fn_stream_set_knn},
         {"modelCreate", fn_model_create}, {"modelDestroy", fn_model_destroy}, {"train", fn_train}, {"regressRows", fn_regress_rows},
         {"dbPredict", fn_db_predict}, {"dbTable", fn_db_table},
-        {"knnCreate", fn_knn_create}, {"knnDestroy", fn_knn_destroy}, {"knnAdd", fn_knn_add}, {"knnClassify", fn_knn_classify}, {"batchKnn", fn_batch_knn}};
+        {"knnCreate", fn_knn_create}, {"knnDestroy", fn_knn_destroy}, {"knnAdd", fn_knn_add}, {"knnClassify", fn_knn_classify}, {"batchKnn", fn_batch_knn}, {"batchKnnFold", fn_batch_knn_fold}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;
