@@ -654,8 +654,8 @@ void       wsa_trainer_destroy(wsa_trainer *t);
  * A regression model is an ordinary wsa_model whose last layer has ONE unit and is linear, relu, sigmoid or tanh; wsa_model_desc is
  * unchanged and the output range travels as arguments.  Every entry refuses (WSA_ERR_INVALID with a message) more than one output
  * unit, a softmax last layer, non-finite out_min / out_max and out_max == out_min.
- * No fold and no per-callback decision: the reference's live path with an ords model sums the `confidence` fields a regression result
- * does not have (ref src/prediction.js:96-101: undefined, so NaN) and defines nothing worth restating.  Streams take no regression model.
+ * One value per callback and a running value per clip or stream, and regression models on streams: specification RG-1 of DESIGN.md,
+ * "Regression groups" below (wsa_regress_group_create).
  */
 /* K6 with the un-normalising epilogue on device rows (ref src/neuralmodel.js:540-585 predict_single -> predictMultiple; :410-535
  * predict_db_nn -> result_out[0].value): dense d_feat [n_rows][units[0]] f64 -> d_value [n_rows] f64 = (double)p * (out_max - out_min) +
@@ -862,6 +862,81 @@ typedef struct {
 /* After wsa_stream_collect of the same step: host memory owned by the stream object, valid until the next step.
  * WSA_ERR_INVALID without an attached store. */
 wsa_status wsa_stream_knn_classes(wsa_stream *st, wsa_stream_knn_result *out);
+
+/*
+ * ---- Regression groups: V, A and D per callback, in batches and streams (additions within version 5: probe for wsa_regress_group_create).
+ * Specification RG-1 (csrc/regress_fold.hpp, regress_fold.hip).  The reference application wires this path up and breaks
+ * it: `?type=ords&label=V` sets predict_type = "ords" (ref src/index.js:892-893), every level-13 callback then goes through
+ * predict_by_multiple_syllables -> predictMultiple (ref src/prediction.js:47-123, src/neuralmodel.js:564-565), and the fold reads
+ * result_out[ph].confidence, which a regression result does not have: every sum is NaN.  The definition is therefore this project's:
+ * per head h, the rows' values v_h weighted as the app weights every per-syllable result, by w = sqrt(d), d = parseFloat(((len + 1) *
+ * step_s).toFixed(3)) (ref src/prediction.js:93):  cb_value[h] = (sum v w) / (sum w) over the callback's rows whose v_h is finite, in
+ * row order, each product and each sum rounded on its own; a callback whose durations sum to 0 is skipped (value NaN, weight 0); the
+ * same terms in the same order, continued from callback to callback (skipped ones left out), are the running sums of the clip or the
+ * stream.  A signal dealt over stream steps gives the bits of the whole signal in one batch.
+ * A group is 1 .. WSA_REGRESS_GROUP_MAX heads: regression models (what wsa_regress_rows accepts) of 53 inputs on one context, each with
+ * its output range; the same model may appear twice.  All heads run in ONE grouped K6 launch (the ensemble's kernel with the regression
+ * epilogue); head h's values equal wsa_regress_rows with that model and range bit for bit.  The models must outlive the group.
+ */
+#define WSA_REGRESS_GROUP_MAX 8
+typedef struct wsa_regress_group wsa_regress_group;
+/* WSA_ERR_INVALID with a message: n outside 1 .. 8, a NULL member, a member of another context, a member that does not take 53 inputs,
+ * and per member everything wsa_regress_rows refuses (a classifier, several output units, a bad range). */
+wsa_status wsa_regress_group_create(wsa_ctx *ctx, const wsa_model *const *models, const double *out_min, const double *out_max,
+                                    uint32_t n, wsa_regress_group **out);
+void       wsa_regress_group_destroy(wsa_regress_group *g);
+/* dense d_feat [n_rows][53] f64 -> d_value[h] [n_rows] f64 for every head h (d_value: a HOST array of n device pointers), one grouped
+ * launch on `stream`.  The group keeps one launch table: a call waits (on the host) for the group's previous call to finish. */
+wsa_status wsa_regress_group_rows(wsa_regress_group *g, const double *d_feat, uint32_t n_rows, double *const *d_value, void *stream);
+/* The group over the rows of the batch's last run, and at output_level 13 the RG-1 fold behind it, one accumulator set per clip.
+ * Output_level 5 and 13 only: every other level is refused by name.  Only enqueues; after the first call on a batch with a group
+ * nothing is allocated, so it can be captured behind wsa_batch_run.  It is the batch's ONE last model call (beside wsa_batch_classify,
+ * _classify_ensemble and _regress): their result functions are refused after it, and these after them. */
+wsa_status wsa_batch_regress_group(wsa_batch *b, const wsa_regress_group *g, void *stream);
+/* device tables of the last wsa_batch_regress_group, valid until the next one that allocates or wsa_batch_destroy.  Level 5: d_value
+ * only, n_callbacks 0 and every other pointer NULL. */
+typedef struct {
+    uint32_t n_rows, n_heads, n_callbacks, n_clips;
+    const double  *d_value[WSA_REGRESS_GROUP_MAX];        /* [n_rows] v_h, rows in wsa_device_result's order */
+    const double  *d_cb_value[WSA_REGRESS_GROUP_MAX];     /* [n_callbacks] S_h / W_h; NaN: skipped callback, or no usable row */
+    const double  *d_cb_weight[WSA_REGRESS_GROUP_MAX];    /* [n_callbacks] W_h */
+    const double  *d_clip_sum[WSA_REGRESS_GROUP_MAX];     /* [n_clips] A_h */
+    const double  *d_clip_weight[WSA_REGRESS_GROUP_MAX];  /* [n_clips] B_h */
+    const double  *d_clip_value[WSA_REGRESS_GROUP_MAX];   /* [n_clips] A_h / B_h, NaN when B_h == 0 */
+    const int32_t *d_cb;                                  /* [n_callbacks][4] = {clip, si, first row, rows}, as wsa_class_result's */
+} wsa_value_result;
+wsa_status wsa_batch_value_result(wsa_batch *b, void *stream, wsa_value_result *out);            /* synchronises `stream` */
+/* the same tables copied to host buffers; any pointer may be NULL to skip it.  value: [rows_cap] each; cb [cb_cap][4], cb_value and
+ * cb_weight [cb_cap] each; clip_* [n_clips] each.  WSA_ERR_INVALID if a capacity is too small for a table that is asked for. */
+typedef struct {
+    uint32_t rows_cap, cb_cap;
+    double  *value[WSA_REGRESS_GROUP_MAX], *cb_value[WSA_REGRESS_GROUP_MAX], *cb_weight[WSA_REGRESS_GROUP_MAX];
+    double  *clip_sum[WSA_REGRESS_GROUP_MAX], *clip_weight[WSA_REGRESS_GROUP_MAX], *clip_value[WSA_REGRESS_GROUP_MAX];
+    int32_t *cb;
+} wsa_value_host;
+wsa_status wsa_batch_copy_value_fold(wsa_batch *b, void *stream, const wsa_value_host *dst);
+/* Attach (g != NULL) or detach (NULL) a regression group: the grouped K6 on every step's rows and, at output_level 13, RG-1 with the
+ * running sums of every (stream, head) carried on the device — reset by START (a START step's rows belong to the new launch), untouched
+ * on idle steps, kept after STOP; STOP-flush rows and the rows of cut spans fold like any others — as kernels of the step, on the step's
+ * own stream behind its other kernels; the step stays one graph launch.  Levels 5 and 13 only (refused by name otherwise), a group of
+ * the streams' context.  Synchronises the last step, allocates everything (tables, the carried sums, zeroed) and drops the captured graph.
+ * These tables are separate from a model's, an ensemble's and a KNN store's: attaching a group neither detaches any of those nor is
+ * detached by them, and classes and V, A, D come out of the same step.  The group must outlive its attachment.
+ * wsa_stream_time_steps times the step with these kernels in it. */
+wsa_status wsa_stream_set_regress(wsa_stream *st, const wsa_regress_group *g);
+typedef struct {
+    uint32_t n_rows, n_heads, n_callbacks, n_streams;
+    const double  *value[WSA_REGRESS_GROUP_MAX];          /* [n_rows], rows in wsa_stream_rows order */
+    const int32_t *cb;                                    /* [n_callbacks][4] = {stream, si, first row, rows} (level 13; else 0 / NULL) */
+    const double  *cb_value[WSA_REGRESS_GROUP_MAX];       /* [n_callbacks] */
+    const double  *cb_weight[WSA_REGRESS_GROUP_MAX];      /* [n_callbacks] */
+    const double  *stream_sum[WSA_REGRESS_GROUP_MAX];     /* [n_streams] A_h since each stream's START */
+    const double  *stream_weight[WSA_REGRESS_GROUP_MAX];  /* [n_streams] B_h */
+    const double  *stream_value[WSA_REGRESS_GROUP_MAX];   /* [n_streams] A_h / B_h, NaN when B_h == 0 */
+} wsa_stream_value_result;
+/* After wsa_stream_collect of the same step: host memory owned by the stream object, valid until the next step.
+ * WSA_ERR_INVALID without an attached group. */
+wsa_status wsa_stream_values(wsa_stream *st, wsa_stream_value_result *out);
 
 #ifdef __cplusplus
 }

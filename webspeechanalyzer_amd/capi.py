@@ -149,6 +149,28 @@ class _StreamKnnResult(ctypes.Structure):
                 ("cb", ctypes.c_void_p), ("cb_label", ctypes.c_void_p), ("cb_conf", ctypes.c_void_p), ("stream_conf", ctypes.c_void_p)]
 
 
+REGRESS_GROUP_MAX = 8      # WSA_REGRESS_GROUP_MAX
+_VPH = ctypes.c_void_p * REGRESS_GROUP_MAX
+
+
+class _ValueResult(ctypes.Structure):
+    _fields_ = [("n_rows", ctypes.c_uint32), ("n_heads", ctypes.c_uint32), ("n_callbacks", ctypes.c_uint32), ("n_clips", ctypes.c_uint32),
+                ("d_value", _VPH), ("d_cb_value", _VPH), ("d_cb_weight", _VPH), ("d_clip_sum", _VPH), ("d_clip_weight", _VPH), ("d_clip_value", _VPH),
+                ("d_cb", ctypes.c_void_p)]
+
+
+class _ValueHost(ctypes.Structure):
+    _fields_ = [("rows_cap", ctypes.c_uint32), ("cb_cap", ctypes.c_uint32),
+                ("value", _VPH), ("cb_value", _VPH), ("cb_weight", _VPH), ("clip_sum", _VPH), ("clip_weight", _VPH), ("clip_value", _VPH),
+                ("cb", ctypes.c_void_p)]
+
+
+class _StreamValueResult(ctypes.Structure):
+    _fields_ = [("n_rows", ctypes.c_uint32), ("n_heads", ctypes.c_uint32), ("n_callbacks", ctypes.c_uint32), ("n_streams", ctypes.c_uint32),
+                ("value", _VPH), ("cb", ctypes.c_void_p), ("cb_value", _VPH), ("cb_weight", _VPH),
+                ("stream_sum", _VPH), ("stream_weight", _VPH), ("stream_value", _VPH)]
+
+
 # every symbol include/wsa.h declares (checked by tests/test_abi.py)
 ABI_VERSION = 5            # WSA_ABI_VERSION of include/wsa.h this binding's structures follow
 ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destroy", "wsa_last_error",
@@ -185,7 +207,10 @@ ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destr
                "wsa_knn_create", "wsa_knn_destroy", "wsa_knn_add", "wsa_knn_count", "wsa_knn_classify_rows", "wsa_knn_tile_info",
                "wsa_batch_knn", "wsa_batch_knn_result", "wsa_batch_copy_knn",
                # additions within version 5 (probe for wsa_stream_set_knn): KNN on live streams (K9s) and the fold of KNN results (spec KN-2)
-               "wsa_batch_knn_fold", "wsa_batch_knn_fold_result", "wsa_batch_copy_knn_fold", "wsa_stream_set_knn", "wsa_stream_knn_classes"]
+               "wsa_batch_knn_fold", "wsa_batch_knn_fold_result", "wsa_batch_copy_knn_fold", "wsa_stream_set_knn", "wsa_stream_knn_classes",
+               # additions within version 5 (probe for wsa_regress_group_create): V, A, D per callback in batches and streams (spec RG-1)
+               "wsa_regress_group_create", "wsa_regress_group_destroy", "wsa_regress_group_rows", "wsa_batch_regress_group", "wsa_batch_value_result",
+               "wsa_batch_copy_value_fold", "wsa_stream_set_regress", "wsa_stream_values"]
 
 _LIB = None
 _U32_RESULT = ("wsa_stream_input_capacity", "wsa_stream_paced_input", "wsa_stream_input_stride", "wsa_stream_step_frame_capacity", "wsa_stream_frames_bound")
@@ -337,12 +362,21 @@ def lib():
     L.wsa_batch_copy_knn_fold.argtypes = [vp, vp, vp, vp, vp, u32, vp]
     L.wsa_stream_set_knn.argtypes = [vp, vp, u32]
     L.wsa_stream_knn_classes.argtypes = [vp, ctypes.POINTER(_StreamKnnResult)]
+    L.wsa_regress_group_create.argtypes = [vp, vp, vp, vp, u32, ctypes.POINTER(vp)]
+    L.wsa_regress_group_destroy.argtypes = [vp]
+    L.wsa_regress_group_rows.argtypes = [vp, vp, u32, vp, vp]
+    L.wsa_batch_regress_group.argtypes = [vp, vp, vp]
+    L.wsa_batch_value_result.argtypes = [vp, vp, ctypes.POINTER(_ValueResult)]
+    L.wsa_batch_copy_value_fold.argtypes = [vp, vp, ctypes.POINTER(_ValueHost)]
+    L.wsa_stream_set_regress.argtypes = [vp, vp]
+    L.wsa_stream_values.argtypes = [vp, ctypes.POINTER(_StreamValueResult)]
     for name in ABI_SYMBOLS:
         if name in _U32_RESULT or name in ("wsa_resample_ready", "wsa_level_feature_count"):
             continue
         if name not in ("wsa_abi_version", "wsa_last_error", "wsa_config_default", "wsa_destroy", "wsa_batch_destroy", "wsa_resample_length",
                         "wsa_stream_destroy", "wsa_stream_samples_per_step", "wsa_stream_host_input", "wsa_gather_destroy", "wsa_host_free",
-                        "wsa_model_destroy", "wsa_ensemble_destroy", "wsa_trainer_destroy", "wsa_dbstats_destroy", "wsa_knn_destroy"):
+                        "wsa_model_destroy", "wsa_ensemble_destroy", "wsa_trainer_destroy", "wsa_dbstats_destroy", "wsa_knn_destroy",
+                        "wsa_regress_group_destroy"):
             getattr(L, name).restype = ctypes.c_int
     _LIB = L
     return L
@@ -443,6 +477,11 @@ class Analyzer:
     def ensemble(self, models):
         """The app's `available_DBs` on this context: a list of 1 .. 8 Models in that order (every tie between DBs goes to the earlier one)."""
         return Ensemble(self, models)
+
+    def regress_group(self, models, ranges=None):
+        """1 .. 8 regression Models (the app's ords_<label>: V, A, D) as the heads of one grouped launch and of the fold RG-1; ranges = one
+        (out_min, out_max) per head, None (or a None entry) for the model's own."""
+        return RegressGroup(self, models, ranges)
 
     def close(self):
         if self.h:
@@ -729,6 +768,37 @@ class Batch:
         out = dict(cb=np.zeros((k, 4), np.int32), cb_label=np.zeros(k, np.int32), cb_conf=np.zeros(k, np.float64), clip_conf=np.zeros((int(r.n_clips), C), np.float64))
         self.an._check(self.L.wsa_batch_copy_knn_fold(self.h, stream, out["cb"].ctypes.data, out["cb_label"].ctypes.data, out["cb_conf"].ctypes.data, max(k, 1),
                                                        out["clip_conf"].ctypes.data))
+        return out
+
+    def regress_group(self, group, stream=0):
+        """The grouped K6 over a RegressGroup's heads on the rows of the last run and, at level 13, the fold RG-1, enqueued on `stream`
+        (wsa_batch_regress_group); levels 5 and 13."""
+        self.an._check(self.L.wsa_batch_regress_group(self.h, group.h, stream))
+        self._group = group
+
+    def value_result(self, stream=0):
+        r = _ValueResult()
+        self.an._check(self.L.wsa_batch_value_result(self.h, stream, ctypes.byref(r)))
+        return r
+
+    def value_fold(self, stream=0):
+        """Host copies of the last regress_group(): dict(value [H, n_rows] f64; at level 13 also cb [n_cb, 4] i32 = {clip, si, first row,
+        rows}, cb_value / cb_weight [H, n_cb] f64 (NaN / 0: a skipped callback), clip_sum / clip_weight / clip_value [H, n_clips] f64)."""
+        r = self.value_result(stream)
+        H, n, k, nc = int(r.n_heads), int(r.n_rows), int(r.n_callbacks), int(r.n_clips)
+        out = dict(value=np.zeros((H, n), np.float64))
+        if r.d_cb:
+            out.update(cb=np.zeros((k, 4), np.int32), cb_value=np.zeros((H, k)), cb_weight=np.zeros((H, k)),
+                       clip_sum=np.zeros((H, nc)), clip_weight=np.zeros((H, nc)), clip_value=np.zeros((H, nc)))
+        h = _ValueHost()
+        h.rows_cap, h.cb_cap = max(n, 1), max(k, 1)
+        for name, v in out.items():
+            if name == "cb":
+                h.cb = v.ctypes.data
+            else:
+                for d in range(H):
+                    getattr(h, name)[d] = v[d].ctypes.data
+        self.an._check(self.L.wsa_batch_copy_value_fold(self.h, stream, ctypes.byref(h)))
         return out
 
     def classify_ensemble(self, ensemble, stream=0):
@@ -1083,6 +1153,43 @@ class Ensemble:
             pass
 
 
+class RegressGroup:
+    """wsa_regress_group: 1 .. 8 regression Models with their output ranges, predicted in one grouped launch and folded by RG-1."""
+
+    def __init__(self, an, models, ranges=None):
+        self.an, self.L, self.models = an, an.L, list(models)
+        ranges = list(ranges) if ranges is not None else [None] * len(self.models)
+        if len(ranges) != len(self.models):
+            raise ValueError("one (out_min, out_max) per model")
+        lo_hi = [m.out_range(*(r if r is not None else (None, None))) if m is not None else (0.0, 1.0) for m, r in zip(self.models, ranges)]
+        n = max(len(self.models), 1)
+        arr = (ctypes.c_void_p * n)(*[m.h if m is not None else None for m in self.models])
+        lo, hi = (ctypes.c_double * n)(*[a for a, _ in lo_hi]), (ctypes.c_double * n)(*[b for _, b in lo_hi])
+        self.ranges = lo_hi
+        self.h = ctypes.c_void_p()
+        an._check(self.L.wsa_regress_group_create(an.h, ctypes.cast(arr, ctypes.c_void_p), ctypes.cast(lo, ctypes.c_void_p), ctypes.cast(hi, ctypes.c_void_p),
+                                                  len(self.models), ctypes.byref(self.h)))
+
+    def regress_rows(self, d_feat, n_rows, d_values, stream=0):
+        """One grouped launch over dense device rows: d_feat [n_rows][53] f64 -> d_values[h] [n_rows] f64 (one device pointer per head),
+        asynchronous on `stream`; head h's values are Model.regress_rows' bit for bit."""
+        ptrs = (ctypes.c_void_p * max(len(d_values), 1))(*d_values)
+        if len(d_values) != len(self.models):
+            raise ValueError("one value pointer per head")
+        self.an._check(self.L.wsa_regress_group_rows(self.h, d_feat, int(n_rows), ctypes.cast(ptrs, ctypes.c_void_p), stream))
+
+    def close(self):
+        if self.h:
+            self.L.wsa_regress_group_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class _GatherResult(ctypes.Structure):
     _fields_ = [("n_ranks", ctypes.c_uint32), ("n_rows", ctypes.c_uint32), ("rows_per_rank", ctypes.POINTER(ctypes.c_uint32)),
                 ("d_row_meta", ctypes.c_void_p), ("d_row_feat", ctypes.c_void_p)]
@@ -1268,6 +1375,34 @@ class Streams:
                     k_eff=int(r.k_eff), slices=int(r.slices), cb=arr(r.cb, *i32, (ncb, 4)), cb_label=arr(r.cb_label, *i32, (ncb,)),
                     cb_conf=arr(r.cb_conf, *f64, (ncb,)), stream_conf=arr(r.stream_conf, *f64, (int(r.n_streams), C)))
 
+    def set_regress(self, group):
+        """Attach a RegressGroup (the grouped K6 on every step's rows; at level 13 the fold RG-1, the running sums of every (stream, head)
+        reset by START) or detach (None).  Stands beside a Model or an Ensemble and a KnnStore; the next step recaptures the graph."""
+        self.an._check(self.L.wsa_stream_set_regress(self.h, group.h if group is not None else None))
+        self._group = group
+
+    def values(self):
+        """After collect(): host copies of the step's regression tables, dict(value [H, n_rows] f64, cb [n_cb, 4] i32 = {stream, si, first
+        row, rows}, cb_value / cb_weight [H, n_cb] f64, stream_sum / stream_weight / stream_value [H, n] f64 since each stream's START).
+        Level 5: value only, the others None."""
+        r = _StreamValueResult()
+        self.an._check(self.L.wsa_stream_values(self.h, ctypes.byref(r)))
+        H, n, k, ns = int(r.n_heads), int(r.n_rows), int(r.n_callbacks), int(r.n_streams)
+
+        def arr(ptr, ctype, dtype, shape):
+            if not ptr:
+                return None
+            if not int(np.prod(shape)):
+                return np.zeros(shape, dtype)
+            return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctype)), shape=shape).copy()
+
+        def per_head(ptrs, m):
+            cols = [arr(ptrs[h], ctypes.c_double, np.float64, (m,)) for h in range(H)]
+            return None if any(c is None for c in cols) else np.stack(cols) if cols else np.zeros((0, m))
+        return dict(value=per_head(r.value, n), cb=arr(r.cb, ctypes.c_int32, np.int32, (k, 4)), cb_value=per_head(r.cb_value, k),
+                    cb_weight=per_head(r.cb_weight, k), stream_sum=per_head(r.stream_sum, ns), stream_weight=per_head(r.stream_weight, ns),
+                    stream_value=per_head(r.stream_value, ns))
+
     def set_ensemble(self, ensemble):
         """Attach an Ensemble (K6e on every step's rows; at level 13 one accumulator per stream and member and one running min_entropy_db
         per stream, reset by START) or detach (None).  Detaches a Model; the next step recaptures the graph."""
@@ -1340,6 +1475,41 @@ class Streams:
 GATE_INT_RUNS, GATE_INT_GENERAL, GATE_F64, GATE_STREAM = 0, 1, 2, 3
 GATE_STATE_WORDS = 16
 GATE_SENTINEL = -2
+
+
+def debug_regress_fold(meta, values, step_s, row_off, ctl=None, device=0, sentinel=-7.0):
+    """Test access to the fold RG-1 on its own (csrc/debug.hip wsa_debug_regress_fold; not part of include/wsa.h): hand-built row meta
+    [n_rows, 8] i32 and value columns [H, n_rows] f64.  ctl None: a batch, row_off [n + 1]; else streams, row_off [n_steps, n + 1] counting
+    from each step's first row and ctl [n_steps, n] control bytes.  Returns dict(n_cb (int, or [n_steps]), cb [K, 4], cb_value / cb_weight
+    [H, K] over all K callbacks (the steps' one after the other), run_sum / run_weight / run_value [H, n] (streams: [n_steps, H, n]))."""
+    L = lib()
+    vp, u32, i32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32
+    L.wsa_debug_regress_fold.argtypes = [i32, vp, vp, u32, u32, ctypes.c_double, u32, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
+    L.wsa_debug_regress_fold.restype = ctypes.c_int
+    meta = np.ascontiguousarray(meta, np.int32).reshape(-1, 8)
+    values = np.ascontiguousarray(values, np.float64)
+    H, n_rows = values.shape
+    assert n_rows == len(meta)
+    row_off = np.ascontiguousarray(row_off, np.uint32)
+    streams = ctl is not None
+    n_steps = row_off.shape[0] if streams else 0
+    n = row_off.shape[-1] - 1
+    ctl_a = np.ascontiguousarray(ctl, np.uint8) if streams else None
+    K = max(n_rows, 1)
+    tables = max(n_steps, 1)
+    n_cb = np.zeros(tables, np.uint32)
+    cb = np.full((K, 4), int(sentinel), np.int32)
+    cbv, cbw = np.full((H, K), sentinel), np.full((H, K), sentinel)
+    run = [np.full((tables, H, n), sentinel) for _ in range(3)]
+    rc = L.wsa_debug_regress_fold(device, meta.ctypes.data, values.ctypes.data, n_rows, H, float(step_s), n, n_steps, row_off.ctypes.data,
+                                  ctl_a.ctypes.data if streams else None, K, n_cb.ctypes.data, cb.ctypes.data, cbv.ctypes.data, cbw.ctypes.data,
+                                  run[0].ctypes.data, run[1].ctypes.data, run[2].ctypes.data)
+    if rc != 0:
+        raise WsaError(f"wsa_debug_regress_fold: status {rc}")
+    k = int(n_cb.sum())
+    sel = (lambda a: a) if streams else (lambda a: a[0])
+    return dict(n_cb=n_cb if streams else int(n_cb[0]), cb=cb[:k], cb_value=cbv[:, :k], cb_weight=cbw[:, :k],
+                run_sum=sel(run[0]), run_weight=sel(run[1]), run_value=sel(run[2]))
 
 
 def debug_knn_split(store, d_feat, n_rows, k, slices, d_label, d_conf, d_nbr, d_sim, stream=0):

@@ -62,8 +62,9 @@ struct wsa_batch {
     const uint32_t* spec_in_use = nullptr;
     wsa_cls* cls = nullptr;                 // wsa_batch_classify (classify_batch.hip)
     wsa_ecls* ecls = nullptr;               // wsa_batch_classify_ensemble (classify_batch.hip)
-    int cls_last = 0;                       // which the last classification was (1 / 2; 3: wsa_batch_regress): their results stay apart
+    int cls_last = 0;                       // which the last classification was (1 / 2; 3: wsa_batch_regress; 4: wsa_batch_regress_group): their results stay apart
     wsa_kcls* kcls = nullptr;               // wsa_batch_knn (knn.hip): its tables stand beside the model calls'
+    wsa_rcls* rcls = nullptr;               // wsa_batch_regress_group (regress_fold.hip)
 };
 
 namespace wsa {
@@ -170,6 +171,7 @@ void wsa_batch_destroy(wsa_batch* b) {
     wsa_cls_free(b->cls);
     wsa_ecls_free(b->ecls);
     wsa_kcls_free(b->kcls);
+    wsa_rcls_free(b->rcls);
     delete b;                           // (the arena frees the rest)
 }
 
@@ -664,7 +666,7 @@ void wsa_queue_destroy(wsa_ctx* ctx, void* stream) {
 void wsa_batch_view_internal(wsa_batch* b, wsa_batch_view* v) {
     v->ctx = b->ctx; v->level = b->ctx->cfg.output_level; v->n_clips = b->n_clips; v->rows_cap = b->n_clips * (uint32_t)b->be.row_cap;
     v->d_utt_feat = b->be.d_utt_feat; v->d_utt_off = b->be.d_utt_off; v->utt_cap = b->n_clips * (uint32_t)b->be.seg_cap;
-    v->d_meta = b->be.d_meta; v->d_feat = b->be.d_feat; v->d_row_off = b->be.d_row_off; v->reruns = b->reruns; v->cls = &b->cls; v->ecls = &b->ecls; v->cls_last = &b->cls_last; v->kcls = &b->kcls;
+    v->d_meta = b->be.d_meta; v->d_feat = b->be.d_feat; v->d_row_off = b->be.d_row_off; v->reruns = b->reruns; v->cls = &b->cls; v->ecls = &b->ecls; v->cls_last = &b->cls_last; v->kcls = &b->kcls; v->rcls = &b->rcls;
 }
 wsa_status wsa_batch_fetch_internal(wsa_batch* b, hipStream_t s) { return fetch_totals(b, s); }
 const uint32_t* wsa_batch_counters_internal(wsa_batch* b, int keep, wsa_ctx** ctx) {

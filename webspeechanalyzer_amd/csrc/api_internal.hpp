@@ -26,13 +26,15 @@ struct wsa_ecls;                                // ensemble tables of one batch 
 void wsa_ecls_free(wsa_ecls* c);
 struct wsa_kcls;                                // KNN tables of one batch (allocated by the first wsa_batch_knn, knn.hip)
 void wsa_kcls_free(wsa_kcls* c);
+struct wsa_rcls;                                // regression-group tables of one batch (allocated by the first wsa_batch_regress_group, regress_fold.hip)
+void wsa_rcls_free(wsa_rcls* c);
 struct wsa_batch_view {
     wsa_ctx* ctx; int level; uint32_t n_clips, rows_cap;
     const int32_t* d_meta; const double* d_feat; const uint32_t* d_row_off;     // compacted rows, d_row_off[n_clips] = rows on the device
     const double* d_utt_feat; const uint32_t* d_utt_off; uint32_t utt_cap;      // level 11: utterance rows [..][WSA_NUTT], d_utt_off[n_clips] = their count on the device
     uint32_t reruns;                                                            // wsa_batch_backend_reruns
-    wsa_cls** cls; wsa_ecls** ecls; wsa_kcls** kcls;
-    int* cls_last;                                                              // 1: the last classification was one model's, 2: an ensemble's, 3: wsa_batch_regress
+    wsa_cls** cls; wsa_ecls** ecls; wsa_kcls** kcls; wsa_rcls** rcls;
+    int* cls_last;                                                              // 1: the last classification was one model's, 2: an ensemble's, 3: wsa_batch_regress, 4: wsa_batch_regress_group
 };
 extern "C" {
 void wsa_batch_view_internal(wsa_batch* b, wsa_batch_view* v);
@@ -69,6 +71,13 @@ wsa_status wsa_sknn_create(const wsa_scls_view& v, const wsa_knn* kn, uint32_t k
 void wsa_sknn_free(wsa_sknn* c);
 wsa_status wsa_sknn_enqueue(wsa_sknn* c, hipStream_t s);
 wsa_status wsa_sknn_result(wsa_sknn* c, uint32_t rows, wsa_stream_knn_result* out);
+
+// ... and, beside all of them, grouped K6 over regression heads and the fold RG-1 (wsa_stream_set_regress; regress_fold.hip)
+struct wsa_sreg;
+wsa_status wsa_sreg_create(const wsa_scls_view& v, const wsa_regress_group* g, wsa_sreg** out);     // checks the level, allocates, zeroes the carried sums
+void wsa_sreg_free(wsa_sreg* c);
+wsa_status wsa_sreg_enqueue(wsa_sreg* c, hipStream_t s);
+wsa_status wsa_sreg_result(wsa_sreg* c, uint32_t rows, wsa_stream_value_result* out);
 
 // classify.hip: NULL for the row width of an ML level (53, 264, 23), else the rest of the refusal after "the model takes N"
 const char* wsa_model_width_refusal(int n_inputs);

@@ -282,6 +282,7 @@ wsa_status wsa_batch_class_result(wsa_batch* b, void* stream, wsa_class_result* 
     wsa_cls* c = *v.cls;
     if (!c || !c->done) return fail(ctx, WSA_ERR_INVALID, "no wsa_batch_classify on this batch yet");
     if (*v.cls_last == 3) return fail(ctx, WSA_ERR_INVALID, "the batch's last model call was wsa_batch_regress: its values are wsa_batch_copy_values'");
+    if (*v.cls_last == 4) return fail(ctx, WSA_ERR_INVALID, "the batch's last model call was wsa_batch_regress_group: its tables are wsa_batch_value_result's");
     if (*v.cls_last != 1) return fail(ctx, WSA_ERR_INVALID, "the batch's last classification was an ensemble's: its tables are wsa_batch_ensemble_result's");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     wsa_device_result r;
@@ -385,6 +386,7 @@ wsa_status wsa_batch_ensemble_result(wsa_batch* b, void* stream, wsa_ensemble_re
     wsa_ctx* ctx = v.ctx;
     wsa_ecls* ec = *v.ecls;
     if (!ec) return fail(ctx, WSA_ERR_INVALID, "no wsa_batch_classify_ensemble on this batch yet");
+    if (*v.cls_last == 4) return fail(ctx, WSA_ERR_INVALID, "the batch's last model call was wsa_batch_regress_group: its tables are wsa_batch_value_result's");
     if (*v.cls_last != 2) return fail(ctx, WSA_ERR_INVALID, "the batch's last classification was one model's: its tables are wsa_batch_class_result's");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     wsa_device_result r;

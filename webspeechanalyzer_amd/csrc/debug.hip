@@ -1,5 +1,6 @@
 // debug.hip — test entries of libwsa that are NOT part of include/wsa.h: unit access to device-side pieces that the public
-// entry points only exercise through their consequences (tests/test_gpu_units.py, tests/test_gpu_coeffs.py, tests/test_gpu_utterance.py, tests/test_gpu_gate.py).
+// entry points only exercise through their consequences (tests/test_gpu_units.py, tests/test_gpu_coeffs.py, tests/test_gpu_utterance.py, tests/test_gpu_gate.py,
+// tests/test_gpu_regress_group.py).
 #include <cstring>
 #include <vector>
 #include "host_plan.hpp"
@@ -8,6 +9,7 @@
 #include "gate_floor.hpp"
 #include "tracker_score.hpp"
 #include "tracker_features.hpp"
+#include "regress_internal.hpp"
 
 namespace wsa {
 // fn 0: jsm::log10(x[i]); fn 1: jsm::pow_pos(x[i], y[i]) — the V8 Math.log10 / Math.pow ports the noise gate's
@@ -192,6 +194,106 @@ extern "C" int wsa_debug_batch_tiers(wsa_batch* b, void* stream, uint32_t* out3)
     if (hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)) != hipSuccess || hipMemcpy(c, d, sizeof(c), hipMemcpyDeviceToHost) != hipSuccess) return WSA_ERR_HIP;
     out3[0] = c[1]; out3[1] = c[5]; out3[2] = c[6];       // d_counters[1]: flags; [4 + 1]: spans (span_order_kernel); [4 + 2]: TrParams::redo_count
     return WSA_OK;
+}
+
+// RG-1 (csrc/regress_fold.hpp) on its own: hand-built row meta [n_rows][8] i32 (slot 0 the clip or stream, 1 si, 3 len) and H value columns
+// values [H][n_rows] f64 straight into the batch fold or the stream-step fold; no audio, no model.
+//   n_steps == 0, a batch of n clips: row_off [n + 1].  Out: n_cb [1]; cb [cb_cap][4]; cb_value, cb_weight [H][cb_cap]; run_sum, run_weight,
+//   run_value [H][n].
+//   n_steps > 0, n streams: the tables hold the steps' rows one step after the other; row_off [n_steps][n + 1] counts from each step's first row
+//   (row_off[k][n] = the rows of step k), ctl [n_steps][n] the steps' control bytes (WSA_STREAM_START resets the stream's sums; a stream
+//   without rows in a step is idle whatever its byte says otherwise).  The running sums start from zero and are carried from
+//   step to step on the device.  Out: n_cb [n_steps]; the steps' callbacks one step after the other in cb, cb_value, cb_weight (first rows count
+//   from their step's first row); run_* [n_steps][H][n], as each step leaves them.
+// Every slot of cb_value / cb_weight / cb that no callback fills keeps what the caller put there.  Refused, nothing run and nothing written:
+// whatever would make a kernel read or write outside these tables.
+extern "C" int wsa_debug_regress_fold(int32_t device, const int32_t* meta, const double* values, uint32_t n_rows, uint32_t H, double step_s, uint32_t n,
+                                      uint32_t n_steps, const uint32_t* row_off, const uint8_t* ctl, uint32_t cb_cap, uint32_t* n_cb, int32_t* cb,
+                                      double* cb_value, double* cb_weight, double* run_sum, double* run_weight, double* run_value) {
+    if (!row_off || !n_cb || !cb || !cb_value || !cb_weight || !run_sum || !run_weight || !run_value) return WSA_ERR_INVALID;
+    if ((n_rows && (!meta || !values)) || H < 1 || H > WSA_REGRESS_GROUP_MAX || n < 1 || n > (1u << 16) || n_rows > (1u << 22) || cb_cap < 1 || cb_cap > (1u << 22)) return WSA_ERR_INVALID;
+    if (n_steps > (1u << 12) || (n_steps && !ctl)) return WSA_ERR_INVALID;
+    const uint32_t tables = n_steps ? n_steps : 1;
+    uint64_t rows = 0, callbacks = 0;
+    for (uint32_t k = 0; k < tables; k++) {                        // every table: offsets in order, rows of their own clip / stream; callbacks counted
+        const uint32_t* off = row_off + (size_t)k * (n + 1);
+        if (off[0] != 0) return WSA_ERR_INVALID;
+        for (uint32_t c = 0; c < n; c++) if (off[c + 1] < off[c]) return WSA_ERR_INVALID;
+        if (rows + off[n] > n_rows) return WSA_ERR_INVALID;
+        for (uint32_t c = 0; c < n; c++)
+            for (uint32_t r = off[c]; r < off[c + 1]; r++) {
+                const int32_t* m = meta + (rows + r) * 8;
+                if (m[0] != (int32_t)c || m[3] < 0 || m[3] == 0x7fffffff) return WSA_ERR_INVALID;
+                callbacks += (r == off[c] || m[1] != m[1 - 8]) ? 1 : 0;
+            }
+        rows += off[n];
+    }
+    if (rows != n_rows || callbacks > cb_cap) return WSA_ERR_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return WSA_ERR_NO_DEVICE;
+    wsa::DevArena A;
+    int32_t *d_meta = nullptr, *d_cb = nullptr, *d_t_n = nullptr, *d_t_local = nullptr; double *d_val = nullptr, *d_cbv = nullptr, *d_cbw = nullptr, *d_tv = nullptr, *d_tw = nullptr;
+    double *d_sum = nullptr, *d_weight = nullptr, *d_value = nullptr, *d_carry_s = nullptr, *d_carry_w = nullptr;
+    uint32_t *d_off = nullptr, *d_bits = nullptr, *d_clip_cb = nullptr, *d_cb_off = nullptr, *d_count = nullptr;
+    const size_t R = n_rows ? n_rows : 1, K = cb_cap, HN = (size_t)H * n;
+    std::vector<uint32_t> bits((size_t)tables * n, 0u);
+    for (size_t i = 0; n_steps && i < bits.size(); i++) bits[i] = (ctl[i] & WSA_STREAM_START) ? 1u : 0u;      // the device control word's bit 0
+    bool ok = A.alloc(&d_meta, R * 8) && A.alloc(&d_val, (size_t)H * R) && A.upload(&d_bits, bits) && A.alloc(&d_off, (size_t)tables * (n + 1))
+           && A.alloc(&d_cb, K * 4) && A.alloc(&d_cbv, (size_t)H * K) && A.alloc(&d_cbw, (size_t)H * K) && A.alloc(&d_tv, (size_t)H * R) && A.alloc(&d_tw, (size_t)H * R)
+           && A.alloc(&d_t_n, R) && A.alloc(&d_t_local, R) && A.alloc(&d_clip_cb, (size_t)n) && A.alloc(&d_cb_off, (size_t)n) && A.alloc(&d_count, 1, true)
+           && A.alloc(&d_sum, HN) && A.alloc(&d_weight, HN) && A.alloc(&d_value, HN) && A.alloc(&d_carry_s, HN, true) && A.alloc(&d_carry_w, HN, true)
+           && (n_rows == 0 || (hipMemcpy(d_meta, meta, (size_t)n_rows * 8 * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess
+                               && hipMemcpy(d_val, values, (size_t)H * n_rows * sizeof(double), hipMemcpyHostToDevice) == hipSuccess))
+           && hipMemcpy(d_off, row_off, (size_t)tables * (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess
+           && hipMemcpy(d_cb, cb, K * 4 * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess
+           && hipMemcpy(d_cbv, cb_value, (size_t)H * K * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
+           && hipMemcpy(d_cbw, cb_weight, (size_t)H * K * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) return WSA_ERR_HIP;
+    if (!n_steps) {
+        wsa_regress::RegressFoldParams p{};
+        p.n_clips = n; p.H = H; p.stride = (uint32_t)R; p.step_s = step_s; p.meta = d_meta; p.row_off = d_off;
+        for (uint32_t h = 0; h < H; h++) p.value[h] = d_val + (size_t)h * n_rows;
+        p.t_value = d_tv; p.t_weight = d_tw; p.t_n = d_t_n; p.t_local = d_t_local; p.clip_cb = d_clip_cb; p.cb_off = d_cb_off;
+        p.clip_sum = d_sum; p.clip_weight = d_weight; p.clip_value = d_value; p.cb = d_cb; p.host = d_count;
+        // (the compaction's tables have the rows' stride; the callbacks come out through a staging pair of that stride)
+        double *d_kv = nullptr, *d_kw = nullptr;
+        ok = A.alloc(&d_kv, (size_t)H * R) && A.alloc(&d_kw, (size_t)H * R);
+        p.cb_value = d_kv; p.cb_weight = d_kw;
+        if (ok) wsa_regress::launch_regress_fold(p, nullptr);
+        ok = ok && hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess
+             && hipMemcpy(n_cb, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess;
+        for (uint32_t h = 0; ok && h < H; h++)
+            ok = callbacks == 0 || (hipMemcpy(cb_value + (size_t)h * K, d_kv + (size_t)h * R, callbacks * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess
+                                    && hipMemcpy(cb_weight + (size_t)h * K, d_kw + (size_t)h * R, callbacks * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess);
+        ok = ok && (callbacks == 0 || hipMemcpy(cb, d_cb, callbacks * 4 * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess)
+             && hipMemcpy(run_sum, d_sum, HN * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess
+             && hipMemcpy(run_weight, d_weight, HN * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess
+             && hipMemcpy(run_value, d_value, HN * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+        return ok ? WSA_OK : WSA_ERR_HIP;
+    }
+    uint64_t row0 = 0, cb0 = 0;
+    for (uint32_t k = 0; ok && k < n_steps; k++) {
+        const uint32_t step_rows = row_off[(size_t)k * (n + 1) + n];
+        wsa_regress::RegressStepParams p{};
+        p.n = n; p.H = H; p.stride = (uint32_t)K; p.cap = 0; p.fold = 1; p.step_s = step_s;       // cap 0: nothing goes to a D2H window
+        p.meta = d_meta + row0 * 8; p.row_off = d_off + (size_t)k * (n + 1); p.bits = d_bits + (size_t)k * n;
+        for (uint32_t h = 0; h < H; h++) p.value[h] = d_val + (size_t)h * n_rows + row0;
+        p.run_sum = d_carry_s; p.run_weight = d_carry_w;
+        p.cb = d_cb + cb0 * 4; p.cb_value = d_cbv + cb0; p.cb_weight = d_cbw + cb0;                // this step's callbacks behind the earlier steps'
+        p.h_value = nullptr; p.h_cb = nullptr; p.h_cb_value = nullptr; p.h_cb_weight = nullptr;
+        p.h_sum = d_sum; p.h_weight = d_weight; p.h_run_value = d_value; p.h_count = d_count;
+        wsa_regress::launch_regress_step(p, nullptr);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess
+             && hipMemcpy(n_cb + k, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess
+             && hipMemcpy(run_sum + (size_t)k * HN, d_sum, HN * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess
+             && hipMemcpy(run_weight + (size_t)k * HN, d_weight, HN * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess
+             && hipMemcpy(run_value + (size_t)k * HN, d_value, HN * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+        if (ok && cb0 + n_cb[k] > callbacks) return WSA_ERR_HIP;                                    // (cannot happen: the host counted them)
+        row0 += step_rows; cb0 += ok ? n_cb[k] : 0;
+    }
+    ok = ok && hipMemcpy(cb, d_cb, K * 4 * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess
+         && hipMemcpy(cb_value, d_cbv, (size_t)H * K * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess
+         && hipMemcpy(cb_weight, d_cbw, (size_t)H * K * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+    return ok ? WSA_OK : WSA_ERR_HIP;
 }
 
 // K4 (csrc/utterance.hip) on its own: hand-built segments, syllable rows and frames straight into ONE launch_utterance, in the batch geometry

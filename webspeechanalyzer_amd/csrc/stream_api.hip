@@ -65,6 +65,7 @@ struct wsa_stream {
     wsa_scls* scls = nullptr;               // the attached classifier's tables and carried fold (wsa_stream_set_model), or NULL
     wsa_sens* sens = nullptr;               // ... or the attached ensemble's (wsa_stream_set_ensemble); never both
     wsa_sknn* sknn = nullptr;               // the attached KNN store's tables, scratch and carried fold (wsa_stream_set_knn), beside either
+    wsa_sreg* sreg = nullptr;               // the attached regression group's tables and carried sums (wsa_stream_set_regress), beside all of them
     uint32_t in_stride = 0, ctl_words = 3;  // floats per stream in the input buffers (a plain set: step_samples), control words per stream
     // a mixed set (wsa_stream_create_mixed): F above is the step's internal frame CAPACITY (resample_step_frames_bound), F_user the caller's frames_per_step
     bool mixed = false;
@@ -134,6 +135,7 @@ void wsa_stream_destroy(wsa_stream* b) {
     wsa_scls_free(b->scls);
     wsa_sens_free(b->sens);
     wsa_sknn_free(b->sknn);
+    wsa_sreg_free(b->sreg);
     delete b;                               // (the arena frees the rest)
 }
 
@@ -341,6 +343,10 @@ static wsa_status enqueue_step(wsa_stream* b, const float* d_pcm, uint64_t strid
     }
     if (b->sknn) {                         // K9s (partial, merge), then the push / KN-2 fold kernel
         const wsa_status st = wsa_sknn_enqueue(b->sknn, s);
+        if (st != WSA_OK) return st;
+    }
+    if (b->sreg) {                         // the grouped K6 over the regression heads, then the push / RG-1 fold kernel
+        const wsa_status st = wsa_sreg_enqueue(b->sreg, s);
         if (st != WSA_OK) return st;
     }
     hipLaunchKernelGGL(stream_push_kernel, dim3(16), dim3(256), 0, s, b->be.d_totals, b->be.d_counters, b->be.d_meta, b->be.d_feat, b->be.d_seg,
@@ -647,6 +653,33 @@ wsa_status wsa_stream_knn_classes(wsa_stream* b, wsa_stream_knn_result* out) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(b->last_stream ? b->last_stream : b->own));
     return wsa_sknn_result(b->sknn, b->h_totals[0], out);
+}
+
+wsa_status wsa_stream_set_regress(wsa_stream* b, const wsa_regress_group* g) {
+    if (!b) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = b->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (b->stepped) HIP_TRY(ctx, hipStreamSynchronize(b->last_stream ? b->last_stream : b->own));     // the last step may still read the tables
+    wsa_sreg* n = nullptr;
+    if (g) {
+        const wsa_scls_view v{ctx, ctx->cfg.output_level, b->n, b->rows_cap, b->d2h_rows, b->be.d_meta, b->be.d_feat, b->be.d_row_off, b->be.d_totals, b->d_ctl + 2 * (size_t)b->n};
+        const wsa_status st = wsa_sreg_create(v, g, &n);
+        if (st != WSA_OK) return st;
+    }
+    if (b->gexec) { (void)hipGraphExecDestroy(b->gexec); b->gexec = nullptr; }         // the next step recaptures with (or without) the group's kernels
+    wsa_sreg_free(b->sreg);
+    b->sreg = n;                                                                       // (a model, an ensemble and a KNN store stay attached)
+    return WSA_OK;
+}
+
+wsa_status wsa_stream_values(wsa_stream* b, wsa_stream_value_result* out) {
+    if (!b || !out) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = b->ctx;
+    if (!b->sreg) return fail(ctx, WSA_ERR_INVALID, "no regression group attached to these streams (wsa_stream_set_regress)");
+    if (!b->stepped) return fail(ctx, WSA_ERR_INVALID, "no step on this stream object yet");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(b->last_stream ? b->last_stream : b->own));
+    return wsa_sreg_result(b->sreg, b->h_totals[0], out);
 }
 
 wsa_status wsa_stream_ensemble_classes(wsa_stream* b, wsa_stream_ensemble_result* out) {

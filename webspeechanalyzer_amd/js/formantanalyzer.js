@@ -423,6 +423,69 @@ function knn_fold_into(nat, ctx, res, pred) {
   const t = nat.batchKnn(ctx, knn_store_on(nat, ctx, pred.knn), pred.k), f = nat.batchKnnFold(ctx);
   res.prob = t.conf; res.nClasses = t.nClasses; res.cb = f.cb; res.cbLabel = f.cbLabel; res.cbConf = f.cbConf; res.clipConf = f.clipConf;
 }
+// setPredictionValues(handles | null, on_values): 1 .. 8 regression handles (loadModel of an ords_<label> directory, or trainRegression) — the app's V, A and D
+// models — predicted in one grouped launch and folded per callback by specification RG-1 (DESIGN.md §3; ours: the reference wires `?type=ords` up, ref
+// src/index.js:892-893, and its fold then sums fields a regression result does not have, ref src/prediction.js:96-101).  Every level-13 LaunchBatch /
+// LaunchBatches launch and every StreamOpen set opened from here on calls, on the JS thread and in callback order, right after each segment's callback
+// (and its on_prediction, if a prediction model is set too),
+//     on_values(si, values[H], clip_or_stream_index, {weights, per_syllable, running})
+// values[h] = the callback's sqrt(duration)-weighted mean of head h's per-syllable values (NaN: no usable row), weights[h] the sum of the weights,
+// per_syllable[q][h] the rows' own values, running[h] the running weighted mean of the clip (or of the stream since its START) after this callback.
+// A skipped callback (durations that sum to 0) gets no call, as on_prediction does not.  Independent of setPredictionModel, setPredictionModels and
+// setPredictionKnn: it neither replaces them nor is replaced by them.
+let value_prediction = null;
+function setPredictionValues(handles, on_values) {
+  if (handles === null || handles === undefined) { value_prediction = null; return; }
+  if (!Array.isArray(handles) || handles.length < 1 || handles.length > 8) throw 'setPredictionValues([handles] | null, on_values): 1 .. 8 regression model handles';
+  for (const h of handles) if (!loaded_models.has(h) || h.released) throw 'setPredictionValues: a model handle was released (shutdown()) or is not one of loadModel / trainRegression';
+  for (const h of handles) if (typeof h.spec.outMin !== 'number') throw 'setPredictionValues: a classifier has no value to fold; setPredictionModel takes it';
+  for (const h of handles) if (h.spec.units[0] !== 53) throw 'setPredictionValues: a model takes ' + h.spec.units[0] + ' inputs; live prediction folds the 53-feature syllable rows of output_level 13';
+  if (typeof on_values !== 'function') throw 'setPredictionValues([handles] | null, on_values)';
+  value_prediction = { models: handles.slice(), on_values };
+}
+// the native models and ranges of the value heads on one context (a model is created at its first use there)
+function value_heads_on(nat, ctx, vp) {
+  const models = vp.models.map((h) => {
+    if (h.released) throw 'a value model was released (shutdown())';
+    let m = h.natives.get(ctx);
+    if (!m) { m = nat.modelCreate(ctx, h.spec); h.natives.set(ctx, m); }
+    return m;
+  });
+  return [models, Float64Array.from(vp.models, (h) => h.spec.outMin), Float64Array.from(vp.models, (h) => h.spec.outMax)];
+}
+// the grouped launch + RG-1 over the rows of the batch a context has just finished
+function values_fold_into(nat, ctx, res, vp) {
+  res.reg = nat.batchRegressGroup(ctx, ...value_heads_on(nat, ctx, vp));
+}
+// RG-1's running sums per unit (clip / stream), kept here by the specification's own rule from the device's per-row values, so that the running value
+// exists after EVERY callback (the device hands out each unit's last state); JavaScript's doubles round as the device's do, so the last one is the device's
+function values_after(G, meta, r, si, unit, vp, accs) {
+  if (!G.cbIndex) { G.cbIndex = new Map(); for (let k = 0; k < G.cb.length / 4; k++) G.cbIndex.set(G.cb[k * 4 + 2], k); }
+  const k = G.cbIndex.get(r);
+  if (k === undefined) return;
+  const H = G.nHeads, K = G.cb.length / 4, R = G.value.length / H, n = G.cb[k * 4 + 3], step = settings.window_step / 1e3;
+  const d = Array.from({ length: n }, (_, q) => parseFloat(((meta[(r + q) * 8 + 3] + 1) * step).toFixed(3)));
+  let seg_weight = 0;
+  for (const x of d) seg_weight += x;
+  if (!(seg_weight > 0)) return;                                 // skipped: no call, the running sums untouched
+  if (!accs.get(unit)) accs.set(unit, { A: new Array(H).fill(0), B: new Array(H).fill(0) });
+  const acc = accs.get(unit);
+  const per = Array.from({ length: n }, (_, q) => Array.from({ length: H }, (_, h) => G.value[h * R + r + q]));
+  for (let h = 0; h < H; h++)
+    for (let q = 0; q < n; q++) {
+      const v = per[q][h], w = Math.sqrt(d[q]);
+      if (!Number.isFinite(v)) continue;
+      const t = v * w;
+      acc.A[h] += t; acc.B[h] += w;
+    }
+  vp.on_values(si, Array.from({ length: H }, (_, h) => G.cbValue[h * K + k]), unit,
+    { weights: Array.from({ length: H }, (_, h) => G.cbWeight[h * K + k]), per_syllable: per, running: acc.A.map((a, h) => (acc.B[h] !== 0 ? a / acc.B[h] : NaN)) });
+}
+// clip c's {sum, weight, value}, one entry per head, from a batch's RG-1 tables
+function clip_values_of(G, c) {
+  const H = G.nHeads, N = G.clipValue.length / H, at = (t) => Array.from({ length: H }, (_, h) => t[h * N + c]);
+  return { sum: at(G.clipSum), weight: at(G.clipWeight), value: at(G.clipValue) };
+}
 function saveModel(handle, dir) {
   if (!handle || !handle.spec) throw 'saveModel(handle, dir)';
   require('./trainmodel.js').saveModelFiles(handle.spec, dir);
@@ -450,7 +513,7 @@ function release_models() {           // shutdown(): the native models go with t
   for (const h of loaded_models) { h.released = true; h.natives.clear(); }
   loaded_models.clear();
   knn_natives.clear();                  // (the stores went with their contexts)
-  prediction = null;
+  prediction = null; value_prediction = null;
 }
 function model_on(nat, ctx) {         // the native model of the prediction model on one context (created at its first use there)
   if (!prediction || prediction.knn || settings.output_level !== 13) return undefined;
@@ -549,7 +612,7 @@ function ensemble_meters_of(res, unit, pred, accs_of) {
 }
 
 // rows of one clip -> the reference's callback sequence (ref dispatcher P() @B28869)
-function dispatch(res, clip, callback, label, pred = null, clip_index = clip) {
+function dispatch(res, clip, callback, label, pred = null, clip_index = clip, vp = null) {
   const level = settings.output_level, step = settings.window_step / 1e3;
   const a = res.rowOff[clip], b = res.rowOff[clip + 1];
   const feat = (r) => Array.from(res.feat.subarray(r * 53, r * 53 + 53));
@@ -578,6 +641,7 @@ function dispatch(res, clip, callback, label, pred = null, clip_index = clip) {
       if (feats.length > 0) {
         if (callback) callback(si, label, times, feats);                                      // ref @B29138 (`p[e].length>0`)
         if (pred && has_cb(res) && level === 13) predict_after(res, r - times.length, si, clip_index, pred);       // ref src/index.js:56 -> prediction.js:70
+        if (vp && res.reg && res.reg.cb && level === 13) values_after(res.reg, res.meta, r - times.length, si, clip_index, vp, res.regAccs || (res.regAccs = new Map()));
       }
     }
   } else if (level === 11) {
@@ -710,12 +774,18 @@ async function run(clips, callback, labels_of, test_play) {
     if (pred && pred.knn) {
       try { results.forEach((res, i) => knn_fold_into(nat, ctxs[i], res, pred)); } catch (e) { drop_contexts(nat); throw e; }
     }
+    const vp = value_prediction && settings.output_level === 13 ? value_prediction : null;
+    if (vp) {
+      try { results.forEach((res, i) => values_fold_into(nat, ctxs[i], res, vp)); } catch (e) { drop_contexts(nat); throw e; }
+    }
     // StopAudioNodes while the work was in flight: the reference tears the nodes down at the next frame and resolves (ref @B8851) —
     // nothing is dispatched any more, the launch still resolves
-    if (!test_play && (callback || pred)) {                                                   // ref @B24762: silent when test_play
+    if (!test_play && (callback || pred || vp)) {                                             // ref @B24762: silent when test_play
       for (let i = 0; i < shards.length && !stop_requested; i++)
-        for (let c = shards[i][0]; c < shards[i][1] && !stop_requested; c++) dispatch(results[i], c - shards[i][0], callback, labels_of(c), pred, c);
+        for (let c = shards[i][0]; c < shards[i][1] && !stop_requested; c++) dispatch(results[i], c - shards[i][0], callback, labels_of(c), pred, c, vp);
     }
+    // per clip: the device's running sums and value of every head (not `values`: results is an Array)
+    if (vp) results.head_values = [].concat(...shards.map(([a, b], i) => Array.from({ length: b - a }, (_, c) => clip_values_of(results[i].reg, c))));
     if (pred && pred.models) {
       // (dispatch numbers the clips of all shards 0 .. n - 1, a shard's tables its own from 0)
       results.meters = [].concat(...shards.map(([a, b], i) => Array.from({ length: b - a }, (_, c) =>
@@ -757,7 +827,7 @@ function LaunchBatch(clips, callback = null, labels = [], test_play = false) {
     const cb = callback ? (si, label, t, f) => callback(si, label, t, f, current) : null;
     const labels_of = (c) => { current = c; return labels[c] || []; };
     run(list, cb, labels_of, test_play).then((rs) => resolve(Object.assign({ rows: rs.reduce((t, r) => t + r.meta.length / 8, 0), segments: rs.reduce((t, r) => t + r.segments.length / 4, 0),
-      stageMs: Array.from(rs[0].stageMs), shards: rs.length, stopped: stop_requested }, rs.meters ? { meters: rs.meters } : {},
+      stageMs: Array.from(rs[0].stageMs), shards: rs.length, stopped: stop_requested }, rs.meters ? { meters: rs.meters } : {}, rs.head_values ? { values: rs.head_values } : {},
       rs.min_entropy_db ? { min_entropy_db: rs.min_entropy_db, shown_min_entropy_db: rs.shown_min_entropy_db } : {})),
       (e) => reject(typeof e === 'string' ? e : String(e.message || e)));
   });
@@ -793,8 +863,10 @@ async function run_batches(batches, callback, labels, test_play) {
     const ctxs = pipe_contexts(nat);
     const pred = prediction && settings.output_level === 13 ? prediction : null;
     const models = ctxs.map((c) => (pred ? model_on(nat, c) : undefined));
+    const vp = value_prediction && settings.output_level === 13 ? value_prediction : null;
     const meters = pred ? [] : null;
     const mdbs = pred && pred.models ? [] : null;          // per batch and clip: the clip's min_entropy_db (null: none)
+    const vals = vp ? [] : null;                           // per batch and clip: the value heads' {sum, weight, value}
     const lists = batches.map((b) => b.map(to_pcm));
     const bands = settings.spec_type === 1 ? settings.N_mel_bins : settings.N_fft_bins;
     const start = (k) => {
@@ -824,21 +896,26 @@ async function run_batches(batches, callback, labels, test_play) {
       if (pred && pred.knn) {               // (context k % 2 is idle until batch k + 2 starts)
         try { knn_fold_into(nat, ctxs[k % 2], res, pred); } catch (e) { if (next) { try { await next; } catch (e2) { /* the first failure is reported */ } } drop_pipe_contexts(nat); throw e; }
       }
+      if (vp) {                             // (likewise)
+        try { values_fold_into(nat, ctxs[k % 2], res, vp); } catch (e) { if (next) { try { await next; } catch (e2) { /* the first failure is reported */ } } drop_pipe_contexts(nat); throw e; }
+      }
       rows += res.meta.length / 8; segments += res.segments.length / 4; done++;
-      if (!test_play && (callback || pred) && !stop_requested) {                              // ref @B24762: silent when test_play
+      if (!test_play && (callback || pred || vp) && !stop_requested) {                              // ref @B24762: silent when test_play
         const lb = labels[k] || [];
         for (let c = 0; c < lists[k].length && !stop_requested; c++) {
           const cb = callback ? (si, label, t, f) => callback(si, label, t, f, c, k) : null;
           const pk = pred ? { model: pred.model, models: pred.models, state: pred.state, on_prediction: (si, lc, ci, per) => pred.on_prediction(si, lc, ci, per, k) } : null;
-          dispatch(res, c, cb, lb[c] || [], pk, c);
+          const vk = vp ? { on_values: (si, v, ci, detail) => vp.on_values(si, v, ci, detail, k) } : null;
+          dispatch(res, c, cb, lb[c] || [], pk, c, vk);
         }
       }
+      if (vals) vals.push(Array.from({ length: lists[k].length }, (_, c) => clip_values_of(res.reg, c)));
       if (meters) meters.push(Array.from({ length: lists[k].length }, (_, c) => (pred.models ? ensemble_meters_of(res, c, pred, res.ensAccs) : meters_of(res, c, pred.model.labels))));
       if (mdbs) mdbs.push(Array.from(res.ens.minDb.subarray(0, lists[k].length), (v) => (v >= 0 ? v : null)));
       if (stop_requested && next) { try { await next; } catch (e) { /* stopping */ } next = null; done++; break; }
     }
     return Object.assign({ rows, segments, batches: done, stopped: stop_requested }, meters ? { meters } : {},
-      mdbs ? { min_entropy_db: mdbs, shown_min_entropy_db: pred.state.min_db } : {});
+      vals ? { values: vals } : {}, mdbs ? { min_entropy_db: mdbs, shown_min_entropy_db: pred.state.min_db } : {});
   } finally {
     playing = false;
   }
@@ -880,6 +957,7 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
   if (new Set(rates).size !== 1 && !convert) throw 'All streams of one set must share a sample rate (configure resample_to to convert each from its own)';
   const fs_an = convert ? settings.resample_to : rates[0];      // the rate the analysis runs at (K0s converts inside the step)
   const pred = prediction && level === 13 ? prediction : null;
+  const vp = value_prediction && level === 13 ? value_prediction : null;
   const ctx = nat.create(native_config(), settings.device);
   let st;
   try {
@@ -891,9 +969,11 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
     if (pred && pred.knn) nat.streamSetKnn(st, knn_store_on(nat, ctx, pred.knn), pred.k);
     else if (pred && pred.models) nat.streamSetEnsemble(st, model_on(nat, ctx));
     else if (pred) nat.streamSetModel(st, model_on(nat, ctx));       // the native model on the stream's own context (ref src/index.js:56)
+    if (vp) nat.streamSetRegress(st, ...value_heads_on(nat, ctx, vp));
   } catch (e) {
     if (st) nat.streamClose(st);
     if (pred) forget_natives(pred, ctx);
+    if (vp) for (const h of vp.models) h.natives.delete(ctx);
     nat.destroy(ctx); throw (typeof e === 'string' ? e : String(e.message || e));
   }
   const input = nat.streamInput(st);
@@ -902,6 +982,9 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
   // the step's KNN tables under the names predict_after and meters_of read a model's by
   const knn_view = (res) => ({ cb: res.knnCb, cbLabel: res.knnCbLabel, cbConf: res.knnCbConf, prob: res.knnConf, nClasses: res.knnNClasses });
   const spred = pred && pred.knn ? { model: { labels: names }, on_prediction: pred.on_prediction } : pred && pred.models ? { models: pred.models, state: pred.state, on_prediction: pred.on_prediction, accs: new Map() } : pred;   // accs: per stream, since its START
+  const reg_accs = new Map();                         // value heads: RG-1's running sums per stream, since its START
+  const reg_view = (res) => ({ cb: res.regCb, cbValue: res.regCbValue, cbWeight: res.regCbWeight, value: res.regValue, nHeads: res.regNHeads });
+  let values = null;                                    // ... and of the value heads
   let open = true, started = false, meters = null;      // meters: the per-stream Label_conf_all of the last step (a prediction model only)
   const stopped = new Uint8Array(n_streams);          // streams that have had their segment_truncate since their last START
   const seg_seen = new Uint32Array(n_streams);        // level 3: segments a stream has closed since its last START (the callback index, ref @B28273)
@@ -921,7 +1004,7 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
         const m = res.uttMeta.subarray(k * 4, k * 4 + 4);
         callback(0, labels[m[0]] || [], [m[2] * step, (m[3] + 1) * step], Array.from(res.uttFeat.subarray(k * 264, k * 264 + 264)), m[0]);   // ref Y() @B31330
       }
-    } else if (callback || (pred && level === 13)) {
+    } else if (callback || ((pred || vp) && level === 13)) {
       let r = 0;
       while (r < rows) {
         const s = res.meta[r * 8], si = res.meta[r * 8 + 1];
@@ -951,6 +1034,7 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
             if (callback) callback(si, labels[s] || [], times, feats, s);                                                      // ref @B29138 (`p[e].length>0`)
             if (pred && pred.knn) { if (res.knnCb) { res.knnView = res.knnView || knn_view(res); predict_after(res.knnView, r - times.length, si, s, spred); } }
             else if (pred && has_cb(res) && level === 13) predict_after(res, r - times.length, si, s, spred);                         // ref prediction.js:70
+            if (vp && res.regCb) { res.regView = res.regView || reg_view(res); values_after(res.regView, res.meta, r - times.length, si, s, vp, reg_accs); }
           }
         }
       }
@@ -963,6 +1047,10 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
       out.min_entropy_db = Array.from(res.ens.minDb, (v) => (v >= 0 ? v : null));
       out.shown_min_entropy_db = pred.state.min_db;
     } else if (pred && res.streamConf) meters = out.meters = Array.from({ length: n_streams }, (_, s) => meters_of({ nClasses: res.nClasses, clipConf: res.streamConf }, s, pred.model.labels));
+    if (vp && res.regRunValue) {        // per stream: the device's running sums and value of every head
+      const H = res.regNHeads, at = (t, s) => Array.from({ length: H }, (_, h) => t[h * n_streams + s]);
+      values = out.values = Array.from({ length: n_streams }, (_, s) => ({ sum: at(res.regSum, s), weight: at(res.regWeight, s), value: at(res.regRunValue, s) }));
+    }
     return out;
   };
   const handle = {
@@ -975,7 +1063,7 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
       for (let i = 0; i < n_streams; i++) {
         c[i] = ctl ? ctl[i] : (STREAM_ACTIVE | (started ? 0 : STREAM_START));
         if (handle.stopPending && !stopped[i]) c[i] |= STREAM_STOP;
-        if (c[i] & STREAM_START) { stopped[i] = 0; seg_seen[i] = 0; if (spred && spred.accs) spred.accs.delete(i); }
+        if (c[i] & STREAM_START) { stopped[i] = 0; seg_seen[i] = 0; if (spred && spred.accs) spred.accs.delete(i); reg_accs.delete(i); }
         if (c[i] & STREAM_STOP) stopped[i] = 1;
       }
       started = true;
@@ -987,7 +1075,7 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
     // segment a source is in the middle of is reported like the reference reports it when its nodes are disconnected
     close(flush = true) {
       if (!open) return { rows: 0, segments: 0 };
-      let out = Object.assign({ rows: 0, segments: 0 }, meters ? { meters } : {});
+      let out = Object.assign({ rows: 0, segments: 0 }, meters ? { meters } : {}, values ? { values } : {});
       if (flush && started && stopped.some((v) => !v)) {
         const c = new Uint8Array(n_streams);
         for (let i = 0; i < n_streams; i++) if (!stopped[i]) { c[i] = STREAM_STOP; stopped[i] = 1; }
@@ -996,6 +1084,7 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
       open = false; open_streams.delete(handle);
       nat.streamClose(st);                             // detaches `input`: the pinned buffer is gone; releases the model
       if (pred) forget_natives(pred, ctx);              // the native models go with the stream's context
+      if (vp) for (const h of vp.models) h.natives.delete(ctx);
       nat.destroy(ctx);
       return out;
     },
@@ -1020,5 +1109,5 @@ function set_predicted_label_for_segment(si, idx, label) {                      
 
 module.exports = { configure, LaunchAudioNodes, StopAudioNodes, set_predicted_label_for_segment, LaunchBatch, LaunchBatches,
   StreamOpen, STREAM_ACTIVE, STREAM_START, STREAM_STOP, shutdown, allocPinned, freePinned,
-  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, loadModel, setPredictionModel, setPredictionModels, setPredictionKnn, trainModel, saveModel, trainRegression, predictValues, predictDB, statsTable,
+  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, _values_after: values_after, loadModel, setPredictionModel, setPredictionModels, setPredictionKnn, setPredictionValues, trainModel, saveModel, trainRegression, predictValues, predictDB, statsTable,
   KNNClassifier, trainKnn, predictKnn };

@@ -22,6 +22,10 @@
  *       one hipGraph launch, well under a millisecond, so it runs on the calling thread; counts: samples per stream in this step, else paced)
  *   processBatch(..., [models])                 (8th argument an array of models: wsa_batch_classify_ensemble; the result gains `ens`)
  *   streamSetEnsemble(stream, [models] | null)  (wsa_stream_set_ensemble: streamStep results gain `ens`)
+ *   streamSetRegress(stream, [models] | null, outMin: Float64Array, outMax: Float64Array)   (wsa_stream_set_regress: streamStep results gain regValue [H][rows], regCb, regCbValue / regCbWeight
+ *                                               [H][callbacks], regSum / regWeight / regRunValue [H][streams], regNHeads; the stream object owns the group it makes of the models)
+ *   batchRegressGroup(ctx, [models], outMin, outMax) -> the same tables (value, cb, cbValue, cbWeight, clipSum, clipWeight, clipValue, nHeads) over the rows of the context's last
+ *                                               processBatch (wsa_batch_regress_group on its kept plan; specification RG-1)
  *   streamSetKnn(stream, knn | null, k)         (wsa_stream_set_knn: streamStep results gain knnLabel, knnConf, knnCb, knnCbLabel, knnCbConf, knnStreamConf, knnNClasses;
  *                                                beside a model or an ensemble, not in place of one)
  *   streamSetModel(stream, model | null)        (wsa_stream_set_model: streamStep results gain prob, cb, cbLabel, cbConf, streamConf, nClasses)
@@ -108,6 +112,9 @@ typedef struct {
      * kept plan keeps its ensemble tables too; made and replaced by the job (one job at a time uses a context), dropped by destroy() */
     wsa_ensemble *ens; struct model_box *ens_models[WSA_ENSEMBLE_MAX]; uint32_t ens_n;
     struct knn_box *knns;         /* the KNN stores created on this context (knnCreate): destroy() destroys them with it */
+    /* the regression group of the last batchRegressGroup call (wsa_regress_group_create over reg_models and their ranges): a call with the same models
+     * and ranges reuses it, so the kept plan keeps its group tables and allocates nothing; replaced by the next other list, dropped by destroy() */
+    wsa_regress_group *reg; struct model_box *reg_models[WSA_REGRESS_GROUP_MAX]; double reg_lo[WSA_REGRESS_GROUP_MAX], reg_hi[WSA_REGRESS_GROUP_MAX]; uint32_t reg_n;
 } ctx_box;
 /* What JS holds for a model (wsa_model): like the context's box it outlives the model, so that a handle used after modelDestroy() or after its
  * context's destroy() finds NULL; `busy` counts the jobs that classify with it (modelDestroy() refuses meanwhile) */
@@ -125,6 +132,10 @@ static void knn_unlink(knn_box *kb) {
 static void box_drop_ensemble(ctx_box *b) {
     if (b->ens) wsa_ensemble_destroy(b->ens);
     b->ens = NULL; b->ens_n = 0;
+}
+static void box_drop_regress(ctx_box *b) {
+    if (b->reg) wsa_regress_group_destroy(b->reg);
+    b->reg = NULL; b->reg_n = 0;
 }
 static void box_drop_plan(ctx_box *b) {
     if (b->plan) wsa_batch_destroy(b->plan);
@@ -175,6 +186,7 @@ static napi_value fn_destroy(napi_env env, napi_callback_info info) {
         pthread_mutex_unlock(&g_gather_lock);
         box_drop_plan(b);
         box_drop_ensemble(b);                /* (before its models) */
+        box_drop_regress(b);
         while (b->models) { model_box *mb = b->models; wsa_model_destroy(mb->m); mb->m = NULL; model_unlink(mb); }     /* models go before their context */
         while (b->knns) { knn_box *kb = b->knns; wsa_knn_destroy(kb->k); kb->k = NULL; knn_unlink(kb); }               /* and so do KNN stores */
         if (b->queue) { wsa_queue_destroy(b->ctx, b->queue); b->queue = NULL; }
@@ -447,6 +459,15 @@ static napi_value make_typed(napi_env env, napi_typedarray_type type, const void
     return ta;
 }
 
+/* H tables of `count` doubles each as one Float64Array [H][count] */
+static napi_value make_heads(napi_env env, const double *const *src, uint32_t H, size_t count) {
+    napi_value ab, ta; void *data = NULL;
+    if (napi_create_arraybuffer(env, (size_t)H * count * 8, &data, &ab) != napi_ok) return NULL;
+    for (uint32_t h = 0; count && h < H; h++) memcpy((double *)data + (size_t)h * count, src[h], count * 8);
+    if (napi_create_typedarray(env, napi_float64_array, (size_t)H * count, ab, 0, &ta) != napi_ok) return NULL;
+    return ta;
+}
+
 static void job_complete(napi_env env, napi_status status, void *data) {
     job_t *j = (job_t *)data;
     if (j->box && j->box->children) j->box->children--;
@@ -695,7 +716,7 @@ static napi_value fn_gather_rows(napi_env env, napi_callback_info info) {
 }
 
 /* ---- streams ---- */
-typedef struct { wsa_stream *st; wsa_ctx *ctx; ctx_box *box; uint32_t n, sps; napi_ref input_ref; model_box *model; wsa_ensemble *ens; model_box *ens_models[WSA_ENSEMBLE_MAX]; uint32_t n_ens; struct knn_box *knn; } stream_t;   /* input_ref: the ArrayBuffer over the pinned input, detached at close; model: attached classifier (holds its busy count) */
+typedef struct { wsa_stream *st; wsa_ctx *ctx; ctx_box *box; uint32_t n, sps; napi_ref input_ref; model_box *model; wsa_ensemble *ens; model_box *ens_models[WSA_ENSEMBLE_MAX]; uint32_t n_ens; struct knn_box *knn; wsa_regress_group *reg; model_box *reg_models[WSA_REGRESS_GROUP_MAX]; uint32_t n_reg; } stream_t;   /* input_ref: the ArrayBuffer over the pinned input, detached at close; model: attached classifier (holds its busy count) */
 static void stream_finalize(napi_env env, void *data, void *hint) { /* explicit streamClose() only */ }
 static stream_t *get_stream(napi_env env, napi_value v) {
     void *p = NULL; if (napi_get_value_external(env, v, &p) != napi_ok) return NULL; return (stream_t *)p;
@@ -866,12 +887,31 @@ static napi_value fn_stream_step(napi_env env, napi_callback_info info) {
                             c.cb, c.cb_db, c.cb_top_label, c.cb_min_db, c.stream_min_db, c.cb_top_conf, c.cb_entropy};
         napi_set_named_property(env, o, "ens", ens_object(env, &v));
     }
+    if (h->reg) {                                   /* the attached regression group's tables of this step (level 13: the fold RG-1; regSum / regWeight / regRunValue per stream, carried) */
+        wsa_stream_value_result c;
+        if (wsa_stream_values(h->st, &c) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(h->ctx)); return NULL; }
+        napi_set_named_property(env, o, "regValue", make_heads(env, c.value, c.n_heads, c.n_rows));
+        if (c.cb) {
+            napi_set_named_property(env, o, "regCb", make_typed(env, napi_int32_array, c.cb, (size_t)c.n_callbacks * 4, 4));
+            napi_set_named_property(env, o, "regCbValue", make_heads(env, c.cb_value, c.n_heads, c.n_callbacks));
+            napi_set_named_property(env, o, "regCbWeight", make_heads(env, c.cb_weight, c.n_heads, c.n_callbacks));
+            napi_set_named_property(env, o, "regSum", make_heads(env, c.stream_sum, c.n_heads, c.n_streams));
+            napi_set_named_property(env, o, "regWeight", make_heads(env, c.stream_weight, c.n_heads, c.n_streams));
+            napi_set_named_property(env, o, "regRunValue", make_heads(env, c.stream_value, c.n_heads, c.n_streams));
+        }
+        napi_value nh; napi_create_uint32(env, c.n_heads, &nh); napi_set_named_property(env, o, "regNHeads", nh);
+    }
     return o;
 }
 static void stream_drop_ensemble(stream_t *h) {     /* after the stream object stopped using it */
     if (h->ens) wsa_ensemble_destroy(h->ens);
     for (uint32_t d = 0; d < h->n_ens; d++) if (h->ens_models[d]->busy) h->ens_models[d]->busy--;
     h->ens = NULL; h->n_ens = 0;
+}
+static void stream_drop_regress(stream_t *h) {      /* after the stream object stopped using it */
+    if (h->reg) wsa_regress_group_destroy(h->reg);
+    for (uint32_t d = 0; d < h->n_reg; d++) if (h->reg_models[d]->busy) h->reg_models[d]->busy--;
+    h->reg = NULL; h->n_reg = 0;
 }
 static napi_value fn_stream_close(napi_env env, napi_callback_info info) {
     size_t argc = 1; napi_value argv[1];
@@ -885,6 +925,7 @@ static napi_value fn_stream_close(napi_env env, napi_callback_info info) {
         }
         wsa_stream_destroy(h->st); h->st = NULL;
         h->knn = NULL;
+        stream_drop_regress(h);
         if (h->model) { if (h->model->busy) h->model->busy--; h->model = NULL; }
         stream_drop_ensemble(h);
         if (h->box && h->box->children) h->box->children--;
@@ -1039,6 +1080,8 @@ static napi_value fn_model_destroy(napi_env env, napi_callback_info info) {
             box_drop_ensemble(mb->owner); break;
         }
     }
+    if (mb->owner && mb->owner->reg)            /* ... and so may its kept regression group (batchRegressGroup is synchronous: nothing is in flight with it) */
+        for (uint32_t d = 0; d < mb->owner->reg_n; d++) if (mb->owner->reg_models[d] == mb) { box_drop_regress(mb->owner); break; }
     if (mb->m) { wsa_model_destroy(mb->m); mb->m = NULL; }
     model_unlink(mb);
     return NULL;
@@ -1485,6 +1528,114 @@ static napi_value fn_batch_knn_fold(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* ---- regression groups (wsa_regress_group_*, specification RG-1): V, A and D per callback.  [models]: 1 .. 8 handles of modelCreate on the same context, each a
+ * regression model of 53 inputs; outMin / outMax: Float64Array, one range per model.  The library refuses whatever is not one. */
+static int group_args(napi_env env, const char *who, napi_value arr, napi_value lo, napi_value hi, ctx_box *box, model_box **mbs, const wsa_model **ms,
+                      const double **out_min, const double **out_max, uint32_t *n) {
+    char msg[160];
+    bool is_arr = false, ta = false; napi_typedarray_type tt; size_t nl = 0, nh = 0; void *pl = NULL, *ph = NULL;
+    if (napi_is_array(env, arr, &is_arr) != napi_ok || !is_arr || napi_get_array_length(env, arr, n) != napi_ok || *n < 1 || *n > WSA_REGRESS_GROUP_MAX) {
+        snprintf(msg, sizeof msg, "%s: a regression group has 1 .. 8 models", who); napi_throw_error(env, NULL, msg); return 0;
+    }
+    for (uint32_t d = 0; d < *n; d++) {
+        napi_value el; napi_valuetype et = napi_undefined; void *p = NULL;
+        if (napi_get_element(env, arr, d, &el) != napi_ok || napi_typeof(env, el, &et) != napi_ok || et != napi_external || napi_get_value_external(env, el, &p) != napi_ok || !p || !((model_box *)p)->m) {
+            snprintf(msg, sizeof msg, "%s: a model handle was destroyed (or is not a model)", who); napi_throw_error(env, NULL, msg); return 0;
+        }
+        mbs[d] = (model_box *)p; ms[d] = mbs[d]->m;
+        if (mbs[d]->owner != box) { snprintf(msg, sizeof msg, "%s: a model belongs to another context", who); napi_throw_error(env, NULL, msg); return 0; }
+    }
+    if (napi_is_typedarray(env, lo, &ta) != napi_ok || !ta || napi_get_typedarray_info(env, lo, &tt, &nl, &pl, NULL, NULL) != napi_ok || tt != napi_float64_array || nl != *n ||
+        napi_is_typedarray(env, hi, &ta) != napi_ok || !ta || napi_get_typedarray_info(env, hi, &tt, &nh, &ph, NULL, NULL) != napi_ok || tt != napi_float64_array || nh != *n) {
+        snprintf(msg, sizeof msg, "%s: outMin and outMax are Float64Arrays with one entry per model", who); napi_throw_type_error(env, NULL, msg); return 0;
+    }
+    *out_min = (const double *)pl; *out_max = (const double *)ph;
+    return 1;
+}
+/* streamSetRegress(stream, [models] | null, outMin, outMax): the stream object owns the wsa_regress_group it makes of them, until it is replaced, detached or closed */
+static napi_value fn_stream_set_regress(napi_env env, napi_callback_info info) {
+    size_t argc = 4; napi_value argv[4];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    stream_t *h = argc ? get_stream(env, argv[0]) : NULL;
+    if (!h || !h->st || argc < 2) { napi_throw_type_error(env, NULL, "streamSetRegress(stream, [models] | null, outMin, outMax)"); return NULL; }
+    model_box *mbs[WSA_REGRESS_GROUP_MAX] = {0}; const wsa_model *ms[WSA_REGRESS_GROUP_MAX]; const double *lo = NULL, *hi = NULL; uint32_t n = 0;
+    napi_valuetype t;
+    NAPI_OK(env, napi_typeof(env, argv[1], &t));
+    if (t != napi_null && t != napi_undefined) {
+        if (argc < 4) { napi_throw_type_error(env, NULL, "streamSetRegress(stream, [models] | null, outMin, outMax)"); return NULL; }
+        if (!group_args(env, "streamSetRegress", argv[1], argv[2], argv[3], h->box, mbs, ms, &lo, &hi, &n)) return NULL;
+    }
+    wsa_regress_group *g = NULL;
+    if (n && wsa_regress_group_create(h->ctx, ms, lo, hi, n, &g) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(h->ctx)); return NULL; }
+    if (wsa_stream_set_regress(h->st, g) != WSA_OK) { if (g) wsa_regress_group_destroy(g); napi_throw_error(env, NULL, wsa_last_error(h->ctx)); return NULL; }
+    stream_drop_regress(h);
+    if (g) {
+        h->reg = g; h->n_reg = n; memcpy(h->reg_models, mbs, sizeof h->reg_models);
+        for (uint32_t d = 0; d < n; d++) mbs[d]->busy++;            /* modelDestroy() refuses while a stream holds the model */
+    }
+    return NULL;
+}
+/* batchRegressGroup(ctx, [models], outMin, outMax) -> {value: Float64Array [H][rows], cb: Int32Array [n][4], cbValue, cbWeight: Float64Array [H][n], clipSum, clipWeight,
+ * clipValue: Float64Array [H][clips], nHeads}: the grouped launch and the fold RG-1 over the rows of the context's last processBatch (output_level 5: value and nHeads only) */
+static napi_value fn_batch_regress_group(napi_env env, napi_callback_info info) {
+    size_t argc = 4; napi_value argv[4];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ctx_box *box = argc ? get_box(env, argv[0]) : NULL;
+    if (!box || !box->ctx || argc < 4) { napi_throw_type_error(env, NULL, "batchRegressGroup(ctx, [models], outMin, outMax)"); return NULL; }
+    if (!box->plan) { napi_throw_error(env, NULL, "batchRegressGroup: no finished processBatch on this context (or one is in flight)"); return NULL; }
+    model_box *mbs[WSA_REGRESS_GROUP_MAX] = {0}; const wsa_model *ms[WSA_REGRESS_GROUP_MAX]; const double *lo = NULL, *hi = NULL; uint32_t H = 0;
+    if (!group_args(env, "batchRegressGroup", argv[1], argv[2], argv[3], box, mbs, ms, &lo, &hi, &H)) return NULL;
+    bool same = box->reg != NULL && box->reg_n == H;             /* the context's kept group, if it was made of these models and ranges */
+    for (uint32_t d = 0; same && d < H; d++) same = box->reg_models[d] == mbs[d] && box->reg_lo[d] == lo[d] && box->reg_hi[d] == hi[d];
+    if (!same) {
+        wsa_regress_group *g = NULL;
+        if (wsa_regress_group_create(box->ctx, ms, lo, hi, H, &g) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(box->ctx)); return NULL; }
+        box_drop_regress(box);
+        box->reg = g; box->reg_n = H; memcpy(box->reg_models, mbs, sizeof box->reg_models);
+        for (uint32_t d = 0; d < H; d++) { box->reg_lo[d] = lo[d]; box->reg_hi[d] = hi[d]; }
+    }
+    wsa_value_result r;
+    wsa_status st = wsa_batch_regress_group(box->plan, box->reg, box->queue);
+    if (st == WSA_OK) st = wsa_batch_value_result(box->plan, box->queue, &r);
+    if (st != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(box->ctx)); return NULL; }
+    const size_t R = r.n_rows, K = r.n_callbacks, N = r.n_clips;
+    const int fold = r.d_cb != NULL;
+    double *buf = malloc(((size_t)H * (R + 2 * K + 3 * N) + 1) * sizeof(double));
+    int32_t *cb = malloc((4 * K + 1) * sizeof(int32_t));
+    napi_value out = NULL;
+    if (!buf || !cb) napi_throw_error(env, NULL, "out of memory");
+    else {
+        double *value = buf, *cbv = value + (size_t)H * R, *cbw = cbv + (size_t)H * K, *cs = cbw + (size_t)H * K, *cw = cs + (size_t)H * N, *cv = cw + (size_t)H * N;
+        wsa_value_host dst;
+        memset(&dst, 0, sizeof dst);
+        dst.rows_cap = (uint32_t)(R ? R : 1); dst.cb_cap = (uint32_t)(K ? K : 1);
+        for (uint32_t h = 0; h < H; h++) {
+            dst.value[h] = value + (size_t)h * R;
+            if (!fold) continue;
+            dst.cb_value[h] = cbv + (size_t)h * K; dst.cb_weight[h] = cbw + (size_t)h * K;
+            dst.clip_sum[h] = cs + (size_t)h * N; dst.clip_weight[h] = cw + (size_t)h * N; dst.clip_value[h] = cv + (size_t)h * N;
+        }
+        dst.cb = fold ? cb : NULL;
+        if (wsa_batch_copy_value_fold(box->plan, box->queue, &dst) != WSA_OK) napi_throw_error(env, NULL, wsa_last_error(box->ctx));
+        else {
+            napi_value v;
+            napi_create_object(env, &out);
+            napi_set_named_property(env, out, "value", make_typed(env, napi_float64_array, value, (size_t)H * R, 8));
+            if (fold) {
+                napi_set_named_property(env, out, "cb", make_typed(env, napi_int32_array, cb, K * 4, 4));
+                napi_set_named_property(env, out, "cbValue", make_typed(env, napi_float64_array, cbv, (size_t)H * K, 8));
+                napi_set_named_property(env, out, "cbWeight", make_typed(env, napi_float64_array, cbw, (size_t)H * K, 8));
+                napi_set_named_property(env, out, "clipSum", make_typed(env, napi_float64_array, cs, (size_t)H * N, 8));
+                napi_set_named_property(env, out, "clipWeight", make_typed(env, napi_float64_array, cw, (size_t)H * N, 8));
+                napi_set_named_property(env, out, "clipValue", make_typed(env, napi_float64_array, cv, (size_t)H * N, 8));
+            }
+            napi_create_uint32(env, H, &v); napi_set_named_property(env, out, "nHeads", v);
+        }
+    }
+    free(buf); free(cb);
+    return out;
+}
+
 NAPI_MODULE_INIT() {
     /* the structures below follow the header this file was compiled against: refuse a libwsa.so of another ABI version */
     if (wsa_abi_version() != WSA_ABI_VERSION) { napi_throw_error(env, NULL, "libwsa.so ABI version differs from the one wsa_napi.node was built against (include/wsa.h): rebuild"); return NULL; }
@@ -1494,7 +1645,8 @@ NAPI_MODULE_INIT() {
         {"streamOpen", fn_stream_open}, {"streamOpenMixed", fn_stream_open_mixed}, {"streamInfo", fn_stream_info}, {"streamPaced", fn_stream_paced}, {"streamInput", fn_stream_input}, {"streamStep", fn_stream_step}, {"streamClose", fn_stream_close}, {"streamSetModel", fn_stream_set_model}, {"streamSetEnsemble", fn_stream_set_ensemble}, {"streamSetKnn", fn_stream_set_knn},
         {"modelCreate", fn_model_create}, {"modelDestroy", fn_model_destroy}, {"train", fn_train}, {"regressRows", fn_regress_rows},
         {"dbPredict", fn_db_predict}, {"dbTable", fn_db_table},
-        {"knnCreate", fn_knn_create}, {"knnDestroy", fn_knn_destroy}, {"knnAdd", fn_knn_add}, {"knnClassify", fn_knn_classify}, {"batchKnn", fn_batch_knn}, {"batchKnnFold", fn_batch_knn_fold}};
+        {"knnCreate", fn_knn_create}, {"knnDestroy", fn_knn_destroy}, {"knnAdd", fn_knn_add}, {"knnClassify", fn_knn_classify}, {"batchKnn", fn_batch_knn}, {"batchKnnFold", fn_batch_knn_fold},
+        {"streamSetRegress", fn_stream_set_regress}, {"batchRegressGroup", fn_batch_regress_group}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;
