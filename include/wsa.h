@@ -682,6 +682,39 @@ wsa_status wsa_regress_trainer_create(wsa_ctx *ctx, const wsa_model_desc *init, 
                                       double learning_rate, double out_min, double out_max, wsa_trainer **out);
 
 /*
+ * ---- Training groups (additions within version 5: probe for wsa_train_group_create).
+ * At the app's settings (ml5's batch of 32) an epoch of one trainer is bound by its launches, not by arithmetic, and the app needs one
+ * model per DB and head (setPredictionModels / setPredictionValues: available_DBs x {cats_emotion, ords_V, ords_A, ords_D}).  A group
+ * steps up to WSA_TRAIN_GROUP_MAX trainers in lock step: every launch covers the same stage of every member that has that stage in this
+ * step (K7g, csrc/train.hip), so N models train in about the wall time of the longest one.  Specification TG-1 of DESIGN.md: a group
+ * epoch IS wsa_trainer_epoch on every member, in any order, bit for bit (weights, Adam's moments, wsa_train_stats).
+ * The group adopts existing trainers, classification and regression alike, of any stack, width (53 / 264 / 23), row count, batch size,
+ * n_val and learning rate; it owns only a descriptor table.  wsa_trainer_stats / _copy_weights / _model keep working on a member, and
+ * wsa_trainer_epoch on a member between group epochs is legal on the same stream (it is that member's next solo epoch).  Every call on
+ * a group and on its members passes the SAME stream.  Destroy a group BEFORE any of its members; wsa_train_group_destroy releases
+ * the members, which live on as solo trainers and may join another group.  (A member destroyed first empties the group: the other members are
+ * released and wsa_train_group_epoch refuses from then on; the group itself is still to be destroyed.)
+ */
+#define WSA_TRAIN_GROUP_MAX 32
+typedef struct wsa_train_group wsa_train_group;
+/* WSA_ERR_INVALID with a message that names the member index: n of 0 or above WSA_TRAIN_GROUP_MAX, a NULL member, a member of another
+ * context, the same trainer given twice, a trainer already in a living group. */
+wsa_status wsa_train_group_create(wsa_ctx *ctx, wsa_trainer *const *members, uint32_t n, wsa_train_group **out);
+void       wsa_train_group_destroy(wsa_train_group *g);             /* releases the members; they live on as solo trainers */
+/* One epoch of every member: orders[m] as wsa_trainer_epoch's `order` of member m (host [n_train of m], or NULL = 0, 1, 2, ...);
+ * orders itself may be NULL.  Every member's order is checked before anything is enqueued (the message names member and index) and is
+ * staged through that member's own pinned buffers.  A member whose epoch has fewer steps drops out of the later launches; after the
+ * longest member's last step comes one validation pass for the members with n_val > 0, then one finish.  Only enqueues; allocates nothing. */
+wsa_status wsa_train_group_epoch(wsa_train_group *g, const uint32_t *const *orders, void *stream);
+wsa_status wsa_train_group_stats(wsa_train_group *g, void *stream, wsa_train_stats *out /* [n] */);  /* one synchronisation for all members */
+/* host arithmetic only: the kernel launches of one group epoch, TG-1's formula over the members' (nl, n_train, batch, n_val) */
+wsa_status wsa_train_group_launches(const wsa_train_group *g, uint32_t *per_epoch);
+/* pure, needs no device: the same formula over n (1 .. WSA_TRAIN_GROUP_MAX) shapes given as arrays; nl 1 .. 8, n_train and batch >= 1
+ * (a batch above n_train is one step), else WSA_ERR_INVALID */
+wsa_status wsa_train_group_launch_count(const uint32_t *nl, const uint32_t *n_train, const uint32_t *batch, const uint32_t *n_val,
+                                        uint32_t n, uint64_t *per_epoch);
+
+/*
  * ---- Predicting a labelled feature DB and the app's results table (additions within version 5: probe for wsa_dbstats_create).
  * Stands in for the reference APPLICATION's "Predict" button and the panel it fills: src/neuralmodel.js:410-535 (start_nn_prediction ->
  * predict_db_nn -> nn_db_results_handler) runs a model over EVERY stored row of a DB, update_pred_label (src/localstore.js:723-769)

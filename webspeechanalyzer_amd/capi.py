@@ -210,7 +210,11 @@ ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destr
                "wsa_batch_knn_fold", "wsa_batch_knn_fold_result", "wsa_batch_copy_knn_fold", "wsa_stream_set_knn", "wsa_stream_knn_classes",
                # additions within version 5 (probe for wsa_regress_group_create): V, A, D per callback in batches and streams (spec RG-1)
                "wsa_regress_group_create", "wsa_regress_group_destroy", "wsa_regress_group_rows", "wsa_batch_regress_group", "wsa_batch_value_result",
-               "wsa_batch_copy_value_fold", "wsa_stream_set_regress", "wsa_stream_values"]
+               "wsa_batch_copy_value_fold", "wsa_stream_set_regress", "wsa_stream_values",
+               # additions within version 5 (probe for wsa_train_group_create): a group of trainers in one pass of grouped launches (K7g, spec TG-1)
+               "wsa_train_group_create", "wsa_train_group_destroy", "wsa_train_group_epoch", "wsa_train_group_stats", "wsa_train_group_launches",
+               "wsa_train_group_launch_count"]
+TRAIN_GROUP_MAX = 32       # WSA_TRAIN_GROUP_MAX of include/wsa.h
 
 _LIB = None
 _U32_RESULT = ("wsa_stream_input_capacity", "wsa_stream_paced_input", "wsa_stream_input_stride", "wsa_stream_step_frame_capacity", "wsa_stream_frames_bound")
@@ -370,13 +374,19 @@ def lib():
     L.wsa_batch_copy_value_fold.argtypes = [vp, vp, ctypes.POINTER(_ValueHost)]
     L.wsa_stream_set_regress.argtypes = [vp, vp]
     L.wsa_stream_values.argtypes = [vp, ctypes.POINTER(_StreamValueResult)]
+    L.wsa_train_group_create.argtypes = [vp, vp, u32, ctypes.POINTER(vp)]
+    L.wsa_train_group_destroy.argtypes = [vp]
+    L.wsa_train_group_epoch.argtypes = [vp, vp, vp]
+    L.wsa_train_group_stats.argtypes = [vp, vp, vp]
+    L.wsa_train_group_launches.argtypes = [vp, ctypes.POINTER(u32)]
+    L.wsa_train_group_launch_count.argtypes = [vp, vp, vp, vp, u32, ctypes.POINTER(ctypes.c_uint64)]
     for name in ABI_SYMBOLS:
         if name in _U32_RESULT or name in ("wsa_resample_ready", "wsa_level_feature_count"):
             continue
         if name not in ("wsa_abi_version", "wsa_last_error", "wsa_config_default", "wsa_destroy", "wsa_batch_destroy", "wsa_resample_length",
                         "wsa_stream_destroy", "wsa_stream_samples_per_step", "wsa_stream_host_input", "wsa_gather_destroy", "wsa_host_free",
                         "wsa_model_destroy", "wsa_ensemble_destroy", "wsa_trainer_destroy", "wsa_dbstats_destroy", "wsa_knn_destroy",
-                        "wsa_regress_group_destroy"):
+                        "wsa_regress_group_destroy", "wsa_train_group_destroy"):
             getattr(L, name).restype = ctypes.c_int
     _LIB = L
     return L
@@ -465,6 +475,11 @@ class Analyzer:
         and their real-valued targets; the range defaults to spec.out_min / spec.out_max (webspeechanalyzer_amd.train drives it)."""
         return Trainer(self, spec, features, values, n_val, batch_size, learning_rate,
                        regression=(spec.out_min if out_min is None else out_min, spec.out_max if out_max is None else out_max))
+
+    def train_group(self, trainers):
+        """K7g on this context: 1 .. 32 of its Trainers (classifiers and regression models alike) stepped in lock step, one launch per
+        stage for all of them (see TrainGroup; webspeechanalyzer_amd.train.train_many drives it)."""
+        return TrainGroup(self, trainers)
 
     def feature_db(self, features, durations, vocab_sizes=(), n_ord=0):
         """K8 on this context: a labelled feature DB on the device (see FeatureDBStats; webspeechanalyzer_amd.dbstats drives it)."""
@@ -981,6 +996,67 @@ class Trainer:
     def close(self):
         if self.h:
             self.L.wsa_trainer_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def train_group_launch_count(nl, n_train, batch, n_val):
+    """wsa_train_group_launch_count: the kernel launches of one group epoch (spec TG-1) from the members' shapes alone; needs no device."""
+    a = [np.ascontiguousarray(v, np.uint32) for v in (nl, n_train, batch, n_val)]
+    if any(v.ndim != 1 or v.shape != a[0].shape for v in a):
+        raise ValueError("nl, n_train, batch and n_val are sequences of one length")
+    out = ctypes.c_uint64()
+    st = lib().wsa_train_group_launch_count(*[v.ctypes.data for v in a], len(a[0]), ctypes.byref(out))
+    if st != 0:
+        raise WsaError(f"wsa_train_group_launch_count refused the shapes ({st}): 1 .. {TRAIN_GROUP_MAX} members, nl 1 .. 8, n_train and batch at least 1")
+    return int(out.value)
+
+
+class TrainGroup:
+    """wsa_train_group: Trainers of one Analyzer stepped in lock step (K7g, spec TG-1): a group epoch is Trainer.epoch on every member,
+    bit for bit, in about the launches of the longest one.  The members stay usable (stats, weights, model, a solo epoch between group
+    epochs, all on the same stream); close the group before its members."""
+
+    def __init__(self, an, trainers):
+        self.an, self.L, self.trainers = an, an.L, list(trainers)
+        hs = (ctypes.c_void_p * max(len(self.trainers), 1))(*[t.h for t in self.trainers])
+        self.h = ctypes.c_void_p()
+        an._check(self.L.wsa_train_group_create(an.h, ctypes.cast(hs, ctypes.c_void_p), len(self.trainers), ctypes.byref(self.h)))
+
+    def epoch(self, orders=None, stream=0):
+        """Enqueues one epoch of every member; orders: None, or one entry per member, each None or that member's order (see Trainer.epoch)."""
+        ptr = None
+        if orders is not None:
+            if len(orders) != len(self.trainers):
+                raise ValueError(f"{len(orders)} orders for {len(self.trainers)} members")
+            keep = [None if o is None else np.ascontiguousarray(o, np.uint32) for o in orders]
+            for i, (o, t) in enumerate(zip(keep, self.trainers)):
+                if o is not None and o.shape != (t.n_train,):
+                    raise ValueError(f"member {i}: order has shape {o.shape}, the trainer has {t.n_train} training rows")
+            arr = (ctypes.c_void_p * len(keep))(*[None if o is None else o.ctypes.data for o in keep])
+            ptr = ctypes.cast(arr, ctypes.c_void_p)
+        self.an._check(self.L.wsa_train_group_epoch(self.h, ptr, stream))
+
+    def stats(self, stream=0):
+        """Synchronises once; one Trainer.stats dict per member, in member order."""
+        st = (_TrainStats * len(self.trainers))()
+        self.an._check(self.L.wsa_train_group_stats(self.h, stream, ctypes.cast(st, ctypes.c_void_p)))
+        return [{k: getattr(x, k) for k, _ in _TrainStats._fields_} for x in st]
+
+    def launches(self):
+        """The kernel launches of one epoch of this group (spec TG-1's formula; host arithmetic)."""
+        n = ctypes.c_uint32()
+        self.an._check(self.L.wsa_train_group_launches(self.h, ctypes.byref(n)))
+        return int(n.value)
+
+    def close(self):
+        if self.h:
+            self.L.wsa_train_group_destroy(self.h)
             self.h = ctypes.c_void_p()
 
     def __del__(self):

@@ -65,9 +65,11 @@ __device__ __forceinline__ float tr_derivative(float a, int act) {          // t
 // ---- forward: out [mp][np] = act(in [m][kp] . w [kp][np] + b), rows m .. mp-1 and columns n .. np-1 written as zero
 struct TrFwd { TrRows in; const float* w; const float* b; float* out; int kp, np, n, act; uint32_t mp; };
 
-__global__ void __launch_bounds__(TR_THREADS) train_forward_kernel(TrFwd p) {
+// (the stage bodies take the workgroup's index within their launch's part for ONE trainer: blockIdx.x in the solo kernels, the index
+// past the member's prefix in the grouped ones, K7g below; the arithmetic and its order are the same in both)
+__device__ __forceinline__ void tr_forward_body(const TrFwd& p, uint32_t block) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t cbs = p.np / 16, tile = blockIdx.x * TR_WAVES + wave;
+    const uint32_t cbs = p.np / 16, tile = block * TR_WAVES + wave;
     if (tile >= (p.mp / 16) * cbs) return;
     const uint32_t r0 = (tile / cbs) * 16; const int n0 = (tile % cbs) * 16;
     const float* ap = tr_row(p.in, r0 + (lane & 15));
@@ -99,6 +101,8 @@ __global__ void __launch_bounds__(TR_THREADS) train_forward_kernel(TrFwd p) {
     }
 }
 
+__global__ void __launch_bounds__(TR_THREADS) train_forward_kernel(TrFwd p) { tr_forward_body(p, blockIdx.x); }
+
 // ---- loss: softmax (K6's formula), tfjs categoricalCrossentropy and categoricalAccuracy per row, dZ of the last layer; one workgroup:
 // thread t sums rows t, t + 1024, ... in that order, then a fixed tree over the threads -> part_loss / part_hit [slot]
 struct TrLoss {
@@ -108,9 +112,7 @@ struct TrLoss {
     double* part_loss; uint32_t* part_hit; uint32_t slot;
 };
 
-__global__ void __launch_bounds__(TR_LOSS_THREADS) train_loss_kernel(TrLoss p) {
-    __shared__ double s_loss[TR_LOSS_THREADS];
-    __shared__ uint32_t s_hit[TR_LOSS_THREADS];
+__device__ __forceinline__ void tr_loss_body(const TrLoss& p, double* s_loss, uint32_t* s_hit) {   // s_loss, s_hit: LDS [TR_LOSS_THREADS]
     const int tid = threadIdx.x;
     double loss = 0.0; uint32_t hit = 0;
     for (uint32_t r = tid; r < p.mp; r += TR_LOSS_THREADS) {
@@ -156,12 +158,18 @@ __global__ void __launch_bounds__(TR_LOSS_THREADS) train_loss_kernel(TrLoss p) {
     if (tid == 0) { p.part_loss[p.slot] = s_loss[0]; p.part_hit[p.slot] = s_hit[0]; }
 }
 
+__global__ void __launch_bounds__(TR_LOSS_THREADS) train_loss_kernel(TrLoss p) {
+    __shared__ double s_loss[TR_LOSS_THREADS];
+    __shared__ uint32_t s_hit[TR_LOSS_THREADS];
+    tr_loss_body(p, s_loss, s_hit);
+}
+
 // ---- backward through one layer's kernel: dzp [mp][kp] = (dz [mp][np] . w^T) . act'(a [mp][kp]); columns k .. kp-1, rows m .. zero
 struct TrBack { const float* dz; const float* w; const float* a; float* dzp; int kp, np, k, act; uint32_t m, mp; };
 
-__global__ void __launch_bounds__(TR_THREADS) train_backward_kernel(TrBack p) {
+__device__ __forceinline__ void tr_backward_body(const TrBack& p, uint32_t block) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t kbs = p.kp / 16, tile = blockIdx.x * TR_WAVES + wave;
+    const uint32_t kbs = p.kp / 16, tile = block * TR_WAVES + wave;
     if (tile >= (p.mp / 16) * kbs) return;
     const uint32_t r0 = (tile / kbs) * 16; const int k0 = (tile % kbs) * 16;
     const float* ap = p.dz + (size_t)(r0 + (lane & 15)) * p.np + (lane >> 4);
@@ -184,6 +192,8 @@ __global__ void __launch_bounds__(TR_THREADS) train_backward_kernel(TrBack p) {
         p.dzp[at] = v;
     }
 }
+
+__global__ void __launch_bounds__(TR_THREADS) train_backward_kernel(TrBack p) { tr_backward_body(p, blockIdx.x); }
 
 // ---- update: w [kp][np] -= lr a^T dz, b -= lr 1^T dz.  Tiles (kb, cb), kb = kp / 16 is the bias's tile (A = ones).  The wave that
 // owns a tile sums over all batch rows in ascending order and writes the new weights; padded rows / columns stay zero.
@@ -208,9 +218,9 @@ __device__ __forceinline__ f32x4 tr_gradient_tile(const TrUpd& p, int lane, int 
     return acc;
 }
 
-__global__ void __launch_bounds__(TR_THREADS) train_update_kernel(TrUpd p) {
+__device__ __forceinline__ void tr_update_body(const TrUpd& p, uint32_t block) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t cbs = p.np / 16, kbs = p.kp / 16, tile = blockIdx.x * TR_WAVES + wave;
+    const uint32_t cbs = p.np / 16, kbs = p.kp / 16, tile = block * TR_WAVES + wave;
     if (tile >= (kbs + 1) * cbs) return;
     const uint32_t kb = tile / cbs; const int n0 = (tile % cbs) * 16, k0 = kb * 16;
     const bool bias = kb == kbs;
@@ -229,6 +239,8 @@ __global__ void __launch_bounds__(TR_THREADS) train_update_kernel(TrUpd p) {
         p.w[at] = p.w[at] - p.lr * acc[i];                                  // tf.train.sgd: value + (-lr) gradient, in f32
     }
 }
+
+__global__ void __launch_bounds__(TR_THREADS) train_update_kernel(TrUpd p) { tr_update_body(p, blockIdx.x); }
 
 // ---- loss of a regression model (TR-2): tfjs meanSquaredError over the one output unit, binaryAccuracy (what "accuracy" resolves to for
 // a one-unit output: the target equals 1 if p > 0.5 else 0), dZ of the last layer THROUGH its activation (the forward pass has applied
@@ -256,9 +268,7 @@ __device__ __forceinline__ double tr_derivative_f64(double a, int act) {    // t
     }
 }
 
-__global__ void __launch_bounds__(TR_LOSS_THREADS) train_loss_mse_kernel(TrLossMse p) {
-    __shared__ double s_loss[TR_LOSS_THREADS];
-    __shared__ uint32_t s_hit[TR_LOSS_THREADS];
+__device__ __forceinline__ void tr_loss_mse_body(const TrLossMse& p, double* s_loss, uint32_t* s_hit) {   // s_loss, s_hit: LDS [TR_LOSS_THREADS]
     const int tid = threadIdx.x;
     double loss = 0.0; uint32_t hit = 0;
     for (uint32_t r = tid; r < p.mp; r += TR_LOSS_THREADS) {
@@ -293,6 +303,12 @@ __global__ void __launch_bounds__(TR_LOSS_THREADS) train_loss_mse_kernel(TrLossM
     }
 }
 
+__global__ void __launch_bounds__(TR_LOSS_THREADS) train_loss_mse_kernel(TrLossMse p) {
+    __shared__ double s_loss[TR_LOSS_THREADS];
+    __shared__ uint32_t s_hit[TR_LOSS_THREADS];
+    tr_loss_mse_body(p, s_loss, s_hit);
+}
+
 // ---- tfjs 1.7.2 AdamOptimizer.applyGradients on one element, operation for operation; every intermediate is rounded to f32 once, as
 // the CPU backend's Float32Array stores round it.  Its divisions and its square root are JavaScript doubles stored to f32: written
 // that way here, so their rounding does not hang on how the compiler expands an f32 division or square root.  No contraction: JavaScript
@@ -315,10 +331,10 @@ __device__ __forceinline__ float adam_step(float w, float g, float* m, float* v,
 // elements of w / m / v (mw, vw [kp][np] and mb, vb [np]: padded exactly as the weights are; padded elements are never touched and stay 0)
 struct TrUpdAdam { TrUpd u; float* mw; float* vw; float* mb; float* vb; const float* adam; };
 
-__global__ void __launch_bounds__(TR_THREADS) train_update_adam_kernel(TrUpdAdam q) {
+__device__ __forceinline__ void tr_update_adam_body(const TrUpdAdam& q, uint32_t block) {
     const TrUpd& p = q.u;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t cbs = p.np / 16, kbs = p.kp / 16, tile = blockIdx.x * TR_WAVES + wave;
+    const uint32_t cbs = p.np / 16, kbs = p.kp / 16, tile = block * TR_WAVES + wave;
     if (tile >= (kbs + 1) * cbs) return;
     const uint32_t kb = tile / cbs; const int n0 = (tile % cbs) * 16, k0 = kb * 16;
     const bool bias = kb == kbs;
@@ -339,6 +355,8 @@ __global__ void __launch_bounds__(TR_THREADS) train_update_adam_kernel(TrUpdAdam
     }
 }
 
+__global__ void __launch_bounds__(TR_THREADS) train_update_adam_kernel(TrUpdAdam q) { tr_update_adam_body(q, blockIdx.x); }
+
 __global__ void train_adam_reset_kernel(float* adam) {                      // accBeta = beta: no step taken yet
     if (threadIdx.x == 0 && blockIdx.x == 0) { adam[0] = ADAM_BETA1; adam[1] = ADAM_BETA2; adam[2] = 1.f - ADAM_BETA1; adam[3] = 1.f - ADAM_BETA2; }
 }
@@ -352,9 +370,7 @@ __global__ void __launch_bounds__(256) train_normalise_target_kernel(const doubl
 // ---- epoch end: the steps' partials in a fixed order -> the epoch's statistics (history of tfjs's BaseLogger / testLoop)
 struct TrFin { const double* part_loss; const uint32_t* part_hit; uint32_t n_steps, n_train, n_val, epoch; wsa_train_stats* out; };
 
-__global__ void __launch_bounds__(256) train_finish_kernel(TrFin p) {
-    __shared__ double s_loss[256];
-    __shared__ uint32_t s_hit[256];
+__device__ __forceinline__ void tr_finish_body(const TrFin& p, double* s_loss, uint32_t* s_hit) {   // s_loss, s_hit: LDS [256]
     const int tid = threadIdx.x;
     double loss = 0.0; uint32_t hit = 0;
     for (uint32_t i = tid; i < p.n_steps; i += 256) { loss += p.part_loss[i]; hit += p.part_hit[i]; }
@@ -374,6 +390,12 @@ __global__ void __launch_bounds__(256) train_finish_kernel(TrFin p) {
     }
 }
 
+__global__ void __launch_bounds__(256) train_finish_kernel(TrFin p) {
+    __shared__ double s_loss[256];
+    __shared__ uint32_t s_hit[256];
+    tr_finish_body(p, s_loss, s_hit);
+}
+
 // ---- create: (x - min) / (max - min) in double, rounded to f32 (ml5 normalizeValue, as K6); feat [n_rows][nin] dense, x [n_rows][xs],
 // xs = nin padded to 16-column blocks, the padding written as zero
 __global__ void __launch_bounds__(256) train_normalise_kernel(const double* feat, const double* mn, const double* mx, uint64_t n_rows, int nin, int xs, float* x) {
@@ -383,10 +405,135 @@ __global__ void __launch_bounds__(256) train_normalise_kernel(const double* feat
     x[i] = k < nin ? (float)((feat[r * (uint64_t)nin + k] - mn[k]) / (mx[k] - mn[k])) : 0.f;
 }
 
+// ---- K7g: the same stages for a GROUP of trainers stepped in lock step (specification TG-1; wsa_train_group_* below).  One
+// launch covers one stage of every member that has that stage in this step.  Whole workgroups belong to one member: member i owns
+// workgroups prefix[i] .. prefix[i + 1] - 1 (none when it has dropped out of the epoch or has no layer at this position), its
+// workgroup's index within its part is blockIdx.x - prefix[i], and from there on the solo kernel's body runs on parameters built from
+// the member's row of the descriptor table (device memory, written once at wsa_train_group_create) and the step's offset and size,
+// computed here from (step, n_train, batch).  Members share no buffer, no sum crosses a workgroup: a member's bits are its solo run's.
+// The loss and the update each have ONE grouped kernel that takes the member's kind (softmax + SGD, or mean squared error + Adam)
+// from its descriptor, so a step of a mixed group still costs 3 . max nl launches.
+constexpr int TG_MAX = WSA_TRAIN_GROUP_MAX;
+constexpr uint32_t TG_VALIDATION = 0xFFFFFFFFu;                             // TgLaunch::step of the pass over the validation rows
+
+struct TgMember {                                                           // what enqueue_step reads of a wsa_trainer
+    const float* x; const uint32_t* order; const uint32_t* identity;
+    const int32_t* label; const float* target; float* adam;
+    float *w[WSA_MODEL_MAX_LAYERS], *b[WSA_MODEL_MAX_LAYERS];
+    float *mw[WSA_MODEL_MAX_LAYERS], *vw[WSA_MODEL_MAX_LAYERS], *mb[WSA_MODEL_MAX_LAYERS], *vb[WSA_MODEL_MAX_LAYERS];
+    float* a[WSA_MODEL_MAX_LAYERS + 1]; float* dz[2];
+    double* part_loss; uint32_t* part_hit; wsa_train_stats* stats;
+    int units[WSA_MODEL_MAX_LAYERS + 1], pad[WSA_MODEL_MAX_LAYERS + 1], act[WSA_MODEL_MAX_LAYERS];
+    int nl, regress; uint32_t n_train, n_val, batch, n_steps; float lr;
+};
+
+// by value, 37 words: the workgroup-count prefix over the members, the step (or TG_VALIDATION), bit i of order_mask set when member i
+// reads its rows through its order buffer in this epoch (clear: the identity), and the layer position of the launch
+struct TgLaunch { uint32_t prefix[TG_MAX + 1]; uint32_t n, step, order_mask; int pos; };
+
+__device__ __forceinline__ uint32_t tg_member_of(const TgLaunch& g, uint32_t block) {    // uniform over the workgroup
+    uint32_t i = 0;
+    while (i + 1 < g.n && block >= g.prefix[i + 1]) i++;
+    return i;
+}
+
+struct TgStep { const uint32_t* idx; uint32_t off, m, mp; bool training; };
+
+__device__ __forceinline__ TgStep tg_step(const TgMember& t, const TgLaunch& g, uint32_t i) {
+    TgStep s;
+    s.training = g.step != TG_VALIDATION;
+    if (s.training) {
+        s.idx = (g.order_mask >> i) & 1u ? t.order : t.identity;
+        s.off = g.step * t.batch; s.m = t.n_train - s.off < t.batch ? t.n_train - s.off : t.batch;
+    } else { s.idx = nullptr; s.off = t.n_train; s.m = t.n_val; }
+    s.mp = (s.m + 15u) & ~15u;
+    return s;
+}
+
+__device__ __forceinline__ TrRows tg_layer_input(const TgMember& t, const TgStep& s, int l) {
+    return l == 0 ? TrRows{t.x, t.pad[0], s.idx, s.off, s.m} : TrRows{t.a[l], t.pad[l], nullptr, 0, s.m};
+}
+
+__global__ void __launch_bounds__(TR_THREADS) train_group_forward_kernel(const TgMember* tab, TgLaunch g) {   // g.pos: the layer
+    const uint32_t i = tg_member_of(g, blockIdx.x);
+    const TgMember& t = tab[i];
+    const TgStep s = tg_step(t, g, i);
+    const int l = g.pos;
+    TrFwd f;
+    f.in = tg_layer_input(t, s, l);
+    f.w = t.w[l]; f.b = t.b[l]; f.out = t.a[l + 1];
+    f.kp = t.pad[l]; f.np = t.pad[l + 1]; f.n = t.units[l + 1]; f.act = t.act[l]; f.mp = s.mp;
+    tr_forward_body(f, blockIdx.x - g.prefix[i]);
+}
+
+__global__ void __launch_bounds__(TR_LOSS_THREADS) train_group_loss_kernel(const TgMember* tab, TgLaunch g) {   // one workgroup per member
+    __shared__ double s_loss[TR_LOSS_THREADS];
+    __shared__ uint32_t s_hit[TR_LOSS_THREADS];
+    const uint32_t i = tg_member_of(g, blockIdx.x);
+    const TgMember& t = tab[i];
+    const TgStep s = tg_step(t, g, i);
+    float* dz = s.training ? t.dz[0] : nullptr;
+    const uint32_t slot = s.training ? g.step : t.n_steps;
+    if (t.regress) {
+        TrLossMse p;
+        p.z = t.a[t.nl]; p.np = t.pad[t.nl]; p.act = t.act[t.nl - 1]; p.m = s.m; p.mp = s.mp;
+        p.target = t.target; p.idx = s.idx; p.off = s.off; p.dz = dz; p.adam = s.training ? t.adam : nullptr;
+        p.part_loss = t.part_loss; p.part_hit = t.part_hit; p.slot = slot;
+        tr_loss_mse_body(p, s_loss, s_hit);
+    } else {
+        TrLoss p;
+        p.z = t.a[t.nl]; p.np = t.pad[t.nl]; p.C = t.units[t.nl]; p.m = s.m; p.mp = s.mp;
+        p.label = t.label; p.idx = s.idx; p.off = s.off; p.dz = dz;
+        p.part_loss = t.part_loss; p.part_hit = t.part_hit; p.slot = slot;
+        tr_loss_body(p, s_loss, s_hit);
+    }
+}
+
+// pos j of the backward / update launches is layer nl - 1 - j of a member; dZ of that layer is in dz[j & 1], as enqueue_step's `cur`
+__global__ void __launch_bounds__(TR_THREADS) train_group_backward_kernel(const TgMember* tab, TgLaunch g) {
+    const uint32_t i = tg_member_of(g, blockIdx.x);
+    const TgMember& t = tab[i];
+    const TgStep s = tg_step(t, g, i);
+    const int l = t.nl - 1 - g.pos, cur = g.pos & 1;                        // l > 0: the host gives a member with l <= 0 no workgroup
+    TrBack b;
+    b.dz = t.dz[cur]; b.w = t.w[l]; b.a = t.a[l]; b.dzp = t.dz[cur ^ 1];
+    b.kp = t.pad[l]; b.np = t.pad[l + 1]; b.k = t.units[l]; b.act = t.act[l - 1]; b.m = s.m; b.mp = s.mp;
+    tr_backward_body(b, blockIdx.x - g.prefix[i]);
+}
+
+__global__ void __launch_bounds__(TR_THREADS) train_group_update_kernel(const TgMember* tab, TgLaunch g) {
+    const uint32_t i = tg_member_of(g, blockIdx.x);
+    const TgMember& t = tab[i];
+    const TgStep s = tg_step(t, g, i);
+    const int l = t.nl - 1 - g.pos, cur = g.pos & 1;
+    TrUpdAdam q;
+    TrUpd& u = q.u;
+    u.a = tg_layer_input(t, s, l);
+    u.dz = t.dz[cur]; u.w = t.w[l]; u.b = t.b[l];
+    u.kp = t.pad[l]; u.np = t.pad[l + 1]; u.k = t.units[l]; u.n = t.units[l + 1]; u.mp = s.mp; u.lr = t.lr;
+    if (t.regress) {
+        q.mw = t.mw[l]; q.vw = t.vw[l]; q.mb = t.mb[l]; q.vb = t.vb[l]; q.adam = t.adam;
+        tr_update_adam_body(q, blockIdx.x - g.prefix[i]);
+    } else {
+        tr_update_body(u, blockIdx.x - g.prefix[i]);
+    }
+}
+
+struct TgFinish { uint32_t epoch[TG_MAX]; };                                // by value: the epoch each member has just finished
+
+__global__ void __launch_bounds__(256) train_group_finish_kernel(const TgMember* tab, TgFinish g) {   // workgroup i: member i
+    __shared__ double s_loss[256];
+    __shared__ uint32_t s_hit[256];
+    const TgMember& t = tab[blockIdx.x];
+    const TrFin f{t.part_loss, t.part_hit, t.n_steps, t.n_train, t.n_val, g.epoch[blockIdx.x], t.stats};
+    tr_finish_body(f, s_loss, s_hit);
+}
+
 }  // namespace
 
 struct wsa_trainer {
     wsa_ctx* ctx = nullptr;
+    wsa_train_group* group = nullptr;                          // the living group that has adopted this trainer, if any
     int nl = 0;
     int units[WSA_MODEL_MAX_LAYERS + 1] = {}, pad[WSA_MODEL_MAX_LAYERS + 1] = {}, act[WSA_MODEL_MAX_LAYERS] = {};
     uint32_t n_rows = 0, n_train = 0, n_val = 0, batch = 0, n_steps = 0, mcap = 0, epoch = 0;
@@ -465,6 +612,26 @@ void enqueue_step(wsa_trainer* t, const uint32_t* idx, uint32_t step, hipStream_
         }
         cur ^= 1;
     }
+}
+
+void tg_orphan(wsa_train_group* g);                                          // with wsa_train_group, below
+
+// "" or why `order` (not NULL) is refused: an entry outside the training rows
+std::string order_refusal(const wsa_trainer* t, const uint32_t* order) {
+    for (uint32_t i = 0; i < t->n_train; i++)
+        if (order[i] >= t->n_train) return "order[" + std::to_string(i) + "] = " + std::to_string(order[i]) + " is outside 0 .. " + std::to_string(t->n_train - 1);
+    return "";
+}
+
+// the epoch's order through the trainer's pinned staging (two epochs deep) into d_order, on s
+wsa_status stage_order(wsa_trainer* t, const uint32_t* order, hipStream_t s) {
+    wsa_ctx* ctx = t->ctx;
+    const int slot = t->epoch & 1;                                           // the copy that last read this staging buffer is two epochs back
+    HIP_TRY(ctx, hipEventSynchronize(t->ev[slot]));
+    std::memcpy(t->h_order[slot], order, (size_t)t->n_train * sizeof(uint32_t));
+    HIP_TRY(ctx, hipMemcpyAsync(t->d_order, t->h_order[slot], (size_t)t->n_train * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipEventRecord(t->ev[slot], s));
+    return WSA_OK;
 }
 
 }  // namespace
@@ -591,6 +758,7 @@ wsa_status wsa_regress_trainer_create(wsa_ctx* ctx, const wsa_model_desc* d, con
 void wsa_trainer_destroy(wsa_trainer* t) {
     if (!t) return;
     (void)hipSetDevice(t->ctx->device);
+    if (t->group) tg_orphan(t->group);                                       // against the documented order: the group refuses from here on
     for (int i = 0; i < 2; i++) {
         if (t->ev[i]) { (void)hipEventSynchronize(t->ev[i]); (void)hipEventDestroy(t->ev[i]); }
         if (t->h_order[i]) (void)hipHostFree(t->h_order[i]);
@@ -602,17 +770,15 @@ wsa_status wsa_trainer_epoch(wsa_trainer* t, const uint32_t* order, void* stream
     if (!t) return WSA_ERR_INVALID;
     wsa_ctx* ctx = t->ctx;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (order)
-        for (uint32_t i = 0; i < t->n_train; i++)
-            if (order[i] >= t->n_train) return fail(ctx, WSA_ERR_INVALID, "order[" + std::to_string(i) + "] = " + std::to_string(order[i]) + " is outside 0 .. " + std::to_string(t->n_train - 1));
+    if (order) {
+        const std::string why = order_refusal(t, order);
+        if (!why.empty()) return fail(ctx, WSA_ERR_INVALID, why);
+    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint32_t* idx = t->d_identity;
     if (order) {
-        const int slot = t->epoch & 1;                                       // the copy that last read this staging buffer is two epochs back
-        HIP_TRY(ctx, hipEventSynchronize(t->ev[slot]));
-        std::memcpy(t->h_order[slot], order, (size_t)t->n_train * sizeof(uint32_t));
-        HIP_TRY(ctx, hipMemcpyAsync(t->d_order, t->h_order[slot], (size_t)t->n_train * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipEventRecord(t->ev[slot], s));
+        const wsa_status st = stage_order(t, order, s);
+        if (st != WSA_OK) return st;
         idx = t->d_order;
     }
     for (uint32_t step = 0; step < t->n_steps; step++) enqueue_step(t, idx, step, s);
@@ -674,6 +840,206 @@ wsa_status wsa_trainer_model(wsa_trainer* t, void* stream, wsa_model** out) {
     d.kernel = kp.data(); d.bias = bp.data(); d.in_min = t->in_min.data(); d.in_max = t->in_max.data();
     d.labels = t->has_labels ? lab.data() : nullptr;
     return wsa_model_create(ctx, &d, out);
+}
+
+}  // extern "C"
+
+// ---- training groups (K7g, specification TG-1)
+struct wsa_train_group {
+    wsa_ctx* ctx = nullptr;
+    uint32_t n = 0;
+    wsa_trainer* member[WSA_TRAIN_GROUP_MAX] = {};
+    TgMember* d_tab = nullptr;                                 // all the group owns
+    wsa::DevArena mem;
+};
+
+namespace {
+
+// TG-1's launch count from the members' shapes alone; walk(step or TG_VALIDATION, Lmax) is called once per step that has a member,
+// in the order the launches go out, so wsa_train_group_epoch and the formula cannot drift apart
+template <typename Walk>
+uint64_t group_plan(const uint32_t* nl, const uint32_t* n_steps, const uint32_t* n_val, uint32_t n, Walk walk) {
+    uint32_t longest = 0, lval = 0;
+    for (uint32_t i = 0; i < n; i++) { if (n_steps[i] > longest) longest = n_steps[i]; if (n_val[i] && nl[i] > lval) lval = nl[i]; }
+    uint64_t launches = 0;
+    for (uint32_t step = 0; step < longest; step++) {
+        uint32_t lmax = 0;
+        for (uint32_t i = 0; i < n; i++) if (n_steps[i] > step && nl[i] > lmax) lmax = nl[i];
+        launches += 3ull * lmax;                                             // lmax forward, the loss, lmax - 1 backward, lmax update
+        walk(step, lmax);
+    }
+    if (lval) { launches += lval + 1; walk(TG_VALIDATION, lval); }           // forward + loss over the validation rows
+    return launches + 1;                                                     // the finish
+}
+
+// does member t take part in the launches of `step` (or of the validation pass)?
+inline bool tg_active(const wsa_trainer* t, uint32_t step) { return step == TG_VALIDATION ? t->n_val > 0 : t->n_steps > step; }
+inline uint32_t tg_rows(const wsa_trainer* t, uint32_t step) {               // up16(m) of the step
+    if (step == TG_VALIDATION) return up16(t->n_val);
+    const uint32_t off = step * t->batch;
+    return up16(t->n_train - off < t->batch ? t->n_train - off : t->batch);
+}
+
+// a member is being destroyed before its group: the table points at its buffers, so the group lets go of every member and is empty
+void tg_orphan(wsa_train_group* g) {
+    for (uint32_t i = 0; i < g->n; i++) g->member[i]->group = nullptr;
+    g->n = 0;
+}
+
+enum TgStage { TG_FORWARD, TG_LOSS, TG_BACKWARD, TG_UPDATE };
+
+// one grouped launch: the prefix of workgroup counts over the members that have `stage` at `pos` in `step`, then the kernel
+void tg_launch(wsa_train_group* g, TgStage stage, uint32_t step, int pos, uint32_t order_mask, hipStream_t s) {
+    TgLaunch a{};
+    a.n = g->n; a.step = step; a.order_mask = order_mask; a.pos = pos;
+    for (uint32_t i = 0; i < g->n; i++) {
+        const wsa_trainer* t = g->member[i];
+        uint32_t blocks = 0;
+        if (tg_active(t, step)) {
+            const uint64_t rb = tg_rows(t, step) / 16;
+            const int l = stage == TG_FORWARD ? pos : t->nl - 1 - pos;       // the member's layer at this position
+            switch (stage) {
+                case TG_FORWARD: if (l < t->nl) blocks = blocks_for(rb * (t->pad[l + 1] / 16)); break;
+                case TG_LOSS: blocks = 1; break;
+                case TG_BACKWARD: if (l > 0) blocks = blocks_for(rb * (t->pad[l] / 16)); break;
+                case TG_UPDATE: if (l >= 0) blocks = blocks_for((uint64_t)(t->pad[l] / 16 + 1) * (t->pad[l + 1] / 16)); break;
+            }
+        }
+        a.prefix[i + 1] = a.prefix[i] + blocks;
+    }
+    for (uint32_t i = g->n; i < WSA_TRAIN_GROUP_MAX; i++) a.prefix[i + 1] = a.prefix[i];
+    const dim3 grid(a.prefix[g->n]);
+    if (grid.x == 0) return;
+    switch (stage) {
+        case TG_FORWARD: hipLaunchKernelGGL(train_group_forward_kernel, grid, dim3(TR_THREADS), 0, s, g->d_tab, a); break;
+        case TG_LOSS: hipLaunchKernelGGL(train_group_loss_kernel, grid, dim3(TR_LOSS_THREADS), 0, s, g->d_tab, a); break;
+        case TG_BACKWARD: hipLaunchKernelGGL(train_group_backward_kernel, grid, dim3(TR_THREADS), 0, s, g->d_tab, a); break;
+        case TG_UPDATE: hipLaunchKernelGGL(train_group_update_kernel, grid, dim3(TR_THREADS), 0, s, g->d_tab, a); break;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+wsa_status wsa_train_group_launch_count(const uint32_t* nl, const uint32_t* n_train, const uint32_t* batch, const uint32_t* n_val,
+                                        uint32_t n, uint64_t* per_epoch) {
+    if (!nl || !n_train || !batch || !n_val || !per_epoch || n == 0 || n > WSA_TRAIN_GROUP_MAX) return WSA_ERR_INVALID;
+    uint32_t steps[WSA_TRAIN_GROUP_MAX];
+    for (uint32_t i = 0; i < n; i++) {
+        if (nl[i] < 1 || nl[i] > WSA_MODEL_MAX_LAYERS || n_train[i] == 0 || batch[i] == 0) return WSA_ERR_INVALID;
+        const uint32_t b = batch[i] < n_train[i] ? batch[i] : n_train[i];
+        steps[i] = (n_train[i] + b - 1) / b;
+    }
+    *per_epoch = group_plan(nl, steps, n_val, n, [](uint32_t, uint32_t) {});
+    return WSA_OK;
+}
+
+wsa_status wsa_train_group_create(wsa_ctx* ctx, wsa_trainer* const* members, uint32_t n, wsa_train_group** out) {
+    if (!ctx || !members || !out) return fail(ctx, WSA_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (n == 0 || n > WSA_TRAIN_GROUP_MAX) return fail(ctx, WSA_ERR_INVALID, "a training group has 1 .. " + std::to_string(WSA_TRAIN_GROUP_MAX) + " members, got " + std::to_string(n));
+    for (uint32_t i = 0; i < n; i++) {
+        const std::string who = "member " + std::to_string(i);
+        if (!members[i]) return fail(ctx, WSA_ERR_INVALID, who + " is NULL");
+        if (members[i]->ctx != ctx) return fail(ctx, WSA_ERR_INVALID, who + " belongs to another context");
+        for (uint32_t j = 0; j < i; j++)
+            if (members[j] == members[i]) return fail(ctx, WSA_ERR_INVALID, who + " is the same trainer as member " + std::to_string(j));
+        if (members[i]->group) return fail(ctx, WSA_ERR_INVALID, who + " is already in a living group");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<TgMember> tab(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const wsa_trainer* t = members[i];
+        TgMember& m = tab[i];
+        std::memset(&m, 0, sizeof m);
+        m.x = t->d_x; m.order = t->d_order; m.identity = t->d_identity; m.label = t->d_label; m.target = t->d_target; m.adam = t->d_adam;
+        for (int l = 0; l < t->nl; l++) {
+            m.w[l] = t->d_w[l]; m.b[l] = t->d_b[l]; m.mw[l] = t->d_mw[l]; m.vw[l] = t->d_vw[l]; m.mb[l] = t->d_mb[l]; m.vb[l] = t->d_vb[l];
+            m.act[l] = t->act[l];
+        }
+        for (int l = 0; l <= t->nl; l++) { m.a[l] = t->d_a[l]; m.units[l] = t->units[l]; m.pad[l] = t->pad[l]; }
+        m.dz[0] = t->d_dz[0]; m.dz[1] = t->d_dz[1];
+        m.part_loss = t->d_part_loss; m.part_hit = t->d_part_hit; m.stats = t->d_stats;
+        m.nl = t->nl; m.regress = t->regress ? 1 : 0;
+        m.n_train = t->n_train; m.n_val = t->n_val; m.batch = t->batch; m.n_steps = t->n_steps; m.lr = t->lr;
+    }
+    wsa_train_group* g = new wsa_train_group();
+    g->ctx = ctx; g->n = n;
+    if (!g->mem.upload(&g->d_tab, tab)) {
+        const std::string msg = std::string("device allocation / copy failed: ") + hipGetErrorString(hipGetLastError());
+        delete g;
+        return fail(ctx, WSA_ERR_HIP, msg);
+    }
+    for (uint32_t i = 0; i < n; i++) { g->member[i] = members[i]; members[i]->group = g; }
+    *out = g;
+    return WSA_OK;
+}
+
+void wsa_train_group_destroy(wsa_train_group* g) {
+    if (!g) return;
+    (void)hipSetDevice(g->ctx->device);
+    (void)hipDeviceSynchronize();                                            // launches still in flight read the table
+    for (uint32_t i = 0; i < g->n; i++) g->member[i]->group = nullptr;
+    delete g;
+}
+
+wsa_status wsa_train_group_epoch(wsa_train_group* g, const uint32_t* const* orders, void* stream) {
+    if (!g) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = g->ctx;
+    if (g->n == 0) return fail(ctx, WSA_ERR_INVALID, "a member of the group was destroyed before the group: the group is empty");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    for (uint32_t i = 0; orders && i < g->n; i++) {                          // every member's order before anything is enqueued
+        if (!orders[i]) continue;
+        const std::string why = order_refusal(g->member[i], orders[i]);
+        if (!why.empty()) return fail(ctx, WSA_ERR_INVALID, "member " + std::to_string(i) + ": " + why);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint32_t order_mask = 0, nl[WSA_TRAIN_GROUP_MAX], n_steps[WSA_TRAIN_GROUP_MAX], n_val[WSA_TRAIN_GROUP_MAX];
+    for (uint32_t i = 0; i < g->n; i++) {
+        wsa_trainer* t = g->member[i];
+        nl[i] = (uint32_t)t->nl; n_steps[i] = t->n_steps; n_val[i] = t->n_val;
+        if (orders && orders[i]) {
+            const wsa_status st = stage_order(t, orders[i], s);
+            if (st != WSA_OK) return st;
+            order_mask |= 1u << i;
+        }
+    }
+    group_plan(nl, n_steps, n_val, g->n, [&](uint32_t step, uint32_t lmax) {
+        for (uint32_t l = 0; l < lmax; l++) tg_launch(g, TG_FORWARD, step, (int)l, order_mask, s);
+        tg_launch(g, TG_LOSS, step, 0, order_mask, s);
+        if (step == TG_VALIDATION) return;
+        for (uint32_t j = 0; j < lmax; j++) {                                // a layer's backward reads its weights: before their update
+            if (j + 1 < lmax) tg_launch(g, TG_BACKWARD, step, (int)j, order_mask, s);
+            tg_launch(g, TG_UPDATE, step, (int)j, order_mask, s);
+        }
+    });
+    TgFinish f{};
+    for (uint32_t i = 0; i < g->n; i++) f.epoch[i] = ++g->member[i]->epoch;
+    hipLaunchKernelGGL(train_group_finish_kernel, dim3(g->n), dim3(256), 0, s, g->d_tab, f);
+    HIP_TRY(ctx, hipGetLastError());
+    return WSA_OK;
+}
+
+wsa_status wsa_train_group_stats(wsa_train_group* g, void* stream, wsa_train_stats* out) {
+    if (!g) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = g->ctx;
+    if (!out) return fail(ctx, WSA_ERR_INVALID, "null argument");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    for (uint32_t i = 0; i < g->n; i++)
+        HIP_TRY(ctx, hipMemcpyAsync(out + i, g->member[i]->d_stats, sizeof(wsa_train_stats), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    return WSA_OK;
+}
+
+wsa_status wsa_train_group_launches(const wsa_train_group* g, uint32_t* per_epoch) {
+    if (!g) return WSA_ERR_INVALID;
+    if (!per_epoch) return fail(g->ctx, WSA_ERR_INVALID, "null argument");
+    uint32_t nl[WSA_TRAIN_GROUP_MAX], n_steps[WSA_TRAIN_GROUP_MAX], n_val[WSA_TRAIN_GROUP_MAX];
+    for (uint32_t i = 0; i < g->n; i++) { nl[i] = (uint32_t)g->member[i]->nl; n_steps[i] = g->member[i]->n_steps; n_val[i] = g->member[i]->n_val; }
+    *per_epoch = (uint32_t)group_plan(nl, n_steps, n_val, g->n, [](uint32_t, uint32_t) {});
+    return WSA_OK;
 }
 
 }  // extern "C"

@@ -269,29 +269,34 @@ function loadModel(src) {
 // val_loss, val_acc}) mirrors ml5's whileTraining.  The selection, balancing, seeded initial weights and epoch orders live in trainmodel.js;
 // `init` ({kernels, biases}) and `orders` (Uint32Array [epochs][nTrain]) replace the seeded ones.  The epochs run off the JS thread.
 // The handle also carries `history` ([{loss, acc, val_loss, val_acc}] per epoch).  saveModel(handle, dir) writes the three files loadModel reads.
-function trainModel(o) {
+function plan_train_model(o) {        // -> {spec, job, onEpoch}: what the addon's train takes
   const tm = require('./trainmodel.js');
-  let nat, ctx, spec, data, job;
-  try {
-    const opt = Object.assign({}, tm.DEFAULT_OPTIONS, o.options || {});
-    data = tm.prepare(o.features, o.labels, o.classes);
-    const st = tm.stack(opt.layers, data.legend.length, data.width), epochs = o.epochs === undefined ? 10 : o.epochs | 0, seed = o.seed | 0;
-    const sp = tm.split(data.y.length, o.validationSplit);
-    const init = o.init || tm.glorotInit(Array.from(st.units), seed);
-    spec = { units: st.units, activation: st.activation, kernels: init.kernels.map((k) => Float32Array.from(k)), biases: init.biases.map((b) => Float32Array.from(b)),
-      inMin: data.inMin, inMax: data.inMax, labels: data.legend.slice() };
-    job = { features: data.features, y: data.y, nVal: sp.nVal, batchSize: o.batchSize === undefined ? 32 : o.batchSize, learningRate: opt.learningRate, epochs,
-      orders: o.orders || tm.epochOrders(sp.nTrain, epochs, seed + 1) };
-    nat = addon();
-    ctx = contexts_for(nat, settings.devices ? settings.devices.slice() : [settings.device])[0];
-  } catch (e) { return Promise.reject(e); }
-  return nat.train(ctx, spec, job, typeof o.onEpoch === 'function' ? o.onEpoch : undefined).then((r) => {
-    const h = { spec: Object.assign({}, spec, { kernels: r.kernels, biases: r.biases }), natives: new Map(), released: false, history: [] };
-    for (let e = 0; e < job.epochs; e++) h.history.push({ loss: r.history[4 * e], acc: r.history[4 * e + 1], val_loss: r.history[4 * e + 2], val_acc: r.history[4 * e + 3] });
-    h.labels = h.spec.labels.slice();
-    loaded_models.add(h);
-    return h;
-  });
+  const opt = Object.assign({}, tm.DEFAULT_OPTIONS, o.options || {});
+  const data = tm.prepare(o.features, o.labels, o.classes);
+  const st = tm.stack(opt.layers, data.legend.length, data.width), epochs = o.epochs === undefined ? 10 : o.epochs | 0, seed = o.seed | 0;
+  const sp = tm.split(data.y.length, o.validationSplit);
+  const init = o.init || tm.glorotInit(Array.from(st.units), seed);
+  const spec = { units: st.units, activation: st.activation, kernels: init.kernels.map((k) => Float32Array.from(k)), biases: init.biases.map((b) => Float32Array.from(b)),
+    inMin: data.inMin, inMax: data.inMax, labels: data.legend.slice() };
+  const job = { features: data.features, y: data.y, nVal: sp.nVal, batchSize: o.batchSize === undefined ? 32 : o.batchSize, learningRate: opt.learningRate, epochs,
+    orders: o.orders || tm.epochOrders(sp.nTrain, epochs, seed + 1) };
+  return { spec, job, onEpoch: typeof o.onEpoch === 'function' ? o.onEpoch : undefined };
+}
+function trained_handle(plan, r) {    // the model handle of a finished run `r` of the addon's train / trainGroup
+  const h = { spec: Object.assign({}, plan.spec, { kernels: r.kernels, biases: r.biases }), natives: new Map(), released: false, history: [] };
+  for (let e = 0; e < plan.job.epochs; e++) h.history.push({ loss: r.history[4 * e], acc: r.history[4 * e + 1], val_loss: r.history[4 * e + 2], val_acc: r.history[4 * e + 3] });
+  h.labels = h.spec.labels.slice();
+  loaded_models.add(h);
+  return h;
+}
+function train_context() {
+  const nat = addon();
+  return { nat, ctx: contexts_for(nat, settings.devices ? settings.devices.slice() : [settings.device])[0] };
+}
+function trainModel(o) {
+  let plan, t;
+  try { plan = plan_train_model(o); t = train_context(); } catch (e) { return Promise.reject(e); }
+  return t.nat.train(t.ctx, plan.spec, plan.job, plan.onEpoch).then((r) => trained_handle(plan, r));
 }
 // ---- the app's regression models for the ordinal labels V, A and D (ref src/neuralmodel.js:268-333 train_nn's ordinal branch, :410-585 predict_db_nn /
 // predict_single; specification TR-2, include/wsa.h "Regression models").
@@ -300,30 +305,44 @@ function trainModel(o) {
 // `history` and spec.outMin / spec.outMax; saveModel / loadModel write and read its directory (dist/nnmodel/<db>/ords_<label>/).
 // predictValues(handle, features: [[53 numbers]]) -> Float64Array, per row what ml5's predictMultiple gives as result[0].value.
 // A regression handle is not a prediction model: setPredictionModel(s) need class probabilities, and trainModel keeps refusing a stack without softmax.
-function trainRegression(features, values, o) {
-  o = o || {};
+function plan_train_regression(features, values, o) {
   const tm = require('./trainmodel.js');
-  let nat, ctx, spec, data, job;
+  const opt = Object.assign({}, tm.DEFAULT_OPTIONS_ORDS, o.options || {});
+  const data = tm.prepareOrdinal(features, values);
+  const st = tm.stackRegression(opt.layers, data.width), epochs = o.epochs === undefined ? 10 : o.epochs | 0, seed = o.seed | 0;
+  const sp = tm.split(data.values.length, o.validationSplit);
+  const init = o.init || tm.glorotInit(Array.from(st.units), seed);
+  const spec = { units: st.units, activation: st.activation, kernels: init.kernels.map((k) => Float32Array.from(k)), biases: init.biases.map((b) => Float32Array.from(b)),
+    inMin: data.inMin, inMax: data.inMax, labels: [], outMin: data.outMin, outMax: data.outMax };
+  const job = { features: data.features, values: data.values, outMin: data.outMin, outMax: data.outMax, nVal: sp.nVal, batchSize: o.batchSize === undefined ? 32 : o.batchSize,
+    learningRate: opt.learningRate, epochs, orders: o.orders || tm.epochOrders(sp.nTrain, epochs, seed + 1) };
+  return { spec, job, onEpoch: typeof o.onEpoch === 'function' ? o.onEpoch : undefined };
+}
+function trainRegression(features, values, o) {
+  let plan, t;
+  try { plan = plan_train_regression(features, values, o || {}); t = train_context(); } catch (e) { return Promise.reject(e); }
+  return t.nat.train(t.ctx, plan.spec, plan.job, plan.onEpoch).then((r) => trained_handle(plan, r));
+}
+// ---- several models at once (K7g / specification TG-1, include/wsa.h "Training groups"): the app needs one model per DB and head, and at ml5's batch of 32
+// an epoch is bound by its launches, so the jobs' trainers step in lock step, one launch per stage for all of them.
+// trainModels(jobs) -> Promise of an array of model handles, in job order, identical to the handles of one-by-one calls.  A job is either the object
+// trainModel takes or {regression: true, features, values, ...trainRegression's options}; onEpoch is per job.  A job with fewer epochs stops stepping;
+// more than 32 jobs run as consecutive groups of 32.
+const TRAIN_GROUP_MAX = 32;
+function trainModels(jobs) {
+  let plans, t;
   try {
-    const opt = Object.assign({}, tm.DEFAULT_OPTIONS_ORDS, o.options || {});
-    data = tm.prepareOrdinal(features, values);
-    const st = tm.stackRegression(opt.layers, data.width), epochs = o.epochs === undefined ? 10 : o.epochs | 0, seed = o.seed | 0;
-    const sp = tm.split(data.values.length, o.validationSplit);
-    const init = o.init || tm.glorotInit(Array.from(st.units), seed);
-    spec = { units: st.units, activation: st.activation, kernels: init.kernels.map((k) => Float32Array.from(k)), biases: init.biases.map((b) => Float32Array.from(b)),
-      inMin: data.inMin, inMax: data.inMax, labels: [], outMin: data.outMin, outMax: data.outMax };
-    job = { features: data.features, values: data.values, outMin: data.outMin, outMax: data.outMax, nVal: sp.nVal, batchSize: o.batchSize === undefined ? 32 : o.batchSize,
-      learningRate: opt.learningRate, epochs, orders: o.orders || tm.epochOrders(sp.nTrain, epochs, seed + 1) };
-    nat = addon();
-    ctx = contexts_for(nat, settings.devices ? settings.devices.slice() : [settings.device])[0];
+    if (!Array.isArray(jobs)) throw 'trainModels(jobs): an array of trainModel objects and {regression: true, features, values, ...} objects';
+    plans = jobs.map((o) => (o && o.regression ? plan_train_regression(o.features, o.values, o) : plan_train_model(o)));
+    t = train_context();
   } catch (e) { return Promise.reject(e); }
-  return nat.train(ctx, spec, job, typeof o.onEpoch === 'function' ? o.onEpoch : undefined).then((r) => {
-    const h = { spec: Object.assign({}, spec, { kernels: r.kernels, biases: r.biases }), natives: new Map(), released: false, history: [] };
-    for (let e = 0; e < job.epochs; e++) h.history.push({ loss: r.history[4 * e], acc: r.history[4 * e + 1], val_loss: r.history[4 * e + 2], val_acc: r.history[4 * e + 3] });
-    h.labels = [];
-    loaded_models.add(h);
-    return h;
-  });
+  let chain = Promise.resolve([]);
+  for (let first = 0; first < plans.length; first += TRAIN_GROUP_MAX) {
+    const part = plans.slice(first, first + TRAIN_GROUP_MAX);
+    chain = chain.then((done) => t.nat.trainGroup(t.ctx, part.map((p) => (p.onEpoch ? [p.spec, p.job, p.onEpoch] : [p.spec, p.job])))
+      .then((rs) => done.concat(rs.map((r, i) => trained_handle(part[i], r)))));
+  }
+  return chain;
 }
 function predictValues(handle, features) {
   if (!loaded_models.has(handle) || handle.released) throw 'predictValues: the model handle was released (shutdown()) or is not one of loadModel / trainRegression';
@@ -1109,5 +1128,5 @@ function set_predicted_label_for_segment(si, idx, label) {                      
 
 module.exports = { configure, LaunchAudioNodes, StopAudioNodes, set_predicted_label_for_segment, LaunchBatch, LaunchBatches,
   StreamOpen, STREAM_ACTIVE, STREAM_START, STREAM_STOP, shutdown, allocPinned, freePinned,
-  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, _values_after: values_after, loadModel, setPredictionModel, setPredictionModels, setPredictionKnn, setPredictionValues, trainModel, saveModel, trainRegression, predictValues, predictDB, statsTable,
+  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, _values_after: values_after, loadModel, setPredictionModel, setPredictionModels, setPredictionKnn, setPredictionValues, trainModel, trainModels, saveModel, trainRegression, predictValues, predictDB, statsTable,
   KNNClassifier, trainKnn, predictKnn };

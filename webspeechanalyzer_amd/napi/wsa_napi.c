@@ -1130,18 +1130,33 @@ static void *train_thread(void *arg) {
     if (m) { m->j = j; m->epoch = -1; napi_call_threadsafe_function(j->tsfn, m, napi_tsfn_blocking); }
     return NULL;
 }
+/* {kernels, biases, history} of a finished job */
+static napi_value train_result(napi_env env, train_job *j) {
+    napi_value o, ka, ba; napi_create_object(env, &o); napi_create_array_with_length(env, (size_t)j->nl, &ka); napi_create_array_with_length(env, (size_t)j->nl, &ba);
+    for (int l = 0; l < j->nl; l++) {
+        napi_set_element(env, ka, (uint32_t)l, make_typed(env, napi_float32_array, j->kernel[l], (size_t)j->units[l] * (size_t)j->units[l + 1], sizeof(float)));
+        napi_set_element(env, ba, (uint32_t)l, make_typed(env, napi_float32_array, j->bias[l], (size_t)j->units[l + 1], sizeof(float)));
+    }
+    napi_set_named_property(env, o, "kernels", ka); napi_set_named_property(env, o, "biases", ba);
+    napi_set_named_property(env, o, "history", make_typed(env, napi_float64_array, j->history, (size_t)j->epochs * 4, sizeof(double)));
+    return o;
+}
+/* the job's onEpoch(epoch, {loss, acc, val_loss, val_acc}), if it has one */
+static void train_on_epoch(napi_env env, train_job *j, int32_t epoch, const wsa_train_stats *s) {
+    napi_value fn, undef, argv[2], v;
+    if (j->on_epoch && napi_get_reference_value(env, j->on_epoch, &fn) == napi_ok && napi_get_undefined(env, &undef) == napi_ok &&
+        napi_create_int32(env, epoch, &argv[0]) == napi_ok && napi_create_object(env, &argv[1]) == napi_ok) {
+        const char *names[4] = {"loss", "acc", "val_loss", "val_acc"}; const double vals[4] = {s->loss, s->acc, s->val_loss, s->val_acc};
+        for (int i = 0; i < 4; i++) if (napi_create_double(env, vals[i], &v) == napi_ok) napi_set_named_property(env, argv[1], names[i], v);
+        napi_call_function(env, undef, fn, 2, argv, NULL);
+    }
+}
 static void train_call_js(napi_env env, napi_value js_cb, void *context, void *data) {
     train_msg *m = (train_msg *)data;
     train_job *j = m->j;
     if (!env) { free(m); return; }
     if (m->epoch >= 0) {
-        napi_value fn, undef, argv[2], v;
-        if (j->on_epoch && napi_get_reference_value(env, j->on_epoch, &fn) == napi_ok && napi_get_undefined(env, &undef) == napi_ok &&
-            napi_create_int32(env, m->epoch, &argv[0]) == napi_ok && napi_create_object(env, &argv[1]) == napi_ok) {
-            const char *names[4] = {"loss", "acc", "val_loss", "val_acc"}; const double vals[4] = {m->s.loss, m->s.acc, m->s.val_loss, m->s.val_acc};
-            for (int i = 0; i < 4; i++) if (napi_create_double(env, vals[i], &v) == napi_ok) napi_set_named_property(env, argv[1], names[i], v);
-            napi_call_function(env, undef, fn, 2, argv, NULL);
-        }
+        train_on_epoch(env, j, m->epoch, &m->s);
         free(m);
         return;
     }
@@ -1151,16 +1166,7 @@ static void train_call_js(napi_env env, napi_value js_cb, void *context, void *d
     if (j->st != WSA_OK) {
         napi_value msg; napi_create_string_utf8(env, j->err, NAPI_AUTO_LENGTH, &msg);
         napi_reject_deferred(env, j->deferred, msg);
-    } else {
-        napi_value o, ka, ba; napi_create_object(env, &o); napi_create_array_with_length(env, (size_t)j->nl, &ka); napi_create_array_with_length(env, (size_t)j->nl, &ba);
-        for (int l = 0; l < j->nl; l++) {
-            napi_set_element(env, ka, (uint32_t)l, make_typed(env, napi_float32_array, j->kernel[l], (size_t)j->units[l] * (size_t)j->units[l + 1], sizeof(float)));
-            napi_set_element(env, ba, (uint32_t)l, make_typed(env, napi_float32_array, j->bias[l], (size_t)j->units[l + 1], sizeof(float)));
-        }
-        napi_set_named_property(env, o, "kernels", ka); napi_set_named_property(env, o, "biases", ba);
-        napi_set_named_property(env, o, "history", make_typed(env, napi_float64_array, j->history, (size_t)j->epochs * 4, sizeof(double)));
-        napi_resolve_deferred(env, j->deferred, o);
-    }
+    } else napi_resolve_deferred(env, j->deferred, train_result(env, j));
     if (j->on_epoch) napi_delete_reference(env, j->on_epoch);
     napi_release_threadsafe_function(j->tsfn, napi_tsfn_release);
     train_job_free(j);
@@ -1170,17 +1176,16 @@ static int num_of(napi_env env, napi_value o, const char *name, double *out) {
     return napi_get_named_property(env, o, name, &v) == napi_ok && napi_typeof(env, v, &t) == napi_ok && t == napi_number && napi_get_value_double(env, v, out) == napi_ok;
 }
 static void *dup_bytes(const void *p, size_t bytes) { void *q = malloc(bytes ? bytes : 1); if (q && bytes) memcpy(q, p, bytes); return q; }
-static napi_value fn_train(napi_env env, napi_callback_info info) {
-    size_t argc = 4; napi_value argv[4];
-    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    ctx_box *box = argc ? get_box(env, argv[0]) : NULL;
-    const char *usage = "train(ctx, {units, activation, kernels, biases, inMin, inMax}, {features: Float64Array, y: Int32Array | values: Float64Array + outMin + outMax, nVal, batchSize, learningRate, epochs, orders?: Uint32Array}, onEpoch?)";
-    if (!box || !box->ctx || argc < 3) { napi_throw_type_error(env, NULL, usage); return NULL; }
+static const char *TRAIN_USAGE = "train(ctx, {units, activation, kernels, biases, inMin, inMax}, {features: Float64Array, y: Int32Array | values: Float64Array + outMin + outMax, nVal, batchSize, learningRate, epochs, orders?: Uint32Array}, onEpoch?)";
+/* a job from train's arguments (argv[0] unused, argv[1] the spec, argv[2] the run, argv[3] onEpoch when argc > 3), the inputs copied; NULL with an
+ * exception pending */
+static train_job *train_job_from(napi_env env, ctx_box *box, size_t argc, const napi_value *argv) {
+    const char *usage = TRAIN_USAGE;
     int32_t *units = NULL, *act = NULL, *y = NULL; double *mn = NULL, *mx = NULL, *feat = NULL, *values = NULL; uint32_t *orders = NULL;
     size_t nu = 0, na = 0, nmn = 0, nmx = 0, nf = 0, ny = 0, no = 0;
     double n_val = 0, batch = 0, lr = 0, epochs = 0, out_min = 0, out_max = 0;
     /* a regression run (specification TR-2): `values` (the label's real values) with `outMin` / `outMax` in place of `y` */
-    const int regress = argc >= 3 && typed_of(env, argv[2], "values", napi_float64_array, (void **)&values, &ny);
+    const int regress = typed_of(env, argv[2], "values", napi_float64_array, (void **)&values, &ny);
     if (regress && (!num_of(env, argv[2], "outMin", &out_min) || !num_of(env, argv[2], "outMax", &out_max))) { napi_throw_type_error(env, NULL, usage); return NULL; }
     if (!typed_of(env, argv[1], "units", napi_int32_array, (void **)&units, &nu) || !typed_of(env, argv[1], "activation", napi_int32_array, (void **)&act, &na) ||
         !typed_of(env, argv[1], "inMin", napi_float64_array, (void **)&mn, &nmn) || !typed_of(env, argv[1], "inMax", napi_float64_array, (void **)&mx, &nmx) ||
@@ -1216,6 +1221,15 @@ static napi_value fn_train(napi_env env, napi_callback_info info) {
     if (!j->feat || (regress ? !j->values : !j->y) || !j->history || (orders && !j->orders)) { train_job_free(j); napi_throw_error(env, NULL, "out of memory"); return NULL; }
     napi_valuetype ft = napi_undefined;
     if (argc > 3 && napi_typeof(env, argv[3], &ft) == napi_ok && ft == napi_function && napi_create_reference(env, argv[3], 1, &j->on_epoch) != napi_ok) j->on_epoch = NULL;
+    return j;
+}
+static napi_value fn_train(napi_env env, napi_callback_info info) {
+    size_t argc = 4; napi_value argv[4];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ctx_box *box = argc ? get_box(env, argv[0]) : NULL;
+    if (!box || !box->ctx || argc < 3) { napi_throw_type_error(env, NULL, TRAIN_USAGE); return NULL; }
+    train_job *j = train_job_from(env, box, argc, argv);
+    if (!j) return NULL;
     napi_value promise, name;
     if (napi_create_promise(env, &j->deferred, &promise) != napi_ok || napi_create_string_utf8(env, "wsa_train", NAPI_AUTO_LENGTH, &name) != napi_ok ||
         napi_create_threadsafe_function(env, NULL, NULL, name, 0, 1, NULL, NULL, NULL, train_call_js, &j->tsfn) != napi_ok) {
@@ -1228,6 +1242,137 @@ static napi_value fn_train(napi_env env, napi_callback_info info) {
         if (j->on_epoch) napi_delete_reference(env, j->on_epoch);
         napi_value msg; napi_create_string_utf8(env, "train: could not start a thread", NAPI_AUTO_LENGTH, &msg); napi_reject_deferred(env, j->deferred, msg);
         train_job_free(j);
+    }
+    return promise;
+}
+
+/* ---- training groups (wsa_train_group_*, K7g, specification TG-1): trainGroup(ctx, [[spec, run, onEpoch | undefined], ...]) -> Promise of an array with,
+ * per job and in job order, what train resolves to.  1 .. WSA_TRAIN_GROUP_MAX jobs, each with train's own arguments; classifiers and regression
+ * models mix.  All jobs' trainers step in lock step on one thread, one launch per stage for all of them; a job with fewer epochs leaves and the group
+ * is formed again from the rest, so every job's result equals its own train call bit for bit.  A job's onEpoch fires after each of ITS epochs. */
+typedef struct {
+    ctx_box *box; napi_deferred deferred; napi_threadsafe_function tsfn; pthread_t thread;
+    uint32_t n; train_job *job[WSA_TRAIN_GROUP_MAX];
+    wsa_status st; char err[512];
+} train_group_job;
+typedef struct { train_group_job *g; uint32_t member; int32_t epoch; wsa_train_stats s; } train_group_msg;          /* epoch < 0: the run is over */
+
+static void train_group_free(napi_env env, train_group_job *g) {
+    for (uint32_t i = 0; i < g->n; i++) {
+        if (env && g->job[i]->on_epoch) napi_delete_reference(env, g->job[i]->on_epoch);
+        train_job_free(g->job[i]);
+    }
+    free(g);
+}
+static void *train_group_thread(void *arg) {
+    train_group_job *g = (train_group_job *)arg;
+    wsa_ctx *ctx = g->box->ctx;
+    wsa_trainer *t[WSA_TRAIN_GROUP_MAX] = {0};
+    uint32_t longest = 0;
+    g->st = WSA_OK;
+    for (uint32_t i = 0; i < g->n && g->st == WSA_OK; i++) {
+        train_job *j = g->job[i];
+        wsa_model_desc d = {j->nl, j->units, j->act, (const float *const *)j->kernel, (const float *const *)j->bias, j->mn, j->mx, NULL};
+        g->st = j->values ? wsa_regress_trainer_create(ctx, &d, j->feat, j->values, j->n, j->n_val, j->batch, j->lr, j->out_min, j->out_max, &t[i])
+                          : wsa_trainer_create(ctx, &d, j->feat, j->y, j->n, j->n_val, j->batch, j->lr, &t[i]);
+        if (j->epochs > longest) longest = j->epochs;
+    }
+    wsa_train_group *grp = NULL;
+    uint32_t live[WSA_TRAIN_GROUP_MAX], n_live = 0;                      /* the members of grp, as job indices */
+    for (uint32_t e = 0; g->st == WSA_OK && e < longest; e++) {
+        uint32_t now[WSA_TRAIN_GROUP_MAX], n_now = 0;
+        for (uint32_t i = 0; i < g->n; i++) if (g->job[i]->epochs > e) now[n_now++] = i;
+        if (!grp || n_now != n_live) {                                   /* jobs only ever leave: the same count is the same set */
+            wsa_trainer *members[WSA_TRAIN_GROUP_MAX];
+            if (grp) { wsa_train_group_destroy(grp); grp = NULL; }
+            for (uint32_t k = 0; k < n_now; k++) { live[k] = now[k]; members[k] = t[now[k]]; }
+            n_live = n_now;
+            g->st = wsa_train_group_create(ctx, members, n_live, &grp);
+            if (g->st != WSA_OK) break;
+        }
+        const uint32_t *orders[WSA_TRAIN_GROUP_MAX];
+        wsa_train_stats s[WSA_TRAIN_GROUP_MAX];
+        for (uint32_t k = 0; k < n_live; k++) {
+            const train_job *j = g->job[live[k]];
+            orders[k] = j->orders ? j->orders + (size_t)e * (j->n - j->n_val) : NULL;
+        }
+        g->st = wsa_train_group_epoch(grp, orders, g->box->queue);
+        if (g->st == WSA_OK) g->st = wsa_train_group_stats(grp, g->box->queue, s);
+        if (g->st != WSA_OK) break;
+        for (uint32_t k = 0; k < n_live; k++) {
+            train_job *j = g->job[live[k]];
+            j->history[4 * e] = s[k].loss; j->history[4 * e + 1] = s[k].acc; j->history[4 * e + 2] = s[k].val_loss; j->history[4 * e + 3] = s[k].val_acc;
+            train_group_msg *m = malloc(sizeof *m);
+            if (m) { m->g = g; m->member = live[k]; m->epoch = (int32_t)e; m->s = s[k]; if (napi_call_threadsafe_function(g->tsfn, m, napi_tsfn_blocking) != napi_ok) free(m); }
+        }
+    }
+    if (g->st != WSA_OK) snprintf(g->err, sizeof g->err, "%s", wsa_last_error(ctx));
+    if (grp) wsa_train_group_destroy(grp);                               /* before its members */
+    for (uint32_t i = 0; i < g->n; i++) {
+        if (g->st == WSA_OK && t[i]) {
+            g->st = wsa_trainer_copy_weights(t[i], g->box->queue, g->job[i]->kernel, g->job[i]->bias);
+            if (g->st != WSA_OK) snprintf(g->err, sizeof g->err, "%s", wsa_last_error(ctx));
+        }
+        if (t[i]) wsa_trainer_destroy(t[i]);
+    }
+    train_group_msg *m = malloc(sizeof *m);                              /* (a few bytes: if even this fails the Promise stays pending) */
+    if (m) { m->g = g; m->member = 0; m->epoch = -1; napi_call_threadsafe_function(g->tsfn, m, napi_tsfn_blocking); }
+    return NULL;
+}
+static void train_group_call_js(napi_env env, napi_value js_cb, void *context, void *data) {
+    train_group_msg *m = (train_group_msg *)data;
+    train_group_job *g = m->g;
+    if (!env) { free(m); return; }
+    if (m->epoch >= 0) {
+        train_on_epoch(env, g->job[m->member], m->epoch, &m->s);
+        free(m);
+        return;
+    }
+    free(m);
+    pthread_join(g->thread, NULL);
+    if (g->box->children) g->box->children--;
+    if (g->st != WSA_OK) {
+        napi_value msg; napi_create_string_utf8(env, g->err, NAPI_AUTO_LENGTH, &msg);
+        napi_reject_deferred(env, g->deferred, msg);
+    } else {
+        napi_value out; napi_create_array_with_length(env, (size_t)g->n, &out);
+        for (uint32_t i = 0; i < g->n; i++) napi_set_element(env, out, i, train_result(env, g->job[i]));
+        napi_resolve_deferred(env, g->deferred, out);
+    }
+    napi_release_threadsafe_function(g->tsfn, napi_tsfn_release);
+    train_group_free(env, g);
+}
+static napi_value fn_train_group(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ctx_box *box = argc ? get_box(env, argv[0]) : NULL;
+    const char *usage = "trainGroup(ctx, [[spec, run, onEpoch?], ...]): 1 .. 32 jobs, each with train's arguments";
+    bool is_array = false; uint32_t n = 0;
+    if (!box || !box->ctx || argc < 2 || napi_is_array(env, argv[1], &is_array) != napi_ok || !is_array || napi_get_array_length(env, argv[1], &n) != napi_ok ||
+        n < 1 || n > WSA_TRAIN_GROUP_MAX) { napi_throw_type_error(env, NULL, usage); return NULL; }
+    train_group_job *g = calloc(1, sizeof *g);
+    if (!g) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    g->box = box;
+    for (uint32_t i = 0; i < n; i++) {
+        napi_value item, a[4]; bool ia = false; uint32_t len = 0;
+        if (napi_get_element(env, argv[1], i, &item) != napi_ok || napi_is_array(env, item, &ia) != napi_ok || !ia || napi_get_array_length(env, item, &len) != napi_ok ||
+            len < 2 || len > 3) { train_group_free(env, g); napi_throw_type_error(env, NULL, usage); return NULL; }
+        a[0] = argv[0];
+        for (uint32_t k = 0; k < len; k++) if (napi_get_element(env, item, k, &a[k + 1]) != napi_ok) { train_group_free(env, g); napi_throw_type_error(env, NULL, usage); return NULL; }
+        train_job *j = train_job_from(env, box, (size_t)len + 1, a);
+        if (!j) { train_group_free(env, g); return NULL; }
+        g->job[g->n++] = j;
+    }
+    napi_value promise, name;
+    if (napi_create_promise(env, &g->deferred, &promise) != napi_ok || napi_create_string_utf8(env, "wsa_train_group", NAPI_AUTO_LENGTH, &name) != napi_ok ||
+        napi_create_threadsafe_function(env, NULL, NULL, name, 0, 1, NULL, NULL, NULL, train_group_call_js, &g->tsfn) != napi_ok) {
+        train_group_free(env, g); napi_throw_error(env, NULL, "trainGroup: could not set up the job"); return NULL;
+    }
+    box->children++;                                             /* until the run's last message: destroy() refuses meanwhile */
+    if (pthread_create(&g->thread, NULL, train_group_thread, g) != 0) {
+        box->children--; napi_release_threadsafe_function(g->tsfn, napi_tsfn_release);
+        napi_value msg; napi_create_string_utf8(env, "trainGroup: could not start a thread", NAPI_AUTO_LENGTH, &msg); napi_reject_deferred(env, g->deferred, msg);
+        train_group_free(env, g);
     }
     return promise;
 }
@@ -1643,7 +1788,7 @@ NAPI_MODULE_INIT() {
         {"abiVersion", fn_abi_version}, {"freePinned", fn_free_pinned}, {"defaults", fn_defaults}, {"create", fn_create}, {"destroy", fn_destroy},
         {"geometry", fn_geometry}, {"allocPinned", fn_alloc_pinned}, {"binsHz", fn_bins_hz}, {"processBatch", fn_process_batch}, {"gatherRows", fn_gather_rows},
         {"streamOpen", fn_stream_open}, {"streamOpenMixed", fn_stream_open_mixed}, {"streamInfo", fn_stream_info}, {"streamPaced", fn_stream_paced}, {"streamInput", fn_stream_input}, {"streamStep", fn_stream_step}, {"streamClose", fn_stream_close}, {"streamSetModel", fn_stream_set_model}, {"streamSetEnsemble", fn_stream_set_ensemble}, {"streamSetKnn", fn_stream_set_knn},
-        {"modelCreate", fn_model_create}, {"modelDestroy", fn_model_destroy}, {"train", fn_train}, {"regressRows", fn_regress_rows},
+        {"modelCreate", fn_model_create}, {"modelDestroy", fn_model_destroy}, {"train", fn_train}, {"trainGroup", fn_train_group}, {"regressRows", fn_regress_rows},
         {"dbPredict", fn_db_predict}, {"dbTable", fn_db_table},
         {"knnCreate", fn_knn_create}, {"knnDestroy", fn_knn_destroy}, {"knnAdd", fn_knn_add}, {"knnClassify", fn_knn_classify}, {"batchKnn", fn_batch_knn}, {"batchKnnFold", fn_batch_knn_fold},
         {"streamSetRegress", fn_stream_set_regress}, {"batchRegressGroup", fn_batch_regress_group}};

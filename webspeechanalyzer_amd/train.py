@@ -3,7 +3,7 @@ ml5.neuralNetwork(...).train — selecting and balancing the stored level-13 row
 per-epoch orders (both from numpy's generator: the reference draws them from Math.random, so they are ours) — and the epochs on the
 GPU through capi.Trainer.  Classification only: the regression models (ords_*) and the '*' wildcard class are not supported.
 (That holds for prepare / stack / train.  The regression models have their own entry points below, specification TR-2:
-prepare_ordinal and train_regression.)"""
+prepare_ordinal and train_regression.  train_many runs several of either kind at once as a training group, specification TG-1.)"""
 import math
 
 import numpy as np
@@ -102,17 +102,23 @@ def stack(layers, n_classes, n_inputs=nnmodel.NFEAT):
     return units, acts
 
 
-def train(an, data, layers=None, learning_rate=DEFAULT_LEARNING_RATE, epochs=10, batch_size=32, validation_split=0.1, seed=0,
-          init=None, orders=None, on_epoch=None, stream=0):
-    """Trains on `an` (a capi.Analyzer) over data = prepare(...).  init: (kernels, biases) instead of glorot_init(units, seed); orders:
-    one order per epoch instead of epoch_orders(n_train, epochs, seed + 1).  on_epoch(epoch, stats) mirrors ml5's whileTraining (it
-    synchronises every epoch; without it only the last epoch is waited for).  Returns (nnmodel.ModelSpec, history)."""
+def _trainer(an, data, layers, learning_rate, epochs, batch_size, validation_split, seed, init, orders):
+    """(capi.Trainer, orders) of train's arguments"""
     units, acts = stack(layers or DEFAULT_LAYERS, len(data["legend"]), np.shape(data["features"])[1])
     ks, bs = init if init is not None else glorot_init(units, seed)
     n_train, n_val = split(len(data["features"]), validation_split)
     orders = orders if orders is not None else epoch_orders(n_train, epochs, seed + 1)
     spec = nnmodel.ModelSpec(units, acts, ks, bs, np.asarray(data["in_min"], np.float64), np.asarray(data["in_max"], np.float64), list(data["legend"]))
     tr = an.trainer(spec, data["features"], data["y"], n_val, batch_size, learning_rate)
+    return tr, orders
+
+
+def train(an, data, layers=None, learning_rate=DEFAULT_LEARNING_RATE, epochs=10, batch_size=32, validation_split=0.1, seed=0,
+          init=None, orders=None, on_epoch=None, stream=0):
+    """Trains on `an` (a capi.Analyzer) over data = prepare(...).  init: (kernels, biases) instead of glorot_init(units, seed); orders:
+    one order per epoch instead of epoch_orders(n_train, epochs, seed + 1).  on_epoch(epoch, stats) mirrors ml5's whileTraining (it
+    synchronises every epoch; without it only the last epoch is waited for).  Returns (nnmodel.ModelSpec, history)."""
+    tr, orders = _trainer(an, data, layers, learning_rate, epochs, batch_size, validation_split, seed, init, orders)
     try:
         history = []
         for e in range(epochs):
@@ -178,11 +184,8 @@ def stack_regression(layers, n_inputs=nnmodel.NFEAT):
     return units, acts
 
 
-def train_regression(an, data, layers=None, learning_rate=DEFAULT_LEARNING_RATE, epochs=10, batch_size=32, validation_split=0.1, seed=0,
-                     init=None, orders=None, on_epoch=None, stream=0):
-    """train(...) for a regression model (specification TR-2) over data = prepare_ordinal(...): the app's nn_default_options_ords stack
-    unless `layers` is given, Adam on the mean squared error of the normalised output.  Returns (nnmodel.ModelSpec with out_min /
-    out_max, history)."""
+def _regress_trainer(an, data, layers, learning_rate, epochs, batch_size, validation_split, seed, init, orders):
+    """(capi.Trainer, orders) of train_regression's arguments"""
     units, acts = stack_regression(layers or DEFAULT_LAYERS_ORDS, np.shape(data["features"])[1])
     ks, bs = init if init is not None else glorot_init(units, seed)
     n_train, n_val = split(len(data["features"]), validation_split)
@@ -190,6 +193,15 @@ def train_regression(an, data, layers=None, learning_rate=DEFAULT_LEARNING_RATE,
     spec = nnmodel.ModelSpec(units, acts, ks, bs, np.asarray(data["in_min"], np.float64), np.asarray(data["in_max"], np.float64), [],
                              float(data["out_min"]), float(data["out_max"]))
     tr = an.regress_trainer(spec, data["features"], data["values"], n_val, batch_size, learning_rate)
+    return tr, orders
+
+
+def train_regression(an, data, layers=None, learning_rate=DEFAULT_LEARNING_RATE, epochs=10, batch_size=32, validation_split=0.1, seed=0,
+                     init=None, orders=None, on_epoch=None, stream=0):
+    """train(...) for a regression model (specification TR-2) over data = prepare_ordinal(...): the app's nn_default_options_ords stack
+    unless `layers` is given, Adam on the mean squared error of the normalised output.  Returns (nnmodel.ModelSpec with out_min /
+    out_max, history)."""
+    tr, orders = _regress_trainer(an, data, layers, learning_rate, epochs, batch_size, validation_split, seed, init, orders)
     try:
         history = []
         for e in range(epochs):
@@ -202,3 +214,56 @@ def train_regression(an, data, layers=None, learning_rate=DEFAULT_LEARNING_RATE,
         return tr.spec_now(stream), history
     finally:
         tr.close()
+
+
+_JOB_DEFAULTS = dict(layers=None, learning_rate=DEFAULT_LEARNING_RATE, epochs=10, batch_size=32, validation_split=0.1, seed=0, init=None,
+                     orders=None, on_epoch=None)
+
+
+def train_many(an, jobs, stream=0):
+    """train / train_regression for several models at once (specification TG-1, K7g): jobs are dicts with those functions' arguments
+    (data, layers, learning_rate, epochs, batch_size, validation_split, seed, init, orders, on_epoch); data from prepare_ordinal
+    (it has "values") makes the job a regression model's.  The jobs' trainers step in lock step as one capi.TrainGroup, one launch per
+    stage for all of them; a job with fewer epochs stops stepping (the group is re-formed from the rest); more than 32 jobs run as
+    consecutive groups of 32.  Returns, in job order, exactly what train / train_regression return for the same arguments."""
+    from . import capi
+    out = [None] * len(jobs)
+    for first in range(0, len(jobs), capi.TRAIN_GROUP_MAX):
+        part = range(first, min(first + capi.TRAIN_GROUP_MAX, len(jobs)))
+        runs = []                                       # per job of the part: index, arguments, trainer, orders, history
+        try:
+            for j in part:
+                unknown = set(jobs[j]) - set(_JOB_DEFAULTS) - {"data"}
+                if unknown or "data" not in jobs[j]:
+                    raise ValueError(f"job {j}: " + (f"unknown arguments {sorted(unknown)}" if unknown else "no data"))
+                a = dict(_JOB_DEFAULTS, **jobs[j])
+                make = _regress_trainer if "values" in a["data"] else _trainer
+                tr, orders = make(an, a["data"], a["layers"], a["learning_rate"], a["epochs"], a["batch_size"], a["validation_split"],
+                                  a["seed"], a["init"], a["orders"])
+                runs.append(dict(j=j, a=a, tr=tr, orders=orders, history=[]))
+            e = 0
+            while True:
+                live = [r for r in runs if r["a"]["epochs"] > e]
+                if not live:
+                    break
+                until = min(r["a"]["epochs"] for r in live)             # the members are the same up to this epoch
+                group = an.train_group([r["tr"] for r in live])
+                try:
+                    for e in range(e, until):
+                        group.epoch([r["orders"][e] for r in live], stream)
+                        want = [r["a"]["on_epoch"] is not None or e == r["a"]["epochs"] - 1 for r in live]
+                        if any(want):
+                            for r, w, st in zip(live, want, group.stats(stream)):
+                                if w:
+                                    r["history"].append(st)
+                                    if r["a"]["on_epoch"] is not None:
+                                        r["a"]["on_epoch"](e, st)
+                finally:
+                    group.close()
+                e = until
+            for r in runs:
+                out[r["j"]] = (r["tr"].spec_now(stream), r["history"])
+        finally:
+            for r in runs:
+                r["tr"].close()
+    return out
