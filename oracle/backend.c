@@ -70,6 +70,32 @@ static const char *const arm_names[ARM_COUNT] = { GATE_ARMS(X) };
 #undef X
 #define ARM(S, a) ((S)->arms[ARM_##a]++)
 
+/* the arms of accumulate_fm and finalize that tests/tracker_rule_cases.py aims at (wsa_or_track_arm_*): one per side of every comparison, bumped where
+ * the arm is taken, read only by tests.  win<gap>_{lo,hi}_{in,out}: a peak below / above the track's bin at dist == win - 1 / dist == win (four per gap, in
+ * this order: accumulate_fm indexes them) */
+#define TRACK_ARMS(X) \
+    X(acc_no_peak) X(acc_called) \
+    X(gap_neg) X(gap0_in) X(gap1_in) X(gap2_in) X(gap3_in) X(gap4_in) \
+    X(win0_lo_in) X(win0_lo_out) X(win0_hi_in) X(win0_hi_out) X(win1_lo_in) X(win1_lo_out) X(win1_hi_in) X(win1_hi_out) \
+    X(win2_lo_in) X(win2_lo_out) X(win2_hi_in) X(win2_hi_out) X(win3_lo_in) X(win3_lo_out) X(win3_hi_in) X(win3_hi_out) \
+    X(score_pamp_le0) X(score_zero) X(score_le1) X(score_first) X(score_replaces) X(score_below_best) X(score_tie_kept) X(score_inf) \
+    X(multi_en_raised) X(multi_st_lowered) X(multi_pb_moved) X(multi_pb_equal_kept) \
+    X(upd_above) X(upd_equal) X(upd_below) X(upd_quirk) \
+    X(vel_h1) X(vel_h2) X(vel_h3) \
+    X(new_above) X(new_equal) X(new_below) \
+    X(rank_count1) X(rank_count2) X(rank_mb_lt7) X(rank_mb_eq7) X(rank_mb_tie) \
+    X(slot_first_le20) X(slot_first_gt20) X(slot_diff_eq20) X(slot_step) X(slot_fourth) \
+    X(str_bump) X(str_bump_int_above) X(str_bump_frac_above) X(str_ref_floor) X(str_ref_floor_eq) X(str_ref_frac_below) X(str_ref_floor_256) \
+    X(str_ref_f_eq) X(str_ref_l2) X(str_twice) \
+    X(syl_a_u20) X(syl_a_u21) X(syl_b_u10) X(syl_b_u11) X(syl_c_c4) X(syl_c_c5) X(syl_d_u4) X(syl_d_u5) X(syl_short) X(syl_sm_eq_floor)
+#define X(a) TARM_##a,
+enum { TRACK_ARMS(X) TARM_COUNT };
+#undef X
+#define X(a) #a,
+static const char *const tarm_names[TARM_COUNT] = { TRACK_ARMS(X) };
+#undef X
+#define TARM(S, a) ((S)->tarms[TARM_##a]++)
+
 struct wsa_or_seg {
     wsa_or_cfg cfg;
     /* segmenter state `o` (@B23439) */
@@ -92,6 +118,7 @@ struct wsa_or_seg {
     VEC(wsa_or_gate_frame) gframes;
     int32_t span_begin, reset0_in_frame, voiced_now;
     int64_t arms[ARM_COUNT];
+    int64_t tarms[TARM_COUNT];
 };
 
 static void track_free(track_t *t) {
@@ -165,7 +192,8 @@ double wsa_or_match_score(double gap, double dist, double n, double tbin, double
 static void accumulate_fm(wsa_or_seg *S, const uint32_t *e, const peak_t *pk, int32_t U, double n,
                           double energy, double floor_) {
     static const double win[4] = {3, 4, 6, 9};                                /* @B32325 */
-    if (U < 1) return;
+    if (U < 1) { TARM(S, acc_no_peak); return; }
+    TARM(S, acc_called);
     int32_t *asg = malloc(sizeof(int32_t) * (size_t)U);
     double *best = malloc(sizeof(double) * (size_t)U);
     for (int32_t o = 0; o < U; o++) { asg[o] = -1; best[o] = 0; }
@@ -174,13 +202,26 @@ static void accumulate_fm(wsa_or_seg *S, const uint32_t *e, const peak_t *pk, in
     for (int32_t r = 0; r < ntr; r++) {
         track_t *tr = &S->tracks.p[r];
         double gap = n - tr->last_frame;
+        if (gap < 0) TARM(S, gap_neg);
+        if (gap == 4) for (int32_t o = 0; o < U; o++) if (fabs(tr->last_bin - pk[o].l) < win[3]) TARM(S, gap4_in);
         if (gap >= 0 && gap < 4) {
             double len = tr->frames.n;
             for (int32_t o = 0; o < U; o++) {
                 double dist = fabs(tr->last_bin - pk[o].l);
+                const int32_t wa = TARM_win0_lo_in + 4 * (int32_t)gap + (pk[o].l > tr->last_bin ? 2 : 0);
+                if (dist == win[(int32_t)gap] - 1) S->tarms[wa]++;
+                if (dist == win[(int32_t)gap]) S->tarms[wa + 1]++;
                 if (dist < win[(int32_t)gap]) {
                     double sc = match_score(gap, dist, len, tr->last_bin, pk[o].l, tr->last_amp,
                                             (double)e[pk[o].l], tr->vel);
+                    S->tarms[TARM_gap0_in + (int32_t)gap]++;
+                    if (tr->last_amp < (double)e[pk[o].l] && !((double)e[pk[o].l] > 0)) TARM(S, score_pamp_le0);
+                    if (sc == 0) TARM(S, score_zero); else if (sc <= 1) TARM(S, score_le1);
+                    else if (best[o] == 0) TARM(S, score_first);
+                    else if (sc > best[o]) TARM(S, score_replaces);
+                    else if (sc == best[o]) TARM(S, score_tie_kept);
+                    else TARM(S, score_below_best);
+                    if (sc > 1 && isinf(sc)) TARM(S, score_inf);
                     if (sc > 1 && sc > best[o]) { best[o] = sc; asg[o] = r; }
                 }
             }
@@ -193,17 +234,24 @@ static void accumulate_fm(wsa_or_seg *S, const uint32_t *e, const peak_t *pk, in
         track_t *tr = &S->tracks.p[r];
         int32_t pb = pk[first].l;
         double amp = e[pb];                              /* read before the arg-max loop (quirk 3) */
+        if (amp > floor_) TARM(S, upd_above);
+        else {
+            if (amp == floor_) TARM(S, upd_equal); else TARM(S, upd_below);
+            for (int32_t o = first + 1; o < U; o++) if (asg[o] == r && e[pk[o].l] > floor_) { TARM(S, upd_quirk); break; }
+        }
         if (amp > floor_) {
             int32_t st = pk[first].i, en = pk[first].s;
             for (int32_t o = first; o < U; o++) if (asg[o] == r) {
-                if (pk[o].s > en) en = pk[o].s;
-                if (pk[o].i < st) st = pk[o].i;
-                if (e[pk[o].l] > e[pb]) pb = pk[o].l;
+                if (pk[o].s > en) { en = pk[o].s; TARM(S, multi_en_raised); }
+                if (pk[o].i < st) { st = pk[o].i; TARM(S, multi_st_lowered); }
+                if (o > first && e[pk[o].l] == e[pb]) TARM(S, multi_pb_equal_kept);
+                if (e[pk[o].l] > e[pb]) { pb = pk[o].l; TARM(S, multi_pb_moved); }
             }
             double be = 0;
             for (int32_t t = st; t <= en; t++) be += e[t];
             int32_t h = tr->bins.n;
             const double *P = tr->bins.p;
+            if (h >= 3) TARM(S, vel_h3); else if (h == 2) TARM(S, vel_h2); else if (h == 1) TARM(S, vel_h1);
             if (h >= 3) tr->vel = (pb - P[h - 1] + (P[h - 2] - P[h - 1]) + (P[h - 3] - P[h - 2])) / 3;
             else if (h == 2) tr->vel = (pb - P[h - 1] + (P[h - 2] - P[h - 1])) / 2;
             else if (h == 1) tr->vel = pb - P[h - 1];
@@ -217,6 +265,7 @@ static void accumulate_fm(wsa_or_seg *S, const uint32_t *e, const peak_t *pk, in
     for (int32_t o = 0; o < U; o++) if (asg[o] == -1) {
         int32_t pb = pk[o].l;
         double amp = e[pb];
+        if (amp > floor_) TARM(S, new_above); else if (amp == floor_) TARM(S, new_equal); else TARM(S, new_below);
         if (amp > floor_) {
             int32_t st = pk[o].i, en = pk[o].s;
             double be = 0;
@@ -318,13 +367,18 @@ static void finalize(wsa_or_seg *S, double e) {
     int32_t *rk = malloc(sizeof(int32_t) * (size_t)(ntr > 0 ? ntr : 1));
     for (int32_t t = 0; t < ntr; t++) {
         track_t *tr = &S->tracks.p[t];
+        if (tr->count == 1) TARM(S, rank_count1);
+        if (tr->count == 2) TARM(S, rank_count2);
         if (tr->count >= 2) {
             double mb = tr->sumEbin / tr->sumE;
+            if (mb < 7) TARM(S, rank_mb_lt7);
+            if (mb == 7) TARM(S, rank_mb_eq7);
             if (mb >= 7) {
                 int32_t r = 0;
                 while (r < nr) {
                     track_t *q = &S->tracks.p[rk[r]];
                     if (q->sumEbin / q->sumE > mb) break;
+                    if (q->sumEbin / q->sumE == mb) TARM(S, rank_mb_tie);
                     r++;
                 }
                 memmove(rk + r + 1, rk + r, sizeof(int32_t) * (size_t)(nr - r));
@@ -366,6 +420,10 @@ static void finalize(wsa_or_seg *S, double e) {
     for (int32_t t = 0; t < nr && !bad; t++) {
         track_t *tr = &S->tracks.p[rk[t]];
         double mb = tr->sumEbin / tr->sumE;
+        if (t == 0) { if (mb <= 20) TARM(S, slot_first_le20); else TARM(S, slot_first_gt20); }
+        else if (fabs(mb - last) == 20) TARM(S, slot_diff_eq20);
+        else if (fabs(mb - last) > 20) TARM(S, slot_step);
+        if (fabs(mb - last) > 20 && slot + 1 >= 3) TARM(S, slot_fourth);
         if (fabs(mb - last) > 20) { last = mb; slot++; if (slot >= 3) break; }
         for (int32_t i = 0; i < (int32_t)tr->count; i++) {
             int32_t l = slot;
@@ -375,7 +433,25 @@ static void finalize(wsa_or_seg *S, double e) {
                 int32_t d = (int32_t)tr->frames.p[i];
                 double wd = tr->ends.p[i] - tr->starts.p[i] + 1;
                 if (d >= len || d < 0) { bad = 1; break; }
+                {
+                    const double cur = fr[9 * d + 3 * l], fl = S->floor_;
+                    if (cur > fl && cur < f && l < 2) {
+                        TARM(S, str_bump);
+                        if (fl == floor(fl) && cur == fl + 1) TARM(S, str_bump_int_above);
+                        if (fl != floor(fl) && cur == floor(fl) + 1) TARM(S, str_bump_frac_above);
+                    } else if (cur > 0) {
+                        if (cur <= fl && cur < f && l < 2) {
+                            TARM(S, str_ref_floor);
+                            if (cur == fl) TARM(S, str_ref_floor_eq);
+                            if (fl != floor(fl) && cur == floor(fl)) TARM(S, str_ref_frac_below);
+                            if (fl >= 256) TARM(S, str_ref_floor_256);
+                        }
+                        if (cur > fl && cur == f && l < 2) TARM(S, str_ref_f_eq);
+                        if (cur > fl && cur < f && l == 2) TARM(S, str_ref_l2);
+                    }
+                }
                 if (fr[9 * d + 3 * l] > S->floor_ && fr[9 * d + 3 * l] < f && l < 2) l++;
+                if (fr[9 * d + 3 * l] != 0) TARM(S, str_twice);
                 fr[9 * d + 3 * l] = (float)f; fr[9 * d + 3 * l + 1] = (float)E; fr[9 * d + 3 * l + 2] = (float)wd;
                 sm[3 * d + 0] = (float)((double)sm[3 * d + 0] + f * E);
                 sm[3 * d + 1] = (float)((double)sm[3 * d + 1] + E);
@@ -393,9 +469,22 @@ static void finalize(wsa_or_seg *S, double e) {
     if (level == 10 || level == 13) {
         int32_t i = -1; double c = 0, u = 0;
         for (int32_t e2 = 0; e2 < len; e2++) {
+            if (sm[3 * e2 + 1] == S->floor_) TARM(S, syl_sm_eq_floor);
             if (sm[3 * e2 + 1] > S->floor_) { c = 0; u++; if (i < 0) i = e2; } else c++;
+            if (e2 < len - 1) {               /* each close condition at its two boundary values, where no other condition closes */
+                if (c == 1 && u == 20) TARM(S, syl_a_u20);
+                if (c == 1 && u == 21) TARM(S, syl_a_u21);
+                if (c == 2 && u == 10) TARM(S, syl_b_u10);
+                if (c == 2 && u == 11) TARM(S, syl_b_u11);
+                if (c == 4 && u > 0 && u <= 10) TARM(S, syl_c_c4);
+                if (c == 5 && u > 0 && u <= 10) TARM(S, syl_c_c5);
+            } else if (c == 0) {
+                if (u == 4) TARM(S, syl_d_u4);
+                if (u == 5) TARM(S, syl_d_u5);
+            }
             if ((u > 20 && c > 0) || (u > 10 && c > 1) || (u > 0 && c > 4) || (e2 >= len - 1 && u > 4)) {
                 int32_t t = e2 - (int32_t)c;
+                if (!(t - i > 1)) TARM(S, syl_short);
                 if (t - i > 1) {
                     syllable_t sy; memset(&sy, 0, sizeof(sy));
                     sy.seg = S->segs.n; sy.start = i; sy.len = t - i;
@@ -596,6 +685,10 @@ void wsa_or_gate_state(const wsa_or_seg *s, double out[12]) {
 int32_t wsa_or_gate_n_arms(void) { return ARM_COUNT; }
 const char *wsa_or_gate_arm_name(int32_t i) { return i >= 0 && i < ARM_COUNT ? arm_names[i] : NULL; }
 int64_t wsa_or_gate_arm_count(const wsa_or_seg *s, int32_t i) { return i >= 0 && i < ARM_COUNT ? s->arms[i] : -1; }
+
+int32_t wsa_or_track_n_arms(void) { return TARM_COUNT; }
+const char *wsa_or_track_arm_name(int32_t i) { return i >= 0 && i < TARM_COUNT ? tarm_names[i] : NULL; }
+int64_t wsa_or_track_arm_count(const wsa_or_seg *s, int32_t i) { return i >= 0 && i < TARM_COUNT ? s->tarms[i] : -1; }
 
 int32_t wsa_or_n_segments(const wsa_or_seg *s) { return s->segs.n; }
 void wsa_or_segment(const wsa_or_seg *s, int32_t i, int32_t out[5]) {

@@ -69,6 +69,11 @@ def lib():
     L.wsa_or_gate_arm_name.argtypes = [i32]
     L.wsa_or_gate_arm_count.restype = ctypes.c_int64
     L.wsa_or_gate_arm_count.argtypes = [vp, i32]
+    L.wsa_or_track_n_arms.restype = i32
+    L.wsa_or_track_arm_name.restype = ctypes.c_char_p
+    L.wsa_or_track_arm_name.argtypes = [i32]
+    L.wsa_or_track_arm_count.restype = ctypes.c_int64
+    L.wsa_or_track_arm_count.argtypes = [vp, i32]
     L.wsa_or_enable_trace.argtypes = [vp, i32]
     L.wsa_or_seg_free.argtypes = [vp]
     for name in ("wsa_or_n_segments", "wsa_or_n_syllables", "wsa_or_trace_len"):
@@ -177,6 +182,11 @@ def gate_arm_names():
     return [L.wsa_or_gate_arm_name(i).decode() for i in range(L.wsa_or_gate_n_arms())]
 
 
+def track_arm_names():
+    L = lib()
+    return [L.wsa_or_track_arm_name(i).decode() for i in range(L.wsa_or_track_n_arms())]
+
+
 def _gate_report(L, h):
     """What the gate decided (wsa_oracle.h "what the gate decided"): per frame called / t / stale / v / fl, per finalized segment
     [start, len, span begin, span end, c_ci, ctx_max, floor], the arm counters by name, the state as gate.hip's streams carry it."""
@@ -197,13 +207,14 @@ def _gate_report(L, h):
     return out
 
 
-def run_backend(spectra, cfg, trace=False, gate=False, cuts=()):
+def run_backend(spectra, cfg, trace=False, gate=False, cuts=(), track=False):
     """spectra: (frames, bands) uint32.  Returns dict mirroring tests/golden/gen/ref_driver.js output:
     segments_ci [[start,len]], syllables_ci [[[start,len]...]] (levels 10/13), features
     (level 5: [53] per segment; level 13: [[53]...] per segment), formants (level>=4); load [[max peaks, max live]] per
     segment (wsa_or_segment_load: what the device tracker's table limits are compared with).
     gate: also out["gate"], what the gate decided and which arms it took (_gate_report).  cuts: frames f after which (once frame f is pushed)
-    wsa_or_seg_cut is called, as csrc/gate.hip's stream kernel cuts a span at its ring."""
+    wsa_or_seg_cut is called, as csrc/gate.hip's stream kernel cuts a span at its ring.  track: also out["track"]["arms"], which arms of accumulate_fm and
+    finalize the clip took (wsa_oracle.h wsa_or_track_arm_*)."""
     L = lib()
     spectra = np.ascontiguousarray(spectra, dtype=np.uint32)
     frames, bands = spectra.shape
@@ -267,6 +278,8 @@ def run_backend(spectra, cfg, trace=False, gate=False, cuts=()):
         out["callbacks"] = callbacks(out, cfg)
         if gate:
             out["gate"] = _gate_report(L, h)
+        if track:
+            out["track"] = dict(arms={L.wsa_or_track_arm_name(i).decode(): int(L.wsa_or_track_arm_count(h, i)) for i in range(L.wsa_or_track_n_arms())})
         if trace:
             n = L.wsa_or_trace_len(h)
             out["trace"] = np.ctypeslib.as_array(L.wsa_or_trace(h), shape=(n, 10)).copy() if n else np.zeros((0, 10))
