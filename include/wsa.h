@@ -617,7 +617,7 @@ wsa_status wsa_stream_copy_converted(wsa_stream *st, float *out, uint32_t cap, u
  * `trainInternal` @2768349 ({epochs: 10, batchSize: 32, validationSplit: .1}; model.fit @2755107 shuffles per epoch),
  * `normalizeValue` @2469274, `createOneHotEncodings` @2745375.  One run is the deterministic function TR-1 of DESIGN.md: the SGD
  * arithmetic is pinned to tfjs by tests/golden/train_expected.json; the initial weights and the order of the training rows in every
- * epoch are the caller's (the reference draws both from Math.random).  K7 (csrc/train.hip) is reproducible bit for bit.
+ * epoch are the caller's (the reference draws both from Math.random).  K7 (csrc/train.hip, csrc/train_stages.hpp) is reproducible bit for bit.
  * Classification only: the regression models (ords_*: mean squared error, Adam) are not trained.
  * A trainer belongs to the context it was created on; destroy it before that context.
  */
@@ -686,7 +686,7 @@ wsa_status wsa_regress_trainer_create(wsa_ctx *ctx, const wsa_model_desc *init, 
  * At the app's settings (ml5's batch of 32) an epoch of one trainer is bound by its launches, not by arithmetic, and the app needs one
  * model per DB and head (setPredictionModels / setPredictionValues: available_DBs x {cats_emotion, ords_V, ords_A, ords_D}).  A group
  * steps up to WSA_TRAIN_GROUP_MAX trainers in lock step: every launch covers the same stage of every member that has that stage in this
- * step (K7g, csrc/train.hip), so N models train in about the wall time of the longest one.  Specification TG-1 of DESIGN.md: a group
+ * step (K7g, csrc/train_group.hip), so N models train in about the wall time of the longest one.  Specification TG-1 of DESIGN.md: a group
  * epoch IS wsa_trainer_epoch on every member, in any order, bit for bit (weights, Adam's moments, wsa_train_stats).
  * The group adopts existing trainers, classification and regression alike, of any stack, width (53 / 264 / 23), row count, batch size,
  * n_val and learning rate; it owns only a descriptor table.  wsa_trainer_stats / _copy_weights / _model keep working on a member, and

@@ -19,6 +19,8 @@ Measured on an MI355X, device against restatement (D32 beside it; bound 1.82e-6 
   r_batch_1      1.19e-07  (D32 1.19e-07)
 Counts equal the restatement's in every epoch of every case, the ambiguous ones included.  K6 over the trained weights: eight_layers
 5.9e-8, widest 2.4e-7, classes_33 2.4e-7 (bound 1e-5); r_wide 5.8e-7 (bound 1e-5 of the range = 6.9e-6)."""
+import hashlib
+
 import numpy as np
 import pytest
 
@@ -105,6 +107,37 @@ def same_bits(a, b):
         all(x[k] == y[k] for x, y in zip(a, b) for k in ("loss", "acc", "val_loss", "val_acc", "epochs_done"))
 
 
+# sha256 of every epoch's kernels, biases, loss, acc, val_loss, val_acc and epochs_done (digest_of), recorded once on an MI355X from the
+# library of the commit before train.hip was split by job (9cdca6b's tree, built into a directory of its own and selected with
+# WSA_LIB_DIR): a change to the trainer that is not meant to move a bit is held to these
+DIGESTS = {
+    "one_layer": "224268c9a49e80984c9db56ecc2974e35e0c268a7f72ce3ea4f67bc7f5fbcfd1",
+    "width_edges": "a2a06bcbf4814c7876a07014cb76575ae0e4a6d477eac1d7370913990d544a76",
+    "eight_layers": "54e18517903f42d98410b16851c9658126ba08ec92dd813888cb89263a70f32c",
+    "widest": "170e5aab7ab6b93978364b1696998d85b55b559086feada7337c554ecefe38b2",
+    "classes_33": "5c2fb82b2cd05395d2028839562977f4b3e363532e8f9a3c06b4b559f775d769",
+    "big_batch": "2add8bf79e3b15a22fbc8e9f1e6f42afdfa5d9070f8fe025e053df6614308245",
+    "batch_1": "1621ff5fe7b7fed57b76b5e81b7a0c15aee871a13bf697d535783b6ace798cd4",
+    "last_of_1": "605ca11418ef536c5a36101f74a42e012b7dbfe6dc322d014d97f5092d42b116",
+    "r_one_layer": "5e16915bf133dd3aa52f2b09c3844d9702848011b9a02477771d01a5a144fae7",
+    "r_width_edges": "76e591dcbcb59685cdf3958b3296db16b60da71dc9d88b40ca058131ca9ad853",
+    "r_wide": "58568d630f60a40e5054028b20fb5f5e3a57000f034a11a124f445dac2e1f7ae",
+    "r_relu_out": "9fb9ab753f8d1d4b38963fe4e56722a01f026b1b94b759ce08a0525114635696",
+    "r_big_batch": "c01bb47f823250a41b5cc23ab1726674ad5689b2715926e4648b4c4116354908",
+    "r_batch_1": "98532cd8e962dfcf9370c0c76f31c1a0f25e5db4275737bc882154f1915bfb8a",
+}
+
+
+def digest_of(run):
+    h = hashlib.sha256()
+    for e in run:
+        for a in e["kernels"] + e["biases"]:
+            h.update(np.ascontiguousarray(a).tobytes())
+        h.update(np.array([e["loss"], e["acc"], e["val_loss"], e["val_acc"]], "<f8").tobytes())
+        h.update(np.array([e["epochs_done"]], "<u4").tobytes())
+    return h.hexdigest()
+
+
 def check_count(got_fraction, rows, want, ambiguous):
     """the device's count against the restatement's: exactly (the fraction's bits too) where no row of the evaluation is ambiguous,
     else within the number of ambiguous rows"""
@@ -131,6 +164,15 @@ def test_case_matches_the_restatement(key, device_runs):
         else:
             assert g["val_loss"] == 0.0 and g["val_acc"] == 0.0
     assert d <= tc.bound(c)
+
+
+@pytest.mark.parametrize("key", list(tc.CASES))
+def test_case_keeps_its_bits(key, device_runs):
+    """the solo trainer's bits at every edge of tests/train_cases.py, pinned (the grouped runs are held to the solo runs byte for byte
+    by tests/test_gpu_train_group.py)"""
+    got = digest_of(device_runs(key)[0])
+    print(f"{key}: {got}")
+    assert got == DIGESTS[key]
 
 
 @pytest.mark.parametrize("key", RERUN_KEYS)

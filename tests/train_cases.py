@@ -1,4 +1,5 @@
-"""The shapes at which K7's kernels (csrc/train.hip, specifications TR-1 and TR-2) reach their tile, batch and width edges (test helper):
+"""The shapes at which K7's kernels (the stage bodies of csrc/train_stages.hpp, launched by csrc/train.hip and csrc/train_group.hip;
+specifications TR-1 and TR-2) reach their tile, batch and width edges (test helper):
 one table of cases, rows and orders made by integer arithmetic (no random generator, no libm: the same on every numpy build), initial
 weights from train_ref.hash_init.  tests/test_train_shapes_reference.py proves from the float64 restatements alone that every case moves
 every layer, has (nearly) no ambiguous counts and tells the wrong variants of train_ref.FAULTS apart; tests/test_gpu_train_shapes.py
