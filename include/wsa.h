@@ -971,6 +971,48 @@ typedef struct {
  * WSA_ERR_INVALID without an attached group. */
 wsa_status wsa_stream_values(wsa_stream *st, wsa_stream_value_result *out);
 
+/*
+ * ---- Packed PCM into streams, unpacked on the GPU inside the step (additions within version 5: probe for wsa_stream_set_input_format).
+ *
+ * The stream counterpart of wsa_batch_run_host_i16: a live source hands over 16-bit PCM (often interleaved stereo) or 8-bit G.711, and
+ * the host puts exactly those bytes into the stream set's pinned buffer — half or a quarter of the PCIe bytes of floats, no widening loop
+ * on the CPU.  Spec PK-1: a packed sample becomes the float the float entry points would have been given, and nothing
+ * else changes — a set fed packed input gives, step for step and byte for byte, what the same set gives when fed wsa_pcm_decode(packed)
+ * through wsa_stream_step_host / wsa_stream_step (rows, segments, cuts, formants, utterance rows, raw tracks, wsa_stream_copy_converted,
+ * every attached model's tables), eager or graph.
+ *   - WSA_PCM_I16: (float)x / 32768, exact in fp32, as wsa_batch_run_host_i16 converts.  WSA_PCM_MULAW / WSA_PCM_ALAW: the 16-bit linear
+ *     value of ITU-T G.711 (mu-law +-32124, A-law +-32256) / 32768, exact as well.
+ *   - Stream i delivers frames interleaved over channels[i] channels (1 .. 64, as for batches); channel 0 is analysed: sample j is element
+ *     j * channels[i] of the stream's row.  Counts (n_in, wsa_stream_input_capacity, wsa_stream_paced_input) stay frames of one channel.
+ *   - Bytes of a row behind the step's count for that stream, the other channels and the rows of streams not active in the step are
+ *     never read into a result.
+ * wsa_stream_set_input_format is legal before the first step and between a wsa_stream_collect and the next step; it (re)allocates the
+ * pinned packed buffer — [n_streams][wsa_stream_input_stride_bytes] bytes, a row = wsa_stream_input_stride * max channels * sample size
+ * rounded up to 16, zeroed — and drops a captured graph.  WSA_PCM_F32 returns to the float buffers (channels NULL or all 1).  While a
+ * packed format is set, wsa_stream_step_host / _host_n read the packed buffer, wsa_stream_step_packed takes device-resident packed rows
+ * (d_pcm aligned to 16 bytes, stream i's row at d_pcm + i * stream_stride_bytes, n_streams * stream_stride_bytes bytes readable; n_in
+ * NULL: samples_per_step / the paced counts), and the float device entry points are refused.  WSA_ERR_INVALID with a message naming the
+ * fault: an unknown format; a channel count outside 1 .. 64; channels above 1 with WSA_PCM_F32; wsa_stream_step_packed on an F32 set;
+ * wsa_stream_step / wsa_stream_step_n on a packed set; wsa_stream_time_steps with a float feed on a packed set and
+ * wsa_stream_time_steps_packed with a feed on an F32 set; a stream_stride_bytes that is no multiple of 16 or too small for the largest
+ * count of the step.
+ */
+#define WSA_PCM_F32   0   /* floats, mono: the entry points above as they are */
+#define WSA_PCM_I16   1   /* signed 16-bit, native byte order */
+#define WSA_PCM_MULAW 2   /* G.711 mu-law, one byte per sample */
+#define WSA_PCM_ALAW  3   /* G.711 A-law, one byte per sample */
+wsa_status wsa_stream_set_input_format(wsa_stream *st, int32_t format, const uint32_t *channels /* [n_streams], NULL = mono */);
+void      *wsa_stream_host_input_packed(wsa_stream *st);        /* NULL while the format is F32 */
+uint32_t   wsa_stream_input_stride_bytes(const wsa_stream *st); /* bytes per stream row of that buffer, a multiple of 16 (F32: of the float buffer) */
+wsa_status wsa_stream_step_packed(wsa_stream *st, const void *d_pcm, uint64_t stream_stride_bytes,
+                                  const uint32_t *n_in, const uint8_t *ctl, void *stream);   /* device-resident packed input */
+/* wsa_stream_time_steps with feed blocks of [n_streams][wsa_stream_input_stride_bytes] packed bytes */
+wsa_status wsa_stream_time_steps_packed(wsa_stream *st, uint32_t n_steps, const void *feed, uint32_t feed_steps,
+                                        void *stream, double *out_us, uint64_t *rows_total);
+/* PK-1 on the host, no device: channel 0 of n_frames interleaved frames -> out[n_frames].  WSA_ERR_INVALID (no context, no message):
+ * an unknown format, channels outside 1 .. 64, a NULL buffer with n_frames > 0. */
+wsa_status wsa_pcm_decode(int32_t format, const void *in, uint64_t n_frames, uint32_t channels, float *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,415 @@
+"""Packed PCM into streams (spec PK-1, wsa_stream_set_input_format): a stream set fed 16-bit or G.711 samples gives, step for step and
+byte for byte, what the same set gives when fed pcm_decode(packed) through the float entry points — rows, segments, cuts, converted
+samples, the attached classifier's tables — eager or graph, from the pinned buffer or from device memory, whatever the other channels and
+the bytes behind a stream's count hold."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden")
+G711 = json.load(open(os.path.join(GOLD, "g711_expected.json")))
+DTYPE = {"i16": np.int16, "mulaw": np.uint8, "alaw": np.uint8}
+SECONDS = 2.4
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+@pytest.fixture(scope="module")
+def wsa():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    import webspeechanalyzer_amd as w
+    return w
+
+
+def _encode(fmt, x):
+    """float signal -> packed mono samples: 16-bit rounding, or the G.711 code whose table value lies nearest (test-side encoder)."""
+    v = np.clip(np.rint(x.astype(np.float64) * 32767.0), -32768, 32767).astype(np.int64)
+    if fmt == "i16":
+        return v.astype(np.int16)
+    table = np.asarray(G711[fmt], np.int64)
+    order = np.argsort(table, kind="stable")
+    srt = table[order]
+    hi = np.clip(np.searchsorted(srt, v), 1, 255)
+    pick = np.where(np.abs(srt[hi] - v) < np.abs(srt[hi - 1] - v), hi, hi - 1)
+    return order[pick].astype(np.uint8)
+
+
+_SIG = {}
+
+
+def _packed_signals(fmt, rates):
+    """One signal of SECONDS per stream at its own rate, packed in `fmt`, and the floats PK-1 makes of it (computed once, never changed)."""
+    from webspeechanalyzer_amd import capi
+    from webspeechanalyzer_amd.synth import synth_clips
+    key = (fmt, tuple(rates))
+    if key not in _SIG:
+        pk = [_encode(fmt, synth_clips(1, int(SECONDS * r), fs=int(r), seed=500 + k, device="cpu")[0].numpy()) for k, r in enumerate(rates)]
+        fl = [capi.pcm_decode(fmt, p) for p in pk]
+        for a in pk + fl:
+            a.setflags(write=False)
+        _SIG[key] = (pk, fl)
+    return _SIG[key]
+
+
+def _paced(st, i, s):
+    """The count a stream takes in its s-th active step since START when n_in is None (include/wsa.h: floor((s + 1) F hop ratio) -
+    floor(s F hop ratio); a stream at the analysis rate and a plain set: samples_per_step)."""
+    sps = st.samples_per_step
+    if not st.mixed or st.fs_in[i] == st.fs:
+        return sps
+    r = st.fs_in[i] / st.fs
+    return int(np.floor(float((s + 1) * sps) * r)) - int(np.floor(float(s * sps) * r))
+
+
+def _plan_whole(wsa, st, lens, counts_of=None):
+    """Every stream from START (step 0) to STOP, active in every step between: [(ctl [n], n_in [n] or None, counts [n])].  counts_of(k, i,
+    cap) -> the count of stream i in step k; None: the set's own count — samples_per_step or the paced count — handed over as n_in = None
+    wherever every stream takes exactly that.  A mixed set's last step carries what is left; a plain set stops at its last whole step."""
+    n = st.n
+    pos, done, plan, k = [0] * n, [False] * n, [], 0
+    while not all(done):
+        ctl, n_in, own = np.zeros(n, np.uint8), np.zeros(n, np.uint32), True
+        for i in range(n):
+            if done[i]:
+                continue
+            paced = _paced(st, i, k)
+            want = paced if counts_of is None else int(counts_of(k, i, int(st.input_capacity[i])))
+            want = min(want, lens[i] - pos[i])
+            own = own and want == paced
+            ctl[i] = wsa.ACTIVE | (wsa.START if k == 0 else 0)
+            n_in[i] = want
+            pos[i] += want
+            if pos[i] >= lens[i] or (not st.mixed and pos[i] + want > lens[i]):
+                ctl[i] |= wsa.STOP
+                done[i] = True
+        plan.append((ctl, None if counts_of is None and own else n_in, n_in.copy()))
+        k += 1
+    return plan
+
+
+def _run(wsa, st, fmt, sigs, plan, where, channels=None, poison=False, model=False, formats=None):
+    """Feeds `sigs` (per stream: packed mono samples, or floats for 'f32') to the set in the plan's steps.  where: 'host' (the pinned
+    buffer) or 'dev' (a device tensor).  channels: interleaved channels per stream; the other channels and everything behind a stream's
+    count hold what the previous steps left there, or (poison) full-scale values and noise rewritten at every step.  formats: per step the
+    format to switch to before it (sigs is then {fmt: signals}).  -> per step dict(rows=collect(), conv=converted(), cls=classes())"""
+    n = st.n
+    ch = np.ones(n, np.int64) if channels is None else np.asarray(channels, np.int64)
+    cur = None
+    pos = [0] * n
+    out = []
+    rng = np.random.default_rng(77)
+    bufs = {}
+    for k, (ctl, n_in, take) in enumerate(plan):
+        f = formats[k] if formats else fmt
+        if f != cur:
+            st.set_input_format(f, None if f == "f32" else ch)
+            cur = f
+        src = sigs[f] if formats else sigs
+        if f == "f32":
+            if ("f32", where) not in bufs:
+                bufs[("f32", where)] = st.host_input() if where == "host" else np.zeros((n, st.input_stride), np.float32)
+            buf = bufs[("f32", where)]
+        else:
+            if (f, where) not in bufs:
+                bufs[(f, where)] = st.host_input_packed() if where == "host" else np.zeros((n, st.input_stride_bytes // np.dtype(DTYPE[f]).itemsize), DTYPE[f])
+            buf = bufs[(f, where)]
+            assert buf.dtype == DTYPE[f] and buf.shape[1] * buf.dtype.itemsize == st.input_stride_bytes and st.input_stride_bytes % 16 == 0
+            if poison:                                         # 0x7FFF / 0xFF, then the format's other extreme, then noise: never twice the same
+                fill = (0x7FFF if f == "i16" else 0xFF, -0x8000 if f == "i16" else (0x80 if f == "mulaw" else 0xAA))      # 0x80 / 0xAA: +32124 / +32256
+                buf[:] = fill[k % 3] if k % 3 < 2 else (rng.integers(-32768, 32768, buf.shape) if f == "i16" else rng.integers(0, 256, buf.shape)).astype(buf.dtype)
+        for i in range(n):
+            c = int(take[i])
+            if ctl[i] & wsa.ACTIVE and c:
+                x = src[i][pos[i]:pos[i] + c]
+                assert len(x) == c
+                if f == "f32":
+                    buf[i, :c] = x
+                else:
+                    buf[i, 0:(c - 1) * ch[i] + 1:ch[i]] = x
+                pos[i] += c
+        if where == "host":
+            st.step_host(ctl, _stream(), n_in=n_in)
+        else:
+            dev = torch.from_numpy(np.ascontiguousarray(buf)).cuda()
+            if f == "f32":
+                st.step(dev.data_ptr(), dev.stride(0), ctl, _stream(), n_in=n_in)
+            else:
+                st.step_packed(dev.data_ptr(), dev.stride(0) * dev.element_size(), ctl, _stream(), n_in=n_in)
+        r = st.collect(_stream())
+        out.append(dict(rows=r, conv=st.converted() if st.mixed else [], cls=st.classes() if model else {}))
+    return out
+
+
+def _bytes(a):
+    return np.ascontiguousarray(a).tobytes()
+
+
+def _assert_same(got, want, n_active, tag):
+    """Every step's collect(), converted() and classes() byte for byte; first the condition on the input: the float twin produced at least
+    one row for each of the n_active streams, so an empty comparison cannot pass."""
+    seen = set()
+    for s in want:
+        seen |= {int(m[0]) for m in s["rows"]["meta"]}
+    assert len(seen) >= n_active, f"{tag}: the float twin produced rows for streams {sorted(seen)} only"
+    assert len(got) == len(want)
+    for k, (g, w) in enumerate(zip(got, want)):
+        assert set(g["rows"]) == set(w["rows"])
+        for key, val in w["rows"].items():
+            if key == "tracks":
+                continue
+            if isinstance(val, np.ndarray):
+                assert g["rows"][key].shape == val.shape and _bytes(g["rows"][key]) == _bytes(val), f"{tag} step {k}: collect()[{key!r}] differs"
+            else:
+                assert g["rows"][key] == val, f"{tag} step {k}: collect()[{key!r}] differs"
+        assert len(g["conv"]) == len(w["conv"])
+        for i, (a, b) in enumerate(zip(g["conv"], w["conv"])):
+            assert a.shape == b.shape and _bytes(a) == _bytes(b), f"{tag} step {k} stream {i}: converted() differs"
+        assert set(g["cls"]) == set(w["cls"])
+        for key, val in w["cls"].items():
+            if isinstance(val, np.ndarray):
+                assert g["cls"][key].shape == val.shape and _bytes(g["cls"][key]) == _bytes(val), f"{tag} step {k}: classes()[{key!r}] differs"
+            else:
+                assert g["cls"][key] == val, f"{tag} step {k}: classes()[{key!r}] differs"
+
+
+# ---- decode on the device ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fmt", ["i16", "mulaw", "alaw"])
+def test_every_code_decodes_on_the_device_as_on_the_host(wsa, fmt):
+    """A mixed set whose streams all sit at fs_out copies its input: converted() is d_pcm_in as the kernel wrote it.  41 streams x 4 steps
+    x 400 samples carry all 65536 16-bit values (all 256 codes of a law, many times over)."""
+    from webspeechanalyzer_amd import capi
+    n, steps, fs = 41, 4, 16000.0
+    an = wsa.Analyzer(wsa.Config(output_level=5))
+    st = an.streams(n, [fs] * n, frames_per_step=1, resample_to=fs)
+    c = st.samples_per_step
+    assert c == 400 and n * steps * c >= 65536
+    st.set_input_format(fmt)
+    st.enable_graph(True)
+    buf = st.host_input_packed()
+    assert buf.dtype == DTYPE[fmt] and buf.shape == (n, st.input_stride_bytes // buf.dtype.itemsize)
+    allv = np.arange(n * steps * c, dtype=np.int64)
+    allv = (allv % 65536 - 32768).astype(np.int16) if fmt == "i16" else (allv % 256).astype(np.uint8)
+    allv = allv.reshape(steps, n, c)
+    seen = set()
+    for k in range(steps):
+        buf[:, :c] = allv[k]
+        st.step_host(None, _stream())
+        st.collect(_stream())
+        conv = st.converted()
+        for i in range(n):
+            want = capi.pcm_decode(fmt, allv[k, i])
+            assert conv[i].shape == (c,) and _bytes(conv[i]) == _bytes(want), (fmt, k, i)
+        seen |= set(np.unique(allv[k]).tolist())
+    assert len(seen) == (65536 if fmt == "i16" else 256)
+    st.close(); an.close()
+
+
+# ---- plain set, hop 240: the history shuffle runs behind the packed pull -------------------------------------------------------------
+PLAIN_FS, PLAIN_F = 16000.0, 4
+_TWIN = {}
+
+
+def _plain(wsa, level):
+    an = wsa.Analyzer(wsa.Config(output_level=level, window_step=15))
+    assert an.geometry(PLAIN_FS)["hop"] == 240
+    return an, an.streams(3, PLAIN_FS, frames_per_step=PLAIN_F)
+
+
+def _plain_twin(wsa, level, fmt):
+    """The float twin of the plain set fed decode(packed), from the pinned float buffer without a graph: computed once per (level, format)."""
+    if (level, fmt) not in _TWIN:
+        pk, fl = _packed_signals(fmt, [PLAIN_FS] * 3)
+        an, st = _plain(wsa, level)
+        plan = _plan_whole(wsa, st, [len(x) for x in pk])
+        _TWIN[(level, fmt)] = (plan, _run(wsa, st, "f32", fl, plan, "host"))
+        st.close(); an.close()
+    return _TWIN[(level, fmt)]
+
+
+@pytest.mark.parametrize("where", ["host", "dev"])
+@pytest.mark.parametrize("graph", [False, True])
+@pytest.mark.parametrize("fmt", ["i16", "mulaw", "alaw"])
+@pytest.mark.parametrize("level", [5, 13])
+def test_plain_set_equals_its_float_twin(wsa, level, fmt, graph, where):
+    pk, _ = _packed_signals(fmt, [PLAIN_FS] * 3)
+    plan, want = _plain_twin(wsa, level, fmt)
+    an, st = _plain(wsa, level)
+    st.enable_graph(graph)
+    got = _run(wsa, st, fmt, pk, plan, where)
+    _assert_same(got, want, 3, f"plain level {level} {fmt} graph {graph} {where}")
+    st.close(); an.close()
+
+
+# ---- mixed set 44.1 -> 48 kHz, one frame per step: the tails of the 8-wide loads, channels ------------------------------------------
+def _mixed(wsa, level, rate, model=False):
+    an = wsa.Analyzer(wsa.Config(output_level=level))
+    st = an.streams(3, [rate] * 3, frames_per_step=1, resample_to=48000.0)
+    m = None
+    if model:
+        from webspeechanalyzer_amd import nnmodel
+        m = an.load_model(nnmodel.load_dir(os.path.join(GOLD, "nn", "1/cats_emotion")))
+        st.set_model(m)
+    return an, st, m
+
+
+def _odd_counts(k, i, cap):
+    """0, 1, 7, 9 and the capacity in the first steps of every stream (shifted from stream to stream), the capacity afterwards."""
+    head = [0, 1, 7, 9, cap, 9, 7, 1, 0]
+    return head[(k + 2 * i) % len(head)] if k < 18 else cap
+
+
+@pytest.mark.parametrize("graph", [False, True])
+@pytest.mark.parametrize("feed", ["paced", "counts"])
+def test_mixed_set_i16_with_channels_equals_its_float_twin(wsa, feed, graph):
+    pk, fl = _packed_signals("i16", [44100.0] * 3)
+    an, st, _ = _mixed(wsa, 5, 44100.0)
+    plan = _plan_whole(wsa, st, [len(x) for x in pk], None if feed == "paced" else _odd_counts)
+    if feed == "paced":
+        assert {int(c) for _, _, t in plan[:-1] for c in t} == {1102, 1103} and sum(p[1] is None for p in plan) >= len(plan) - 1
+    else:
+        assert {0, 1, 7, 9, 1103} <= {int(c) for _, _, t in plan for c in t}
+    want = _run(wsa, st, "f32", fl, plan, "host")
+    st.close(); an.close()
+    an, st, _ = _mixed(wsa, 5, 44100.0)
+    st.enable_graph(graph)
+    got = _run(wsa, st, "i16", pk, plan, "host" if graph else "dev", channels=(1, 2, 3))
+    assert sum(len(c) for s in want for c in s["conv"]) > 3 * 48000 * (SECONDS - 0.1)
+    _assert_same(got, want, 3, f"mixed 44.1 kHz i16 {feed} graph {graph}")
+    st.close(); an.close()
+
+
+@pytest.mark.parametrize("fmt", ["mulaw", "alaw"])
+def test_g711_at_8_khz_with_the_classifier_equals_its_float_twin(wsa, fmt):
+    pk, fl = _packed_signals(fmt, [8000.0] * 3)
+    runs = []
+    for f, sig in (("f32", fl), (fmt, pk)):
+        an, st, m = _mixed(wsa, 13, 8000.0, model=True)
+        st.enable_graph(True)
+        plan = _plan_whole(wsa, st, [len(x) for x in pk])
+        runs.append(_run(wsa, st, f, sig, plan, "host", model=True))
+        st.close(); m.close(); an.close()
+    want, got = runs
+    assert sum(len(s["cls"]["prob"]) for s in want) > 0 and sum(len(s["cls"]["cb"]) for s in want) > 0
+    _assert_same(got, want, 3, f"8 kHz {fmt} level 13 with classifier")
+
+
+# ---- poison: the other channels and everything behind a stream's count never reach a result ------------------------------------------
+@pytest.mark.parametrize("fmt,channels", [("i16", (2, 3, 64)), ("mulaw", (3, 1, 2)), ("alaw", (1, 17, 5))])
+def test_other_channels_and_bytes_behind_the_count_are_never_read(wsa, fmt, channels):
+    rate = 44100.0 if fmt == "i16" else 8000.0
+    pk, fl = _packed_signals(fmt, [rate] * 3)
+    an, st, _ = _mixed(wsa, 5, rate)
+    plan = _plan_whole(wsa, st, [len(x) for x in pk], _odd_counts)
+    want = _run(wsa, st, "f32", fl, plan, "host")
+    st.close(); an.close()
+    for where in ("host", "dev"):
+        an, st, _ = _mixed(wsa, 5, rate)
+        st.enable_graph(True)
+        got = _run(wsa, st, fmt, pk, plan, where, channels=channels, poison=True)
+        _assert_same(got, want, 3, f"poisoned {fmt} channels {channels} {where}")
+        st.close(); an.close()
+
+
+# ---- control bytes -----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("graph", [False, True])
+def test_idle_stop_start_and_an_empty_stop_step(wsa, graph):
+    """Stream 0 runs through; stream 1 idles for ten steps in mid-run; stream 2 is stopped by a step with zero samples, stays idle for
+    three steps and starts afresh."""
+    pk, fl = _packed_signals("i16", [44100.0] * 3)
+    an, st, _ = _mixed(wsa, 5, 44100.0)
+    base = _plan_whole(wsa, st, [len(x) for x in pk], lambda k, i, cap: cap)
+    plan = []
+    for k, (ctl, n_in, take) in enumerate(base):
+        ctl, take = ctl.copy(), take.copy()
+        if 30 <= k < 40:
+            ctl[1], take[1] = 0, 0
+        if k == 45:
+            ctl[2], take[2] = wsa.ACTIVE | wsa.STOP, 0
+        if 46 <= k < 49:
+            ctl[2], take[2] = 0, 0
+        if k == 49:
+            ctl[2] |= wsa.START
+        plan.append((ctl, take.copy(), take))
+    assert len(plan) > 60 and plan[45][2][2] == 0 and plan[45][0][2] & wsa.STOP
+    want = _run(wsa, st, "f32", fl, plan, "host")
+    st.close(); an.close()
+    assert any(int(m[0]) == 2 and int(m[1]) == 0 for s in want[50:] for m in s["rows"]["meta"]), "stream 2 has no callback 0 after its restart"
+    an, st, _ = _mixed(wsa, 5, 44100.0)
+    st.enable_graph(graph)
+    got = _run(wsa, st, "i16", pk, plan, "host", channels=(2, 1, 2), poison=True)
+    _assert_same(got, want, 3, f"control bytes graph {graph}")
+    st.close(); an.close()
+
+
+# ---- format switch between steps ---------------------------------------------------------------------------------------------------------
+def test_switching_the_format_between_steps_recaptures_the_graph(wsa):
+    pk, fl = _packed_signals("i16", [PLAIN_FS] * 3)
+    plan, want = _plain_twin(wsa, 13, "i16")
+    third = len(plan) // 3
+    formats = ["f32"] * third + ["i16"] * third + ["f32"] * (len(plan) - 2 * third)
+    an, st = _plain(wsa, 13)
+    st.enable_graph(True)
+    got = _run(wsa, st, None, {"f32": fl, "i16": pk}, plan, "host", formats=formats)
+    _assert_same(got, want, 3, "f32 -> i16 -> f32 with the graph on")
+    with pytest.raises(wsa.WsaError, match="no packed input buffer"):
+        st.host_input_packed()                                  # back at F32: the packed buffer is gone
+    st.close(); an.close()
+
+
+# ---- refusals ------------------------------------------------------------------------------------------------------------------------------
+def test_refusals_name_the_fault(wsa):
+    an = wsa.Analyzer(wsa.Config(output_level=5))
+    st = an.streams(3, 16000.0, frames_per_step=2)
+    L, sps = an.L, st.samples_per_step
+    one = np.ones(3, np.uint32)
+    for bad in (4, -1, 99):
+        with pytest.raises(wsa.WsaError, match=f"libwsa error 1: unknown input format {bad} "):
+            an._check(L.wsa_stream_set_input_format(st.h, bad, None))
+    with pytest.raises(wsa.WsaError, match="unknown input format"):
+        st.set_input_format("pcm24")
+    for bad in (0, 65):
+        with pytest.raises(wsa.WsaError, match=rf"stream 1: channel count {bad} outside 1 \.\. 64"):
+            st.set_input_format("i16", [1, bad, 2])
+    with pytest.raises(wsa.WsaError, match=r"stream 2: 2 channels with WSA_PCM_F32"):
+        st.set_input_format("f32", [1, 1, 2])
+    st.set_input_format("f32", one)                            # all 1 is mono
+    dev = torch.zeros((3, 4 * sps), dtype=torch.int16, device="cuda")
+    fdev = torch.zeros((3, sps), dtype=torch.float32, device="cuda")
+    with pytest.raises(wsa.WsaError, match="wsa_stream_step_packed on a set whose input format is WSA_PCM_F32"):
+        st.step_packed(dev.data_ptr(), dev.stride(0) * 2)
+    feed16 = np.zeros((1, 3, 1), np.int16)
+    out, rows = np.zeros(1), np.zeros(1, np.uint64)
+    with pytest.raises(wsa.WsaError, match="wsa_stream_time_steps_packed with a packed feed on a set whose input format is WSA_PCM_F32"):
+        an._check(L.wsa_stream_time_steps_packed(st.h, 1, feed16.ctypes.data, 1, _stream(), out.ctypes.data, rows.ctypes.data))
+    st.set_input_format("i16", [1, 2, 1])
+    assert st.input_stride_bytes == (sps * 2 * 2 + 15) // 16 * 16 and st.host_input_packed().shape == (3, st.input_stride_bytes // 2)
+    with pytest.raises(wsa.WsaError, match="wsa_stream_step takes floats, this set's input format is i16"):
+        st.step(fdev.data_ptr(), fdev.stride(0))
+    with pytest.raises(wsa.WsaError, match="wsa_stream_step_n takes floats, this set's input format is i16"):
+        st.step(fdev.data_ptr(), fdev.stride(0), n_in=np.full(3, sps, np.uint32))
+    with pytest.raises(wsa.WsaError, match="wsa_stream_time_steps with a float feed, this set's input format is i16"):
+        st.time_steps(1, np.zeros((1, 3, st.input_stride), np.float32))
+    with pytest.raises(wsa.WsaError, match=r"stream_stride_bytes \d+ is not a multiple of 16"):
+        st.step_packed(dev.data_ptr(), dev.stride(0) * 2 + 8)
+    small = (sps * 2 * 2) // 16 * 16 - 16                      # stream 1 carries sps frames of 2 channels: one chunk too few
+    with pytest.raises(wsa.WsaError, match=rf"stream_stride_bytes {small} too small: stream 1 carries {sps} frames of 2 channels"):
+        st.step_packed(dev.data_ptr(), small)
+    # none of the refusals counted a step: the same set still takes its first step, from either side
+    st.step_packed(dev.data_ptr(), dev.stride(0) * 2)
+    st.collect(_stream())
+    st.step_host(None, _stream())
+    st.collect(_stream())
+    us, _ = st.time_steps_packed(2, np.zeros((1, 3, st.input_stride_bytes // 2), np.int16))
+    assert us.shape == (2,) and (us > 0).all()
+    us, _ = st.time_steps(1)                                   # without a feed either call steps the set as it is
+    assert us.shape == (1,)
+    st.close(); an.close()

@@ -213,11 +213,18 @@ ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destr
                "wsa_batch_copy_value_fold", "wsa_stream_set_regress", "wsa_stream_values",
                # additions within version 5 (probe for wsa_train_group_create): a group of trainers in one pass of grouped launches (K7g, spec TG-1)
                "wsa_train_group_create", "wsa_train_group_destroy", "wsa_train_group_epoch", "wsa_train_group_stats", "wsa_train_group_launches",
-               "wsa_train_group_launch_count"]
+               "wsa_train_group_launch_count",
+               # additions within version 5 (probe for wsa_stream_set_input_format): 16-bit and G.711 PCM into streams, unpacked in the step (spec PK-1)
+               "wsa_stream_set_input_format", "wsa_stream_host_input_packed", "wsa_stream_input_stride_bytes", "wsa_stream_step_packed",
+               "wsa_stream_time_steps_packed", "wsa_pcm_decode"]
+PCM_F32, PCM_I16, PCM_MULAW, PCM_ALAW = 0, 1, 2, 3      # WSA_PCM_* of include/wsa.h
+_PCM_NAMES = {"f32": PCM_F32, "i16": PCM_I16, "mulaw": PCM_MULAW, "alaw": PCM_ALAW}
+_PCM_DTYPE = {PCM_F32: np.float32, PCM_I16: np.int16, PCM_MULAW: np.uint8, PCM_ALAW: np.uint8}
 TRAIN_GROUP_MAX = 32       # WSA_TRAIN_GROUP_MAX of include/wsa.h
 
 _LIB = None
-_U32_RESULT = ("wsa_stream_input_capacity", "wsa_stream_paced_input", "wsa_stream_input_stride", "wsa_stream_step_frame_capacity", "wsa_stream_frames_bound")
+_U32_RESULT = ("wsa_stream_input_capacity", "wsa_stream_paced_input", "wsa_stream_input_stride", "wsa_stream_step_frame_capacity", "wsa_stream_frames_bound",
+               "wsa_stream_input_stride_bytes")
 
 
 def library_path():
@@ -380,16 +387,53 @@ def lib():
     L.wsa_train_group_stats.argtypes = [vp, vp, vp]
     L.wsa_train_group_launches.argtypes = [vp, ctypes.POINTER(u32)]
     L.wsa_train_group_launch_count.argtypes = [vp, vp, vp, vp, u32, ctypes.POINTER(ctypes.c_uint64)]
+    L.wsa_stream_set_input_format.argtypes = [vp, i32, vp]
+    L.wsa_stream_host_input_packed.argtypes = [vp]
+    L.wsa_stream_host_input_packed.restype = vp
+    L.wsa_stream_input_stride_bytes.argtypes = [vp]
+    L.wsa_stream_input_stride_bytes.restype = u32
+    L.wsa_stream_step_packed.argtypes = [vp, vp, u64, vp, vp, vp]
+    L.wsa_stream_time_steps_packed.argtypes = [vp, u32, vp, u32, vp, vp, vp]
+    L.wsa_pcm_decode.argtypes = [i32, vp, u64, u32, vp]
     for name in ABI_SYMBOLS:
         if name in _U32_RESULT or name in ("wsa_resample_ready", "wsa_level_feature_count"):
             continue
         if name not in ("wsa_abi_version", "wsa_last_error", "wsa_config_default", "wsa_destroy", "wsa_batch_destroy", "wsa_resample_length",
-                        "wsa_stream_destroy", "wsa_stream_samples_per_step", "wsa_stream_host_input", "wsa_gather_destroy", "wsa_host_free",
+                        "wsa_stream_destroy", "wsa_stream_samples_per_step", "wsa_stream_host_input", "wsa_stream_host_input_packed", "wsa_gather_destroy", "wsa_host_free",
                         "wsa_model_destroy", "wsa_ensemble_destroy", "wsa_trainer_destroy", "wsa_dbstats_destroy", "wsa_knn_destroy",
                         "wsa_regress_group_destroy", "wsa_train_group_destroy"):
             getattr(L, name).restype = ctypes.c_int
     _LIB = L
     return L
+
+
+def pcm_format(fmt):
+    """A WSA_PCM_* number from a number or one of 'f32', 'i16', 'mulaw', 'alaw'; anything else is refused."""
+    if isinstance(fmt, str):
+        if fmt not in _PCM_NAMES:
+            raise WsaError(f"unknown input format {fmt!r} ('f32', 'i16', 'mulaw', 'alaw')")
+        return _PCM_NAMES[fmt]
+    if isinstance(fmt, (bool, float)) or int(fmt) not in _PCM_DTYPE:
+        raise WsaError(f"unknown input format {fmt!r} (PCM_F32 0, PCM_I16 1, PCM_MULAW 2, PCM_ALAW 3)")
+    return int(fmt)
+
+
+def pcm_decode(fmt, array, channels=1):
+    """Spec PK-1 on the host (wsa_pcm_decode, no device): channel 0 of the interleaved frames in `array` (int16 for 'i16', uint8 for the
+    G.711 laws, float32 for 'f32'; a trailing partial frame is ignored) as float32 — the floats a stream set fed `array` analyses."""
+    f = pcm_format(fmt)
+    ch = int(channels)
+    if not 1 <= ch <= 64:
+        raise WsaError(f"channel count {ch} outside 1 .. 64")
+    a = np.ascontiguousarray(array)
+    if a.dtype != _PCM_DTYPE[f]:
+        raise WsaError(f"format {fmt!r} takes {np.dtype(_PCM_DTYPE[f]).name} samples, not {a.dtype.name}")
+    a = a.reshape(-1)
+    n = (a.size - 1) // ch + 1 if a.size else 0      # frames whose channel 0 is present
+    out = np.zeros(n, np.float32)
+    if lib().wsa_pcm_decode(f, a.ctypes.data, n, ch, out.ctypes.data) != 0:
+        raise WsaError("wsa_pcm_decode refused its arguments")
+    return out
 
 
 def level_feature_count(output_level):
@@ -1338,6 +1382,8 @@ class Streams:
         self.input_stride = int(self.L.wsa_stream_input_stride(self.h))
         self.input_capacity = np.array([self.L.wsa_stream_input_capacity(self.h, i) for i in range(self.n)], np.uint32)
         self.frame_capacity = int(self.L.wsa_stream_step_frame_capacity(self.h))
+        self.input_format, self.channels = PCM_F32, np.ones(self.n, np.uint32)
+        self.input_stride_bytes = int(self.L.wsa_stream_input_stride_bytes(self.h))
 
     def paced_input(self):
         """What n_in=None takes from every stream in the next step (a step without START): [n] uint32."""
@@ -1388,6 +1434,55 @@ class Streams:
         else:
             cnt = np.ascontiguousarray(n_in, dtype=np.uint32)
             self.an._check(self.L.wsa_stream_step_host_n(self.h, cnt.ctypes.data, ptr, stream))
+
+    def set_input_format(self, fmt, channels=None):
+        """The format of the samples the set is fed from now on (spec PK-1, wsa_stream_set_input_format): 'f32' (the default), 'i16', 'mulaw'
+        or 'alaw' (or a PCM_* number); channels = interleaved channels per stream, one number or one per stream (1 .. 64, channel 0 is
+        analysed).  Legal before the first step and between a collect() and the next step; the next step recaptures the graph."""
+        f = pcm_format(fmt)
+        ch = None
+        if channels is not None:
+            ch = np.ascontiguousarray(np.broadcast_to(np.asarray(channels, np.int64), (self.n,)) if np.ndim(channels) == 0 else channels, dtype=np.int64)
+            if ch.shape != (self.n,):
+                raise WsaError("channels as a sequence holds one count per stream")
+            if ch.min() < 0 or ch.max() > 0xFFFFFFFF:
+                raise WsaError(f"channel count {int(ch.min() if ch.min() < 0 else ch.max())} outside 1 .. 64")
+            ch = ch.astype(np.uint32)
+        self.an._check(self.L.wsa_stream_set_input_format(self.h, f, ch.ctypes.data if ch is not None else None))
+        self.input_format = f
+        self.channels = ch if ch is not None else np.ones(self.n, np.uint32)
+        self.input_stride_bytes = int(self.L.wsa_stream_input_stride_bytes(self.h))
+
+    def host_input_packed(self):
+        """The pinned packed input buffer of step_host while a packed format is set: a numpy view, int16 ('i16') or uint8 (G.711), shape
+        [n, input_stride_bytes / itemsize]; stream i's interleaved frames of the step at the start of row i."""
+        p = self.L.wsa_stream_host_input_packed(self.h)
+        if not p:
+            raise WsaError("no packed input buffer: the input format is 'f32' (set_input_format)")
+        dt = np.dtype(_PCM_DTYPE[self.input_format])
+        stride = int(self.L.wsa_stream_input_stride_bytes(self.h))
+        ctype = ctypes.c_int16 if dt == np.int16 else ctypes.c_uint8
+        return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctype)), shape=(self.n, stride // dt.itemsize))
+
+    def step_packed(self, d_ptr, stride_bytes, ctl=None, stream=0, n_in=None):
+        """One step on device-resident packed input (wsa_stream_step_packed): stream i's interleaved frames at d_ptr + i * stride_bytes
+        (16-byte aligned, stride_bytes a multiple of 16); n_in as for step()."""
+        keep, ptr = self._ctl(ctl)
+        cnt = None if n_in is None else np.ascontiguousarray(n_in, dtype=np.uint32)
+        self.an._check(self.L.wsa_stream_step_packed(self.h, d_ptr, int(stride_bytes), cnt.ctypes.data if cnt is not None else None, ptr, stream))
+
+    def time_steps_packed(self, n_steps, feed=None, stream=0):
+        """time_steps() on a packed set: feed = [k, n, input_stride_bytes / itemsize] blocks of the format's dtype, or None."""
+        out = np.zeros(n_steps)
+        rows = ctypes.c_uint64(0)
+        fptr, fk = None, 0
+        if feed is not None:
+            feed = np.ascontiguousarray(feed)
+            stride = int(self.L.wsa_stream_input_stride_bytes(self.h))
+            assert feed.ndim == 3 and feed.shape[1] == self.n and feed.shape[2] * feed.dtype.itemsize == stride, "feed blocks are [k, n, input_stride_bytes / itemsize]"
+            fptr, fk = feed.ctypes.data, feed.shape[0]
+        self.an._check(self.L.wsa_stream_time_steps_packed(self.h, int(n_steps), fptr, int(fk), stream, out.ctypes.data, ctypes.byref(rows)))
+        return out, rows.value
 
     def time_steps(self, n_steps, feed=None, stream=0):
         """n_steps steps timed inside the library (step_host + collect, microseconds each); feed = [k, n, input_stride] float32

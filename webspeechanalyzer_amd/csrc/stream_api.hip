@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 #include "host_plan.hpp"
+#include "pcm_formats.hpp"
 
 using namespace wsa;
 using wsa_api::fail;
@@ -74,6 +75,12 @@ struct wsa_stream {
     std::vector<uint32_t> in_cap, last_nfr, last_out;      // per stream: samples one step accepts, frames / outputs of its last active step
     std::vector<uint64_t> cN, cY, cK, cS;                  // per stream since START: inputs received, outputs handed on, frames analysed, active steps
     float *d_conv = nullptr, *d_hist = nullptr, *d_rs_tables = nullptr; RsClass* d_rs_cls = nullptr; uint32_t* d_rs_class = nullptr;
+    // packed input (spec PK-1, wsa_stream_set_input_format): own allocations, replaced whenever the format is set
+    int32_t fmt = WSA_PCM_F32, g_fmt = WSA_PCM_F32;
+    std::vector<uint32_t> chan;             // channels per stream (empty: mono)
+    uint8_t *h_pk = nullptr, *h_pk_dev = nullptr;      // [n][pk_stride] bytes, mapped pinned
+    uint32_t pk_stride = 0, max_ch = 1;
+    uint32_t* d_chan = nullptr;
 };
 
 namespace wsa {
@@ -96,6 +103,56 @@ __global__ __launch_bounds__(256) void stream_pull_kernel(float* dst, const floa
     const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i + 3 < n) *reinterpret_cast<float4*>(dst + i) = *reinterpret_cast<const float4*>(src + i);
     else for (size_t k = i; k < n; k++) dst[k] = src[k];
+}
+// packed host or device input -> floats in d_pcm_in (spec PK-1), a kernel node like the float pull.  One block row per stream; a lane takes
+// whole 16-byte chunks of the stream's row (8 i16 samples or 16 G.711 codes), decodes channel 0's samples in registers and stores floats.
+// Rows of streams that are not active in the step are skipped, and so is everything behind the step's count of a stream.
+// ctl: the device control words the step's prologue has just written (word w of stream s at ctl[w * n + s]); count_word = 0: every
+// active stream carries fixed_count samples (a plain set), else the word that holds the stream's count (RS_CTL_NIN of a mixed set).
+// The caller guarantees count * channels * sample size <= src_stride, src and src_stride multiples of 16, count <= dst_stride.
+template <int FORMAT>
+__global__ __launch_bounds__(128) void stream_pull_packed_kernel(float* __restrict__ dst, uint32_t dst_stride, const uint8_t* __restrict__ src, uint64_t src_stride,
+                                                                 const uint32_t* __restrict__ chan, const uint32_t* __restrict__ ctl, uint32_t n,
+                                                                 uint32_t count_word, uint32_t fixed_count) {
+    constexpr uint32_t E = FORMAT == WSA_PCM_I16 ? 8u : 16u;      // samples in a 16-byte chunk
+    constexpr uint32_t PER = E / 4u;                               // samples per 32-bit word
+    constexpr uint32_t BITS = 32u / PER, MASK = BITS == 16u ? 0xFFFFu : 0xFFu;
+    const uint32_t s = blockIdx.x;
+    if (!(ctl[RS_CTL_BITS * n + s] & 4u)) return;
+    const uint32_t cnt = count_word ? ctl[count_word * n + s] : fixed_count;
+    if (cnt == 0) return;
+    const uint32_t ch = chan[s];
+    const uint4* row = reinterpret_cast<const uint4*>(src + (uint64_t)s * src_stride);
+    float* out = dst + (uint64_t)s * dst_stride;
+    const uint32_t n_el = (cnt - 1u) * ch + 1u;                   // elements of the row up to channel 0 of the last frame (cnt <= 2^24, ch <= 64)
+    const uint32_t n_chunks = (n_el + E - 1u) / E;
+    const bool vec = (dst_stride & 3u) == 0;                       // rows of d_pcm_in start on 16 bytes
+    for (uint32_t c = blockIdx.y * 128u + threadIdx.x; c < n_chunks; c += gridDim.y * 128u) {
+        const uint32_t e0 = c * E;
+        if (ch == 1u) {
+            const uint4 v = row[c];
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+            float f[E];
+#pragma unroll
+            for (uint32_t k = 0; k < E; k++) f[k] = pcm_decode_one<FORMAT>((w[k / PER] >> (BITS * (k % PER))) & MASK);
+            if (vec && e0 + E <= cnt) {
+#pragma unroll
+                for (uint32_t k = 0; k < E; k += 4) *reinterpret_cast<float4*>(out + e0 + k) = make_float4(f[k], f[k + 1], f[k + 2], f[k + 3]);
+            } else {
+#pragma unroll
+                for (uint32_t k = 0; k < E; k++) if (e0 + k < cnt) out[e0 + k] = f[k];
+            }
+        } else {
+            uint32_t j = (e0 + ch - 1u) / ch;                      // first frame whose channel 0 lies in this chunk or behind it
+            uint32_t next = j * ch - e0;
+            if (next >= E || j >= cnt) continue;                   // no sample of channel 0 in this chunk: not loaded
+            const uint4 v = row[c];
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (uint32_t k = 0; k < E; k++)
+                if (k == next && j < cnt) { out[j] = pcm_decode_one<FORMAT>((w[k / PER] >> (BITS * (k % PER))) & MASK); j++; next += ch; }
+        }
+    }
 }
 // step prologue: control words host -> device (mapped pinned memory), counters cleared
 // (level 3: the per (stream, k of this step) table of the segments' track pools starts every step empty, so that an entry the step did not write reads as
@@ -132,6 +189,8 @@ void wsa_stream_destroy(wsa_stream* b) {
     if (b->own) (void)hipStreamDestroy(b->own);
     if (b->ev_in) (void)hipEventDestroy(b->ev_in);
     if (b->d_collect) (void)hipFree(b->d_collect);
+    if (b->h_pk) (void)hipHostFree(b->h_pk);
+    if (b->d_chan) (void)hipFree(b->d_chan);
     wsa_scls_free(b->scls);
     wsa_sens_free(b->sens);
     wsa_sknn_free(b->sknn);
@@ -259,6 +318,46 @@ uint32_t wsa_stream_paced_input(const wsa_stream* b, uint32_t i) { return !b || 
 uint64_t wsa_resample_ready(uint64_t n_in, double fs_in, double fs_out) { return fs_in > 0 && fs_out > 0 ? resample_ready(n_in, fs_in, fs_out) : 0; }
 uint32_t wsa_stream_frames_bound(uint32_t frames_per_step, uint32_t hop, double min_ratio) { return resample_step_frames_bound(frames_per_step, hop, min_ratio); }
 float* wsa_stream_host_input(wsa_stream* b) { return b ? b->h_pcm : nullptr; }
+void* wsa_stream_host_input_packed(wsa_stream* b) { return b && b->fmt != WSA_PCM_F32 ? b->h_pk : nullptr; }
+uint32_t wsa_stream_input_stride_bytes(const wsa_stream* b) { return !b ? 0 : (b->fmt != WSA_PCM_F32 ? b->pk_stride : b->in_stride * (uint32_t)sizeof(float)); }
+
+wsa_status wsa_stream_set_input_format(wsa_stream* b, int32_t format, const uint32_t* channels) {
+    if (!b) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = b->ctx;
+    if (format != WSA_PCM_F32 && format != WSA_PCM_I16 && format != WSA_PCM_MULAW && format != WSA_PCM_ALAW)
+        return fail(ctx, WSA_ERR_INVALID, "unknown input format " + std::to_string(format) + " (WSA_PCM_F32 0, WSA_PCM_I16 1, WSA_PCM_MULAW 2, WSA_PCM_ALAW 3)");
+    uint32_t max_ch = 1;
+    for (uint32_t i = 0; channels && i < b->n; i++) {
+        if (channels[i] < 1 || channels[i] > 64) return fail(ctx, WSA_ERR_INVALID, "stream " + std::to_string(i) + ": channel count " + std::to_string(channels[i]) + " outside 1 .. 64");
+        if (format == WSA_PCM_F32 && channels[i] != 1)
+            return fail(ctx, WSA_ERR_INVALID, "stream " + std::to_string(i) + ": " + std::to_string(channels[i]) + " channels with WSA_PCM_F32: float input is mono, interleaved channels need a packed format");
+        if (channels[i] > max_ch) max_ch = channels[i];
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (b->stepped) HIP_TRY(ctx, hipStreamSynchronize(b->last_stream ? b->last_stream : b->own));     // the last step may still read the buffer
+    if (b->gexec) { (void)hipGraphExecDestroy(b->gexec); b->gexec = nullptr; }         // the next step recaptures with the format's pull kernel
+    if (b->h_pk) { (void)hipHostFree(b->h_pk); b->h_pk = b->h_pk_dev = nullptr; }
+    if (b->d_chan) { (void)hipFree(b->d_chan); b->d_chan = nullptr; }
+    b->fmt = WSA_PCM_F32; b->chan.clear(); b->pk_stride = 0; b->max_ch = 1;
+    if (format == WSA_PCM_F32) return WSA_OK;
+    std::vector<uint32_t> ch(b->n, 1u);
+    if (channels) ch.assign(channels, channels + b->n);
+    const uint64_t row = ((uint64_t)b->in_stride * max_ch * pcm_sample_bytes(format) + 15u) & ~(uint64_t)15u;
+    if (row > 0xFFFFFFF0ull) return fail(ctx, WSA_ERR_INVALID, "a packed input row of " + std::to_string(row) + " bytes: fewer channels or frames per step");
+    void *hp = nullptr, *hd = nullptr, *dc = nullptr;
+    bool ok = hipHostMalloc(&hp, (size_t)row * b->n, hipHostMallocMapped) == hipSuccess;
+    if (ok) { std::memset(hp, 0, (size_t)row * b->n); ok = hipHostGetDevicePointer(&hd, hp, 0) == hipSuccess; }
+    ok = ok && hipMalloc(&dc, (size_t)b->n * sizeof(uint32_t)) == hipSuccess && hipMemcpy(dc, ch.data(), (size_t)b->n * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+        const std::string m = std::string("packed input buffer allocation failed: ") + hipGetErrorString(hipGetLastError());
+        if (hp) (void)hipHostFree(hp);
+        if (dc) (void)hipFree(dc);
+        return fail(ctx, WSA_ERR_HIP, m);
+    }
+    b->h_pk = static_cast<uint8_t*>(hp); b->h_pk_dev = static_cast<uint8_t*>(hd); b->d_chan = static_cast<uint32_t*>(dc);
+    b->fmt = format; b->chan = ch; b->pk_stride = (uint32_t)row; b->max_ch = max_ch;
+    return WSA_OK;
+}
 
 wsa_status wsa_stream_enable_graph(wsa_stream* b, int32_t on) {
     if (!b) return WSA_ERR_INVALID;
@@ -278,7 +377,21 @@ static wsa_status enqueue_step(wsa_stream* b, const float* d_pcm, uint64_t strid
     const uint32_t cw = b->ctl_words * n;
     hipLaunchKernelGGL(stream_begin_kernel, dim3((cw + 255) / 256), dim3(256), 0, s, b->d_ctl, b->h_ctl_dev, cw, B.d_counters, B.d_totals,
                        B.d_trk_seg, B.d_trk_seg ? (uint32_t)((size_t)n * B.seg_cap * 4) : 0u);
-    if (host_in) {
+    if (b->fmt != WSA_PCM_F32) {           // packed input (PK-1): d_pcm / stride are the packed device buffer and its row stride in bytes, or the mapped pinned one
+        const uint8_t* src = host_in ? b->h_pk_dev : reinterpret_cast<const uint8_t*>(d_pcm);
+        const uint64_t src_stride = host_in ? b->pk_stride : stride;
+        const uint32_t per_chunk = b->fmt == WSA_PCM_I16 ? 8u : 16u;
+        const uint64_t chunks = ((uint64_t)b->in_stride * b->max_ch + per_chunk - 1) / per_chunk;
+        const dim3 grid(n, (unsigned)std::min<uint64_t>((chunks + 127) / 128, 1024));
+        const uint32_t count_word = b->mixed ? (uint32_t)RS_CTL_NIN : 0u;
+        if (b->fmt == WSA_PCM_I16)
+            hipLaunchKernelGGL(stream_pull_packed_kernel<WSA_PCM_I16>, grid, dim3(128), 0, s, b->d_pcm_in, b->in_stride, src, src_stride, b->d_chan, b->d_ctl, n, count_word, b->step_samples);
+        else if (b->fmt == WSA_PCM_MULAW)
+            hipLaunchKernelGGL(stream_pull_packed_kernel<WSA_PCM_MULAW>, grid, dim3(128), 0, s, b->d_pcm_in, b->in_stride, src, src_stride, b->d_chan, b->d_ctl, n, count_word, b->step_samples);
+        else
+            hipLaunchKernelGGL(stream_pull_packed_kernel<WSA_PCM_ALAW>, grid, dim3(128), 0, s, b->d_pcm_in, b->in_stride, src, src_stride, b->d_chan, b->d_ctl, n, count_word, b->step_samples);
+        d_pcm = b->d_pcm_in; stride = b->in_stride;
+    } else if (host_in) {
         const size_t cnt = (size_t)n * b->in_stride;
         hipLaunchKernelGGL(stream_pull_kernel, dim3((unsigned)((cnt / 4 + 256) / 256)), dim3(256), 0, s, b->d_pcm_in, b->h_pcm_dev, cnt);
         d_pcm = b->d_pcm_in; stride = b->in_stride;
@@ -364,7 +477,12 @@ static wsa_status step_impl(wsa_stream* b, const float* d_pcm, uint64_t stride, 
         HIP_TRY(ctx, hipStreamWaitEvent(s, b->ev_in, 0));
     }
     if (!host_in && !d_pcm) return fail(ctx, WSA_ERR_INVALID, "null PCM pointer");
-    if (!b->mixed && !host_in && stride < b->step_samples && b->n > 1) return fail(ctx, WSA_ERR_INVALID, "stream_stride smaller than samples_per_step");
+    const bool packed = b->fmt != WSA_PCM_F32;
+    if (packed && !host_in) {              // device-resident packed input: rows are read in whole 16-byte chunks
+        if (stride % 16 != 0) return fail(ctx, WSA_ERR_INVALID, "stream_stride_bytes " + std::to_string(stride) + " is not a multiple of 16");
+        if (reinterpret_cast<uintptr_t>(d_pcm) % 16 != 0) return fail(ctx, WSA_ERR_INVALID, "the packed input pointer is not aligned to 16 bytes");
+    }
+    if (!packed && !b->mixed && !host_in && stride < b->step_samples && b->n > 1) return fail(ctx, WSA_ERR_INVALID, "stream_stride smaller than samples_per_step");
     const auto ctl_of = [&](uint32_t i) -> uint32_t { return ctl ? ctl[i] : (b->steps == 0 ? (WSA_STREAM_ACTIVE | WSA_STREAM_START) : WSA_STREAM_ACTIVE); };
     for (uint32_t i = 0; n_in && i < b->n; i++) {           // counts are checked before anything is counted
         if (!(ctl_of(i) & WSA_STREAM_ACTIVE)) continue;
@@ -372,9 +490,17 @@ static wsa_status step_impl(wsa_stream* b, const float* d_pcm, uint64_t stride, 
             return fail(ctx, WSA_ERR_INVALID, "stream " + std::to_string(i) + ": a plain stream set takes exactly " + std::to_string(b->step_samples) + " samples per step, not " + std::to_string(n_in[i]));
         if (b->mixed && n_in[i] > b->in_cap[i])
             return fail(ctx, WSA_ERR_INVALID, "stream " + std::to_string(i) + ": " + std::to_string(n_in[i]) + " samples in one step, its capacity is " + std::to_string(b->in_cap[i]));
-        if (b->mixed && !host_in && b->n > 1 && stride < n_in[i]) return fail(ctx, WSA_ERR_INVALID, "stream_stride smaller than the samples of stream " + std::to_string(i));
+        if (!packed && b->mixed && !host_in && b->n > 1 && stride < n_in[i]) return fail(ctx, WSA_ERR_INVALID, "stream_stride smaller than the samples of stream " + std::to_string(i));
     }
-    for (uint32_t i = 0; b->mixed && !n_in && !host_in && b->n > 1 && i < b->n; i++)      // paced: no count exceeds the capacity
+    for (uint32_t i = 0; packed && !host_in && i < b->n; i++) {        // the largest row any active stream can have in this step fits the stride
+        if (!(ctl_of(i) & WSA_STREAM_ACTIVE)) continue;
+        const uint64_t cnt = n_in ? n_in[i] : (b->mixed ? b->in_cap[i] : b->step_samples);
+        const uint64_t need = cnt * b->chan[i] * pcm_sample_bytes(b->fmt);
+        if (need > stride)
+            return fail(ctx, WSA_ERR_INVALID, "stream_stride_bytes " + std::to_string(stride) + " too small: stream " + std::to_string(i) + " carries " + std::to_string(cnt) + " frames of "
+                        + std::to_string(b->chan[i]) + " channels, " + std::to_string(need) + " bytes");
+    }
+    for (uint32_t i = 0; !packed && b->mixed && !n_in && !host_in && b->n > 1 && i < b->n; i++)      // paced: no count exceeds the capacity
         if (stride < b->in_cap[i]) return fail(ctx, WSA_ERR_INVALID, "stream_stride smaller than the input capacity of stream " + std::to_string(i));
     // the pinned control words are read by the step's first H2D copy: the previous step must be done
     if (b->stepped) HIP_TRY(ctx, hipStreamSynchronize(b->last_stream ? b->last_stream : s));      // ... on whichever stream it ran
@@ -424,7 +550,7 @@ static wsa_status step_impl(wsa_stream* b, const float* d_pcm, uint64_t stride, 
         b->h_ctl[i] = nfr; b->h_ctl[n + i] = off; b->h_ctl[2 * n + i] = bits;
     }
     if (b->graph_on && b->steps >= 1) {
-        if (b->gexec && (b->g_pcm != d_pcm || b->g_stride != stride || b->g_stream != s || b->g_host != host_in)) { (void)hipGraphExecDestroy(b->gexec); b->gexec = nullptr; }
+        if (b->gexec && (b->g_pcm != d_pcm || b->g_stride != stride || b->g_stream != s || b->g_host != host_in || b->g_fmt != b->fmt)) { (void)hipGraphExecDestroy(b->gexec); b->gexec = nullptr; }
         if (!b->gexec) {
             hipGraph_t graph = nullptr;
             HIP_TRY(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
@@ -435,7 +561,7 @@ static wsa_status step_impl(wsa_stream* b, const float* d_pcm, uint64_t stride, 
             const hipError_t e2 = hipGraphInstantiate(&b->gexec, graph, nullptr, nullptr, 0);
             (void)hipGraphDestroy(graph);
             if (e2 != hipSuccess) { b->gexec = nullptr; return fail(ctx, WSA_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e2)); }
-            b->g_pcm = d_pcm; b->g_stride = stride; b->g_stream = s; b->g_host = host_in;
+            b->g_pcm = d_pcm; b->g_stride = stride; b->g_stream = s; b->g_host = host_in; b->g_fmt = b->fmt;
         }
         HIP_TRY(ctx, hipGraphLaunch(b->gexec, s));
     } else {
@@ -446,8 +572,13 @@ static wsa_status step_impl(wsa_stream* b, const float* d_pcm, uint64_t stride, 
     return WSA_OK;
 }
 
+static wsa_status refuse_float_entry(wsa_stream* b, const char* name) {
+    return fail(b->ctx, WSA_ERR_INVALID, std::string(name) + " takes floats, this set's input format is " + pcm_format_name(b->fmt)
+                + ": use wsa_stream_step_packed, or wsa_stream_set_input_format(WSA_PCM_F32)");
+}
 wsa_status wsa_stream_step(wsa_stream* b, const float* d_pcm, uint64_t stream_stride, const uint8_t* ctl, void* stream) {
     if (!b) return WSA_ERR_INVALID;
+    if (b->fmt != WSA_PCM_F32) return refuse_float_entry(b, "wsa_stream_step");
     return step_impl(b, d_pcm, stream_stride, false, nullptr, ctl, reinterpret_cast<hipStream_t>(stream));
 }
 wsa_status wsa_stream_step_host(wsa_stream* b, const uint8_t* ctl, void* stream) {
@@ -456,7 +587,13 @@ wsa_status wsa_stream_step_host(wsa_stream* b, const uint8_t* ctl, void* stream)
 }
 wsa_status wsa_stream_step_n(wsa_stream* b, const float* d_pcm, uint64_t stream_stride, const uint32_t* n_in, const uint8_t* ctl, void* stream) {
     if (!b) return WSA_ERR_INVALID;
+    if (b->fmt != WSA_PCM_F32) return refuse_float_entry(b, "wsa_stream_step_n");
     return step_impl(b, d_pcm, stream_stride, false, n_in, ctl, reinterpret_cast<hipStream_t>(stream));
+}
+wsa_status wsa_stream_step_packed(wsa_stream* b, const void* d_pcm, uint64_t stream_stride_bytes, const uint32_t* n_in, const uint8_t* ctl, void* stream) {
+    if (!b) return WSA_ERR_INVALID;
+    if (b->fmt == WSA_PCM_F32) return fail(b->ctx, WSA_ERR_INVALID, "wsa_stream_step_packed on a set whose input format is WSA_PCM_F32: set a packed format with wsa_stream_set_input_format first");
+    return step_impl(b, static_cast<const float*>(d_pcm), stream_stride_bytes, false, n_in, ctl, reinterpret_cast<hipStream_t>(stream));
 }
 wsa_status wsa_stream_step_host_n(wsa_stream* b, const uint32_t* n_in, const uint8_t* ctl, void* stream) {
     if (!b) return WSA_ERR_INVALID;
@@ -705,12 +842,11 @@ wsa_status wsa_stream_classes(wsa_stream* b, wsa_stream_class_result* out) {
 // Timed steps for the latency figure of BASELINE config 5: step k copies feed[k mod feed_steps] (n_streams x samples_per_step floats,
 // the audio "arriving") into the pinned input buffer — outside the timed region — then times wsa_stream_step_host +
 // wsa_stream_collect with the host's monotonic clock and notes the microseconds (no interpreter between the two calls).
-wsa_status wsa_stream_time_steps(wsa_stream* b, uint32_t n_steps, const float* feed, uint32_t feed_steps, void* stream, double* out_us, uint64_t* rows_total) {
-    if (!b || !out_us || (feed && feed_steps == 0)) return WSA_ERR_INVALID;
-    const size_t words = (size_t)b->n * b->in_stride;
+// `feed` blocks of block_bytes each go into `dst`, the pinned input buffer of the set's format
+static wsa_status time_steps_impl(wsa_stream* b, uint32_t n_steps, const void* feed, size_t block_bytes, void* dst, uint32_t feed_steps, void* stream, double* out_us, uint64_t* rows_total) {
     uint64_t rows = 0;
     for (uint32_t k = 0; k < n_steps; k++) {
-        if (feed) std::memcpy(b->h_pcm, feed + (size_t)(k % feed_steps) * words, words * sizeof(float));
+        if (feed) std::memcpy(dst, static_cast<const uint8_t*>(feed) + (size_t)(k % feed_steps) * block_bytes, block_bytes);
         const auto t0 = std::chrono::steady_clock::now();
         wsa_status st = wsa_stream_step_host(b, nullptr, stream);
         wsa_stream_rows r;
@@ -721,6 +857,31 @@ wsa_status wsa_stream_time_steps(wsa_stream* b, uint32_t n_steps, const float* f
         rows += r.n_rows;
     }
     if (rows_total) *rows_total = rows;
+    return WSA_OK;
+}
+wsa_status wsa_stream_time_steps(wsa_stream* b, uint32_t n_steps, const float* feed, uint32_t feed_steps, void* stream, double* out_us, uint64_t* rows_total) {
+    if (!b || !out_us || (feed && feed_steps == 0)) return WSA_ERR_INVALID;
+    if (feed && b->fmt != WSA_PCM_F32)
+        return fail(b->ctx, WSA_ERR_INVALID, std::string("wsa_stream_time_steps with a float feed, this set's input format is ") + pcm_format_name(b->fmt) + ": use wsa_stream_time_steps_packed");
+    return time_steps_impl(b, n_steps, feed, (size_t)b->n * b->in_stride * sizeof(float), b->h_pcm, feed_steps, stream, out_us, rows_total);
+}
+// the same with feed blocks of [n_streams][wsa_stream_input_stride_bytes] bytes in the set's packed format
+wsa_status wsa_stream_time_steps_packed(wsa_stream* b, uint32_t n_steps, const void* feed, uint32_t feed_steps, void* stream, double* out_us, uint64_t* rows_total) {
+    if (!b || !out_us || (feed && feed_steps == 0)) return WSA_ERR_INVALID;
+    if (feed && b->fmt == WSA_PCM_F32)
+        return fail(b->ctx, WSA_ERR_INVALID, "wsa_stream_time_steps_packed with a packed feed on a set whose input format is WSA_PCM_F32: use wsa_stream_time_steps");
+    return time_steps_impl(b, n_steps, feed, (size_t)b->n * b->pk_stride, b->h_pk, feed_steps, stream, out_us, rows_total);
+}
+
+// spec PK-1 on the host, no device involved: channel 0 of n_frames interleaved frames -> floats
+wsa_status wsa_pcm_decode(int32_t format, const void* in, uint64_t n_frames, uint32_t channels, float* out) {
+    if (channels < 1 || channels > 64 || (n_frames && (!in || !out))) return WSA_ERR_INVALID;
+    const uint64_t ch = channels;
+    if (format == WSA_PCM_F32) { const float* p = static_cast<const float*>(in); for (uint64_t j = 0; j < n_frames; j++) out[j] = p[j * ch]; }
+    else if (format == WSA_PCM_I16) { const uint16_t* p = static_cast<const uint16_t*>(in); for (uint64_t j = 0; j < n_frames; j++) out[j] = pcm_decode_one<WSA_PCM_I16>(p[j * ch]); }
+    else if (format == WSA_PCM_MULAW) { const uint8_t* p = static_cast<const uint8_t*>(in); for (uint64_t j = 0; j < n_frames; j++) out[j] = pcm_decode_one<WSA_PCM_MULAW>(p[j * ch]); }
+    else if (format == WSA_PCM_ALAW) { const uint8_t* p = static_cast<const uint8_t*>(in); for (uint64_t j = 0; j < n_frames; j++) out[j] = pcm_decode_one<WSA_PCM_ALAW>(p[j * ch]); }
+    else return WSA_ERR_INVALID;
     return WSA_OK;
 }
 

@@ -965,7 +965,20 @@ function LaunchBatches(batches, callback = null, labels = [], test_play = false)
 // stream.  samplesPerStep keeps its meaning: frames_per_step * hop samples at the analysis rate.  The reference's live path runs at the hardware's
 // rate and converts nothing; this is ours, like resample_to.
 const STREAM_ACTIVE = 1, STREAM_START = 2, STREAM_STOP = 4;
-function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames_per_step = 1, max_span_frames = 1024) {
+// The seventh argument (optional) = {format: 'f32' | 'i16' | 'mulaw' | 'alaw', channels}: the sources hand over packed PCM (spec PK-1), unpacked
+// on the GPU inside the step.  handle.input is then an Int16Array ('i16') or Uint8Array (G.711) over the packed pinned buffer, handle.inputStride
+// counts elements of that array, stream i's frames of a push are interleaved over channels (a number, or one per stream; 1 .. 64) from
+// input[i * inputStride] on and channel 0 is analysed.  push(ctl, counts) is unchanged: counts are frames of one channel.
+const PCM_FORMATS = { f32: 0, i16: 1, mulaw: 2, alaw: 3 };
+function pcm_format(format) {
+  if (!Object.prototype.hasOwnProperty.call(PCM_FORMATS, format)) throw "unknown input format '" + format + "' ('f32', 'i16', 'mulaw', 'alaw')";
+  return PCM_FORMATS[format];
+}
+// channel 0 of the interleaved frames in typedArray as the floats the analysis is given (Int16Array for 'i16', Uint8Array for 'mulaw' / 'alaw')
+function decodePcm(format, typedArray, channels = 1) {
+  try { return addon().decodePcm(pcm_format(format), typedArray, channels); } catch (e) { throw (typeof e === 'string' ? e : String(e.message || e)); }
+}
+function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames_per_step = 1, max_span_frames = 1024, input_format = null) {
   const nat = addon();
   const level = settings.output_level, step = settings.window_step / 1e3;
   if (![3, 4, 5, 10, 11, 12, 13].includes(level)) throw 'output_level ' + level + ' is not available for streams through this build (3, 4, 5, 10, 11, 12 and 13 are)';
@@ -985,6 +998,12 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
     if (g.bands !== bands) throw 'Bins count mismatch: ' + g.bands + ', ' + bands;              // ref @B8568 check
     st = convert ? nat.streamOpenMixed(ctx, n_streams, Float64Array.from(per_stream ? rates : new Array(n_streams).fill(rates[0])), fs_an, frames_per_step, max_span_frames)
       : nat.streamOpen(ctx, n_streams, rates[0], frames_per_step, max_span_frames);
+    if (input_format) {
+      const chans = input_format.channels;
+      const ch = chans === undefined || chans === null ? null : Uint32Array.from(Array.isArray(chans) || ArrayBuffer.isView(chans) ? chans : new Array(n_streams).fill(chans));
+      if (ch && ch.length !== n_streams) throw 'channels as an array holds one count per stream (' + ch.length + ' counts, ' + n_streams + ' streams)';
+      nat.streamSetInput(st, pcm_format(input_format.format === undefined ? 'f32' : input_format.format), ch);
+    }
     if (pred && pred.knn) nat.streamSetKnn(st, knn_store_on(nat, ctx, pred.knn), pred.k);
     else if (pred && pred.models) nat.streamSetEnsemble(st, model_on(nat, ctx));
     else if (pred) nat.streamSetModel(st, model_on(nat, ctx));       // the native model on the stream's own context (ref src/index.js:56)
@@ -995,8 +1014,10 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
     if (vp) for (const h of vp.models) h.natives.delete(ctx);
     nat.destroy(ctx); throw (typeof e === 'string' ? e : String(e.message || e));
   }
+  const packed = !!input_format && input_format.format !== undefined && input_format.format !== 'f32';
   const input = nat.streamInput(st);
-  const info = convert ? nat.streamInfo(st) : null;
+  const info = convert || packed ? nat.streamInfo(st) : null;
+  if (packed) info.inputStride = info.inputStrideBytes / input.BYTES_PER_ELEMENT;
   const names = pred && pred.knn ? pred.knn.names.slice() : null;       // a KNN store: the labels of the rows the set opened with
   // the step's KNN tables under the names predict_after and meters_of read a model's by
   const knn_view = (res) => ({ cb: res.knnCb, cbLabel: res.knnCbLabel, cbConf: res.knnCbConf, prob: res.knnConf, nClasses: res.knnNClasses });
@@ -1127,6 +1148,6 @@ function set_predicted_label_for_segment(si, idx, label) {                      
 }
 
 module.exports = { configure, LaunchAudioNodes, StopAudioNodes, set_predicted_label_for_segment, LaunchBatch, LaunchBatches,
-  StreamOpen, STREAM_ACTIVE, STREAM_START, STREAM_STOP, shutdown, allocPinned, freePinned,
+  StreamOpen, decodePcm, STREAM_ACTIVE, STREAM_START, STREAM_STOP, shutdown, allocPinned, freePinned,
   _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, _values_after: values_after, loadModel, setPredictionModel, setPredictionModels, setPredictionKnn, setPredictionValues, trainModel, trainModels, saveModel, trainRegression, predictValues, predictDB, statsTable,
   KNNClassifier, trainKnn, predictKnn };

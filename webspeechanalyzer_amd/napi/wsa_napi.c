@@ -18,6 +18,9 @@
  *   streamInfo(stream) -> {capacity: Uint32Array, inputStride, samplesPerStep}   (wsa_stream_input_capacity / _input_stride / _samples_per_step)
  *   streamPaced(stream) -> Uint32Array: the samples a paced step takes from every stream next   (wsa_stream_paced_input)
  *   streamInput(stream) -> Float32Array over the pinned [nStreams][inputStride] input buffer (no copy; inputStride = samplesPerStep on a plain set)
+ *   streamSetInput(stream, format, channels) before the first streamInput: wsa_stream_set_input_format; streamInput then gives an Int16Array / Uint8Array
+ *     over the packed pinned buffer, [nStreams][streamInfo().inputStrideBytes / element size]
+ *   decodePcm(format, typedArray, channels) -> Float32Array   (wsa_pcm_decode: channel 0 of interleaved frames, spec PK-1)
  *   streamStep(stream, ctl: Uint8Array | null[, counts: Uint32Array | null]) -> {meta, feat, segments}   (wsa_stream_step_host[_n] + wsa_stream_collect;
  *       one hipGraph launch, well under a millisecond, so it runs on the calling thread; counts: samples per stream in this step, else paced)
  *   processBatch(..., [models])                 (8th argument an array of models: wsa_batch_classify_ensemble; the result gains `ens`)
@@ -716,7 +719,7 @@ static napi_value fn_gather_rows(napi_env env, napi_callback_info info) {
 }
 
 /* ---- streams ---- */
-typedef struct { wsa_stream *st; wsa_ctx *ctx; ctx_box *box; uint32_t n, sps; napi_ref input_ref; model_box *model; wsa_ensemble *ens; model_box *ens_models[WSA_ENSEMBLE_MAX]; uint32_t n_ens; struct knn_box *knn; wsa_regress_group *reg; model_box *reg_models[WSA_REGRESS_GROUP_MAX]; uint32_t n_reg; } stream_t;   /* input_ref: the ArrayBuffer over the pinned input, detached at close; model: attached classifier (holds its busy count) */
+typedef struct { wsa_stream *st; wsa_ctx *ctx; ctx_box *box; uint32_t n, sps; int32_t fmt; napi_ref input_ref; model_box *model; wsa_ensemble *ens; model_box *ens_models[WSA_ENSEMBLE_MAX]; uint32_t n_ens; struct knn_box *knn; wsa_regress_group *reg; model_box *reg_models[WSA_REGRESS_GROUP_MAX]; uint32_t n_reg; } stream_t;   /* input_ref: the ArrayBuffer over the pinned input, detached at close; model: attached classifier (holds its busy count) */
 static void stream_finalize(napi_env env, void *data, void *hint) { /* explicit streamClose() only */ }
 static stream_t *get_stream(napi_env env, napi_value v) {
     void *p = NULL; if (napi_get_value_external(env, v, &p) != napi_ok) return NULL; return (stream_t *)p;
@@ -773,7 +776,50 @@ static napi_value fn_stream_info(napi_env env, napi_callback_info info) {
     free(cap);
     napi_create_uint32(env, wsa_stream_input_stride(h->st), &v); napi_set_named_property(env, o, "inputStride", v);
     napi_create_uint32(env, wsa_stream_samples_per_step(h->st), &v); napi_set_named_property(env, o, "samplesPerStep", v);
+    napi_create_uint32(env, wsa_stream_input_stride_bytes(h->st), &v); napi_set_named_property(env, o, "inputStrideBytes", v);
     return o;
+}
+/* streamSetInput(stream, format 0 .. 3, channels: Uint32Array(nStreams) | null): wsa_stream_set_input_format, before the first streamInput */
+static napi_value fn_stream_set_input(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3]; int32_t fmt = 0;
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    stream_t *h = argc ? get_stream(env, argv[0]) : NULL;
+    if (!h || !h->st || argc < 2 || napi_get_value_int32(env, argv[1], &fmt) != napi_ok) { napi_throw_type_error(env, NULL, "streamSetInput(stream, format, channels)"); return NULL; }
+    if (h->input_ref) { napi_throw_error(env, NULL, "streamSetInput: the input buffer of this stream object has been handed out already"); return NULL; }
+    const uint32_t *chan = NULL;
+    if (argc > 2) {
+        bool is_ta = false; napi_typedarray_type tt; size_t len; void *data;
+        if (napi_is_typedarray(env, argv[2], &is_ta) == napi_ok && is_ta) {
+            if (napi_get_typedarray_info(env, argv[2], &tt, &len, &data, NULL, NULL) != napi_ok || tt != napi_uint32_array || len != h->n) {
+                napi_throw_type_error(env, NULL, "channels must be a Uint32Array with one count per stream"); return NULL;
+            }
+            chan = (const uint32_t *)data;
+        }
+    }
+    if (wsa_stream_set_input_format(h->st, fmt, chan) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(h->ctx)); return NULL; }
+    h->fmt = fmt;
+    return NULL;
+}
+/* decodePcm(format, typedArray, channels) -> Float32Array: wsa_pcm_decode, channel 0 of the interleaved frames (spec PK-1, no device) */
+static napi_value fn_decode_pcm(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3]; int32_t fmt = 0; uint32_t ch = 1;
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    bool is_ta = false; napi_typedarray_type tt = napi_int8_array; size_t len = 0; void *data = NULL;
+    if (argc < 2 || napi_get_value_int32(env, argv[0], &fmt) != napi_ok || napi_is_typedarray(env, argv[1], &is_ta) != napi_ok || !is_ta
+        || napi_get_typedarray_info(env, argv[1], &tt, &len, &data, NULL, NULL) != napi_ok) {
+        napi_throw_type_error(env, NULL, "decodePcm(format, typedArray, channels)"); return NULL;
+    }
+    if (argc > 2) napi_get_value_uint32(env, argv[2], &ch);
+    const napi_typedarray_type want = fmt == WSA_PCM_F32 ? napi_float32_array : fmt == WSA_PCM_I16 ? napi_int16_array : napi_uint8_array;
+    if (fmt < WSA_PCM_F32 || fmt > WSA_PCM_ALAW) { napi_throw_error(env, NULL, "decodePcm: unknown input format"); return NULL; }
+    if (tt != want) { napi_throw_type_error(env, NULL, "decodePcm: f32 takes a Float32Array, i16 an Int16Array, mulaw / alaw a Uint8Array"); return NULL; }
+    if (ch < 1 || ch > 64) { napi_throw_error(env, NULL, "decodePcm: channel count outside 1 .. 64"); return NULL; }
+    const size_t frames = len ? (len - 1) / ch + 1 : 0;
+    napi_value ab, ta; void *out = NULL;
+    NAPI_OK(env, napi_create_arraybuffer(env, frames * sizeof(float), &out, &ab));
+    if (wsa_pcm_decode(fmt, data, frames, ch, (float *)out) != WSA_OK) { napi_throw_error(env, NULL, "decodePcm: refused"); return NULL; }
+    NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, frames, ab, 0, &ta));
+    return ta;
 }
 static napi_value fn_stream_paced(napi_env env, napi_callback_info info) {
     size_t argc = 1; napi_value argv[1];
@@ -791,15 +837,18 @@ static napi_value fn_stream_input(napi_env env, napi_callback_info info) {
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     stream_t *h = argc ? get_stream(env, argv[0]) : NULL;
     if (!h || !h->st) { napi_throw_type_error(env, NULL, "streamInput(stream)"); return NULL; }
-    const size_t count = (size_t)h->n * h->sps;
+    /* a packed format (streamSetInput): the Int16Array / Uint8Array over the pinned packed buffer, [nStreams][inputStrideBytes / element size] */
+    void *packed = wsa_stream_host_input_packed(h->st);
+    const size_t elt = !packed ? sizeof(float) : h->fmt == WSA_PCM_I16 ? 2 : 1;
+    const size_t count = packed ? (size_t)h->n * wsa_stream_input_stride_bytes(h->st) / elt : (size_t)h->n * h->sps;
     napi_value ab, ta;
     if (h->input_ref) {                      /* one ArrayBuffer per stream object: hand the same one out again */
         NAPI_OK(env, napi_get_reference_value(env, h->input_ref, &ab));
     } else {
-        NAPI_OK(env, napi_create_external_arraybuffer(env, wsa_stream_host_input(h->st), count * sizeof(float), NULL, NULL, &ab));
+        NAPI_OK(env, napi_create_external_arraybuffer(env, packed ? packed : (void *)wsa_stream_host_input(h->st), count * elt, NULL, NULL, &ab));
         NAPI_OK(env, napi_create_reference(env, ab, 1, &h->input_ref));
     }
-    NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, count, ab, 0, &ta));
+    NAPI_OK(env, napi_create_typedarray(env, !packed ? napi_float32_array : h->fmt == WSA_PCM_I16 ? napi_int16_array : napi_uint8_array, count, ab, 0, &ta));
     return ta;
 }
 static napi_value fn_stream_step(napi_env env, napi_callback_info info) {
@@ -1787,7 +1836,7 @@ NAPI_MODULE_INIT() {
     const struct { const char *name; napi_callback fn; } fns[] = {
         {"abiVersion", fn_abi_version}, {"freePinned", fn_free_pinned}, {"defaults", fn_defaults}, {"create", fn_create}, {"destroy", fn_destroy},
         {"geometry", fn_geometry}, {"allocPinned", fn_alloc_pinned}, {"binsHz", fn_bins_hz}, {"processBatch", fn_process_batch}, {"gatherRows", fn_gather_rows},
-        {"streamOpen", fn_stream_open}, {"streamOpenMixed", fn_stream_open_mixed}, {"streamInfo", fn_stream_info}, {"streamPaced", fn_stream_paced}, {"streamInput", fn_stream_input}, {"streamStep", fn_stream_step}, {"streamClose", fn_stream_close}, {"streamSetModel", fn_stream_set_model}, {"streamSetEnsemble", fn_stream_set_ensemble}, {"streamSetKnn", fn_stream_set_knn},
+        {"streamOpen", fn_stream_open}, {"streamOpenMixed", fn_stream_open_mixed}, {"streamInfo", fn_stream_info}, {"streamPaced", fn_stream_paced}, {"streamInput", fn_stream_input}, {"streamSetInput", fn_stream_set_input}, {"decodePcm", fn_decode_pcm}, {"streamStep", fn_stream_step}, {"streamClose", fn_stream_close}, {"streamSetModel", fn_stream_set_model}, {"streamSetEnsemble", fn_stream_set_ensemble}, {"streamSetKnn", fn_stream_set_knn},
         {"modelCreate", fn_model_create}, {"modelDestroy", fn_model_destroy}, {"train", fn_train}, {"trainGroup", fn_train_group}, {"regressRows", fn_regress_rows},
         {"dbPredict", fn_db_predict}, {"dbTable", fn_db_table},
         {"knnCreate", fn_knn_create}, {"knnDestroy", fn_knn_destroy}, {"knnAdd", fn_knn_add}, {"knnClassify", fn_knn_classify}, {"batchKnn", fn_batch_knn}, {"batchKnnFold", fn_batch_knn_fold},
