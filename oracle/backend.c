@@ -96,6 +96,30 @@ static const char *const tarm_names[TARM_COUNT] = { TRACK_ARMS(X) };
 #undef X
 #define TARM(S, a) ((S)->tarms[TARM_##a]++)
 
+/* the arms of the peak scan that tests/peak_cases.py aims at (wsa_or_peak_arm_*; the same names in the same order as tests/peak_ref.py ARMS): one per
+ * side of every comparison of the scan and of the shrink, bumped where the arm is taken, read only by tests */
+#define PEAK_PRED(X, p) X(p##true_a1) X(p##true_a2) X(p##true_a3plus) X(p##eq_1) X(p##eq_2_alone) X(p##eq_3_alone) X(p##wrong_2) X(p##wrong_3)
+#define PEAK_ARMS(X) \
+    PEAK_PRED(X, R_) PEAK_PRED(X, F_) \
+    X(rise_from_idle) X(rise_closes_candidate) X(rise_leaves_c_1) X(rise_leaves_c_2) X(rise_while_rising) X(close_guard_fails) \
+    X(fall_from_rising) X(fall_moves_s) X(fall_while_idle) \
+    X(flat_counts_1) X(flat_counts_2) X(flat_timeout) X(flat_timeout_carried_1) X(flat_timeout_carried_2) \
+    X(creep_moves_l) X(creep_equal_kept) X(creep_below_kept) X(idle_neither) \
+    X(eos_emit) X(eos_after_creep) X(eos_while_falling) X(eos_rise_on_last_bin) X(eos_guard_fails) \
+    X(floor_equal_refused) X(floor_below_refused) X(h_2v_not_above) \
+    X(shrink_left_0) X(shrink_left_1) X(shrink_left_2) X(shrink_left_3) X(shrink_left_4) X(shrink_left_5plus) X(shrink_left_to_l) \
+    X(shrink_right_0) X(shrink_right_1) X(shrink_right_2) X(shrink_right_3) X(shrink_right_4) X(shrink_right_5plus) X(shrink_right_to_l) \
+    X(shrink_equal_stops) X(shrink_10k1_floor_goes_on) X(shrink_10k1_ceil_stops) X(shrink_10k9_floor_goes_on) X(shrink_10k9_ceil_stops) X(shrink_big) \
+    X(shrink_left_outlasts_right) X(shrink_right_outlasts_left) \
+    X(largest_tie_first_kept) X(largest_eos_excluded) X(largest_none) \
+    X(g_above_2_32) X(p_cross_inside_shoulder) X(p_cross_at_i_minus_1) X(p_cross_at_s) X(p_high_byte_255) X(cand_64) X(cand_65)
+#define X(a) PARM_##a,
+enum { PEAK_ARMS(X) PARM_COUNT };
+#undef X
+#define X(a) #a,
+static const char *const parm_names[PARM_COUNT] = { PEAK_ARMS(X) };
+#undef X
+
 struct wsa_or_seg {
     wsa_or_cfg cfg;
     /* segmenter state `o` (@B23439) */
@@ -119,6 +143,7 @@ struct wsa_or_seg {
     int32_t span_begin, reset0_in_frame, voiced_now;
     int64_t arms[ARM_COUNT];
     int64_t tarms[TARM_COUNT];
+    int64_t parms[PARM_COUNT];
 };
 
 static void track_free(track_t *t) {
@@ -541,38 +566,118 @@ static void noise_gate(wsa_or_seg *S, double h) {
     } else if (S->w > 20 && S->floor_ < S->last_floor) ARM(S, decay_stop);      /* a decay that has run into max(10, last_floor / 10) */
 }
 
+/* The scan of the frame loop D() @B25827 on its own: the candidates [i, s, l] of frame e that pass `e[l] > v`, after the /10 shoulder shrink, and
+ * n, p, h, d, g as the loop hands them on.  A negative v keeps every candidate (amplitudes are unsigned), which is the table csrc/peaks.hip writes.
+ * `last` (may be NULL) marks the end-of-spectrum emission, psum (may be NULL) takes the exact P[i - 1] and P[s] per candidate, A the arm counts. */
+typedef struct { int32_t n, p, raw, n_early; double h, d, g, d_early; } scan_t;
+
+static void scan_count_pred(const uint32_t *e, int32_t a, int above, int64_t *A) {
+    const uint32_t ea = e[a];
+#define CMP(x, y) (above ? (x) > (y) : (x) < (y))
+    if (ea == e[a - 1]) { A[3]++; return; }
+    if (!CMP(ea, e[a - 1])) return;
+    const int ok2 = a < 2 || CMP(ea, e[a - 2]), ok3 = a < 3 || CMP(ea, e[a - 3]);
+    if (a >= 2 && !ok2) { if (ea != e[a - 2]) A[6]++; else if (ok3) A[4]++; }
+    if (ok2 && !ok3) A[ea == e[a - 3] ? 5 : 7]++;
+    if (ok2 && ok3) A[a == 1 ? 0 : a == 2 ? 1 : 2]++;
+#undef CMP
+}
+
+/* the arms of one step of the shrink's walk: e[x] against e[l] / 10 */
+static void scan_count_shrink(const uint32_t *e, int32_t x, int32_t l, int64_t *A) {
+    const uint32_t ex = e[x], el = e[l], k = el / 10, m = el % 10;
+    if (ex >= 429496730u) A[PARM_shrink_big]++;
+    if (m == 0 && ex == k) A[PARM_shrink_equal_stops]++;
+    if (m == 1 && ex == k) A[PARM_shrink_10k1_floor_goes_on]++;
+    if (m == 1 && ex == k + 1) A[PARM_shrink_10k1_ceil_stops]++;
+    if (m == 9 && ex == k) A[PARM_shrink_10k9_floor_goes_on]++;
+    if (m == 9 && ex == k + 1) A[PARM_shrink_10k9_ceil_stops]++;
+}
+
+static void scan_frame(const uint32_t *e, int32_t B, double v, peak_t *pk, uint8_t *last, uint64_t *psum, scan_t *o, int64_t *A) {
+    int32_t n = 0, i = 0, l = 0, s = 0, c = 0, u = 0, p = 0, c0 = 0;
+    double d = 0, h = v < 0 ? 0 : 2 * v, g = 0;            /* (every candidate kept: the largest starts from 0, as the device's header does) */
+    int32_t raw = 0, n_early = 0; double d_early = 0;     /* tests only: candidates by geometry alone (the device's table order); accepted ones among the first 16 */
+    uint64_t *P = malloc(sizeof(uint64_t) * (size_t)(B > 0 ? B : 1));
+    { uint64_t t = 0; for (int32_t a = 0; a < B; a++) { t += e[a]; P[a] = t; } }
+#define PA(a) (A[PARM_##a]++)
+#define EMIT(upd) do { \
+        if (!(e[l] > v)) { if (e[l] == v) PA(floor_equal_refused); else PA(floor_below_refused); break; } \
+        if (raw - 1 < 16) { n_early++; d_early += e[l]; } \
+        if (upd) { if (p > 0 && e[l] == h) PA(largest_tie_first_kept); if (v >= 0 && p == 0 && !(e[l] > h)) PA(h_2v_not_above); } \
+        else if (e[l] > h) PA(largest_eos_excluded); \
+        if ((upd) && e[l] > h) { h = e[l]; p = l; } \
+        double thr = e[l] / 10.0; int32_t nl = 0, nr = 0; \
+        while (i < l && (scan_count_shrink(e, i, l, A), e[i] < thr)) { i++; nl++; } \
+        while (s > l && (scan_count_shrink(e, s, l, A), e[s] < thr)) { s--; nr++; } \
+        A[PARM_shrink_left_0 + (nl < 5 ? nl : 5)]++; if (i == l) PA(shrink_left_to_l); \
+        A[PARM_shrink_right_0 + (nr < 5 ? nr : 5)]++; if (s == l) PA(shrink_right_to_l); \
+        if (nl > nr) PA(shrink_left_outlasts_right); else if (nr > nl) PA(shrink_right_outlasts_left); \
+        { const uint64_t pi = i > 0 ? P[i - 1] : 0, ps = P[s]; \
+          if (ps >> 32 != pi >> 32) PA(p_cross_inside_shoulder); \
+          if (i > 0 && pi >> 32 != (i > 1 ? P[i - 2] : 0) >> 32) PA(p_cross_at_i_minus_1); \
+          if (ps >> 32 != P[s - 1] >> 32) PA(p_cross_at_s); \
+          if (ps >> 32 == 255) PA(p_high_byte_255); \
+          if (psum) { psum[2 * n] = pi; psum[2 * n + 1] = ps; } } \
+        if (last) last[n] = !(upd); \
+        pk[n].i = i; pk[n].s = s; pk[n].l = l; n++; d += e[l]; } while (0)
+    for (int32_t a = 1; a < B; a++) {                                          /* @B25827 */
+        g += e[a];
+        scan_count_pred(e, a, 1, A + PARM_R_true_a1);
+        if (e[a] > e[a - 1] && (a < 2 || e[a] > e[a - 2]) && (a < 3 || e[a] > e[a - 3])) {
+            if (a == B - 1) PA(eos_rise_on_last_bin);
+            if (u == -1 || u == 0) {
+                if (u == 0) PA(rise_from_idle);
+                else if (i <= l && l < s) { PA(rise_closes_candidate); if (c == 1) PA(rise_leaves_c_1); else if (c == 2) PA(rise_leaves_c_2); }
+                else PA(close_guard_fails);
+                if (u == -1 && i <= l && l < s) { raw++; EMIT(1); }
+                i = a - 1; l = a;
+            } else if (u == 1) { l = a; PA(rise_while_rising); }
+            u = 1;
+        } else if (scan_count_pred(e, a, 0, A + PARM_F_true_a1), e[a] < e[a - 1] && (a < 2 || e[a] < e[a - 2]) && (a < 3 || e[a] < e[a - 3])) {
+            if (u == 1) { PA(fall_from_rising); c0 = c; } else if (u == -1) PA(fall_moves_s); else PA(fall_while_idle);
+            if (u == 1 || u == -1) { s = a; u = -1; }
+        } else if (u == -1) {
+            c++;
+            if (c == 1) PA(flat_counts_1); else if (c == 2) PA(flat_counts_2);
+            if (c > 2) {
+                c = 0;
+                if (i <= l && l < s) { PA(flat_timeout); if (c0 == 1) PA(flat_timeout_carried_1); else if (c0 == 2) PA(flat_timeout_carried_2); } else PA(close_guard_fails);
+                if (i <= l && l < s) { raw++; EMIT(1); }
+                u = 0;
+            }
+        } else if (u == 1 && e[a] > e[a - 1]) { l = a; PA(creep_moves_l); }
+        else if (u == 1) { if (e[a] == e[a - 1]) PA(creep_equal_kept); else PA(creep_below_kept); }
+        else PA(idle_neither);
+        if (a == B - 1 && u == -1) PA(eos_while_falling);
+        if (a == B - 1 && u == 1) {
+            const int crept = l != a && e[l] > e[a];
+            s = a; l = a;
+            if (i < l && l <= s) { PA(eos_emit); if (crept) PA(eos_after_creep); } else PA(eos_guard_fails);
+            if (i < l && l <= s) { raw++; EMIT(0); }
+        }
+    }
+#undef EMIT
+    if (g >= 4294967296.0) PA(g_above_2_32);
+    if (p == 0) PA(largest_none);
+    if (n == 64) PA(cand_64);
+    if (n > 64) PA(cand_65);
+#undef PA
+    free(P);
+    o->n = n; o->p = p; o->raw = raw; o->n_early = n_early; o->h = h; o->d = d; o->g = g; o->d_early = d_early;
+}
+
 /* spectrum_push I(e,t) @B30392 (levels > 2) followed by one pass of the frame loop D() @B25717 */
 void wsa_or_seg_push(wsa_or_seg *S, const uint32_t *e) {
     const int32_t B = S->bands;
     S->cur_frame++;
     double t = S->c_ci;                           /* captured before the start test (quirk 1) */
     double v = S->floor_;
-    int32_t n = 0, i = 0, l = 0, s = 0, c = 0, u = 0, p = 0;
-    double d = 0, h = 2 * v, g = 0;
     peak_t *pk = malloc(sizeof(peak_t) * (size_t)(B > 0 ? B : 1));
-    int32_t raw = 0, n_early = 0; double d_early = 0;     /* tests only: candidates by geometry alone (the device's table order); accepted ones among the first 16 */
-#define EMIT(upd) do { if (raw - 1 < 16) { n_early++; d_early += e[l]; } if ((upd) && e[l] > h) { h = e[l]; p = l; } \
-        double thr = e[l] / 10.0; \
-        while (i < l && e[i] < thr) i++; \
-        while (s > l && e[s] < thr) s--; \
-        pk[n].i = i; pk[n].s = s; pk[n].l = l; n++; d += e[l]; } while (0)
-    for (int32_t a = 1; a < B; a++) {                                          /* @B25827 */
-        g += e[a];
-        if (e[a] > e[a - 1] && (a < 2 || e[a] > e[a - 2]) && (a < 3 || e[a] > e[a - 3])) {
-            if (u == -1 || u == 0) {
-                if (u == -1 && i <= l && l < s) { raw++; if (e[l] > v) EMIT(1); }
-                i = a - 1; l = a;
-            } else if (u == 1) l = a;
-            u = 1;
-        } else if (e[a] < e[a - 1] && (a < 2 || e[a] < e[a - 2]) && (a < 3 || e[a] < e[a - 3])) {
-            if (u == 1 || u == -1) { s = a; u = -1; }
-        } else if (u == -1) {
-            c++;
-            if (c > 2) { c = 0; if (i <= l && l < s) { raw++; if (e[l] > v) EMIT(1); } u = 0; }
-        } else if (u == 1 && e[a] > e[a - 1]) l = a;
-        if (a == B - 1 && u == 1) { s = a; l = a; if (i < l && l <= s) { raw++; if (e[l] > v) EMIT(0); } }
-    }
-#undef EMIT
+    scan_t sc;
+    scan_frame(e, B, v, pk, NULL, NULL, &sc, S->parms);
+    const int32_t n = sc.n, p = sc.p, n_early = sc.n_early;
+    const double d = sc.d, h = sc.h, g = sc.g, d_early = sc.d_early;
     /* ---- what the arms below are counted from (tests only; nothing here feeds the state) */
     const double mvb = S->max_voiced_bin;
     const double d16 = d_early; const int32_t n16 = n_early;
@@ -689,6 +794,24 @@ int64_t wsa_or_gate_arm_count(const wsa_or_seg *s, int32_t i) { return i >= 0 &&
 int32_t wsa_or_track_n_arms(void) { return TARM_COUNT; }
 const char *wsa_or_track_arm_name(int32_t i) { return i >= 0 && i < TARM_COUNT ? tarm_names[i] : NULL; }
 int64_t wsa_or_track_arm_count(const wsa_or_seg *s, int32_t i) { return i >= 0 && i < TARM_COUNT ? s->tarms[i] : -1; }
+
+int32_t wsa_or_peak_n_arms(void) { return PARM_COUNT; }
+const char *wsa_or_peak_arm_name(int32_t i) { return i >= 0 && i < PARM_COUNT ? parm_names[i] : NULL; }
+int64_t wsa_or_peak_arm_count(const wsa_or_seg *s, int32_t i) { return i >= 0 && i < PARM_COUNT ? s->parms[i] : -1; }
+
+/* the scan of one frame without a segmenter (tests/peak_cases.py): cand [bands][4] = i, s, l, last; out5 = n, p, h, d, g; psum [bands][2] = P[i - 1], P[s];
+ * arms [wsa_or_peak_n_arms()] is added to.  v < 0 keeps every candidate.  Returns n. */
+int32_t wsa_or_scan_frame(const uint32_t *e, int32_t bands, double v, int32_t *cand, double *out5, uint64_t *psum, int64_t *arms) {
+    int64_t own[PARM_COUNT] = {0};
+    peak_t *pk = malloc(sizeof(peak_t) * (size_t)(bands > 0 ? bands : 1));
+    uint8_t *last = calloc((size_t)(bands > 0 ? bands : 1), 1);
+    scan_t sc;
+    scan_frame(e, bands, v, pk, last, psum, &sc, arms ? arms : own);
+    for (int32_t k = 0; cand && k < sc.n; k++) { cand[4 * k] = pk[k].i; cand[4 * k + 1] = pk[k].s; cand[4 * k + 2] = pk[k].l; cand[4 * k + 3] = last[k]; }
+    if (out5) { out5[0] = sc.n; out5[1] = sc.p; out5[2] = sc.h; out5[3] = sc.d; out5[4] = sc.g; }
+    free(pk); free(last);
+    return sc.n;
+}
 
 int32_t wsa_or_n_segments(const wsa_or_seg *s) { return s->segs.n; }
 void wsa_or_segment(const wsa_or_seg *s, int32_t i, int32_t out[5]) {

@@ -74,6 +74,13 @@ def lib():
     L.wsa_or_track_arm_name.argtypes = [i32]
     L.wsa_or_track_arm_count.restype = ctypes.c_int64
     L.wsa_or_track_arm_count.argtypes = [vp, i32]
+    L.wsa_or_peak_n_arms.restype = i32
+    L.wsa_or_peak_arm_name.restype = ctypes.c_char_p
+    L.wsa_or_peak_arm_name.argtypes = [i32]
+    L.wsa_or_peak_arm_count.restype = ctypes.c_int64
+    L.wsa_or_peak_arm_count.argtypes = [vp, i32]
+    L.wsa_or_scan_frame.restype = i32
+    L.wsa_or_scan_frame.argtypes = [vp, i32, d, vp, vp, vp, vp]
     L.wsa_or_enable_trace.argtypes = [vp, i32]
     L.wsa_or_seg_free.argtypes = [vp]
     for name in ("wsa_or_n_segments", "wsa_or_n_syllables", "wsa_or_trace_len"):
@@ -180,6 +187,28 @@ def default_cfg(level=5, bands=128, **kw):
 def gate_arm_names():
     L = lib()
     return [L.wsa_or_gate_arm_name(i).decode() for i in range(L.wsa_or_gate_n_arms())]
+
+
+def peak_arm_names():
+    L = lib()
+    return [L.wsa_or_peak_arm_name(i).decode() for i in range(L.wsa_or_peak_n_arms())]
+
+
+def scan_frame(e, v=None):
+    """The frame loop's scan of one u32 frame on its own (oracle/backend.c scan_frame, the function wsa_or_seg_push calls): cands [(i, s, l, last)]
+    after the shrink, their exact prefix sums p_i = P[i - 1] and p_s = P[s], n, p, h, d, g and the arm counts.  v is the noise floor; None keeps every
+    candidate and lets h start from 0 (the device's table)."""
+    L = lib()
+    e = np.ascontiguousarray(e, np.uint32)
+    B = len(e)
+    cand = np.zeros((max(B, 1), 4), np.int32)
+    psum = np.zeros((max(B, 1), 2), np.uint64)
+    out5 = np.zeros(5)
+    arms = np.zeros(L.wsa_or_peak_n_arms(), np.int64)
+    n = L.wsa_or_scan_frame(e.ctypes.data, B, -1.0 if v is None else float(v), cand.ctypes.data, out5.ctypes.data, psum.ctypes.data, arms.ctypes.data)
+    p, h = int(out5[1]), out5[2]
+    return dict(cands=[tuple(int(x) for x in r) for r in cand[:n]], p_i=[int(x) for x in psum[:n, 0]], p_s=[int(x) for x in psum[:n, 1]],
+                n=n, p=p, h=h, d=out5[3], g=out5[4], largest=(int(h), p) if p > 0 else (0, 0), arms=dict(zip(peak_arm_names(), (int(x) for x in arms))))
 
 
 def track_arm_names():

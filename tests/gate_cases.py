@@ -24,6 +24,7 @@ import hashlib
 import numpy as np
 
 from oracle import pyoracle
+from tests import peak_ref
 
 U32 = 4294967295
 AUTO = dict(window_step=25.0, pause_length=200.0, min_seg_length=50.0, auto_noise_gate=1, voiced_max_dB=100.0, voiced_min_dB=10.0)
@@ -37,38 +38,7 @@ UNREACHABLE = {
 
 def scan(e):
     """the candidates of frame e by geometry alone (ref @B25827 without `e[l] > v`): [(l, is end-of-spectrum emission)]"""
-    B = len(e)
-    e = [int(x) for x in e]
-    out = []
-    i = l = s = c = u = 0
-    for a in range(1, B):
-        up = e[a] > e[a - 1] and (a < 2 or e[a] > e[a - 2]) and (a < 3 or e[a] > e[a - 3])
-        dn = e[a] < e[a - 1] and (a < 2 or e[a] < e[a - 2]) and (a < 3 or e[a] < e[a - 3])
-        if up:
-            if u in (-1, 0):
-                if u == -1 and i <= l and l < s:
-                    out.append((l, False))
-                i, l = a - 1, a
-            else:
-                l = a
-            u = 1
-        elif dn:
-            if u in (1, -1):
-                s, u = a, -1
-        elif u == -1:
-            c += 1
-            if c > 2:
-                c = 0
-                if i <= l and l < s:
-                    out.append((l, False))
-                u = 0
-        elif u == 1 and e[a] > e[a - 1]:
-            l = a
-        if a == B - 1 and u == 1:
-            s = l = a
-            if i < l:
-                out.append((l, True))
-    return out
+    return [(l, bool(last)) for _, _, l, last in peak_ref.scan(e)["cands"]]
 
 
 def _fill_g(e, g, last_free):

@@ -18,7 +18,8 @@
 //               "clips": [{"spectra": "x.bin", "frames": F, "bands": B, "level": 5,
 //                          "window_step": 25, "pause_length": 200, "min_seg_length": 50,
 //                          "auto_noise_gate": true, "voiced_max_dB": 100, "voiced_min_dB": 10,
-//                          "trace": false}, ...]}
+//                          "trace": false, "peaks": false}, ...]}
+//   "peaks": per frame the candidate list [i, s, l] that accumulate_fm receives and n, p, h, d, g (tests/golden/gen/make_peaks_golden.py)
 'use strict';
 const fs = require('fs');
 
@@ -32,7 +33,7 @@ function load_reference(bundle_path) {
   const hook = 'o.c_ci++,f=null';
   if (src.indexOf(hook) < 0) throw new Error('trace hook site not found');
   src = src.replace(hook,
-    '(globalThis.__fa_trace&&globalThis.__fa_trace(o,y,v,n,p,h,d,g)),' + hook);
+    '(globalThis.__fa_trace&&globalThis.__fa_trace(o,y,v,n,p,h,d,g)),(globalThis.__fa_peaks&&globalThis.__fa_peaks(f,n,p,h,d,g)),' + hook);
   // the match score `_` (@B37340) is module-private: hand it out through a global (function-level fixture G2)
   const score_decl = 'function _(e,t,n,r,a,i,o,l){let s=0;';
   if (src.indexOf(score_decl) < 0) throw new Error('score function not found');
@@ -66,6 +67,10 @@ async function run_clip(ref, c) {
   globalThis.__fa_trace = c.trace ? (o, y, v, n, p, h, d, g) => {
     trace.push([o.c_ci, o.c_started, o.no_fm_segs, y, v, n, p, h, d, g]);
   } : null;
+  const peaks = [];
+  globalThis.__fa_peaks = c.peaks ? (f, n, p, h, d, g) => {
+    peaks.push([f.map(t => [t[0], t[1], t[2]]), [n, p, h, d, g]]);
+  } : null;
   const log = console.log; console.log = () => {};   // "seg_size ... ignored" chatter
   try {
     await ref.seg.reset_segmentation(c.level, c.bands, 200, c.window_step, c.pause_length,
@@ -90,6 +95,7 @@ async function run_clip(ref, c) {
   }
   const out = { segments_ci: segs, syllables_ci: syls, callbacks: calls };
   if (c.trace) out.trace = enc(trace);
+  if (c.peaks) out.peaks = enc(peaks);
   return out;
 }
 

@@ -7,6 +7,7 @@ import struct
 import numpy as np
 import pytest
 
+from tests import peak_ref
 from tests.util import GOLDEN, rel_err, same_f64
 
 pytestmark = pytest.mark.gpu
@@ -109,52 +110,10 @@ def test_device_match_score_equals_the_reference_function():
 
 def _peak_scan_reference(e):
     """The reference's scan of one u32 frame (ref dist/main.js:2 @B25827) with the noise floor left out
-    (every candidate is kept; the gate applies `e[l] > v` later): candidates (i, s, l, last) after the /10 shoulder shrink, g."""
-    B = len(e)
-    e = [int(x) for x in e]
-    out = []
-    i = l = s = c = u = 0
-
-    def emit(last):
-        nonlocal i, s
-        qi, qs = i, s
-        while qi < l and 10 * e[qi] < e[l]:
-            qi += 1
-        while qs > l and 10 * e[qs] < e[l]:
-            qs -= 1
-        out.append((qi, qs, l, last))
-        i, s = qi, qs
-
-    g = 0
-    for a in range(1, B):
-        g += e[a]
-        R = e[a] > e[a - 1] and (a < 2 or e[a] > e[a - 2]) and (a < 3 or e[a] > e[a - 3])
-        F = e[a] < e[a - 1] and (a < 2 or e[a] < e[a - 2]) and (a < 3 or e[a] < e[a - 3])
-        if R:
-            if u in (-1, 0):
-                if u == -1 and i <= l and l < s:
-                    emit(0)
-                i = a - 1; l = a
-            else:
-                l = a
-            u = 1
-        elif F:
-            if u in (1, -1):
-                s = a; u = -1
-        elif u == -1:
-            c += 1
-            if c > 2:
-                c = 0
-                if i <= l and l < s:
-                    emit(0)
-                u = 0
-        elif u == 1 and e[a] > e[a - 1]:
-            l = a
-        if a == B - 1 and u == 1:
-            s = a; l = a
-            if i < l and l <= s:
-                emit(1)
-    return out, g
+    (every candidate is kept; the gate applies `e[l] > v` later): candidates (i, s, l, last) after the /10 shoulder shrink, g.  The restatement
+    itself is tests/peak_ref.py, which tests/test_peaks_reference.py pins to the oracle and to the reference's own run."""
+    r = peak_ref.scan(e)
+    return r["cands"], r["g"]
 
 
 def _peak_frames(rng, n, B):

@@ -1745,3 +1745,34 @@ def debug_gate(variant, clips, settings, blocks=0, F=0, max_span=0, step_nfr=Non
     if streams:
         out.update(fr_span=cut(fr_span), state=state, ring=ring)
     return out
+
+
+PEAKS_LANES_16, PEAKS_LANES_32, PEAKS_WAVE = 3, 4, 2          # modes of wsa_debug_peaks: peaks_kernel<16>, peaks_kernel<32>, peaks_wave_kernel (at most 128 bands)
+CAND_CAP = 64
+
+
+def debug_peaks(spec, mode, device=0):
+    """Test access to the peak scan on its own (csrc/debug.hip wsa_debug_peaks; not part of include/wsa.h): spec = [n_frames, bands] u32, one launch of
+    the kernel behind `mode` (PEAKS_*).  Returns the frame records as the kernel left them in zero-filled tables, decoded: g [n] (40 bits), n [n], largest
+    amplitude and bin [n], table base [n]; per candidate slot [n, 64] i, s, l, last, amp and the 40-bit prefix sums p_i = P[i - 1] and p_s = P[s]; the flag word;
+    and the raw words hdr [n, 4], amp, ent [n, 64, 4] for bitwise comparisons.  Raises WsaError on a refusal."""
+    L = lib()
+    vp, i32, u32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32
+    L.wsa_debug_peaks.argtypes = [i32, vp, u32, i32, i32, vp, vp, vp, vp]
+    L.wsa_debug_peaks.restype = ctypes.c_int
+    spec = np.ascontiguousarray(spec, np.uint32)
+    n, bands = spec.shape
+    hdr = np.zeros((n, 4), np.uint32)
+    amp = np.zeros((n, CAND_CAP), np.uint32)
+    ent = np.zeros((n, CAND_CAP, 4), np.uint32)
+    flags = np.zeros(1, np.uint32)
+    rc = L.wsa_debug_peaks(device, spec.ctypes.data, n, bands, mode, hdr.ctypes.data, amp.ctypes.data, ent.ctypes.data, flags.ctypes.data)
+    if rc != 0:
+        raise WsaError(f"wsa_debug_peaks: error {rc}")
+    h1, w, hi = hdr[:, 1].astype(np.uint64), ent[:, :, 0], ent[:, :, 3].astype(np.uint64)
+    return dict(g=hdr[:, 0].astype(np.uint64) | ((h1 & np.uint64(0xff)) << np.uint64(32)), n=(hdr[:, 1] >> 8) & 0xff, largest_bin=(hdr[:, 1] >> 16) & 0xff,
+                largest_amp=hdr[:, 2].copy(), base=hdr[:, 3].copy(), hdr_top=hdr[:, 1] >> 24,
+                i=w & 0xff, s=(w >> 8) & 0xff, l=(w >> 16) & 0xff, last=w >> 24, amp=amp,
+                p_i=ent[:, :, 1].astype(np.uint64) | ((hi & np.uint64(0xff)) << np.uint64(32)),
+                p_s=ent[:, :, 2].astype(np.uint64) | (((hi >> np.uint64(8)) & np.uint64(0xff)) << np.uint64(32)), ent_top=ent[:, :, 3] >> 16,
+                flags=int(flags[0]), hdr=hdr, ent=ent)

@@ -126,8 +126,9 @@ extern "C" int wsa_debug_features(int32_t device, const float* frames9, uint32_t
     return ok ? WSA_OK : WSA_ERR_HIP;
 }
 
-// the peak-candidate scan on its own: `spec` = n_frames rows of `bands` u32 (host), mode 1 = lane-per-frame kernel, 2 = wave-per-frame
-// kernel; out: hdr [n_frames][4], amp [n_frames * 64], ent [n_frames * 64][4] (u32, candidate tables zero-filled beforehand), flags
+// the peak-candidate scan on its own: `spec` = n_frames rows of `bands` u32 (host); mode as launch_peaks_mode takes it: 0 = by size, 1 = one lane per
+// frame, 2 = one wave per frame (up to 128 bands; wider frames fall to the lane kernel), 3 / 4 = one lane per frame in rounds of 16 / 32 bins
+// (peaks_kernel<16> / <32>); out: hdr [n_frames][4], amp [n_frames * 64], ent [n_frames * 64][4] (u32, candidate tables zero-filled beforehand), flags
 extern "C" int wsa_debug_peaks(int32_t device, const uint32_t* spec, uint32_t n_frames, int32_t bands, int32_t mode,
                                uint32_t* hdr, uint32_t* amp, uint32_t* ent, uint32_t* flags) {
     if (!spec || !hdr || !amp || !ent || !flags || bands < 1 || n_frames < 1) return WSA_ERR_INVALID;
