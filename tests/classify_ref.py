@@ -3,7 +3,8 @@ src/prediction.js:86-169 (one model DB).  The network is the yardstick for K6 wi
 arithmetic, so K6b must equal it bit for bit when fed the same f32 probabilities."""
 import math
 import os
-from decimal import ROUND_HALF_UP, Decimal
+from collections import Counter
+from decimal import ROUND_FLOOR, ROUND_HALF_UP, Decimal, localcontext
 
 import numpy as np
 
@@ -26,27 +27,47 @@ def forward(spec, feat):
     return x
 
 
+# How often each arm of the fold's comparisons was taken (tests/test_fold_reference.py asserts that the hand-built cases of
+# tests/fold_cases.py reach every one; ensemble_ref counts the ensemble's).  "seg" / "all": the segment and the launch accumulator.
+FOLD_ARM_NAMES = (
+    "fixed3.down", "fixed3.up", "fixed3.tie", "skip.zero", "skip.positive", "syllables.one", "syllables.several",
+    "seg.absent", "seg.zero", "seg.nan", "seg.added", "all.absent", "all.zero", "all.nan", "all.added",
+    "rank_tie.yes", "rank_tie.no", "rank_tie.all_nan", "key.index", "key.string",
+    "sum_tie.index_index", "sum_tie.string_string", "sum_tie.index_string", "label.found", "label.null",
+    "winner.replaced", "winner.tie_kept", "winner.none", "min_db.raised", "min_db.tie_kept", "min_db.skipped", "min_db.none",
+    "all_sum.legend_order", "all_sum.key_order_differs")
+FOLD_ARMS = Counter()
+
+
 def fixed3(x):
     """parseFloat(x.toFixed(3)): toFixed takes the n for which n / 1000 - x is closest to zero on the EXACT binary value of x, the larger
     n on a tie — and ties do occur (every odd multiple of 1/2000 that is a binary fraction, e.g. 0.0625 -> "0.063"), so round half up on
     the exact value (Decimal(x) is exact), not '%.3f' (half even)."""
+    with localcontext() as ctx:
+        ctx.prec = 1200                           # exact: a double has at most 1074 fractional digits
+        k = Decimal(x) * 1000
+        frac = k - k.to_integral_value(rounding=ROUND_FLOOR)
+    FOLD_ARMS["fixed3.tie" if frac == Decimal("0.5") else ("fixed3.up" if frac > Decimal("0.5") else "fixed3.down")] += 1
     return float(Decimal(x).quantize(Decimal("0.001"), rounding=ROUND_HALF_UP))
 
 
 def _array_index(label):
     s = str(label)
-    return int(s) if s.isdigit() and (s == "0" or s[0] != "0") and int(s) < 2 ** 31 else None
+    return int(s) if s.isascii() and s.isdigit() and (s == "0" or s[0] != "0") and int(s) <= 2 ** 32 - 2 else None      # V8's array indices end at 2^32 - 2
 
 
 def _keys(acc):
     """Object.keys order: array-index keys ascending, then the rest in insertion order."""
     ks = list(acc.keys())
+    for k in ks:
+        FOLD_ARMS["key.index" if _array_index(k) is not None else "key.string"] += 1
     idx = sorted((k for k in ks if _array_index(k) is not None), key=_array_index)
     return idx + [k for k in ks if _array_index(k) is None]
 
 
-def _add(acc, label, w):
+def _add(acc, label, w, arm="all"):
     v = acc.get(label)              # `if(!acc[label]) acc[label] = wconf; else acc[label] += wconf;` (absent / 0 / NaN: assign)
+    FOLD_ARMS[arm + (".absent" if v is None else ".zero" if v == 0 else ".nan" if v != v else ".added")] += 1
     if v is None or v == 0 or v != v:
         acc[label] = w
     else:
@@ -54,9 +75,48 @@ def _add(acc, label, w):
 
 
 def classify_multiple(prob_row, labels):
-    """ml5 classifyMultiple's per-input result: {label, confidence} sorted by confidence descending, ties in legend order."""
-    order = sorted(range(len(labels)), key=lambda c: -float(prob_row[c]))
-    return [(labels[c], float(prob_row[c])) for c in order]
+    """ml5 classifyMultiple's per-input result: {label, confidence} sorted by confidence descending (`b.confidence - a.confidence` under
+    V8's stable sort), ties in legend order.  A row that is NaN throughout (K6's output for a non-finite feature) stays in legend order:
+    every comparison answers NaN, which the sort reads as "not before" (recorded from ml5 itself in tests/golden/fold_expected.json,
+    ml5_order).  A row that mixes NaN and numbers has no specified order (an inconsistent comparator) and is refused."""
+    p = [float(v) for v in prob_row]
+    n_nan = sum(1 for v in p if v != v)
+    if n_nan:
+        if n_nan != len(p):
+            raise ValueError("a row that mixes NaN and finite confidences has no specified order")
+        FOLD_ARMS["rank_tie.all_nan"] += 1
+        return [(labels[c], p[c]) for c in range(len(labels))]
+    FOLD_ARMS["rank_tie.yes" if len(set(p)) < len(p) else "rank_tie.no"] += 1
+    order = sorted(range(len(labels)), key=lambda c: -p[c])
+    return [(labels[c], p[c]) for c in order]
+
+
+def fold_segment(acc_all, durs, probs, labels):
+    """nn_prediction's call_back_x4 (ref prediction.js:89-115) for one model DB: adds the callback's syllables to acc_all, returns
+    Label_conf_seg."""
+    acc_seg = {}
+    FOLD_ARMS["syllables.one" if len(durs) == 1 else "syllables.several"] += 1
+    for d, p in zip(durs, probs):
+        w = math.sqrt(d)
+        res = classify_multiple(p, labels)
+        for lab, conf in (res[:1] if len(durs) == 1 else res):
+            _add(acc_all, lab, conf * w, "all")
+            _add(acc_seg, lab, conf * w, "seg")
+    return acc_seg
+
+
+def segment_label(acc_all, acc_seg):
+    """The segment's label and maximum as seg_confidence_sort finds them (ref prediction.js:134-151): Label_conf_all's keys in
+    Object.keys order, strict > from 0 — so equal sums go to the earlier key."""
+    best, mx = None, 0.0
+    for k in _keys(acc_all):
+        if k in acc_seg and acc_seg[k] > mx:
+            mx, best = acc_seg[k], k
+        elif k in acc_seg and mx > 0 and acc_seg[k] == mx:
+            a, b = _array_index(best) is not None, _array_index(k) is not None
+            FOLD_ARMS["sum_tie.index_index" if a and b else "sum_tie.index_string" if a else "sum_tie.string_string"] += 1
+    FOLD_ARMS["label.null" if best is None else "label.found"] += 1
+    return best, mx
 
 
 def fold_clip(callbacks, labels):
@@ -68,20 +128,12 @@ def fold_clip(callbacks, labels):
         seg_weight = 0.0
         for d in durs:
             seg_weight += d
+        FOLD_ARMS["skip.positive" if seg_weight > 0 else "skip.zero"] += 1
         if not seg_weight > 0:
             out.append(("skip", 0.0))
             continue
-        acc_seg = {}
-        for d, p in zip(durs, probs):
-            w = math.sqrt(d)
-            res = classify_multiple(p, labels)
-            for lab, conf in (res[:1] if len(durs) == 1 else res):
-                _add(acc_all, lab, conf * w)
-                _add(acc_seg, lab, conf * w)
-        best, mx = None, 0.0
-        for k in _keys(acc_all):
-            if k in acc_seg and acc_seg[k] > mx:
-                mx, best = acc_seg[k], k
+        acc_seg = fold_segment(acc_all, durs, probs, labels)
+        best, mx = segment_label(acc_all, acc_seg)
         out.append((best, mx / seg_weight))
     return out, acc_all
 

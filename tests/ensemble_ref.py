@@ -2,11 +2,10 @@
 (classify_ref.fold_clip's arithmetic, one accumulator per DB) and the decision of seg_confidence_sort (lines 127-169) with the readout
 of plot_prediction_meters (lines 172-215).  Exact double arithmetic in the reference's order of operations, so K6b-e and the decision
 must equal it bit for bit when fed the same f32 probabilities."""
-import math
-
 from tests import classify_ref
 
 NAN = float("nan")
+ARMS = classify_ref.FOLD_ARMS                        # the arm counters of the fold's comparisons, shared with classify_ref
 
 
 class Launch:
@@ -27,22 +26,17 @@ class Launch:
         for d in durs:
             seg_weight += d
         skipped = not seg_weight > 0
+        ARMS["skip.zero" if skipped else "skip.positive"] += 1
         per_db, seg_max = [], []
         if not skipped:
             for di, labels in enumerate(self.legends):
-                acc_all, acc_seg = self.acc_all[di], {}
-                for d, p in zip(durs, probs[di]):
-                    w = math.sqrt(d)
-                    res = classify_ref.classify_multiple(p, labels)
-                    for lab, conf in (res[:1] if len(durs) == 1 else res):
-                        classify_ref._add(acc_all, lab, conf * w)
-                        classify_ref._add(acc_seg, lab, conf * w)
-                max_all, max_seg, lab_seg = 0.0, 0.0, None
-                for k in classify_ref._keys(acc_all):
+                acc_all = self.acc_all[di]
+                acc_seg = classify_ref.fold_segment(acc_all, durs, probs[di], labels)
+                lab_seg, max_seg = classify_ref.segment_label(acc_all, acc_seg)
+                max_all = 0.0
+                for k in acc_all:                   # (a maximum does not depend on the key order)
                     if acc_all[k] > max_all:
                         max_all = acc_all[k]
-                    if k in acc_seg and acc_seg[k] > max_seg:
-                        max_seg, lab_seg = acc_seg[k], k
                 self.db_all[di] = max_all
                 seg_max.append(max_seg)
                 per_db.append((lab_seg, max_seg / seg_weight, max_all))
@@ -50,16 +44,29 @@ class Launch:
             for di in range(len(self.legends)):
                 if seg_max[di] > best:
                     best, db, label = seg_max[di], di, per_db[di][0]
+                    ARMS["winner.replaced"] += 1
+                elif best > 0 and seg_max[di] == best:
+                    ARMS["winner.tie_kept"] += 1
                 if self.db_all[di] > self.max_inv_entropy:
                     self.max_inv_entropy, self.min_entropy_db = self.db_all[di], di
+                    ARMS["min_db.raised"] += 1
+                elif self.max_inv_entropy > 0 and self.db_all[di] == self.max_inv_entropy and di != self.min_entropy_db:
+                    ARMS["min_db.tie_kept"] += 1
+            if db is None:
+                ARMS["winner.none"] += 1
+            if self.min_entropy_db is None:
+                ARMS["min_db.none"] += 1
             conf = best / seg_weight
         else:
+            ARMS["min_db.skipped"] += 1
             per_db = [("skip", 0.0, self.db_all[di]) for di in range(len(self.legends))]
             db, label, conf = "skip", None, 0.0
         entropy, meters = NAN, []
         m = self.min_entropy_db
         if m is not None:
             keys = classify_ref._keys(self.acc_all[m])
+            in_legend_order = [k for k in self.legends[m] if k in self.acc_all[m]]
+            ARMS["all_sum.legend_order" if keys == in_legend_order else "all_sum.key_order_differs"] += 1
             total = 0
             for k in keys:
                 total += self.acc_all[m][k]

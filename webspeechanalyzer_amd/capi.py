@@ -1683,6 +1683,75 @@ def debug_regress_fold(meta, values, step_s, row_off, ctl=None, device=0, sentin
                 run_sum=sel(run[0]), run_weight=sel(run[1]), run_value=sel(run[2]))
 
 
+class _DebugFoldIO(ctypes.Structure):
+    """struct wsa_debug_fold_io of csrc/debug.hip"""
+    _M = 8                                            # WSA_ENSEMBLE_MAX
+    _vp, _u32, _i32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32
+    _fields_ = [("meta", _vp), ("row_off", _vp), ("ctl", _vp), ("step_s", ctypes.c_double),
+                ("n_rows", _u32), ("n", _u32), ("n_steps", _u32), ("cap", _u32), ("n_members", _u32), ("cb_cap", _u32), ("single", _i32), ("f64", _i32),
+                ("C", _u32 * _M), ("legend", _vp * _M), ("conf", _vp * _M),
+                ("n_cb", _vp), ("cb", _vp),
+                ("cb_label", _vp * _M), ("cb_conf", _vp * _M), ("cb_all_max", _vp * _M), ("run_conf", _vp * _M),
+                ("cb_db", _vp), ("cb_top_label", _vp), ("cb_top_conf", _vp), ("cb_min_db", _vp), ("cb_entropy", _vp), ("run_min_db", _vp),
+                ("h_cb", _vp), ("h_cb_label", _vp * _M), ("h_cb_conf", _vp * _M), ("h_cb_all_max", _vp * _M),
+                ("h_cb_db", _vp), ("h_cb_top_label", _vp), ("h_cb_top_conf", _vp), ("h_cb_min_db", _vp), ("h_cb_entropy", _vp)]
+
+
+def debug_class_fold(meta, row_off, step_s, legends, conf, single=False, f64=False, ctl=None, cap=0, cb_cap=None, device=0, sentinel=-7):
+    """Test access to the class fold K6b / K6b-e on its own (csrc/debug.hip wsa_debug_class_fold; not part of include/wsa.h): hand-built row
+    meta [n_rows, 8] i32, per member a legend (strings) and confidences conf[d] [n_rows, C_d] (sent as float32, or float64 with f64).
+    single: the one-model kernels (one member), else the group's.  ctl None: a batch, row_off [n + 1]; else streams, row_off
+    [n_steps, n + 1] counting from each step's first row, ctl [n_steps, n] control bytes and the D2H window `cap`.
+    Every output table starts as `sentinel` and comes back whole.  Returns a dict: n_cb (int, or [n_steps]); cb [K, 4]; cb_label / cb_conf /
+    cb_all_max [M][K]; run_conf [M] of [n, C_d] (streams: [n_steps, n, C_d]); cb_db, cb_top_label, cb_top_conf, cb_min_db, cb_entropy [K];
+    run_min_db [n] (streams: [n_steps, n]); streams also h_* [n_steps, max(cap, 1)] like the cb_* tables."""
+    L = lib()
+    L.wsa_debug_class_fold.argtypes = [ctypes.c_int32, ctypes.c_void_p]
+    L.wsa_debug_class_fold.restype = ctypes.c_int
+    meta = np.ascontiguousarray(meta, np.int32).reshape(-1, 8)
+    n_rows, M = len(meta), len(legends)
+    row_off = np.ascontiguousarray(row_off, np.uint32)
+    streams = ctl is not None
+    n_steps = row_off.shape[0] if streams else 0
+    n = row_off.shape[-1] - 1
+    ctl_a = np.ascontiguousarray(ctl, np.uint8) if streams else None
+    K = int(cb_cap) if cb_cap is not None else 2 * max(n_rows, 1) + 3          # room beyond the callbacks: the sentinel must survive there
+    tables, W = max(n_steps, 1), max(int(cap), 1)
+    confs = [np.ascontiguousarray(c, np.float64 if f64 else np.float32).reshape(n_rows, len(leg)) for c, leg in zip(conf, legends)]
+    io = _DebugFoldIO()
+    keep = [meta, row_off, ctl_a, confs]
+    io.meta, io.row_off, io.ctl, io.step_s = meta.ctypes.data, row_off.ctypes.data, ctl_a.ctypes.data if streams else None, float(step_s)
+    io.n_rows, io.n, io.n_steps, io.cap, io.n_members, io.cb_cap, io.single, io.f64 = n_rows, n, n_steps, int(cap), M, K, int(bool(single)), int(bool(f64))
+    sent_i = lambda *shape: np.full(shape, int(sentinel), np.int32)
+    sent_d = lambda *shape: np.full(shape, float(sentinel), np.float64)
+    out = dict(n_cb=np.zeros(tables, np.uint32), cb=sent_i(K, 4), cb_label=[sent_i(K) for _ in range(M)], cb_conf=[sent_d(K) for _ in range(M)],
+               cb_all_max=[sent_d(K) for _ in range(M)], run_conf=[sent_d(tables, n, len(leg)) for leg in legends],
+               cb_db=sent_i(K), cb_top_label=sent_i(K), cb_top_conf=sent_d(K), cb_min_db=sent_i(K), cb_entropy=sent_d(K), run_min_db=sent_i(tables, n),
+               h_cb=sent_i(n_steps, W, 4), h_cb_label=[sent_i(n_steps, W) for _ in range(M)], h_cb_conf=[sent_d(n_steps, W) for _ in range(M)],
+               h_cb_all_max=[sent_d(n_steps, W) for _ in range(M)], h_cb_db=sent_i(n_steps, W), h_cb_top_label=sent_i(n_steps, W),
+               h_cb_top_conf=sent_d(n_steps, W), h_cb_min_db=sent_i(n_steps, W), h_cb_entropy=sent_d(n_steps, W))
+    for d in range(min(M, _DebugFoldIO._M)):          # (more members than the struct holds: n_members says so, the entry refuses)
+        strs = [str(s).encode() for s in legends[d]]
+        arr = (ctypes.c_char_p * len(strs))(*strs)
+        keep += [strs, arr]
+        io.C[d], io.legend[d], io.conf[d] = len(strs), ctypes.cast(arr, ctypes.c_void_p).value, confs[d].ctypes.data
+    for name, v in out.items():
+        if isinstance(v, list):
+            for d in range(min(M, _DebugFoldIO._M)):
+                getattr(io, name)[d] = v[d].ctypes.data
+        else:
+            setattr(io, name, v.ctypes.data)
+    rc = L.wsa_debug_class_fold(device, ctypes.addressof(io))
+    if rc != 0:
+        raise WsaError(f"wsa_debug_class_fold: status {rc}")
+    del keep
+    if not streams:
+        out["n_cb"] = int(out["n_cb"][0])
+        out["run_conf"] = [r[0] for r in out["run_conf"]]
+        out["run_min_db"] = out["run_min_db"][0]
+    return out
+
+
 def debug_knn_split(store, d_feat, n_rows, k, slices, d_label, d_conf, d_nbr, d_sim, stream=0):
     """Test access to K9s on its own (csrc/knn.hip wsa_debug_knn_split; not part of include/wsa.h): the split-store kernels over n_rows dense
     device rows with a forced slice count (0: the rule's), outputs as KnnStore.classify_rows.  Only enqueues (its scratch table stays with

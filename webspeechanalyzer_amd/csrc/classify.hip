@@ -160,18 +160,19 @@ __global__ void __launch_bounds__(CLS_THREADS) classify_group_kernel(const ClsGr
     }
 }
 
-bool array_index_key(const char* s, int32_t* out) {       // "0", "17" (no sign, no leading zero) below 2^31: an array index for Object.keys
-    if (!s || !*s) return false;
-    if (s[0] == '0' && s[1]) return false;
-    long long v = 0;
-    for (const char* c = s; *c; c++) { if (*c < '0' || *c > '9') return false; v = v * 10 + (*c - '0'); if (v > 0x7fffffff) return false; }
-    *out = (int32_t)v;
-    return true;
-}
-
 }  // namespace
 
 namespace wsa_classify {
+
+// V8 orders a key as an array index up to 2^32 - 2 ("4294967294"); "4294967295" and beyond are string keys
+bool array_index_key(const char* s, int64_t* out) {
+    if (!s || !*s) return false;
+    if (s[0] == '0' && s[1]) return false;
+    int64_t v = 0;
+    for (const char* c = s; *c; c++) { if (*c < '0' || *c > '9') return false; v = v * 10 + (*c - '0'); if (v > 0xfffffffell) return false; }
+    *out = v;
+    return true;
+}
 
 ClsParams cls_params(const wsa_model* m, const double* feat, uint32_t n_rows, const uint32_t* d_n_rows, float* prob) {
     ClsParams p{};
@@ -276,8 +277,8 @@ wsa_status wsa_model_create(wsa_ctx* ctx, const wsa_model_desc* d, wsa_model** o
         ok = m->mem.upload(&dw, w) && m->mem.upload(&db, bb);
         m->L[l] = ClsLayer{dw, db, kp, np, N, d->activation[l]};
     }
-    std::vector<int32_t> kr(m->C, -1);
-    if (d->labels) for (int c = 0; c < m->C; c++) { int32_t v; if (array_index_key(d->labels[c], &v)) kr[c] = v; }
+    std::vector<int64_t> kr(m->C, -1);
+    if (d->labels) for (int c = 0; c < m->C; c++) { int64_t v; if (array_index_key(d->labels[c], &v)) kr[c] = v; }
     ok = ok && m->mem.alloc(&m->d_min, (size_t)nin) && m->mem.alloc(&m->d_max, (size_t)nin) && m->mem.upload(&m->d_key_rank, kr)
          && hipMemcpy(m->d_min, d->in_min, (size_t)nin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
          && hipMemcpy(m->d_max, d->in_max, (size_t)nin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;

@@ -47,14 +47,7 @@ void wsa_ecls_free(wsa_ecls* c) { free_on_device(c); }
 
 namespace {
 
-// ---- K6b-e: the fold for every member of an ensemble, one wave per (clip, member)
-struct FoldGroupParams {
-    uint32_t n_clips, n_members; double step_s;
-    const int32_t* meta; const uint32_t* row_off; const FoldMember* tab;
-    int32_t* t_n; int32_t* t_local; uint32_t* clip_cb;                                       // shared by the members
-    EnsTables t;                                                                             // the decision per row (callback starts); cb unused
-};
-
+// ---- K6b-e: the fold for every member of an ensemble, one wave per (clip, member) (FoldGroupParams, classify_internal.hpp)
 // One workgroup per clip, one wave per member: the waves walk the clip's callbacks in step (the rows and so the trip counts are the same
 // for all of them), leave each callback's three figures in LDS, and after one barrier every thread holds the decision — so the running
 // max_inv_entropy / min_entropy_db, a chain over the clip's callbacks, costs nothing beyond the fold's own walk.  Two LDS sets by callback
@@ -67,7 +60,7 @@ __global__ void __launch_bounds__(64 * WSA_ENSEMBLE_MAX) fold_group_kernel(FoldG
     const FoldMember m = p.tab[d];
     const uint32_t r0 = p.row_off[clip], r1 = p.row_off[clip + 1];
     const bool cls = (uint32_t)lane < m.C;
-    const int kr = cls ? m.key_rank[lane] : -1;
+    const long long kr = cls ? (long long)m.key_rank[lane] : -1;
     FoldAcc a{0.0, false, 0, 0};
     uint32_t ncb = 0;
     double max_inv = 0.0; int min_db = -1;
@@ -125,6 +118,31 @@ __global__ void __launch_bounds__(1024) fold_compact_group_kernel(uint32_t n_cli
     if (tid == 0) host[0] = n_cb;
 }
 
+}  // namespace
+
+// ---- the folds' launches (classify_internal.hpp): four clips per workgroup of K6b, one workgroup per clip of K6b-e, one workgroup of 1024 for
+// either compaction
+namespace wsa_classify {
+
+template <typename P>
+void launch_fold(const FoldParams<P>& f, uint32_t* cb_off, int32_t* cb, int32_t* cb_label, double* cb_conf, uint32_t* host, hipStream_t s) {
+    if (f.n_clips) hipLaunchKernelGGL(fold_kernel<P>, dim3((f.n_clips + 3) / 4), dim3(256), 0, s, f);
+    hipLaunchKernelGGL(fold_compact_kernel, dim3(1), dim3(1024), 0, s, f.n_clips, f.row_off, f.meta, f.clip_cb, cb_off,
+                       f.t_label, f.t_conf, f.t_n, f.t_local, cb, cb_label, cb_conf, host);
+}
+template void launch_fold<float>(const FoldParams<float>&, uint32_t*, int32_t*, int32_t*, double*, uint32_t*, hipStream_t);
+template void launch_fold<double>(const FoldParams<double>&, uint32_t*, int32_t*, int32_t*, double*, uint32_t*, hipStream_t);
+
+void launch_fold_group(const FoldGroupParams& f, uint32_t* cb_off, const EnsTables& o, uint32_t* host, hipStream_t s) {
+    if (f.n_clips) hipLaunchKernelGGL(fold_group_kernel, dim3(f.n_clips), dim3(64 * f.n_members), 0, s, f);
+    hipLaunchKernelGGL(fold_compact_group_kernel, dim3(1), dim3(1024), 0, s, f.n_clips, f.n_members, f.row_off, f.meta, f.clip_cb, cb_off,
+                       f.t_n, f.t_local, f.tab, f.t, o, host);
+}
+
+}  // namespace wsa_classify
+
+namespace {
+
 // ---- the host side
 // the rows a batch hands K6: the row table (levels 5 and 13; level 12 at its stride of WSA_NFEAT, slots 0 .. 22, slot 23 the throw mark)
 // or the utterance table (level 11); both counts sit on the device
@@ -162,9 +180,7 @@ wsa_status enqueue_batch(const wsa_batch_view& v, wsa_cls* c, const wsa_model* m
         f.meta = v.d_meta; f.row_off = v.d_row_off; f.prob = c->d_prob; f.key_rank = m->d_key_rank;
         f.t_label = c->d_t_label; f.t_conf = c->d_t_conf; f.t_n = c->d_t_n; f.t_local = c->d_t_local;
         f.clip_cb = c->d_clip_cb; f.clip_conf = c->d_clip_conf;
-        if (v.n_clips) hipLaunchKernelGGL(fold_kernel<float>, dim3((v.n_clips + 3) / 4), dim3(256), 0, s, f);
-        hipLaunchKernelGGL(fold_compact_kernel, dim3(1), dim3(1024), 0, s, v.n_clips, v.d_row_off, v.d_meta, c->d_clip_cb, c->d_cb_off,
-                           c->d_t_label, c->d_t_conf, c->d_t_n, c->d_t_local, c->d_cb, c->d_cb_label, c->d_cb_conf, c->h_count_dev);
+        launch_fold(f, c->d_cb_off, c->d_cb, c->d_cb_label, c->d_cb_conf, c->h_count_dev, s);
         HIP_TRY(ctx, hipGetLastError());
     }
     return WSA_OK;
@@ -208,9 +224,7 @@ wsa_status enqueue_batch_ensemble(const wsa_batch_view& v, wsa_ecls* c, hipStrea
         FoldGroupParams f{};
         f.n_clips = v.n_clips; f.n_members = c->n; f.step_s = ctx->cfg.window_step / 1e3;
         f.meta = v.d_meta; f.row_off = v.d_row_off; f.tab = c->d_ftab; f.t_n = c->d_t_n; f.t_local = c->d_t_local; f.clip_cb = c->d_clip_cb; f.t = c->t;
-        if (v.n_clips) hipLaunchKernelGGL(fold_group_kernel, dim3(v.n_clips), dim3(64 * c->n), 0, s, f);
-        hipLaunchKernelGGL(fold_compact_group_kernel, dim3(1), dim3(1024), 0, s, v.n_clips, c->n, v.d_row_off, v.d_meta, c->d_clip_cb, c->d_cb_off,
-                           c->d_t_n, c->d_t_local, c->d_ftab, c->t, c->o, c->h_count_dev);
+        launch_fold_group(f, c->d_cb_off, c->o, c->h_count_dev, s);
         HIP_TRY(ctx, hipGetLastError());
     }
     return WSA_OK;

@@ -6,8 +6,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "classify_internal.hpp"
 
 namespace {
+using namespace wsa_classify;
 
 // parseFloat(x.toFixed(3)): k = the integer nearest to 1000 x (the exact binary value; the larger on a tie), then k / 1000 (correctly
 // rounded, = parseFloat of the decimal string).  k is right iff k - 0.5 <= 1000 x < k + 0.5; the sign of fma(x, 1000, -(k -+ 0.5)) is
@@ -66,10 +68,7 @@ struct FoldAcc {
     long long stamp;
 };
 
-// A stream's fold lives in device memory from step to step: [n][C], [n][C], [n][C], [n].  It starts from nothing when the step's control
-// word has START (bit 0: the step's rows belong to the new launch).
-struct CarriedFold { double* acc_all; int32_t* in_all; long long* first; long long* stamp; };
-
+// (a stream's fold between steps: CarriedFold, classify_internal.hpp)
 __device__ __forceinline__ FoldAcc load_fold(const CarriedFold& c, uint32_t s, size_t sc, bool cls, bool start) {
     FoldAcc a{0.0, false, 0, 0};
     if (!start) {
@@ -86,7 +85,7 @@ __device__ __forceinline__ void store_fold(const CarriedFold& c, uint32_t s, siz
 // one callback: rows r .. e - 1 (the same clip / stream and si); label -1 / -2 as wsa_class_result.  P is the type the confidences
 // arrive in: float for a network's probabilities (K6), double for KNN's votes / k_eff (K9, specification KN-2); the sums are double.
 template <typename P>
-__device__ __forceinline__ void fold_callback(const int32_t* meta, const P* prob, uint32_t C, double step_s, int lane, bool cls, int kr,
+__device__ __forceinline__ void fold_callback(const int32_t* meta, const P* prob, uint32_t C, double step_s, int lane, bool cls, long long kr,
                                               uint32_t r, uint32_t e, FoldAcc& a, int& label, double& conf, double& seg_max) {
     const uint32_t nsyl = e - r;
     double seg_weight = 0.0;                 // sum of parseFloat(seg_time[ph][1]) (ref prediction.js:55)
@@ -97,11 +96,13 @@ __device__ __forceinline__ void fold_callback(const int32_t* meta, const P* prob
     for (uint32_t q = r; q < e; q++) {
         const double w = __dsqrt_rn(fixed3((double)(meta[(size_t)q * 8 + 3] + 1) * step_s));
         const P pf = cls ? prob[(size_t)q * C + lane] : P(0);
-        // rank in classifyMultiple's order: confidence descending, ties in legend order (a stable sort)
+        // rank in classifyMultiple's order: confidence descending, ties in legend order (a stable sort).  A row that is NaN throughout (K6's
+        // answer to a non-finite feature) stays in legend order: ml5's comparator `b - a` answers NaN, which the sort reads as "not before",
+        // so a NaN ranks behind the NaNs in front of it.  (A row that mixes NaN and numbers has no specified order; K6 produces none.)
         int rank = 0;
         for (int j = 0; j < (int)C; j++) {
             const P pj = __shfl(pf, j);
-            rank += (pj > pf || (pj == pf && j < lane)) ? 1 : 0;
+            rank += (pj > pf || ((pj == pf || (pj != pj && pf != pf)) && j < lane)) ? 1 : 0;
         }
         const bool add = cls && (nsyl > 1 || rank == 0);   // one syllable: only result_out[0] (the one-input quirk)
         if (add) {
@@ -116,7 +117,7 @@ __device__ __forceinline__ void fold_callback(const int32_t* meta, const P* prob
     // segment label: keys of Label_conf_all in Object.keys order, the first whose segment sum exceeds the running maximum (from 0)
     const double v = (in_seg && acc_seg > 0.0) ? acc_seg : 0.0;
     const double mx = wave_max_d(v);
-    const long long key = (kr >= 0) ? (long long)kr : ((1ll << 40) + a.first);
+    const long long key = (kr >= 0) ? kr : ((1ll << 40) + a.first);
     const long long best = wave_min_ll((in_seg && a.in_all && v == mx && mx > 0.0) ? key : 0x7fffffffffffffffll);
     if (mx > 0.0) {
         const unsigned long long hit = __ballot(cls && in_seg && a.in_all && v == mx && key == best);
@@ -129,23 +130,13 @@ __device__ __forceinline__ void fold_callback(const int32_t* meta, const P* prob
 // ---- K6b on a batch: one wave per clip, classes on lanes, callbacks walked in order (ref prediction.js:86-169 with one model DB); P as
 // for fold_callback
 template <typename P>
-struct FoldParams {
-    uint32_t n_clips, C; double step_s;
-    const int32_t* meta; const uint32_t* row_off; const P* prob;
-    const int32_t* key_rank;                 // [C] array-index value of the label, or -1
-    int32_t* t_label; double* t_conf; int32_t* t_n; int32_t* t_local;   // per row: the callback that starts there (t_n = 0 elsewhere)
-    uint32_t* clip_cb;                       // [n_clips] callbacks per clip
-    double* clip_conf;                       // [n_clips][C]
-};
-
-template <typename P>
 __global__ void __launch_bounds__(256) fold_kernel(FoldParams<P> p) {
     const int lane = threadIdx.x & 63;
     const uint32_t clip = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (clip >= p.n_clips) return;
     const uint32_t r0 = p.row_off[clip], r1 = p.row_off[clip + 1];
     const bool cls = (uint32_t)lane < p.C;
-    const int kr = cls ? p.key_rank[lane] : -1;
+    const long long kr = cls ? (long long)p.key_rank[lane] : -1;
     FoldAcc a{0.0, false, 0, 0};
     uint32_t ncb = 0;
     for (uint32_t r = r0; r < r1;) {
@@ -208,13 +199,8 @@ __global__ void __launch_bounds__(1024) fold_compact_kernel(uint32_t n_clips, co
 
 // ---- the same fold on a stream step: one wave per stream with the stream's carried fold.  Callbacks are written straight to their place
 // in the step's table (callback_starts); callbacks and the per-stream sums also go to the mapped pinned tables (callbacks below `cap`).
-struct StepFoldTables {
-    uint32_t cap;
-    int32_t* cb; int32_t* cb_label; double* cb_conf;                               // device: every callback of the step
-    int32_t* h_cb; int32_t* h_cb_label; double* h_cb_conf; double* h_conf; uint32_t* h_count;   // mapped pinned
-};
 template <typename P>
-__device__ __forceinline__ void fold_stream_step(const int32_t* meta, const P* prob, uint32_t C, double step_s, int lane, int kr, uint32_t s, uint32_t n,
+__device__ __forceinline__ void fold_stream_step(const int32_t* meta, const P* prob, uint32_t C, double step_s, int lane, long long kr, uint32_t s, uint32_t n,
                                                  uint32_t r0, uint32_t r1, const CarriedFold& carried, bool start, const StepFoldTables& t) {
     const bool cls = (uint32_t)lane < C;
     const size_t sc = (size_t)s * C + lane;
@@ -245,10 +231,10 @@ __device__ __forceinline__ void fold_stream_step(const int32_t* meta, const P* p
 // leaves what seg_confidence_sort derives from each member's tables: DB_entropies_seg (the segment maximum), DB_entropies_all (the maximum
 // of Label_conf_all, strict > from 0 in key order — a maximum does not depend on the order) and the sum plot_prediction_meters forms over
 // Label_conf_all in Object.keys order (ref prediction.js:182-184).
-__device__ __forceinline__ void all_max_and_sum(const FoldAcc& a, uint32_t C, int lane, bool cls, int kr, double& all_max, double& all_sum) {
+__device__ __forceinline__ void all_max_and_sum(const FoldAcc& a, uint32_t C, int lane, bool cls, long long kr, double& all_max, double& all_sum) {
     const bool in = cls && a.in_all;
     all_max = wave_max_d((in && a.acc_all > 0.0) ? a.acc_all : 0.0);
-    const long long key = (kr >= 0) ? (long long)kr : ((1ll << 40) + a.first);
+    const long long key = (kr >= 0) ? kr : ((1ll << 40) + a.first);
     int rank = 0;                                                  // place among the keys in Object.keys order
     for (int j = 0; j < (int)C; j++) {
         const long long kj = __shfl(key, j);
@@ -289,8 +275,10 @@ __device__ __forceinline__ double ensemble_min_db(const F& of, uint32_t n_member
             const double am = of(d).all_max;
             if (am > max_inv) { max_inv = am; min_db = (int)d; }
         }
-    if (min_db < 0) return __longlong_as_double(0x7ff8000000000000ll);
-    return 1.0 - of(min_db).all_max / of(min_db).all_sum;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    if (min_db < 0) return nan;
+    const double e = 1.0 - of(min_db).all_max / of(min_db).all_sum;
+    return e == e ? e : nan;                 // JavaScript has one NaN ("Entropy: NaN" once a sum is NaN): one bit pattern here, whatever the subtraction leaves
 }
 
 }  // namespace

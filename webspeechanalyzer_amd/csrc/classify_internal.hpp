@@ -25,7 +25,7 @@ struct ClsGroupEntry { ClsParams p; int rb; };   // one member of K6e's work lis
 // one member of an ensemble's fold (K6b-e), one wave per (clip, member) or (stream, member).  In a stream step the t_* tables are indexed
 // by callback, not by row
 struct FoldMember {
-    uint32_t C; const float* prob; const int32_t* key_rank;
+    uint32_t C; const float* prob; const int64_t* key_rank;
     int32_t* t_label; double* t_conf; double* t_all_max;                                     // per row: the callback that starts there
     double* t_seg; double* t_all_sum;                                                        // (stream steps only: batches keep these two in LDS)
     double* clip_conf;                                                                       // [n_clips][C]
@@ -35,6 +35,75 @@ struct FoldMember {
 struct EnsTables {
     int32_t* cb; int32_t* cb_db; int32_t* cb_top_label; double* cb_top_conf; int32_t* cb_min_db; double* cb_entropy; int32_t* clip_min_db;
 };
+
+// ---- the folds' kernel parameters (the kernels: classify_fold.hpp, classify_batch.hip, classify_stream.hip, knn_fold.hip)
+// K6b on a batch: one wave per clip.  P is the type the confidences arrive in (float: K6's probabilities, double: K9's votes / k_eff)
+template <typename P>
+struct FoldParams {
+    uint32_t n_clips, C; double step_s;
+    const int32_t* meta; const uint32_t* row_off; const P* prob;
+    const int64_t* key_rank;                 // [C] array-index value of the label (0 .. 2^32 - 2), or -1
+    int32_t* t_label; double* t_conf; int32_t* t_n; int32_t* t_local;   // per row: the callback that starts there (t_n = 0 elsewhere)
+    uint32_t* clip_cb;                       // [n_clips] callbacks per clip
+    double* clip_conf;                       // [n_clips][C]
+};
+// K6b-e on a batch: one wave per (clip, member)
+struct FoldGroupParams {
+    uint32_t n_clips, n_members; double step_s;
+    const int32_t* meta; const uint32_t* row_off; const FoldMember* tab;
+    int32_t* t_n; int32_t* t_local; uint32_t* clip_cb;                                       // shared by the members
+    EnsTables t;                                                                             // the decision per row (callback starts); cb unused
+};
+// A stream's fold lives in device memory from step to step: [n][C], [n][C], [n][C], [n].  It starts from nothing when the step's control
+// word has START (bit 0: the step's rows belong to the new launch).
+struct CarriedFold { double* acc_all; int32_t* in_all; long long* first; long long* stamp; };
+// a stream step's callback tables: on the device every callback of the step, in mapped pinned memory those below `cap`
+struct StepFoldTables {
+    uint32_t cap;
+    int32_t* cb; int32_t* cb_label; double* cb_conf;                               // device: every callback of the step
+    int32_t* h_cb; int32_t* h_cb_label; double* h_cb_conf; double* h_conf; uint32_t* h_count;   // mapped pinned
+};
+struct StreamClsParams {
+    uint32_t n, C; int fold; double step_s;
+    const int32_t* meta; const uint32_t* row_off; const float* prob; const int64_t* key_rank; const uint32_t* bits;
+    CarriedFold carried;
+    StepFoldTables t;
+    float* h_prob;                                                                 // mapped pinned
+};
+struct StreamKnnParams {
+    uint32_t n, C, k; int fold; double step_s;
+    const int32_t* meta; const uint32_t* row_off; const uint32_t* bits; const int64_t* key_rank;
+    const int32_t* label; const double* conf; const int32_t* nbr; const float* sim;       // K9s' tables of the step
+    CarriedFold carried;
+    StepFoldTables t;
+    int32_t* h_label; double* h_conf; int32_t* h_nbr; float* h_sim;                       // mapped pinned
+};
+struct StreamMember {
+    CarriedFold carried;
+    float* h_prob; int32_t* h_cb_label; double* h_cb_conf; double* h_cb_all_max; double* h_conf;   // mapped pinned
+};
+struct StreamEnsParams {
+    uint32_t n, n_members, cap; int fold; double step_s;
+    const int32_t* meta; const uint32_t* row_off; const uint32_t* bits;
+    const FoldMember* tab; const StreamMember* stab;
+    EnsTables o, h;                                                                           // device / mapped pinned (clip_min_db: per stream)
+    double* max_inv; int32_t* min_db;                                                         // carried per stream
+    uint32_t* h_count;
+};
+
+// ---- the folds' launches, with the product's geometry; the drivers and the test entry wsa_debug_class_fold (debug.hip) both go through these
+// K6b and its compaction (classify_batch.hip; P = float and double): cb_off [n_clips] scratch, cb [.][4], cb_label, cb_conf per callback,
+// host: the callback count
+template <typename P>
+void launch_fold(const FoldParams<P>& f, uint32_t* cb_off, int32_t* cb, int32_t* cb_label, double* cb_conf, uint32_t* host, hipStream_t s);
+// K6b-e and its compaction with the decision (classify_batch.hip): t the per-row decision (f.t), o the per-callback tables
+void launch_fold_group(const FoldGroupParams& f, uint32_t* cb_off, const EnsTables& o, uint32_t* host, hipStream_t s);
+// the stream step's push / fold kernels (classify_stream.hip, knn_fold.hip)
+void launch_stream_classes(const StreamClsParams& p, hipStream_t s);
+void launch_stream_knn(const StreamKnnParams& p, hipStream_t s);
+void launch_stream_ensemble(const StreamEnsParams& p, hipStream_t s);
+// "0", "17" (no sign, no leading zero) up to 2^32 - 2: an array index for Object.keys (classify.hip)
+bool array_index_key(const char* s, int64_t* out);
 
 // ---- the launches (classify.hip)
 ClsParams cls_params(const wsa_model* m, const double* feat, uint32_t n_rows, const uint32_t* d_n_rows, float* prob);
@@ -128,7 +197,7 @@ struct wsa_model {
     int n_layers = 0, C = 0, S = 0, rb = 0, nin = 0;      // nin = units[0], the row width of the level the model was trained at
     wsa_classify::ClsLayer L[WSA_MODEL_MAX_LAYERS] = {};
     double *d_min = nullptr, *d_max = nullptr;
-    int32_t* d_key_rank = nullptr;
+    int64_t* d_key_rank = nullptr;
     bool softmax = false;
     wsa::DevArena mem;
 };

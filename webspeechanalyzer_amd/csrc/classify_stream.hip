@@ -14,13 +14,7 @@ namespace {
 
 // ---- K6b on a stream step: one wave per stream pushes its rows' probabilities to the mapped pinned table (rows below the D2H window)
 // and, at level 13, folds them with the stream's carried fold (fold_stream_step, classify_fold.hpp).
-struct StreamClsParams {
-    uint32_t n, C; int fold; double step_s;
-    const int32_t* meta; const uint32_t* row_off; const float* prob; const int32_t* key_rank; const uint32_t* bits;
-    CarriedFold carried;
-    StepFoldTables t;
-    float* h_prob;                                                                 // mapped pinned
-};
+// (StreamClsParams, classify_internal.hpp)
 
 // the probabilities of rows r0 .. r1 - 1 below `cap` (the D2H window), C per row, to the pinned table
 __device__ __forceinline__ void push_prob(float* h_prob, const float* prob, uint32_t r0, uint32_t r1, uint32_t cap, uint32_t C, int lane) {
@@ -35,7 +29,7 @@ __global__ void __launch_bounds__(256) stream_classes_kernel(StreamClsParams p) 
     const uint32_t r0 = p.row_off[s], r1 = p.row_off[s + 1];
     push_prob(p.h_prob, p.prob, r0, r1, p.t.cap, p.C, lane);
     if (!p.fold) return;
-    fold_stream_step(p.meta, p.prob, p.C, p.step_s, lane, (uint32_t)lane < p.C ? p.key_rank[lane] : -1, s, p.n, r0, r1, p.carried, p.bits[s] & 1u, p.t);
+    fold_stream_step(p.meta, p.prob, p.C, p.step_s, lane, (uint32_t)lane < p.C ? (long long)p.key_rank[lane] : -1, s, p.n, r0, r1, p.carried, p.bits[s] & 1u, p.t);
 }
 
 // ---- K6b-e on a stream step: one wave per (stream, member) folds with that pair's carried accumulator and writes the member's entries
@@ -43,18 +37,7 @@ __global__ void __launch_bounds__(256) stream_classes_kernel(StreamClsParams p) 
 // lanes, min_entropy_db by lane 0 in callback order with the stream's running max_inv_entropy / min_entropy_db carried on the device and
 // reset by START (ref reset_predictions(true), prediction.js:24-36; the device also forgets min_entropy_db, see wsa.h).  In a step the
 // members' tables (FoldMember t_*) are indexed by callback, not by row.
-struct StreamMember {
-    CarriedFold carried;
-    float* h_prob; int32_t* h_cb_label; double* h_cb_conf; double* h_cb_all_max; double* h_conf;   // mapped pinned
-};
-struct StreamEnsParams {
-    uint32_t n, n_members, cap; int fold; double step_s;
-    const int32_t* meta; const uint32_t* row_off; const uint32_t* bits;
-    const FoldMember* tab; const StreamMember* stab;
-    EnsTables o, h;                                                                           // device / mapped pinned (clip_min_db: per stream)
-    double* max_inv; int32_t* min_db;                                                         // carried per stream
-    uint32_t* h_count;
-};
+// (StreamMember, StreamEnsParams: classify_internal.hpp)
 
 __global__ void __launch_bounds__(256) stream_fold_group_kernel(StreamEnsParams p) {
     const int lane = threadIdx.x & 63;
@@ -67,7 +50,7 @@ __global__ void __launch_bounds__(256) stream_fold_group_kernel(StreamEnsParams 
     push_prob(sm.h_prob, m.prob, r0, r1, p.cap, m.C, lane);
     if (!p.fold) return;
     const bool cls = (uint32_t)lane < m.C;
-    const int kr = cls ? m.key_rank[lane] : -1;
+    const long long kr = cls ? (long long)m.key_rank[lane] : -1;
     const size_t sc = (size_t)s * m.C + lane;
     FoldAcc a = load_fold(sm.carried, s, sc, cls, p.bits[s] & 1u);
     uint32_t k = callback_starts(p.meta, 0, r0, lane);
@@ -131,6 +114,20 @@ bool alloc_carried(wsa::DevArena& A, CarriedFold& f, size_t n, size_t C) {
 
 }  // namespace
 
+// ---- the step's fold launches (classify_internal.hpp): four streams, or four (stream, member) pairs, per workgroup
+namespace wsa_classify {
+
+void launch_stream_classes(const StreamClsParams& p, hipStream_t s) {
+    hipLaunchKernelGGL(stream_classes_kernel, dim3((p.n + 3) / 4), dim3(256), 0, s, p);
+}
+void launch_stream_ensemble(const StreamEnsParams& p, hipStream_t s) {
+    const uint32_t waves = p.n * p.n_members;
+    hipLaunchKernelGGL(stream_fold_group_kernel, dim3((waves + 3) / 4), dim3(256), 0, s, p);
+    if (p.fold) hipLaunchKernelGGL(stream_decide_kernel, dim3((p.n + 3) / 4), dim3(256), 0, s, p);
+}
+
+}  // namespace wsa_classify
+
 // ---- streams (wsa_stream_set_model): K6 on every step's rows, the carried fold at level 13; everything allocated at attach time
 struct wsa_scls {
     int device = 0;
@@ -185,7 +182,7 @@ wsa_status wsa_scls_enqueue(wsa_scls* c, hipStream_t s) {
     p.carried = c->carried;
     p.t = StepFoldTables{v.d2h_rows, c->d_cb, c->d_cb_label, c->d_cb_conf, c->h_cb_dev, c->h_cb_label_dev, c->h_cb_conf_dev, c->h_conf_dev, c->h_count_dev};
     p.h_prob = c->h_prob_dev;
-    hipLaunchKernelGGL(stream_classes_kernel, dim3((v.n_streams + 3) / 4), dim3(256), 0, s, p);
+    launch_stream_classes(p, s);
     HIP_TRY(v.ctx, hipGetLastError());
     return WSA_OK;
 }
@@ -291,9 +288,7 @@ wsa_status wsa_sens_enqueue(wsa_sens* c, hipStream_t s) {
     p.n = v.n_streams; p.n_members = c->n; p.cap = v.d2h_rows; p.fold = v.level == 13 ? 1 : 0; p.step_s = v.ctx->cfg.window_step / 1e3;
     p.meta = v.d_meta; p.row_off = v.d_row_off; p.bits = v.d_bits; p.tab = c->d_ftab; p.stab = c->d_stab;
     p.o = c->o; p.h = c->h_dev; p.max_inv = c->d_max_inv; p.min_db = c->d_min_db; p.h_count = c->h_count_dev;
-    const uint32_t waves = v.n_streams * c->n;
-    hipLaunchKernelGGL(stream_fold_group_kernel, dim3((waves + 3) / 4), dim3(256), 0, s, p);
-    if (p.fold) hipLaunchKernelGGL(stream_decide_kernel, dim3((v.n_streams + 3) / 4), dim3(256), 0, s, p);
+    launch_stream_ensemble(p, s);
     HIP_TRY(v.ctx, hipGetLastError());
     return WSA_OK;
 }

@@ -1,6 +1,6 @@
 // debug.hip — test entries of libwsa that are NOT part of include/wsa.h: unit access to device-side pieces that the public
 // entry points only exercise through their consequences (tests/test_gpu_units.py, tests/test_gpu_coeffs.py, tests/test_gpu_utterance.py, tests/test_gpu_gate.py,
-// tests/test_gpu_regress_group.py).
+// tests/test_gpu_regress_group.py, tests/test_gpu_fold.py).
 #include <cstring>
 #include <vector>
 #include "host_plan.hpp"
@@ -10,6 +10,7 @@
 #include "tracker_score.hpp"
 #include "tracker_features.hpp"
 #include "regress_internal.hpp"
+#include "classify_internal.hpp"
 
 namespace wsa {
 // fn 0: jsm::log10(x[i]); fn 1: jsm::pow_pos(x[i], y[i]) — the V8 Math.log10 / Math.pow ports the noise gate's
@@ -574,5 +575,243 @@ extern "C" int wsa_debug_gate(int32_t device, int32_t variant, const uint32_t* s
             fed[i] += nf[i];
         }
     }
+    return ok ? WSA_OK : WSA_ERR_HIP;
+}
+
+// K6b / K6b-e (csrc/classify_fold.hpp) on their own: hand-built row meta [n_rows][8] i32 (slot 0 the clip or stream, 1 si, 3 t_len) and, per member
+// d of n_members, a legend of C[d] strings and confidences conf[d] [n_rows][C[d]] (float, or double with f64 set) straight into the product's fold
+// launches (classify_internal.hpp launch_*); no audio, no model.  key_rank comes from the legend through array_index_key.
+//   n_steps == 0, a batch of n clips, row_off [n + 1]: single set (one member) runs fold_kernel<float / double> + fold_compact_kernel, else
+//   fold_group_kernel + fold_compact_group_kernel (float only).  Out: n_cb [1]; cb [cb_cap][4]; per member cb_label, cb_conf [cb_cap], run_conf
+//   [n][C[d]]; for the group also cb_all_max per member, cb_db, cb_top_label, cb_top_conf, cb_min_db, cb_entropy [cb_cap] and run_min_db [n].
+//   n_steps > 0, n streams: tables, row_off [n_steps][n + 1] and ctl [n_steps][n] as wsa_debug_regress_fold; one launch_stream_classes /
+//   launch_stream_knn (single) or launch_stream_ensemble per step, the carried folds (and the group's max_inv / min_db) zeroed at entry and kept
+//   on the device between steps.  Out: n_cb [n_steps]; the steps' callbacks one after the other in the cb* tables; run_conf [n_steps][n][C[d]] and
+//   run_min_db [n_steps][n] as each step leaves them; h_* [n_steps][max(cap, 1)]: what the step wrote to its D2H window of `cap` callbacks
+//   (plain device buffers here).
+// Every output table goes to the device as the caller filled it and comes back whole: a slot no callback fills keeps the caller's value.
+// Refused, nothing run and nothing written: whatever would make a kernel read or write outside these tables — offsets out of order, a row filed
+// under another clip, a negative si, t_len negative or INT32_MAX, more callbacks than cb_cap, a stream's callback whose rows continue in the next
+// step, class or member counts past the library's limits.
+struct wsa_debug_fold_io {
+    const int32_t* meta; const uint32_t* row_off; const uint8_t* ctl;
+    double step_s;
+    uint32_t n_rows, n, n_steps, cap, n_members, cb_cap; int32_t single, f64;
+    uint32_t C[WSA_ENSEMBLE_MAX];
+    const char* const* legend[WSA_ENSEMBLE_MAX];
+    const void* conf[WSA_ENSEMBLE_MAX];
+    uint32_t* n_cb; int32_t* cb;
+    int32_t* cb_label[WSA_ENSEMBLE_MAX]; double* cb_conf[WSA_ENSEMBLE_MAX]; double* cb_all_max[WSA_ENSEMBLE_MAX]; double* run_conf[WSA_ENSEMBLE_MAX];
+    int32_t* cb_db; int32_t* cb_top_label; double* cb_top_conf; int32_t* cb_min_db; double* cb_entropy; int32_t* run_min_db;
+    int32_t* h_cb; int32_t* h_cb_label[WSA_ENSEMBLE_MAX]; double* h_cb_conf[WSA_ENSEMBLE_MAX]; double* h_cb_all_max[WSA_ENSEMBLE_MAX];
+    int32_t* h_cb_db; int32_t* h_cb_top_label; double* h_cb_top_conf; int32_t* h_cb_min_db; double* h_cb_entropy;
+};
+
+namespace {
+// a device table holding the caller's `count` entries (one entry at least), and its way back
+template <typename T>
+bool fold_up(wsa::DevArena& A, T** d, const T* h, size_t count) {
+    return A.alloc(d, count) && (!count || hipMemcpy(*d, h, count * sizeof(T), hipMemcpyHostToDevice) == hipSuccess);
+}
+template <typename T>
+bool fold_down(T* h, const T* d, size_t count) { return !count || hipMemcpy(h, d, count * sizeof(T), hipMemcpyDeviceToHost) == hipSuccess; }
+}  // namespace
+
+extern "C" int wsa_debug_class_fold(int32_t device, const wsa_debug_fold_io* io) {
+    using namespace wsa_classify;
+    if (!io || !io->row_off || !io->n_cb || !io->cb) return WSA_ERR_INVALID;
+    const uint32_t n = io->n, n_rows = io->n_rows, n_steps = io->n_steps, M = io->n_members;
+    if ((n_rows && !io->meta) || M < 1 || M > WSA_ENSEMBLE_MAX || n < 1 || n > (1u << 16) || n_rows > (1u << 22) || io->cb_cap < 1 || io->cb_cap > (1u << 22)) return WSA_ERR_INVALID;
+    if (n_steps > (1u << 12) || (n_steps && !io->ctl) || io->cap > (1u << 22)) return WSA_ERR_INVALID;
+    const bool single = io->single != 0, f64 = io->f64 != 0, streams = n_steps != 0;
+    if (single ? M != 1 : f64) return WSA_ERR_INVALID;                  // double confidences are the single fold's (KN-2)
+    const size_t W = io->cap ? io->cap : 1;
+    if (streams && (uint64_t)n_steps * W > (1u << 24)) return WSA_ERR_INVALID;
+    for (uint32_t d = 0; d < M; d++) {
+        if (io->C[d] < 1 || io->C[d] > WSA_MODEL_MAX_CLASSES || !io->legend[d] || (n_rows && !io->conf[d])) return WSA_ERR_INVALID;
+        for (uint32_t c = 0; c < io->C[d]; c++) if (!io->legend[d][c]) return WSA_ERR_INVALID;
+        if (!io->cb_label[d] || !io->cb_conf[d] || !io->run_conf[d] || (!single && !io->cb_all_max[d])) return WSA_ERR_INVALID;
+        if (streams && (!io->h_cb_label[d] || !io->h_cb_conf[d] || (!single && !io->h_cb_all_max[d]))) return WSA_ERR_INVALID;
+    }
+    if (!single && (!io->cb_db || !io->cb_top_label || !io->cb_top_conf || !io->cb_min_db || !io->cb_entropy || !io->run_min_db)) return WSA_ERR_INVALID;
+    if (streams && (!io->h_cb || (!single && (!io->h_cb_db || !io->h_cb_top_label || !io->h_cb_top_conf || !io->h_cb_min_db || !io->h_cb_entropy)))) return WSA_ERR_INVALID;
+    const uint32_t tables = streams ? n_steps : 1;
+    uint64_t rows = 0, callbacks = 0;
+    std::vector<uint64_t> step_cb0(tables + 1, 0), step_row0(tables + 1, 0);
+    std::vector<int64_t> last_si(n, -1);                                // the si a stream's rows ended on in an earlier step of its launch; -1: none
+    for (uint32_t k = 0; k < tables; k++) {                             // every table: offsets in order, rows of their own clip / stream; callbacks counted
+        const uint32_t* off = io->row_off + (size_t)k * (n + 1);
+        if (off[0] != 0) return WSA_ERR_INVALID;
+        for (uint32_t c = 0; c < n; c++) if (off[c + 1] < off[c]) return WSA_ERR_INVALID;
+        if (rows + off[n] > n_rows) return WSA_ERR_INVALID;
+        for (uint32_t c = 0; c < n; c++) {
+            if (streams && (io->ctl[(size_t)k * n + c] & WSA_STREAM_START)) last_si[c] = -1;
+            for (uint32_t r = off[c]; r < off[c + 1]; r++) {
+                const int32_t* m = io->meta + (rows + r) * 8;
+                if (m[0] != (int32_t)c || m[1] < 0 || m[3] < 0 || m[3] == 0x7fffffff) return WSA_ERR_INVALID;
+                if (r == off[c] && (int64_t)m[1] == last_si[c]) return WSA_ERR_INVALID;       // a callback's rows split across steps
+                callbacks += (r == off[c] || m[1] != m[1 - 8]) ? 1 : 0;
+            }
+            if (streams && off[c + 1] > off[c]) last_si[c] = io->meta[(rows + off[c + 1] - 1) * 8 + 1];
+        }
+        rows += off[n];
+        step_cb0[k + 1] = callbacks; step_row0[k + 1] = rows;
+    }
+    if (rows != n_rows || callbacks > io->cb_cap) return WSA_ERR_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return WSA_ERR_NO_DEVICE;
+
+    wsa::DevArena A;
+    const size_t R = n_rows ? n_rows : 1, K = io->cb_cap, HW = (size_t)n_steps * W;
+    int32_t *d_meta = nullptr, *d_cb = nullptr, *d_t_n = nullptr, *d_t_local = nullptr;
+    uint32_t *d_off = nullptr, *d_bits = nullptr, *d_clip_cb = nullptr, *d_cb_off = nullptr, *d_count = nullptr;
+    std::vector<uint32_t> bits((size_t)tables * n, 0u);
+    for (size_t i = 0; streams && i < bits.size(); i++) bits[i] = (io->ctl[i] & WSA_STREAM_START) ? 1u : 0u;      // the device control word's bit 0
+    bool ok = fold_up(A, &d_meta, io->meta, (size_t)n_rows * 8) && fold_up(A, &d_off, io->row_off, (size_t)tables * (n + 1)) && A.upload(&d_bits, bits)
+           && fold_up(A, &d_cb, (const int32_t*)io->cb, K * 4) && A.alloc(&d_t_n, R) && A.alloc(&d_t_local, R) && A.alloc(&d_clip_cb, (size_t)n)
+           && A.alloc(&d_cb_off, (size_t)n) && A.alloc(&d_count, 1, true);
+    // per member: confidences, key_rank, the callback tables, the running sums
+    const void* d_conf[WSA_ENSEMBLE_MAX] = {}; int64_t* d_kr[WSA_ENSEMBLE_MAX] = {};
+    int32_t* d_cb_label[WSA_ENSEMBLE_MAX] = {}; double *d_cb_conf[WSA_ENSEMBLE_MAX] = {}, *d_cb_all_max[WSA_ENSEMBLE_MAX] = {}, *d_run[WSA_ENSEMBLE_MAX] = {};
+    for (uint32_t d = 0; ok && d < M; d++) {
+        const size_t Cd = io->C[d];
+        std::vector<int64_t> kr(Cd, -1);
+        for (size_t c = 0; c < Cd; c++) { int64_t v; if (array_index_key(io->legend[d][c], &v)) kr[c] = v; }
+        if (f64) { double* p = nullptr; ok = fold_up(A, &p, (const double*)io->conf[d], (size_t)n_rows * Cd); d_conf[d] = p; }
+        else { float* p = nullptr; ok = fold_up(A, &p, (const float*)io->conf[d], (size_t)n_rows * Cd); d_conf[d] = p; }
+        ok = ok && A.upload(&d_kr[d], kr) && fold_up(A, &d_cb_label[d], (const int32_t*)io->cb_label[d], K) && fold_up(A, &d_cb_conf[d], (const double*)io->cb_conf[d], K)
+             && A.alloc(&d_run[d], (size_t)n * Cd);
+        if (ok && !single) ok = fold_up(A, &d_cb_all_max[d], (const double*)io->cb_all_max[d], K);
+    }
+    EnsTables o{};                                                      // the group's decision per callback; clip_min_db per clip (streams: the step's pinned column)
+    if (ok && !single)
+        ok = fold_up(A, &o.cb_db, (const int32_t*)io->cb_db, K) && fold_up(A, &o.cb_top_label, (const int32_t*)io->cb_top_label, K)
+             && fold_up(A, &o.cb_top_conf, (const double*)io->cb_top_conf, K) && fold_up(A, &o.cb_min_db, (const int32_t*)io->cb_min_db, K)
+             && fold_up(A, &o.cb_entropy, (const double*)io->cb_entropy, K) && fold_up(A, &o.clip_min_db, (const int32_t*)io->run_min_db, (size_t)n);
+    o.cb = d_cb;
+    if (!ok) return WSA_ERR_HIP;
+
+    if (!streams) {
+        if (single) {
+            int32_t* d_t_label = nullptr; double* d_t_conf = nullptr;
+            ok = A.alloc(&d_t_label, R) && A.alloc(&d_t_conf, R);
+            if (ok && f64) {
+                FoldParams<double> f{n, io->C[0], io->step_s, d_meta, d_off, (const double*)d_conf[0], d_kr[0], d_t_label, d_t_conf, d_t_n, d_t_local, d_clip_cb, d_run[0]};
+                launch_fold(f, d_cb_off, d_cb, d_cb_label[0], d_cb_conf[0], d_count, nullptr);
+            } else if (ok) {
+                FoldParams<float> f{n, io->C[0], io->step_s, d_meta, d_off, (const float*)d_conf[0], d_kr[0], d_t_label, d_t_conf, d_t_n, d_t_local, d_clip_cb, d_run[0]};
+                launch_fold(f, d_cb_off, d_cb, d_cb_label[0], d_cb_conf[0], d_count, nullptr);
+            }
+        } else {
+            std::vector<FoldMember> ftab(M);
+            EnsTables t{};
+            ok = alloc_ens_tables(A, t, R, 0, true);
+            t.clip_min_db = o.clip_min_db;
+            for (uint32_t d = 0; ok && d < M; d++) {
+                FoldMember& m = ftab[d];
+                m = FoldMember{};
+                m.C = io->C[d]; m.prob = (const float*)d_conf[d]; m.key_rank = d_kr[d];
+                ok = A.alloc(&m.t_label, R) && A.alloc(&m.t_conf, R) && A.alloc(&m.t_all_max, R);
+                m.clip_conf = d_run[d]; m.cb_label = d_cb_label[d]; m.cb_conf = d_cb_conf[d]; m.cb_all_max = d_cb_all_max[d];
+            }
+            FoldMember* d_ftab = nullptr;
+            ok = ok && A.upload(&d_ftab, ftab);
+            if (ok) {
+                FoldGroupParams f{};
+                f.n_clips = n; f.n_members = M; f.step_s = io->step_s; f.meta = d_meta; f.row_off = d_off; f.tab = d_ftab;
+                f.t_n = d_t_n; f.t_local = d_t_local; f.clip_cb = d_clip_cb; f.t = t;
+                launch_fold_group(f, d_cb_off, o, d_count, nullptr);
+            }
+        }
+        ok = ok && hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && fold_down(io->n_cb, d_count, 1);
+        for (uint32_t d = 0; ok && d < M; d++) ok = fold_down(io->run_conf[d], d_run[d], (size_t)n * io->C[d]);
+        if (ok && !single) ok = fold_down(io->run_min_db, o.clip_min_db, (size_t)n);
+    } else {
+        // the carried state, zeroed (min_db: -1), and the steps' D2H windows one after the other
+        CarriedFold carried[WSA_ENSEMBLE_MAX] = {};
+        int32_t *d_h_cb = nullptr, *d_h_cb_label[WSA_ENSEMBLE_MAX] = {}, *d_h_min = nullptr, *d_min_db = nullptr;
+        double *d_h_cb_conf[WSA_ENSEMBLE_MAX] = {}, *d_h_cb_all_max[WSA_ENSEMBLE_MAX] = {}, *d_seg[WSA_ENSEMBLE_MAX] = {}, *d_sum[WSA_ENSEMBLE_MAX] = {}, *d_max_inv = nullptr;
+        float* d_h_prob[WSA_ENSEMBLE_MAX] = {};
+        EnsTables h{};
+        ok = fold_up(A, &d_h_cb, (const int32_t*)io->h_cb, HW * 4);
+        for (uint32_t d = 0; ok && d < M; d++) {
+            const size_t Cd = io->C[d];
+            ok = A.alloc(&carried[d].acc_all, (size_t)n * Cd, true) && A.alloc(&carried[d].in_all, (size_t)n * Cd, true) && A.alloc(&carried[d].first, (size_t)n * Cd, true)
+                 && A.alloc(&carried[d].stamp, (size_t)n, true) && fold_up(A, &d_h_cb_label[d], (const int32_t*)io->h_cb_label[d], HW)
+                 && fold_up(A, &d_h_cb_conf[d], (const double*)io->h_cb_conf[d], HW) && A.alloc(&d_h_prob[d], W * Cd);
+            if (ok && !single) ok = fold_up(A, &d_h_cb_all_max[d], (const double*)io->h_cb_all_max[d], HW) && A.alloc(&d_seg[d], K) && A.alloc(&d_sum[d], K);
+        }
+        if (ok && !single)
+            ok = fold_up(A, &h.cb_db, (const int32_t*)io->h_cb_db, HW) && fold_up(A, &h.cb_top_label, (const int32_t*)io->h_cb_top_label, HW)
+                 && fold_up(A, &h.cb_top_conf, (const double*)io->h_cb_top_conf, HW) && fold_up(A, &h.cb_min_db, (const int32_t*)io->h_cb_min_db, HW)
+                 && fold_up(A, &h.cb_entropy, (const double*)io->h_cb_entropy, HW) && A.alloc(&d_h_min, (size_t)n) && A.alloc(&d_max_inv, (size_t)n, true)
+                 && A.alloc(&d_min_db, (size_t)n) && hipMemset(d_min_db, 0xff, (size_t)n * sizeof(int32_t)) == hipSuccess;
+        // the KNN step kernel also pushes its rows' labels (one per row) and neighbours (k per row; none here)
+        int32_t *d_klabel = nullptr, *d_h_klabel = nullptr; double* d_h_kconf = nullptr;
+        if (ok && f64) ok = A.alloc(&d_klabel, R, true) && A.alloc(&d_h_klabel, W) && A.alloc(&d_h_kconf, W * io->C[0]);
+        // the members' tables of every step (a step's callbacks sit behind the earlier steps')
+        FoldMember* d_ftab = nullptr; StreamMember* d_stab = nullptr;
+        if (ok && !single) {
+            std::vector<FoldMember> ftab((size_t)n_steps * M);
+            std::vector<StreamMember> stab((size_t)n_steps * M);
+            for (uint32_t k = 0; k < n_steps; k++)
+                for (uint32_t d = 0; d < M; d++) {
+                    const size_t cb0 = step_cb0[k], hw0 = (size_t)k * W;
+                    FoldMember& m = ftab[(size_t)k * M + d];
+                    m = FoldMember{};
+                    m.C = io->C[d]; m.prob = (const float*)d_conf[d] + step_row0[k] * io->C[d]; m.key_rank = d_kr[d];
+                    m.t_label = d_cb_label[d] + cb0; m.t_conf = d_cb_conf[d] + cb0; m.t_all_max = d_cb_all_max[d] + cb0; m.t_seg = d_seg[d] + cb0; m.t_all_sum = d_sum[d] + cb0;
+                    m.cb_label = m.t_label; m.cb_conf = m.t_conf; m.cb_all_max = m.t_all_max;
+                    stab[(size_t)k * M + d] = StreamMember{carried[d], d_h_prob[d], d_h_cb_label[d] + hw0, d_h_cb_conf[d] + hw0, d_h_cb_all_max[d] + hw0, d_run[d]};
+                }
+            ok = A.upload(&d_ftab, ftab) && A.upload(&d_stab, stab);
+        }
+        for (uint32_t k = 0; ok && k < n_steps; k++) {
+            const size_t row0 = step_row0[k], cb0 = step_cb0[k], hw0 = (size_t)k * W;
+            const uint32_t* off = d_off + (size_t)k * (n + 1);
+            const uint32_t* bk = d_bits + (size_t)k * n;
+            if (single) {
+                const StepFoldTables t{io->cap, d_cb + cb0 * 4, d_cb_label[0] + cb0, d_cb_conf[0] + cb0, d_h_cb + hw0 * 4, d_h_cb_label[0] + hw0, d_h_cb_conf[0] + hw0, d_run[0], d_count};
+                if (f64) {
+                    StreamKnnParams p{};
+                    p.n = n; p.C = io->C[0]; p.k = 0; p.fold = 1; p.step_s = io->step_s; p.meta = d_meta + row0 * 8; p.row_off = off; p.bits = bk; p.key_rank = d_kr[0];
+                    p.label = d_klabel; p.conf = (const double*)d_conf[0] + row0 * io->C[0]; p.carried = carried[0]; p.t = t;
+                    p.h_label = d_h_klabel; p.h_conf = d_h_kconf;
+                    launch_stream_knn(p, nullptr);
+                } else {
+                    StreamClsParams p{};
+                    p.n = n; p.C = io->C[0]; p.fold = 1; p.step_s = io->step_s; p.meta = d_meta + row0 * 8; p.row_off = off; p.prob = (const float*)d_conf[0] + row0 * io->C[0];
+                    p.key_rank = d_kr[0]; p.bits = bk; p.carried = carried[0]; p.t = t; p.h_prob = d_h_prob[0];
+                    launch_stream_classes(p, nullptr);
+                }
+            } else {
+                StreamEnsParams p{};
+                p.n = n; p.n_members = M; p.cap = io->cap; p.fold = 1; p.step_s = io->step_s; p.meta = d_meta + row0 * 8; p.row_off = off; p.bits = bk;
+                p.tab = d_ftab + (size_t)k * M; p.stab = d_stab + (size_t)k * M;
+                p.o = EnsTables{d_cb + cb0 * 4, o.cb_db + cb0, o.cb_top_label + cb0, o.cb_top_conf + cb0, o.cb_min_db + cb0, o.cb_entropy + cb0, nullptr};
+                p.h = EnsTables{d_h_cb + hw0 * 4, h.cb_db + hw0, h.cb_top_label + hw0, h.cb_top_conf + hw0, h.cb_min_db + hw0, h.cb_entropy + hw0, d_h_min};
+                p.max_inv = d_max_inv; p.min_db = d_min_db; p.h_count = d_count;
+                launch_stream_ensemble(p, nullptr);
+            }
+            ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && fold_down(io->n_cb + k, d_count, 1);
+            for (uint32_t d = 0; ok && d < M; d++) ok = fold_down(io->run_conf[d] + (size_t)k * n * io->C[d], d_run[d], (size_t)n * io->C[d]);
+            if (ok && !single) ok = fold_down(io->run_min_db + (size_t)k * n, d_h_min, (size_t)n);
+        }
+        ok = ok && fold_down(io->h_cb, d_h_cb, HW * 4);
+        for (uint32_t d = 0; ok && d < M; d++) {
+            ok = fold_down(io->h_cb_label[d], d_h_cb_label[d], HW) && fold_down(io->h_cb_conf[d], d_h_cb_conf[d], HW);
+            if (ok && !single) ok = fold_down(io->h_cb_all_max[d], d_h_cb_all_max[d], HW);
+        }
+        if (ok && !single)
+            ok = fold_down(io->h_cb_db, h.cb_db, HW) && fold_down(io->h_cb_top_label, h.cb_top_label, HW) && fold_down(io->h_cb_top_conf, h.cb_top_conf, HW)
+                 && fold_down(io->h_cb_min_db, h.cb_min_db, HW) && fold_down(io->h_cb_entropy, h.cb_entropy, HW);
+    }
+    ok = ok && fold_down(io->cb, d_cb, K * 4);
+    for (uint32_t d = 0; ok && d < M; d++) {
+        ok = fold_down(io->cb_label[d], d_cb_label[d], K) && fold_down(io->cb_conf[d], d_cb_conf[d], K);
+        if (ok && !single) ok = fold_down(io->cb_all_max[d], d_cb_all_max[d], K);
+    }
+    if (ok && !single)
+        ok = fold_down(io->cb_db, o.cb_db, K) && fold_down(io->cb_top_label, o.cb_top_label, K) && fold_down(io->cb_top_conf, o.cb_top_conf, K)
+             && fold_down(io->cb_min_db, o.cb_min_db, K) && fold_down(io->cb_entropy, o.cb_entropy, K);
     return ok ? WSA_OK : WSA_ERR_HIP;
 }

@@ -19,8 +19,8 @@ using namespace wsa_knn_detail;
 namespace {
 
 // key_rank of the class-index legend: [WSA_MODEL_MAX_CLASSES] = 0, 1, 2, ...
-bool upload_index_legend(wsa::DevArena& A, int32_t** out) {
-    std::vector<int32_t> iota(WSA_MODEL_MAX_CLASSES);
+bool upload_index_legend(wsa::DevArena& A, int64_t** out) {
+    std::vector<int64_t> iota(WSA_MODEL_MAX_CLASSES);
     for (int c = 0; c < WSA_MODEL_MAX_CLASSES; c++) iota[c] = c;
     return A.upload(out, iota);
 }
@@ -31,7 +31,7 @@ bool upload_index_legend(wsa::DevArena& A, int32_t** out) {
 struct wsa_kfold {
     int device = 0;
     uint32_t cap_c = 0;
-    int32_t *d_t_label = nullptr, *d_t_n = nullptr, *d_t_local = nullptr, *d_cb = nullptr, *d_cb_label = nullptr, *d_key_rank = nullptr;
+    int32_t *d_t_label = nullptr, *d_t_n = nullptr, *d_t_local = nullptr, *d_cb = nullptr, *d_cb_label = nullptr; int64_t* d_key_rank = nullptr;
     double *d_t_conf = nullptr, *d_cb_conf = nullptr, *d_clip_conf = nullptr;
     uint32_t *d_clip_cb = nullptr, *d_cb_off = nullptr;
     uint32_t *h_count = nullptr, *h_count_dev = nullptr;     // pinned + mapped: callbacks of the last fold
@@ -49,9 +49,7 @@ wsa_status enqueue_batch_fold(const wsa_batch_view& v, const wsa_kcls* c, hipStr
     p.meta = v.d_meta; p.row_off = v.d_row_off; p.prob = c->d_conf; p.key_rank = f->d_key_rank;
     p.t_label = f->d_t_label; p.t_conf = f->d_t_conf; p.t_n = f->d_t_n; p.t_local = f->d_t_local;
     p.clip_cb = f->d_clip_cb; p.clip_conf = f->d_clip_conf;
-    if (v.n_clips) hipLaunchKernelGGL(fold_kernel<double>, dim3((v.n_clips + 3) / 4), dim3(256), 0, s, p);
-    hipLaunchKernelGGL(fold_compact_kernel, dim3(1), dim3(1024), 0, s, v.n_clips, v.d_row_off, v.d_meta, f->d_clip_cb, f->d_cb_off,
-                       f->d_t_label, f->d_t_conf, f->d_t_n, f->d_t_local, f->d_cb, f->d_cb_label, f->d_cb_conf, f->h_count_dev);
+    launch_fold(p, f->d_cb_off, f->d_cb, f->d_cb_label, f->d_cb_conf, f->h_count_dev, s);
     HIP_TRY(v.ctx, hipGetLastError());
     return WSA_OK;
 }
@@ -132,14 +130,7 @@ wsa_status wsa_batch_copy_knn_fold(wsa_batch* b, void* stream, int32_t* cb, int3
 // ---- streams (wsa_stream_set_knn): K9s on every step's rows, KN-2 carried per stream at level 13; everything allocated at attach time
 namespace {
 
-struct StreamKnnParams {
-    uint32_t n, C, k; int fold; double step_s;
-    const int32_t* meta; const uint32_t* row_off; const uint32_t* bits; const int32_t* key_rank;
-    const int32_t* label; const double* conf; const int32_t* nbr; const float* sim;       // K9s' tables of the step
-    CarriedFold carried;
-    StepFoldTables t;
-    int32_t* h_label; double* h_conf; int32_t* h_nbr; float* h_sim;                       // mapped pinned
-};
+// (StreamKnnParams, classify_internal.hpp)
 
 // `per` entries of each of rows r0 .. r1 - 1 below `cap` (the D2H window) to the pinned table
 template <typename T>
@@ -159,10 +150,14 @@ __global__ void __launch_bounds__(256) stream_knn_kernel(StreamKnnParams p) {
     push_rows(p.h_nbr, p.nbr, r0, r1, p.t.cap, p.k, lane);
     push_rows(p.h_sim, p.sim, r0, r1, p.t.cap, p.k, lane);
     if (!p.fold) return;
-    fold_stream_step(p.meta, p.conf, p.C, p.step_s, lane, (uint32_t)lane < p.C ? p.key_rank[lane] : -1, s, p.n, r0, r1, p.carried, p.bits[s] & 1u, p.t);
+    fold_stream_step(p.meta, p.conf, p.C, p.step_s, lane, (uint32_t)lane < p.C ? (long long)p.key_rank[lane] : -1, s, p.n, r0, r1, p.carried, p.bits[s] & 1u, p.t);
 }
 
 }  // namespace
+
+void wsa_classify::launch_stream_knn(const StreamKnnParams& p, hipStream_t s) {      // four streams per workgroup
+    hipLaunchKernelGGL(stream_knn_kernel, dim3((p.n + 3) / 4), dim3(256), 0, s, p);
+}
 
 struct wsa_sknn {
     int device = 0;
@@ -171,7 +166,7 @@ struct wsa_sknn {
     uint32_t C = 0, k = 0;
     KnnParams p{};                           // the store as it stood at attach (row count, k_eff) and the step's tables
     KnnSplit sp;
-    int32_t *d_label = nullptr, *d_nbr = nullptr, *d_key_rank = nullptr; double* d_conf = nullptr; float* d_sim = nullptr;
+    int32_t *d_label = nullptr, *d_nbr = nullptr; int64_t* d_key_rank = nullptr; double* d_conf = nullptr; float* d_sim = nullptr;
     CarriedFold carried{};
     double* d_cb_conf = nullptr; int32_t *d_cb = nullptr, *d_cb_label = nullptr;
     wsa::DevArena mem;
@@ -243,7 +238,7 @@ wsa_status wsa_sknn_enqueue(wsa_sknn* c, hipStream_t s) {
     p.carried = c->carried;
     p.t = StepFoldTables{v.d2h_rows, c->d_cb, c->d_cb_label, c->d_cb_conf, c->h_cb_dev, c->h_cb_label_dev, c->h_cb_conf_dev, c->h_all_dev, c->h_count_dev};
     p.h_label = c->h_label_dev; p.h_conf = c->h_conf_dev; p.h_nbr = c->h_nbr_dev; p.h_sim = c->h_sim_dev;
-    hipLaunchKernelGGL(stream_knn_kernel, dim3((v.n_streams + 3) / 4), dim3(256), 0, s, p);
+    launch_stream_knn(p, s);
     HIP_TRY(v.ctx, hipGetLastError());
     return WSA_OK;
 }
