@@ -311,6 +311,10 @@ def test_frontend_overlapping_windows_and_emphasis(wsa):
     (6000, {}), (5500, dict(f_max=2000.0, N_fft_bins=128)), (96000, {}), (88200, dict(window_width=30.0)), (12000, dict(window_width=50.0, window_step=20.0)),
     (48000, dict(window_width=40.0, window_step=10.0)),
     (48000, dict(window_width=150.0, window_step=50.0)), (16000, dict(window_width=500.0, window_step=250.0)), (48000, dict(window_width=200.0, window_step=100.0)), (64000, dict(window_width=190.0, window_step=95.0, spec_type=2)),
+    # one geometry for each front-end instantiation the cases above do not select (profiles/frontend_split.md has the table)
+    (16000, dict(window_width=15.0)), (16000, dict(window_width=20.0)), (16000, dict(f_min=500.0, f_max=3500.0, N_fft_bins=224, N_mel_bins=92)),
+    (8000, dict(window_width=50.0)), (32000, dict(window_width=20.0)), (64000, dict(window_width=20.0)), (64000, {}), (6000, dict(window_width=50.0)),
+    (24000, dict(f_max=6000.0, N_fft_bins=384)), (24000, dict(window_width=40.0)), (48000, dict(f_max=8000.0, N_fft_bins=512)), (96000, dict(window_width=50.0)),
 ])
 def test_frontend_other_fft_lengths_bit_exact(wsa, fs, kw):
     """NFFT 256 / 512 / 2048 / 4096 / 8192 (R = 2, 4, 16, 32, 64) and 384 / 768 / 1536 / 3072 / 6144 / 12288 (radix-3 stage + R = 1, 2, 4, 8, 16, 32: FE-1 F2 picks

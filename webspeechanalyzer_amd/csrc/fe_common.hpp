@@ -1,4 +1,4 @@
-// fe_common.hpp — device helpers shared by the front-end kernels (frontend.hip: K1, fused.hip: K1 + peak scan in one launch):
+// fe_common.hpp — device helpers shared by the front-end kernels (K1: fe_r8.hip, fe_rx.hip, fe_r3.hip through fe_stages.hpp):
 // the FE-1 arithmetic as packed-fp32 operations and the radix-8 butterfly.
 #pragma once
 #include "wsa_internal.hpp"
@@ -7,52 +7,6 @@
 namespace wsa {
 
 struct __attribute__((packed, aligned(4))) pcm2 { float x, y; };
-
-__device__ __forceinline__ float2 cmul(float2 x, float2 w) {        // FE-1 generic complex multiply
-    float2 y;
-    y.x = __builtin_fmaf(-x.y, w.y, x.x * w.x);
-    y.y = __builtin_fmaf(x.y, w.x, x.x * w.y);
-    return y;
-}
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 mul_mi(float2 t) { return make_float2(t.y, -t.x); }                 // * (-i)
-__device__ __forceinline__ float2 mul_w8(float2 t) {                                                   // * W8
-    const float s = 0.70710678118654752440f;
-    return make_float2(s * (t.x + t.y), s * (t.y - t.x));
-}
-__device__ __forceinline__ float2 mul_w83(float2 t) {                                                  // * W8^3
-    const float s = 0.70710678118654752440f;
-    return make_float2(s * (t.y - t.x), -(s * (t.x + t.y)));
-}
-
-// radix-8 DIF butterfly = three radix-2 stages (FE-1); result returned in natural order.
-// NZ = number of leading non-zero inputs (inputs >= NZ are exactly zero and pruned).
-template <int NZ>
-__device__ __forceinline__ void radix8(float2 (&v)[8]) {
-    float2 a0, a1, a2, a3, b0, b1, b2, b3;
-    if (NZ > 4) {
-        a0 = cadd(v[0], v[4]); b0 = csub(v[0], v[4]);
-        a1 = cadd(v[1], v[5]); b1 = mul_w8(csub(v[1], v[5]));
-        a2 = cadd(v[2], v[6]); b2 = mul_mi(csub(v[2], v[6]));
-        a3 = cadd(v[3], v[7]); b3 = mul_w83(csub(v[3], v[7]));
-    } else {           // v[4..7] == 0: u + 0 = u, (u - 0) * W = u * W
-        a0 = v[0]; b0 = v[0];
-        a1 = v[1]; b1 = mul_w8(v[1]);
-        a2 = v[2]; b2 = mul_mi(v[2]);
-        a3 = v[3]; b3 = mul_w83(v[3]);
-    }
-    // stage h = 2 on (a0..a3) and (b0..b3)
-    float2 c0 = cadd(a0, a2), c2 = csub(a0, a2);
-    float2 c1 = cadd(a1, a3), c3 = mul_mi(csub(a1, a3));
-    float2 d0 = cadd(b0, b2), d2 = csub(b0, b2);
-    float2 d1 = cadd(b1, b3), d3 = mul_mi(csub(b1, b3));
-    // stage h = 1; bit-reversed positions -> natural order: out[k] = pos[bitrev3(k)]
-    v[0] = cadd(c0, c1); v[4] = csub(c0, c1);      // pos 0,1 -> k 0,4
-    v[2] = cadd(c2, c3); v[6] = csub(c2, c3);      // pos 2,3 -> k 2,6
-    v[1] = cadd(d0, d1); v[5] = csub(d0, d1);      // pos 4,5 -> k 1,5
-    v[3] = cadd(d2, d3); v[7] = csub(d2, d3);      // pos 6,7 -> k 3,7
-}
 
 // lanes of one wave exchange through LDS: hardware runs a wave's LDS instructions in order, so only
 // the compiler has to be kept from moving accesses across (a fence would also drain the PCM prefetch)
@@ -125,8 +79,24 @@ __device__ __forceinline__ v2f pk_add_conj(v2f a, v2f b) { return mk2(a.x + b.x,
 __device__ __forceinline__ v2f pk_sub_conj(v2f a, v2f b) { return mk2(a.x - b.x, a.y + b.y); }
 #endif
 __device__ __forceinline__ v2f to_v2f(float2 a) { v2f d; d.x = a.x; d.y = a.y; return d; }
+// t * (-i) = (t.y, -t.x) as one packed multiply by (1, -1)
+__device__ __forceinline__ v2f pk_mi(v2f t, v2f one_mone) {
+#if WSA_FE_PK_ASM
+    v2f d; asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[0,1]" : "=v"(d) : "v"(t), "v"(one_mone)); return d;
+#else
+    v2f d; d.x = t.y; d.y = -t.x; return d;
+#endif
+}
+// one bin of the real-FFT split + power (FE-1 F4): 4 |X[k]|^2 from za = Z[k], zb = Z[N2 - k], w = W_NFFT^k
+__device__ __forceinline__ float pk_split1(v2f za, v2f zb, v2f w) {
+    const v2f e = pk_add_conj(za, zb), o = pk_sub_conj(za, zb);      // za +- conj(zb)
+    const v2f t = pk_cmul(o, w);
+    const v2f xx = pk_add_mi(e, t);                                  // (e.x + t.y, e.y - t.x)
+    return __builtin_fmaf(xx.x, xx.x, xx.y * xx.y);
+}
 
-// radix-8 DIF butterfly on packed values, same stages and operation order as radix8<NZ> above; the -i twiddles
+// radix-8 DIF butterfly on packed values = three radix-2 stages (FE-1), result in natural order; NZ = number of leading non-zero
+// inputs (inputs >= NZ are exactly zero and pruned: u + 0 = u, (u - 0) * W = u * W).  The -i twiddles
 // of stages 1 and 2 are folded into the adds of the following stage.
 // One asm block per butterfly (fe_blocks.inc, generated and checked by tools/gen/fe_blocks.py): between separate asm statements the compiler's hazard recognizer puts an `s_nop` in front of every
 // statement that reads a register an asm statement wrote (an asm statement has unknown length, so the producer always counts as
@@ -146,12 +116,7 @@ __device__ __forceinline__ void pk_split5(const v2f (&za)[5], const v2f (&zb)[5]
 #else
 __device__ __forceinline__ void pk_split5(const v2f (&za)[5], const v2f (&zb)[5], const v2f (&w)[5], float (&pw)[5]) {
 #pragma unroll
-    for (int c = 0; c < 5; c++) {
-        const v2f e = pk_add_conj(za[c], zb[c]), o = pk_sub_conj(za[c], zb[c]);
-        const v2f t = pk_cmul(o, w[c]);
-        const v2f xx = pk_add_mi(e, t);
-        pw[c] = __builtin_fmaf(xx.x, xx.x, xx.y * xx.y);
-    }
+    for (int c = 0; c < 5; c++) pw[c] = pk_split1(za[c], zb[c], w[c]);
 }
 template <int NZ>
 __device__ __forceinline__ void radix8_pk(v2f (&v)[8], const v2f ss) {
