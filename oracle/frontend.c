@@ -186,6 +186,12 @@ int32_t wsa_or_fe_n_frames(const wsa_or_fe *f, int64_t n_samples) {
     if (n_samples < f->win) return 0;
     return (int32_t)((n_samples - f->win) / f->hop) + 1;                        /* F1: tail dropped */
 }
+/* first bin and tap count of mel band m (tests/test_fe_reference.py holds them against the float64 statement tests/fe_ref.py) */
+int32_t wsa_or_fe_mel_band(const wsa_or_fe *f, int32_t m, int32_t *k0, int32_t *cnt) {
+    if (!f->mel_k0 || m < 0 || m >= f->bands) return 0;
+    *k0 = f->mel_k0[m]; *cnt = f->mel_cnt[m];
+    return 1;
+}
 /* table access for the table-equality test against the product's host-side plan */
 const float *wsa_or_fe_table(const wsa_or_fe *f, int32_t which, int32_t *n) {
     switch (which) {

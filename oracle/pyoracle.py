@@ -117,6 +117,8 @@ def lib():
     L.wsa_or_fe_bins_hz.argtypes = [vp]
     L.wsa_or_fe_table.restype = ctypes.POINTER(ctypes.c_float)
     L.wsa_or_fe_table.argtypes = [vp, i32, ctypes.POINTER(i32)]
+    L.wsa_or_fe_mel_band.restype = i32
+    L.wsa_or_fe_mel_band.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.wsa_or_fe_power4.argtypes = [vp, vp, vp]
     L.wsa_or_fe_frame.argtypes = [vp, vp, vp]
     L.wsa_or_fe_run.restype = i32
@@ -159,6 +161,16 @@ class FrontEnd:
         n = ctypes.c_int32()
         p = self.L.wsa_or_fe_table(self.h, which, ctypes.byref(n))
         return np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, np.float32)
+
+    def mel_bands(self):
+        """(k0, cnt) of every mel band: first bin and tap count (None when the bands are FFT bins)"""
+        k0, cnt = np.zeros(self.bands, np.int64), np.zeros(self.bands, np.int64)
+        a, b = ctypes.c_int32(), ctypes.c_int32()
+        for m in range(self.bands):
+            if not self.L.wsa_or_fe_mel_band(self.h, m, ctypes.byref(a), ctypes.byref(b)):
+                return None
+            k0[m], cnt[m] = a.value, b.value
+        return k0, cnt
 
     def power4(self, frame):
         frame = np.ascontiguousarray(frame, dtype=np.float32)

@@ -1845,3 +1845,29 @@ def debug_peaks(spec, mode, device=0):
                 p_i=ent[:, :, 1].astype(np.uint64) | ((hi & np.uint64(0xff)) << np.uint64(32)),
                 p_s=ent[:, :, 2].astype(np.uint64) | (((hi >> np.uint64(8)) & np.uint64(0xff)) << np.uint64(32)), ent_top=ent[:, :, 3] >> 16,
                 flags=int(flags[0]), hdr=hdr, ent=ent)
+
+
+def debug_fe_choice(analyzer, fs):
+    """Test access (csrc/debug.hip wsa_debug_fe_choice; not part of include/wsa.h): the name of the K1 instantiation the analyzer's settings select at the
+    sample rate fs, as profiles/frontend_split.md writes it, e.g. 'fe_kernel_r8<4,5,8,true,4,3>'.  Plans on the host; launches nothing."""
+    L = lib()
+    L.wsa_debug_fe_choice.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_char_p, ctypes.c_uint32]
+    L.wsa_debug_fe_choice.restype = ctypes.c_int
+    buf = ctypes.create_string_buffer(64)
+    rc = L.wsa_debug_fe_choice(analyzer.h, float(fs), buf, 64)
+    if rc != 0:
+        raise WsaError(f"wsa_debug_fe_choice: error {rc}")
+    return buf.value.decode()
+
+
+def debug_stream_spectra(streams, bands):
+    """Test access (csrc/debug.hip wsa_debug_stream_spectra): the u32 frames the front end wrote in the stream set's last step,
+    [n_streams, frames_per_step, bands]; call behind collect()."""
+    L = lib()
+    L.wsa_debug_stream_spectra.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
+    L.wsa_debug_stream_spectra.restype = ctypes.c_int
+    out = np.zeros((streams.n, streams.frame_capacity, int(bands)), np.uint32)
+    rc = L.wsa_debug_stream_spectra(streams.h, out.ctypes.data, out.size)
+    if rc != 0:
+        raise WsaError(f"wsa_debug_stream_spectra: error {rc}")
+    return out

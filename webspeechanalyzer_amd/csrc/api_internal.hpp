@@ -42,6 +42,8 @@ wsa_status wsa_batch_fetch_internal(wsa_batch* b, hipStream_t s);
 // debug.hip (wsa_debug_batch_tiers): keep >= 0 sets whether the batch's runs leave their device counters standing (1) instead of having the fused
 // compaction clear them for the next run (0, the default); returns the batch's 16 device counters
 const uint32_t* wsa_batch_counters_internal(wsa_batch* b, int keep, wsa_ctx** ctx);
+// debug.hip (wsa_debug_stream_spectra): the u32 frames of a stream set's last step on the device, [n_streams][frames_per_step][bands]
+const uint32_t* wsa_stream_spec_internal(wsa_stream* b, wsa_ctx** ctx, uint32_t* n_streams, uint32_t* frames_per_step, uint32_t* bands);
 void wsa_model_info_internal(const wsa_model* m, wsa_ctx** ctx, int* n_classes, int* softmax);   // classify.hip, for dbstats.hip (K8)
 int wsa_model_inputs_internal(const wsa_model* m);                                               // units[0]
 }              // fetch_totals: synchronise, read the counters (reruns the back end on a table overflow)

@@ -1,6 +1,6 @@
 // debug.hip — test entries of libwsa that are NOT part of include/wsa.h: unit access to device-side pieces that the public
 // entry points only exercise through their consequences (tests/test_gpu_units.py, tests/test_gpu_coeffs.py, tests/test_gpu_utterance.py, tests/test_gpu_gate.py,
-// tests/test_gpu_regress_group.py, tests/test_gpu_fold.py).
+// tests/test_gpu_regress_group.py, tests/test_gpu_fold.py, tests/test_gpu_frontend.py).
 #include <cstring>
 #include <vector>
 #include "host_plan.hpp"
@@ -195,6 +195,30 @@ extern "C" int wsa_debug_batch_tiers(wsa_batch* b, void* stream, uint32_t* out3)
     if (!ctx || !d || hipSetDevice(ctx->device) != hipSuccess) return WSA_ERR_NO_DEVICE;
     if (hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)) != hipSuccess || hipMemcpy(c, d, sizeof(c), hipMemcpyDeviceToHost) != hipSuccess) return WSA_ERR_HIP;
     out3[0] = c[1]; out3[1] = c[5]; out3[2] = c[6];       // d_counters[1]: flags; [4 + 1]: spans (span_order_kernel); [4 + 2]: TrParams::redo_count
+    return WSA_OK;
+}
+
+// which K1 instantiation a geometry runs (csrc/fe_r8.hip, fe_rx.hip, fe_r3.hip fe_select_*): its name as profiles/frontend_split.md writes it, e.g.
+// "fe_kernel_r8<4,5,8,true,4,3>", into buf (n bytes, zero terminated).  Plans on the host, launches nothing.
+extern "C" int wsa_debug_fe_choice(wsa_ctx* ctx, double fs, char* buf, uint32_t n) {
+    if (!ctx || !buf || n < 1) return WSA_ERR_INVALID;
+    wsa::FePlanHost P; std::string err;
+    if (!wsa::build_fe_plan(ctx->cfg, fs, P, err)) return WSA_ERR_INVALID;
+    const char* name = wsa::fe_choice_name(P, wsa::Tuning::from_env().fe_fat);
+    if (std::strlen(name) + 1 > n) return WSA_ERR_INVALID;
+    std::strcpy(buf, name);
+    return WSA_OK;
+}
+// the u32 frames the front end wrote in a stream set's last step, [n_streams][frames_per_step][bands] (a stream that had fewer frames in the step
+// leaves the rest of its block as it was); call behind collect
+extern "C" int wsa_debug_stream_spectra(wsa_stream* st, uint32_t* out, uint64_t cap_words) {
+    if (!st || !out) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = nullptr; uint32_t n = 0, F = 0, bands = 0;
+    const uint32_t* d = wsa_stream_spec_internal(st, &ctx, &n, &F, &bands);
+    const uint64_t words = (uint64_t)n * F * bands;
+    if (!ctx || !d || cap_words < words) return WSA_ERR_INVALID;
+    if (hipSetDevice(ctx->device) != hipSuccess) return WSA_ERR_NO_DEVICE;
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, d, words * 4, hipMemcpyDeviceToHost) != hipSuccess) return WSA_ERR_HIP;
     return WSA_OK;
 }
 

@@ -44,6 +44,8 @@ __global__ __launch_bounds__(256) void fe_kernel_r3(FeParams p) {
     v2f* X = reinterpret_cast<v2f*>(smem + L.wave0 + (size_t)wave * L.xbytes);
     float* P = reinterpret_cast<float*>(smem + L.wave0 + 4 * L.xbytes + (size_t)wave * L.pbytes);
 
+    const int zslot = (int)(reinterpret_cast<float*>(smem + L.zero) - P);      // the zero word a band's padded taps read, as an index into this wave's power rows
+    if (threadIdx.x == 0) *reinterpret_cast<float*>(smem + L.zero) = 0.f;
     fe_tables_fill(T, p);
     for (int i = threadIdx.x; i < 2 * RM * 64; i += 256) {
         const int ln = i & 63, aM = (i >> 6) % RM, k3 = (i >> 6) / RM + 1;
@@ -64,8 +66,8 @@ __global__ __launch_bounds__(256) void fe_kernel_r3(FeParams p) {
     // partner lanes of the real split (see the header): transform 0 as in fe_kernel_rx, transforms 1 <-> 2 mirrored
     const FePartners part = fe_partners(RM, lane);
     const int part_x = ((((AL - 1 - hi3) & 7) << 3) | (7 - lo3)) & 63;
-    int mk[2];
-    fe_mel_first_bin(mk, p, T, lane);
+    int mk[2], mn[2];
+    fe_mel_first_bin(mk, mn, p, T, lane);
 
     int ld_idx[AZ]; uint32_t ld_off[AZ]; FeWinPred<LN> ld_w[AZ];          // LN: byte offsets and lane masks
 #pragma unroll
@@ -163,7 +165,7 @@ __global__ __launch_bounds__(256) void fe_kernel_r3(FeParams p) {
         wave_lds_sync();
         // ---- bands (F5-F8)
         uint32_t* out = ck.out + (uint64_t)f * (uint32_t)p.bands;
-        if (mel_fast) fe_bands_two<MW>(p, T, s_mwp, P, mk, lane, [&](int m, float e) __attribute__((always_inline)) {
+        if (mel_fast) fe_bands_two<MW>(p, T, s_mwp, P, mk, mn, zslot, lane, [&](int m, float e) __attribute__((always_inline)) {
             if constexpr (LN) __builtin_amdgcn_raw_buffer_store_b32(to_u32(e), r_out, (uint32_t)m * 4u, (f - f_begin) * (uint32_t)p.bands * 4u, 0);
             else out[m] = to_u32(e);
         });
@@ -177,9 +179,9 @@ __global__ __launch_bounds__(256) void fe_kernel_r3(FeParams p) {
 }
 
 template <int RM, int AZ, int MW, int CR = 8, int AF = 0>
-static FeChoice choice_r3(const FeParams& p) {
+static FeChoice choice_r3(const FeParams& p, const char* name) {
     FeChoice c;
-    c.kernel = fe_kernel_r3<RM, AZ, MW, CR, AF>;
+    c.kernel = fe_kernel_r3<RM, AZ, MW, CR, AF>; c.name = name;
     c.lds = fe_lds(p.mel_total, p.bands, p.kmax, 2 * RM, RM > 1 ? RM - 1 : 1, AZ, MW, AF > 0 ? 3 * 8 * RM * CR + 2 : 0).total;
     c.grid_2d = true;
     // persistent launch (batches) of the AF > 0 instantiation: n_cu x WSA_FE_WGS workgroups (default 2: the kernel's 162 VGPRs admit three) take the chunks
@@ -191,22 +193,22 @@ static FeChoice choice_r3(const FeParams& p) {
 // NFFT = 3 * 64 RM * 2: the smallest instantiation whose non-zero blocks cover the window
 FeChoice fe_select_r3(const FeParams& p, int RM) {
     const int az = (p.win + 127) / 128;       // non-zero 64-point blocks of packed input
-    if (RM == 1) return az <= 2 ? choice_r3<1, 2, 12>(p) : choice_r3<1, 3, 12>(p);
-    if (RM == 2) return az <= 3 ? choice_r3<2, 3, 12>(p) : choice_r3<2, 6, 12>(p);
+    if (RM == 1) return az <= 2 ? choice_r3<1, 2, 12>(p, "fe_kernel_r3<1,2,12>") : choice_r3<1, 3, 12>(p, "fe_kernel_r3<1,3,12>");
+    if (RM == 2) return az <= 3 ? choice_r3<2, 3, 12>(p, "fe_kernel_r3<2,3,12>") : choice_r3<2, 6, 12>(p, "fe_kernel_r3<2,6,12>");
     if (RM == 4) {
-        if (az <= 5 && p.kmax < 3 * 8 * 4 * 3 && !p.fat) return choice_r3<4, 5, 14, 3>(p);          // 1536 points = 22.05 kHz: rows c = 0 .. 2
-        return az <= 5 ? choice_r3<4, 5, 14>(p) : az <= 8 ? choice_r3<4, 8, 14>(p) : choice_r3<4, 12, 14>(p);
+        if (az <= 5 && p.kmax < 3 * 8 * 4 * 3 && !p.fat) return choice_r3<4, 5, 14, 3>(p, "fe_kernel_r3<4,5,14,3>");          // 1536 points = 22.05 kHz: rows c = 0 .. 2
+        return az <= 5 ? choice_r3<4, 5, 14>(p, "fe_kernel_r3<4,5,14>") : az <= 8 ? choice_r3<4, 8, 14>(p, "fe_kernel_r3<4,8,14>") : choice_r3<4, 12, 14>(p, "fe_kernel_r3<4,12,14>");
     }
     if (RM == 8) {
         // (3072 points = 44.1 / 48 kHz with the default 4 kHz band limit: bins <= 383 sit in rows c = 0, 1 of the output registers)
         // ... and, at the reference's own geometry (25 ms window at 48 kHz — the offline context's rate; 1102 samples at 44.1 kHz fall short —: at least nine blocks inside the window, both kept rows of every residue
         // exist), the instantiation with the window in registers, mask selects and buffer addressing (AF = 9)
-        if (az <= 10 && p.kmax < 3 * 8 * 8 * 2 && p.kmax >= 3 * 8 * 8 + 2 && p.win >= 128 * 9 && !p.fat) return choice_r3<8, 10, 14, 2, 9>(p);
-        if (az <= 10 && p.kmax < 3 * 8 * 8 * 2 && !p.fat) return choice_r3<8, 10, 14, 2>(p);
-        return az <= 10 ? choice_r3<8, 10, 14>(p) : az <= 16 ? choice_r3<8, 16, 14>(p) : choice_r3<8, 24, 14>(p);
+        if (az <= 10 && p.kmax < 3 * 8 * 8 * 2 && p.kmax >= 3 * 8 * 8 + 2 && p.win >= 128 * 9 && !p.fat) return choice_r3<8, 10, 14, 2, 9>(p, "fe_kernel_r3<8,10,14,2,9>");
+        if (az <= 10 && p.kmax < 3 * 8 * 8 * 2 && !p.fat) return choice_r3<8, 10, 14, 2>(p, "fe_kernel_r3<8,10,14,2>");
+        return az <= 10 ? choice_r3<8, 10, 14>(p, "fe_kernel_r3<8,10,14>") : az <= 16 ? choice_r3<8, 16, 14>(p, "fe_kernel_r3<8,16,14>") : choice_r3<8, 24, 14>(p, "fe_kernel_r3<8,24,14>");
     }
-    if (RM == 16) return az <= 20 ? choice_r3<16, 20, 14>(p) : az <= 32 ? choice_r3<16, 32, 14>(p) : choice_r3<16, 48, 14>(p);
-    if (RM == 32) return choice_r3<32, 96, 14>(p);
+    if (RM == 16) return az <= 20 ? choice_r3<16, 20, 14>(p, "fe_kernel_r3<16,20,14>") : az <= 32 ? choice_r3<16, 32, 14>(p, "fe_kernel_r3<16,32,14>") : choice_r3<16, 48, 14>(p, "fe_kernel_r3<16,48,14>");
+    if (RM == 32) return choice_r3<32, 96, 14>(p, "fe_kernel_r3<32,96,14>");
     return FeChoice();
 }
 

@@ -53,6 +53,8 @@ __global__ __launch_bounds__(256, (T1L && MWL == 4) ? 4 : 1) void fe_kernel_r8(F
     //  W_1024^k of the lane make room — read from this table beside the partner values, same round trip)
     v2f* s_tws = reinterpret_cast<v2f*>(smem + L.tws);                                                                          // [5][64]
     if (BASE) for (int i = threadIdx.x; i < 5 * 64; i += 256) { const int l = i & 63, k = (l >> 3) + 8 * (l & 7) + 64 * (i >> 6); s_tws[i] = to_v2f(k <= p.kmax ? p.tw_nfft[k] : make_float2(0.f, 0.f)); }
+    const int zslot = (int)(reinterpret_cast<float*>(smem + L.zero) - P);                                                      // the zero word, as an index into this wave's power rows
+    if (threadIdx.x == 0) *reinterpret_cast<float*>(smem + L.zero) = 0.f;
     fe_tables_fill(T, p);
     // without a queue chunk = blockIdx.x; the barrier also stands between the tables' fill and their first read
     uint32_t nxt = 0; int phase = 0;
@@ -81,8 +83,8 @@ __global__ __launch_bounds__(256, (T1L && MWL == 4) ? 4 : 1) void fe_kernel_r8(F
         tws[c] = to_v2f((k <= p.kmax) ? p.tw_nfft[k] : make_float2(0.f, 0.f));       // (dead in the BASE instantiation: its loop reads s_tws)
     }
 
-    // mel taps of this lane's two bands (m = lane, lane + 64): loop invariant, zero padded.  A padded
-    // tap contributes fmaf(0, P, e) = e exactly, so the fixed-length chain equals the FE-1 chain.
+    // mel taps of this lane's two bands (m = lane, lane + 64): loop invariant, zero padded.  A padded tap multiplies the zero word, not a power
+    // bin (fe_mel_taps: 0 * P is not 0 when P overflowed to Inf), so the fixed-length chain equals the FE-1 chain whatever the power rows hold.
     float mw[2][MW]; int mk[2], mn[2];
 #pragma unroll
     for (int q = 0; q < 2; q++) {
@@ -101,7 +103,6 @@ __global__ __launch_bounds__(256, (T1L && MWL == 4) ? 4 : 1) void fe_kernel_r8(F
     float emph_r[2];
 #pragma unroll
     for (int q = 0; q < 2; q++) { const int m = lane + 64 * q; emph_r[q] = T.emph[m < p.bands ? m : 0]; }
-    const int pmax = p.kmax;                                    // padded taps read a valid P slot
     const bool all_bands = BASE || p.bands == 128;              // both of a lane's bands exist: the stores need no lane test
 
     // PCM of frame f+1 is requested before frame f is transformed
@@ -160,7 +161,7 @@ __global__ __launch_bounds__(256, (T1L && MWL == 4) ? 4 : 1) void fe_kernel_r8(F
     // (the two bands' chains are independent)
     auto request_taps = [&]() __attribute__((always_inline)) {
 #pragma unroll
-        for (int q = 0; q < 2; q++) fe_mel_taps<MW>(pv[q], P, mk[q], q == 1 ? MW : MWL, pmax, psw);
+        for (int q = 0; q < 2; q++) fe_mel_taps<MW>(pv[q], P, mk[q], mn[q], q == 1 ? MW : MWL, zslot, psw);
         wave_lds_sync();
     };
     auto band_value = [&](int q) __attribute__((always_inline)) { return fe_mel_chain<MW>(mw[q], pv[q], q == 1 ? MW : MWL, emph_r[q], p.gain); };
@@ -239,13 +240,13 @@ FeChoice fe_select_r8(const FeParams& p) {
     c.queue_wgs = 4;
     const int az = (p.win + 127) / 128;       // non-zero 64-point blocks of packed input
     const bool lean = p.kmax / 64 + 1 <= 5 && p.mel_max_taps <= 8 && p.spec_type == 1 && !p.fat;
-    if (az <= 2) c.kernel = fe_kernel_r8<2, 9, MELW, false>;
+    if (az <= 2) { c.kernel = fe_kernel_r8<2, 9, MELW, false>; c.name = "fe_kernel_r8<2,9,12,false>"; }
     else if (az <= 4 && lean && p.mel_max_taps_lo <= 4 && p.win >= 384 && p.bands == 128 && p.kmax / 64 + 1 == 5)
-        c.kernel = fe_kernel_r8<4, 5, 8, true, 4, 3>;      // the baseline geometry (16 kHz: 400-sample window, 128 bands, five rows of bins): BASE
-    else if (az <= 4 && lean && p.mel_max_taps_lo <= 4) c.kernel = fe_kernel_r8<4, 5, 8, true, 4>;
-    else if (az <= 4 && lean) c.kernel = fe_kernel_r8<4, 5, 8, true>;
-    else if (az <= 4) c.kernel = fe_kernel_r8<4, 9, MELW, false>;
-    else c.kernel = fe_kernel_r8<8, 9, MELW, false>;
+        { c.kernel = fe_kernel_r8<4, 5, 8, true, 4, 3>; c.name = "fe_kernel_r8<4,5,8,true,4,3>"; }      // the baseline geometry (16 kHz: 400-sample window, 128 bands, five rows of bins): BASE
+    else if (az <= 4 && lean && p.mel_max_taps_lo <= 4) { c.kernel = fe_kernel_r8<4, 5, 8, true, 4>; c.name = "fe_kernel_r8<4,5,8,true,4>"; }
+    else if (az <= 4 && lean) { c.kernel = fe_kernel_r8<4, 5, 8, true>; c.name = "fe_kernel_r8<4,5,8,true>"; }
+    else if (az <= 4) { c.kernel = fe_kernel_r8<4, 9, MELW, false>; c.name = "fe_kernel_r8<4,9,12,false>"; }
+    else { c.kernel = fe_kernel_r8<8, 9, MELW, false>; c.name = "fe_kernel_r8<8,9,12,false>"; }
     return c;
 }
 

@@ -30,6 +30,8 @@ __global__ __launch_bounds__(256) void fe_kernel_rx(FeParams p) {
     v2f* X = reinterpret_cast<v2f*>(smem + L.wave0 + (size_t)wave * L.xbytes);
     float* P = reinterpret_cast<float*>(smem + L.wave0 + 4 * L.xbytes + (size_t)wave * L.pbytes);
 
+    const int zslot = (int)(reinterpret_cast<float*>(smem + L.zero) - P);      // the zero word a band's padded taps read, as an index into this wave's power rows
+    if (threadIdx.x == 0) *reinterpret_cast<float*>(smem + L.zero) = 0.f;
     fe_tables_fill(T, p);
     fe_fill_twiddle_rows(s_twl, p.tw_n2, R - 1);
     for (int i = threadIdx.x; i <= p.kmax; i += 256) s_tws[i] = to_v2f(p.tw_nfft[i]);
@@ -48,8 +50,8 @@ __global__ __launch_bounds__(256) void fe_kernel_rx(FeParams p) {
     const int hi3 = lane >> 3, lo3 = lane & 7;
     const bool act = hi3 < AL;                                   // lane carries a sub-FFT (always for R >= 8)
     const FePartners part = fe_partners(R, lane);
-    int mk[2];
-    fe_mel_first_bin(mk, p, T, lane);
+    int mk[2], mn[2];
+    fe_mel_first_bin(mk, mn, p, T, lane);
 
     // branch-free prefetch: clamped 8-byte pairs, untouched until the next iteration
     int ld_idx[AZ]; FeWinPred<false> ld_w[AZ];
@@ -102,18 +104,18 @@ __global__ __launch_bounds__(256) void fe_kernel_rx(FeParams p) {
         // ---- bands (F5-F8)
         uint32_t* out = ck.out + (uint64_t)f * (uint32_t)p.bands;
         auto store_band = [&](int m, float e) __attribute__((always_inline)) { out[m] = to_u32(e); };
-        if (mel_fast) fe_bands_two<MW>(p, T, s_mwp, P, mk, lane, store_band);
+        if (mel_fast) fe_bands_two<MW>(p, T, s_mwp, P, mk, mn, zslot, lane, store_band);
         else fe_bands_general(p, T, P, lane, FeIdentity(), store_band);
         wave_lds_sync();
     }
 }
 
 template <int R, int AZ, int MW>
-static FeChoice choice_rx(const FeParams& p) {
+static FeChoice choice_rx(const FeParams& p, const char* name) {
     // dynamic LDS up to the device limit (160 KB per workgroup on gfx950) needs no opt-in on ROCm; a configuration
     // that asks for more fails the launch and is reported through hipGetLastError by the caller
     FeChoice c;
-    c.kernel = fe_kernel_rx<R, AZ, MW>;
+    c.kernel = fe_kernel_rx<R, AZ, MW>; c.name = name;
     c.lds = fe_lds(p.mel_total, p.bands, p.kmax, 0, R - 1, AZ, MW).total;
     c.grid_2d = true;
     return c;
@@ -122,11 +124,11 @@ static FeChoice choice_rx(const FeParams& p) {
 // the smallest instantiation whose non-zero blocks cover the window
 FeChoice fe_select_rx(const FeParams& p, int R) {
     const int az = (p.win + 127) / 128;       // non-zero 64-point blocks of packed input
-    if (R == 2) return choice_rx<2, 2, 12>(p);
-    if (R == 4) return az <= 2 ? choice_rx<4, 2, 12>(p) : choice_rx<4, 4, 12>(p);
-    if (R == 16) return az <= 5 ? choice_rx<16, 5, 14>(p) : az <= 8 ? choice_rx<16, 8, 14>(p) : choice_rx<16, 16, 14>(p);
-    if (R == 32) return az <= 10 ? choice_rx<32, 10, 14>(p) : az <= 16 ? choice_rx<32, 16, 14>(p) : choice_rx<32, 32, 14>(p);
-    if (R == 64) return choice_rx<64, 64, 14>(p);
+    if (R == 2) return choice_rx<2, 2, 12>(p, "fe_kernel_rx<2,2,12>");
+    if (R == 4) return az <= 2 ? choice_rx<4, 2, 12>(p, "fe_kernel_rx<4,2,12>") : choice_rx<4, 4, 12>(p, "fe_kernel_rx<4,4,12>");
+    if (R == 16) return az <= 5 ? choice_rx<16, 5, 14>(p, "fe_kernel_rx<16,5,14>") : az <= 8 ? choice_rx<16, 8, 14>(p, "fe_kernel_rx<16,8,14>") : choice_rx<16, 16, 14>(p, "fe_kernel_rx<16,16,14>");
+    if (R == 32) return az <= 10 ? choice_rx<32, 10, 14>(p, "fe_kernel_rx<32,10,14>") : az <= 16 ? choice_rx<32, 16, 14>(p, "fe_kernel_rx<32,16,14>") : choice_rx<32, 32, 14>(p, "fe_kernel_rx<32,32,14>");
+    if (R == 64) return choice_rx<64, 64, 14>(p, "fe_kernel_rx<64,64,14>");
     return FeChoice();
 }
 

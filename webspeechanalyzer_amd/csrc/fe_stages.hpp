@@ -16,21 +16,22 @@ __host__ __device__ inline size_t fe_tables_bytes(int mel_total, int bands) {
     return ((shared_words + 3) & ~(size_t)3) * 4;
 }
 // the 1024-point family: the waves' exchange buffers (the power rows live in them), then the W_512 table of the <.., true> variants [7][64] and the
-// split twiddles of the baseline instantiation [5][64]
-struct FeLdsR8 { size_t wave0, tw1, tws, total; };
+// split twiddles of the baseline instantiation [5][64], and the word of 0.0f that a band's padded taps read (fe_mel_taps)
+struct FeLdsR8 { size_t wave0, tw1, tws, zero, total; };
 __host__ __device__ inline FeLdsR8 fe_lds_r8(int mel_total, int bands) {
     FeLdsR8 L;
     L.wave0 = fe_tables_bytes(mel_total, bands);
     L.tw1 = L.wave0 + (size_t)4 * XBUF * 8;
     L.tws = L.tw1 + (size_t)7 * 64 * 8;
-    L.total = L.tws + (size_t)5 * 64 * 8;
+    L.zero = L.tws + (size_t)5 * 64 * 8;
+    L.total = L.zero + 16;
     return L;
 }
 // the general families: loop invariants that do not fit the register file next to 2 R data registers live in LDS, one
 // conflict-free [..][lane] row per use.  tw3_rows: W_N2^{(64 aM + lane) k3}, [k3 - 1][aM][lane] v2f (NFFT = 3 * 2^k only);
 // twl_rows: the inter-pass twiddles W^{lane k}, [k - 1][lane] v2f; pad_k: split twiddles and power rows reach at least this bin
-// (the AF > 0 instantiation: up to the last bin of the rows it keeps)
-struct FeLds { size_t tw3, twl, tws, wn, mwp, wave0, xbytes, pbytes, total; };
+// (the AF > 0 instantiation: up to the last bin of the rows it keeps); zero: the word of 0.0f that a band's padded taps read (fe_mel_taps)
+struct FeLds { size_t tw3, twl, tws, wn, mwp, wave0, xbytes, pbytes, zero, total; };
 __host__ __device__ inline FeLds fe_lds(int mel_total, int bands, int kmax, int tw3_rows, int twl_rows, int AZ, int MW, int pad_k = 0) {
     if (pad_k > kmax) kmax = pad_k;
     FeLds L;
@@ -42,7 +43,8 @@ __host__ __device__ inline FeLds fe_lds(int mel_total, int bands, int kmax, int 
     L.wave0 = L.mwp + (size_t)2 * MW * 64 * 4;
     L.xbytes = (size_t)XBUF * 8;
     L.pbytes = (size_t)((kmax + 1 + 3) & ~3) * 4;
-    L.total = L.wave0 + 4 * (L.xbytes + L.pbytes);
+    L.zero = L.wave0 + 4 * (L.xbytes + L.pbytes);
+    L.total = L.zero + 16;
     return L;
 }
 
@@ -77,8 +79,8 @@ template <int AZ>
 __device__ __forceinline__ void fe_fill_window(v2f* s_wn, const FeParams& p) {
     for (int i = threadIdx.x; i < AZ * 64; i += 256) s_wn[i] = fe_window_pair(p, 2 * (64 * (i >> 6) + (i & 63)));
 }
-// [q][j][lane]: tap j of band lane + 64 q, zero padded (a padded tap contributes fmaf(0, P, e) = e exactly, so the fixed-length chain equals the
-// FE-1 chain).  Reads the shared tables: behind their barrier.  Returns mel_fast: every band's taps fit and each lane has at most two bands.
+// [q][j][lane]: tap j of band lane + 64 q, zero padded (a padded tap multiplies the zero word, not a power bin: fe_mel_taps).  Reads the shared
+// tables: behind their barrier.  Returns mel_fast: every band's taps fit and each lane has at most two bands.
 template <int MW>
 __device__ __forceinline__ bool fe_fill_taps(float* s_mwp, const FeTables& T, const FeParams& p) {
     bool taps_fit = true;
@@ -346,36 +348,39 @@ __device__ __forceinline__ void fe_bands_general(const FeParams& p, const FeTabl
         store(m, e);
     }
 }
-// the two-band form (mel_fast: at most 128 bands, lane takes m = lane and lane + 64, fixed-length chains over zero-padded taps), in two steps so that a
+// the two-band form (mel_fast: at most 128 bands, lane takes m = lane and lane + 64, fixed-length chains whose padded taps multiply the zero word), in two steps so that a
 // caller can request the taps of both bands — or put other work — before the first multiply-add: the wave issues nothing while it waits for a read
-// first bin of the lane's two bands
-__device__ __forceinline__ void fe_mel_first_bin(int (&mk)[2], const FeParams& p, const FeTables& T, int lane) {
+// first bin and tap count of the lane's two bands
+__device__ __forceinline__ void fe_mel_first_bin(int (&mk)[2], int (&mn)[2], const FeParams& p, const FeTables& T, int lane) {
 #pragma unroll
-    for (int q = 0; q < 2; q++) { const int m = lane + 64 * q; mk[q] = (p.spec_type == 1 && m < p.bands) ? T.k0[m] : 0; }
+    for (int q = 0; q < 2; q++) { const int m = lane + 64 * q; const bool has = p.spec_type == 1 && m < p.bands; mk[q] = has ? T.k0[m] : 0; mn[q] = has ? T.cnt[m] : 0; }
 }
-// the first n of a band's MW taps; padded taps read a valid P slot (pmax)
+// The first n of a band's MW taps, cnt of them its own.  A padded tap (j >= cnt) must leave the chain's e alone WHATEVER the power row holds: its weight is
+// 0, but fmaf(0, P, e) is e only while P is finite — one bin can overflow to Inf beside finite neighbours (a loud tone under a small pre_norm_gain), and
+// 0 * Inf = NaN would turn a band into 0 that FE-1 gives a value.  So a padded tap reads the word of 0.0f at P[zslot] instead of a bin (0 * 0 + e = e for
+// every e the chain can hold: e is never -0).  The tap addresses are loop invariants either way: nothing is added to the frame loop.
 template <int MW, class PIdx>
-__device__ __forceinline__ void fe_mel_taps(float (&pv)[MW], const float* P, int k0, int n, int pmax, PIdx pidx) {
+__device__ __forceinline__ void fe_mel_taps(float (&pv)[MW], const float* P, int k0, int cnt, int n, int zslot, PIdx pidx) {
 #pragma unroll
-    for (int j = 0; j < MW; j++) if (j < n) { const int k = k0 + j; pv[j] = P[pidx(k <= pmax ? k : pmax)]; }
+    for (int j = 0; j < MW; j++) if (j < n) pv[j] = P[j < cnt ? pidx(k0 + j) : zslot];
 }
 template <int MW>
 __device__ __forceinline__ float fe_mel_chain(const float (&w)[MW], const float (&pv)[MW], int n, float emph, float gain) {
     float e = 0.f;
 #pragma unroll
-    for (int j = 0; j < MW; j++) if (j < n) e = __builtin_fmaf(w[j], pv[j], e);       // (a dropped tap is a zero weight: fmaf(0, P, e) = e)
+    for (int j = 0; j < MW; j++) if (j < n) e = __builtin_fmaf(w[j], pv[j], e);       // (a padded tap is 0 * 0: fe_mel_taps; a tap dropped by n < MW has a zero weight in every band the caller admits)
     e = e * emph;
     return e * gain;
 }
 // ... with the weights in the padded LDS table of fe_fill_taps (the general families)
 template <int MW, class Store>
-__device__ __forceinline__ void fe_bands_two(const FeParams& p, const FeTables& T, const float* s_mwp, const float* P, const int (&mk)[2], int lane, Store store) {
+__device__ __forceinline__ void fe_bands_two(const FeParams& p, const FeTables& T, const float* s_mwp, const float* P, const int (&mk)[2], const int (&mn)[2], int zslot, int lane, Store store) {
 #pragma unroll
     for (int q = 0; q < 2; q++) {
         const int m = lane + 64 * q;
         // (taps and weights of the band requested before the first multiply-add)
         float pvq[MW], wq[MW];
-        fe_mel_taps<MW>(pvq, P, mk[q], MW, p.kmax, FeIdentity());
+        fe_mel_taps<MW>(pvq, P, mk[q], mn[q], MW, zslot, FeIdentity());
 #pragma unroll
         for (int j = 0; j < MW; j++) wq[j] = s_mwp[(q * MW + j) * 64 + lane];
         const float e = fe_mel_chain<MW>(wq, pvq, MW, T.emph[m < p.bands ? m : 0], p.gain);
@@ -389,6 +394,7 @@ __device__ __forceinline__ void fe_bands_two(const FeParams& p, const FeTables& 
 typedef void (*FeKernel)(FeParams);
 struct FeChoice {
     FeKernel kernel = nullptr;
+    const char* name = "";      // the instantiation as profiles/frontend_split.md writes it (wsa_debug_fe_choice: the tests assert which one a geometry runs)
     size_t lds = 0;             // dynamic LDS bytes
     int queue_wgs = 0;          // persistent launch: most workgroups per CU Tuning::fe_wg_per_cu may ask for (default 2); 0: the kernel takes no queue
     bool grid_2d = false;       // one chunk per workgroup as grid (chunk of the clip, clip); else as a flat grid of chunks

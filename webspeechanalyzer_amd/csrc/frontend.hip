@@ -33,13 +33,16 @@ void launch_frontend(const FeParams& p, int n_clips, int max_frames, int R, int 
 }
 
 // dynamic LDS the front-end kernel of this geometry asks for (a workgroup may have 160 KB on gfx950; wsa_batch_create / wsa_stream_create refuse settings beyond that)
-size_t fe_lds_required(const FePlanHost& P, bool fat) {
+static FeChoice fe_choice_of_plan(const FePlanHost& P, bool fat) {
     FeParams p{};
     p.win = P.win; p.hop = P.hop; p.kmax = P.kmax; p.bands = P.bands; p.spec_type = P.spec_type; p.mel_total = (int)P.mel_w.size();
     for (int32_t c_ : P.mel_cnt) if (c_ > p.mel_max_taps) p.mel_max_taps = c_;
     for (size_t i_ = 0; i_ < P.mel_cnt.size() && i_ < 64; i_++) if (P.mel_cnt[i_] > p.mel_max_taps_lo) p.mel_max_taps_lo = P.mel_cnt[i_];
     p.fat = fat ? 1 : 0;
-    return fe_select(p, P.R, P.three).lds;
+    return fe_select(p, P.R, P.three);
 }
+size_t fe_lds_required(const FePlanHost& P, bool fat) { return fe_choice_of_plan(P, fat).lds; }
+// the instantiation this geometry runs, as profiles/frontend_split.md names it ("" for an FFT length no family serves); launches nothing
+const char* fe_choice_name(const FePlanHost& P, bool fat) { return fe_supported_R(P.R, P.three) ? fe_choice_of_plan(P, fat).name : ""; }
 
 }  // namespace wsa

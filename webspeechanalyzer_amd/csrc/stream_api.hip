@@ -304,6 +304,11 @@ wsa_status wsa_stream_create_mixed(wsa_ctx* ctx, uint32_t n_streams, const doubl
     return create_impl(ctx, n_streams, fs_in, fs_out, frames_per_step, max_span_frames, out);
 }
 
+const uint32_t* wsa_stream_spec_internal(wsa_stream* b, wsa_ctx** ctx, uint32_t* n_streams, uint32_t* frames_per_step, uint32_t* bands) {
+    *ctx = b->ctx; *n_streams = b->n; *frames_per_step = b->F; *bands = (uint32_t)b->fe.plan.bands;
+    return b->d_spec;
+}
+
 uint32_t wsa_stream_samples_per_step(const wsa_stream* b) { return b ? b->step_samples : 0; }
 uint32_t wsa_stream_input_capacity(const wsa_stream* b, uint32_t i) { return !b || i >= b->n ? 0 : (b->mixed ? b->in_cap[i] : b->step_samples); }
 uint32_t wsa_stream_input_stride(const wsa_stream* b) { return b ? b->in_stride : 0; }
