@@ -1013,6 +1013,47 @@ wsa_status wsa_stream_time_steps_packed(wsa_stream *st, uint32_t n_steps, const 
  * an unknown format, channels outside 1 .. 64, a NULL buffer with n_frames > 0. */
 wsa_status wsa_pcm_decode(int32_t format, const void *in, uint64_t n_frames, uint32_t channels, float *out);
 
+/*
+ * ---- Every PCM encoding a WAV holds into batches, unpacked on the GPU (additions within version 5: probe for wsa_batch_run_host_packed).
+ *
+ * The batch counterpart of the packed stream input, spec PK-2: a batch's clips go to the device as the bytes the file
+ * holds, every clip in its own format and with its own channel count, and ONE kernel (batch_unpack_kernel) turns channel 0 of each clip
+ * into the floats the float path would have been given.  A run on packed clips gives byte for byte what the same batch gives through
+ * wsa_batch_run_host on wsa_pcm_decode(packed): every result table, wsa_batch_copy_pcm on resampling batches, every attached model's
+ * output — at every output level, on plain, resampled and mixed-rate batches.
+ *   - The formats of PK-1 (WSA_PCM_F32 .. WSA_PCM_ALAW above) and the linear encodings below, little-endian as a WAV holds them.
+ *     Numbers 4 .. 7 are unassigned (kept for further 8-bit companded codes) and refused everywhere.
+ *       WSA_PCM_U8   1 byte            (x - 128) / 128                                   exact
+ *       WSA_PCM_I24  3 bytes, packed   the sign-extended value / 2^23                    exact in fp32
+ *       WSA_PCM_I32  4 bytes           (float)x / 2^31, converted to nearest even        2^31 - 1 gives 1.0f
+ *       WSA_PCM_F64  8 bytes           the double rounded to fp32, nearest even          overflow gives +-Inf, -0 is kept, results below 2^-126
+ *                                                                                        are fp32 denormals and are kept, NaN stays NaN
+ *     WSA_PCM_F32 with more than one channel is legal for batches (interleaved floats, channel 0 copied bit for bit); streams keep
+ *     refusing it, and wsa_stream_set_input_format keeps refusing 8 .. 11: these are file encodings.
+ *   - Clip i is n_samples(_in)[i] frames interleaved over channels[i] channels (1 .. 64; NULL: all mono): sample j is element
+ *     j * channels[i] of the clip's bytes.  Bytes behind a clip's last frame and the other channels never influence a result; floats
+ *     behind a clip's count in its staging row are not written.
+ * wsa_batch_run_host_packed: clips in host memory (clip i at pcm[i], any alignment); one upload per clip (clips that lie back to back
+ * in one wsa_host_alloc slab travel merged where the device layout allows it), then the unpack kernel, then the run.
+ * wsa_batch_set_input_format plans the device-resident layout once — the descriptor table is uploaded and the float staging
+ * allocated — and is legal before a run and between a result and the next run.  wsa_batch_packed_offset(b, i) is then the byte
+ * offset of clip i (a multiple of 16), and with i == n_clips the number of bytes to provide.  wsa_batch_run_packed reads
+ * device-resident packed clips at d_packed + offset(i) (d_packed aligned to 16 bytes): kernel launches only, nothing is allocated, the
+ * call can be captured into a hipGraph like wsa_batch_run.
+ * WSA_ERR_INVALID with a message that names the clip: an unknown format (4 .. 7 included), channels outside 1 .. 64;
+ * wsa_batch_run_packed before wsa_batch_set_input_format, or with a NULL or misaligned d_packed.
+ * wsa_pcm_decode knows the same formats, any channel count 1 .. 64 for each.
+ */
+#define WSA_PCM_U8    8   /* unsigned 8-bit, as an 8-bit WAV holds it */
+#define WSA_PCM_I24   9   /* signed 24-bit, 3 bytes per sample, little-endian */
+#define WSA_PCM_I32  10   /* signed 32-bit, little-endian */
+#define WSA_PCM_F64  11   /* IEEE double, little-endian */
+wsa_status wsa_batch_run_host_packed(wsa_batch *b, const void *const *pcm, const int32_t *formats /* [n_clips] */,
+                                     const uint32_t *channels /* [n_clips], NULL = mono */, void *stream);
+wsa_status wsa_batch_set_input_format(wsa_batch *b, const int32_t *formats, const uint32_t *channels);
+uint64_t   wsa_batch_packed_offset(const wsa_batch *b, uint32_t clip);   /* 0 before wsa_batch_set_input_format and for clip > n_clips */
+wsa_status wsa_batch_run_packed(wsa_batch *b, const void *d_packed, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

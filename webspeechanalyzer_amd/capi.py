@@ -216,10 +216,15 @@ ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destr
                "wsa_train_group_launch_count",
                # additions within version 5 (probe for wsa_stream_set_input_format): 16-bit and G.711 PCM into streams, unpacked in the step (spec PK-1)
                "wsa_stream_set_input_format", "wsa_stream_host_input_packed", "wsa_stream_input_stride_bytes", "wsa_stream_step_packed",
-               "wsa_stream_time_steps_packed", "wsa_pcm_decode"]
+               "wsa_stream_time_steps_packed", "wsa_pcm_decode",
+               # additions within version 5 (probe for wsa_batch_run_host_packed): every PCM encoding a WAV holds into batches, unpacked on the GPU (spec PK-2)
+               "wsa_batch_run_host_packed", "wsa_batch_set_input_format", "wsa_batch_packed_offset", "wsa_batch_run_packed"]
 PCM_F32, PCM_I16, PCM_MULAW, PCM_ALAW = 0, 1, 2, 3      # WSA_PCM_* of include/wsa.h
-_PCM_NAMES = {"f32": PCM_F32, "i16": PCM_I16, "mulaw": PCM_MULAW, "alaw": PCM_ALAW}
-_PCM_DTYPE = {PCM_F32: np.float32, PCM_I16: np.int16, PCM_MULAW: np.uint8, PCM_ALAW: np.uint8}
+PCM_U8, PCM_I24, PCM_I32, PCM_F64 = 8, 9, 10, 11        # ... the file encodings of spec PK-2 (batches and pcm_decode; 4 .. 7 are unassigned)
+_PCM_NAMES = {"f32": PCM_F32, "i16": PCM_I16, "mulaw": PCM_MULAW, "alaw": PCM_ALAW, "u8": PCM_U8, "i24": PCM_I24, "i32": PCM_I32, "f64": PCM_F64}
+_PCM_DTYPE = {PCM_F32: np.float32, PCM_I16: np.int16, PCM_MULAW: np.uint8, PCM_ALAW: np.uint8,
+              PCM_U8: np.uint8, PCM_I24: np.uint8, PCM_I32: np.int32, PCM_F64: np.float64}
+_PCM_ELEMS = {PCM_I24: 3}                               # array elements per sample ('i24': three uint8)
 TRAIN_GROUP_MAX = 32       # WSA_TRAIN_GROUP_MAX of include/wsa.h
 
 _LIB = None
@@ -395,8 +400,13 @@ def lib():
     L.wsa_stream_step_packed.argtypes = [vp, vp, u64, vp, vp, vp]
     L.wsa_stream_time_steps_packed.argtypes = [vp, u32, vp, u32, vp, vp, vp]
     L.wsa_pcm_decode.argtypes = [i32, vp, u64, u32, vp]
+    L.wsa_batch_run_host_packed.argtypes = [vp, vp, vp, vp, vp]
+    L.wsa_batch_set_input_format.argtypes = [vp, vp, vp]
+    L.wsa_batch_packed_offset.argtypes = [vp, u32]
+    L.wsa_batch_packed_offset.restype = u64
+    L.wsa_batch_run_packed.argtypes = [vp, vp, vp]
     for name in ABI_SYMBOLS:
-        if name in _U32_RESULT or name in ("wsa_resample_ready", "wsa_level_feature_count"):
+        if name in _U32_RESULT or name in ("wsa_resample_ready", "wsa_level_feature_count", "wsa_batch_packed_offset"):
             continue
         if name not in ("wsa_abi_version", "wsa_last_error", "wsa_config_default", "wsa_destroy", "wsa_batch_destroy", "wsa_resample_length",
                         "wsa_stream_destroy", "wsa_stream_samples_per_step", "wsa_stream_host_input", "wsa_stream_host_input_packed", "wsa_gather_destroy", "wsa_host_free",
@@ -408,28 +418,35 @@ def lib():
 
 
 def pcm_format(fmt):
-    """A WSA_PCM_* number from a number or one of 'f32', 'i16', 'mulaw', 'alaw'; anything else is refused."""
+    """A WSA_PCM_* number from a number or one of 'f32', 'i16', 'mulaw', 'alaw', 'u8', 'i24', 'i32', 'f64'; anything else is refused."""
     if isinstance(fmt, str):
         if fmt not in _PCM_NAMES:
-            raise WsaError(f"unknown input format {fmt!r} ('f32', 'i16', 'mulaw', 'alaw')")
+            raise WsaError(f"unknown input format {fmt!r} ('f32', 'i16', 'mulaw', 'alaw', 'u8', 'i24', 'i32', 'f64')")
         return _PCM_NAMES[fmt]
     if isinstance(fmt, (bool, float)) or int(fmt) not in _PCM_DTYPE:
-        raise WsaError(f"unknown input format {fmt!r} (PCM_F32 0, PCM_I16 1, PCM_MULAW 2, PCM_ALAW 3)")
+        raise WsaError(f"unknown input format {fmt!r} (PCM_F32 0, PCM_I16 1, PCM_MULAW 2, PCM_ALAW 3, PCM_U8 8, PCM_I24 9, PCM_I32 10, PCM_F64 11)")
     return int(fmt)
 
 
+def _pcm_array(fmt, f, array):
+    """`array` as the contiguous flat samples of format `f`; the wrong sample type is refused, never converted."""
+    a = np.ascontiguousarray(array)
+    if a.dtype != _PCM_DTYPE[f]:
+        raise WsaError(f"format {fmt!r} takes {np.dtype(_PCM_DTYPE[f]).name} samples, not {a.dtype.name}")
+    return a.reshape(-1)
+
+
 def pcm_decode(fmt, array, channels=1):
-    """Spec PK-1 on the host (wsa_pcm_decode, no device): channel 0 of the interleaved frames in `array` (int16 for 'i16', uint8 for the
-    G.711 laws, float32 for 'f32'; a trailing partial frame is ignored) as float32 — the floats a stream set fed `array` analyses."""
+    """Specs PK-1 / PK-2 on the host (wsa_pcm_decode, no device): channel 0 of the interleaved frames in `array` (int16 for 'i16', uint8 for
+    the G.711 laws and 'u8', three uint8 per sample for 'i24', int32 for 'i32', float64 for 'f64', float32 for 'f32'; a trailing partial
+    frame is ignored) as float32 — the floats a stream set or a batch fed `array` analyses."""
     f = pcm_format(fmt)
     ch = int(channels)
     if not 1 <= ch <= 64:
         raise WsaError(f"channel count {ch} outside 1 .. 64")
-    a = np.ascontiguousarray(array)
-    if a.dtype != _PCM_DTYPE[f]:
-        raise WsaError(f"format {fmt!r} takes {np.dtype(_PCM_DTYPE[f]).name} samples, not {a.dtype.name}")
-    a = a.reshape(-1)
-    n = (a.size - 1) // ch + 1 if a.size else 0      # frames whose channel 0 is present
+    a = _pcm_array(fmt, f, array)
+    size = a.size // _PCM_ELEMS.get(f, 1)            # whole samples
+    n = (size - 1) // ch + 1 if size else 0          # frames whose channel 0 is present
     out = np.zeros(n, np.float32)
     if lib().wsa_pcm_decode(f, a.ctypes.data, n, ch, out.ctypes.data) != 0:
         raise WsaError("wsa_pcm_decode refused its arguments")
@@ -607,6 +624,46 @@ class Batch:
         ptrs = (ctypes.c_void_p * len(clips))(*[c.ctypes.data for c in clips])
         ch = None if channels is None else (ctypes.c_uint32 * len(clips))(*[int(c) for c in channels])
         self.an._check(self.L.wsa_batch_run_host_i16(self.h, ptrs, ch, stream))
+
+    def _formats(self, formats, channels):
+        n = len(self.n_samples)
+        fm = [formats] * n if isinstance(formats, (str, int)) else list(formats)
+        if len(fm) != n or (channels is not None and len(channels) != n):
+            raise WsaError("one format (and one channel count) per clip")
+        # (numbers go to the library as they are: it names the clip when it refuses one)
+        fm = (ctypes.c_int32 * max(n, 1))(*[pcm_format(f) if isinstance(f, str) else int(f) for f in fm])
+        ch = None if channels is None else (ctypes.c_uint32 * max(n, 1))(*[int(c) for c in channels])
+        return fm, ch
+
+    def run_host_packed(self, clips, formats, channels=None, stream=0):
+        """Clips in host memory as the bytes a file holds (spec PK-2): clip i in formats[i] ('f32', 'i16', 'mulaw', 'alaw', 'u8', 'i24', 'i32',
+        'f64' or the numbers; one name for all clips is fine), interleaved over channels[i] channels, channel 0 analysed; unpacked on the device.
+        The arrays have the format's sample type (as pcm_decode takes them) and hold at least the plan's frames."""
+        fm, ch = self._formats(formats, channels)
+        held = []
+        ns_in = getattr(self, "n_samples_in", self.n_samples)
+        for i, c in enumerate(clips):
+            f = int(fm[i])
+            a = _pcm_array(f, f, c) if f in _PCM_DTYPE else np.ascontiguousarray(c).reshape(-1)
+            need = int(ns_in[i]) * (int(ch[i]) if ch is not None else 1) * _PCM_ELEMS.get(f, 1)
+            if f in _PCM_DTYPE and a.size < need:
+                raise WsaError(f"clip {i}: {a.size} elements, the plan's {int(ns_in[i])} frames need {need}")
+            held.append(a)
+        ptrs = (ctypes.c_void_p * max(len(held), 1))(*[a.ctypes.data for a in held])
+        self.an._check(self.L.wsa_batch_run_host_packed(self.h, ptrs, fm, ch, stream))
+
+    def set_input_format(self, formats, channels=None):
+        """Plans the device-resident packed layout (wsa_batch_set_input_format): packed_offsets() says where each clip's bytes go."""
+        fm, ch = self._formats(formats, channels)
+        self.an._check(self.L.wsa_batch_set_input_format(self.h, fm, ch))
+
+    def packed_offsets(self):
+        """uint64 [n_clips + 1]: clip i's bytes start at offset i (a multiple of 16) of the packed buffer, the last entry is the buffer's size."""
+        return np.array([self.L.wsa_batch_packed_offset(self.h, i) for i in range(len(self.n_samples) + 1)], np.uint64)
+
+    def run_packed(self, d_packed, stream=0):
+        """Device-resident packed clips at d_packed + packed_offsets()[i] (a raw device pointer, 16-byte aligned): kernel launches only."""
+        self.an._check(self.L.wsa_batch_run_packed(self.h, d_packed, stream))
 
     def enable_timing(self, on):
         self.an._check(self.L.wsa_batch_enable_timing(self.h, int(on)))

@@ -13,6 +13,7 @@
 #include <system_error>
 #include <thread>
 #include "host_plan.hpp"
+#include "pcm_formats.hpp"
 
 using namespace wsa;
 
@@ -37,6 +38,10 @@ struct wsa_batch {
     hipStream_t up_stream[8] = {}; hipEvent_t up_event[8] = {}, up_start = nullptr; bool up_ready = false;   // upload_clips
     int16_t* d_i16 = nullptr; uint64_t i16_cap = 0; uint64_t* d_i16_off = nullptr; uint32_t *d_i16_ch = nullptr, *d_i16_ns = nullptr;   // wsa_batch_run_host_i16: upload buffer (own allocation, grows) + clip tables
     std::vector<uint64_t> h_i16_off; std::vector<uint32_t> h_i16_ch;
+    // packed clips of any format (spec PK-2, batch_pcm.hip).  wsa_batch_run_host_packed: upload buffer (own allocation, grows) + its descriptor table;
+    // wsa_batch_set_input_format / wsa_batch_run_packed: the planned layout's table and offsets — two tables, so that a host run never rewrites what a captured graph reads
+    uint8_t* d_pk = nullptr; uint64_t pk_cap = 0; PcmClipDesc* d_pk_desc = nullptr; std::vector<PcmClipDesc> h_pk_desc;
+    PcmClipDesc* d_pkf_desc = nullptr; std::vector<uint64_t> pkf_off; bool pkf_set = false;
     bool pair = false;                   // tracker: two spans per wave (tracker_kernel_pair)
     bool published = false;              // the last back-end run's compaction kernel has handed the result counters to the host itself
     Tuning tune;                         // tuning / test switches, read from the environment when the batch is planned
@@ -164,6 +169,7 @@ void wsa_batch_destroy(wsa_batch* b) {
     if (!b) return;
     (void)hipSetDevice(b->ctx->device);
     if (b->d_i16) (void)hipFree(b->d_i16);
+    if (b->d_pk) (void)hipFree(b->d_pk);
     for (auto& st : b->up_stream) if (st) (void)hipStreamDestroy(st);
     for (auto& e : b->up_event) if (e) (void)hipEventDestroy(e);
     if (b->up_start) (void)hipEventDestroy(b->up_start);
@@ -597,6 +603,81 @@ wsa_status wsa_batch_run_host_i16(wsa_batch* b, const int16_t* const* pcm, const
         hipLaunchKernelGGL(pcm_i16_to_f32_kernel, dim3((mx + 1023) / 1024 ? (mx + 1023) / 1024 : 1, b->n_clips), dim3(256), 0, s, b->d_i16, b->d_i16_off, b->d_i16_ch, b->d_i16_ns, b->d_pcm_own, stride);
         HIP_TRY(ctx, hipGetLastError());
     }
+    return run_impl(b, b->d_pcm_own, stride, nullptr, true, true, s);
+}
+
+// PK-2: the clips' formats and channel counts -> one descriptor per clip, clip i's bytes at a multiple of 16; off [n_clips + 1], off[n_clips] = bytes in all
+static wsa_status plan_packed(wsa_batch* b, const int32_t* formats, const uint32_t* channels, std::vector<PcmClipDesc>& desc, std::vector<uint64_t>& off) {
+    wsa_ctx* ctx = b->ctx;
+    if (!formats && b->n_clips) return fail(ctx, WSA_ERR_INVALID, "null formats: one WSA_PCM_* number per clip");
+    const std::vector<uint32_t>& ns_host = b->rs_on ? b->n_samples_in : b->n_samples;
+    desc.assign(b->n_clips ? b->n_clips : 1, PcmClipDesc{}); off.assign((size_t)b->n_clips + 1, 0);
+    for (uint32_t i = 0; i < b->n_clips; i++) {
+        const uint32_t ch = channels ? channels[i] : 1u;
+        if (!pcm_format_known(formats[i]))
+            return fail(ctx, WSA_ERR_INVALID, "clip " + std::to_string(i) + ": unknown input format " + std::to_string(formats[i])
+                        + " (WSA_PCM_F32 0, WSA_PCM_I16 1, WSA_PCM_MULAW 2, WSA_PCM_ALAW 3, WSA_PCM_U8 8, WSA_PCM_I24 9, WSA_PCM_I32 10, WSA_PCM_F64 11)");
+        if (ch < 1 || ch > 64) return fail(ctx, WSA_ERR_INVALID, "clip " + std::to_string(i) + ": channel count " + std::to_string(ch) + " outside 1 .. 64");
+        desc[i].offset = off[i]; desc[i].format = formats[i]; desc[i].channels = ch; desc[i].n_frames = ns_host[i];
+        off[i + 1] = off[i] + (((uint64_t)ns_host[i] * ch * pcm_sample_bytes(formats[i]) + 15u) & ~15ull);
+    }
+    return WSA_OK;
+}
+
+wsa_status wsa_batch_run_host_packed(wsa_batch* b, const void* const* pcm, const int32_t* formats, const uint32_t* channels, void* stream) {
+    if (!b || (!pcm && b->n_clips)) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = b->ctx;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    std::vector<PcmClipDesc> desc; std::vector<uint64_t> off;
+    { const wsa_status st = plan_packed(b, formats, channels, desc, off); if (st != WSA_OK) return st; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t stride = ((b->rs_on ? b->max_samples_in : b->max_samples) + 3u) & ~3ull;
+    if (!b->d_pcm_own && !b->mem.alloc(&b->d_pcm_own, (size_t)b->n_clips * stride)) return fail(ctx, WSA_ERR_HIP, "PCM staging allocation failed");
+    if (!b->d_pk || off[b->n_clips] > b->pk_cap) {                  // one upload buffer, grown when a run needs more than the last one
+        if (b->d_pk) { (void)hipFree(b->d_pk); b->d_pk = nullptr; b->pk_cap = 0; }
+        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&b->d_pk), (size_t)off[b->n_clips] + 16));
+        b->pk_cap = off[b->n_clips];
+    }
+    if (!b->d_pk_desc && !b->mem.alloc(&b->d_pk_desc, (size_t)b->n_clips)) return fail(ctx, WSA_ERR_HIP, "packed clip table allocation failed");
+    b->h_pk_desc = desc;                                           // (the table travels from a buffer the batch owns: the copy is asynchronous)
+    HIP_TRY(ctx, hipMemcpyAsync(b->d_pk_desc, b->h_pk_desc.data(), b->h_pk_desc.size() * sizeof(PcmClipDesc), hipMemcpyHostToDevice, s));
+    {
+        const wsa_status st = upload_clips(b, b->n_clips, [&](uint32_t i) { return b->d_pk + off[i]; }, [&](uint32_t i) { return pcm[i]; },
+                                           [&](uint32_t i) { return (size_t)desc[i].n_frames * desc[i].channels * pcm_sample_bytes(desc[i].format); }, s);
+        if (st != WSA_OK) return st;
+    }
+    launch_batch_unpack(b->d_pk, b->d_pk_desc, b->n_clips, b->rs_on ? b->max_samples_in : b->max_samples, b->d_pcm_own, stride, s);
+    HIP_TRY(ctx, hipGetLastError());
+    return run_impl(b, b->d_pcm_own, stride, nullptr, true, true, s);
+}
+
+wsa_status wsa_batch_set_input_format(wsa_batch* b, const int32_t* formats, const uint32_t* channels) {
+    if (!b) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = b->ctx;
+    std::vector<PcmClipDesc> desc; std::vector<uint64_t> off;
+    { const wsa_status st = plan_packed(b, formats, channels, desc, off); if (st != WSA_OK) return st; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t stride = ((b->rs_on ? b->max_samples_in : b->max_samples) + 3u) & ~3ull;
+    if (!b->d_pcm_own && !b->mem.alloc(&b->d_pcm_own, (size_t)b->n_clips * stride)) return fail(ctx, WSA_ERR_HIP, "PCM staging allocation failed");
+    if (!b->d_pkf_desc && !b->mem.alloc(&b->d_pkf_desc, (size_t)b->n_clips)) return fail(ctx, WSA_ERR_HIP, "packed clip table allocation failed");
+    HIP_TRY(ctx, hipMemcpy(b->d_pkf_desc, desc.data(), desc.size() * sizeof(PcmClipDesc), hipMemcpyHostToDevice));
+    b->pkf_off = off; b->pkf_set = true;
+    return WSA_OK;
+}
+
+uint64_t wsa_batch_packed_offset(const wsa_batch* b, uint32_t clip) { return b && b->pkf_set && clip <= b->n_clips ? b->pkf_off[clip] : 0; }
+
+wsa_status wsa_batch_run_packed(wsa_batch* b, const void* d_packed, void* stream) {
+    if (!b) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = b->ctx;
+    if (!b->pkf_set) return fail(ctx, WSA_ERR_INVALID, "wsa_batch_run_packed before wsa_batch_set_input_format: the clips' formats and offsets are not planned");
+    if (!d_packed && b->pkf_off[b->n_clips]) return fail(ctx, WSA_ERR_INVALID, "wsa_batch_run_packed: null packed pointer");
+    if (reinterpret_cast<uintptr_t>(d_packed) & 15u) return fail(ctx, WSA_ERR_INVALID, "wsa_batch_run_packed: the packed pointer is not aligned to 16 bytes");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t stride = ((b->rs_on ? b->max_samples_in : b->max_samples) + 3u) & ~3ull;
+    launch_batch_unpack(d_packed, b->d_pkf_desc, b->n_clips, b->rs_on ? b->max_samples_in : b->max_samples, b->d_pcm_own, stride, s);
+    HIP_TRY(ctx, hipGetLastError());
     return run_impl(b, b->d_pcm_own, stride, nullptr, true, true, s);
 }
 

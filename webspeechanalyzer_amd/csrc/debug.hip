@@ -1,6 +1,6 @@
 // debug.hip — test entries of libwsa that are NOT part of include/wsa.h: unit access to device-side pieces that the public
 // entry points only exercise through their consequences (tests/test_gpu_units.py, tests/test_gpu_coeffs.py, tests/test_gpu_utterance.py, tests/test_gpu_gate.py,
-// tests/test_gpu_regress_group.py, tests/test_gpu_fold.py, tests/test_gpu_frontend.py).
+// tests/test_gpu_regress_group.py, tests/test_gpu_fold.py, tests/test_gpu_frontend.py, tests/test_gpu_batch_pcm.py).
 #include <cstring>
 #include <vector>
 #include "host_plan.hpp"
@@ -11,6 +11,7 @@
 #include "tracker_features.hpp"
 #include "regress_internal.hpp"
 #include "classify_internal.hpp"
+#include "pcm_formats.hpp"
 
 namespace wsa {
 // fn 0: jsm::log10(x[i]); fn 1: jsm::pow_pos(x[i], y[i]) — the V8 Math.log10 / Math.pow ports the noise gate's
@@ -837,5 +838,36 @@ extern "C" int wsa_debug_class_fold(int32_t device, const wsa_debug_fold_io* io)
     if (ok && !single)
         ok = fold_down(io->cb_db, o.cb_db, K) && fold_down(io->cb_top_label, o.cb_top_label, K) && fold_down(io->cb_top_conf, o.cb_top_conf, K)
              && fold_down(io->cb_min_db, o.cb_min_db, K) && fold_down(io->cb_entropy, o.cb_entropy, K);
+    return ok ? WSA_OK : WSA_ERR_HIP;
+}
+
+// PK-2's kernel (csrc/batch_pcm.hip) on its own: host-given packed bytes through ONE launch of batch_unpack_kernel, floats back.  off [n_clips + 1]:
+// clip i's bytes start at packed + off[i] (a multiple of 16) and lie in front of off[i + 1]; off[n_clips] = the bytes of `packed`.  out [n_clips][stride]
+// goes to the device as the caller filled it and comes back: what the kernel did not write keeps the caller's value.
+// Refused, nothing run: an unknown format, channels outside 1 .. 64, an offset that is no multiple of 16, a clip whose frames do not fit between its
+// offset and the next or into a row of `stride` floats.
+extern "C" int wsa_debug_batch_unpack(int32_t device, const void* packed, const uint64_t* off, const int32_t* formats, const uint32_t* channels,
+                                      const uint32_t* n_frames, uint32_t n_clips, float* out, uint64_t stride) {
+    if (!off || !formats || !channels || !n_frames || !out || n_clips < 1 || n_clips > 65535u || stride < 1 || stride > (1u << 26)) return WSA_ERR_INVALID;
+    if (off[0] != 0 || off[n_clips] > (1ull << 32) || (off[n_clips] && !packed)) return WSA_ERR_INVALID;
+    std::vector<wsa::PcmClipDesc> desc(n_clips);
+    uint32_t max_frames = 0;
+    for (uint32_t i = 0; i < n_clips; i++) {
+        if (!wsa::pcm_format_known(formats[i]) || channels[i] < 1 || channels[i] > 64 || (off[i] & 15u) || off[i + 1] < off[i] || n_frames[i] > stride) return WSA_ERR_INVALID;
+        const uint64_t need = n_frames[i] ? ((uint64_t)(n_frames[i] - 1u) * channels[i] + 1u) * wsa::pcm_sample_bytes(formats[i]) : 0;   // up to channel 0 of the last frame
+        if (need > off[i + 1] - off[i]) return WSA_ERR_INVALID;
+        desc[i] = wsa::PcmClipDesc{off[i], formats[i], channels[i], n_frames[i], {0, 0, 0}};
+        if (n_frames[i] > max_frames) max_frames = n_frames[i];
+    }
+    if (hipSetDevice(device) != hipSuccess) return WSA_ERR_NO_DEVICE;
+    wsa::DevArena A; uint4* dp = nullptr; wsa::PcmClipDesc* dd = nullptr; float* dout = nullptr;
+    const size_t nout = (size_t)n_clips * stride;
+    bool ok = A.alloc(&dp, (size_t)(off[n_clips] + 15u) / 16u) && A.upload(&dd, desc) && A.alloc(&dout, nout)
+           && (off[n_clips] == 0 || hipMemcpy(dp, packed, (size_t)off[n_clips], hipMemcpyHostToDevice) == hipSuccess)
+           && hipMemcpy(dout, out, nout * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        wsa::launch_batch_unpack(dp, dd, n_clips, max_frames, dout, stride, nullptr);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dout, nout * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess;
+    }
     return ok ? WSA_OK : WSA_ERR_HIP;
 }

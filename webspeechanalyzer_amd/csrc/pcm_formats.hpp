@@ -1,5 +1,6 @@
-// pcm_formats.hpp — spec PK-1: a packed sample becomes the float the float path would have been given.  The same
-// functions run on the host (wsa_pcm_decode) and in stream_pull_packed_kernel, integer arithmetic first and one exact division.
+// pcm_formats.hpp — specs PK-1 and PK-2: a packed sample becomes the float the float path would have been given.  The same
+// functions run on the host (wsa_pcm_decode), in stream_pull_packed_kernel and in batch_unpack_kernel: integer arithmetic first, then one
+// conversion and one exact division.
 #pragma once
 #include <cstdint>
 #include <hip/hip_runtime.h>
@@ -27,9 +28,78 @@ __host__ __device__ inline float pcm_decode_one(uint32_t raw) {
     if (FORMAT == WSA_PCM_MULAW) return (float)pcm_mulaw_linear(raw) / 32768.0f;
     return (float)pcm_alaw_linear(raw) / 32768.0f;
 }
-inline uint32_t pcm_sample_bytes(int32_t format) { return format == WSA_PCM_F32 ? 4u : format == WSA_PCM_I16 ? 2u : 1u; }
-inline const char* pcm_format_name(int32_t format) {
-    return format == WSA_PCM_F32 ? "f32" : format == WSA_PCM_I16 ? "i16" : format == WSA_PCM_MULAW ? "mulaw" : format == WSA_PCM_ALAW ? "alaw" : "unknown";
+// ---- PK-2: the linear encodings a WAV holds, little-endian (batches only)
+// 8-bit unsigned: (x - 128) / 128, exact
+__host__ __device__ inline float pcm_u8_f32(uint32_t x) { return (float)((int32_t)(x & 0xFFu) - 128) / 128.0f; }
+// 24-bit signed in the low 24 bits of a word: the sign-extended value / 2^23, exact in fp32
+__host__ __device__ inline float pcm_i24_f32(uint32_t x) { return (float)((int32_t)(x << 8) >> 8) / 8388608.0f; }
+// 32-bit signed: the conversion rounds to nearest even (2^31 - 1 gives 2^31), the division by 2^31 is exact: fl32(x / 2^31)
+__host__ __device__ inline float pcm_i32_f32(uint32_t x) { return (float)(int32_t)x / 2147483648.0f; }
+// the bits of a double -> the bits of the nearest float, ties to even, in integer arithmetic: the result does not depend on a denormal mode
+// (results below 2^-126 are fp32 denormals and are kept), overflow gives +-Inf, -0 stays -0, a NaN stays a (quiet) NaN
+__host__ __device__ inline uint32_t pcm_f64_bits_to_f32_bits(uint64_t b) {
+    const uint32_t sign = (uint32_t)(b >> 32) & 0x80000000u, e = (uint32_t)(b >> 52) & 0x7FFu;
+    const uint64_t m = b & 0xFFFFFFFFFFFFFull;
+    if (e == 0x7FFu) return sign | 0x7F800000u | (m ? 0x400000u | (uint32_t)(m >> 29) : 0u);
+    const int32_t E = (int32_t)e - 1023 + 127;                       // the float's biased exponent
+    if (E >= 255) return sign | 0x7F800000u;
+    if (E >= 1) {                                                    // normal: 23 of the 52 fraction bits, a carry out of them moves the exponent (up to Inf)
+        const uint32_t q = ((uint32_t)E << 23) | (uint32_t)(m >> 29), rem = (uint32_t)m & 0x1FFFFFFFu;
+        return sign | (q + ((rem > 0x10000000u || (rem == 0x10000000u && (q & 1u))) ? 1u : 0u));
+    }
+    if (e == 0 || E < -24) return sign;                              // below half of the smallest denormal (2^-150)
+    const uint32_t sh = 30u - (uint32_t)E;                           // 30 .. 54: the 53-bit significand in units of 2^-149
+    const uint64_t sig = m | (1ull << 52), q = sh >= 64u ? 0ull : sig >> sh, rem = sig & ((1ull << sh) - 1ull), half = 1ull << (sh - 1u);
+    return sign | ((uint32_t)q + ((rem > half || (rem == half && (q & 1ull))) ? 1u : 0u));
 }
+__host__ __device__ inline float pcm_bits_f32(uint32_t u) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __uint_as_float(u);
+#else
+    float f; __builtin_memcpy(&f, &u, 4); return f;
+#endif
+}
+__host__ __device__ inline float pcm_f64_f32(uint64_t bits) { return pcm_bits_f32(pcm_f64_bits_to_f32_bits(bits)); }
+
+// one sample of any format from its own bytes (p: the sample's first byte, any alignment): the host's statement, and the kernel's path for
+// interleaved channels and tails
+__host__ __device__ inline float pcm_decode_bytes(int32_t format, const uint8_t* p) {
+    switch (format) {
+    case WSA_PCM_I16:   return pcm_decode_one<WSA_PCM_I16>((uint32_t)p[0] | ((uint32_t)p[1] << 8));
+    case WSA_PCM_MULAW: return pcm_decode_one<WSA_PCM_MULAW>(p[0]);
+    case WSA_PCM_ALAW:  return pcm_decode_one<WSA_PCM_ALAW>(p[0]);
+    case WSA_PCM_U8:    return pcm_u8_f32(p[0]);
+    case WSA_PCM_I24:   return pcm_i24_f32((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16));
+    case WSA_PCM_I32:   return pcm_i32_f32((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));
+    case WSA_PCM_F64: {
+        uint64_t b = 0;
+        for (int k = 7; k >= 0; k--) b = (b << 8) | p[k];
+        return pcm_f64_f32(b);
+    }
+    default:            return pcm_bits_f32((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));      // WSA_PCM_F32: bit for bit
+    }
+}
+__host__ __device__ inline bool pcm_format_known(int32_t format) { return (format >= WSA_PCM_F32 && format <= WSA_PCM_ALAW) || (format >= WSA_PCM_U8 && format <= WSA_PCM_F64); }
+// bytes of one sample; 0 for a format nobody knows (4 .. 7 are kept for further 8-bit companded codes)
+__host__ __device__ inline uint32_t pcm_sample_bytes(int32_t format) {
+    return format == WSA_PCM_F32 || format == WSA_PCM_I32 ? 4u : format == WSA_PCM_I16 ? 2u : format == WSA_PCM_I24 ? 3u : format == WSA_PCM_F64 ? 8u
+         : format == WSA_PCM_MULAW || format == WSA_PCM_ALAW || format == WSA_PCM_U8 ? 1u : 0u;
+}
+inline const char* pcm_format_name(int32_t format) {
+    return format == WSA_PCM_F32 ? "f32" : format == WSA_PCM_I16 ? "i16" : format == WSA_PCM_MULAW ? "mulaw" : format == WSA_PCM_ALAW ? "alaw"
+         : format == WSA_PCM_U8 ? "u8" : format == WSA_PCM_I24 ? "i24" : format == WSA_PCM_I32 ? "i32" : format == WSA_PCM_F64 ? "f64" : "unknown";
+}
+
+// ---- batch_unpack_kernel (batch_pcm.hip): one 32-byte descriptor per clip
+struct PcmClipDesc {
+    uint64_t offset;       // bytes from the packed base to the clip's first byte, a multiple of 16
+    int32_t format;        // WSA_PCM_*
+    uint32_t channels;     // 1 .. 64
+    uint32_t n_frames;     // floats written to the clip's staging row
+    uint32_t pad[3];
+};
+static_assert(sizeof(PcmClipDesc) == 32, "one 32-byte descriptor per clip");
+// packed (16-byte aligned) + desc[c].offset -> out + c * stride, channel 0 of desc[c].n_frames frames; max_frames: the longest clip's count (sizes the grid)
+void launch_batch_unpack(const void* packed, const PcmClipDesc* desc, uint32_t n_clips, uint32_t max_frames, float* out, uint64_t stride, hipStream_t s);
 
 }  // namespace wsa

@@ -878,15 +878,12 @@ wsa_status wsa_stream_time_steps_packed(wsa_stream* b, uint32_t n_steps, const v
     return time_steps_impl(b, n_steps, feed, (size_t)b->n * b->pk_stride, b->h_pk, feed_steps, stream, out_us, rows_total);
 }
 
-// spec PK-1 on the host, no device involved: channel 0 of n_frames interleaved frames -> floats
+// specs PK-1 / PK-2 on the host, no device involved: channel 0 of n_frames interleaved frames -> floats
 wsa_status wsa_pcm_decode(int32_t format, const void* in, uint64_t n_frames, uint32_t channels, float* out) {
-    if (channels < 1 || channels > 64 || (n_frames && (!in || !out))) return WSA_ERR_INVALID;
-    const uint64_t ch = channels;
-    if (format == WSA_PCM_F32) { const float* p = static_cast<const float*>(in); for (uint64_t j = 0; j < n_frames; j++) out[j] = p[j * ch]; }
-    else if (format == WSA_PCM_I16) { const uint16_t* p = static_cast<const uint16_t*>(in); for (uint64_t j = 0; j < n_frames; j++) out[j] = pcm_decode_one<WSA_PCM_I16>(p[j * ch]); }
-    else if (format == WSA_PCM_MULAW) { const uint8_t* p = static_cast<const uint8_t*>(in); for (uint64_t j = 0; j < n_frames; j++) out[j] = pcm_decode_one<WSA_PCM_MULAW>(p[j * ch]); }
-    else if (format == WSA_PCM_ALAW) { const uint8_t* p = static_cast<const uint8_t*>(in); for (uint64_t j = 0; j < n_frames; j++) out[j] = pcm_decode_one<WSA_PCM_ALAW>(p[j * ch]); }
-    else return WSA_ERR_INVALID;
+    if (channels < 1 || channels > 64 || (n_frames && (!in || !out)) || !pcm_format_known(format)) return WSA_ERR_INVALID;
+    const uint8_t* p = static_cast<const uint8_t*>(in);
+    const uint64_t step = (uint64_t)channels * pcm_sample_bytes(format);
+    for (uint64_t j = 0; j < n_frames; j++) out[j] = pcm_decode_bytes(format, p + j * step);
     return WSA_OK;
 }
 

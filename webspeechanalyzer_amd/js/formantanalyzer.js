@@ -91,52 +91,84 @@ function decode_wav(buf) {
   }
   if (!fmt || !data) throw 'Unable to decode audio data';
   const bytes = fmt.bits >> 3, n = Math.floor(data.length / (bytes * fmt.ch));
-  if (fmt.ch < 1 || !(fmt.tag === 1 || fmt.tag === 3)) throw 'Unable to decode audio data';
-  if (fmt.tag === 1 && fmt.bits === 16 && LITTLE_ENDIAN) {
+  // the encodings the browser's decodeAudioData takes from a WAV: integer PCM (1), IEEE float (3), G.711 A-law (6) and mu-law (7), plain or extensible
+  const format = fmt.tag === 1 ? { 8: 'u8', 16: 'i16', 24: 'i24', 32: 'i32' }[fmt.bits] : fmt.tag === 3 ? { 32: 'f32', 64: 'f64' }[fmt.bits]
+    : fmt.tag === 6 && fmt.bits === 8 ? 'alaw' : fmt.tag === 7 && fmt.bits === 8 ? 'mulaw' : undefined;
+  if (fmt.ch < 1 || !format) throw 'Unable to decode audio data';
+  if (format === 'i16' && LITTLE_ENDIAN) {
     // 16-bit PCM (what WAV files usually hold) is not decoded here at all: the data chunk goes to the device as it is — interleaved
     // channels and all, half the PCIe bytes of floats — and libwsa converts channel 0 there (x / 32768, exact in fp32)
     const bytes_used = n * fmt.ch * 2;
     const aligned = (data.byteOffset & 1) === 0 ? data : Buffer.from(data.subarray(0, bytes_used));      // an odd offset needs one memcpy
     return { pcm16: new Int16Array(aligned.buffer, aligned.byteOffset, n * fmt.ch), channels: fmt.ch, sampleRate: fmt.rate };
   }
-  const pcm = new Float32Array(n);
-  for (let i = 0; i < n; i++) {
-    const o = i * fmt.ch * bytes;                      // channel 0
-    let v;
-    if (fmt.tag === 3 && fmt.bits === 32) v = data.readFloatLE(o);
-    else if (fmt.tag === 3 && fmt.bits === 64) v = data.readDoubleLE(o);
-    else if (fmt.bits === 16) v = data.readInt16LE(o) / 32768;
-    else if (fmt.bits === 8) v = (data.readUInt8(o) - 128) / 128;
-    else if (fmt.bits === 24) v = data.readIntLE(o, 3) / 8388608;
-    else if (fmt.bits === 32) v = data.readInt32LE(o) / 2147483648;
-    else throw 'Unable to decode audio data';
-    pcm[i] = v;
-  }
-  return { pcm, sampleRate: fmt.rate };
+  // every other encoding likewise (spec PK-2): a view of the data chunk's whole frames, whatever its address, and the name of what it holds —
+  // no loop over the samples and no copy here; libwsa turns channel 0 into floats on the device (clip_floats does it on the host for who needs floats)
+  return { packed: new Uint8Array(data.buffer, data.byteOffset, n * fmt.ch * bytes), format, channels: fmt.ch, sampleRate: fmt.rate };
 }
 
-// a clip = { pcm: Float32Array (mono), sampleRate } or { pcm16: Int16Array (interleaved over `channels`), channels, sampleRate }
+// a clip = { pcm: Float32Array (mono), sampleRate }, { pcm16: Int16Array (interleaved over `channels`), channels, sampleRate } or
+// { packed: Uint8Array (the bytes a file holds, little-endian, interleaved over `channels`), format: a name of CLIP_FORMATS, channels, sampleRate }
+const CLIP_FORMATS = { f32: [0, 4], i16: [1, 2], mulaw: [2, 1], alaw: [3, 1], u8: [8, 1], i24: [9, 3], i32: [10, 4], f64: [11, 8] };       // name: [WSA_PCM_* of include/wsa.h, bytes per sample]
 function to_pcm(source_obj) {
   if (source_obj instanceof Float32Array) return { pcm: source_obj, sampleRate: settings.sample_rate };
   if (source_obj instanceof Int16Array) return { pcm16: source_obj, channels: 1, sampleRate: settings.sample_rate };
   if (source_obj && source_obj.pcm instanceof Float32Array) return { pcm: source_obj.pcm, sampleRate: source_obj.sampleRate || settings.sample_rate };
   if (source_obj && source_obj.pcm16 instanceof Int16Array) return { pcm16: source_obj.pcm16, channels: source_obj.channels || 1, sampleRate: source_obj.sampleRate || settings.sample_rate };
+  if (source_obj && source_obj.packed instanceof Uint8Array) {
+    const ch = source_obj.channels || 1;
+    if (!Object.prototype.hasOwnProperty.call(CLIP_FORMATS, source_obj.format) || !(ch >= 1 && ch <= 64)) throw 'Invalid audio source';
+    return { packed: source_obj.packed, format: source_obj.format, channels: ch, sampleRate: source_obj.sampleRate || settings.sample_rate };
+  }
   if (source_obj instanceof ArrayBuffer || Buffer.isBuffer(source_obj) || ArrayBuffer.isView(source_obj)) return decode_wav(source_obj);
   throw 'Invalid audio source';
 }
 
-function clip_floats(c) {              // channel 0 of an int16 clip as floats (only batches that mix the two kinds need it)
+function g711_linear(code, mulaw) {    // ITU-T G.711 code -> 16-bit linear value (spec PK-1)
+  if (mulaw) { const u = ~code & 0xff, e = (u >> 4) & 7, m = u & 15, mag = (((m << 3) + 0x84) << e) - 0x84; return (u & 0x80 ? -mag : mag) | 0; }      // (| 0: codes 0x7F and 0xFF give +0, as the integer arithmetic of the library does)
+  const a = (code ^ 0x55) & 0xff, e = (a >> 4) & 7, m = a & 15, mag = e === 0 ? (m << 4) + 8 : ((m << 4) + 0x108) << (e - 1);
+  return a & 0x80 ? mag : -mag;
+}
+function clip_floats(c) {              // channel 0 of a clip as floats, decoded here on the host (for callers that need the floats: the launches send the bytes)
   if (c.pcm) return c.pcm;
-  const ch = c.channels, n = Math.floor(c.pcm16.length / ch), x = new Float32Array(n);
-  for (let i = 0; i < n; i++) x[i] = c.pcm16[i * ch] / 32768;
+  const ch = c.channels, n = clip_length(c), x = new Float32Array(n);
+  if (c.pcm16) { for (let i = 0; i < n; i++) x[i] = c.pcm16[i * ch] / 32768; return x; }
+  const d = Buffer.from(c.packed.buffer, c.packed.byteOffset, c.packed.length), step = ch * CLIP_FORMATS[c.format][1];
+  for (let i = 0; i < n; i++) {
+    const o = i * step;
+    switch (c.format) {
+      case 'f32': x[i] = d.readFloatLE(o); break;
+      case 'f64': x[i] = d.readDoubleLE(o); break;
+      case 'i16': x[i] = d.readInt16LE(o) / 32768; break;
+      case 'u8': x[i] = (d[o] - 128) / 128; break;
+      case 'i24': x[i] = d.readIntLE(o, 3) / 8388608; break;
+      case 'i32': x[i] = d.readInt32LE(o) / 2147483648; break;
+      default: x[i] = g711_linear(d[o], c.format === 'mulaw') / 32768;
+    }
+  }
   return x;
 }
 function clip_slice(c, a, b) {         // samples [a, b) of a clip (bufferSource.start(0, offset, duration))
   if (c.pcm) return { pcm: c.pcm.subarray(a, Math.min(b, c.pcm.length)), sampleRate: c.sampleRate };
-  const ch = c.channels, n = Math.floor(c.pcm16.length / ch);
-  return { pcm16: c.pcm16.subarray(a * ch, Math.min(b, n) * ch), channels: ch, sampleRate: c.sampleRate };
+  const ch = c.channels, n = clip_length(c);
+  if (c.pcm16) return { pcm16: c.pcm16.subarray(a * ch, Math.min(b, n) * ch), channels: ch, sampleRate: c.sampleRate };
+  const step = ch * CLIP_FORMATS[c.format][1];
+  return { packed: c.packed.subarray(a * step, Math.min(b, n) * step), format: c.format, channels: ch, sampleRate: c.sampleRate };
 }
-function clip_length(c) { return c.pcm ? c.pcm.length : Math.floor(c.pcm16.length / c.channels); }
+function clip_length(c) {
+  return c.pcm ? c.pcm.length : c.pcm16 ? Math.floor(c.pcm16.length / c.channels) : Math.floor(c.packed.length / (c.channels * CLIP_FORMATS[c.format][1]));
+}
+// one batch of clips to the addon.  Clips of one kind keep their call (all floats: wsa_batch_run_host, all Int16Array: wsa_batch_run_host_i16); any
+// other mix travels as the bytes the clips hold, every clip with its own format and channel count, and is unpacked on the device
+// (wsa_batch_run_host_packed, spec PK-2): Float32Array clips as 'f32', Int16Array clips as 'i16' — views, nothing is converted or copied here
+function submit_clips(nat, ctx, clips, fs, fs_an, defer, extra) {
+  if (clips.every((c) => c.pcm16)) return nat.processBatch(ctx, clips.map((c) => c.pcm16), fs, settings.output_level, fs_an, Uint32Array.from(clips, (c) => c.channels), defer, ...extra);
+  if (clips.every((c) => c.pcm)) return nat.processBatch(ctx, clips.map((c) => c.pcm), fs, settings.output_level, fs_an, undefined, defer, ...extra);
+  const bytes_of = (a) => new Uint8Array(a.buffer, a.byteOffset, a.byteLength);
+  return nat.processBatch(ctx, clips.map((c) => (c.pcm ? bytes_of(c.pcm) : c.pcm16 ? bytes_of(c.pcm16) : c.packed)), fs, settings.output_level, fs_an,
+    Uint32Array.from(clips, (c) => (c.pcm ? 1 : c.channels)), defer, extra[0],
+    Int32Array.from(clips, (c) => (c.pcm ? CLIP_FORMATS.f32[0] : c.pcm16 ? CLIP_FORMATS.i16[0] : CLIP_FORMATS[c.format][0])));
+}
 
 // ---- contexts are kept across launches (creating one is cheap, but the planned batch the addon keeps with it is not: GBs of
 // work space); a launch with other settings or devices replaces them, shutdown() releases them
@@ -761,8 +793,7 @@ async function run(clips, callback, labels_of, test_play) {
     const g = nat.geometry(ctxs[0], fs_an);
     const bands = settings.spec_type === 1 ? settings.N_mel_bins : settings.N_fft_bins;
     if (g.bands !== bands) throw 'Bins count mismatch: ' + g.bands + ', ' + bands;              // ref @B8568 check
-    // 16-bit clips travel as they are (Int16Array + channel counts); a batch that mixes them with float clips is sent as floats
-    const all16 = clips.every((c) => c.pcm16);
+    // (the clips travel as they are, whatever they hold: submit_clips)
     // the feature rows of all shards in one piece: they stay on their devices, one grouped RCCL send / receive over xGMI moves them to the first
     // device (include/wsa.h wsa_gather_rows) and ONE copy brings them to the host; a shard's small tables (segments, offsets) come with its own job
     const gather = (settings.output_level === 5 || settings.output_level === 13) && (settings.gather === null ? devs.length > 1 && new Set(devs).size === devs.length : settings.gather);      // (a rank is a GPU: contexts that share a device are not gathered)
@@ -772,8 +803,7 @@ async function run(clips, callback, labels_of, test_play) {
       const part = clips.slice(a, b);
       const extra = pred && !pred.knn ? [models[i]] : [];        // (no model: the addon is called exactly as before; a KNN store classifies behind the job)
       const fs_i = rates_of(part);                               // (a shard whose clips share a rate: the number, as before)
-      return all16 ? nat.processBatch(ctxs[i], part.map((c) => c.pcm16), fs_i, settings.output_level, fs_an, Uint32Array.from(part, (c) => c.channels), gather, ...extra)
-        : nat.processBatch(ctxs[i], part.map(clip_floats), fs_i, settings.output_level, fs_an, undefined, gather, ...extra);
+      return submit_clips(nat, ctxs[i], part, fs_i, fs_an, gather, extra);
     };
     // every shard runs to its end before anything else happens (a context with work in flight must not be touched), then the
     // first failure, if any, is what the launch rejects with
@@ -895,10 +925,8 @@ async function run_batches(batches, callback, labels, test_play) {
       const fs = rates_of(clips), fs_an = settings.resample_to > 0 ? settings.resample_to : clips[0].sampleRate;
       const g = nat.geometry(ctxs[k % 2], fs_an);
       if (g.bands !== bands) throw 'Bins count mismatch: ' + g.bands + ', ' + bands;          // ref @B8568 check
-      const all16 = clips.every((c) => c.pcm16);
       const extra = pred && !pred.knn ? [models[k % 2]] : [];
-      return all16 ? nat.processBatch(ctxs[k % 2], clips.map((c) => c.pcm16), fs, settings.output_level, fs_an, Uint32Array.from(clips, (c) => c.channels), false, ...extra)
-        : nat.processBatch(ctxs[k % 2], clips.map(clip_floats), fs, settings.output_level, fs_an, undefined, false, ...extra);
+      return submit_clips(nat, ctxs[k % 2], clips, fs, fs_an, false, extra);
     };
     let rows = 0, segments = 0, done = 0;
     let next = lists.length > 0 ? start(0) : null;
@@ -1149,5 +1177,5 @@ function set_predicted_label_for_segment(si, idx, label) {                      
 
 module.exports = { configure, LaunchAudioNodes, StopAudioNodes, set_predicted_label_for_segment, LaunchBatch, LaunchBatches,
   StreamOpen, decodePcm, STREAM_ACTIVE, STREAM_START, STREAM_STOP, shutdown, allocPinned, freePinned,
-  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, _values_after: values_after, loadModel, setPredictionModel, setPredictionModels, setPredictionKnn, setPredictionValues, trainModel, trainModels, saveModel, trainRegression, predictValues, predictDB, statsTable,
+  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, _clip_length: clip_length, _values_after: values_after, loadModel, setPredictionModel, setPredictionModels, setPredictionKnn, setPredictionValues, trainModel, trainModels, saveModel, trainRegression, predictValues, predictDB, statsTable,
   KNNClassifier, trainKnn, predictKnn };

@@ -23,6 +23,8 @@
  *   decodePcm(format, typedArray, channels) -> Float32Array   (wsa_pcm_decode: channel 0 of interleaved frames, spec PK-1)
  *   streamStep(stream, ctl: Uint8Array | null[, counts: Uint32Array | null]) -> {meta, feat, segments}   (wsa_stream_step_host[_n] + wsa_stream_collect;
  *       one hipGraph launch, well under a millisecond, so it runs on the calling thread; counts: samples per stream in this step, else paced)
+ *   processBatch(..., model, formats)           (9th argument an Int32Array of WSA_PCM_* numbers: the clips are Uint8Arrays over the bytes a file holds, any
+ *                                               mix of encodings, clip i interleaved over channels[i] channels: wsa_batch_run_host_packed, spec PK-2)
  *   processBatch(..., [models])                 (8th argument an array of models: wsa_batch_classify_ensemble; the result gains `ens`)
  *   streamSetEnsemble(stream, [models] | null)  (wsa_stream_set_ensemble: streamStep results gain `ens`)
  *   streamSetRegress(stream, [models] | null, outMin: Float64Array, outMax: Float64Array)   (wsa_stream_set_regress: streamStep results gain regValue [H][rows], regCb, regCbValue / regCbWeight
@@ -276,6 +278,7 @@ typedef struct {
     double *fs_each;                             /* one rate per clip (a Float64Array in place of fs): wsa_batch_create_mixed, fs is 0 */
     uint32_t n_clips; uint32_t *n_samples; const float **pcm; napi_ref *clip_refs;
     int is_i16; uint32_t *channels;   /* Int16Array clips (pcm[] then holds int16 pointers): wsa_batch_run_host_i16 */
+    int32_t *formats;                 /* 9th argument: one WSA_PCM_* number per clip, the clips Uint8Arrays of the files' bytes (pcm[] holds byte pointers): wsa_batch_run_host_packed */
     wsa_batch *plan; int plan_reused; /* taken from / returned to the box on the JS thread */
     /* results */
     wsa_status st; char err[512];
@@ -350,7 +353,8 @@ static void job_execute(napi_env env, void *data) {
         j->plan = b;
     }
     do {
-        j->st = j->is_i16 ? wsa_batch_run_host_i16(b, (const int16_t *const *)j->pcm, j->channels, j->queue) : wsa_batch_run_host(b, j->pcm, j->queue);
+        j->st = j->formats ? wsa_batch_run_host_packed(b, (const void *const *)j->pcm, j->formats, j->channels, j->queue)
+              : j->is_i16 ? wsa_batch_run_host_i16(b, (const int16_t *const *)j->pcm, j->channels, j->queue) : wsa_batch_run_host(b, j->pcm, j->queue);
         if (j->st != WSA_OK) break;
         wsa_device_result r;
         j->st = wsa_batch_result(b, j->queue, &r);
@@ -539,11 +543,11 @@ static void job_complete(napi_env env, napi_status status, void *data) {
     ens_host_free(&j->eh);
     free(j->prob); free(j->cb); free(j->cb_label); free(j->cb_conf); free(j->clip_conf);
     free(j->meta); free(j->feat); free(j->segs); free(j->row_off); free(j->seg_off); free(j->formants); free(j->frame_off); free(j->utt_meta); free(j->utt_feat); free(j->utt_off); free(j->trk_off); free(j->trk_pts); free(j->trk_rank);
-    free(j->n_samples); free(j->fs_each); free((void *)j->pcm); free(j->clip_refs); free(j->channels); free(j);
+    free(j->n_samples); free(j->fs_each); free((void *)j->pcm); free(j->clip_refs); free(j->channels); free(j->formats); free(j);
 }
 
 static napi_value fn_process_batch(napi_env env, napi_callback_info info) {
-    size_t argc = 8; napi_value argv[8];
+    size_t argc = 9; napi_value argv[9];
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     wsa_ctx *ctx = argc ? get_ctx(env, argv[0]) : NULL;
     bool is_arr = false; double fs = 0; uint32_t n = 0;
@@ -600,15 +604,45 @@ static napi_value fn_process_batch(napi_env env, napi_callback_info info) {
         napi_typedarray_type ct; void *cd = NULL; bool cta = false;
         if (napi_is_typedarray(env, argv[5], &cta) == napi_ok && cta && napi_get_typedarray_info(env, argv[5], &ct, &chan_len, &cd, NULL, NULL) == napi_ok && ct == napi_uint32_array) chan = (uint32_t *)cd;
     }
+    /* ... or, with a 9th argument (an Int32Array of WSA_PCM_* numbers, one per clip): every clip a Uint8Array over the bytes a file holds, clip i in
+     * formats[i] and interleaved over channels[i] channels — any mix of encodings in one batch, unpacked on the device (spec PK-2) */
+    if (argc >= 9) {
+        napi_typedarray_type ft; void *fd = NULL; bool fta = false; size_t fl = 0; napi_valuetype vt = napi_undefined;
+        napi_typeof(env, argv[8], &vt);
+        if (vt != napi_undefined && vt != napi_null) {
+            if (napi_is_typedarray(env, argv[8], &fta) != napi_ok || !fta || napi_get_typedarray_info(env, argv[8], &ft, &fl, &fd, NULL, NULL) != napi_ok || ft != napi_int32_array || fl != n) {
+                free(j->n_samples); free(j->fs_each); free((void *)j->pcm); free(j->clip_refs); free(j);
+                napi_throw_type_error(env, NULL, "processBatch: formats is an Int32Array with one WSA_PCM_* number per clip"); return NULL;
+            }
+            j->formats = malloc(sizeof(int32_t) * (n ? n : 1)); j->channels = calloc(n ? n : 1, sizeof(uint32_t));
+            if (!j->formats || !j->channels) { free(j->n_samples); free(j->fs_each); free((void *)j->pcm); free(j->clip_refs); free(j->channels); free(j->formats); free(j); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+            memcpy(j->formats, fd, sizeof(int32_t) * n);
+        }
+    }
     for (uint32_t i = 0; i < n; i++) {
         napi_value el; napi_typedarray_type tt; size_t len; void *data; bool is_ta = false;
         const char *bad = NULL;
-        if (napi_get_element(env, argv[1], i, &el) != napi_ok || napi_is_typedarray(env, el, &is_ta) != napi_ok || !is_ta ||
+        if (j->formats) {
+            const int32_t f = j->formats[i];
+            const uint32_t sb = (f == WSA_PCM_F32 || f == WSA_PCM_I32) ? 4u : f == WSA_PCM_I16 ? 2u : f == WSA_PCM_I24 ? 3u : f == WSA_PCM_F64 ? 8u
+                              : (f == WSA_PCM_MULAW || f == WSA_PCM_ALAW || f == WSA_PCM_U8) ? 1u : 0u;
+            const uint32_t ch = (chan && i < chan_len) ? chan[i] : 1;
+            if (napi_get_element(env, argv[1], i, &el) != napi_ok || napi_is_typedarray(env, el, &is_ta) != napi_ok || !is_ta ||
+                napi_get_typedarray_info(env, el, &tt, &len, &data, NULL, NULL) != napi_ok || tt != napi_uint8_array) bad = "with formats every clip must be a Uint8Array over the file's bytes";
+            else if (!sb) bad = "processBatch: unknown input format";
+            else if (ch < 1 || ch > 64) bad = "processBatch: channels must be 1 .. 64";
+            if (!bad) {
+                j->channels[i] = ch; j->n_samples[i] = (uint32_t)(len / ((size_t)sb * ch)); j->pcm[i] = (const float *)data;
+                napi_create_reference(env, el, 1, &j->clip_refs[i]);
+                continue;
+            }
+        }
+        else if (napi_get_element(env, argv[1], i, &el) != napi_ok || napi_is_typedarray(env, el, &is_ta) != napi_ok || !is_ta ||
             napi_get_typedarray_info(env, el, &tt, &len, &data, NULL, NULL) != napi_ok || (tt != napi_float32_array && tt != napi_int16_array)) bad = "every clip must be a Float32Array or an Int16Array";
         else if (i > 0 && (tt == napi_int16_array) != (j->is_i16 != 0)) bad = "the clips of one batch must be of one kind";
         if (bad) {
             for (uint32_t k = 0; k < i; k++) napi_delete_reference(env, j->clip_refs[k]);
-            free(j->n_samples); free(j->fs_each); free((void *)j->pcm); free(j->clip_refs); free(j->channels); free(j);
+            free(j->n_samples); free(j->fs_each); free((void *)j->pcm); free(j->clip_refs); free(j->channels); free(j->formats); free(j);
             napi_throw_type_error(env, NULL, bad); return NULL;
         }
         if (i == 0) { j->is_i16 = tt == napi_int16_array; if (j->is_i16) j->channels = calloc(n, sizeof(uint32_t)); }
