@@ -458,6 +458,31 @@ def level_feature_count(output_level):
     return int(lib().wsa_level_feature_count(int(output_level)))
 
 
+def rows_to_callbacks(level, step, meta, feat, payload):
+    """One clip's compacted rows (meta [n, 8] i32 = {clip, si, t_start, t_len, ..}, feat [n, 53]) as the callbacks the reference's dispatcher delivers
+    for them: levels 4 / 5 one per row with the time pair as numbers, levels 10 / 12 / 13 one per result with the syllables' time pairs as the
+    reference's toFixed(3) strings.  step = window_step in seconds; payload(m, f) = what the row hands over.  Other levels have no row callbacks."""
+    cbs = []
+    if level in (4, 5):
+        for m, f in zip(meta, feat):
+            cbs.append([int(m[1]), [], [m[2] * step, (m[3] + 1) * step], payload(m, f)])
+    elif level in (10, 12, 13):
+        i = 0
+        while i < len(meta):
+            j = i
+            while j < len(meta) and meta[j][1] == meta[i][1]:
+                j += 1
+            tm = [["%.3f" % (m[2] * step), "%.3f" % ((m[3] + 1) * step)] for m in meta[i:j]]
+            rows_ = list(zip(meta[i:j], feat[i:j]))
+            if level == 12:                  # numeric threw on a syllable: the reference keeps the rows before it
+                cut = next((q for q, (_, f) in enumerate(rows_) if f[23] != 0), len(rows_))
+                rows_ = rows_[:cut]
+            if level != 12 or rows_:
+                cbs.append([int(meta[i][1]), [], tm, [payload(m, f) for m, f in rows_]])
+            i = j
+    return cbs
+
+
 class Config(dict):
     """The reference's settings object (defaults dist/main.js:2 @B2965, output_level 4 = Segment Formants)."""
 
@@ -787,23 +812,8 @@ class Batch:
                 for k in range(int(utt["off"][c]), int(utt["off"][c + 1])):
                     m = utt["meta"][k]
                     cbs.append([0, [], [m[2] * step, (m[3] + 1) * step], utt["feat"][k].copy()])
-            elif level in (4, 5):
-                for m, f in zip(meta, feat):
-                    cbs.append([int(m[1]), [], [m[2] * step, (m[3] + 1) * step], payload(m, f)])
-            elif level in (10, 12, 13):
-                i = 0
-                while i < len(meta):
-                    j = i
-                    while j < len(meta) and meta[j][1] == meta[i][1]:
-                        j += 1
-                    tm = [["%.3f" % (m[2] * step), "%.3f" % ((m[3] + 1) * step)] for m in meta[i:j]]
-                    rows_ = list(zip(meta[i:j], feat[i:j]))
-                    if level == 12:                  # numeric threw on a syllable: the reference keeps the rows before it
-                        cut = next((q for q, (_, f) in enumerate(rows_) if f[23] != 0), len(rows_))
-                        rows_ = rows_[:cut]
-                    if level != 12 or rows_:
-                        cbs.append([int(meta[i][1]), [], tm, [payload(m, f) for m, f in rows_]])
-                    i = j
+            else:
+                cbs = rows_to_callbacks(level, step, meta, feat, payload)
             sa, sb = int(r["seg_off"][c]), int(r["seg_off"][c + 1])
             if level == 3:                           # ref @B30132: `s[e].length > 0 && b(e, label, s[e])` (three arguments)
                 cbs = [[k, [], trk[sa + k]] for k in range(sb - sa) if len(trk[sa + k]) > 0]
@@ -1928,3 +1938,119 @@ def debug_stream_spectra(streams, bands):
     if rc != 0:
         raise WsaError(f"wsa_debug_stream_spectra: error {rc}")
     return out
+
+
+COMPACT_FUSED, COMPACT_SCAN, COMPACT_COUNT_SCAN = 0, 1, 2      # compact_path of csrc/tracker.hip: what launch_compact ran
+CARRY_HIST = 32
+CARRY_WORDS = 2 + 2 * CARRY_HIST
+SPAN_BUCKETS = 2048
+COMPACT_SENTINEL = -7
+
+
+class _DebugCompactIO(ctypes.Structure):
+    """struct wsa_debug_compact_io of csrc/debug.hip"""
+    _vp, _u32, _i32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32
+    _fields_ = [("seg_i", _vp), ("seg_count", _vp), ("ctl", _vp), ("row_meta_in", _vp), ("row_feat_in", _vp), ("clip_rows", _vp), ("carry_in", _vp),
+                ("n", _u32), ("seg_cap", _u32), ("pool", _u32), ("n_steps", _u32), ("rows_cap", _u32), ("segs_cap", _u32),
+                ("level", _i32), ("fused", _i32), ("give_clr", _i32), ("give_host", _i32),
+                ("seg_out", _vp), ("row_meta_out", _vp), ("row_feat_out", _vp), ("clip_row_off", _vp), ("clip_seg_off", _vp), ("totals", _vp),
+                ("host4", _vp), ("counters", _vp), ("hist", _vp), ("path", _vp), ("carry", _vp)]
+
+
+def debug_compact(seg_i, seg_count, row_meta_in, row_feat_in, level, fused=True, clip_rows=None, ctl=None, carry_in=None, counters=None, totals=None, hist=None,
+                  give_clr=False, give_host=False, rows_cap=None, segs_cap=None, pool=None, device=0, sentinel=COMPACT_SENTINEL):
+    """Test access to K3 on its own (csrc/debug.hip wsa_debug_compact; not part of include/wsa.h).  Batch (ctl None): seg_i [n, seg_cap, 8] i32, seg_count [n],
+    clip_rows [n] or None; streams: seg_i [n_steps, n, seg_cap, 8], seg_count / ctl [n_steps, n], carry_in [n, CARRY_WORDS] or None.  row_meta_in [pool, 8] i32,
+    row_feat_in [pool, 53] (float64, or uint64 bit patterns).  counters [16] / totals [4] / hist [SPAN_BUCKETS]: the seeds (default: `sentinel` as u32, totals[2] = 0).
+    Every output slot starts as `sentinel` (feature words: the u64 pattern of the sentinel repeated).  Returns dict(seg_out [.., segs_cap, 4], row_meta_out
+    [.., rows_cap, 8], row_feat_out [.., rows_cap, 53] u64, clip_row_off / clip_seg_off [.., n + 1], totals [.., 4], host4, counters, hist, path (int, or
+    [n_steps]), carry [n_steps, n, CARRY_WORDS]); `..` = n_steps for streams.  Raises WsaError on a refusal."""
+    L = lib()
+    L.wsa_debug_compact.argtypes = [ctypes.c_int32, ctypes.c_void_p]
+    L.wsa_debug_compact.restype = ctypes.c_int
+    streams = ctl is not None
+    seg_i = np.ascontiguousarray(seg_i, np.int32)
+    seg_count = np.ascontiguousarray(seg_count, np.uint32)
+    n_steps = seg_i.shape[0] if streams else 0
+    n, seg_cap = seg_i.shape[-3], seg_i.shape[-2]
+    lead = (n_steps,) if streams else (1,)
+    assert seg_i.shape == (lead if streams else ()) + (n, seg_cap, 8) and seg_count.shape == (lead if streams else ()) + (n,)
+    meta_in = np.ascontiguousarray(row_meta_in, np.int32).reshape(-1, 8)
+    feat_in = np.ascontiguousarray(row_feat_in)
+    assert feat_in.dtype in (np.float64, np.uint64)
+    feat_in = feat_in.reshape(-1, NFEAT)
+    npool = len(meta_in) if pool is None else int(pool)
+    su = np.uint32(sentinel & 0xffffffff)
+    R = int(rows_cap) if rows_cap is not None else max(1, int(max(seg_i.reshape(lead[0], -1, 8)[k, :, 6].clip(0).sum() for k in range(lead[0])))) + 5
+    S = int(segs_cap) if segs_cap is not None else int(seg_count.reshape(lead[0], -1).sum(axis=1).max()) + 3
+    u64s = np.uint64((int(su) << 32) | int(su))
+    out = dict(seg_out=np.full(lead + (S, 4), sentinel, np.int32), row_meta_out=np.full(lead + (R, 8), sentinel, np.int32), row_feat_out=np.full(lead + (R, NFEAT), u64s, np.uint64),
+               clip_row_off=np.full(lead + (n + 1,), su, np.uint32), clip_seg_off=np.full(lead + (n + 1,), su, np.uint32),
+               totals=np.tile(np.array([su, su, 0, su], np.uint32) if totals is None else np.ascontiguousarray(totals, np.uint32), lead + (1,)),
+               host4=np.full(4, su, np.uint32), counters=np.full(16, su, np.uint32) if counters is None else np.array(counters, np.uint32),
+               hist=np.full(SPAN_BUCKETS, su, np.uint32) if hist is None else np.array(hist, np.uint32), path=np.full(lead, -9, np.int32),
+               carry=np.full((n_steps, n, CARRY_WORDS), sentinel, np.int32))
+    assert out["counters"].shape == (16,) and out["hist"].shape == (SPAN_BUCKETS,) and out["totals"].shape == lead + (4,)
+    ctl_a = np.ascontiguousarray(ctl, np.uint32) if streams else None
+    rows_a = np.ascontiguousarray(clip_rows, np.uint32) if clip_rows is not None else None
+    carry_a = np.ascontiguousarray(carry_in, np.int32) if carry_in is not None else None
+    io = _DebugCompactIO()
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+    io.seg_i, io.seg_count, io.ctl, io.row_meta_in, io.row_feat_in, io.clip_rows, io.carry_in = seg_i.ctypes.data, seg_count.ctypes.data, ptr(ctl_a), ptr(meta_in), ptr(feat_in), ptr(rows_a), ptr(carry_a)
+    io.n, io.seg_cap, io.pool, io.n_steps, io.rows_cap, io.segs_cap = n, seg_cap, npool, n_steps, R, S
+    io.level, io.fused, io.give_clr, io.give_host = int(level), int(bool(fused)), int(bool(give_clr)), int(bool(give_host))
+    for name, v in out.items():
+        setattr(io, name, v.ctypes.data if (name != "carry" or streams) else None)
+    rc = L.wsa_debug_compact(device, ctypes.addressof(io))
+    if rc != 0:
+        e = WsaError(f"wsa_debug_compact: status {rc}")
+        e.out = out                                      # a refusal writes nothing: the tests look at the sentinels
+        raise e
+    if not streams:
+        for k in ("seg_out", "row_meta_out", "row_feat_out", "clip_row_off", "clip_seg_off", "totals"):
+            out[k] = out[k][0]
+        out["path"] = int(out["path"][0])
+        del out["carry"]
+    return out
+
+
+def debug_span_order(variant, clips, settings, blocks=0, device=0, sentinel=0xfffffff9, seg_cap=None):
+    """Test access to the span order on its own (csrc/debug.hip wsa_debug_span_order; not part of include/wsa.h): clips / settings / variant / blocks as
+    debug_gate's batch form; the gate counts the spans into hist / key as the batch driver has it, launch_span_order sorts.  Returns dict(seg_i [n, seg_cap, 8],
+    seg_count [n], hist [SPAN_BUCKETS], key [n, seg_cap, 2] = {bucket, rank}, order [n * seg_cap, 2] = {clip, segment}, counters [4], seg_cap); key and order
+    slots nobody wrote keep `sentinel`.  seg_cap: skip the sizing call and hand this number over.  A WsaError raised by the run carries the untouched tables as .out."""
+    L = lib()
+    vp, i32, u32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32
+    L.wsa_debug_span_order.argtypes = [i32, i32, vp, vp, u32, i32, vp, u32, vp] + [vp] * 6
+    L.wsa_debug_span_order.restype = ctypes.c_int
+    n = len(clips)
+    bands = int(clips[0].shape[1])
+    nfr = np.array([len(c) for c in clips], np.uint32)
+    total = int(nfr.sum())
+    spec = np.ascontiguousarray(np.concatenate([np.asarray(c, np.uint32).reshape(-1, bands) for c in clips], axis=0)) if total else np.zeros((1, bands), np.uint32)
+    s6 = np.array([settings["window_step"], settings["pause_length"], settings["min_seg_length"], float(bool(settings["auto_noise_gate"])),
+                   settings["voiced_max_dB"], settings["voiced_min_dB"]], np.float64)
+    caps = np.zeros(2, np.int32)
+
+    def call(*outs):
+        rc = L.wsa_debug_span_order(device, variant, spec.ctypes.data, nfr.ctypes.data, n, bands, s6.ctypes.data, blocks, caps.ctypes.data, *outs)
+        if rc != 0:
+            raise WsaError(f"wsa_debug_span_order: error {rc}")
+    if seg_cap is None:
+        call(*([None] * 6))
+        seg_cap = int(caps[0])
+    else:
+        caps[0] = int(seg_cap)                          # (tests: a table size the entry did not hand out is refused)
+    seg_i = np.full((n, seg_cap, 8), GATE_SENTINEL, np.int32)
+    seg_count = np.full(n, 0xffffffff, np.uint32)
+    hist = np.full(SPAN_BUCKETS, sentinel, np.uint32)
+    key = np.full((n, seg_cap, 2), sentinel, np.uint32)
+    order = np.full((n * seg_cap, 2), sentinel, np.uint32)
+    counters = np.full(4, sentinel, np.uint32)
+    out = dict(seg_i=seg_i, seg_count=seg_count, hist=hist, key=key, order=order, counters=counters, seg_cap=seg_cap)
+    try:
+        call(seg_i.ctypes.data, seg_count.ctypes.data, hist.ctypes.data, key.ctypes.data, order.ctypes.data, counters.ctypes.data)
+    except WsaError as e:
+        e.out = out
+        raise
+    return dict(seg_i=seg_i, seg_count=seg_count, hist=hist, key=key, order=order, counters=counters, seg_cap=seg_cap)

@@ -1,6 +1,6 @@
 // debug.hip — test entries of libwsa that are NOT part of include/wsa.h: unit access to device-side pieces that the public
 // entry points only exercise through their consequences (tests/test_gpu_units.py, tests/test_gpu_coeffs.py, tests/test_gpu_utterance.py, tests/test_gpu_gate.py,
-// tests/test_gpu_regress_group.py, tests/test_gpu_fold.py, tests/test_gpu_frontend.py, tests/test_gpu_batch_pcm.py).
+// tests/test_gpu_regress_group.py, tests/test_gpu_fold.py, tests/test_gpu_frontend.py, tests/test_gpu_batch_pcm.py, tests/test_gpu_dispatch.py).
 #include <cstring>
 #include <vector>
 #include "host_plan.hpp"
@@ -869,5 +869,180 @@ extern "C" int wsa_debug_batch_unpack(int32_t device, const void* packed, const 
         wsa::launch_batch_unpack(dp, dd, n_clips, max_frames, dout, stride, nullptr);
         ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dout, nout * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess;
     }
+    return ok ? WSA_OK : WSA_ERR_HIP;
+}
+
+// K3 (csrc/tracker.hip: compact_count_kernel, compact_scan_kernel, compact_gather_kernel) on its own: hand-built segment tables and a hand-built row
+// pool straight into launch_compact, which picks its form from n, fused, clip_rows and carry itself (path = what compact_path said it ran).
+//   n_steps == 0, a batch of n clips: seg_i [n][seg_cap][8], seg_count [n], clip_rows [n] (or NULL: no fused form) — the per-clip row counters as the
+//   tracker leaves them, which must equal the rows of the clip's reported segments.  counters [16] (word 1 is the flag word the fused form publishes), totals
+//   [4] and hist [SPAN_BUCKETS] go to the device as the caller seeded them and come back as the run left them; give_clr hands counters and hist over as
+//   clr_counters / clr_hist, give_host the four host words (mapped pinned memory, as the batch driver's).
+//   n_steps > 0, n streams: seg_i [n_steps][n][seg_cap][8], seg_count and ctl [n_steps][n]; each step runs launch_stream_prepare (ctl bit 0 START clears the
+//   stream's carry) and launch_compact with the carry, which starts as carry_in [n][CARRY_WORDS] (NULL: zeros) and stays on the device between steps.  The
+//   seeded totals go up afresh before every step; carry [n_steps][n][CARRY_WORDS] comes back as each step left it.
+// The pool (row_meta_in [pool][8], row_feat_in [pool][53]) is one for all steps.  Out, per step: seg_out [segs_cap][4], row_meta_out [rows_cap][8], row_feat_out
+// [rows_cap][53], clip_row_off / clip_seg_off [n + 1], totals [4].  Every output table goes to the device as the caller filled it and comes back whole: a slot
+// the kernels do not write keeps the caller's value.
+// Refused, nothing run and nothing written: whatever would make a kernel index outside these tables — seg_count > seg_cap, SEG_ROW0 + SEG_NROWS past the
+// pool, a negative SEG_NROWS or SEG_ROW0, more rows or segments in a step than rows_cap / segs_cap, clip_rows that differ from the rows reported, a carry whose
+// counts are negative or that has counted more results than segments (the result index would then run ahead of the step's table), an unknown level.
+struct wsa_debug_compact_io {
+    const int32_t* seg_i; const uint32_t* seg_count; const uint32_t* ctl; const int32_t* row_meta_in; const double* row_feat_in; const uint32_t* clip_rows;
+    const int32_t* carry_in;
+    uint32_t n, seg_cap, pool, n_steps, rows_cap, segs_cap; int32_t level, fused, give_clr, give_host;
+    int32_t* seg_out; int32_t* row_meta_out; double* row_feat_out; uint32_t* clip_row_off; uint32_t* clip_seg_off; uint32_t* totals;
+    uint32_t* host4; uint32_t* counters; uint32_t* hist; int32_t* path; int32_t* carry;
+};
+
+extern "C" int wsa_debug_compact(int32_t device, const wsa_debug_compact_io* io) {
+    using namespace wsa;
+    if (!io || !io->seg_i || !io->seg_count || !io->seg_out || !io->row_meta_out || !io->row_feat_out || !io->clip_row_off || !io->clip_seg_off || !io->totals
+        || !io->host4 || !io->counters || !io->hist || !io->path) return WSA_ERR_INVALID;
+    const uint32_t n = io->n, n_steps = io->n_steps, pool = io->pool;
+    const bool streams = n_steps != 0;
+    if (n < 1 || n > (1u << 14) || io->seg_cap < 1 || io->seg_cap > (1u << 12) || pool > (1u << 20) || (pool && (!io->row_meta_in || !io->row_feat_in))) return WSA_ERR_INVALID;
+    if (io->rows_cap < 1 || io->rows_cap > (1u << 20) || io->segs_cap < 1 || io->segs_cap > (1u << 20) || n_steps > (1u << 12)) return WSA_ERR_INVALID;
+    if (io->level != 3 && io->level != 4 && io->level != 5 && io->level != 10 && io->level != 13) return WSA_ERR_INVALID;
+    if (streams && (!io->ctl || !io->carry || io->clip_rows || io->give_clr || io->give_host)) return WSA_ERR_INVALID;        // the fused form is the batches'
+    if (!streams && (io->carry_in || io->carry)) return WSA_ERR_INVALID;
+    const uint32_t tables = streams ? n_steps : 1;
+    const size_t seg_cap = io->seg_cap, segs = (size_t)n * seg_cap;
+    std::vector<int64_t> seg_before(n, 0), res_before(n, 0);
+    for (uint32_t c = 0; streams && io->carry_in && c < n; c++) {
+        const int32_t* cy = io->carry_in + (size_t)c * CARRY_WORDS;
+        if (cy[0] < 0 || cy[1] < 0 || cy[1] > cy[0]) return WSA_ERR_INVALID;
+        seg_before[c] = cy[0]; res_before[c] = cy[1];
+    }
+    for (uint32_t k = 0; k < tables; k++) {
+        uint64_t rows = 0, nsegs = 0;
+        for (uint32_t c = 0; c < n; c++) {
+            const uint32_t ns = io->seg_count[(size_t)k * n + c];
+            if (ns > seg_cap) return WSA_ERR_INVALID;
+            if (streams && (io->ctl[(size_t)k * n + c] & ~3u)) return WSA_ERR_INVALID;
+            if (streams && (io->ctl[(size_t)k * n + c] & 1u)) { seg_before[c] = 0; res_before[c] = 0; }
+            uint64_t clip_rows = 0, results = 0;
+            for (uint32_t q = 0; q < ns; q++) {
+                const int32_t* sg = io->seg_i + ((size_t)k * segs + (size_t)c * seg_cap + q) * 8;
+                if (sg[SEG_NROWS] < 0 || sg[SEG_ROW0] < 0 || (uint64_t)sg[SEG_ROW0] + (uint64_t)sg[SEG_NROWS] > pool) return WSA_ERR_INVALID;
+                if (sg[SEG_FLAG] >= 0) { clip_rows += (uint32_t)sg[SEG_NROWS]; results++; }
+            }
+            if (io->clip_rows && io->clip_rows[c] != clip_rows) return WSA_ERR_INVALID;
+            seg_before[c] += ns; res_before[c] += (int64_t)results;
+            if (seg_before[c] > (1 << 30)) return WSA_ERR_INVALID;
+            rows += clip_rows; nsegs += ns;
+        }
+        if (rows > io->rows_cap || nsegs > io->segs_cap) return WSA_ERR_INVALID;
+    }
+    if (hipSetDevice(device) != hipSuccess) return WSA_ERR_NO_DEVICE;
+    DevArena A;
+    int32_t *d_seg_i = nullptr, *d_meta_in = nullptr, *d_seg_out = nullptr, *d_meta_out = nullptr, *d_carry = nullptr; double *d_feat_in = nullptr, *d_feat_out = nullptr, *d_state = nullptr;
+    uint32_t *d_seg_count = nullptr, *d_clip_rows = nullptr, *d_ctl = nullptr, *d_row_off = nullptr, *d_seg_off = nullptr, *d_totals = nullptr, *d_counters = nullptr, *d_hist = nullptr;
+    uint32_t *h_host = nullptr, *h_host_dev = nullptr;
+    const size_t R = io->rows_cap, S = io->segs_cap;
+    bool ok = A.alloc(&d_seg_i, segs * 8) && A.alloc(&d_seg_count, n) && fold_up(A, &d_meta_in, io->row_meta_in, (size_t)pool * 8) && fold_up(A, &d_feat_in, io->row_feat_in, (size_t)pool * WSA_NFEAT)
+           && A.alloc(&d_seg_out, S * 4) && A.alloc(&d_meta_out, R * 8) && A.alloc(&d_feat_out, R * WSA_NFEAT) && A.alloc(&d_row_off, (size_t)n + 1) && A.alloc(&d_seg_off, (size_t)n + 1)
+           && A.alloc(&d_totals, 4) && fold_up(A, &d_counters, io->counters, 16) && fold_up(A, &d_hist, io->hist, (size_t)SPAN_BUCKETS) && A.pin(&h_host, &h_host_dev, 4);
+    if (ok && io->clip_rows) ok = fold_up(A, &d_clip_rows, io->clip_rows, n);
+    if (ok && streams) {
+        ok = A.alloc(&d_ctl, n) && A.alloc(&d_state, (size_t)n * GATE_STATE, true) && A.alloc(&d_carry, (size_t)n * CARRY_WORDS, true)
+          && (!io->carry_in || hipMemcpy(d_carry, io->carry_in, (size_t)n * CARRY_WORDS * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess);
+    }
+    if (!ok) return WSA_ERR_HIP;
+    for (int q = 0; q < 4; q++) h_host[q] = io->host4[q];
+    for (uint32_t k = 0; ok && k < tables; k++) {
+        ok = hipMemcpy(d_seg_i, io->seg_i + (size_t)k * segs * 8, segs * 8 * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess
+          && hipMemcpy(d_seg_count, io->seg_count + (size_t)k * n, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess
+          && hipMemcpy(d_seg_out, io->seg_out + (size_t)k * S * 4, S * 4 * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess
+          && hipMemcpy(d_meta_out, io->row_meta_out + (size_t)k * R * 8, R * 8 * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess
+          && hipMemcpy(d_feat_out, io->row_feat_out + (size_t)k * R * WSA_NFEAT, R * WSA_NFEAT * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
+          && hipMemcpy(d_row_off, io->clip_row_off + (size_t)k * (n + 1), ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess
+          && hipMemcpy(d_seg_off, io->clip_seg_off + (size_t)k * (n + 1), ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess
+          && hipMemcpy(d_totals, io->totals + (size_t)k * 4, 4 * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess
+          && (!streams || hipMemcpy(d_ctl, io->ctl + (size_t)k * n, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess);
+        if (!ok) break;
+        CompactParams cp;
+        cp.n_clips = n; cp.seg_cap = (int)seg_cap; cp.level = io->level; cp.seg_i = d_seg_i; cp.seg_count = d_seg_count; cp.row_meta_in = d_meta_in; cp.row_feat_in = d_feat_in;
+        cp.seg_out = d_seg_out; cp.row_meta_out = d_meta_out; cp.row_feat_out = d_feat_out; cp.clip_row_off = d_row_off; cp.clip_seg_off = d_seg_off; cp.totals = d_totals;
+        if (streams) {
+            launch_stream_prepare(d_state, d_carry, nullptr, d_ctl, n, 0.0, 0.0, nullptr);
+            cp.carry = d_carry; cp.ctl = d_ctl;
+        } else {
+            cp.clip_rows = d_clip_rows; cp.flags = d_counters + 1; cp.fused = io->fused ? 1 : 0; cp.host = io->give_host ? h_host_dev : nullptr;
+            cp.clr_counters = io->give_clr ? d_counters : nullptr; cp.clr_hist = io->give_clr ? d_hist : nullptr;
+        }
+        io->path[k] = compact_path(cp);
+        launch_compact(cp, nullptr);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess
+          && fold_down(io->seg_out + (size_t)k * S * 4, d_seg_out, S * 4) && fold_down(io->row_meta_out + (size_t)k * R * 8, d_meta_out, R * 8)
+          && fold_down(io->row_feat_out + (size_t)k * R * WSA_NFEAT, d_feat_out, R * WSA_NFEAT) && fold_down(io->clip_row_off + (size_t)k * (n + 1), d_row_off, (size_t)n + 1)
+          && fold_down(io->clip_seg_off + (size_t)k * (n + 1), d_seg_off, (size_t)n + 1) && fold_down(io->totals + (size_t)k * 4, d_totals, 4)
+          && (!streams || fold_down(io->carry + (size_t)k * n * CARRY_WORDS, d_carry, (size_t)n * CARRY_WORDS));
+    }
+    ok = ok && fold_down(io->counters, d_counters, 16) && fold_down(io->hist, d_hist, (size_t)SPAN_BUCKETS);
+    if (ok) for (int q = 0; q < 4; q++) io->host4[q] = h_host[q];
+    return ok ? WSA_OK : WSA_ERR_HIP;
+}
+
+// The span order on its own: wsa_debug_gate's batch form (variants 0 .. 2, `blocks`, the same settings6 and caps_io) with the gate's counting switched on
+// — span_hist / span_key set as the batch driver sets them — and launch_span_order behind it.  Out: seg_i [n_clips][seg_cap][8], seg_count [n_clips], hist
+// [SPAN_BUCKETS] (zero before the gate, as the batch's clear leaves it), key [n_clips][seg_cap][2] and order [n_clips * seg_cap][2] (both go to the device as
+// the caller filled them: a slot nobody writes keeps its value), counters4 = counters[0 .. 3] as the driver hands them to launch_span_order.
+// Refused, nothing run: what wsa_debug_gate refuses for a batch, and the stream variant.  One refusal comes AFTER the peak scan has run (as in wsa_debug_gate):
+// a frame with more than CAND_CAP candidates, which only the scan finds — the gate and the span order are then not run, and nothing is written to the caller.
+extern "C" int wsa_debug_span_order(int32_t device, int32_t variant, const uint32_t* spec, const uint32_t* n_frames, uint32_t n_clips, int32_t bands, const double* settings6,
+                                    uint32_t blocks, int32_t* caps_io, int32_t* seg_i, uint32_t* seg_count, uint32_t* hist, uint32_t* key, uint32_t* order, uint32_t* counters4) {
+    using namespace wsa;
+    if (!n_frames || !settings6 || !caps_io || variant < 0 || variant > 2 || n_clips < 1 || n_clips > 4096 || bands < 4 || bands > 256) return WSA_ERR_INVALID;
+    wsa_config c{};
+    c.output_level = 5; c.N_mel_bins = bands; c.window_width = c.window_step = settings6[0]; c.pause_length = settings6[1]; c.min_seg_length = settings6[2];
+    c.auto_noise_gate = settings6[3] != 0 ? 1 : 0; c.voiced_max_dB = settings6[4]; c.voiced_min_dB = settings6[5];
+    if (!(c.window_step > 0) || !(c.pause_length >= 0) || !(c.min_seg_length >= 0)) return WSA_ERR_INVALID;
+    if (variant < 2 && !c.auto_noise_gate) return WSA_ERR_INVALID;                     // the integer kernel's state is integers only under the auto gate
+    uint64_t total = 0; uint32_t max_frames = 0;
+    std::vector<uint32_t> foff((size_t)n_clips + 1, 0);
+    for (uint32_t i = 0; i < n_clips; i++) {
+        if (n_frames[i] > (1u << 20)) return WSA_ERR_INVALID;
+        total += n_frames[i]; foff[i + 1] = (uint32_t)total; if (n_frames[i] > max_frames) max_frames = n_frames[i];
+    }
+    if (total > (1u << 22) || (total && !spec)) return WSA_ERR_INVALID;
+    const Derived D(c, bands);
+    const int seg_cap = batch_seg_cap(max_frames, D);
+    if (caps_io[0] == 0) { caps_io[0] = seg_cap; return WSA_OK; }
+    if (caps_io[0] != seg_cap || !seg_i || !seg_count || !hist || !key || !order || !counters4) return WSA_ERR_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return WSA_ERR_NO_DEVICE;
+    const size_t segs = (size_t)n_clips * seg_cap;
+    DevArena A;
+    uint32_t *d_spec = nullptr, *d_nfr = nullptr, *d_foff = nullptr, *d_seg_count = nullptr, *d_clip_rows = nullptr, *d_counters = nullptr, *d_hist = nullptr, *d_key = nullptr, *d_order = nullptr;
+    RecPtrs rec; int32_t *d_info = nullptr, *d_seg_i = nullptr; double *d_v = nullptr, *d_fl = nullptr, *d_seg_d = nullptr;
+    bool ok = A.alloc(&d_spec, (size_t)total * bands + 4, true) && A.upload(&d_foff, foff) && fold_up(A, &d_nfr, n_frames, n_clips) && A.alloc(&rec.hdr, (size_t)total, true)
+           && A.alloc(&rec.amp, (size_t)total * CAND_CAP, true) && A.alloc(&rec.ent, (size_t)total * CAND_CAP, true) && A.alloc(&d_info, (size_t)total, true) && A.alloc(&d_v, (size_t)total, true)
+           && A.alloc(&d_fl, (size_t)total, true) && A.alloc(&d_seg_i, segs * 8, true) && A.alloc(&d_seg_d, segs * 2, true) && A.alloc(&d_seg_count, n_clips, true)
+           && A.alloc(&d_clip_rows, n_clips, true) && A.alloc(&d_counters, 16, true) && A.alloc(&d_hist, (size_t)SPAN_BUCKETS, true)
+           && fold_up(A, &d_key, key, segs * 2) && fold_up(A, &d_order, order, segs * 2)
+           && (total == 0 || hipMemcpy(d_spec, spec, (size_t)total * bands * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess);
+    if (!ok) return WSA_ERR_HIP;
+    uint32_t cnt[16];
+    if (total) {
+        PkParams pk; pk.spec = d_spec; pk.rec = rec; pk.bands = bands; pk.flags = d_counters + 8; pk.total_frames = (uint32_t)total;
+        launch_peaks(pk, nullptr);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(cnt, d_counters, sizeof(cnt), hipMemcpyDeviceToHost) == hipSuccess;
+        if (ok && (cnt[8] & 1u)) return WSA_ERR_INVALID;                                // a frame with more than CAND_CAP candidates: its table is cut short
+        if (!ok) return WSA_ERR_HIP;
+    }
+    GateParams g;
+    g.rec = rec; g.n_frames = d_nfr; g.frame_off = d_foff; g.n_clips = n_clips; g.level = D.klevel; g.max_voiced_bin = D.max_voiced_bin; g.breaker = D.breaker;
+    g.min_frames = D.min_frames; g.auto_gate = D.auto_gate; g.ctx_max0 = D.ctx_max0; g.floor0 = D.floor0; g.fr_info = d_info; g.fr_v = d_v; g.fr_fl = d_fl;
+    g.seg_i = d_seg_i; g.seg_d = d_seg_d; g.seg_cap = seg_cap; g.seg_count = d_seg_count; g.clip_rows = d_clip_rows; g.counters = d_counters + 4; g.shared = d_counters;
+    g.dbg = variant == 1 ? DBG_GATE_GENERAL : (variant == 2 ? DBG_GATE_F64 : 0);
+    g.span_hist = d_hist; g.span_key = reinterpret_cast<uint2*>(d_key);
+    launch_gate_blocks(g, blocks, nullptr);
+    TrParams t;
+    t.n_clips = n_clips; t.seg_count = d_seg_count; t.seg_cap = seg_cap; t.seg_i = d_seg_i;
+    launch_span_order(t, d_hist, reinterpret_cast<const uint2*>(d_key), reinterpret_cast<uint2*>(d_order), d_counters + 4, nullptr);
+    ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(cnt, d_counters, sizeof(cnt), hipMemcpyDeviceToHost) == hipSuccess
+      && fold_down(seg_i, d_seg_i, segs * 8) && fold_down(seg_count, d_seg_count, (size_t)n_clips) && fold_down(hist, d_hist, (size_t)SPAN_BUCKETS)
+      && fold_down(key, d_key, segs * 2) && fold_down(order, d_order, segs * 2);
+    if (ok) for (int q = 0; q < 4; q++) counters4[q] = cnt[4 + q];
     return ok ? WSA_OK : WSA_ERR_HIP;
 }

@@ -201,6 +201,9 @@ struct CompactParams {
     uint32_t* clr_counters = nullptr; uint32_t* clr_hist = nullptr;
 };
 bool compact_is_fused(const CompactParams& p);
+// the form launch_compact runs: nothing (no clips), the fused gather, compact_scan_kernel<true> + gather, compact_count_kernel + compact_scan_kernel<false> + gather
+enum { COMPACT_NOTHING = -1, COMPACT_FUSED = 0, COMPACT_SCAN = 1, COMPACT_COUNT_SCAN = 2 };
+int compact_path(const CompactParams& p);
 enum { CARRY_HIST = 32, CARRY_WORDS = 2 + 2 * CARRY_HIST };
 
 // ---- K4 utterance features (output_level 11): reads the compacted level-10 products
