@@ -1054,6 +1054,46 @@ wsa_status wsa_batch_set_input_format(wsa_batch *b, const int32_t *formats, cons
 uint64_t   wsa_batch_packed_offset(const wsa_batch *b, uint32_t clip);   /* 0 before wsa_batch_set_input_format and for clip > n_clips */
 wsa_status wsa_batch_run_packed(wsa_batch *b, const void *d_packed, void *stream);
 
+/*
+ * ---- Multichannel PCM: any channel, every channel or the mono mix (additions within version 5: probe for wsa_batch_set_input_channels).
+ *
+ * The entries above analyse channel 0 of an interleaved clip or stream.  Spec PK-3: each clip (each stream) names what it
+ * takes from an interleaved source of `channels` channels through a `select` word and a `source` word.
+ *   - select: a channel index 0 .. channels - 1 — sample j is element j * channels + select, decoded as PK-1 / PK-2 decode channel 0 — or
+ *     WSA_CHANNEL_MIX: m_j = (((x_j,0 + x_j,1) + x_j,2) + ...) * fl32(1 / channels), every term a PK-2 decoded fp32 value, fp32 additions in
+ *     ascending channel order, then one fp32 multiply (two channels: Web Audio's 0.5 * (L + R)).  NaN and Inf propagate as fp32 arithmetic
+ *     gives them; one channel with MIX is the plain decode.  NULL: every clip takes channel 0.
+ *   - source: NULL (every clip reads its own bytes), or source[i] = the clip whose bytes clip i reads.  A source names itself
+ *     (source[source[i]] == source[i]); a consumer takes its source's format and channel count (its own formats / channels entries are
+ *     not read) and has no more frames than its source.  The bytes of a C-channel file travel once and feed up to C + 1 clips.  Consumers
+ *     have no bytes of their own: wsa_batch_packed_offset of a consumer is its source's offset.
+ *   - Nothing behind a source's last frame is read, nothing behind a clip's own frame count is written.
+ * A clip that selects c, or the mix, gives byte for byte what the same batch gives through wsa_batch_run_host on a mono float clip holding
+ * wsa_pcm_decode_select of those bytes: every result table at every output level, on plain, resampled and mixed-rate batches, every
+ * attached model's output; streams the same, step for step, against wsa_stream_step_host.
+ * wsa_batch_set_input_channels has the role of wsa_batch_set_input_format (plans the layout, uploads the descriptors, allocates the
+ * staging); wsa_batch_run_packed then runs it, launches only (batch_deinterleave_kernel: each source's bytes once through LDS, one float
+ * row per clip that reads them).  wsa_batch_run_host_channels takes host clips; pcm[i] of a consumer is ignored.
+ * wsa_stream_set_input_channels: stream i reads the packed row of stream source[i] (formats as wsa_stream_set_input_format takes them);
+ * counts and control bytes stay per stream, the host fills one row per source.  WSA_PCM_F32 returns to the float buffers (channels all 1,
+ * select 0 or the mix, every stream its own source).
+ * WSA_ERR_INVALID with a message that names the clip or stream: a select that is neither an index below `channels` nor
+ * WSA_CHANNEL_MIX; a source out of range, or one that is not its own source; a consumer with more frames than its source; what the
+ * format entries refuse.  wsa_pcm_decode_select (no context, no message) refuses what wsa_pcm_decode refuses, and such a select.
+ * wsa_pcm_channels_tile_frames: the frames of one source a workgroup of batch_deinterleave_kernel takes at a time (a multiple of 16; 0 for
+ * an unknown format or channels outside 1 .. 64).
+ */
+#define WSA_CHANNEL_MIX 0xFFFFFFFFu
+/* PK-3 on the host, no device.  select = c reads nothing behind channel c of the last frame; the mix reads whole frames */
+wsa_status wsa_pcm_decode_select(int32_t format, const void *in, uint64_t n_frames, uint32_t channels, uint32_t select, float *out);
+wsa_status wsa_batch_set_input_channels(wsa_batch *b, const int32_t *formats, const uint32_t *channels, const uint32_t *select,
+                                        const uint32_t *source);
+wsa_status wsa_batch_run_host_channels(wsa_batch *b, const void *const *pcm, const int32_t *formats, const uint32_t *channels,
+                                       const uint32_t *select, const uint32_t *source, void *stream);
+wsa_status wsa_stream_set_input_channels(wsa_stream *st, int32_t format, const uint32_t *channels, const uint32_t *select,
+                                         const uint32_t *source);
+uint32_t   wsa_pcm_channels_tile_frames(int32_t format, uint32_t channels);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,63 @@
+"""Spec PK-3's test inputs, shared by tests/test_pcm_channels_host.py and tests/test_gpu_pcm_channels.py: numpy's float32 statement of the
+channel select and the mono mix, interleaved sample matrices of every format, and the planning call of the kernel's debug entry."""
+import ctypes
+
+import numpy as np
+
+from tests.batch_pcm_cases import DTYPE, SAMPLE_BYTES, reference, samples
+from webspeechanalyzer_amd import capi
+
+MIX = capi.CHANNEL_MIX
+ELEMS = {"i24": 3}                      # array elements per sample
+
+
+def frames_matrix(fmt, n, channels, seed):
+    """[n, channels] samples of a format (i24: [n, channels, 3] bytes): the format's edge values, tiled, each channel starting elsewhere in them"""
+    e = ELEMS.get(fmt, 1)
+    cols = [np.roll(samples(fmt, n + 11, seed + c), -(3 * c + seed) * e)[:n * e].reshape(n, e) for c in range(channels)]
+    return np.stack(cols, axis=1).reshape((n, channels, e) if e > 1 else (n, channels))
+
+
+def interleaved(m):
+    """the matrix as the flat array pcm_decode takes"""
+    return np.ascontiguousarray(m).reshape(-1)
+
+
+def decoded_channels(fmt, m):
+    """float32 [n, channels]: numpy's statement of the format's rule (tests/batch_pcm_cases.reference) for every sample of the matrix"""
+    n, ch = m.shape[0], m.shape[1]
+    return reference(fmt, interleaved(m)).reshape(n, ch)
+
+
+def pk3(fmt, m, select):
+    """spec PK-3 in numpy float32: channel `select`, or (((x0 + x1) + x2) + ...) * fl32(1 / channels), every operation rounded to float32"""
+    x = decoded_channels(fmt, m)
+    if select != MIX:
+        return x[:, select].copy()
+    acc = x[:, 0].copy()
+    if x.shape[1] == 1:
+        return acc
+    with np.errstate(over="ignore", invalid="ignore"):
+        for c in range(1, x.shape[1]):
+            acc = (acc + x[:, c]).astype(np.float32)
+        return (acc * (np.float32(1.0) / np.float32(x.shape[1]))).astype(np.float32)
+
+
+def plan(formats, channels, select, source, n_frames):
+    """pcm_plan_channels through wsa_debug_batch_deinterleave's planning call (no device): (status, offsets [n + 1], message)"""
+    L = capi.lib()
+    f = L.wsa_debug_batch_deinterleave
+    f.argtypes = [ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 5 + [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                                                               ctypes.c_char_p, ctypes.c_uint32]
+    f.restype = ctypes.c_int
+    n = len(n_frames)
+    arr = lambda v, dt: None if v is None else np.ascontiguousarray(v, dtype=dt)
+    fm, ch, sel, src, nf = arr(formats, np.int32), arr(channels, np.uint32), arr(select, np.uint32), arr(source, np.uint32), arr(n_frames, np.uint32)
+    off = np.zeros(n + 1, np.uint64)
+    err = ctypes.create_string_buffer(512)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    st = f(0, None, 0, ptr(fm), ptr(ch), ptr(sel), ptr(src), ptr(nf), n, off.ctypes.data, None, 0, err, 512)
+    return st, off, err.value.decode()
+
+
+__all__ = ["DTYPE", "SAMPLE_BYTES", "MIX", "ELEMS", "frames_matrix", "interleaved", "decoded_channels", "pk3", "plan"]

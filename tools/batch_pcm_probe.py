@@ -7,11 +7,16 @@
                 entries that exist without PK-2 are unchanged by it: their rows are the parent's numbers, taken in the same session.
   step unpack   the same clips device-resident: wsa_batch_run_packed per format beside wsa_batch_run on the decoded floats, device events
                 around each; the difference of the medians is batch_unpack_kernel's time (one kernel in front of an unchanged run).
+  step channels the interleaved path (spec PK-3; profiles/pcm_channels.md): the same clips as stereo files, i16 and i24, device-resident, the second
+                channel another signal.  Per format: channel 0 through batch_unpack_kernel (wsa_batch_set_input_format, the strided path), then
+                batch_deinterleave_kernel (wsa_batch_set_input_channels) for channel 0 alone, for both channels (2 x clips analyses) and for both
+                channels and the mix (3 x clips analyses) — each beside wsa_batch_run on the decoded floats of the same analyses, device events
+                around each, the difference of the medians the kernel's time; and the bytes each kernel has to move.
 
 Run without --step, the script touches no GPU itself: it starts every step as a child under its own time limit and stops at the first
 that fails.
 
-    python tools/batch_pcm_probe.py [--clips 1024] [--seconds 10] [--rounds 15] [--out FILE]"""
+    python tools/batch_pcm_probe.py [--clips 1024] [--seconds 10] [--rounds 15] [--only STEP] [--out FILE]"""
 import argparse
 import ctypes
 import json
@@ -28,16 +33,17 @@ ap.add_argument("--clips", type=int, default=1024)
 ap.add_argument("--seconds", type=float, default=10.0)
 ap.add_argument("--rounds", type=int, default=15)
 ap.add_argument("--warmup", type=int, default=3)
-ap.add_argument("--step", default="", help="host | unpack (a child of the driver)")
+ap.add_argument("--step", default="", help="host | unpack | channels (a child of the driver)")
+ap.add_argument("--only", default="", help="the driver runs this step alone")
 ap.add_argument("--limit", type=int, default=240, help="seconds a step may take")
 ap.add_argument("--out", default="")
 args = ap.parse_args()
 FS = 16000
-STEPS = ["host", "unpack"]
+STEPS = ["host", "unpack", "channels"]
 
 if not args.step:
     results = []
-    for step in STEPS:                       # each GPU step under its own limit, chained: a failure ends the probe
+    for step in ([args.only] if args.only else STEPS):       # each GPU step under its own limit, chained: a failure ends the probe
         cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--step", step, "--clips", str(args.clips),
                "--seconds", str(args.seconds), "--rounds", str(args.rounds), "--warmup", str(args.warmup)]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
@@ -141,7 +147,7 @@ if args.step == "host":
     for name, fmt, call, b in opened:
         stats(name, ms[name], step="host", format=fmt, link_bytes=int(n * ns * BYTES[fmt]), rows=rows[name])
         b.close()
-else:
+elif args.step in ("unpack", "channels"):
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
     def timed(call):
@@ -156,7 +162,36 @@ else:
                 out.append(ev0.elapsed_time(ev1))
         return out
 
-    for fmt in ("f32", "i16", "mulaw", "i24"):
+    for fmt in (("i16", "i24") if args.step == "channels" else ()):
+        sb = BYTES[fmt]
+        mono = encoded(fmt).reshape(distinct, ns, sb)
+        e = np.stack([mono, np.roll(mono, 1, axis=0)], axis=2).reshape(distinct, -1)      # stereo files: channel 1 is the next signal
+        flo = {sel: np.stack([capi.pcm_decode(fmt, e[i].view(DT[fmt]), 2, sel) for i in range(distinct)]) for sel in (0, 1, "mix")}
+        file_bytes = n * ns * 2 * sb
+        # (name, select per analysis of a file, the plan): the analyses of file i stand side by side, the first is the source
+        for name, sels in (("ch0_strided", None), ("ch0", [0]), ("both", [0, 1]), ("both_mix", [0, 1, "mix"])):
+            k = len(sels) if sels else 1
+            b = an.batch([ns] * (n * k), FS)
+            b.enable_timing(False)
+            if sels is None:
+                b.set_input_format(fmt, [2] * n)
+            else:
+                b.set_input_channels(fmt, [2] * (n * k), sels * n, [i - i % k for i in range(n * k)])
+            off = b.packed_offsets()
+            host = np.zeros(int(off[-1]), np.uint8)
+            for i in range(n):
+                host[int(off[i * k]):int(off[i * k]) + e.shape[1]] = e[i % distinct]
+            dev = torch.from_numpy(host).cuda()
+            floats = torch.from_numpy(np.stack([flo[sel][i % distinct] for i in range(n) for sel in (sels or [0])])).cuda().contiguous()
+            t_packed = timed(lambda: b.run_packed(dev.data_ptr(), stream))
+            t_float = timed(lambda: b.run(floats.data_ptr(), floats.stride(0), stream))
+            # read: the strided path touches every 64-byte line of a stereo file for half of its content; the tile reads each byte once
+            stats("channels_%s_%s" % (fmt, name), t_packed, step="channels", format=fmt, analyses=n * k, float_run_median_ms=float(np.median(t_float)),
+                  kernel_ms=float(np.median(t_packed) - np.median(t_float)), source_bytes=int(file_bytes), bytes_used=int(file_bytes if sels else file_bytes // 2),
+                  bytes_written=int(n * k * ns * 4))
+            b.close()
+            del dev, floats
+    for fmt in (("f32", "i16", "mulaw", "i24") if args.step == "unpack" else ()):
         e = encoded(fmt)
         b = an.batch([ns] * n, FS)
         b.enable_timing(False)

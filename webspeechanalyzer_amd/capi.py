@@ -218,7 +218,11 @@ ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destr
                "wsa_stream_set_input_format", "wsa_stream_host_input_packed", "wsa_stream_input_stride_bytes", "wsa_stream_step_packed",
                "wsa_stream_time_steps_packed", "wsa_pcm_decode",
                # additions within version 5 (probe for wsa_batch_run_host_packed): every PCM encoding a WAV holds into batches, unpacked on the GPU (spec PK-2)
-               "wsa_batch_run_host_packed", "wsa_batch_set_input_format", "wsa_batch_packed_offset", "wsa_batch_run_packed"]
+               "wsa_batch_run_host_packed", "wsa_batch_set_input_format", "wsa_batch_packed_offset", "wsa_batch_run_packed",
+               # additions within version 5 (probe for wsa_batch_set_input_channels): any channel, every channel or the mono mix of interleaved PCM (spec PK-3)
+               "wsa_pcm_decode_select", "wsa_batch_set_input_channels", "wsa_batch_run_host_channels", "wsa_stream_set_input_channels",
+               "wsa_pcm_channels_tile_frames"]
+CHANNEL_MIX = 0xFFFFFFFF                                # WSA_CHANNEL_MIX: the `select` word that takes the mono mix (spec PK-3); 'mix' in the Python entries
 PCM_F32, PCM_I16, PCM_MULAW, PCM_ALAW = 0, 1, 2, 3      # WSA_PCM_* of include/wsa.h
 PCM_U8, PCM_I24, PCM_I32, PCM_F64 = 8, 9, 10, 11        # ... the file encodings of spec PK-2 (batches and pcm_decode; 4 .. 7 are unassigned)
 _PCM_NAMES = {"f32": PCM_F32, "i16": PCM_I16, "mulaw": PCM_MULAW, "alaw": PCM_ALAW, "u8": PCM_U8, "i24": PCM_I24, "i32": PCM_I32, "f64": PCM_F64}
@@ -405,8 +409,13 @@ def lib():
     L.wsa_batch_packed_offset.argtypes = [vp, u32]
     L.wsa_batch_packed_offset.restype = u64
     L.wsa_batch_run_packed.argtypes = [vp, vp, vp]
+    L.wsa_pcm_decode_select.argtypes = [i32, vp, u64, u32, u32, vp]
+    L.wsa_batch_set_input_channels.argtypes = [vp, vp, vp, vp, vp]
+    L.wsa_batch_run_host_channels.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.wsa_stream_set_input_channels.argtypes = [vp, i32, vp, vp, vp]
+    L.wsa_pcm_channels_tile_frames.argtypes = [i32, u32]
     for name in ABI_SYMBOLS:
-        if name in _U32_RESULT or name in ("wsa_resample_ready", "wsa_level_feature_count", "wsa_batch_packed_offset"):
+        if name in _U32_RESULT or name in ("wsa_resample_ready", "wsa_level_feature_count", "wsa_batch_packed_offset", "wsa_pcm_channels_tile_frames"):
             continue
         if name not in ("wsa_abi_version", "wsa_last_error", "wsa_config_default", "wsa_destroy", "wsa_batch_destroy", "wsa_resample_length",
                         "wsa_stream_destroy", "wsa_stream_samples_per_step", "wsa_stream_host_input", "wsa_stream_host_input_packed", "wsa_gather_destroy", "wsa_host_free",
@@ -436,21 +445,43 @@ def _pcm_array(fmt, f, array):
     return a.reshape(-1)
 
 
-def pcm_decode(fmt, array, channels=1):
-    """Specs PK-1 / PK-2 on the host (wsa_pcm_decode, no device): channel 0 of the interleaved frames in `array` (int16 for 'i16', uint8 for
-    the G.711 laws and 'u8', three uint8 per sample for 'i24', int32 for 'i32', float64 for 'f64', float32 for 'f32'; a trailing partial
-    frame is ignored) as float32 — the floats a stream set or a batch fed `array` analyses."""
+def channel_select(select, channels=None):
+    """A PK-3 `select` word from a channel index or 'mix' (or CHANNEL_MIX); with `channels` given, an index at or above it is refused."""
+    if isinstance(select, str):
+        if select != "mix":
+            raise WsaError(f"select {select!r}: a channel index or 'mix'")
+        return CHANNEL_MIX
+    if isinstance(select, (bool, float)) or not 0 <= int(select) <= CHANNEL_MIX:
+        raise WsaError(f"select {select!r}: a channel index or 'mix'")
+    s = int(select)
+    if channels is not None and s != CHANNEL_MIX and s >= int(channels):
+        raise WsaError(f"select {s} is neither a channel below {int(channels)} nor 'mix'")
+    return s
+
+
+def pcm_decode(fmt, array, channels=1, select=0):
+    """Specs PK-1 / PK-2 / PK-3 on the host (wsa_pcm_decode_select, no device): channel `select` (0 by default; 'mix': the mono mix) of the
+    interleaved frames in `array` (int16 for 'i16', uint8 for the G.711 laws and 'u8', three uint8 per sample for 'i24', int32 for 'i32',
+    float64 for 'f64', float32 for 'f32'; a trailing partial frame is ignored where it does not hold the selected channel) as float32 — the
+    floats a stream set or a batch fed `array` analyses."""
     f = pcm_format(fmt)
     ch = int(channels)
     if not 1 <= ch <= 64:
         raise WsaError(f"channel count {ch} outside 1 .. 64")
+    sel = channel_select(select, ch)
     a = _pcm_array(fmt, f, array)
     size = a.size // _PCM_ELEMS.get(f, 1)            # whole samples
-    n = (size - 1) // ch + 1 if size else 0          # frames whose channel 0 is present
+    last = ch - 1 if sel == CHANNEL_MIX else sel     # the last channel of a frame that is read
+    n = (size - 1 - last) // ch + 1 if size > last else 0          # frames whose selected channel (the mix: every channel) is present
     out = np.zeros(n, np.float32)
-    if lib().wsa_pcm_decode(f, a.ctypes.data, n, ch, out.ctypes.data) != 0:
-        raise WsaError("wsa_pcm_decode refused its arguments")
+    if lib().wsa_pcm_decode_select(f, a.ctypes.data, n, ch, sel, out.ctypes.data) != 0:
+        raise WsaError("wsa_pcm_decode_select refused its arguments")
     return out
+
+
+def pcm_channels_tile_frames(fmt, channels):
+    """wsa_pcm_channels_tile_frames: the frames of one source a workgroup of batch_deinterleave_kernel takes at a time (spec PK-3)."""
+    return int(lib().wsa_pcm_channels_tile_frames(pcm_format(fmt), int(channels)))
 
 
 def level_feature_count(output_level):
@@ -689,6 +720,54 @@ class Batch:
     def run_packed(self, d_packed, stream=0):
         """Device-resident packed clips at d_packed + packed_offsets()[i] (a raw device pointer, 16-byte aligned): kernel launches only."""
         self.an._check(self.L.wsa_batch_run_packed(self.h, d_packed, stream))
+
+    def _select_source(self, select, source):
+        n = len(self.n_samples)
+        sel = None
+        if select is not None:
+            sv = [select] * n if isinstance(select, (str, int)) else list(select)
+            if len(sv) != n:
+                raise WsaError("one select (a channel index or 'mix') per clip")
+            sel = (ctypes.c_uint32 * max(n, 1))(*[channel_select(v) for v in sv])
+        src = None
+        if source is not None:
+            if len(source) != n:
+                raise WsaError("one source (a clip index) per clip")
+            if any(int(v) < 0 or int(v) > 0xFFFFFFFF for v in source):
+                raise WsaError("a source is a clip index")
+            src = (ctypes.c_uint32 * max(n, 1))(*[int(v) for v in source])
+        return sel, src
+
+    def set_input_channels(self, formats, channels=None, select=None, source=None):
+        """Plans the device-resident layout of spec PK-3 (wsa_batch_set_input_channels): clip i takes channel select[i] ('mix': the mono mix; None:
+        channel 0) of the bytes of clip source[i] (None: its own).  Only sources have bytes: packed_offsets()[i] of a consumer is its source's
+        offset, the last entry the buffer's size.  run_packed() then runs it."""
+        fm, ch = self._formats(formats, channels)
+        sel, src = self._select_source(select, source)
+        self.an._check(self.L.wsa_batch_set_input_channels(self.h, fm, ch, sel, src))
+
+    def run_host_channels(self, clips, formats, channels=None, select=None, source=None, stream=0):
+        """run_host_packed() with a select and a source per clip (spec PK-3, wsa_batch_run_host_channels): a source's bytes are uploaded once and
+        feed every clip that names it; clips[i] of a consumer is not read (None is fine)."""
+        fm, ch = self._formats(formats, channels)
+        sel, src = self._select_source(select, source)
+        held, ptrs = [], []
+        ns_in = getattr(self, "n_samples_in", self.n_samples)
+        for i, c in enumerate(clips):
+            if src is not None and int(src[i]) != i:
+                ptrs.append(None)
+                continue
+            f = int(fm[i])
+            a = _pcm_array(f, f, c) if f in _PCM_DTYPE else np.ascontiguousarray(c).reshape(-1)
+            need = int(ns_in[i]) * (int(ch[i]) if ch is not None else 1) * _PCM_ELEMS.get(f, 1)
+            if f in _PCM_DTYPE and a.size < need:
+                raise WsaError(f"clip {i}: {a.size} elements, the plan's {int(ns_in[i])} frames need {need}")
+            held.append(a)
+            ptrs.append(a.ctypes.data)
+        if len(ptrs) != len(self.n_samples):
+            raise WsaError("one entry per clip (a consumer's may be None)")
+        arr = (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
+        self.an._check(self.L.wsa_batch_run_host_channels(self.h, arr, fm, ch, sel, src, stream))
 
     def enable_timing(self, on):
         self.an._check(self.L.wsa_batch_enable_timing(self.h, int(on)))
@@ -1516,6 +1595,37 @@ class Streams:
                 raise WsaError(f"channel count {int(ch.min() if ch.min() < 0 else ch.max())} outside 1 .. 64")
             ch = ch.astype(np.uint32)
         self.an._check(self.L.wsa_stream_set_input_format(self.h, f, ch.ctypes.data if ch is not None else None))
+        self.input_format = f
+        self.channels = ch if ch is not None else np.ones(self.n, np.uint32)
+        self.input_stride_bytes = int(self.L.wsa_stream_input_stride_bytes(self.h))
+
+    def set_input_channels(self, fmt, channels=None, select=None, source=None):
+        """set_input_format() with a select and a source per stream (spec PK-3, wsa_stream_set_input_channels): stream i takes channel select[i]
+        ('mix': the mono mix; None: channel 0; one value for all is fine) of the packed row of stream source[i] (None: its own).  The host fills
+        one row per source; counts and control bytes stay per stream."""
+        f = pcm_format(fmt)
+        ch = None
+        if channels is not None:
+            ch = np.ascontiguousarray(np.broadcast_to(np.asarray(channels, np.int64), (self.n,)) if np.ndim(channels) == 0 else channels, dtype=np.int64)
+            if ch.shape != (self.n,):
+                raise WsaError("channels as a sequence holds one count per stream")
+            if ch.min() < 0 or ch.max() > 0xFFFFFFFF:
+                raise WsaError(f"channel count {int(ch.min() if ch.min() < 0 else ch.max())} outside 1 .. 64")
+            ch = ch.astype(np.uint32)
+        sel = None
+        if select is not None:
+            sv = [select] * self.n if isinstance(select, (str, int)) else list(select)
+            if len(sv) != self.n:
+                raise WsaError("one select (a channel index or 'mix') per stream")
+            sel = np.asarray([channel_select(v) for v in sv], np.uint32)
+        src = None
+        if source is not None:
+            src = np.ascontiguousarray(source, dtype=np.int64)
+            if src.shape != (self.n,) or src.min() < 0 or src.max() > 0xFFFFFFFF:
+                raise WsaError("one source (a stream index) per stream")
+            src = src.astype(np.uint32)
+        self.an._check(self.L.wsa_stream_set_input_channels(self.h, f, ch.ctypes.data if ch is not None else None, sel.ctypes.data if sel is not None else None,
+                                                            src.ctypes.data if src is not None else None))
         self.input_format = f
         self.channels = ch if ch is not None else np.ones(self.n, np.uint32)
         self.input_stride_bytes = int(self.L.wsa_stream_input_stride_bytes(self.h))

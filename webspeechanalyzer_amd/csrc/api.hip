@@ -42,6 +42,7 @@ struct wsa_batch {
     // wsa_batch_set_input_format / wsa_batch_run_packed: the planned layout's table and offsets — two tables, so that a host run never rewrites what a captured graph reads
     uint8_t* d_pk = nullptr; uint64_t pk_cap = 0; PcmClipDesc* d_pk_desc = nullptr; std::vector<PcmClipDesc> h_pk_desc;
     PcmClipDesc* d_pkf_desc = nullptr; std::vector<uint64_t> pkf_off; bool pkf_set = false;
+    bool pkf_channels = false;              // the planned table is PK-3's (wsa_batch_set_input_channels): wsa_batch_run_packed launches batch_deinterleave_kernel
     bool pair = false;                   // tracker: two spans per wave (tracker_kernel_pair)
     bool published = false;              // the last back-end run's compaction kernel has handed the result counters to the host itself
     Tuning tune;                         // tuning / test switches, read from the environment when the batch is planned
@@ -661,10 +662,11 @@ wsa_status wsa_batch_set_input_format(wsa_batch* b, const int32_t* formats, cons
     if (!b->d_pcm_own && !b->mem.alloc(&b->d_pcm_own, (size_t)b->n_clips * stride)) return fail(ctx, WSA_ERR_HIP, "PCM staging allocation failed");
     if (!b->d_pkf_desc && !b->mem.alloc(&b->d_pkf_desc, (size_t)b->n_clips)) return fail(ctx, WSA_ERR_HIP, "packed clip table allocation failed");
     HIP_TRY(ctx, hipMemcpy(b->d_pkf_desc, desc.data(), desc.size() * sizeof(PcmClipDesc), hipMemcpyHostToDevice));
-    b->pkf_off = off; b->pkf_set = true;
+    b->pkf_off = off; b->pkf_set = true; b->pkf_channels = false;
     return WSA_OK;
 }
 
+// (PK-3: pkf_off[i] of a consumer is its source's offset)
 uint64_t wsa_batch_packed_offset(const wsa_batch* b, uint32_t clip) { return b && b->pkf_set && clip <= b->n_clips ? b->pkf_off[clip] : 0; }
 
 wsa_status wsa_batch_run_packed(wsa_batch* b, const void* d_packed, void* stream) {
@@ -676,10 +678,63 @@ wsa_status wsa_batch_run_packed(wsa_batch* b, const void* d_packed, void* stream
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint64_t stride = ((b->rs_on ? b->max_samples_in : b->max_samples) + 3u) & ~3ull;
-    launch_batch_unpack(d_packed, b->d_pkf_desc, b->n_clips, b->rs_on ? b->max_samples_in : b->max_samples, b->d_pcm_own, stride, s);
+    if (b->pkf_channels) launch_batch_deinterleave(d_packed, b->d_pkf_desc, b->n_clips, b->rs_on ? b->max_samples_in : b->max_samples, b->d_pcm_own, stride, s);
+    else launch_batch_unpack(d_packed, b->d_pkf_desc, b->n_clips, b->rs_on ? b->max_samples_in : b->max_samples, b->d_pcm_own, stride, s);
     HIP_TRY(ctx, hipGetLastError());
     return run_impl(b, b->d_pcm_own, stride, nullptr, true, true, s);
 }
+
+// ---- PK-3: any channel, every channel or the mix (pcm_channels.hip)
+static wsa_status plan_channels(wsa_batch* b, const int32_t* formats, const uint32_t* channels, const uint32_t* select, const uint32_t* source,
+                                std::vector<PcmClipDesc>& desc, std::vector<uint64_t>& off) {
+    const std::vector<uint32_t>& ns_host = b->rs_on ? b->n_samples_in : b->n_samples;
+    const std::string err = pcm_plan_channels(b->n_clips, ns_host.data(), formats, channels, select, source, desc, off);
+    return err.empty() ? WSA_OK : fail(b->ctx, WSA_ERR_INVALID, err);
+}
+
+wsa_status wsa_batch_set_input_channels(wsa_batch* b, const int32_t* formats, const uint32_t* channels, const uint32_t* select, const uint32_t* source) {
+    if (!b) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = b->ctx;
+    std::vector<PcmClipDesc> desc; std::vector<uint64_t> off;
+    { const wsa_status st = plan_channels(b, formats, channels, select, source, desc, off); if (st != WSA_OK) return st; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t stride = ((b->rs_on ? b->max_samples_in : b->max_samples) + 3u) & ~3ull;
+    if (!b->d_pcm_own && !b->mem.alloc(&b->d_pcm_own, (size_t)b->n_clips * stride)) return fail(ctx, WSA_ERR_HIP, "PCM staging allocation failed");
+    if (!b->d_pkf_desc && !b->mem.alloc(&b->d_pkf_desc, (size_t)b->n_clips)) return fail(ctx, WSA_ERR_HIP, "packed clip table allocation failed");
+    HIP_TRY(ctx, hipMemcpy(b->d_pkf_desc, desc.data(), desc.size() * sizeof(PcmClipDesc), hipMemcpyHostToDevice));
+    b->pkf_off = off; b->pkf_set = true; b->pkf_channels = true;
+    return WSA_OK;
+}
+
+wsa_status wsa_batch_run_host_channels(wsa_batch* b, const void* const* pcm, const int32_t* formats, const uint32_t* channels, const uint32_t* select,
+                                       const uint32_t* source, void* stream) {
+    if (!b || (!pcm && b->n_clips)) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = b->ctx;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    std::vector<PcmClipDesc> desc; std::vector<uint64_t> off;
+    { const wsa_status st = plan_channels(b, formats, channels, select, source, desc, off); if (st != WSA_OK) return st; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t stride = ((b->rs_on ? b->max_samples_in : b->max_samples) + 3u) & ~3ull;
+    if (!b->d_pcm_own && !b->mem.alloc(&b->d_pcm_own, (size_t)b->n_clips * stride)) return fail(ctx, WSA_ERR_HIP, "PCM staging allocation failed");
+    if (!b->d_pk || off[b->n_clips] > b->pk_cap) {                  // the upload buffer of wsa_batch_run_host_packed, grown the same way
+        if (b->d_pk) { (void)hipFree(b->d_pk); b->d_pk = nullptr; b->pk_cap = 0; }
+        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&b->d_pk), (size_t)off[b->n_clips] + 16));
+        b->pk_cap = off[b->n_clips];
+    }
+    if (!b->d_pk_desc && !b->mem.alloc(&b->d_pk_desc, (size_t)b->n_clips)) return fail(ctx, WSA_ERR_HIP, "packed clip table allocation failed");
+    b->h_pk_desc = desc;
+    HIP_TRY(ctx, hipMemcpyAsync(b->d_pk_desc, b->h_pk_desc.data(), b->h_pk_desc.size() * sizeof(PcmClipDesc), hipMemcpyHostToDevice, s));
+    {   // a source's bytes travel once; a consumer brings none
+        const wsa_status st = upload_clips(b, b->n_clips, [&](uint32_t i) { return b->d_pk + off[i]; }, [&](uint32_t i) { return pcm[i]; },
+                                           [&](uint32_t i) { return desc[i].source != i ? (size_t)0 : (size_t)desc[i].n_frames * desc[i].channels * pcm_sample_bytes(desc[i].format); }, s);
+        if (st != WSA_OK) return st;
+    }
+    launch_batch_deinterleave(b->d_pk, b->d_pk_desc, b->n_clips, b->rs_on ? b->max_samples_in : b->max_samples, b->d_pcm_own, stride, s);
+    HIP_TRY(ctx, hipGetLastError());
+    return run_impl(b, b->d_pcm_own, stride, nullptr, true, true, s);
+}
+
+uint32_t wsa_pcm_channels_tile_frames(int32_t format, uint32_t channels) { return pcm_format_known(format) && channels >= 1 && channels <= 64 ? pcm_tile_frames(format, channels) : 0u; }
 
 static wsa_status fetch_totals(wsa_batch* b, hipStream_t s) {
     wsa_ctx* ctx = b->ctx;

@@ -856,7 +856,7 @@ extern "C" int wsa_debug_batch_unpack(int32_t device, const void* packed, const 
         if (!wsa::pcm_format_known(formats[i]) || channels[i] < 1 || channels[i] > 64 || (off[i] & 15u) || off[i + 1] < off[i] || n_frames[i] > stride) return WSA_ERR_INVALID;
         const uint64_t need = n_frames[i] ? ((uint64_t)(n_frames[i] - 1u) * channels[i] + 1u) * wsa::pcm_sample_bytes(formats[i]) : 0;   // up to channel 0 of the last frame
         if (need > off[i + 1] - off[i]) return WSA_ERR_INVALID;
-        desc[i] = wsa::PcmClipDesc{off[i], formats[i], channels[i], n_frames[i], {0, 0, 0}};
+        desc[i] = wsa::PcmClipDesc{off[i], formats[i], channels[i], n_frames[i], 0, 0, 0};
         if (n_frames[i] > max_frames) max_frames = n_frames[i];
     }
     if (hipSetDevice(device) != hipSuccess) return WSA_ERR_NO_DEVICE;
@@ -867,6 +867,47 @@ extern "C" int wsa_debug_batch_unpack(int32_t device, const void* packed, const 
            && hipMemcpy(dout, out, nout * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
         wsa::launch_batch_unpack(dp, dd, n_clips, max_frames, dout, stride, nullptr);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dout, nout * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    return ok ? WSA_OK : WSA_ERR_HIP;
+}
+
+// PK-3's kernel (csrc/pcm_channels.hip) on its own: host-given packed bytes through ONE launch of batch_deinterleave_kernel, floats back.  The plan is
+// pcm_plan_channels', as the batch entries use it: off_out [n_clips + 1] comes back as planned (off_out[i]: where clip i's source starts), `packed` holds
+// packed_bytes bytes laid out by it — call with out == NULL first to get the offsets alone.  out [n_clips][stride] (any stride >= the longest clip, multiples
+// of four or not) goes to the device as the caller filled it and comes back: what the kernel did not write keeps the caller's value.  The device buffer is
+// exactly packed_bytes long.  Refused, nothing run: what the plan refuses (its message goes to err [err_cap], the planning call needs no device), a clip
+// longer than `stride`, fewer bytes than the plan needs.
+extern "C" int wsa_debug_batch_deinterleave(int32_t device, const void* packed, uint64_t packed_bytes, const int32_t* formats, const uint32_t* channels,
+                                            const uint32_t* select, const uint32_t* source, const uint32_t* n_frames, uint32_t n_clips, uint64_t* off_out,
+                                            float* out, uint64_t stride, char* err, uint32_t err_cap) {
+    if (err && err_cap) err[0] = 0;
+    if (!formats || !n_frames || !off_out || n_clips < 1 || n_clips > 65535u) return WSA_ERR_INVALID;
+    std::vector<wsa::PcmClipDesc> desc; std::vector<uint64_t> off;
+    const std::string why = wsa::pcm_plan_channels(n_clips, n_frames, formats, channels, select, source, desc, off);
+    if (!why.empty()) {
+        if (err && err_cap) { const size_t k = std::min<size_t>(why.size(), err_cap - 1u); std::memcpy(err, why.data(), k); err[k] = 0; }
+        return WSA_ERR_INVALID;
+    }
+    for (uint32_t i = 0; i <= n_clips; i++) off_out[i] = off[i];
+    if (!out) return WSA_OK;
+    if (stride < 1 || stride > (1u << 26) || off[n_clips] > (1ull << 32)) return WSA_ERR_INVALID;
+    uint32_t max_frames = 0;
+    uint64_t need = 0;                                             // the last byte any source's frames reach
+    for (uint32_t i = 0; i < n_clips; i++) {
+        if (n_frames[i] > stride) return WSA_ERR_INVALID;
+        if (n_frames[i] > max_frames) max_frames = n_frames[i];
+        if (desc[i].source == i) need = std::max<uint64_t>(need, desc[i].offset + (uint64_t)n_frames[i] * desc[i].channels * wsa::pcm_sample_bytes(desc[i].format));
+    }
+    if (need > packed_bytes || (packed_bytes && !packed)) return WSA_ERR_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return WSA_ERR_NO_DEVICE;
+    wsa::DevArena A; uint8_t* dp = nullptr; wsa::PcmClipDesc* dd = nullptr; float* dout = nullptr;
+    const size_t nout = (size_t)n_clips * stride;
+    bool ok = A.alloc(&dp, (size_t)packed_bytes + 1) && A.upload(&dd, desc) && A.alloc(&dout, nout)
+           && (packed_bytes == 0 || hipMemcpy(dp, packed, (size_t)packed_bytes, hipMemcpyHostToDevice) == hipSuccess)
+           && hipMemcpy(dout, out, nout * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        wsa::launch_batch_deinterleave(dp, dd, n_clips, max_frames, dout, stride, nullptr);
         ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dout, nout * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess;
     }
     return ok ? WSA_OK : WSA_ERR_HIP;

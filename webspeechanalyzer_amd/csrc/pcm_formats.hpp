@@ -1,8 +1,10 @@
-// pcm_formats.hpp — specs PK-1 and PK-2: a packed sample becomes the float the float path would have been given.  The same
-// functions run on the host (wsa_pcm_decode), in stream_pull_packed_kernel and in batch_unpack_kernel: integer arithmetic first, then one
-// conversion and one exact division.
+// pcm_formats.hpp — specs PK-1, PK-2 and PK-3: a packed sample becomes the float the float path would have been given.  The same
+// functions run on the host (wsa_pcm_decode, wsa_pcm_decode_select), in stream_pull_packed_kernel, stream_pull_channels_kernel,
+// batch_unpack_kernel and batch_deinterleave_kernel: integer arithmetic first, then one conversion and one exact division.
 #pragma once
 #include <cstdint>
+#include <string>
+#include <vector>
 #include <hip/hip_runtime.h>
 #include "../../include/wsa.h"
 
@@ -90,15 +92,45 @@ inline const char* pcm_format_name(int32_t format) {
          : format == WSA_PCM_U8 ? "u8" : format == WSA_PCM_I24 ? "i24" : format == WSA_PCM_I32 ? "i32" : format == WSA_PCM_F64 ? "f64" : "unknown";
 }
 
-// ---- batch_unpack_kernel (batch_pcm.hip): one 32-byte descriptor per clip
+// ---- PK-3: what a clip or a stream takes from its interleaved frames.  select: a channel index below `channels`, or WSA_CHANNEL_MIX
+__host__ __device__ inline bool pcm_select_known(uint32_t select, uint32_t channels) { return select < channels || select == WSA_CHANNEL_MIX; }
+// the mix of one frame: at(c) is channel c's decoded float.  fp32 additions in ascending channel order, then ONE multiply by fl32(1 / channels);
+// every decode scale is a power of two, so no product in front of an addition is inexact and a contracted build gives the same bits
+template <class At>
+__host__ __device__ inline float pcm_mix_frame(uint32_t channels, At at) {
+    float acc = at(0u);
+    if (channels == 1u) return acc;                                  // the plain decode, bit for bit
+    for (uint32_t c = 1; c < channels; c++) acc = acc + at(c);
+    return acc * (1.0f / (float)channels);
+}
+
+// ---- batch_unpack_kernel (batch_pcm.hip), batch_deinterleave_kernel (pcm_channels.hip): one 32-byte descriptor per clip
 struct PcmClipDesc {
-    uint64_t offset;       // bytes from the packed base to the clip's first byte, a multiple of 16
+    uint64_t offset;       // bytes from the packed base to the clip's first byte, a multiple of 16 (PK-3: the first byte of the clip's source)
     int32_t format;        // WSA_PCM_*
     uint32_t channels;     // 1 .. 64
     uint32_t n_frames;     // floats written to the clip's staging row
-    uint32_t pad[3];
+    // PK-3 only (batch_unpack_kernel reads none of them)
+    uint32_t select;       // channel index, or WSA_CHANNEL_MIX
+    uint32_t source;       // the clip whose bytes this one reads; a source names itself
+    uint32_t next;         // the next clip that reads the same source, PCM_NO_CLIP behind the last: a source heads the list of its consumers
 };
 static_assert(sizeof(PcmClipDesc) == 32, "one 32-byte descriptor per clip");
+constexpr uint32_t PCM_NO_CLIP = 0xFFFFFFFFu;
+// PK-3's tile: frames of one source a workgroup of batch_deinterleave_kernel holds in LDS at a time.  A multiple of 16, so that a tile's bytes
+// are whole 16-byte chunks for every format and channel count; at most PCM_TILE_BYTES (64 channels of f64, 512 bytes a frame: 32 frames)
+constexpr uint32_t PCM_TILE_BYTES = 16384u, PCM_TILE_MAX_FRAMES = 2048u;
+__host__ __device__ inline uint32_t pcm_tile_frames(int32_t format, uint32_t channels) {
+    const uint32_t fb = channels * pcm_sample_bytes(format);
+    if (fb == 0) return 0;
+    const uint32_t t = (PCM_TILE_BYTES / fb) & ~15u;
+    return t > PCM_TILE_MAX_FRAMES ? PCM_TILE_MAX_FRAMES : t;
+}
+// PK-3: every source's tiles once through LDS, one float row per clip that reads it.  desc as plan_channels (api.hip) builds it.
+void launch_batch_deinterleave(const void* packed, const PcmClipDesc* desc, uint32_t n_clips, uint32_t max_frames, float* out, uint64_t stride, hipStream_t s);
+// PK-3's plan (pcm_channels.hip): desc [n_clips], off [n_clips + 1] (off[i]: where clip i's source starts, off[n_clips]: bytes in all); the refusal's text, or empty
+std::string pcm_plan_channels(uint32_t n_clips, const uint32_t* n_frames, const int32_t* formats, const uint32_t* channels, const uint32_t* select,
+                              const uint32_t* source, std::vector<PcmClipDesc>& desc, std::vector<uint64_t>& off);
 // packed (16-byte aligned) + desc[c].offset -> out + c * stride, channel 0 of desc[c].n_frames frames; max_frames: the longest clip's count (sizes the grid)
 void launch_batch_unpack(const void* packed, const PcmClipDesc* desc, uint32_t n_clips, uint32_t max_frames, float* out, uint64_t stride, hipStream_t s);
 

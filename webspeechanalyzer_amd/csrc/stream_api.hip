@@ -81,6 +81,9 @@ struct wsa_stream {
     uint8_t *h_pk = nullptr, *h_pk_dev = nullptr;      // [n][pk_stride] bytes, mapped pinned
     uint32_t pk_stride = 0, max_ch = 1;
     uint32_t* d_chan = nullptr;
+    // spec PK-3 (wsa_stream_set_input_channels): stream i takes channel sel[i] (or the mix) of the packed row of stream src[i]; d_sel = [sel | src]
+    bool chsel = false;
+    uint32_t* d_sel = nullptr;
 };
 
 namespace wsa {
@@ -154,6 +157,25 @@ __global__ __launch_bounds__(128) void stream_pull_packed_kernel(float* __restri
         }
     }
 }
+// spec PK-3 for streams: stream s takes channel sel[s], or the mix, of the packed row of stream srcs[s] — one sample per lane from the sample's own
+// bytes (a step's few hundred samples per stream; the source's row is read once per stream that takes from it).  Counts and control words are the
+// stream's own; the caller guarantees that the source's row holds the stream's count of frames.
+template <int FORMAT>
+__global__ __launch_bounds__(128) void stream_pull_channels_kernel(float* __restrict__ dst, uint32_t dst_stride, const uint8_t* __restrict__ src, uint64_t src_stride,
+                                                                   const uint32_t* __restrict__ chan, const uint32_t* __restrict__ sel, const uint32_t* __restrict__ srcs,
+                                                                   const uint32_t* __restrict__ ctl, uint32_t n, uint32_t count_word, uint32_t fixed_count) {
+    constexpr uint32_t SB = FORMAT == WSA_PCM_I16 ? 2u : 1u;
+    const uint32_t s = blockIdx.x;
+    if (!(ctl[RS_CTL_BITS * n + s] & 4u)) return;
+    const uint32_t cnt = count_word ? ctl[count_word * n + s] : fixed_count;
+    const uint32_t ch = chan[s], pick = sel[s];
+    const uint8_t* row = src + (uint64_t)srcs[s] * src_stride;
+    float* out = dst + (uint64_t)s * dst_stride;
+    for (uint32_t j = blockIdx.y * 128u + threadIdx.x; j < cnt; j += gridDim.y * 128u) {
+        const uint8_t* fr = row + (uint64_t)j * ch * SB;
+        out[j] = pick == WSA_CHANNEL_MIX ? pcm_mix_frame(ch, [&](uint32_t c) { return pcm_decode_bytes(FORMAT, fr + c * SB); }) : pcm_decode_bytes(FORMAT, fr + pick * SB);
+    }
+}
 // step prologue: control words host -> device (mapped pinned memory), counters cleared
 // (level 3: the per (stream, k of this step) table of the segments' track pools starts every step empty, so that an entry the step did not write reads as
 //  "no tracks", not as a previous step's pool offsets — cleared HERE, by a kernel: a memset node inside the captured step did not replay reliably on this ROCm)
@@ -191,6 +213,7 @@ void wsa_stream_destroy(wsa_stream* b) {
     if (b->d_collect) (void)hipFree(b->d_collect);
     if (b->h_pk) (void)hipHostFree(b->h_pk);
     if (b->d_chan) (void)hipFree(b->d_chan);
+    if (b->d_sel) (void)hipFree(b->d_sel);
     wsa_scls_free(b->scls);
     wsa_sens_free(b->sens);
     wsa_sknn_free(b->sknn);
@@ -326,42 +349,67 @@ float* wsa_stream_host_input(wsa_stream* b) { return b ? b->h_pcm : nullptr; }
 void* wsa_stream_host_input_packed(wsa_stream* b) { return b && b->fmt != WSA_PCM_F32 ? b->h_pk : nullptr; }
 uint32_t wsa_stream_input_stride_bytes(const wsa_stream* b) { return !b ? 0 : (b->fmt != WSA_PCM_F32 ? b->pk_stride : b->in_stride * (uint32_t)sizeof(float)); }
 
-wsa_status wsa_stream_set_input_format(wsa_stream* b, int32_t format, const uint32_t* channels) {
-    if (!b) return WSA_ERR_INVALID;
+// wsa_stream_set_input_format (select and source NULL, chsel false: the PK-1 pull kernel) and wsa_stream_set_input_channels (PK-3)
+static wsa_status set_input_impl(wsa_stream* b, int32_t format, const uint32_t* channels, const uint32_t* select, const uint32_t* source, bool chsel) {
     wsa_ctx* ctx = b->ctx;
     if (format != WSA_PCM_F32 && format != WSA_PCM_I16 && format != WSA_PCM_MULAW && format != WSA_PCM_ALAW)
         return fail(ctx, WSA_ERR_INVALID, "unknown input format " + std::to_string(format) + " (WSA_PCM_F32 0, WSA_PCM_I16 1, WSA_PCM_MULAW 2, WSA_PCM_ALAW 3)");
     uint32_t max_ch = 1;
     for (uint32_t i = 0; channels && i < b->n; i++) {
+        if (chsel && source && source[i] != i) continue;          // a consumer takes its source's channel count, its own entry is not read
         if (channels[i] < 1 || channels[i] > 64) return fail(ctx, WSA_ERR_INVALID, "stream " + std::to_string(i) + ": channel count " + std::to_string(channels[i]) + " outside 1 .. 64");
         if (format == WSA_PCM_F32 && channels[i] != 1)
             return fail(ctx, WSA_ERR_INVALID, "stream " + std::to_string(i) + ": " + std::to_string(channels[i]) + " channels with WSA_PCM_F32: float input is mono, interleaved channels need a packed format");
         if (channels[i] > max_ch) max_ch = channels[i];
+    }
+    std::vector<uint32_t> ss(chsel ? 2 * (size_t)b->n : 0, 0u);     // [select | source], a consumer's channel count is its source's
+    std::vector<uint32_t> ch_of(b->n, 1u);
+    for (uint32_t i = 0; chsel && i < b->n; i++) {
+        const uint32_t src = source ? source[i] : i;
+        if (src >= b->n) return fail(ctx, WSA_ERR_INVALID, "stream " + std::to_string(i) + ": source " + std::to_string(src) + " outside 0 .. " + std::to_string(b->n - 1));
+        if ((source ? source[src] : src) != src)
+            return fail(ctx, WSA_ERR_INVALID, "stream " + std::to_string(i) + ": source " + std::to_string(src) + " is not its own source (it reads stream " + std::to_string(source[src]) + ")");
+        ch_of[i] = channels ? channels[src] : 1u;
+        ss[i] = select ? select[i] : 0u; ss[b->n + i] = src;
+        if (!pcm_select_known(ss[i], ch_of[i]))
+            return fail(ctx, WSA_ERR_INVALID, "stream " + std::to_string(i) + ": select " + std::to_string(ss[i]) + " is neither a channel below " + std::to_string(ch_of[i]) + " nor WSA_CHANNEL_MIX");
+        if (format == WSA_PCM_F32 && src != i)
+            return fail(ctx, WSA_ERR_INVALID, "stream " + std::to_string(i) + ": source " + std::to_string(src) + " with WSA_PCM_F32: float input has one row per stream, shared rows need a packed format");
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (b->stepped) HIP_TRY(ctx, hipStreamSynchronize(b->last_stream ? b->last_stream : b->own));     // the last step may still read the buffer
     if (b->gexec) { (void)hipGraphExecDestroy(b->gexec); b->gexec = nullptr; }         // the next step recaptures with the format's pull kernel
     if (b->h_pk) { (void)hipHostFree(b->h_pk); b->h_pk = b->h_pk_dev = nullptr; }
     if (b->d_chan) { (void)hipFree(b->d_chan); b->d_chan = nullptr; }
-    b->fmt = WSA_PCM_F32; b->chan.clear(); b->pk_stride = 0; b->max_ch = 1;
+    if (b->d_sel) { (void)hipFree(b->d_sel); b->d_sel = nullptr; }
+    b->fmt = WSA_PCM_F32; b->chan.clear(); b->pk_stride = 0; b->max_ch = 1; b->chsel = false;
     if (format == WSA_PCM_F32) return WSA_OK;
     std::vector<uint32_t> ch(b->n, 1u);
-    if (channels) ch.assign(channels, channels + b->n);
+    if (chsel) ch = ch_of;
+    else if (channels) ch.assign(channels, channels + b->n);
     const uint64_t row = ((uint64_t)b->in_stride * max_ch * pcm_sample_bytes(format) + 15u) & ~(uint64_t)15u;
     if (row > 0xFFFFFFF0ull) return fail(ctx, WSA_ERR_INVALID, "a packed input row of " + std::to_string(row) + " bytes: fewer channels or frames per step");
-    void *hp = nullptr, *hd = nullptr, *dc = nullptr;
+    void *hp = nullptr, *hd = nullptr, *dc = nullptr, *ds = nullptr;
     bool ok = hipHostMalloc(&hp, (size_t)row * b->n, hipHostMallocMapped) == hipSuccess;
+    if (ok && chsel) ok = hipMalloc(&ds, ss.size() * sizeof(uint32_t)) == hipSuccess && hipMemcpy(ds, ss.data(), ss.size() * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess;
     if (ok) { std::memset(hp, 0, (size_t)row * b->n); ok = hipHostGetDevicePointer(&hd, hp, 0) == hipSuccess; }
     ok = ok && hipMalloc(&dc, (size_t)b->n * sizeof(uint32_t)) == hipSuccess && hipMemcpy(dc, ch.data(), (size_t)b->n * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) {
         const std::string m = std::string("packed input buffer allocation failed: ") + hipGetErrorString(hipGetLastError());
         if (hp) (void)hipHostFree(hp);
         if (dc) (void)hipFree(dc);
+        if (ds) (void)hipFree(ds);
         return fail(ctx, WSA_ERR_HIP, m);
     }
-    b->h_pk = static_cast<uint8_t*>(hp); b->h_pk_dev = static_cast<uint8_t*>(hd); b->d_chan = static_cast<uint32_t*>(dc);
-    b->fmt = format; b->chan = ch; b->pk_stride = (uint32_t)row; b->max_ch = max_ch;
+    b->h_pk = static_cast<uint8_t*>(hp); b->h_pk_dev = static_cast<uint8_t*>(hd); b->d_chan = static_cast<uint32_t*>(dc); b->d_sel = static_cast<uint32_t*>(ds);
+    b->fmt = format; b->chan = ch; b->pk_stride = (uint32_t)row; b->max_ch = max_ch; b->chsel = chsel;
     return WSA_OK;
+}
+wsa_status wsa_stream_set_input_format(wsa_stream* b, int32_t format, const uint32_t* channels) {
+    return b ? set_input_impl(b, format, channels, nullptr, nullptr, false) : WSA_ERR_INVALID;
+}
+wsa_status wsa_stream_set_input_channels(wsa_stream* b, int32_t format, const uint32_t* channels, const uint32_t* select, const uint32_t* source) {
+    return b ? set_input_impl(b, format, channels, select, source, true) : WSA_ERR_INVALID;
 }
 
 wsa_status wsa_stream_enable_graph(wsa_stream* b, int32_t on) {
@@ -389,7 +437,15 @@ static wsa_status enqueue_step(wsa_stream* b, const float* d_pcm, uint64_t strid
         const uint64_t chunks = ((uint64_t)b->in_stride * b->max_ch + per_chunk - 1) / per_chunk;
         const dim3 grid(n, (unsigned)std::min<uint64_t>((chunks + 127) / 128, 1024));
         const uint32_t count_word = b->mixed ? (uint32_t)RS_CTL_NIN : 0u;
-        if (b->fmt == WSA_PCM_I16)
+        if (b->chsel) {                    // PK-3: a lane per frame
+            const dim3 gsel(n, (unsigned)std::min<uint32_t>((b->in_stride + 127u) / 128u, 1024u));
+            if (b->fmt == WSA_PCM_I16)
+                hipLaunchKernelGGL(stream_pull_channels_kernel<WSA_PCM_I16>, gsel, dim3(128), 0, s, b->d_pcm_in, b->in_stride, src, src_stride, b->d_chan, b->d_sel, b->d_sel + n, b->d_ctl, n, count_word, b->step_samples);
+            else if (b->fmt == WSA_PCM_MULAW)
+                hipLaunchKernelGGL(stream_pull_channels_kernel<WSA_PCM_MULAW>, gsel, dim3(128), 0, s, b->d_pcm_in, b->in_stride, src, src_stride, b->d_chan, b->d_sel, b->d_sel + n, b->d_ctl, n, count_word, b->step_samples);
+            else
+                hipLaunchKernelGGL(stream_pull_channels_kernel<WSA_PCM_ALAW>, gsel, dim3(128), 0, s, b->d_pcm_in, b->in_stride, src, src_stride, b->d_chan, b->d_sel, b->d_sel + n, b->d_ctl, n, count_word, b->step_samples);
+        } else if (b->fmt == WSA_PCM_I16)
             hipLaunchKernelGGL(stream_pull_packed_kernel<WSA_PCM_I16>, grid, dim3(128), 0, s, b->d_pcm_in, b->in_stride, src, src_stride, b->d_chan, b->d_ctl, n, count_word, b->step_samples);
         else if (b->fmt == WSA_PCM_MULAW)
             hipLaunchKernelGGL(stream_pull_packed_kernel<WSA_PCM_MULAW>, grid, dim3(128), 0, s, b->d_pcm_in, b->in_stride, src, src_stride, b->d_chan, b->d_ctl, n, count_word, b->step_samples);
@@ -876,6 +932,19 @@ wsa_status wsa_stream_time_steps_packed(wsa_stream* b, uint32_t n_steps, const v
     if (feed && b->fmt == WSA_PCM_F32)
         return fail(b->ctx, WSA_ERR_INVALID, "wsa_stream_time_steps_packed with a packed feed on a set whose input format is WSA_PCM_F32: use wsa_stream_time_steps");
     return time_steps_impl(b, n_steps, feed, (size_t)b->n * b->pk_stride, b->h_pk, feed_steps, stream, out_us, rows_total);
+}
+
+// spec PK-3 on the host: channel `select` of the frames, or their mix
+wsa_status wsa_pcm_decode_select(int32_t format, const void* in, uint64_t n_frames, uint32_t channels, uint32_t select, float* out) {
+    if (channels < 1 || channels > 64 || (n_frames && (!in || !out)) || !pcm_format_known(format) || !pcm_select_known(select, channels)) return WSA_ERR_INVALID;
+    const uint8_t* p = static_cast<const uint8_t*>(in);
+    const uint32_t sb = pcm_sample_bytes(format);
+    const uint64_t step = (uint64_t)channels * sb;
+    for (uint64_t j = 0; j < n_frames; j++) {
+        const uint8_t* fr = p + j * step;
+        out[j] = select == WSA_CHANNEL_MIX ? pcm_mix_frame(channels, [&](uint32_t c) { return pcm_decode_bytes(format, fr + c * sb); }) : pcm_decode_bytes(format, fr + (uint64_t)select * sb);
+    }
+    return WSA_OK;
 }
 
 // specs PK-1 / PK-2 on the host, no device involved: channel 0 of n_frames interleaved frames -> floats

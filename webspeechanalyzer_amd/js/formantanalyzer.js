@@ -36,11 +36,17 @@ const settings = {
                                           // (levels 5 / 13; null = whenever more than one device is configured, true / false = always / never)
   resample_to: 0,                         // ours: analysis rate the audio is converted to first (0 = analyse at its own rate); 48000 = what the
                                           // reference's offline path gets from the browser (OfflineAudioContext at 48 kHz, ref @B18769)
+  channel: 'first',                       // ours: what LaunchBatch / LaunchAudioNodes analyse of an interleaved clip (spec PK-3): 'first' (channel 0), 'mix' (the mono
+                                          // mix, what a one-channel Web Audio context makes of the source), a channel number, or 'each' (every channel an
+                                          // analysis of its own; the clip's bytes travel once)
 };
 
 // ref @B3292: truthy-merge, except the five keys tested with `null !==` (0 / false are honoured,
 // and an absent key overwrites with undefined — the app always passes all keys, src/index.js:370-390)
 function configure(e) {
+  // (our key `channel` is checked before anything is taken over: a refused call changes no setting)
+  if (e.channel !== undefined && e.channel !== null && !(e.channel === 'first' || e.channel === 'mix' || e.channel === 'each' || (Number.isInteger(e.channel) && e.channel >= 0 && e.channel < 64)))
+    throw "channel: 'first', 'mix', 'each' or a channel number 0 .. 63";
   if (null !== e.spec_type) settings.spec_type = e.spec_type;
   if (e.output_level) settings.output_level = e.output_level;
   if (null !== e.f_min) settings.f_min = e.f_min;
@@ -61,6 +67,7 @@ function configure(e) {
   if (e.devices !== undefined) settings.devices = Array.isArray(e.devices) && e.devices.length > 0 ? e.devices.slice() : null;
   if (e.resample_to !== undefined && e.resample_to !== null) settings.resample_to = e.resample_to;
   if (e.gather !== undefined) settings.gather = e.gather === null ? null : !!e.gather;
+  if (e.channel !== undefined && e.channel !== null) settings.channel = e.channel;
   settings.plot_enable = false;            // no canvas under Node
 }
 
@@ -161,13 +168,42 @@ function clip_length(c) {
 // one batch of clips to the addon.  Clips of one kind keep their call (all floats: wsa_batch_run_host, all Int16Array: wsa_batch_run_host_i16); any
 // other mix travels as the bytes the clips hold, every clip with its own format and channel count, and is unpacked on the device
 // (wsa_batch_run_host_packed, spec PK-2): Float32Array clips as 'f32', Int16Array clips as 'i16' — views, nothing is converted or copied here
+// With configure({channel}) other than 'first' the clips are analyses (expand_channels): every one travels as bytes with the channel it takes (or the mix) and
+// the analysis whose bytes it reads — the first of its file in this batch, so a file's bytes travel once (wsa_batch_run_host_channels, spec PK-3)
+const CHANNEL_MIX = 0xFFFFFFFF;
 function submit_clips(nat, ctx, clips, fs, fs_an, defer, extra) {
+  if (clips.some((c) => c.select !== undefined)) {
+    const bytes_of = (a) => new Uint8Array(a.buffer, a.byteOffset, a.byteLength);
+    const first = new Map();                   // file -> the first analysis of it in this batch
+    clips.forEach((c, i) => { if (!first.has(c.origin)) first.set(c.origin, i); });
+    return nat.processBatch(ctx, clips.map((c) => (c.pcm ? bytes_of(c.pcm) : c.pcm16 ? bytes_of(c.pcm16) : c.packed)), fs, settings.output_level, fs_an,
+      Uint32Array.from(clips, (c) => (c.pcm ? 1 : c.channels)), defer, extra[0],
+      Int32Array.from(clips, (c) => (c.pcm ? CLIP_FORMATS.f32[0] : c.pcm16 ? CLIP_FORMATS.i16[0] : CLIP_FORMATS[c.format][0])),
+      Uint32Array.from(clips, (c) => c.select), Uint32Array.from(clips, (c) => first.get(c.origin)));
+  }
   if (clips.every((c) => c.pcm16)) return nat.processBatch(ctx, clips.map((c) => c.pcm16), fs, settings.output_level, fs_an, Uint32Array.from(clips, (c) => c.channels), defer, ...extra);
   if (clips.every((c) => c.pcm)) return nat.processBatch(ctx, clips.map((c) => c.pcm), fs, settings.output_level, fs_an, undefined, defer, ...extra);
   const bytes_of = (a) => new Uint8Array(a.buffer, a.byteOffset, a.byteLength);
   return nat.processBatch(ctx, clips.map((c) => (c.pcm ? bytes_of(c.pcm) : c.pcm16 ? bytes_of(c.pcm16) : c.packed)), fs, settings.output_level, fs_an,
     Uint32Array.from(clips, (c) => (c.pcm ? 1 : c.channels)), defer, extra[0],
     Int32Array.from(clips, (c) => (c.pcm ? CLIP_FORMATS.f32[0] : c.pcm16 ? CLIP_FORMATS.i16[0] : CLIP_FORMATS[c.format][0])));
+}
+
+// configure({channel}): the launch's clips -> its analyses.  'first': the clips as they are (channel 0, the calls of before).  'mix' / a number: one analysis per
+// clip.  'each': a clip of C channels becomes C analyses in channel order, labelled labels[clip].concat('ch' + c).  -> { list, labels }
+function expand_channels(list, labels) {
+  const want = settings.channel;
+  if (want === 'first') return { list, labels };
+  const out = [], lab = [];
+  list.forEach((c, i) => {
+    const ch = c.pcm ? 1 : c.channels;
+    const picks = want === 'each' ? Array.from({ length: ch }, (_, k) => k) : [want === 'mix' ? CHANNEL_MIX : want];
+    for (const k of picks) {
+      out.push(Object.assign({}, c, { select: k, origin: c }));
+      lab.push(want === 'each' ? (labels[i] || []).concat('ch' + k) : (labels[i] || []));
+    }
+  });
+  return { list: out, labels: lab };
 }
 
 // ---- contexts are kept across launches (creating one is cheap, but the planned batch the addon keeps with it is not: GBs of
@@ -862,7 +898,8 @@ function LaunchAudioNodes(context_source, source_obj = null, callback = null, fi
         clip = clip_slice(clip, a, b);
       }
     } catch (e) { reject(typeof e === 'string' ? e : String(e.message || e)); return; }
-    run([clip], callback, () => file_labels, test_play).then(() => resolve(true), (e) => reject(typeof e === 'string' ? e : String(e.message || e)));
+    const ex = expand_channels([clip], [file_labels]);          // ('each': the channels' callbacks one after the other, file_labels.concat('ch' + c))
+    run(ex.list, callback, (c) => ex.labels[c], test_play).then(() => resolve(true), (e) => reject(typeof e === 'string' ? e : String(e.message || e)));
   });
 }
 
@@ -872,6 +909,8 @@ function LaunchBatch(clips, callback = null, labels = [], test_play = false) {
   return new Promise((resolve, reject) => {
     let list;
     try { list = clips.map(to_pcm); } catch (e) { reject(typeof e === 'string' ? e : String(e.message || e)); return; }
+    // configure({channel: 'each'}): the callbacks arrive in (clip, channel) order, clip_index counts the analyses
+    ({ list, labels } = expand_channels(list, labels));
     let current = 0;
     const cb = callback ? (si, label, t, f) => callback(si, label, t, f, current) : null;
     const labels_of = (c) => { current = c; return labels[c] || []; };
@@ -916,6 +955,7 @@ async function run_batches(batches, callback, labels, test_play) {
     const meters = pred ? [] : null;
     const mdbs = pred && pred.models ? [] : null;          // per batch and clip: the clip's min_entropy_db (null: none)
     const vals = vp ? [] : null;                           // per batch and clip: the value heads' {sum, weight, value}
+    if (settings.channel !== 'first') throw "LaunchBatches analyses channel 0: configure({channel: 'first'}), or LaunchBatch for '" + settings.channel + "'";
     const lists = batches.map((b) => b.map(to_pcm));
     const bands = settings.spec_type === 1 ? settings.N_mel_bins : settings.N_fft_bins;
     const start = (k) => {
@@ -997,14 +1037,22 @@ const STREAM_ACTIVE = 1, STREAM_START = 2, STREAM_STOP = 4;
 // on the GPU inside the step.  handle.input is then an Int16Array ('i16') or Uint8Array (G.711) over the packed pinned buffer, handle.inputStride
 // counts elements of that array, stream i's frames of a push are interleaved over channels (a number, or one per stream; 1 .. 64) from
 // input[i * inputStride] on and channel 0 is analysed.  push(ctl, counts) is unchanged: counts are frames of one channel.
+// With select ('mix' or a channel number, one value or one per stream) and / or source (one stream index per stream) stream i analyses that channel, or the
+// mono mix, of the row of stream source[i] (spec PK-3): a stereo call is written once, into its source's row, and feeds a stream per speaker.
 const PCM_FORMATS = { f32: 0, i16: 1, mulaw: 2, alaw: 3 };
 function pcm_format(format) {
   if (!Object.prototype.hasOwnProperty.call(PCM_FORMATS, format)) throw "unknown input format '" + format + "' ('f32', 'i16', 'mulaw', 'alaw')";
   return PCM_FORMATS[format];
 }
-// channel 0 of the interleaved frames in typedArray as the floats the analysis is given (Int16Array for 'i16', Uint8Array for 'mulaw' / 'alaw')
-function decodePcm(format, typedArray, channels = 1) {
-  try { return addon().decodePcm(pcm_format(format), typedArray, channels); } catch (e) { throw (typeof e === 'string' ? e : String(e.message || e)); }
+// channel `select` (0; 'mix': the mono mix, spec PK-3) of the interleaved frames in typedArray as the floats the analysis is given (Int16Array for 'i16',
+// Uint8Array for 'mulaw' / 'alaw')
+function channel_select(select) {
+  if (select === 'mix') return CHANNEL_MIX;
+  if (!(Number.isInteger(select) && select >= 0 && select <= CHANNEL_MIX)) throw "select: a channel number or 'mix'";
+  return select;
+}
+function decodePcm(format, typedArray, channels = 1, select = 0) {
+  try { return addon().decodePcm(pcm_format(format), typedArray, channels, channel_select(select)); } catch (e) { throw (typeof e === 'string' ? e : String(e.message || e)); }
 }
 function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames_per_step = 1, max_span_frames = 1024, input_format = null) {
   const nat = addon();
@@ -1030,7 +1078,16 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
       const chans = input_format.channels;
       const ch = chans === undefined || chans === null ? null : Uint32Array.from(Array.isArray(chans) || ArrayBuffer.isView(chans) ? chans : new Array(n_streams).fill(chans));
       if (ch && ch.length !== n_streams) throw 'channels as an array holds one count per stream (' + ch.length + ' counts, ' + n_streams + ' streams)';
-      nat.streamSetInput(st, pcm_format(input_format.format === undefined ? 'f32' : input_format.format), ch);
+      // select / source (spec PK-3): what each stream takes ('mix' or a channel, one value or one per stream) of which stream's packed row
+      const per = (v, what) => {
+        if (v === undefined || v === null) return null;
+        const a = Array.isArray(v) || ArrayBuffer.isView(v) ? Array.from(v) : new Array(n_streams).fill(v);
+        if (a.length !== n_streams) throw what + ' as an array holds one entry per stream (' + a.length + ' entries, ' + n_streams + ' streams)';
+        return a;
+      };
+      const sel = per(input_format.select, 'select'), src = per(input_format.source, 'source');
+      if (sel || src) nat.streamSetInput(st, pcm_format(input_format.format === undefined ? 'f32' : input_format.format), ch, sel ? Uint32Array.from(sel, channel_select) : null, src ? Uint32Array.from(src) : null);
+      else nat.streamSetInput(st, pcm_format(input_format.format === undefined ? 'f32' : input_format.format), ch);
     }
     if (pred && pred.knn) nat.streamSetKnn(st, knn_store_on(nat, ctx, pred.knn), pred.k);
     else if (pred && pred.models) nat.streamSetEnsemble(st, model_on(nat, ctx));

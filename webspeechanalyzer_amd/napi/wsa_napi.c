@@ -20,11 +20,15 @@
  *   streamInput(stream) -> Float32Array over the pinned [nStreams][inputStride] input buffer (no copy; inputStride = samplesPerStep on a plain set)
  *   streamSetInput(stream, format, channels) before the first streamInput: wsa_stream_set_input_format; streamInput then gives an Int16Array / Uint8Array
  *     over the packed pinned buffer, [nStreams][streamInfo().inputStrideBytes / element size]
- *   decodePcm(format, typedArray, channels) -> Float32Array   (wsa_pcm_decode: channel 0 of interleaved frames, spec PK-1)
+ *   streamSetInput(stream, format, channels, select, source): wsa_stream_set_input_channels (spec PK-3: stream i takes channel select[i], 0xFFFFFFFF the mix,
+ *     of the packed row of stream source[i])
+ *   decodePcm(format, typedArray, channels[, select]) -> Float32Array   (wsa_pcm_decode_select: channel `select` of interleaved frames or their mix, specs PK-1 / PK-3)
  *   streamStep(stream, ctl: Uint8Array | null[, counts: Uint32Array | null]) -> {meta, feat, segments}   (wsa_stream_step_host[_n] + wsa_stream_collect;
  *       one hipGraph launch, well under a millisecond, so it runs on the calling thread; counts: samples per stream in this step, else paced)
  *   processBatch(..., model, formats)           (9th argument an Int32Array of WSA_PCM_* numbers: the clips are Uint8Arrays over the bytes a file holds, any
  *                                               mix of encodings, clip i interleaved over channels[i] channels: wsa_batch_run_host_packed, spec PK-2)
+ *   processBatch(..., model, formats, select, source)   (10th / 11th argument Uint32Arrays: clip i takes channel select[i] or the mix of the bytes of clip
+ *                                               source[i], which travel once: wsa_batch_run_host_channels, spec PK-3)
  *   processBatch(..., [models])                 (8th argument an array of models: wsa_batch_classify_ensemble; the result gains `ens`)
  *   streamSetEnsemble(stream, [models] | null)  (wsa_stream_set_ensemble: streamStep results gain `ens`)
  *   streamSetRegress(stream, [models] | null, outMin: Float64Array, outMax: Float64Array)   (wsa_stream_set_regress: streamStep results gain regValue [H][rows], regCb, regCbValue / regCbWeight
@@ -278,6 +282,7 @@ typedef struct {
     double *fs_each;                             /* one rate per clip (a Float64Array in place of fs): wsa_batch_create_mixed, fs is 0 */
     uint32_t n_clips; uint32_t *n_samples; const float **pcm; napi_ref *clip_refs;
     int is_i16; uint32_t *channels;   /* Int16Array clips (pcm[] then holds int16 pointers): wsa_batch_run_host_i16 */
+    uint32_t *select, *source;        /* 10th / 11th argument (with formats): clip i takes channel select[i] (0xFFFFFFFF: the mix) of the bytes of clip source[i]: wsa_batch_run_host_channels, spec PK-3 */
     int32_t *formats;                 /* 9th argument: one WSA_PCM_* number per clip, the clips Uint8Arrays of the files' bytes (pcm[] holds byte pointers): wsa_batch_run_host_packed */
     wsa_batch *plan; int plan_reused; /* taken from / returned to the box on the JS thread */
     /* results */
@@ -353,7 +358,8 @@ static void job_execute(napi_env env, void *data) {
         j->plan = b;
     }
     do {
-        j->st = j->formats ? wsa_batch_run_host_packed(b, (const void *const *)j->pcm, j->formats, j->channels, j->queue)
+        j->st = j->select ? wsa_batch_run_host_channels(b, (const void *const *)j->pcm, j->formats, j->channels, j->select, j->source, j->queue)
+              : j->formats ? wsa_batch_run_host_packed(b, (const void *const *)j->pcm, j->formats, j->channels, j->queue)
               : j->is_i16 ? wsa_batch_run_host_i16(b, (const int16_t *const *)j->pcm, j->channels, j->queue) : wsa_batch_run_host(b, j->pcm, j->queue);
         if (j->st != WSA_OK) break;
         wsa_device_result r;
@@ -543,11 +549,11 @@ static void job_complete(napi_env env, napi_status status, void *data) {
     ens_host_free(&j->eh);
     free(j->prob); free(j->cb); free(j->cb_label); free(j->cb_conf); free(j->clip_conf);
     free(j->meta); free(j->feat); free(j->segs); free(j->row_off); free(j->seg_off); free(j->formants); free(j->frame_off); free(j->utt_meta); free(j->utt_feat); free(j->utt_off); free(j->trk_off); free(j->trk_pts); free(j->trk_rank);
-    free(j->n_samples); free(j->fs_each); free((void *)j->pcm); free(j->clip_refs); free(j->channels); free(j->formats); free(j);
+    free(j->n_samples); free(j->fs_each); free((void *)j->pcm); free(j->clip_refs); free(j->channels); free(j->formats); free(j->select); free(j);
 }
 
 static napi_value fn_process_batch(napi_env env, napi_callback_info info) {
-    size_t argc = 9; napi_value argv[9];
+    size_t argc = 11; napi_value argv[11];
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     wsa_ctx *ctx = argc ? get_ctx(env, argv[0]) : NULL;
     bool is_arr = false; double fs = 0; uint32_t n = 0;
@@ -619,6 +625,23 @@ static napi_value fn_process_batch(napi_env env, napi_callback_info info) {
             memcpy(j->formats, fd, sizeof(int32_t) * n);
         }
     }
+    /* ... and with a 10th and an 11th (Uint32Arrays, one word per clip): what each clip takes of which clip's bytes (spec PK-3).  A consumer's entry of
+     * the clip array is its source's Uint8Array (its length gives the frames; the library does not read a consumer's pointer) */
+    if (argc >= 11 && j->formats) {
+        napi_typedarray_type st, ut; void *sd = NULL, *ud = NULL; bool sta = false, uta = false; size_t sl = 0, ul = 0; napi_valuetype vt = napi_undefined;
+        napi_typeof(env, argv[9], &vt);
+        if (vt != napi_undefined && vt != napi_null) {
+            if (napi_is_typedarray(env, argv[9], &sta) != napi_ok || !sta || napi_get_typedarray_info(env, argv[9], &st, &sl, &sd, NULL, NULL) != napi_ok || st != napi_uint32_array || sl != n
+                || napi_is_typedarray(env, argv[10], &uta) != napi_ok || !uta || napi_get_typedarray_info(env, argv[10], &ut, &ul, &ud, NULL, NULL) != napi_ok || ut != napi_uint32_array || ul != n) {
+                free(j->n_samples); free(j->fs_each); free((void *)j->pcm); free(j->clip_refs); free(j->channels); free(j->formats); free(j);
+                napi_throw_type_error(env, NULL, "processBatch: select and source are Uint32Arrays with one word per clip"); return NULL;
+            }
+            j->select = malloc(sizeof(uint32_t) * 2 * (n ? n : 1));
+            if (!j->select) { free(j->n_samples); free(j->fs_each); free((void *)j->pcm); free(j->clip_refs); free(j->channels); free(j->formats); free(j); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+            j->source = j->select + (n ? n : 1);
+            memcpy(j->select, sd, sizeof(uint32_t) * n); memcpy(j->source, ud, sizeof(uint32_t) * n);
+        }
+    }
     for (uint32_t i = 0; i < n; i++) {
         napi_value el; napi_typedarray_type tt; size_t len; void *data; bool is_ta = false;
         const char *bad = NULL;
@@ -642,7 +665,7 @@ static napi_value fn_process_batch(napi_env env, napi_callback_info info) {
         else if (i > 0 && (tt == napi_int16_array) != (j->is_i16 != 0)) bad = "the clips of one batch must be of one kind";
         if (bad) {
             for (uint32_t k = 0; k < i; k++) napi_delete_reference(env, j->clip_refs[k]);
-            free(j->n_samples); free(j->fs_each); free((void *)j->pcm); free(j->clip_refs); free(j->channels); free(j->formats); free(j);
+            free(j->n_samples); free(j->fs_each); free((void *)j->pcm); free(j->clip_refs); free(j->channels); free(j->formats); free(j->select); free(j);
             napi_throw_type_error(env, NULL, bad); return NULL;
         }
         if (i == 0) { j->is_i16 = tt == napi_int16_array; if (j->is_i16) j->channels = calloc(n, sizeof(uint32_t)); }
@@ -813,9 +836,10 @@ static napi_value fn_stream_info(napi_env env, napi_callback_info info) {
     napi_create_uint32(env, wsa_stream_input_stride_bytes(h->st), &v); napi_set_named_property(env, o, "inputStrideBytes", v);
     return o;
 }
-/* streamSetInput(stream, format 0 .. 3, channels: Uint32Array(nStreams) | null): wsa_stream_set_input_format, before the first streamInput */
+/* streamSetInput(stream, format 0 .. 3, channels: Uint32Array(nStreams) | null[, select, source: Uint32Array(nStreams) | null]): wsa_stream_set_input_format, or with
+ * a select or a source wsa_stream_set_input_channels (spec PK-3); before the first streamInput */
 static napi_value fn_stream_set_input(napi_env env, napi_callback_info info) {
-    size_t argc = 3; napi_value argv[3]; int32_t fmt = 0;
+    size_t argc = 5; napi_value argv[5]; int32_t fmt = 0;
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     stream_t *h = argc ? get_stream(env, argv[0]) : NULL;
     if (!h || !h->st || argc < 2 || napi_get_value_int32(env, argv[1], &fmt) != napi_ok) { napi_throw_type_error(env, NULL, "streamSetInput(stream, format, channels)"); return NULL; }
@@ -830,13 +854,25 @@ static napi_value fn_stream_set_input(napi_env env, napi_callback_info info) {
             chan = (const uint32_t *)data;
         }
     }
-    if (wsa_stream_set_input_format(h->st, fmt, chan) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(h->ctx)); return NULL; }
+    const uint32_t *ss[2] = {NULL, NULL};
+    for (size_t a = 3; a < argc && a < 5; a++) {
+        bool is_ta = false; napi_typedarray_type tt; size_t len; void *data;
+        if (napi_is_typedarray(env, argv[a], &is_ta) == napi_ok && is_ta) {
+            if (napi_get_typedarray_info(env, argv[a], &tt, &len, &data, NULL, NULL) != napi_ok || tt != napi_uint32_array || len != h->n) {
+                napi_throw_type_error(env, NULL, "select and source must be Uint32Arrays with one word per stream"); return NULL;
+            }
+            ss[a - 3] = (const uint32_t *)data;
+        }
+    }
+    const wsa_status sst = (ss[0] || ss[1]) ? wsa_stream_set_input_channels(h->st, fmt, chan, ss[0], ss[1]) : wsa_stream_set_input_format(h->st, fmt, chan);
+    if (sst != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(h->ctx)); return NULL; }
     h->fmt = fmt;
     return NULL;
 }
-/* decodePcm(format, typedArray, channels) -> Float32Array: wsa_pcm_decode, channel 0 of the interleaved frames (spec PK-1, no device) */
+/* decodePcm(format, typedArray, channels[, select]) -> Float32Array: wsa_pcm_decode_select, channel `select` (0; 0xFFFFFFFF: the mix) of the interleaved frames
+ * (specs PK-1 / PK-3, no device) */
 static napi_value fn_decode_pcm(napi_env env, napi_callback_info info) {
-    size_t argc = 3; napi_value argv[3]; int32_t fmt = 0; uint32_t ch = 1;
+    size_t argc = 4; napi_value argv[4]; int32_t fmt = 0; uint32_t ch = 1, sel = 0;
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     bool is_ta = false; napi_typedarray_type tt = napi_int8_array; size_t len = 0; void *data = NULL;
     if (argc < 2 || napi_get_value_int32(env, argv[0], &fmt) != napi_ok || napi_is_typedarray(env, argv[1], &is_ta) != napi_ok || !is_ta
@@ -848,10 +884,13 @@ static napi_value fn_decode_pcm(napi_env env, napi_callback_info info) {
     if (fmt < WSA_PCM_F32 || fmt > WSA_PCM_ALAW) { napi_throw_error(env, NULL, "decodePcm: unknown input format"); return NULL; }
     if (tt != want) { napi_throw_type_error(env, NULL, "decodePcm: f32 takes a Float32Array, i16 an Int16Array, mulaw / alaw a Uint8Array"); return NULL; }
     if (ch < 1 || ch > 64) { napi_throw_error(env, NULL, "decodePcm: channel count outside 1 .. 64"); return NULL; }
-    const size_t frames = len ? (len - 1) / ch + 1 : 0;
+    if (argc > 3) napi_get_value_uint32(env, argv[3], &sel);
+    if (sel >= ch && sel != WSA_CHANNEL_MIX) { napi_throw_error(env, NULL, "decodePcm: select is neither a channel below the channel count nor the mix"); return NULL; }
+    const size_t last = sel == WSA_CHANNEL_MIX ? ch - 1u : sel;           /* the last channel of a frame that is read */
+    const size_t frames = len > last ? (len - 1 - last) / ch + 1 : 0;
     napi_value ab, ta; void *out = NULL;
     NAPI_OK(env, napi_create_arraybuffer(env, frames * sizeof(float), &out, &ab));
-    if (wsa_pcm_decode(fmt, data, frames, ch, (float *)out) != WSA_OK) { napi_throw_error(env, NULL, "decodePcm: refused"); return NULL; }
+    if (wsa_pcm_decode_select(fmt, data, frames, ch, sel, (float *)out) != WSA_OK) { napi_throw_error(env, NULL, "decodePcm: refused"); return NULL; }
     NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, frames, ab, 0, &ta));
     return ta;
 }
