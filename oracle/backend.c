@@ -140,6 +140,10 @@ struct wsa_or_seg {
     VEC(double) trace;
     /* what the gate decided (test access, wsa_or_gate_*): per frame the accumulate_fm call, the span bookkeeping of csrc/gate.hip, the arm counters */
     VEC(wsa_or_gate_frame) gframes;
+    /* the tracker's table as csrc/tracker_one.hpp holds it between frames (test access, wsa_or_track_frames): entries left by the last accumulate_fm call
+     * (tracks not yet 4 filing indices old then, the frame's new ones included), the smallest last_frame among them, whether a stale filing index is set */
+    int32_t tbl_n, tbl_min_lf, tbl_stale;
+    VEC(int32_t) tframes;
     int32_t span_begin, reset0_in_frame, voiced_now;
     int64_t arms[ARM_COUNT];
     int64_t tarms[TARM_COUNT];
@@ -155,6 +159,7 @@ static void clear_fm(wsa_or_seg *s) {
     for (int32_t i = 0; i < s->tracks.n; i++) track_free(&s->tracks.p[i]);
     s->tracks.n = 0; s->accS = 0; s->accC = 0;
     s->max_peaks = 0; s->max_live = 0;
+    s->tbl_n = 0; s->tbl_min_lf = 0; s->tbl_stale = 0;
 }
 
 /* L(e) reset_segment @B25649 */
@@ -187,7 +192,7 @@ void wsa_or_seg_free(wsa_or_seg *s) {
     if (!s) return;
     clear_fm(s); VFREE(s->tracks);
     for (int32_t i = 0; i < s->segs.n; i++) { free(s->segs.p[i].fr); free(s->segs.p[i].sm); free(s->segs.p[i].trk); }
-    VFREE(s->segs); VFREE(s->syls); VFREE(s->trace); VFREE(s->gframes);
+    VFREE(s->segs); VFREE(s->syls); VFREE(s->trace); VFREE(s->gframes); VFREE(s->tframes);
     free(s);
 }
 
@@ -305,8 +310,9 @@ static void accumulate_fm(wsa_or_seg *S, const uint32_t *e, const peak_t *pk, in
     }
     free(asg); free(best);
     /* the load the device tracker's tables see: peaks handed in, and tracks not yet 4 filing indices old once the frame's new ones are in */
-    int32_t live = 0;
-    for (int32_t r = 0; r < S->tracks.n; r++) if (n - S->tracks.p[r].last_frame < 4) live++;
+    int32_t live = 0, min_lf = 0;
+    for (int32_t r = 0; r < S->tracks.n; r++) if (n - S->tracks.p[r].last_frame < 4) { if (!live || S->tracks.p[r].last_frame < min_lf) min_lf = (int32_t)S->tracks.p[r].last_frame; live++; }
+    S->tbl_n = live; S->tbl_min_lf = min_lf;
     if (U > S->max_peaks) S->max_peaks = U;
     if (live > S->max_live) S->max_live = live;
 }
@@ -709,7 +715,7 @@ void wsa_or_seg_push(wsa_or_seg *S, const uint32_t *e) {
         if (n > 0 && p > 7 && p < S->max_voiced_bin && n > 4 && r > 4) { reset_segment(S, 0); S->span_begin = (int32_t)S->cur_frame - 1; }
         else S->no_fm++;
     }
-    int32_t do_reset = 0;
+    int32_t do_reset = 0, gate_reset = 0;
     if (S->c_started >= 0) {                                                   /* @B26646 */
         const int unv = n == 0 || p < 7 || p >= S->max_voiced_bin || (n > 3 && d / (g - d) < .1);
         if (n == 0) ARM(S, voiced_n0);
@@ -739,11 +745,12 @@ void wsa_or_seg_push(wsa_or_seg *S, const uint32_t *e) {
                 if (S->breaker == trunc(S->breaker)) ARM(S, pause_int); else ARM(S, pause_frac);
                 finalize(S, S->c_ci + 1); do_reset = 1;
             }
-            else if (S->cfg.auto_noise_gate) { noise_gate(S, h); if (S->reset0_in_frame) S->span_begin = (int32_t)S->cur_frame; }
+            else if (S->cfg.auto_noise_gate) { noise_gate(S, h); if (S->reset0_in_frame) { S->span_begin = (int32_t)S->cur_frame; gate_reset = 1; } }
         } else {
-            if (S->cfg.auto_noise_gate) { const int32_t before = S->reset0_in_frame; noise_gate(S, h); if (S->reset0_in_frame && !before) S->span_begin = (int32_t)S->cur_frame - 1; }
+            if (S->cfg.auto_noise_gate) { const int32_t before = S->reset0_in_frame; noise_gate(S, h); if (S->reset0_in_frame && !before) { S->span_begin = (int32_t)S->cur_frame - 1; gate_reset = 1; } }
             rec.called = 1; rec.stale = S->reset0_in_frame; rec.fl = S->floor_;
             accumulate_fm(S, e, pk, n, t, g, S->floor_);
+            if (rec.stale) S->tbl_stale = 1;
             if (S->c_started < 2) S->c_started++; else S->no_fm = 0;
         }
     }
@@ -757,6 +764,7 @@ void wsa_or_seg_push(wsa_or_seg *S, const uint32_t *e) {
     S->c_ci++;
     /* the reference resets in the Promise .then microtask, i.e. after the frame completes (quirk 8) */
     if (do_reset) { reset_segment(S, -1); S->span_begin = (int32_t)S->cur_frame; }
+    { const int32_t row[5] = {S->tbl_n, S->tbl_min_lf, S->tbl_stale, S->tracks.n, gate_reset}; for (int k = 0; k < 5; k++) VPUSH(S->tframes, row[k]); }
     free(pk);
 }
 
@@ -794,6 +802,7 @@ int64_t wsa_or_gate_arm_count(const wsa_or_seg *s, int32_t i) { return i >= 0 &&
 int32_t wsa_or_track_n_arms(void) { return TARM_COUNT; }
 const char *wsa_or_track_arm_name(int32_t i) { return i >= 0 && i < TARM_COUNT ? tarm_names[i] : NULL; }
 int64_t wsa_or_track_arm_count(const wsa_or_seg *s, int32_t i) { return i >= 0 && i < TARM_COUNT ? s->tarms[i] : -1; }
+const int32_t *wsa_or_track_frames(const wsa_or_seg *s) { return s->tframes.p; }
 
 int32_t wsa_or_peak_n_arms(void) { return PARM_COUNT; }
 const char *wsa_or_peak_arm_name(int32_t i) { return i >= 0 && i < PARM_COUNT ? parm_names[i] : NULL; }

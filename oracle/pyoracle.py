@@ -74,6 +74,8 @@ def lib():
     L.wsa_or_track_arm_name.argtypes = [i32]
     L.wsa_or_track_arm_count.restype = ctypes.c_int64
     L.wsa_or_track_arm_count.argtypes = [vp, i32]
+    L.wsa_or_track_frames.restype = ctypes.POINTER(ctypes.c_int32)
+    L.wsa_or_track_frames.argtypes = [vp]
     L.wsa_or_peak_n_arms.restype = i32
     L.wsa_or_peak_arm_name.restype = ctypes.c_char_p
     L.wsa_or_peak_arm_name.argtypes = [i32]
@@ -255,7 +257,7 @@ def run_backend(spectra, cfg, trace=False, gate=False, cuts=(), track=False):
     segment (wsa_or_segment_load: what the device tracker's table limits are compared with).
     gate: also out["gate"], what the gate decided and which arms it took (_gate_report).  cuts: frames f after which (once frame f is pushed)
     wsa_or_seg_cut is called, as csrc/gate.hip's stream kernel cuts a span at its ring.  track: also out["track"]["arms"], which arms of accumulate_fm and
-    finalize the clip took (wsa_oracle.h wsa_or_track_arm_*)."""
+    finalize the clip took (wsa_oracle.h wsa_or_track_arm_*), and out["track"]["frames"], the tracker's table behind every frame (wsa_or_track_frames)."""
     L = lib()
     spectra = np.ascontiguousarray(spectra, dtype=np.uint32)
     frames, bands = spectra.shape
@@ -321,6 +323,8 @@ def run_backend(spectra, cfg, trace=False, gate=False, cuts=(), track=False):
             out["gate"] = _gate_report(L, h)
         if track:
             out["track"] = dict(arms={L.wsa_or_track_arm_name(i).decode(): int(L.wsa_or_track_arm_count(h, i)) for i in range(L.wsa_or_track_n_arms())})
+            nf = L.wsa_or_gate_n_frames(h)                  # per frame [table entries, smallest last_frame among them, stale index set, tracks held, reset by the automatic gate]
+            out["track"]["frames"] = np.ctypeslib.as_array(L.wsa_or_track_frames(h), shape=(nf, 5)).copy() if nf else np.zeros((0, 5), np.int32)
         if trace:
             n = L.wsa_or_trace_len(h)
             out["trace"] = np.ctypeslib.as_array(L.wsa_or_trace(h), shape=(n, 10)).copy() if n else np.zeros((0, 10))

@@ -2050,7 +2050,30 @@ def debug_stream_spectra(streams, bands):
     return out
 
 
-COMPACT_FUSED, COMPACT_SCAN, COMPACT_COUNT_SCAN = 0, 1, 2      # compact_path of csrc/tracker.hip: what launch_compact ran
+def debug_stream_step_backend(streams, n_frames, ctl, frames, stream=0, bands=None):
+    """Test access (csrc/debug.hip wsa_debug_stream_step_backend; not part of include/wsa.h): one step of a plain stream set past the front end.  frames
+    [n_streams, frames_per_step, bands] u32 (stream i's first n_frames[i] frames count), n_frames [n] u32 (0 .. frames_per_step), ctl [n] u8
+    (ACTIVE / START / STOP); the product's own launches from the peak scan down follow, uncaptured; collect() afterwards as behind any step.  A set is
+    stepped through this entry only, or never through it.  bands: the band count handed down (default: frames' last axis); None arguments go down as
+    null pointers (the refusals)."""
+    L = lib()
+    vp, u32 = ctypes.c_void_p, ctypes.c_uint32
+    L.wsa_debug_stream_step_backend.argtypes = [vp, vp, vp, vp, u32, vp]
+    L.wsa_debug_stream_step_backend.restype = ctypes.c_int
+    nfr = None if n_frames is None else np.ascontiguousarray(n_frames, dtype=np.uint32)
+    cb = None if ctl is None else np.ascontiguousarray(ctl, dtype=np.uint8)
+    fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.uint32)
+    if fr is not None and bands is None:
+        if fr.shape[:2] != (streams.n, streams.frame_capacity):
+            raise WsaError(f"frames of shape {fr.shape}: [n_streams, frames_per_step, bands] = [{streams.n}, {streams.frame_capacity}, bands] wanted")
+        bands = fr.shape[2]
+    if (nfr is not None and nfr.shape != (streams.n,)) or (cb is not None and cb.shape != (streams.n,)):
+        raise WsaError("n_frames and ctl hold one entry per stream")
+    ptr = lambda a: None if a is None else a.ctypes.data
+    streams.an._check(L.wsa_debug_stream_step_backend(streams.h, ptr(nfr), ptr(cb), ptr(fr), int(bands or 0), stream))
+
+
+COMPACT_FUSED, COMPACT_SCAN, COMPACT_COUNT_SCAN = 0, 1, 2     # compact_path of csrc/tracker.hip: what launch_compact ran
 CARRY_HIST = 32
 CARRY_WORDS = 2 + 2 * CARRY_HIST
 SPAN_BUCKETS = 2048

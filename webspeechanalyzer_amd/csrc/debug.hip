@@ -222,6 +222,16 @@ extern "C" int wsa_debug_stream_spectra(wsa_stream* st, uint32_t* out, uint64_t 
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, d, words * 4, hipMemcpyDeviceToHost) != hipSuccess) return WSA_ERR_HIP;
     return WSA_OK;
 }
+// One stream step past the front end (stream_api.hip wsa_stream_step_backend_internal): stream i of a plain set gets the first n_frames[i] <= frames_per_step
+// frames of its block of frames [n_streams][frames_per_step][bands] (u32, on the host) under the control byte ctl[i] (WSA_STREAM_ACTIVE / START / STOP); the
+// control words are written as wsa_stream_step writes them and the product's own launches follow, uncaptured: the step's prologue, launch_stream_prepare,
+// then the step's back-end half from the peak scan to the epilogue.  wsa_stream_collect afterwards, as behind any step.  Refused with the stream named: a
+// mixed-rate set, a count above frames_per_step, a band count other than the set's, a null pointer.  The step counter and what the next step waits for
+// move as in wsa_stream_step, but the input half's carried samples do not: an object is stepped through this entry only, or never through it.
+extern "C" int wsa_debug_stream_step_backend(wsa_stream* st, const uint32_t* n_frames, const uint8_t* ctl, const uint32_t* frames, uint32_t bands, void* stream) {
+    if (!st) return WSA_ERR_INVALID;
+    return wsa_stream_step_backend_internal(st, n_frames, ctl, frames, bands, stream);
+}
 
 // RG-1 (csrc/regress_fold.hpp) on its own: hand-built row meta [n_rows][8] i32 (slot 0 the clip or stream, 1 si, 3 len) and H value columns
 // values [H][n_rows] f64 straight into the batch fold or the stream-step fold; no audio, no model.

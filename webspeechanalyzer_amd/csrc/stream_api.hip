@@ -419,9 +419,9 @@ wsa_status wsa_stream_enable_graph(wsa_stream* b, int32_t on) {
     return WSA_OK;
 }
 
-// everything one step puts on the stream (this is what the graph holds)
-static wsa_status enqueue_step(wsa_stream* b, const float* d_pcm, uint64_t stride, bool host_in, hipStream_t s) {
-    wsa_ctx* ctx = b->ctx;
+// One step in two halves, enqueued one after the other (this is what the graph holds).
+// The input half: prologue, the step's samples (pull / stage / K0s) and the front end; it leaves the step's u32 frames in d_spec.
+static void enqueue_input(wsa_stream* b, const float* d_pcm, uint64_t stride, bool host_in, hipStream_t s) {
     const Derived& D = b->D;
     const BackEnd& B = b->be;
     const FePlanHost& P = b->fe.plan;
@@ -475,6 +475,16 @@ static wsa_status enqueue_step(wsa_stream* b, const float* d_pcm, uint64_t strid
     p.pcm = d_pcm; p.clip_stride = stride; p.n_frames = d_nfr; p.frame_off = b->d_frame_off; p.spec = b->d_spec; p.pcm_off = d_off;
     p.frames_per_wave = (int)((b->F + 3) / 4); if (p.frames_per_wave > 25) p.frames_per_wave = 25;
     launch_frontend(p, (int)n, (int)b->F, P.R, P.three, s);
+}
+// The back-end half, from the u32 frames in d_spec and the control words in d_ctl: peak scan, gate, tracker, compaction, the level's and the attached
+// models' kernels, epilogue.  (wsa_debug_stream_step_backend enqueues this half behind hand-built frames.)
+static wsa_status enqueue_backend(wsa_stream* b, hipStream_t s) {
+    wsa_ctx* ctx = b->ctx;
+    const Derived& D = b->D;
+    const BackEnd& B = b->be;
+    const FePlanHost& P = b->fe.plan;
+    const uint32_t n = b->n;
+    const uint32_t *d_nfr = b->d_ctl, *d_bits = b->d_ctl + 2 * n;
     PkParams pk;
     pk.spec = b->d_spec; pk.rec = B.rec; pk.total_frames = n * b->F; pk.bands = P.bands;
     pk.stream_state = b->d_state; pk.n_frames = d_nfr; pk.step_frames = b->F; pk.ring = b->ring; pk.flags = B.d_counters + 1; pk.lanes_only = b->tune.peaks_lanes ? 1 : 0; pk.round_bins = b->tune.peaks_w;
@@ -526,6 +536,53 @@ static wsa_status enqueue_step(wsa_stream* b, const float* d_pcm, uint64_t strid
     hipLaunchKernelGGL(stream_push_kernel, dim3(16), dim3(256), 0, s, b->be.d_totals, b->be.d_counters, b->be.d_meta, b->be.d_feat, b->be.d_seg,
                        b->h_totals_dev, b->h_meta_dev, b->h_feat_dev, b->h_seg_dev, b->d2h_rows, b->d2h_segs, b->d_state, b->n);
     HIP_TRY(ctx, hipGetLastError());
+    return WSA_OK;
+}
+static wsa_status enqueue_step(wsa_stream* b, const float* d_pcm, uint64_t stride, bool host_in, hipStream_t s) {
+    enqueue_input(b, d_pcm, stride, host_in, s);
+    return enqueue_backend(b, s);
+}
+
+// Test entry behind wsa_debug_stream_step_backend (debug.hip; not part of wsa.h): one step of a plain set whose u32 frames come from the caller instead of
+// the front end.  Stream i gets n_frames[i] <= frames_per_step frames (frames [n][frames_per_step][bands] on the host, the first n_frames[i] of its block)
+// under the control byte ctl[i].  The control words are written as step_impl writes them (nfr as given, off 0, the same bits; no warm-up frames are
+// skipped), then the product's own launches run without capture: the prologue, launch_stream_prepare and the back-end half of the step.
+// wsa_stream_collect works as after any step.  The step counter, `stepped` and `last_stream` move as in step_impl, but nothing here feeds the input
+// half's carried samples: an object steps EITHER through this entry OR through wsa_stream_step*, never both.
+wsa_status wsa_stream_step_backend_internal(wsa_stream* b, const uint32_t* n_frames, const uint8_t* ctl, const uint32_t* frames, uint32_t bands, void* stream) {
+    wsa_ctx* ctx = b->ctx;
+    const uint32_t n = b->n, F = b->F, own_bands = (uint32_t)b->fe.plan.bands;
+    if (b->mixed) return fail(ctx, WSA_ERR_INVALID, "wsa_debug_stream_step_backend: a mixed-rate stream set has no step of whole frames (streams 0 .. " + std::to_string(n - 1) + " convert their input)");
+    if (!n_frames || !ctl || !frames) return fail(ctx, WSA_ERR_INVALID, std::string("wsa_debug_stream_step_backend: null ") + (!n_frames ? "frame counts" : !ctl ? "control bytes" : "frames") + " for streams 0 .. " + std::to_string(n - 1));
+    if (bands != own_bands) return fail(ctx, WSA_ERR_INVALID, "wsa_debug_stream_step_backend: frames of " + std::to_string(bands) + " bands, streams 0 .. " + std::to_string(n - 1) + " analyse " + std::to_string(own_bands));
+    for (uint32_t i = 0; i < n; i++)
+        if (n_frames[i] > F) return fail(ctx, WSA_ERR_INVALID, "wsa_debug_stream_step_backend: stream " + std::to_string(i) + ": " + std::to_string(n_frames[i]) + " frames in one step, frames_per_step is " + std::to_string(F));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (!s) {
+        HIP_TRY(ctx, hipEventRecord(b->ev_in, nullptr));
+        s = b->own;
+        HIP_TRY(ctx, hipStreamWaitEvent(s, b->ev_in, 0));
+    }
+    if (b->stepped) HIP_TRY(ctx, hipStreamSynchronize(b->last_stream ? b->last_stream : s));      // the previous step still reads the pinned control words
+    b->last_stream = s;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t cb = ctl[i];
+        uint32_t bits = 0;
+        if (cb & WSA_STREAM_START) bits |= 1u;
+        if (cb & WSA_STREAM_ACTIVE) bits |= 4u;
+        if (cb & WSA_STREAM_STOP) bits |= 2u;
+        b->h_ctl[i] = (cb & WSA_STREAM_ACTIVE) ? n_frames[i] : 0u; b->h_ctl[n + i] = 0; b->h_ctl[2 * n + i] = bits;
+    }
+    // (the copy is ordered behind the previous step by the synchronize above, the launches below behind the copy by the stream)
+    HIP_TRY(ctx, hipMemcpyAsync(b->d_spec, frames, (size_t)n * F * own_bands * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    const uint32_t cw = b->ctl_words * n;
+    hipLaunchKernelGGL(stream_begin_kernel, dim3((cw + 255) / 256), dim3(256), 0, s, b->d_ctl, b->h_ctl_dev, cw, b->be.d_counters, b->be.d_totals,
+                       b->be.d_trk_seg, b->be.d_trk_seg ? (uint32_t)((size_t)n * b->be.seg_cap * 4) : 0u);
+    launch_stream_prepare(b->d_state, b->d_carry, b->d_tr_state, b->d_ctl + 2 * n, n, b->D.ctx_max0, b->D.floor0, s);
+    const wsa_status st = enqueue_backend(b, s);
+    if (st != WSA_OK) return st;
+    b->steps++; b->stepped = true;
     return WSA_OK;
 }
 
