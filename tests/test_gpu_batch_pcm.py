@@ -244,6 +244,13 @@ def test_device_resident_packed_clips_inside_a_captured_graph(torch, mix_clips):
     plain.close(); b.close(); an.close()
 
 
+def _workspace_bytes(an, b):
+    """the device bytes the batch's arena has handed out so far (wsa_batch_info.workspace_bytes, read again)"""
+    info = capi._BatchInfo()
+    an._check(an.L.wsa_batch_get_info(b.h, ctypes.byref(info)))
+    return info.workspace_bytes
+
+
 def test_refusals_name_the_clip(torch):
     import webspeechanalyzer_amd as wsa
     an = wsa.Analyzer(wsa.Config(output_level=5))
@@ -260,12 +267,15 @@ def test_refusals_name_the_clip(torch):
         with pytest.raises(wsa.WsaError, match=r"clip 0: channel count %d outside 1 \.\. 64" % bad):
             b.set_input_format("mulaw", [bad, 1, 1])
     assert list(b.packed_offsets()) == [0, 0, 0, 0]                 # nothing was planned by a refused call
+    assert _workspace_bytes(an, b) == b.info["workspace_bytes"]     # ... and nothing allocated: the plan refuses before the staging buffer and the tables
     with pytest.raises(wsa.WsaError, match="before wsa_batch_set_input_format"):
         b.run_packed(16, _s(torch))
     with pytest.raises(wsa.WsaError, match="takes int32"):
         b.run_host_packed([np.zeros(1600, np.float32)] * 3, "i32", None, _s(torch))
     with pytest.raises(wsa.WsaError, match="clip 1: 100 elements"):
         b.run_host_packed([np.zeros(1600, np.uint8), np.zeros(100, np.uint8), np.zeros(1600, np.uint8)], "u8", None, _s(torch))
+    b.set_input_format("u8", None)                                  # an accepted plan allocates the staging buffer and its table
+    assert _workspace_bytes(an, b) > b.info["workspace_bytes"] and list(b.packed_offsets()) == [0, 1600, 3200, 4800]
     # streams keep their four formats
     st = an.streams(2, 16000)
     for name in ("u8", "i24", "i32", "f64"):

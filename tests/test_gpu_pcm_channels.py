@@ -2,6 +2,8 @@
 counts 2, 3, 6 and 64, rows that do not start on 16 bytes, poisoned bytes behind every source; whole batches whose clips take a channel or
 the mix of shared sources against the same Analyzer fed the host-decoded mono floats through run_host (spectra and rows, bit for bit: plain,
 resampled, mixed-rate at level 13, run_packed inside a captured graph); stream sets whose streams share packed rows against the float set."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -300,6 +302,9 @@ def test_refusals_name_the_clip_or_stream(torch):
         with pytest.raises(wsa.WsaError, match=r"clip 0: channel count 65 outside 1 \.\. 64"):
             call("i16", [65, 2, 2], None, None)
     assert list(b.packed_offsets()) == [0, 0, 0, 0]                 # nothing was planned by a refused call
+    info = capi._BatchInfo()
+    an._check(an.L.wsa_batch_get_info(b.h, ctypes.byref(info)))
+    assert info.workspace_bytes == b.info["workspace_bytes"]        # ... and nothing allocated: the plan refuses before the staging buffer and the tables
     with pytest.raises(wsa.WsaError, match="before wsa_batch_set_input_format"):
         b.run_packed(16, _s(torch))
     st = an.streams(3, 16000)

@@ -312,6 +312,64 @@ def test_rows_unchanged_and_swapping_model_and_ensemble_recaptures(torch):
     _close(an, ens, members)
 
 
+def test_a_refused_attach_changes_nothing(torch):
+    """A wsa_stream_set_* call that is refused (the object belongs to another context) leaves what was attached attached and detaches nothing:
+    with the graph on, a run that suffers refused set_model / set_ensemble calls between its steps gives in every step the tables of the
+    undisturbed run — once with a model attached, once with an ensemble."""
+    import webspeechanalyzer_amd as wsa
+    from webspeechanalyzer_amd.synth import synth_clips
+    fs = 16000
+    pcm = synth_clips(2, 14400, fs=fs, seed=31, device="cuda")          # 0.9 s, voiced to the end: STOP closes a segment with rows
+    an, other = wsa.Analyzer(wsa.Config(output_level=13)), wsa.Analyzer(wsa.Config(output_level=13))
+    members = _members(an, [1, 2])
+    ens = an.ensemble(members)
+    ms_other = _members(other, [2])
+    e_other = other.ensemble(ms_other)
+
+    def run(kind, disturb):
+        st = an.streams(2, fs, frames_per_step=4)
+        st.enable_graph(True)
+        (st.set_model if kind == "model" else st.set_ensemble)(members[0] if kind == "model" else ens)
+        sps = st.samples_per_step
+        buf = torch.zeros((2, sps), device="cuda", dtype=torch.float32)
+        out, nsteps = [], pcm.shape[1] // sps
+        for k in range(nsteps):
+            if disturb and k in (0, 2, nsteps - 1):                     # before the first step, behind a captured one, before the STOP
+                with pytest.raises(wsa.WsaError, match="another context"):
+                    st.set_ensemble(e_other)
+                with pytest.raises(wsa.WsaError, match="another context"):
+                    st.set_model(ms_other[0])
+            ctl = np.full(2, wsa.ACTIVE | (wsa.START if k == 0 else 0) | (wsa.STOP if k == nsteps - 1 else 0), np.uint8)
+            buf.copy_(pcm[:, k * sps:(k + 1) * sps])
+            st.step(buf.data_ptr(), buf.stride(0), ctl, _stream(torch))
+            r = st.collect(_stream(torch))
+            with pytest.raises(wsa.WsaError, match="no ensemble" if kind == "model" else "no classifier"):
+                st.ensemble_classes() if kind == "model" else st.classes()       # the other kind was not attached by the refused call
+            out.append((r, st.classes() if kind == "model" else st.ensemble_classes()))
+        st.close()
+        return out
+
+    for kind in ("model", "ensemble"):
+        want, got = run(kind, False), run(kind, True)
+        rows = sum(len(r["meta"]) for r, _ in want)
+        print(kind, "steps", len(want), "rows", rows)
+        assert rows > 0 and len(got) == len(want)
+        for (rw, cw), (rg, cg) in zip(want, got):
+            for key in ("meta", "feat", "segments"):
+                assert np.array_equal(rw[key], rg[key], equal_nan=True), (kind, key)
+            if kind == "model":
+                for key in ("prob", "cb", "cb_label", "cb_conf", "stream_conf"):
+                    assert np.array_equal(cw[key], cg[key]), (kind, key)
+            else:
+                for key in ("prob",) + PER_MEMBER + ("stream_conf",):
+                    for d in range(2):
+                        assert np.array_equal(cw[key][d], cg[key][d]), (kind, key, d)
+                for key in ("cb",) + SHARED + ("stream_min_db",):
+                    assert np.array_equal(cw[key], cg[key], equal_nan=True), (kind, key)
+    _close(other, e_other, ms_other)
+    _close(an, ens, members)
+
+
 def test_level5_probabilities_only(torch):
     import webspeechanalyzer_amd as wsa
     from webspeechanalyzer_amd.synth import synth_clips

@@ -392,6 +392,14 @@ def test_refusals_name_the_fault(wsa):
         an._check(L.wsa_stream_time_steps_packed(st.h, 1, feed16.ctypes.data, 1, _stream(), out.ctypes.data, rows.ctypes.data))
     st.set_input_format("i16", [1, 2, 1])
     assert st.input_stride_bytes == (sps * 2 * 2 + 15) // 16 * 16 and st.host_input_packed().shape == (3, st.input_stride_bytes // 2)
+    view = st.host_input_packed()
+    view[:] = 7
+    for refused in (lambda: st.set_input_format("i16", [1, 65, 1]), lambda: an._check(L.wsa_stream_set_input_format(st.h, 99, None))):
+        with pytest.raises(wsa.WsaError):
+            refused()                                           # validation comes first: a refused call frees nothing and keeps the format
+        again = st.host_input_packed()
+        assert again.ctypes.data == view.ctypes.data and again.shape == view.shape and (again == 7).all()
+    view[:] = 0
     with pytest.raises(wsa.WsaError, match="wsa_stream_step takes floats, this set's input format is i16"):
         st.step(fdev.data_ptr(), fdev.stride(0))
     with pytest.raises(wsa.WsaError, match="wsa_stream_step_n takes floats, this set's input format is i16"):

@@ -1,5 +1,5 @@
-// api_internal.hpp — what api.hip (batches) and stream_api.hip (streams) share: the context object and
-// the error plumbing of the C ABI.
+// api_internal.hpp — what the sources behind include/wsa.h share (api.hip: context and host helpers, batch_*.hip: batches, stream_*.hip:
+// streams): the context object and the error plumbing of the C ABI.
 #pragma once
 #include <string>
 #include "wsa_internal.hpp"
@@ -17,9 +17,13 @@ inline wsa_status fail(wsa_ctx* c, wsa_status st, const std::string& msg) {
     if (c) c->err = msg; else g_create_error = msg;
     return st;
 }
+#pragma GCC visibility push(hidden)
+// api.hip: the page-locked slab of wsa_host_alloc that p lies in, if any (batch_input.hip merges uploads only inside one)
+bool slab_of(const void* p, uintptr_t* base, size_t* size);
+#pragma GCC visibility pop
 }  // namespace wsa_api
 
-// classify_batch.hip (K6 / K6b) reads a batch's compacted rows and keeps its own per-batch state; api.hip owns the batch object
+// classify_batch.hip (K6 / K6b) reads a batch's compacted rows and keeps its own per-batch state; batch_internal.hpp has the batch object
 struct wsa_cls;                                 // classification buffers of one batch (allocated by the first wsa_batch_classify)
 void wsa_cls_free(wsa_cls* c);                  // (wsa_batch_destroy)
 struct wsa_ecls;                                // ensemble tables of one batch (allocated by the first wsa_batch_classify_ensemble with an ensemble)
@@ -38,6 +42,7 @@ struct wsa_batch_view {
 };
 extern "C" {
 void wsa_batch_view_internal(wsa_batch* b, wsa_batch_view* v);
+// fetch_totals: synchronise, read the counters (reruns the back end on a table overflow)
 wsa_status wsa_batch_fetch_internal(wsa_batch* b, hipStream_t s);
 // debug.hip (wsa_debug_batch_tiers): keep >= 0 sets whether the batch's runs leave their device counters standing (1) instead of having the fused
 // compaction clear them for the next run (0, the default); returns the batch's 16 device counters
@@ -48,9 +53,9 @@ const uint32_t* wsa_stream_spec_internal(wsa_stream* b, wsa_ctx** ctx, uint32_t*
 wsa_status wsa_stream_step_backend_internal(wsa_stream* b, const uint32_t* n_frames, const uint8_t* ctl, const uint32_t* frames, uint32_t bands, void* stream);
 void wsa_model_info_internal(const wsa_model* m, wsa_ctx** ctx, int* n_classes, int* softmax);   // classify.hip, for dbstats.hip (K8)
 int wsa_model_inputs_internal(const wsa_model* m);                                               // units[0]
-}              // fetch_totals: synchronise, read the counters (reruns the back end on a table overflow)
+}
 
-// classify_stream.hip runs K6 / K6b inside a stream object's step (wsa_stream_set_model); stream_api.hip owns the stream object
+// classify_stream.hip runs K6 / K6b inside a stream object's step (wsa_stream_set_model); stream_internal.hpp has the stream object
 struct wsa_scls;                                // classification state of one stream object: class tables, carried fold, pinned D2H tables
 struct wsa_scls_view {
     wsa_ctx* ctx; int level; uint32_t n_streams, rows_cap, d2h_rows;

@@ -1,6 +1,6 @@
 // classify_stream.hip — the classifier inside a stream object's step (wsa_stream_set_model / wsa_stream_set_ensemble): K6 (or K6e) on
 // every step's rows, and at level 13 the app's per-callback fold K6b (classify_fold.hpp) carried from step to step on the device, with
-// the step's tables pushed to mapped pinned memory.  stream_api.hip owns the stream object and captures these launches into its step.
+// the step's tables pushed to mapped pinned memory.  stream_step.hip captures these launches into the stream object's step.
 #include <cstring>
 #include <string>
 #include <vector>

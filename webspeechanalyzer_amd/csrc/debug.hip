@@ -222,7 +222,7 @@ extern "C" int wsa_debug_stream_spectra(wsa_stream* st, uint32_t* out, uint64_t 
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, d, words * 4, hipMemcpyDeviceToHost) != hipSuccess) return WSA_ERR_HIP;
     return WSA_OK;
 }
-// One stream step past the front end (stream_api.hip wsa_stream_step_backend_internal): stream i of a plain set gets the first n_frames[i] <= frames_per_step
+// One stream step past the front end (stream_step.hip wsa_stream_step_backend_internal): stream i of a plain set gets the first n_frames[i] <= frames_per_step
 // frames of its block of frames [n_streams][frames_per_step][bands] (u32, on the host) under the control byte ctl[i] (WSA_STREAM_ACTIVE / START / STOP); the
 // control words are written as wsa_stream_step writes them and the product's own launches follow, uncaptured: the step's prologue, launch_stream_prepare,
 // then the step's back-end half from the peak scan to the epilogue.  wsa_stream_collect afterwards, as behind any step.  Refused with the stream named: a
@@ -429,7 +429,7 @@ extern "C" int wsa_debug_utterance(int32_t device, const int32_t* segments, uint
 // syllable: stream c's ring is rows frame_off[c] .. + ring).  formants [frame_off[n_clips]][9] f32, sums [frame_off[n_clips]] f32, frame_off [n_clips + 1],
 // row_meta [n_rows][8] i32 (slot 0 the clip, 6 the syllable's first frame, 7 its length), one launch_coeffs over rows_cap >= n_rows rows.
 // out [rows_cap][WSA_NFEAT] f64: every slot starts as `sentinel`, slot 23 of the first n_rows rows as 0 (what the level-10 row leaves there).
-// total_frames is the drivers': all frames of a batch (api.hip), n x 2 x ring for streams (stream_api.hip; here n x scratch_stride).
+// total_frames is the drivers': all frames of a batch (batch_run.hip), n x 2 x ring for streams (stream_step.hip; here n x scratch_stride).
 // Refused, nothing run: whatever would make the kernel read or write outside these tables.
 extern "C" int wsa_debug_coeffs(int32_t device, const float* formants, const float* sums, const uint32_t* frame_off, uint32_t n_clips,
                                 const int32_t* row_meta, uint32_t n_rows, uint32_t rows_cap, uint32_t ring_mask, uint32_t scratch_stride,

@@ -73,7 +73,7 @@ struct DeviceGuard {
 #define NCCL_TRY(ctx, call) do { ncclResult_t r_ = (call); if (r_ != ncclSuccess) \
         return fail((ctx), WSA_ERR_HIP, std::string(#call) + ": " + g_rccl.GetErrorString(r_)); } while (0)
 
-// the context a planned batch belongs to (api.hip)
+// the context a planned batch belongs to (batch_run.hip)
 extern "C" wsa_ctx* wsa_batch_ctx_internal(const wsa_batch* b);
 
 extern "C" {

@@ -1,4 +1,4 @@
-// host_plan.hpp — what the two host-side drivers of the kernel chain (api.hip: batches, stream_api.hip: lock-step stream sets) plan in the
+// host_plan.hpp — what the two host-side drivers of the kernel chain (batch_*.hip: batches, stream_*.hip: lock-step stream sets) plan in the
 // same way: device memory ownership, the front end's device tables, the rules that come from the reference's configuration, the back end's
 // buffers with the common part of every kernel parameter block, the level-3 raw-track gather and the rate check.  Nothing here is exported.
 #pragma once

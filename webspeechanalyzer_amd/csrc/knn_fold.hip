@@ -1,7 +1,7 @@
 // knn_fold.hip — specification KN-2: the app's per-callback fold K6b (classify_fold.hpp) fed KNN confidences, for a batch
 // (wsa_batch_knn_fold, one accumulator per clip) and inside a stream object's step (wsa_stream_set_knn: K9s on every step's rows, then the
 // fold carried from step to step on the device, with the step's tables pushed to mapped pinned memory).  knn.hip owns the store and the
-// K9 / K9s kernels; stream_api.hip owns the stream object and captures these launches into its step.
+// K9 / K9s kernels; stream_step.hip captures these launches into the stream object's step.
 //
 // The fold sees, per row, the C pairs (class index, votes / k_eff as the f64 K9's epilogue writes).  The legend is the class indices
 // themselves, so every label is an array-index key: Object.keys order is class order (key_rank[c] = c).

@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void batch_deinterleave_kernel(const uint8_t* 
 
 }  // namespace
 
-// PK-3's plan, shared by the batch entries (api.hip) and wsa_debug_batch_deinterleave: checks select and source, gives a consumer its source's format,
+// PK-3's plan, shared by the batch entries (batch_input.hip) and wsa_debug_batch_deinterleave: checks select and source, gives a consumer its source's format,
 // channel count and offset, lays the sources' bytes out in clip order at multiples of 16 and threads every source's list.  Empty string: fine.
 std::string pcm_plan_channels(uint32_t n_clips, const uint32_t* n_frames, const int32_t* formats, const uint32_t* channels, const uint32_t* select,
                               const uint32_t* source, std::vector<PcmClipDesc>& desc, std::vector<uint64_t>& off) {

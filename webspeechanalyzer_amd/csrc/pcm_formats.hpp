@@ -126,7 +126,7 @@ __host__ __device__ inline uint32_t pcm_tile_frames(int32_t format, uint32_t cha
     const uint32_t t = (PCM_TILE_BYTES / fb) & ~15u;
     return t > PCM_TILE_MAX_FRAMES ? PCM_TILE_MAX_FRAMES : t;
 }
-// PK-3: every source's tiles once through LDS, one float row per clip that reads it.  desc as plan_channels (api.hip) builds it.
+// PK-3: every source's tiles once through LDS, one float row per clip that reads it.  desc as plan_channels (batch_input.hip) builds it.
 void launch_batch_deinterleave(const void* packed, const PcmClipDesc* desc, uint32_t n_clips, uint32_t max_frames, float* out, uint64_t stride, hipStream_t s);
 // PK-3's plan (pcm_channels.hip): desc [n_clips], off [n_clips + 1] (off[i]: where clip i's source starts, off[n_clips]: bytes in all); the refusal's text, or empty
 std::string pcm_plan_channels(uint32_t n_clips, const uint32_t* n_frames, const int32_t* formats, const uint32_t* channels, const uint32_t* select,

@@ -2,7 +2,7 @@
 // (the app's ords_<label> models for V, A and D) through ONE grouped K6 launch (classify.hip's classify_group_kernel with the regression
 // epilogue), and the fold RG-1 (regress_fold.hpp) behind it: on a batch one wave per clip and a compaction (wsa_batch_regress_group),
 // inside a stream object's step one wave per stream with the running sums carried on the device (wsa_stream_set_regress).
-// classify.hip owns the models and K6; api.hip and stream_api.hip own the batch and the stream object and capture these launches.
+// classify.hip owns the models and K6; batch_run.hip and stream_step.hip run the batch and the stream object's step and capture these launches.
 #include <atomic>
 #include <cstring>
 #include <string>
