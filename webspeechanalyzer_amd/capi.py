@@ -1929,6 +1929,56 @@ def debug_class_fold(meta, row_off, step_s, legends, conf, single=False, f64=Fal
     return out
 
 
+class _DebugClassifyIO(ctypes.Structure):
+    """struct wsa_debug_classify_io of csrc/debug.hip"""
+    _vp, _u32, _i32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32
+    _fields_ = [("models", _vp), ("n_models", _u32), ("feat", _vp), ("feat_rows", _u32), ("stride", _u32), ("nan_slot", _i32),
+                ("n_rows", _u32), ("rows_cap", _u32), ("n_dev", _i32), ("rb", _i32), ("one_block", _i32), ("regress", _i32),
+                ("out_min", ctypes.c_double), ("out_max", ctypes.c_double), ("out", _vp * 8), ("out_rows", _u32)]
+
+
+DEBUG_CLASSIFY_SEED_F32, DEBUG_CLASSIFY_SEED_F64 = 0xffc0beef, 0xfff8beef0000beef      # NaNs no kernel writes: K6's own NaN is the positive quiet one
+
+
+def debug_classify(models, feat, n_rows=None, n_dev=None, rows_cap=None, rb=0, one_block=False, nan_slot=-1, out_range=None, out_rows=None):
+    """Test access to K6 / K6e through the product's own launches (csrc/debug.hip wsa_debug_classify; not part of include/wsa.h): one Model, or a
+    list of 2 .. 8 as a group, over host rows feat [rows, stride] f64 (stride >= the models' inputs; nan_slot as level 12's `threw` mark).
+    n_dev: the row count on the device (n_rows: the launch's own, one model only; default every row of feat); rows_cap sizes the grid (default the
+    count, at least 1); rb 0 / 1 / 2 / 4 overrides the row-block factor; one_block runs a group's members with one row block each;
+    out_range (out_min, out_max): the regression epilogue.  Every output table has out_rows rows (default the count + 3), starts as the seed
+    pattern and comes back whole: a uint32 view [out_rows, C] per model, or uint64 [out_rows] for a regression; a list for a group."""
+    L = lib()
+    L.wsa_debug_classify.argtypes = [ctypes.c_void_p]
+    L.wsa_debug_classify.restype = ctypes.c_int
+    group = isinstance(models, (list, tuple))
+    ms = list(models) if group else [models]
+    feat = np.ascontiguousarray(feat, np.float64)
+    assert feat.ndim == 2
+    count = int(n_dev) if n_dev is not None else (int(n_rows) if n_rows is not None else len(feat))
+    cap = int(rows_cap) if rows_cap is not None else max(count, 1)
+    R = int(out_rows) if out_rows is not None else count + 3
+    if len(feat) == 0:
+        feat = np.zeros((1, feat.shape[1]), np.float64)
+    io = _DebugClassifyIO()
+    handles = (ctypes.c_void_p * len(ms))(*[m.h for m in ms])
+    io.models, io.n_models = ctypes.cast(handles, ctypes.c_void_p), len(ms)
+    io.feat, io.feat_rows, io.stride, io.nan_slot = feat.ctypes.data, feat.shape[0], feat.shape[1], int(nan_slot)
+    io.n_rows, io.rows_cap, io.n_dev, io.rb, io.one_block = count, cap, -1 if n_dev is None else int(n_dev), int(rb), int(bool(one_block))
+    io.regress = int(out_range is not None)
+    io.out_min, io.out_max = (float(out_range[0]), float(out_range[1])) if out_range is not None else (0.0, 0.0)
+    if out_range is not None:
+        outs = [np.full(R, DEBUG_CLASSIFY_SEED_F64, np.uint64) for _ in ms]
+    else:
+        outs = [np.full((R, m.n_classes), DEBUG_CLASSIFY_SEED_F32, np.uint32) for m in ms]
+    for d, o in enumerate(outs[:8]):
+        io.out[d] = o.ctypes.data
+    io.out_rows = R
+    rc = L.wsa_debug_classify(ctypes.addressof(io))
+    if rc != 0:
+        raise WsaError(f"wsa_debug_classify: status {rc}")
+    return outs if group else outs[0]
+
+
 def debug_knn_split(store, d_feat, n_rows, k, slices, d_label, d_conf, d_nbr, d_sim, stream=0):
     """Test access to K9s on its own (csrc/knn.hip wsa_debug_knn_split; not part of include/wsa.h): the split-store kernels over n_rows dense
     device rows with a forced slice count (0: the rule's), outputs as KnnStore.classify_rows.  Only enqueues (its scratch table stays with
