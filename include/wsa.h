@@ -1094,6 +1094,70 @@ wsa_status wsa_stream_set_input_channels(wsa_stream *st, int32_t format, const u
                                          const uint32_t *source);
 uint32_t   wsa_pcm_channels_tile_frames(int32_t format, uint32_t channels);
 
+/*
+ * ---- A feature DB that stays on the device (additions within version 5: probe for wsa_featdb_create).
+ * Stands in for what the reference APPLICATION keeps between its steps: every callback's rows go into a feature DB (ref src/index.js:35-100
+ * call_backed -> StoreFeatures, js/featuredb.js), and training (src/neuralmodel.js:163-403), prediction (:410-535), the results table
+ * (src/localstore.js:498-627) and the KNN learner (src/neuralmodel.js:731-837) all read that DB.  Specification FD-1 of DESIGN.md §3,
+ * kernels K10 (csrc/featdb.hip).  A wsa_featdb holds the FEATURE columns of such a DB on the context's device, ONE allocation of
+ * capacity_rows x width doubles made at create; rows are appended behind the ones it holds and never move.  Strings (file names, part
+ * tags, times, labels) stay on the host, which learns from `kept` which source row each stored row came from.
+ * One set of buffers: pass the SAME stream to every call on it.  A DB belongs to the context it was created on; destroy it before that
+ * context.  Trainers, DB statistics and KNN stores made from a DB hold no reference to it.
+ */
+typedef struct wsa_featdb wsa_featdb;
+/* width: 53, 264 or 23 (wsa_level_feature_count), anything else is refused; capacity_rows at least 1 */
+wsa_status wsa_featdb_create(wsa_ctx *ctx, int32_t width, uint32_t capacity_rows, wsa_featdb **out);
+void       wsa_featdb_destroy(wsa_featdb *db);
+wsa_status wsa_featdb_clear(wsa_featdb *db);                       /* the count returns to 0; nothing is freed */
+wsa_status wsa_featdb_count(const wsa_featdb *db, uint32_t *n_rows);
+/* The rows of the batch's last run that the app's storing keeps, appended in source order, columns copied bit for bit:
+ *   levels 5 and 13 (width 53): every row;
+ *   level 12 (width 23): row r of the row table unless a row r' <= r of the same callback (meta[0], meta[1]) has a slot 23 that is not
+ *            equal to 0 (NaN counts as marked): a syllable on which uncmin threw ends its callback's list; columns 0 .. 22 are stored;
+ *   level 11 (width 264): of the utterance rows the last one of every clip that has any, row d_clip_utt_off[c + 1] - 1.
+ * *first_row = the DB row of the first appended one, *n_added their number (either may be NULL); kept (host int32 [kept_cap], or NULL)
+ * receives, per appended row, its source row (level 11: utterance row) index.  SYNCHRONISES `stream` for the run's counters (as
+ * wsa_batch_result does, with its rerun rule) and, at levels 11 and 12, once more for the number of kept rows; at levels 5 and 13 the copy
+ * is only enqueued behind that.
+ * WSA_ERR_INVALID with a message: a level that does not go with the width (naming both), a batch of another context, a batch without
+ * a run, kept_cap below the rows to add.  A run with WSA_FLAG_CAPACITY set is refused with WSA_ERR_CAPACITY and the message of
+ * wsa_batch_result.  WSA_ERR_CAPACITY naming the DB's count, the rows to add and the capacity when they do not fit.  A refused call
+ * leaves the DB unchanged in every byte. */
+wsa_status wsa_featdb_append_batch(wsa_featdb *db, wsa_batch *batch, void *stream, uint32_t *first_row, uint32_t *n_added,
+                                   int32_t *kept, uint32_t kept_cap);
+/* n dense host rows [n][width] (an imported data_<db>.json); WSA_ERR_CAPACITY as above.  Returns when the rows are on the device. */
+wsa_status wsa_featdb_append_host(wsa_featdb *db, const double *feat, uint32_t n, void *stream);
+/* the DB's rows on the device, dense [count][width] f64; the pointer is valid until wsa_featdb_destroy */
+wsa_status wsa_featdb_device_rows(const wsa_featdb *db, const double **d_feat);
+/* rows first .. first + n - 1 to host memory out [n][width]; synchronises `stream` */
+wsa_status wsa_featdb_copy_rows(wsa_featdb *db, void *stream, uint32_t first, uint32_t n, double *out);
+/* d_out [n][width] (device) = DB rows rows[0 .. n-1] (host uint32, duplicates allowed).  Every index is checked against the count before
+ * anything is enqueued (the message names the entry); the list is staged through pinned memory.  Only enqueues. */
+wsa_status wsa_featdb_gather(wsa_featdb *db, const uint32_t *rows, uint32_t n, double *d_out, void *stream);
+/* Per column the minimum and the maximum over the selected rows (rows == NULL: rows 0 .. n - 1; duplicates allowed; n at least 1) into
+ * host in_min / in_max [width].  A column that holds a NaN among the selected rows gives NaN for both; otherwise the exact minimum and
+ * maximum with -0 below +0.  Both are exact selections on the bit patterns, so the result does not depend on the grid; there are no
+ * floating-point atomics.  Synchronises `stream`. */
+wsa_status wsa_featdb_ranges(wsa_featdb *db, const uint32_t *rows, uint32_t n, void *stream, double *in_min, double *in_max);
+/* sizes of K10 in rows (tests place their edge cases by these): the keep / scan kernel ballots rows_per_wave_tile source rows per wave and
+ * walks the source rows_per_workgroup at a time; the copy kernel takes rows_per_pass appended rows per pass of its grid */
+wsa_status wsa_featdb_tile_info(int32_t *rows_per_wave_tile, int32_t *rows_per_workgroup, int32_t *rows_per_pass);
+/* wsa_trainer_create / wsa_regress_trainer_create with feat = DB rows rows[0 .. n_rows - 1] in that order (host uint32 [n_rows],
+ * duplicates allowed): the trainer is in every bit the one the host entry makes from the host copy of those rows (one kernel normalises
+ * row rows[i] into the trainer's x[i] with the same expression).  Refuses what those refuse, and a DB of another context, a DB whose
+ * width is not units[0], a row index outside the DB (naming the entry).  Waits for the device before it reads the DB; the trainer keeps
+ * no reference to the DB. */
+wsa_status wsa_trainer_create_db(wsa_ctx *ctx, const wsa_model_desc *init, const wsa_featdb *db, const uint32_t *rows, const int32_t *label,
+                                 uint32_t n_rows, uint32_t n_val, uint32_t batch_size, double learning_rate, wsa_trainer **out);
+wsa_status wsa_regress_trainer_create_db(wsa_ctx *ctx, const wsa_model_desc *init, const wsa_featdb *db, const uint32_t *rows,
+                                         const double *target, uint32_t n_rows, uint32_t n_val, uint32_t batch_size,
+                                         double learning_rate, double out_min, double out_max, wsa_trainer **out);
+/* wsa_wide_dbstats_create over DB rows first_row .. first_row + n_rows - 1, copied device to device (n_feat = the DB's width);
+ * waits for the device before it reads the DB */
+wsa_status wsa_featdb_dbstats_create(wsa_ctx *ctx, const wsa_featdb *db, uint32_t first_row, uint32_t n_rows, const double *duration,
+                                 uint32_t n_cat, const uint32_t *vocab, uint32_t n_ord, wsa_dbstats **out);
+
 #ifdef __cplusplus
 }
 #endif

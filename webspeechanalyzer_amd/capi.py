@@ -221,7 +221,11 @@ ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destr
                "wsa_batch_run_host_packed", "wsa_batch_set_input_format", "wsa_batch_packed_offset", "wsa_batch_run_packed",
                # additions within version 5 (probe for wsa_batch_set_input_channels): any channel, every channel or the mono mix of interleaved PCM (spec PK-3)
                "wsa_pcm_decode_select", "wsa_batch_set_input_channels", "wsa_batch_run_host_channels", "wsa_stream_set_input_channels",
-               "wsa_pcm_channels_tile_frames"]
+               "wsa_pcm_channels_tile_frames",
+               # additions within version 5 (probe for wsa_featdb_create): the feature DB that stays on the device (K10, spec FD-1)
+               "wsa_featdb_create", "wsa_featdb_destroy", "wsa_featdb_clear", "wsa_featdb_count", "wsa_featdb_append_batch", "wsa_featdb_append_host",
+               "wsa_featdb_device_rows", "wsa_featdb_copy_rows", "wsa_featdb_gather", "wsa_featdb_ranges", "wsa_featdb_tile_info",
+               "wsa_trainer_create_db", "wsa_regress_trainer_create_db", "wsa_featdb_dbstats_create"]
 CHANNEL_MIX = 0xFFFFFFFF                                # WSA_CHANNEL_MIX: the `select` word that takes the mono mix (spec PK-3); 'mix' in the Python entries
 PCM_F32, PCM_I16, PCM_MULAW, PCM_ALAW = 0, 1, 2, 3      # WSA_PCM_* of include/wsa.h
 PCM_U8, PCM_I24, PCM_I32, PCM_F64 = 8, 9, 10, 11        # ... the file encodings of spec PK-2 (batches and pcm_decode; 4 .. 7 are unassigned)
@@ -414,13 +418,27 @@ def lib():
     L.wsa_batch_run_host_channels.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.wsa_stream_set_input_channels.argtypes = [vp, i32, vp, vp, vp]
     L.wsa_pcm_channels_tile_frames.argtypes = [i32, u32]
+    L.wsa_featdb_create.argtypes = [vp, i32, u32, ctypes.POINTER(vp)]
+    L.wsa_featdb_destroy.argtypes = [vp]
+    L.wsa_featdb_clear.argtypes = [vp]
+    L.wsa_featdb_count.argtypes = [vp, ctypes.POINTER(u32)]
+    L.wsa_featdb_append_batch.argtypes = [vp, vp, vp, ctypes.POINTER(u32), ctypes.POINTER(u32), vp, u32]
+    L.wsa_featdb_append_host.argtypes = [vp, vp, u32, vp]
+    L.wsa_featdb_device_rows.argtypes = [vp, ctypes.POINTER(vp)]
+    L.wsa_featdb_copy_rows.argtypes = [vp, vp, u32, u32, vp]
+    L.wsa_featdb_gather.argtypes = [vp, vp, u32, vp, vp]
+    L.wsa_featdb_ranges.argtypes = [vp, vp, u32, vp, vp, vp]
+    L.wsa_featdb_tile_info.argtypes = [ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.wsa_trainer_create_db.argtypes = [vp, ctypes.POINTER(_ModelDesc), vp, vp, vp, u32, u32, u32, dbl, ctypes.POINTER(vp)]
+    L.wsa_regress_trainer_create_db.argtypes = [vp, ctypes.POINTER(_ModelDesc), vp, vp, vp, u32, u32, u32, dbl, dbl, dbl, ctypes.POINTER(vp)]
+    L.wsa_featdb_dbstats_create.argtypes = [vp, vp, u32, u32, vp, u32, vp, u32, ctypes.POINTER(vp)]
     for name in ABI_SYMBOLS:
         if name in _U32_RESULT or name in ("wsa_resample_ready", "wsa_level_feature_count", "wsa_batch_packed_offset", "wsa_pcm_channels_tile_frames"):
             continue
         if name not in ("wsa_abi_version", "wsa_last_error", "wsa_config_default", "wsa_destroy", "wsa_batch_destroy", "wsa_resample_length",
                         "wsa_stream_destroy", "wsa_stream_samples_per_step", "wsa_stream_host_input", "wsa_stream_host_input_packed", "wsa_gather_destroy", "wsa_host_free",
                         "wsa_model_destroy", "wsa_ensemble_destroy", "wsa_trainer_destroy", "wsa_dbstats_destroy", "wsa_knn_destroy",
-                        "wsa_regress_group_destroy", "wsa_train_group_destroy"):
+                        "wsa_regress_group_destroy", "wsa_train_group_destroy", "wsa_featdb_destroy"):
             getattr(L, name).restype = ctypes.c_int
     _LIB = L
     return L
@@ -598,9 +616,14 @@ class Analyzer:
         stage for all of them (see TrainGroup; webspeechanalyzer_amd.train.train_many drives it)."""
         return TrainGroup(self, trainers)
 
-    def feature_db(self, features, durations, vocab_sizes=(), n_ord=0):
+    def feature_db(self, features, durations, vocab_sizes=(), n_ord=0, first_row=0):
         """K8 on this context: a labelled feature DB on the device (see FeatureDBStats; webspeechanalyzer_amd.dbstats drives it)."""
-        return FeatureDBStats(self, features, durations, vocab_sizes, n_ord)
+        return FeatureDBStats(self, features, durations, vocab_sizes, n_ord, first_row)
+
+    def device_db(self, width, capacity):
+        """K10 on this context: an empty feature DB of `capacity` rows of `width` features that stays on the device (see FeatDB;
+        webspeechanalyzer_amd.featdb.DeviceDB drives it)."""
+        return FeatDB(self, width, capacity)
 
     def knn_store(self, width, n_classes, capacity):
         """K9 on this context: an empty ml5 KNN store of `capacity` rows of `width` features (see KnnStore; webspeechanalyzer_amd.knn drives it)."""
@@ -828,6 +851,20 @@ class Batch:
         self.an._check(self.L.wsa_batch_copy_rows(self.h, stream, meta.ctypes.data, feat.ctypes.data, max(n, 1),
                                                    segs.ctypes.data, max(m, 1), roff.ctypes.data, soff.ctypes.data))
         return dict(meta=meta, feat=feat, segments=segs, row_off=roff, seg_off=soff)
+
+    def row_meta(self, stream=0):
+        """The row metadata alone, [n, 8] i32: the features stay on the device (featdb.DeviceDB)."""
+        n = self.device_result(stream).n_rows
+        meta = np.zeros((n, 8), np.int32)
+        self.an._check(self.L.wsa_batch_copy_rows(self.h, stream, meta.ctypes.data, None, max(n, 1), None, 0, None, None))
+        return meta
+
+    def utterance_meta(self, stream=0):
+        """level 11: the utterance metadata alone, [n, 4] i32."""
+        n = self.device_result(stream).n_utterance_rows
+        meta = np.zeros((n, 4), np.int32)
+        self.an._check(self.L.wsa_batch_copy_utterance(self.h, stream, meta.ctypes.data, None, max(n, 1), None))
+        return meta
 
     def spectra(self, stream=0):
         words = self.info["n_frames_total"] * self.info["bands"]
@@ -1120,12 +1157,29 @@ class Trainer:
     """wsa_trainer: minibatch SGD on the app's Dense classifiers (K7, spec TR-1).  `spec` holds the INITIAL weights, the ranges to
     normalise with and the legend; features [n][spec.units[0]] f64 (53, 264 or 23 wide) and labels [n] class indices are host arrays, the last n_val rows validation."""
 
-    def __init__(self, an, spec, features, labels, n_val, batch_size, learning_rate, regression=None):
-        """regression: None, or (out_min, out_max): `labels` are then real-valued targets and the trainer is TR-2's (Adam, mean squared error)"""
+    def __init__(self, an, spec, features, labels, n_val, batch_size, learning_rate, regression=None, db=None):
+        """regression: None, or (out_min, out_max): `labels` are then real-valued targets and the trainer is TR-2's (Adam, mean squared error).
+        db: a FeatDB of `an`; `features` is then the list of its rows to train on, in that order (wsa_trainer_create_db: nothing is uploaded
+        but the list), and the trainer is bit for bit the one made from the host copy of those rows."""
         self.an, self.L, self.spec = an, an.L, spec
         self.out_range = None if regression is None else (float(regression[0]), float(regression[1]))
-        feat = np.ascontiguousarray(features, np.float64)
         lab = np.ascontiguousarray(labels, np.int32 if regression is None else np.float64)
+        if db is not None:
+            rows = np.ascontiguousarray(features, np.uint32)
+            if rows.ndim != 1 or lab.shape != rows.shape:
+                raise ValueError(f"rows {rows.shape} / labels {lab.shape}: expected [n] DB row indices and [n]")
+            self.n_rows, self.n_val, self.n_train = rows.shape[0], int(n_val), rows.shape[0] - int(n_val)
+            d, keep = _model_desc(spec)
+            self.h = ctypes.c_void_p()
+            if regression is None:
+                an._check(self.L.wsa_trainer_create_db(an.h, ctypes.byref(d), db.h, rows.ctypes.data, lab.ctypes.data, rows.shape[0], int(n_val),
+                                                       int(batch_size), float(learning_rate), ctypes.byref(self.h)))
+            else:
+                an._check(self.L.wsa_regress_trainer_create_db(an.h, ctypes.byref(d), db.h, rows.ctypes.data, lab.ctypes.data, rows.shape[0], int(n_val),
+                                                               int(batch_size), float(learning_rate), self.out_range[0], self.out_range[1], ctypes.byref(self.h)))
+            del keep
+            return
+        feat = np.ascontiguousarray(features, np.float64)
         if feat.ndim != 2 or feat.shape[1] != int(spec.units[0]) or lab.shape != (feat.shape[0],):
             raise ValueError(f"features {feat.shape} / labels {lab.shape}: expected [n][{int(spec.units[0])}] (the model's inputs) and [n]")
         self.n_rows, self.n_val, self.n_train = feat.shape[0], int(n_val), feat.shape[0] - int(n_val)
@@ -1267,9 +1321,19 @@ class FeatureDBStats:
     durations [n] f64 are host arrays; vocab_sizes has one vocabulary size per categorical head, n_ord is the number of ordinal heads.
     Indices and values are what the device sees; webspeechanalyzer_amd.dbstats builds them from the app's rows."""
 
-    def __init__(self, an, features, durations, vocab_sizes=(), n_ord=0):
+    def __init__(self, an, features, durations, vocab_sizes=(), n_ord=0, first_row=0):
+        """first_row: with a FeatDB as `features`, the DB row of the first of the len(durations) rows taken"""
         self.an, self.L = an, an.L
         dur = np.ascontiguousarray(durations, np.float64)
+        if isinstance(features, FeatDB):                 # the rows of a device DB, copied device to device (wsa_featdb_dbstats_create)
+            if dur.ndim != 1:
+                raise ValueError(f"durations {dur.shape}: expected [n]")
+            self.n_feat, self.n_rows, self.vocab, self.n_ord = features.width, dur.shape[0], [int(v) for v in vocab_sizes], int(n_ord)
+            voc = np.ascontiguousarray(self.vocab, np.uint32)
+            self.h = ctypes.c_void_p()
+            an._check(self.L.wsa_featdb_dbstats_create(an.h, features.h, int(first_row), self.n_rows, dur.ctypes.data if self.n_rows else None, len(self.vocab),
+                                                   voc.ctypes.data if len(self.vocab) else None, self.n_ord, ctypes.byref(self.h)))
+            return
         feat = None if features is None else np.ascontiguousarray(features, np.float64)
         if dur.ndim != 1 or (feat is not None and (feat.ndim != 2 or feat.shape[0] != dur.shape[0] or feat.shape[1] not in (53, 264, 23))):
             raise ValueError(f"features {None if feat is None else feat.shape} / durations {dur.shape}: expected [n][53] (or [n][264], [n][23]) and [n]")
@@ -1354,6 +1418,123 @@ class FeatureDBStats:
             self.close()
         except Exception:
             pass
+
+
+class FeatDB:
+    """wsa_featdb: the feature columns of the app's feature DB on the device of one context (K10, spec FD-1): one allocation of
+    capacity x width doubles, rows appended behind the ones it holds and never moved.  Strings stay with the caller
+    (webspeechanalyzer_amd.featdb.DeviceDB keeps them); pass the same stream to every call."""
+
+    def __init__(self, an, width, capacity):
+        self.an, self.L, self.h = an, an.L, ctypes.c_void_p()
+        self.width, self.capacity = int(width), int(capacity)
+        an._check(self.L.wsa_featdb_create(an.h, self.width, self.capacity, ctypes.byref(self.h)))
+
+    @staticmethod
+    def tile_info():
+        """(source rows per wave tile, per step of the keep kernel's workgroup, appended rows per pass of the copy kernel) of K10."""
+        a, b, c = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        lib().wsa_featdb_tile_info(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
+        return a.value, b.value, c.value
+
+    @property
+    def count(self):
+        n = ctypes.c_uint32()
+        self.an._check(self.L.wsa_featdb_count(self.h, ctypes.byref(n)))
+        return int(n.value)
+
+    def clear(self):
+        self.an._check(self.L.wsa_featdb_clear(self.h))
+
+    def append_batch(self, batch, stream=0):
+        """The rows of the batch's last run that the app's storing keeps (wsa_featdb_append_batch; synchronises).  Returns (first DB row,
+        kept): kept [n_added] i32 = the source row (level 11: utterance row) of every appended row."""
+        cap = max(int(batch.info["rows_cap"]), int(batch.info["n_clips"]))       # what a run can keep at most; more than the DB's capacity is refused before
+        kept = np.zeros(max(min(cap, self.capacity), 1), np.int32)
+        first, n = ctypes.c_uint32(), ctypes.c_uint32()
+        self.an._check(self.L.wsa_featdb_append_batch(self.h, batch.h, stream, ctypes.byref(first), ctypes.byref(n), kept.ctypes.data, len(kept)))
+        return int(first.value), kept[:n.value].copy()
+
+    def append_host(self, features, stream=0):
+        """Dense host rows [n][width] (an imported DB); returns the first DB row."""
+        feat = np.ascontiguousarray(features, np.float64).reshape(-1, self.width)
+        first = self.count
+        self.an._check(self.L.wsa_featdb_append_host(self.h, feat.ctypes.data if len(feat) else None, len(feat), stream))
+        return first
+
+    def device_rows(self):
+        """The device pointer of the dense table [count][width] f64 (valid until close)."""
+        p = ctypes.c_void_p()
+        self.an._check(self.L.wsa_featdb_device_rows(self.h, ctypes.byref(p)))
+        return p.value
+
+    def copy_rows(self, first=0, n=None, stream=0):
+        n = self.count - int(first) if n is None else int(n)
+        out = np.zeros((n, self.width), np.float64)
+        self.an._check(self.L.wsa_featdb_copy_rows(self.h, stream, int(first), n, out.ctypes.data if n else None))
+        return out
+
+    def gather(self, rows, d_out, stream=0):
+        """d_out [n][width] f64 (device pointer) = DB rows `rows`; only enqueues."""
+        r = np.ascontiguousarray(rows, np.uint32)
+        if r.ndim != 1:
+            raise ValueError(f"rows has shape {r.shape}: expected a list of DB row indices")
+        self.an._check(self.L.wsa_featdb_gather(self.h, r.ctypes.data if len(r) else None, len(r), d_out, stream))
+
+    def ranges(self, rows=None, stream=0):
+        """(in_min, in_max) [width] over the selected rows (None: all); NaN for a column that holds one; synchronises."""
+        r = None if rows is None else np.ascontiguousarray(rows, np.uint32)
+        n = self.count if r is None else len(r)
+        mn, mx = np.zeros(self.width, np.float64), np.zeros(self.width, np.float64)
+        self.an._check(self.L.wsa_featdb_ranges(self.h, None if r is None else r.ctypes.data, n, stream, mn.ctypes.data, mx.ctypes.data))
+        return mn, mx
+
+    def trainer(self, spec, rows, labels, n_val, batch_size, learning_rate):
+        """A Trainer over DB rows `rows` in that order (wsa_trainer_create_db)."""
+        return Trainer(self.an, spec, rows, labels, n_val, batch_size, learning_rate, db=self)
+
+    def regress_trainer(self, spec, rows, values, n_val, batch_size, learning_rate, out_min=None, out_max=None):
+        return Trainer(self.an, spec, rows, values, n_val, batch_size, learning_rate, db=self,
+                       regression=(spec.out_min if out_min is None else out_min, spec.out_max if out_max is None else out_max))
+
+    def close(self):
+        if self.h:
+            self.L.wsa_featdb_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def debug_featdb_append(db, level, meta, feat, clip_off=None, stream=0):
+    """Test access to K10 on hand-built tables (csrc/featdb.hip wsa_debug_featdb_append; not part of include/wsa.h): meta [n][8] i32
+    (None at levels 5 / 13 / 11), feat [n][stride] f64, clip_off [n_clips + 1] u32 (level 11).  The tables are uploaded with torch, the
+    product's keep, scan and copy kernels run over them.  Returns (first DB row, kept)."""
+    import torch
+    L = lib()
+    vp, i32, u32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32
+    L.wsa_debug_featdb_append.argtypes = [vp, i32, vp, vp, u32, vp, u32, u32, vp, ctypes.POINTER(u32), ctypes.POINTER(u32), vp, u32]
+    L.wsa_debug_featdb_append.restype = ctypes.c_int
+    dev = f"cuda:{db.an.device}"
+    feat = np.ascontiguousarray(feat, np.float64)
+    n, stride = feat.shape
+    t_feat = torch.from_numpy(feat.view(np.int64)).to(dev)
+    t_meta = None if meta is None else torch.from_numpy(np.ascontiguousarray(meta, np.int32).reshape(n, 8)).to(dev)
+    off = None if clip_off is None else np.ascontiguousarray(clip_off, np.uint32)
+    t_off = None if off is None else torch.from_numpy(off.view(np.int32)).to(dev)
+    n_clips = 0 if off is None else len(off) - 1
+    items = n_clips if level == 11 else n
+    kept = np.zeros(max(items, 1), np.int32)
+    first, added = u32(), u32()
+    torch.cuda.synchronize(dev)
+    db.an._check(L.wsa_debug_featdb_append(db.h, int(level), None if t_meta is None else t_meta.data_ptr(), t_feat.data_ptr() if n else None, stride,
+                                           None if t_off is None else t_off.data_ptr(), n, n_clips, stream, ctypes.byref(first), ctypes.byref(added),
+                                           kept.ctypes.data, len(kept)))
+    torch.cuda.synchronize(dev)
+    return int(first.value), kept[:added.value].copy()
 
 
 class KnnStore:

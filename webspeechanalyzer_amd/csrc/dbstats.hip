@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 #include "host_plan.hpp"
+#include "featdb_internal.hpp"
 
 #pragma clang fp contract(off)
 
@@ -297,6 +298,29 @@ wsa_status wsa_wide_dbstats_create(wsa_ctx* ctx, const double* feat, uint32_t n_
     t.n_rows = n_rows; t.n_chunks = db->n_chunks; t.n_cat = n_cat; t.n_ord = n_ord; t.items = db->items; t.dur = db->d_dur;
     std::memcpy(t.voff, db->voff, sizeof(t.voff));
     for (int h = 0; h < DS_H; h++) { t.t_idx[h] = db->d_t_idx[h]; t.p_idx[h] = db->d_p_idx[h]; t.t_val[h] = db->d_t_val[h]; t.p_val[h] = db->d_p_val[h]; }
+    *out = db;
+    return WSA_OK;
+}
+
+// the same DB with its feature rows taken from a device feature DB (FD-1): rows first_row .. first_row + n_rows - 1, device to device
+wsa_status wsa_featdb_dbstats_create(wsa_ctx* ctx, const wsa_featdb* src, uint32_t first_row, uint32_t n_rows, const double* duration, uint32_t n_cat,
+                                 const uint32_t* vocab, uint32_t n_ord, wsa_dbstats** out) {
+    if (!ctx || !out) return fail(ctx, WSA_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!src) return fail(ctx, WSA_ERR_INVALID, "null feature DB");
+    if (src->ctx != ctx) return fail(ctx, WSA_ERR_INVALID, "the feature DB belongs to another context");
+    if ((uint64_t)first_row + n_rows > src->count)
+        return fail(ctx, WSA_ERR_INVALID, "rows " + std::to_string(first_row) + " .. " + std::to_string((uint64_t)first_row + n_rows) + " are outside the DB's "
+                                          + std::to_string(src->count) + " rows");
+    wsa_dbstats* db = nullptr;
+    if (const wsa_status st = wsa_wide_dbstats_create(ctx, nullptr, (uint32_t)src->width, duration, n_rows, n_cat, vocab, n_ord, &db)) return st;
+    const size_t words = (size_t)n_rows * (size_t)src->width;
+    if (!(hipDeviceSynchronize() == hipSuccess && db->mem.alloc(&db->d_feat, words)
+          && hipMemcpy(db->d_feat, src->d_feat + (size_t)first_row * src->width, words * sizeof(double), hipMemcpyDeviceToDevice) == hipSuccess)) {
+        const std::string msg = std::string("device allocation / copy failed: ") + hipGetErrorString(hipGetLastError());
+        wsa_dbstats_destroy(db);
+        return fail(ctx, WSA_ERR_HIP, msg);
+    }
     *out = db;
     return WSA_OK;
 }

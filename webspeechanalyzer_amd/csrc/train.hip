@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include "train_internal.hpp"
+#include "featdb_internal.hpp"
 
 using wsa_api::fail;
 using namespace wsa_train;
@@ -61,6 +62,14 @@ __global__ void __launch_bounds__(256) train_normalise_kernel(const double* feat
     x[i] = k < nin ? (float)((feat[r * (uint64_t)nin + k] - mn[k]) / (mx[k] - mn[k])) : 0.f;
 }
 
+// ---- create from a device feature DB (FD-1): the same, x[r] from row rows[r] of the DB's dense table
+__global__ void __launch_bounds__(256) train_normalise_db_kernel(const double* db, const uint32_t* rows, const double* mn, const double* mx, uint64_t n_rows, int nin, int xs, float* x) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_rows * (uint64_t)xs) return;
+    const uint64_t r = i / (uint64_t)xs; const int k = (int)(i % (uint64_t)xs);
+    x[i] = k < nin ? (float)((db[(uint64_t)rows[r] * (uint64_t)nin + k] - mn[k]) / (mx[k] - mn[k])) : 0.f;
+}
+
 // one launch of the solo trainer's epoch: the stage's kernel on the parameters built from the description; idx: the order or identity buffer
 void solo_launch(wsa_trainer* t, const uint32_t* idx, TrStage stage, uint32_t step, int pos, hipStream_t s) {
     const TrainDesc& d = t->desc;
@@ -87,6 +96,7 @@ void solo_launch(wsa_trainer* t, const uint32_t* idx, TrStage stage, uint32_t st
 struct CreateArgs {
     const wsa_model_desc* d; const double* feat; const int32_t* label; const double* target; bool regress;
     uint32_t n_rows, n_val, batch_size; double learning_rate, out_min, out_max;
+    const wsa_featdb* db = nullptr; const uint32_t* rows = nullptr;          // wsa_trainer_create_db: row r is DB row rows[r], feat is NULL
 };
 
 // "" or why the arguments are refused; host only, nothing is allocated before it has passed
@@ -115,7 +125,12 @@ std::string create_refusal(const CreateArgs& a) {
         if (!std::isfinite(d->in_min[k]) || !std::isfinite(d->in_max[k])) return "non-finite in_min / in_max of input " + std::to_string(k);
         if (d->in_max[k] == d->in_min[k]) return "feature " + std::to_string(k) + " has max == min: it cannot be normalised";
     }
-    if (!a.feat || (a.regress ? !a.target : !a.label)) return a.regress ? "null feature / target pointer" : "null feature / label pointer";
+    if ((a.db ? !a.rows : !a.feat) || (a.regress ? !a.target : !a.label)) return a.regress ? "null feature / target pointer" : "null feature / label pointer";
+    if (a.db) {
+        if (a.db->width != nin) return "the model takes " + std::to_string(nin) + " inputs; the DB's rows have " + std::to_string(a.db->width) + " features";
+        const std::string why = wsa_fd::rows_refusal(a.db, a.rows, a.n_rows);
+        if (!why.empty()) return why;
+    }
     if (a.n_val >= a.n_rows) return "n_val " + std::to_string(a.n_val) + " leaves no training rows of " + std::to_string(a.n_rows);
     if (a.batch_size == 0) return "batch_size must be at least 1";
     if (!std::isfinite(a.learning_rate) || !std::isfinite((float)a.learning_rate)) return "the learning rate is not finite as an f32";
@@ -162,8 +177,13 @@ bool create_buffers(wsa_trainer* t, const CreateArgs& a) {
     for (int i = 0; i < 2; i++) if (hipEventCreateWithFlags(&t->ev[i], hipEventDisableTiming) != hipSuccess) return false;
     wsa::DevArena tmp;                                                        // the double rows live only until they are normalised
     double *d_feat = nullptr, *d_mn = nullptr, *d_mx = nullptr, *d_y = nullptr;
-    if (!(tmp.alloc(&d_feat, (size_t)n_rows * nin) && tmp.alloc(&d_mn, (size_t)nin) && tmp.alloc(&d_mx, (size_t)nin)
-          && hipMemcpy(d_feat, a.feat, (size_t)n_rows * nin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
+    uint32_t* d_rows = nullptr;
+    if (a.db) {                                                               // the DB's rows stay where they are: only the row list travels
+        if (!(hipDeviceSynchronize() == hipSuccess && tmp.alloc(&d_rows, (size_t)n_rows)
+              && hipMemcpy(d_rows, a.rows, (size_t)n_rows * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess)) return false;
+    } else if (!(tmp.alloc(&d_feat, (size_t)n_rows * nin)
+                 && hipMemcpy(d_feat, a.feat, (size_t)n_rows * nin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess)) return false;
+    if (!(tmp.alloc(&d_mn, (size_t)nin) && tmp.alloc(&d_mx, (size_t)nin)
           && hipMemcpy(d_mn, d->in_min, (size_t)nin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
           && hipMemcpy(d_mx, d->in_max, (size_t)nin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess)) return false;
     if (a.regress) {
@@ -172,7 +192,8 @@ bool create_buffers(wsa_trainer* t, const CreateArgs& a) {
         hipLaunchKernelGGL(train_adam_reset_kernel, dim3(1), dim3(1), 0, nullptr, D.adam);
     } else if (hipMemcpy(D.label, a.label, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) return false;
     const uint64_t total = (uint64_t)n_rows * xs;
-    hipLaunchKernelGGL(train_normalise_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, nullptr, d_feat, d_mn, d_mx, (uint64_t)n_rows, nin, (int)xs, D.x);
+    if (a.db) hipLaunchKernelGGL(train_normalise_db_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, nullptr, a.db->d_feat, d_rows, d_mn, d_mx, (uint64_t)n_rows, nin, (int)xs, D.x);
+    else hipLaunchKernelGGL(train_normalise_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, nullptr, d_feat, d_mn, d_mx, (uint64_t)n_rows, nin, (int)xs, D.x);
     return hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
 }
 
@@ -217,6 +238,24 @@ wsa_status wsa_trainer_create(wsa_ctx* ctx, const wsa_model_desc* d, const doubl
 wsa_status wsa_regress_trainer_create(wsa_ctx* ctx, const wsa_model_desc* d, const double* feat, const double* target, uint32_t n_rows,
                                       uint32_t n_val, uint32_t batch_size, double learning_rate, double out_min, double out_max, wsa_trainer** out) {
     return trainer_create(ctx, CreateArgs{d, feat, nullptr, target, true, n_rows, n_val, batch_size, learning_rate, out_min, out_max}, out);
+}
+
+wsa_status wsa_trainer_create_db(wsa_ctx* ctx, const wsa_model_desc* d, const wsa_featdb* db, const uint32_t* rows, const int32_t* label, uint32_t n_rows,
+                                 uint32_t n_val, uint32_t batch_size, double learning_rate, wsa_trainer** out) {
+    if (!db) return fail(ctx, WSA_ERR_INVALID, "null feature DB");
+    if (db->ctx != ctx) return fail(ctx, WSA_ERR_INVALID, "the feature DB belongs to another context");
+    CreateArgs a{d, nullptr, label, nullptr, false, n_rows, n_val, batch_size, learning_rate, 0.0, 1.0};
+    a.db = db; a.rows = rows;
+    return trainer_create(ctx, a, out);
+}
+
+wsa_status wsa_regress_trainer_create_db(wsa_ctx* ctx, const wsa_model_desc* d, const wsa_featdb* db, const uint32_t* rows, const double* target, uint32_t n_rows,
+                                         uint32_t n_val, uint32_t batch_size, double learning_rate, double out_min, double out_max, wsa_trainer** out) {
+    if (!db) return fail(ctx, WSA_ERR_INVALID, "null feature DB");
+    if (db->ctx != ctx) return fail(ctx, WSA_ERR_INVALID, "the feature DB belongs to another context");
+    CreateArgs a{d, nullptr, nullptr, target, true, n_rows, n_val, batch_size, learning_rate, out_min, out_max};
+    a.db = db; a.rows = rows;
+    return trainer_create(ctx, a, out);
 }
 
 void wsa_trainer_destroy(wsa_trainer* t) {

@@ -269,22 +269,31 @@ def _model_of(an, spec_or_model):
 def predict_db(an, db_rows, heads, label_type, label_name, spec, out_min=None, out_max=None, stream=0, return_raw=False):
     """predict_db_nn (neuralmodel.js:410-535) on the GPU: runs the model over EVERY row, with or without a true label, and writes each
     row's prediction into its `pred` pair by update_pred_label's rule.  heads = (class_labels, ordinal_labels); label_type 'cats' or
-    'ords'; spec: a capi.Model, an nnmodel.ModelSpec or a model directory.  Returns the per-row predictions (labels or None for 'cats',
+    'ords'; spec: a capi.Model, an nnmodel.ModelSpec or a model directory.  db_rows may be a featdb.DeviceDB of `an`: the model then runs over
+    its rows where they are (a device-to-device copy, wsa_featdb_dbstats_create) and the predictions go into its records.  Returns the per-row predictions (labels or None for 'cats',
     values for 'ords'); return_raw adds the probabilities [n][C] / the values K8 used."""
     if label_type not in ("cats", "ords"):
         raise ValueError(f"label_type is 'cats' or 'ords', got {label_type!r}")
     cats, ords = head_settings(*heads)
-    if len(db_rows) < 1:
+    from . import capi, nnmodel
+    if (db_rows.count if isinstance(db_rows, capi.FeatDB) else len(db_rows)) < 1:
         raise ValueError("a feature DB has at least one row")
-    from . import nnmodel
-    feat = np.array([r["features"] for r in db_rows], np.float64)
-    if feat.ndim != 2 or feat.shape[1] not in nnmodel.WIDTHS:
-        raise ValueError(f"features {feat.shape}: the models take level-5 / level-13 rows of 53 features (or level-11 rows of 264, level-12 rows of 23)")
+    if isinstance(db_rows, capi.FeatDB):                 # the features stay on the device; the records are the rows
+        if not hasattr(db_rows, "records"):
+            raise TypeError("predict_db takes a featdb.DeviceDB (it keeps the rows' records); a bare capi.FeatDB has none")
+        feat, width, db_rows = db_rows, db_rows.width, db_rows.records
+        if len(db_rows) != feat.count:
+            raise ValueError(f"the device DB holds {feat.count} rows and {len(db_rows)} records")
+    else:
+        feat = np.array([r["features"] for r in db_rows], np.float64)
+        if feat.ndim != 2 or feat.shape[1] not in nnmodel.WIDTHS:
+            raise ValueError(f"features {feat.shape}: the models take level-5 / level-13 rows of 53 features (or level-11 rows of 264, level-12 rows of 23)")
+        width = feat.shape[1]
     dur = np.array([parse_float(r["time"][1]) for r in db_rows], np.float64)
     model, mine = _model_of(an, spec)
     try:
-        if model.n_inputs != feat.shape[1]:              # before anything is uploaded or enqueued
-            raise ValueError(f"the model takes {model.n_inputs} inputs; the DB's rows have {feat.shape[1]} features")
+        if model.n_inputs != width:                      # before anything is uploaded or enqueued
+            raise ValueError(f"the model takes {model.n_inputs} inputs; the DB's rows have {width} features")
         if label_type == "cats":
             legend = [js_str(x) for x in model.labels]
             if len(legend) != model.n_classes:
@@ -316,7 +325,8 @@ def predict_db(an, db_rows, heads, label_type, label_name, spec, out_min=None, o
 def stats_table(an, db_rows, class_labels, ordinal_labels, stream=0):
     """shows_stats_table's numbers (localstore.js:498-627) on the GPU, as plain data:
     {cats: [{name, correct, wrong, blank, classes: [{label, count, duration, correct, wrong}]}], ords: [{name, min, max, true_n, pred_n,
-    sq_sum, rmse}]}; stats_lines(table) prints it as the app does."""
+    sq_sum, rmse}]}; stats_lines(table) prints it as the app does.  db_rows may be a featdb.DeviceDB: its records are counted."""
+    db_rows = getattr(db_rows, "records", db_rows)
     col = build_columns(db_rows, class_labels, ordinal_labels)
     if not col["cats"] and not col["ords"]:
         return dict(cats=[], ords=[])

@@ -340,13 +340,13 @@ function loadModel(src) {
 function plan_train_model(o) {        // -> {spec, job, onEpoch}: what the addon's train takes
   const tm = require('./trainmodel.js');
   const opt = Object.assign({}, tm.DEFAULT_OPTIONS, o.options || {});
-  const data = tm.prepare(o.features, o.labels, o.classes);
+  const data = o.db ? device_db_data(o.db, tm.select(o.labels, o.classes), o.labels.length) : tm.prepare(o.features, o.labels, o.classes);
   const st = tm.stack(opt.layers, data.legend.length, data.width), epochs = o.epochs === undefined ? 10 : o.epochs | 0, seed = o.seed | 0;
   const sp = tm.split(data.y.length, o.validationSplit);
   const init = o.init || tm.glorotInit(Array.from(st.units), seed);
   const spec = { units: st.units, activation: st.activation, kernels: init.kernels.map((k) => Float32Array.from(k)), biases: init.biases.map((b) => Float32Array.from(b)),
     inMin: data.inMin, inMax: data.inMax, labels: data.legend.slice() };
-  const job = { features: data.features, y: data.y, nVal: sp.nVal, batchSize: o.batchSize === undefined ? 32 : o.batchSize, learningRate: opt.learningRate, epochs,
+  const job = { ...rows_of(data), y: data.y, nVal: sp.nVal, batchSize: o.batchSize === undefined ? 32 : o.batchSize, learningRate: opt.learningRate, epochs,
     orders: o.orders || tm.epochOrders(sp.nTrain, epochs, seed + 1) };
   return { spec, job, onEpoch: typeof o.onEpoch === 'function' ? o.onEpoch : undefined };
 }
@@ -357,6 +357,8 @@ function trained_handle(plan, r) {    // the model handle of a finished run `r` 
   loaded_models.add(h);
   return h;
 }
+// a run's rows for the addon's train: host rows, or the rows of a device DB by index (they stay on the device)
+function rows_of(data) { return data.db ? { db: data.db.native, rows: data.rows32 } : { features: data.features }; }
 function train_context() {
   const nat = addon();
   return { nat, ctx: contexts_for(nat, settings.devices ? settings.devices.slice() : [settings.device])[0] };
@@ -376,13 +378,13 @@ function trainModel(o) {
 function plan_train_regression(features, values, o) {
   const tm = require('./trainmodel.js');
   const opt = Object.assign({}, tm.DEFAULT_OPTIONS_ORDS, o.options || {});
-  const data = tm.prepareOrdinal(features, values);
+  const data = is_device_db(features) ? device_db_data(features, tm.selectOrdinal(values), values.length) : tm.prepareOrdinal(features, values);
   const st = tm.stackRegression(opt.layers, data.width), epochs = o.epochs === undefined ? 10 : o.epochs | 0, seed = o.seed | 0;
   const sp = tm.split(data.values.length, o.validationSplit);
   const init = o.init || tm.glorotInit(Array.from(st.units), seed);
   const spec = { units: st.units, activation: st.activation, kernels: init.kernels.map((k) => Float32Array.from(k)), biases: init.biases.map((b) => Float32Array.from(b)),
     inMin: data.inMin, inMax: data.inMax, labels: [], outMin: data.outMin, outMax: data.outMax };
-  const job = { features: data.features, values: data.values, outMin: data.outMin, outMax: data.outMax, nVal: sp.nVal, batchSize: o.batchSize === undefined ? 32 : o.batchSize,
+  const job = { ...rows_of(data), values: data.values, outMin: data.outMin, outMax: data.outMax, nVal: sp.nVal, batchSize: o.batchSize === undefined ? 32 : o.batchSize,
     learningRate: opt.learningRate, epochs, orders: o.orders || tm.epochOrders(sp.nTrain, epochs, seed + 1) };
   return { spec, job, onEpoch: typeof o.onEpoch === 'function' ? o.onEpoch : undefined };
 }
@@ -817,6 +819,8 @@ async function run(clips, callback, labels_of, test_play) {
   try {
     // one geometry per launch: without a conversion in front the clips must share a rate; with resample_to every clip is converted from its own
     // (what the app's folder loop gets from decodeAudioData, ref src/index.js:277-296) and a clip already at resample_to passes unfiltered
+    // a collecting DB and several contexts do not go together: said before the contexts of the new device list replace the DB's
+    if (collect_db && several_devices()) throw several_devices_message();
     const rates = new Set(clips.map((c) => c.sampleRate));
     if (rates.size !== 1 && !(settings.resample_to > 0)) throw 'All clips of one launch must share a sample rate';
     const fs = clips[0].sampleRate;
@@ -832,6 +836,8 @@ async function run(clips, callback, labels_of, test_play) {
     // (the clips travel as they are, whatever they hold: submit_clips)
     // the feature rows of all shards in one piece: they stay on their devices, one grouped RCCL send / receive over xGMI moves them to the first
     // device (include/wsa.h wsa_gather_rows) and ONE copy brings them to the host; a shard's small tables (segments, offsets) come with its own job
+    const files = collect_db ? clips.map((_, c) => (labels_of(c) || [])[0]) : null;
+    const cdb = collect_db ? collect_check(ctxs[0], files) : null;
     const gather = (settings.output_level === 5 || settings.output_level === 13) && (settings.gather === null ? devs.length > 1 && new Set(devs).size === devs.length : settings.gather);      // (a rank is a GPU: contexts that share a device are not gathered)
     const pred = prediction && settings.output_level === 13 ? prediction : null;
     const models = ctxs.map((c) => (pred ? model_on(nat, c) : undefined));
@@ -856,6 +862,8 @@ async function run(clips, callback, labels_of, test_play) {
         off += k;
       }
     }
+    if (cdb && results.length !== 1) throw 'setCollectDB: the launch ran as ' + results.length + ' shards; a device DB takes the rows of one context';      // (collect_check refuses it before anything runs)
+    if (cdb) collect_append(nat, ctxs[0], cdb, results[0], files);       // (one shard; a refusal — the DB is full — rejects the launch, the DB unchanged)
     if (pred && pred.knn) {
       try { results.forEach((res, i) => knn_fold_into(nat, ctxs[i], res, pred)); } catch (e) { drop_contexts(nat); throw e; }
     }
@@ -882,6 +890,90 @@ async function run(clips, callback, labels_of, test_play) {
   } finally {
     playing = false;
   }
+}
+
+// ---- the feature DB that stays on the GPU (specification FD-1, include/wsa.h "A feature DB that stays on the device"; the addon's featdb*).
+// createDeviceDB(level, capacity) -> a DB of `capacity` rows of the level's vectors (5 / 13: 53 numbers, 11: 264, 12: 23) on the configured device.
+// setCollectDB(db | null): every LaunchBatch / LaunchBatches launch from then on appends its run to `db` by the app's storing rules (ref src/index.js:35-100)
+// before the batch's tables are reused — the vectors never leave the device for it; callbacks are delivered exactly as without it.  The file name of a
+// clip is labels[clip][0], as the collector of js/featuredb.js takes it; a file the DB already holds is refused before anything runs (the app skips
+// it, src/index.js:277).  A device DB lives on ONE device, in one context: with more than one entry in `devices` (also [0, 0]: every entry is a context
+// of its own that takes a shard of the launch) setCollectDB is refused, and so is a launch while a DB collects.  While a DB collects, LaunchBatches
+// runs its batches one after the other on the DB's context instead of pipelining them through two.
+// db.records: per stored row {file, part, time, truth, guess}; db.count(); db.toFeatureDB(db_id) -> an ordinary FeatureDB (one copy of the vectors to the
+// host); db.close().  trainModel({db, labels, classes, ...}) and trainRegression(db, values, ...) take the DB in place of `features` (labels / values: one
+// per stored row): the ranges are taken on the device and the trainer reads the rows where they are.  predictDB, statsTable and the KNN functions take host rows.
+const LEVEL_WIDTH = { 5: 53, 13: 53, 11: 264, 12: 23 };
+let collect_db = null;
+function is_device_db(v) { return Boolean(v) && typeof v === 'object' && v.native !== undefined && typeof v.toFeatureDB === 'function'; }
+function live_device_db(db, who) {
+  if (!is_device_db(db)) throw who + ': not a device DB (createDeviceDB)';
+  if (db.released) throw who + ': the device DB was closed';
+  if (!ctx_cache.ctxs.includes(db.ctx)) throw who + ': the device DB was created under other settings (its context is gone)';
+  return db;
+}
+function createDeviceDB(level, capacity) {
+  const width = LEVEL_WIDTH[level];
+  if (!width) throw 'createDeviceDB: output_level ' + level + ' stores no feature vectors (5, 11, 12 and 13 do)';
+  const t = train_context();
+  const db = { level, width, capacity, ctx: t.ctx, native: t.nat.featdbCreate(t.ctx, width, capacity), records: [], files: new Set(), released: false };
+  db.count = () => addon().featdbCount(live_device_db(db, 'count').native);
+  db.toFeatureDB = (db_id) => {
+    const { FeatureDB } = require('./featuredb.js');
+    const rows = addon().featdbCopyRows(live_device_db(db, 'toFeatureDB').native), out = new FeatureDB();
+    db.records.forEach((r, i) => {
+      out.put(level, db_id, r.file, r.part, r.time, Array.from(rows.subarray(i * width, (i + 1) * width)));
+      if (r.truth || r.guess) { const smp = out.table(db_id, false).get(FeatureDB.key(db_id, r.file, r.part)); smp.truth = r.truth || null; smp.guess = r.guess || null; }
+    });
+    return out;
+  };
+  db.close = () => { if (!db.released) { if (collect_db === db) collect_db = null; if (ctx_cache.ctxs.includes(db.ctx)) addon().featdbDestroy(db.native); db.released = true; } };
+  return db;
+}
+// more than one entry in `devices` shards a launch over as many contexts, also where the entries name one GPU twice: a DB belongs to ONE context
+function several_devices() { return Boolean(settings.devices) && settings.devices.length > 1; }
+function several_devices_message() {
+  return 'setCollectDB: a device DB lives on one device, in one context; `devices` has ' + settings.devices.length + ' entries, one context each (configure({devices: null}))';
+}
+function setCollectDB(db) {
+  if (db === null || db === undefined) { collect_db = null; return; }
+  if (several_devices()) throw several_devices_message();
+  collect_db = live_device_db(db, 'setCollectDB');
+}
+// before a collecting launch: the DB fits the launch, and none of its files is held already
+function collect_check(ctx, files) {
+  const db = live_device_db(collect_db, 'setCollectDB');
+  if (several_devices()) throw several_devices_message();
+  if (db.ctx !== ctx) throw 'setCollectDB: the launch runs on another context than the device DB';
+  if (db.level !== settings.output_level) throw 'setCollectDB: the DB holds the vectors of output_level ' + db.level + ', the launch runs at ' + settings.output_level;
+  files.forEach((f, i) => { if (db.files.has(f) || files.indexOf(f) < i) throw 'setCollectDB: the DB already holds ' + JSON.stringify(f); });
+  return db;
+}
+// after the launch's job: the run goes into the DB (the context's kept plan still holds it), the records are built from the metadata the job copied anyway
+function collect_append(nat, ctx, db, res, files) {
+  const r = nat.featdbAppendBatch(ctx, db.native);
+  const level = db.level, step = settings.window_step / 1e3;
+  const pos = new Uint32Array(res.meta.length / 8);          // a row's position in its callback: the rows before it with the same (clip, si)
+  for (let q = 1; q < pos.length; q++) if (res.meta[q * 8] === res.meta[q * 8 - 8] && res.meta[q * 8 + 1] === res.meta[q * 8 - 7]) pos[q] = pos[q - 1] + 1;
+  r.kept.forEach((src) => {
+    if (level === 11) {
+      const m = res.uttMeta.subarray(src * 4, src * 4 + 4);
+      db.records.push({ file: files[m[0]], part: 0, time: [m[2] * step, (m[3] + 1) * step], truth: null, guess: null });
+      return;
+    }
+    const m = res.meta.subarray(src * 8, src * 8 + 8);
+    if (level === 5) db.records.push({ file: files[m[0]], part: m[1], time: [m[2] * step, (m[3] + 1) * step], truth: null, guess: null });
+    else db.records.push({ file: files[m[0]], part: m[1] + pos[src] / 100, time: [(m[2] * step).toFixed(3), ((m[3] + 1) * step).toFixed(3)], truth: null, guess: null });
+  });
+  files.forEach((f) => db.files.add(f));
+}
+// what trainModel / trainRegression need of a device DB in place of prepared host rows: the selection as a row list and its ranges, taken on the device
+function device_db_data(db, sel, n_labels) {
+  live_device_db(db, 'trainModel');
+  if (n_labels !== db.records.length) throw 'trainModel: ' + n_labels + ' labels for a device DB of ' + db.records.length + ' rows';
+  const rows32 = Uint32Array.from(sel.rows);
+  const rg = addon().featdbRanges(db.native, rows32);
+  return Object.assign({}, sel, { db, rows32, inMin: rg.min, inMax: rg.max, width: db.width });
 }
 
 function LaunchAudioNodes(context_source, source_obj = null, callback = null, file_labels = [], offline = false,
@@ -948,7 +1040,9 @@ async function run_batches(batches, callback, labels, test_play) {
   if (playing) throw 'Error: Already playing';                                               // ref @B4554
   playing = true; stop_requested = false; labels_per_segment = [];
   try {
-    const ctxs = pipe_contexts(nat);
+    // a collecting DB lives on one context: its batches run there one after the other
+    const cdb = collect_db ? live_device_db(collect_db, 'setCollectDB') : null;
+    const ctxs = cdb ? [cdb.ctx, cdb.ctx] : pipe_contexts(nat);
     const pred = prediction && settings.output_level === 13 ? prediction : null;
     const models = ctxs.map((c) => (pred ? model_on(nat, c) : undefined));
     const vp = value_prediction && settings.output_level === 13 ? value_prediction : null;
@@ -966,6 +1060,7 @@ async function run_batches(batches, callback, labels, test_play) {
       const g = nat.geometry(ctxs[k % 2], fs_an);
       if (g.bands !== bands) throw 'Bins count mismatch: ' + g.bands + ', ' + bands;          // ref @B8568 check
       const extra = pred && !pred.knn ? [models[k % 2]] : [];
+      if (cdb) collect_check(ctxs[0], clips.map((_, c) => ((labels[k] || [])[c] || [])[0]));
       return submit_clips(nat, ctxs[k % 2], clips, fs, fs_an, false, extra);
     };
     let rows = 0, segments = 0, done = 0;
@@ -975,17 +1070,20 @@ async function run_batches(batches, callback, labels, test_play) {
       // batch k + 1 goes to the other context now (its previous job, batch k - 1, was awaited one turn ago); a failure to start it must not leave batch k unawaited
       let start_err = null;
       next = null;
-      if (k + 1 < lists.length && !stop_requested) { try { next = start(k + 1); } catch (e) { start_err = e; } }
+      if (!cdb && k + 1 < lists.length && !stop_requested) { try { next = start(k + 1); } catch (e) { start_err = e; } }
       let res;
       try { res = await mine; }
-      catch (e) { if (next) { try { await next; } catch (e2) { /* the first failure is reported */ } } drop_pipe_contexts(nat); throw e; }
-      if (start_err) { drop_pipe_contexts(nat); throw start_err; }
+      catch (e) { if (next) { try { await next; } catch (e2) { /* the first failure is reported */ } } if (!cdb) drop_pipe_contexts(nat); throw e; }
+      if (start_err) { drop_pipe_contexts(nat); throw start_err; }     // (only without a collecting DB: with one, nothing was started above)
+      // the run goes into the DB before the context's next batch reuses its tables (that batch starts below, behind the folds that read the same tables)
+      if (cdb) collect_append(nat, ctxs[0], cdb, res, lists[k].map((_, c) => ((labels[k] || [])[c] || [])[0]));
       if (pred && pred.knn) {               // (context k % 2 is idle until batch k + 2 starts)
-        try { knn_fold_into(nat, ctxs[k % 2], res, pred); } catch (e) { if (next) { try { await next; } catch (e2) { /* the first failure is reported */ } } drop_pipe_contexts(nat); throw e; }
+        try { knn_fold_into(nat, ctxs[k % 2], res, pred); } catch (e) { if (next) { try { await next; } catch (e2) { /* the first failure is reported */ } } if (!cdb) drop_pipe_contexts(nat); throw e; }
       }
       if (vp) {                             // (likewise)
-        try { values_fold_into(nat, ctxs[k % 2], res, vp); } catch (e) { if (next) { try { await next; } catch (e2) { /* the first failure is reported */ } } drop_pipe_contexts(nat); throw e; }
+        try { values_fold_into(nat, ctxs[k % 2], res, vp); } catch (e) { if (next) { try { await next; } catch (e2) { /* the first failure is reported */ } } if (!cdb) drop_pipe_contexts(nat); throw e; }
       }
+      if (cdb && k + 1 < lists.length && !stop_requested) next = start(k + 1);       // (a collecting DB's context is free again: nothing is in flight if this throws)
       rows += res.meta.length / 8; segments += res.segments.length / 4; done++;
       if (!test_play && (callback || pred || vp) && !stop_requested) {                              // ref @B24762: silent when test_play
         const lb = labels[k] || [];
@@ -1235,4 +1333,4 @@ function set_predicted_label_for_segment(si, idx, label) {                      
 module.exports = { configure, LaunchAudioNodes, StopAudioNodes, set_predicted_label_for_segment, LaunchBatch, LaunchBatches,
   StreamOpen, decodePcm, STREAM_ACTIVE, STREAM_START, STREAM_STOP, shutdown, allocPinned, freePinned,
   _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, _clip_length: clip_length, _values_after: values_after, loadModel, setPredictionModel, setPredictionModels, setPredictionKnn, setPredictionValues, trainModel, trainModels, saveModel, trainRegression, predictValues, predictDB, statsTable,
-  KNNClassifier, trainKnn, predictKnn };
+  KNNClassifier, trainKnn, predictKnn, createDeviceDB, setCollectDB };

@@ -20,32 +20,38 @@ const DEFAULT_OPTIONS = { layers: [{ type: 'dense', units: 8, activation: 'relu'
 
 // ref neuralmodel.js:216-264: rows whose label is one of `classes` in DB order; fewer than 10 refused; every class with more than 3 and fewer
 // than the largest count is topped up by cycling through the DB in order; min / max over the balanced set; legend = order of first appearance
-function prepare(features, labels, classes) {
+// the label-only half: which DB rows are added, in which order, with which class index (nothing here reads a feature, so it serves host rows and a device DB alike)
+function select(labels, classes) {
   classes = classes.map(String);
   if (classes.indexOf('*') >= 0) throw "trainModel: the '*' wildcard class is not supported";
-  if (!Array.isArray(features) || features.length !== labels.length) throw 'trainModel: features and labels must have one entry per row';
+  const n = labels.length;
   const cls = labels.map((v) => (v === null || v === undefined ? -1 : classes.indexOf(String(v))));
   const rows = [], count = new Array(classes.length).fill(0);
   cls.forEach((c, i) => { if (c >= 0) { rows.push(i); count[c]++; } });
-  if (rows.length < 10) throw 'Sample size ' + rows.length + '/' + features.length + ' too small for training';
+  if (rows.length < 10) throw 'Sample size ' + rows.length + '/' + n + ' too small for training';
   const max_n = Math.max(...count);
   for (let c = 0; c < classes.length; c++)
     while (count[c] < max_n && count[c] > 3)
-      for (let i = 0; i < features.length; i++) {
+      for (let i = 0; i < n; i++) {
         if (cls[i] === c && count[c] < max_n) { rows.push(i); count[c]++; }
         if (count[c] >= max_n) break;
       }
   const legend = [];
   for (const i of rows) if (legend.indexOf(classes[cls[i]]) < 0) legend.push(classes[cls[i]]);
+  return { rows, y: Int32Array.from(rows, (i) => legend.indexOf(classes[cls[i]])), legend, counts: count };
+}
+function prepare(features, labels, classes) {
+  if (classes.map(String).indexOf('*') >= 0) throw "trainModel: the '*' wildcard class is not supported";
+  if (!Array.isArray(features) || features.length !== labels.length) throw 'trainModel: features and labels must have one entry per row';
+  const { rows, y, legend, counts } = select(labels, classes);
   const W = rowWidth(features, 'trainModel');
-  const x = new Float64Array(rows.length * W), y = new Int32Array(rows.length);
+  const x = new Float64Array(rows.length * W);
   const inMin = new Float64Array(W).fill(Infinity), inMax = new Float64Array(W).fill(-Infinity);
   rows.forEach((i, r) => {
     if (features[i].length !== W) throw 'trainModel: row ' + i + ' has ' + features[i].length + ' features; ' + W + ' expected';
     for (let k = 0; k < W; k++) { const v = Number(features[i][k]); x[r * W + k] = v; if (v < inMin[k]) inMin[k] = v; if (v > inMax[k]) inMax[k] = v; }
-    y[r] = legend.indexOf(classes[cls[i]]);
   });
-  return { features: x, y, legend, inMin, inMax, counts: count, rows, width: W };
+  return { features: x, y, legend, inMin, inMax, counts, rows, width: W };
 }
 
 function rng(seed) {            // mulberry32: 32 bits of state, enough for weights and shuffles that only have to be repeatable
@@ -78,31 +84,36 @@ const ORDINAL_RANGES = [0.25, 0.5, 0.75, 1.0];
 // ref neuralmodel.js:278-332: a row's bin is the first range that holds its value; null / undefined and values above 1.0 are dropped; fewer than 10
 // rows refused; only when the largest bin exceeds 3, every bin with more than 3 and fewer than the largest count is topped up by cycling through
 // the DB in order; the input and output ranges over the balanced set
-function prepareOrdinal(features, values) {
-  if (!Array.isArray(features) || features.length !== values.length) throw 'trainRegression: features and values must have one entry per row';
-  const nb = ORDINAL_RANGES.length;
+function selectOrdinal(values) {
+  const nb = ORDINAL_RANGES.length, n = values.length;
   const bins = values.map((v) => (v === null || v === undefined ? -1 : ORDINAL_RANGES.findIndex((hi) => v <= hi)));       // -1: above 1.0 (or NaN)
   const rows = [], count = new Array(nb).fill(0);
   bins.forEach((b, i) => { if (b >= 0) { rows.push(i); count[b]++; } });
-  if (rows.length < 10) throw 'Sample size ' + rows.length + '/' + features.length + ' too small for training';
+  if (rows.length < 10) throw 'Sample size ' + rows.length + '/' + n + ' too small for training';
   const max_n = Math.max(...count);
   if (max_n > 3)
     for (let c = 0; c < nb; c++)
       while (count[c] < max_n && count[c] > 3)
-        for (let i = 0; i < features.length; i++) {
+        for (let i = 0; i < n; i++) {
           if (bins[i] === c && count[c] < max_n) { rows.push(i); count[c]++; }
           if (count[c] >= max_n) break;
         }
-  const W = rowWidth(features, 'trainRegression');
-  const x = new Float64Array(rows.length * W), y = new Float64Array(rows.length);
-  const inMin = new Float64Array(W).fill(Infinity), inMax = new Float64Array(W).fill(-Infinity);
+  const y = Float64Array.from(rows, (i) => Number(values[i]));
   let outMin = Infinity, outMax = -Infinity;
+  for (const v of y) { if (v < outMin) outMin = v; if (v > outMax) outMax = v; }
+  return { rows, values: y, outMin, outMax, counts: count };
+}
+function prepareOrdinal(features, values) {
+  if (!Array.isArray(features) || features.length !== values.length) throw 'trainRegression: features and values must have one entry per row';
+  const sel = selectOrdinal(values), rows = sel.rows;
+  const W = rowWidth(features, 'trainRegression');
+  const x = new Float64Array(rows.length * W);
+  const inMin = new Float64Array(W).fill(Infinity), inMax = new Float64Array(W).fill(-Infinity);
   rows.forEach((i, r) => {
     if (features[i].length !== W) throw 'trainRegression: row ' + i + ' has ' + features[i].length + ' features; ' + W + ' expected';
     for (let k = 0; k < W; k++) { const v = Number(features[i][k]); x[r * W + k] = v; if (v < inMin[k]) inMin[k] = v; if (v > inMax[k]) inMax[k] = v; }
-    y[r] = Number(values[i]); if (y[r] < outMin) outMin = y[r]; if (y[r] > outMax) outMax = y[r];
   });
-  return { features: x, values: y, inMin, inMax, outMin, outMax, counts: count, rows, width: W };
+  return { features: x, values: sel.values, inMin, inMax, outMin: sel.outMin, outMax: sel.outMax, counts: sel.counts, rows, width: W };
 }
 function stackRegression(layers, nInputs) {
   const units = [nInputs === undefined ? 53 : nInputs], activation = [];
@@ -158,4 +169,4 @@ function saveModelFiles(spec, dir) {
   fs.writeFileSync(path.join(dir, 'model.weights.bin'), Buffer.concat(blobs));
 }
 
-module.exports = { prepare, glorotInit, epochOrders, split, stack, saveModelFiles, DEFAULT_OPTIONS, prepareOrdinal, stackRegression, DEFAULT_OPTIONS_ORDS, WIDTHS };
+module.exports = { prepare, glorotInit, epochOrders, split, stack, saveModelFiles, DEFAULT_OPTIONS, prepareOrdinal, stackRegression, DEFAULT_OPTIONS_ORDS, WIDTHS, select, selectOrdinal };

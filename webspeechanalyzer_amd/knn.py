@@ -102,6 +102,57 @@ class Knn:
         self.store.add(f.data_ptr(), c.data_ptr(), len(index), torch.cuda.current_stream(dev).cuda_stream)
         torch.cuda.current_stream(dev).synchronize()
 
+    def _upload_db(self, db, rows, index):
+        """rows of a device DB: gathered on the device into a dense table, added from there"""
+        import torch
+        dev = f"cuda:{self.an.device}"
+        s = torch.cuda.current_stream(dev)
+        f = torch.empty((max(len(rows), 1), self.width), dtype=torch.float64, device=dev)
+        c = torch.from_numpy(np.ascontiguousarray(index, np.int32)).to(dev)
+        db.gather(rows, f.data_ptr(), s.cuda_stream)
+        self.store.add(f.data_ptr(), c.data_ptr(), len(index), s.cuda_stream)
+        s.synchronize()
+
+    def _refill(self, index):
+        """a fresh store filled with everything added so far, host rows and DB rows in the order they came"""
+        self.store.close()
+        self.store = self.an.knn_store(self.width, MAX_CLASSES, self.capacity)
+        at = 0
+        for part in self._rows:
+            n = len(part[1]) if isinstance(part, tuple) else len(part)
+            if n:
+                if isinstance(part, tuple):
+                    self._upload_db(part[0], part[1], index[at:at + n])
+                else:
+                    self._upload(part, index[at:at + n])
+            at += n
+
+    def add_db(self, db, rows, labels):
+        """add() with the rows taken from a featdb.DeviceDB (capi.FeatDB) of the same Analyzer: `rows` are its row indices; the features
+        never visit the host (wsa_featdb_gather, then wsa_knn_add).  This object keeps (db, rows), not a copy: a later add() or add_db() whose
+        label renumbers the stored classes refills the store and gathers these rows AGAIN, so the DB must stay alive and uncleared for
+        as long as anything may still be added here."""
+        rows = np.ascontiguousarray(rows, np.uint32).reshape(-1)
+        labels = list(labels)
+        if db.width != self.width:
+            raise ValueError(f"the DB's rows have {db.width} features, the store takes {self.width}")
+        if len(labels) != len(rows):
+            raise ValueError(f"{len(rows)} rows, {len(labels)} labels")
+        names, index = label_order(self._labels + labels)
+        if len(names) > MAX_CLASSES:
+            raise ValueError(f"{len(names)} classes: a KNN store takes {MAX_CLASSES}")
+        if len(index) > self.capacity:
+            raise ValueError(f"{len(index)} rows: the store was created for {self.capacity}")
+        old = len(self._labels)
+        self._rows.append((db, rows))
+        self._labels += labels
+        if np.array_equal(index[:old], self._index):
+            if len(labels):
+                self._upload_db(db, rows, index[old:])
+        else:
+            self._refill(index)
+        self._index, self.classes = index, names
+
     def add(self, rows, labels):
         rows = np.asarray(rows, np.float64).reshape(-1, self.width)
         labels = list(labels)
@@ -118,6 +169,8 @@ class Knn:
         if np.array_equal(index[:old], self._index):
             if len(labels):
                 self._upload(rows, index[old:])
+        elif any(isinstance(part, tuple) for part in self._rows):
+            self._refill(index)                      # rows of a device DB among them (add_db): part by part, the DB's gathered again
         else:                                        # stored classes were renumbered: a fresh store, filled in one go
             self.store.close()
             self.store = self.an.knn_store(self.width, MAX_CLASSES, self.capacity)

@@ -121,6 +121,7 @@ typedef struct {
      * kept plan keeps its ensemble tables too; made and replaced by the job (one job at a time uses a context), dropped by destroy() */
     wsa_ensemble *ens; struct model_box *ens_models[WSA_ENSEMBLE_MAX]; uint32_t ens_n;
     struct knn_box *knns;         /* the KNN stores created on this context (knnCreate): destroy() destroys them with it */
+    struct fdb_box *fdbs;         /* the device feature DBs created on this context (featdbCreate): destroy() destroys them with it */
     /* the regression group of the last batchRegressGroup call (wsa_regress_group_create over reg_models and their ranges): a call with the same models
      * and ranges reuses it, so the kept plan keeps its group tables and allocates nothing; replaced by the next other list, dropped by destroy() */
     wsa_regress_group *reg; struct model_box *reg_models[WSA_REGRESS_GROUP_MAX]; double reg_lo[WSA_REGRESS_GROUP_MAX], reg_hi[WSA_REGRESS_GROUP_MAX]; uint32_t reg_n;
@@ -137,6 +138,12 @@ typedef struct knn_box { wsa_knn *k; ctx_box *owner; uint32_t width, n_classes; 
 static void knn_unlink(knn_box *kb) {
     if (kb->owner) for (knn_box **q = &kb->owner->knns; *q; q = &(*q)->next) if (*q == kb) { *q = kb->next; break; }
     kb->owner = NULL; kb->next = NULL;
+}
+/* What JS holds for a device feature DB (wsa_featdb): a box like a KNN store's; every call on a DB is synchronous but train, which counts as a child of the context */
+typedef struct fdb_box { wsa_featdb *db; ctx_box *owner; uint32_t width; struct fdb_box *next; } fdb_box;
+static void fdb_unlink(fdb_box *fb) {
+    if (fb->owner) for (fdb_box **q = &fb->owner->fdbs; *q; q = &(*q)->next) if (*q == fb) { *q = fb->next; break; }
+    fb->owner = NULL; fb->next = NULL;
 }
 static void box_drop_ensemble(ctx_box *b) {
     if (b->ens) wsa_ensemble_destroy(b->ens);
@@ -198,6 +205,7 @@ static napi_value fn_destroy(napi_env env, napi_callback_info info) {
         box_drop_regress(b);
         while (b->models) { model_box *mb = b->models; wsa_model_destroy(mb->m); mb->m = NULL; model_unlink(mb); }     /* models go before their context */
         while (b->knns) { knn_box *kb = b->knns; wsa_knn_destroy(kb->k); kb->k = NULL; knn_unlink(kb); }               /* and so do KNN stores */
+        while (b->fdbs) { fdb_box *fb = b->fdbs; wsa_featdb_destroy(fb->db); fb->db = NULL; fdb_unlink(fb); }           /* and device feature DBs */
         if (b->queue) { wsa_queue_destroy(b->ctx, b->queue); b->queue = NULL; }
         wsa_destroy(b->ctx); b->ctx = NULL;
     }
@@ -1220,6 +1228,7 @@ typedef struct {
     float *kernel[WSA_MODEL_MAX_LAYERS], *bias[WSA_MODEL_MAX_LAYERS];
     double mn[WSA_NUTT], mx[WSA_NUTT];                     /* units[0] entries: the widest row of an ML level has WSA_NUTT */
     double *feat; int32_t *y; uint32_t *orders; uint32_t n, n_val, batch, epochs; double lr;
+    const wsa_featdb *db; uint32_t *rows;                 /* db != NULL: the rows are DB rows rows[0 .. n-1] (wsa_trainer_create_db), feat is NULL */
     double *values, out_min, out_max;                     /* values != NULL: a regression model (wsa_regress_trainer_create) instead of y */
     double *history; wsa_status st; char err[512];
 } train_job;
@@ -1227,15 +1236,21 @@ typedef struct { train_job *j; int32_t epoch; wsa_train_stats s; } train_msg;   
 
 static void train_job_free(train_job *j) {
     for (int l = 0; l < WSA_MODEL_MAX_LAYERS; l++) { free(j->kernel[l]); free(j->bias[l]); }
-    free(j->feat); free(j->y); free(j->values); free(j->orders); free(j->history); free(j);
+    free(j->feat); free(j->y); free(j->values); free(j->orders); free(j->history); free(j->rows); free(j);
+}
+/* the trainer of a job: from host rows, or from the rows of a device feature DB */
+static wsa_status train_job_trainer(wsa_ctx *ctx, const train_job *j, const wsa_model_desc *d, wsa_trainer **t) {
+    if (j->db) return j->values ? wsa_regress_trainer_create_db(ctx, d, j->db, j->rows, j->values, j->n, j->n_val, j->batch, j->lr, j->out_min, j->out_max, t)
+                                : wsa_trainer_create_db(ctx, d, j->db, j->rows, j->y, j->n, j->n_val, j->batch, j->lr, t);
+    return j->values ? wsa_regress_trainer_create(ctx, d, j->feat, j->values, j->n, j->n_val, j->batch, j->lr, j->out_min, j->out_max, t)
+                     : wsa_trainer_create(ctx, d, j->feat, j->y, j->n, j->n_val, j->batch, j->lr, t);
 }
 static void *train_thread(void *arg) {
     train_job *j = (train_job *)arg;
     wsa_ctx *ctx = j->box->ctx;
     wsa_trainer *t = NULL;
     wsa_model_desc d = {j->nl, j->units, j->act, (const float *const *)j->kernel, (const float *const *)j->bias, j->mn, j->mx, NULL};
-    j->st = j->values ? wsa_regress_trainer_create(ctx, &d, j->feat, j->values, j->n, j->n_val, j->batch, j->lr, j->out_min, j->out_max, &t)
-                      : wsa_trainer_create(ctx, &d, j->feat, j->y, j->n, j->n_val, j->batch, j->lr, &t);
+    j->st = train_job_trainer(ctx, j, &d, &t);
     for (uint32_t e = 0; j->st == WSA_OK && e < j->epochs; e++) {
         j->st = wsa_trainer_epoch(t, j->orders ? j->orders + (size_t)e * (j->n - j->n_val) : NULL, j->box->queue);
         wsa_train_stats s;
@@ -1298,7 +1313,7 @@ static int num_of(napi_env env, napi_value o, const char *name, double *out) {
     return napi_get_named_property(env, o, name, &v) == napi_ok && napi_typeof(env, v, &t) == napi_ok && t == napi_number && napi_get_value_double(env, v, out) == napi_ok;
 }
 static void *dup_bytes(const void *p, size_t bytes) { void *q = malloc(bytes ? bytes : 1); if (q && bytes) memcpy(q, p, bytes); return q; }
-static const char *TRAIN_USAGE = "train(ctx, {units, activation, kernels, biases, inMin, inMax}, {features: Float64Array, y: Int32Array | values: Float64Array + outMin + outMax, nVal, batchSize, learningRate, epochs, orders?: Uint32Array}, onEpoch?)";
+static const char *TRAIN_USAGE = "train(ctx, {units, activation, kernels, biases, inMin, inMax}, {features: Float64Array | db + rows: Uint32Array, y: Int32Array | values: Float64Array + outMin + outMax, nVal, batchSize, learningRate, epochs, orders?: Uint32Array}, onEpoch?)";
 /* a job from train's arguments (argv[0] unused, argv[1] the spec, argv[2] the run, argv[3] onEpoch when argc > 3), the inputs copied; NULL with an
  * exception pending */
 static train_job *train_job_from(napi_env env, ctx_box *box, size_t argc, const napi_value *argv) {
@@ -1308,12 +1323,18 @@ static train_job *train_job_from(napi_env env, ctx_box *box, size_t argc, const 
     double n_val = 0, batch = 0, lr = 0, epochs = 0, out_min = 0, out_max = 0;
     /* a regression run (specification TR-2): `values` (the label's real values) with `outMin` / `outMax` in place of `y` */
     const int regress = typed_of(env, argv[2], "values", napi_float64_array, (void **)&values, &ny);
+    /* `db` (a featdbCreate handle of this context) with `rows` (its row indices) in place of `features`: the rows stay on the device */
+    fdb_box *fb = NULL; uint32_t *rows = NULL; size_t nr = 0;
+    { napi_value dv; napi_valuetype dt = napi_undefined; void *pp = NULL;
+      if (napi_get_named_property(env, argv[2], "db", &dv) == napi_ok && napi_typeof(env, dv, &dt) == napi_ok && dt == napi_external && napi_get_value_external(env, dv, &pp) == napi_ok) fb = (fdb_box *)pp; }
+    if (fb && (!fb->db || fb->owner != box)) { napi_throw_error(env, NULL, "train: the device DB was destroyed or belongs to another context"); return NULL; }
+    if (fb && !typed_of(env, argv[2], "rows", napi_uint32_array, (void **)&rows, &nr)) { napi_throw_type_error(env, NULL, usage); return NULL; }
     if (regress && (!num_of(env, argv[2], "outMin", &out_min) || !num_of(env, argv[2], "outMax", &out_max))) { napi_throw_type_error(env, NULL, usage); return NULL; }
     if (!typed_of(env, argv[1], "units", napi_int32_array, (void **)&units, &nu) || !typed_of(env, argv[1], "activation", napi_int32_array, (void **)&act, &na) ||
         !typed_of(env, argv[1], "inMin", napi_float64_array, (void **)&mn, &nmn) || !typed_of(env, argv[1], "inMax", napi_float64_array, (void **)&mx, &nmx) ||
         nu < 2 || na != nu - 1 || na > WSA_MODEL_MAX_LAYERS || units[0] < 1 || units[0] > WSA_NUTT || nmn != (size_t)units[0] || nmx != (size_t)units[0] ||
-        !typed_of(env, argv[2], "features", napi_float64_array, (void **)&feat, &nf) || (!regress && !typed_of(env, argv[2], "y", napi_int32_array, (void **)&y, &ny)) ||
-        ny < 1 || nf != ny * (size_t)units[0] || ny > 0xffffffffu ||
+        (!fb && !typed_of(env, argv[2], "features", napi_float64_array, (void **)&feat, &nf)) || (!regress && !typed_of(env, argv[2], "y", napi_int32_array, (void **)&y, &ny)) ||
+        ny < 1 || (fb ? nr != ny : nf != ny * (size_t)units[0]) || ny > 0xffffffffu ||
         !num_of(env, argv[2], "nVal", &n_val) || !num_of(env, argv[2], "batchSize", &batch) || !num_of(env, argv[2], "learningRate", &lr) || !num_of(env, argv[2], "epochs", &epochs) ||
         n_val < 0 || n_val >= (double)ny || batch < 0 || batch > 4294967295.0 || epochs < 1 || epochs > 1e6) { napi_throw_type_error(env, NULL, usage); return NULL; }
     const uint32_t n_train = (uint32_t)ny - (uint32_t)n_val;
@@ -1336,11 +1357,13 @@ static train_job *train_job_from(napi_env env, ctx_box *box, size_t argc, const 
         if (ok) { j->kernel[l] = dup_bytes(dk, lk * sizeof(float)); j->bias[l] = dup_bytes(db, lb * sizeof(float)); ok = j->kernel[l] && j->bias[l]; }
     }
     if (!ok) { train_job_free(j); napi_throw_type_error(env, NULL, "train: kernels[i] must be a Float32Array of units[i] x units[i+1], biases[i] one of units[i+1]"); return NULL; }
-    j->feat = dup_bytes(feat, nf * sizeof(double)); j->history = calloc((size_t)j->epochs * 4, sizeof(double));
+    if (fb) { j->db = fb->db; j->rows = dup_bytes(rows, nr * sizeof(uint32_t)); }
+    else j->feat = dup_bytes(feat, nf * sizeof(double));
+    j->history = calloc((size_t)j->epochs * 4, sizeof(double));
     if (regress) { j->values = dup_bytes(values, ny * sizeof(double)); j->out_min = out_min; j->out_max = out_max; }
     else j->y = dup_bytes(y, ny * sizeof(int32_t));
     if (orders) j->orders = dup_bytes(orders, no * sizeof(uint32_t));
-    if (!j->feat || (regress ? !j->values : !j->y) || !j->history || (orders && !j->orders)) { train_job_free(j); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    if ((fb ? !j->rows : !j->feat) || (regress ? !j->values : !j->y) || !j->history || (orders && !j->orders)) { train_job_free(j); napi_throw_error(env, NULL, "out of memory"); return NULL; }
     napi_valuetype ft = napi_undefined;
     if (argc > 3 && napi_typeof(env, argv[3], &ft) == napi_ok && ft == napi_function && napi_create_reference(env, argv[3], 1, &j->on_epoch) != napi_ok) j->on_epoch = NULL;
     return j;
@@ -1395,8 +1418,7 @@ static void *train_group_thread(void *arg) {
     for (uint32_t i = 0; i < g->n && g->st == WSA_OK; i++) {
         train_job *j = g->job[i];
         wsa_model_desc d = {j->nl, j->units, j->act, (const float *const *)j->kernel, (const float *const *)j->bias, j->mn, j->mx, NULL};
-        g->st = j->values ? wsa_regress_trainer_create(ctx, &d, j->feat, j->values, j->n, j->n_val, j->batch, j->lr, j->out_min, j->out_max, &t[i])
-                          : wsa_trainer_create(ctx, &d, j->feat, j->y, j->n, j->n_val, j->batch, j->lr, &t[i]);
+        g->st = train_job_trainer(ctx, j, &d, &t[i]);
         if (j->epochs > longest) longest = j->epochs;
     }
     wsa_train_group *grp = NULL;
@@ -1621,6 +1643,119 @@ done:
     if (db) wsa_dbstats_destroy(db);
     free(cat); free(cls); free(od); free(flat);
     return res;
+}
+
+/* ---- the feature DB that stays on the device (wsa_featdb_*, K10, specification FD-1).  Every call is synchronous, on the context's own stream.
+ *   featdbCreate(ctx, width, capacity) -> handle;  featdbDestroy(handle);  featdbCount(handle) -> rows held
+ *   featdbAppendBatch(ctx, db) -> {first, kept: Int32Array}: the rows of the context's last processBatch that the app's storing keeps
+ *     (wsa_featdb_append_batch on its kept plan), kept[i] = the source row (level 11: utterance row) of DB row first + i
+ *   featdbCopyRows(db) -> Float64Array [count][width];  featdbRanges(db, rows: Uint32Array) -> {min, max}: Float64Array [width] */
+static void fdb_finalize(napi_env env, void *data, void *hint) {
+    fdb_box *fb = (fdb_box *)data;
+    if (!fb->db && !fb->owner) free(fb);             /* a live DB stays (explicit destroy only, as models) */
+}
+static fdb_box *get_fdb(napi_env env, napi_value v) {
+    void *p = NULL; napi_valuetype t = napi_undefined;
+    if (napi_typeof(env, v, &t) != napi_ok || t != napi_external || napi_get_value_external(env, v, &p) != napi_ok) return NULL;
+    return (fdb_box *)p;
+}
+static napi_value fn_featdb_create(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ctx_box *box = argc ? get_box(env, argv[0]) : NULL;
+    int32_t width = 0; uint32_t cap = 0;
+    if (!box || !box->ctx || argc < 3 || napi_get_value_int32(env, argv[1], &width) != napi_ok || napi_get_value_uint32(env, argv[2], &cap) != napi_ok) {
+        napi_throw_type_error(env, NULL, "featdbCreate(ctx, width, capacity)"); return NULL;
+    }
+    wsa_featdb *db = NULL;
+    if (wsa_featdb_create(box->ctx, width, cap, &db) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(box->ctx)); return NULL; }
+    fdb_box *fb = calloc(1, sizeof *fb);
+    if (!fb) { wsa_featdb_destroy(db); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    fb->db = db; fb->owner = box; fb->width = (uint32_t)width; fb->next = box->fdbs; box->fdbs = fb;
+    napi_value ext; NAPI_OK(env, napi_create_external(env, fb, fdb_finalize, NULL, &ext));
+    return ext;
+}
+static napi_value fn_featdb_destroy(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    fdb_box *fb = argc ? get_fdb(env, argv[0]) : NULL;
+    if (!fb) { napi_throw_type_error(env, NULL, "featdbDestroy(db)"); return NULL; }
+    if (fb->owner && fb->owner->children) { napi_throw_error(env, NULL, "the device DB's context has a batch or a training run in flight"); return NULL; }
+    if (fb->db) { wsa_featdb_destroy(fb->db); fb->db = NULL; }
+    fdb_unlink(fb);
+    return NULL;
+}
+/* the live DB of a handle with its context idle, or NULL with an exception pending */
+static fdb_box *fdb_idle(napi_env env, napi_value v, const char *usage) {
+    fdb_box *fb = get_fdb(env, v);
+    if (!fb) { napi_throw_type_error(env, NULL, usage); return NULL; }
+    if (!fb->db || !fb->owner || !fb->owner->ctx) { napi_throw_error(env, NULL, "the device DB was destroyed"); return NULL; }
+    if (fb->owner->children) { napi_throw_error(env, NULL, "the device DB's context has a batch or a training run in flight"); return NULL; }
+    return fb;
+}
+static napi_value fn_featdb_count(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    fdb_box *fb = argc ? fdb_idle(env, argv[0], "featdbCount(db)") : NULL;
+    if (!fb) { if (!argc) napi_throw_type_error(env, NULL, "featdbCount(db)"); return NULL; }
+    uint32_t n = 0; napi_value out;
+    wsa_featdb_count(fb->db, &n);
+    NAPI_OK(env, napi_create_uint32(env, n, &out));
+    return out;
+}
+static napi_value fn_featdb_append_batch(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ctx_box *box = argc ? get_box(env, argv[0]) : NULL;
+    if (!box || !box->ctx || argc < 2) { napi_throw_type_error(env, NULL, "featdbAppendBatch(ctx, db)"); return NULL; }
+    fdb_box *fb = fdb_idle(env, argv[1], "featdbAppendBatch(ctx, db)");
+    if (!fb) return NULL;
+    if (fb->owner != box) { napi_throw_error(env, NULL, "featdbAppendBatch: the device DB belongs to another context"); return NULL; }
+    if (!box->plan) { napi_throw_error(env, NULL, "featdbAppendBatch: no finished processBatch on this context (or one is in flight)"); return NULL; }
+    wsa_batch_info bi;
+    if (wsa_batch_get_info(box->plan, &bi) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(box->ctx)); return NULL; }
+    const uint32_t cap = bi.rows_cap > bi.n_clips ? bi.rows_cap : bi.n_clips;
+    int32_t *kept = malloc(sizeof(int32_t) * (size_t)(cap ? cap : 1));
+    if (!kept) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    uint32_t first = 0, added = 0;
+    napi_value out = NULL, v;
+    if (wsa_featdb_append_batch(fb->db, box->plan, box->queue, &first, &added, kept, cap ? cap : 1) != WSA_OK) napi_throw_error(env, NULL, wsa_last_error(box->ctx));
+    else if (napi_create_object(env, &out) == napi_ok && napi_create_uint32(env, first, &v) == napi_ok) {
+        napi_set_named_property(env, out, "first", v);
+        napi_set_named_property(env, out, "kept", make_typed(env, napi_int32_array, kept, added, 4));
+    }
+    free(kept);
+    return out;
+}
+static napi_value fn_featdb_copy_rows(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    fdb_box *fb = argc ? fdb_idle(env, argv[0], "featdbCopyRows(db)") : NULL;
+    if (!fb) { if (!argc) napi_throw_type_error(env, NULL, "featdbCopyRows(db)"); return NULL; }
+    uint32_t n = 0;
+    wsa_featdb_count(fb->db, &n);
+    napi_value ab, ta; void *data = NULL;
+    const size_t words = (size_t)n * fb->width;
+    if (napi_create_arraybuffer(env, words * sizeof(double), &data, &ab) != napi_ok || napi_create_typedarray(env, napi_float64_array, words, ab, 0, &ta) != napi_ok) {
+        napi_throw_error(env, NULL, "out of memory"); return NULL;
+    }
+    if (wsa_featdb_copy_rows(fb->db, fb->owner->queue, 0, n, (double *)data) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(fb->owner->ctx)); return NULL; }
+    return ta;
+}
+static napi_value fn_featdb_ranges(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    const char *usage = "featdbRanges(db, rows: Uint32Array)";
+    fdb_box *fb = argc ? fdb_idle(env, argv[0], usage) : NULL;
+    if (!fb) { if (!argc) napi_throw_type_error(env, NULL, usage); return NULL; }
+    void *rows = NULL; size_t n = 0;
+    if (argc < 2 || !typed_arg(env, argv[1], napi_uint32_array, &rows, &n) || n < 1 || n > 0xffffffffu) { napi_throw_type_error(env, NULL, usage); return NULL; }
+    double mn[WSA_NUTT], mx[WSA_NUTT];
+    if (wsa_featdb_ranges(fb->db, (const uint32_t *)rows, (uint32_t)n, fb->owner->queue, mn, mx) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(fb->owner->ctx)); return NULL; }
+    napi_value out; NAPI_OK(env, napi_create_object(env, &out));
+    napi_set_named_property(env, out, "min", make_typed(env, napi_float64_array, mn, fb->width, 8));
+    napi_set_named_property(env, out, "max", make_typed(env, napi_float64_array, mx, fb->width, 8));
+    return out;
 }
 
 /* ---- the app's ml5 KNN classifier (wsa_knn_*, K9, specification KN-1): what train_knn does with ml5.KNNClassifier() (ref src/neuralmodel.js:729-837).
@@ -1913,7 +2048,9 @@ NAPI_MODULE_INIT() {
         {"modelCreate", fn_model_create}, {"modelDestroy", fn_model_destroy}, {"train", fn_train}, {"trainGroup", fn_train_group}, {"regressRows", fn_regress_rows},
         {"dbPredict", fn_db_predict}, {"dbTable", fn_db_table},
         {"knnCreate", fn_knn_create}, {"knnDestroy", fn_knn_destroy}, {"knnAdd", fn_knn_add}, {"knnClassify", fn_knn_classify}, {"batchKnn", fn_batch_knn}, {"batchKnnFold", fn_batch_knn_fold},
-        {"streamSetRegress", fn_stream_set_regress}, {"batchRegressGroup", fn_batch_regress_group}};
+        {"streamSetRegress", fn_stream_set_regress}, {"batchRegressGroup", fn_batch_regress_group},
+        {"featdbCreate", fn_featdb_create}, {"featdbDestroy", fn_featdb_destroy}, {"featdbCount", fn_featdb_count}, {"featdbAppendBatch", fn_featdb_append_batch},
+        {"featdbCopyRows", fn_featdb_copy_rows}, {"featdbRanges", fn_featdb_ranges}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

@@ -26,26 +26,23 @@ def _rows_2d(features, n_labels, what):
     return feat
 
 
-def prepare(features, labels, classes):
-    """The selection and balancing loop of neuralmodel.js:216-264.  features [n][53] (or 264 / 23 wide: the rows of level 11 / 12); labels: per row the label's value or None;
-    classes: the label's class list.  Rows whose label is one of `classes` are added in DB order; fewer than 10 of them is refused;
-    then each class with more than 3 and fewer than the largest count is topped up by cycling through the DB in order until it
-    reaches that count.  Returns dict(features, y, legend, in_min, in_max, counts, rows): y are indices into legend, which lists the
-    labels in order of first appearance (ml5's uniqueValues); in_min / in_max are taken over the balanced set, duplicates included
-    (ml5 normalizeData); rows are the DB indices in the order added."""
+def select(labels, classes):
+    """The label-only half of prepare: which DB rows train_nn adds, in which order (neuralmodel.js:216-264).  labels: per row the label's
+    value or None; classes: the label's class list.  Returns dict(rows, y, legend, counts) as prepare describes them; nothing here reads a
+    feature, so the same selection serves host rows (prepare) and a device DB (prepare_db)."""
     classes = [str(c) for c in classes]
     if "*" in classes:
         raise ValueError("the '*' wildcard class is not supported")
-    feat = _rows_2d(features, len(labels), "labels")
+    n = len(labels)
     cls = [classes.index(str(v)) if v is not None and str(v) in classes else -1 for v in labels]
     rows = [i for i, c in enumerate(cls) if c >= 0]
     count = [sum(1 for i in rows if cls[i] == c) for c in range(len(classes))]
     if len(rows) < 10:
-        raise ValueError(f"Sample size {len(rows)}/{len(feat)} too small for training")
+        raise ValueError(f"Sample size {len(rows)}/{n} too small for training")
     max_n = max(count)
     for c in range(len(classes)):
         while 3 < count[c] < max_n:
-            for i in range(len(feat)):
+            for i in range(n):
                 if cls[i] == c and count[c] < max_n:
                     rows.append(i); count[c] += 1
                 if count[c] >= max_n:
@@ -54,9 +51,37 @@ def prepare(features, labels, classes):
     for i in rows:
         if classes[cls[i]] not in legend:
             legend.append(classes[cls[i]])
-    x = feat[rows]
     y = np.array([legend.index(classes[cls[i]]) for i in rows], np.int32)
-    return dict(features=x, y=y, legend=legend, in_min=x.min(axis=0), in_max=x.max(axis=0), counts=count, rows=rows)
+    return dict(rows=rows, y=y, legend=legend, counts=count)
+
+
+def prepare(features, labels, classes):
+    """The selection and balancing loop of neuralmodel.js:216-264.  features [n][53] (or 264 / 23 wide: the rows of level 11 / 12); labels: per row the label's value or None;
+    classes: the label's class list.  Rows whose label is one of `classes` are added in DB order; fewer than 10 of them is refused;
+    then each class with more than 3 and fewer than the largest count is topped up by cycling through the DB in order until it
+    reaches that count.  Returns dict(features, y, legend, in_min, in_max, counts, rows): y are indices into legend, which lists the
+    labels in order of first appearance (ml5's uniqueValues); in_min / in_max are taken over the balanced set, duplicates included
+    (ml5 normalizeData); rows are the DB indices in the order added."""
+    if "*" in [str(c) for c in classes]:
+        raise ValueError("the '*' wildcard class is not supported")
+    feat = _rows_2d(features, len(labels), "labels")
+    sel = select(labels, classes)
+    x = feat[sel["rows"]]
+    return dict(features=x, y=sel["y"], legend=sel["legend"], in_min=x.min(axis=0), in_max=x.max(axis=0), counts=sel["counts"], rows=sel["rows"])
+
+
+def _db_data(db, n_labels, what, sel, stream):
+    """sel with the DB and the ranges of its selected rows in place of host features (wsa_featdb_ranges)"""
+    if n_labels != db.count:
+        raise ValueError(f"{n_labels} {what} for a device DB of {db.count} rows")
+    in_min, in_max = db.ranges(sel["rows"], stream)
+    return dict(sel, db=db, in_min=in_min, in_max=in_max)
+
+
+def prepare_db(db, labels, classes, stream=0):
+    """prepare over a featdb.DeviceDB: the same selection, the features left on the device.  Returns dict(db, rows, y, legend, in_min,
+    in_max, counts); train and train_many take it where they take prepare's."""
+    return _db_data(db, len(labels), "labels", select(labels, classes), stream)
 
 
 def glorot_init(units, seed):
@@ -102,20 +127,28 @@ def stack(layers, n_classes, n_inputs=nnmodel.NFEAT):
     return units, acts
 
 
+def _width(data):
+    """the row width of prepare's or prepare_db's data"""
+    return data["db"].width if "db" in data else np.shape(data["features"])[1]
+
+
 def _trainer(an, data, layers, learning_rate, epochs, batch_size, validation_split, seed, init, orders):
     """(capi.Trainer, orders) of train's arguments"""
-    units, acts = stack(layers or DEFAULT_LAYERS, len(data["legend"]), np.shape(data["features"])[1])
+    units, acts = stack(layers or DEFAULT_LAYERS, len(data["legend"]), _width(data))
     ks, bs = init if init is not None else glorot_init(units, seed)
-    n_train, n_val = split(len(data["features"]), validation_split)
+    n_train, n_val = split(len(data["rows"]) if "db" in data else len(data["features"]), validation_split)
     orders = orders if orders is not None else epoch_orders(n_train, epochs, seed + 1)
     spec = nnmodel.ModelSpec(units, acts, ks, bs, np.asarray(data["in_min"], np.float64), np.asarray(data["in_max"], np.float64), list(data["legend"]))
-    tr = an.trainer(spec, data["features"], data["y"], n_val, batch_size, learning_rate)
+    if "db" in data:
+        tr = data["db"].trainer(spec, data["rows"], data["y"], n_val, batch_size, learning_rate)
+    else:
+        tr = an.trainer(spec, data["features"], data["y"], n_val, batch_size, learning_rate)
     return tr, orders
 
 
 def train(an, data, layers=None, learning_rate=DEFAULT_LEARNING_RATE, epochs=10, batch_size=32, validation_split=0.1, seed=0,
           init=None, orders=None, on_epoch=None, stream=0):
-    """Trains on `an` (a capi.Analyzer) over data = prepare(...).  init: (kernels, biases) instead of glorot_init(units, seed); orders:
+    """Trains on `an` (a capi.Analyzer) over data = prepare(...) or prepare_db(...) (a DeviceDB of `an`; its rows stay on the device).  init: (kernels, biases) instead of glorot_init(units, seed); orders:
     one order per epoch instead of epoch_orders(n_train, epochs, seed + 1).  on_epoch(epoch, stats) mirrors ml5's whileTraining (it
     synchronises every epoch; without it only the last epoch is waited for).  Returns (nnmodel.ModelSpec, history)."""
     tr, orders = _trainer(an, data, layers, learning_rate, epochs, batch_size, validation_split, seed, init, orders)
@@ -133,14 +166,9 @@ def train(an, data, layers=None, learning_rate=DEFAULT_LEARNING_RATE, epochs=10,
         tr.close()
 
 
-def prepare_ordinal(features, values):
-    """The selection and balancing loop of neuralmodel.js:278-332 for an ordinal label (V, A or D).  features [n][53] (or 264 / 23 wide); values: per row
-    the label's value or None.  A row's bin is the first of (-inf, 0.25], (0.25, 0.5], (0.5, 0.75], (0.75, 1.0] that holds its value; rows
-    with None or a value above 1.0 are dropped; the others are added in DB order; fewer than 10 of them is refused; then, only when the
-    largest bin holds more than 3, each bin with more than 3 and fewer than the largest count is topped up by cycling through the DB in
-    order until it reaches that count.  Returns dict(features, values, in_min, in_max, out_min, out_max, counts, rows): the ranges are
-    taken over the balanced set, duplicates included (ml5 normalizeData); rows are the DB indices in the order added."""
-    feat = _rows_2d(features, len(values), "values")
+def select_ordinal(values):
+    """The label-only half of prepare_ordinal (neuralmodel.js:278-332): dict(rows, values, out_min, out_max, counts) as it describes them."""
+    n = len(values)
     nb = len(ORDINAL_RANGES)
 
     def bin_of(v):
@@ -155,19 +183,38 @@ def prepare_ordinal(features, values):
     rows = [i for i, b in enumerate(bins) if b >= 0]
     count = [sum(1 for i in rows if bins[i] == b) for b in range(nb)]
     if len(rows) < 10:
-        raise ValueError(f"Sample size {len(rows)}/{len(feat)} too small for training")
+        raise ValueError(f"Sample size {len(rows)}/{n} too small for training")
     max_n = max(count)
     if max_n > 3:
         for b in range(nb):
             while 3 < count[b] < max_n:
-                for i in range(len(feat)):
+                for i in range(n):
                     if bins[i] == b and count[b] < max_n:
                         rows.append(i); count[b] += 1
                     if count[b] >= max_n:
                         break
-    x = feat[rows]
     y = np.array([float(values[i]) for i in rows], np.float64)
-    return dict(features=x, values=y, in_min=x.min(axis=0), in_max=x.max(axis=0), out_min=float(y.min()), out_max=float(y.max()), counts=count, rows=rows)
+    return dict(rows=rows, values=y, out_min=float(y.min()), out_max=float(y.max()), counts=count)
+
+
+def prepare_ordinal(features, values):
+    """The selection and balancing loop of neuralmodel.js:278-332 for an ordinal label (V, A or D).  features [n][53] (or 264 / 23 wide); values: per row
+    the label's value or None.  A row's bin is the first of (-inf, 0.25], (0.25, 0.5], (0.5, 0.75], (0.75, 1.0] that holds its value; rows
+    with None or a value above 1.0 are dropped; the others are added in DB order; fewer than 10 of them is refused; then, only when the
+    largest bin holds more than 3, each bin with more than 3 and fewer than the largest count is topped up by cycling through the DB in
+    order until it reaches that count.  Returns dict(features, values, in_min, in_max, out_min, out_max, counts, rows): the ranges are
+    taken over the balanced set, duplicates included (ml5 normalizeData); rows are the DB indices in the order added."""
+    feat = _rows_2d(features, len(values), "values")
+    sel = select_ordinal(values)
+    x = feat[sel["rows"]]
+    return dict(features=x, values=sel["values"], in_min=x.min(axis=0), in_max=x.max(axis=0), out_min=sel["out_min"], out_max=sel["out_max"],
+                counts=sel["counts"], rows=sel["rows"])
+
+
+def prepare_ordinal_db(db, values, stream=0):
+    """prepare_ordinal over a featdb.DeviceDB: dict(db, rows, values, in_min, in_max, out_min, out_max, counts); train_regression and
+    train_many take it where they take prepare_ordinal's."""
+    return _db_data(db, len(values), "values", select_ordinal(values), stream)
 
 
 def stack_regression(layers, n_inputs=nnmodel.NFEAT):
@@ -186,13 +233,16 @@ def stack_regression(layers, n_inputs=nnmodel.NFEAT):
 
 def _regress_trainer(an, data, layers, learning_rate, epochs, batch_size, validation_split, seed, init, orders):
     """(capi.Trainer, orders) of train_regression's arguments"""
-    units, acts = stack_regression(layers or DEFAULT_LAYERS_ORDS, np.shape(data["features"])[1])
+    units, acts = stack_regression(layers or DEFAULT_LAYERS_ORDS, _width(data))
     ks, bs = init if init is not None else glorot_init(units, seed)
-    n_train, n_val = split(len(data["features"]), validation_split)
+    n_train, n_val = split(len(data["rows"]) if "db" in data else len(data["features"]), validation_split)
     orders = orders if orders is not None else epoch_orders(n_train, epochs, seed + 1)
     spec = nnmodel.ModelSpec(units, acts, ks, bs, np.asarray(data["in_min"], np.float64), np.asarray(data["in_max"], np.float64), [],
                              float(data["out_min"]), float(data["out_max"]))
-    tr = an.regress_trainer(spec, data["features"], data["values"], n_val, batch_size, learning_rate)
+    if "db" in data:
+        tr = data["db"].regress_trainer(spec, data["rows"], data["values"], n_val, batch_size, learning_rate)
+    else:
+        tr = an.regress_trainer(spec, data["features"], data["values"], n_val, batch_size, learning_rate)
     return tr, orders
 
 
