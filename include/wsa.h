@@ -1158,6 +1158,50 @@ wsa_status wsa_regress_trainer_create_db(wsa_ctx *ctx, const wsa_model_desc *ini
 wsa_status wsa_featdb_dbstats_create(wsa_ctx *ctx, const wsa_featdb *db, uint32_t first_row, uint32_t n_rows, const double *duration,
                                  uint32_t n_cat, const uint32_t *vocab, uint32_t n_ord, wsa_dbstats **out);
 
+/*
+ * ---- Live streams collect into the device DB (additions within version 5: probe for wsa_stream_set_featdb).
+ * The other half of the app's collecting: call_backed -> StoreFeatures files every callback, from a file or from the microphone
+ * (ref src/index.js:35-100, src/localstore.js:39-65).  Specification FD-2 of DESIGN.md §3, kernels in csrc/stream_featdb.hip.
+ * Attach (db != NULL) or detach (NULL) a feature DB: while attached, every step appends that step's rows to the DB as two kernels of the
+ * step — a plan kernel (keep rule, scan, capacity decision) and a copy kernel — on the step's own stream, behind the level's own
+ * kernels and before the epilogue; the step stays one graph launch.  What a step stores:
+ *   levels 5 and 13 (width 53): every row of the step;
+ *   level 12 (width 23): FD-1's rule on the step's row table (a callback's rows all arrive in one step), columns 0 .. 22;
+ *   level 11 (width 264): every stream owns ONE DB row per launch (the app files every utterance result under part 0, so each replaces
+ *            the one before): a stream's START forgets its row; a stream with results in the step takes the next new DB row if it has
+ *            none (new rows in stream order) and the LAST of its results of the step is written there.  Rows never move.
+ * Every column is the source's 64 bits.  Each step is decided alone before anything is written: a step whose flags carry
+ * WSA_FLAG_CAPACITY stores nothing; a step whose new rows do not fit the DB's capacity stores nothing at all (level 11: no replacement
+ * and no row handed out either; START still forgets), reports their number in not_fitted and sets WSA_FLAG_DB_FULL in the step's
+ * status_flags (not fatal).  A later step that fits is stored.
+ * The host owns the count: it hands wsa_featdb_count to every step before the launch and advances it when it reads the step's outcome,
+ * in wsa_stream_collect or at the start of the next step.  Between a collect and the next step every wsa_featdb_* entry, the DB
+ * trainers and wsa_featdb_dbstats_create work on an attached DB as on any; between a step and its collect they are refused with a
+ * message (wsa_featdb_count then tells the count before the step).  wsa_featdb_clear on an attached DB is always refused: detach, clear,
+ * attach.
+ * Synchronises the last step, allocates everything and drops the captured graph.  Refused with a message that names the values: a DB of
+ * another context; a width that does not go with the set's output_level (53: levels 5 / 13, 23: level 12, 264: level 11; levels 3, 4
+ * and 10 store nothing); a DB that is attached to another stream set.  Separate from the model, ensemble, KNN and regression
+ * attachments.  The DB must outlive its attachment (detach, or destroy the stream set, first).
+ */
+#define WSA_FLAG_DB_FULL 16u     /* streams: this step's new rows did not fit the attached feature DB; the step stored nothing (wsa_stream_db_rows) */
+wsa_status wsa_stream_set_featdb(wsa_stream *st, wsa_featdb *db);
+typedef struct {
+    uint32_t first_row;          /* the DB row of the step's first new row (the count before the step) */
+    uint32_t n_added;            /* new DB rows: first_row .. first_row + n_added - 1 */
+    uint32_t n_replaced;         /* level 11: DB rows rewritten in place */
+    uint32_t not_fitted;         /* the new rows of a step that stored nothing because they did not fit; else 0 */
+    const int32_t *kept;         /* [n_added]: the row of wsa_stream_rows (level 11: the utterance row) that became DB row first_row + i */
+    const int32_t *replaced;     /* [n_replaced][2] = {utterance row, DB row} (level 11; else NULL) */
+} wsa_stream_db_result;
+/* After wsa_stream_collect of the same step: host memory owned by the stream object, valid until the next step.
+ * WSA_ERR_INVALID without an attached DB. */
+wsa_status wsa_stream_db_rows(wsa_stream *st, wsa_stream_db_result *out);
+/* sizes of the step's DB kernels in rows: the plan kernel ballots rows_per_wave_tile rows per wave and walks the step's table
+ * rows_per_workgroup at a time; the copy kernel moves tiles of copy_tile_rows stored rows with a grid of at most copy_grid workgroups,
+ * fixed at attach (min(copy_grid, tiles of the step's row capacity)) */
+wsa_status wsa_stream_featdb_tile_info(int32_t *rows_per_wave_tile, int32_t *rows_per_workgroup, int32_t *copy_tile_rows, int32_t *copy_grid);
+
 #ifdef __cplusplus
 }
 #endif

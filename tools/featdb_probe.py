@@ -5,7 +5,15 @@ clock after its own warm-up:
   host    wsa_batch_copy_rows (metadata and features) followed by wsa_trainer_create on the copied rows — the code of the commit before
           the device feature DB, unchanged by it: the yardstick;
   device  wsa_featdb_append_batch, wsa_batch_copy_rows for the metadata alone, then wsa_trainer_create_db.
-Prints both times, the row count and the bytes each path moves over PCIe.  python tools/featdb_probe.py [--clips N] [--seconds S] [--reps R]"""
+Prints both times, the row count and the bytes each path moves over PCIe.  python tools/featdb_probe.py [--clips N] [--seconds S] [--reps R]
+
+--only stream (specification FD-2, profiles/stream_featdb.md): what collecting a live stream set's rows costs per step.  BASELINE config 5
+(512 streams x 48 kHz, one frame per step, level 13), one stream set in one process, `--rounds` rounds alternating
+  a       nothing attached                                   (wsa_stream_time_steps)
+  b       a device DB attached: the step stores its rows     (wsa_stream_time_steps)
+  a_loop  nothing attached, step + collect called from here  (the yardstick of c: the same loop without the append)
+  c       nothing attached, wsa_featdb_append_host of the collected rows after every step, inside the timed region
+and prints p50 / p99 of every round in microseconds.  [--streams N] [--steps K] [--rounds R]"""
 import argparse
 import os
 import sys
@@ -19,12 +27,78 @@ from webspeechanalyzer_amd import capi, nnmodel, train  # noqa: E402
 from webspeechanalyzer_amd.synth import synth_clips  # noqa: E402
 
 
+def stream_probe(args):
+    import ctypes
+    import torch
+    n, fs = args.streams, 48000
+    an = capi.Analyzer(capi.Config(output_level=13), device=0)
+    st = an.streams(n, fs, frames_per_step=1, max_span_frames=1024)
+    st.enable_graph(True)
+    sps = st.samples_per_step
+    loop = max(1, int(5 * fs) // sps)
+    feed = np.ascontiguousarray(synth_clips(n, loop * sps, fs=fs, seed=5, device="cuda").cpu().numpy().reshape(n, loop, sps).transpose(1, 0, 2))
+    db = an.device_db(53, (args.steps + args.warmup) * 256)
+    hin = st.host_input()
+    L, h = st.L, st.h
+    out = capi._StreamRows()
+    state = dict(k=0)
+
+    def timed(n_steps):
+        us, _ = st.time_steps(n_steps, feed)
+        return us
+
+    def loop_steps(n_steps, append):
+        us = np.zeros(n_steps)
+        for i in range(n_steps):
+            hin[:] = feed[state["k"] % loop]
+            state["k"] += 1
+            t0 = time.perf_counter()
+            rc = L.wsa_stream_step_host(h, None, None) or L.wsa_stream_collect(h, None, ctypes.byref(out))
+            if append and out.n_rows and not rc:
+                rc = L.wsa_featdb_append_host(db.h, out.row_feat, min(out.n_rows, 1024), None)
+            us[i] = (time.perf_counter() - t0) * 1e6
+            if rc:
+                an._check(rc)
+        return us
+
+    def variant(name):
+        db.clear()
+        if name == "b":
+            st.set_featdb(db)
+        run = (lambda k: timed(k)) if name in ("a", "b") else (lambda k: loop_steps(k, name == "c"))
+        run(args.warmup)                                 # the graph is captured again after an attach or a detach
+        us = run(args.steps)
+        rows = db.count
+        if name == "b":
+            st.set_featdb(None)
+        return float(np.percentile(us, 50)), float(np.percentile(us, 99)), rows
+
+    print(f"{n} streams x {fs} Hz, level 13, 1 frame per step, {args.steps} steps per round after {args.warmup} of warm-up; microseconds")
+    res = {v: [] for v in ("a", "b", "a_loop", "c")}
+    for r in range(args.rounds):
+        for v in res:
+            p50, p99, rows = variant(v)
+            res[v].append((p50, p99))
+            print(f"round {r} {v:7s} p50 {p50:8.1f}  p99 {p99:8.1f}  DB rows {rows}")
+    for v in res:
+        a = np.array(res[v])
+        print(f"{v:7s} p50 median {np.median(a[:, 0]):8.1f} (min {a[:, 0].min():.1f}, max {a[:, 0].max():.1f})   p99 median {np.median(a[:, 1]):8.1f} (min {a[:, 1].min():.1f}, max {a[:, 1].max():.1f})")
+    db.close(); st.close(); an.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--only", choices=["batch", "stream"], default="batch")
+    ap.add_argument("--streams", type=int, default=512)
+    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--warmup", type=int, default=200)
+    ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--clips", type=int, default=1024)
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--reps", type=int, default=50)
     args = ap.parse_args()
+    if args.only == "stream":
+        return stream_probe(args)
     import torch
     fs = 16000
     ns = int(args.seconds * fs)

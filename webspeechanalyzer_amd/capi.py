@@ -165,6 +165,11 @@ class _ValueHost(ctypes.Structure):
                 ("cb", ctypes.c_void_p)]
 
 
+class _StreamDbResult(ctypes.Structure):
+    _fields_ = [("first_row", ctypes.c_uint32), ("n_added", ctypes.c_uint32), ("n_replaced", ctypes.c_uint32), ("not_fitted", ctypes.c_uint32),
+                ("kept", ctypes.c_void_p), ("replaced", ctypes.c_void_p)]
+
+
 class _StreamValueResult(ctypes.Structure):
     _fields_ = [("n_rows", ctypes.c_uint32), ("n_heads", ctypes.c_uint32), ("n_callbacks", ctypes.c_uint32), ("n_streams", ctypes.c_uint32),
                 ("value", _VPH), ("cb", ctypes.c_void_p), ("cb_value", _VPH), ("cb_weight", _VPH),
@@ -225,7 +230,9 @@ ABI_SYMBOLS = ["wsa_config_default", "wsa_abi_version", "wsa_create", "wsa_destr
                # additions within version 5 (probe for wsa_featdb_create): the feature DB that stays on the device (K10, spec FD-1)
                "wsa_featdb_create", "wsa_featdb_destroy", "wsa_featdb_clear", "wsa_featdb_count", "wsa_featdb_append_batch", "wsa_featdb_append_host",
                "wsa_featdb_device_rows", "wsa_featdb_copy_rows", "wsa_featdb_gather", "wsa_featdb_ranges", "wsa_featdb_tile_info",
-               "wsa_trainer_create_db", "wsa_regress_trainer_create_db", "wsa_featdb_dbstats_create"]
+               "wsa_trainer_create_db", "wsa_regress_trainer_create_db", "wsa_featdb_dbstats_create",
+               # additions within version 5 (probe for wsa_stream_set_featdb): live streams collect into the device DB, inside the step (spec FD-2)
+               "wsa_stream_set_featdb", "wsa_stream_db_rows", "wsa_stream_featdb_tile_info"]
 CHANNEL_MIX = 0xFFFFFFFF                                # WSA_CHANNEL_MIX: the `select` word that takes the mono mix (spec PK-3); 'mix' in the Python entries
 PCM_F32, PCM_I16, PCM_MULAW, PCM_ALAW = 0, 1, 2, 3      # WSA_PCM_* of include/wsa.h
 PCM_U8, PCM_I24, PCM_I32, PCM_F64 = 8, 9, 10, 11        # ... the file encodings of spec PK-2 (batches and pcm_decode; 4 .. 7 are unassigned)
@@ -432,6 +439,9 @@ def lib():
     L.wsa_trainer_create_db.argtypes = [vp, ctypes.POINTER(_ModelDesc), vp, vp, vp, u32, u32, u32, dbl, ctypes.POINTER(vp)]
     L.wsa_regress_trainer_create_db.argtypes = [vp, ctypes.POINTER(_ModelDesc), vp, vp, vp, u32, u32, u32, dbl, dbl, dbl, ctypes.POINTER(vp)]
     L.wsa_featdb_dbstats_create.argtypes = [vp, vp, u32, u32, vp, u32, vp, u32, ctypes.POINTER(vp)]
+    L.wsa_stream_set_featdb.argtypes = [vp, vp]
+    L.wsa_stream_db_rows.argtypes = [vp, ctypes.POINTER(_StreamDbResult)]
+    L.wsa_stream_featdb_tile_info.argtypes = [ctypes.POINTER(i32)] * 4
     for name in ABI_SYMBOLS:
         if name in _U32_RESULT or name in ("wsa_resample_ready", "wsa_level_feature_count", "wsa_batch_packed_offset", "wsa_pcm_channels_tile_frames"):
             continue
@@ -1537,6 +1547,55 @@ def debug_featdb_append(db, level, meta, feat, clip_off=None, stream=0):
     return int(first.value), kept[:added.value].copy()
 
 
+def debug_featdb_copy_capacity(db):
+    """Test access (csrc/stream_featdb.hip wsa_debug_featdb_copy_capacity; not part of include/wsa.h): the DB's whole table
+    [capacity][width], the rows beyond its count included."""
+    L = lib()
+    L.wsa_debug_featdb_copy_capacity.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    L.wsa_debug_featdb_copy_capacity.restype = ctypes.c_int
+    out = np.zeros((db.capacity, db.width), np.float64)
+    db.an._check(L.wsa_debug_featdb_copy_capacity(db.h, out.ctypes.data))
+    return out
+
+
+def debug_stream_featdb_step(db, level, meta, feat, n_rows=None, flags=0, utt_off=None, bits=None, slot=None, rows_cap=None, stream=0):
+    """Test access to the stream step's DB kernels on hand-built tables (csrc/debug.hip wsa_debug_stream_featdb_step; not part of
+    include/wsa.h): meta [n][8] i32 (level 12; else None), feat [n][stride] f64, n_rows = the step's row-count word (None: n), flags = its
+    flags word, and at level 11 utt_off [n_streams + 1] u32, bits [n_streams] u32 (bit 0: START) and slot [n_streams] i32.  The tables are
+    uploaded with torch; the plan and the copy kernel run once.  Returns dict(first_row, n_added, n_replaced, not_fitted, kept, replaced,
+    slot = the slot table afterwards)."""
+    import torch
+    L = lib()
+    vp, i32, u32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32
+    L.wsa_debug_stream_featdb_step.argtypes = [vp, i32, vp, vp, u32, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp, u32]
+    L.wsa_debug_stream_featdb_step.restype = ctypes.c_int
+    dev = f"cuda:{db.an.device}"
+    feat = np.ascontiguousarray(feat, np.float64)
+    n, stride = feat.shape
+    up = lambda a: torch.from_numpy(a).to(dev)
+    t_feat = up(feat.view(np.int64)) if n else None
+    t_meta = None if meta is None or not n else up(np.ascontiguousarray(meta, np.int32).reshape(n, 8))
+    t_words = up(np.array([n if n_rows is None else n_rows, flags], np.uint32).view(np.int32))
+    n_streams, t_off, t_bits, t_slot = 0, None, None, None
+    if utt_off is not None:
+        off = np.ascontiguousarray(utt_off, np.uint32)
+        n_streams = len(off) - 1
+        t_off = up(off.view(np.int32))
+        t_bits = up(np.ascontiguousarray(bits, np.uint32).view(np.int32))
+        t_slot = up(np.ascontiguousarray(slot, np.int32).copy())
+    kept = np.zeros(max(n, n_streams, 1), np.int32)
+    rep = np.zeros((max(n_streams, 1), 2), np.int32)
+    out4 = np.zeros(4, np.uint32)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    torch.cuda.synchronize(dev)
+    db.an._check(L.wsa_debug_stream_featdb_step(db.h, int(level), ptr(t_meta), ptr(t_feat), stride, n if rows_cap is None else int(rows_cap), ptr(t_off), n_streams,
+                                                t_words.data_ptr(), t_words.data_ptr() + 4, ptr(t_bits), ptr(t_slot), stream, out4.ctypes.data,
+                                                kept.ctypes.data, len(kept), rep.ctypes.data, len(rep)))
+    torch.cuda.synchronize(dev)
+    return dict(first_row=int(out4[0]), n_added=int(out4[1]), n_replaced=int(out4[2]), not_fitted=int(out4[3]), kept=kept[:out4[1]].copy(),
+                replaced=rep[:out4[2]].copy() if utt_off is not None else None, slot=None if t_slot is None else t_slot.cpu().numpy())
+
+
 class KnnStore:
     """wsa_knn: the unit rows of an ml5 KNN classifier on the device (K9, spec KN-1).  Class indices are what the device sees;
     webspeechanalyzer_amd.knn maps labels to them."""
@@ -1931,6 +1990,32 @@ class Streams:
         return dict(value=per_head(r.value, n), cb=arr(r.cb, ctypes.c_int32, np.int32, (k, 4)), cb_value=per_head(r.cb_value, k),
                     cb_weight=per_head(r.cb_weight, k), stream_sum=per_head(r.stream_sum, ns), stream_weight=per_head(r.stream_weight, ns),
                     stream_value=per_head(r.stream_value, ns))
+
+    def set_featdb(self, db):
+        """Attach a FeatDB (every step appends its rows to it on the device, spec FD-2: two kernels of the step) or detach (None).  Stands
+        beside every other attachment; the next step recaptures the graph.  The DB's count advances at collect()."""
+        self.an._check(self.L.wsa_stream_set_featdb(self.h, db.h if db is not None else None))
+        self._featdb = db
+
+    @staticmethod
+    def featdb_tile_info():
+        """(rows per wave tile, rows per step of the plan kernel's walk, stored rows per copy tile, the copy kernel's largest grid)."""
+        v = [ctypes.c_int32() for _ in range(4)]
+        lib().wsa_stream_featdb_tile_info(*[ctypes.byref(x) for x in v])
+        return tuple(x.value for x in v)
+
+    def db_rows(self):
+        """After collect(): what the step stored in the attached DB, dict(first_row, n_added, n_replaced, not_fitted, kept [n_added] i32 =
+        the collected row (level 11: utterance row) behind DB row first_row + i, replaced [n_replaced, 2] i32 = {utterance row, DB row}
+        (level 11; else None))."""
+        r = _StreamDbResult()
+        self.an._check(self.L.wsa_stream_db_rows(self.h, ctypes.byref(r)))
+        na, nr = int(r.n_added), int(r.n_replaced)
+        kept = np.ctypeslib.as_array(ctypes.cast(r.kept, ctypes.POINTER(ctypes.c_int32)), shape=(na,)).copy() if na else np.zeros(0, np.int32)
+        rep = None
+        if r.replaced:
+            rep = np.ctypeslib.as_array(ctypes.cast(r.replaced, ctypes.POINTER(ctypes.c_int32)), shape=(nr, 2)).copy() if nr else np.zeros((0, 2), np.int32)
+        return dict(first_row=int(r.first_row), n_added=na, n_replaced=nr, not_fitted=int(r.not_fitted), kept=kept, replaced=rep)
 
     def set_ensemble(self, ensemble):
         """Attach an Ensemble (K6e on every step's rows; at level 13 one accumulator per stream and member and one running min_entropy_db

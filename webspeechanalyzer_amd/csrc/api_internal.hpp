@@ -88,6 +88,30 @@ void wsa_sreg_free(wsa_sreg* c);
 wsa_status wsa_sreg_enqueue(wsa_sreg* c, hipStream_t s);
 wsa_status wsa_sreg_result(wsa_sreg* c, uint32_t rows, wsa_stream_value_result* out);
 
+// ... and, beside all of those, the step's rows appended to a device feature DB (wsa_stream_set_featdb, spec FD-2; stream_featdb.hip)
+struct wsa_sfdb;
+struct wsa_sfdb_view {
+    wsa_ctx* ctx; int level; uint32_t n_streams;
+    uint32_t rows_cap;                                     // rows the source table can hold (level 11: utterance rows)
+    const int32_t* d_meta; const double* d_feat; uint32_t stride;      // the source table (level 11: the utterance rows, stride WSA_NUTT)
+    const uint32_t* d_utt_off;                             // level 11: [n_streams + 1] utterance-row offsets of the step
+    const uint32_t* d_n_rows;                              // device word: rows in the source table
+    const uint32_t *d_flags, *d_lost;                      // device words: bit 0 of *d_flags, or a nonzero *d_lost (may be NULL), is WSA_FLAG_CAPACITY
+    const uint32_t* d_bits;                                // per stream control word of the step (bit 0: START)
+    const void* owner;                                     // the stream set (a DB feeds one)
+};
+// checks the DB against the view (context, level / width, not attached elsewhere), allocates everything, marks the DB attached.
+// d_slot: level 11's slot table [n_streams] if the caller owns it (the test entry), NULL: allocated here, all -1
+wsa_status wsa_sfdb_create(const wsa_sfdb_view& v, wsa_featdb* db, int32_t* d_slot, wsa_sfdb** out);
+void wsa_sfdb_free(wsa_sfdb* c);                           // (the DB is attached to nothing afterwards, unless it was attached again meanwhile)
+void wsa_sfdb_begin_step(wsa_sfdb* c);                     // host side, the previous step done: settles it, hands the DB's count to the step about to be launched
+wsa_status wsa_sfdb_enqueue(wsa_sfdb* c, hipStream_t s);   // part of enqueue_step (captured): the plan and the copy kernel
+uint32_t wsa_sfdb_settle(wsa_sfdb* c);                     // the launched step is done: reads its outcome once, advances the DB's count; returns not_fitted
+wsa_status wsa_sfdb_result(wsa_sfdb* c, wsa_stream_db_result* out);
+extern "C" wsa_status wsa_sfdb_debug_step(wsa_featdb* db, int32_t level, const int32_t* d_meta, const double* d_feat, uint32_t feat_stride, uint32_t rows_cap,
+                                          const uint32_t* d_utt_off, uint32_t n_streams, const uint32_t* d_n_rows, const uint32_t* d_flags, const uint32_t* d_bits,
+                                          int32_t* d_slot, void* stream, uint32_t* out4, int32_t* kept, uint32_t kept_cap, int32_t* replaced, uint32_t replaced_cap);
+
 // classify.hip: NULL for the row width of an ML level (53, 264, 23), else the rest of the refusal after "the model takes N"
 const char* wsa_model_width_refusal(int n_inputs);
 

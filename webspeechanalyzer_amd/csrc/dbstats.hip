@@ -309,6 +309,7 @@ wsa_status wsa_featdb_dbstats_create(wsa_ctx* ctx, const wsa_featdb* src, uint32
     *out = nullptr;
     if (!src) return fail(ctx, WSA_ERR_INVALID, "null feature DB");
     if (src->ctx != ctx) return fail(ctx, WSA_ERR_INVALID, "the feature DB belongs to another context");
+    if (const std::string why = wsa_fd::pending_refusal(src, "wsa_featdb_dbstats_create"); !why.empty()) return fail(ctx, WSA_ERR_INVALID, why);
     if ((uint64_t)first_row + n_rows > src->count)
         return fail(ctx, WSA_ERR_INVALID, "rows " + std::to_string(first_row) + " .. " + std::to_string((uint64_t)first_row + n_rows) + " are outside the DB's "
                                           + std::to_string(src->count) + " rows");

@@ -244,6 +244,15 @@ extern "C" int wsa_debug_stream_step_backend(wsa_stream* st, const uint32_t* n_f
 //   from their step's first row); run_* [n_steps][H][n], as each step leaves them.
 // Every slot of cb_value / cb_weight / cb that no callback fills keeps what the caller put there.  Refused, nothing run and nothing written:
 // whatever would make a kernel read or write outside these tables.
+// Test access to the stream step's feature-DB kernels (spec FD-2; stream_featdb.hip has the body): the plan and the copy kernel once
+// over caller-given device tables, so that tests can place rows on the kernels' edges without speech that happens to land there
+extern "C" int wsa_debug_stream_featdb_step(wsa_featdb* db, int32_t level, const int32_t* d_meta, const double* d_feat, uint32_t feat_stride, uint32_t rows_cap,
+                                            const uint32_t* d_utt_off, uint32_t n_streams, const uint32_t* d_n_rows, const uint32_t* d_flags, const uint32_t* d_bits,
+                                            int32_t* d_slot, void* stream, uint32_t* out4, int32_t* kept, uint32_t kept_cap, int32_t* replaced, uint32_t replaced_cap) {
+    return wsa_sfdb_debug_step(db, level, d_meta, d_feat, feat_stride, rows_cap, d_utt_off, n_streams, d_n_rows, d_flags, d_bits, d_slot, stream, out4, kept, kept_cap,
+                               replaced, replaced_cap);
+}
+
 extern "C" int wsa_debug_regress_fold(int32_t device, const int32_t* meta, const double* values, uint32_t n_rows, uint32_t H, double step_s, uint32_t n,
                                       uint32_t n_steps, const uint32_t* row_off, const uint8_t* ctl, uint32_t cb_cap, uint32_t* n_cb, int32_t* cb,
                                       double* cb_value, double* cb_weight, double* run_sum, double* run_weight, double* run_value) {

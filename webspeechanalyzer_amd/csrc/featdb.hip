@@ -7,21 +7,18 @@
 #include <cstring>
 #include <string>
 #include "featdb_internal.hpp"
-#include "wave_ops.hpp"
+#include "featdb_keep.hpp"
 
 using wsa_api::fail;
 
 namespace {
 
-enum { FD_ALL = 0, FD_L12 = 1, FD_L11 = 2 };              // which rows are kept: all (levels 5 / 13: no kernel decides that), FD-1's level-12 rule, the last utterance row per clip
-constexpr int FD_WAVE = 64;                               // source rows one wave ballots
-constexpr int FD_WAVES = 16;
-constexpr int FD_WG = FD_WAVE * FD_WAVES;                 // source rows per step of the keep kernel's walk
+using wsa_fd::FD_ALL; using wsa_fd::FD_L12; using wsa_fd::FD_L11;
+using wsa_fd::FD_WAVE; using wsa_fd::FD_WG; using wsa_fd::FD_MARK_SLOT;      // (featdb_keep.hpp: source rows one wave ballots, rows per step of the keep kernel's walk)
 constexpr int FD_COPY_THREADS = 256;
 constexpr int FD_COPY_ROWS = 64;                          // appended rows per workgroup tile of the copy kernel
 constexpr int FD_COPY_GRID = 512;                         // its grid is capped here: FD_COPY_GRID * FD_COPY_ROWS rows per pass
 constexpr int FD_RANGE_ROWS = 256;                        // selected rows per chunk of the ranges kernel
-constexpr int FD_MARK_SLOT = 23;                          // level 12: the slot that marks a thrown uncmin
 
 struct FdKeep {
     int mode;                                             // FD_L12 or FD_L11
@@ -38,8 +35,8 @@ struct FdKeep {
 // that is open at the end of the step has been marked.  Level 12 takes a callback to be a RUN of rows with one (clip, si), which is what the
 // row table holds (it is in (clip, si) order); FD-1's "no earlier row of the same (clip, si) is marked" and this agree on such tables only.
 __global__ void __launch_bounds__(FD_WG) featdb_keep_kernel(FdKeep p) {
-    __shared__ uint32_t s_cnt[FD_WAVES], s_head[FD_WAVES], s_tail[FD_WAVES];
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ wsa_fd::KeepShared sh;
+    const int tid = (int)threadIdx.x;
     uint32_t base = 0;
     bool carry = false;
     for (uint64_t t0 = 0; t0 < p.n_items; t0 += FD_WG) {
@@ -51,40 +48,11 @@ __global__ void __launch_bounds__(FD_WG) featdb_keep_kernel(FdKeep p) {
             const uint32_t lo = valid ? p.off[r] : 0u, hi = valid ? p.off[r + 1] : 0u;
             keep = valid && hi > lo && hi <= p.n_src;
             src = hi - 1u;
-        } else {
-            bool mark = false, head = false;
-            if (valid) {
-                const uint64_t bits = p.feat[r * (uint64_t)p.stride + FD_MARK_SLOT];
-                mark = (bits << 1) != 0;                                      // anything but +0 and -0, NaN among it: the JS `!== 0`
-                head = r == 0 || p.meta[r * 8] != p.meta[(r - 1) * 8] || p.meta[r * 8 + 1] != p.meta[(r - 1) * 8 + 1];
-            }
-            const uint64_t mm = __ballot(mark), hm = __ballot(head);
-            const uint64_t le = wsa::lanemask_lt(lane) | (1ull << lane);
-            const uint64_t h = hm & le;                                       // the callbacks that start in this wave at or before this row
-            const uint64_t from = h ? (~0ull << (63 - __clzll((long long)h))) : ~0ull;
-            const bool local = (mm & le & from) != 0;                         // a mark between the row's callback start (or the wave's) and the row
-            if (lane == 0) {
-                const uint64_t tail = hm ? (~0ull << (63 - __clzll((long long)hm))) : ~0ull;
-                s_head[wave] = hm != 0; s_tail[wave] = (mm & tail) != 0;
-            }
-            __syncthreads();
-            bool c = carry, cend = carry;
-            for (int w = 0; w < FD_WAVES; w++) {
-                cend = s_head[w] ? s_tail[w] != 0 : (cend || s_tail[w] != 0);
-                if (w + 1 == wave) c = cend;
-            }
-            if (wave == 0) c = carry;
-            keep = valid && !(local || (h == 0 && c));
-            carry = cend;
-        }
-        const uint64_t km = __ballot(keep);
-        if (lane == 0) s_cnt[wave] = (uint32_t)__popcll(km);
-        __syncthreads();
-        uint32_t before = 0, tot = 0;
-        for (int w = 0; w < FD_WAVES; w++) { if (w < wave) before += s_cnt[w]; tot += s_cnt[w]; }
-        if (keep) p.kept[base + before + (uint32_t)__popcll(km & wsa::lanemask_lt(lane))] = src;
+        } else keep = wsa_fd::keep_l12(p.meta, p.feat, p.stride, r, valid, carry, sh);      // (the rule itself: featdb_keep.hpp)
+        uint32_t before, tot;
+        wsa_fd::scan_step(keep, sh, &before, &tot);
+        if (keep) p.kept[base + before] = src;
         base += tot;
-        __syncthreads();                                                      // the next step rewrites the shared words
     }
     if (tid == 0) { *p.total = base; __threadfence_system(); }
 }
@@ -159,13 +127,7 @@ void launch_copy(const FdCopy& c, hipStream_t s) {
     hipLaunchKernelGGL(featdb_copy_kernel, dim3(tiles < (uint32_t)FD_COPY_GRID ? tiles : (uint32_t)FD_COPY_GRID), dim3(FD_COPY_THREADS), 0, s, c);
 }
 
-// the level that goes with a width: the mode of the keep rule, or -1
-int mode_for(int level, int width) {
-    if ((level == 5 || level == 13) && width == WSA_NFEAT) return FD_ALL;
-    if (level == 12 && width == 23) return FD_L12;
-    if (level == 11 && width == WSA_NUTT) return FD_L11;
-    return -1;
-}
+using wsa_fd::mode_for;      // (featdb_internal.hpp: the level that goes with a width)
 
 struct Source { const int32_t* meta; const double* feat; uint32_t stride; const uint32_t* off; uint32_t n_src, n_clips; };
 
@@ -255,6 +217,9 @@ void wsa_featdb_destroy(wsa_featdb* db) {
 
 wsa_status wsa_featdb_clear(wsa_featdb* db) {
     if (!db) return WSA_ERR_INVALID;
+    if (db->attached_to)
+        return fail(db->ctx, WSA_ERR_INVALID, "wsa_featdb_clear on a feature DB that is attached to a stream set (" + std::to_string(db->count)
+                                              + " rows): detach it (wsa_stream_set_featdb with NULL), clear, attach again");
     db->count = 0;
     return WSA_OK;
 }
@@ -268,6 +233,7 @@ wsa_status wsa_featdb_count(const wsa_featdb* db, uint32_t* n_rows) {
 
 wsa_status wsa_featdb_append_batch(wsa_featdb* db, wsa_batch* batch, void* stream, uint32_t* first_row, uint32_t* n_added, int32_t* kept, uint32_t kept_cap) {
     if (!db) return WSA_ERR_INVALID;
+    if (const std::string why = wsa_fd::pending_refusal(db, "wsa_featdb_append_batch"); !why.empty()) return fail(db->ctx, WSA_ERR_INVALID, why);
     wsa_ctx* ctx = db->ctx;
     if (!batch) return fail(ctx, WSA_ERR_INVALID, "null batch");
     wsa_batch_view v{};
@@ -309,6 +275,7 @@ wsa_status wsa_debug_featdb_append(wsa_featdb* db, int32_t level, const int32_t*
 
 wsa_status wsa_featdb_append_host(wsa_featdb* db, const double* feat, uint32_t n, void* stream) {
     if (!db) return WSA_ERR_INVALID;
+    if (const std::string why = wsa_fd::pending_refusal(db, "wsa_featdb_append_host"); !why.empty()) return fail(db->ctx, WSA_ERR_INVALID, why);
     wsa_ctx* ctx = db->ctx;
     if (n && !feat) return fail(ctx, WSA_ERR_INVALID, "null feature pointer");
     if ((uint64_t)db->count + n > db->capacity)
@@ -332,6 +299,7 @@ wsa_status wsa_featdb_device_rows(const wsa_featdb* db, const double** d_feat) {
 
 wsa_status wsa_featdb_copy_rows(wsa_featdb* db, void* stream, uint32_t first, uint32_t n, double* out) {
     if (!db) return WSA_ERR_INVALID;
+    if (const std::string why = wsa_fd::pending_refusal(db, "wsa_featdb_copy_rows"); !why.empty()) return fail(db->ctx, WSA_ERR_INVALID, why);
     wsa_ctx* ctx = db->ctx;
     if ((uint64_t)first + n > db->count)
         return fail(ctx, WSA_ERR_INVALID, "rows " + std::to_string(first) + " .. " + std::to_string((uint64_t)first + n) + " are outside the DB's " + std::to_string(db->count) + " rows");
@@ -345,6 +313,7 @@ wsa_status wsa_featdb_copy_rows(wsa_featdb* db, void* stream, uint32_t first, ui
 
 wsa_status wsa_featdb_gather(wsa_featdb* db, const uint32_t* rows, uint32_t n, double* d_out, void* stream) {
     if (!db) return WSA_ERR_INVALID;
+    if (const std::string why = wsa_fd::pending_refusal(db, "wsa_featdb_gather"); !why.empty()) return fail(db->ctx, WSA_ERR_INVALID, why);
     wsa_ctx* ctx = db->ctx;
     if (n && (!rows || !d_out)) return fail(ctx, WSA_ERR_INVALID, "null row list / output pointer");
     const std::string why = wsa_fd::rows_refusal(db, rows, n);
@@ -363,6 +332,7 @@ wsa_status wsa_featdb_gather(wsa_featdb* db, const uint32_t* rows, uint32_t n, d
 
 wsa_status wsa_featdb_ranges(wsa_featdb* db, const uint32_t* rows, uint32_t n, void* stream, double* in_min, double* in_max) {
     if (!db) return WSA_ERR_INVALID;
+    if (const std::string why = wsa_fd::pending_refusal(db, "wsa_featdb_ranges"); !why.empty()) return fail(db->ctx, WSA_ERR_INVALID, why);
     wsa_ctx* ctx = db->ctx;
     if (!in_min || !in_max) return fail(ctx, WSA_ERR_INVALID, "null in_min / in_max");
     if (n == 0) return fail(ctx, WSA_ERR_INVALID, "ranges over no row");

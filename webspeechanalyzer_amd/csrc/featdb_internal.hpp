@@ -38,9 +38,30 @@ struct wsa_featdb {
     uint32_t* h_rows = nullptr; size_t h_rows_cap = 0;   // pinned staging of a row list
     hipEvent_t ev_rows = nullptr;                        // the copy that last read h_rows
     wsa::DevArena mem;
+    // FD-2: the stream set whose steps append to this DB (wsa_stream_set_featdb), and whether one of its steps has been launched whose
+    // outcome the host has not read yet — `count` is then behind the device, and whatever reads or moves it is refused
+    const void* attached_to = nullptr;
+    bool step_pending = false;
 };
 
 namespace wsa_fd {
+
+// which rows are kept: all (levels 5 / 13: no kernel decides that), the level-12 rule, the last utterance row per clip / stream
+enum { FD_ALL = 0, FD_L12 = 1, FD_L11 = 2 };
+// the level that goes with a width: the mode of the keep rule, or -1 (levels 3, 4 and 10 store nothing)
+inline int mode_for(int level, int width) {
+    if ((level == 5 || level == 13) && width == WSA_NFEAT) return FD_ALL;
+    if (level == 12 && width == 23) return FD_L12;
+    if (level == 11 && width == WSA_NUTT) return FD_L11;
+    return -1;
+}
+
+// "" or why `what` is refused on this DB right now (FD-2 "who owns the count")
+inline std::string pending_refusal(const wsa_featdb* db, const char* what) {
+    if (!db->step_pending) return "";
+    return std::string(what) + ": a stream step that appends to this feature DB (" + std::to_string(db->count) + " rows before it) has not been collected yet: "
+           "call wsa_stream_collect first";
+}
 
 // "" or why a row list over the DB is refused: the first entry outside its rows
 inline std::string rows_refusal(const wsa_featdb* db, const uint32_t* rows, uint32_t n) {

@@ -34,6 +34,7 @@ void wsa_stream_destroy(wsa_stream* b) {
     wsa_sens_free(b->sens);
     wsa_sknn_free(b->sknn);
     wsa_sreg_free(b->sreg);
+    wsa_sfdb_free(b->sfdb);
     delete b;                               // (the arena frees the rest)
 }
 

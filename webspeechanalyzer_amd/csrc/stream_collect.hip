@@ -1,5 +1,5 @@
 // stream_collect.hip — what a step left behind, handed to the caller: wsa_stream_collect with one gather per level, and the models a stream set
-// can have attached (classifier, ensemble, KNN store, regression group) with their per-step results.
+// can have attached (classifier, ensemble, KNN store, regression group, feature DB) with their per-step results.
 #include "stream_internal.hpp"
 
 using namespace wsa;
@@ -150,6 +150,8 @@ wsa_status wsa_stream_collect(wsa_stream* b, void* stream, wsa_stream_rows* o) {
     const uint32_t rows = b->h_totals[0], segs = b->h_totals[1];
     o->n_rows = rows; o->n_segments = segs; o->status_flags = (b->h_totals[3] & 1u) | (b->h_totals[2] ? 1u : 0u);
     o->row_meta = b->h_meta; o->row_feat = b->h_feat; o->segments = b->h_seg; o->stream_cuts = b->h_totals + 4;
+    // FD-2: the step's outcome for the attached feature DB is read here, once, and the DB's count advances
+    if (b->sfdb && wsa_sfdb_settle(b->sfdb)) o->status_flags |= WSA_FLAG_DB_FULL;
     // a span cut at the ring's capacity in this step is flagged for hosts that do not look at the per-stream counters
     if (b->seen_cuts.size() != b->n) b->seen_cuts.assign(b->n, 0u);
     for (uint32_t i = 0; i < b->n; i++) if (b->h_totals[4 + i] != b->seen_cuts[i]) { o->status_flags |= WSA_FLAG_STREAM_CUT; b->seen_cuts[i] = b->h_totals[4 + i]; }
@@ -185,6 +187,36 @@ wsa_status wsa_stream_set_knn(wsa_stream* b, const wsa_knn* kn, uint32_t k) {   
 wsa_status wsa_stream_set_regress(wsa_stream* b, const wsa_regress_group* g) {      // (a model, an ensemble and a KNN store stay attached)
     if (!b) return WSA_ERR_INVALID;
     return attach_state(b, &b->sreg, wsa_sreg_free, g != nullptr, [&](const wsa_scls_view& v, wsa_sreg** out) { return wsa_sreg_create(v, g, out); });
+}
+
+// (a model, an ensemble, a KNN store and a regression group stay attached; neither of them detaches the DB)
+wsa_status wsa_stream_set_featdb(wsa_stream* b, wsa_featdb* db) {
+    if (!b) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = b->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (b->stepped) HIP_TRY(ctx, hipStreamSynchronize(b->last_stream ? b->last_stream : b->own));     // the last step may still write the DB
+    if (b->sfdb) (void)wsa_sfdb_settle(b->sfdb);              // ... and its rows count
+    wsa_sfdb* n = nullptr;
+    if (db) {
+        const bool utt = ctx->cfg.output_level == 11;
+        const wsa_sfdb_view v{ctx, ctx->cfg.output_level, b->n, utt ? b->n * (uint32_t)b->be.seg_cap : b->rows_cap, b->be.d_meta, utt ? b->be.d_utt_feat : b->be.d_feat,
+                              utt ? (uint32_t)WSA_NUTT : (uint32_t)WSA_NFEAT, b->be.d_utt_off, b->be.d_totals + (utt ? 3 : 0), b->be.d_counters + 1, b->be.d_totals + 2,
+                              b->d_ctl + 2 * (size_t)b->n, b};
+        if (const wsa_status st = wsa_sfdb_create(v, db, nullptr, &n); st != WSA_OK) return st;
+    }
+    b->drop_graph();
+    wsa_sfdb_free(b->sfdb);
+    b->sfdb = n;
+    return WSA_OK;
+}
+wsa_status wsa_stream_db_rows(wsa_stream* b, wsa_stream_db_result* out) {
+    if (!b || !out) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = b->ctx;
+    if (!b->sfdb) return fail(ctx, WSA_ERR_INVALID, "no feature DB attached to these streams (wsa_stream_set_featdb)");
+    if (!b->stepped) return wsa_api::no_step_yet(b);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(b->last_stream ? b->last_stream : b->own));
+    return wsa_sfdb_result(b->sfdb, out);
 }
 
 wsa_status wsa_stream_classes(wsa_stream* b, wsa_stream_class_result* out) {

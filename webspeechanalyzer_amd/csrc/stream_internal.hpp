@@ -48,6 +48,7 @@ struct wsa_stream {
     wsa_sens* sens = nullptr;               // ... or the attached ensemble's (wsa_stream_set_ensemble); never both
     wsa_sknn* sknn = nullptr;               // the attached KNN store's tables, scratch and carried fold (wsa_stream_set_knn), beside either
     wsa_sreg* sreg = nullptr;               // the attached regression group's tables and carried sums (wsa_stream_set_regress), beside all of them
+    wsa_sfdb* sfdb = nullptr;               // the attached feature DB's plan tables, slots and push words (wsa_stream_set_featdb, spec FD-2), beside all of them
     uint32_t in_stride = 0, ctl_words = 3;  // floats per stream in the input buffers (a plain set: step_samples), control words per stream
     // a mixed set (wsa_stream_create_mixed): F above is the step's internal frame CAPACITY (resample_step_frames_bound), F_user the caller's frames_per_step
     bool mixed = false;

@@ -51,6 +51,9 @@ static wsa_status await_previous_step(wsa_stream* b, hipStream_t s) {
     b->last_stream = s;
     return WSA_OK;
 }
+// FD-2, behind await_previous_step: an attached feature DB reads the previous step's outcome if no collect did, and its count goes to the step about to
+// be launched through a mapped pinned word, like the control words
+static void hand_count_to_step(wsa_stream* b) { if (b->sfdb) wsa_sfdb_begin_step(b->sfdb); }
 // a stream's control byte (WSA_STREAM_*) -> the device control word's bits: 1 START, 2 STOP, 4 active in this step
 static uint32_t ctl_bits(uint32_t cb) { return (cb & WSA_STREAM_START ? 1u : 0u) | (cb & WSA_STREAM_STOP ? 2u : 0u) | (cb & WSA_STREAM_ACTIVE ? 4u : 0u); }
 // the control words to the device, counters cleared; then the streams' carried state reset where START says so
@@ -138,6 +141,8 @@ static wsa_status enqueue_backend(wsa_stream* b, hipStream_t s) {
     if (b->sknn) if (const wsa_status st = wsa_sknn_enqueue(b->sknn, s); st != WSA_OK) return st;
     // the grouped K6 over the regression heads, then the push / RG-1 fold kernel
     if (b->sreg) if (const wsa_status st = wsa_sreg_enqueue(b->sreg, s); st != WSA_OK) return st;
+    // FD-2: the plan and the copy kernel that append the step's rows to the attached feature DB
+    if (b->sfdb) if (const wsa_status st = wsa_sfdb_enqueue(b->sfdb, s); st != WSA_OK) return st;
     hipLaunchKernelGGL(stream_push_kernel, dim3(16), dim3(256), 0, s, b->be.d_totals, b->be.d_counters, b->be.d_meta, b->be.d_feat, b->be.d_seg,
                        b->h_totals_dev, b->h_meta_dev, b->h_feat_dev, b->h_seg_dev, b->d2h_rows, b->d2h_segs, b->d_state, b->n);
     HIP_TRY(ctx, hipGetLastError());
@@ -261,7 +266,13 @@ static wsa_status step_impl(wsa_stream* b, const float* d_pcm, uint64_t stride, 
     if (const wsa_status st = own_stream_for_null(b, &s); st != WSA_OK) return st;
     if (const wsa_status st = check_step_args(b, d_pcm, stride, host_in, n_in, ctl); st != WSA_OK) return st;
     if (const wsa_status st = await_previous_step(b, s); st != WSA_OK) return st;
-    if (b->mixed) { if (const wsa_status st = plan_mixed_step(b, n_in, ctl); st != WSA_OK) return st; }
+    hand_count_to_step(b);
+    if (b->mixed) {
+        if (const wsa_status st = plan_mixed_step(b, n_in, ctl); st != WSA_OK) {
+            if (b->sfdb) (void)wsa_sfdb_settle(b->sfdb);      // nothing was launched: the attached DB has no outcome to wait for
+            return st;
+        }
+    }
     else plan_plain_step(b, ctl);
     const wsa_status st = b->graph_on && b->steps >= 1 ? launch_step_graph(b, d_pcm, stride, host_in, s) : enqueue_step(b, d_pcm, stride, host_in, s);
     if (st != WSA_OK) return st;
@@ -318,6 +329,7 @@ wsa_status wsa_stream_step_backend_internal(wsa_stream* b, const uint32_t* n_fra
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (const wsa_status st = own_stream_for_null(b, &s); st != WSA_OK) return st;
     if (const wsa_status st = await_previous_step(b, s); st != WSA_OK) return st;
+    hand_count_to_step(b);
     for (uint32_t i = 0; i < n; i++) { b->h_ctl[i] = (ctl[i] & WSA_STREAM_ACTIVE) ? n_frames[i] : 0u; b->h_ctl[n + i] = 0; b->h_ctl[2 * n + i] = ctl_bits(ctl[i]); }
     // (the copy is ordered behind the previous step by the synchronize above, the launches below behind the copy by the stream)
     HIP_TRY(ctx, hipMemcpyAsync(b->d_spec, frames, (size_t)n * F * own_bands * sizeof(uint32_t), hipMemcpyHostToDevice, s));

@@ -244,6 +244,7 @@ wsa_status wsa_trainer_create_db(wsa_ctx* ctx, const wsa_model_desc* d, const ws
                                  uint32_t n_val, uint32_t batch_size, double learning_rate, wsa_trainer** out) {
     if (!db) return fail(ctx, WSA_ERR_INVALID, "null feature DB");
     if (db->ctx != ctx) return fail(ctx, WSA_ERR_INVALID, "the feature DB belongs to another context");
+    if (const std::string why = wsa_fd::pending_refusal(db, "wsa_trainer_create_db"); !why.empty()) return fail(ctx, WSA_ERR_INVALID, why);
     CreateArgs a{d, nullptr, label, nullptr, false, n_rows, n_val, batch_size, learning_rate, 0.0, 1.0};
     a.db = db; a.rows = rows;
     return trainer_create(ctx, a, out);
@@ -253,6 +254,7 @@ wsa_status wsa_regress_trainer_create_db(wsa_ctx* ctx, const wsa_model_desc* d, 
                                          uint32_t n_val, uint32_t batch_size, double learning_rate, double out_min, double out_max, wsa_trainer** out) {
     if (!db) return fail(ctx, WSA_ERR_INVALID, "null feature DB");
     if (db->ctx != ctx) return fail(ctx, WSA_ERR_INVALID, "the feature DB belongs to another context");
+    if (const std::string why = wsa_fd::pending_refusal(db, "wsa_regress_trainer_create_db"); !why.empty()) return fail(ctx, WSA_ERR_INVALID, why);
     CreateArgs a{d, nullptr, nullptr, target, true, n_rows, n_val, batch_size, learning_rate, out_min, out_max};
     a.db = db; a.rows = rows;
     return trainer_create(ctx, a, out);

@@ -1,13 +1,14 @@
-"""The feature DB that stays on the device: the host half of specification FD-1 (K10 is the device half, capi.FeatDB).
+"""The feature DB that stays on the device: the host half of specifications FD-1 and FD-2 (K10 and the stream step's DB
+kernels are the device half, capi.FeatDB).
 What the reference application does between analysing and learning: src/index.js:35-100 (call_backed -> StoreFeatures) files every
 callback's vectors under (db, file, part) — js/featuredb.js is this library's writer of the same format — and training, prediction, the
 results table and the KNN learner then read that DB.  Here the FEATURE columns never leave the GPU: a DeviceDB appends the rows of batch
-runs on the device and hands them to train.prepare_db / train, dbstats.predict_db and knn.Knn.add_db; everything that is a string — file
+runs (append) and of live streams' steps (attach / append_step: the step itself stores them, FD-2) on the device and hands them to train.prepare_db / train, dbstats.predict_db and knn.Knn.add_db; everything that is a string — file
 name, part tag, time, labels — is kept here, one record per stored row, in the shape of the app's rows without `features`.
 
-Not done here (DESIGN.md FD-1 "out of scope"): rows of live streams (they reach the host through pinned memory already: append_host takes
-them), replacing a stored identity in place (a file the DB already holds is refused, as the app skips it: src/index.js:277), label editing,
-a DB spread over several devices, '*' classes."""
+Not done here (DESIGN.md FD-1 / FD-2 "out of scope"): replacing a stored identity in place other than level 11's one row per stream
+launch (a file the DB already holds is refused, as the app skips it: src/index.js:277), label editing, a DB spread over several
+devices, '*' classes, a KNN store that grows by itself from the DB."""
 import numpy as np
 
 from . import capi
@@ -53,6 +54,59 @@ class DeviceDB(capi.FeatDB):
         self.step = float(analyzer.config["window_step"]) / 1e3
         self.records = []
         self.files = set()
+        self.streams, self.names, self.next_names = None, [], {}
+
+    def attach(self, streams, names):
+        """Every step of `streams` appends its rows to this DB on the device from now on (Streams.set_featdb, spec FD-2).  names: one
+        per stream, the "file" of that stream's current launch; a name the DB already holds is refused, as append refuses files."""
+        names = [str(f) for f in names]
+        if len(names) != streams.n:
+            raise ValueError(f"{len(names)} names for {streams.n} streams")
+        again = [f for f in names if f in self.files] or [f for i, f in enumerate(names) if f in names[:i]]
+        if again:
+            raise ValueError(f"the DB already holds {again[0]!r}")
+        streams.set_featdb(self)
+        self.streams, self.names, self.next_names = streams, names, {}
+        self.files.update(names)
+
+    def detach(self):
+        if self.streams is not None:
+            self.streams.set_featdb(None)
+        self.streams, self.names, self.next_names = None, [], {}
+
+    def rename(self, i, name):
+        """The name of stream i's NEXT launch: it takes effect in the step whose control byte carries START for it (append_step's ctl)."""
+        name = str(name)
+        if name in self.files:
+            raise ValueError(f"the DB already holds {name!r}")
+        if not 0 <= int(i) < len(self.names):
+            raise ValueError(f"stream {i} of {len(self.names)}")
+        self.files.discard(self.next_names.get(int(i)))
+        self.next_names[int(i)] = name
+        self.files.add(name)
+
+    def append_step(self, rows, ctl=None):
+        """After streams.collect(): rows is what it returned, ctl the control bytes the step was given (a stream with START takes the name
+        set by rename).  Turns the step's kept / replaced lists into host records, shaped as append's, and returns them; at level 11 a
+        replaced row's record is updated in place (and returned too)."""
+        if self.streams is None:
+            raise ValueError("append_step on a DB that is attached to no stream set")
+        for i, cb in enumerate(ctl if ctl is not None else []):
+            if int(cb) & 2 and i in self.next_names:         # WSA_STREAM_START
+                self.names[i] = self.next_names.pop(i)
+        d = self.streams.db_rows()
+        meta = rows["utt_meta"] if self.level == 11 else rows["meta"]
+        new = records(self.level, self.step, meta, d["kept"], self.names)
+        for i, r in enumerate(new):
+            r["row"] = d["first_row"] + i
+        self.records += new
+        out = list(new)
+        for u, row in (d["replaced"] if d["replaced"] is not None else []):
+            fresh = records(self.level, self.step, meta, [int(u)], self.names)[0]
+            old = next(r for r in self.records if r["row"] == int(row))
+            old.update(file=fresh["file"], seg=fresh["seg"], time=fresh["time"])
+            out.append(old)
+        return out
 
     def append(self, batch, files, stream=0):
         """Appends the batch's last run (one file name per clip) and returns the new records.  A file name the DB already holds is
@@ -84,8 +138,13 @@ class DeviceDB(capi.FeatDB):
         self.files.update(r["file"] for r in new)
         return new
 
+    def close(self):
+        if getattr(self, "streams", None) is not None and self.streams.h and self.h:      # the DB must outlive its attachment
+            self.detach()
+        super().close()
+
     def clear(self):
-        super().clear()
+        super().clear()                                  # (refused while attached: detach, clear, attach)
         self.records, self.files = [], set()
 
     def to_rows(self, stream=0):

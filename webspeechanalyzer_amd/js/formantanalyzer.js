@@ -1152,9 +1152,27 @@ function channel_select(select) {
 function decodePcm(format, typedArray, channels = 1, select = 0) {
   try { return addon().decodePcm(pcm_format(format), typedArray, channels, channel_select(select)); } catch (e) { throw (typeof e === 'string' ? e : String(e.message || e)); }
 }
-function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames_per_step = 1, max_span_frames = 1024, input_format = null) {
+// The eighth argument (optional) = {collect: db, names: [one per stream]}: every push appends the step's vectors to the device DB `db` (createDeviceDB)
+// on the GPU, inside the step (spec FD-2), by the app's storing rules; names[i] is the "file" of stream i's launch (default labels[i][0], as the
+// collector of js/featuredb.js takes it; handle.rename(i, name) names the launch its next START begins).  db.records grows per push as it does per
+// batch; at level 11 a launch owns one record, rewritten by every later result.  Without the argument the DB given to setCollectDB collects the sets
+// opened from then on.  The set then runs on the DB's context (a DB lives in one context): refused like setCollectDB with several devices or another
+// level.  db.count() and db.toFeatureDB() are for after handle.close(): the addon refuses them while the context has an open stream set.
+function stream_collect_db(opts, n_streams, labels) {
+  const db = opts && opts.collect ? opts.collect : (opts ? null : collect_db);
+  if (!db) return null;
+  live_device_db(db, 'StreamOpen');
+  if (several_devices()) throw several_devices_message();
+  if (db.level !== settings.output_level) throw 'StreamOpen: the DB holds the vectors of output_level ' + db.level + ', the streams run at ' + settings.output_level;
+  const names = opts && opts.names ? Array.from(opts.names, String) : Array.from({ length: n_streams }, (_, i) => (labels[i] || [])[0]);
+  if (names.length !== n_streams || names.some((f) => f === undefined)) throw 'StreamOpen: names holds one name per stream (' + n_streams + ' streams)';
+  names.forEach((f, i) => { if (db.files.has(f) || names.indexOf(f) < i) throw 'StreamOpen: the DB already holds ' + JSON.stringify(f); });
+  return { db, names };
+}
+function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames_per_step = 1, max_span_frames = 1024, input_format = null, collect = undefined) {
   const nat = addon();
   const level = settings.output_level, step = settings.window_step / 1e3;
+  const cdb = stream_collect_db(collect, n_streams, labels);
   if (![3, 4, 5, 10, 11, 12, 13].includes(level)) throw 'output_level ' + level + ' is not available for streams through this build (3, 4, 5, 10, 11, 12 and 13 are)';
   const per_stream = Array.isArray(sample_rate) || ArrayBuffer.isView(sample_rate);
   if (per_stream && sample_rate.length !== n_streams) throw 'sample_rate as an array holds one rate per stream (' + sample_rate.length + ' rates, ' + n_streams + ' streams)';
@@ -1164,7 +1182,7 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
   const fs_an = convert ? settings.resample_to : rates[0];      // the rate the analysis runs at (K0s converts inside the step)
   const pred = prediction && level === 13 ? prediction : null;
   const vp = value_prediction && level === 13 ? value_prediction : null;
-  const ctx = nat.create(native_config(), settings.device);
+  const ctx = cdb ? cdb.db.ctx : nat.create(native_config(), settings.device);      // a collecting set runs on its DB's context, which stays when the set closes
   let st;
   try {
     const g = nat.geometry(ctx, fs_an);
@@ -1191,11 +1209,15 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
     else if (pred && pred.models) nat.streamSetEnsemble(st, model_on(nat, ctx));
     else if (pred) nat.streamSetModel(st, model_on(nat, ctx));       // the native model on the stream's own context (ref src/index.js:56)
     if (vp) nat.streamSetRegress(st, ...value_heads_on(nat, ctx, vp));
+    if (cdb) { nat.streamSetFeatdb(st, cdb.db.native); cdb.names.forEach((f) => cdb.db.files.add(f)); }
   } catch (e) {
     if (st) nat.streamClose(st);
-    if (pred) forget_natives(pred, ctx);
-    if (vp) for (const h of vp.models) h.natives.delete(ctx);
-    nat.destroy(ctx); throw (typeof e === 'string' ? e : String(e.message || e));
+    if (!cdb) {
+      if (pred) forget_natives(pred, ctx);
+      if (vp) for (const h of vp.models) h.natives.delete(ctx);
+      nat.destroy(ctx);
+    }
+    throw (typeof e === 'string' ? e : String(e.message || e));
   }
   const packed = !!input_format && input_format.format !== undefined && input_format.format !== 'f32';
   const input = nat.streamInput(st);
@@ -1262,7 +1284,8 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
         }
       }
     }
-    const out = { rows, segments: res.segments.length / 4, cuts: res.cuts, cut: (res.flags & 8) !== 0 };   // cut: some stream's span reached max_span_frames in this step (WSA_FLAG_STREAM_CUT)
+    if (cdb) collect_step(res);
+    const out = { rows, segments: res.segments.length / 4, cuts: res.cuts, cut: (res.flags & 8) !== 0, dbFull: (res.flags & 16) !== 0 };   // dbFull: the step's vectors did not fit the collecting DB (WSA_FLAG_DB_FULL); cut: some stream's span reached max_span_frames in this step (WSA_FLAG_STREAM_CUT)
     if (pred && pred.knn) {
       if (res.knnStreamConf) meters = out.meters = Array.from({ length: n_streams }, (_, s) => meters_of({ nClasses: res.knnNClasses, clipConf: res.knnStreamConf }, s, names));
     } else if (pred && pred.models && res.ens && res.ens.cb) {
@@ -1276,8 +1299,31 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
     }
     return out;
   };
+  // FD-2's host half: the step's kept / replaced lists become the DB's records, shaped as collect_append shapes a batch's
+  const next_names = new Map();
+  const collect_step = (res) => {
+    const d = nat.streamDbRows(st), db = cdb.db;
+    const pos = new Uint32Array(res.meta.length / 8);
+    for (let q = 1; q < pos.length; q++) if (res.meta[q * 8] === res.meta[q * 8 - 8] && res.meta[q * 8 + 1] === res.meta[q * 8 - 7]) pos[q] = pos[q - 1] + 1;
+    const record = (src) => {
+      if (level === 11) { const m = res.uttMeta.subarray(src * 4, src * 4 + 4); return { file: cdb.names[m[0]], part: 0, time: [m[2] * step, (m[3] + 1) * step], truth: null, guess: null }; }
+      const m = res.meta.subarray(src * 8, src * 8 + 8);
+      if (level === 5) return { file: cdb.names[m[0]], part: m[1], time: [m[2] * step, (m[3] + 1) * step], truth: null, guess: null };
+      return { file: cdb.names[m[0]], part: m[1] + pos[src] / 100, time: [(m[2] * step).toFixed(3), ((m[3] + 1) * step).toFixed(3)], truth: null, guess: null };
+    };
+    if (d.first !== db.records.length && d.added) throw 'StreamOpen: the collecting DB holds ' + db.records.length + ' records, the step stored from row ' + d.first;
+    d.kept.forEach((src) => db.records.push(record(src)));
+    for (let q = 0; q < d.replaced; q++) Object.assign(db.records[d.replacedRows[2 * q + 1]], { time: record(d.replacedRows[2 * q]).time });
+  };
   const handle = {
     input, samplesPerStep: info ? info.samplesPerStep : input.length / n_streams, stopPending: false,
+    rename(i, name) {
+      if (!cdb) throw 'rename: this stream set collects into no device DB';
+      name = String(name);
+      if (cdb.db.files.has(name)) throw 'StreamOpen: the DB already holds ' + JSON.stringify(name);
+      if (next_names.has(i)) cdb.db.files.delete(next_names.get(i));
+      next_names.set(i, name); cdb.db.files.add(name);
+    },
     push(ctl = null, counts = null) {
       if (!open) throw 'stream closed';
       // StopAudioNodes (ref @B5699 -> disconnect_nodes @B21559): the frame in flight is still pushed, then every source is truncated
@@ -1286,6 +1332,7 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
       for (let i = 0; i < n_streams; i++) {
         c[i] = ctl ? ctl[i] : (STREAM_ACTIVE | (started ? 0 : STREAM_START));
         if (handle.stopPending && !stopped[i]) c[i] |= STREAM_STOP;
+        if ((c[i] & STREAM_START) && next_names.has(i)) { cdb.names[i] = next_names.get(i); next_names.delete(i); }
         if (c[i] & STREAM_START) { stopped[i] = 0; seg_seen[i] = 0; if (spred && spred.accs) spred.accs.delete(i); reg_accs.delete(i); }
         if (c[i] & STREAM_STOP) stopped[i] = 1;
       }
@@ -1305,10 +1352,12 @@ function StreamOpen(n_streams, sample_rate, callback = null, labels = [], frames
         out = deliver(nat.streamStep(st, c));
       }
       open = false; open_streams.delete(handle);
-      nat.streamClose(st);                             // detaches `input`: the pinned buffer is gone; releases the model
-      if (pred) forget_natives(pred, ctx);              // the native models go with the stream's context
-      if (vp) for (const h of vp.models) h.natives.delete(ctx);
-      nat.destroy(ctx);
+      nat.streamClose(st);                             // detaches `input`: the pinned buffer is gone; releases the model; the collecting DB is attached to nothing
+      if (!cdb) {
+        if (pred) forget_natives(pred, ctx);            // the native models go with the stream's context
+        if (vp) for (const h of vp.models) h.natives.delete(ctx);
+        nat.destroy(ctx);
+      }
       return out;
     },
   };

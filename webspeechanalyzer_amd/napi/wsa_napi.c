@@ -38,6 +38,8 @@
  *   streamSetKnn(stream, knn | null, k)         (wsa_stream_set_knn: streamStep results gain knnLabel, knnConf, knnCb, knnCbLabel, knnCbConf, knnStreamConf, knnNClasses;
  *                                                beside a model or an ensemble, not in place of one)
  *   streamSetModel(stream, model | null)        (wsa_stream_set_model: streamStep results gain prob, cb, cbLabel, cbConf, streamConf, nClasses)
+ *   streamSetFeatdb(stream, db | null)          (wsa_stream_set_featdb, specification FD-2: every streamStep appends its rows to the device DB; flags gain WSA_FLAG_DB_FULL)
+ *   streamDbRows(stream) -> {first, added, replaced, notFitted, kept, replacedRows}      (wsa_stream_db_rows of the last streamStep)
  *   streamClose(stream)
  * Rejections carry the library's error string.  No compute happens in this file.
  */
@@ -1727,6 +1729,41 @@ static napi_value fn_featdb_append_batch(napi_env env, napi_callback_info info) 
     free(kept);
     return out;
 }
+/* ---- live streams collect into the device DB (wsa_stream_set_featdb, specification FD-2).
+ *   streamSetFeatdb(stream, db | null): every streamStep of the stream object appends its rows to the DB on the device; the DB must be of the
+ *     stream's context and outlive the stream object (featdbDestroy refuses while the context has open streams)
+ *   streamDbRows(stream) -> {first, added, replaced, notFitted, kept: Int32Array, replacedRows: Int32Array [replaced][2]} of the last streamStep */
+static napi_value fn_stream_set_featdb(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    stream_t *h = argc ? get_stream(env, argv[0]) : NULL;
+    if (!h || !h->st || argc < 2) { napi_throw_type_error(env, NULL, "streamSetFeatdb(stream, db | null)"); return NULL; }
+    fdb_box *fb = NULL;
+    napi_valuetype t;
+    NAPI_OK(env, napi_typeof(env, argv[1], &t));
+    if (t != napi_null && t != napi_undefined) {
+        fb = get_fdb(env, argv[1]);
+        if (!fb || !fb->db || !fb->owner) { napi_throw_error(env, NULL, "streamSetFeatdb: the device DB was destroyed (or is not a device DB)"); return NULL; }
+        if (fb->owner != h->box) { napi_throw_error(env, NULL, "streamSetFeatdb: the device DB belongs to another context"); return NULL; }
+    }
+    if (wsa_stream_set_featdb(h->st, fb ? fb->db : NULL) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(h->ctx)); return NULL; }
+    return NULL;
+}
+static napi_value fn_stream_db_rows(napi_env env, napi_callback_info info) {
+    size_t argc = 1; napi_value argv[1];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    stream_t *h = argc ? get_stream(env, argv[0]) : NULL;
+    if (!h || !h->st) { napi_throw_type_error(env, NULL, "streamDbRows(stream)"); return NULL; }
+    wsa_stream_db_result r;
+    if (wsa_stream_db_rows(h->st, &r) != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(h->ctx)); return NULL; }
+    napi_value out = NULL, v;
+    NAPI_OK(env, napi_create_object(env, &out));
+    const struct { const char *name; uint32_t val; } words[] = {{"first", r.first_row}, {"added", r.n_added}, {"replaced", r.n_replaced}, {"notFitted", r.not_fitted}};
+    for (size_t i = 0; i < 4; i++) { NAPI_OK(env, napi_create_uint32(env, words[i].val, &v)); napi_set_named_property(env, out, words[i].name, v); }
+    napi_set_named_property(env, out, "kept", make_typed(env, napi_int32_array, r.kept, r.n_added, 4));
+    napi_set_named_property(env, out, "replacedRows", make_typed(env, napi_int32_array, r.replaced, r.replaced ? 2 * (size_t)r.n_replaced : 0, 4));
+    return out;
+}
 static napi_value fn_featdb_copy_rows(napi_env env, napi_callback_info info) {
     size_t argc = 1; napi_value argv[1];
     NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -2050,7 +2087,7 @@ NAPI_MODULE_INIT() {
         {"knnCreate", fn_knn_create}, {"knnDestroy", fn_knn_destroy}, {"knnAdd", fn_knn_add}, {"knnClassify", fn_knn_classify}, {"batchKnn", fn_batch_knn}, {"batchKnnFold", fn_batch_knn_fold},
         {"streamSetRegress", fn_stream_set_regress}, {"batchRegressGroup", fn_batch_regress_group},
         {"featdbCreate", fn_featdb_create}, {"featdbDestroy", fn_featdb_destroy}, {"featdbCount", fn_featdb_count}, {"featdbAppendBatch", fn_featdb_append_batch},
-        {"featdbCopyRows", fn_featdb_copy_rows}, {"featdbRanges", fn_featdb_ranges}};
+        {"featdbCopyRows", fn_featdb_copy_rows}, {"featdbRanges", fn_featdb_ranges}, {"streamSetFeatdb", fn_stream_set_featdb}, {"streamDbRows", fn_stream_db_rows}};
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;
         if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;
