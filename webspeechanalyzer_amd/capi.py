@@ -2340,6 +2340,38 @@ def debug_peaks(spec, mode, device=0):
                 flags=int(flags[0]), hdr=hdr, ent=ent)
 
 
+def debug_resample(clips, fs_in, fs_out, form=0, S=0, J=0, chunks=0, offset_bytes=0, stride_in=None, stride_out=None, pad_bits=0, sentinel=0x7fa5c3d1, device=0):
+    """Test access to the batch rate converter K0 on its own (csrc/debug.hip wsa_debug_resample; not part of include/wsa.h), no front end behind it.
+    clips = float32 arrays, fs_in one rate or one per clip.  form 0: resample_kernel (one rate; S, J, chunks override the launch shape as WSA_RS_S / _J / _C do),
+    1: resample_mixed_kernel with one launch per rate class, 2: with one launch over the whole work list.  The device copy starts offset_bytes (0, 4, 8, 12)
+    behind a 16-byte boundary; pad_bits is the bit pattern of everything around the clips' samples: behind each clip inside its row of stride_in samples, the
+    whole row of an empty clip, the words in front of and behind the copy.  Returns out [n, stride_out] as the kernel left rows that started as the
+    `sentinel` bit pattern, n_out [n], plan [classes, 6] = {S, J, span, block, lds bytes, copy} per rate class and the launch's block and lds.  Raises WsaError
+    on a refusal (status 1: overrides that cannot launch)."""
+    L = lib()
+    vp, i32, u32, u64, dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double
+    L.wsa_debug_resample.argtypes = [i32, vp, u32, u64, u32, u32, vp, vp, dbl, i32, i32, i32, i32, vp, u64, vp, vp, u32, vp]
+    L.wsa_debug_resample.restype = ctypes.c_int
+    n = len(clips)
+    rates = np.ascontiguousarray(np.broadcast_to(np.asarray(fs_in, np.float64), (n,)))
+    n_in = np.array([len(c) for c in clips], np.uint32)
+    stride_in = int(stride_in or max(int(n_in.max()), 1))
+    buf = np.full((n, stride_in), pad_bits, np.uint32)
+    for i, c in enumerate(clips):
+        buf[i, :len(c)] = np.ascontiguousarray(c, np.float32).view(np.uint32)
+    longest = max(int(L.wsa_resample_length(int(k), float(r), float(fs_out))) for k, r in zip(n_in, rates))
+    stride_out = int(stride_out or longest + 8)
+    out = np.full((n, stride_out), sentinel, np.uint32)
+    n_out = np.zeros(n, np.uint32)
+    plan = np.zeros((max(n, 1), 6), np.int32)
+    shape3 = np.zeros(3, np.uint32)
+    rc = L.wsa_debug_resample(device, buf.ctypes.data, n, stride_in, offset_bytes, pad_bits, n_in.ctypes.data, rates.ctypes.data, float(fs_out), form, S, J, chunks,
+                              out.ctypes.data, stride_out, n_out.ctypes.data, plan.ctypes.data, len(plan), shape3.ctypes.data)
+    if rc != 0:
+        raise WsaError(f"wsa_debug_resample: error {rc}")
+    return dict(out=out.view(np.float32), n_out=n_out, plan=plan[:int(shape3[0])].copy(), block=int(shape3[1]), lds=int(shape3[2]))
+
+
 def debug_fe_choice(analyzer, fs):
     """Test access (csrc/debug.hip wsa_debug_fe_choice; not part of include/wsa.h): the name of the K1 instantiation the analyzer's settings select at the
     sample rate fs, as profiles/frontend_split.md writes it, e.g. 'fe_kernel_r8<4,5,8,true,4,3>'.  Plans on the host; launches nothing."""

@@ -109,8 +109,8 @@ wsa_status wsa_api::run_impl(wsa_batch* b, const float* d_pcm, uint64_t stride, 
             d_pcm = b->d_rs_pcm; stride = b->rs_stride;
         } else if (b->rs_on) {               // K0: the caller's PCM (fs_in) -> the batch's own buffer at the analysis rate
             RsParams r; r.in = d_pcm; r.stride_in = stride; r.out = b->d_rs_pcm; r.stride_out = b->rs_stride;
-            r.n_in = b->d_rs_n_in; r.n_out = b->d_rs_n_out; r.table = b->d_rs_table; r.ratio = b->fs_in / b->fs; r.S = b->tune.rs_s > 0 ? b->tune.rs_s : resample_stride(b->fs_in, b->fs);
-            r.J = b->tune.rs_j > 0 ? b->tune.rs_j : resample_outputs_per_lane(r.S, r.ratio); r.span = resample_span(r.ratio, r.S, r.J); r.chunks = b->tune.rs_c > 0 ? b->tune.rs_c : 1;       // (more runs per block never won: tools/resample_sweep.sh)
+            r.n_in = b->d_rs_n_in; r.n_out = b->d_rs_n_out; r.table = b->d_rs_table;
+            resample_shape(b->fs_in, b->fs, b->tune.rs_s, b->tune.rs_j, b->tune.rs_c, r);
             launch_resample(r, b->n_clips, b->max_samples, s);
             HIP_TRY(ctx, hipGetLastError());
             d_pcm = b->d_rs_pcm; stride = b->rs_stride;

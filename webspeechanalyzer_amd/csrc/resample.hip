@@ -353,16 +353,23 @@ int resample_stride(double fs_in, double fs_out) {
     return 256;
 }
 
-void launch_resample(const RsParams& p, uint32_t n_clips, uint64_t max_out, hipStream_t s) {
-    if (n_clips == 0 || max_out == 0) return;
-    const size_t lds = sizeof(float) * ((size_t)2 * RS_OFFS * RS_KSTRIDE + (size_t)rs_xlen(p.span));
-    const uint64_t per_block = (uint64_t)p.S * (uint64_t)p.J * (uint64_t)p.chunks;
-    const dim3 grid((unsigned)((max_out + per_block - 1) / per_block), n_clips), block((unsigned)((p.S + 63) / 64 * 64));
-    hipLaunchKernelGGL(resample_kernel, grid, block, lds, s, p);
-}
-
 int resample_outputs_per_lane(int S, double ratio) { return rs_j(S, ratio); }
 int resample_span(double ratio, int S, int J) { return (int)std::ceil((double)(S * J - 1) * ratio) + RS_TAPS + 2; }
+
+// The single-rate launch's shape: ratio, S, J, span and runs per block — each override where it is positive (WSA_RS_S / WSA_RS_J / WSA_RS_C), else the default
+void resample_shape(double fs_in, double fs_out, int S, int J, int chunks, RsParams& p) {
+    p.ratio = fs_in / fs_out; p.S = S > 0 ? S : resample_stride(fs_in, fs_out);
+    p.J = J > 0 ? J : rs_j(p.S, p.ratio); p.span = resample_span(p.ratio, p.S, p.J); p.chunks = chunks > 0 ? chunks : 1;       // (more runs per block never won: tools/resample_sweep.sh)
+}
+uint32_t resample_block(const RsParams& p) { return (uint32_t)((p.S + 63) / 64 * 64); }
+size_t resample_lds(const RsParams& p) { return sizeof(float) * ((size_t)2 * RS_OFFS * RS_KSTRIDE + (size_t)rs_xlen(p.span)); }
+
+void launch_resample(const RsParams& p, uint32_t n_clips, uint64_t max_out, hipStream_t s) {
+    if (n_clips == 0 || max_out == 0) return;
+    const uint64_t per_block = (uint64_t)p.S * (uint64_t)p.J * (uint64_t)p.chunks;
+    const dim3 grid((unsigned)((max_out + per_block - 1) / per_block), n_clips), block(resample_block(p));
+    hipLaunchKernelGGL(resample_kernel, grid, block, resample_lds(p), s, p);
+}
 
 // The rate classes of a mixed batch (the distinct fs_in, in order of first appearance) and the work list: per class every clip's blocks, clip by clip.
 bool plan_resample_mixed(uint32_t n_clips, const uint32_t* n_out, const double* fs_in, double fs_out, RsMixedPlan& P, std::string& err) {

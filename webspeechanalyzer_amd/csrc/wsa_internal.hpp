@@ -236,6 +236,9 @@ uint64_t resample_length(uint64_t n_in, double fs_in, double fs_out);
 int resample_stride(double fs_in, double fs_out);
 int resample_span(double ratio, int S, int J);
 int resample_outputs_per_lane(int S, double ratio);
+void resample_shape(double fs_in, double fs_out, int S, int J, int chunks, RsParams& p);      // ratio, S, J, span, chunks of a single-rate launch; S, J, chunks > 0 override the defaults
+uint32_t resample_block(const RsParams& p);                                                    // lanes per block and dynamic LDS bytes of that launch
+size_t resample_lds(const RsParams& p);
 void launch_resample(const RsParams& p, uint32_t n_clips, uint64_t max_out, hipStream_t s);
 // K0 for clips of different rates (wsa_batch_create_mixed): one rate class per distinct fs_in, each with the table, S, J and span the single-rate
 // launch would choose for it (copy: fs_in == fs_out, the samples pass unfiltered), and a plan-time work list of one entry per block, sorted by class.
