@@ -318,7 +318,14 @@ void       wsa_stream_destroy(wsa_stream *st);
 uint32_t   wsa_stream_samples_per_step(const wsa_stream *st);        /* frames_per_step * hop */
 
 /* One step on device-resident PCM: stream i's new samples at d_pcm + i * stream_stride.  ctl = host array
- * of n_streams control bytes (WSA_STREAM_*), or NULL: START|ACTIVE on the first step, ACTIVE afterwards. */
+ * of n_streams control bytes (WSA_STREAM_*), or NULL: START|ACTIVE on the first step, ACTIVE afterwards.
+ * A launch's signal is the concatenation of the samples the stream was handed in its ACTIVE steps since its START.  A step without
+ * WSA_STREAM_ACTIVE is a step in which no time passes for that stream: its row is not read (it may hold anything), its carried samples and
+ * its analysis state stay as they are, and the next ACTIVE step continues the signal where the last one ended, however many steps lie
+ * between.  WSA_STREAM_START needs no WSA_STREAM_STOP before it: a START while a launch is live, even one whose first frames have not yet
+ * been delivered, drops that launch where it stands (its open segment is not reported) and begins a new one whose frames see none of the
+ * earlier samples.  With overlapping windows (q = ceil(win / hop) > 1) frame k of a launch, samples [k hop, k hop + win), is analysed in the
+ * step that brings the launch to (k + q) hop samples, so the first q - 1 frame slots after a START stay empty. */
 wsa_status wsa_stream_step(wsa_stream *st, const float *d_pcm, uint64_t stream_stride, const uint8_t *ctl, void *stream);
 /* Same with the samples in the stream object's own pinned host buffer ([n_streams][samples_per_step]
  * floats): fill it, call this; the H2D copy is part of the step (and of its graph).  The device reads the buffer while the

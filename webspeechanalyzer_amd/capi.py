@@ -2398,6 +2398,19 @@ def debug_stream_spectra(streams, bands):
     return out
 
 
+def debug_stream_ctl(streams):
+    """Test access (csrc/debug.hip wsa_debug_stream_ctl; not part of include/wsa.h): the device control words of a plain stream set's last step,
+    [3, n_streams] uint32 = nfr, off (samples), bits (1 START, 2 STOP, 4 active); call behind collect().  A mixed-rate set is refused."""
+    L = lib()
+    L.wsa_debug_stream_ctl.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
+    L.wsa_debug_stream_ctl.restype = ctypes.c_int
+    out = np.zeros((3, streams.n), np.uint32)
+    rc = L.wsa_debug_stream_ctl(streams.h, out.ctypes.data, out.size)
+    if rc != 0:
+        raise WsaError(f"wsa_debug_stream_ctl: error {rc}" + (" (a mixed-rate set has no plain control words)" if streams.mixed else ""))
+    return out
+
+
 def debug_stream_step_backend(streams, n_frames, ctl, frames, stream=0, bands=None):
     """Test access (csrc/debug.hip wsa_debug_stream_step_backend; not part of include/wsa.h): one step of a plain stream set past the front end.  frames
     [n_streams, frames_per_step, bands] u32 (stream i's first n_frames[i] frames count), n_frames [n] u32 (0 .. frames_per_step), ctl [n] u8

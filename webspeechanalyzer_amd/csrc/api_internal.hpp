@@ -49,6 +49,8 @@ wsa_status wsa_batch_fetch_internal(wsa_batch* b, hipStream_t s);
 const uint32_t* wsa_batch_counters_internal(wsa_batch* b, int keep, wsa_ctx** ctx);
 // debug.hip (wsa_debug_stream_spectra): the u32 frames of a stream set's last step on the device, [n_streams][frames_per_step][bands]
 const uint32_t* wsa_stream_spec_internal(wsa_stream* b, wsa_ctx** ctx, uint32_t* n_streams, uint32_t* frames_per_step, uint32_t* bands);
+// debug.hip (wsa_debug_stream_ctl): the device control words of a stream set's last step, word w of stream s at [w * n_streams + s]
+const uint32_t* wsa_stream_ctl_internal(wsa_stream* b, wsa_ctx** ctx, uint32_t* n_streams, int* mixed);
 // debug.hip (wsa_debug_stream_step_backend): one step of a plain stream set from hand-built u32 frames, the product's back-end launches behind them
 wsa_status wsa_stream_step_backend_internal(wsa_stream* b, const uint32_t* n_frames, const uint8_t* ctl, const uint32_t* frames, uint32_t bands, void* stream);
 void wsa_model_info_internal(const wsa_model* m, wsa_ctx** ctx, int* n_classes, int* softmax);   // classify.hip, for dbstats.hip (K8)

@@ -223,6 +223,18 @@ extern "C" int wsa_debug_stream_spectra(wsa_stream* st, uint32_t* out, uint64_t 
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, d, words * 4, hipMemcpyDeviceToHost) != hipSuccess) return WSA_ERR_HIP;
     return WSA_OK;
 }
+// the control words the last step of a PLAIN stream set ran under, as the step's prologue left them on the device: out [3][n_streams] = nfr (frames of
+// the stream in the step), off (samples its first frame lies behind the start of its row: the skipped warm-up frames times hop), bits (1 START, 2 STOP,
+// 4 active); call behind collect.  A mixed-rate set is refused: its step has other words (RS_CTL_*), planned and tested in tests/stream_resample_model.py
+extern "C" int wsa_debug_stream_ctl(wsa_stream* st, uint32_t* out, uint64_t cap_words) {
+    if (!st || !out) return WSA_ERR_INVALID;
+    wsa_ctx* ctx = nullptr; uint32_t n = 0; int mixed = 0;
+    const uint32_t* d = wsa_stream_ctl_internal(st, &ctx, &n, &mixed);
+    if (!ctx || !d || mixed || cap_words < 3ull * n) return WSA_ERR_INVALID;
+    if (hipSetDevice(ctx->device) != hipSuccess) return WSA_ERR_NO_DEVICE;
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, d, 3ull * n * 4, hipMemcpyDeviceToHost) != hipSuccess) return WSA_ERR_HIP;
+    return WSA_OK;
+}
 // One stream step past the front end (stream_step.hip wsa_stream_step_backend_internal): stream i of a plain set gets the first n_frames[i] <= frames_per_step
 // frames of its block of frames [n_streams][frames_per_step][bands] (u32, on the host) under the control byte ctl[i] (WSA_STREAM_ACTIVE / START / STOP); the
 // control words are written as wsa_stream_step writes them and the product's own launches follow, uncaptured: the step's prologue, launch_stream_prepare,

@@ -148,6 +148,10 @@ const uint32_t* wsa_stream_spec_internal(wsa_stream* b, wsa_ctx** ctx, uint32_t*
     *ctx = b->ctx; *n_streams = b->n; *frames_per_step = b->F; *bands = (uint32_t)b->fe.plan.bands;
     return b->d_spec;
 }
+const uint32_t* wsa_stream_ctl_internal(wsa_stream* b, wsa_ctx** ctx, uint32_t* n_streams, int* mixed) {
+    *ctx = b->ctx; *n_streams = b->n; *mixed = b->mixed ? 1 : 0;
+    return b->d_ctl;
+}
 
 uint32_t wsa_stream_samples_per_step(const wsa_stream* b) { return b ? b->step_samples : 0; }
 uint32_t wsa_stream_input_capacity(const wsa_stream* b, uint32_t i) { return !b || i >= b->n ? 0 : (b->mixed ? b->in_cap[i] : b->step_samples); }
