@@ -1,4 +1,4 @@
-"""K5 (csrc/coeffs.hip) on its own: the hand-built syllables of tests/coeffs_cases.py through the test entry wsa_debug_coeffs (csrc/debug.hip) — one
+"""K5 (csrc/coeffs.hip) on its own: the hand-built syllables of tests/coeffs_cases.py through the test entry wsa_debug_coeffs (csrc/debug_rows.hip) — one
 launch_coeffs per layout, in the batch geometry (several clips, syllables back to back inside a clip and across a clip boundary, at frame 0 and on a
 clip's last frame, 1 / 15 / 16 / 17 / 33 rows and the whole table with rows_cap far above the row count) and in the streams' (ring 64, scratch stride
 128: syllables that wrap the ring's end on either storage path, one that starts on the ring's last row, one of 63 frames and one that fills the ring).

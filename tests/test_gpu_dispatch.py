@@ -1,6 +1,6 @@
 """K3 (csrc/tracker.hip compact_count_kernel, compact_scan_kernel<COUNT>, compact_gather_kernel<FUSED>, launch_compact) and the span order
 (span_order_kernel + the gate's counting, GateParams::span_hist / span_key) on their own (-m gpu): the hand-built tables of tests/dispatch_cases.py
-through the test entries wsa_debug_compact / wsa_debug_span_order (csrc/debug.hip) against the dispatcher's restatement tests/dispatch_ref.py, which
+through the test entries wsa_debug_compact (csrc/debug_rows.hip) / wsa_debug_span_order (csrc/debug_gate.hip) against the dispatcher's restatement tests/dispatch_ref.py, which
 tests/test_dispatch_reference.py holds to the reference.  Integers and bit copies: every comparison is on bits, nothing has a tolerance.  The one thing
 left out: columns 2 and 3 of rows whose segments_ci entry has left the streams' 32-deep history, in the stream-lost-* cases of tests/dispatch_cases.py only
 (the stream layouts of tests/utterance_cases.py are held to the ring form of the restatement, every word).
@@ -313,6 +313,19 @@ def test_span_order(capi, n, variant):
         assert [by[(c, 0)] for c in longs] == [2046, 2047, 2048, 2580][:len(longs)], what
         assert [int(out["key"][c, 0, 0]) for c in longs] == [1, 0, 0, 0][:len(longs)], f"{what}: the clamp at SPAN_BUCKETS - 1 frames"
         assert int(out["hist"][0]) == max(len(longs) - 1, 0) and int(out["hist"][1]) == 1, what
+
+
+@pytest.mark.parametrize("variant", list(VARIANTS))
+@pytest.mark.parametrize("n", [1, 257])
+def test_span_order_runs_the_gate_as_the_gate_entry_does(capi, n, variant):
+    """the two entries share one gate set-up (csrc/debug_gate.hip): with the span counting on the gate kernels only add the span_key / span_hist writes, and
+    span_order_kernel reads seg_count and writes only order and counters — so both leave the same segment tables, over the whole zero-filled tables"""
+    clips, st = _span_clips(n)
+    span = capi.debug_span_order(VARIANTS[variant], clips, st, blocks=0)
+    gate = capi.debug_gate(VARIANTS[variant], clips, st, blocks=0)
+    assert span["seg_cap"] == gate["seg_cap"], f"{n} clips {variant}"
+    assert np.array_equal(span["seg_count"], gate["seg_count"]), f"{n} clips {variant}: seg_count"
+    assert span["seg_i"].shape == gate["seg_i"].shape and np.array_equal(span["seg_i"], gate["seg_i"]), f"{n} clips {variant}: seg_i"
 
 
 def _other_groups():

@@ -1,4 +1,4 @@
-"""The class fold K6b / K6b-e (csrc/classify_fold.hpp) on its own, through the test entry wsa_debug_class_fold (csrc/debug.hip): the
+"""The class fold K6b / K6b-e (csrc/classify_fold.hpp) on its own, through the test entry wsa_debug_class_fold (csrc/debug_fold.hip): the
 hand-built cases of tests/fold_cases.py straight into the product's fold launches — fold_kernel<float> and <double> with
 fold_compact_kernel, fold_group_kernel with fold_compact_group_kernel, and on streams stream_classes_kernel, stream_knn_kernel and
 stream_fold_group_kernel with stream_decide_kernel — against the float64 restatements (tests/classify_ref.py, tests/ensemble_ref.py, pinned

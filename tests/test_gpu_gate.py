@@ -1,4 +1,4 @@
-"""K2a (csrc/gate.hip) on its own (-m gpu): the hand-built frames of tests/gate_cases.py through the test entry wsa_debug_gate (csrc/debug.hip) — the
+"""K2a (csrc/gate.hip) on its own (-m gpu): the hand-built frames of tests/gate_cases.py through the test entry wsa_debug_gate (csrc/debug_gate.hip) — the
 peak scan, then ONE of the gate's four forms — against the oracle's record of what the gate decided (pyoracle.run_backend(gate=True), pinned to the
 reference by tests/test_gate_reference.py): per frame whether accumulate_fm is called, its filing index, the stale bit and both floors; per segment
 start, length, the span that owns its tracks, c_ci, ctx_max and the floor; the counts and the overflow flag.  Integers and doubles, compared bit

@@ -1,5 +1,5 @@
 """K6 / K6e (csrc/classify.hip classify_tile<RB>, classify_kernel, classify_group_kernel) on hand-built networks (-m gpu): the cases of
-tests/k6_cases.py through wsa_classify_rows / wsa_regress_rows and through the test entry wsa_debug_classify (csrc/debug.hip), against the literal
+tests/k6_cases.py through wsa_classify_rows / wsa_regress_rows and through the test entry wsa_debug_classify (csrc/debug_classify.hip), against the literal
 restatement tests/k6_ref.py (oracle/dense.c), which tests/test_k6_reference.py examines on the CPU.
 
 What is compared bit for bit (a NaN standing for any NaN: the payload of a generated NaN is the machine's own): the output of every network whose

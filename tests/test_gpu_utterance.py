@@ -1,4 +1,4 @@
-"""K4 (csrc/utterance.hip) on its own: the hand-built results of tests/utterance_cases.py through the test entry wsa_debug_utterance (csrc/debug.hip)
+"""K4 (csrc/utterance.hip) on its own: the hand-built results of tests/utterance_cases.py through the test entry wsa_debug_utterance (csrc/debug_rows.hip)
 — one launch_utterance per batch layout (one case per clip; all cases with empty and all-dropped clips between them at other frame offsets; that launch
 at 1 / 255 / 256 / 257 / 513 clips for the count kernel's ranges) and one per step of the stream layouts (one segment per step in rings of 64 with
 wrapping syllables, steps of 0 .. 3 segments, everything in one step, 129 syllables in a step's result, START in mid-life, an idle stream beside the

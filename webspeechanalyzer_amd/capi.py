@@ -2092,7 +2092,7 @@ GATE_SENTINEL = -2
 
 
 def debug_regress_fold(meta, values, step_s, row_off, ctl=None, device=0, sentinel=-7.0):
-    """Test access to the fold RG-1 on its own (csrc/debug.hip wsa_debug_regress_fold; not part of include/wsa.h): hand-built row meta
+    """Test access to the fold RG-1 on its own (csrc/debug_fold.hip wsa_debug_regress_fold; not part of include/wsa.h): hand-built row meta
     [n_rows, 8] i32 and value columns [H, n_rows] f64.  ctl None: a batch, row_off [n + 1]; else streams, row_off [n_steps, n + 1] counting
     from each step's first row and ctl [n_steps, n] control bytes.  Returns dict(n_cb (int, or [n_steps]), cb [K, 4], cb_value / cb_weight
     [H, K] over all K callbacks (the steps' one after the other), run_sum / run_weight / run_value [H, n] (streams: [n_steps, H, n]))."""
@@ -2127,7 +2127,7 @@ def debug_regress_fold(meta, values, step_s, row_off, ctl=None, device=0, sentin
 
 
 class _DebugFoldIO(ctypes.Structure):
-    """struct wsa_debug_fold_io of csrc/debug.hip"""
+    """struct wsa_debug_fold_io of csrc/debug_fold.hip"""
     _M = 8                                            # WSA_ENSEMBLE_MAX
     _vp, _u32, _i32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32
     _fields_ = [("meta", _vp), ("row_off", _vp), ("ctl", _vp), ("step_s", ctypes.c_double),
@@ -2141,7 +2141,7 @@ class _DebugFoldIO(ctypes.Structure):
 
 
 def debug_class_fold(meta, row_off, step_s, legends, conf, single=False, f64=False, ctl=None, cap=0, cb_cap=None, device=0, sentinel=-7):
-    """Test access to the class fold K6b / K6b-e on its own (csrc/debug.hip wsa_debug_class_fold; not part of include/wsa.h): hand-built row
+    """Test access to the class fold K6b / K6b-e on its own (csrc/debug_fold.hip wsa_debug_class_fold; not part of include/wsa.h): hand-built row
     meta [n_rows, 8] i32, per member a legend (strings) and confidences conf[d] [n_rows, C_d] (sent as float32, or float64 with f64).
     single: the one-model kernels (one member), else the group's.  ctl None: a batch, row_off [n + 1]; else streams, row_off
     [n_steps, n + 1] counting from each step's first row, ctl [n_steps, n] control bytes and the D2H window `cap`.
@@ -2196,7 +2196,7 @@ def debug_class_fold(meta, row_off, step_s, legends, conf, single=False, f64=Fal
 
 
 class _DebugClassifyIO(ctypes.Structure):
-    """struct wsa_debug_classify_io of csrc/debug.hip"""
+    """struct wsa_debug_classify_io of csrc/debug_classify.hip"""
     _vp, _u32, _i32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32
     _fields_ = [("models", _vp), ("n_models", _u32), ("feat", _vp), ("feat_rows", _u32), ("stride", _u32), ("nan_slot", _i32),
                 ("n_rows", _u32), ("rows_cap", _u32), ("n_dev", _i32), ("rb", _i32), ("one_block", _i32), ("regress", _i32),
@@ -2207,7 +2207,7 @@ DEBUG_CLASSIFY_SEED_F32, DEBUG_CLASSIFY_SEED_F64 = 0xffc0beef, 0xfff8beef0000bee
 
 
 def debug_classify(models, feat, n_rows=None, n_dev=None, rows_cap=None, rb=0, one_block=False, nan_slot=-1, out_range=None, out_rows=None):
-    """Test access to K6 / K6e through the product's own launches (csrc/debug.hip wsa_debug_classify; not part of include/wsa.h): one Model, or a
+    """Test access to K6 / K6e through the product's own launches (csrc/debug_classify.hip wsa_debug_classify; not part of include/wsa.h): one Model, or a
     list of 2 .. 8 as a group, over host rows feat [rows, stride] f64 (stride >= the models' inputs; nan_slot as level 12's `threw` mark).
     n_dev: the row count on the device (n_rows: the launch's own, one model only; default every row of feat); rows_cap sizes the grid (default the
     count, at least 1); rb 0 / 1 / 2 / 4 overrides the row-block factor; one_block runs a group's members with one row block each;
@@ -2257,7 +2257,7 @@ def debug_knn_split(store, d_feat, n_rows, k, slices, d_label, d_conf, d_nbr, d_
 
 
 def debug_gate(variant, clips, settings, blocks=0, F=0, max_span=0, step_nfr=None, step_ctl=None, device=0):
-    """Test access to the gate on its own (csrc/debug.hip wsa_debug_gate; not part of include/wsa.h): clips = [frames_c, bands] u32 arrays, settings =
+    """Test access to the gate on its own (csrc/debug_gate.hip wsa_debug_gate; not part of include/wsa.h): clips = [frames_c, bands] u32 arrays, settings =
     the six gate settings by name, variant = GATE_*.  Streams (GATE_STREAM): step_nfr / step_ctl [n_steps, n_clips].  Returns the gate's outputs as the
     kernel left them: fr_info / fr_v / fr_fl (fr_span) per clip, seg_i [.., seg_cap, 8], seg_d [.., seg_cap, 2], seg_count, flags, counter0, seg_cap (ring,
     state per step); frames no step fed keep GATE_SENTINEL.  Raises WsaError on a refusal."""
@@ -2314,7 +2314,7 @@ CAND_CAP = 64
 
 
 def debug_peaks(spec, mode, device=0):
-    """Test access to the peak scan on its own (csrc/debug.hip wsa_debug_peaks; not part of include/wsa.h): spec = [n_frames, bands] u32, one launch of
+    """Test access to the peak scan on its own (csrc/debug_gate.hip wsa_debug_peaks; not part of include/wsa.h): spec = [n_frames, bands] u32, one launch of
     the kernel behind `mode` (PEAKS_*).  Returns the frame records as the kernel left them in zero-filled tables, decoded: g [n] (40 bits), n [n], largest
     amplitude and bin [n], table base [n]; per candidate slot [n, 64] i, s, l, last, amp and the 40-bit prefix sums p_i = P[i - 1] and p_s = P[s]; the flag word;
     and the raw words hdr [n, 4], amp, ent [n, 64, 4] for bitwise comparisons.  Raises WsaError on a refusal."""
@@ -2341,7 +2341,7 @@ def debug_peaks(spec, mode, device=0):
 
 
 def debug_resample(clips, fs_in, fs_out, form=0, S=0, J=0, chunks=0, offset_bytes=0, stride_in=None, stride_out=None, pad_bits=0, sentinel=0x7fa5c3d1, device=0):
-    """Test access to the batch rate converter K0 on its own (csrc/debug.hip wsa_debug_resample; not part of include/wsa.h), no front end behind it.
+    """Test access to the batch rate converter K0 on its own (csrc/debug_input.hip wsa_debug_resample; not part of include/wsa.h), no front end behind it.
     clips = float32 arrays, fs_in one rate or one per clip.  form 0: resample_kernel (one rate; S, J, chunks override the launch shape as WSA_RS_S / _J / _C do),
     1: resample_mixed_kernel with one launch per rate class, 2: with one launch over the whole work list.  The device copy starts offset_bytes (0, 4, 8, 12)
     behind a 16-byte boundary; pad_bits is the bit pattern of everything around the clips' samples: behind each clip inside its row of stride_in samples, the
@@ -2373,7 +2373,7 @@ def debug_resample(clips, fs_in, fs_out, form=0, S=0, J=0, chunks=0, offset_byte
 
 
 def debug_fe_choice(analyzer, fs):
-    """Test access (csrc/debug.hip wsa_debug_fe_choice; not part of include/wsa.h): the name of the K1 instantiation the analyzer's settings select at the
+    """Test access (csrc/debug_units.hip wsa_debug_fe_choice; not part of include/wsa.h): the name of the K1 instantiation the analyzer's settings select at the
     sample rate fs, as profiles/frontend_split.md writes it, e.g. 'fe_kernel_r8<4,5,8,true,4,3>'.  Plans on the host; launches nothing."""
     L = lib()
     L.wsa_debug_fe_choice.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_char_p, ctypes.c_uint32]
@@ -2442,7 +2442,7 @@ COMPACT_SENTINEL = -7
 
 
 class _DebugCompactIO(ctypes.Structure):
-    """struct wsa_debug_compact_io of csrc/debug.hip"""
+    """struct wsa_debug_compact_io of csrc/debug_rows.hip"""
     _vp, _u32, _i32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32
     _fields_ = [("seg_i", _vp), ("seg_count", _vp), ("ctl", _vp), ("row_meta_in", _vp), ("row_feat_in", _vp), ("clip_rows", _vp), ("carry_in", _vp),
                 ("n", _u32), ("seg_cap", _u32), ("pool", _u32), ("n_steps", _u32), ("rows_cap", _u32), ("segs_cap", _u32),
@@ -2453,7 +2453,7 @@ class _DebugCompactIO(ctypes.Structure):
 
 def debug_compact(seg_i, seg_count, row_meta_in, row_feat_in, level, fused=True, clip_rows=None, ctl=None, carry_in=None, counters=None, totals=None, hist=None,
                   give_clr=False, give_host=False, rows_cap=None, segs_cap=None, pool=None, device=0, sentinel=COMPACT_SENTINEL):
-    """Test access to K3 on its own (csrc/debug.hip wsa_debug_compact; not part of include/wsa.h).  Batch (ctl None): seg_i [n, seg_cap, 8] i32, seg_count [n],
+    """Test access to K3 on its own (csrc/debug_rows.hip wsa_debug_compact; not part of include/wsa.h).  Batch (ctl None): seg_i [n, seg_cap, 8] i32, seg_count [n],
     clip_rows [n] or None; streams: seg_i [n_steps, n, seg_cap, 8], seg_count / ctl [n_steps, n], carry_in [n, CARRY_WORDS] or None.  row_meta_in [pool, 8] i32,
     row_feat_in [pool, 53] (float64, or uint64 bit patterns).  counters [16] / totals [4] / hist [SPAN_BUCKETS]: the seeds (default: `sentinel` as u32, totals[2] = 0).
     Every output slot starts as `sentinel` (feature words: the u64 pattern of the sentinel repeated).  Returns dict(seg_out [.., segs_cap, 4], row_meta_out
@@ -2509,7 +2509,7 @@ def debug_compact(seg_i, seg_count, row_meta_in, row_feat_in, level, fused=True,
 
 
 def debug_span_order(variant, clips, settings, blocks=0, device=0, sentinel=0xfffffff9, seg_cap=None):
-    """Test access to the span order on its own (csrc/debug.hip wsa_debug_span_order; not part of include/wsa.h): clips / settings / variant / blocks as
+    """Test access to the span order on its own (csrc/debug_gate.hip wsa_debug_span_order; not part of include/wsa.h): clips / settings / variant / blocks as
     debug_gate's batch form; the gate counts the spans into hist / key as the batch driver has it, launch_span_order sorts.  Returns dict(seg_i [n, seg_cap, 8],
     seg_count [n], hist [SPAN_BUCKETS], key [n, seg_cap, 2] = {bucket, rank}, order [n * seg_cap, 2] = {clip, segment}, counters [4], seg_cap); key and order
     slots nobody wrote keep `sentinel`.  seg_cap: skip the sizing call and hand this number over.  A WsaError raised by the run carries the untouched tables as .out."""

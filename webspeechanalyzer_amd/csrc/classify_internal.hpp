@@ -91,7 +91,7 @@ struct StreamEnsParams {
     uint32_t* h_count;
 };
 
-// ---- the folds' launches, with the product's geometry; the drivers and the test entry wsa_debug_class_fold (debug.hip) both go through these
+// ---- the folds' launches, with the product's geometry; the drivers and the test entry wsa_debug_class_fold (debug_fold.hip) both go through these
 // K6b and its compaction (classify_batch.hip; P = float and double): cb_off [n_clips] scratch, cb [.][4], cb_label, cb_conf per callback,
 // host: the callback count
 template <typename P>

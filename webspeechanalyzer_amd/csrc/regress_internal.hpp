@@ -1,5 +1,5 @@
 // regress_internal.hpp — what regress_fold.hip (regression groups: the grouped K6 over regression heads and the fold RG-1, on batches
-// and inside a stream step) shares with debug.hip (wsa_debug_regress_fold): the group object, the two fold kernels' parameter blocks
+// and inside a stream step) shares with debug_fold.hip (wsa_debug_regress_fold): the group object, the two fold kernels' parameter blocks
 // and their launches.  Nothing here is exported.
 #pragma once
 #include "classify_internal.hpp"

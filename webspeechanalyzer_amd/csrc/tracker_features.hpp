@@ -1,6 +1,6 @@
 // tracker_features.hpp — formant_features (ref dist/main.js:2 @B32369): the 53-feature reduction of the tracker's finalize, in its three device forms
 // (formant_features_wave, formant_features_lds with its two event implementations, formant_columns_packed).  A header of its own so that the test entry
-// wsa_debug_features (debug.hip, tests/test_gpu_units.py) runs the very functions the tracker kernels inline.
+// wsa_debug_features (debug_units.hip, tests/test_gpu_units.py) runs the very functions the tracker kernels inline.
 #pragma once
 #include "wsa_internal.hpp"
 #include "jsmath_device.hpp"

@@ -1,4 +1,4 @@
-// tracker_score.hpp — the formant tracker's match score (its own header so that the unit test entry of debug.hip evaluates the very
+// tracker_score.hpp — the formant tracker's match score (its own header so that the unit test entry of debug_units.hip evaluates the very
 // function tracker.hip uses; fixture tests/golden/score_expected.json = the reference's `_` under Node).
 #pragma once
 #include <hip/hip_runtime.h>
