@@ -47,9 +47,6 @@ def plan(formats, channels, select, source, n_frames):
     """pcm_plan_channels through wsa_debug_batch_deinterleave's planning call (no device): (status, offsets [n + 1], message)"""
     L = capi.lib()
     f = L.wsa_debug_batch_deinterleave
-    f.argtypes = [ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 5 + [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
-                                                                                               ctypes.c_char_p, ctypes.c_uint32]
-    f.restype = ctypes.c_int
     n = len(n_frames)
     arr = lambda v, dt: None if v is None else np.ascontiguousarray(v, dtype=dt)
     fm, ch, sel, src, nf = arr(formats, np.int32), arr(channels, np.uint32), arr(select, np.uint32), arr(source, np.uint32), arr(n_frames, np.uint32)

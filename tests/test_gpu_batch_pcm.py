@@ -34,8 +34,6 @@ def unpack(clips, stride, fill):
     """clips: [(format name, channels, frames, channel-0 samples as pcm_decode takes them)] -> one launch of the kernel; the bytes between the
     clips and every other channel hold `fill`.  Returns out [n_clips, stride] (pre-filled with SENTINEL)."""
     L = capi.lib()
-    L.wsa_debug_batch_unpack.argtypes = [ctypes.c_int32] + [ctypes.c_void_p] * 5 + [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64]
-    L.wsa_debug_batch_unpack.restype = ctypes.c_int
     off, blobs = [0], []
     for fmt, ch, n, ch0 in clips:
         sb = SAMPLE_BYTES[fmt]

@@ -39,9 +39,6 @@ LAYOUTS = {l["name"]: l for l in cc.layouts()}
 def _lib():
     from webspeechanalyzer_amd import capi
     L = capi.lib()
-    vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-    L.wsa_debug_coeffs.argtypes = [ctypes.c_int32, vp, vp, vp, u32, vp, u32, u32, u32, u32, ctypes.c_double, vp]
-    L.wsa_debug_coeffs.restype = ctypes.c_int
     return L
 
 

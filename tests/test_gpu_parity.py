@@ -1303,8 +1303,6 @@ def test_per_clip_pinned_buffers_of_page_multiple_length_are_not_merged_across_a
     x16 = (x * 32767).astype(np.int16)
     an = wsa.Analyzer(wsa.Config(output_level=5))
     L = an.L
-    L.wsa_host_alloc.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p)]
-    L.wsa_host_free.argtypes = [ctypes.c_void_p]
     held = []
 
     def pinned(arr):

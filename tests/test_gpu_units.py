@@ -24,8 +24,6 @@ def test_device_log10_and_pow_are_bit_exact_with_v8():
     from oracle import pyoracle
     from webspeechanalyzer_amd import capi
     L = capi.lib()
-    L.wsa_debug_jsmath.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]
-    L.wsa_debug_jsmath.restype = ctypes.c_int
     d = json.load(open(os.path.join(GOLDEN, "jsmath_v8.json")))
     h2d = lambda h: struct.unpack(">d", bytes.fromhex(h))[0]
 
@@ -78,8 +76,6 @@ def test_integer_floor_law_equals_the_f64_evaluation_for_every_ctx_max():
         pytest.skip("needs a GPU")
     from webspeechanalyzer_amd import capi
     L = capi.lib()
-    L.wsa_debug_floor_law.argtypes = [ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
-    L.wsa_debug_floor_law.restype = ctypes.c_int
     out = (ctypes.c_uint64 * 3)()
     total_exact = 0
     for lo in range(0, 1 << 32, 1 << 30):
@@ -97,8 +93,6 @@ def test_device_match_score_equals_the_reference_function():
         pytest.skip("needs a GPU")
     from webspeechanalyzer_amd import capi
     L = capi.lib()
-    L.wsa_debug_score.argtypes = [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]
-    L.wsa_debug_score.restype = ctypes.c_int
     d = json.load(open(os.path.join(GOLDEN, "score_expected.json")))
     args = np.ascontiguousarray(np.array(d["args"], dtype=np.float64))
     want = np.array([struct.unpack(">d", bytes.fromhex(h))[0] for h in d["expected_f64_hex"]])
@@ -152,8 +146,6 @@ def test_peak_scan_kernels_equal_the_reference_scan(bands):
     g, n, the largest candidate."""
     from webspeechanalyzer_amd import capi
     L = capi.lib()
-    L.wsa_debug_peaks.argtypes = [ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 4
-    L.wsa_debug_peaks.restype = ctypes.c_int
     rng = np.random.default_rng(100 + bands)
     n = 64 * 5 + 17
     spec = np.ascontiguousarray(_peak_frames(rng, n, bands))
@@ -356,8 +348,6 @@ def test_formant_features_device_functions_against_the_oracle():
     from oracle import pyoracle
     from webspeechanalyzer_amd import capi
     L = capi.lib()
-    L.wsa_debug_features.argtypes = [ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p]
-    L.wsa_debug_features.restype = ctypes.c_int
     cases = _feat_cases()
     ran = refused = 0
     worst = {}

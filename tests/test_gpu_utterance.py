@@ -54,9 +54,6 @@ GARBAGE = (0xA5C30000 + 257 * np.arange(uc.UTT_STATE_WORDS)).astype(np.uint32)  
 def _lib():
     from webspeechanalyzer_amd import capi
     L = capi.lib()
-    vp, u32, i32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32
-    L.wsa_debug_utterance.argtypes = [i32, vp, u32, vp, vp, u32, vp, vp, vp, u32, u32, u32, vp, vp, vp, i32, vp, vp, vp, vp]
-    L.wsa_debug_utterance.restype = ctypes.c_int
     return L
 
 

@@ -66,8 +66,6 @@ from webspeechanalyzer_amd.synth import synth_clips
 n, ns = args.clips, int(args.seconds * FS)
 an = wsa.Analyzer(wsa.Config(output_level=5))
 L = capi.lib()
-L.wsa_host_alloc.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p)]
-L.wsa_host_free.argtypes = [ctypes.c_void_p]
 stream = torch.cuda.current_stream().cuda_stream
 distinct = min(n, 32)                        # distinct signals, repeated over the batch: the link does not care, the kernels hardly
 x = synth_clips(distinct, ns, fs=FS, seed=5, device="cuda").cpu().numpy().astype(np.float64)

@@ -18,8 +18,6 @@ b.run(pcm.data_ptr(), pcm.stride(0), st)
 spec, foff = b.spectra(st)
 spec = np.ascontiguousarray(spec)
 L = capi.lib()
-L.wsa_debug_peaks_time.argtypes = [ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]
-L.wsa_debug_peaks_time.restype = ctypes.c_int
 for dbg in [int(x) for x in sys.argv[1:]] or [0]:
     for mode, name in ((4, "rounds of 32 bins"), (3, "rounds of 16 bins")):
         ms = ctypes.c_float(0)

@@ -1,0 +1,188 @@
+"""Feature DBs on the device: the labelled DB of K8 (wsa_dbstats) and the DB that stays there (K10, wsa_featdb)."""
+import ctypes
+
+import numpy as np
+
+from ._abi import lib
+from ._util import _Handle
+from .training import Trainer
+
+DBSTATS_MAX_CLASSES, DBSTATS_MAX_HEADS, DBSTATS_CHUNK_ROWS = 256, 8, 256      # WSA_DBSTATS_* of include/wsa.h
+_DB_CAT = np.dtype([("correct", "<u8"), ("wrong", "<u8"), ("blank", "<u8")])
+_DB_CLASS = np.dtype([("count", "<u8"), ("correct", "<u8"), ("wrong", "<u8"), ("duration", "<f8"), ("first_row", "<u4"), ("reserved", "<u4")])
+_DB_ORD = np.dtype([("true_n", "<u8"), ("pred_n", "<u8"), ("min", "<f8"), ("max", "<f8"), ("sq_sum", "<f8")])
+
+
+class FeatureDBStats(_Handle):
+    """wsa_dbstats: one labelled feature DB on the device (K8, spec DS-1).  features [n][53] f64, or 264 / 23 wide: the rows of level 11 / 12 (None: a DB that is only counted) and
+    durations [n] f64 are host arrays; vocab_sizes has one vocabulary size per categorical head, n_ord is the number of ordinal heads.
+    Indices and values are what the device sees; webspeechanalyzer_amd.dbstats builds them from the app's rows."""
+
+    _destroy = "wsa_dbstats_destroy"
+
+    def __init__(self, an, features, durations, vocab_sizes=(), n_ord=0, first_row=0):
+        """first_row: with a FeatDB as `features`, the DB row of the first of the len(durations) rows taken"""
+        self.an, self.L = an, an.L
+        dur = np.ascontiguousarray(durations, np.float64)
+        if isinstance(features, FeatDB):                 # the rows of a device DB, copied device to device (wsa_featdb_dbstats_create)
+            if dur.ndim != 1:
+                raise ValueError(f"durations {dur.shape}: expected [n]")
+            self.n_feat, self.n_rows, self.vocab, self.n_ord = features.width, dur.shape[0], [int(v) for v in vocab_sizes], int(n_ord)
+            voc = np.ascontiguousarray(self.vocab, np.uint32)
+            self.h = ctypes.c_void_p()
+            an._check(self.L.wsa_featdb_dbstats_create(an.h, features.h, int(first_row), self.n_rows, dur.ctypes.data if self.n_rows else None, len(self.vocab),
+                                                   voc.ctypes.data if len(self.vocab) else None, self.n_ord, ctypes.byref(self.h)))
+            return
+        feat = None if features is None else np.ascontiguousarray(features, np.float64)
+        if dur.ndim != 1 or (feat is not None and (feat.ndim != 2 or feat.shape[0] != dur.shape[0] or feat.shape[1] not in (53, 264, 23))):
+            raise ValueError(f"features {None if feat is None else feat.shape} / durations {dur.shape}: expected [n][53] (or [n][264], [n][23]) and [n]")
+        self.n_feat = 53 if feat is None else feat.shape[1]
+        self.n_rows, self.vocab, self.n_ord = dur.shape[0], [int(v) for v in vocab_sizes], int(n_ord)
+        voc = np.ascontiguousarray(self.vocab, np.uint32)
+        self.h = ctypes.c_void_p()
+        an._check(self.L.wsa_wide_dbstats_create(an.h, None if feat is None else feat.ctypes.data, self.n_feat, dur.ctypes.data if self.n_rows else None,
+                                                 self.n_rows, len(self.vocab), voc.ctypes.data if len(self.vocab) else None, self.n_ord, ctypes.byref(self.h)))
+
+    def _column(self, x, dtype, name):
+        if x is None:
+            return None
+        a = np.ascontiguousarray(x, dtype)
+        if a.shape != (self.n_rows,):
+            raise ValueError(f"{name} has shape {a.shape}, the DB has {self.n_rows} rows")
+        return a
+
+    def set_classes(self, head, true_idx, pred_idx=None):
+        """true_idx [n] (-1: the row does not count), pred_idx [n] (-1: blank) or None (all blank): vocabulary indices of categorical head `head`."""
+        t, p = self._column(true_idx, np.int32, "true_idx"), self._column(pred_idx, np.int32, "pred_idx")
+        self.an._check(self.L.wsa_dbstats_set_classes(self.h, int(head), t.ctypes.data, None if p is None else p.ctypes.data))
+
+    def set_values(self, head, true_value, pred_value=None):
+        """true_value [n], pred_value [n] or None (all missing) of ordinal head `head`; NaN = missing."""
+        t, p = self._column(true_value, np.float64, "true_value"), self._column(pred_value, np.float64, "pred_value")
+        self.an._check(self.L.wsa_dbstats_set_values(self.h, int(head), t.ctypes.data, None if p is None else p.ctypes.data))
+
+    @staticmethod
+    def _map(legend_to_vocab):
+        return np.ascontiguousarray(legend_to_vocab, np.int32)
+
+    def predict_classes(self, head, model, legend_to_vocab, stream=0):
+        """K6 over every row, then K8's decision into the head's predicted column (enqueues)."""
+        m = self._map(legend_to_vocab)
+        if m.shape != (model.n_classes,):
+            raise ValueError(f"legend_to_vocab has shape {m.shape}, the model has {model.n_classes} classes")
+        self.an._check(self.L.wsa_dbstats_predict_classes(self.h, int(head), model.h, m.ctypes.data, stream))
+
+    def decide_rows(self, head, d_prob, n_classes, legend_to_vocab, stream=0):
+        """K8's decision alone on a device table d_prob [n_rows][n_classes] f32 (enqueues)."""
+        m = self._map(legend_to_vocab)
+        if m.shape != (int(n_classes),):
+            raise ValueError(f"legend_to_vocab has shape {m.shape}, the table has {n_classes} classes")
+        self.an._check(self.L.wsa_dbstats_decide_rows(self.h, int(head), d_prob, int(n_classes), m.ctypes.data, stream))
+
+    def predict_values(self, head, model, out_min=None, out_max=None, stream=0):
+        """K6 with the regression epilogue into the head's predicted column (enqueues); the range defaults to the spec's own."""
+        lo, hi = model.out_range(out_min, out_max)
+        self.an._check(self.L.wsa_dbstats_predict_values(self.h, int(head), model.h, lo, hi, stream))
+
+    def table(self, stream=0):
+        """Synchronises; (cat [n_cat], cls [sum V], ord [n_ord]) as numpy records (wsa_dbstats_cat / _class / _ord)."""
+        cat, cls, od = np.zeros(len(self.vocab), _DB_CAT), np.zeros(sum(self.vocab), _DB_CLASS), np.zeros(self.n_ord, _DB_ORD)
+        self.an._check(self.L.wsa_dbstats_table(self.h, stream, cat.ctypes.data if len(cat) else None, cls.ctypes.data if len(cls) else None,
+                                                od.ctypes.data if len(od) else None))
+        return cat, cls, od
+
+    def pred_classes(self, head, stream=0):
+        out = np.zeros(self.n_rows, np.int32)
+        self.an._check(self.L.wsa_dbstats_copy_classes(self.h, int(head), stream, out.ctypes.data))
+        return out
+
+    def pred_values(self, head, stream=0):
+        out = np.zeros(self.n_rows, np.float64)
+        self.an._check(self.L.wsa_dbstats_copy_values(self.h, int(head), stream, out.ctypes.data))
+        return out
+
+    def probs(self, n_classes, stream=0):
+        """The probabilities the last predict_classes decided on, [n_rows][n_classes] f32."""
+        out = np.zeros((self.n_rows, int(n_classes)), np.float32)
+        self.an._check(self.L.wsa_dbstats_copy_probs(self.h, stream, out.ctypes.data, int(n_classes)))
+        return out
+
+
+class FeatDB(_Handle):
+    """wsa_featdb: the feature columns of the app's feature DB on the device of one context (K10, spec FD-1): one allocation of
+    capacity x width doubles, rows appended behind the ones it holds and never moved.  Strings stay with the caller
+    (webspeechanalyzer_amd.featdb.DeviceDB keeps them); pass the same stream to every call."""
+
+    _destroy = "wsa_featdb_destroy"
+
+    def __init__(self, an, width, capacity):
+        self.an, self.L, self.h = an, an.L, ctypes.c_void_p()
+        self.width, self.capacity = int(width), int(capacity)
+        an._check(self.L.wsa_featdb_create(an.h, self.width, self.capacity, ctypes.byref(self.h)))
+
+    @staticmethod
+    def tile_info():
+        """(source rows per wave tile, per step of the keep kernel's workgroup, appended rows per pass of the copy kernel) of K10."""
+        a, b, c = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        lib().wsa_featdb_tile_info(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
+        return a.value, b.value, c.value
+
+    @property
+    def count(self):
+        n = ctypes.c_uint32()
+        self.an._check(self.L.wsa_featdb_count(self.h, ctypes.byref(n)))
+        return int(n.value)
+
+    def clear(self):
+        self.an._check(self.L.wsa_featdb_clear(self.h))
+
+    def append_batch(self, batch, stream=0):
+        """The rows of the batch's last run that the app's storing keeps (wsa_featdb_append_batch; synchronises).  Returns (first DB row,
+        kept): kept [n_added] i32 = the source row (level 11: utterance row) of every appended row."""
+        cap = max(int(batch.info["rows_cap"]), int(batch.info["n_clips"]))       # what a run can keep at most; more than the DB's capacity is refused before
+        kept = np.zeros(max(min(cap, self.capacity), 1), np.int32)
+        first, n = ctypes.c_uint32(), ctypes.c_uint32()
+        self.an._check(self.L.wsa_featdb_append_batch(self.h, batch.h, stream, ctypes.byref(first), ctypes.byref(n), kept.ctypes.data, len(kept)))
+        return int(first.value), kept[:n.value].copy()
+
+    def append_host(self, features, stream=0):
+        """Dense host rows [n][width] (an imported DB); returns the first DB row."""
+        feat = np.ascontiguousarray(features, np.float64).reshape(-1, self.width)
+        first = self.count
+        self.an._check(self.L.wsa_featdb_append_host(self.h, feat.ctypes.data if len(feat) else None, len(feat), stream))
+        return first
+
+    def device_rows(self):
+        """The device pointer of the dense table [count][width] f64 (valid until close)."""
+        p = ctypes.c_void_p()
+        self.an._check(self.L.wsa_featdb_device_rows(self.h, ctypes.byref(p)))
+        return p.value
+
+    def copy_rows(self, first=0, n=None, stream=0):
+        n = self.count - int(first) if n is None else int(n)
+        out = np.zeros((n, self.width), np.float64)
+        self.an._check(self.L.wsa_featdb_copy_rows(self.h, stream, int(first), n, out.ctypes.data if n else None))
+        return out
+
+    def gather(self, rows, d_out, stream=0):
+        """d_out [n][width] f64 (device pointer) = DB rows `rows`; only enqueues."""
+        r = np.ascontiguousarray(rows, np.uint32)
+        if r.ndim != 1:
+            raise ValueError(f"rows has shape {r.shape}: expected a list of DB row indices")
+        self.an._check(self.L.wsa_featdb_gather(self.h, r.ctypes.data if len(r) else None, len(r), d_out, stream))
+
+    def ranges(self, rows=None, stream=0):
+        """(in_min, in_max) [width] over the selected rows (None: all); NaN for a column that holds one; synchronises."""
+        r = None if rows is None else np.ascontiguousarray(rows, np.uint32)
+        n = self.count if r is None else len(r)
+        mn, mx = np.zeros(self.width, np.float64), np.zeros(self.width, np.float64)
+        self.an._check(self.L.wsa_featdb_ranges(self.h, None if r is None else r.ctypes.data, n, stream, mn.ctypes.data, mx.ctypes.data))
+        return mn, mx
+
+    def trainer(self, spec, rows, labels, n_val, batch_size, learning_rate):
+        """A Trainer over DB rows `rows` in that order (wsa_trainer_create_db)."""
+        return Trainer(self.an, spec, rows, labels, n_val, batch_size, learning_rate, db=self)
+
+    def regress_trainer(self, spec, rows, values, n_val, batch_size, learning_rate, out_min=None, out_max=None):
+        return Trainer(self.an, spec, rows, values, n_val, batch_size, learning_rate, db=self,
+                       regression=(spec.out_min if out_min is None else out_min, spec.out_max if out_max is None else out_max))
