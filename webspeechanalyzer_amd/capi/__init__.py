@@ -17,7 +17,7 @@ from .models import *  # noqa: F401,F403
 from .models import _model_desc  # noqa: F401
 from .training import *  # noqa: F401,F403
 from .db import *  # noqa: F401,F403
-from .db import _DB_CAT, _DB_CLASS, _DB_ORD  # noqa: F401
+from .db import _DB_AGREE, _DB_CAT, _DB_CLASS, _DB_ORD  # noqa: F401
 from .gather import *  # noqa: F401,F403
 from .gather import _GatherResult  # noqa: F401
 from .analyzer import *  # noqa: F401,F403

@@ -338,6 +338,24 @@ ABI_TABLE = {
     "wsa_stream_featdb_tile_info": (st, [P(i32)] * 4),
 }
 ABI_SYMBOLS = list(ABI_TABLE)
+# the same for include/wsa_eval.h (additions within version 5, probe for wsa_dbstats_confusion): evaluating a labelled DB (K8e, spec EV-1).
+# A table of its own because the header is: tests/test_abi.py pins what wsa.h declares, tests/test_dbeval_host.py holds this one to its header.
+EVAL_TABLE = {
+    "wsa_dbstats_confusion": (st, [vp, u32, vp, vp]),
+    "wsa_dbstats_agreement": (st, [vp, vp, vp]),
+    "wsa_dbstats_set_files": (st, [vp, vp, vp, u32]),
+    "wsa_dbstats_set_file_classes": (st, [vp, u32, vp]),
+    "wsa_dbstats_set_file_values": (st, [vp, u32, vp]),
+    "wsa_dbstats_fold_files": (st, [vp, u32, vp]),
+    "wsa_dbstats_fold_file_values": (st, [vp, u32, vp]),
+    "wsa_dbstats_file_table": (st, [vp, vp, vp, vp, vp]),
+    "wsa_dbstats_file_confusion": (st, [vp, u32, vp, vp]),
+    "wsa_dbstats_file_agreement": (st, [vp, vp, vp]),
+    "wsa_dbstats_copy_file_sums": (st, [vp, u32, vp, vp, u32]),
+    "wsa_dbstats_copy_file_classes": (st, [vp, u32, vp, vp]),
+    "wsa_dbstats_copy_file_values": (st, [vp, u32, vp, vp]),
+}
+EVAL_SYMBOLS = list(EVAL_TABLE)
 
 _LIB = None
 
@@ -372,7 +390,7 @@ def lib():
     L.wsa_abi_version.restype = ctypes.c_int
     if L.wsa_abi_version() != ABI_VERSION:
         raise WsaError(f"{path} has ABI version {L.wsa_abi_version()}, this binding is written against {ABI_VERSION} (include/wsa.h): rebuild the library")
-    for name, (restype, argtypes) in ABI_TABLE.items():
+    for name, (restype, argtypes) in list(ABI_TABLE.items()) + list(EVAL_TABLE.items()):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     from .debug import DEBUG_TABLE

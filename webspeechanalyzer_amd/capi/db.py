@@ -11,6 +11,7 @@ DBSTATS_MAX_CLASSES, DBSTATS_MAX_HEADS, DBSTATS_CHUNK_ROWS = 256, 8, 256      # 
 _DB_CAT = np.dtype([("correct", "<u8"), ("wrong", "<u8"), ("blank", "<u8")])
 _DB_CLASS = np.dtype([("count", "<u8"), ("correct", "<u8"), ("wrong", "<u8"), ("duration", "<f8"), ("first_row", "<u4"), ("reserved", "<u4")])
 _DB_ORD = np.dtype([("true_n", "<u8"), ("pred_n", "<u8"), ("min", "<f8"), ("max", "<f8"), ("sq_sum", "<f8")])
+_DB_AGREE = np.dtype([("n", "<u8")] + [(k, "<f8") for k in ("mean_true", "mean_pred", "var_true", "var_pred", "cov", "ccc", "pearson")])   # wsa_dbstats_agree (wsa_eval.h)
 
 
 class FeatureDBStats(_Handle):
@@ -19,6 +20,7 @@ class FeatureDBStats(_Handle):
     Indices and values are what the device sees; webspeechanalyzer_amd.dbstats builds them from the app's rows."""
 
     _destroy = "wsa_dbstats_destroy"
+    n_files = 0               # until set_files
 
     def __init__(self, an, features, durations, vocab_sizes=(), n_ord=0, first_row=0):
         """first_row: with a FeatDB as `features`, the DB row of the first of the len(durations) rows taken"""
@@ -90,6 +92,85 @@ class FeatureDBStats(_Handle):
         self.an._check(self.L.wsa_dbstats_table(self.h, stream, cat.ctypes.data if len(cat) else None, cls.ctypes.data if len(cls) else None,
                                                 od.ctypes.data if len(od) else None))
         return cat, cls, od
+
+    def confusion(self, head, stream=0):
+        """K8e (spec EV-1): categorical head `head`'s confusion matrix [V][V + 1] u64 over the counted rows, m[true][predicted]; column V
+        collects the blank predictions.  Synchronises."""
+        V = self.vocab[int(head)] if 0 <= int(head) < len(self.vocab) else 1      # (a head the DB lacks is refused by the library, before m is touched)
+        m = np.zeros((V, V + 1), np.uint64)
+        self.an._check(self.L.wsa_dbstats_confusion(self.h, int(head), stream, m.ctypes.data))
+        return m
+
+    def agreement(self, stream=0):
+        """K8e (spec EV-1): [n_ord] records (wsa_dbstats_agree) over the rows whose true and predicted value both count.  Synchronises."""
+        out = np.zeros(self.n_ord, _DB_AGREE)
+        self.an._check(self.L.wsa_dbstats_agreement(self.h, stream, out.ctypes.data if len(out) else None))
+        return out
+
+    # ---- per file (K8e): a file where K6b / RG-1 have a clip, then the files evaluated as rows
+    def set_files(self, file_of_row, callback_of_row, n_files):
+        """file_of_row [n] i32 (-1: no file; non-decreasing otherwise), callback_of_row [n] i32 (the row's si); set once."""
+        f, c = self._column(file_of_row, np.int32, "file_of_row"), self._column(callback_of_row, np.int32, "callback_of_row")
+        self.an._check(self.L.wsa_dbstats_set_files(self.h, f.ctypes.data, c.ctypes.data, int(n_files)))
+        self.n_files = int(n_files)
+
+    def _file_column(self, x, dtype, name):
+        a = np.ascontiguousarray(x, dtype)
+        if a.shape != (self.n_files,):
+            raise ValueError(f"{name} has shape {a.shape}, the DB has {self.n_files} files")
+        return a
+
+    def set_file_classes(self, head, true_idx):
+        """true_idx [n_files] i32: a file's true class of categorical head `head`, -1: the file does not count (the predicted column stays)."""
+        t = self._file_column(true_idx, np.int32, "true_idx")             # (held until the call returns: a converted copy is a temporary)
+        self.an._check(self.L.wsa_dbstats_set_file_classes(self.h, int(head), t.ctypes.data))
+
+    def set_file_values(self, head, true_value):
+        """true_value [n_files] f64 of ordinal head `head`; NaN = missing."""
+        t = self._file_column(true_value, np.float64, "true_value")
+        self.an._check(self.L.wsa_dbstats_set_file_values(self.h, int(head), t.ctypes.data))
+
+    def fold_files(self, head, stream=0):
+        """K6b per file on the probabilities the last predict_classes(head, ..) kept (enqueues)."""
+        self.an._check(self.L.wsa_dbstats_fold_files(self.h, int(head), stream))
+
+    def fold_file_values(self, head, stream=0):
+        """RG-1's running value per file over ordinal head `head`'s predicted column (enqueues)."""
+        self.an._check(self.L.wsa_dbstats_fold_file_values(self.h, int(head), stream))
+
+    def file_table(self, stream=0):
+        nf = self.n_files
+        cat, cls, od = np.zeros(len(self.vocab), _DB_CAT), np.zeros(sum(self.vocab), _DB_CLASS), np.zeros(self.n_ord, _DB_ORD)
+        self.an._check(self.L.wsa_dbstats_file_table(self.h, stream, cat.ctypes.data if len(cat) and nf else None, cls.ctypes.data if len(cls) and nf else None,
+                                                     od.ctypes.data if len(od) and nf else None))
+        return cat, cls, od
+
+    def file_confusion(self, head, stream=0):
+        V = self.vocab[int(head)] if 0 <= int(head) < len(self.vocab) else 1
+        m = np.zeros((V, V + 1), np.uint64)
+        self.an._check(self.L.wsa_dbstats_file_confusion(self.h, int(head), stream, m.ctypes.data))
+        return m
+
+    def file_agreement(self, stream=0):
+        out = np.zeros(self.n_ord, _DB_AGREE)
+        self.an._check(self.L.wsa_dbstats_file_agreement(self.h, stream, out.ctypes.data if len(out) else None))
+        return out
+
+    def file_sums(self, head, n_classes, stream=0):
+        """The meter sums (Label_conf_all at the file's end) [n_files][n_classes] f64 of a folded head."""
+        out = np.zeros((max(self.n_files, 1), int(n_classes)), np.float64)
+        self.an._check(self.L.wsa_dbstats_copy_file_sums(self.h, int(head), stream, out.ctypes.data, int(n_classes)))
+        return out[:self.n_files]
+
+    def file_classes(self, head, stream=0):
+        out = np.zeros(max(self.n_files, 1), np.int32)
+        self.an._check(self.L.wsa_dbstats_copy_file_classes(self.h, int(head), stream, out.ctypes.data))
+        return out[:self.n_files]
+
+    def file_values(self, head, stream=0):
+        out = np.zeros(max(self.n_files, 1), np.float64)
+        self.an._check(self.L.wsa_dbstats_copy_file_values(self.h, int(head), stream, out.ctypes.data))
+        return out[:self.n_files]
 
     def pred_classes(self, head, stream=0):
         out = np.zeros(self.n_rows, np.int32)

@@ -55,6 +55,7 @@ const uint32_t* wsa_stream_ctl_internal(wsa_stream* b, wsa_ctx** ctx, uint32_t* 
 wsa_status wsa_stream_step_backend_internal(wsa_stream* b, const uint32_t* n_frames, const uint8_t* ctl, const uint32_t* frames, uint32_t bands, void* stream);
 void wsa_model_info_internal(const wsa_model* m, wsa_ctx** ctx, int* n_classes, int* softmax);   // classify.hip, for dbstats.hip (K8)
 int wsa_model_inputs_internal(const wsa_model* m);                                               // units[0]
+const int64_t* wsa_model_key_rank_internal(const wsa_model* m);                                  // device [classes]: the legend's Object.keys ranks (K8e's per-file fold)
 }
 
 // classify_stream.hip runs K6 / K6b inside a stream object's step (wsa_stream_set_model); stream_internal.hpp has the stream object

@@ -302,6 +302,7 @@ void wsa_model_info_internal(const wsa_model* m, wsa_ctx** ctx, int* n_classes, 
     *ctx = m->ctx; *n_classes = m->C; *softmax = m->softmax ? 1 : 0;
 }
 int wsa_model_inputs_internal(const wsa_model* m) { return m->nin; }
+const int64_t* wsa_model_key_rank_internal(const wsa_model* m) { return m->d_key_rank; }
 
 wsa_status wsa_classify_rows(const wsa_model* m, const double* d_feat, uint32_t n_rows, float* d_prob, void* stream) {
     if (!m) return WSA_ERR_INVALID;

@@ -17,20 +17,14 @@
 #include <limits>
 #include <string>
 #include <vector>
-#include "host_plan.hpp"
-#include "featdb_internal.hpp"
+#include "dbstats_internal.hpp"
 
 #pragma clang fp contract(off)
 
 using wsa_api::fail;
+using namespace wsa_dbstats_detail;        // DsTable, struct wsa_dbstats' parts, check_head: shared with K8e (dbeval.hip)
 
 namespace {
-
-constexpr int DS_R = WSA_DBSTATS_CHUNK_ROWS;
-constexpr int DS_THREADS = 256;
-constexpr int DS_H = WSA_DBSTATS_MAX_HEADS;
-static_assert(DS_THREADS == DS_R, "pass 1 stages one row per thread");
-static_assert(WSA_DBSTATS_MAX_CLASSES <= DS_THREADS, "pass 2 owns one vocabulary entry per thread");
 
 struct DsDecide {
     const float* prob; int32_t* out; uint32_t n_rows; int C, G;
@@ -57,19 +51,7 @@ __global__ void __launch_bounds__(DS_THREADS) dbstats_decide_kernel(DsDecide p) 
     if (c == 0 && row < p.n_rows) p.out[row] = first < 64 ? s_map[first] : -1;
 }
 
-struct DsTable {
-    uint32_t n_rows, n_chunks, n_cat, n_ord, items;        // items = the sum of the vocabulary sizes
-    uint32_t voff[DS_H + 1];                               // head h owns items voff[h] .. voff[h + 1] - 1
-    const int32_t *t_idx[DS_H], *p_idx[DS_H];
-    const double *t_val[DS_H], *p_val[DS_H];
-    const double* dur;
-    uint32_t* s_u32;      // slabs: [chunk][4][items] count, correct, wrong, first_row
-    double* s_dur;        //        [chunk][items]
-    uint32_t* o_u32;      //        [n_ord][2][n_chunks] true_n, pred_n
-    double* o_f64;        //        [n_ord][3][n_chunks] min, max, sq_sum
-    wsa_dbstats_cat* cat; wsa_dbstats_class* cls; wsa_dbstats_ord* ord;
-};
-
+// (DsTable, the parameter block of the two table passes: dbstats_internal.hpp)
 // LDS of pass 1: durations, then per ordinal head true / predicted values, then per categorical head true / predicted indices
 inline size_t chunk_lds(uint32_t n_cat, uint32_t n_ord) { return (size_t)DS_R * (sizeof(double) * (1 + 2 * n_ord) + sizeof(int32_t) * 2 * n_cat); }
 
@@ -201,25 +183,8 @@ __global__ void __launch_bounds__(DS_THREADS) dbstats_sum_kernel(DsTable p) {
 
 }  // namespace
 
-struct wsa_dbstats {
-    wsa_ctx* ctx = nullptr;
-    uint32_t n_rows = 0, n_chunks = 0, n_cat = 0, n_ord = 0, items = 0, n_feat = 0;     // n_feat: features per row (53, 264 or 23)
-    uint32_t voff[DS_H + 1] = {};
-    double *d_feat = nullptr, *d_dur = nullptr;
-    int32_t *d_t_idx[DS_H] = {}, *d_p_idx[DS_H] = {};
-    double *d_t_val[DS_H] = {}, *d_p_val[DS_H] = {};
-    float* d_prob = nullptr; uint32_t prob_classes = 0;     // [n_rows][WSA_MODEL_MAX_CLASSES], allocated by the first wsa_dbstats_predict_classes
-    DsTable tab{};
-    wsa::DevArena mem;
-};
-
+// (struct wsa_dbstats and check_head: dbstats_internal.hpp)
 namespace {
-
-wsa_status check_head(wsa_dbstats* db, uint32_t head, bool cat) {
-    const uint32_t n = cat ? db->n_cat : db->n_ord;
-    if (head >= n) return fail(db->ctx, WSA_ERR_INVALID, std::string(cat ? "categorical" : "ordinal") + " head " + std::to_string(head) + " of " + std::to_string(n));
-    return WSA_OK;
-}
 
 // predict_db_nn runs a model over the stored rows as they are: the model's input count must be the DB's width
 wsa_status check_width(wsa_dbstats* db, const wsa_model* m) {
@@ -329,6 +294,7 @@ wsa_status wsa_featdb_dbstats_create(wsa_ctx* ctx, const wsa_featdb* src, uint32
 void wsa_dbstats_destroy(wsa_dbstats* db) {
     if (!db) return;
     (void)hipSetDevice(db->ctx->device);
+    if (db->eval.files) wsa_dbstats_destroy(db->eval.files);      // the file-level DB of wsa_dbstats_set_files
     delete db;
 }
 
@@ -395,8 +361,14 @@ wsa_status wsa_dbstats_predict_classes(wsa_dbstats* db, uint32_t head, const wsa
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!db->d_prob && !db->mem.alloc(&db->d_prob, (size_t)db->n_rows * WSA_MODEL_MAX_CLASSES))
         return fail(ctx, WSA_ERR_HIP, std::string("device allocation failed: ") + hipGetErrorString(hipGetLastError()));
+    if (!db->d_prob_key_rank && !db->mem.alloc(&db->d_prob_key_rank, (size_t)WSA_MODEL_MAX_CLASSES))
+        return fail(ctx, WSA_ERR_HIP, std::string("device allocation failed: ") + hipGetErrorString(hipGetLastError()));
     if (const wsa_status st = wsa_classify_rows(m, db->d_feat, db->n_rows, db->d_prob, stream)) return st;
     db->prob_classes = (uint32_t)C;
+    // kept for the per-file fold (K8e, wsa_dbstats_fold_files): whose probabilities these are, and the key order of their legend
+    db->prob_head = (int)head;
+    std::memcpy(db->prob_map, p.map, sizeof(db->prob_map));
+    HIP_TRY(ctx, hipMemcpyAsync(db->d_prob_key_rank, wsa_model_key_rank_internal(m), (size_t)C * sizeof(int64_t), hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream)));
     launch_decide(db, head, db->d_prob, (uint32_t)C, p, reinterpret_cast<hipStream_t>(stream));
     HIP_TRY(ctx, hipGetLastError());
     return WSA_OK;

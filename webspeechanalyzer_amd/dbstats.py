@@ -246,6 +246,212 @@ def stats_lines(table):
     return [" ".join(x.split()) for x in lines]
 
 
+# ---- evaluation beyond the panel: specification EV-1 (K8e is the device half, capi.FeatureDBStats.confusion / .agreement)
+def _ratio(a, b):
+    return a / b if b else math.nan                  # 0 / 0 stays NaN, as the panel's Accuracy does
+
+
+def confusion_metrics(matrix):
+    """matrix [V][V + 1] integers, m[true][predicted] with the blank predictions in column V -> dict(recall [V], precision [V], uar).
+    recall[t] = m[t][t] / (row t's sum, blanks included: a blank row is a missed row); precision[p] = m[p][p] / (column p's sum);
+    uar = the unweighted mean of the recalls of the classes that have a counted row (NaN without one)."""
+    m = [[int(x) for x in row] for row in matrix]
+    V = len(m)
+    rows = [sum(r) for r in m]
+    recall = [_ratio(m[t][t], rows[t]) for t in range(V)]
+    precision = [_ratio(m[p][p], sum(m[t][p] for t in range(V))) for p in range(V)]
+    have = [recall[t] for t in range(V) if rows[t]]
+    return dict(recall=recall, precision=precision, uar=_ratio(sum(have), len(have)))       # a plain in-order sum: js/dbstats.js adds the same way
+
+
+def assemble_confusion(columns, matrices):
+    """[{name, labels, matrix, recall, precision, uar}] per categorical head from K8e's matrices (plain lists; labels = the vocabulary,
+    whose order is the panel's: first appearance among the counted rows, then legend and predicted-only labels)."""
+    out = []
+    for col, m in zip(columns["cats"], matrices):
+        m = [[int(x) for x in row] for row in m]
+        out.append(dict(name=col["name"], labels=list(col["vocab"]), matrix=m, **confusion_metrics(m)))
+    return out
+
+
+def assemble_agreement(columns, agree):
+    """[{name, n, mean_true, mean_pred, var_true, var_pred, cov, ccc, pearson}] per ordinal head from K8e's records."""
+    keys = ("mean_true", "mean_pred", "var_true", "var_pred", "cov", "ccc", "pearson")
+    return [dict(name=col["name"], n=int(agree["n"][o]), **{k: float(agree[k][o]) for k in keys}) for o, col in enumerate(columns["ords"])]
+
+
+def _pct(x):
+    return to_fixed(x * 100, 2) + "%"
+
+
+def confusion_lines(confusion):
+    """Text in the style of stats_lines: per head the matrix over the classes that occur (a counted row or a prediction), one line per
+    true class with its recall, then the precisions and the UAR; percentages through to_fixed, 0 / 0 printed as NaN as the panel does."""
+    lines = []
+    for h in confusion:
+        m, V = h["matrix"], len(h["labels"])
+        used = [v for v in range(V) if sum(m[v]) or sum(m[t][v] for t in range(V))]
+        lines.append(f"Label: {h['name']}, Type: Class, Confusion")
+        lines.append("True \\ Predicted: " + ",".join([h["labels"][v] for v in used] + ["NaN"]))
+        for t in used:
+            lines.append(f"{h['labels'][t]} : " + " ".join(str(m[t][p]) for p in used + [V]) + f" recall: {_pct(h['recall'][t])}")
+        lines.append("Precision: " + ", ".join(f"{h['labels'][p]} {_pct(h['precision'][p])}" for p in used))
+        lines.append(f"UAR: {_pct(h['uar'])}")
+    return [" ".join(x.split()) for x in lines]
+
+
+def agreement_lines(agreement):
+    lines = []
+    for o in agreement:
+        lines.append(f"Label: {o['name']}, Type: Ordinal, Agreement")
+        lines.append(f"Pairs: {o['n']}")
+        lines.append(f"Mean: {to_fixed(o['mean_true'], 3)} true, {to_fixed(o['mean_pred'], 3)} predicted")
+        lines.append(f"Variance: {to_fixed(o['var_true'], 3)} true, {to_fixed(o['var_pred'], 3)} predicted, covariance {to_fixed(o['cov'], 3)}")
+        lines.append(f"CCC: {to_fixed(o['ccc'], 3)}")
+        lines.append(f"Pearson: {to_fixed(o['pearson'], 3)}")
+    return [" ".join(x.split()) for x in lines]
+
+
+def file_columns(db_rows):
+    """(file_of_row [n] i32, callback_of_row [n] i32, file names) from the rows' `file` and `seg`: files are numbered in order of first
+    appearance, a row without a file name gets -1; the callback is the integer part of the `seg` tag (String(si) at level 5,
+    String(si + k / 100) at levels 12 / 13), 0 where it is no number.  A file whose rows are not together makes file_of_row decrease,
+    which wsa_dbstats_set_files refuses naming the row."""
+    names, index = [], {}
+    file_of_row, callback_of_row = np.full(len(db_rows), -1, np.int32), np.zeros(len(db_rows), np.int32)
+    for i, r in enumerate(db_rows):
+        f = r.get("file")
+        if f is not None and f != "":
+            key = js_str(f)
+            if key not in index:
+                index[key] = len(names)
+                names.append(key)
+            file_of_row[i] = index[key]
+        si = parse_float(r.get("seg"))
+        callback_of_row[i] = int(math.floor(si)) if si == si and abs(si) < 2 ** 31 else 0
+    return file_of_row, callback_of_row, names
+
+
+def file_truths(columns, file_of_row, n_files):
+    """The host rule for a file's label: per head the label of the file's FIRST COUNTED row (true_idx >= 0; a true value that is neither
+    0 nor NaN); -1 / NaN for a file without one.  Returns ([true_idx [n_files]] per categorical head, [true_value [n_files]] per ordinal head)."""
+    cats = [np.full(n_files, -1, np.int32) for _ in columns["cats"]]
+    ords = [np.full(n_files, np.nan) for _ in columns["ords"]]
+    for h, c in enumerate(columns["cats"]):
+        for i in range(len(file_of_row) - 1, -1, -1):
+            if file_of_row[i] >= 0 and c["true_idx"][i] >= 0:
+                cats[h][file_of_row[i]] = c["true_idx"][i]
+    for o, c in enumerate(columns["ords"]):
+        for i in range(len(file_of_row) - 1, -1, -1):
+            v = c["true_value"][i]
+            if file_of_row[i] >= 0 and v == v and v != 0:
+                ords[o][file_of_row[i]] = v
+    return cats, ords
+
+
+def _level_result(col, cat, cls, od, matrices, agree):
+    table = assemble_table(col, cat, cls, od)
+    confusion = assemble_confusion(col, matrices)
+    agreement = assemble_agreement(col, agree) if col["ords"] else []
+    return dict(table=table, confusion=confusion, agreement=agreement,
+                lines=stats_lines(table) + confusion_lines(confusion) + agreement_lines(agreement))
+
+
+def evaluate(an, db_rows, class_labels, ordinal_labels, models=None, per_file=True, first_row=0, n_rows=None, stream=0):
+    """The evaluation of a labelled DB on the GPU (spec EV-1), from ONE device object: DS-1's table, a confusion matrix per categorical
+    head and the agreement (CCC, Pearson) per ordinal head, at row level and, with per_file, with a file as the row.
+    db_rows: rows as for stats_table, or a featdb.DeviceDB (its rows stay on the device); first_row / n_rows select a run of consecutive
+    rows of either (default: all; of a DeviceDB the run is copied device to device, wsa_featdb_dbstats_create).  models: {head name: a capi.Model, an
+    nnmodel.ModelSpec or a model directory}; a named head is predicted on the device (every row, as predict_db does, and the rows' `pred`
+    pairs are written by update_pred_label's rule); the other heads are evaluated on the predictions the rows hold.
+    Per file: a categorical head WITH a model is folded as the app folds a launch (K6b over the file's callbacks; the file's class is the
+    largest meter sum); one without a model has no probabilities to fold and its files stay blank.  An ordinal head's file value is RG-1's
+    running value over the rows' predictions.  A file's true label is that of its first counted row (file_truths).
+    Returns {rows: {table, confusion, agreement, lines}, files: the same over the files plus names, durations per file in the table's
+    classes, sums {head: [n_files][C]}, classes {head: [label or None]}, values {head: [..]}, folded {head: bool} — False for a
+    categorical head without a model: its file-level counts and matrix are all blank because nothing was folded, not because the model
+    abstained} (files: None without per_file)."""
+    from . import capi
+    cats, ords = head_settings(class_labels, ordinal_labels)
+    models = dict(models or {})
+    for name in models:
+        if not (any(name == c for c, _ in cats) or name in ords):
+            raise ValueError(f"models names the head {name!r}; the settings have {[c for c, _ in cats] + ords}")
+    records = getattr(db_rows, "records", db_rows)
+    if isinstance(db_rows, capi.FeatDB) and len(records) != db_rows.count:
+        raise ValueError(f"the device DB holds {db_rows.count} rows and {len(records)} records")
+    first_row = int(first_row)
+    n_rows = len(records) - first_row if n_rows is None else int(n_rows)
+    if first_row < 0 or n_rows < 0 or first_row + n_rows > len(records):
+        raise ValueError(f"rows {first_row} .. {first_row + n_rows} are outside the DB's {len(records)} rows")
+    records = records[first_row:first_row + n_rows]
+    if len(records) < 1:
+        raise ValueError("a feature DB has at least one row")
+    feat = None
+    if models:
+        if isinstance(db_rows, capi.FeatDB):
+            feat = db_rows
+        else:
+            feat = np.array([r["features"] for r in records], np.float64)
+    loaded = {name: _model_of(an, spec) for name, spec in models.items()}
+    try:
+        legends = {name: [js_str(x) for x in m.labels] for name, (m, _) in loaded.items() if any(name == c for c, _ in cats)}
+        col = build_columns(records, class_labels, ordinal_labels, legends)
+        if not col["cats"] and not col["ords"]:
+            empty = dict(table=dict(cats=[], ords=[]), confusion=[], agreement=[], lines=[])
+            return dict(rows=empty, files=None)
+        db = an.feature_db(feat, col["durations"], [len(c["vocab"]) for c in col["cats"]], len(col["ords"]),
+                           first_row=first_row if isinstance(feat, capi.FeatDB) else 0)
+        try:
+            for h, c in enumerate(col["cats"]):
+                db.set_classes(h, c["true_idx"], c["pred_idx"])
+            for o, c in enumerate(col["ords"]):
+                db.set_values(o, c["true_value"], c["pred_value"])
+            files = None
+            if per_file:
+                file_of_row, callback_of_row, names = file_columns(records)
+                if names:
+                    db.set_files(file_of_row, callback_of_row, len(names))
+                    t_cats, t_ords = file_truths(col, file_of_row, len(names))
+                    for h, t in enumerate(t_cats):
+                        db.set_file_classes(h, t)
+                    for o, t in enumerate(t_ords):
+                        db.set_file_values(o, t)
+                    files = dict(names=names, sums={}, classes={}, values={}, folded={c["name"]: c["name"] in loaded for c in col["cats"]})
+            for h, c in enumerate(col["cats"]):
+                if c["name"] not in loaded:
+                    continue
+                model = loaded[c["name"]][0]
+                legend = legends[c["name"]]
+                db.predict_classes(h, model, [c["vocab"].index(x) for x in legend], stream)
+                if files is not None:
+                    db.fold_files(h, stream)
+                    files["sums"][c["name"]] = db.file_sums(h, len(legend), stream)
+                    files["classes"][c["name"]] = [c["vocab"][i] if i >= 0 else None for i in db.file_classes(h, stream)]
+                for r, i in zip(records, db.pred_classes(h, stream)):
+                    update_pred_label(r, cats, ords, c["name"], c["vocab"][i] if i >= 0 else None)
+            for o, c in enumerate(col["ords"]):
+                if c["name"] in loaded:
+                    db.predict_values(o, loaded[c["name"]][0], None, None, stream)
+                    for r, v in zip(records, db.pred_values(o, stream)):
+                        update_pred_label(r, cats, ords, c["name"], float(v))
+                if files is not None:
+                    db.fold_file_values(o, stream)
+                    files["values"][c["name"]] = [float(v) for v in db.file_values(o, stream)]
+            n_cat = len(col["cats"])
+            rows = _level_result(col, *db.table(stream), [db.confusion(h, stream) for h in range(n_cat)], db.agreement(stream) if col["ords"] else None)
+            if files is not None:
+                files.update(_level_result(col, *db.file_table(stream), [db.file_confusion(h, stream) for h in range(n_cat)],
+                                           db.file_agreement(stream) if col["ords"] else None))
+        finally:
+            db.close()
+    finally:
+        for m, mine in loaded.values():
+            if mine:
+                m.close()
+    return dict(rows=rows, files=files)
+
+
 def update_pred_label(row, cats, ords, label, value):
     """localstore.js:723-769 on one row: slot 0 when `label` names a categorical head, else slot 1 when it names an ordinal head; the pair
     is stored in every case.  The value goes through JSON as the app's storage does: NaN / Infinity become null, -0 becomes 0."""

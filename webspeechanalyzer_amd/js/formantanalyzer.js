@@ -448,6 +448,16 @@ function dbstats_device() {
       return ords ? nat.dbPredict(ctx, m, x, true, handle.spec.outMin, handle.spec.outMax) : nat.dbPredict(ctx, m, x, false);
     },
     table(col) { return nat.dbTable(ctx, col); },
+    evaluate(spec, catHandles, ordHandles) {
+      const native_of = (handle) => {
+        if (!handle) return null;
+        if (!loaded_models.has(handle) || handle.released) throw 'evaluateDB: the model handle was released (shutdown()) or is not one of loadModel / trainModel / trainRegression';
+        let m = handle.natives.get(ctx);
+        if (!m) { m = nat.modelCreate(ctx, handle.spec); handle.natives.set(ctx, m); }
+        return m;
+      };
+      return nat.dbEval(ctx, Object.assign({}, spec, { catModels: catHandles.map(native_of), ordModels: ordHandles.map(native_of) }));
+    },
   };
 }
 function predictDB(featureDB, o) {
@@ -457,6 +467,17 @@ function predictDB(featureDB, o) {
   return require('./dbstats.js').predictDB(dbstats_device(), featureDB, o);
 }
 function statsTable(featureDB, o) { return require('./dbstats.js').statsTable(dbstats_device(), featureDB, o || {}); }
+// evaluateDB(featureDB, {db, classLabels, ordinalLabels, models: {head name: model handle | model directory}, perFile}) -> {rows, files}: beyond the
+// panel (specification EV-1 / K8e, include/wsa_eval.h, the addon's dbEval): DS-1's table, a confusion matrix per categorical head (recall, precision,
+// UAR) and CCC / Pearson per ordinal head, per row and per file — a file's class from the app's own fold over the file's callbacks, its value the
+// running value; the same structure as webspeechanalyzer_amd.dbstats.evaluate, as plain JSON-able data with the text lines.
+function evaluateDB(featureDB, o) {
+  o = Object.assign({}, o || {});
+  const models = {};
+  for (const name of Object.keys(o.models || {})) models[name] = typeof o.models[name] === 'string' ? loadModel(o.models[name]) : o.models[name];
+  o.models = models;
+  return require('./dbstats.js').evaluateDB(dbstats_device(), featureDB, o);
+}
 // ---- the app's ml5 KNN classifier (ref src/neuralmodel.js:729-837 train_knn; specification KN-1 / K9, include/wsa.h "KNN classifier"; js/knn.js).
 // KNNClassifier(width, capacity) -> ml5.KNNClassifier()'s addExample / classify / getCountByLabel on the device (classify is synchronous and
 //   returns ml5's result object; addExamples / classifyMultiple take many rows at once);
@@ -1381,5 +1402,5 @@ function set_predicted_label_for_segment(si, idx, label) {                      
 
 module.exports = { configure, LaunchAudioNodes, StopAudioNodes, set_predicted_label_for_segment, LaunchBatch, LaunchBatches,
   StreamOpen, decodePcm, STREAM_ACTIVE, STREAM_START, STREAM_STOP, shutdown, allocPinned, freePinned,
-  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, _clip_length: clip_length, _values_after: values_after, loadModel, setPredictionModel, setPredictionModels, setPredictionKnn, setPredictionValues, trainModel, trainModels, saveModel, trainRegression, predictValues, predictDB, statsTable,
+  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, _clip_length: clip_length, _values_after: values_after, loadModel, setPredictionModel, setPredictionModels, setPredictionKnn, setPredictionValues, trainModel, trainModels, saveModel, trainRegression, predictValues, predictDB, statsTable, evaluateDB,
   KNNClassifier, trainKnn, predictKnn, createDeviceDB, setCollectDB };

@@ -50,6 +50,7 @@
 #include <string.h>
 #include <pthread.h>
 #include "../../include/wsa.h"
+#include "../../include/wsa_eval.h"
 
 #define NAPI_OK(env, call) do { if ((call) != napi_ok) { napi_throw_error((env), NULL, "N-API call failed: " #call); return NULL; } } while (0)
 
@@ -1647,6 +1648,153 @@ done:
     return res;
 }
 
+/* ---- evaluating a labelled DB beyond the panel (include/wsa_eval.h, K8e, specification EV-1): one synchronous call that builds the device object,
+ * predicts the heads that have a model, folds per file and returns every table; js/dbstats.js resolves the strings and assembles the result.
+ *   dbEval(ctx, {durations, vocab, trueIdx, predIdx, trueVal, predVal (as dbTable),
+ *                features: Float64Array [n][width], width (only with models), catModels: [model | null] per categorical head, catMaps: Int32Array [nCat][64]
+ *                legend -> vocabulary, ordModels: [model | null] per ordinal head, ordRange: Float64Array [nOrd][2],
+ *                nFiles (0: no file level), fileOfRow, callbackOfRow: Int32Array [n], fileTrueIdx: Int32Array [nCat][nFiles], fileTrueVal: Float64Array [nOrd][nFiles]})
+ *     -> {rows: {cat, cls, ord (as dbTable), conf: Float64Array, every head's [V][V + 1] one after the other, agree: Float64Array [nOrd][8] n, mean_true, mean_pred,
+ *         var_true, var_pred, cov, ccc, pearson}, predIdx: Int32Array [nCat][n], predVal: Float64Array [nOrd][n] (after the predictions),
+ *         files: null | {cat, cls, ord, conf, agree, idx: Int32Array [nCat][nFiles], val: Float64Array [nOrd][nFiles], sums: [Float64Array [nFiles][C] | null]}} */
+static int set_typed(napi_env env, napi_value o, const char *name, napi_typedarray_type type, const void *src, size_t count, size_t elt) {
+    napi_value v = make_typed(env, type, src, count, elt);
+    return v && napi_set_named_property(env, o, name, v) == napi_ok;
+}
+/* one level's tables into a new object: files = 0 the rows, 1 the files */
+static napi_value eval_level(napi_env env, ctx_box *box, wsa_dbstats *db, int files, size_t n_cat, const uint32_t *vocab, size_t n_ord, wsa_status *st) {
+    size_t items = 0, cells = 0;
+    for (size_t h = 0; h < n_cat; h++) { items += vocab[h]; cells += (size_t)vocab[h] * (vocab[h] + 1); }
+    wsa_dbstats_cat *cat = calloc(n_cat ? n_cat : 1, sizeof *cat); wsa_dbstats_class *cls = calloc(items ? items : 1, sizeof *cls);
+    wsa_dbstats_ord *od = calloc(n_ord ? n_ord : 1, sizeof *od); wsa_dbstats_agree *ag = calloc(n_ord ? n_ord : 1, sizeof *ag);
+    uint64_t *m = calloc(cells ? cells : 1, sizeof *m);
+    double *flat = calloc(n_cat * 3 + items * 5 + n_ord * 5 + cells + n_ord * 8 + 1, sizeof(double));
+    napi_value res = NULL;
+    if (!(cat && cls && od && ag && m && flat)) { *st = WSA_ERR_INVALID; napi_throw_error(env, NULL, "out of memory"); goto done; }
+    *st = files ? wsa_dbstats_file_table(db, box->queue, cat, cls, od) : wsa_dbstats_table(db, box->queue, cat, cls, od);
+    for (size_t h = 0, off = 0; *st == WSA_OK && h < n_cat; off += (size_t)vocab[h] * (vocab[h] + 1), h++)
+        *st = files ? wsa_dbstats_file_confusion(db, (uint32_t)h, box->queue, m + off) : wsa_dbstats_confusion(db, (uint32_t)h, box->queue, m + off);
+    if (*st == WSA_OK && n_ord) *st = files ? wsa_dbstats_file_agreement(db, box->queue, ag) : wsa_dbstats_agreement(db, box->queue, ag);
+    if (*st != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(box->ctx)); goto done; }
+    {
+        double *fc = flat, *fk = fc + n_cat * 3, *fo = fk + items * 5, *fm = fo + n_ord * 5, *fa = fm + cells;
+        for (size_t h = 0; h < n_cat; h++) { fc[h * 3] = (double)cat[h].correct; fc[h * 3 + 1] = (double)cat[h].wrong; fc[h * 3 + 2] = (double)cat[h].blank; }
+        for (size_t i = 0; i < items; i++) {
+            fk[i * 5] = (double)cls[i].count; fk[i * 5 + 1] = (double)cls[i].correct; fk[i * 5 + 2] = (double)cls[i].wrong;
+            fk[i * 5 + 3] = cls[i].duration; fk[i * 5 + 4] = (double)cls[i].first_row;
+        }
+        for (size_t o = 0; o < n_ord; o++) {
+            fo[o * 5] = (double)od[o].true_n; fo[o * 5 + 1] = (double)od[o].pred_n; fo[o * 5 + 2] = od[o].min; fo[o * 5 + 3] = od[o].max; fo[o * 5 + 4] = od[o].sq_sum;
+            fa[o * 8] = (double)ag[o].n; fa[o * 8 + 1] = ag[o].mean_true; fa[o * 8 + 2] = ag[o].mean_pred; fa[o * 8 + 3] = ag[o].var_true;
+            fa[o * 8 + 4] = ag[o].var_pred; fa[o * 8 + 5] = ag[o].cov; fa[o * 8 + 6] = ag[o].ccc; fa[o * 8 + 7] = ag[o].pearson;
+        }
+        for (size_t i = 0; i < cells; i++) fm[i] = (double)m[i];
+        if (napi_create_object(env, &res) != napi_ok ||
+            !set_typed(env, res, "cat", napi_float64_array, fc, n_cat * 3, sizeof(double)) || !set_typed(env, res, "cls", napi_float64_array, fk, items * 5, sizeof(double)) ||
+            !set_typed(env, res, "ord", napi_float64_array, fo, n_ord * 5, sizeof(double)) || !set_typed(env, res, "conf", napi_float64_array, fm, cells, sizeof(double)) ||
+            !set_typed(env, res, "agree", napi_float64_array, fa, n_ord * 8, sizeof(double))) { res = NULL; *st = WSA_ERR_INVALID; napi_throw_error(env, NULL, "dbEval: result allocation failed"); }
+    }
+done:
+    free(cat); free(cls); free(od); free(ag); free(m); free(flat);
+    return res;
+}
+/* element i of the array property `name`: a live model of this context, NULL for null / undefined; *bad set when it is anything else */
+static model_box *eval_model(napi_env env, napi_value spec, const char *name, uint32_t i, ctx_box *box, int *bad) {
+    napi_value arr, el; bool has = false, is_arr = false; napi_valuetype t; void *p = NULL; uint32_t len = 0;
+    if (napi_has_named_property(env, spec, name, &has) != napi_ok || !has) return NULL;
+    if (napi_get_named_property(env, spec, name, &arr) != napi_ok || napi_is_array(env, arr, &is_arr) != napi_ok || !is_arr || napi_get_array_length(env, arr, &len) != napi_ok) { *bad = 1; return NULL; }
+    if (i >= len || napi_get_element(env, arr, i, &el) != napi_ok || napi_typeof(env, el, &t) != napi_ok) { *bad = 1; return NULL; }
+    if (t == napi_null || t == napi_undefined) return NULL;
+    if (t != napi_external || napi_get_value_external(env, el, &p) != napi_ok || !p || !((model_box *)p)->m || ((model_box *)p)->owner != box) { *bad = 1; return NULL; }
+    return (model_box *)p;
+}
+static napi_value fn_db_eval(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ctx_box *box = argc ? get_box(env, argv[0]) : NULL;
+    const char *usage = "dbEval(ctx, {durations, vocab, trueIdx, predIdx, trueVal, predVal, [features, width, catModels, catMaps, ordModels, ordRange], [nFiles, fileOfRow, callbackOfRow, fileTrueIdx, fileTrueVal]})";
+    double *dur = NULL, *tv = NULL, *pv = NULL, *feat = NULL, *range = NULL, *ftv = NULL; uint32_t *vocab = NULL; int32_t *ti = NULL, *pi = NULL, *maps = NULL, *fo = NULL, *co = NULL, *fti = NULL;
+    size_t n = 0, n_cat = 0, nti = 0, npi = 0, ntv = 0, npv = 0, nfeat = 0, nmaps = 0, nrange = 0, nfo = 0, nco = 0, nfti = 0, nftv = 0;
+    uint32_t width = 0, n_files = 0; napi_value v;
+    wsa_dbstats *db = NULL;
+    napi_value res = NULL, rows = NULL, files = NULL, sums = NULL;
+    int32_t *idx = NULL; double *val = NULL, *fs = NULL;
+    wsa_status st = WSA_OK;
+    if (!box || !box->ctx || argc < 2 || !typed_of(env, argv[1], "durations", napi_float64_array, (void **)&dur, &n) ||
+        !typed_of(env, argv[1], "vocab", napi_uint32_array, (void **)&vocab, &n_cat) || !typed_of(env, argv[1], "trueIdx", napi_int32_array, (void **)&ti, &nti) ||
+        !typed_of(env, argv[1], "predIdx", napi_int32_array, (void **)&pi, &npi) || !typed_of(env, argv[1], "trueVal", napi_float64_array, (void **)&tv, &ntv) ||
+        !typed_of(env, argv[1], "predVal", napi_float64_array, (void **)&pv, &npv) || n < 1 || n > 0xffffffffu || nti != n_cat * n || npi != nti || ntv % n || npv != ntv) {
+        napi_throw_type_error(env, NULL, usage); return NULL;
+    }
+    const size_t n_ord = ntv / n;
+    if (n_cat > WSA_DBSTATS_MAX_HEADS || n_ord > WSA_DBSTATS_MAX_HEADS) { napi_throw_type_error(env, NULL, usage); return NULL; }
+    if (napi_get_named_property(env, argv[1], "nFiles", &v) == napi_ok) (void)napi_get_value_uint32(env, v, &n_files);
+    if (napi_get_named_property(env, argv[1], "width", &v) == napi_ok) (void)napi_get_value_uint32(env, v, &width);
+    const int with_feat = typed_of(env, argv[1], "features", napi_float64_array, (void **)&feat, &nfeat);
+    if (with_feat && (!width || nfeat != n * (size_t)width)) { napi_throw_type_error(env, NULL, usage); return NULL; }
+    (void)typed_of(env, argv[1], "catMaps", napi_int32_array, (void **)&maps, &nmaps);
+    (void)typed_of(env, argv[1], "ordRange", napi_float64_array, (void **)&range, &nrange);
+    if (n_files && (!typed_of(env, argv[1], "fileOfRow", napi_int32_array, (void **)&fo, &nfo) || !typed_of(env, argv[1], "callbackOfRow", napi_int32_array, (void **)&co, &nco) ||
+                    !typed_of(env, argv[1], "fileTrueIdx", napi_int32_array, (void **)&fti, &nfti) || !typed_of(env, argv[1], "fileTrueVal", napi_float64_array, (void **)&ftv, &nftv) ||
+                    nfo != n || nco != n || nfti != n_cat * n_files || nftv != n_ord * n_files)) { napi_throw_type_error(env, NULL, usage); return NULL; }
+    model_box *cm[WSA_DBSTATS_MAX_HEADS] = {0}, *om[WSA_DBSTATS_MAX_HEADS] = {0};
+    int bad = 0, any = 0;
+    for (size_t h = 0; h < n_cat; h++) cm[h] = eval_model(env, argv[1], "catModels", (uint32_t)h, box, &bad);
+    for (size_t o = 0; o < n_ord; o++) om[o] = eval_model(env, argv[1], "ordModels", (uint32_t)o, box, &bad);
+    if (bad) { napi_throw_error(env, NULL, "dbEval: catModels / ordModels hold one model handle of this context, or null, per head"); return NULL; }
+    for (size_t h = 0; h < WSA_DBSTATS_MAX_HEADS; h++) any |= cm[h] != NULL || om[h] != NULL;
+    if (any && (!with_feat || nmaps != n_cat * WSA_MODEL_MAX_CLASSES || nrange != n_ord * 2)) { napi_throw_type_error(env, NULL, usage); return NULL; }
+
+    const size_t longest = n > n_files ? n : n_files;
+    idx = calloc(n_cat * longest + 1, sizeof *idx); val = calloc(n_ord * longest + 1, sizeof *val);
+    fs = calloc((size_t)(n_files ? n_files : 1) * WSA_MODEL_MAX_CLASSES, sizeof *fs);
+    if (!idx || !val || !fs) { napi_throw_error(env, NULL, "out of memory"); goto done; }
+    st = with_feat ? wsa_wide_dbstats_create(box->ctx, feat, width, dur, (uint32_t)n, (uint32_t)n_cat, vocab, (uint32_t)n_ord, &db)
+                   : wsa_dbstats_create(box->ctx, NULL, dur, (uint32_t)n, (uint32_t)n_cat, vocab, (uint32_t)n_ord, &db);
+    for (size_t h = 0; st == WSA_OK && h < n_cat; h++) st = wsa_dbstats_set_classes(db, (uint32_t)h, ti + h * n, pi + h * n);
+    for (size_t o = 0; st == WSA_OK && o < n_ord; o++) st = wsa_dbstats_set_values(db, (uint32_t)o, tv + o * n, pv + o * n);
+    if (st == WSA_OK && n_files) st = wsa_dbstats_set_files(db, fo, co, n_files);
+    for (size_t h = 0; st == WSA_OK && n_files && h < n_cat; h++) st = wsa_dbstats_set_file_classes(db, (uint32_t)h, fti + h * n_files);
+    for (size_t o = 0; st == WSA_OK && n_files && o < n_ord; o++) st = wsa_dbstats_set_file_values(db, (uint32_t)o, ftv + o * n_files);
+    if (st == WSA_OK && n_files && napi_create_array_with_length(env, n_cat, &sums) != napi_ok) { napi_throw_error(env, NULL, "dbEval: result allocation failed"); goto done; }
+    for (size_t h = 0; st == WSA_OK && h < n_cat; h++) {       /* a head is folded right after its prediction: the fold reads the probabilities that call kept */
+        napi_value s_h = NULL;
+        if (cm[h]) {
+            st = wsa_dbstats_predict_classes(db, (uint32_t)h, cm[h]->m, maps + h * WSA_MODEL_MAX_CLASSES, box->queue);
+            if (st == WSA_OK && n_files) st = wsa_dbstats_fold_files(db, (uint32_t)h, box->queue);
+            if (st == WSA_OK && n_files) st = wsa_dbstats_copy_file_sums(db, (uint32_t)h, box->queue, fs, cm[h]->n_classes);
+            if (st == WSA_OK && n_files) s_h = make_typed(env, napi_float64_array, fs, (size_t)n_files * cm[h]->n_classes, sizeof(double));
+        }
+        if (st == WSA_OK && n_files) { if (!s_h) napi_get_null(env, &s_h); napi_set_element(env, sums, (uint32_t)h, s_h); }
+    }
+    for (size_t o = 0; st == WSA_OK && o < n_ord; o++) {
+        if (om[o]) st = wsa_dbstats_predict_values(db, (uint32_t)o, om[o]->m, range[o * 2], range[o * 2 + 1], box->queue);
+        if (st == WSA_OK && n_files) st = wsa_dbstats_fold_file_values(db, (uint32_t)o, box->queue);
+    }
+    for (size_t h = 0; st == WSA_OK && h < n_cat; h++) st = wsa_dbstats_copy_classes(db, (uint32_t)h, box->queue, idx + h * n);
+    for (size_t o = 0; st == WSA_OK && o < n_ord; o++) st = wsa_dbstats_copy_values(db, (uint32_t)o, box->queue, val + o * n);
+    if (st != WSA_OK) { napi_throw_error(env, NULL, wsa_last_error(box->ctx)); goto done; }
+    if (napi_create_object(env, &res) != napi_ok || !set_typed(env, res, "predIdx", napi_int32_array, idx, n_cat * n, sizeof(int32_t)) ||
+        !set_typed(env, res, "predVal", napi_float64_array, val, n_ord * n, sizeof(double))) { res = NULL; napi_throw_error(env, NULL, "dbEval: result allocation failed"); goto done; }
+    rows = eval_level(env, box, db, 0, n_cat, vocab, n_ord, &st);
+    if (!rows) { res = NULL; goto done; }
+    napi_set_named_property(env, res, "rows", rows);
+    if (n_files) {
+        files = eval_level(env, box, db, 1, n_cat, vocab, n_ord, &st);
+        if (!files) { res = NULL; goto done; }
+        for (size_t h = 0; st == WSA_OK && h < n_cat; h++) st = wsa_dbstats_copy_file_classes(db, (uint32_t)h, box->queue, idx + h * n_files);
+        for (size_t o = 0; st == WSA_OK && o < n_ord; o++) st = wsa_dbstats_copy_file_values(db, (uint32_t)o, box->queue, val + o * n_files);
+        if (st != WSA_OK) { res = NULL; napi_throw_error(env, NULL, wsa_last_error(box->ctx)); goto done; }
+        if (!set_typed(env, files, "idx", napi_int32_array, idx, n_cat * n_files, sizeof(int32_t)) || !set_typed(env, files, "val", napi_float64_array, val, n_ord * n_files, sizeof(double)) ||
+            napi_set_named_property(env, files, "sums", sums) != napi_ok) { res = NULL; napi_throw_error(env, NULL, "dbEval: result allocation failed"); goto done; }
+    } else napi_get_null(env, &files);
+    napi_set_named_property(env, res, "files", files);
+done:
+    if (db) wsa_dbstats_destroy(db);
+    free(idx); free(val); free(fs);
+    return res;
+}
+
 /* ---- the feature DB that stays on the device (wsa_featdb_*, K10, specification FD-1).  Every call is synchronous, on the context's own stream.
  *   featdbCreate(ctx, width, capacity) -> handle;  featdbDestroy(handle);  featdbCount(handle) -> rows held
  *   featdbAppendBatch(ctx, db) -> {first, kept: Int32Array}: the rows of the context's last processBatch that the app's storing keeps
@@ -2083,7 +2231,7 @@ NAPI_MODULE_INIT() {
         {"geometry", fn_geometry}, {"allocPinned", fn_alloc_pinned}, {"binsHz", fn_bins_hz}, {"processBatch", fn_process_batch}, {"gatherRows", fn_gather_rows},
         {"streamOpen", fn_stream_open}, {"streamOpenMixed", fn_stream_open_mixed}, {"streamInfo", fn_stream_info}, {"streamPaced", fn_stream_paced}, {"streamInput", fn_stream_input}, {"streamSetInput", fn_stream_set_input}, {"decodePcm", fn_decode_pcm}, {"streamStep", fn_stream_step}, {"streamClose", fn_stream_close}, {"streamSetModel", fn_stream_set_model}, {"streamSetEnsemble", fn_stream_set_ensemble}, {"streamSetKnn", fn_stream_set_knn},
         {"modelCreate", fn_model_create}, {"modelDestroy", fn_model_destroy}, {"train", fn_train}, {"trainGroup", fn_train_group}, {"regressRows", fn_regress_rows},
-        {"dbPredict", fn_db_predict}, {"dbTable", fn_db_table},
+        {"dbPredict", fn_db_predict}, {"dbTable", fn_db_table}, {"dbEval", fn_db_eval},
         {"knnCreate", fn_knn_create}, {"knnDestroy", fn_knn_destroy}, {"knnAdd", fn_knn_add}, {"knnClassify", fn_knn_classify}, {"batchKnn", fn_batch_knn}, {"batchKnnFold", fn_batch_knn_fold},
         {"streamSetRegress", fn_stream_set_regress}, {"batchRegressGroup", fn_batch_regress_group},
         {"featdbCreate", fn_featdb_create}, {"featdbDestroy", fn_featdb_destroy}, {"featdbCount", fn_featdb_count}, {"featdbAppendBatch", fn_featdb_append_batch},
