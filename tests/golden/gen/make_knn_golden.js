@@ -10,6 +10,8 @@
 //     predictClass itself makes — as insertion indices in selection order;
 //   * per evaluation job: the (correct, all) figure of the app's train_knn procedure (ref src/neuralmodel.js:761-828), whose loop
 //     over rows is restated here around ml5's addExample / classify (the function itself needs the app's storage module and DOM).
+// make_knn_golden.py --exact sends the hand-built exact rows of tests/knn_exact_cases.py through run_case as they are, with each row's
+// class index as a NUMBER label (ml5 takes a number as the class id itself), for tests/golden/knn_exact_expected.json.
 // /root/reference does not exist on the GPU box: only tests/golden/gen/make_knn_golden.py runs this script.
 //
 // usage: node make_knn_golden.js job.json out.json

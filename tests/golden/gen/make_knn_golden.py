@@ -13,12 +13,24 @@ row and its double).  A case that fails it is redrawn with the next seed.  D = m
 is recorded: the tests' bounds refer to it.
 
     python3 tests/golden/gen/make_knn_golden.py
+
+With --exact it writes tests/golden/knn_exact_expected.json instead: what ml5 computes on the hand-built exact rows of
+tests/knn_exact_cases.py (every case marked ml5: no NaN rows, no out-of-range class, not the query-grid case), named by case key only —
+the rows are rebuilt from the cases file.  A row's class index goes to ml5 as a NUMBER label, which ml5 takes as the class id itself.  Per
+case: ml5's similarities [q, n] in insertion order, and per k classify()'s labels [q], its confidences [q, classes the store holds,
+ascending] and the neighbours tf.topk picks [q, k_eff] in selection order — the tables as the bytes of little-endian f32 / f64 / i16
+(zlib, base64: they are mostly zeros and repeats, and the file stays small).
+There is no margin condition: the arithmetic on these rows is exact, for tfjs too (tests/test_knn_exact_reference.py asserts it).
+
+    python3 tests/golden/gen/make_knn_golden.py --exact
 """
+import base64
 import json
 import os
 import subprocess
 import sys
 import tempfile
+import zlib
 
 import numpy as np
 
@@ -115,5 +127,32 @@ def main():
     print("wrote", path, os.path.getsize(path), "bytes; D =", D)
 
 
+def exact_main():
+    from tests import knn_exact_cases as kc
+    fixture = dict(cases={})
+    for key, c in kc.CASES.items():
+        if not c["ml5"]:
+            continue
+        out = run_node([dict(key=key, store=c["store"].tolist(), labels=[int(x) for x in c["cls"]], queries=c["queries"].tolist(), ks=list(c["ks"]))], [])
+        got = out["cases"][0]
+        for f in ("generator", "node", "ml5", "tfjs", "backend"):
+            fixture[f] = out[f]
+        assert got["class_index"] == [sorted(set(c["cls"].tolist())).index(int(x)) for x in c["cls"]], key
+        grouped = np.array(got["grouped"])
+        sims = np.zeros((len(c["queries"]), len(grouped)), np.float32)
+        sims[:, grouped] = np.array(got["sims"], np.float32)              # ml5's grouped order -> insertion order
+        def pack(a, dtype):
+            return base64.b64encode(zlib.compress(np.asarray(a).astype(dtype).tobytes(), 9)).decode()
+        res = got["results"]                                              # per query, per k -> per k: [q] labels, [q, classes] f64, [q, k_eff] i16
+        fixture["cases"][key] = dict(class_keys=got["class_keys"], sims_f32_zlib_b64=pack(sims, "<f4"),
+                                     results={str(k): dict(label=[int(r[str(k)]["label"]) for r in res], conf_f64_zlib_b64=pack([r[str(k)]["conf"] for r in res], "<f8"),
+                                                           nbr_i16_zlib_b64=pack([r[str(k)]["nbr"] for r in res], "<i2")) for k in c["ks"]})
+        print(key, sims.shape)
+    path = os.path.join(GOLD, "knn_exact_expected.json")
+    with open(path, "w") as f:
+        json.dump(fixture, f, separators=(",", ":"))
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(exact_main() if "--exact" in sys.argv[1:] else main())
