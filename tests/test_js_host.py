@@ -721,7 +721,7 @@ fa.LaunchBatch(clips, () => {{}}).then(() => {{ out.first = 'resolved'; }}, (e) 
 
 @pytest.mark.gpu
 def test_addon_context_handle_is_safe_after_destroy():
-    """napi/wsa_napi.c: the JS handle of a context is a box that outlives wsa_destroy — destroy() is refused while a stream created from the
+    """napi/napi_handles.c: the JS handle of a context is a box that outlives wsa_destroy — destroy() is refused while a stream created from the
     context is open, a second destroy() is a no-op and any use of the handle afterwards throws instead of touching freed memory."""
     import torch
     if not torch.cuda.is_available():
