@@ -356,6 +356,16 @@ EVAL_TABLE = {
     "wsa_dbstats_copy_file_values": (st, [vp, u32, vp, vp]),
 }
 EVAL_SYMBOLS = list(EVAL_TABLE)
+# the same for include/wsa_crossval.h (additions within version 5, probe for wsa_dbstats_set_folds): held-out prediction (K6f, spec CV-1);
+# tests/test_crossval_host.py holds this one to its header
+CROSSVAL_MAX_FOLDS = 32    # WSA_CROSSVAL_MAX_FOLDS (= WSA_TRAIN_GROUP_MAX)
+CROSSVAL_TABLE = {
+    "wsa_dbstats_set_folds": (st, [vp, vp, u32]),
+    "wsa_dbstats_predict_classes_folds": (st, [vp, u32, vp, u32, vp, vp]),
+    "wsa_dbstats_predict_values_folds": (st, [vp, u32, vp, u32, vp, vp, vp]),
+    "wsa_crossval_tiles": (st, [vp, vp, u32, vp]),
+}
+CROSSVAL_SYMBOLS = list(CROSSVAL_TABLE)
 
 _LIB = None
 
@@ -390,7 +400,7 @@ def lib():
     L.wsa_abi_version.restype = ctypes.c_int
     if L.wsa_abi_version() != ABI_VERSION:
         raise WsaError(f"{path} has ABI version {L.wsa_abi_version()}, this binding is written against {ABI_VERSION} (include/wsa.h): rebuild the library")
-    for name, (restype, argtypes) in list(ABI_TABLE.items()) + list(EVAL_TABLE.items()):
+    for name, (restype, argtypes) in list(ABI_TABLE.items()) + list(EVAL_TABLE.items()) + list(CROSSVAL_TABLE.items()):
         f = getattr(L, name)
         f.restype, f.argtypes = restype, argtypes
     from .debug import DEBUG_TABLE

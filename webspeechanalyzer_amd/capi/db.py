@@ -3,7 +3,7 @@ import ctypes
 
 import numpy as np
 
-from ._abi import lib
+from ._abi import CROSSVAL_MAX_FOLDS, WsaError, lib
 from ._util import _Handle
 from .training import Trainer
 
@@ -21,6 +21,7 @@ class FeatureDBStats(_Handle):
 
     _destroy = "wsa_dbstats_destroy"
     n_files = 0               # until set_files
+    n_folds = 0               # until set_folds
 
     def __init__(self, an, features, durations, vocab_sizes=(), n_ord=0, first_row=0):
         """first_row: with a FeatDB as `features`, the DB row of the first of the len(durations) rows taken"""
@@ -85,6 +86,40 @@ class FeatureDBStats(_Handle):
         """K6 with the regression epilogue into the head's predicted column (enqueues); the range defaults to the spec's own."""
         lo, hi = model.out_range(out_min, out_max)
         self.an._check(self.L.wsa_dbstats_predict_values(self.h, int(head), model.h, lo, hi, stream))
+
+    # ---- held-out prediction (K6f, spec CV-1; include/wsa_crossval.h)
+    def set_folds(self, fold_of_row, n_folds):
+        """fold_of_row [n] i32 (-1: the row is never held out and never predicted; else 0 .. n_folds - 1), n_folds 2 .. 32; set once."""
+        f = self._column(fold_of_row, np.int32, "fold_of_row")
+        self.an._check(self.L.wsa_dbstats_set_folds(self.h, f.ctypes.data, int(n_folds)))
+        self.n_folds = int(n_folds)
+
+    @staticmethod
+    def _members(models):
+        models = list(models)
+        return models, (ctypes.c_void_p * max(len(models), 1))(*[m.h if m is not None else None for m in models])
+
+    def predict_classes_folds(self, head, models, legend_to_vocab, stream=0):
+        """predict_classes with models[k] over the rows of fold k, in one launch of K6f; rows without a fold get zero probabilities and
+        are decided blank (enqueues).  The models share one legend."""
+        models, arr = self._members(models)
+        m = self._map(legend_to_vocab)
+        if models and models[0] is not None and m.shape != (models[0].n_classes,):
+            raise ValueError(f"legend_to_vocab has shape {m.shape}, the models have {models[0].n_classes} classes")
+        self.an._check(self.L.wsa_dbstats_predict_classes_folds(self.h, int(head), ctypes.cast(arr, ctypes.c_void_p), len(models), m.ctypes.data, stream))
+
+    def predict_values_folds(self, head, models, ranges=None, stream=0):
+        """predict_values with models[k] and its own range over the rows of fold k, in one launch of K6f; rows without a fold get NaN
+        (enqueues).  ranges: one (out_min, out_max) per model, None: the spec's own."""
+        models, arr = self._members(models)
+        ranges = list(ranges) if ranges is not None else [None] * len(models)
+        if len(ranges) != len(models):
+            raise ValueError("one (out_min, out_max) per model")
+        lo_hi = [m.out_range(*(r if r is not None else (None, None))) if m is not None else (0.0, 1.0) for m, r in zip(models, ranges)]
+        n = max(len(models), 1)
+        lo, hi = (ctypes.c_double * n)(*[a for a, _ in lo_hi]), (ctypes.c_double * n)(*[b for _, b in lo_hi])
+        self.an._check(self.L.wsa_dbstats_predict_values_folds(self.h, int(head), ctypes.cast(arr, ctypes.c_void_p), len(models),
+                                                               ctypes.cast(lo, ctypes.c_void_p), ctypes.cast(hi, ctypes.c_void_p), stream))
 
     def table(self, stream=0):
         """Synchronises; (cat [n_cat], cls [sum V], ord [n_ord]) as numpy records (wsa_dbstats_cat / _class / _ord)."""
@@ -187,6 +222,19 @@ class FeatureDBStats(_Handle):
         out = np.zeros((self.n_rows, int(n_classes)), np.float32)
         self.an._check(self.L.wsa_dbstats_copy_probs(self.h, stream, out.ctypes.data, int(n_classes)))
         return out
+
+
+def crossval_tiles(rows_per_fold, rb):
+    """wsa_crossval_tiles: the (member, tile) pairs of one K6f launch from the folds' row counts and the members' row-block factors
+    (1, 2 or 4) alone; needs no device."""
+    n, b = np.ascontiguousarray(rows_per_fold, np.uint32), np.ascontiguousarray(rb, np.int32)
+    if n.ndim != 1 or n.shape != b.shape:
+        raise ValueError(f"rows_per_fold {n.shape} / rb {b.shape}: expected one of each per fold")
+    out = ctypes.c_uint64()
+    st = lib().wsa_crossval_tiles(n.ctypes.data if len(n) else None, b.ctypes.data if len(b) else None, len(n), ctypes.byref(out))
+    if st != 0:
+        raise WsaError(f"wsa_crossval_tiles refused the shapes ({st}): 1 .. {CROSSVAL_MAX_FOLDS} folds, rb 1, 2 or 4")
+    return int(out.value)
 
 
 class FeatDB(_Handle):

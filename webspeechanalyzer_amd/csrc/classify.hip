@@ -1,4 +1,5 @@
-// classify.hip — K6 (the app's dense classifier over feature rows, f32 MFMA), its grouped form K6e, the model and ensemble objects
+// classify.hip — K6 (the app's dense classifier over feature rows, f32 MFMA), its grouped forms K6e (every member over every row) and
+// K6f (every member over its own row list, crossval.hip), the model and ensemble objects
 // and the row-wise part of the C ABI (include/wsa.h "Syllable classification").  The per-callback fold K6b is classify_fold.hpp,
 // run over a batch by classify_batch.hip and inside a stream step by classify_stream.hip.
 //
@@ -43,11 +44,13 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // row = 4 (l>>4) + i.  S = 64 j + 4 keeps both the A reads and the epilogue's writes on 64 distinct banks.
 // The body is one tile (classify_tile): K6's own kernel strides over the tiles of one model, K6e over the (member, tile) pairs of an
 // ensemble, so a row's probabilities are the same bits whichever launch computed them.
-template <int RB>
+// MAP (K6f): row i of the n rows of the launch is row p.row_map[i] of feat and of prob / value; the list is read only for i < n.
+template <int RB, bool MAP = false>
 __device__ __forceinline__ void classify_tile(const ClsParams& p, float* s_act, uint32_t tile, uint32_t n) {
     constexpr int TM = 16 * RB;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = CLS_THREADS / 64;
     const int S = p.S;
+    const auto at = [&](uint32_t i) -> size_t { if constexpr (MAP) return p.row_map[i]; else return i; };
     {
         const uint32_t row0 = tile * TM;
         float* in = s_act;
@@ -57,7 +60,7 @@ __device__ __forceinline__ void classify_tile(const ClsParams& p, float* s_act, 
             const int r = idx / p0, k = idx - r * p0;
             float v = 0.f;
             if (row0 + r < n && k < p.nin) {                                   // ml5 normalizeValue in double, then the f32 tensor
-                const double x = p.feat[(size_t)(row0 + r) * p.stride + k];
+                const double x = p.feat[at(row0 + r) * p.stride + k];
                 v = (float)((x - p.in_min[k]) / (p.in_max[k] - p.in_min[k]));
             }
             in[r * S + k] = v;
@@ -104,16 +107,17 @@ __device__ __forceinline__ void classify_tile(const ClsParams& p, float* s_act, 
         for (int r = tid; r < TM; r += CLS_THREADS) {
             if (row0 + r >= n) continue;
             const float* x = in + r * S;
-            if (p.nan_slot >= 0 && p.feat[(size_t)(row0 + r) * p.stride + p.nan_slot] != 0.0) {   // no coefficients: nothing to predict from
-                if (p.value) p.value[row0 + r] = __longlong_as_double(0x7ff8000000000000ll);
-                else for (int c = 0; c < p.C; c++) p.prob[(size_t)(row0 + r) * p.C + c] = __int_as_float(0x7fc00000);
+            const size_t row = at(row0 + r);
+            if (p.nan_slot >= 0 && p.feat[row * p.stride + p.nan_slot] != 0.0) {   // no coefficients: nothing to predict from
+                if (p.value) p.value[row] = __longlong_as_double(0x7ff8000000000000ll);
+                else for (int c = 0; c < p.C; c++) p.prob[row * p.C + c] = __int_as_float(0x7fc00000);
                 continue;
             }
             if (p.value) {                                                  // K6's regression epilogue: the one unit's output, un-normalised
-                p.value[row0 + r] = unnormalise_value(x[0], p.out_min, p.out_span);
+                p.value[row] = unnormalise_value(x[0], p.out_min, p.out_span);
                 continue;
             }
-            float* o = p.prob + (size_t)(row0 + r) * p.C;
+            float* o = p.prob + row * p.C;
             if (sm) {
                 float m = x[0];
                 for (int c = 1; c < p.C; c++) m = fmaxf(m, x[c]);
@@ -160,9 +164,65 @@ __global__ void __launch_bounds__(CLS_THREADS) classify_group_kernel(const ClsGr
     }
 }
 
+// ---- K6f: K6e with a row list per member (cross-validation, specification CV-1: member k is the model that did not see fold k, its list
+// fold k's rows).  Member d runs over tab[d].n rows, row i of them being row tab[d].p.row_map[i] of the dense table: the tile loads from
+// there and writes its probabilities or its value there, so the members fill disjoint rows of ONE table in place.  The work list, the order
+// (descending cost per tile), the members' own row-block factors and the LDS are K6e's; the counts are the host's (the lists are made
+// once), so a member with an empty list has no tile and the host launches nothing when every list is empty.
+__global__ void __launch_bounds__(CLS_THREADS) classify_folds_kernel(const ClsFoldEntry* __restrict__ tab, int n_members) {
+    extern __shared__ __attribute__((aligned(16))) float s_act[];
+    uint32_t total = 0;
+    for (int d = 0; d < n_members; d++) { const uint32_t tm = 16u * (uint32_t)tab[d].rb; total += (tab[d].n + tm - 1) / tm; }
+    for (uint32_t i = blockIdx.x; i < total; i += gridDim.x) {
+        int d = 0; uint32_t tile = i;
+        for (; d < n_members - 1; d++) {
+            const uint32_t tm = 16u * (uint32_t)tab[d].rb, t = (tab[d].n + tm - 1) / tm;
+            if (tile < t) break;
+            tile -= t;
+        }
+        const ClsFoldEntry& e = tab[d];
+        if (e.rb == 4) classify_tile<4, true>(e.p, s_act, tile, e.n);
+        else if (e.rb == 2) classify_tile<2, true>(e.p, s_act, tile, e.n);
+        else classify_tile<1, true>(e.p, s_act, tile, e.n);
+    }
+}
+
 }  // namespace
 
 namespace wsa_classify {
+
+uint64_t folds_table(const wsa_model* const* m, uint32_t n, const double* feat, const uint32_t* d_rows, const uint32_t* off, float* prob, double* value,
+                     const double* out_min, const double* out_max, ClsFoldEntry* tab, size_t* lds) {
+    std::vector<int> order(n);
+    std::vector<double> cost(n);
+    *lds = 0;
+    for (uint32_t k = 0; k < n; k++) {
+        order[k] = (int)k;
+        double w = 0.0;
+        for (int l = 0; l < m[k]->n_layers; l++) w += (double)m[k]->L[l].kp * m[k]->L[l].np;
+        cost[k] = w * 16.0 * m[k]->rb;                             // multiply-adds of one tile
+        const size_t need = (size_t)2 * 16 * m[k]->rb * m[k]->S * sizeof(float);
+        *lds = need > *lds ? need : *lds;
+    }
+    for (uint32_t i = 1; i < n; i++)                               // stable insertion sort, descending
+        for (uint32_t j = i; j > 0 && cost[order[j]] > cost[order[j - 1]]; j--) { const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
+    uint64_t tiles = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const int k = order[i];
+        ClsFoldEntry e{};
+        e.p = cls_params(m[k], feat, 0, nullptr, prob);
+        if (value) e.p = regress_params(e.p, value, out_min[k], out_max[k] - out_min[k]);
+        e.p.row_map = d_rows + off[k];
+        e.rb = m[k]->rb; e.n = off[k + 1] - off[k];
+        tab[i] = e;
+        tiles += fold_tiles(e.n, e.rb);
+    }
+    return tiles;
+}
+
+void launch_classify_folds(const wsa_ctx* ctx, const ClsFoldEntry* d_tab, uint32_t n_members, uint64_t tiles, size_t lds, hipStream_t s) {
+    hipLaunchKernelGGL(classify_folds_kernel, dim3(classify_grid(ctx, tiles)), dim3(CLS_THREADS), lds, s, d_tab, (int)n_members);
+}
 
 // V8 orders a key as an array index up to 2^32 - 2 ("4294967294"); "4294967295" and beyond are string keys
 bool array_index_key(const char* s, int64_t* out) {
@@ -279,6 +339,7 @@ wsa_status wsa_model_create(wsa_ctx* ctx, const wsa_model_desc* d, wsa_model** o
     }
     std::vector<int64_t> kr(m->C, -1);
     if (d->labels) for (int c = 0; c < m->C; c++) { int64_t v; if (array_index_key(d->labels[c], &v)) kr[c] = v; }
+    m->key_rank = kr;
     ok = ok && m->mem.alloc(&m->d_min, (size_t)nin) && m->mem.alloc(&m->d_max, (size_t)nin) && m->mem.upload(&m->d_key_rank, kr)
          && hipMemcpy(m->d_min, d->in_min, (size_t)nin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
          && hipMemcpy(m->d_max, d->in_max, (size_t)nin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;

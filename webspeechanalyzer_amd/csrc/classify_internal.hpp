@@ -19,8 +19,10 @@ struct ClsParams {
                                              // slot nan_slot is not 0 (level 12: uncmin threw) gets NaN in every output
     float* prob;
     double* value; double out_min, out_span;                                 // value != NULL: a regression model, one f64 per row instead of prob
+    const uint32_t* row_map;                 // K6f only: row i of the launch is row row_map[i] of feat and of prob / value (i < the list's length)
 };
 struct ClsGroupEntry { ClsParams p; int rb; };   // one member of K6e's work list, with its row-block factor
+struct ClsFoldEntry { ClsParams p; int rb; uint32_t n; };   // one member of K6f's work list: its row-block factor and the length of p.row_map
 
 // one member of an ensemble's fold (K6b-e), one wave per (clip, member) or (stream, member).  In a stream step the t_* tables are indexed
 // by callback, not by row
@@ -121,6 +123,15 @@ uint32_t group_table(const wsa_ensemble* e, const double* feat, const uint32_t* 
                      std::vector<ClsGroupEntry>& tab);
 // K6e over the uploaded table: every member's rows (their count on the device) in one launch
 void launch_classify_group(const ClsGroupEntry* d_tab, uint32_t n_members, const uint32_t* d_n_rows, uint32_t grid, size_t lds, hipStream_t s);
+// K6f's table in work-list order (descending multiply-adds per tile, a stable sort) for members m[0 .. n): member k runs over the n_k =
+// off[k + 1] - off[k] rows d_rows[off[k] ..] of feat and writes prob (value == NULL) or value at those rows, un-normalised with its own
+// out_min[k] / out_max[k]; tab holds n entries.  Returns the tile count of the launch (0: nothing to launch), *lds the dynamic LDS
+uint64_t folds_table(const wsa_model* const* m, uint32_t n, const double* feat, const uint32_t* d_rows, const uint32_t* off, float* prob, double* value,
+                     const double* out_min, const double* out_max, ClsFoldEntry* tab, size_t* lds);
+// K6f over the uploaded table; tiles > 0
+void launch_classify_folds(const wsa_ctx* ctx, const ClsFoldEntry* d_tab, uint32_t n_members, uint64_t tiles, size_t lds, hipStream_t s);
+// the tiles of a list of `rows` rows at row-block factor rb
+inline uint64_t fold_tiles(uint32_t rows, int rb) { return ((uint64_t)rows + 16u * (uint32_t)rb - 1) / (16u * (uint32_t)rb); }
 // what every regression entry point refuses (all WSA_ERR_INVALID); NULL when the model and the range will do
 const char* regress_refusal(const wsa_model* m, double out_min, double out_max);
 
@@ -198,6 +209,7 @@ struct wsa_model {
     wsa_classify::ClsLayer L[WSA_MODEL_MAX_LAYERS] = {};
     double *d_min = nullptr, *d_max = nullptr;
     int64_t* d_key_rank = nullptr;
+    std::vector<int64_t> key_rank;           // d_key_rank as the host made it
     bool softmax = false;
     wsa::DevArena mem;
 };

@@ -2,9 +2,13 @@
 // the device (struct wsa_dbstats), the parameter block of DS-1's two table passes, and the check of a head's index.
 #pragma once
 #include <string>
+#include <vector>
 #include "host_plan.hpp"
 #include "featdb_internal.hpp"
 #include "../../include/wsa_eval.h"
+#include "../../include/wsa_crossval.h"
+
+namespace wsa_classify { struct ClsFoldEntry; }            // classify_internal.hpp
 
 namespace wsa_dbstats_detail {
 
@@ -49,6 +53,19 @@ struct DsEval {
     int32_t* d_map = nullptr;                              // [WSA_MODEL_MAX_CLASSES] legend_to_vocab of the kept prediction
 };
 
+// the folds of a cross-validation (specification CV-1, wsa_dbstats_set_folds; crossval.hip): the rows of every fold, and K6f's table
+struct DsFolds {
+    uint32_t n_folds = 0;                                  // 0: not set
+    std::vector<uint32_t> off;                             // [n_folds + 1] offsets into d_rows
+    uint32_t* d_rows = nullptr;                            // the rows of fold 0 ascending, then fold 1's, ..: every row with a fold >= 0 once
+    wsa_classify::ClsFoldEntry *h_tab = nullptr, *d_tab = nullptr;   // [n_folds] pinned staging (copied from, not read in place) and the device table
+    hipEvent_t done = nullptr;                             // the last launch that read d_tab
+    DsFolds() = default;
+    DsFolds(const DsFolds&) = delete;
+    DsFolds& operator=(const DsFolds&) = delete;
+    ~DsFolds() { if (done) { (void)hipEventSynchronize(done); (void)hipEventDestroy(done); } }
+};
+
 }  // namespace wsa_dbstats_detail
 
 struct wsa_dbstats {
@@ -65,6 +82,7 @@ struct wsa_dbstats {
     wsa_dbstats_detail::DsTable tab{};
     wsa_dbstats_detail::DsEval eval{};
     wsa::DevArena mem;
+    wsa_dbstats_detail::DsFolds folds;                      // (after mem: it waits for its last launch before mem frees the table)
 };
 
 namespace wsa_dbstats_detail {

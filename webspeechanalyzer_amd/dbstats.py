@@ -396,59 +396,73 @@ def evaluate(an, db_rows, class_labels, ordinal_labels, models=None, per_file=Tr
     loaded = {name: _model_of(an, spec) for name, spec in models.items()}
     try:
         legends = {name: [js_str(x) for x in m.labels] for name, (m, _) in loaded.items() if any(name == c for c, _ in cats)}
-        col = build_columns(records, class_labels, ordinal_labels, legends)
-        if not col["cats"] and not col["ords"]:
-            empty = dict(table=dict(cats=[], ords=[]), confusion=[], agreement=[], lines=[])
-            return dict(rows=empty, files=None)
-        db = an.feature_db(feat, col["durations"], [len(c["vocab"]) for c in col["cats"]], len(col["ords"]),
-                           first_row=first_row if isinstance(feat, capi.FeatDB) else 0)
-        try:
-            for h, c in enumerate(col["cats"]):
-                db.set_classes(h, c["true_idx"], c["pred_idx"])
-            for o, c in enumerate(col["ords"]):
-                db.set_values(o, c["true_value"], c["pred_value"])
-            files = None
-            if per_file:
-                file_of_row, callback_of_row, names = file_columns(records)
-                if names:
-                    db.set_files(file_of_row, callback_of_row, len(names))
-                    t_cats, t_ords = file_truths(col, file_of_row, len(names))
-                    for h, t in enumerate(t_cats):
-                        db.set_file_classes(h, t)
-                    for o, t in enumerate(t_ords):
-                        db.set_file_values(o, t)
-                    files = dict(names=names, sums={}, classes={}, values={}, folded={c["name"]: c["name"] in loaded for c in col["cats"]})
-            for h, c in enumerate(col["cats"]):
-                if c["name"] not in loaded:
-                    continue
-                model = loaded[c["name"]][0]
-                legend = legends[c["name"]]
-                db.predict_classes(h, model, [c["vocab"].index(x) for x in legend], stream)
-                if files is not None:
-                    db.fold_files(h, stream)
-                    files["sums"][c["name"]] = db.file_sums(h, len(legend), stream)
-                    files["classes"][c["name"]] = [c["vocab"][i] if i >= 0 else None for i in db.file_classes(h, stream)]
-                for r, i in zip(records, db.pred_classes(h, stream)):
-                    update_pred_label(r, cats, ords, c["name"], c["vocab"][i] if i >= 0 else None)
-            for o, c in enumerate(col["ords"]):
-                if c["name"] in loaded:
-                    db.predict_values(o, loaded[c["name"]][0], None, None, stream)
-                    for r, v in zip(records, db.pred_values(o, stream)):
-                        update_pred_label(r, cats, ords, c["name"], float(v))
-                if files is not None:
-                    db.fold_file_values(o, stream)
-                    files["values"][c["name"]] = [float(v) for v in db.file_values(o, stream)]
-            n_cat = len(col["cats"])
-            rows = _level_result(col, *db.table(stream), [db.confusion(h, stream) for h in range(n_cat)], db.agreement(stream) if col["ords"] else None)
-            if files is not None:
-                files.update(_level_result(col, *db.file_table(stream), [db.file_confusion(h, stream) for h in range(n_cat)],
-                                           db.file_agreement(stream) if col["ords"] else None))
-        finally:
-            db.close()
+        predict_cat = {name: (lambda db, h, legend_to_vocab, m=loaded[name][0]: db.predict_classes(h, m, legend_to_vocab, stream)) for name in legends}
+        predict_ord = {name: (lambda db, o, m=loaded[name][0]: db.predict_values(o, m, None, None, stream)) for name in loaded if name in ords}
+        return evaluate_columns(an, records, feat, first_row, class_labels, ordinal_labels, legends, predict_cat, predict_ord, per_file, stream)
     finally:
         for m, mine in loaded.values():
             if mine:
                 m.close()
+
+
+def evaluate_columns(an, records, feat, first_row, class_labels, ordinal_labels, legends, predict_cat, predict_ord, per_file=True, stream=0,
+                     prepare=None):
+    """What evaluate does once it knows who predicts a head, shared with crossval.cross_validate: the columns, ONE device object, the
+    predictions, the per-file fold and both levels' results.  records: the rows evaluated; feat: their features (host array, a capi.FeatDB
+    whose rows first_row .. are theirs, or None); legends {categorical head: legend labels}; predict_cat {head: f(db, h, legend_to_vocab)}
+    and predict_ord {head: f(db, o)} enqueue a head's prediction on the capi.FeatureDBStats; prepare(db) runs once before them."""
+    from . import capi
+    cats, ords = head_settings(class_labels, ordinal_labels)
+    col = build_columns(records, class_labels, ordinal_labels, legends)
+    if not col["cats"] and not col["ords"]:
+        empty = dict(table=dict(cats=[], ords=[]), confusion=[], agreement=[], lines=[])
+        return dict(rows=empty, files=None)
+    db = an.feature_db(feat, col["durations"], [len(c["vocab"]) for c in col["cats"]], len(col["ords"]),
+                       first_row=first_row if isinstance(feat, capi.FeatDB) else 0)
+    try:
+        for h, c in enumerate(col["cats"]):
+            db.set_classes(h, c["true_idx"], c["pred_idx"])
+        for o, c in enumerate(col["ords"]):
+            db.set_values(o, c["true_value"], c["pred_value"])
+        files = None
+        if per_file:
+            file_of_row, callback_of_row, names = file_columns(records)
+            if names:
+                db.set_files(file_of_row, callback_of_row, len(names))
+                t_cats, t_ords = file_truths(col, file_of_row, len(names))
+                for h, t in enumerate(t_cats):
+                    db.set_file_classes(h, t)
+                for o, t in enumerate(t_ords):
+                    db.set_file_values(o, t)
+                files = dict(names=names, sums={}, classes={}, values={}, folded={c["name"]: c["name"] in predict_cat for c in col["cats"]})
+        if prepare is not None:
+            prepare(db)
+        for h, c in enumerate(col["cats"]):
+            if c["name"] not in predict_cat:
+                continue
+            legend = legends[c["name"]]
+            predict_cat[c["name"]](db, h, [c["vocab"].index(x) for x in legend])
+            if files is not None:
+                db.fold_files(h, stream)
+                files["sums"][c["name"]] = db.file_sums(h, len(legend), stream)
+                files["classes"][c["name"]] = [c["vocab"][i] if i >= 0 else None for i in db.file_classes(h, stream)]
+            for r, i in zip(records, db.pred_classes(h, stream)):
+                update_pred_label(r, cats, ords, c["name"], c["vocab"][i] if i >= 0 else None)
+        for o, c in enumerate(col["ords"]):
+            if c["name"] in predict_ord:
+                predict_ord[c["name"]](db, o)
+                for r, v in zip(records, db.pred_values(o, stream)):
+                    update_pred_label(r, cats, ords, c["name"], float(v))
+            if files is not None:
+                db.fold_file_values(o, stream)
+                files["values"][c["name"]] = [float(v) for v in db.file_values(o, stream)]
+        n_cat = len(col["cats"])
+        rows = _level_result(col, *db.table(stream), [db.confusion(h, stream) for h in range(n_cat)], db.agreement(stream) if col["ords"] else None)
+        if files is not None:
+            files.update(_level_result(col, *db.file_table(stream), [db.file_confusion(h, stream) for h in range(n_cat)],
+                                       db.file_agreement(stream) if col["ords"] else None))
+    finally:
+        db.close()
     return dict(rows=rows, files=files)
 
 

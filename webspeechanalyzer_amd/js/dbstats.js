@@ -231,14 +231,20 @@ function levelResult(col, t) {
 // row, the samples' `pred` pairs written as predictDB does); the others are evaluated on the predictions the samples hold.  Returns
 // {rows: {table, confusion, agreement, lines}, files: null | the same over the files plus names, sums, classes, values, folded}: the structure
 // webspeechanalyzer_amd.dbstats.evaluate returns.
+// Cross-validation (specification CV-1, js/crossval.js): with o.foldOfRow (Int32Array [n], -1: never held out) and o.nFolds, a head's entry of
+// models may be an ARRAY of nFolds handles that share one legend — model k predicts the rows of fold k (K6f through the addon's dbEval), the rows
+// of no fold stay blank.
 function evaluateDB(device, featureDB, o) {
   o = o || {};
+  const K = o.foldOfRow ? o.nFolds | 0 : 0, first = (m) => (Array.isArray(m) ? m[0] : m), members = (m) => (Array.isArray(m) ? m : [m]);
   const samples = featureDB.samples(o.db), hd = heads(o.classLabels, o.ordinalLabels), models = o.models || {};
   if (!samples.length) throw 'evaluateDB: a feature DB has at least one row';
   for (const name of Object.keys(models))
     if (!hd.cats.some((c) => c.name === name) && hd.ords.indexOf(name) < 0) throw 'evaluateDB: models names the head ' + name + '; the settings have ' + hd.cats.map((c) => c.name).concat(hd.ords);
+  for (const name of Object.keys(models))
+    if (Array.isArray(models[name]) && (models[name].length !== K || !K)) throw 'evaluateDB: head ' + name + ' has ' + models[name].length + ' models for ' + K + ' folds (foldOfRow, nFolds)';
   const legends = {};
-  for (const c of hd.cats) if (models[c.name]) legends[c.name] = models[c.name].labels;
+  for (const c of hd.cats) if (models[c.name]) legends[c.name] = first(models[c.name]).labels;
   const col = columns(samples, o.classLabels, o.ordinalLabels, legends), n = col.n, nCat = col.labels.length, nOrd = col.ordNames.length;
   const empty = { table: { cats: [], ords: [] }, confusion: [], agreement: [], lines: [] };
   if (!nCat && !nOrd) return { rows: empty, files: null };
@@ -251,18 +257,24 @@ function evaluateDB(device, featureDB, o) {
       if (s.vector.length !== W) throw 'evaluateDB: row ' + r + ' has ' + s.vector.length + ' features, row 0 has ' + W;
       for (let k = 0; k < W; k++) spec.features[r * W + k] = Number(s.vector[k]);
     });
-    spec.catMaps = new Int32Array(nCat * 64).fill(-1); spec.ordRange = new Float64Array(nOrd * 2);
-    catHandles.forEach((m, h) => {
-      if (!m) return;
-      if (typeof m.spec.outMin === 'number') throw 'evaluateDB: head ' + col.names[h] + ' needs a classifier';
-      if (m.spec.units[0] !== W) throw 'evaluateDB: the model takes ' + m.spec.units[0] + ' inputs; the rows of the DB have ' + W + ' features';
-      m.labels.forEach((label, c) => { spec.catMaps[h * 64 + c] = col.labels[h].findIndex((e) => e == label); });
+    const per = K || 1;                                            // ranges per ordinal head: one per member of a fold-wise head
+    spec.catMaps = new Int32Array(nCat * 64).fill(-1); spec.ordRange = new Float64Array(nOrd * 2 * per);
+    if (K) { spec.foldOfRow = Int32Array.from(o.foldOfRow); spec.nFolds = K; }
+    catHandles.forEach((ms, h) => {
+      if (!ms) return;
+      for (const m of members(ms)) {
+        if (typeof m.spec.outMin === 'number') throw 'evaluateDB: head ' + col.names[h] + ' needs a classifier';
+        if (m.spec.units[0] !== W) throw 'evaluateDB: the model takes ' + m.spec.units[0] + ' inputs; the rows of the DB have ' + W + ' features';
+      }
+      first(ms).labels.forEach((label, c) => { spec.catMaps[h * 64 + c] = col.labels[h].findIndex((e) => e == label); });
     });
-    ordHandles.forEach((m, k) => {
-      if (!m) return;
-      if (typeof m.spec.outMin !== 'number') throw 'evaluateDB: head ' + col.ordNames[k] + ' needs a regression model';
-      if (m.spec.units[0] !== W) throw 'evaluateDB: the model takes ' + m.spec.units[0] + ' inputs; the rows of the DB have ' + W + ' features';
-      spec.ordRange[k * 2] = m.spec.outMin; spec.ordRange[k * 2 + 1] = m.spec.outMax;
+    ordHandles.forEach((ms, k) => {
+      if (!ms) return;
+      members(ms).forEach((m, f) => {
+        if (typeof m.spec.outMin !== 'number') throw 'evaluateDB: head ' + col.ordNames[k] + ' needs a regression model';
+        if (m.spec.units[0] !== W) throw 'evaluateDB: the model takes ' + m.spec.units[0] + ' inputs; the rows of the DB have ' + W + ' features';
+        spec.ordRange[(k * per + f) * 2] = m.spec.outMin; spec.ordRange[(k * per + f) * 2 + 1] = m.spec.outMax;
+      });
     });
   }
   let fc = null;
@@ -283,7 +295,7 @@ function evaluateDB(device, featureDB, o) {
     col.names.forEach((name, h) => {
       files.folded[name] = !!catHandles[h];                        // a head without a model has no probabilities to fold: its files are blank
       if (!catHandles[h]) return;
-      const C = catHandles[h].labels.length, s = r.files.sums[h];
+      const C = first(catHandles[h]).labels.length, s = r.files.sums[h];
       files.sums[name] = Array.from({ length: nf }, (_, f) => Array.from(s.subarray(f * C, (f + 1) * C)));
       files.classes[name] = Array.from(r.files.idx.subarray(h * nf, (h + 1) * nf), (v) => (v >= 0 ? String(col.labels[h][v]) : null));
     });

@@ -341,6 +341,11 @@ function plan_train_model(o) {        // -> {spec, job, onEpoch}: what the addon
   const tm = require('./trainmodel.js');
   const opt = Object.assign({}, tm.DEFAULT_OPTIONS, o.options || {});
   const data = o.db ? device_db_data(o.db, tm.select(o.labels, o.classes), o.labels.length) : tm.prepare(o.features, o.labels, o.classes);
+  if (o.legend) {                       // a legend given from outside (crossValidate: the one legend of all folds), y re-indexed against it
+    const legend = o.legend.map(String), own = data.legend;
+    data.y = Int32Array.from(data.y, (j) => { const c = legend.indexOf(own[j]); if (c < 0) throw 'trainModel: the legend lacks the class ' + own[j]; return c; });
+    data.legend = legend;
+  }
   const st = tm.stack(opt.layers, data.legend.length, data.width), epochs = o.epochs === undefined ? 10 : o.epochs | 0, seed = o.seed | 0;
   const sp = tm.split(data.y.length, o.validationSplit);
   const init = o.init || tm.glorotInit(Array.from(st.units), seed);
@@ -456,7 +461,8 @@ function dbstats_device() {
         if (!m) { m = nat.modelCreate(ctx, handle.spec); handle.natives.set(ctx, m); }
         return m;
       };
-      return nat.dbEval(ctx, Object.assign({}, spec, { catModels: catHandles.map(native_of), ordModels: ordHandles.map(native_of) }));
+      const natives_of = (h) => (Array.isArray(h) ? h.map(native_of) : native_of(h));          // an array: the folds' models of a head (CV-1)
+      return nat.dbEval(ctx, Object.assign({}, spec, { catModels: catHandles.map(natives_of), ordModels: ordHandles.map(natives_of) }));
     },
   };
 }
@@ -477,6 +483,13 @@ function evaluateDB(featureDB, o) {
   for (const name of Object.keys(o.models || {})) models[name] = typeof o.models[name] === 'string' ? loadModel(o.models[name]) : o.models[name];
   o.models = models;
   return require('./dbstats.js').evaluateDB(dbstats_device(), featureDB, o);
+}
+// crossValidate(featureDB, {db, classLabels, ordinalLabels, heads: [names], k, groupOf, foldOfFile, options, epochs, batchSize, validationSplit, seed,
+// perFile, keepModels}) -> Promise of evaluateDB's {rows, files} plus folds, foldOfRow, foldOfFile (and models with keepModels): K-fold
+// cross-validation with a file's rows on one side of every split (specification CV-1, js/crossval.js; webspeechanalyzer_amd.crossval in Python).
+function crossValidate(featureDB, o) {
+  try { return require('./crossval.js').crossValidate({ trainModels, evaluate: (db, e) => require('./dbstats.js').evaluateDB(dbstats_device(), db, e) }, featureDB, o || {}); }
+  catch (e) { return Promise.reject(e); }
 }
 // ---- the app's ml5 KNN classifier (ref src/neuralmodel.js:729-837 train_knn; specification KN-1 / K9, include/wsa.h "KNN classifier"; js/knn.js).
 // KNNClassifier(width, capacity) -> ml5.KNNClassifier()'s addExample / classify / getCountByLabel on the device (classify is synchronous and
@@ -1402,5 +1415,5 @@ function set_predicted_label_for_segment(si, idx, label) {                      
 
 module.exports = { configure, LaunchAudioNodes, StopAudioNodes, set_predicted_label_for_segment, LaunchBatch, LaunchBatches,
   StreamOpen, decodePcm, STREAM_ACTIVE, STREAM_START, STREAM_STOP, shutdown, allocPinned, freePinned,
-  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, _clip_length: clip_length, _values_after: values_after, loadModel, setPredictionModel, setPredictionModels, setPredictionKnn, setPredictionValues, trainModel, trainModels, saveModel, trainRegression, predictValues, predictDB, statsTable, evaluateDB,
+  _settings: settings, _decode_wav: decode_wav, _clip_floats: clip_floats, _clip_length: clip_length, _values_after: values_after, loadModel, setPredictionModel, setPredictionModels, setPredictionKnn, setPredictionValues, trainModel, trainModels, saveModel, trainRegression, predictValues, predictDB, statsTable, evaluateDB, crossValidate,
   KNNClassifier, trainKnn, predictKnn, createDeviceDB, setCollectDB };

@@ -2,6 +2,7 @@
 // and the app's ml5 KNN classifier (knn*).  Every call is synchronous, on the context's own stream.
 #include "napi_handles.h"
 #include "../../include/wsa_eval.h"
+#include "../../include/wsa_crossval.h"
 
 // ---- predicting a labelled feature DB and the app's results table (wsa_dbstats_*, K8, specification DS-1): what the app's Predict button does over
 // the stored rows (ref src/neuralmodel.js:410-535 predict_db_nn, src/localstore.js:498-627 shows_stats_table).  The calls build the device object for
@@ -141,10 +142,14 @@ napi_value fn_db_table(napi_env env, napi_callback_info info) {
 //     mean_pred,
 //         var_true, var_pred, cov, ccc, pearson}, predIdx: Int32Array [nCat][n], predVal: Float64Array [nOrd][n] (after the predictions),
 // files: null | {cat, cls, ord, conf, agree, idx: Int32Array [nCat][nFiles], val: Float64Array [nOrd][nFiles], sums: [Float64Array [nFiles][C] | null]}}
+// Cross-validation (include/wsa_crossval.h, K6f, specification CV-1): with foldOfRow: Int32Array [n] (-1: never held out) and nFolds, a head's entry of
+// catModels / ordModels may be an ARRAY of nFolds model handles — model k predicts the rows of fold k, one launch per head — and ordRange is then
+// Float64Array [nOrd][nFolds][2], a range per member.  Without foldOfRow nothing changes.
 typedef struct {
     table_args a;
-    double *feat, *range, *ftv; int32_t *maps, *fo, *co, *fti; uint32_t width, n_files;
+    double *feat, *range, *ftv; int32_t *maps, *fo, *co, *fti, *fold; uint32_t width, n_files, n_folds;
     model_box *cm[WSA_DBSTATS_MAX_HEADS], *om[WSA_DBSTATS_MAX_HEADS];
+    model_box *cmf[WSA_DBSTATS_MAX_HEADS][WSA_CROSSVAL_MAX_FOLDS], *omf[WSA_DBSTATS_MAX_HEADS][WSA_CROSSVAL_MAX_FOLDS];   /* [h][0] set: the head is predicted fold-wise */
 } eval_args;
 static napi_value eval_alloc_failed(napi_env env) { return fail_error(env, "dbEval: result allocation failed"); }
 /* one level's tables into a new object: files = 0 the rows, 1 the files */
@@ -178,6 +183,18 @@ static model_box *eval_model(napi_env env, napi_value spec, const char *name, ui
     if (!mb || !child_is(&mb->link, box)) { *bad = 1; return NULL; }
     return mb;
 }
+/* the same element as an array of n_folds live models of this context into out[]: 1 when it is one, 0 when it is no array (or there are no folds) */
+static int eval_fold_models(napi_env env, napi_value spec, const char *name, uint32_t i, ctx_box *box, uint32_t n_folds, model_box **out, int *bad) {
+    napi_value arr, el, m; bool has = false, is = false; uint32_t len = 0, k = 0;
+    if (!n_folds || napi_has_named_property(env, spec, name, &has) != napi_ok || !has) return 0;
+    if (napi_get_named_property(env, spec, name, &arr) != napi_ok || !array_arg(env, arr, &len) || i >= len || napi_get_element(env, arr, i, &el) != napi_ok) return 0;
+    if (napi_is_array(env, el, &is) != napi_ok || !is) return 0;
+    if (napi_get_array_length(env, el, &len) != napi_ok || len != n_folds) { *bad = 1; return 1; }
+    for (; k < n_folds; k++) {
+        if (napi_get_element(env, el, k, &m) != napi_ok || !(out[k] = (model_box *)external_of(env, m)) || !child_is(&out[k]->link, box)) { *bad = 1; return 1; }
+    }
+    return 1;
+}
 /* dbEval's argument object: 1, or 0 with an exception pending */
 static int eval_read(napi_env env, napi_value o, ctx_box *box, const char *usage, eval_args *e) {
     size_t nfeat = 0, nmaps = 0, nrange = 0, nfo = 0, nco = 0, nfti = 0, nftv = 0; napi_value v;
@@ -197,11 +214,22 @@ static int eval_read(napi_env env, napi_value o, ctx_box *box, const char *usage
                            (void **)&e->ftv, &nftv) ||
                        nfo != a->n || nco != a->n || nfti != a->n_cat * e->n_files || nftv != a->n_ord * e->n_files)) { fail_usage(env, usage); return 0; }
     int bad = 0, any = 0;
-    for (size_t h = 0; h < a->n_cat; h++) e->cm[h] = eval_model(env, o, "catModels", (uint32_t)h, box, &bad);
-    for (size_t h = 0; h < a->n_ord; h++) e->om[h] = eval_model(env, o, "ordModels", (uint32_t)h, box, &bad);
-    if (bad) { fail_error(env, "dbEval: catModels / ordModels hold one model handle of this context, or null, per head"); return 0; }
-    for (size_t h = 0; h < WSA_DBSTATS_MAX_HEADS; h++) any |= e->cm[h] != NULL || e->om[h] != NULL;
-    if (any && (!with_feat || nmaps != a->n_cat * WSA_MODEL_MAX_CLASSES || nrange != a->n_ord * 2)) { fail_usage(env, usage); return 0; }
+    size_t nfold = 0;
+    if (typed_of(env, o, "foldOfRow", napi_int32_array, (void **)&e->fold, &nfold)) {
+        if (napi_get_named_property(env, o, "nFolds", &v) == napi_ok) (void)napi_get_value_uint32(env, v, &e->n_folds);
+        if (nfold != a->n || e->n_folds < 2 || e->n_folds > WSA_CROSSVAL_MAX_FOLDS) { fail_error(env, "dbEval: foldOfRow is an Int32Array [n] and comes with nFolds 2 .. 32"); return 0; }
+    } else e->fold = NULL;
+    for (size_t h = 0; h < a->n_cat; h++)
+        if (!eval_fold_models(env, o, "catModels", (uint32_t)h, box, e->n_folds, e->cmf[h], &bad)) e->cm[h] = eval_model(env, o, "catModels", (uint32_t)h, box, &bad);
+    for (size_t h = 0; h < a->n_ord; h++)
+        if (!eval_fold_models(env, o, "ordModels", (uint32_t)h, box, e->n_folds, e->omf[h], &bad)) e->om[h] = eval_model(env, o, "ordModels", (uint32_t)h, box, &bad);
+    if (bad) {
+        fail_error(env, e->n_folds ? "dbEval: catModels / ordModels hold one model handle of this context, an array of nFolds of them, or null, per head"
+                                   : "dbEval: catModels / ordModels hold one model handle of this context, or null, per head");
+        return 0;
+    }
+    for (size_t h = 0; h < WSA_DBSTATS_MAX_HEADS; h++) any |= e->cm[h] != NULL || e->om[h] != NULL || e->cmf[h][0] != NULL || e->omf[h][0] != NULL;
+    if (any && (!with_feat || nmaps != a->n_cat * WSA_MODEL_MAX_CLASSES || nrange != a->n_ord * 2 * (e->n_folds ? e->n_folds : 1))) { fail_usage(env, usage); return 0; }
     return 1;
 }
 /* the device object with every label, prediction and file table set */
@@ -213,25 +241,34 @@ static wsa_status eval_create(ctx_box *box, const eval_args *e, wsa_dbstats **db
     if (st == WSA_OK && nf) st = wsa_dbstats_set_files(*db, e->fo, e->co, nf);
     for (size_t h = 0; st == WSA_OK && nf && h < a->n_cat; h++) st = wsa_dbstats_set_file_classes(*db, (uint32_t)h, e->fti + h * nf);
     for (size_t o = 0; st == WSA_OK && nf && o < a->n_ord; o++) st = wsa_dbstats_set_file_values(*db, (uint32_t)o, e->ftv + o * nf);
+    if (st == WSA_OK && e->fold && e->feat) st = wsa_dbstats_set_folds(*db, e->fold, e->n_folds);
     return st;
 }
 // the heads that have a model predicted and folded per file (a head is folded right after its prediction: the fold reads the probabilities that call
 // kept), sums[h] set to the head's file sums or null; then every head's predictions into idx / val
 static wsa_status eval_predict(napi_env env, ctx_box *box, wsa_dbstats *db, const eval_args *e, napi_value sums, double *fs, int32_t *idx, double *val) {
-    const table_args *a = &e->a; const uint32_t nf = e->n_files;
+    const table_args *a = &e->a; const uint32_t nf = e->n_files, K = e->n_folds, per = K ? K : 1;     /* per: ranges per ordinal head */
+    const wsa_model *members[WSA_CROSSVAL_MAX_FOLDS]; double lo[WSA_CROSSVAL_MAX_FOLDS], hi[WSA_CROSSVAL_MAX_FOLDS];
     wsa_status st = WSA_OK;
     for (size_t h = 0; st == WSA_OK && h < a->n_cat; h++) {
         napi_value s_h = NULL;
-        if (e->cm[h]) {
-            st = wsa_dbstats_predict_classes(db, (uint32_t)h, model_of(e->cm[h]), e->maps + h * WSA_MODEL_MAX_CLASSES, box->queue);
+        const model_box *first = e->cmf[h][0] ? e->cmf[h][0] : e->cm[h];
+        if (first) {
+            if (e->cmf[h][0]) {
+                for (uint32_t k = 0; k < K; k++) members[k] = model_of(e->cmf[h][k]);
+                st = wsa_dbstats_predict_classes_folds(db, (uint32_t)h, members, K, e->maps + h * WSA_MODEL_MAX_CLASSES, box->queue);
+            } else st = wsa_dbstats_predict_classes(db, (uint32_t)h, model_of(e->cm[h]), e->maps + h * WSA_MODEL_MAX_CLASSES, box->queue);
             if (st == WSA_OK && nf) st = wsa_dbstats_fold_files(db, (uint32_t)h, box->queue);
-            if (st == WSA_OK && nf) st = wsa_dbstats_copy_file_sums(db, (uint32_t)h, box->queue, fs, e->cm[h]->n_classes);
-            if (st == WSA_OK && nf) s_h = make_typed(env, napi_float64_array, fs, (size_t)nf * e->cm[h]->n_classes);
+            if (st == WSA_OK && nf) st = wsa_dbstats_copy_file_sums(db, (uint32_t)h, box->queue, fs, first->n_classes);
+            if (st == WSA_OK && nf) s_h = make_typed(env, napi_float64_array, fs, (size_t)nf * first->n_classes);
         }
         if (st == WSA_OK && nf) { if (!s_h) napi_get_null(env, &s_h); napi_set_element(env, sums, (uint32_t)h, s_h); }
     }
     for (size_t o = 0; st == WSA_OK && o < a->n_ord; o++) {
-        if (e->om[o]) st = wsa_dbstats_predict_values(db, (uint32_t)o, model_of(e->om[o]), e->range[o * 2], e->range[o * 2 + 1], box->queue);
+        if (e->omf[o][0]) {
+            for (uint32_t k = 0; k < K; k++) { members[k] = model_of(e->omf[o][k]); lo[k] = e->range[(o * K + k) * 2]; hi[k] = e->range[(o * K + k) * 2 + 1]; }
+            st = wsa_dbstats_predict_values_folds(db, (uint32_t)o, members, K, lo, hi, box->queue);
+        } else if (e->om[o]) st = wsa_dbstats_predict_values(db, (uint32_t)o, model_of(e->om[o]), e->range[o * per * 2], e->range[o * per * 2 + 1], box->queue);
         if (st == WSA_OK && nf) st = wsa_dbstats_fold_file_values(db, (uint32_t)o, box->queue);
     }
     for (size_t h = 0; st == WSA_OK && h < a->n_cat; h++) st = wsa_dbstats_copy_classes(db, (uint32_t)h, box->queue, idx + h * a->n);

@@ -47,7 +47,7 @@
 // napi_db.c — stored rows
 //   dbPredict(ctx, model, features, ords, outMin, outMax) -> Int32Array | Float64Array
 //   dbTable(ctx, tables) -> {cat, cls, ord}
-//   dbEval(ctx, tables) -> {rows, predIdx, predVal, files}
+//   dbEval(ctx, tables) -> {rows, predIdx, predVal, files}          (with foldOfRow / nFolds: a head's models may be an array, one per fold)
 //   featdbCreate(ctx, width, capacity) -> db
 //   featdbDestroy(db)
 //   featdbCount(db) -> number
